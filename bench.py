@@ -16,6 +16,10 @@ barrier-bracketed timing, max over ranks, value = streams * steps / time  ("scal
 `python bench.py --gpus N` with no launcher environment spawns the N ranks ITSELF (fresh child
 processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, started before the parent touches any GPU; the
 parent only forwards rank 0's JSON line); under `torch.distributed.run` (RANK already set) it is one of the ranks.
+
+A plain run sets up, warms up, times --steps decode steps and prints the JSON line.  --full adds the legs that run after
+the timed region: the two prefill legs and the host-CPU baseline.  --dump-outputs DIR writes what the timed call returned
+(the greedy tokens of every step, the logits of the last step) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -300,6 +304,23 @@ def prefill_leg(wrk, ctx, rt, model, batch, prompt, chunk, repeats=5, warmups=2,
             "protocol": "examples/bench.rs: random prompt, token_chunk_size chunks, wall clock incl. logits read-back of the last row"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(path, arrays, budget):
+    """--dump-outputs: every array as <path>/<name>.npy.  An array over its share of `budget` bytes is cut to a fixed, seeded
+    sample of its flattened elements; their indices go beside it as <name>_index.npy (so sample and index together fit the share)."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // len(arrays)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            keep = share // (a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -377,8 +398,12 @@ def main():
     ap.add_argument("--batch", type=int, default=1, help="independent streams per GPU")
     ap.add_argument("--mode", type=int, default=1, help="1 = fused decode kernels, 0 = one kernel per reference op")
     ap.add_argument("--groups", type=int, default=1, help="deal the --batch streams of a GPU over this many concurrent decode pipelines (RWKV-7; 1 = one batched step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prefill", action="store_true", help="skip the prefill legs (pp512 of the reference's protocol, and 32 x 128 stacked tokens)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed decode, also run the prefill legs and the host-CPU baseline (one GPU); a plain run times the decode only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed call returned (greedy tokens of every step, logits of the last step) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host-CPU baseline")
+    ap.add_argument("--no-prefill", action="store_true", help="with --full: skip the prefill legs (pp512 of the reference's protocol, and 32 x 128 stacked tokens)")
     ap.add_argument("--quant", default="", help="ModelBuilder::quant map, e.g. int8:0-29,nf4:30-60 (layers inclusive)")
     ap.add_argument("--mixed", action="store_true", help="llama.cpp Q4_K_M tensor mix: Q6_K for attn value / ffn value in about half of the layers")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -391,6 +416,8 @@ def main():
     ap.add_argument("--rendezvous-timeout", type=float, default=120.0, help="seconds a rank waits for the others in init_process_group / the barriers")
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help="TEST ONLY: with --stub-device this rank exits with code 3 before the rendezvous")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_replicas(args.gpus, sys.argv[1:]))
@@ -483,12 +510,16 @@ def main():
         runtime.generate_greedy(first, args.warmup, mode=args.mode, groups=args.groups)
     barrier()
     w0 = time.perf_counter()
-    toks, dev_ms = runtime.generate_greedy(first, args.steps, mode=args.mode, groups=args.groups)     # HIP events on the ctx stream
+    # HIP events on the ctx stream; the last step's logits are copied back after the closing event
+    toks, dev_ms, *last = runtime.generate_greedy(first, args.steps, mode=args.mode, groups=args.groups, want_logits=bool(args.dump_outputs))
     ctx.sync()
     wall_ms = (time.perf_counter() - w0) * 1e3
     barrier()
     ms = group.max_over_ranks(max(dev_ms, 0.0))
     wall_ms = group.max_over_ranks(wall_ms)
+    if args.dump_outputs:
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"tokens" + sfx: toks.astype(np.float64), "logits" + sfx: last[0]}, DUMP_BUDGET_BYTES // world)
 
     if rank == 0:
         ms_per_step = ms / args.steps
@@ -515,8 +546,8 @@ def main():
             "wall_ms_per_step_incl_host": round(wall_ms / args.steps, 5), "load_seconds": round(load_s, 1),
         }
         # the reference's bench is pp512 + tg128 (examples/bench.rs:33,94-97): the decode above is the tg leg (headline metric); the prefill
-        # legs ride in the same line.  RWKV-7 models, one GPU, after the timed region.
-        if world == 1 and not args.no_prefill and args.model in CONFIGS:
+        # legs ride in the same line.  RWKV-7 models, one GPU, after the timed region, with --full.
+        if args.full and world == 1 and not args.no_prefill and args.model in CONFIGS:
             try:
                 out["prefill"] = prefill_leg(wrk, ctx, runtime, args.model, 1, 512, 128, mode=args.mode)
                 runtime.close()
@@ -526,7 +557,7 @@ def main():
                 runtime = None
             except Exception as e:      # a failing extra leg must not take the headline line with it
                 out["prefill"] = out.get("prefill") or {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(gg, first[0]) if args.model not in CONFIGS_V6 else None     # the C port is RWKV-7 only
         else:
             out["cpu_baseline"] = None

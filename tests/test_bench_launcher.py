@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -80,3 +82,42 @@ def test_stream_partition_of_cfg4():
         assert len(set(first)) == 16
         seen += mine
     assert sorted(seen) == list(range(128))
+
+
+def test_full_is_an_option_of_every_run():
+    # the extra legs (prefill, host-CPU baseline) sit behind --full; the stub line is the same with or without it
+    out = run("--gpus", "1", "--steps", "7", "--warmup", "0", "--stub-device", "--full")
+    assert out["steps"] == 7 and out["n_gpus"] == 1 and "ms_per_step" in out
+
+
+def test_dump_outputs_stays_within_its_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    small = np.arange(12, dtype=np.float64).reshape(3, 4)
+    big = np.random.default_rng(1).standard_normal((64, 4096)).astype(np.float32)       # 1 MiB
+    budget = 256 << 10
+    bench.dump_outputs(str(tmp_path), {"small": small, "big": big}, budget)
+    assert np.array_equal(np.load(tmp_path / "small.npy"), small)
+    sample, idx = np.load(tmp_path / "big.npy"), np.load(tmp_path / "big_index.npy")
+    assert sample.dtype == np.float32 and idx.dtype == np.float64
+    assert np.array_equal(sample, big.reshape(-1)[idx.astype(np.int64)])
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= budget + 4 * 128          # + the .npy headers
+    bench.dump_outputs(str(tmp_path / "again"), {"small": small, "big": big}, budget)         # the sample is fixed
+    assert np.array_equal(np.load(tmp_path / "again" / "big_index.npy"), idx)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_timed_decode(tmp_path):
+    # --steps sets the timed steps; two runs with the same arguments return the same tokens and last-step logits
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        line = run("--model", "tiny", "--steps", "12", "--warmup", "3", "--dump-outputs", str(tmp_path / d))
+        assert line["steps"] == 12 and line["ms_per_step"] > 0 and "prefill" not in line
+        toks, logits = np.load(tmp_path / d / "tokens.npy"), np.load(tmp_path / d / "logits.npy")
+        assert toks.dtype == np.float64 and toks.shape == (12, 1)
+        assert logits.dtype == np.float32 and logits.shape == (1, 512)
+        assert int(toks[-1, 0]) == int(logits[0].argmax())          # the last step's token is the argmax of its logits
+        outs.append((toks, logits))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])

@@ -10,7 +10,7 @@ WRK_NO_GRAPH=1 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof_w -- py
 F=$(find $O/prof_f -name "*counter_collection.csv" | head -1); W=$(find $O/prof_w -name "*counter_collection.csv" | head -1)
 python3 $R/tools/pmc_summary.py $F $W 20 $O/r02_pmc_traffic.json; rm -rf $O/prof_f $O/prof_w
 cd $R
-python bench.py > $O/r02_bench_headline.json 2>/dev/null
+python bench.py --full > $O/r02_bench_headline.json 2>/dev/null
 python bench.py --mixed --no-cpu-baseline > $O/r02_q4km_mixed_bench.json 2>/dev/null
 python bench.py --model 2.9B --mixed --batch 32 --steps 64 --warmup 8 --no-cpu-baseline > $O/r02_cfg3_2p9b_batch32_decode_bench.json 2>/dev/null
 python bench.py --model v6-7B --no-cpu-baseline --steps 64 --warmup 8 > $O/r02_v6_7b_bench.json 2>/dev/null

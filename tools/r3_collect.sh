@@ -13,7 +13,7 @@ F=$(find $O/prof_f -name "*counter_collection.csv" | head -1); W=$(find $O/prof_
 python3 $R/tools/pmc_summary.py $F $W 20 $O/r03_pmc_traffic.json; rm -rf $O/prof_f $O/prof_w
 echo "[r3] pmc done"
 cd $R
-python bench.py > $O/r03_bench_headline.json 2>/dev/null
+python bench.py --full > $O/r03_bench_headline.json 2>/dev/null
 echo "[r3] headline done"
 WRK_ENGINE=0 python bench.py $P > $O/r03_bench_launches_same_box.json 2>/dev/null
 python bench.py --mixed $P > $O/r03_q4km_mixed_bench.json 2>/dev/null
