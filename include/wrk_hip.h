@@ -315,6 +315,19 @@ int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* 
                                const uint32_t* first_tokens, uint32_t num_batch, uint32_t steps,
                                uint32_t* out_tokens, float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
 
+/* examples/chat.rs:150-190 Sampler::sample on the device, one token per row of f32 logits [num_rows][row_stride] (first num_vocab used):
+ * softmax, nucleus = the tokens (by probability descending, ties by index ascending) whose preceding mass is <= top_p, weights p^(1/T)
+ * inside it, then the first token whose cumulative weight reaches u * total, u = SplitMix64((seed << 32) | step) >> 40, times 2^-24.
+ * temperature or top_p == 0: the first index of the maximum (greedy); NaN or negative: WRK_E_ARG; num_vocab > 2^20: WRK_E_UNSUPPORTED.
+ * temperature / top_p / seed: host arrays of num_rows.  Blocking; out_tokens: host u32 [num_rows]. */
+int32_t wrk_sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                          const float* temperature, const float* top_p, const uint32_t* seed, uint32_t step, uint32_t* out_tokens);
+/* as wrk_v7_generate_greedy, the next token of sequence b drawn as wrk_sample_logits does with (temperature[b], top_p[b], seed[b]) at
+ * step t = 0..steps-1 of this call.  The parameters are uploaded per call: one cached step program serves any parameters. */
+int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
+                               uint32_t steps, const float* temperature, const float* top_p, const uint32_t* seed,
+                               uint32_t* out_tokens, float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
+
 /* ---------------------------------------------------------------- RWKV-6 (v6::Model, src/runtime/v6.rs)
  * Same chunk semantics, state layout ([D, S+2, B] per layer: v6.rs:150-214 == v7) and entry points as the V7
  * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph. */
@@ -356,6 +369,10 @@ int32_t wrk_v6_infer(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state,
                      const uint32_t* headers, uint32_t num_header, float* logits, uint32_t* argmax, uint32_t mode);
 int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state,
                                const uint32_t* first_tokens, uint32_t num_batch, uint32_t steps,
+                               uint32_t* out_tokens, float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
+/* as wrk_v7_generate_sample */
+int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
+                               uint32_t steps, const float* temperature, const float* top_p, const uint32_t* seed,
                                uint32_t* out_tokens, float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
 
 #ifdef __cplusplus

@@ -1,0 +1,90 @@
+"""Cost of on-device sampling in the decode loop: generate_greedy against generate_sample (T = 1, top_p = 0.9) on the bench's synthetic
+RWKV-7 1.5B Q4_K_M model, alternating the two, medians of the per-step time (HIP events around the replays).  Also prints, as context,
+what the host alternative would cost per step: reading the logits back and a NumPy restatement of chat.rs's sampler per row.
+
+    python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7]
+
+Prints one JSON object.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "web-rwkv-gguf_amd"))
+
+import bench  # noqa: E402  (the bench's model writer; bench.py itself is not changed)
+
+
+def chat_rs_sample(probs, top_p, temp, u):
+    """examples/chat.rs:150-190 in NumPy f32: sort, scan to top_p, p^(1/T), normalise, find_or_first."""
+    order = np.argsort(-probs, kind="stable")
+    sp = probs[order]
+    cum = np.cumsum(sp, dtype=np.float32)
+    n = int(np.count_nonzero((cum - sp) <= top_p))
+    w = sp[:n] ** np.float32(1.0 / temp)
+    c = np.cumsum(w / w.sum(), dtype=np.float32)
+    hit = np.flatnonzero(u <= c)
+    return int(order[hit[0] if hit.size else 0])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="1.5B")
+    ap.add_argument("--batches", default="1,16,32")
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-p", type=float, default=0.9)
+    args = ap.parse_args()
+    import wrk
+
+    batches = [int(b) for b in args.batches.split(",")]
+    ctx = wrk.Context(0)
+    rt = wrk.Runtime(ctx, wrk.GgufReader(bench.make_model_gguf(args.model, seed=42)), num_batch=max(batches))
+    V = rt.info.num_vocab
+    out = {"model": f"RWKV-7 {args.model} Q4_K_M (synthetic)", "temperature": args.temperature, "top_p": args.top_p, "steps": args.steps,
+           "reps": args.reps, "batches": []}
+    for B in batches:
+        first = [(17 + 101 * b) % (V - 1) for b in range(B)]
+        engine = rt.engine_status()[0] if B == 1 else False
+        rt.generate_greedy(first, 4)
+        rt.generate_sample(first, 4, temperature=args.temperature, top_p=args.top_p)
+        g, s = [], []
+        for _ in range(args.reps):
+            g.append(rt.generate_greedy(first, args.steps)[1] / args.steps)
+            s.append(rt.generate_sample(first, args.steps, temperature=args.temperature, top_p=args.top_p)[1] / args.steps)
+        gm, sm = float(np.median(g)), float(np.median(s))
+        # host alternative: logits back over PCIe + a CPU sort per row (what a caller of wrk_v7_infer has to do today)
+        _, _, logits = rt.generate_greedy(first, 1, want_logits=True)
+        buf = ctx.buffer(logits)
+        rd = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            buf.read(np.float32, B * V)
+            rd.append((time.perf_counter() - t0) * 1e3)
+        host = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            for b in range(B):
+                z = np.exp(logits[b] - logits[b].max())
+                chat_rs_sample((z / z.sum()).astype(np.float32), args.top_p, args.temperature, np.float32(0.5))
+            host.append((time.perf_counter() - t0) * 1e3)
+        out["batches"].append({
+            "batch": B, "decode_engine": bool(engine),
+            "greedy_ms_per_step": round(gm, 5), "sample_ms_per_step": round(sm, 5), "sample_minus_greedy_us": round((sm - gm) * 1e3, 2),
+            "greedy_ms_all": [round(x, 5) for x in g], "sample_ms_all": [round(x, 5) for x in s],
+            "host_alternative_ms_per_step": {"logits_readback": round(float(np.median(rd)), 4), "numpy_chat_rs_sampler": round(float(np.median(host)), 4)},
+        })
+    rt.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

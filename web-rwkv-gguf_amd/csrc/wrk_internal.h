@@ -171,6 +171,13 @@ void gather_rows_f16(hipStream_t s, const void* table, const uint32_t* ids, void
 void gather_rows_any(hipStream_t s, DTensor in, const uint32_t* rows, DTensor out, uint32_t n);
 void argmax_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t v_stride, uint32_t n, uint32_t* out);
 
+// wrk_sample.hip: examples/chat.rs:150-190 Sampler::sample per row (nucleus cut at top_p, temperature inside it, inverse-CDF draw with
+// the SplitMix64 uniform of (seed, *step)); temperature or top_p == 0 is argmax_rows.  -1: v == 0, v > SAMPLE_MAX_VOCAB or stride < v
+struct SampleParam { float temperature, top_p; uint32_t seed, pad; };
+static constexpr uint32_t SAMPLE_MAX_VOCAB = 1u << 20;
+int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
+                uint32_t* out);
+
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled
 void timing_report(wrk_ctx* ctx);
@@ -236,3 +243,7 @@ int repack_rows(uint32_t kind, uint32_t k, uint32_t m, const uint8_t* src, uint8
 size_t stored_bytes(uint32_t kind, uint32_t k, uint32_t m);
 
 }  // namespace wrk
+
+// validated per-sequence sampler parameters (WRK_E_ARG on NULL arrays or a NaN / negative temperature or top_p)
+int32_t wrk_sample_pack(wrk_ctx* ctx, const float* temperature, const float* top_p, const uint32_t* seed, uint32_t n,
+                        std::vector<wrk::SampleParam>& out);

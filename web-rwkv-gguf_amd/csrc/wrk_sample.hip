@@ -1,0 +1,285 @@
+// On-device nucleus sampling for gfx950: examples/chat.rs:150-190 `Sampler::sample` (softmax, top-p cut, temperature inside the
+// nucleus, inverse-CDF draw), one workgroup per row of f32 logits.  See DESIGN.md "Sampling on the device".
+//
+// Order: tokens by logit descending (== p descending), ties by index ascending.  That order is the 52-bit key
+// K = monotone(logit) << 20 | (2^20 - 1 - index), unique per token.  Both decisions -- the nucleus boundary and the drawn token --
+// are a weighted select over K, done as a radix descent with LDS histograms:
+//   pass 0      digit = distance below the row max, the row's finite range cut into 2048 bins (monotone in K), which spreads a row over
+//               many bins (the top bits of K are nearly constant over a row and would pile every token into a few bins);
+//   passes 1-5  digits = bits [41,52), [30,41), [19,30), [8,19), [0,8) of K, among the tokens left in the chosen bins;
+// each pass stops the descent as soon as the chosen bin holds one token.  Masses are fixed point (e * 2^40 in u64): every sum that
+// feeds a decision is an integer sum, so the result does not depend on the order the atomics land in.
+#include "wrk_device.h"
+
+namespace wrk {
+
+static constexpr uint32_t SAMPLE_BINS = 2048;
+static constexpr uint32_t SAMPLE_THREADS = 1024;
+static constexpr float SAMPLE_ONE = 1099511627776.0f;      // 2^40: mass of the row's top token
+
+__host__ __device__ inline uint64_t sample_splitmix(uint32_t seed, uint32_t step) {
+    uint64_t z = (((uint64_t)seed << 32) | step) + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ uint64_t rank_key(float l, uint32_t i) {
+    uint32_t b = __float_as_uint(l);
+    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((uint64_t)b << 20) | (0xFFFFFu - i);
+}
+
+// pass-0 digit, higher = earlier rank: (mx - l) * scale, monotone in l; l == mx also covers mx = +inf
+__device__ __forceinline__ uint32_t coarse_digit(float l, float mx, float scale) {
+    const float d = l == mx ? 0.0f : (mx - l) * scale;
+    return (SAMPLE_BINS - 1) - (uint32_t)fminf(d, (float)(SAMPLE_BINS - 1));
+}
+
+struct SampleSmem {
+    unsigned long long mass[SAMPLE_BINS];
+    uint32_t cnt[SAMPLE_BINS];
+    uint32_t idx[SAMPLE_BINS];
+    unsigned long long wsum[SAMPLE_THREADS / WAVE];
+    float wmax[SAMPLE_THREADS / WAVE], wmin[SAMPLE_THREADS / WAVE];
+    uint32_t widx[SAMPLE_THREADS / WAVE];
+    unsigned long long sel_above;
+    uint32_t sel, sel_cnt, sel_idx;
+};
+
+// exclusive prefix of v over the workgroup in thread order; *total = the sum (same value in every thread)
+__device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long v, SampleSmem& sm, unsigned long long* total) {
+    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned long long x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long t = __shfl_up(x, o, WAVE);
+        if (lane >= (uint32_t)o) x += t;
+    }
+    if (lane == 63) sm.wsum[wid] = x;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < SAMPLE_THREADS / WAVE; ++w) {
+        const unsigned long long s = sm.wsum[w];
+        if (w < wid) before += s;
+        all += s;
+    }
+    *total = all;
+    return before + x - v;
+}
+
+// One row per workgroup.  NPT > 0: the row (V <= 1024 * NPT) stays in registers; NPT == 0: every pass re-reads it from L2 (V <= 2^20;
+// a 64-per-thread register copy of a 65536-token row spills, the passes' own state needs ~95 VGPRs)
+template <int NPT>
+__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
+                                                                     const SampleParam* __restrict__ par, const uint32_t* __restrict__ step_word,
+                                                                     uint32_t* __restrict__ out) {
+    __shared__ SampleSmem sm;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const float* row = logits + (size_t)blockIdx.x * stride;
+    const int nj = NPT > 0 ? NPT : (int)((V + SAMPLE_THREADS - 1) / SAMPLE_THREADS);
+    auto load = [&](int j) -> float {
+        const uint32_t i = tid + SAMPLE_THREADS * (uint32_t)j;
+        const float x = i < V ? row[i] : -INFINITY;
+        return x != x ? -INFINITY : x + 0.0f;       // NaN counts as -inf (p = 0); -0 becomes +0 (ties by index, not by sign bit)
+    };
+    float lv[NPT > 0 ? NPT : 1];
+    if constexpr (NPT > 0) {
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) lv[j] = load(j);
+    }
+    // f(j, logit) over this thread's elements; from memory, 16 loads are issued ahead of their use (one at a time, every pass would pay the
+    // L2 latency 64 times over)
+    auto for_each = [&](auto&& f) {
+        if constexpr (NPT > 0) {
+#pragma unroll
+            for (int j = 0; j < NPT; ++j) f(j, lv[j]);
+        } else {
+            for (int j0 = 0; j0 < nj; j0 += 16) {
+                float c[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) c[u] = load(j0 + u);      // past the row: -inf, and i >= V for every test below
+#pragma unroll
+                for (int u = 0; u < 16; ++u) f(j0 + u, c[u]);
+            }
+        }
+    };
+
+    // row max and the first index holding it (argmax_rows' answer whenever the max exceeds -3e38)
+    float best = -INFINITY, low = INFINITY;        // low: the smallest logit above -inf
+    uint32_t bi = 0xffffffffu;
+    for_each([&](int j, float x) {
+        if (x > best) { best = x; bi = tid + SAMPLE_THREADS * (uint32_t)j; }
+        if (x > -INFINITY) low = fminf(low, x);
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, WAVE);
+        const uint32_t oi = __shfl_xor(bi, o, WAVE);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        low = fminf(low, __shfl_xor(low, o, WAVE));
+    }
+    if (lane == 0) { sm.wmax[wid] = best; sm.widx[wid] = bi; sm.wmin[wid] = low; }
+    __syncthreads();
+    best = sm.wmax[0]; bi = sm.widx[0]; low = sm.wmin[0];
+    for (uint32_t w = 1; w < SAMPLE_THREADS / WAVE; ++w) {
+        if (sm.wmax[w] > best || (sm.wmax[w] == best && sm.widx[w] < bi)) { best = sm.wmax[w]; bi = sm.widx[w]; }
+        low = fminf(low, sm.wmin[w]);
+    }
+    const float mx = best;
+    const uint32_t top = bi;
+    // pass-0 bins span the row's finite range, so that a row whose logits lie close together (a flat distribution) still spreads over the
+    // bins instead of piling into a few and serialising their atomics; the digit only has to be monotone in l
+    const float span = (mx - low) * (1.0f / (float)(SAMPLE_BINS - 1));
+    float scale = 1.0f / span;
+    if (!(scale > 0.0f) || !(scale < INFINITY)) scale = 64.0f;
+
+    const SampleParam pr = par[blockIdx.x];
+    const float temp = pr.temperature, top_p = pr.top_p;
+    if (!(temp > 0.0f) || !(top_p > 0.0f) || mx == -INFINITY) {       // greedy: bit-identical to argmax_rows
+        if (tid == 0) out[blockIdx.x] = mx > -3.0e38f ? top : 0u;
+        return;
+    }
+    const float inv_t = 1.0f / temp;
+
+    // Weighted select over K among the tokens with K >= kmin.  use_w = false: masses e = exp(l - mx); the LAST rank whose mass before
+    // it is <= P * sum (the nucleus boundary).  use_w = true: masses w = exp((l - mx) / T); the FIRST rank whose mass up to and
+    // including it is >= u * sum (the draw).  Returns the token index.
+    auto select = [&](bool use_w, uint64_t kmin) -> uint32_t {
+        uint32_t sel0 = 0;              // pass-0 bin
+        uint64_t prefix = 0;            // K bits [lo, 52) of the candidates (passes >= 2)
+        uint32_t lo = 52;
+        unsigned long long base = 0;    // mass of the candidates' predecessors
+        unsigned long long target = 0;
+        for (int p = 0; p < 6; ++p) {
+            const uint32_t width = p == 5 ? 8 : 11, shift = p == 5 ? 0 : 52 - 11 * p;    // passes >= 1: K bits [shift, shift + width)
+            for (uint32_t b = tid; b < SAMPLE_BINS; b += SAMPLE_THREADS) { sm.mass[b] = 0; sm.cnt[b] = 0; sm.idx[b] = 0; }
+            if (tid == 0) sm.sel = use_w ? 0u : 0xffffffffu;
+            if constexpr (NPT > 0) {
+                // keys are cheap to recompute; hoisted out of the pass loop they would take three more registers per element and spill
+#pragma unroll
+                for (int j = 0; j < NPT; ++j) asm volatile("" : "+v"(lv[j]));
+            }
+            __syncthreads();
+            for_each([&](int j, float l) {
+                const uint32_t i = tid + SAMPLE_THREADS * (uint32_t)j;
+                const uint64_t k = rank_key(l, i);
+                const uint32_t c = coarse_digit(l, mx, scale);
+                bool cand = i < V && k >= kmin;
+                if (p >= 1) cand = cand && c == sel0;
+                if (p >= 2) cand = cand && (k >> lo) == prefix;
+                if (cand) {
+                    const uint32_t d = p == 0 ? c : (uint32_t)(k >> shift) & ((1u << width) - 1u);
+                    const float e = l == mx ? 1.0f : expf(use_w ? (l - mx) * inv_t : l - mx);
+                    atomicAdd(&sm.mass[d], (unsigned long long)(e * SAMPLE_ONE));
+                    atomicAdd(&sm.cnt[d], 1u);
+                    atomicMax(&sm.idx[d], i);
+                }
+            });
+            __syncthreads();
+            // thread t owns bins dh = 2047 - 2t and dl = dh - 1: the exclusive scan in thread order is the mass of the higher bins
+            const uint32_t dh = SAMPLE_BINS - 1 - 2 * tid, dl = dh - 1;
+            const unsigned long long mh = sm.mass[dh], ml = sm.mass[dl];
+            unsigned long long total = 0;
+            const unsigned long long above_h = block_excl_scan(mh + ml, sm, &total), above_l = above_h + mh;
+            if (p == 0) {
+                if (!use_w) target = (unsigned long long)floor((double)top_p * (double)total);
+                else {          // ceil(u * W), u = U / 2^24, in 128-bit integer arithmetic
+                    const unsigned long long U = sample_splitmix(pr.seed, *step_word) >> 40;
+                    const unsigned long long plo = U * total, phi = __umul64hi(U, total);
+                    target = (phi << 40) | (plo >> 24);
+                    if (plo & 0xFFFFFFull) ++target;
+                }
+            }
+            if (!use_w) {
+                if (sm.cnt[dl] && base + above_l <= target) atomicMin(&sm.sel, dl);
+                else if (sm.cnt[dh] && base + above_h <= target) atomicMin(&sm.sel, dh);
+            } else {
+                if (sm.cnt[dh] && base + above_h + mh >= target) atomicMax(&sm.sel, dh + 1);
+                else if (sm.cnt[dl] && base + above_l + ml >= target) atomicMax(&sm.sel, dl + 1);
+            }
+            __syncthreads();
+            const uint32_t raw = sm.sel;
+            const bool none = use_w ? raw == 0 : raw == 0xffffffffu;
+            const uint32_t d = use_w ? raw - 1 : raw;
+            if (!none && (d == dh || d == dl)) {
+                sm.sel_above = d == dh ? above_h : above_l;
+                sm.sel_cnt = sm.cnt[d];
+                sm.sel_idx = sm.idx[d];
+            }
+            __syncthreads();
+            if (none) return top;       // nothing qualifies (cannot happen in integer arithmetic): rank 0, find_or_first
+            base += sm.sel_above;
+            const uint32_t n = sm.sel_cnt, ix = sm.sel_idx;
+            __syncthreads();            // sel / sel_* are rewritten by the next pass
+            if (n == 1 || p == 5) return ix;
+            if (p == 0) sel0 = d;
+            else { prefix = p == 1 ? d : (prefix << width) | d; lo = shift; }
+        }
+        return top;
+    };
+
+    uint64_t kmin = 0;              // P >= 1: every token is in the nucleus
+    if (!(top_p >= 1.0f)) {
+        const uint32_t r = select(false, 0);
+        const float lr = row[r];       // r < V: a token index
+        kmin = rank_key(lr != lr ? -INFINITY : lr + 0.0f, r);
+    }
+    const uint32_t tok = select(true, kmin);
+    if (tid == 0) out[blockIdx.x] = tok;
+}
+
+int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
+                uint32_t* out) {
+    if (n == 0) return 0;
+    if (v == 0 || v > SAMPLE_MAX_VOCAB || stride < v) return -1;
+    if (v <= 1024) sample_rows_kernel<1><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
+    else if (v <= 4096) sample_rows_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
+    else if (v <= 16384) sample_rows_kernel<16><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
+    else sample_rows_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
+    return 0;
+}
+
+}  // namespace wrk
+
+int32_t wrk_sample_pack(wrk_ctx* ctx, const float* temperature, const float* top_p, const uint32_t* seed, uint32_t n,
+                        std::vector<wrk::SampleParam>& out) {
+    WRK_ARG(ctx, temperature && top_p && seed, "temperature, top_p and seed arrays are required");
+    out.resize(n);
+    for (uint32_t b = 0; b < n; ++b) {
+        const float t = temperature[b], p = top_p[b];
+        WRK_ARG(ctx, !(t != t) && t >= 0.0f, "temperature[%u] = %g: must be >= 0", b, (double)t);
+        WRK_ARG(ctx, !(p != p) && p >= 0.0f, "top_p[%u] = %g: must be >= 0", b, (double)p);
+        out[b] = wrk::SampleParam{t, p, seed[b], 0u};
+    }
+    return WRK_OK;
+}
+
+extern "C" int32_t wrk_sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const float* temperature,
+                                     const float* top_p, const uint32_t* seed, uint32_t step, uint32_t* out_tokens) {
+    if (!ctx || !logits || !out_tokens) return WRK_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    std::vector<wrk::SampleParam> par;
+    int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, n, par);
+    if (rc != WRK_OK) return rc;
+    if (n == 0) return WRK_OK;
+    WRK_ARG(ctx, !ctx->capturing_here(), "wrk_sample_logits is blocking: not inside a capture");
+    WRK_ARG(ctx, V >= 1 && stride >= V, "num_vocab %u / row_stride %u", V, stride);
+    if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "num_vocab %u > %u", V, wrk::SAMPLE_MAX_VOCAB);
+    WRK_ARG(ctx, ((size_t)(n - 1) * stride + V) * 4 <= logits->bytes, "%u rows of stride %u exceed the buffer of %zu bytes", n, stride,
+            logits->bytes);
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t o_step = (size_t)n * sizeof(wrk::SampleParam), o_out = o_step + 256;
+    char* dev = nullptr;
+    WRK_HIP(ctx, hipMalloc((void**)&dev, o_out + (size_t)n * 4));
+    struct Free { char* p; ~Free() { hipFree(p); } } guard{dev};
+    WRK_HIP(ctx, hipMemcpyAsync(dev, par.data(), o_step, hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev + o_step, &step, 4, hipMemcpyHostToDevice, ctx->stream));
+    wrk::sample_rows(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, (const uint32_t*)(dev + o_step),
+                     (uint32_t*)(dev + o_out));
+    WRK_LAUNCH_CHECK(ctx);
+    WRK_HIP(ctx, hipMemcpyAsync(out_tokens, dev + o_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}

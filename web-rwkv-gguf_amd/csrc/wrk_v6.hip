@@ -26,6 +26,8 @@ struct wrk_v6_model {
     V6Scratch s{};
     uint32_t* history = nullptr;
     size_t history_cap = 0;
+    wrk::SampleParam* sample_par = nullptr;    // generate_sample's per-sequence parameters (written per call, read by the step program)
+    uint32_t sample_par_cap = 0;
     uint32_t wkv_nseq = 0;      // sequences of the job being enqueued (0: unknown): picks the WKV chunk kernel (wrk::time_mix_v6)
     std::map<std::tuple<const void*, uint32_t, uint32_t>, wrk_program*> graphs;      // (state, sequences, mode)
 
@@ -600,6 +602,7 @@ int32_t wrk_v6_model_destroy(wrk_v6_model* m) {
         m->drop_graphs();
         if (m->scratch) hipFree(m->scratch);
         if (m->history) hipFree(m->history);
+        if (m->sample_par) hipFree(m->sample_par);
     }
     for_each_handle(m, [](const wrk_buf* b) { if (b) wrk_buf_release(const_cast<wrk_buf*>(b)); },
                     [](const wrk_matrix* x) { if (x) wrk_matrix_release(const_cast<wrk_matrix*>(x)); });
@@ -685,9 +688,9 @@ int32_t wrk_v6_infer(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint
     return WRK_OK;
 }
 
-int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
-                               uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
-    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
+// par: sampler parameters of the B sequences (generate_sample), or nullptr (generate_greedy)
+static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                           const wrk::SampleParam* par, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
     LOCK(ctx);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
     WRK_ARG(ctx, m->d.emb_f16, "generate_greedy needs the device embedding table");
@@ -698,12 +701,22 @@ int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, 
     if (steps == 0) return WRK_OK;
     int32_t rc = m->ensure_scratch(B, B);
     if (rc == WRK_OK) rc = m->ensure_history((size_t)steps * B);
+    if (rc == WRK_OK && par && B > m->sample_par_cap) {      // outside capture; the programs holding the old pointer go with it
+        WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        m->drop_graphs();
+        if (m->sample_par) hipFree(m->sample_par);
+        m->sample_par = nullptr;
+        m->sample_par_cap = 0;
+        WRK_HIP(ctx, hipMalloc((void**)&m->sample_par, (size_t)B * sizeof(wrk::SampleParam)));
+        m->sample_par_cap = B;
+    }
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = b | (b << 8) | (1u << 24); hdr[b] = b; }
     rc = wrk_buf_write_raw(ctx, m->s.cursors, cur.data(), (size_t)B * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.headers, hdr.data(), (size_t)B * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.tokens, first_tokens, (size_t)B * 4);
+    if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, m->sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
     if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipMemsetAsync(m->s.counter, 0, 4, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -715,12 +728,14 @@ int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, 
         if (mode == 1) r = m->enqueue_fused_decode(st, B, B, true, 0);
         if (r == WRK_E_UNSUPPORTED) r = m->enqueue_ops(st, B, B, true);
         if (r != WRK_OK) return r;
-        wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->s.argmax);
+        if (!par) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->s.argmax);
+        else if (wrk::sample_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->sample_par, m->s.counter, m->s.argmax) != 0)
+            return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
         wrk::advance_tokens(ctx->op_stream(), m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
         return WRK_OK;
     };
     wrk_program* prog = nullptr;
-    const auto key = std::make_tuple(st->uid, B, mode);
+    const auto key = std::make_tuple(st->uid, B, mode | (par ? 32u : 0u));       // sampled steps never alias greedy ones
     if (!eager) {
         auto it = m->graphs.find(key);
         if (it != m->graphs.end()) prog = it->second;
@@ -755,6 +770,24 @@ int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, 
     if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits, m->s.head_o, (size_t)B * V * 4, hipMemcpyDeviceToHost, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
+}
+
+int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                               uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
+    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
+    return v6_generate(ctx, m, st, first_tokens, B, steps, nullptr, out_tokens, last_logits, elapsed_ms, mode);
+}
+
+int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                               const float* temperature, const float* top_p, const uint32_t* seed, uint32_t* out_tokens, float* last_logits,
+                               float* elapsed_ms, uint32_t mode) {
+    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
+    LOCK(ctx);
+    std::vector<wrk::SampleParam> par;
+    const int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, B >= 1, "num_batch 0");
+    return v6_generate(ctx, m, st, first_tokens, B, steps, par.data(), out_tokens, last_logits, elapsed_ms, mode);
 }
 
 }  // extern "C"

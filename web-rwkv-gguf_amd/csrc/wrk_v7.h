@@ -41,6 +41,8 @@ struct wrk_v7_model {
     V7Scratch s{};
     uint32_t* history = nullptr;    // generated tokens [steps][B] (device)
     size_t history_cap = 0;
+    wrk::SampleParam* sample_par = nullptr;    // generate_sample: per-sequence sampler parameters, written before every call (not baked
+    uint32_t sample_par_cap = 0;                // into the step programs, which read them through this pointer)
 
     // b: tokens (generate_greedy: sequences); mode: 0/1 for generate_greedy, or 16 + flag bits for wrk_v7_infer jobs
     // (the analogue of the reference's cached RnnJob per RnnInfo, runtime/mod.rs:110-209); nh: header rows
@@ -81,6 +83,7 @@ struct wrk_v7_model {
     bool engine_on() const;             // WRK_ENGINE != 0 and the engine exists
     int32_t ensure_scratch(uint32_t T, uint32_t NH);
     int32_t ensure_history(size_t n);
+    int32_t ensure_sample_params(uint32_t n);
     void drop_graphs();
     int32_t enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity_headers, bool merged = false);
     // from_tokens: gather embedding rows of s.tokens on the device; want_argmax: greedy token per header row into

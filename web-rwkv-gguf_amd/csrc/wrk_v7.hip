@@ -367,6 +367,7 @@ int32_t wrk_v7_model_destroy(wrk_v7_model* m) {
     for (wrk_v7_model* lane : m->lanes) wrk_v7_model_destroy(lane);
     m->lanes.clear();
     if (m->history) { LOCK(ctx); hipFree(m->history); m->history = nullptr; }
+    if (m->sample_par) { LOCK(ctx); hipFree(m->sample_par); m->sample_par = nullptr; }
     auto fb = [](const wrk_buf* b) { if (b) wrk_buf_release(const_cast<wrk_buf*>(b)); };
     auto fm = [](const wrk_matrix* x) { if (x) wrk_matrix_release(const_cast<wrk_matrix*>(x)); };
     fb(m->ln0_w); fb(m->ln0_b); fb(m->ln_out_w); fb(m->ln_out_b); fb(m->emb); fm(m->head);
@@ -685,41 +686,60 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
     return wrk_fail(ctx, WRK_E_ARG, "no frame buffer named %s", name);
 }
 
-// generate_greedy, part 1: frame, token / cursor upload and the (cached) decode-step program of sequences [b0, b0 + B) on model frame `m`
-static int32_t greedy_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t b0, uint32_t B,
-                              uint32_t steps, uint32_t mode, bool eager, wrk_program** prog_out) {
-    const uint32_t D = m->d.num_emb, V = m->d.num_vocab;
+// one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers, pick each sequence's next token -- the arg-max,
+// or with `sampled` the sampler (wrk_sample.hip) on the frame's per-sequence parameters at step *s.counter -- and advance
+// tokens / history / counter
+static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled) {
+    const uint32_t V = m->d.num_vocab;
+    hipStream_t q = ctx->op_stream();
+    int32_t rc;
+    if (mode == 1 && m->act_dtype == WRK_F16) rc = m->enqueue_fused_decode(st, B, B, true, true, !sampled, !sampled, b0, true);
+    else {
+        wrk::gather_rows_f16(q, m->emb->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
+        rc = m->enqueue_ops(st, B, B, true);
+        if (rc == WRK_OK && !sampled) {
+            wrk::argmax_rows(q, m->s.head_o, V, V, B, m->s.argmax);
+            wrk::advance_tokens(q, m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
+        }
+    }
+    if (rc != WRK_OK || !sampled) return rc;
+    // the sampler only reads the counter: rows run in different workgroups, so advance_tokens moves it after all of them
+    if (wrk::sample_rows(q, m->s.head_o, V, V, B, m->sample_par, m->s.counter, m->s.argmax) != 0)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    wrk::advance_tokens(q, m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
+    return WRK_OK;
+}
+
+// generate_greedy / generate_sample, part 1: frame, token / cursor / sampler-parameter upload and the (cached) decode-step program of
+// sequences [b0, b0 + B) on model frame `m`; par: the B sequences' sampler parameters, or nullptr for the arg-max
+static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t b0, uint32_t B,
+                              uint32_t steps, uint32_t mode, bool eager, const wrk::SampleParam* par, wrk_program** prog_out) {
     int32_t rc = m->ensure_scratch(B, B);
     if (rc != WRK_OK) return rc;
     if (B == 1 && mode == 1) { rc = m->ensure_engine(); if (rc != WRK_OK) return rc; }
     rc = m->ensure_history((size_t)steps * B);
+    if (rc == WRK_OK && par) rc = m->ensure_sample_params(B);
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
     rc = wrk_buf_write_raw(ctx, m->s.cursors, cur.data(), (size_t)B * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.headers, hdr.data(), (size_t)B * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.tokens, first_tokens, (size_t)B * 4);
+    if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, m->sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
     if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipMemsetAsync(m->s.counter, 0, 4, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *prog_out = nullptr;
     if (eager) return WRK_OK;
-    // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo
+    // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo; sampled
+    // steps have their own key bit, so greedy and sampled programs never alias
     const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
-                                                             (split_head_env_on() ? 0u : 16u)};
+                                                             (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u)};
     auto it = m->graphs.find(key);
     if (it != m->graphs.end()) { *prog_out = it->second; return WRK_OK; }
     rc = wrk_capture_begin(ctx);
     if (rc != WRK_OK) return rc;
-    if (mode == 1 && m->act_dtype == WRK_F16) rc = m->enqueue_fused_decode(st, B, B, true, true, true, true, b0, true);
-    else {
-        wrk::gather_rows_f16(ctx->op_stream(), m->emb->ptr, m->s.tokens, m->s.input, D, B);
-        rc = m->enqueue_ops(st, B, B, true);
-        if (rc == WRK_OK) {
-            wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->s.argmax);
-            wrk::advance_tokens(ctx->op_stream(), m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
-        }
-    }
+    rc = enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr);
     wrk_program* p = nullptr;
     const int32_t rc2 = wrk_capture_end(ctx, &p);
     if (rc != WRK_OK) { if (p) wrk_program_destroy(p); return rc; }
@@ -729,9 +749,10 @@ static int32_t greedy_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, c
     return WRK_OK;
 }
 
-int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
-                               uint32_t steps, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg) {
-    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
+// par: sampler parameters of the num_batch sequences (generate_sample), or nullptr (generate_greedy)
+static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
+                           uint32_t steps, const wrk::SampleParam* par, uint32_t* out_tokens, float* last_logits, float* elapsed_ms,
+                           uint32_t mode_arg) {
     LOCK(ctx);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
     WRK_ARG(ctx, m->emb, "generate_greedy needs the device embedding table");
@@ -776,7 +797,9 @@ int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, 
         L[g].mdl->engine_blocked = groups > 1;
         L[g].b0 = (uint32_t)((uint64_t)B * g / groups);
         L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
-        const int32_t rc = greedy_prepare(ctx, L[g].mdl, st, first_tokens + L[g].b0, L[g].b0, L[g].nb, steps, mode, eager, &L[g].prog);
+        // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
+        const int32_t rc = decode_prepare(ctx, L[g].mdl, st, first_tokens + L[g].b0, L[g].b0, L[g].nb, steps, mode, eager,
+                                          par ? par + L[g].b0 : nullptr, &L[g].prog);
         if (rc != WRK_OK) return rc;
     }
     // every early return below leaves through this guard: the timing events are destroyed and, after an error, the lane streams are
@@ -796,16 +819,7 @@ int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, 
     if (groups == 1) {
         for (uint32_t i = 0; i < steps; ++i) {
             if (eager) {
-                int32_t rc;
-                if (mode == 1 && m->act_dtype == WRK_F16) rc = m->enqueue_fused_decode(st, B, B, true, true, true, true, 0, true);
-                else {
-                    wrk::gather_rows_f16(ctx->op_stream(), m->emb->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
-                    rc = m->enqueue_ops(st, B, B, true);
-                    if (rc == WRK_OK) {
-                        wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->s.argmax);
-                        wrk::advance_tokens(ctx->op_stream(), m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
-                    }
-                }
+                const int32_t rc = enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr);
                 if (rc != WRK_OK) return rc;
             } else WRK_HIP(ctx, hipGraphLaunch(L[0].prog->exec, ctx->stream));
         }
@@ -845,6 +859,24 @@ int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, 
     return WRK_OK;
 }
 
+int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
+                               uint32_t steps, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg) {
+    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
+    return v7_generate(ctx, m, st, first_tokens, B, steps, nullptr, out_tokens, last_logits, elapsed_ms, mode_arg);
+}
+
+int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                               const float* temperature, const float* top_p, const uint32_t* seed, uint32_t* out_tokens, float* last_logits,
+                               float* elapsed_ms, uint32_t mode_arg) {
+    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
+    LOCK(ctx);
+    std::vector<wrk::SampleParam> par;
+    const int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, B >= 1, "num_batch 0");
+    return v7_generate(ctx, m, st, first_tokens, B, steps, par.data(), out_tokens, last_logits, elapsed_ms, mode_arg);
+}
+
 }  // extern "C"
 
 // Persistent decode engine: built once, outside captures.  WRK_ENGINE=0 keeps the five-launch layer (read per call, part of the
@@ -871,6 +903,17 @@ int32_t wrk_v7_model::ensure_history(size_t n) {
     history = nullptr;
     WRK_HIP(ctx, hipMalloc((void**)&history, n * 4 + 256));
     history_cap = n;
+    return WRK_OK;
+}
+
+int32_t wrk_v7_model::ensure_sample_params(uint32_t n) {
+    if (n <= sample_par_cap && sample_par) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drop_graphs();                  // captured sampled steps hold the old pointer
+    if (sample_par) hipFree(sample_par);
+    sample_par = nullptr;
+    WRK_HIP(ctx, hipMalloc((void**)&sample_par, (size_t)n * sizeof(wrk::SampleParam)));
+    sample_par_cap = n;
     return WRK_OK;
 }
 

@@ -137,6 +137,11 @@ HIP_SYMBOLS = {
     "wrk_v6_state_create": (C.c_int32, [_P, _P, C.c_uint32, C.POINTER(_P)]),
     "wrk_v6_infer": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _f32p, _u32p, C.c_uint32]),
     "wrk_v6_generate_greedy": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p, _f32p, C.c_uint32]),
+    "wrk_sample_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, C.c_uint32, _u32p]),
+    "wrk_v7_generate_sample": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _f32p, _f32p,
+                                           C.c_uint32]),
+    "wrk_v6_generate_sample": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _f32p, _f32p,
+                                           C.c_uint32]),
 }
 RT_SYMBOLS = {
     "wrk_host_last_error": (C.c_char_p, []),
@@ -185,6 +190,12 @@ def _u32(a) -> np.ndarray:
 
 def _ptr(a: np.ndarray, ty):
     return a.ctypes.data_as(ty)
+
+
+def _per_row(v, n: int, dtype) -> np.ndarray:
+    """A scalar broadcast to n entries, or a length-n array."""
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (n,)))
+    return a
 
 
 # ----------------------------------------------------------------------------- backend objects
@@ -242,6 +253,24 @@ class Context:
     def buffer(self, array: np.ndarray) -> "Buffer":
         a = np.ascontiguousarray(array)
         return Buffer(self, a.nbytes, a)
+
+    def sample_logits(self, logits, temperature=1.0, top_p=0.5, seed=0, step: int = 0, num_vocab: Optional[int] = None) -> np.ndarray:
+        """`Sampler::sample` (examples/chat.rs:150-190; defaults are its `--temp 1.0 --top-p 0.5`) on the device, one token per row.
+        `logits`: an [n, V] f32 array, or a `Buffer` of n rows of `num_vocab` f32; temperature / top_p / seed: scalars or per-row arrays.
+        Returns uint32 [n]."""
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            n = buf.nbytes // (4 * V)
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            n, V = a.shape
+            buf = self.buffer(a)
+        t, p, sd = _per_row(temperature, n, np.float32), _per_row(top_p, n, np.float32), _per_row(seed, n, np.uint32)
+        out = np.zeros(n, np.uint32)
+        self.check(hip.wrk_sample_logits(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p), step, _ptr(out, _u32p)))
+        return out
 
 
 class Program:
@@ -727,6 +756,23 @@ class Runtime:
         fn, mdl = (hip.wrk_v6_generate_greedy, self.model6) if self.model6 else (hip.wrk_v7_generate_greedy, self.model)
         self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, _ptr(out, _u32p),
                           _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
+        return (out, ms.value, logits) if want_logits else (out, ms.value)
+
+    def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
+                        groups: int = 1):
+        """As `generate_greedy`, each sequence's next token drawn by `Sampler::sample` (examples/chat.rs:150-190) on the device with its
+        own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b."""
+        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
+        ft = _u32(first_tokens)
+        B = ft.size
+        t, p = _per_row(temperature, B, np.float32), _per_row(top_p, B, np.float32)
+        sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
+        out = np.zeros((steps, B), np.uint32)
+        ms = C.c_float()
+        logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
+        fn, mdl = (hip.wrk_v6_generate_sample, self.model6) if self.model6 else (hip.wrk_v7_generate_sample, self.model)
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p),
+                          _ptr(out, _u32p), _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
 
     def state_back(self, batch: int) -> np.ndarray:
