@@ -328,6 +328,21 @@ int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* 
                                uint32_t steps, const float* temperature, const float* top_p, const uint32_t* seed,
                                uint32_t* out_tokens, float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
 
+/* Sequence scoring on the device, per row of f32 logits [num_rows][row_stride] (first num_vocab used) and its target token t:
+ *   logprob = x_t - (m + log sum_i exp(x_i - m)), m = the row max;   rank = #{i : x_i > x_t} + #{i < t : x_i == x_t}
+ * so rank == 0 exactly when t is the greedy token (the first index of the maximum).  A NaN anywhere in the row gives logprob NaN
+ * (rank unspecified); a target logit of -inf gives -inf.  targets: host u32 [num_rows], each < num_vocab (else WRK_E_ARG).
+ * Blocking; logprob: host f32 [num_rows], rank: host u32 [num_rows].  Same bits for the same (num_rows, num_vocab, row_stride). */
+int32_t wrk_score_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                         const uint32_t* targets, float* logprob, uint32_t* rank);
+/* as wrk_v7_infer, with the header rows scored instead of read back: header row h gets wrk_score_logits' (logprob[h], rank[h]) of
+ * target targets[h] (host u32 [num_header], each < num_vocab, required when num_header > 0).  The state advances exactly as
+ * wrk_v7_infer's on the same job; only num_header floats and u32 come back.  Targets are device data: one cached program per job shape
+ * serves any targets (score jobs never share a program with infer jobs).  Not inside a capture. */
+int32_t wrk_v7_score(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state,
+                     const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors, uint32_t num_token,
+                     const uint32_t* headers, uint32_t num_header, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode);
+
 /* ---------------------------------------------------------------- RWKV-6 (v6::Model, src/runtime/v6.rs)
  * Same chunk semantics, state layout ([D, S+2, B] per layer: v6.rs:150-214 == v7) and entry points as the V7
  * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph. */
@@ -374,6 +389,10 @@ int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* 
 int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
                                uint32_t steps, const float* temperature, const float* top_p, const uint32_t* seed,
                                uint32_t* out_tokens, float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
+/* as wrk_v7_score */
+int32_t wrk_v6_score(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state,
+                     const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors, uint32_t num_token,
+                     const uint32_t* headers, uint32_t num_header, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode);
 
 #ifdef __cplusplus
 }

@@ -130,6 +130,19 @@ wrk_v6_model* wrk_runtime_model_v6(wrk_runtime* rt);
  * Returns WRK_E_ARG with "input iterator exhausted" when nothing is left (RuntimeError::InputExhausted). */
 int32_t wrk_runtime_infer(wrk_runtime* rt, wrk_rnn_input* in, float* logits, size_t capacity_rows, uint32_t* rows, uint32_t mode);
 
+/* Scoring plan of the next chunk: lens = what wrk_rnn_iter_next returns for `in` (before wrk_rnn_input_step).  Position i < lens[b] of
+ * batch b is scored iff token i + 1 of b is still in `in` (this covers the chunk boundary: the target of a chunk's last position is
+ * the first token of the next chunk); its target is that token and its header its stacked row.  Rows go in batch order, then position;
+ * rows[b] = the count of batch b (a sequence's final token has no target).  The RnnOption of a batch is ignored.  headers / targets
+ * (capacity = sum lens) may be NULL to count only.  Pure host logic. */
+int32_t wrk_rnn_score_plan(const wrk_rnn_input* in, const uint32_t* lens, uint32_t* headers, uint32_t* targets, uint32_t* num_header,
+                           uint32_t* rows);
+/* The scoring analogue of wrk_runtime_infer: take the next chunk, plan it (wrk_rnn_score_plan), run wrk_v7_score / wrk_v6_score,
+ * then input.step().  logprob / rank receive the rows of every batch back to back; rows[b] = rows of batch b.  Errors as
+ * wrk_runtime_infer ("input iterator exhausted", more than 255 tokens of one batch in a chunk, capacity). */
+int32_t wrk_runtime_score(wrk_runtime* rt, wrk_rnn_input* in, float* logprob, uint32_t* rank, size_t capacity_rows, uint32_t* rows,
+                          uint32_t mode);
+
 #ifdef __cplusplus
 }
 #endif

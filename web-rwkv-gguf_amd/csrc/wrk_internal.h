@@ -178,6 +178,15 @@ static constexpr uint32_t SAMPLE_MAX_VOCAB = 1u << 20;
 int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
                 uint32_t* out);
 
+// wrk_score.hip: per row, logprob = x_t - logsumexp(x) and rank = #{x_i > x_t} + #{i < t : x_i == x_t} of the target t = targets[row]
+// (targets < v: the caller validates them).  Each row is split over score_slices(n, v, num_cu) workgroups; part holds n * that many
+// partials (at most n * SCORE_MAX_SLICES).  -1: v == 0 or stride < v
+struct ScorePart { float m, s; uint32_t gt, eq; };
+static constexpr uint32_t SCORE_MAX_SLICES = 32;
+uint32_t score_slices(uint32_t n, uint32_t v, int num_cu);
+int score_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const uint32_t* targets, ScorePart* part,
+               float* logprob, uint32_t* rank, int num_cu);
+
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled
 void timing_report(wrk_ctx* ctx);
@@ -247,3 +256,18 @@ size_t stored_bytes(uint32_t kind, uint32_t k, uint32_t m);
 // validated per-sequence sampler parameters (WRK_E_ARG on NULL arrays or a NaN / negative temperature or top_p)
 int32_t wrk_sample_pack(wrk_ctx* ctx, const float* temperature, const float* top_p, const uint32_t* seed, uint32_t n,
                         std::vector<wrk::SampleParam>& out);
+
+// device slots of a scoring job (wrk_score.hip): targets u32, logprob f32, rank u32 [cap] and the slice partials [cap][SCORE_MAX_SLICES];
+// ensure() reallocates (after a stream sync) when n > cap and then sets *grown: programs captured with the old pointers must go
+struct wrk_score_scratch {
+    void* buf = nullptr;
+    uint32_t cap = 0;
+    uint32_t* targets = nullptr;
+    float* logprob = nullptr;
+    uint32_t* rank = nullptr;
+    wrk::ScorePart* part = nullptr;
+    int32_t ensure(wrk_ctx* ctx, uint32_t n, bool* grown);
+    void release();
+};
+// WRK_E_ARG unless every target < V (targets may be NULL only when n == 0)
+int32_t wrk_score_check_targets(wrk_ctx* ctx, const uint32_t* targets, uint32_t n, uint32_t V);

@@ -28,6 +28,7 @@ struct wrk_v6_model {
     size_t history_cap = 0;
     wrk::SampleParam* sample_par = nullptr;    // generate_sample's per-sequence parameters (written per call, read by the step program)
     uint32_t sample_par_cap = 0;
+    wrk_score_scratch score;    // wrk_v6_score: targets / logprob / rank / slice partials of the header rows (read by no captured program)
     uint32_t wkv_nseq = 0;      // sequences of the job being enqueued (0: unknown): picks the WKV chunk kernel (wrk::time_mix_v6)
     std::map<std::tuple<const void*, uint32_t, uint32_t>, wrk_program*> graphs;      // (state, sequences, mode)
 
@@ -603,6 +604,7 @@ int32_t wrk_v6_model_destroy(wrk_v6_model* m) {
         if (m->scratch) hipFree(m->scratch);
         if (m->history) hipFree(m->history);
         if (m->sample_par) hipFree(m->sample_par);
+        m->score.release();
     }
     for_each_handle(m, [](const wrk_buf* b) { if (b) wrk_buf_release(const_cast<wrk_buf*>(b)); },
                     [](const wrk_matrix* x) { if (x) wrk_matrix_release(const_cast<wrk_matrix*>(x)); });
@@ -639,8 +641,10 @@ int32_t wrk_v6_state_create(wrk_ctx* ctx, const wrk_v6_model* model, uint32_t nu
     return WRK_OK;
 }
 
-int32_t wrk_v6_infer(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors,
-                     uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax, uint32_t mode) {
+// one RnnJob: wrk_v6_infer, or with `score` wrk_v6_score (the header rows' logits scored against targets instead of read back)
+static int32_t v6_job(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors,
+                      uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax, bool score, const uint32_t* targets,
+                      float* logprob, uint32_t* rank, uint32_t mode) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
@@ -661,8 +665,20 @@ int32_t wrk_v6_infer(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint
     }
     bool identity = (NH == T);
     for (uint32_t h = 0; h < NH; ++h) { WRK_ARG(ctx, headers[h] < T, "header %u out of range", h); if (headers[h] != h) identity = false; }
+    if (score) {
+        WRK_ARG(ctx, !ctx->capturing_here(), "wrk_v6_score is blocking: not inside a capture");
+        WRK_ARG(ctx, NH == 0 || (logprob && rank), "logprob and rank are required");
+        const int32_t rt = wrk_score_check_targets(ctx, targets, NH, V);
+        if (rt != WRK_OK) return rt;
+    }
     int32_t rc = m->ensure_scratch(T, NH ? NH : 1);
     if (rc != WRK_OK) return rc;
+    if (score && NH) {
+        bool grown = false;
+        rc = m->score.ensure(ctx, NH, &grown);
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->score.targets, targets, (size_t)NH * 4);
+        if (rc != WRK_OK) return rc;
+    }
     rc = wrk_buf_write_raw(ctx, m->s.cursors, cursors, (size_t)T * 4);
     if (rc == WRK_OK && NH) rc = wrk_buf_write_raw(ctx, m->s.headers, headers, (size_t)NH * 4);
     if (rc != WRK_OK) return rc;
@@ -680,12 +696,30 @@ int32_t wrk_v6_infer(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint
     if (rc == WRK_E_UNSUPPORTED) rc = m->enqueue_ops(st, T, NH, identity, mode == 1 && !one_token_each);
     if (rc != WRK_OK) return rc;
     if (NH && argmax) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->s.argmax);
+    if (NH && score &&
+        wrk::score_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->score.targets, m->score.part, m->score.logprob, m->score.rank,
+                        ctx->num_cu) != 0)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "score: vocabulary of %u tokens", V);
     WRK_LAUNCH_CHECK(ctx);
     if (ctx->capturing_here()) return WRK_OK;   // recorded into the caller's program: results exist after it has been launched
     if (NH && logits) WRK_HIP(ctx, hipMemcpyAsync(logits, m->s.head_o, (size_t)NH * V * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (NH && argmax) WRK_HIP(ctx, hipMemcpyAsync(argmax, m->s.argmax, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (NH && score) {
+        WRK_HIP(ctx, hipMemcpyAsync(logprob, m->score.logprob, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(rank, m->score.rank, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
+}
+
+int32_t wrk_v6_infer(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors,
+                     uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax, uint32_t mode) {
+    return v6_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, logits, argmax, false, nullptr, nullptr, nullptr, mode);
+}
+
+int32_t wrk_v6_score(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors,
+                     uint32_t T, const uint32_t* headers, uint32_t NH, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode) {
+    return v6_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank, mode);
 }
 
 // par: sampler parameters of the B sequences (generate_sample), or nullptr (generate_greedy)

@@ -43,6 +43,7 @@ struct wrk_v7_model {
     size_t history_cap = 0;
     wrk::SampleParam* sample_par = nullptr;    // generate_sample: per-sequence sampler parameters, written before every call (not baked
     uint32_t sample_par_cap = 0;                // into the step programs, which read them through this pointer)
+    wrk_score_scratch score;                    // wrk_v7_score: targets / logprob / rank / slice partials of the header rows
 
     // b: tokens (generate_greedy: sequences); mode: 0/1 for generate_greedy, or 16 + flag bits for wrk_v7_infer jobs
     // (the analogue of the reference's cached RnnJob per RnnInfo, runtime/mod.rs:110-209); nh: header rows

@@ -368,6 +368,7 @@ int32_t wrk_v7_model_destroy(wrk_v7_model* m) {
     m->lanes.clear();
     if (m->history) { LOCK(ctx); hipFree(m->history); m->history = nullptr; }
     if (m->sample_par) { LOCK(ctx); hipFree(m->sample_par); m->sample_par = nullptr; }
+    if (m->score.buf) { LOCK(ctx); m->score.release(); }
     auto fb = [](const wrk_buf* b) { if (b) wrk_buf_release(const_cast<wrk_buf*>(b)); };
     auto fm = [](const wrk_matrix* x) { if (x) wrk_matrix_release(const_cast<wrk_matrix*>(x)); };
     fb(m->ln0_w); fb(m->ln0_b); fb(m->ln_out_w); fb(m->ln_out_b); fb(m->emb); fm(m->head);
@@ -472,9 +473,10 @@ static int32_t state_d2d(wrk_ctx* ctx, const wrk_v7_state* st, uint32_t batch, c
 int32_t wrk_v7_state_read(wrk_ctx* ctx, const wrk_v7_state* st, uint32_t batch, wrk_buf* buf) { return state_d2d(ctx, st, batch, buf, false); }
 int32_t wrk_v7_state_write(wrk_ctx* ctx, wrk_v7_state* st, uint32_t batch, const wrk_buf* buf) { return state_d2d(ctx, st, batch, buf, true); }
 
-int32_t wrk_v7_infer(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows,
-                     const uint32_t* cursors, uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax,
-                     uint32_t mode) {
+// one RnnJob: wrk_v7_infer, or with `score` wrk_v7_score (the header rows' logits scored against targets instead of read back)
+static int32_t v7_job(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows,
+                      const uint32_t* cursors, uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax,
+                      bool score, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
@@ -509,9 +511,23 @@ int32_t wrk_v7_infer(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint
         WRK_ARG(ctx, headers[h] < T, "header %u: row %u >= %u tokens", h, headers[h], T);
         if (headers[h] != h) identity = false;
     }
+    if (score) {
+        WRK_ARG(ctx, !ctx->capturing_here(), "wrk_v7_score is blocking: not inside a capture");
+        WRK_ARG(ctx, NH == 0 || (logprob && rank), "logprob and rank are required");
+        const int32_t rt = wrk_score_check_targets(ctx, targets, NH, V);
+        if (rt != WRK_OK) return rt;
+    }
     int32_t rc = m->ensure_scratch(T, NH ? NH : 1);
     if (rc != WRK_OK) return rc;
     if (T == 1 && mode == 1) { rc = m->ensure_engine(); if (rc != WRK_OK) return rc; }
+    if (score && NH) {
+        bool grown = false;
+        rc = m->score.ensure(ctx, NH, &grown);
+        if (rc != WRK_OK) return rc;
+        if (grown) m->drop_graphs();            // captured score jobs hold the old slots
+        rc = wrk_buf_write_raw(ctx, m->score.targets, targets, (size_t)NH * 4);
+        if (rc != WRK_OK) return rc;
+    }
     rc = wrk_buf_write_raw(ctx, m->s.cursors, cursors, (size_t)T * 4);
     if (rc != WRK_OK) return rc;
     if (NH) { rc = wrk_buf_write_raw(ctx, m->s.headers, headers, (size_t)NH * 4); if (rc != WRK_OK) return rc; }
@@ -535,6 +551,11 @@ int32_t wrk_v7_infer(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint
             r = m->enqueue_ops(st, T, NH, identity, mode == 1);
             if (r == WRK_OK && NH && argmax) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->s.argmax);
         }
+        // scoring: the epilogue on head_o, which every path above materialises
+        if (r == WRK_OK && score && NH &&
+            wrk::score_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->score.targets, m->score.part, m->score.logprob, m->score.rank,
+                            ctx->num_cu) != 0)
+            r = wrk_fail(ctx, WRK_E_UNSUPPORTED, "score: vocabulary of %u tokens", V);
         return r;
     };
     static const bool no_graph = [] { const char* e = getenv("WRK_NO_GRAPH"); return e && e[0] == '1'; }();
@@ -544,7 +565,7 @@ int32_t wrk_v7_infer(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint
         const uint32_t flags = 16u | (m->act_dtype == WRK_F32 ? 64u : 0u) | (fused ? 1u : 0u) | (identity ? 2u : 0u) | (tokens ? 4u : 0u) | ((NH && argmax) ? 8u : 0u) |
                                ((!fused && mode == 1) ? 32u : 0u) | (fused ? (cursors[0] & 0xffu) << 8 : 0u) | ((fused && contiguous) ? 1u << 16 : 0u) |
                                ((fused && T == 1 && m->engine_on()) ? 1u << 17 : 0u) | (split_head_env_on() ? 0u : 1u << 18) |
-                               ((!fused && (size_t)nseq * m->d.num_head >= 768) ? 1u << 19 : 0u);
+                               ((!fused && (size_t)nseq * m->d.num_head >= 768) ? 1u << 19 : 0u) | (score ? 1u << 20 : 0u);
         const wrk_v7_model::GraphKey key{st->uid, T, flags, NH};
         wrk_program* prog = nullptr;
         auto it = m->graphs.find(key);
@@ -569,8 +590,24 @@ int32_t wrk_v7_infer(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint
     if (ctx->capturing_here()) return WRK_OK;   // recorded into the caller's program: results exist after it has been launched
     if (NH && logits) WRK_HIP(ctx, hipMemcpyAsync(logits, m->s.head_o, (size_t)NH * V * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (NH && argmax) WRK_HIP(ctx, hipMemcpyAsync(argmax, m->s.argmax, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (NH && score) {
+        WRK_HIP(ctx, hipMemcpyAsync(logprob, m->score.logprob, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(rank, m->score.rank, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return wrk_v7_engine_check(m->engine);
+}
+
+int32_t wrk_v7_infer(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows,
+                     const uint32_t* cursors, uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax,
+                     uint32_t mode) {
+    return v7_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, logits, argmax, false, nullptr, nullptr, nullptr, mode);
+}
+
+int32_t wrk_v7_score(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows,
+                     const uint32_t* cursors, uint32_t T, const uint32_t* headers, uint32_t NH, const uint32_t* targets, float* logprob,
+                     uint32_t* rank, uint32_t mode) {
+    return v7_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank, mode);
 }
 
 // Bundle::<F>::new (v7.rs:514-536): the activation type of the frame.  F16 is the reference's default build

@@ -1242,26 +1242,58 @@ wrk_v7_model* wrk_runtime_model(wrk_runtime* rt) { return rt ? rt->model : nullp
 wrk_v7_state* wrk_runtime_state(wrk_runtime* rt) { return rt ? rt->state : nullptr; }
 wrk_v6_model* wrk_runtime_model_v6(wrk_runtime* rt) { return rt ? rt->model6 : nullptr; }
 
-// SimpleRuntime::infer (mod.rs:238-263) with RnnJob::{load, submit, back} (v7.rs:434-492)
-int32_t wrk_runtime_infer(wrk_runtime* rt, wrk_rnn_input* in, float* logits, size_t capacity_rows, uint32_t* rows, uint32_t mode) {
-    if (!rt || !in || !rows) return fail(WRK_E_ARG, "null argument");
+// scoring rows of the chunk `lens` (see wrk_runtime.h)
+static void score_plan(const wrk_rnn_input& in, const uint32_t* lens, std::vector<uint32_t>& headers, std::vector<uint32_t>& targets,
+                       uint32_t* rows) {
+    headers.clear();
+    targets.clear();
+    uint32_t p_in = 0;
+    for (size_t b = 0; b < in.tokens.size(); ++b) {
+        const std::vector<uint32_t>& t = in.tokens[b];
+        uint32_t n = 0;
+        for (uint32_t i = 0; i < lens[b] && (size_t)i + 1 < t.size(); ++i, ++n) {
+            headers.push_back(p_in + i);
+            targets.push_back(t[i + 1]);
+        }
+        rows[b] = n;
+        p_in += lens[b];
+    }
+}
+
+int32_t wrk_rnn_score_plan(const wrk_rnn_input* in, const uint32_t* lens, uint32_t* headers, uint32_t* targets, uint32_t* num_header,
+                           uint32_t* rows) {
+    if (!in || !lens || !num_header || !rows) return fail(WRK_E_ARG, "null argument");
+    for (size_t b = 0; b < in->tokens.size(); ++b)
+        if (lens[b] > in->tokens[b].size()) return fail(WRK_E_ARG, "batch %zu: chunk of %u tokens, %zu remain", b, lens[b], in->tokens[b].size());
+    std::vector<uint32_t> h, t;
+    score_plan(*in, lens, h, t, rows);
+    *num_header = (uint32_t)h.size();
+    if (headers) memcpy(headers, h.data(), h.size() * 4);
+    if (targets) memcpy(targets, t.data(), t.size() * 4);
+    return WRK_OK;
+}
+
+// the chunk sizes of the next job (RnnIter::next); rows[] zeroed.  Fails when the input is exhausted
+static int32_t next_chunk(wrk_runtime* rt, const wrk_rnn_input* in, std::vector<uint32_t>& lens, std::vector<int32_t>& opts, uint32_t* rows) {
     const uint32_t nb = (uint32_t)in->tokens.size();
     if (nb != rt->num_batch) return fail(WRK_E_ARG, "input has %u batches, bundle was built for %u", nb, rt->num_batch);
     wrk_rnn_iter it;
     make_iter(*in, it);
-    std::vector<uint32_t> lens(nb);
-    std::vector<int32_t> opts(nb);
+    lens.assign(nb, 0);
+    opts.assign(nb, 0);
     it.next(lens.data(), opts.data());
     uint32_t T = 0;
     for (uint32_t b = 0; b < nb; ++b) T += lens[b];
     for (uint32_t b = 0; b < nb; ++b) rows[b] = 0;
     if (T == 0) return fail(WRK_E_ARG, "input iterator exhausted");
-    std::vector<uint32_t> headers;
-    std::vector<std::pair<uint32_t, uint32_t>> inputs, outputs;
-    redirect(lens.data(), opts.data(), nb, headers, inputs, outputs);
-    if (headers.size() > capacity_rows) return fail(WRK_E_ARG, "logits buffer holds %zu rows, chunk produces %zu", capacity_rows, headers.size());
-    // chunk + TensorStack cursors (tensor/mod.rs:1185-1233, into_cursors :70-84)
-    std::vector<uint32_t> toks, cursors;
+    return WRK_OK;
+}
+
+// chunk + TensorStack cursors (tensor/mod.rs:1185-1233, into_cursors :70-84)
+static int32_t stack_chunk(const wrk_rnn_input* in, const std::vector<uint32_t>& lens, std::vector<uint32_t>& toks, std::vector<uint32_t>& cursors) {
+    const uint32_t nb = (uint32_t)in->tokens.size();
+    toks.clear();
+    cursors.clear();
     uint32_t token = 0;
     for (uint32_t b = 0; b < nb; ++b) {
         if (lens[b] > 255) return fail(WRK_E_UNSUPPORTED, "batch %u: %u tokens in one chunk exceed the cursor's u8 length (tensor/mod.rs:53-60)", b, lens[b]);
@@ -1271,11 +1303,54 @@ int32_t wrk_runtime_infer(wrk_runtime* rt, wrk_rnn_input* in, float* logits, siz
         }
         token += lens[b];
     }
-    const int32_t rc = rt->model6
+    return WRK_OK;
+}
+
+// SimpleRuntime::infer (mod.rs:238-263) with RnnJob::{load, submit, back} (v7.rs:434-492)
+int32_t wrk_runtime_infer(wrk_runtime* rt, wrk_rnn_input* in, float* logits, size_t capacity_rows, uint32_t* rows, uint32_t mode) {
+    if (!rt || !in || !rows) return fail(WRK_E_ARG, "null argument");
+    const uint32_t nb = (uint32_t)in->tokens.size();
+    std::vector<uint32_t> lens, toks, cursors;
+    std::vector<int32_t> opts;
+    int32_t rc = next_chunk(rt, in, lens, opts, rows);
+    if (rc != WRK_OK) return rc;
+    std::vector<uint32_t> headers;
+    std::vector<std::pair<uint32_t, uint32_t>> inputs, outputs;
+    redirect(lens.data(), opts.data(), nb, headers, inputs, outputs);
+    if (headers.size() > capacity_rows) return fail(WRK_E_ARG, "logits buffer holds %zu rows, chunk produces %zu", capacity_rows, headers.size());
+    rc = stack_chunk(in, lens, toks, cursors);
+    if (rc != WRK_OK) return rc;
+    const uint32_t T = (uint32_t)toks.size();
+    rc = rt->model6
         ? wrk_v6_infer(rt->ctx, rt->model6, rt->state, toks.data(), nullptr, cursors.data(), T, headers.data(), (uint32_t)headers.size(), logits, nullptr, mode)
         : wrk_v7_infer(rt->ctx, rt->model, rt->state, toks.data(), nullptr, cursors.data(), T, headers.data(), (uint32_t)headers.size(), logits, nullptr, mode);
     if (rc != WRK_OK) return fail(rc, "infer: %s", wrk_last_error(rt->ctx));
     for (uint32_t b = 0; b < nb; ++b) rows[b] = outputs[b].second - outputs[b].first;
+    for (uint32_t b = 0; b < nb; ++b) in->tokens[b].erase(in->tokens[b].begin(), in->tokens[b].begin() + lens[b]);   // input.step()
+    return WRK_OK;
+}
+
+int32_t wrk_runtime_score(wrk_runtime* rt, wrk_rnn_input* in, float* logprob, uint32_t* rank, size_t capacity_rows, uint32_t* rows,
+                          uint32_t mode) {
+    if (!rt || !in || !rows) return fail(WRK_E_ARG, "null argument");
+    const uint32_t nb = (uint32_t)in->tokens.size();
+    std::vector<uint32_t> lens, toks, cursors;
+    std::vector<int32_t> opts;
+    int32_t rc = next_chunk(rt, in, lens, opts, rows);
+    if (rc != WRK_OK) return rc;
+    std::vector<uint32_t> headers, targets, count(nb);
+    score_plan(*in, lens.data(), headers, targets, count.data());
+    if (headers.size() > capacity_rows) return fail(WRK_E_ARG, "score buffers hold %zu rows, chunk produces %zu", capacity_rows, headers.size());
+    if (!headers.empty() && (!logprob || !rank)) return fail(WRK_E_ARG, "logprob and rank are required");
+    rc = stack_chunk(in, lens, toks, cursors);
+    if (rc != WRK_OK) return rc;
+    const uint32_t T = (uint32_t)toks.size();
+    const uint32_t NH = (uint32_t)headers.size();
+    rc = rt->model6
+        ? wrk_v6_score(rt->ctx, rt->model6, rt->state, toks.data(), nullptr, cursors.data(), T, headers.data(), NH, targets.data(), logprob, rank, mode)
+        : wrk_v7_score(rt->ctx, rt->model, rt->state, toks.data(), nullptr, cursors.data(), T, headers.data(), NH, targets.data(), logprob, rank, mode);
+    if (rc != WRK_OK) return fail(rc, "score: %s", wrk_last_error(rt->ctx));
+    for (uint32_t b = 0; b < nb; ++b) rows[b] = count[b];
     for (uint32_t b = 0; b < nb; ++b) in->tokens[b].erase(in->tokens[b].begin(), in->tokens[b].begin() + lens[b]);   // input.step()
     return WRK_OK;
 }

@@ -142,6 +142,11 @@ HIP_SYMBOLS = {
                                            C.c_uint32]),
     "wrk_v6_generate_sample": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _f32p, _f32p,
                                            C.c_uint32]),
+    "wrk_score_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p, _u32p]),
+    "wrk_v7_score": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _u32p, _f32p, _u32p,
+                                 C.c_uint32]),
+    "wrk_v6_score": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _u32p, _f32p, _u32p,
+                                 C.c_uint32]),
 }
 RT_SYMBOLS = {
     "wrk_host_last_error": (C.c_char_p, []),
@@ -176,6 +181,8 @@ RT_SYMBOLS = {
     "wrk_runtime_state": (_P, [_P]),
     "wrk_runtime_model_v6": (_P, [_P]),
     "wrk_runtime_infer": (C.c_int32, [_P, _P, _f32p, C.c_size_t, _u32p, C.c_uint32]),
+    "wrk_rnn_score_plan": (C.c_int32, [_P, _u32p, _u32p, _u32p, _u32p, _u32p]),
+    "wrk_runtime_score": (C.c_int32, [_P, _P, _f32p, _u32p, C.c_size_t, _u32p, C.c_uint32]),
 }
 for _lib, _tab in ((hip, HIP_SYMBOLS), (rt, RT_SYMBOLS)):
     for _name, (_res, _args) in _tab.items():
@@ -271,6 +278,27 @@ class Context:
         out = np.zeros(n, np.uint32)
         self.check(hip.wrk_sample_logits(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p), step, _ptr(out, _u32p)))
         return out
+
+    def score_logits(self, logits, targets, num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
+        """Per row of f32 logits and its target token t: (logprob = x_t - logsumexp(x), rank = #{x_i > x_t} + #{i < t : x_i == x_t}),
+        computed on the device.  `logits`: an [n, V] f32 array, or a `Buffer` of n rows of `row_stride` f32 (first `num_vocab` used).
+        Returns (float32 [n], uint32 [n])."""
+        tg = _u32(targets).reshape(-1)
+        n = tg.size
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            stride = int(row_stride or V)
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            assert a.shape[0] == n, "one target per row"
+            V = stride = a.shape[1]
+            buf = self.buffer(a)
+        lp = np.zeros(n, np.float32)
+        rk = np.zeros(n, np.uint32)
+        self.check(hip.wrk_score_logits(self.h, buf.h, V, stride, n, _ptr(tg, _u32p), _ptr(lp, _f32p), _ptr(rk, _u32p)))
+        return lp, rk
 
 
 class Program:
@@ -646,6 +674,19 @@ class RnnInput:
         self.h = None
 
 
+def score_plan(inp: RnnInput, lens):
+    """`wrk_rnn_score_plan` of the chunk `lens` (RnnIter::next of `inp`, before `inp.step()`): (headers, targets, rows per batch)."""
+    ln = _u32(lens)
+    cap = max(int(ln.sum()), 1)
+    headers = np.zeros(cap, np.uint32)
+    targets = np.zeros(cap, np.uint32)
+    nh = C.c_uint32()
+    rows = np.zeros(inp.num_batch, np.uint32)
+    _host_check(rt.wrk_rnn_score_plan(inp.h, _ptr(ln, _u32p), _ptr(headers, _u32p), _ptr(targets, _u32p), C.byref(nh), _ptr(rows, _u32p)))
+    n = nh.value
+    return headers[:n].tolist(), targets[:n].tolist(), rows.tolist()
+
+
 def redirect(info):
     """`RnnInfo::redirect` -> (headers, inputs, outputs)."""
     nb = len(info)
@@ -700,6 +741,45 @@ class Runtime:
             out.append(logits[p:p + rows[b]].copy())
             p += int(rows[b])
         return out
+
+    def score(self, inp: RnnInput, mode: int = 1):
+        """The scoring analogue of `infer`: runs one chunk and returns per-batch (logprob, rank) of every position whose next token
+        is still in `inp` (`score_plan`); the state advances as `infer`'s would."""
+        cap = inp.token_chunk_size + inp.num_batch
+        lp = np.empty(cap, np.float32)
+        rk = np.empty(cap, np.uint32)
+        rows = np.zeros(inp.num_batch, np.uint32)
+        _host_check(rt.wrk_runtime_score(self.h, inp.h, _ptr(lp, _f32p), _ptr(rk, _u32p), cap, _ptr(rows, _u32p), mode))
+        out, p = [], 0
+        for b in range(inp.num_batch):
+            out.append((lp[p:p + rows[b]].copy(), rk[p:p + rows[b]].copy()))
+            p += int(rows[b])
+        return out
+
+    def score_sequences(self, seqs, token_chunk_size: int = 128, mode: int = 1):
+        """Scores whole sequences, one per state slot (len(seqs) == num_batch): for each, (logprob[len-1], rank[len-1]) where entry i
+        is `log p(seq[i+1] | seq[:i+1])` and that token's greedy rank.  Scoring continues from the runtime's current state slots, as
+        `infer` does: reset them first (`state_load` / `state_write`) to score from an empty context."""
+        inp = RnnInput(seqs, token_chunk_size)
+        lps = [[] for _ in seqs]
+        rks = [[] for _ in seqs]
+        while any(inp.remaining(b) for b in range(inp.num_batch)):
+            for b, (lp, rk) in enumerate(self.score(inp, mode)):
+                lps[b].append(lp)
+                rks[b].append(rk)
+        return [(np.concatenate(l) if l else np.zeros(0, np.float32), np.concatenate(r) if r else np.zeros(0, np.uint32))
+                for l, r in zip(lps, rks)]
+
+    def score_raw(self, tokens, cursors, headers, targets, mode: int = 1):
+        """One RnnJob on explicit stacked tokens / packed cursors / header rows, the header rows scored against `targets`:
+        (logprob float32 [NH], rank uint32 [NH])."""
+        t, c, h, tg = _u32(tokens), _u32(cursors), _u32(headers), _u32(targets)
+        lp = np.zeros(max(h.size, 1), np.float32)
+        rk = np.zeros(max(h.size, 1), np.uint32)
+        fn, mdl = (hip.wrk_v6_score, self.model6) if self.model6 else (hip.wrk_v7_score, self.model)
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(t, _u32p), None, _ptr(c, _u32p), t.size, _ptr(h, _u32p), h.size,
+                          _ptr(tg, _u32p) if tg.size else None, _ptr(lp, _f32p), _ptr(rk, _u32p), mode))
+        return lp[: h.size], rk[: h.size]
 
     def infer_raw(self, tokens, cursors, headers, mode: int = 1, want_argmax: bool = False):
         """One RnnJob on explicit stacked tokens / packed cursors / header rows."""
