@@ -343,6 +343,41 @@ int32_t wrk_v7_score(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state,
                      const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors, uint32_t num_token,
                      const uint32_t* headers, uint32_t num_header, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode);
 
+/* Repetition penalties (ChatRWKV PIPELINE.generate: alpha_presence / alpha_frequency / alpha_decay / token_ban) on the device.
+ * An occurrence table has num_batch slots of num_vocab entries (slot b belongs to state slot b): count[n] f32 and flags[n] (bit 0
+ * present, bit 1 banned), plus one weight vector w[n] (finite, >= 0, default 1: ChatRWKV's `www`).  A row x of slot b is penalised as
+ *   x'[n] = -inf if banned[n];  x[n] - (presence + count[n] * frequency) if present[n] (t = count * frequency; t = presence + t;
+ *   x - t, each rounded to f32);  x[n] otherwise
+ * and a drawn token y updates the slot as: count[n] *= decay for every n; then count[y] += w[y]; then present[y] = 1.
+ * Flags cross the ABI as one uint32_t per token.  Every call validates on the host first (WRK_E_ARG): NULL arrays, slots out of range,
+ * tokens >= num_vocab, a table of another context, non-finite presence / frequency, decay outside [0, 1], weights < 0 or non-finite,
+ * and any ban or load that would leave a slot with no allowed token.  num_vocab > 2^20: WRK_E_UNSUPPORTED (the sampler's limit). */
+typedef struct wrk_occurrence wrk_occurrence;
+int32_t wrk_occurrence_create(wrk_ctx* ctx, uint32_t num_batch, uint32_t num_vocab, wrk_occurrence** out);   /* zero counts and flags */
+int32_t wrk_occurrence_destroy(wrk_occurrence* occ);
+/* weights: host f32 [num_vocab], or NULL for all 1 */
+int32_t wrk_occurrence_set_weights(wrk_ctx* ctx, wrk_occurrence* occ, const float* weights);
+/* sets (banned != 0) or clears the banned bit of tokens[0..n) in slot `batch` */
+int32_t wrk_occurrence_ban(wrk_ctx* ctx, wrk_occurrence* occ, uint32_t batch, const uint32_t* tokens, uint32_t n, int32_t banned);
+/* applies the update rule for tokens[0], tokens[1], ... in order (e.g. to count a prompt) */
+int32_t wrk_occurrence_add(wrk_ctx* ctx, wrk_occurrence* occ, uint32_t batch, const uint32_t* tokens, uint32_t n, float decay);
+/* counts: host f32 [num_vocab], flags: host u32 [num_vocab] */
+int32_t wrk_occurrence_back(wrk_ctx* ctx, const wrk_occurrence* occ, uint32_t batch, float* counts, uint32_t* flags);
+/* counts (finite) and flags (values 0..3) of one slot; both NULL: reset the slot to zero counts and no flags */
+int32_t wrk_occurrence_load(wrk_ctx* ctx, wrk_occurrence* occ, uint32_t batch, const float* counts, const uint32_t* flags);
+/* penalises f32 logits [num_rows][row_stride] (first num_vocab used) in place; row r uses slot first_batch + r and presence[r] /
+ * frequency[r] (host f32 [num_rows]).  Blocking.  In a host-side chat loop it goes between infer and wrk_sample_logits. */
+int32_t wrk_penalize_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                            const wrk_occurrence* occ, uint32_t first_batch, const float* presence, const float* frequency);
+/* as wrk_v7_generate_sample, the draw of sequence b made on its logits penalised with slot b of `occ` and (presence[b], frequency[b]),
+ * and slot b updated with decay[b] after every draw (host f32 [num_batch]).  The first token of a call is not counted; the last drawn
+ * token is.  last_logits stays the head output before penalties.  The table is passed to the step program as data: one cached program
+ * serves any table and any parameters; occ->num_batch >= num_batch and occ->num_vocab == the model's. */
+int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
+                                  uint32_t steps, const float* temperature, const float* top_p, const uint32_t* seed, const float* presence,
+                                  const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens,
+                                  float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
+
 /* ---------------------------------------------------------------- RWKV-6 (v6::Model, src/runtime/v6.rs)
  * Same chunk semantics, state layout ([D, S+2, B] per layer: v6.rs:150-214 == v7) and entry points as the V7
  * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph. */
@@ -393,6 +428,12 @@ int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* 
 int32_t wrk_v6_score(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state,
                      const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors, uint32_t num_token,
                      const uint32_t* headers, uint32_t num_header, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode);
+
+/* as wrk_v7_generate_penalized */
+int32_t wrk_v6_generate_penalized(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
+                                  uint32_t steps, const float* temperature, const float* top_p, const uint32_t* seed, const float* presence,
+                                  const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens,
+                                  float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
 
 #ifdef __cplusplus
 }

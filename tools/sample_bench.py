@@ -1,8 +1,10 @@
 """Cost of on-device sampling in the decode loop: generate_greedy against generate_sample (T = 1, top_p = 0.9) on the bench's synthetic
 RWKV-7 1.5B Q4_K_M model, alternating the two, medians of the per-step time (HIP events around the replays).  Also prints, as context,
 what the host alternative would cost per step: reading the logits back and a NumPy restatement of chat.rs's sampler per row.
+A third leg, alternating with the other two, is generate_penalized with the same sampler parameters and ChatRWKV-style repetition
+penalties (presence = frequency = 0.2, decay = 0.996, 16 banned tokens per sequence; --no-penalized skips it).
 
-    python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7]
+    python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized]
 
 Prints one JSON object.
 """
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-p", type=float, default=0.9)
+    ap.add_argument("--no-penalized", action="store_true")
     args = ap.parse_args()
     import wrk
 
@@ -50,15 +53,26 @@ def main():
     V = rt.info.num_vocab
     out = {"model": f"RWKV-7 {args.model} Q4_K_M (synthetic)", "temperature": args.temperature, "top_p": args.top_p, "steps": args.steps,
            "reps": args.reps, "batches": []}
+    pen = not args.no_penalized
+    occ = wrk.Occurrence(ctx, max(batches), V) if pen else None
+    pkw = dict(temperature=args.temperature, top_p=args.top_p, presence=0.2, frequency=0.2, decay=0.996)
+    if pen:
+        out["penalties"] = {"presence": 0.2, "frequency": 0.2, "decay": 0.996, "banned_per_sequence": 16}
+        for b in range(max(batches)):
+            occ.ban(b, [(1000 + 997 * i + 31 * b) % V for i in range(16)])
     for B in batches:
         first = [(17 + 101 * b) % (V - 1) for b in range(B)]
         engine = rt.engine_status()[0] if B == 1 else False
         rt.generate_greedy(first, 4)
         rt.generate_sample(first, 4, temperature=args.temperature, top_p=args.top_p)
-        g, s = [], []
+        if pen:
+            rt.generate_penalized(first, 4, occ, **pkw)
+        g, s, p = [], [], []
         for _ in range(args.reps):
             g.append(rt.generate_greedy(first, args.steps)[1] / args.steps)
             s.append(rt.generate_sample(first, args.steps, temperature=args.temperature, top_p=args.top_p)[1] / args.steps)
+            if pen:
+                p.append(rt.generate_penalized(first, args.steps, occ, **pkw)[1] / args.steps)
         gm, sm = float(np.median(g)), float(np.median(s))
         # host alternative: logits back over PCIe + a CPU sort per row (what a caller of wrk_v7_infer has to do today)
         _, _, logits = rt.generate_greedy(first, 1, want_logits=True)
@@ -81,6 +95,12 @@ def main():
             "greedy_ms_all": [round(x, 5) for x in g], "sample_ms_all": [round(x, 5) for x in s],
             "host_alternative_ms_per_step": {"logits_readback": round(float(np.median(rd)), 4), "numpy_chat_rs_sampler": round(float(np.median(host)), 4)},
         })
+        if pen:
+            pm = float(np.median(p))
+            out["batches"][-1].update({"penalized_ms_per_step": round(pm, 5), "penalized_minus_sample_us": round((pm - sm) * 1e3, 2),
+                                       "penalized_ms_all": [round(x, 5) for x in p]})
+    if occ is not None:
+        occ.close()
     rt.close()
     ctx.close()
     print(json.dumps(out))

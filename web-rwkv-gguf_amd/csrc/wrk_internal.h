@@ -187,6 +187,16 @@ uint32_t score_slices(uint32_t n, uint32_t v, int num_cu);
 int score_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const uint32_t* targets, ScorePart* part,
                float* logprob, uint32_t* rank, int num_cu);
 
+// wrk_penalty.hip: repetition penalties.  One PenaltyParam per row: the row's slot of an occurrence table (count f32 [v],
+// flags u8 [v]: bit 0 present, bit 1 banned), the table's weights f32 [v] and the sequence's (presence, frequency, decay).  Decode loops
+// keep these in a per-frame device buffer written before every call, so a captured step never holds a table pointer of its own.
+// penalize_rows: dst row r = the penalised src row r (src == dst allowed).  occurrence_update: row r applies tokens[r * ntok ..] in
+// order (count *= decay, then count[y] += weight[y], present[y] = 1); tokens < v (the caller validates them)
+struct PenaltyParam { float* count; uint8_t* flags; const float* weight; float presence, frequency, decay; uint32_t pad; };
+void penalize_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_stride, uint32_t n, const PenaltyParam* par, float* dst,
+                   uint32_t dst_stride);
+void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, uint32_t ntok);
+
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled
 void timing_report(wrk_ctx* ctx);
@@ -271,3 +281,19 @@ struct wrk_score_scratch {
 };
 // WRK_E_ARG unless every target < V (targets may be NULL only when n == 0)
 int32_t wrk_score_check_targets(wrk_ctx* ctx, const uint32_t* targets, uint32_t n, uint32_t V);
+
+// include/wrk_hip.h wrk_occurrence: one allocation holding counts f32 [num_batch][num_vocab], weights f32 [num_vocab] and
+// flags u8 [num_batch][num_vocab] (bit 0 present, bit 1 banned)
+struct wrk_occurrence {
+    wrk_ctx* ctx = nullptr;
+    uint32_t num_batch = 0, num_vocab = 0;
+    void* mem = nullptr;
+    float* counts = nullptr;
+    float* weights = nullptr;
+    uint8_t* flags = nullptr;
+    wrk::PenaltyParam row(uint32_t slot, float presence, float frequency, float decay) const;
+};
+// validated PenaltyParam rows of slots [first, first + n) (WRK_E_ARG on a NULL table or array, a table of another context or another
+// vocabulary, slots out of range, a non-finite presence / frequency, a decay outside [0, 1]); decay NULL: 1
+int32_t wrk_penalty_pack(wrk_ctx* ctx, const wrk_occurrence* occ, uint32_t first, uint32_t n, uint32_t V, const float* presence,
+                         const float* frequency, const float* decay, std::vector<wrk::PenaltyParam>& out);

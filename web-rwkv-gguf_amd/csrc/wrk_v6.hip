@@ -28,6 +28,9 @@ struct wrk_v6_model {
     size_t history_cap = 0;
     wrk::SampleParam* sample_par = nullptr;    // generate_sample's per-sequence parameters (written per call, read by the step program)
     uint32_t sample_par_cap = 0;
+    wrk::PenaltyParam* pen_par = nullptr;      // generate_penalized: occurrence rows and penalties (written per call) and the penalised
+    float* pen_o = nullptr;                     // logits [B][V] the sampler draws from
+    uint32_t pen_cap = 0;
     wrk_score_scratch score;    // wrk_v6_score: targets / logprob / rank / slice partials of the header rows (read by no captured program)
     uint32_t wkv_nseq = 0;      // sequences of the job being enqueued (0: unknown): picks the WKV chunk kernel (wrk::time_mix_v6)
     std::map<std::tuple<const void*, uint32_t, uint32_t>, wrk_program*> graphs;      // (state, sequences, mode)
@@ -604,6 +607,8 @@ int32_t wrk_v6_model_destroy(wrk_v6_model* m) {
         if (m->scratch) hipFree(m->scratch);
         if (m->history) hipFree(m->history);
         if (m->sample_par) hipFree(m->sample_par);
+        if (m->pen_par) hipFree(m->pen_par);
+        if (m->pen_o) hipFree(m->pen_o);
         m->score.release();
     }
     for_each_handle(m, [](const wrk_buf* b) { if (b) wrk_buf_release(const_cast<wrk_buf*>(b)); },
@@ -722,9 +727,11 @@ int32_t wrk_v6_score(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint
     return v6_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank, mode);
 }
 
-// par: sampler parameters of the B sequences (generate_sample), or nullptr (generate_greedy)
+// par: sampler parameters of the B sequences (generate_sample), or nullptr (generate_greedy); pen: their occurrence rows and penalties
+// (generate_penalized, with par), or nullptr
 static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
-                           const wrk::SampleParam* par, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
+                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen, uint32_t* out_tokens, float* last_logits,
+                           float* elapsed_ms, uint32_t mode) {
     LOCK(ctx);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
     WRK_ARG(ctx, m->d.emb_f16, "generate_greedy needs the device embedding table");
@@ -744,6 +751,18 @@ static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, cons
         WRK_HIP(ctx, hipMalloc((void**)&m->sample_par, (size_t)B * sizeof(wrk::SampleParam)));
         m->sample_par_cap = B;
     }
+    if (rc == WRK_OK && pen && (B > m->pen_cap || !m->pen_par || !m->pen_o)) {     // as sample_par
+        WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        m->drop_graphs();
+        if (m->pen_par) hipFree(m->pen_par);
+        if (m->pen_o) hipFree(m->pen_o);
+        m->pen_par = nullptr;
+        m->pen_o = nullptr;
+        m->pen_cap = 0;
+        WRK_HIP(ctx, hipMalloc((void**)&m->pen_par, (size_t)B * sizeof(wrk::PenaltyParam)));
+        WRK_HIP(ctx, hipMalloc((void**)&m->pen_o, (size_t)B * V * 4));
+        m->pen_cap = B;
+    }
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = b | (b << 8) | (1u << 24); hdr[b] = b; }
@@ -751,6 +770,7 @@ static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, cons
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.headers, hdr.data(), (size_t)B * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.tokens, first_tokens, (size_t)B * 4);
     if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, m->sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
+    if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, m->pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
     if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipMemsetAsync(m->s.counter, 0, 4, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -762,14 +782,20 @@ static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, cons
         if (mode == 1) r = m->enqueue_fused_decode(st, B, B, true, 0);
         if (r == WRK_E_UNSUPPORTED) r = m->enqueue_ops(st, B, B, true);
         if (r != WRK_OK) return r;
+        const float* logits = m->s.head_o;
+        if (pen) {      // the sampler draws from the penalised copy; the drawn tokens are counted before the counter moves
+            wrk::penalize_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->pen_par, m->pen_o, V);
+            logits = m->pen_o;
+        }
         if (!par) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->s.argmax);
-        else if (wrk::sample_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->sample_par, m->s.counter, m->s.argmax) != 0)
+        else if (wrk::sample_rows(ctx->op_stream(), logits, V, V, B, m->sample_par, m->s.counter, m->s.argmax) != 0)
             return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+        if (pen) wrk::occurrence_update(ctx->op_stream(), V, B, m->pen_par, m->s.argmax, 1);
         wrk::advance_tokens(ctx->op_stream(), m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
         return WRK_OK;
     };
     wrk_program* prog = nullptr;
-    const auto key = std::make_tuple(st->uid, B, mode | (par ? 32u : 0u));       // sampled steps never alias greedy ones
+    const auto key = std::make_tuple(st->uid, B, mode | (par ? 32u : 0u) | (pen ? 64u : 0u));   // nor do greedy, sampled and penalised steps
     if (!eager) {
         auto it = m->graphs.find(key);
         if (it != m->graphs.end()) prog = it->second;
@@ -809,7 +835,7 @@ static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, cons
 int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
     if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
-    return v6_generate(ctx, m, st, first_tokens, B, steps, nullptr, out_tokens, last_logits, elapsed_ms, mode);
+    return v6_generate(ctx, m, st, first_tokens, B, steps, nullptr, nullptr, out_tokens, last_logits, elapsed_ms, mode);
 }
 
 int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
@@ -821,7 +847,24 @@ int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, 
     const int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
     if (rc != WRK_OK) return rc;
     WRK_ARG(ctx, B >= 1, "num_batch 0");
-    return v6_generate(ctx, m, st, first_tokens, B, steps, par.data(), out_tokens, last_logits, elapsed_ms, mode);
+    return v6_generate(ctx, m, st, first_tokens, B, steps, par.data(), nullptr, out_tokens, last_logits, elapsed_ms, mode);
+}
+
+int32_t wrk_v6_generate_penalized(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                                  const float* temperature, const float* top_p, const uint32_t* seed, const float* presence,
+                                  const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens, float* last_logits,
+                                  float* elapsed_ms, uint32_t mode) {
+    if (!ctx || !m || !st || !first_tokens || !occ) return WRK_E_ARG;
+    LOCK(ctx);
+    std::vector<wrk::SampleParam> par;
+    int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, B >= 1, "num_batch 0");
+    WRK_ARG(ctx, decay, "decay array required");
+    std::vector<wrk::PenaltyParam> pen;
+    rc = wrk_penalty_pack(ctx, occ, 0, B, m->d.num_vocab, presence, frequency, decay, pen);
+    if (rc != WRK_OK) return rc;
+    return v6_generate(ctx, m, st, first_tokens, B, steps, par.data(), pen.data(), out_tokens, last_logits, elapsed_ms, mode);
 }
 
 }  // extern "C"

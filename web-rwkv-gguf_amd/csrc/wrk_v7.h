@@ -44,6 +44,9 @@ struct wrk_v7_model {
     wrk::SampleParam* sample_par = nullptr;    // generate_sample: per-sequence sampler parameters, written before every call (not baked
     uint32_t sample_par_cap = 0;                // into the step programs, which read them through this pointer)
     wrk_score_scratch score;                    // wrk_v7_score: targets / logprob / rank / slice partials of the header rows
+    wrk::PenaltyParam* pen_par = nullptr;      // generate_penalized: per-sequence occurrence rows and penalties, written before every call
+    float* pen_o = nullptr;                     // (the step programs read the table's pointers from here); pen_o: penalised logits [B][V]
+    uint32_t pen_cap = 0;
 
     // b: tokens (generate_greedy: sequences); mode: 0/1 for generate_greedy, or 16 + flag bits for wrk_v7_infer jobs
     // (the analogue of the reference's cached RnnJob per RnnInfo, runtime/mod.rs:110-209); nh: header rows
@@ -85,6 +88,7 @@ struct wrk_v7_model {
     int32_t ensure_scratch(uint32_t T, uint32_t NH);
     int32_t ensure_history(size_t n);
     int32_t ensure_sample_params(uint32_t n);
+    int32_t ensure_penalty(uint32_t n);
     void drop_graphs();
     int32_t enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity_headers, bool merged = false);
     // from_tokens: gather embedding rows of s.tokens on the device; want_argmax: greedy token per header row into

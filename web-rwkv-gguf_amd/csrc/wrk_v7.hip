@@ -368,6 +368,8 @@ int32_t wrk_v7_model_destroy(wrk_v7_model* m) {
     m->lanes.clear();
     if (m->history) { LOCK(ctx); hipFree(m->history); m->history = nullptr; }
     if (m->sample_par) { LOCK(ctx); hipFree(m->sample_par); m->sample_par = nullptr; }
+    if (m->pen_par) { LOCK(ctx); hipFree(m->pen_par); m->pen_par = nullptr; }
+    if (m->pen_o) { LOCK(ctx); hipFree(m->pen_o); m->pen_o = nullptr; }
     if (m->score.buf) { LOCK(ctx); m->score.release(); }
     auto fb = [](const wrk_buf* b) { if (b) wrk_buf_release(const_cast<wrk_buf*>(b)); };
     auto fm = [](const wrk_matrix* x) { if (x) wrk_matrix_release(const_cast<wrk_matrix*>(x)); };
@@ -725,8 +727,10 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
 
 // one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers, pick each sequence's next token -- the arg-max,
 // or with `sampled` the sampler (wrk_sample.hip) on the frame's per-sequence parameters at step *s.counter -- and advance
-// tokens / history / counter
-static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled) {
+// tokens / history / counter.  `penalized` (implies `sampled`): the sampler draws from pen_o = head_o penalised with the occurrence rows of
+// pen_par, and those rows count the drawn tokens (wrk_penalty.hip)
+static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled,
+                                   bool penalized) {
     const uint32_t V = m->d.num_vocab;
     hipStream_t q = ctx->op_stream();
     int32_t rc;
@@ -740,22 +744,31 @@ static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* 
         }
     }
     if (rc != WRK_OK || !sampled) return rc;
+    const float* logits = m->s.head_o;
+    if (penalized) {
+        wrk::penalize_rows(q, m->s.head_o, V, V, B, m->pen_par, m->pen_o, V);
+        logits = m->pen_o;
+    }
     // the sampler only reads the counter: rows run in different workgroups, so advance_tokens moves it after all of them
-    if (wrk::sample_rows(q, m->s.head_o, V, V, B, m->sample_par, m->s.counter, m->s.argmax) != 0)
+    if (wrk::sample_rows(q, logits, V, V, B, m->sample_par, m->s.counter, m->s.argmax) != 0)
         return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    if (penalized) wrk::occurrence_update(q, V, B, m->pen_par, m->s.argmax, 1);
     wrk::advance_tokens(q, m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
     return WRK_OK;
 }
 
-// generate_greedy / generate_sample, part 1: frame, token / cursor / sampler-parameter upload and the (cached) decode-step program of
-// sequences [b0, b0 + B) on model frame `m`; par: the B sequences' sampler parameters, or nullptr for the arg-max
+// generate_greedy / generate_sample / generate_penalized, part 1: frame, token / cursor / sampler-parameter upload and the (cached)
+// decode-step program of sequences [b0, b0 + B) on model frame `m`; par: the B sequences' sampler parameters, or nullptr for the arg-max;
+// pen: their occurrence rows and penalties (with par), or nullptr
 static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t b0, uint32_t B,
-                              uint32_t steps, uint32_t mode, bool eager, const wrk::SampleParam* par, wrk_program** prog_out) {
+                              uint32_t steps, uint32_t mode, bool eager, const wrk::SampleParam* par, const wrk::PenaltyParam* pen,
+                              wrk_program** prog_out) {
     int32_t rc = m->ensure_scratch(B, B);
     if (rc != WRK_OK) return rc;
     if (B == 1 && mode == 1) { rc = m->ensure_engine(); if (rc != WRK_OK) return rc; }
     rc = m->ensure_history((size_t)steps * B);
     if (rc == WRK_OK && par) rc = m->ensure_sample_params(B);
+    if (rc == WRK_OK && pen) rc = m->ensure_penalty(B);
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
@@ -763,20 +776,21 @@ static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, c
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.headers, hdr.data(), (size_t)B * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.tokens, first_tokens, (size_t)B * 4);
     if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, m->sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
+    if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, m->pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
     if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipMemsetAsync(m->s.counter, 0, 4, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *prog_out = nullptr;
     if (eager) return WRK_OK;
     // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo; sampled
-    // steps have their own key bit, so greedy and sampled programs never alias
+    // steps have their own key bit, so greedy and sampled programs never alias, and so do penalised ones (bit 24, above every infer flag)
     const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
-                                                             (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u)};
+                                                             (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u) | (pen ? 1u << 24 : 0u)};
     auto it = m->graphs.find(key);
     if (it != m->graphs.end()) { *prog_out = it->second; return WRK_OK; }
     rc = wrk_capture_begin(ctx);
     if (rc != WRK_OK) return rc;
-    rc = enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr);
+    rc = enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr);
     wrk_program* p = nullptr;
     const int32_t rc2 = wrk_capture_end(ctx, &p);
     if (rc != WRK_OK) { if (p) wrk_program_destroy(p); return rc; }
@@ -786,10 +800,11 @@ static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, c
     return WRK_OK;
 }
 
-// par: sampler parameters of the num_batch sequences (generate_sample), or nullptr (generate_greedy)
+// par: sampler parameters of the num_batch sequences (generate_sample), or nullptr (generate_greedy); pen: their occurrence rows and
+// penalties (generate_penalized), or nullptr
 static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
-                           uint32_t steps, const wrk::SampleParam* par, uint32_t* out_tokens, float* last_logits, float* elapsed_ms,
-                           uint32_t mode_arg) {
+                           uint32_t steps, const wrk::SampleParam* par, const wrk::PenaltyParam* pen, uint32_t* out_tokens, float* last_logits,
+                           float* elapsed_ms, uint32_t mode_arg) {
     LOCK(ctx);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
     WRK_ARG(ctx, m->emb, "generate_greedy needs the device embedding table");
@@ -836,7 +851,7 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
         L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
         // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
         const int32_t rc = decode_prepare(ctx, L[g].mdl, st, first_tokens + L[g].b0, L[g].b0, L[g].nb, steps, mode, eager,
-                                          par ? par + L[g].b0 : nullptr, &L[g].prog);
+                                          par ? par + L[g].b0 : nullptr, pen ? pen + L[g].b0 : nullptr, &L[g].prog);
         if (rc != WRK_OK) return rc;
     }
     // every early return below leaves through this guard: the timing events are destroyed and, after an error, the lane streams are
@@ -856,7 +871,7 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
     if (groups == 1) {
         for (uint32_t i = 0; i < steps; ++i) {
             if (eager) {
-                const int32_t rc = enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr);
+                const int32_t rc = enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr, pen != nullptr);
                 if (rc != WRK_OK) return rc;
             } else WRK_HIP(ctx, hipGraphLaunch(L[0].prog->exec, ctx->stream));
         }
@@ -899,7 +914,7 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
 int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
                                uint32_t steps, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg) {
     if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
-    return v7_generate(ctx, m, st, first_tokens, B, steps, nullptr, out_tokens, last_logits, elapsed_ms, mode_arg);
+    return v7_generate(ctx, m, st, first_tokens, B, steps, nullptr, nullptr, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
@@ -911,7 +926,24 @@ int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, 
     const int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
     if (rc != WRK_OK) return rc;
     WRK_ARG(ctx, B >= 1, "num_batch 0");
-    return v7_generate(ctx, m, st, first_tokens, B, steps, par.data(), out_tokens, last_logits, elapsed_ms, mode_arg);
+    return v7_generate(ctx, m, st, first_tokens, B, steps, par.data(), nullptr, out_tokens, last_logits, elapsed_ms, mode_arg);
+}
+
+int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                                  const float* temperature, const float* top_p, const uint32_t* seed, const float* presence,
+                                  const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens, float* last_logits,
+                                  float* elapsed_ms, uint32_t mode_arg) {
+    if (!ctx || !m || !st || !first_tokens || !occ) return WRK_E_ARG;
+    LOCK(ctx);
+    std::vector<wrk::SampleParam> par;
+    int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, B >= 1, "num_batch 0");
+    WRK_ARG(ctx, decay, "decay array required");
+    std::vector<wrk::PenaltyParam> pen;
+    rc = wrk_penalty_pack(ctx, occ, 0, B, m->d.num_vocab, presence, frequency, decay, pen);
+    if (rc != WRK_OK) return rc;
+    return v7_generate(ctx, m, st, first_tokens, B, steps, par.data(), pen.data(), out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 }  // extern "C"
@@ -951,6 +983,21 @@ int32_t wrk_v7_model::ensure_sample_params(uint32_t n) {
     sample_par = nullptr;
     WRK_HIP(ctx, hipMalloc((void**)&sample_par, (size_t)n * sizeof(wrk::SampleParam)));
     sample_par_cap = n;
+    return WRK_OK;
+}
+
+int32_t wrk_v7_model::ensure_penalty(uint32_t n) {
+    if (n <= pen_cap && pen_par && pen_o) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drop_graphs();                  // captured penalised steps hold the old pointers
+    if (pen_par) hipFree(pen_par);
+    if (pen_o) hipFree(pen_o);
+    pen_par = nullptr;
+    pen_o = nullptr;
+    pen_cap = 0;
+    WRK_HIP(ctx, hipMalloc((void**)&pen_par, (size_t)n * sizeof(wrk::PenaltyParam)));
+    WRK_HIP(ctx, hipMalloc((void**)&pen_o, (size_t)n * d.num_vocab * 4));
+    pen_cap = n;
     return WRK_OK;
 }
 

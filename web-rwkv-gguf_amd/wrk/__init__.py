@@ -147,6 +147,18 @@ HIP_SYMBOLS = {
                                  C.c_uint32]),
     "wrk_v6_score": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _u32p, _f32p, _u32p,
                                  C.c_uint32]),
+    "wrk_occurrence_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "wrk_occurrence_destroy": (C.c_int32, [_P]),
+    "wrk_occurrence_set_weights": (C.c_int32, [_P, _P, _f32p]),
+    "wrk_occurrence_ban": (C.c_int32, [_P, _P, C.c_uint32, _u32p, C.c_uint32, C.c_int32]),
+    "wrk_occurrence_add": (C.c_int32, [_P, _P, C.c_uint32, _u32p, C.c_uint32, C.c_float]),
+    "wrk_occurrence_back": (C.c_int32, [_P, _P, C.c_uint32, _f32p, _u32p]),
+    "wrk_occurrence_load": (C.c_int32, [_P, _P, C.c_uint32, _f32p, _u32p]),
+    "wrk_penalize_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, _f32p, _f32p]),
+    "wrk_v7_generate_penalized": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _f32p, _f32p, _f32p, _P,
+                                              _u32p, _f32p, _f32p, C.c_uint32]),
+    "wrk_v6_generate_penalized": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _f32p, _f32p, _f32p, _P,
+                                              _u32p, _f32p, _f32p, C.c_uint32]),
 }
 RT_SYMBOLS = {
     "wrk_host_last_error": (C.c_char_p, []),
@@ -299,6 +311,84 @@ class Context:
         rk = np.zeros(n, np.uint32)
         self.check(hip.wrk_score_logits(self.h, buf.h, V, stride, n, _ptr(tg, _u32p), _ptr(lp, _f32p), _ptr(rk, _u32p)))
         return lp, rk
+
+    def penalize_logits(self, logits, occ: "Occurrence", presence, frequency, first_batch: int = 0, num_vocab: Optional[int] = None,
+                        row_stride: Optional[int] = None):
+        """ChatRWKV's repetition penalties on the device: row r of the logits penalised with slot first_batch + r of `occ` (banned:
+        -inf; present: x - (presence + count * frequency)).  `logits`: an [n, V] f32 array (returns the penalised
+        copy), or a `Buffer` of n rows of `row_stride` f32 (first `num_vocab` used), penalised in place (returns None).
+        presence / frequency: scalars or per-row arrays."""
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            stride = int(row_stride or V)
+            n = (buf.nbytes // 4 - V) // stride + 1 if buf.nbytes >= 4 * V else 0
+            a = None
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            n, V = a.shape
+            stride = V
+            buf = self.buffer(a)
+        ap, af = _per_row(presence, n, np.float32), _per_row(frequency, n, np.float32)
+        self.check(hip.wrk_penalize_logits(self.h, buf.h, V, stride, n, occ.h, first_batch, _ptr(ap, _f32p), _ptr(af, _f32p)))
+        return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
+
+
+class Occurrence:
+    """The per-sequence occurrence table of the repetition penalties (ChatRWKV's `occurrence` dict and `token_ban`, on the device):
+    num_batch slots of num_vocab (count f32, flags: bit 0 present, bit 1 banned), slot b belonging to state slot b, and one weight vector
+    (ChatRWKV's `www`, default 1).  Survives across calls, like the RNN state."""
+
+    PRESENT, BANNED = 1, 2
+
+    def __init__(self, ctx: Context, num_batch: int, num_vocab: int):
+        h = _P()
+        ctx.check(hip.wrk_occurrence_create(ctx.h, num_batch, num_vocab, C.byref(h)))
+        self.ctx, self.h, self.num_batch, self.num_vocab = ctx, h, num_batch, num_vocab
+
+    def set_weights(self, weights=None):
+        """weights: f32 [num_vocab], finite and >= 0; None: all 1."""
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+        assert w is None or w.size == self.num_vocab
+        self.ctx.check(hip.wrk_occurrence_set_weights(self.ctx.h, self.h, None if w is None else _ptr(w, _f32p)))
+
+    def ban(self, b: int, tokens, banned: bool = True):
+        t = _u32(tokens).reshape(-1)
+        self.ctx.check(hip.wrk_occurrence_ban(self.ctx.h, self.h, b, _ptr(t, _u32p), t.size, 1 if banned else 0))
+
+    def add(self, b: int, tokens, decay: float = 1.0):
+        """Counts tokens in order as the decode loop counts drawn ones: count *= decay, then count[y] += w[y], present[y] = 1."""
+        t = _u32(tokens).reshape(-1)
+        self.ctx.check(hip.wrk_occurrence_add(self.ctx.h, self.h, b, _ptr(t, _u32p), t.size, decay))
+
+    def back(self, b: int):
+        """(counts f32 [num_vocab], flags u32 [num_vocab]) of slot b."""
+        c = np.empty(self.num_vocab, np.float32)
+        f = np.empty(self.num_vocab, np.uint32)
+        self.ctx.check(hip.wrk_occurrence_back(self.ctx.h, self.h, b, _ptr(c, _f32p), _ptr(f, _u32p)))
+        return c, f
+
+    def load(self, b: int, counts=None, flags=None):
+        """Sets slot b; counts=None and flags=None reset it (zero counts, no flags)."""
+        if counts is None and flags is None:
+            self.ctx.check(hip.wrk_occurrence_load(self.ctx.h, self.h, b, None, None))
+            return
+        c = np.ascontiguousarray(counts, dtype=np.float32)
+        f = _u32(flags)
+        assert c.size == self.num_vocab and f.size == self.num_vocab
+        self.ctx.check(hip.wrk_occurrence_load(self.ctx.h, self.h, b, _ptr(c, _f32p), _ptr(f, _u32p)))
+
+    def close(self):
+        if self.h and self.ctx.h:
+            hip.wrk_occurrence_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Program:
@@ -853,6 +943,27 @@ class Runtime:
         fn, mdl = (hip.wrk_v6_generate_sample, self.model6) if self.model6 else (hip.wrk_v7_generate_sample, self.model)
         self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p),
                           _ptr(out, _u32p), _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
+        return (out, ms.value, logits) if want_logits else (out, ms.value)
+
+    def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
+                           frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1):
+        """As `generate_sample`, each draw made on the logits penalised with the sequence's slot of `occurrence` (ChatRWKV's
+        alpha_presence / alpha_frequency / token_ban), and the slot updated after every draw (count *= decay, then the drawn token's
+        weight added).  The first token of a call is not counted; the last drawn one is.  The table carries over between calls.
+        Scalars broadcast; seed=None: seed[b] = b.  last logits: the head output before penalties."""
+        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
+        ft = _u32(first_tokens)
+        B = ft.size
+        t, p = _per_row(temperature, B, np.float32), _per_row(top_p, B, np.float32)
+        sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
+        ap, af, g = _per_row(presence, B, np.float32), _per_row(frequency, B, np.float32), _per_row(decay, B, np.float32)
+        out = np.zeros((steps, B), np.uint32)
+        ms = C.c_float()
+        logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
+        fn, mdl = (hip.wrk_v6_generate_penalized, self.model6) if self.model6 else (hip.wrk_v7_generate_penalized, self.model)
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p),
+                          _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h, _ptr(out, _u32p),
+                          _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
 
     def state_back(self, batch: int) -> np.ndarray:
