@@ -5,6 +5,17 @@ un-vendored ``gguf`` package), so these are this repo's own, used only to
 *manufacture* legal GGUF blocks for fixtures and synthetic benchmarks.  They are
 simple min/max quantisers, not ggml's error-minimising search; any legal block
 is a valid input for the dequantisers under test.
+
+A round trip through these quantisers is NOT coverage of the formats.  Their output never contains:
+  * Q4_K / Q5_K: a sub-block scale or min of 0 (``_k4_scales`` clips to [1, 63]), a negative or zero ``d``, a negative ``dmin``, an f16
+    subnormal ``d`` (with N(0, 1/K) weights ``d`` is ~1e-3);
+  * Q6_K: a negative scale, 0 or -128 (clipped to [1, 127]), a negative ``d`` -- although the format stores signed bytes and other
+    quantisers use the sign;
+  * Q8_0: the code -128 (clipped to [-127, 127]), a negative ``d``;
+  * any kind: blocks of all-0xFF or all-zero quants, arbitrary ``scales[12]`` bytes (the 6-bit packing of sub-blocks 4..7 only sees what
+    the quantiser happens to emit).
+tests/blocks_ref.py writes such blocks directly; tests/test_blocks_ref.py pins the dequantisers on them and
+tests/test_gpu_matmul_edges.py the kernels.
 """
 from __future__ import annotations
 

@@ -142,9 +142,10 @@ def v7_tensor_plan(cfg: V7Config, seed: int):
 
 
 def make_v7_gguf(cfg: V7Config, seed: int = 42, mat: str = "Q4_K", head: str = "Q6_K", emb: str = "F16",
-                 lora: str = "F32", vec: str = "F32", mat_override: Dict[str, str] | None = None) -> bytes:
+                 lora: str = "F32", vec: str = "F32", mat_override: Dict[str, str] | None = None, reencode=None) -> bytes:
     """Build a complete GGUF file.  ``mat_override`` maps a substring of a tensor name to a type
-    (to make Q4_K_M-style mixtures)."""
+    (to make Q4_K_M-style mixtures).  ``reencode(name, type, raw) -> raw`` may rewrite a tensor's bytes after
+    quantisation (same type and size): the tests use it for encodings the quantisers never emit."""
     kinds = {"mat": mat, "head": head, "emb": emb, "lora": lora, "vec": vec}
     tensors: List[Tuple[str, List[int], str, np.ndarray]] = []
     for name, dims, kind, vals in v7_tensor_plan(cfg, seed):
@@ -153,7 +154,12 @@ def make_v7_gguf(cfg: V7Config, seed: int = 42, mat: str = "Q4_K", head: str = "
             for sub, t in mat_override.items():
                 if sub in name:
                     tn = t
-        tensors.append((name, dims, tn, QUANTIZE[tn](vals.astype(np.float32))))
+        raw = QUANTIZE[tn](vals.astype(np.float32))
+        if reencode is not None:
+            new = np.ascontiguousarray(reencode(name, tn, raw))
+            assert new.dtype == raw.dtype and new.shape == raw.shape, name
+            raw = new
+        tensors.append((name, dims, tn, raw))
     meta = [
         ("general.architecture", "str", "rwkv7"),
         ("general.alignment", "u32", 32),

@@ -434,7 +434,7 @@ int32_t wrk_op_matmul(wrk_ctx* ctx, const wrk_matrix* mat, const wrk_tensor* inp
     if (turbo && ntok >= 128 && (mat->kind == WRK_MAT_Q4_K || mat->kind == WRK_MAT_Q5_K)) {                             // the third-generation prefill tile wants its sum scratch
         // (+ the f32 partial tiles of a K-split launch: chunks of up to 256 tokens, at most one slice per 256-block)
         const size_t part = ntok <= 256 ? ntok * (size_t)mat->m * (mat->k >> 8) * 4 : 0;
-        const int32_t rs = wrk_ctx_reserve_gemm_scratch(ctx, ntok * (mat->k >> 5) * 4 + 1024 + part);
+        const int32_t rs = wrk_ctx_reserve_gemm_scratch(ctx, ntok * (mat->k >> 5) * 4 + ntok * 4 /* per-token factors of the sums */ + 1024 + part);
         if (rs != WRK_OK) return rs;
     }
     j.xsum = ctx->gemm_scratch; j.xsum_cap = ctx->gemm_scratch_cap;

@@ -37,6 +37,7 @@ struct T3Batch {
     GemmBatch g;
     const f16* sh[GEMM_MAX_JOBS];       // input sums, high parts: [token][K / 32]
     const f16* sl[GEMM_MAX_JOBS];       // low parts
+    const float* ts[GEMM_MAX_JOBS];     // per token: the factor its sums (and its column of the accumulators) carry, 1 or 2^-5
     // K split over blockIdx.z (round 3: chunks of 128 .. 256 tokens -- one or two token tiles -- leave most CUs without a workgroup otherwise):
     // slice z multiplies blocks [z bps, (z + 1) bps) and leaves an f32 partial tile [z][token][row]; t3_reduce_kernel adds them in slice order
     uint32_t bps, kslices;              // kslices == 1: the whole K, epilogue in this kernel
@@ -44,12 +45,15 @@ struct T3Batch {
     size_t poff[GEMM_MAX_JOBS];         // floats
 };
 
-// sums of the 32 inputs of every sub-block, f32, stored as hi + lo f16 (hi = round(s), lo = round(s - hi): 22 significant bits)
-__global__ void __launch_bounds__(256) xsum_kernel(const f16* __restrict__ x, uint32_t xs, uint32_t n, uint32_t nsub, f16* __restrict__ sh, f16* __restrict__ sl) {
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    if (idx >= n * nsub) return;
-    const uint32_t tok = idx / nsub, sub = idx - tok * nsub;
-    const f16x8* p = (const f16x8*)(x + (size_t)tok * xs + sub * 32u);
+// sums of the 32 inputs of every sub-block, f32, stored as hi + lo f16 (hi = round(s), lo = round(s - hi): 22 significant bits).
+// One wave per token.  32 same-signed inputs above ~2047 put |s| beyond the f16 range (hi = inf, lo = -inf, A_min . S = NaN where the
+// reference's f32 loop is finite): a token with such a sum stores ALL its sums times 2^-5 (32 inputs of at most 65504: exact, and inside
+// f16) and ts[token] = 2^-5, else ts = 1.  gemm_tile3_kernel multiplies that token's column of the accumulators by ts in front of the
+// min-term MFMAs and by 1 / ts behind them (both exact), only in waves that hold such a token: an unscaled token's arithmetic is bit for
+// bit what it was.  A scaled token resolves its sums to
+// 2^-20 absolutely instead of 2^-25: against a sub-block sum beyond 65504 in the same token, nothing.
+__device__ __forceinline__ float xsum32(const f16* __restrict__ x) {
+    const f16x8* p = (const f16x8*)x;
     const f16x2 one = {(f16)1.0f, (f16)1.0f};
     float s = 0.0f;
 #pragma unroll
@@ -60,9 +64,52 @@ __global__ void __launch_bounds__(256) xsum_kernel(const f16* __restrict__ x, ui
         s = __builtin_amdgcn_fdot2(__builtin_shufflevector(v, v, 4, 5), one, s, false);
         s = __builtin_amdgcn_fdot2(__builtin_shufflevector(v, v, 6, 7), one, s, false);
     }
-    const f16 h = (f16)s;
-    sh[idx] = h;
-    sl[idx] = (f16)(s - (float)h);
+    return s;
+}
+// WPT waves per token: 1 for rows up to 2048 elements (a sum per lane, four tokens per workgroup), 4 beyond (a token per workgroup: a chunk of
+// 128 tokens of K = 8192 is 128 workgroups with one sum per thread, not 32 with four)
+template <int WPT>
+__global__ void __launch_bounds__(256) xsum_kernel(const f16* __restrict__ x, uint32_t xs, uint32_t n, uint32_t nsub, f16* __restrict__ sh, f16* __restrict__ sl,
+                                                   float* __restrict__ ts) {
+    constexpr uint32_t TPT = 64u * WPT;     // threads per token
+    __shared__ float wmax[4];
+    const uint32_t tok = WPT == 4 ? blockIdx.x : blockIdx.x * 4u + (threadIdx.x >> 6), lane = WPT == 4 ? threadIdx.x : (threadIdx.x & 63u);
+    if (WPT == 1 && tok >= n) return;       // uniform over the wave (WPT == 4: the grid is n workgroups)
+    const f16* xr = x + (size_t)tok * xs;
+    float sv[8], mx = 0.0f;                 // rows of up to 512 WPT sums keep them in registers; longer ones are summed twice
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t sub = lane + TPT * i;
+        sv[i] = sub < nsub ? xsum32(xr + sub * 32u) : 0.0f;
+        mx = fmaxf(mx, fabsf(sv[i]));
+    }
+    for (uint32_t sub = lane + 8u * TPT; sub < nsub; sub += TPT) mx = fmaxf(mx, fabsf(xsum32(xr + sub * 32u)));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    if (WPT == 4) {
+        if ((threadIdx.x & 63u) == 0) wmax[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    }
+    const float sc = mx > 65504.0f ? 0.03125f : 1.0f;
+    if (lane == 0) ts[tok] = sc;
+    f16* oh = sh + (size_t)tok * nsub;
+    f16* ol = sl + (size_t)tok * nsub;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t sub = lane + TPT * i;
+        if (sub >= nsub) break;
+        const float s = sv[i] * sc;
+        const f16 h = (f16)s;
+        oh[sub] = h;
+        ol[sub] = (f16)(s - (float)h);
+    }
+    for (uint32_t sub = lane + 8u * TPT; sub < nsub; sub += TPT) {
+        const float s = xsum32(xr + sub * 32u) * sc;
+        const f16 h = (f16)s;
+        oh[sub] = h;
+        ol[sub] = (f16)(s - (float)h);
+    }
 }
 
 struct T3W { u32x2 q[4]; u32x4 sm; uint32_t dd; u32x2 qh; };        // qh: Q5_K high bits of this lane's 8 columns (bit s = sub-block s)
@@ -138,6 +185,7 @@ __global__ void __launch_bounds__(512) gemm_tile3_kernel(const T3Batch B) {
     const GemmParams& P = B.g.jobs[ji];
     const f16* __restrict__ SH = B.sh[ji];
     const f16* __restrict__ SL = B.sl[ji];
+    const float* __restrict__ TS = B.ts[ji];
     f16* As = (f16*)t3_smem;
     f16* Xs = As + 2 * 128 * T3_LR;
     float* Dd = (float*)(Xs + 2 * 128 * T3_LR);
@@ -195,6 +243,10 @@ __global__ void __launch_bounds__(512) gemm_tile3_kernel(const T3Batch B) {
     for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) { total[rt][tt] = (f32x4v){0.f, 0.f, 0.f, 0.f}; acc[rt][tt] = (f32x4v){0.f, 0.f, 0.f, 0.f}; }
+    // the factor of this lane's two tokens (xsum_kernel): 1, or 2^-5 for a token whose sub-block sums leave the f16 range
+    auto tok_scale = [&](int tt) { return TS[min(n0 + 32u * wx + 16u * tt + r, P.n - 1)]; };        // (re-read where used: no registers across the loop)
+    // uniform over the wave: any of its 32 tokens carries a factor (never, for inputs whose sub-block sums stay inside f16: the min term then runs as it always did)
+    const bool scaled = __builtin_amdgcn_ballot_w64(tok_scale(0) != 1.0f || tok_scale(1) != 1.0f) != 0;
     // input sums of this lane's tokens for the group of four blocks in flight (lane g: block 4 bq + g)
     f16x8 shf[2], slf[2];
     auto load_sums = [&](uint32_t bq) {
@@ -284,6 +336,14 @@ __global__ void __launch_bounds__(512) gemm_tile3_kernel(const T3Batch B) {
         tick(1);                // MFMA groups + the pieces of the next half
         if (hf == 0 && ((b & 3u) == 3u || b + 1 == b_end)) {
             // the min term of this group of (up to) four blocks: A_min (LDS, complete since the last barrier) x the input sums
+            // a token whose sums are stored times 2^-5: its column times 2^-5 around the MFMAs (both exact), so that A_min . (S 2^-5) lands in scale
+            if (scaled) {
+                const float f[2] = {tok_scale(0), tok_scale(1)};
+#pragma unroll
+                for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) total[rt][tt] *= f[tt];
+            }
 #pragma unroll
             for (int rt = 0; rt < 4; ++rt) {
                 const uint32_t ro = (64u * wy + 16u * rt + r) * T3_MR + 8u * g;
@@ -294,6 +354,13 @@ __global__ void __launch_bounds__(512) gemm_tile3_kernel(const T3Batch B) {
                     total[rt][tt] = mfma16(ah, slf[tt], total[rt][tt]);
                     total[rt][tt] = mfma16(al, shf[tt], total[rt][tt]);
                 }
+            }
+            if (scaled) {
+                const float f[2] = {1.0f / tok_scale(0), 1.0f / tok_scale(1)};                 // 1 or 32
+#pragma unroll
+                for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) total[rt][tt] *= f[tt];
             }
             load_sums((b >> 2) + 1);            // the next group's sums (clamped / zeroed beyond the end)
         }
@@ -396,15 +463,17 @@ int gemm_tile3_launch(hipStream_t s, const GemmBatch& T3, uint32_t row_tiles, ui
         int hit = -1;
         for (int u = 0; u < q; ++u)
             if (T3.jobs[u].x == P.x && T3.jobs[u].xs == P.xs && T3.jobs[u].k == P.k) { hit = u; break; }
-        if (hit >= 0) { B.sh[q] = B.sh[hit]; B.sl[q] = B.sl[hit]; continue; }
-        const size_t cnt = (size_t)n * (P.k >> 5), bytes = (cnt * 2 + 255) & ~(size_t)255;
-        if (used + 2 * bytes > xsum_cap) return -1;
+        if (hit >= 0) { B.sh[q] = B.sh[hit]; B.sl[q] = B.sl[hit]; B.ts[q] = B.ts[hit]; continue; }
+        const size_t cnt = (size_t)n * (P.k >> 5), bytes = (cnt * 2 + 255) & ~(size_t)255, tbytes = ((size_t)n * 4 + 255) & ~(size_t)255;
+        if (used + 2 * bytes + tbytes > xsum_cap) return -1;
         f16* sh = (f16*)((char*)xsum + used);
         f16* sl = (f16*)((char*)xsum + used + bytes);
-        used += 2 * bytes;
-        B.sh[q] = sh; B.sl[q] = sl;
+        float* ts = (float*)((char*)xsum + used + 2 * bytes);
+        used += 2 * bytes + tbytes;
+        B.sh[q] = sh; B.sl[q] = sl; B.ts[q] = ts;
         seen_x[nseen++] = P.x;
-        xsum_kernel<<<dim3((uint32_t)((cnt + 255) / 256)), 256, 0, s>>>(P.x, P.xs, n, P.k >> 5, sh, sl);
+        if ((P.k >> 5) > 64) xsum_kernel<4><<<dim3(n), 256, 0, s>>>(P.x, P.xs, n, P.k >> 5, sh, sl, ts);
+        else xsum_kernel<1><<<dim3((n + 3) / 4), 256, 0, s>>>(P.x, P.xs, n, P.k >> 5, sh, sl, ts);
     }
     (void)seen_x;
     // K split: one or two token tiles and fewer than ~160 workgroups -> slices of 4, 2 or 1 blocks (the first that fills the chip), all jobs of the

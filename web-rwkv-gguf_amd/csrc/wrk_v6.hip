@@ -82,7 +82,7 @@ int32_t wrk_v6_model::ensure_scratch(uint32_t T, uint32_t NH) {
         // prefill GEMM (wrk_gemm3.hip, Q4_K / Q5_K): sub-block input sums of the stacked tokens for the up to four distinct inputs of a launch (the
         // k, v, r, g projections read four shifted inputs) or the F-wide ffn vector, + the f32 partial tiles of K-split launches (chunks <= 256 tokens)
         const size_t widest = std::max<size_t>(4 * D, F);
-        const int32_t rs = wrk_ctx_reserve_gemm_scratch(ctx, (size_t)nt * (widest / 32) * 4 + 16 * 1024 + (size_t)256 * widest * 4 * 4);
+        const int32_t rs = wrk_ctx_reserve_gemm_scratch(ctx, (size_t)nt * (widest / 32) * 4 + 4 * ((size_t)nt * 4 + 256) /* per-token factors of the sums */ + 16 * 1024 + (size_t)256 * widest * 4 * 4);
         if (rs != WRK_OK) return rs;
     }
     char* b = (char*)scratch;

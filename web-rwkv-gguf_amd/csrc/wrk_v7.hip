@@ -66,7 +66,7 @@ int32_t wrk_v7_model::ensure_scratch(uint32_t T, uint32_t NH) {
         // the widest launch, r / k / v or the ffn key, in two to four slices)
         const size_t widest = std::max<size_t>(3 * D, F);
         const size_t part = (size_t)256 * widest * 4 * 4;
-        const int32_t rs = wrk_ctx_reserve_gemm_scratch(ctx, (size_t)nt * (widest / 32) * 4 + 8 * 1024 + part);
+        const int32_t rs = wrk_ctx_reserve_gemm_scratch(ctx, (size_t)nt * (widest / 32) * 4 + 3 * ((size_t)nt * 4 + 256) /* per-token factors of the sums */ + 8 * 1024 + part);
         if (rs != WRK_OK) return rs;
     }
     char* b = (char*)scratch;
