@@ -168,6 +168,19 @@ def test_v6_prefill_then_greedy_decode(ctx, name, weights, kw):
     rt.close()
 
 
+def test_v6_generate_rejects_a_state_of_another_model(ctx):
+    """Generation checks that the state belongs to the model, as wrk_v6_infer does: the state of a different-sized model is
+    E_ARG, not a walk over someone else's rows.  (The small model's state is the larger one.)"""
+    tiny = wrk.Runtime(ctx, wrk.GgufReader(synth.make_v6_gguf(synth.V6_CONFIGS["tiny"], 42)), num_batch=1, weights=wrk.WEIGHTS_INLINE)
+    small = wrk.Runtime(ctx, wrk.GgufReader(synth.make_v6_gguf(synth.V6_CONFIGS["small"], 42)), num_batch=1, weights=wrk.WEIGHTS_INLINE)
+    cs, ct = synth.V6_CONFIGS["small"], synth.V6_CONFIGS["tiny"]
+    assert (cs.num_layer, cs.num_emb) != (ct.num_layer, ct.num_emb) and cs.num_layer >= ct.num_layer and cs.num_emb >= ct.num_emb
+    first, out = np.array([1], np.uint32), np.zeros((4, 1), np.uint32)
+    rc = wrk.hip.wrk_v6_generate_greedy(ctx.h, tiny.model6, small.state, wrk._ptr(first, wrk._u32p), 1, 4, wrk._ptr(out, wrk._u32p), None, None, 1)
+    assert rc == wrk.E_ARG
+    tiny.close(); small.close()
+
+
 @pytest.mark.parametrize("B", [1, 3, 5])
 @pytest.mark.parametrize("mat", ["Q5_K", "Q8_0"])
 def test_v6_fused_decode_matches_op_by_op_and_oracle(ctx, B, mat):

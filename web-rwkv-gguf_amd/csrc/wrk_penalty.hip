@@ -10,7 +10,7 @@
 // 65 536-token row spreads over 64 workgroups instead of one CU.  The update has no atomics: the thread that owns element y also does
 // its decay, so the result is the same on every replay.  Rows with g == 1 touch only element y.
 #include "wrk_device.h"
-#include "wrk_v7.h"     // wrk_buf_write_raw
+#include "wrk_runner.h" // wrk_buf_write_raw
 
 #include <cmath>
 

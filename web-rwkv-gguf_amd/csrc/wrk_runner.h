@@ -1,0 +1,151 @@
+// Host-side driver shared by the RWKV-7 and RWKV-6 runners (wrk_v7.hip, wrk_v6.hip): matmul launches, job validation, the
+// frame state both models carry, cached step programs, job upload / read-back and the timed decode loop.  A runner keeps what is
+// its own -- the scratch layout, enqueue_ops / enqueue_fused_decode, its graph-key bits -- and hands these functions a callback
+// that enqueues its launches.
+#pragma once
+#include <atomic>
+#include <functional>
+#include <map>
+#include <tuple>
+#include <vector>
+
+#include "wrk_internal.h"
+#include "wrk_device.h"
+
+struct wrk_v7_state {       // recurrent state of either model family
+    // captured graphs bake the state's addresses and strides in: they are keyed by this id, never reused, rather than by
+    // the handle's address (a destroyed state's address can come back with another num_batch)
+    const void* uid = next_uid();
+    static const void* next_uid() { static std::atomic<uintptr_t> n{1}; return (const void*)(n.fetch_add(1) << 4); }
+    wrk_ctx* ctx = nullptr;
+    uint32_t num_layer = 0, num_emb = 0, head_size = 0, num_batch = 0;
+    float* data = nullptr;      // [L][B][S+2][D] f32 == L tensors [D, S+2, B] (v7.rs:514-527)
+    size_t layer_elems() const { return (size_t)num_batch * (head_size + 2) * num_emb; }
+    float* layer_ptr(uint32_t l) const { return data + layer_elems() * l; }
+};
+
+namespace wrk {
+// the part of a frame that jobs and decode steps go through, laid out by each model's ensure_scratch (base of V7Scratch / V6Scratch)
+struct FrameIo {
+    float* head_o;      // f32 logits [V, num_header]
+    uint32_t *cursors, *tokens, *headers, *argmax, *counter;
+};
+
+MatJob mat_job(const wrk_matrix* m, DTensor in, DTensor out, uint32_t act);
+
+// tokens <- argmax; history[counter][b] = argmax[b]; counter += 1   (one tiny kernel)
+void advance_tokens(hipStream_t s, const uint32_t* argmax, uint32_t* tokens, uint32_t* history, uint32_t* counter, uint32_t b);
+void argmax_finish(hipStream_t s, const float* pv, const uint32_t* pi, uint32_t nwg, uint32_t ntok, uint32_t* argmax, uint32_t* tokens,
+                   uint32_t* history, uint32_t* counter);
+
+// K0 / K4 of the fused decode paths (wrk_v7_fused.hip): layer norm + token shifts of stacked tokens, one workgroup per token
+struct LnMixParams {
+    const f16* src;             // [T][D] rows, or the embedding table when `ids` is set
+    const uint32_t* ids;        // optional row index per token (embedding gather / header rows)
+    const f16 *ln_w, *ln_b;
+    float eps;
+    uint32_t d, nmix;
+    const f16* mix[6];          // token-shift factors
+    f16* out[6];                // shifted outputs [T][D]
+    f16* ln_out;                // optional: LN output [T][D]
+    float* state_row;           // optional: shift state row, element (batch, c) at state_row[batch * state_stride + c]
+    size_t state_stride;
+    const uint32_t* cursors;    // batch id per token
+    uint32_t batch1;            // host-known batches: token t is batch batch1 - 1 + t (0: read the cursor)
+    uint32_t no_carry;          // 1: leave the shift state alone (a later kernel of the layer still reads it: RWKV-6)
+};
+int ln_mix(hipStream_t s, const LnMixParams& P, uint32_t T);      // -1: unsupported shape (D % 8, D > 8192, nmix not in {0, 1, 2, 6})
+}  // namespace wrk
+
+int32_t wrk_buf_write_raw(wrk_ctx* ctx, void* dst, const void* src, size_t bytes);
+
+// one matrix, or several matrices x the same token count in one MFMA launch per kernel family; per-matrix launches (MFMA GEMM, else
+// the matvec kernels) when the grouped GEMM declines
+int32_t wrk_mm(wrk_ctx* ctx, const wrk_matrix* m, DTensor in, DTensor out, uint32_t act);
+int32_t wrk_mm_group(wrk_ctx* ctx, wrk::MatJob* jobs, int n);
+
+// ------------------------------------------------------------------ one RnnJob (wrk_v*_infer, with `score` wrk_v*_score)
+struct wrk_job_args {
+    const uint32_t* tokens; const uint16_t* emb_rows;       // token ids, or gathered embedding rows
+    const uint32_t* cursors; uint32_t T;
+    const uint32_t* headers; uint32_t NH;
+    float* logits; uint32_t* argmax;                        // read back when set
+    bool score; const uint32_t* targets; float* logprob; uint32_t* rank;
+};
+struct wrk_job_shape { uint32_t nseq; bool one_token_each, contiguous, identity; };
+// validates cursors (batch | token << 8 | len << 24: ranges, one writer per state slice), token ids and header rows on the host -- a bad
+// index would fault the GPU -- and derives the job's shape.  contiguous: token t is batch (batch of token 0) + t
+int32_t wrk_job_check(wrk_ctx* ctx, const wrk_v7_state* st, const uint32_t* cursors, uint32_t T, const uint32_t* tokens_or_null, uint32_t V,
+                      const uint32_t* headers, uint32_t NH, wrk_job_shape* shape);
+int32_t wrk_score_check(wrk_ctx* ctx, const wrk_job_args& a, uint32_t V, const char* who);
+
+// ------------------------------------------------------------------ frame state of a model (base of wrk_v7_model / wrk_v6_model)
+struct wrk_frame_common {
+    wrk_ctx* ctx = nullptr;
+    void* scratch = nullptr;
+    uint32_t scratch_tokens = 0, scratch_headers = 0;
+    uint32_t* history = nullptr;    // generated tokens [steps][B] (device)
+    size_t history_cap = 0;
+    wrk::SampleParam* sample_par = nullptr;    // generate_sample: per-sequence sampler parameters, written before every call (not baked
+    uint32_t sample_par_cap = 0;                // into the step programs, which read them through this pointer)
+    wrk::PenaltyParam* pen_par = nullptr;      // generate_penalized: per-sequence occurrence rows and penalties, written before every call
+    float* pen_o = nullptr;                     // (the step programs read the table's pointers from here); pen_o: penalised logits [B][V]
+    uint32_t pen_cap = 0;
+    wrk_score_scratch score;                    // wrk_v*_score: targets / logprob / rank / slice partials of the header rows
+    uint32_t wkv_nseq = 0;          // sequences of the job being enqueued (0: unknown): picks the WKV chunk kernel (wrk::time_mix_v7 / _v6)
+
+    // b: tokens (generate: sequences | first sequence << 16); mode: the runner's mode and flag bits; nh: header rows
+    // (the analogue of the reference's cached RnnJob per RnnInfo, runtime/mod.rs:110-209)
+    struct GraphKey {
+        const void* state; uint32_t b, mode, nh = 0;
+        bool operator<(const GraphKey& o) const { return std::tie(state, b, mode, nh) < std::tie(o.state, o.b, o.mode, o.nh); }
+    };
+    std::map<GraphKey, wrk_program*> graphs;
+
+    // the ensure_* reallocate after a stream sync and drop the captured programs, which hold the old pointers; never inside a capture
+    void drop_graphs();
+    int32_t ensure_history(size_t n);
+    int32_t ensure_sample_params(uint32_t n);
+    int32_t ensure_penalty(uint32_t n, uint32_t num_vocab);
+    void release_common();          // destroy paths: programs, scratch and every buffer above
+};
+
+// the program cached under `key`, or -- captured from `enqueue`, which records this thread's launches -- a new one.  A program whose
+// enqueue failed is destroyed and the enqueue's code returned
+int32_t wrk_cached_program(wrk_ctx* ctx, std::map<wrk_frame_common::GraphKey, wrk_program*>& graphs, const wrk_frame_common::GraphKey& key,
+                           const std::function<int32_t()>& enqueue, wrk_program** prog);
+
+// upload half of a job: score targets (programs go when the slots grow), cursors, header rows, and token ids (gathered from `emb` into
+// `input` with `gather`) or the embedding rows.  Read-back half: logits / arg-max / logprob + rank, then the sync; nothing inside a capture
+int32_t wrk_job_upload(wrk_frame_common& f, wrk::FrameIo& io, void* input, const wrk_buf* emb, uint32_t D, const wrk_job_args& a, bool gather);
+int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t V, const wrk_job_args& a);
+
+// ------------------------------------------------------------------ generate_greedy / generate_sample / generate_penalized
+struct wrk_pick_args {      // the ABI's sampler (and with `penalized` penalty) arrays; generate_greedy passes none
+    const float *temperature, *top_p; const uint32_t* seed;
+    bool penalized = false;
+    const float *presence = nullptr, *frequency = nullptr, *decay = nullptr; wrk_occurrence* occ = nullptr;
+};
+struct wrk_pick_params {    // validated per-sequence rows; par / pen: nullptr for the arg-max / without penalties
+    std::vector<wrk::SampleParam> par_rows; std::vector<wrk::PenaltyParam> pen_rows;
+    const wrk::SampleParam* par = nullptr; const wrk::PenaltyParam* pen = nullptr;
+};
+int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args* pick, uint32_t B, uint32_t V, wrk_pick_params& out);
+int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, uint32_t num_emb, uint32_t num_layer, uint32_t V,
+                           const uint32_t* first_tokens, uint32_t B);
+// after the model's ensure_scratch: history / parameter buffers, then cursors, header rows, first tokens and parameters of sequences
+// [b0, b0 + B) and a zero step counter
+int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps,
+                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen);
+// after the layers and the head: pick each sequence's next token from head_o -- the arg-max, or with `sampled` the sampler (wrk_sample.hip)
+// on the frame's parameters at step *counter; `penalized` (implies `sampled`): from pen_o = head_o penalised with the occurrence rows of
+// pen_par, which then count the drawn tokens (wrk_penalty.hip) -- and advance tokens / history / counter
+int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized);
+
+// a pipeline of the timed replay: sequences [b0, b0 + nb) on their own frame; prog: its step program, or nullptr to enqueue eagerly
+struct wrk_lane { wrk::FrameIo* io; uint32_t* history; uint32_t b0, nb; wrk_program* prog; };
+// `steps` steps of every lane between two events: one lane on the submission stream (eagerly through `eager_step` without a program),
+// several on streams[g], joined through events[g].  Then tokens [steps][B] and last logits [B][V] come back
+int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const std::vector<hipStream_t>& streams, const std::vector<hipEvent_t>& events,
+                      uint32_t B, uint32_t V, uint32_t steps, const std::function<int32_t()>& eager_step, uint32_t* out_tokens, float* last_logits,
+                      float* elapsed_ms);

@@ -1,0 +1,283 @@
+// Host-side driver shared by the RWKV-7 and RWKV-6 runners (wrk_runner.h).  No kernels here.
+#include "wrk_runner.h"
+
+// ------------------------------------------------------------------ matmul launches
+wrk::MatJob wrk::mat_job(const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
+    wrk::MatJob j{m->data, m->aux, m->kind, m->flags, m->k, m->m, (uint32_t)m->row_bytes, in, out, act, 0};
+    j.scale = m->out_scale;
+    return j;
+}
+
+int32_t wrk_mm(wrk_ctx* ctx, const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
+    wrk::MatJob j = wrk::mat_job(m, in, out, act);
+    return wrk_mm_group(ctx, &j, 1);
+}
+
+int32_t wrk_mm_group(wrk_ctx* ctx, wrk::MatJob* jobs, int n) {
+    hipStream_t q = ctx->op_stream();
+    const bool gemm = jobs[0].in.shape[1] * jobs[0].in.shape[2] >= wrk::gemm_min_tokens();
+    // scratch of the third-generation prefill tile: a launch reads it from its first job, and every job may lead a launch of its own below
+    for (int i = 0; i < n; ++i) { jobs[i].xsum = ctx->gemm_scratch; jobs[i].xsum_cap = ctx->gemm_scratch_cap; }
+    if (gemm && wrk::matmul_mfma_multi(q, jobs, n, ctx->num_cu) == 0) return WRK_OK;
+    for (int i = 0; i < n; ++i) {
+        int rc = gemm ? wrk::matmul_mfma(q, jobs[i], ctx->num_cu) : -2;
+        if (rc == -2) rc = wrk::matvec(q, &jobs[i], 1, ctx->num_cu);
+        if (rc != 0) return wrk_fail(ctx, WRK_E_ARG, "matmul launch rejected (K=%u M=%u rc=%d)", jobs[i].k, jobs[i].m, rc);
+    }
+    return WRK_OK;
+}
+
+int32_t wrk_buf_write_raw(wrk_ctx* ctx, void* dst, const void* src, size_t bytes) {
+    wrk_buf tmp{ctx, dst, bytes, {1}};
+    return wrk_buf_write(ctx, &tmp, 0, src, bytes);
+}
+
+// ------------------------------------------------------------------ job validation
+int32_t wrk_job_check(wrk_ctx* ctx, const wrk_v7_state* st, const uint32_t* cursors, uint32_t T, const uint32_t* tokens, uint32_t V,
+                      const uint32_t* headers, uint32_t NH, wrk_job_shape* shape) {
+    wrk_job_shape sh{0, true, true, NH == T};
+    std::vector<uint8_t> seen(256, 0);
+    for (uint32_t t = 0; t < T; ++t) {
+        const uint32_t c = cursors[t], b = c & 0xff, tok = (c >> 8) & 0xffff, len = c >> 24;
+        WRK_ARG(ctx, b < st->num_batch, "cursor %u: batch %u >= %u", t, b, st->num_batch);
+        WRK_ARG(ctx, len >= 1 && tok <= t && t < tok + len && tok + len <= T, "cursor %u: bad range (token %u len %u)", t, tok, len);
+        if (tok == t) {
+            ++sh.nseq;
+            WRK_ARG(ctx, !seen[b], "cursor %u: batch %u appears in two chunks of one dispatch", t, b);   // two writers of one state slice
+            seen[b] = 1;
+        }
+        if (len != 1) sh.one_token_each = false;
+        if (tokens) WRK_ARG(ctx, tokens[t] < V, "token %u: id %u >= vocab %u", t, tokens[t], V);
+        // batches of consecutive tokens are consecutive: the few-sequence decode kernels address per-sequence state rows by a stride
+        if (b != (cursors[0] & 0xff) + t) sh.contiguous = false;
+    }
+    for (uint32_t h = 0; h < NH; ++h) {
+        WRK_ARG(ctx, headers[h] < T, "header %u: row %u >= %u tokens", h, headers[h], T);
+        if (headers[h] != h) sh.identity = false;
+    }
+    *shape = sh;
+    return WRK_OK;
+}
+
+int32_t wrk_score_check(wrk_ctx* ctx, const wrk_job_args& a, uint32_t V, const char* who) {
+    if (!a.score) return WRK_OK;
+    WRK_ARG(ctx, !ctx->capturing_here(), "%s is blocking: not inside a capture", who);
+    WRK_ARG(ctx, a.NH == 0 || (a.logprob && a.rank), "logprob and rank are required");
+    return wrk_score_check_targets(ctx, a.targets, a.NH, V);
+}
+
+// ------------------------------------------------------------------ frame state
+void wrk_frame_common::drop_graphs() {
+    for (auto& kv : graphs) wrk_program_destroy(kv.second);
+    graphs.clear();
+}
+
+int32_t wrk_frame_common::ensure_history(size_t n) {
+    if (n <= history_cap && history) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drop_graphs();
+    if (history) hipFree(history);
+    history = nullptr;
+    WRK_HIP(ctx, hipMalloc((void**)&history, n * 4 + 256));
+    history_cap = n;
+    return WRK_OK;
+}
+
+int32_t wrk_frame_common::ensure_sample_params(uint32_t n) {
+    if (n <= sample_par_cap && sample_par) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drop_graphs();
+    if (sample_par) hipFree(sample_par);
+    sample_par = nullptr;
+    WRK_HIP(ctx, hipMalloc((void**)&sample_par, (size_t)n * sizeof(wrk::SampleParam)));
+    sample_par_cap = n;
+    return WRK_OK;
+}
+
+int32_t wrk_frame_common::ensure_penalty(uint32_t n, uint32_t num_vocab) {
+    if (n <= pen_cap && pen_par && pen_o) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drop_graphs();
+    if (pen_par) hipFree(pen_par);
+    if (pen_o) hipFree(pen_o);
+    pen_par = nullptr;
+    pen_o = nullptr;
+    pen_cap = 0;
+    WRK_HIP(ctx, hipMalloc((void**)&pen_par, (size_t)n * sizeof(wrk::PenaltyParam)));
+    WRK_HIP(ctx, hipMalloc((void**)&pen_o, (size_t)n * num_vocab * 4));
+    pen_cap = n;
+    return WRK_OK;
+}
+
+void wrk_frame_common::release_common() {
+    drop_graphs();
+    void* bufs[] = {scratch, history, sample_par, pen_par, pen_o};
+    for (void* p : bufs) if (p) hipFree(p);
+    scratch = nullptr; history = nullptr; sample_par = nullptr; pen_par = nullptr; pen_o = nullptr;
+    score.release();
+}
+
+int32_t wrk_cached_program(wrk_ctx* ctx, std::map<wrk_frame_common::GraphKey, wrk_program*>& graphs, const wrk_frame_common::GraphKey& key,
+                           const std::function<int32_t()>& enqueue, wrk_program** prog) {
+    auto it = graphs.find(key);
+    if (it != graphs.end()) { *prog = it->second; return WRK_OK; }
+    int32_t rc = wrk_capture_begin(ctx);
+    if (rc != WRK_OK) return rc;
+    rc = enqueue();
+    wrk_program* p = nullptr;
+    const int32_t rc2 = wrk_capture_end(ctx, &p);
+    if (rc != WRK_OK) { if (p) wrk_program_destroy(p); return rc; }
+    if (rc2 != WRK_OK) return rc2;
+    graphs[key] = p;
+    *prog = p;
+    return WRK_OK;
+}
+
+// ------------------------------------------------------------------ job upload / read-back
+int32_t wrk_job_upload(wrk_frame_common& f, wrk::FrameIo& io, void* input, const wrk_buf* emb, uint32_t D, const wrk_job_args& a, bool gather) {
+    wrk_ctx* ctx = f.ctx;
+    int32_t rc = WRK_OK;
+    if (a.score && a.NH) {
+        bool grown = false;
+        rc = f.score.ensure(ctx, a.NH, &grown);
+        if (rc != WRK_OK) return rc;
+        if (grown) f.drop_graphs();            // captured score jobs hold the old slots
+        rc = wrk_buf_write_raw(ctx, f.score.targets, a.targets, (size_t)a.NH * 4);
+    }
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.cursors, a.cursors, (size_t)a.T * 4);
+    if (rc == WRK_OK && a.NH) rc = wrk_buf_write_raw(ctx, io.headers, a.headers, (size_t)a.NH * 4);
+    if (rc != WRK_OK) return rc;
+    if (!a.tokens) return wrk_buf_write_raw(ctx, input, a.emb_rows, (size_t)a.T * D * 2);
+    rc = wrk_buf_write_raw(ctx, io.tokens, a.tokens, (size_t)a.T * 4);
+    if (rc == WRK_OK && gather) wrk::gather_rows_f16(ctx->op_stream(), emb->ptr, io.tokens, input, D, a.T);
+    return rc;
+}
+
+int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t V, const wrk_job_args& a) {
+    wrk_ctx* ctx = f.ctx;
+    WRK_LAUNCH_CHECK(ctx);
+    if (ctx->capturing_here()) return WRK_OK;   // recorded into the caller's program: results exist after it has been launched
+    if (a.NH && a.logits) WRK_HIP(ctx, hipMemcpyAsync(a.logits, io.head_o, (size_t)a.NH * V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (a.NH && a.argmax) WRK_HIP(ctx, hipMemcpyAsync(a.argmax, io.argmax, (size_t)a.NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (a.NH && a.score) {
+        WRK_HIP(ctx, hipMemcpyAsync(a.logprob, f.score.logprob, (size_t)a.NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(a.rank, f.score.rank, (size_t)a.NH * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+// ------------------------------------------------------------------ decode loop
+int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args* pick, uint32_t B, uint32_t V, wrk_pick_params& out) {
+    if (!pick) return WRK_OK;
+    int32_t rc = wrk_sample_pack(ctx, pick->temperature, pick->top_p, pick->seed, B, out.par_rows);
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, B >= 1, "num_batch 0");
+    out.par = out.par_rows.data();
+    if (!pick->penalized) return WRK_OK;
+    WRK_ARG(ctx, pick->decay, "decay array required");
+    rc = wrk_penalty_pack(ctx, pick->occ, 0, B, V, pick->presence, pick->frequency, pick->decay, out.pen_rows);
+    out.pen = out.pen_rows.data();
+    return rc;
+}
+
+int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, uint32_t num_emb, uint32_t num_layer, uint32_t V,
+                           const uint32_t* first_tokens, uint32_t B) {
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    WRK_ARG(ctx, has_emb, "generate_greedy needs the device embedding table");
+    WRK_ARG(ctx, B >= 1 && B <= st->num_batch, "num_batch %u exceeds the state's %u", B, st->num_batch);
+    WRK_ARG(ctx, st->num_emb == num_emb && st->num_layer == num_layer, "state does not belong to this model");
+    for (uint32_t b = 0; b < B; ++b) WRK_ARG(ctx, first_tokens[b] < V, "first token %u out of vocab", first_tokens[b]);
+    return WRK_OK;
+}
+
+int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps,
+                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen) {
+    wrk_ctx* ctx = f.ctx;
+    int32_t rc = f.ensure_history((size_t)steps * B);
+    if (rc == WRK_OK && par) rc = f.ensure_sample_params(B);
+    if (rc == WRK_OK && pen) rc = f.ensure_penalty(B, V);
+    if (rc != WRK_OK) return rc;
+    std::vector<uint32_t> cur(B), hdr(B);
+    for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
+    rc = wrk_buf_write_raw(ctx, io.cursors, cur.data(), (size_t)B * 4);
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.headers, hdr.data(), (size_t)B * 4);
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.tokens, first_tokens, (size_t)B * 4);
+    if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, f.sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
+    if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, f.pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
+    if (rc != WRK_OK) return rc;
+    WRK_HIP(ctx, hipMemsetAsync(io.counter, 0, 4, ctx->stream));
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized) {
+    hipStream_t q = f.ctx->op_stream();
+    const float* logits = io.head_o;
+    if (penalized) {
+        wrk::penalize_rows(q, io.head_o, V, V, B, f.pen_par, f.pen_o, V);
+        logits = f.pen_o;
+    }
+    // the sampler only reads the counter: rows run in different workgroups, so advance_tokens moves it after all of them
+    if (!sampled) wrk::argmax_rows(q, io.head_o, V, V, B, io.argmax);
+    else if (wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax) != 0)
+        return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    if (penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
+    wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);
+    return WRK_OK;
+}
+
+int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const std::vector<hipStream_t>& streams, const std::vector<hipEvent_t>& events,
+                      uint32_t B, uint32_t V, uint32_t steps, const std::function<int32_t()>& eager_step, uint32_t* out_tokens, float* last_logits,
+                      float* elapsed_ms) {
+    const size_t groups = lanes.size();
+    // every early return below leaves through this guard: the timing events are destroyed and, after an error, the lane streams are
+    // drained (a lane's queued step programs must not outlive a frame that the next call may reallocate)
+    struct Guard {
+        wrk_ctx* ctx; const std::vector<hipStream_t>& streams; hipEvent_t e0 = nullptr, e1 = nullptr; bool ok = false;
+        ~Guard() {
+            if (!ok) { for (hipStream_t ls : streams) hipStreamSynchronize(ls); hipStreamSynchronize(ctx->stream); }
+            if (e0) hipEventDestroy(e0);
+            if (e1) hipEventDestroy(e1);
+        }
+    } guard{ctx, streams};
+    WRK_HIP(ctx, hipEventCreate(&guard.e0));
+    WRK_HIP(ctx, hipEventCreate(&guard.e1));
+    hipEvent_t e0 = guard.e0, e1 = guard.e1;
+    WRK_HIP(ctx, hipEventRecord(e0, ctx->stream));
+    if (groups == 1) {
+        for (uint32_t i = 0; i < steps; ++i) {
+            if (lanes[0].prog) WRK_HIP(ctx, hipGraphLaunch(lanes[0].prog->exec, ctx->stream));
+            else {
+                const int32_t rc = eager_step();
+                if (rc != WRK_OK) return rc;
+            }
+        }
+    } else {
+        // every lane replays its own step program on its own stream; the lanes start together behind e0 and the submission
+        // stream joins them all before e1
+        for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipStreamWaitEvent(streams[g], e0, 0));
+        for (uint32_t i = 0; i < steps; ++i)
+            for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipGraphLaunch(lanes[g].prog->exec, streams[g]));
+        for (size_t g = 0; g < groups; ++g) {
+            WRK_HIP(ctx, hipEventRecord(events[g], streams[g]));
+            WRK_HIP(ctx, hipStreamWaitEvent(ctx->stream, events[g], 0));
+        }
+    }
+    WRK_HIP(ctx, hipEventRecord(e1, ctx->stream));
+    WRK_HIP(ctx, hipEventSynchronize(e1));
+    float ms = 0.0f;
+    WRK_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+    if (elapsed_ms) *elapsed_ms = ms;
+    for (const wrk_lane& ln : lanes) {
+        if (out_tokens) {
+            if (groups == 1) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.history, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
+            else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)B * 4, ln.history, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
+                                               hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits + (size_t)ln.b0 * V, ln.io->head_o, (size_t)ln.nb * V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    guard.ok = true;
+    return WRK_OK;
+}

@@ -3,41 +3,25 @@
 // matrices through the inline-dequant matvec / MFMA GEMM.  Buffer dtypes follow Runtime<f16> (v6.rs:265-300):
 // att_k, att_v, att_r and time_decay are f32, everything else f16.
 #include "wrk_internal.h"
-#include "wrk_v7.h"
+#include "wrk_runner.h"
 
 #define LOCK(ctx) std::lock_guard<std::recursive_mutex> _lk((ctx)->mu)
 
 static constexpr float LN_EPS = 1.0e-5f;    // v6.rs:46
 static constexpr float GN_EPS = 64.0e-5f;   // v6.rs:47
 
-struct V6Scratch {
+struct V6Scratch : wrk::FrameIo {
     void *input, *x, *aux_x, *att_x, *att_xx, *att_sx, *att_w, *att_g, *att_o, *tmx, *tmt, *tm, *ffn_x, *ffn_kx, *ffn_rx, *ffn_k, *ffn_v, *ffn_r, *head_x;
-    float *att_k, *att_v, *att_r, *time_decay, *head_o;
-    uint32_t *cursors, *tokens, *headers, *argmax, *counter;
+    float *att_k, *att_v, *att_r, *time_decay;
     float* ks_part; uint32_t* ks_cnt; size_t ks_part_cap; uint32_t ks_cnt_cap;     // K-sliced GEMM scratch (2 .. 32 sequences), see MatJob
 };
 
-struct wrk_v6_model {
-    wrk_ctx* ctx = nullptr;
+struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64)
     wrk_v6_model_desc d{};
     std::vector<wrk_v6_layer_desc> layers;
-    void* scratch = nullptr;
-    uint32_t scratch_tokens = 0, scratch_headers = 0;
     V6Scratch s{};
-    uint32_t* history = nullptr;
-    size_t history_cap = 0;
-    wrk::SampleParam* sample_par = nullptr;    // generate_sample's per-sequence parameters (written per call, read by the step program)
-    uint32_t sample_par_cap = 0;
-    wrk::PenaltyParam* pen_par = nullptr;      // generate_penalized: occurrence rows and penalties (written per call) and the penalised
-    float* pen_o = nullptr;                     // logits [B][V] the sampler draws from
-    uint32_t pen_cap = 0;
-    wrk_score_scratch score;    // wrk_v6_score: targets / logprob / rank / slice partials of the header rows (read by no captured program)
-    uint32_t wkv_nseq = 0;      // sequences of the job being enqueued (0: unknown): picks the WKV chunk kernel (wrk::time_mix_v6)
-    std::map<std::tuple<const void*, uint32_t, uint32_t>, wrk_program*> graphs;      // (state, sequences, mode)
 
-    void drop_graphs() { for (auto& kv : graphs) wrk_program_destroy(kv.second); graphs.clear(); }
     int32_t ensure_scratch(uint32_t T, uint32_t NH);
-    int32_t ensure_history(size_t n);
     int32_t enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity, bool merged = false);
     int32_t enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity, uint32_t batch0);
 };
@@ -99,47 +83,9 @@ int32_t wrk_v6_model::ensure_scratch(uint32_t T, uint32_t NH) {
     return WRK_OK;
 }
 
-int32_t wrk_v6_model::ensure_history(size_t n) {
-    if (n <= history_cap && history) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();
-    if (history) hipFree(history);
-    history = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&history, n * 4 + 256));
-    history_cap = n;
-    return WRK_OK;
-}
-
-static int32_t mm6(wrk_ctx* ctx, const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
-    wrk::MatJob j{m->data, m->aux, m->kind, m->flags, m->k, m->m, (uint32_t)m->row_bytes, in, out, act, 0};
-    j.scale = m->out_scale;
-    j.xsum = ctx->gemm_scratch; j.xsum_cap = ctx->gemm_scratch_cap;        // third-generation prefill tile (Q4_K / Q5_K chunks)
-    int rc = -2;
-    if (in.shape[1] * in.shape[2] >= wrk::gemm_min_tokens()) rc = wrk::matmul_mfma(ctx->op_stream(), j, ctx->num_cu);
-    if (rc == -2) rc = wrk::matvec(ctx->op_stream(), &j, 1, ctx->num_cu);
-    if (rc != 0) return wrk_fail(ctx, WRK_E_ARG, "matmul launch rejected (K=%u M=%u rc=%d)", m->k, m->m, rc);
-    return WRK_OK;
-}
-#define MM(...) do { int32_t _r = mm6(ctx, __VA_ARGS__); if (_r != WRK_OK) return _r; } while (0)
-static wrk::MatJob job6m(const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
-    wrk::MatJob j{m->data, m->aux, m->kind, m->flags, m->k, m->m, (uint32_t)m->row_bytes, in, out, act, 0};
-    j.scale = m->out_scale;
-    return j;
-}
-// several matrices x the same token count in one MFMA launch per kernel family; per-matrix launches when the GEMM declines
-static int32_t mm6_group(wrk_ctx* ctx, wrk::MatJob* jobs, int n) {
-    const uint32_t T = jobs[0].in.shape[1] * jobs[0].in.shape[2];
-    for (int i = 0; i < n; ++i) { jobs[i].xsum = ctx->gemm_scratch; jobs[i].xsum_cap = ctx->gemm_scratch_cap; }
-    if (T >= wrk::gemm_min_tokens() && wrk::matmul_mfma_multi(ctx->op_stream(), jobs, n, ctx->num_cu) == 0) return WRK_OK;
-    for (int i = 0; i < n; ++i) {
-        int rc = -2;
-        if (T >= wrk::gemm_min_tokens()) rc = wrk::matmul_mfma(ctx->op_stream(), jobs[i], ctx->num_cu);
-        if (rc == -2) rc = wrk::matvec(ctx->op_stream(), &jobs[i], 1, ctx->num_cu);
-        if (rc != 0) return wrk_fail(ctx, WRK_E_ARG, "matmul launch rejected (K=%u M=%u rc=%d)", jobs[i].k, jobs[i].m, rc);
-    }
-    return WRK_OK;
-}
-#define MMG(jobs, n) do { int32_t _r = mm6_group(ctx, jobs, n); if (_r != WRK_OK) return _r; } while (0)
+using wrk::mat_job;
+#define MM(...) do { int32_t _r = wrk_mm(ctx, __VA_ARGS__); if (_r != WRK_OK) return _r; } while (0)
+#define MMG(jobs, n) do { int32_t _r = wrk_mm_group(ctx, jobs, n); if (_r != WRK_OK) return _r; } while (0)
 
 int32_t wrk_v6_model::enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity, bool merged) {
     hipStream_t q = ctx->op_stream();
@@ -176,7 +122,7 @@ int32_t wrk_v6_model::enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, boo
         wrk::transpose(q, make_dense(s.tmx, WRK_F16, R, 5, T), make_dense(s.tmt, WRK_F16, R, T, 5));
         if (merged) {
             wrk::MatJob jw[5];
-            for (uint32_t i = 0; i < 5; ++i) jw[i] = job6m(L.time_mix_w2[i], slice(make_dense(s.tmt, WRK_F16, R, T, 5), i), slice(tm5, i), WRK_ACT_NONE);
+            for (uint32_t i = 0; i < 5; ++i) jw[i] = mat_job(L.time_mix_w2[i], slice(make_dense(s.tmt, WRK_F16, R, T, 5), i), slice(tm5, i), WRK_ACT_NONE);
             MMG(jw, 5);
         } else
             for (uint32_t i = 0; i < 5; ++i)                                                              // batched [R, D, 5] matmul
@@ -184,9 +130,9 @@ int32_t wrk_v6_model::enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, boo
         wrk::binary(q, 0, make_dense(L.time_mix->ptr, WRK_F16, D, 1, 5), tm5, 0, 0, 0);                    // add(time_mix, buffer.time_mix)
         wrk::token_shift(q, s.cursors, tm5, st_row0, att_x, sx5, 1);
         if (merged) {
-            wrk::MatJob jp[5] = {job6m(L.w_k, slice(sx5, 1), att_k, WRK_ACT_NONE), job6m(L.w_v, slice(sx5, 2), att_v, WRK_ACT_NONE),
-                                 job6m(L.w_r, slice(sx5, 3), att_r, WRK_ACT_NONE), job6m(L.w_g, slice(sx5, 4), att_g, WRK_ACT_NONE),
-                                 job6m(L.time_decay_w1, slice(sx5, 0), att_w, WRK_ACT_TANH)};
+            wrk::MatJob jp[5] = {mat_job(L.w_k, slice(sx5, 1), att_k, WRK_ACT_NONE), mat_job(L.w_v, slice(sx5, 2), att_v, WRK_ACT_NONE),
+                                 mat_job(L.w_r, slice(sx5, 3), att_r, WRK_ACT_NONE), mat_job(L.w_g, slice(sx5, 4), att_g, WRK_ACT_NONE),
+                                 mat_job(L.time_decay_w1, slice(sx5, 0), att_w, WRK_ACT_TANH)};
             MMG(jp, 5);
         } else {
             MM(L.w_k, slice(sx5, 1), att_k, WRK_ACT_NONE);
@@ -205,14 +151,14 @@ int32_t wrk_v6_model::enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, boo
         wrk::blit(q, aux_x, att_x);
         wrk::binary(q, 1, att_g, att_x, WRK_ACT_SILU, 0, 0);                                              // mul_activate(att_g Silu, att_x)
         if (merged) {
-            wrk::MatJob jo = job6m(L.w_o, att_x, x, WRK_ACT_NONE);       // x = round(W_o att_x) + x
+            wrk::MatJob jo = mat_job(L.w_o, att_x, x, WRK_ACT_NONE);       // x = round(W_o att_x) + x
             jo.has_res = 1;
             jo.res = x;
             MMG(&jo, 1);
             wrk::layer_norm_from(q, L.ln2_w->ptr, L.ln2_b->ptr, x, ffn_x, LN_EPS);
             const DTensor fm[2] = {bvec(L.ffn_mix_k), bvec(L.ffn_mix_r)}, fo[2] = {ffn_kx, ffn_rx};
             wrk::token_shift_multi(q, s.cursors, fm, fo, 2, st_ffn, ffn_x, 1);
-            wrk::MatJob jf[2] = {job6m(L.ffn_w_k, ffn_kx, ffn_k, WRK_ACT_SQUARED_RELU), job6m(L.ffn_w_r, ffn_rx, ffn_r, WRK_ACT_NONE)};
+            wrk::MatJob jf[2] = {mat_job(L.ffn_w_k, ffn_kx, ffn_k, WRK_ACT_SQUARED_RELU), mat_job(L.ffn_w_r, ffn_rx, ffn_r, WRK_ACT_NONE)};
             MMG(jf, 2);
             MM(L.ffn_w_v, ffn_k, ffn_v, WRK_ACT_NONE);
         } else {
@@ -400,12 +346,6 @@ __global__ void __launch_bounds__(256) v6_head_kernel(const V6HeadParams P) {
 
 }  // namespace wrk
 
-static wrk::MatJob job6(const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
-    wrk::MatJob j{m->data, m->aux, m->kind, m->flags, m->k, m->m, (uint32_t)m->row_bytes, in, out, act, 0};
-    j.scale = m->out_scale;
-    return j;
-}
-
 // One decode step for T stacked tokens, each its own sequence.  Returns WRK_E_UNSUPPORTED (without launching anything)
 // when the model's shapes are outside the fused kernels' range; callers then use enqueue_ops.
 int32_t wrk_v6_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity, uint32_t batch0) {
@@ -449,15 +389,15 @@ int32_t wrk_v6_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         // per layer: can the two LN prologues / the gated epilogue ride the register-input matvec kernels?
         bool single = (T == 1) && D <= 4096;
         if (single) {
-            wrk::MatJob a = job6(L.time_mix_w1, vec(s.x), vec(s.tmx, 5 * R), 0); a.pro = 1;
-            wrk::MatJob b[2] = {job6(L.ffn_w_k, vec(s.x), vec(s.ffn_k, F), 0), job6(L.ffn_w_r, vec(s.x), vec(s.ffn_r), 0)};
+            wrk::MatJob a = mat_job(L.time_mix_w1, vec(s.x), vec(s.tmx, 5 * R), 0); a.pro = 1;
+            wrk::MatJob b[2] = {mat_job(L.ffn_w_k, vec(s.x), vec(s.ffn_k, F), 0), mat_job(L.ffn_w_r, vec(s.x), vec(s.ffn_r), 0)};
             b[0].pro = b[1].pro = 1;
-            wrk::MatJob c = job6(L.ffn_w_v, vec(s.ffn_k, F), vec(s.x), 0); c.gate = s.ffn_r; c.carry_dst = (float*)s.x;
+            wrk::MatJob c = mat_job(L.ffn_w_v, vec(s.ffn_k, F), vec(s.x), 0); c.gate = s.ffn_r; c.carry_dst = (float*)s.x;
             single = wrk::matvec(q, &a, 1, ctx->num_cu, true) == 0 && wrk::matvec_grouped(q, b, 2, ctx->num_cu, true) == 0 &&
                      wrk::matvec(q, &c, 1, ctx->num_cu, true) == 0;
         }
         {   // K1
-            wrk::MatJob j = job6(L.time_mix_w1, vec(s.att_xx), vec(s.tmx, 5 * R), WRK_ACT_TANH);
+            wrk::MatJob j = mat_job(L.time_mix_w1, vec(s.att_xx), vec(s.tmx, 5 * R), WRK_ACT_TANH);
             if (single) {
                 j.in = vec(s.x);
                 j.pro = 1; j.pro_eps = LN_EPS; j.ln_w = L.ln1_w->ptr; j.ln_b = L.ln1_b->ptr; j.mixw = L.time_mix_x->ptr; j.prev = row0;
@@ -481,11 +421,11 @@ int32_t wrk_v6_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         }
         {   // K3: order of the shifted inputs is w, k, v, r, g (v6.rs:1054-1071)
             f16* sx = (f16*)s.att_sx;
-            wrk::MatJob jobs[5] = {job6(L.w_k, vec(sx + 1 * sxs), vec(s.att_k, 0, WRK_F32), WRK_ACT_NONE),
-                                   job6(L.w_v, vec(sx + 2 * sxs), vec(s.att_v, 0, WRK_F32), WRK_ACT_NONE),
-                                   job6(L.w_r, vec(sx + 3 * sxs), vec(s.att_r, 0, WRK_F32), WRK_ACT_NONE),
-                                   job6(L.w_g, vec(sx + 4 * sxs), vec(s.att_g), WRK_ACT_NONE),
-                                   job6(L.time_decay_w1, vec(sx + 0 * sxs), vec(s.att_w, W), WRK_ACT_TANH)};
+            wrk::MatJob jobs[5] = {mat_job(L.w_k, vec(sx + 1 * sxs), vec(s.att_k, 0, WRK_F32), WRK_ACT_NONE),
+                                   mat_job(L.w_v, vec(sx + 2 * sxs), vec(s.att_v, 0, WRK_F32), WRK_ACT_NONE),
+                                   mat_job(L.w_r, vec(sx + 3 * sxs), vec(s.att_r, 0, WRK_F32), WRK_ACT_NONE),
+                                   mat_job(L.w_g, vec(sx + 4 * sxs), vec(s.att_g), WRK_ACT_NONE),
+                                   mat_job(L.time_decay_w1, vec(sx + 0 * sxs), vec(s.att_w, W), WRK_ACT_TANH)};
             if (run_jobs(jobs, 5) != 0) return wrk_fail(ctx, WRK_E_ARG, "fused V6 K3 rejected");
         }
         {   // K4
@@ -499,12 +439,12 @@ int32_t wrk_v6_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
             wrk::v6_head_kernel<<<dim3(H, T), 256, 0, q>>>(P);
         }
         {   // K5: x += W_o . att
-            wrk::MatJob j = job6(L.w_o, vec(s.aux_x), vec(s.x), WRK_ACT_NONE);
+            wrk::MatJob j = mat_job(L.w_o, vec(s.aux_x), vec(s.x), WRK_ACT_NONE);
             j.has_res = 1; j.res = vec(s.x);
             if (run_jobs(&j, 1) != 0) return wrk_fail(ctx, WRK_E_ARG, "fused V6 K5 rejected");
         }
         {   // K6
-            wrk::MatJob jobs[2] = {job6(L.ffn_w_k, vec(s.ffn_kx), vec(s.ffn_k, F), WRK_ACT_SQUARED_RELU), job6(L.ffn_w_r, vec(s.ffn_rx), vec(s.ffn_r), WRK_ACT_NONE)};
+            wrk::MatJob jobs[2] = {mat_job(L.ffn_w_k, vec(s.ffn_kx), vec(s.ffn_k, F), WRK_ACT_SQUARED_RELU), mat_job(L.ffn_w_r, vec(s.ffn_rx), vec(s.ffn_r), WRK_ACT_NONE)};
             if (single) {
                 const wrk_buf* mx[2] = {L.ffn_mix_k, L.ffn_mix_r};
                 for (int i = 0; i < 2; ++i) {
@@ -524,7 +464,7 @@ int32_t wrk_v6_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
             if (run_jobs(jobs, 2) != 0) return wrk_fail(ctx, WRK_E_ARG, "fused V6 K6 rejected");
         }
         {   // K7
-            wrk::MatJob j = job6(L.ffn_w_v, vec(s.ffn_k, F), vec(s.ffn_v), WRK_ACT_NONE);
+            wrk::MatJob j = mat_job(L.ffn_w_v, vec(s.ffn_k, F), vec(s.ffn_v), WRK_ACT_NONE);
             if (single) {
                 j.out = vec(s.x); j.has_res = 1; j.res = vec(s.x); j.gate = s.ffn_r; j.carry_src = s.ffn_x; j.carry_dst = rowf;
                 if (run_jobs(&j, 1) != 0) return wrk_fail(ctx, WRK_E_ARG, "fused V6 K7 rejected");
@@ -544,7 +484,7 @@ int32_t wrk_v6_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         P.ln_w = (const f16*)d.ln_out_w->ptr; P.ln_b = (const f16*)d.ln_out_b->ptr; P.eps = LN_EPS;
         P.d = D; P.nmix = 0; P.ln_out = (f16*)s.head_x;
         LNMIX(P, NH);
-        wrk::MatJob j = job6(d.head, make_dense(s.head_x, WRK_F16, D, NH), make_dense(s.head_o, WRK_F32, V, NH), WRK_ACT_NONE);
+        wrk::MatJob j = mat_job(d.head, make_dense(s.head_x, WRK_F16, D, NH), make_dense(s.head_o, WRK_F32, V, NH), WRK_ACT_NONE);
         if (run_jobs(&j, 1) != 0) return wrk_fail(ctx, WRK_E_ARG, "fused V6 head rejected");
     }
 #undef LNMIX
@@ -603,13 +543,7 @@ int32_t wrk_v6_model_destroy(wrk_v6_model* m) {
         LOCK(m->ctx);
         hipSetDevice(m->ctx->device);
         hipStreamSynchronize(m->ctx->stream);
-        m->drop_graphs();
-        if (m->scratch) hipFree(m->scratch);
-        if (m->history) hipFree(m->history);
-        if (m->sample_par) hipFree(m->sample_par);
-        if (m->pen_par) hipFree(m->pen_par);
-        if (m->pen_o) hipFree(m->pen_o);
-        m->score.release();
+        m->release_common();
     }
     for_each_handle(m, [](const wrk_buf* b) { if (b) wrk_buf_release(const_cast<wrk_buf*>(b)); },
                     [](const wrk_matrix* x) { if (x) wrk_matrix_release(const_cast<wrk_matrix*>(x)); });
@@ -646,225 +580,96 @@ int32_t wrk_v6_state_create(wrk_ctx* ctx, const wrk_v6_model* model, uint32_t nu
     return WRK_OK;
 }
 
-// one RnnJob: wrk_v6_infer, or with `score` wrk_v6_score (the header rows' logits scored against targets instead of read back)
-static int32_t v6_job(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors,
-                      uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax, bool score, const uint32_t* targets,
-                      float* logprob, uint32_t* rank, uint32_t mode) {
+// one RnnJob: wrk_v6_infer, or with a.score wrk_v6_score (the header rows' logits scored against targets instead of read back).
+// Uncached: the launches are enqueued on every call
+static int32_t v6_job(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const wrk_job_args& a, uint32_t mode) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t T = a.T, NH = a.NH, V = m->d.num_vocab;
     if (T == 0) return WRK_OK;
-    WRK_ARG(ctx, cursors && (tokens || emb_rows) && (!tokens || m->d.emb_f16) && (NH == 0 || headers), "missing inputs");
+    WRK_ARG(ctx, a.cursors && (a.tokens || a.emb_rows) && (!a.tokens || m->d.emb_f16) && (NH == 0 || a.headers), "missing inputs");
     WRK_ARG(ctx, st->num_emb == m->d.num_emb && st->num_layer == m->d.num_layer, "state does not belong to this model");
-    const uint32_t D = m->d.num_emb, V = m->d.num_vocab;
-    std::vector<uint8_t> seen(256, 0);
-    bool one_token_each = true;
-    uint32_t nseq = 0;
-    for (uint32_t t = 0; t < T; ++t) {
-        const uint32_t c = cursors[t], b = c & 0xff, tok = (c >> 8) & 0xffff, len = c >> 24;
-        WRK_ARG(ctx, b < st->num_batch, "cursor %u: batch %u >= %u", t, b, st->num_batch);
-        WRK_ARG(ctx, len >= 1 && tok <= t && t < tok + len && tok + len <= T, "cursor %u: bad range", t);
-        if (tok == t) { WRK_ARG(ctx, !seen[b], "cursor %u: batch %u appears twice", t, b); seen[b] = 1; ++nseq; }
-        if (len != 1) one_token_each = false;
-        if (tokens) WRK_ARG(ctx, tokens[t] < V, "token %u: id %u >= vocab %u", t, tokens[t], V);
-    }
-    bool identity = (NH == T);
-    for (uint32_t h = 0; h < NH; ++h) { WRK_ARG(ctx, headers[h] < T, "header %u out of range", h); if (headers[h] != h) identity = false; }
-    if (score) {
-        WRK_ARG(ctx, !ctx->capturing_here(), "wrk_v6_score is blocking: not inside a capture");
-        WRK_ARG(ctx, NH == 0 || (logprob && rank), "logprob and rank are required");
-        const int32_t rt = wrk_score_check_targets(ctx, targets, NH, V);
-        if (rt != WRK_OK) return rt;
-    }
-    int32_t rc = m->ensure_scratch(T, NH ? NH : 1);
+    wrk_job_shape sh;
+    int32_t rc = wrk_job_check(ctx, st, a.cursors, T, a.tokens, V, a.headers, NH, &sh);
+    if (rc == WRK_OK) rc = wrk_score_check(ctx, a, V, "wrk_v6_score");
+    if (rc == WRK_OK) rc = m->ensure_scratch(T, NH ? NH : 1);
+    if (rc == WRK_OK) rc = wrk_job_upload(*m, m->s, m->s.input, m->d.emb_f16, m->d.num_emb, a, true);
     if (rc != WRK_OK) return rc;
-    if (score && NH) {
-        bool grown = false;
-        rc = m->score.ensure(ctx, NH, &grown);
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->score.targets, targets, (size_t)NH * 4);
-        if (rc != WRK_OK) return rc;
-    }
-    rc = wrk_buf_write_raw(ctx, m->s.cursors, cursors, (size_t)T * 4);
-    if (rc == WRK_OK && NH) rc = wrk_buf_write_raw(ctx, m->s.headers, headers, (size_t)NH * 4);
-    if (rc != WRK_OK) return rc;
-    if (tokens) {
-        rc = wrk_buf_write_raw(ctx, m->s.tokens, tokens, (size_t)T * 4);
-        if (rc != WRK_OK) return rc;
-        wrk::gather_rows_f16(ctx->op_stream(), m->d.emb_f16->ptr, m->s.tokens, m->s.input, D, T);
-    } else {
-        rc = wrk_buf_write_raw(ctx, m->s.input, emb_rows, (size_t)T * D * 2);
-        if (rc != WRK_OK) return rc;
-    }
-    m->wkv_nseq = nseq;
+    m->wkv_nseq = sh.nseq;
     rc = WRK_E_UNSUPPORTED;
-    if (mode == 1 && one_token_each) rc = m->enqueue_fused_decode(st, T, NH, identity, cursors[0] & 0xff);
-    if (rc == WRK_E_UNSUPPORTED) rc = m->enqueue_ops(st, T, NH, identity, mode == 1 && !one_token_each);
+    if (mode == 1 && sh.one_token_each) rc = m->enqueue_fused_decode(st, T, NH, sh.identity, a.cursors[0] & 0xff);
+    if (rc == WRK_E_UNSUPPORTED) rc = m->enqueue_ops(st, T, NH, sh.identity, mode == 1 && !sh.one_token_each);
     if (rc != WRK_OK) return rc;
-    if (NH && argmax) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->s.argmax);
-    if (NH && score &&
+    if (NH && a.argmax) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->s.argmax);
+    if (NH && a.score &&
         wrk::score_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->score.targets, m->score.part, m->score.logprob, m->score.rank,
                         ctx->num_cu) != 0)
         return wrk_fail(ctx, WRK_E_UNSUPPORTED, "score: vocabulary of %u tokens", V);
-    WRK_LAUNCH_CHECK(ctx);
-    if (ctx->capturing_here()) return WRK_OK;   // recorded into the caller's program: results exist after it has been launched
-    if (NH && logits) WRK_HIP(ctx, hipMemcpyAsync(logits, m->s.head_o, (size_t)NH * V * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (NH && argmax) WRK_HIP(ctx, hipMemcpyAsync(argmax, m->s.argmax, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (NH && score) {
-        WRK_HIP(ctx, hipMemcpyAsync(logprob, m->score.logprob, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
-        WRK_HIP(ctx, hipMemcpyAsync(rank, m->score.rank, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return WRK_OK;
+    return wrk_job_read_back(*m, m->s, V, a);
 }
 
 int32_t wrk_v6_infer(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors,
                      uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax, uint32_t mode) {
-    return v6_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, logits, argmax, false, nullptr, nullptr, nullptr, mode);
+    return v6_job(ctx, m, st, {tokens, emb_rows, cursors, T, headers, NH, logits, argmax, false, nullptr, nullptr, nullptr}, mode);
 }
 
 int32_t wrk_v6_score(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors,
                      uint32_t T, const uint32_t* headers, uint32_t NH, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode) {
-    return v6_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank, mode);
+    return v6_job(ctx, m, st, {tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank}, mode);
 }
 
-// par: sampler parameters of the B sequences (generate_sample), or nullptr (generate_greedy); pen: their occurrence rows and penalties
-// (generate_penalized, with par), or nullptr
+// pick: the sampler / penalty arrays of generate_sample / generate_penalized, or nullptr (generate_greedy); mode is used as given
 static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
-                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen, uint32_t* out_tokens, float* last_logits,
-                           float* elapsed_ms, uint32_t mode) {
+                           const wrk_pick_args* pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
+    if (!ctx || !m || !st || !first_tokens || (pick && pick->penalized && !pick->occ)) return WRK_E_ARG;
     LOCK(ctx);
-    WRK_HIP(ctx, hipSetDevice(ctx->device));
-    WRK_ARG(ctx, m->d.emb_f16, "generate_greedy needs the device embedding table");
-    WRK_ARG(ctx, B >= 1 && B <= st->num_batch, "num_batch %u exceeds the state's %u", B, st->num_batch);
-    const uint32_t D = m->d.num_emb, V = m->d.num_vocab;
-    for (uint32_t b = 0; b < B; ++b) WRK_ARG(ctx, first_tokens[b] < V, "first token %u out of vocab", first_tokens[b]);
+    const uint32_t V = m->d.num_vocab;
+    wrk_pick_params pp;
+    int32_t rc = wrk_pick_pack(ctx, pick, B, V, pp);
+    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->d.emb_f16 != nullptr, m->d.num_emb, m->d.num_layer, V, first_tokens, B);
+    if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     if (steps == 0) return WRK_OK;
-    int32_t rc = m->ensure_scratch(B, B);
-    if (rc == WRK_OK) rc = m->ensure_history((size_t)steps * B);
-    if (rc == WRK_OK && par && B > m->sample_par_cap) {      // outside capture; the programs holding the old pointer go with it
-        WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        m->drop_graphs();
-        if (m->sample_par) hipFree(m->sample_par);
-        m->sample_par = nullptr;
-        m->sample_par_cap = 0;
-        WRK_HIP(ctx, hipMalloc((void**)&m->sample_par, (size_t)B * sizeof(wrk::SampleParam)));
-        m->sample_par_cap = B;
-    }
-    if (rc == WRK_OK && pen && (B > m->pen_cap || !m->pen_par || !m->pen_o)) {     // as sample_par
-        WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        m->drop_graphs();
-        if (m->pen_par) hipFree(m->pen_par);
-        if (m->pen_o) hipFree(m->pen_o);
-        m->pen_par = nullptr;
-        m->pen_o = nullptr;
-        m->pen_cap = 0;
-        WRK_HIP(ctx, hipMalloc((void**)&m->pen_par, (size_t)B * sizeof(wrk::PenaltyParam)));
-        WRK_HIP(ctx, hipMalloc((void**)&m->pen_o, (size_t)B * V * 4));
-        m->pen_cap = B;
-    }
+    rc = m->ensure_scratch(B, B);
+    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, V, first_tokens, 0, B, steps, pp.par, pp.pen);
     if (rc != WRK_OK) return rc;
-    std::vector<uint32_t> cur(B), hdr(B);
-    for (uint32_t b = 0; b < B; ++b) { cur[b] = b | (b << 8) | (1u << 24); hdr[b] = b; }
-    rc = wrk_buf_write_raw(ctx, m->s.cursors, cur.data(), (size_t)B * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.headers, hdr.data(), (size_t)B * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.tokens, first_tokens, (size_t)B * 4);
-    if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, m->sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
-    if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, m->pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
-    if (rc != WRK_OK) return rc;
-    WRK_HIP(ctx, hipMemsetAsync(m->s.counter, 0, 4, ctx->stream));
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const char* ng = getenv("WRK_NO_GRAPH");
     const bool eager = ng && ng[0] == '1';
     auto enqueue_step = [&]() -> int32_t {
-        wrk::gather_rows_f16(ctx->op_stream(), m->d.emb_f16->ptr, m->s.tokens, m->s.input, D, B);
+        wrk::gather_rows_f16(ctx->op_stream(), m->d.emb_f16->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
         int32_t r = WRK_E_UNSUPPORTED;
         if (mode == 1) r = m->enqueue_fused_decode(st, B, B, true, 0);
         if (r == WRK_E_UNSUPPORTED) r = m->enqueue_ops(st, B, B, true);
         if (r != WRK_OK) return r;
-        const float* logits = m->s.head_o;
-        if (pen) {      // the sampler draws from the penalised copy; the drawn tokens are counted before the counter moves
-            wrk::penalize_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->pen_par, m->pen_o, V);
-            logits = m->pen_o;
-        }
-        if (!par) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, B, m->s.argmax);
-        else if (wrk::sample_rows(ctx->op_stream(), logits, V, V, B, m->sample_par, m->s.counter, m->s.argmax) != 0)
-            return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
-        if (pen) wrk::occurrence_update(ctx->op_stream(), V, B, m->pen_par, m->s.argmax, 1);
-        wrk::advance_tokens(ctx->op_stream(), m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
-        return WRK_OK;
+        return wrk_enqueue_pick(*m, m->s, V, B, pp.par != nullptr, pp.pen != nullptr);
     };
-    wrk_program* prog = nullptr;
-    const auto key = std::make_tuple(st->uid, B, mode | (par ? 32u : 0u) | (pen ? 64u : 0u));   // nor do greedy, sampled and penalised steps
+    std::vector<wrk_lane> lane{{&m->s, m->history, 0, B, nullptr}};
     if (!eager) {
-        auto it = m->graphs.find(key);
-        if (it != m->graphs.end()) prog = it->second;
-        else {
-            rc = wrk_capture_begin(ctx);
-            if (rc != WRK_OK) return rc;
-            rc = enqueue_step();
-            wrk_program* p = nullptr;
-            int32_t rc2 = wrk_capture_end(ctx, &p);
-            if (rc != WRK_OK) { if (p) wrk_program_destroy(p); return rc; }
-            if (rc2 != WRK_OK) return rc2;
-            prog = p;
-            m->graphs[key] = prog;
-        }
+        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pp.par ? 32u : 0u) | (pp.pen ? 64u : 0u)}, enqueue_step, &lane[0].prog);
+        if (rc != WRK_OK) return rc;
     }
-    hipEvent_t e0, e1;
-    WRK_HIP(ctx, hipEventCreate(&e0));
-    WRK_HIP(ctx, hipEventCreate(&e1));
-    WRK_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    for (uint32_t i = 0; i < steps; ++i) {
-        if (eager) { rc = enqueue_step(); if (rc != WRK_OK) return rc; }
-        else WRK_HIP(ctx, hipGraphLaunch(prog->exec, ctx->stream));
-    }
-    WRK_HIP(ctx, hipEventRecord(e1, ctx->stream));
-    WRK_HIP(ctx, hipEventSynchronize(e1));
-    float ms = 0.0f;
-    WRK_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (elapsed_ms) *elapsed_ms = ms;
-    if (out_tokens) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, m->history, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits, m->s.head_o, (size_t)B * V * 4, hipMemcpyDeviceToHost, ctx->stream));
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return WRK_OK;
+    return wrk_run_lanes(ctx, lane, {}, {}, B, V, steps, enqueue_step, out_tokens, last_logits, elapsed_ms);
 }
 
 int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
-    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
-    return v6_generate(ctx, m, st, first_tokens, B, steps, nullptr, nullptr, out_tokens, last_logits, elapsed_ms, mode);
+    return v6_generate(ctx, m, st, first_tokens, B, steps, nullptr, out_tokens, last_logits, elapsed_ms, mode);
 }
 
 int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                const float* temperature, const float* top_p, const uint32_t* seed, uint32_t* out_tokens, float* last_logits,
                                float* elapsed_ms, uint32_t mode) {
-    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
-    LOCK(ctx);
-    std::vector<wrk::SampleParam> par;
-    const int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
-    if (rc != WRK_OK) return rc;
-    WRK_ARG(ctx, B >= 1, "num_batch 0");
-    return v6_generate(ctx, m, st, first_tokens, B, steps, par.data(), nullptr, out_tokens, last_logits, elapsed_ms, mode);
+    const wrk_pick_args pick{temperature, top_p, seed};
+    return v6_generate(ctx, m, st, first_tokens, B, steps, &pick, out_tokens, last_logits, elapsed_ms, mode);
 }
 
 int32_t wrk_v6_generate_penalized(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                   const float* temperature, const float* top_p, const uint32_t* seed, const float* presence,
                                   const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens, float* last_logits,
                                   float* elapsed_ms, uint32_t mode) {
-    if (!ctx || !m || !st || !first_tokens || !occ) return WRK_E_ARG;
-    LOCK(ctx);
-    std::vector<wrk::SampleParam> par;
-    int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
-    if (rc != WRK_OK) return rc;
-    WRK_ARG(ctx, B >= 1, "num_batch 0");
-    WRK_ARG(ctx, decay, "decay array required");
-    std::vector<wrk::PenaltyParam> pen;
-    rc = wrk_penalty_pack(ctx, occ, 0, B, m->d.num_vocab, presence, frequency, decay, pen);
-    if (rc != WRK_OK) return rc;
-    return v6_generate(ctx, m, st, first_tokens, B, steps, par.data(), pen.data(), out_tokens, last_logits, elapsed_ms, mode);
+    const wrk_pick_args pick{temperature, top_p, seed, true, presence, frequency, decay, occ};
+    return v6_generate(ctx, m, st, first_tokens, B, steps, &pick, out_tokens, last_logits, elapsed_ms, mode);
 }
 
 }  // extern "C"

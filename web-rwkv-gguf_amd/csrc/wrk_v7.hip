@@ -16,7 +16,7 @@ static constexpr float GN_EPS = 64.0e-5f;   // v7.rs:48
 static constexpr float L2_EPS = 1.0e-12f;   // v7.rs:46
 
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-static wrk::MatJob mj(const wrk_matrix* m, DTensor in, DTensor out, uint32_t act);
+using wrk::mat_job;
 
 // ------------------------------------------------------------------ scratch ("Runtime<f16>" + "Header<f16>")
 int32_t wrk_v7_model::ensure_scratch(uint32_t T, uint32_t NH) {
@@ -90,7 +90,7 @@ int32_t wrk_v7_model::ensure_scratch(uint32_t T, uint32_t NH) {
     scratch_headers = nh;
     // arg-max partials of the head matvec: one (value, index) per workgroup and header row
     {
-        wrk::MatJob hj = mj(head, make_dense(s.head_x, WRK_F16, d.num_emb, nh), make_dense(s.head_o, WRK_F32, d.num_vocab, nh), 0);
+        wrk::MatJob hj = mat_job(head, make_dense(s.head_x, WRK_F16, d.num_emb, nh), make_dense(s.head_o, WRK_F32, d.num_vocab, nh), 0);
         const size_t need = (size_t)wrk::matvec_num_wg(&hj, 1, ctx->num_cu, nullptr) * nh;
         if (need > amax_cap) {
             free_fused();
@@ -102,38 +102,9 @@ int32_t wrk_v7_model::ensure_scratch(uint32_t T, uint32_t NH) {
     return WRK_OK;
 }
 
-static wrk::MatJob mj(const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
-    wrk::MatJob j{m->data, m->aux, m->kind, m->flags, m->k, m->m, (uint32_t)m->row_bytes, in, out, act, 0};
-    j.scale = m->out_scale;
-    return j;
-}
-
-static int32_t mm(wrk_ctx* ctx, const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
-    wrk::MatJob j = mj(m, in, out, act);
-    j.xsum = ctx->gemm_scratch; j.xsum_cap = ctx->gemm_scratch_cap;
-    int rc = -2;
-    if (in.shape[1] * in.shape[2] >= wrk::gemm_min_tokens()) rc = wrk::matmul_mfma(ctx->op_stream(), j, ctx->num_cu);
-    if (rc == -2) rc = wrk::matvec(ctx->op_stream(), &j, 1, ctx->num_cu);
-    if (rc != 0) return wrk_fail(ctx, WRK_E_ARG, "matmul launch rejected (K=%u M=%u)", m->k, m->m);
-    return WRK_OK;
-}
-// several matrices x the same token count in one MFMA launch per kernel family; per-matrix launches when the GEMM declines
-static int32_t mm_group(wrk_ctx* ctx, wrk::MatJob* jobs, int n) {
-    const uint32_t T = jobs[0].in.shape[1] * jobs[0].in.shape[2];
-    jobs[0].xsum = ctx->gemm_scratch; jobs[0].xsum_cap = ctx->gemm_scratch_cap;
-    if (T >= wrk::gemm_min_tokens() && wrk::matmul_mfma_multi(ctx->op_stream(), jobs, n, ctx->num_cu) == 0) return WRK_OK;
-    for (int i = 0; i < n; ++i) {
-        jobs[i].xsum = ctx->gemm_scratch; jobs[i].xsum_cap = ctx->gemm_scratch_cap;
-        int rc = -2;
-        if (T >= wrk::gemm_min_tokens()) rc = wrk::matmul_mfma(ctx->op_stream(), jobs[i], ctx->num_cu);
-        if (rc == -2) rc = wrk::matvec(ctx->op_stream(), &jobs[i], 1, ctx->num_cu);
-        if (rc != 0) return wrk_fail(ctx, WRK_E_ARG, "matmul launch rejected (K=%u M=%u)", jobs[i].k, jobs[i].m);
-    }
-    return WRK_OK;
-}
 #define MM(...)                                   \
     do {                                          \
-        int32_t _r = mm(ctx, __VA_ARGS__);        \
+        int32_t _r = wrk_mm(ctx, __VA_ARGS__);    \
         if (_r != WRK_OK) return _r;              \
     } while (0)
 
@@ -198,14 +169,14 @@ int32_t wrk_v7_model::enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, boo
             wrk::token_shift(q, s.cursors, bvec(L.x_g), st_row0, att_x, gx, 1);
         }
         if (m_group) {
-            wrk::MatJob ja[7] = {mj(L.w_r, rx, r, WRK_ACT_NONE), mj(L.w_k, kx, k, WRK_ACT_NONE), mj(L.w_v, vx, v, WRK_ACT_NONE),
-                                 mj(L.w1, wx, aux_w, WRK_ACT_TANH), mj(L.a1, ax, aux_a, WRK_ACT_NONE), mj(L.g1, gx, aux_g, WRK_ACT_SIGMOID),
-                                 mj(li ? L.v1 : L.a1, li ? vx : ax, li ? aux_v : aux_a, WRK_ACT_NONE)};
-            int32_t rg = mm_group(ctx, ja, li ? 7 : 6);
+            wrk::MatJob ja[7] = {mat_job(L.w_r, rx, r, WRK_ACT_NONE), mat_job(L.w_k, kx, k, WRK_ACT_NONE), mat_job(L.w_v, vx, v, WRK_ACT_NONE),
+                                 mat_job(L.w1, wx, aux_w, WRK_ACT_TANH), mat_job(L.a1, ax, aux_a, WRK_ACT_NONE), mat_job(L.g1, gx, aux_g, WRK_ACT_SIGMOID),
+                                 mat_job(li ? L.v1 : L.a1, li ? vx : ax, li ? aux_v : aux_a, WRK_ACT_NONE)};
+            int32_t rg = wrk_mm_group(ctx, ja, li ? 7 : 6);
             if (rg != WRK_OK) return rg;
-            wrk::MatJob jb[4] = {mj(L.w2, aux_w, w, WRK_ACT_NONE), mj(L.a2, aux_a, a, WRK_ACT_NONE), mj(L.g2, aux_g, g, WRK_ACT_NONE),
-                                 mj(li ? L.v2 : L.a2, li ? aux_v : aux_a, li ? vv : a, WRK_ACT_NONE)};
-            rg = mm_group(ctx, jb, li ? 4 : 3);
+            wrk::MatJob jb[4] = {mat_job(L.w2, aux_w, w, WRK_ACT_NONE), mat_job(L.a2, aux_a, a, WRK_ACT_NONE), mat_job(L.g2, aux_g, g, WRK_ACT_NONE),
+                                 mat_job(li ? L.v2 : L.a2, li ? aux_v : aux_a, li ? vv : a, WRK_ACT_NONE)};
+            rg = wrk_mm_group(ctx, jb, li ? 4 : 3);
             if (rg != WRK_OK) return rg;
         } else {
             MM(L.w_r, rx, r, WRK_ACT_NONE);                                                  // 4
@@ -254,10 +225,10 @@ int32_t wrk_v7_model::enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, boo
             wrk::binary(q, 1, g, att_x, 0, 0, 0);                                        // 15
         }
         if (m_res) {        // the add rides the projection's epilogue: x = round(W_o att_x) + x
-            wrk::MatJob jo = mj(L.w_o, att_x, x, WRK_ACT_NONE);
+            wrk::MatJob jo = mat_job(L.w_o, att_x, x, WRK_ACT_NONE);
             jo.has_res = 1;
             jo.res = x;
-            const int32_t rg = mm_group(ctx, &jo, 1);
+            const int32_t rg = wrk_mm_group(ctx, &jo, 1);
             if (rg != WRK_OK) return rg;
         } else {
             MM(L.w_o, att_x, o, WRK_ACT_NONE);                                           // 16
@@ -271,10 +242,10 @@ int32_t wrk_v7_model::enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, boo
         wrk::token_shift(q, s.cursors, bvec(L.ffn_x_k), st_ffn, ffn_x, ffn_kx, 1);        // 18
         MM(L.ffn_w_k, ffn_kx, ffn_k, WRK_ACT_SQUARED_RELU);                              // 19
         if (m_tail) {       // x = round(W_v k) + x in the epilogue; channel_mix still saves the ffn shift state (its copy is dead)
-            wrk::MatJob jv = mj(L.ffn_w_v, ffn_k, x, WRK_ACT_NONE);
+            wrk::MatJob jv = mat_job(L.ffn_w_v, ffn_k, x, WRK_ACT_NONE);
             jv.has_res = 1;
             jv.res = x;
-            const int32_t rg = mm_group(ctx, &jv, 1);
+            const int32_t rg = wrk_mm_group(ctx, &jv, 1);
             if (rg != WRK_OK) return rg;
             wrk::channel_mix_v7(q, s.cursors, st_ffn, ffn_v, ffn_x);
         } else {
@@ -355,22 +326,16 @@ int32_t wrk_v7_model_destroy(wrk_v7_model* m) {
         LOCK(ctx);
         hipSetDevice(ctx->device);
         hipStreamSynchronize(ctx->stream);
-        for (auto& kv : m->graphs) wrk_program_destroy(kv.second);
-        if (m->scratch) hipFree(m->scratch);
+        for (hipStream_t s : m->lane_streams) { hipStreamSynchronize(s); hipStreamDestroy(s); }
+        m->release_common();
         m->free_fused();
         wrk_v7_engine_destroy(m->engine);
         m->engine = nullptr;
-        for (hipStream_t s : m->lane_streams) { hipStreamSynchronize(s); hipStreamDestroy(s); }
         for (hipEvent_t e : m->lane_events) hipEventDestroy(e);
         m->lane_streams.clear(); m->lane_events.clear();
     }
     for (wrk_v7_model* lane : m->lanes) wrk_v7_model_destroy(lane);
     m->lanes.clear();
-    if (m->history) { LOCK(ctx); hipFree(m->history); m->history = nullptr; }
-    if (m->sample_par) { LOCK(ctx); hipFree(m->sample_par); m->sample_par = nullptr; }
-    if (m->pen_par) { LOCK(ctx); hipFree(m->pen_par); m->pen_par = nullptr; }
-    if (m->pen_o) { LOCK(ctx); hipFree(m->pen_o); m->pen_o = nullptr; }
-    if (m->score.buf) { LOCK(ctx); m->score.release(); }
     auto fb = [](const wrk_buf* b) { if (b) wrk_buf_release(const_cast<wrk_buf*>(b)); };
     auto fm = [](const wrk_matrix* x) { if (x) wrk_matrix_release(const_cast<wrk_matrix*>(x)); };
     fb(m->ln0_w); fb(m->ln0_b); fb(m->ln_out_w); fb(m->ln_out_b); fb(m->emb); fm(m->head);
@@ -475,86 +440,41 @@ static int32_t state_d2d(wrk_ctx* ctx, const wrk_v7_state* st, uint32_t batch, c
 int32_t wrk_v7_state_read(wrk_ctx* ctx, const wrk_v7_state* st, uint32_t batch, wrk_buf* buf) { return state_d2d(ctx, st, batch, buf, false); }
 int32_t wrk_v7_state_write(wrk_ctx* ctx, wrk_v7_state* st, uint32_t batch, const wrk_buf* buf) { return state_d2d(ctx, st, batch, buf, true); }
 
-// one RnnJob: wrk_v7_infer, or with `score` wrk_v7_score (the header rows' logits scored against targets instead of read back)
-static int32_t v7_job(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows,
-                      const uint32_t* cursors, uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax,
-                      bool score, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode) {
+// one RnnJob: wrk_v7_infer, or with a.score wrk_v7_score (the header rows' logits scored against targets instead of read back)
+static int32_t v7_job(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const wrk_job_args& a, uint32_t mode) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t T = a.T, NH = a.NH, V = m->d.num_vocab;
     if (T == 0) return WRK_OK;                                  // v7.rs:626-635: empty job
-    WRK_ARG(ctx, cursors, "cursors required");
-    WRK_ARG(ctx, tokens || emb_rows, "either token ids or gathered embedding rows are required");
-    WRK_ARG(ctx, !tokens || m->emb, "token ids given but the model has no device embedding table");
-    WRK_ARG(ctx, NH == 0 || headers, "headers required");
+    WRK_ARG(ctx, a.cursors, "cursors required");
+    WRK_ARG(ctx, a.tokens || a.emb_rows, "either token ids or gathered embedding rows are required");
+    WRK_ARG(ctx, !a.tokens || m->emb, "token ids given but the model has no device embedding table");
+    WRK_ARG(ctx, NH == 0 || a.headers, "headers required");
     WRK_ARG(ctx, st->num_emb == m->d.num_emb && st->num_layer == m->d.num_layer, "state does not belong to this model");
-    const uint32_t D = m->d.num_emb, V = m->d.num_vocab;
-    // validate cursors / tokens / headers on the host: a bad index would fault the GPU
-    uint32_t nseq = 0;
-    bool one_token_each = true;
-    std::vector<uint8_t> seen(256, 0);
-    for (uint32_t t = 0; t < T; ++t) {
-        const uint32_t c = cursors[t], b = c & 0xff, tok = (c >> 8) & 0xffff, len = c >> 24;
-        WRK_ARG(ctx, b < st->num_batch, "cursor %u: batch %u >= %u", t, b, st->num_batch);
-        WRK_ARG(ctx, len >= 1 && tok <= t && t < tok + len && tok + len <= T, "cursor %u: bad range (token %u len %u)", t, tok, len);
-        if (tok == t) {
-            ++nseq;
-            WRK_ARG(ctx, !seen[b], "cursor %u: batch %u appears in two chunks of one dispatch", t, b);   // two writers of one state slice
-            seen[b] = 1;
-        }
-        if (len != 1) one_token_each = false;
-        if (tokens) WRK_ARG(ctx, tokens[t] < V, "token %u: id %u >= vocab %u", t, tokens[t], V);
-    }
-    // batches of consecutive tokens are consecutive: the few-sequence decode kernels address per-sequence state rows by a stride
-    bool contiguous = true;
-    for (uint32_t t = 1; t < T; ++t) contiguous = contiguous && (cursors[t] & 0xff) == (cursors[0] & 0xff) + t;
-    bool identity = (NH == T);
-    for (uint32_t h = 0; h < NH; ++h) {
-        WRK_ARG(ctx, headers[h] < T, "header %u: row %u >= %u tokens", h, headers[h], T);
-        if (headers[h] != h) identity = false;
-    }
-    if (score) {
-        WRK_ARG(ctx, !ctx->capturing_here(), "wrk_v7_score is blocking: not inside a capture");
-        WRK_ARG(ctx, NH == 0 || (logprob && rank), "logprob and rank are required");
-        const int32_t rt = wrk_score_check_targets(ctx, targets, NH, V);
-        if (rt != WRK_OK) return rt;
-    }
-    int32_t rc = m->ensure_scratch(T, NH ? NH : 1);
+    wrk_job_shape sh;
+    int32_t rc = wrk_job_check(ctx, st, a.cursors, T, a.tokens, V, a.headers, NH, &sh);
+    if (rc == WRK_OK) rc = wrk_score_check(ctx, a, V, "wrk_v7_score");
+    if (rc == WRK_OK) rc = m->ensure_scratch(T, NH ? NH : 1);
+    if (rc == WRK_OK && T == 1 && mode == 1) rc = m->ensure_engine();
     if (rc != WRK_OK) return rc;
-    if (T == 1 && mode == 1) { rc = m->ensure_engine(); if (rc != WRK_OK) return rc; }
-    if (score && NH) {
-        bool grown = false;
-        rc = m->score.ensure(ctx, NH, &grown);
-        if (rc != WRK_OK) return rc;
-        if (grown) m->drop_graphs();            // captured score jobs hold the old slots
-        rc = wrk_buf_write_raw(ctx, m->score.targets, targets, (size_t)NH * 4);
-        if (rc != WRK_OK) return rc;
-    }
-    rc = wrk_buf_write_raw(ctx, m->s.cursors, cursors, (size_t)T * 4);
+    const bool fused = (mode == 1 && sh.one_token_each && sh.nseq == T && m->act_dtype == WRK_F16), want_argmax = NH && a.argmax;
+    const uint32_t batch0 = a.cursors[0] & 0xffu;
+    rc = wrk_job_upload(*m, m->s, m->s.input, m->emb, m->d.num_emb, a, !fused);
     if (rc != WRK_OK) return rc;
-    if (NH) { rc = wrk_buf_write_raw(ctx, m->s.headers, headers, (size_t)NH * 4); if (rc != WRK_OK) return rc; }
-    const bool fused = (mode == 1 && one_token_each && nseq == T && m->act_dtype == WRK_F16);
-    if (tokens) {
-        rc = wrk_buf_write_raw(ctx, m->s.tokens, tokens, (size_t)T * 4);
-        if (rc != WRK_OK) return rc;
-        if (!fused) wrk::gather_rows_f16(ctx->op_stream(), m->emb->ptr, m->s.tokens, m->s.input, D, T);
-    } else {
-        rc = wrk_buf_write_raw(ctx, m->s.input, emb_rows, (size_t)T * D * 2);
-        if (rc != WRK_OK) return rc;
-    }
     // The launches of a job depend only on its shape (token count, header rows, flags): cursors, tokens and header rows
     // are device data.  Capture once per shape and replay (the reference caches the RnnJob of a repeated RnnInfo);
     // a 128-token chunk of one sequence is ~1 400 small launches, which replay at graph rate.
-    m->wkv_nseq = nseq;       // chunk kernel of the WKV state: one wave or four per head (part of the graph key below)
+    m->wkv_nseq = sh.nseq;    // chunk kernel of the WKV state: one wave or four per head (part of the graph key below)
     auto enqueue_job = [&]() -> int32_t {
         int32_t r;
-        if (fused) r = m->enqueue_fused_decode(st, T, NH, identity, tokens != nullptr, NH && argmax, false, cursors[0] & 0xff, contiguous);
+        if (fused) r = m->enqueue_fused_decode(st, T, NH, sh.identity, a.tokens != nullptr, want_argmax, false, batch0, sh.contiguous);
         else {
-            r = m->enqueue_ops(st, T, NH, identity, mode == 1);
-            if (r == WRK_OK && NH && argmax) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->s.argmax);
+            r = m->enqueue_ops(st, T, NH, sh.identity, mode == 1);
+            if (r == WRK_OK && want_argmax) wrk::argmax_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->s.argmax);
         }
         // scoring: the epilogue on head_o, which every path above materialises
-        if (r == WRK_OK && score && NH &&
+        if (r == WRK_OK && a.score && NH &&
             wrk::score_rows(ctx->op_stream(), m->s.head_o, V, V, NH, m->score.targets, m->score.part, m->score.logprob, m->score.rank,
                             ctx->num_cu) != 0)
             r = wrk_fail(ctx, WRK_E_UNSUPPORTED, "score: vocabulary of %u tokens", V);
@@ -564,52 +484,32 @@ static int32_t v7_job(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uin
     if (no_graph || ctx->capturing_here()) rc = enqueue_job();
     else {
         // bit 5: a non-fused job enqueues the merged launch list in mode 1 and the reference op list in mode 0 -- two graphs
-        const uint32_t flags = 16u | (m->act_dtype == WRK_F32 ? 64u : 0u) | (fused ? 1u : 0u) | (identity ? 2u : 0u) | (tokens ? 4u : 0u) | ((NH && argmax) ? 8u : 0u) |
-                               ((!fused && mode == 1) ? 32u : 0u) | (fused ? (cursors[0] & 0xffu) << 8 : 0u) | ((fused && contiguous) ? 1u << 16 : 0u) |
+        const uint32_t flags = 16u | (m->act_dtype == WRK_F32 ? 64u : 0u) | (fused ? 1u : 0u) | (sh.identity ? 2u : 0u) | (a.tokens ? 4u : 0u) | (want_argmax ? 8u : 0u) |
+                               ((!fused && mode == 1) ? 32u : 0u) | (fused ? batch0 << 8 : 0u) | ((fused && sh.contiguous) ? 1u << 16 : 0u) |
                                ((fused && T == 1 && m->engine_on()) ? 1u << 17 : 0u) | (split_head_env_on() ? 0u : 1u << 18) |
-                               ((!fused && (size_t)nseq * m->d.num_head >= 768) ? 1u << 19 : 0u) | (score ? 1u << 20 : 0u);
+                               ((!fused && (size_t)sh.nseq * m->d.num_head >= 768) ? 1u << 19 : 0u) | (a.score ? 1u << 20 : 0u);
         const wrk_v7_model::GraphKey key{st->uid, T, flags, NH};
+        if (!m->graphs.count(key) && m->graphs.size() > 64) { WRK_HIP(ctx, hipStreamSynchronize(ctx->stream)); m->drop_graphs(); }    // bound the cache
         wrk_program* prog = nullptr;
-        auto it = m->graphs.find(key);
-        if (it != m->graphs.end()) prog = it->second;
-        else {
-            if (m->graphs.size() > 64) { WRK_HIP(ctx, hipStreamSynchronize(ctx->stream)); m->drop_graphs(); }    // bound the cache
-            rc = wrk_capture_begin(ctx);
-            if (rc != WRK_OK) return rc;
-            rc = enqueue_job();
-            wrk_program* p = nullptr;
-            const int32_t rc2 = wrk_capture_end(ctx, &p);
-            if (rc != WRK_OK) { if (p) wrk_program_destroy(p); return rc; }
-            if (rc2 != WRK_OK) return rc2;
-            prog = p;
-            m->graphs[key] = prog;
-        }
+        rc = wrk_cached_program(ctx, m->graphs, key, enqueue_job, &prog);
+        if (rc != WRK_OK) return rc;
         WRK_HIP(ctx, hipGraphLaunch(prog->exec, ctx->stream));
-        rc = WRK_OK;
     }
-    if (rc != WRK_OK) return rc;
-    WRK_LAUNCH_CHECK(ctx);
-    if (ctx->capturing_here()) return WRK_OK;   // recorded into the caller's program: results exist after it has been launched
-    if (NH && logits) WRK_HIP(ctx, hipMemcpyAsync(logits, m->s.head_o, (size_t)NH * V * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (NH && argmax) WRK_HIP(ctx, hipMemcpyAsync(argmax, m->s.argmax, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (NH && score) {
-        WRK_HIP(ctx, hipMemcpyAsync(logprob, m->score.logprob, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
-        WRK_HIP(ctx, hipMemcpyAsync(rank, m->score.rank, (size_t)NH * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rc == WRK_OK) rc = wrk_job_read_back(*m, m->s, V, a);
+    if (rc != WRK_OK || ctx->capturing_here()) return rc;
     return wrk_v7_engine_check(m->engine);
 }
 
 int32_t wrk_v7_infer(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows,
                      const uint32_t* cursors, uint32_t T, const uint32_t* headers, uint32_t NH, float* logits, uint32_t* argmax,
                      uint32_t mode) {
-    return v7_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, logits, argmax, false, nullptr, nullptr, nullptr, mode);
+    return v7_job(ctx, m, st, {tokens, emb_rows, cursors, T, headers, NH, logits, argmax, false, nullptr, nullptr, nullptr}, mode);
 }
 
 int32_t wrk_v7_score(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows,
                      const uint32_t* cursors, uint32_t T, const uint32_t* headers, uint32_t NH, const uint32_t* targets, float* logprob,
                      uint32_t* rank, uint32_t mode) {
-    return v7_job(ctx, m, st, tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank, mode);
+    return v7_job(ctx, m, st, {tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank}, mode);
 }
 
 // Bundle::<F>::new (v7.rs:514-536): the activation type of the frame.  F16 is the reference's default build
@@ -663,32 +563,22 @@ int32_t wrk_v7_infer_layer(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint
     WRK_ARG(ctx, T >= 1, "no tokens");
     WRK_ARG(ctx, layer == 0 || v_first, "layers above 0 read the layer-0 value (att_v0)");
     WRK_ARG(ctx, st->num_emb == m->d.num_emb && st->num_layer == m->d.num_layer, "state does not belong to this model");
-    bool one_token_each = true;
-    uint32_t nseq = 0;
-    std::vector<uint8_t> seen(256, 0);
-    for (uint32_t t = 0; t < T; ++t) {
-        const uint32_t c = cursors[t], b = c & 0xff, tok = (c >> 8) & 0xffff, len = c >> 24;
-        WRK_ARG(ctx, b < st->num_batch, "cursor %u: batch %u >= %u", t, b, st->num_batch);
-        WRK_ARG(ctx, len >= 1 && tok <= t && t < tok + len && tok + len <= T, "cursor %u: bad range", t);
-        if (tok == t) { ++nseq; WRK_ARG(ctx, !seen[b], "cursor %u: batch %u twice", t, b); seen[b] = 1; }
-        if (len != 1) one_token_each = false;
-    }
-    bool contiguous = true;
-    for (uint32_t t = 1; t < T; ++t) contiguous = contiguous && (cursors[t] & 0xff) == (cursors[0] & 0xff) + t;
-    int32_t rc = m->ensure_scratch(T, 1);
+    wrk_job_shape sh;
+    int32_t rc = wrk_job_check(ctx, st, cursors, T, nullptr, 0, nullptr, 0, &sh);
+    if (rc == WRK_OK) rc = m->ensure_scratch(T, 1);
+    if (rc == WRK_OK && T == 1 && mode == 1) rc = m->ensure_engine();
     if (rc != WRK_OK) return rc;
-    if (T == 1 && mode == 1) { rc = m->ensure_engine(); if (rc != WRK_OK) return rc; }
     const size_t esz = m->act_dtype == WRK_F32 ? 4 : 2;
     rc = wrk_buf_write_raw(ctx, m->s.cursors, cursors, (size_t)T * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.x, x, (size_t)T * m->d.num_emb * esz);
     if (rc == WRK_OK && v_first) rc = wrk_buf_write_raw(ctx, m->s.att_v0, v_first, (size_t)T * m->d.num_emb * esz);
     if (rc != WRK_OK) return rc;
     m->layer_begin = layer; m->layer_end = layer + 1; m->skip_embed = true;
-    m->wkv_nseq = nseq;
+    m->wkv_nseq = sh.nseq;
     // this entry point exists to read the frame buffers of a layer back (wrk_v7_frame_read): the engine keeps them in LDS and granules,
     // so the launches run here; WRK_ENGINE_INSPECT=1 (tests/test_gpu_engine.py) runs the engine's layer instead
     { const char* ei = getenv("WRK_ENGINE_INSPECT"); m->engine_skip_once = !(ei && ei[0] == '1'); }
-    if (mode == 1 && one_token_each && nseq == T && m->act_dtype == WRK_F16) rc = m->enqueue_fused_decode(st, T, 0, true, false, false, false, cursors[0] & 0xff, contiguous);
+    if (mode == 1 && sh.one_token_each && sh.nseq == T && m->act_dtype == WRK_F16) rc = m->enqueue_fused_decode(st, T, 0, true, false, false, false, cursors[0] & 0xff, sh.contiguous);
     else rc = m->enqueue_ops(st, T, 0, true, mode == 1);
     m->layer_begin = 0; m->layer_end = 0xffffffffu; m->skip_embed = false; m->engine_skip_once = false;
     if (rc != WRK_OK) return rc;
@@ -725,36 +615,20 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
     return wrk_fail(ctx, WRK_E_ARG, "no frame buffer named %s", name);
 }
 
-// one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers, pick each sequence's next token -- the arg-max,
-// or with `sampled` the sampler (wrk_sample.hip) on the frame's per-sequence parameters at step *s.counter -- and advance
-// tokens / history / counter.  `penalized` (implies `sampled`): the sampler draws from pen_o = head_o penalised with the occurrence rows of
-// pen_par, and those rows count the drawn tokens (wrk_penalty.hip)
+// one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers, pick each sequence's next token and advance
+// tokens / history / counter (wrk_enqueue_pick; the fused greedy path does both inside its head launch)
 static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled,
                                    bool penalized) {
-    const uint32_t V = m->d.num_vocab;
-    hipStream_t q = ctx->op_stream();
     int32_t rc;
-    if (mode == 1 && m->act_dtype == WRK_F16) rc = m->enqueue_fused_decode(st, B, B, true, true, !sampled, !sampled, b0, true);
-    else {
-        wrk::gather_rows_f16(q, m->emb->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
+    if (mode == 1 && m->act_dtype == WRK_F16) {
+        rc = m->enqueue_fused_decode(st, B, B, true, true, !sampled, !sampled, b0, true);
+        if (!sampled) return rc;
+    } else {
+        wrk::gather_rows_f16(ctx->op_stream(), m->emb->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
         rc = m->enqueue_ops(st, B, B, true);
-        if (rc == WRK_OK && !sampled) {
-            wrk::argmax_rows(q, m->s.head_o, V, V, B, m->s.argmax);
-            wrk::advance_tokens(q, m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
-        }
     }
-    if (rc != WRK_OK || !sampled) return rc;
-    const float* logits = m->s.head_o;
-    if (penalized) {
-        wrk::penalize_rows(q, m->s.head_o, V, V, B, m->pen_par, m->pen_o, V);
-        logits = m->pen_o;
-    }
-    // the sampler only reads the counter: rows run in different workgroups, so advance_tokens moves it after all of them
-    if (wrk::sample_rows(q, logits, V, V, B, m->sample_par, m->s.counter, m->s.argmax) != 0)
-        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
-    if (penalized) wrk::occurrence_update(q, V, B, m->pen_par, m->s.argmax, 1);
-    wrk::advance_tokens(q, m->s.argmax, m->s.tokens, m->history, m->s.counter, B);
-    return WRK_OK;
+    if (rc != WRK_OK) return rc;
+    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, sampled, penalized);
 }
 
 // generate_greedy / generate_sample / generate_penalized, part 1: frame, token / cursor / sampler-parameter upload and the (cached)
@@ -764,54 +638,29 @@ static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, c
                               uint32_t steps, uint32_t mode, bool eager, const wrk::SampleParam* par, const wrk::PenaltyParam* pen,
                               wrk_program** prog_out) {
     int32_t rc = m->ensure_scratch(B, B);
-    if (rc != WRK_OK) return rc;
-    if (B == 1 && mode == 1) { rc = m->ensure_engine(); if (rc != WRK_OK) return rc; }
-    rc = m->ensure_history((size_t)steps * B);
-    if (rc == WRK_OK && par) rc = m->ensure_sample_params(B);
-    if (rc == WRK_OK && pen) rc = m->ensure_penalty(B);
-    if (rc != WRK_OK) return rc;
-    std::vector<uint32_t> cur(B), hdr(B);
-    for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
-    rc = wrk_buf_write_raw(ctx, m->s.cursors, cur.data(), (size_t)B * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.headers, hdr.data(), (size_t)B * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.tokens, first_tokens, (size_t)B * 4);
-    if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, m->sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
-    if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, m->pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
-    if (rc != WRK_OK) return rc;
-    WRK_HIP(ctx, hipMemsetAsync(m->s.counter, 0, 4, ctx->stream));
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rc == WRK_OK && B == 1 && mode == 1) rc = m->ensure_engine();
+    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, m->d.num_vocab, first_tokens, b0, B, steps, par, pen);
     *prog_out = nullptr;
-    if (eager) return WRK_OK;
+    if (rc != WRK_OK || eager) return rc;
     // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo; sampled
     // steps have their own key bit, so greedy and sampled programs never alias, and so do penalised ones (bit 24, above every infer flag)
     const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
                                                              (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u) | (pen ? 1u << 24 : 0u)};
-    auto it = m->graphs.find(key);
-    if (it != m->graphs.end()) { *prog_out = it->second; return WRK_OK; }
-    rc = wrk_capture_begin(ctx);
-    if (rc != WRK_OK) return rc;
-    rc = enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr);
-    wrk_program* p = nullptr;
-    const int32_t rc2 = wrk_capture_end(ctx, &p);
-    if (rc != WRK_OK) { if (p) wrk_program_destroy(p); return rc; }
-    if (rc2 != WRK_OK) return rc2;
-    m->graphs[key] = p;
-    *prog_out = p;
-    return WRK_OK;
+    return wrk_cached_program(ctx, m->graphs, key, [&] { return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr); }, prog_out);
 }
 
-// par: sampler parameters of the num_batch sequences (generate_sample), or nullptr (generate_greedy); pen: their occurrence rows and
-// penalties (generate_penalized), or nullptr
-static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
-                           uint32_t steps, const wrk::SampleParam* par, const wrk::PenaltyParam* pen, uint32_t* out_tokens, float* last_logits,
-                           float* elapsed_ms, uint32_t mode_arg) {
+// pick: the sampler / penalty arrays of generate_sample / generate_penalized, or nullptr (generate_greedy)
+static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                           const wrk_pick_args* pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg) {
+    if (!ctx || !m || !st || !first_tokens || (pick && pick->penalized && !pick->occ)) return WRK_E_ARG;
     LOCK(ctx);
-    WRK_HIP(ctx, hipSetDevice(ctx->device));
-    WRK_ARG(ctx, m->emb, "generate_greedy needs the device embedding table");
-    WRK_ARG(ctx, B >= 1 && B <= st->num_batch, "num_batch %u exceeds the state's %u", B, st->num_batch);
-    WRK_ARG(ctx, st->num_emb == m->d.num_emb && st->num_layer == m->d.num_layer, "state does not belong to this model");
     const uint32_t V = m->d.num_vocab;
-    for (uint32_t b = 0; b < B; ++b) WRK_ARG(ctx, first_tokens[b] < V, "first token %u out of vocab", first_tokens[b]);
+    wrk_pick_params pp;
+    int32_t rc = wrk_pick_pack(ctx, pick, B, V, pp);
+    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->emb != nullptr, m->d.num_emb, m->d.num_layer, V, first_tokens, B);
+    if (rc != WRK_OK) return rc;
+    const wrk::SampleParam* par = pp.par;
+    const wrk::PenaltyParam* pen = pp.pen;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     if (steps == 0) return WRK_OK;
     // mode: bits 0-7 = 0 op-by-op / 1 fused; bits 8-15 = number of concurrent pipelines the sequences are dealt over (0, 1: one)
@@ -827,7 +676,7 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
     // lanes: lane 0 is this model's own frame; lanes 1.. are clones sharing the weight handles
     while (m->lanes.size() + 1 < groups) {
         wrk_v7_model* lane = nullptr;
-        const int32_t rc = wrk_v7_model_create(ctx, &m->d, &lane);
+        rc = wrk_v7_model_create(ctx, &m->d, &lane);
         if (rc != WRK_OK) return rc;
         lane->act_dtype = m->act_dtype;
         m->lanes.push_back(lane);
@@ -840,110 +689,52 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
         m->lane_streams.push_back(s);
         m->lane_events.push_back(e);
     }
-    struct Lane { wrk_v7_model* mdl; uint32_t b0, nb; wrk_program* prog; };
-    std::vector<Lane> L(groups);
+    std::vector<wrk_lane> L(groups);
+    auto frame = [&](uint32_t g) { return g == 0 ? m : m->lanes[g - 1]; };
     for (uint32_t g = 0; g < groups; ++g) {
-        L[g].mdl = g == 0 ? m : m->lanes[g - 1];
+        wrk_v7_model* mdl = frame(g);
         // the persistent engine needs every CU for itself: two of them side by side (one per lane) would each hold part of the chip
         // and wait for the rest forever (until their bounded spins give up) -- concurrent pipelines keep the five-launch layer
-        L[g].mdl->engine_blocked = groups > 1;
+        mdl->engine_blocked = groups > 1;
         L[g].b0 = (uint32_t)((uint64_t)B * g / groups);
         L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
         // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
-        const int32_t rc = decode_prepare(ctx, L[g].mdl, st, first_tokens + L[g].b0, L[g].b0, L[g].nb, steps, mode, eager,
-                                          par ? par + L[g].b0 : nullptr, pen ? pen + L[g].b0 : nullptr, &L[g].prog);
+        rc = decode_prepare(ctx, mdl, st, first_tokens + L[g].b0, L[g].b0, L[g].nb, steps, mode, eager, par ? par + L[g].b0 : nullptr,
+                            pen ? pen + L[g].b0 : nullptr, &L[g].prog);
         if (rc != WRK_OK) return rc;
+        L[g].io = &mdl->s;
+        L[g].history = mdl->history;
     }
-    // every early return below leaves through this guard: the timing events are destroyed and, after an error, the lane streams are
-    // drained (a lane's queued step programs must not outlive a frame that the next call may reallocate) -- ADVICE r02
-    struct Guard {
-        wrk_v7_model* m; hipEvent_t e0 = nullptr, e1 = nullptr; bool ok = false;
-        ~Guard() {
-            if (!ok) { for (hipStream_t ls : m->lane_streams) hipStreamSynchronize(ls); hipStreamSynchronize(m->ctx->stream); }
-            if (e0) hipEventDestroy(e0);
-            if (e1) hipEventDestroy(e1);
-        }
-    } guard{m};
-    WRK_HIP(ctx, hipEventCreate(&guard.e0));
-    WRK_HIP(ctx, hipEventCreate(&guard.e1));
-    hipEvent_t e0 = guard.e0, e1 = guard.e1;
-    WRK_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    if (groups == 1) {
-        for (uint32_t i = 0; i < steps; ++i) {
-            if (eager) {
-                const int32_t rc = enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr, pen != nullptr);
-                if (rc != WRK_OK) return rc;
-            } else WRK_HIP(ctx, hipGraphLaunch(L[0].prog->exec, ctx->stream));
-        }
-    } else {
-        // every lane replays its own step program on its own stream; the lanes start together behind e0 and the submission
-        // stream joins them all before e1
-        for (uint32_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipStreamWaitEvent(m->lane_streams[g], e0, 0));
-        for (uint32_t i = 0; i < steps; ++i)
-            for (uint32_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipGraphLaunch(L[g].prog->exec, m->lane_streams[g]));
-        for (uint32_t g = 0; g < groups; ++g) {
-            WRK_HIP(ctx, hipEventRecord(m->lane_events[g], m->lane_streams[g]));
-            WRK_HIP(ctx, hipStreamWaitEvent(ctx->stream, m->lane_events[g], 0));
-        }
-    }
-    WRK_HIP(ctx, hipEventRecord(e1, ctx->stream));
-    WRK_HIP(ctx, hipEventSynchronize(e1));
-    float ms = 0.0f;
-    WRK_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-    if (elapsed_ms) *elapsed_ms = ms;
-    for (uint32_t g = 0; g < groups; ++g) {
-        const Lane& ln = L[g];
-        if (out_tokens) {
-            if (groups == 1) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.mdl->history, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
-            else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)B * 4, ln.mdl->history, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
-                                               hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits + (size_t)ln.b0 * V, ln.mdl->s.head_o, (size_t)ln.nb * V * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, steps,
+                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr, pen != nullptr); }, out_tokens, last_logits, elapsed_ms);
+    if (rc != WRK_OK) return rc;
     wrk::timing_report(ctx);
     for (uint32_t g = 0; g < groups; ++g) {
-        wrk_v7_engine_report(L[g].mdl->engine);
-        const int32_t rc = wrk_v7_engine_check(L[g].mdl->engine);
+        wrk_v7_engine_report(frame(g)->engine);
+        rc = wrk_v7_engine_check(frame(g)->engine);
         if (rc != WRK_OK) return rc;
     }
-    guard.ok = true;
     return WRK_OK;
 }
 
 int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
                                uint32_t steps, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg) {
-    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
-    return v7_generate(ctx, m, st, first_tokens, B, steps, nullptr, nullptr, out_tokens, last_logits, elapsed_ms, mode_arg);
+    return v7_generate(ctx, m, st, first_tokens, B, steps, nullptr, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                const float* temperature, const float* top_p, const uint32_t* seed, uint32_t* out_tokens, float* last_logits,
                                float* elapsed_ms, uint32_t mode_arg) {
-    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
-    LOCK(ctx);
-    std::vector<wrk::SampleParam> par;
-    const int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
-    if (rc != WRK_OK) return rc;
-    WRK_ARG(ctx, B >= 1, "num_batch 0");
-    return v7_generate(ctx, m, st, first_tokens, B, steps, par.data(), nullptr, out_tokens, last_logits, elapsed_ms, mode_arg);
+    const wrk_pick_args pick{temperature, top_p, seed};
+    return v7_generate(ctx, m, st, first_tokens, B, steps, &pick, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                   const float* temperature, const float* top_p, const uint32_t* seed, const float* presence,
                                   const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens, float* last_logits,
                                   float* elapsed_ms, uint32_t mode_arg) {
-    if (!ctx || !m || !st || !first_tokens || !occ) return WRK_E_ARG;
-    LOCK(ctx);
-    std::vector<wrk::SampleParam> par;
-    int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, B, par);
-    if (rc != WRK_OK) return rc;
-    WRK_ARG(ctx, B >= 1, "num_batch 0");
-    WRK_ARG(ctx, decay, "decay array required");
-    std::vector<wrk::PenaltyParam> pen;
-    rc = wrk_penalty_pack(ctx, occ, 0, B, m->d.num_vocab, presence, frequency, decay, pen);
-    if (rc != WRK_OK) return rc;
-    return v7_generate(ctx, m, st, first_tokens, B, steps, par.data(), pen.data(), out_tokens, last_logits, elapsed_ms, mode_arg);
+    const wrk_pick_args pick{temperature, top_p, seed, true, presence, frequency, decay, occ};
+    return v7_generate(ctx, m, st, first_tokens, B, steps, &pick, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 }  // extern "C"
@@ -962,46 +753,4 @@ int32_t wrk_v7_model::ensure_engine() {
     if (rc != WRK_OK) { engine = nullptr; engine_why = ctx->err; ctx->err = keep; }
     if (rc != WRK_OK && rc != WRK_E_UNSUPPORTED) return rc;
     return WRK_OK;
-}
-
-int32_t wrk_v7_model::ensure_history(size_t n) {
-    if (n <= history_cap && history) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();
-    if (history) hipFree(history);
-    history = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&history, n * 4 + 256));
-    history_cap = n;
-    return WRK_OK;
-}
-
-int32_t wrk_v7_model::ensure_sample_params(uint32_t n) {
-    if (n <= sample_par_cap && sample_par) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();                  // captured sampled steps hold the old pointer
-    if (sample_par) hipFree(sample_par);
-    sample_par = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&sample_par, (size_t)n * sizeof(wrk::SampleParam)));
-    sample_par_cap = n;
-    return WRK_OK;
-}
-
-int32_t wrk_v7_model::ensure_penalty(uint32_t n) {
-    if (n <= pen_cap && pen_par && pen_o) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();                  // captured penalised steps hold the old pointers
-    if (pen_par) hipFree(pen_par);
-    if (pen_o) hipFree(pen_o);
-    pen_par = nullptr;
-    pen_o = nullptr;
-    pen_cap = 0;
-    WRK_HIP(ctx, hipMalloc((void**)&pen_par, (size_t)n * sizeof(wrk::PenaltyParam)));
-    WRK_HIP(ctx, hipMalloc((void**)&pen_o, (size_t)n * d.num_vocab * 4));
-    pen_cap = n;
-    return WRK_OK;
-}
-
-int32_t wrk_buf_write_raw(wrk_ctx* ctx, void* dst, const void* src, size_t bytes) {
-    wrk_buf tmp{ctx, dst, bytes, {1}};
-    return wrk_buf_write(ctx, &tmp, 0, src, bytes);
 }

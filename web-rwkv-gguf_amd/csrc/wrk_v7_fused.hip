@@ -494,21 +494,10 @@ void wrk::timing_report(wrk_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------ host: enqueue one fused decode step
-void wrk_v7_model::drop_graphs() {
-    for (auto& kv : graphs) wrk_program_destroy(kv.second);
-    graphs.clear();
-}
-
 void wrk_v7_model::free_fused() {
     if (amax_val) hipFree(amax_val);
     if (amax_idx) hipFree(amax_idx);
     amax_val = nullptr; amax_idx = nullptr; amax_cap = 0;
-}
-
-static wrk::MatJob job(const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
-    wrk::MatJob j{m->data, m->aux, m->kind, m->flags, m->k, m->m, (uint32_t)m->row_bytes, in, out, act, 0};
-    j.scale = m->out_scale;
-    return j;
 }
 
 int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity_headers, bool from_tokens,
@@ -593,13 +582,13 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         static const uint32_t few_max = [] { const char* e = getenv("WRK_DMV_TOKENS"); const int v = e ? atoi(e) : 4; return (uint32_t)(v < 1 ? 1 : (v > 4 ? 4 : v)); }();
         single = fuse_ln && (T == 1 || (T <= few_max && contiguous)) && D <= 4096;
         if (single) {
-            MatJob k1[7] = {job(L.w_r, vec(s.x), vec(s.r), 0), job(L.w_k, vec(s.x), vec(s.k), 0), job(L.w_v, vec(s.x), vec(s.v), 0),
-                            job(L.w1, vec(s.x), vec(s.aux_w, d.lora_w), 0), job(L.a1, vec(s.x), vec(s.aux_a, d.lora_a), 0),
-                            job(L.g1, vec(s.x), vec(s.aux_g, d.lora_g), 0), job(li ? L.v1 : L.a1, vec(s.x), vec(s.aux_v, d.lora_v), 0)};
+            MatJob k1[7] = {mat_job(L.w_r, vec(s.x), vec(s.r), 0), mat_job(L.w_k, vec(s.x), vec(s.k), 0), mat_job(L.w_v, vec(s.x), vec(s.v), 0),
+                            mat_job(L.w1, vec(s.x), vec(s.aux_w, d.lora_w), 0), mat_job(L.a1, vec(s.x), vec(s.aux_a, d.lora_a), 0),
+                            mat_job(L.g1, vec(s.x), vec(s.aux_g, d.lora_g), 0), mat_job(li ? L.v1 : L.a1, vec(s.x), vec(s.aux_v, d.lora_v), 0)};
             for (MatJob& j : k1) j.pro = 1;
-            MatJob k5 = job(L.ffn_w_k, vec(s.x), vec(s.ffn_k, F), 0);
+            MatJob k5 = mat_job(L.ffn_w_k, vec(s.x), vec(s.ffn_k, F), 0);
             k5.pro = 1;
-            MatJob k6 = job(L.ffn_w_v, vec(s.ffn_k, F), vec(s.x), 0);
+            MatJob k6 = mat_job(L.ffn_w_v, vec(s.ffn_k, F), vec(s.x), 0);
             k6.has_res = 1; k6.res = vec(s.x);
             k6.carry_dst = (float*)s.x;     // any non-null pointer: classification only
             single = matvec_grouped(q, k1, li ? 7 : 6, ctx->num_cu, true) == 0 && matvec(q, &k5, 1, ctx->num_cu, true) == 0 &&
@@ -613,7 +602,7 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         const uint32_t state_stride = (S + 2) * D;       // floats between the state rows of consecutive sequences
         bool split_head = want_split && single && d.lora_w >= 8 && d.lora_a >= 8 && d.lora_g >= 8 && d.lora_v >= 8 && d.lora_g <= 512;
         if (split_head) {
-            MatJob k3 = job(L.w_o, vec(s.att_x), vec(s.x), 0);
+            MatJob k3 = mat_job(L.w_o, vec(s.att_x), vec(s.x), 0);
             k3.has_res = 1; k3.res = vec(s.x);
             k3.pro = 2; k3.ln_w = L.gn_w->ptr; k3.ln_b = L.gn_b->ptr; k3.mixw = s.g; k3.prev = (const float*)s.n;
             split_head = matvec(q, &k3, 1, ctx->num_cu, true) == 0;
@@ -634,12 +623,12 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
             LN(P, T);
         }
         {   // K1
-            MatJob jobs[7] = {job(L.w_r, vec(s.rx), vec(s.r), WRK_ACT_NONE), job(L.w_k, vec(s.kx), vec(s.k), WRK_ACT_NONE),
-                              job(L.w_v, vec(s.vx), vec(s.v), WRK_ACT_NONE),
-                              job(L.w1, vec(s.wx), vec(s.aux_w, d.lora_w), WRK_ACT_TANH),
-                              job(L.a1, vec(s.ax), vec(s.aux_a, d.lora_a), WRK_ACT_NONE),
-                              job(L.g1, vec(s.gx), vec(s.aux_g, d.lora_g), WRK_ACT_SIGMOID),
-                              job(li ? L.v1 : L.a1, vec(s.vx), vec(s.aux_v, d.lora_v), WRK_ACT_NONE)};
+            MatJob jobs[7] = {mat_job(L.w_r, vec(s.rx), vec(s.r), WRK_ACT_NONE), mat_job(L.w_k, vec(s.kx), vec(s.k), WRK_ACT_NONE),
+                              mat_job(L.w_v, vec(s.vx), vec(s.v), WRK_ACT_NONE),
+                              mat_job(L.w1, vec(s.wx), vec(s.aux_w, d.lora_w), WRK_ACT_TANH),
+                              mat_job(L.a1, vec(s.ax), vec(s.aux_a, d.lora_a), WRK_ACT_NONE),
+                              mat_job(L.g1, vec(s.gx), vec(s.aux_g, d.lora_g), WRK_ACT_SIGMOID),
+                              mat_job(li ? L.v1 : L.a1, vec(s.vx), vec(s.aux_v, d.lora_v), WRK_ACT_NONE)};
             if (single) {
                 const wrk_buf* mx[7] = {L.x_r, L.x_k, L.x_v, L.x_w, L.x_a, L.x_g, L.x_v};
                 for (int i = 0; i < 7; ++i) {
@@ -678,7 +667,7 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
             else head_kernel<16><<<dim3(H, T), 256, 0, q>>>(P);
         }
         {   // K3: x += W_o . att_x
-            MatJob j = job(L.w_o, vec(s.att_x), vec(s.x), WRK_ACT_NONE);
+            MatJob j = mat_job(L.w_o, vec(s.att_x), vec(s.x), WRK_ACT_NONE);
             j.has_res = 1; j.res = vec(s.x);
             if (split_head) {       // group norm + time_first + gate of the split head kernel's hand-over, in the prologue
                 j.pro = 2; j.pro_eps = 64.0e-5f; j.ln_w = L.gn_w->ptr; j.ln_b = L.gn_b->ptr; j.mixw = s.g; j.prev = (const float*)s.n;
@@ -696,7 +685,7 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
             LN(P, T);
         }
         {   // K5
-            MatJob j = job(L.ffn_w_k, vec(s.ffn_kx), vec(s.ffn_k, F), WRK_ACT_SQUARED_RELU);
+            MatJob j = mat_job(L.ffn_w_k, vec(s.ffn_kx), vec(s.ffn_k, F), WRK_ACT_SQUARED_RELU);
             if (single) {
                 j.in = vec(s.x);
                 j.pro = 1; j.pro_eps = 1.0e-5f; j.ln_w = L.ln2_w->ptr; j.ln_b = L.ln2_b->ptr; j.mixw = L.ffn_x_k->ptr; j.prev = rowf;
@@ -707,7 +696,7 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
             if (run_jobs(&j, 1) != 0) return wrk_fail(ctx, WRK_E_ARG, "fused K5 rejected");
         }
         {   // K6: x += W_v . relu(k)^2
-            MatJob j = job(L.ffn_w_v, vec(s.ffn_k, F), vec(s.x), WRK_ACT_NONE);
+            MatJob j = mat_job(L.ffn_w_v, vec(s.ffn_k, F), vec(s.x), WRK_ACT_NONE);
             j.has_res = 1; j.res = vec(s.x);
             if (single) { j.carry_src = s.ffn_x; j.carry_dst = rowf; j.tok_carry_src_stride = D; j.tok_carry_dst_stride = state_stride; }
             if (li == TIMED_LAYER) j.dbg = wrk::timing_slot(ctx, "K6 ffn value + residual");
@@ -722,7 +711,7 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         P.ln_w = (const f16*)ln_out_w->ptr; P.ln_b = (const f16*)ln_out_b->ptr; P.eps = 1.0e-5f;
         P.d = D; P.nmix = 0; P.ln_out = (f16*)s.head_x;
         LN(P, NH);
-        MatJob j = job(head, make_dense(s.head_x, WRK_F16, D, NH), make_dense(s.head_o, WRK_F32, V, NH), WRK_ACT_NONE);
+        MatJob j = mat_job(head, make_dense(s.head_x, WRK_F16, D, NH), make_dense(s.head_o, WRK_F32, V, NH), WRK_ACT_NONE);
         uint32_t nwg = 0;
         // a few header rows: the multi-token dmv kernel streams the head once for all of them, arg-max partials fused
         bool head_mv = NH < gemm_min_tokens();
