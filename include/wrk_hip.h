@@ -378,6 +378,34 @@ int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_stat
                                   const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens,
                                   float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
 
+/* Stop tokens in the decode loops.  Sequence b has the stop set stop_tokens[stop_offsets[b] .. stop_offsets[b + 1]) (CSR, num_batch + 1
+ * offsets, at most WRK_MAX_STOP_TOKENS ids each, every id < num_vocab).  Step i feeds x_i (x_0 = first_tokens[b]) and draws y_i; a
+ * sequence that has not ended and whose y_i is in its stop set ends at step i: out_lengths[b] = i + 1 (the stop token is part of the
+ * output); a sequence that never ends has out_lengths[b] = *steps_run.  out_tokens[j][b] for j < out_lengths[b] are the tokens the same
+ * call without stop sets produces; rows out_lengths[b] .. *steps_run repeat the stop token; rows at or after *steps_run are not written.
+ * After the call, state slot b is the state after consuming x_0 .. x_{out_lengths[b] - 1} (the stop token is drawn, not consumed): bit
+ * for bit what a call without stops and steps = out_lengths[b] leaves.  With penalties, slot b of the table has counted exactly the
+ * first out_lengths[b] tokens of the sequence.  last_logits[b] is the head output the last of those tokens was drawn from.
+ * The host submits steps in blocks of poll_steps (0: the default) and stops once every sequence has ended: *steps_run <= steps, and
+ * *steps_run <= (ceil(max(out_lengths) / poll_steps) + 2) * poll_steps.  While a sequence is still running, all `steps` run.
+ * The pick is wrk_v7_generate_greedy's (temperature, top_p, seed all NULL), wrk_v7_generate_sample's, or with `occ`
+ * wrk_v7_generate_penalized's (then the sampler arrays are required); both stop arrays NULL: no stops.  The stop sets are passed to
+ * the step program as data: one cached program serves any stop sets.  WRK_E_ARG before any launch on: a NULL opt / out_lengths /
+ * steps_run, offsets that do not start at 0 or decrease, more than WRK_MAX_STOP_TOKENS ids for a sequence, an id >= num_vocab, sampler
+ * arrays only partly given, penalty arrays without a table, and whatever the three calls above reject. */
+#define WRK_MAX_STOP_TOKENS 16
+typedef struct wrk_generate_options {
+    const float *temperature, *top_p;
+    const uint32_t *seed;
+    const float *presence, *frequency, *decay;
+    wrk_occurrence *occ;
+    const uint32_t *stop_tokens, *stop_offsets;
+    uint32_t poll_steps;
+} wrk_generate_options;
+int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
+                             uint32_t steps, const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths,
+                             float* last_logits_or_null, uint32_t* steps_run, float* elapsed_ms_or_null, uint32_t mode);
+
 /* ---------------------------------------------------------------- RWKV-6 (v6::Model, src/runtime/v6.rs)
  * Same chunk semantics, state layout ([D, S+2, B] per layer: v6.rs:150-214 == v7) and entry points as the V7
  * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph. */
@@ -434,6 +462,11 @@ int32_t wrk_v6_generate_penalized(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_stat
                                   uint32_t steps, const float* temperature, const float* top_p, const uint32_t* seed, const float* presence,
                                   const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens,
                                   float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
+
+/* as wrk_v7_generate_stop */
+int32_t wrk_v6_generate_stop(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
+                             uint32_t steps, const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths,
+                             float* last_logits_or_null, uint32_t* steps_run, float* elapsed_ms_or_null, uint32_t mode);
 
 #ifdef __cplusplus
 }

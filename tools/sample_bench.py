@@ -4,7 +4,11 @@ what the host alternative would cost per step: reading the logits back and a Num
 A third leg, alternating with the other two, is generate_penalized with the same sampler parameters and ChatRWKV-style repetition
 penalties (presence = frequency = 0.2, decay = 0.996, 16 banned tokens per sequence; --no-penalized skips it).
 
-    python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized]
+A fourth leg (--stop) is generate_stop with the same sampler parameters: the per-step cost of a stop program that never stops (16 stop
+ids per sequence that are not drawn) against the sampled leg, for every --poll block size and with polling off, and the wall time of a
+call with --stop-steps steps whose sequences all end by about step 32 against the same call without stops.
+
+    python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
 
 Prints one JSON object.
 """
@@ -35,6 +39,68 @@ def chat_rs_sample(probs, top_p, temp, u):
     return int(order[hit[0] if hit.size else 0])
 
 
+POLL_OFF = 0xffffffff       # one block: the live count is copied once, after the last step
+
+
+def stop_leg(rt, first, B, V, args):
+    """Every call starts from the same state (device snapshots), so the sampled run and the stopped runs draw the same tokens."""
+    skw = dict(temperature=args.temperature, top_p=args.top_p)
+    start = [rt.state_read(b) for b in range(B)]
+
+    def reset():
+        for b in range(B):
+            rt.state_write(start[b], b)
+
+    def wall(fn):
+        reset()
+        t0 = time.perf_counter()
+        r = fn()
+        return (time.perf_counter() - t0) * 1e3, r
+    reset()
+    drawn, _ = rt.generate_sample(first, args.steps, **skw)
+    used = set(drawn.reshape(-1).tolist())
+    never = [i for i in range(V - 1, -1, -1) if i not in used][:16]
+    polls = [int(x) for x in args.poll.split(",")] + [POLL_OFF]
+    per = {p: [] for p in polls}
+    samp, never_stopped = [], True
+    for p in polls:                                                      # capture and warm up
+        reset()
+        rt.generate_stop(first, 4, never, poll_steps=p, **skw)
+    for _ in range(args.reps):
+        reset()
+        samp.append(rt.generate_sample(first, args.steps, **skw)[1] / args.steps)
+        for p in polls:
+            reset()
+            tok, lens = rt.generate_stop(first, args.steps, never, poll_steps=p, **skw)
+            never_stopped &= bool((lens == args.steps).all()) and np.array_equal(tok, drawn)
+            per[p].append(rt.last_stop_ms / args.steps)
+    sm = float(np.median(samp))
+    res = {"never_stops": never_stopped, "sample_ms_per_step": round(sm, 5), "sample_ms_all": [round(x, 5) for x in samp],
+           "sample_spread_us": round((max(samp) - min(samp)) * 1e3, 2), "poll": []}
+    for p in polls:
+        m = float(np.median(per[p]))
+        res["poll"].append({"poll_steps": "off" if p == POLL_OFF else p, "stop_ms_per_step": round(m, 5),
+                            "stop_minus_sample_us": round((m - sm) * 1e3, 2), "stop_ms_all": [round(x, 5) for x in per[p]]})
+    # early exit: every sequence ends by about step 32 of a long call
+    reset()
+    head, _ = rt.generate_sample(first, 40, **skw)
+    stops = []
+    for b in range(B):
+        col = head[:, b].tolist()
+        j = next((j for j in range(24, 40) if col[j] not in col[:j]), None)
+        stops.append([col[j]] if j is not None else [])
+    long_plain, long_stop, runs = [], [], []
+    for _ in range(3):
+        long_plain.append(wall(lambda: rt.generate_sample(first, args.stop_steps, **skw))[0])
+        ms, (tok, lens) = wall(lambda: rt.generate_stop(first, args.stop_steps, stops, **skw))
+        long_stop.append(ms)
+        runs.append(int(tok.shape[0]))
+    res["early_exit"] = {"steps": args.stop_steps, "lengths_max": int(lens.max()), "steps_run": runs, "poll_steps": "default",
+                         "plain_wall_ms": [round(x, 3) for x in long_plain], "stop_wall_ms": [round(x, 3) for x in long_stop]}
+    reset()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -44,6 +110,9 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-p", type=float, default=0.9)
     ap.add_argument("--no-penalized", action="store_true")
+    ap.add_argument("--stop", action="store_true")
+    ap.add_argument("--poll", default="4,8,16,32,64")
+    ap.add_argument("--stop-steps", type=int, default=1024)
     args = ap.parse_args()
     import wrk
 
@@ -99,6 +168,8 @@ def main():
             pm = float(np.median(p))
             out["batches"][-1].update({"penalized_ms_per_step": round(pm, 5), "penalized_minus_sample_us": round((pm - sm) * 1e3, 2),
                                        "penalized_ms_all": [round(x, 5) for x in p]})
+        if args.stop:
+            out["batches"][-1]["stop"] = stop_leg(rt, first, B, V, args)
     if occ is not None:
         occ.close()
     rt.close()

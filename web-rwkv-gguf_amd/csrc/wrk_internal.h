@@ -197,6 +197,28 @@ void penalize_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_str
                    uint32_t dst_stride);
 void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, uint32_t ntok);
 
+// wrk_stop.hip: stop tokens in the decode loops.  One StopParam per sequence in a per-frame device buffer written
+// before every call: the stop ids are data, one captured program serves any stop sets.  done / length / end_token are the device's:
+// the step that draws a stop id sets them (length = step + 1: the stop token is part of the output)
+struct StopParam { uint32_t ids[WRK_MAX_STOP_TOKENS]; uint32_t count, done, length, end_token; };
+// as occurrence_update with ntok == 1, rows whose StopParam is done left alone (a finished sequence's slot is frozen)
+void occurrence_update_live(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const StopParam* stop);
+// a frame's stop buffers and the state they snapshot: sequences [b0, b0 + B) of a state [L][num_batch][slot] f32
+struct StopGeom {
+    float *state, *head_o, *snap_state, *snap_logits;
+    const uint32_t* just_ended; const StopParam* par; const uint32_t* counter; uint32_t* lengths;
+    uint32_t layers, num_batch, b0, v;
+    size_t slot;
+};
+// tokens / history <- drawn (or the ending token of a finished sequence), stop check, just_ended[b], *live -= sequences that ended,
+// counter += 1 last (the sampler reads it)
+void advance_stop(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, StopParam* par,
+                  uint32_t* just_ended, uint32_t* live, uint32_t b);
+// state slot and head_o row of every sequence with just_ended[b] -> snapshot (workgroups of the others return at once)
+void stop_snapshot(hipStream_t s, const StopGeom& g, uint32_t b, int num_cu);
+// snapshot -> state slot and head_o row of every sequence that is done; lengths[b] = its length, or *counter if it never ended
+void stop_restore(hipStream_t s, const StopGeom& g, uint32_t b, int num_cu);
+
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled
 void timing_report(wrk_ctx* ctx);

@@ -64,8 +64,8 @@ __global__ void __launch_bounds__(PEN_THREADS) penalize_rows_kernel(const float*
 // the weight of each token it owns right after that token's decay; g == 1: thread 0 of the workgroup that owns a token adds its weight
 // (in list order, so repeats add one after another) and nothing else is read or written
 template <bool VEC>
-__global__ void __launch_bounds__(PEN_THREADS) occurrence_update_kernel(uint32_t v, const PenaltyParam* __restrict__ par,
-                                                                        const uint32_t* __restrict__ tokens, uint32_t ntok) {
+__device__ __forceinline__ void occurrence_update_row(uint32_t v, const PenaltyParam* __restrict__ par, const uint32_t* __restrict__ tokens,
+                                                      uint32_t ntok) {
     const uint32_t r = blockIdx.y, tid = threadIdx.x;
     const PenaltyParam p = par[r];
     const uint32_t* tk = tokens + (size_t)r * ntok;
@@ -115,6 +115,21 @@ __global__ void __launch_bounds__(PEN_THREADS) occurrence_update_kernel(uint32_t
         if (hit & (1u << j)) p.flags[idx[j]] |= 1u;
 }
 
+template <bool VEC>
+__global__ void __launch_bounds__(PEN_THREADS) occurrence_update_kernel(uint32_t v, const PenaltyParam* __restrict__ par,
+                                                                        const uint32_t* __restrict__ tokens, uint32_t ntok) {
+    occurrence_update_row<VEC>(v, par, tokens, ntok);
+}
+
+// stop programs (wrk_stop.hip): one drawn token per row; the slot of a sequence that has ended stays as the stop token left it
+template <bool VEC>
+__global__ void __launch_bounds__(PEN_THREADS) occurrence_update_live_kernel(uint32_t v, const PenaltyParam* __restrict__ par,
+                                                                             const uint32_t* __restrict__ tokens,
+                                                                             const StopParam* __restrict__ stop) {
+    if (stop[blockIdx.y].done) return;
+    occurrence_update_row<VEC>(v, par, tokens, 1);
+}
+
 // rows of an occurrence table start at slot * v: 16-byte aligned counts (and 4-byte aligned flags) exactly when v % 4 == 0
 static bool pen_vec(uint32_t v) { return v % 4 == 0; }
 
@@ -132,6 +147,13 @@ void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam
     const dim3 grid((v + PEN_TILE - 1) / PEN_TILE, n);
     if (pen_vec(v)) occurrence_update_kernel<true><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, ntok);
     else occurrence_update_kernel<false><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, ntok);
+}
+
+void occurrence_update_live(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const StopParam* stop) {
+    if (n == 0 || v == 0) return;
+    const dim3 grid((v + PEN_TILE - 1) / PEN_TILE, n);
+    if (pen_vec(v)) occurrence_update_live_kernel<true><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, stop);
+    else occurrence_update_live_kernel<false><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, stop);
 }
 
 }  // namespace wrk

@@ -92,6 +92,21 @@ struct wrk_frame_common {
     float* pen_o = nullptr;                     // (the step programs read the table's pointers from here); pen_o: penalised logits [B][V]
     uint32_t pen_cap = 0;
     wrk_score_scratch score;                    // wrk_v*_score: targets / logprob / rank / slice partials of the header rows
+    // generate_stop (wrk_stop.hip), allocated by the first stop call only.  stop_par: per-sequence stop sets and end marks,
+    // written before every call; stop_flags: just_ended [cap], then the frame's live count, then lengths [cap]; stop_snap_state
+    // [cap][L][(S+2) D] and stop_snap_logits [cap][V]: slot and logits row of a sequence at the step that ended it
+    wrk::StopParam* stop_par = nullptr;
+    uint32_t* stop_flags = nullptr;
+    float *stop_snap_state = nullptr, *stop_snap_logits = nullptr;
+    uint32_t stop_cap = 0;
+    size_t stop_slot_cap = 0;                   // floats of one sequence's state snapshot (L * (S+2) * D)
+    uint32_t stop_vocab_cap = 0;
+    uint32_t* stop_just_ended() const { return stop_flags; }
+    uint32_t* stop_live() const { return stop_flags + stop_cap; }
+    uint32_t* stop_lengths() const { return stop_flags + stop_cap + 1; }
+    uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
+    uint32_t live_host_cap = 0;
+    std::vector<hipEvent_t> poll_events;        // [2 blocks][lanes]
     uint32_t wkv_nseq = 0;          // sequences of the job being enqueued (0: unknown): picks the WKV chunk kernel (wrk::time_mix_v7 / _v6)
 
     // b: tokens (generate: sequences | first sequence << 16); mode: the runner's mode and flag bits; nh: header rows
@@ -107,6 +122,8 @@ struct wrk_frame_common {
     int32_t ensure_history(size_t n);
     int32_t ensure_sample_params(uint32_t n);
     int32_t ensure_penalty(uint32_t n, uint32_t num_vocab);
+    int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
+    int32_t ensure_poll(uint32_t lanes);        // lane 0's frame: pinned live counts and events of the polled loop
     void release_common();          // destroy paths: programs, scratch and every buffer above
 };
 
@@ -140,12 +157,31 @@ int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, co
 // after the layers and the head: pick each sequence's next token from head_o -- the arg-max, or with `sampled` the sampler (wrk_sample.hip)
 // on the frame's parameters at step *counter; `penalized` (implies `sampled`): from pen_o = head_o penalised with the occurrence rows of
 // pen_par, which then count the drawn tokens (wrk_penalty.hip) -- and advance tokens / history / counter
-int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized);
+// stop: the step belongs to a stop program (wrk_enqueue_stop_tail instead of advance_tokens)
+struct wrk_stop_step { const wrk_v7_state* st; uint32_t b0; };
+int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
+                         const wrk_stop_step* stop = nullptr);
+// tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
+// (`penalized`), advance_stop, stop_snapshot of sequences [b0, b0 + B) of `st`
+int32_t wrk_enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool penalized, const wrk_stop_step& stop);
+
+// generate_stop: the options' stop sets validated into per-sequence rows (rows.size() == B; all counts 0 without stop arrays)
+int32_t wrk_stop_pack(wrk_ctx* ctx, const wrk_generate_options* opt, uint32_t B, uint32_t V, std::vector<wrk::StopParam>& rows);
+// the pick arrays of the options as generate_greedy / generate_sample / generate_penalized take them; *has_pick false: the arg-max
+int32_t wrk_stop_pick_args(wrk_ctx* ctx, const wrk_generate_options* opt, wrk_pick_args* pick, bool* has_pick);
+// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): stop buffers of
+// the frame, the B rows, zero just_ended, live = B
+int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk::StopParam* rows);
 
 // a pipeline of the timed replay: sequences [b0, b0 + nb) on their own frame; prog: its step program, or nullptr to enqueue eagerly
-struct wrk_lane { wrk::FrameIo* io; uint32_t* history; uint32_t b0, nb; wrk_program* prog; };
+struct wrk_lane { wrk::FrameIo* io; uint32_t* history; uint32_t b0, nb; wrk_program* prog; wrk_frame_common* frame = nullptr; };
+// generate_stop's loop: steps go out in blocks of poll_steps (0: WRK_STOP_POLL_DEFAULT), each followed by a copy of every lane's live
+// count to pinned memory and an event; before block k + 2 the host waits for block k's event and stops submitting once every count
+// is 0.  Then stop_restore, and lengths [B] / *steps_run come back.  Every lane carries its frame
+struct wrk_stop_run { wrk_v7_state* st; uint32_t poll_steps; uint32_t* out_lengths; uint32_t* steps_run; };
+static constexpr uint32_t WRK_STOP_POLL_DEFAULT = 16;
 // `steps` steps of every lane between two events: one lane on the submission stream (eagerly through `eager_step` without a program),
 // several on streams[g], joined through events[g].  Then tokens [steps][B] and last logits [B][V] come back
 int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const std::vector<hipStream_t>& streams, const std::vector<hipEvent_t>& events,
                       uint32_t B, uint32_t V, uint32_t steps, const std::function<int32_t()>& eager_step, uint32_t* out_tokens, float* last_logits,
-                      float* elapsed_ms);
+                      float* elapsed_ms, const wrk_stop_run* stop = nullptr);

@@ -109,12 +109,53 @@ int32_t wrk_frame_common::ensure_penalty(uint32_t n, uint32_t num_vocab) {
     return WRK_OK;
 }
 
+static void free_stop(wrk_frame_common& f) {
+    void* bufs[] = {f.stop_par, f.stop_flags, f.stop_snap_state, f.stop_snap_logits};
+    for (void* p : bufs) if (p) hipFree(p);
+    f.stop_par = nullptr; f.stop_flags = nullptr; f.stop_snap_state = nullptr; f.stop_snap_logits = nullptr;
+    f.stop_cap = 0; f.stop_slot_cap = 0; f.stop_vocab_cap = 0;
+}
+
+int32_t wrk_frame_common::ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V) {
+    const size_t slot = (size_t)L * (S + 2) * D;
+    if (stop_par && n <= stop_cap && slot == stop_slot_cap && V == stop_vocab_cap) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drop_graphs();
+    free_stop(*this);
+    WRK_HIP(ctx, hipMalloc((void**)&stop_par, (size_t)n * sizeof(wrk::StopParam)));
+    WRK_HIP(ctx, hipMalloc((void**)&stop_flags, ((size_t)2 * n + 1) * 4));
+    WRK_HIP(ctx, hipMalloc((void**)&stop_snap_state, (size_t)n * slot * 4));
+    WRK_HIP(ctx, hipMalloc((void**)&stop_snap_logits, (size_t)n * V * 4));
+    stop_cap = n; stop_slot_cap = slot; stop_vocab_cap = V;
+    return WRK_OK;
+}
+
+int32_t wrk_frame_common::ensure_poll(uint32_t lanes) {
+    if (live_host_cap < 2 * lanes) {
+        if (live_host) hipHostFree(live_host);
+        live_host = nullptr; live_host_cap = 0;
+        WRK_HIP(ctx, hipHostMalloc((void**)&live_host, (size_t)2 * lanes * 4, hipHostMallocDefault));
+        live_host_cap = 2 * lanes;
+    }
+    while (poll_events.size() < (size_t)2 * lanes) {
+        hipEvent_t e = nullptr;
+        WRK_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        poll_events.push_back(e);
+    }
+    return WRK_OK;
+}
+
 void wrk_frame_common::release_common() {
     drop_graphs();
     void* bufs[] = {scratch, history, sample_par, pen_par, pen_o};
     for (void* p : bufs) if (p) hipFree(p);
     scratch = nullptr; history = nullptr; sample_par = nullptr; pen_par = nullptr; pen_o = nullptr;
     score.release();
+    free_stop(*this);
+    if (live_host) hipHostFree(live_host);
+    live_host = nullptr; live_host_cap = 0;
+    for (hipEvent_t e : poll_events) hipEventDestroy(e);
+    poll_events.clear();
 }
 
 int32_t wrk_cached_program(wrk_ctx* ctx, std::map<wrk_frame_common::GraphKey, wrk_program*>& graphs, const wrk_frame_common::GraphKey& key,
@@ -211,7 +252,73 @@ int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, co
     return WRK_OK;
 }
 
-int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized) {
+// ------------------------------------------------------------------ stop tokens (wrk_stop.hip)
+int32_t wrk_stop_pack(wrk_ctx* ctx, const wrk_generate_options* opt, uint32_t B, uint32_t V, std::vector<wrk::StopParam>& rows) {
+    WRK_ARG(ctx, opt, "options required");
+    WRK_ARG(ctx, !opt->stop_tokens || opt->stop_offsets, "stop_tokens without stop_offsets");
+    rows.assign(B, wrk::StopParam{});
+    if (!opt->stop_offsets) return WRK_OK;
+    const uint32_t* off = opt->stop_offsets;
+    WRK_ARG(ctx, off[0] == 0, "stop_offsets[0] = %u: must be 0", off[0]);
+    for (uint32_t b = 0; b < B; ++b) {
+        WRK_ARG(ctx, off[b + 1] >= off[b], "stop_offsets[%u] = %u decreases", b + 1, off[b + 1]);
+        const uint32_t n = off[b + 1] - off[b];
+        WRK_ARG(ctx, n <= WRK_MAX_STOP_TOKENS, "sequence %u: %u stop tokens, at most %u", b, n, (uint32_t)WRK_MAX_STOP_TOKENS);
+        WRK_ARG(ctx, n == 0 || opt->stop_tokens, "stop_offsets name %u stop tokens, stop_tokens is NULL", n);
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t id = opt->stop_tokens[off[b] + k];
+            WRK_ARG(ctx, id < V, "sequence %u: stop token %u >= vocab %u", b, id, V);
+            rows[b].ids[k] = id;
+        }
+        rows[b].count = n;
+    }
+    return WRK_OK;
+}
+
+int32_t wrk_stop_pick_args(wrk_ctx* ctx, const wrk_generate_options* opt, wrk_pick_args* pick, bool* has_pick) {
+    WRK_ARG(ctx, opt, "options required");
+    const int given = (opt->temperature != nullptr) + (opt->top_p != nullptr) + (opt->seed != nullptr);
+    WRK_ARG(ctx, given == 0 || given == 3, "temperature, top_p and seed: all three arrays, or none for the arg-max");
+    WRK_ARG(ctx, opt->occ || (!opt->presence && !opt->frequency && !opt->decay), "penalty arrays without an occurrence table");
+    WRK_ARG(ctx, !opt->occ || given == 3, "penalties need the sampler arrays");
+    *has_pick = given == 3;
+    *pick = wrk_pick_args{opt->temperature, opt->top_p, opt->seed, opt->occ != nullptr, opt->presence, opt->frequency, opt->decay, opt->occ};
+    return WRK_OK;
+}
+
+int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk::StopParam* rows) {
+    wrk_ctx* ctx = f.ctx;
+    int32_t rc = f.ensure_stop(B, st->num_layer, st->head_size, st->num_emb, V);
+    if (rc != WRK_OK) return rc;
+    std::vector<uint32_t> flags(f.stop_cap + 1, 0u);      // just_ended = 0, then the live count
+    flags[f.stop_cap] = B;
+    rc = wrk_buf_write_raw(ctx, f.stop_par, rows, (size_t)B * sizeof(wrk::StopParam));
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.stop_flags, flags.data(), flags.size() * 4);
+    if (rc != WRK_OK) return rc;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+static wrk::StopGeom stop_geom(const wrk_frame_common& f, const wrk::FrameIo& io, const wrk_v7_state* st, uint32_t b0, uint32_t V) {
+    wrk::StopGeom g{};
+    g.state = st->data; g.head_o = io.head_o; g.snap_state = f.stop_snap_state; g.snap_logits = f.stop_snap_logits;
+    g.just_ended = f.stop_just_ended(); g.par = f.stop_par; g.counter = io.counter; g.lengths = f.stop_lengths();
+    g.layers = st->num_layer; g.num_batch = st->num_batch; g.b0 = b0; g.v = V;
+    g.slot = (size_t)(st->head_size + 2) * st->num_emb;
+    return g;
+}
+
+int32_t wrk_enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool penalized, const wrk_stop_step& stop) {
+    hipStream_t q = f.ctx->op_stream();
+    if (!f.stop_par || B > f.stop_cap || stop.b0 + B > stop.st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
+    if (penalized) wrk::occurrence_update_live(q, V, B, f.pen_par, io.argmax, f.stop_par);
+    wrk::advance_stop(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(), B);
+    wrk::stop_snapshot(q, stop_geom(f, io, stop.st, stop.b0, V), B, f.ctx->num_cu);
+    return WRK_OK;
+}
+
+int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
+                         const wrk_stop_step* stop) {
     hipStream_t q = f.ctx->op_stream();
     const float* logits = io.head_o;
     if (penalized) {
@@ -222,6 +329,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint
     if (!sampled) wrk::argmax_rows(q, io.head_o, V, V, B, io.argmax);
     else if (wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax) != 0)
         return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    if (stop) return wrk_enqueue_stop_tail(f, io, V, B, penalized, *stop);
     if (penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
     wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);
     return WRK_OK;
@@ -229,7 +337,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint
 
 int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const std::vector<hipStream_t>& streams, const std::vector<hipEvent_t>& events,
                       uint32_t B, uint32_t V, uint32_t steps, const std::function<int32_t()>& eager_step, uint32_t* out_tokens, float* last_logits,
-                      float* elapsed_ms) {
+                      float* elapsed_ms, const wrk_stop_run* stop) {
     const size_t groups = lanes.size();
     // every early return below leaves through this guard: the timing events are destroyed and, after an error, the lane streams are
     // drained (a lane's queued step programs must not outlive a frame that the next call may reallocate)
@@ -244,8 +352,54 @@ int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const st
     WRK_HIP(ctx, hipEventCreate(&guard.e0));
     WRK_HIP(ctx, hipEventCreate(&guard.e1));
     hipEvent_t e0 = guard.e0, e1 = guard.e1;
+    uint32_t* live_host = nullptr;
+    hipEvent_t* poll_events = nullptr;
+    if (stop) {
+        for (const wrk_lane& ln : lanes)
+            if (!ln.frame || !ln.frame->stop_par) return wrk_fail(ctx, WRK_E_ARG, "stop run on a lane without stop buffers");
+        const int32_t rc = lanes[0].frame->ensure_poll((uint32_t)groups);
+        if (rc != WRK_OK) return rc;
+        live_host = lanes[0].frame->live_host;
+        poll_events = lanes[0].frame->poll_events.data();
+    }
     WRK_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    if (groups == 1) {
+    if (stop) {
+        const uint32_t poll = stop->poll_steps ? stop->poll_steps : WRK_STOP_POLL_DEFAULT;
+        if (groups > 1)
+            for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipStreamWaitEvent(streams[g], e0, 0));
+        uint32_t run = 0;
+        for (uint32_t k = 0; run < steps; ++k) {
+            if (k >= 2) {       // block k - 2 has been followed by a whole block of queued work: the wait is an event wait, short or none
+                uint32_t live = 0;
+                for (size_t g = 0; g < groups; ++g) {
+                    WRK_HIP(ctx, hipEventSynchronize(poll_events[(k & 1) * groups + g]));
+                    live += live_host[(k & 1) * groups + g];
+                }
+                if (live == 0) break;
+            }
+            const uint32_t n = steps - run < poll ? steps - run : poll;
+            for (uint32_t i = 0; i < n; ++i) {
+                if (groups == 1 && !lanes[0].prog) {
+                    const int32_t rc = eager_step();
+                    if (rc != WRK_OK) return rc;
+                    continue;
+                }
+                for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipGraphLaunch(lanes[g].prog->exec, groups == 1 ? ctx->stream : streams[g]));
+            }
+            run += n;
+            for (size_t g = 0; g < groups; ++g) {
+                hipStream_t ls = groups == 1 ? ctx->stream : streams[g];
+                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, lanes[g].frame->stop_live(), 4, hipMemcpyDeviceToHost, ls));
+                WRK_HIP(ctx, hipEventRecord(poll_events[(k & 1) * groups + g], ls));
+            }
+        }
+        steps = run;
+        if (groups > 1)
+            for (size_t g = 0; g < groups; ++g) {
+                WRK_HIP(ctx, hipEventRecord(events[g], streams[g]));
+                WRK_HIP(ctx, hipStreamWaitEvent(ctx->stream, events[g], 0));
+            }
+    } else if (groups == 1) {
         for (uint32_t i = 0; i < steps; ++i) {
             if (lanes[0].prog) WRK_HIP(ctx, hipGraphLaunch(lanes[0].prog->exec, ctx->stream));
             else {
@@ -269,6 +423,15 @@ int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const st
     float ms = 0.0f;
     WRK_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
     if (elapsed_ms) *elapsed_ms = ms;
+    if (stop) {
+        // the frozen slots and logits rows go back (head_o is what the read-back below takes), the lengths come out
+        for (const wrk_lane& ln : lanes) {
+            wrk::stop_restore(ctx->stream, stop_geom(*ln.frame, *ln.io, stop->st, ln.b0, V), ln.nb, ctx->num_cu);
+            WRK_HIP(ctx, hipMemcpyAsync(stop->out_lengths + ln.b0, ln.frame->stop_lengths(), (size_t)ln.nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        WRK_LAUNCH_CHECK(ctx);
+        *stop->steps_run = steps;
+    }
     for (const wrk_lane& ln : lanes) {
         if (out_tokens) {
             if (groups == 1) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.history, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));

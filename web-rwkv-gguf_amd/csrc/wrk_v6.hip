@@ -16,7 +16,7 @@ struct V6Scratch : wrk::FrameIo {
     float* ks_part; uint32_t* ks_cnt; size_t ks_part_cap; uint32_t ks_cnt_cap;     // K-sliced GEMM scratch (2 .. 32 sequences), see MatJob
 };
 
-struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64)
+struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64 | stop 128)
     wrk_v6_model_desc d{};
     std::vector<wrk_v6_layer_desc> layers;
     V6Scratch s{};
@@ -621,19 +621,28 @@ int32_t wrk_v6_score(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint
 
 // pick: the sampler / penalty arrays of generate_sample / generate_penalized, or nullptr (generate_greedy); mode is used as given
 static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
-                           const wrk_pick_args* pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
+                           const wrk_pick_args* pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode,
+                           const wrk_generate_options* stop_opt = nullptr, uint32_t* out_lengths = nullptr, uint32_t* steps_run = nullptr) {
     if (!ctx || !m || !st || !first_tokens || (pick && pick->penalized && !pick->occ)) return WRK_E_ARG;
     LOCK(ctx);
     const uint32_t V = m->d.num_vocab;
     wrk_pick_params pp;
+    std::vector<wrk::StopParam> stop_rows;      // generate_stop: one row per sequence
     int32_t rc = wrk_pick_pack(ctx, pick, B, V, pp);
+    if (rc == WRK_OK && stop_opt) rc = wrk_stop_pack(ctx, stop_opt, B, V, stop_rows);
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->d.emb_f16 != nullptr, m->d.num_emb, m->d.num_layer, V, first_tokens, B);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
+    if (stop_opt) {
+        *steps_run = 0;
+        for (uint32_t b = 0; b < B; ++b) out_lengths[b] = 0;
+    }
     if (steps == 0) return WRK_OK;
     rc = m->ensure_scratch(B, B);
     if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, V, first_tokens, 0, B, steps, pp.par, pp.pen);
+    if (rc == WRK_OK && stop_opt) rc = wrk_stop_prepare(*m, st, V, B, stop_rows.data());
     if (rc != WRK_OK) return rc;
+    const wrk_stop_step ss{st, 0};
     const char* ng = getenv("WRK_NO_GRAPH");
     const bool eager = ng && ng[0] == '1';
     auto enqueue_step = [&]() -> int32_t {
@@ -642,14 +651,16 @@ static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, cons
         if (mode == 1) r = m->enqueue_fused_decode(st, B, B, true, 0);
         if (r == WRK_E_UNSUPPORTED) r = m->enqueue_ops(st, B, B, true);
         if (r != WRK_OK) return r;
-        return wrk_enqueue_pick(*m, m->s, V, B, pp.par != nullptr, pp.pen != nullptr);
+        return wrk_enqueue_pick(*m, m->s, V, B, pp.par != nullptr, pp.pen != nullptr, stop_opt ? &ss : nullptr);
     };
-    std::vector<wrk_lane> lane{{&m->s, m->history, 0, B, nullptr}};
+    std::vector<wrk_lane> lane{{&m->s, m->history, 0, B, nullptr, m}};
     if (!eager) {
-        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pp.par ? 32u : 0u) | (pp.pen ? 64u : 0u)}, enqueue_step, &lane[0].prog);
+        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pp.par ? 32u : 0u) | (pp.pen ? 64u : 0u) | (stop_opt ? 128u : 0u)}, enqueue_step,
+                                &lane[0].prog);
         if (rc != WRK_OK) return rc;
     }
-    return wrk_run_lanes(ctx, lane, {}, {}, B, V, steps, enqueue_step, out_tokens, last_logits, elapsed_ms);
+    const wrk_stop_run stop_run{st, stop_opt ? stop_opt->poll_steps : 0u, out_lengths, steps_run};
+    return wrk_run_lanes(ctx, lane, {}, {}, B, V, steps, enqueue_step, out_tokens, last_logits, elapsed_ms, stop_opt ? &stop_run : nullptr);
 }
 
 int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
@@ -670,6 +681,22 @@ int32_t wrk_v6_generate_penalized(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* s
                                   float* elapsed_ms, uint32_t mode) {
     const wrk_pick_args pick{temperature, top_p, seed, true, presence, frequency, decay, occ};
     return v6_generate(ctx, m, st, first_tokens, B, steps, &pick, out_tokens, last_logits, elapsed_ms, mode);
+}
+
+int32_t wrk_v6_generate_stop(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                             const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths, float* last_logits,
+                             uint32_t* steps_run, float* elapsed_ms, uint32_t mode) {
+    if (!ctx) return WRK_E_ARG;
+    wrk_pick_args pick{};
+    bool has_pick = false;
+    {
+        LOCK(ctx);
+        WRK_ARG(ctx, out_lengths && steps_run, "out_lengths and steps_run are required");
+        const int32_t rc = wrk_stop_pick_args(ctx, opt, &pick, &has_pick);
+        if (rc != WRK_OK) return rc;
+    }
+    return v6_generate(ctx, m, st, first_tokens, B, steps, has_pick ? &pick : nullptr, out_tokens, last_logits, elapsed_ms, mode, opt, out_lengths,
+                       steps_run);
 }
 
 }  // extern "C"

@@ -617,18 +617,21 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
 
 // one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers, pick each sequence's next token and advance
 // tokens / history / counter (wrk_enqueue_pick; the fused greedy path does both inside its head launch)
+// stop: a stop program's step (wrk_stop.hip) -- the fused greedy head keeps its arg-max and leaves the advance to the stop tail
 static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled,
-                                   bool penalized) {
+                                   bool penalized, bool stop = false) {
     int32_t rc;
+    const wrk_stop_step ss{st, b0};
     if (mode == 1 && m->act_dtype == WRK_F16) {
-        rc = m->enqueue_fused_decode(st, B, B, true, true, !sampled, !sampled, b0, true);
-        if (!sampled) return rc;
+        rc = m->enqueue_fused_decode(st, B, B, true, true, !sampled, !sampled && !stop, b0, true);
+        if (!sampled && (!stop || rc != WRK_OK)) return rc;
+        if (!sampled) return wrk_enqueue_stop_tail(*m, m->s, m->d.num_vocab, B, false, ss);
     } else {
         wrk::gather_rows_f16(ctx->op_stream(), m->emb->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
         rc = m->enqueue_ops(st, B, B, true);
     }
     if (rc != WRK_OK) return rc;
-    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, sampled, penalized);
+    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, sampled, penalized, stop ? &ss : nullptr);
 }
 
 // generate_greedy / generate_sample / generate_penalized, part 1: frame, token / cursor / sampler-parameter upload and the (cached)
@@ -636,32 +639,43 @@ static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* 
 // pen: their occurrence rows and penalties (with par), or nullptr
 static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t b0, uint32_t B,
                               uint32_t steps, uint32_t mode, bool eager, const wrk::SampleParam* par, const wrk::PenaltyParam* pen,
-                              wrk_program** prog_out) {
+                              const wrk::StopParam* stop, wrk_program** prog_out) {
     int32_t rc = m->ensure_scratch(B, B);
     if (rc == WRK_OK && B == 1 && mode == 1) rc = m->ensure_engine();
     if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, m->d.num_vocab, first_tokens, b0, B, steps, par, pen);
+    if (rc == WRK_OK && stop) rc = wrk_stop_prepare(*m, st, m->d.num_vocab, B, stop);
     *prog_out = nullptr;
     if (rc != WRK_OK || eager) return rc;
     // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo; sampled
     // steps have their own key bit, so greedy and sampled programs never alias, and so do penalised ones (bit 24, above every infer flag)
+    // and stop programs (bit 25)
     const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
-                                                             (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u) | (pen ? 1u << 24 : 0u)};
-    return wrk_cached_program(ctx, m->graphs, key, [&] { return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr); }, prog_out);
+                                                             (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u) | (pen ? 1u << 24 : 0u) |
+                                                             (stop ? 1u << 25 : 0u)};
+    return wrk_cached_program(ctx, m->graphs, key,
+                              [&] { return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr, stop != nullptr); }, prog_out);
 }
 
 // pick: the sampler / penalty arrays of generate_sample / generate_penalized, or nullptr (generate_greedy)
 static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
-                           const wrk_pick_args* pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg) {
+                           const wrk_pick_args* pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,
+                           const wrk_generate_options* stop_opt = nullptr, uint32_t* out_lengths = nullptr, uint32_t* steps_run = nullptr) {
     if (!ctx || !m || !st || !first_tokens || (pick && pick->penalized && !pick->occ)) return WRK_E_ARG;
     LOCK(ctx);
     const uint32_t V = m->d.num_vocab;
     wrk_pick_params pp;
+    std::vector<wrk::StopParam> stop_rows;      // generate_stop: one row per sequence
     int32_t rc = wrk_pick_pack(ctx, pick, B, V, pp);
+    if (rc == WRK_OK && stop_opt) rc = wrk_stop_pack(ctx, stop_opt, B, V, stop_rows);
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->emb != nullptr, m->d.num_emb, m->d.num_layer, V, first_tokens, B);
     if (rc != WRK_OK) return rc;
     const wrk::SampleParam* par = pp.par;
     const wrk::PenaltyParam* pen = pp.pen;
     if (elapsed_ms) *elapsed_ms = 0.0f;
+    if (stop_opt) {
+        *steps_run = 0;
+        for (uint32_t b = 0; b < B; ++b) out_lengths[b] = 0;
+    }
     if (steps == 0) return WRK_OK;
     // mode: bits 0-7 = 0 op-by-op / 1 fused; bits 8-15 = number of concurrent pipelines the sequences are dealt over (0, 1: one)
     const uint32_t mode = mode_arg & 0xffu;
@@ -700,13 +714,16 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
         L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
         // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
         rc = decode_prepare(ctx, mdl, st, first_tokens + L[g].b0, L[g].b0, L[g].nb, steps, mode, eager, par ? par + L[g].b0 : nullptr,
-                            pen ? pen + L[g].b0 : nullptr, &L[g].prog);
+                            pen ? pen + L[g].b0 : nullptr, stop_opt ? stop_rows.data() + L[g].b0 : nullptr, &L[g].prog);
         if (rc != WRK_OK) return rc;
         L[g].io = &mdl->s;
         L[g].history = mdl->history;
+        L[g].frame = mdl;
     }
+    const wrk_stop_run stop_run{st, stop_opt ? stop_opt->poll_steps : 0u, out_lengths, steps_run};
     rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, steps,
-                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr, pen != nullptr); }, out_tokens, last_logits, elapsed_ms);
+                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr, pen != nullptr, stop_opt != nullptr); }, out_tokens,
+                       last_logits, elapsed_ms, stop_opt ? &stop_run : nullptr);
     if (rc != WRK_OK) return rc;
     wrk::timing_report(ctx);
     for (uint32_t g = 0; g < groups; ++g) {
@@ -735,6 +752,22 @@ int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* s
                                   float* elapsed_ms, uint32_t mode_arg) {
     const wrk_pick_args pick{temperature, top_p, seed, true, presence, frequency, decay, occ};
     return v7_generate(ctx, m, st, first_tokens, B, steps, &pick, out_tokens, last_logits, elapsed_ms, mode_arg);
+}
+
+int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                             const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths, float* last_logits,
+                             uint32_t* steps_run, float* elapsed_ms, uint32_t mode_arg) {
+    if (!ctx) return WRK_E_ARG;
+    wrk_pick_args pick{};
+    bool has_pick = false;
+    {
+        LOCK(ctx);
+        WRK_ARG(ctx, out_lengths && steps_run, "out_lengths and steps_run are required");
+        const int32_t rc = wrk_stop_pick_args(ctx, opt, &pick, &has_pick);
+        if (rc != WRK_OK) return rc;
+    }
+    return v7_generate(ctx, m, st, first_tokens, B, steps, has_pick ? &pick : nullptr, out_tokens, last_logits, elapsed_ms, mode_arg, opt,
+                       out_lengths, steps_run);
 }
 
 }  // extern "C"

@@ -69,6 +69,16 @@ _P = C.c_void_p
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
 _f32p = C.POINTER(C.c_float)
+
+
+class GenerateOptions(C.Structure):
+    """wrk_generate_options: the pick (sampler arrays all NULL: arg-max; occ NULL: no penalties) and the stop sets (CSR) of
+    wrk_v*_generate_stop."""
+    _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
+                ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32)]
+
+
+MAX_STOP_TOKENS = 16        # WRK_MAX_STOP_TOKENS
 _TP = C.POINTER(TensorDesc)
 
 # name -> (restype, argtypes); every symbol declared in include/*.h
@@ -159,6 +169,10 @@ HIP_SYMBOLS = {
                                               _u32p, _f32p, _f32p, C.c_uint32]),
     "wrk_v6_generate_penalized": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _f32p, _f32p, _f32p, _P,
                                               _u32p, _f32p, _f32p, C.c_uint32]),
+    "wrk_v7_generate_stop": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(GenerateOptions), _u32p, _u32p, _f32p, _u32p,
+                                         _f32p, C.c_uint32]),
+    "wrk_v6_generate_stop": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(GenerateOptions), _u32p, _u32p, _f32p, _u32p,
+                                         _f32p, C.c_uint32]),
 }
 RT_SYMBOLS = {
     "wrk_host_last_error": (C.c_char_p, []),
@@ -965,6 +979,53 @@ class Runtime:
                           _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h, _ptr(out, _u32p),
                           _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
+
+    def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
+                      presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
+                      poll_steps: int = 0):
+        """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
+        at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
+        MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
+        are what the call without stops draws, the stop token last; later rows repeat it.  The state slot, the occurrence slot and the
+        logits row of a finished sequence are those of a `lengths[b]`-step call.  steps_run < steps once every sequence has ended (the host
+        looks every `poll_steps` steps; 0: the default)."""
+        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
+        ft = _u32(first_tokens)
+        B = ft.size
+        sets = list(stop)
+        if not (sets and all(isinstance(x, (list, tuple, np.ndarray)) for x in sets)):
+            sets = [sets] * B
+        if len(sets) != B:
+            raise ValueError(f"{len(sets)} stop sets for {B} sequences")
+        off = np.zeros(B + 1, np.uint32)
+        off[1:] = np.cumsum([len(x) for x in sets])
+        ids = _u32(np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in sets]) if B else [])
+        if ids.size == 0:
+            ids = np.zeros(1, np.uint32)
+        opt = GenerateOptions()
+        keep = []
+        sampled = temperature is not None or top_p is not None or seed is not None or occurrence is not None
+        if sampled:
+            t = _per_row(1.0 if temperature is None else temperature, B, np.float32)
+            p = _per_row(0.5 if top_p is None else top_p, B, np.float32)
+            sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
+            keep += [t, p, sd]
+            opt.temperature, opt.top_p, opt.seed = _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p)
+        if occurrence is not None:
+            ap, af, g = _per_row(presence, B, np.float32), _per_row(frequency, B, np.float32), _per_row(decay, B, np.float32)
+            keep += [ap, af, g]
+            opt.presence, opt.frequency, opt.decay, opt.occ = _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h
+        opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
+        out = np.zeros((steps, B), np.uint32)
+        lengths = np.zeros(B, np.uint32)
+        run, ms = C.c_uint32(), C.c_float()
+        logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
+        fn, mdl = (hip.wrk_v6_generate_stop, self.model6) if self.model6 else (hip.wrk_v7_generate_stop, self.model)
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, C.byref(opt), _ptr(out, _u32p), _ptr(lengths, _u32p),
+                          _ptr(logits, _f32p) if want_logits else None, C.byref(run), C.byref(ms), mode))
+        self.last_stop_ms = ms.value
+        out = out[:run.value]
+        return (out, lengths, logits) if want_logits else (out, lengths)
 
     def state_back(self, batch: int) -> np.ndarray:
         """`State::back(batch)` -> [L, S+2, D] f32."""
