@@ -406,6 +406,52 @@ int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* st
                              uint32_t steps, const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths,
                              float* last_logits_or_null, uint32_t* steps_run, float* elapsed_ms_or_null, uint32_t mode);
 
+/* A request queue in the decode loops: num_requests requests of different prompt and reply lengths are served on the num_batch slots of
+ * `state` in one call, with the slot bookkeeping on the device (the reference's examples/batch.rs: "multiple inferences of different
+ * length at the same time").  Request r has the prompt prompt_tokens[prompt_offsets[r] .. prompt_offsets[r + 1]) (CSR, at least one
+ * token), max_new[r] >= 1, the stop set stop_tokens[stop_offsets[r] .. stop_offsets[r + 1]) (CSR, at most WRK_MAX_STOP_TOKENS ids; both
+ * arrays NULL: no stops) and, per the pick, temperature / top_p / seed [r] and presence / frequency / decay [r].  The pick is one for the
+ * call, as in wrk_generate_options: no sampler arrays: arg-max; sampler arrays: wrk_v7_generate_sample's; `occ` and the penalty arrays
+ * (then the sampler arrays are required): wrk_v7_generate_penalized's on slot b's row of `occ`.
+ * Requests are dispatched in index order: at step 0 request b goes to slot b (b < min(num_batch, num_requests)); slots that end in the
+ * same step take the next requests in ascending slot order.  A slot that holds request r feeds p_0 .. p_{n-1} on consecutive steps; the
+ * draws of the first n - 1 of them are discarded (not counted in the occurrence row, not checked against the stop set, no sampler step).
+ * The draw of the step that feeds p_{n-1} is reply token y_0; from then on the slot feeds its own draws.  The sampler step of y_j is j:
+ * u = SplitMix64((seed[r] << 32) | j), so a reply does not depend on when the request was scheduled.  The request ends at the first j
+ * with y_j in its stop set (reason 1; the stop token is part of the reply), else at j + 1 == max_new[r] (reason 2).  A request still
+ * running when max_steps steps have run has reason 3 and the tokens drawn so far; one never dispatched has reason 0 and length 0.
+ * The step that ends a request resets its slot: the state slot to zeros (what wrk_v7_state_create leaves), or to a copy of init_state
+ * (a buffer of exactly one sequence's state in wrk_v7_state_read's layout: one shared prefix for every request); with penalties the
+ * slot's occurrence row to count 0 and no present bits -- banned bits are kept.  Then the slot takes the next request, or with none left
+ * idles on its last token.  Every slot that starts a request at step 0 is reset the same way: the call does not continue from what the
+ * slots held.  After the call the contents of the state slots and of rows [0, num_batch) of `occ` are unspecified.
+ * The host submits steps in blocks of poll_steps (0: the default) and stops once every request has ended or max_steps have run:
+ * *steps_run <= (ceil(needed / poll_steps) + 2) * poll_steps.  The requests are passed to the step program as data: one cached
+ * program serves any queue (queue programs never share a program with the other loops).
+ * Results, host u32 [num_requests]: lengths, reasons, slots, start_steps (the step that fed p_0); out_tokens: the reply of request r at
+ * out_tokens[o_r .. o_r + lengths[r]), o_r = max_new[0] + .. + max_new[r - 1]; *steps_run.
+ * WRK_E_ARG before any launch on: NULL opt / out or a NULL required array, num_requests == 0, an empty prompt, max_new == 0, offsets that
+ * do not start at 0 or decrease, a token or stop id >= num_vocab, more than WRK_MAX_STOP_TOKENS stop ids for a request, sampler arrays
+ * only partly given, penalty arrays without a table, a table with fewer slots than num_batch or of another vocabulary or context,
+ * init_state of another size, max_steps == 0, and whatever wrk_v7_generate_stop rejects for the same pick.  mode bits 8-15 > 1 (lanes):
+ * WRK_E_UNSUPPORTED -- a queue shared by several streams would need cross-stream atomics. */
+typedef struct wrk_queue_options {
+    uint32_t num_requests;
+    const uint32_t *prompt_tokens, *prompt_offsets, *max_new;
+    const uint32_t *stop_tokens, *stop_offsets;
+    const float *temperature, *top_p;
+    const uint32_t *seed;
+    const float *presence, *frequency, *decay;
+    wrk_occurrence *occ;
+    const wrk_buf *init_state;
+    uint32_t poll_steps, max_steps;
+} wrk_queue_options;
+typedef struct wrk_queue_result {
+    uint32_t *lengths, *reasons, *slots, *start_steps, *out_tokens, *steps_run;
+} wrk_queue_result;
+int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
+                              const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode);
+
 /* ---------------------------------------------------------------- RWKV-6 (v6::Model, src/runtime/v6.rs)
  * Same chunk semantics, state layout ([D, S+2, B] per layer: v6.rs:150-214 == v7) and entry points as the V7
  * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph. */
@@ -467,6 +513,10 @@ int32_t wrk_v6_generate_penalized(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_stat
 int32_t wrk_v6_generate_stop(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
                              uint32_t steps, const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths,
                              float* last_logits_or_null, uint32_t* steps_run, float* elapsed_ms_or_null, uint32_t mode);
+
+/* as wrk_v7_generate_queue */
+int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
+                              const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode);
 
 #ifdef __cplusplus
 }

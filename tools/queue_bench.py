@@ -1,0 +1,120 @@
+"""Throughput of the request queue on the bench's synthetic RWKV-7 1.5B Q4_K_M model: R = 8 * B requests with prompts of
+8 tokens and reply lengths drawn uniformly from [32, 256] with a fixed seed, enforced through max_new so that both sides do the same
+useful work.  Every B gets a runtime (and state) of its own with num_batch = B, so the queue's slot count and the waves' batch are the
+same number; the tool asserts that the queue used exactly the slots 0 .. B - 1.
+
+  (a) generate_queue: one call, the slots refilled on the device
+  (b) the way without it: waves of B requests; a wave takes its prompts in, then runs generate_stop from p_{n-1} for the longest reply
+      of the wave.  Two intakes are timed: `steps` (n - 1 one-step generate_sample calls, decode rate as in the queue) and `infer` (the
+      first n - 1 tokens of every prompt through Runtime.infer, the prefill path).  The faster one is the baseline and the JSON says
+      which.  A wave resets no state and stops nothing early (no stop ids; replies shorter than the wave's longest are cut by the host,
+      as a caller of generate_stop would cut them): neither changes the time of a step.
+  (c) the added cost per step of a queue program whose requests never end (one request per slot, max_new = steps) against generate_sample
+
+The legs alternate; medians of the wall time of whole calls (a, b) and of the HIP-event time per step (c).
+
+    python tools/queue_bench.py [--batches 16,32] [--reps 5] [--steps 64]
+
+Prints one JSON object.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "web-rwkv-gguf_amd"))
+
+import bench  # noqa: E402  (the bench's model writer; bench.py itself is not changed)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="1.5B")
+    ap.add_argument("--batches", default="16,32")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--prompt", type=int, default=8)
+    ap.add_argument("--requests-per-slot", type=int, default=8)
+    args = ap.parse_args()
+    import wrk
+
+    batches = [int(b) for b in args.batches.split(",")]
+    ctx = wrk.Context(0)
+    data = bench.make_model_gguf(args.model, seed=42)
+    skw = dict(temperature=1.0, top_p=0.9)
+    out = {"model": f"RWKV-7 {args.model} Q4_K_M (synthetic)", "prompt_tokens": args.prompt, "reply_lengths": "uniform [32, 256], seed 7",
+           "reps": args.reps, **skw,
+           "waves_note": "a wave resets no state and gives no per-request max_new: it runs the longest reply of the wave, the host cuts the rest",
+           "batches": []}
+    for B in batches:
+        rt = wrk.Runtime(ctx, wrk.GgufReader(data), num_batch=B)           # one runtime per B: the queue serves on rt.num_batch slots
+        V = rt.info.num_vocab
+        R = args.requests_per_slot * B
+        lens = np.random.default_rng(7).integers(32, 257, R).tolist()
+        prompts = [[(17 + 101 * r + 7 * i) % (V - 1) for i in range(args.prompt)] for r in range(R)]
+        useful = int(sum(lens))
+
+        def queue():
+            t0 = time.perf_counter()
+            res, run = rt.generate_queue(prompts, max_new=lens, **skw)
+            ms = (time.perf_counter() - t0) * 1e3
+            assert [len(t) for t, *_ in res] == lens
+            assert sorted({slot for _, _, slot, _ in res}) == list(range(B)), "the queue must serve on exactly B slots"
+            return ms, run
+
+        def waves(intake):
+            t0 = time.perf_counter()
+            run = 0
+            for w in range(0, R, B):
+                wave = prompts[w:w + B]
+                if intake == "infer" and args.prompt > 1:
+                    inp = wrk.RnnInput([p[:-1] for p in wave], 256)
+                    while sum(inp.remaining(b) for b in range(B)) > 0:
+                        rt.infer(inp)
+                else:
+                    for i in range(args.prompt - 1):
+                        rt.generate_sample([p[i] for p in wave], 1, **skw)
+                n = max(lens[w:w + B])
+                tok, _ = rt.generate_stop([p[-1] for p in wave], n, [], **skw)
+                assert tok.shape == (n, B)
+                run += args.prompt - 1 + n
+            return (time.perf_counter() - t0) * 1e3, run
+
+        first = [p[0] for p in prompts[:B]]
+        queue(), waves("steps"), waves("infer")                     # capture and warm up
+        rt.generate_sample(first, 4, **skw)
+        rt.generate_queue([[t] for t in first], max_new=4, **skw)
+        qa, ws, wi, ss, qs = [], [], [], [], []
+        for _ in range(args.reps):
+            qa.append(queue())
+            ws.append(waves("steps"))
+            wi.append(waves("infer"))
+            ss.append(rt.generate_sample(first, args.steps, **skw)[1] / args.steps)
+            res, run = rt.generate_queue([[t] for t in first], max_new=args.steps, max_steps=args.steps, poll_steps=0xffffffff, **skw)
+            assert run == args.steps and [len(t) for t, *_ in res] == [args.steps] * B
+            qs.append(rt.last_queue_ms / args.steps)
+        med = lambda runs: float(np.median([m for m, _ in runs]))   # noqa: E731
+        qm, wsm, wim = med(qa), med(ws), med(wi)
+        wm, intake = (wsm, "one-step generate_sample calls") if wsm <= wim else (wim, "Runtime.infer of the first n - 1 prompt tokens")
+        out["batches"].append({
+            "batch": B, "slots": B, "requests": R, "reply_tokens": useful,
+            "queue_ms": round(qm, 2), "queue_steps": qa[0][1], "queue_reply_tokens_per_s": round(useful / qm * 1e3, 1),
+            "waves_ms": round(wm, 2), "waves_steps": ws[0][1], "waves_reply_tokens_per_s": round(useful / wm * 1e3, 1),
+            "waves_prompt_intake": intake, "waves_ms_intake_steps": round(wsm, 2), "waves_ms_intake_infer": round(wim, 2),
+            "queue_ms_all": [round(m, 2) for m, _ in qa], "waves_steps_ms_all": [round(m, 2) for m, _ in ws],
+            "waves_infer_ms_all": [round(m, 2) for m, _ in wi],
+            "sample_ms_per_step": round(float(np.median(ss)), 5), "queue_never_ending_ms_per_step": round(float(np.median(qs)), 5),
+            "queue_minus_sample_us": round((float(np.median(qs)) - float(np.median(ss))) * 1e3, 2),
+        })
+        rt.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

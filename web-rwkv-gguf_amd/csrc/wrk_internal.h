@@ -172,8 +172,9 @@ void gather_rows_any(hipStream_t s, DTensor in, const uint32_t* rows, DTensor ou
 void argmax_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t v_stride, uint32_t n, uint32_t* out);
 
 // wrk_sample.hip: examples/chat.rs:150-190 Sampler::sample per row (nucleus cut at top_p, temperature inside it, inverse-CDF draw with
-// the SplitMix64 uniform of (seed, *step)); temperature or top_p == 0 is argmax_rows.  -1: v == 0, v > SAMPLE_MAX_VOCAB or stride < v
-struct SampleParam { float temperature, top_p; uint32_t seed, pad; };
+// the SplitMix64 uniform of (seed, *step - step_base)); temperature or top_p == 0 is argmax_rows.  -1: v == 0, v > SAMPLE_MAX_VOCAB or
+// stride < v.  step_base is 0 everywhere but in queue programs (wrk_queue.hip), where a request's draws are numbered from its own reply
+struct SampleParam { float temperature, top_p; uint32_t seed, step_base; };
 static constexpr uint32_t SAMPLE_MAX_VOCAB = 1u << 20;
 int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
                 uint32_t* out);
@@ -218,6 +219,37 @@ void advance_stop(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32
 void stop_snapshot(hipStream_t s, const StopGeom& g, uint32_t b, int num_cu);
 // snapshot -> state slot and head_o row of every sequence that is done; lengths[b] = its length, or *counter if it never ended
 void stop_restore(hipStream_t s, const StopGeom& g, uint32_t b, int num_cu);
+
+// wrk_queue.hip: a request queue in the decode loops.  R requests are served on the B slots of a state; the slot
+// bookkeeping is device data in per-frame buffers written before every call, so one captured program serves any queue.
+// QueueReq: one request (prompt = pool[prompt_off .. + prompt_len), its pick parameters and stop set).  QueueSlot: what slot b is doing --
+// phase says what the draw of the NEXT step is: QUEUE_PROMPT a draw to discard (the step feeds a prompt token that is not the last),
+// QUEUE_REPLY reply token number `reply`, QUEUE_IDLE nothing.  QueueLog: per request, written as it runs (reason 3 while running)
+enum : uint32_t { QUEUE_IDLE = 0, QUEUE_PROMPT = 1, QUEUE_REPLY = 2 };
+struct QueueReq {
+    uint32_t prompt_off, prompt_len, max_new, seed;
+    float temperature, top_p, presence, frequency, decay;
+    uint32_t stop_count, stop_ids[WRK_MAX_STOP_TOKENS];
+};
+struct QueueSlot { uint32_t req, pos, reply, phase; };
+struct QueueLog { uint32_t length, reason, slot, start_step; };
+struct QueueCtl { uint32_t next_request, num_requests, live, pad; const float* init_state; };     // init_state: [L][slot] f32 or nullptr
+struct QueueBufs {
+    QueueSlot* slots; const QueueReq* reqs; const uint32_t* pool; QueueLog* log; QueueCtl* ctl;
+    uint32_t* started;              // [B]: 1 when the slot took a new request in this step (written for every slot by every launch)
+    SampleParam* sample_par;        // the frame's rows, or nullptr (arg-max)
+    PenaltyParam* pen_par;          // the frame's rows, or nullptr (no penalties)
+};
+// takes advance_tokens' place in a queue program: history <- drawn; per slot the next prompt token or the draw, stop / max_new check,
+// next requests to the slots that ended (ascending slot order), their parameters into the slot's rows, started[b], the log,
+// ctl->live -= ended, counter += 1 last (the sampler reads it)
+void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q, uint32_t b);
+// slots [b0, b0 + b) of a state [L][num_batch][slot] f32 with started[b]: zero fill, or a copy of ctl->init_state; with pen_par their
+// occurrence rows: count = 0, present bit cleared, banned bit kept (v: vocabulary).  Workgroups of the other slots return at once
+struct QueueGeom { float* state; uint32_t layers, num_batch, b0, v; size_t slot; };
+void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t b, int num_cu);
+// as occurrence_update with ntok == 1, for the rows whose draw of this step is a reply token (slots[r].phase == QUEUE_REPLY)
+void occurrence_update_queue(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const QueueSlot* slots);
 
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled

@@ -130,6 +130,15 @@ __global__ void __launch_bounds__(PEN_THREADS) occurrence_update_live_kernel(uin
     occurrence_update_row<VEC>(v, par, tokens, 1);
 }
 
+// queue programs (wrk_queue.hip): only a draw that is a reply token counts -- not a prompt-phase draw, not an idle slot's
+template <bool VEC>
+__global__ void __launch_bounds__(PEN_THREADS) occurrence_update_queue_kernel(uint32_t v, const PenaltyParam* __restrict__ par,
+                                                                              const uint32_t* __restrict__ tokens,
+                                                                              const QueueSlot* __restrict__ slots) {
+    if (slots[blockIdx.y].phase != QUEUE_REPLY) return;
+    occurrence_update_row<VEC>(v, par, tokens, 1);
+}
+
 // rows of an occurrence table start at slot * v: 16-byte aligned counts (and 4-byte aligned flags) exactly when v % 4 == 0
 static bool pen_vec(uint32_t v) { return v % 4 == 0; }
 
@@ -154,6 +163,13 @@ void occurrence_update_live(hipStream_t s, uint32_t v, uint32_t n, const Penalty
     const dim3 grid((v + PEN_TILE - 1) / PEN_TILE, n);
     if (pen_vec(v)) occurrence_update_live_kernel<true><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, stop);
     else occurrence_update_live_kernel<false><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, stop);
+}
+
+void occurrence_update_queue(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const QueueSlot* slots) {
+    if (n == 0 || v == 0) return;
+    const dim3 grid((v + PEN_TILE - 1) / PEN_TILE, n);
+    if (pen_vec(v)) occurrence_update_queue_kernel<true><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, slots);
+    else occurrence_update_queue_kernel<false><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, slots);
 }
 
 }  // namespace wrk

@@ -1,0 +1,162 @@
+// A request queue in the decode loops for gfx950.  R requests of different prompt and reply lengths are served on the
+// B slots of a state inside one call: a slot whose request ends is reset and takes the next request in the same step program, so no
+// slot waits for the longest reply of a batch.  A slot is a fixed-size recurrent state plus one "next token" word, so a refill is a
+// fill of that state and another token in io.tokens; a prompt is taken in at decode rate by feeding its tokens in place of the draws.
+//
+//   advance_queue   takes advance_tokens' place in a queue program: one thread owns a slot, pops the next prompt token or takes the
+//                   draw, checks the stop set and max_new, deals the next requests to the slots that ended (exclusive scan over the slot
+//                   index from one next_request word), copies their parameters into the slot's rows, and moves the step counter last
+//   queue_reset     grid (layer x slice, slot): every workgroup reads started[b] and leaves when it is 0; else zero fill / init_state
+//                   copy of the slot, and a second small grid for the slot's occurrence row when the program is penalised
+//
+// started[b] is written by EVERY advance_queue launch for every slot, so the flag a reset launch reads was written by the launch in front
+// of it in the same stream; nothing has to clear it.  Plain vector stores only; no atomics; no kernel waits on another.
+#include "wrk_device.h"
+#include "wrk_runner.h"
+
+namespace wrk {
+
+static constexpr uint32_t QUEUE_THREADS = 256;
+static constexpr uint32_t QUEUE_CHUNK = QUEUE_THREADS * 4;     // floats a workgroup moves per pass (16 bytes per thread)
+static constexpr uint32_t QUEUE_WAVES = QUEUE_THREADS / 64;
+
+// slots are owned by the threads of ONE workgroup (B <= 256, as advance_stop)
+__global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                                      uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
+                                                                      const QueueBufs Q, uint32_t b) {
+    __shared__ uint32_t wave_ended[QUEUE_WAVES];
+    const uint32_t step = *counter;
+    const uint32_t next = Q.ctl->next_request, live = Q.ctl->live, num_requests = Q.ctl->num_requests;
+    const uint32_t i = threadIdx.x, lane = i & 63u, wave = i >> 6;
+    int ended = 0;
+    QueueSlot s{0u, 0u, 0u, QUEUE_IDLE};
+    if (i < b) {
+        s = Q.slots[i];
+        const uint32_t y = drawn[i];
+        history[(size_t)step * b + i] = y;     // a prompt-phase or idle draw too: the host cuts the replies out by the log
+        if (s.phase == QUEUE_PROMPT) {
+            const QueueReq* r = Q.reqs + s.req;
+            s.pos += 1;
+            tokens[i] = Q.pool[r->prompt_off + s.pos];
+            if (s.pos + 1 == r->prompt_len) s.phase = QUEUE_REPLY;
+        } else if (s.phase == QUEUE_REPLY) {
+            const QueueReq* r = Q.reqs + s.req;
+            tokens[i] = y;
+            const uint32_t n = r->stop_count < WRK_MAX_STOP_TOKENS ? r->stop_count : WRK_MAX_STOP_TOKENS;
+            int hit = 0;
+            for (uint32_t k = 0; k < n; ++k) hit |= (r->stop_ids[k] == y);
+            s.reply += 1;
+            Q.log[s.req].length = s.reply;
+            const uint32_t reason = hit ? 1u : (s.reply == r->max_new ? 2u : 0u);
+            if (reason) { Q.log[s.req].reason = reason; ended = 1; }
+        }                                       // idle: tokens[i] stays, a valid id keeps flowing through the embedding gather
+    }
+    // exclusive scan of `ended` over the slot index: in-wave by ballot, across the four waves through LDS
+    const unsigned long long mask = __ballot(ended);
+    const uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_ended[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();                            // also orders every read of *counter and *ctl before their update
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < QUEUE_WAVES; ++w) {
+        if (w < wave) before += wave_ended[w];
+        total += wave_ended[w];
+    }
+    if (i < b) {
+        uint32_t started = 0;
+        if (ended) {
+            const uint32_t r = next + before + rank;
+            if (r < num_requests) {
+                const QueueReq* q = Q.reqs + r;
+                s = QueueSlot{r, 0u, 0u, q->prompt_len == 1 ? QUEUE_REPLY : QUEUE_PROMPT};
+                tokens[i] = Q.pool[q->prompt_off];
+                // reply token j is drawn at step (step + 1) + prompt_len - 1 + j: its sampler step is j whenever it is scheduled
+                if (Q.sample_par) Q.sample_par[i] = SampleParam{q->temperature, q->top_p, q->seed, step + q->prompt_len};
+                if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
+                Q.log[r] = QueueLog{0u, 3u, i, step + 1};
+                started = 1;
+            } else {
+                s.phase = QUEUE_IDLE;
+            }
+        }
+        Q.slots[i] = s;
+        Q.started[i] = started;
+    }
+    if (i == 0) {
+        if (total) { Q.ctl->next_request = next + total; Q.ctl->live = live - total; }
+        *counter = step + 1;
+    }
+}
+
+struct QueueResetArgs {
+    float* state;               // [L][num_batch][slot] f32
+    const uint32_t* started;
+    const QueueCtl* ctl;
+    uint32_t layers, slices, num_batch, b0, vec;
+    size_t slot;                // (S + 2) * D
+};
+
+__global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_state_kernel(const QueueResetArgs A) {
+    const uint32_t b = blockIdx.y;
+    if (A.started[b] == 0) return;
+    const uint32_t l = blockIdx.x / A.slices, part = blockIdx.x - l * A.slices;
+    float* dst = A.state + ((size_t)l * A.num_batch + A.b0 + b) * A.slot;
+    const float* init = A.ctl->init_state;
+    const float* src = init ? init + (size_t)l * A.slot : nullptr;
+    const size_t n = A.slot;
+    if (A.vec && (((uintptr_t)src) & 15u) == 0) {
+        for (size_t i = (size_t)part * QUEUE_CHUNK + threadIdx.x * 4; i < n; i += (size_t)A.slices * QUEUE_CHUNK)
+            *(f32x4*)(dst + i) = src ? *(const f32x4*)(src + i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    } else {
+        for (size_t i = (size_t)part * QUEUE_THREADS + threadIdx.x; i < n; i += (size_t)A.slices * QUEUE_THREADS) dst[i] = src ? src[i] : 0.0f;
+    }
+}
+
+// occurrence row of a slot that starts a request: count = 0, present cleared, banned kept.  ceil(v / 1024) workgroups per slot, thread
+// tid owns the 4 elements at 4 * tid (VEC: rows start 16-byte aligned, v % 4 == 0, as wrk_penalty.hip) or tid + 256 * j
+template <bool VEC>
+__global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_occurrence_kernel(uint32_t v, const PenaltyParam* __restrict__ par,
+                                                                               const uint32_t* __restrict__ started) {
+    const uint32_t b = blockIdx.y, tid = threadIdx.x;
+    if (started[b] == 0) return;
+    const PenaltyParam p = par[b];
+    const uint32_t a = blockIdx.x * QUEUE_CHUNK;
+    if (VEC) {
+        const uint32_t i = a + tid * 4;
+        if (i >= v) return;
+        *(f32x4*)(p.count + i) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t* f = (uint32_t*)(p.flags + i);
+        *f = *f & 0x02020202u;
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t i = a + j * QUEUE_THREADS + tid;
+            if (i < v) { p.count[i] = 0.0f; p.flags[i] = p.flags[i] & 2u; }
+        }
+    }
+}
+
+void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q, uint32_t b) {
+    advance_queue_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, b);
+}
+
+void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t b, int num_cu) {
+    if (b == 0) return;
+    QueueResetArgs A{};
+    A.state = g.state; A.started = q.started; A.ctl = q.ctl;
+    A.layers = g.layers; A.num_batch = g.num_batch; A.b0 = g.b0; A.slot = g.slot;
+    A.vec = g.slot % 4 == 0;
+    // slices of a layer's slot: layers * slices workgroups come to about two per CU, so that one starting request's fill (13 MB at the
+    // 1.5B shape) runs on the whole chip, and no slice is smaller than one pass
+    const uint32_t per_pass = A.vec ? QUEUE_CHUNK : QUEUE_THREADS;
+    const uint32_t max_slices = (uint32_t)((g.slot + per_pass - 1) / per_pass);
+    const uint32_t want = (2u * (uint32_t)num_cu + g.layers - 1) / g.layers;
+    A.slices = want < 1 ? 1 : (want > max_slices ? max_slices : want);
+    queue_reset_state_kernel<<<dim3(A.layers * A.slices, b), QUEUE_THREADS, 0, s>>>(A);
+    if (!q.pen_par || g.v == 0) return;
+    const dim3 grid((g.v + QUEUE_CHUNK - 1) / QUEUE_CHUNK, b);
+    if (g.v % 4 == 0) queue_reset_occurrence_kernel<true><<<grid, QUEUE_THREADS, 0, s>>>(g.v, q.pen_par, q.started);
+    else queue_reset_occurrence_kernel<false><<<grid, QUEUE_THREADS, 0, s>>>(g.v, q.pen_par, q.started);
+}
+
+}  // namespace wrk

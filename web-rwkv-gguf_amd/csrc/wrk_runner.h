@@ -104,6 +104,17 @@ struct wrk_frame_common {
     uint32_t* stop_just_ended() const { return stop_flags; }
     uint32_t* stop_live() const { return stop_flags + stop_cap; }
     uint32_t* stop_lengths() const { return stop_flags + stop_cap + 1; }
+    // generate_queue (wrk_queue.hip), allocated by the first queue call only and written before every call: slot rows and
+    // started flags [slot cap], the control words, the request table and log [request cap], the prompt token pool [pool cap]
+    wrk::QueueSlot* queue_slots = nullptr;
+    uint32_t* queue_started = nullptr;
+    wrk::QueueCtl* queue_ctl = nullptr;
+    wrk::QueueReq* queue_reqs = nullptr;
+    wrk::QueueLog* queue_log = nullptr;
+    uint32_t* queue_pool = nullptr;
+    uint32_t queue_slot_cap = 0, queue_req_cap = 0;
+    size_t queue_pool_cap = 0;
+    uint32_t* queue_live() const { return &queue_ctl->live; }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
     uint32_t live_host_cap = 0;
     std::vector<hipEvent_t> poll_events;        // [2 blocks][lanes]
@@ -123,6 +134,7 @@ struct wrk_frame_common {
     int32_t ensure_sample_params(uint32_t n);
     int32_t ensure_penalty(uint32_t n, uint32_t num_vocab);
     int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
+    int32_t ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens);
     int32_t ensure_poll(uint32_t lanes);        // lane 0's frame: pinned live counts and events of the polled loop
     void release_common();          // destroy paths: programs, scratch and every buffer above
 };
@@ -157,13 +169,36 @@ int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, co
 // after the layers and the head: pick each sequence's next token from head_o -- the arg-max, or with `sampled` the sampler (wrk_sample.hip)
 // on the frame's parameters at step *counter; `penalized` (implies `sampled`): from pen_o = head_o penalised with the occurrence rows of
 // pen_par, which then count the drawn tokens (wrk_penalty.hip) -- and advance tokens / history / counter
-// stop: the step belongs to a stop program (wrk_enqueue_stop_tail instead of advance_tokens)
-struct wrk_stop_step { const wrk_v7_state* st; uint32_t b0; };
+// stop: the step belongs to a stop program (wrk_enqueue_stop_tail instead of advance_tokens), or with `queue` to a queue program
+// (wrk_enqueue_queue_tail)
+struct wrk_stop_step { const wrk_v7_state* st; uint32_t b0; bool queue = false; };
 int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
                          const wrk_stop_step* stop = nullptr);
 // tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
 // (`penalized`), advance_stop, stop_snapshot of sequences [b0, b0 + B) of `st`
 int32_t wrk_enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool penalized, const wrk_stop_step& stop);
+
+// tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
+// token (`penalized`), advance_queue, queue_reset of slots [b0, b0 + B) of `st`
+int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop);
+
+// generate_queue: the options validated (WRK_E_ARG before any launch) into the request table, the prompt pool and the pick rows the slots
+// start with.  first_tokens [B]: p_0 of the requests dispatched at step 0, a valid id for the slots that start idle
+struct wrk_queue_pack {
+    uint32_t R = 0, max_steps = 0, poll_steps = 0;
+    bool sampled = false, penalized = false;
+    std::vector<wrk::QueueReq> reqs; std::vector<uint32_t> pool, first_tokens;
+    std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen;
+    const float* init_state = nullptr;
+};
+int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
+                        wrk_queue_result* out, wrk_queue_pack& pk);
+// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): queue buffers of the
+// frame, the tables, the slots that start at step 0, live = R; then queue_reset of those slots on the submission stream
+int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk_queue_pack& pk);
+// after the loop: the log and the history rows come back and the replies are cut out of them
+int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,
+                         wrk_queue_result* out);
 
 // generate_stop: the options' stop sets validated into per-sequence rows (rows.size() == B; all counts 0 without stop arrays)
 int32_t wrk_stop_pack(wrk_ctx* ctx, const wrk_generate_options* opt, uint32_t B, uint32_t V, std::vector<wrk::StopParam>& rows);
@@ -178,7 +213,8 @@ struct wrk_lane { wrk::FrameIo* io; uint32_t* history; uint32_t b0, nb; wrk_prog
 // generate_stop's loop: steps go out in blocks of poll_steps (0: WRK_STOP_POLL_DEFAULT), each followed by a copy of every lane's live
 // count to pinned memory and an event; before block k + 2 the host waits for block k's event and stops submitting once every count
 // is 0.  Then stop_restore, and lengths [B] / *steps_run come back.  Every lane carries its frame
-struct wrk_stop_run { wrk_v7_state* st; uint32_t poll_steps; uint32_t* out_lengths; uint32_t* steps_run; };
+// queue: generate_queue's loop -- the live count is the queue's (requests not yet ended), nothing is restored and no lengths come back
+struct wrk_stop_run { wrk_v7_state* st; uint32_t poll_steps; uint32_t* out_lengths; uint32_t* steps_run; bool queue = false; };
 static constexpr uint32_t WRK_STOP_POLL_DEFAULT = 16;
 // `steps` steps of every lane between two events: one lane on the submission stream (eagerly through `eager_step` without a program),
 // several on streams[g], joined through events[g].  Then tokens [steps][B] and last logits [B][V] come back

@@ -130,6 +130,33 @@ int32_t wrk_frame_common::ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32
     return WRK_OK;
 }
 
+static void free_queue(wrk_frame_common& f) {
+    void* bufs[] = {f.queue_slots, f.queue_started, f.queue_ctl, f.queue_reqs, f.queue_log, f.queue_pool};
+    for (void* p : bufs) if (p) hipFree(p);
+    f.queue_slots = nullptr; f.queue_started = nullptr; f.queue_ctl = nullptr; f.queue_reqs = nullptr; f.queue_log = nullptr;
+    f.queue_pool = nullptr;
+    f.queue_slot_cap = 0; f.queue_req_cap = 0; f.queue_pool_cap = 0;
+}
+
+int32_t wrk_frame_common::ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens) {
+    if (queue_ctl && slots <= queue_slot_cap && requests <= queue_req_cap && pool_tokens <= queue_pool_cap) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (queue_ctl) drop_graphs();                    // queue programs hold the old pointers; before the first allocation none exists
+    // never smaller than before: a later, smaller queue reuses the buffers and the program
+    if (slots < queue_slot_cap) slots = queue_slot_cap;
+    if (requests < queue_req_cap) requests = queue_req_cap;
+    if (pool_tokens < queue_pool_cap) pool_tokens = queue_pool_cap;
+    free_queue(*this);
+    WRK_HIP(ctx, hipMalloc((void**)&queue_slots, (size_t)slots * sizeof(wrk::QueueSlot)));
+    WRK_HIP(ctx, hipMalloc((void**)&queue_started, (size_t)slots * 4));
+    WRK_HIP(ctx, hipMalloc((void**)&queue_ctl, sizeof(wrk::QueueCtl)));
+    WRK_HIP(ctx, hipMalloc((void**)&queue_reqs, (size_t)requests * sizeof(wrk::QueueReq)));
+    WRK_HIP(ctx, hipMalloc((void**)&queue_log, (size_t)requests * sizeof(wrk::QueueLog)));
+    WRK_HIP(ctx, hipMalloc((void**)&queue_pool, pool_tokens * 4));
+    queue_slot_cap = slots; queue_req_cap = requests; queue_pool_cap = pool_tokens;
+    return WRK_OK;
+}
+
 int32_t wrk_frame_common::ensure_poll(uint32_t lanes) {
     if (live_host_cap < 2 * lanes) {
         if (live_host) hipHostFree(live_host);
@@ -152,6 +179,7 @@ void wrk_frame_common::release_common() {
     scratch = nullptr; history = nullptr; sample_par = nullptr; pen_par = nullptr; pen_o = nullptr;
     score.release();
     free_stop(*this);
+    free_queue(*this);
     if (live_host) hipHostFree(live_host);
     live_host = nullptr; live_host_cap = 0;
     for (hipEvent_t e : poll_events) hipEventDestroy(e);
@@ -299,6 +327,172 @@ int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V
     return WRK_OK;
 }
 
+// ------------------------------------------------------------------ request queue (wrk_queue.hip)
+static int32_t queue_csr_check(wrk_ctx* ctx, const uint32_t* off, uint32_t R, const char* what) {
+    WRK_ARG(ctx, off[0] == 0, "%s[0] = %u: must be 0", what, off[0]);
+    for (uint32_t r = 0; r < R; ++r) WRK_ARG(ctx, off[r + 1] >= off[r], "%s[%u] = %u decreases", what, r + 1, off[r + 1]);
+    return WRK_OK;
+}
+
+int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
+                        wrk_queue_result* out, wrk_queue_pack& pk) {
+    WRK_ARG(ctx, opt, "options required");
+    WRK_ARG(ctx, out && out->lengths && out->reasons && out->slots && out->start_steps && out->out_tokens && out->steps_run,
+            "every result array is required");
+    const uint32_t R = opt->num_requests;
+    WRK_ARG(ctx, R >= 1, "num_requests 0");
+    WRK_ARG(ctx, opt->prompt_tokens && opt->prompt_offsets && opt->max_new, "prompt_tokens, prompt_offsets and max_new are required");
+    WRK_ARG(ctx, opt->max_steps >= 1, "max_steps 0");
+    WRK_ARG(ctx, B >= 1 && B <= st->num_batch && B <= 256, "num_batch %u: must be in [1, min(%u, 256)]", B, st->num_batch);
+    if (((mode_arg >> 8) & 0xffu) > 1)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "generate_queue on several lanes: one queue shared by several streams would need cross-stream atomics");
+    int32_t rc = queue_csr_check(ctx, opt->prompt_offsets, R, "prompt_offsets");
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, !opt->stop_tokens || opt->stop_offsets, "stop_tokens without stop_offsets");
+    if (opt->stop_offsets) {
+        rc = queue_csr_check(ctx, opt->stop_offsets, R, "stop_offsets");
+        if (rc != WRK_OK) return rc;
+    }
+    const int given = (opt->temperature != nullptr) + (opt->top_p != nullptr) + (opt->seed != nullptr);
+    WRK_ARG(ctx, given == 0 || given == 3, "temperature, top_p and seed: all three arrays, or none for the arg-max");
+    WRK_ARG(ctx, opt->occ || (!opt->presence && !opt->frequency && !opt->decay), "penalty arrays without an occurrence table");
+    WRK_ARG(ctx, !opt->occ || given == 3, "penalties need the sampler arrays");
+    pk.R = R; pk.max_steps = opt->max_steps; pk.poll_steps = opt->poll_steps;
+    pk.sampled = given == 3; pk.penalized = opt->occ != nullptr;
+    pk.reqs.assign(R, wrk::QueueReq{});
+    pk.pool.assign(opt->prompt_tokens, opt->prompt_tokens + opt->prompt_offsets[R]);
+    for (size_t i = 0; i < pk.pool.size(); ++i) WRK_ARG(ctx, pk.pool[i] < V, "prompt token %zu: id %u >= vocab %u", i, pk.pool[i], V);
+    // the pick parameters go through the validation of the other loops, R rows at a time; the penalty rows of the R requests all
+    // name slot 0 here -- only their (presence, frequency, decay) are kept, a slot's row pointers are its own
+    std::vector<wrk::SampleParam> par;
+    std::vector<wrk::PenaltyParam> pen;
+    if (pk.sampled) {
+        rc = wrk_sample_pack(ctx, opt->temperature, opt->top_p, opt->seed, R, par);
+        if (rc != WRK_OK) return rc;
+    }
+    if (pk.penalized) {
+        WRK_ARG(ctx, opt->decay, "decay array required");
+        WRK_ARG(ctx, opt->occ->num_batch >= B, "occurrence table of %u slots, %u state slots", opt->occ->num_batch, B);
+        std::vector<wrk::PenaltyParam> one;
+        for (uint32_t r = 0; r < R; ++r) {
+            rc = wrk_penalty_pack(ctx, opt->occ, 0, 1, V, opt->presence ? opt->presence + r : nullptr, opt->frequency ? opt->frequency + r : nullptr,
+                                  opt->decay + r, one);
+            if (rc != WRK_OK) return rc;
+            pen.push_back(one[0]);
+        }
+    }
+    for (uint32_t r = 0; r < R; ++r) {
+        wrk::QueueReq& q = pk.reqs[r];
+        q.prompt_off = opt->prompt_offsets[r];
+        q.prompt_len = opt->prompt_offsets[r + 1] - opt->prompt_offsets[r];
+        WRK_ARG(ctx, q.prompt_len >= 1, "request %u: empty prompt", r);
+        q.max_new = opt->max_new[r];
+        WRK_ARG(ctx, q.max_new >= 1, "request %u: max_new 0", r);
+        if (pk.sampled) { q.temperature = par[r].temperature; q.top_p = par[r].top_p; q.seed = par[r].seed; }
+        if (pk.penalized) { q.presence = pen[r].presence; q.frequency = pen[r].frequency; q.decay = pen[r].decay; }
+        if (!opt->stop_offsets) continue;
+        const uint32_t n = opt->stop_offsets[r + 1] - opt->stop_offsets[r];
+        WRK_ARG(ctx, n <= WRK_MAX_STOP_TOKENS, "request %u: %u stop tokens, at most %u", r, n, (uint32_t)WRK_MAX_STOP_TOKENS);
+        WRK_ARG(ctx, n == 0 || opt->stop_tokens, "stop_offsets name %u stop tokens, stop_tokens is NULL", n);
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t id = opt->stop_tokens[opt->stop_offsets[r] + k];
+            WRK_ARG(ctx, id < V, "request %u: stop token %u >= vocab %u", r, id, V);
+            q.stop_ids[k] = id;
+        }
+        q.stop_count = n;
+    }
+    if (opt->init_state) {
+        const size_t need = (size_t)st->num_layer * (st->head_size + 2) * st->num_emb * 4;
+        WRK_ARG(ctx, opt->init_state->ctx == ctx, "init_state belongs to another context");
+        WRK_ARG(ctx, opt->init_state->bytes == need, "init_state holds %zu bytes, a sequence's state is %zu", opt->init_state->bytes, need);
+        pk.init_state = (const float*)opt->init_state->ptr;
+    }
+    // what the slots start with: request b in slot b; a slot without a request idles on a valid id
+    pk.first_tokens.assign(B, pk.pool[0]);
+    if (pk.sampled) pk.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
+    if (pk.penalized) pk.pen.resize(B);
+    for (uint32_t b = 0; b < B; ++b) {
+        const uint32_t r = b < R ? b : 0;       // idle slots: any valid row
+        const wrk::QueueReq& q = pk.reqs[r];
+        if (b < R) pk.first_tokens[b] = pk.pool[q.prompt_off];
+        if (pk.sampled && b < R) pk.par[b] = wrk::SampleParam{q.temperature, q.top_p, q.seed, q.prompt_len - 1};
+        if (pk.penalized) pk.pen[b] = opt->occ->row(b, q.presence, q.frequency, q.decay);
+    }
+    return WRK_OK;
+}
+
+static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, bool sampled, bool penalized) {
+    return wrk::QueueBufs{f.queue_slots, f.queue_reqs, f.queue_pool, f.queue_log, f.queue_ctl, f.queue_started,
+                          sampled ? f.sample_par : nullptr, penalized ? f.pen_par : nullptr};
+}
+
+static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V) {
+    return wrk::QueueGeom{st->data, st->num_layer, st->num_batch, b0, V, (size_t)(st->head_size + 2) * st->num_emb};
+}
+
+int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk_queue_pack& pk) {
+    wrk_ctx* ctx = f.ctx;
+    int32_t rc = f.ensure_queue(B, pk.R, pk.pool.size());
+    if (rc != WRK_OK) return rc;
+    const uint32_t nstart = B < pk.R ? B : pk.R;
+    std::vector<wrk::QueueSlot> slots(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
+    std::vector<uint32_t> started(B, 0u);
+    std::vector<wrk::QueueLog> log(pk.R, wrk::QueueLog{0u, 0u, 0u, 0u});
+    for (uint32_t b = 0; b < nstart; ++b) {
+        slots[b] = wrk::QueueSlot{b, 0u, 0u, pk.reqs[b].prompt_len == 1 ? wrk::QUEUE_REPLY : wrk::QUEUE_PROMPT};
+        started[b] = 1;
+        log[b] = wrk::QueueLog{0u, 3u, b, 0u};
+    }
+    const wrk::QueueCtl ctl{nstart, pk.R, pk.R, 0u, pk.init_state};
+    rc = wrk_buf_write_raw(ctx, f.queue_slots, slots.data(), (size_t)B * sizeof(wrk::QueueSlot));
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_started, started.data(), (size_t)B * 4);
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_log, log.data(), (size_t)pk.R * sizeof(wrk::QueueLog));
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_reqs, pk.reqs.data(), (size_t)pk.R * sizeof(wrk::QueueReq));
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_pool, pk.pool.data(), pk.pool.size() * 4);
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_ctl, &ctl, sizeof ctl);
+    if (rc != WRK_OK) return rc;
+    // the slots that start a request at step 0 are reset as the step that ends a request resets its slot
+    wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.sampled, pk.penalized), B, ctx->num_cu);
+    WRK_LAUNCH_CHECK(ctx);
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop) {
+    hipStream_t q = f.ctx->op_stream();
+    if (!f.queue_ctl || B > f.queue_slot_cap || stop.b0 != 0 || B > stop.st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+    if (penalized) wrk::occurrence_update_queue(q, V, B, f.pen_par, io.argmax, f.queue_slots);
+    const wrk::QueueBufs bufs = queue_bufs(f, sampled, penalized);
+    wrk::advance_queue(q, io.argmax, io.tokens, f.history, io.counter, bufs, B);
+    wrk::queue_reset(q, queue_geom(stop.st, stop.b0, V), bufs, B, f.ctx->num_cu);
+    return WRK_OK;
+}
+
+int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,
+                         wrk_queue_result* out) {
+    wrk_ctx* ctx = f.ctx;
+    std::vector<wrk::QueueLog> log(pk.R);
+    std::vector<uint32_t> hist((size_t)steps_run * B);
+    WRK_HIP(ctx, hipMemcpyAsync(log.data(), f.queue_log, (size_t)pk.R * sizeof(wrk::QueueLog), hipMemcpyDeviceToHost, ctx->stream));
+    if (!hist.empty()) WRK_HIP(ctx, hipMemcpyAsync(hist.data(), f.history, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    size_t o = 0;
+    for (uint32_t r = 0; r < pk.R; ++r) {
+        wrk::QueueLog g = log[r];
+        const wrk::QueueReq& q = pk.reqs[r];
+        // dealt to a slot by the last step that ran: its p_0 was never fed, so it was never dispatched
+        if (g.reason == 3 && g.start_step >= steps_run) g = wrk::QueueLog{0u, 0u, 0u, 0u};
+        // reply token j was drawn by step start_step + n - 1 + j; nothing below can leave the rows that ran unless the device log is wrong
+        if (g.length > q.max_new || g.slot >= B || (g.length && (size_t)g.start_step + q.prompt_len - 1 + g.length > steps_run))
+            return wrk_fail(ctx, WRK_E_HIP, "request %u: inconsistent queue log (length %u slot %u start %u)", r, g.length, g.slot, g.start_step);
+        out->lengths[r] = g.length; out->reasons[r] = g.reason; out->slots[r] = g.slot; out->start_steps[r] = g.start_step;
+        for (uint32_t j = 0; j < g.length; ++j) out->out_tokens[o + j] = hist[((size_t)g.start_step + q.prompt_len - 1 + j) * B + g.slot];
+        o += opt->max_new[r];
+    }
+    *out->steps_run = steps_run;
+    return WRK_OK;
+}
+
 static wrk::StopGeom stop_geom(const wrk_frame_common& f, const wrk::FrameIo& io, const wrk_v7_state* st, uint32_t b0, uint32_t V) {
     wrk::StopGeom g{};
     g.state = st->data; g.head_o = io.head_o; g.snap_state = f.stop_snap_state; g.snap_logits = f.stop_snap_logits;
@@ -329,6 +523,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint
     if (!sampled) wrk::argmax_rows(q, io.head_o, V, V, B, io.argmax);
     else if (wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax) != 0)
         return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    if (stop && stop->queue) return wrk_enqueue_queue_tail(f, io, V, B, sampled, penalized, *stop);
     if (stop) return wrk_enqueue_stop_tail(f, io, V, B, penalized, *stop);
     if (penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
     wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);
@@ -356,7 +551,8 @@ int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const st
     hipEvent_t* poll_events = nullptr;
     if (stop) {
         for (const wrk_lane& ln : lanes)
-            if (!ln.frame || !ln.frame->stop_par) return wrk_fail(ctx, WRK_E_ARG, "stop run on a lane without stop buffers");
+            if (!ln.frame || !(stop->queue ? (void*)ln.frame->queue_ctl : (void*)ln.frame->stop_par))
+                return wrk_fail(ctx, WRK_E_ARG, "stop run on a lane without stop buffers");
         const int32_t rc = lanes[0].frame->ensure_poll((uint32_t)groups);
         if (rc != WRK_OK) return rc;
         live_host = lanes[0].frame->live_host;
@@ -389,7 +585,8 @@ int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const st
             run += n;
             for (size_t g = 0; g < groups; ++g) {
                 hipStream_t ls = groups == 1 ? ctx->stream : streams[g];
-                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, lanes[g].frame->stop_live(), 4, hipMemcpyDeviceToHost, ls));
+                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, stop->queue ? lanes[g].frame->queue_live() : lanes[g].frame->stop_live(), 4,
+                                            hipMemcpyDeviceToHost, ls));
                 WRK_HIP(ctx, hipEventRecord(poll_events[(k & 1) * groups + g], ls));
             }
         }
@@ -423,7 +620,8 @@ int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const st
     float ms = 0.0f;
     WRK_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
     if (elapsed_ms) *elapsed_ms = ms;
-    if (stop) {
+    if (stop && stop->queue) *stop->steps_run = steps;
+    else if (stop) {
         // the frozen slots and logits rows go back (head_o is what the read-back below takes), the lengths come out
         for (const wrk_lane& ln : lanes) {
             wrk::stop_restore(ctx->stream, stop_geom(*ln.frame, *ln.io, stop->st, ln.b0, V), ln.nb, ctx->num_cu);

@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
             if (p == 0) {
                 if (!use_w) target = (unsigned long long)floor((double)top_p * (double)total);
                 else {          // ceil(u * W), u = U / 2^24, in 128-bit integer arithmetic
-                    const unsigned long long U = sample_splitmix(pr.seed, *step_word) >> 40;
+                    const unsigned long long U = sample_splitmix(pr.seed, *step_word - pr.step_base) >> 40;
                     const unsigned long long plo = U * total, phi = __umul64hi(U, total);
                     target = (phi << 40) | (plo >> 24);
                     if (plo & 0xFFFFFFull) ++target;

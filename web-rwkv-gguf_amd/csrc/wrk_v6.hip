@@ -16,7 +16,7 @@ struct V6Scratch : wrk::FrameIo {
     float* ks_part; uint32_t* ks_cnt; size_t ks_part_cap; uint32_t ks_cnt_cap;     // K-sliced GEMM scratch (2 .. 32 sequences), see MatJob
 };
 
-struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64 | stop 128)
+struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64 | stop 128 | queue 256)
     wrk_v6_model_desc d{};
     std::vector<wrk_v6_layer_desc> layers;
     V6Scratch s{};
@@ -697,6 +697,49 @@ int32_t wrk_v6_generate_stop(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, co
     }
     return v6_generate(ctx, m, st, first_tokens, B, steps, has_pick ? &pick : nullptr, out_tokens, last_logits, elapsed_ms, mode, opt, out_lengths,
                        steps_run);
+}
+
+// generate_queue: as v6_generate's stop call, the queue tail in the stop tail's place
+int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                              const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+    if (!ctx || !m || !st) return WRK_E_ARG;
+    LOCK(ctx);
+    const uint32_t V = m->d.num_vocab;
+    wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
+    wrk_queue_pack pk;
+    int32_t rc = wrk_queue_check(ctx, opt, st, B, V, mode_arg, out_arg ? &out : nullptr, pk);
+    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->d.emb_f16 != nullptr, m->d.num_emb, m->d.num_layer, V, pk.first_tokens.data(), B);
+    if (rc != WRK_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0f;
+    const uint32_t mode = mode_arg & 0xffu;
+    rc = m->ensure_scratch(B, B);
+    if (rc == WRK_OK)
+        rc = wrk_decode_prepare(*m, m->s, V, pk.first_tokens.data(), 0, B, pk.max_steps, pk.sampled ? pk.par.data() : nullptr,
+                                pk.penalized ? pk.pen.data() : nullptr);
+    if (rc == WRK_OK) rc = wrk_queue_prepare(*m, st, V, B, pk);
+    if (rc != WRK_OK) return rc;
+    const wrk_stop_step ss{st, 0, true};
+    const char* ng = getenv("WRK_NO_GRAPH");
+    const bool eager = ng && ng[0] == '1';
+    auto enqueue_step = [&]() -> int32_t {
+        wrk::gather_rows_f16(ctx->op_stream(), m->d.emb_f16->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
+        int32_t r = WRK_E_UNSUPPORTED;
+        if (mode == 1) r = m->enqueue_fused_decode(st, B, B, true, 0);
+        if (r == WRK_E_UNSUPPORTED) r = m->enqueue_ops(st, B, B, true);
+        if (r != WRK_OK) return r;
+        return wrk_enqueue_pick(*m, m->s, V, B, pk.sampled, pk.penalized, &ss);
+    };
+    std::vector<wrk_lane> lane{{&m->s, m->history, 0, B, nullptr, m}};
+    if (!eager) {
+        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pk.sampled ? 32u : 0u) | (pk.penalized ? 64u : 0u) | 256u}, enqueue_step,
+                                &lane[0].prog);
+        if (rc != WRK_OK) return rc;
+    }
+    uint32_t steps_run = 0;
+    const wrk_stop_run run{st, pk.poll_steps, nullptr, &steps_run, true};
+    rc = wrk_run_lanes(ctx, lane, {}, {}, B, V, pk.max_steps, enqueue_step, nullptr, nullptr, elapsed_ms, &run);
+    if (rc != WRK_OK) return rc;
+    return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
 }
 
 }  // extern "C"

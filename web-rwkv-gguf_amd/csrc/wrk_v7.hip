@@ -617,14 +617,16 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
 
 // one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers, pick each sequence's next token and advance
 // tokens / history / counter (wrk_enqueue_pick; the fused greedy path does both inside its head launch)
-// stop: a stop program's step (wrk_stop.hip) -- the fused greedy head keeps its arg-max and leaves the advance to the stop tail
+// stop: a stop program's step (wrk_stop.hip) -- the fused greedy head keeps its arg-max and leaves the advance to the stop tail;
+// queue (with stop): a queue program's step (wrk_queue.hip), the queue tail in the stop tail's place
 static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled,
-                                   bool penalized, bool stop = false) {
+                                   bool penalized, bool stop = false, bool queue = false) {
     int32_t rc;
-    const wrk_stop_step ss{st, b0};
+    const wrk_stop_step ss{st, b0, queue};
     if (mode == 1 && m->act_dtype == WRK_F16) {
         rc = m->enqueue_fused_decode(st, B, B, true, true, !sampled, !sampled && !stop, b0, true);
         if (!sampled && (!stop || rc != WRK_OK)) return rc;
+        if (!sampled && queue) return wrk_enqueue_queue_tail(*m, m->s, m->d.num_vocab, B, false, false, ss);
         if (!sampled) return wrk_enqueue_stop_tail(*m, m->s, m->d.num_vocab, B, false, ss);
     } else {
         wrk::gather_rows_f16(ctx->op_stream(), m->emb->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
@@ -639,21 +641,25 @@ static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* 
 // pen: their occurrence rows and penalties (with par), or nullptr
 static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t b0, uint32_t B,
                               uint32_t steps, uint32_t mode, bool eager, const wrk::SampleParam* par, const wrk::PenaltyParam* pen,
-                              const wrk::StopParam* stop, wrk_program** prog_out) {
+                              const wrk::StopParam* stop, wrk_program** prog_out, const wrk_queue_pack* queue = nullptr) {
     int32_t rc = m->ensure_scratch(B, B);
     if (rc == WRK_OK && B == 1 && mode == 1) rc = m->ensure_engine();
     if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, m->d.num_vocab, first_tokens, b0, B, steps, par, pen);
     if (rc == WRK_OK && stop) rc = wrk_stop_prepare(*m, st, m->d.num_vocab, B, stop);
+    if (rc == WRK_OK && queue) rc = wrk_queue_prepare(*m, st, m->d.num_vocab, B, *queue);
     *prog_out = nullptr;
     if (rc != WRK_OK || eager) return rc;
     // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo; sampled
     // steps have their own key bit, so greedy and sampled programs never alias, and so do penalised ones (bit 24, above every infer flag)
-    // and stop programs (bit 25)
+    // and stop programs (bit 25) and queue programs (bit 26)
     const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
                                                              (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u) | (pen ? 1u << 24 : 0u) |
-                                                             (stop ? 1u << 25 : 0u)};
+                                                             (stop ? 1u << 25 : 0u) | (queue ? 1u << 26 : 0u)};
     return wrk_cached_program(ctx, m->graphs, key,
-                              [&] { return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr, stop != nullptr); }, prog_out);
+                              [&] {
+                                  return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr, stop || queue, queue != nullptr);
+                              },
+                              prog_out);
 }
 
 // pick: the sampler / penalty arrays of generate_sample / generate_penalized, or nullptr (generate_greedy)
@@ -768,6 +774,39 @@ int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, co
     }
     return v7_generate(ctx, m, st, first_tokens, B, steps, has_pick ? &pick : nullptr, out_tokens, last_logits, elapsed_ms, mode_arg, opt,
                        out_lengths, steps_run);
+}
+
+// generate_queue: one lane, the frame's own; the loop is generate_stop's polled one with the queue's live count
+int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                              const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+    if (!ctx || !m || !st) return WRK_E_ARG;
+    LOCK(ctx);
+    const uint32_t V = m->d.num_vocab;
+    wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
+    wrk_queue_pack pk;
+    int32_t rc = wrk_queue_check(ctx, opt, st, B, V, mode_arg, out_arg ? &out : nullptr, pk);
+    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->emb != nullptr, m->d.num_emb, m->d.num_layer, V, pk.first_tokens.data(), B);
+    if (rc != WRK_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0f;
+    const uint32_t mode = mode_arg & 0xffu;
+    const char* ng = getenv("WRK_NO_GRAPH");
+    const bool eager = ng && ng[0] == '1';
+    wrk::timing_slot(ctx, nullptr);
+    m->engine_blocked = false;
+    std::vector<wrk_lane> L(1);
+    rc = decode_prepare(ctx, m, st, pk.first_tokens.data(), 0, B, pk.max_steps, mode, eager, pk.sampled ? pk.par.data() : nullptr,
+                        pk.penalized ? pk.pen.data() : nullptr, nullptr, &L[0].prog, &pk);
+    if (rc != WRK_OK) return rc;
+    L[0].io = &m->s; L[0].history = m->history; L[0].b0 = 0; L[0].nb = B; L[0].frame = m;
+    uint32_t steps_run = 0;
+    const wrk_stop_run run{st, pk.poll_steps, nullptr, &steps_run, true};
+    rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, pk.max_steps,
+                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, pk.sampled, pk.penalized, true, true); }, nullptr, nullptr, elapsed_ms,
+                       &run);
+    if (rc != WRK_OK) return rc;
+    rc = wrk_v7_engine_check(m->engine);
+    if (rc != WRK_OK) return rc;
+    return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
 }
 
 }  // extern "C"

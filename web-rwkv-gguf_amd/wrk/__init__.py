@@ -78,6 +78,21 @@ class GenerateOptions(C.Structure):
                 ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32)]
 
 
+class QueueOptions(C.Structure):
+    """wrk_queue_options: the requests (CSR prompts, max_new, CSR stop sets), the pick arrays [R] as in GenerateOptions, the shared
+    prefix state and the polled loop's block size and step cap of wrk_v*_generate_queue."""
+    _fields_ = [("num_requests", C.c_uint32), ("prompt_tokens", _u32p), ("prompt_offsets", _u32p), ("max_new", _u32p),
+                ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p),
+                ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("init_state", _P),
+                ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32)]
+
+
+class QueueResult(C.Structure):
+    """wrk_queue_result: host arrays [R] (out_tokens: [sum of max_new]) and the steps the call ran."""
+    _fields_ = [("lengths", _u32p), ("reasons", _u32p), ("slots", _u32p), ("start_steps", _u32p), ("out_tokens", _u32p),
+                ("steps_run", _u32p)]
+
+
 MAX_STOP_TOKENS = 16        # WRK_MAX_STOP_TOKENS
 _TP = C.POINTER(TensorDesc)
 
@@ -173,6 +188,8 @@ HIP_SYMBOLS = {
                                          _f32p, C.c_uint32]),
     "wrk_v6_generate_stop": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(GenerateOptions), _u32p, _u32p, _f32p, _u32p,
                                          _f32p, C.c_uint32]),
+    "wrk_v7_generate_queue": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32]),
+    "wrk_v6_generate_queue": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32]),
 }
 RT_SYMBOLS = {
     "wrk_host_last_error": (C.c_char_p, []),
@@ -1026,6 +1043,66 @@ class Runtime:
         self.last_stop_ms = ms.value
         out = out[:run.value]
         return (out, lengths, logits) if want_logits else (out, lengths)
+
+    def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
+                       presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
+                       mode: int = 1):
+        """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
+        reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
+        same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
+        stop[r] (one list for all requests, or one per request).  The pick is one for the call, as in `generate_stop`; per-request
+        parameters broadcast from scalars; seed=None: seed[r] = r.  The sampler step of a reply token is its index in the reply, so a
+        reply does not depend on when its request was scheduled.  Returns ([(tokens, reason, slot, start_step)] per request, steps_run):
+        reason 1 stop token (part of the reply), 2 max_new, 3 cut by max_steps, 0 never dispatched.  max_steps defaults to the sum of
+        prompt and max_new lengths, enough even for one slot.  The state and the occurrence rows are unspecified afterwards."""
+        prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
+        R = len(prompts)
+        B = self.num_batch
+        sets = [] if stop is None else list(stop)
+        if not (sets and all(isinstance(x, (list, tuple, np.ndarray)) for x in sets)):
+            sets = [sets] * R
+        if len(sets) != R:
+            raise ValueError(f"{len(sets)} stop sets for {R} requests")
+        poff = np.zeros(R + 1, np.uint32)
+        poff[1:] = np.cumsum([x.size for x in prompts])
+        ptok = _u32(np.concatenate(prompts) if R else [])
+        soff = np.zeros(R + 1, np.uint32)
+        soff[1:] = np.cumsum([len(x) for x in sets])
+        ids = _u32(np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in sets]) if R else [])
+        if ids.size == 0:
+            ids = np.zeros(1, np.uint32)
+        if ptok.size == 0:
+            ptok = np.zeros(1, np.uint32)
+        mn = _per_row(max_new, R, np.uint32)
+        opt = QueueOptions()
+        opt.num_requests = R
+        opt.prompt_tokens, opt.prompt_offsets, opt.max_new = _ptr(ptok, _u32p), _ptr(poff, _u32p), _ptr(mn, _u32p)
+        opt.stop_tokens, opt.stop_offsets = _ptr(ids, _u32p), _ptr(soff, _u32p)
+        keep = []
+        if temperature is not None or top_p is not None or seed is not None or occurrence is not None:
+            t = _per_row(1.0 if temperature is None else temperature, R, np.float32)
+            p = _per_row(0.5 if top_p is None else top_p, R, np.float32)
+            sd = np.arange(R, dtype=np.uint32) if seed is None else _per_row(seed, R, np.uint32)
+            keep += [t, p, sd]
+            opt.temperature, opt.top_p, opt.seed = _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p)
+        if occurrence is not None:
+            ap, af, g = _per_row(presence, R, np.float32), _per_row(frequency, R, np.float32), _per_row(decay, R, np.float32)
+            keep += [ap, af, g]
+            opt.presence, opt.frequency, opt.decay, opt.occ = _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h
+        if init_state is not None:
+            opt.init_state = init_state.h
+        opt.poll_steps = poll_steps
+        opt.max_steps = int(poff[-1]) + int(mn.sum()) if max_steps is None else max_steps
+        lengths, reasons, slots, starts = (np.zeros(max(R, 1), np.uint32) for _ in range(4))
+        out = np.zeros(max(int(mn.sum()), 1), np.uint32)
+        run, ms = C.c_uint32(), C.c_float()
+        res = QueueResult(_ptr(lengths, _u32p), _ptr(reasons, _u32p), _ptr(slots, _u32p), _ptr(starts, _u32p), _ptr(out, _u32p),
+                          C.pointer(run))
+        fn, mdl = (hip.wrk_v6_generate_queue, self.model6) if self.model6 else (hip.wrk_v7_generate_queue, self.model)
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode))
+        self.last_queue_ms = ms.value
+        off = np.concatenate([[0], np.cumsum(mn)]).astype(np.int64)
+        return [(out[off[r]:off[r] + lengths[r]].copy(), int(reasons[r]), int(slots[r]), int(starts[r])) for r in range(R)], run.value
 
     def state_back(self, batch: int) -> np.ndarray:
         """`State::back(batch)` -> [L, S+2, D] f32."""
