@@ -327,6 +327,16 @@ int32_t wrk_sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_voca
 int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
                                uint32_t steps, const float* temperature, const float* top_p, const uint32_t* seed,
                                uint32_t* out_tokens, float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
+/* wrk_sample_logits with two more cuts of the candidates per row (ChatRWKV / ai00 top_k, llama.cpp min_p).  In wrk_sample_logits' order
+ * the candidates are the first min(n_P, n_K, n_M) ranks: n_P the nucleus count (against the whole row's softmax mass: not renormalised
+ * after the other cuts; top_p >= 1: num_vocab); n_K = top_k (0 or >= num_vocab: off; exactly top_k tokens survive, ties broken by index);
+ * n_M = the number of tokens with fl32(l - max) >= fl32(ln(min_p)) (the subtraction in f32, the logarithm taken in f64 on the host and
+ * rounded once; min_p == 0: off; rank 0 always passes).  Weights p^(1/T) inside the candidates, the draw as wrk_sample_logits'.
+ * top_k == 1 is the greedy branch.  top_k: host u32 [num_rows], min_p: host f32 [num_rows] in [0, 1] (NaN or outside: WRK_E_ARG); either
+ * may be NULL (off).  With both off every token equals wrk_sample_logits', bit for bit. */
+int32_t wrk_sample_logits_filtered(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                                   const float* temperature, const float* top_p, const uint32_t* top_k, const float* min_p,
+                                   const uint32_t* seed, uint32_t step, uint32_t* out_tokens);
 
 /* Sequence scoring on the device, per row of f32 logits [num_rows][row_stride] (first num_vocab used) and its target token t:
  *   logprob = x_t - (m + log sum_i exp(x_i - m)), m = the row max;   rank = #{i : x_i > x_t} + #{i < t : x_i == x_t}
@@ -392,7 +402,11 @@ int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_stat
  * wrk_v7_generate_penalized's (then the sampler arrays are required); both stop arrays NULL: no stops.  The stop sets are passed to
  * the step program as data: one cached program serves any stop sets.  WRK_E_ARG before any launch on: a NULL opt / out_lengths /
  * steps_run, offsets that do not start at 0 or decrease, more than WRK_MAX_STOP_TOKENS ids for a sequence, an id >= num_vocab, sampler
- * arrays only partly given, penalty arrays without a table, and whatever the three calls above reject. */
+ * arrays only partly given, penalty arrays without a table, and whatever the three calls above reject.
+ * top_k / min_p (host arrays [num_batch], either may be NULL: off) make the pick wrk_sample_logits_filtered's; they need the sampler
+ * arrays (else WRK_E_ARG), and min_p outside [0, 1] is WRK_E_ARG.  With both stop arrays NULL this is the options form of
+ * wrk_v7_generate_sample / wrk_v7_generate_penalized.  Filtered calls replay step programs of their own (any filter values: the rows
+ * are device data); a call with both NULL runs exactly the programs it ran before. */
 #define WRK_MAX_STOP_TOKENS 16
 typedef struct wrk_generate_options {
     const float *temperature, *top_p;
@@ -401,6 +415,8 @@ typedef struct wrk_generate_options {
     wrk_occurrence *occ;
     const uint32_t *stop_tokens, *stop_offsets;
     uint32_t poll_steps;
+    const uint32_t *top_k;
+    const float *min_p;
 } wrk_generate_options;
 int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
                              uint32_t steps, const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths,
@@ -434,7 +450,8 @@ int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* st
  * do not start at 0 or decrease, a token or stop id >= num_vocab, more than WRK_MAX_STOP_TOKENS stop ids for a request, sampler arrays
  * only partly given, penalty arrays without a table, a table with fewer slots than num_batch or of another vocabulary or context,
  * init_state of another size, max_steps == 0, and whatever wrk_v7_generate_stop rejects for the same pick.  mode bits 8-15 > 1 (lanes):
- * WRK_E_UNSUPPORTED -- a queue shared by several streams would need cross-stream atomics. */
+ * WRK_E_UNSUPPORTED -- a queue shared by several streams would need cross-stream atomics.
+ * top_k / min_p [num_requests] (either may be NULL: off): request r's draws are wrk_sample_logits_filtered's, as in wrk_generate_options. */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
     const uint32_t *prompt_tokens, *prompt_offsets, *max_new;
@@ -445,6 +462,8 @@ typedef struct wrk_queue_options {
     wrk_occurrence *occ;
     const wrk_buf *init_state;
     uint32_t poll_steps, max_steps;
+    const uint32_t *top_k;
+    const float *min_p;
 } wrk_queue_options;
 typedef struct wrk_queue_result {
     uint32_t *lengths, *reasons, *slots, *start_steps, *out_tokens, *steps_run;

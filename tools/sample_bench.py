@@ -8,7 +8,12 @@ A fourth leg (--stop) is generate_stop with the same sampler parameters: the per
 ids per sequence that are not drawn) against the sampled leg, for every --poll block size and with polling off, and the wall time of a
 call with --stop-steps steps whose sequences all end by about step 32 against the same call without stops.
 
+A fifth pair of legs (--top-k K and / or --min-p M), alternating with the others: generate_sample with the top-k / min-p cuts next to
+the same top_p (the filtered kernel's fused boundary descent), and with --top-k also top_k alone at top_p = 1 (its count-only descent),
+each against the plain sampled leg, with the run-to-run spread of both.
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
+                                 [--top-k 40] [--min-p 0.05]
 
 Prints one JSON object.
 """
@@ -113,6 +118,8 @@ def main():
     ap.add_argument("--stop", action="store_true")
     ap.add_argument("--poll", default="4,8,16,32,64")
     ap.add_argument("--stop-steps", type=int, default=1024)
+    ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--min-p", type=float, default=None)
     args = ap.parse_args()
     import wrk
 
@@ -129,6 +136,11 @@ def main():
         out["penalties"] = {"presence": 0.2, "frequency": 0.2, "decay": 0.996, "banned_per_sequence": 16}
         for b in range(max(batches)):
             occ.ban(b, [(1000 + 997 * i + 31 * b) % V for i in range(16)])
+    filt = args.top_k is not None or args.min_p is not None
+    fkw = dict(temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, min_p=args.min_p)
+    kkw = dict(temperature=args.temperature, top_p=1.0, top_k=args.top_k)
+    if filt:
+        out["filters"] = {"top_k": args.top_k, "min_p": args.min_p}
     for B in batches:
         first = [(17 + 101 * b) % (V - 1) for b in range(B)]
         engine = rt.engine_status()[0] if B == 1 else False
@@ -136,12 +148,18 @@ def main():
         rt.generate_sample(first, 4, temperature=args.temperature, top_p=args.top_p)
         if pen:
             rt.generate_penalized(first, 4, occ, **pkw)
-        g, s, p = [], [], []
+        if filt:
+            rt.generate_sample(first, 4, **fkw)
+        g, s, p, f, k = [], [], [], [], []
         for _ in range(args.reps):
             g.append(rt.generate_greedy(first, args.steps)[1] / args.steps)
             s.append(rt.generate_sample(first, args.steps, temperature=args.temperature, top_p=args.top_p)[1] / args.steps)
             if pen:
                 p.append(rt.generate_penalized(first, args.steps, occ, **pkw)[1] / args.steps)
+            if filt:
+                f.append(rt.generate_sample(first, args.steps, **fkw)[1] / args.steps)
+            if args.top_k is not None:
+                k.append(rt.generate_sample(first, args.steps, **kkw)[1] / args.steps)
         gm, sm = float(np.median(g)), float(np.median(s))
         # host alternative: logits back over PCIe + a CPU sort per row (what a caller of wrk_v7_infer has to do today)
         _, _, logits = rt.generate_greedy(first, 1, want_logits=True)
@@ -168,6 +186,15 @@ def main():
             pm = float(np.median(p))
             out["batches"][-1].update({"penalized_ms_per_step": round(pm, 5), "penalized_minus_sample_us": round((pm - sm) * 1e3, 2),
                                        "penalized_ms_all": [round(x, 5) for x in p]})
+        if filt:
+            fm = float(np.median(f))
+            out["batches"][-1].update({"filtered_ms_per_step": round(fm, 5), "filtered_minus_sample_us": round((fm - sm) * 1e3, 2),
+                                       "sample_spread_us": round((max(s) - min(s)) * 1e3, 2),
+                                       "filtered_spread_us": round((max(f) - min(f)) * 1e3, 2), "filtered_ms_all": [round(x, 5) for x in f]})
+        if k:
+            km = float(np.median(k))
+            out["batches"][-1].update({"top_k_only_ms_per_step": round(km, 5), "top_k_only_minus_sample_us": round((km - sm) * 1e3, 2),
+                                       "top_k_only_spread_us": round((max(k) - min(k)) * 1e3, 2), "top_k_only_ms_all": [round(x, 5) for x in k]})
         if args.stop:
             out["batches"][-1]["stop"] = stop_leg(rt, first, B, V, args)
     if occ is not None:

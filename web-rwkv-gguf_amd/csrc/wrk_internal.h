@@ -178,6 +178,11 @@ struct SampleParam { float temperature, top_p; uint32_t seed, step_base; };
 static constexpr uint32_t SAMPLE_MAX_VOCAB = 1u << 20;
 int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
                 uint32_t* out);
+// sample_rows with two more cuts of the candidates per row: the first min(n_P, n_K, n_M) ranks stay, n_K = top_k (0 or
+// >= v: v; 1: the arg-max, as temperature 0) and n_M = #{fl32(l - max) >= ln_min_p} (-inf: v).  Both off: sample_rows' token, bit for bit
+struct SampleFilter { uint32_t top_k; float ln_min_p; };
+int sample_rows_filtered(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
+                         const SampleFilter* filt, const uint32_t* step, uint32_t* out);
 
 // wrk_score.hip: per row, logprob = x_t - logsumexp(x) and rank = #{x_i > x_t} + #{i < t : x_i == x_t} of the target t = targets[row]
 // (targets < v: the caller validates them).  Each row is split over score_slices(n, v, num_cu) workgroups; part holds n * that many
@@ -230,6 +235,7 @@ struct QueueReq {
     uint32_t prompt_off, prompt_len, max_new, seed;
     float temperature, top_p, presence, frequency, decay;
     uint32_t stop_count, stop_ids[WRK_MAX_STOP_TOKENS];
+    uint32_t top_k; float ln_min_p;     // the request's SampleFilter row (filtered queues)
 };
 struct QueueSlot { uint32_t req, pos, reply, phase; };
 struct QueueLog { uint32_t length, reason, slot, start_step; };
@@ -239,6 +245,7 @@ struct QueueBufs {
     uint32_t* started;              // [B]: 1 when the slot took a new request in this step (written for every slot by every launch)
     SampleParam* sample_par;        // the frame's rows, or nullptr (arg-max)
     PenaltyParam* pen_par;          // the frame's rows, or nullptr (no penalties)
+    SampleFilter* filter_par;       // the frame's rows, or nullptr (no top-k / min-p)
 };
 // takes advance_tokens' place in a queue program: history <- drawn; per slot the next prompt token or the draw, stop / max_new check,
 // next requests to the slots that ended (ascending slot order), their parameters into the slot's rows, started[b], the log,
@@ -320,6 +327,8 @@ size_t stored_bytes(uint32_t kind, uint32_t k, uint32_t m);
 // validated per-sequence sampler parameters (WRK_E_ARG on NULL arrays or a NaN / negative temperature or top_p)
 int32_t wrk_sample_pack(wrk_ctx* ctx, const float* temperature, const float* top_p, const uint32_t* seed, uint32_t n,
                         std::vector<wrk::SampleParam>& out);
+// validated per-sequence filter rows; either array may be NULL (off).  WRK_E_ARG on a min_p that is NaN or outside [0, 1]
+int32_t wrk_filter_pack(wrk_ctx* ctx, const uint32_t* top_k, const float* min_p, uint32_t n, std::vector<wrk::SampleFilter>& out);
 
 // device slots of a scoring job (wrk_score.hip): targets u32, logprob f32, rank u32 [cap] and the slice partials [cap][SCORE_MAX_SLICES];
 // ensure() reallocates (after a stream sync) when n > cap and then sets *grown: programs captured with the old pointers must go

@@ -72,6 +72,7 @@ __global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_kernel(const uint
                 tokens[i] = Q.pool[q->prompt_off];
                 // reply token j is drawn at step (step + 1) + prompt_len - 1 + j: its sampler step is j whenever it is scheduled
                 if (Q.sample_par) Q.sample_par[i] = SampleParam{q->temperature, q->top_p, q->seed, step + q->prompt_len};
+                if (Q.filter_par) Q.filter_par[i] = SampleFilter{q->top_k, q->ln_min_p};
                 if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
                 Q.log[r] = QueueLog{0u, 3u, i, step + 1};
                 started = 1;

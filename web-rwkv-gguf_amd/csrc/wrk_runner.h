@@ -88,6 +88,8 @@ struct wrk_frame_common {
     size_t history_cap = 0;
     wrk::SampleParam* sample_par = nullptr;    // generate_sample: per-sequence sampler parameters, written before every call (not baked
     uint32_t sample_par_cap = 0;                // into the step programs, which read them through this pointer)
+    wrk::SampleFilter* filter_par = nullptr;   // filtered picks: per-sequence top-k / min-p rows next to sample_par, written before every call
+    uint32_t filter_par_cap = 0;
     wrk::PenaltyParam* pen_par = nullptr;      // generate_penalized: per-sequence occurrence rows and penalties, written before every call
     float* pen_o = nullptr;                     // (the step programs read the table's pointers from here); pen_o: penalised logits [B][V]
     uint32_t pen_cap = 0;
@@ -132,6 +134,7 @@ struct wrk_frame_common {
     void drop_graphs();
     int32_t ensure_history(size_t n);
     int32_t ensure_sample_params(uint32_t n);
+    int32_t ensure_filter_params(uint32_t n);
     int32_t ensure_penalty(uint32_t n, uint32_t num_vocab);
     int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
     int32_t ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens);
@@ -154,10 +157,11 @@ struct wrk_pick_args {      // the ABI's sampler (and with `penalized` penalty) 
     const float *temperature, *top_p; const uint32_t* seed;
     bool penalized = false;
     const float *presence = nullptr, *frequency = nullptr, *decay = nullptr; wrk_occurrence* occ = nullptr;
+    const uint32_t* top_k = nullptr; const float* min_p = nullptr;      // either set: a filtered pick
 };
-struct wrk_pick_params {    // validated per-sequence rows; par / pen: nullptr for the arg-max / without penalties
-    std::vector<wrk::SampleParam> par_rows; std::vector<wrk::PenaltyParam> pen_rows;
-    const wrk::SampleParam* par = nullptr; const wrk::PenaltyParam* pen = nullptr;
+struct wrk_pick_params {    // validated per-sequence rows; par / pen / filt: nullptr for the arg-max / without penalties / without filters
+    std::vector<wrk::SampleParam> par_rows; std::vector<wrk::PenaltyParam> pen_rows; std::vector<wrk::SampleFilter> filt_rows;
+    const wrk::SampleParam* par = nullptr; const wrk::PenaltyParam* pen = nullptr; const wrk::SampleFilter* filt = nullptr;
 };
 int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args* pick, uint32_t B, uint32_t V, wrk_pick_params& out);
 int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, uint32_t num_emb, uint32_t num_layer, uint32_t V,
@@ -165,30 +169,31 @@ int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, u
 // after the model's ensure_scratch: history / parameter buffers, then cursors, header rows, first tokens and parameters of sequences
 // [b0, b0 + B) and a zero step counter
 int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps,
-                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen);
+                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen, const wrk::SampleFilter* filt = nullptr);
 // after the layers and the head: pick each sequence's next token from head_o -- the arg-max, or with `sampled` the sampler (wrk_sample.hip)
 // on the frame's parameters at step *counter; `penalized` (implies `sampled`): from pen_o = head_o penalised with the occurrence rows of
 // pen_par, which then count the drawn tokens (wrk_penalty.hip) -- and advance tokens / history / counter
 // stop: the step belongs to a stop program (wrk_enqueue_stop_tail instead of advance_tokens), or with `queue` to a queue program
-// (wrk_enqueue_queue_tail)
+// (wrk_enqueue_queue_tail).  filtered (with `sampled`): the filtered sampler on the frame's filter_par rows
 struct wrk_stop_step { const wrk_v7_state* st; uint32_t b0; bool queue = false; };
 int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
-                         const wrk_stop_step* stop = nullptr);
+                         const wrk_stop_step* stop = nullptr, bool filtered = false);
 // tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
 // (`penalized`), advance_stop, stop_snapshot of sequences [b0, b0 + B) of `st`
 int32_t wrk_enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool penalized, const wrk_stop_step& stop);
 
 // tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
 // token (`penalized`), advance_queue, queue_reset of slots [b0, b0 + B) of `st`
-int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop);
+int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop,
+                               bool filtered = false);
 
 // generate_queue: the options validated (WRK_E_ARG before any launch) into the request table, the prompt pool and the pick rows the slots
 // start with.  first_tokens [B]: p_0 of the requests dispatched at step 0, a valid id for the slots that start idle
 struct wrk_queue_pack {
     uint32_t R = 0, max_steps = 0, poll_steps = 0;
-    bool sampled = false, penalized = false;
+    bool sampled = false, penalized = false, filtered = false;
     std::vector<wrk::QueueReq> reqs; std::vector<uint32_t> pool, first_tokens;
-    std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen;
+    std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
     const float* init_state = nullptr;
 };
 int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,

@@ -94,6 +94,18 @@ int32_t wrk_frame_common::ensure_sample_params(uint32_t n) {
     return WRK_OK;
 }
 
+int32_t wrk_frame_common::ensure_filter_params(uint32_t n) {
+    if (n <= filter_par_cap && filter_par) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drop_graphs();
+    if (filter_par) hipFree(filter_par);
+    filter_par = nullptr;
+    filter_par_cap = 0;
+    WRK_HIP(ctx, hipMalloc((void**)&filter_par, (size_t)n * sizeof(wrk::SampleFilter)));
+    filter_par_cap = n;
+    return WRK_OK;
+}
+
 int32_t wrk_frame_common::ensure_penalty(uint32_t n, uint32_t num_vocab) {
     if (n <= pen_cap && pen_par && pen_o) return WRK_OK;
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -174,9 +186,10 @@ int32_t wrk_frame_common::ensure_poll(uint32_t lanes) {
 
 void wrk_frame_common::release_common() {
     drop_graphs();
-    void* bufs[] = {scratch, history, sample_par, pen_par, pen_o};
+    void* bufs[] = {scratch, history, sample_par, filter_par, pen_par, pen_o};
     for (void* p : bufs) if (p) hipFree(p);
-    scratch = nullptr; history = nullptr; sample_par = nullptr; pen_par = nullptr; pen_o = nullptr;
+    scratch = nullptr; history = nullptr; sample_par = nullptr; filter_par = nullptr; pen_par = nullptr; pen_o = nullptr;
+    filter_par_cap = 0;
     score.release();
     free_stop(*this);
     free_queue(*this);
@@ -243,6 +256,11 @@ int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args* pick, uint32_t B, uint3
     if (rc != WRK_OK) return rc;
     WRK_ARG(ctx, B >= 1, "num_batch 0");
     out.par = out.par_rows.data();
+    if (pick->top_k || pick->min_p) {
+        rc = wrk_filter_pack(ctx, pick->top_k, pick->min_p, B, out.filt_rows);
+        if (rc != WRK_OK) return rc;
+        out.filt = out.filt_rows.data();
+    }
     if (!pick->penalized) return WRK_OK;
     WRK_ARG(ctx, pick->decay, "decay array required");
     rc = wrk_penalty_pack(ctx, pick->occ, 0, B, V, pick->presence, pick->frequency, pick->decay, out.pen_rows);
@@ -261,10 +279,11 @@ int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, u
 }
 
 int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps,
-                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen) {
+                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen, const wrk::SampleFilter* filt) {
     wrk_ctx* ctx = f.ctx;
     int32_t rc = f.ensure_history((size_t)steps * B);
     if (rc == WRK_OK && par) rc = f.ensure_sample_params(B);
+    if (rc == WRK_OK && filt) rc = f.ensure_filter_params(B);
     if (rc == WRK_OK && pen) rc = f.ensure_penalty(B, V);
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
@@ -273,6 +292,7 @@ int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, co
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.headers, hdr.data(), (size_t)B * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.tokens, first_tokens, (size_t)B * 4);
     if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, f.sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
+    if (rc == WRK_OK && filt) rc = wrk_buf_write_raw(ctx, f.filter_par, filt, (size_t)B * sizeof(wrk::SampleFilter));
     if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, f.pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
     if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipMemsetAsync(io.counter, 0, 4, ctx->stream));
@@ -309,8 +329,10 @@ int32_t wrk_stop_pick_args(wrk_ctx* ctx, const wrk_generate_options* opt, wrk_pi
     WRK_ARG(ctx, given == 0 || given == 3, "temperature, top_p and seed: all three arrays, or none for the arg-max");
     WRK_ARG(ctx, opt->occ || (!opt->presence && !opt->frequency && !opt->decay), "penalty arrays without an occurrence table");
     WRK_ARG(ctx, !opt->occ || given == 3, "penalties need the sampler arrays");
+    WRK_ARG(ctx, (!opt->top_k && !opt->min_p) || given == 3, "top_k / min_p need the sampler arrays");
     *has_pick = given == 3;
-    *pick = wrk_pick_args{opt->temperature, opt->top_p, opt->seed, opt->occ != nullptr, opt->presence, opt->frequency, opt->decay, opt->occ};
+    *pick = wrk_pick_args{opt->temperature, opt->top_p, opt->seed, opt->occ != nullptr, opt->presence, opt->frequency, opt->decay, opt->occ,
+                          opt->top_k, opt->min_p};
     return WRK_OK;
 }
 
@@ -357,8 +379,9 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
     WRK_ARG(ctx, given == 0 || given == 3, "temperature, top_p and seed: all three arrays, or none for the arg-max");
     WRK_ARG(ctx, opt->occ || (!opt->presence && !opt->frequency && !opt->decay), "penalty arrays without an occurrence table");
     WRK_ARG(ctx, !opt->occ || given == 3, "penalties need the sampler arrays");
+    WRK_ARG(ctx, (!opt->top_k && !opt->min_p) || given == 3, "top_k / min_p need the sampler arrays");
     pk.R = R; pk.max_steps = opt->max_steps; pk.poll_steps = opt->poll_steps;
-    pk.sampled = given == 3; pk.penalized = opt->occ != nullptr;
+    pk.sampled = given == 3; pk.penalized = opt->occ != nullptr; pk.filtered = opt->top_k || opt->min_p;
     pk.reqs.assign(R, wrk::QueueReq{});
     pk.pool.assign(opt->prompt_tokens, opt->prompt_tokens + opt->prompt_offsets[R]);
     for (size_t i = 0; i < pk.pool.size(); ++i) WRK_ARG(ctx, pk.pool[i] < V, "prompt token %zu: id %u >= vocab %u", i, pk.pool[i], V);
@@ -366,8 +389,13 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
     // name slot 0 here -- only their (presence, frequency, decay) are kept, a slot's row pointers are its own
     std::vector<wrk::SampleParam> par;
     std::vector<wrk::PenaltyParam> pen;
+    std::vector<wrk::SampleFilter> filt;
     if (pk.sampled) {
         rc = wrk_sample_pack(ctx, opt->temperature, opt->top_p, opt->seed, R, par);
+        if (rc != WRK_OK) return rc;
+    }
+    if (pk.filtered) {
+        rc = wrk_filter_pack(ctx, opt->top_k, opt->min_p, R, filt);
         if (rc != WRK_OK) return rc;
     }
     if (pk.penalized) {
@@ -389,6 +417,8 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
         q.max_new = opt->max_new[r];
         WRK_ARG(ctx, q.max_new >= 1, "request %u: max_new 0", r);
         if (pk.sampled) { q.temperature = par[r].temperature; q.top_p = par[r].top_p; q.seed = par[r].seed; }
+        q.ln_min_p = -INFINITY;
+        if (pk.filtered) { q.top_k = filt[r].top_k; q.ln_min_p = filt[r].ln_min_p; }
         if (pk.penalized) { q.presence = pen[r].presence; q.frequency = pen[r].frequency; q.decay = pen[r].decay; }
         if (!opt->stop_offsets) continue;
         const uint32_t n = opt->stop_offsets[r + 1] - opt->stop_offsets[r];
@@ -411,19 +441,21 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
     pk.first_tokens.assign(B, pk.pool[0]);
     if (pk.sampled) pk.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
     if (pk.penalized) pk.pen.resize(B);
+    if (pk.filtered) pk.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
     for (uint32_t b = 0; b < B; ++b) {
         const uint32_t r = b < R ? b : 0;       // idle slots: any valid row
         const wrk::QueueReq& q = pk.reqs[r];
         if (b < R) pk.first_tokens[b] = pk.pool[q.prompt_off];
         if (pk.sampled && b < R) pk.par[b] = wrk::SampleParam{q.temperature, q.top_p, q.seed, q.prompt_len - 1};
+        if (pk.filtered && b < R) pk.filt[b] = wrk::SampleFilter{q.top_k, q.ln_min_p};
         if (pk.penalized) pk.pen[b] = opt->occ->row(b, q.presence, q.frequency, q.decay);
     }
     return WRK_OK;
 }
 
-static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, bool sampled, bool penalized) {
+static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, bool sampled, bool penalized, bool filtered) {
     return wrk::QueueBufs{f.queue_slots, f.queue_reqs, f.queue_pool, f.queue_log, f.queue_ctl, f.queue_started,
-                          sampled ? f.sample_par : nullptr, penalized ? f.pen_par : nullptr};
+                          sampled ? f.sample_par : nullptr, penalized ? f.pen_par : nullptr, filtered ? f.filter_par : nullptr};
 }
 
 static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V) {
@@ -452,17 +484,18 @@ int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t 
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_ctl, &ctl, sizeof ctl);
     if (rc != WRK_OK) return rc;
     // the slots that start a request at step 0 are reset as the step that ends a request resets its slot
-    wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.sampled, pk.penalized), B, ctx->num_cu);
+    wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.sampled, pk.penalized, pk.filtered), B, ctx->num_cu);
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
 }
 
-int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop) {
+int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop,
+                               bool filtered) {
     hipStream_t q = f.ctx->op_stream();
     if (!f.queue_ctl || B > f.queue_slot_cap || stop.b0 != 0 || B > stop.st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
     if (penalized) wrk::occurrence_update_queue(q, V, B, f.pen_par, io.argmax, f.queue_slots);
-    const wrk::QueueBufs bufs = queue_bufs(f, sampled, penalized);
+    const wrk::QueueBufs bufs = queue_bufs(f, sampled, penalized, filtered);
     wrk::advance_queue(q, io.argmax, io.tokens, f.history, io.counter, bufs, B);
     wrk::queue_reset(q, queue_geom(stop.st, stop.b0, V), bufs, B, f.ctx->num_cu);
     return WRK_OK;
@@ -512,7 +545,7 @@ int32_t wrk_enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V,
 }
 
 int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
-                         const wrk_stop_step* stop) {
+                         const wrk_stop_step* stop, bool filtered) {
     hipStream_t q = f.ctx->op_stream();
     const float* logits = io.head_o;
     if (penalized) {
@@ -521,9 +554,11 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint
     }
     // the sampler only reads the counter: rows run in different workgroups, so advance_tokens moves it after all of them
     if (!sampled) wrk::argmax_rows(q, io.head_o, V, V, B, io.argmax);
-    else if (wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax) != 0)
+    else if (filtered && (!f.filter_par || B > f.filter_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
+    else if ((filtered ? wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax)
+                       : wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax)) != 0)
         return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
-    if (stop && stop->queue) return wrk_enqueue_queue_tail(f, io, V, B, sampled, penalized, *stop);
+    if (stop && stop->queue) return wrk_enqueue_queue_tail(f, io, V, B, sampled, penalized, *stop, filtered);
     if (stop) return wrk_enqueue_stop_tail(f, io, V, B, penalized, *stop);
     if (penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
     wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);

@@ -9,6 +9,14 @@
 //   passes 1-5  digits = bits [41,52), [30,41), [19,30), [8,19), [0,8) of K, among the tokens left in the chosen bins;
 // each pass stops the descent as soon as the chosen bin holds one token.  Masses are fixed point (e * 2^40 in u64): every sum that
 // feeds a decision is an integer sum, so the result does not depend on the order the atomics land in.
+//
+// sample_rows_filtered_kernel (DESIGN.md "Top-k and min-p") shares the body.  A top-k cut is one more prefix of the same order: its
+// boundary, the token at rank top_k - 1, is a COUNT select over K, and the pass histograms already hold cnt next to mass, so it rides the
+// nucleus's descent: each pass finds the bin the mass target chooses and the bin the count target chooses; the higher bin (the earlier
+// rank) wins and the other target is dropped, equal bins descend with both.  The min-p cut, fl32(l - mx) >= ln(min_p), is part of the
+// draw's candidate predicate.
+#include <cmath>
+
 #include "wrk_device.h"
 
 namespace wrk {
@@ -45,6 +53,7 @@ struct SampleSmem {
     uint32_t widx[SAMPLE_THREADS / WAVE];
     unsigned long long sel_above;
     uint32_t sel, sel_cnt, sel_idx;
+    uint32_t wcnt[SAMPLE_THREADS / WAVE], selk, sel_cabove;     // filtered kernel: the count select next to the mass select
 };
 
 // exclusive prefix of v over the workgroup in thread order; *total = the sum (same value in every thread)
@@ -69,13 +78,42 @@ __device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long
     return before + x - v;
 }
 
+// block_excl_scan of v and of c in one go; *cbefore = the exclusive prefix of c
+__device__ __forceinline__ unsigned long long block_excl_scan2(unsigned long long v, uint32_t c, SampleSmem& sm, unsigned long long* total,
+                                                               uint32_t* cbefore) {
+    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned long long x = v;
+    uint32_t y = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long t = __shfl_up(x, o, WAVE);
+        const uint32_t u = __shfl_up(y, o, WAVE);
+        if (lane >= (uint32_t)o) { x += t; y += u; }
+    }
+    if (lane == 63) { sm.wsum[wid] = x; sm.wcnt[wid] = y; }
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+    uint32_t cb = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < SAMPLE_THREADS / WAVE; ++w) {
+        const unsigned long long s = sm.wsum[w];
+        if (w < wid) { before += s; cb += sm.wcnt[w]; }
+        all += s;
+    }
+    *total = all;
+    *cbefore = cb + y - c;
+    return before + x - v;
+}
+
+static constexpr uint32_t SAMPLE_NO_COUNT = 0xffffffffu;
+
 // One row per workgroup.  NPT > 0: the row (V <= 1024 * NPT) stays in registers; NPT == 0: every pass re-reads it from L2 (V <= 2^20;
 // a 64-per-thread register copy of a 65536-token row spills, the passes' own state needs ~95 VGPRs)
-template <int NPT>
-__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
-                                                                     const SampleParam* __restrict__ par, const uint32_t* __restrict__ step_word,
-                                                                     uint32_t* __restrict__ out) {
-    __shared__ SampleSmem sm;
+// FILT: the filtered kernel's body (filt: one SampleFilter per row); every addition sits under `if constexpr (FILT)`
+template <int NPT, bool FILT>
+__device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __restrict__ logits, uint32_t V, uint32_t stride,
+                                                 const SampleParam* __restrict__ par, const SampleFilter* __restrict__ filt,
+                                                 const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* row = logits + (size_t)blockIdx.x * stride;
     const int nj = NPT > 0 ? NPT : (int)((V + SAMPLE_THREADS - 1) / SAMPLE_THREADS);
@@ -137,7 +175,14 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
 
     const SampleParam pr = par[blockIdx.x];
     const float temp = pr.temperature, top_p = pr.top_p;
-    if (!(temp > 0.0f) || !(top_p > 0.0f) || mx == -INFINITY) {       // greedy: bit-identical to argmax_rows
+    uint32_t top_k = 0;             // 0: no top-k cut (top_k >= V cuts nothing either)
+    float ln_min_p = -INFINITY;
+    if constexpr (FILT) {
+        const SampleFilter fl = filt[blockIdx.x];
+        top_k = fl.top_k >= V ? 0u : fl.top_k;
+        ln_min_p = fl.ln_min_p;
+    }
+    if (!(temp > 0.0f) || !(top_p > 0.0f) || mx == -INFINITY || (FILT && top_k == 1)) {       // greedy: bit-identical to argmax_rows
         if (tid == 0) out[blockIdx.x] = mx > -3.0e38f ? top : 0u;
         return;
     }
@@ -146,7 +191,13 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
     // Weighted select over K among the tokens with K >= kmin.  use_w = false: masses e = exp(l - mx); the LAST rank whose mass before
     // it is <= P * sum (the nucleus boundary).  use_w = true: masses w = exp((l - mx) / T); the FIRST rank whose mass up to and
     // including it is >= u * sum (the draw).  Returns the token index.
-    auto select = [&](bool use_w, uint64_t kmin) -> uint32_t {
+    // FILT, boundary only: by_mass = false drops the mass target (no mass atomics, no expf); ktarget != SAMPLE_NO_COUNT adds the count
+    // target, the LAST rank with at most ktarget tokens before it.  The earlier of the two ranks is returned.  FILT, draw: the candidates
+    // also pass the min-p test
+    auto select = [&](bool use_w, uint64_t kmin, bool by_mass, uint32_t ktarget) -> uint32_t {
+        bool live_p = FILT ? by_mass : true;                        // the target is still inside the chosen bins
+        bool live_k = FILT ? ktarget != SAMPLE_NO_COUNT : false;
+        uint32_t cbase = 0;             // number of the candidates' predecessors
         uint32_t sel0 = 0;              // pass-0 bin
         uint64_t prefix = 0;            // K bits [lo, 52) of the candidates (passes >= 2)
         uint32_t lo = 52;
@@ -155,7 +206,10 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
         for (int p = 0; p < 6; ++p) {
             const uint32_t width = p == 5 ? 8 : 11, shift = p == 5 ? 0 : 52 - 11 * p;    // passes >= 1: K bits [shift, shift + width)
             for (uint32_t b = tid; b < SAMPLE_BINS; b += SAMPLE_THREADS) { sm.mass[b] = 0; sm.cnt[b] = 0; sm.idx[b] = 0; }
-            if (tid == 0) sm.sel = use_w ? 0u : 0xffffffffu;
+            if (tid == 0) {
+                sm.sel = use_w ? 0u : 0xffffffffu;
+                if constexpr (FILT) sm.selk = 0xffffffffu;
+            }
             if constexpr (NPT > 0) {
                 // keys are cheap to recompute; hoisted out of the pass loop they would take three more registers per element and spill
 #pragma unroll
@@ -167,12 +221,17 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
                 const uint64_t k = rank_key(l, i);
                 const uint32_t c = coarse_digit(l, mx, scale);
                 bool cand = i < V && k >= kmin;
+                if constexpr (FILT) {
+                    if (use_w) cand = cand && (l == mx || l - mx >= ln_min_p);      // rank 0 always passes (mx = +inf: inf - inf is NaN)
+                }
                 if (p >= 1) cand = cand && c == sel0;
                 if (p >= 2) cand = cand && (k >> lo) == prefix;
                 if (cand) {
                     const uint32_t d = p == 0 ? c : (uint32_t)(k >> shift) & ((1u << width) - 1u);
-                    const float e = l == mx ? 1.0f : expf(use_w ? (l - mx) * inv_t : l - mx);
-                    atomicAdd(&sm.mass[d], (unsigned long long)(e * SAMPLE_ONE));
+                    if (live_p) {
+                        const float e = l == mx ? 1.0f : expf(use_w ? (l - mx) * inv_t : l - mx);
+                        atomicAdd(&sm.mass[d], (unsigned long long)(e * SAMPLE_ONE));
+                    }
                     atomicAdd(&sm.cnt[d], 1u);
                     atomicMax(&sm.idx[d], i);
                 }
@@ -182,10 +241,15 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
             const uint32_t dh = SAMPLE_BINS - 1 - 2 * tid, dl = dh - 1;
             const unsigned long long mh = sm.mass[dh], ml = sm.mass[dl];
             unsigned long long total = 0;
-            const unsigned long long above_h = block_excl_scan(mh + ml, sm, &total), above_l = above_h + mh;
+            unsigned long long above_h;
+            uint32_t cabove_h = 0;      // tokens of the higher bins
+            if constexpr (FILT) above_h = block_excl_scan2(mh + ml, sm.cnt[dh] + sm.cnt[dl], sm, &total, &cabove_h);
+            else above_h = block_excl_scan(mh + ml, sm, &total);
+            const unsigned long long above_l = above_h + mh;
             if (p == 0) {
-                if (!use_w) target = (unsigned long long)floor((double)top_p * (double)total);
-                else {          // ceil(u * W), u = U / 2^24, in 128-bit integer arithmetic
+                if (!use_w) {
+                    if (live_p) target = (unsigned long long)floor((double)top_p * (double)total);
+                } else {          // ceil(u * W), u = U / 2^24, in 128-bit integer arithmetic
                     const unsigned long long U = sample_splitmix(pr.seed, *step_word - pr.step_base) >> 40;
                     const unsigned long long plo = U * total, phi = __umul64hi(U, total);
                     target = (phi << 40) | (plo >> 24);
@@ -193,24 +257,47 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
                 }
             }
             if (!use_w) {
-                if (sm.cnt[dl] && base + above_l <= target) atomicMin(&sm.sel, dl);
-                else if (sm.cnt[dh] && base + above_h <= target) atomicMin(&sm.sel, dh);
+                if (live_p) {
+                    if (sm.cnt[dl] && base + above_l <= target) atomicMin(&sm.sel, dl);
+                    else if (sm.cnt[dh] && base + above_h <= target) atomicMin(&sm.sel, dh);
+                }
+                if constexpr (FILT) {
+                    if (live_k) {
+                        const uint32_t ch = sm.cnt[dh], cl = sm.cnt[dl];
+                        if (cl && cbase + cabove_h + ch <= ktarget) atomicMin(&sm.selk, dl);
+                        else if (ch && cbase + cabove_h <= ktarget) atomicMin(&sm.selk, dh);
+                    }
+                }
             } else {
                 if (sm.cnt[dh] && base + above_h + mh >= target) atomicMax(&sm.sel, dh + 1);
                 else if (sm.cnt[dl] && base + above_l + ml >= target) atomicMax(&sm.sel, dl + 1);
             }
             __syncthreads();
-            const uint32_t raw = sm.sel;
-            const bool none = use_w ? raw == 0 : raw == 0xffffffffu;
-            const uint32_t d = use_w ? raw - 1 : raw;
+            // FILT: the words every thread reads back are pinned to scalar registers (the count select's state would otherwise cost ~25 VGPRs)
+            const uint32_t raw = FILT ? __builtin_amdgcn_readfirstlane(sm.sel) : sm.sel;
+            bool none = use_w ? raw == 0 : raw == 0xffffffffu;
+            uint32_t d = use_w ? raw - 1 : raw;
+            if constexpr (FILT) {
+                if (!use_w) {
+                    // the count target always finds a bin: the first bin that holds a token has nothing before it
+                    const uint32_t dk = live_k ? __builtin_amdgcn_readfirstlane(sm.selk) : 0xffffffffu;
+                    if (!live_p) { none = dk == 0xffffffffu; d = dk; }
+                    else if (!none && live_k) {
+                        if (dk == 0xffffffffu || dk < d) live_k = false;        // the nucleus ends first: its bin, the count target is dropped
+                        else if (dk > d) { d = dk; live_p = false; }            // the top-k cut ends first
+                    }
+                }
+            }
             if (!none && (d == dh || d == dl)) {
                 sm.sel_above = d == dh ? above_h : above_l;
                 sm.sel_cnt = sm.cnt[d];
                 sm.sel_idx = sm.idx[d];
+                if constexpr (FILT) sm.sel_cabove = d == dh ? cabove_h : cabove_h + sm.cnt[dh];
             }
             __syncthreads();
             if (none) return top;       // nothing qualifies (cannot happen in integer arithmetic): rank 0, find_or_first
             base += sm.sel_above;
+            if constexpr (FILT) cbase += __builtin_amdgcn_readfirstlane(sm.sel_cabove);
             const uint32_t n = sm.sel_cnt, ix = sm.sel_idx;
             __syncthreads();            // sel / sel_* are rewritten by the next pass
             if (n == 1 || p == 5) return ix;
@@ -221,13 +308,32 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
     };
 
     uint64_t kmin = 0;              // P >= 1: every token is in the nucleus
-    if (!(top_p >= 1.0f)) {
-        const uint32_t r = select(false, 0);
+    const bool cut_p = !(top_p >= 1.0f), cut_k = FILT && top_k != 0;
+    if (cut_p || cut_k) {           // kmin = max(kmin_P, kmin_K) in one descent; with cut_k alone it is count-only
+        const uint32_t r = select(false, 0, cut_p, cut_k ? top_k - 1u : SAMPLE_NO_COUNT);
         const float lr = row[r];       // r < V: a token index
         kmin = rank_key(lr != lr ? -INFINITY : lr + 0.0f, r);
     }
-    const uint32_t tok = select(true, kmin);
+    const uint32_t tok = select(true, kmin, true, SAMPLE_NO_COUNT);
     if (tid == 0) out[blockIdx.x] = tok;
+}
+
+template <int NPT>
+__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
+                                                                     const SampleParam* __restrict__ par, const uint32_t* __restrict__ step_word,
+                                                                     uint32_t* __restrict__ out) {
+    __shared__ SampleSmem sm;
+    sample_rows_body<NPT, false>(sm, logits, V, stride, par, nullptr, step_word, out);
+}
+
+// sample_rows_kernel with a top-k and a min-p cut per row (filt[row]); both off: sample_rows_kernel's token, bit for bit
+template <int NPT>
+__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_filtered_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
+                                                                              const SampleParam* __restrict__ par,
+                                                                              const SampleFilter* __restrict__ filt,
+                                                                              const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
+    __shared__ SampleSmem sm;
+    sample_rows_body<NPT, true>(sm, logits, V, stride, par, filt, step_word, out);
 }
 
 int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
@@ -238,6 +344,19 @@ int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride,
     else if (v <= 4096) sample_rows_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
     else if (v <= 16384) sample_rows_kernel<16><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
     else sample_rows_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
+    return 0;
+}
+
+int sample_rows_filtered(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
+                         const SampleFilter* filt, const uint32_t* step, uint32_t* out) {
+    if (n == 0) return 0;
+    if (v == 0 || v > SAMPLE_MAX_VOCAB || stride < v) return -1;
+    if (v <= 1024) sample_rows_filtered_kernel<1><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
+    else if (v <= 4096) sample_rows_filtered_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
+    // a 16-per-thread register copy spills next to the count select's state (88 bytes of scratch per lane): this variant keeps 8 per
+    // thread, and rows of 8193..16384 tokens are re-read from L2
+    else if (v <= 8192) sample_rows_filtered_kernel<8><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
+    else sample_rows_filtered_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
     return 0;
 }
 
@@ -256,30 +375,65 @@ int32_t wrk_sample_pack(wrk_ctx* ctx, const float* temperature, const float* top
     return WRK_OK;
 }
 
-extern "C" int32_t wrk_sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const float* temperature,
-                                     const float* top_p, const uint32_t* seed, uint32_t step, uint32_t* out_tokens) {
+int32_t wrk_filter_pack(wrk_ctx* ctx, const uint32_t* top_k, const float* min_p, uint32_t n, std::vector<wrk::SampleFilter>& out) {
+    out.assign(n, wrk::SampleFilter{0u, -INFINITY});
+    for (uint32_t b = 0; b < n; ++b) {
+        if (top_k) out[b].top_k = top_k[b];
+        if (!min_p) continue;
+        const float p = min_p[b];
+        WRK_ARG(ctx, !(p != p) && p >= 0.0f && p <= 1.0f, "min_p[%u] = %g: must be in [0, 1]", b, (double)p);
+        out[b].ln_min_p = (float)std::log((double)p);       // f64, rounded once; min_p = 0: -inf, every token passes
+    }
+    return WRK_OK;
+}
+
+// filtered: the filtered kernel on (top_k, min_p), either of which may be NULL
+static int32_t sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const float* temperature,
+                             const float* top_p, bool filtered, const uint32_t* top_k, const float* min_p, const uint32_t* seed, uint32_t step,
+                             uint32_t* out_tokens, const char* who) {
     if (!ctx || !logits || !out_tokens) return WRK_E_ARG;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     std::vector<wrk::SampleParam> par;
+    std::vector<wrk::SampleFilter> filt;
     int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, n, par);
+    if (rc == WRK_OK && filtered) rc = wrk_filter_pack(ctx, top_k, min_p, n, filt);
     if (rc != WRK_OK) return rc;
     if (n == 0) return WRK_OK;
-    WRK_ARG(ctx, !ctx->capturing_here(), "wrk_sample_logits is blocking: not inside a capture");
+    WRK_ARG(ctx, !ctx->capturing_here(), "%s is blocking: not inside a capture", who);
     WRK_ARG(ctx, V >= 1 && stride >= V, "num_vocab %u / row_stride %u", V, stride);
     if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "num_vocab %u > %u", V, wrk::SAMPLE_MAX_VOCAB);
     WRK_ARG(ctx, ((size_t)(n - 1) * stride + V) * 4 <= logits->bytes, "%u rows of stride %u exceed the buffer of %zu bytes", n, stride,
             logits->bytes);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_step = (size_t)n * sizeof(wrk::SampleParam), o_out = o_step + 256;
+    const size_t o_step = (size_t)n * sizeof(wrk::SampleParam), o_out = o_step + 256, o_filt = (o_out + (size_t)n * 4 + 255) / 256 * 256;
     char* dev = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&dev, o_out + (size_t)n * 4));
+    WRK_HIP(ctx, hipMalloc((void**)&dev, o_filt + (size_t)n * sizeof(wrk::SampleFilter)));
     struct Free { char* p; ~Free() { hipFree(p); } } guard{dev};
     WRK_HIP(ctx, hipMemcpyAsync(dev, par.data(), o_step, hipMemcpyHostToDevice, ctx->stream));
     WRK_HIP(ctx, hipMemcpyAsync(dev + o_step, &step, 4, hipMemcpyHostToDevice, ctx->stream));
-    wrk::sample_rows(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, (const uint32_t*)(dev + o_step),
-                     (uint32_t*)(dev + o_out));
+    if (filtered) {
+        WRK_HIP(ctx, hipMemcpyAsync(dev + o_filt, filt.data(), (size_t)n * sizeof(wrk::SampleFilter), hipMemcpyHostToDevice, ctx->stream));
+        wrk::sample_rows_filtered(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev,
+                                  (const wrk::SampleFilter*)(dev + o_filt), (const uint32_t*)(dev + o_step), (uint32_t*)(dev + o_out));
+    } else {
+        wrk::sample_rows(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, (const uint32_t*)(dev + o_step),
+                         (uint32_t*)(dev + o_out));
+    }
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipMemcpyAsync(out_tokens, dev + o_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
+}
+
+extern "C" int32_t wrk_sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const float* temperature,
+                                     const float* top_p, const uint32_t* seed, uint32_t step, uint32_t* out_tokens) {
+    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, false, nullptr, nullptr, seed, step, out_tokens, "wrk_sample_logits");
+}
+
+// both filter arrays NULL: wrk_sample_logits' kernel
+extern "C" int32_t wrk_sample_logits_filtered(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n,
+                                              const float* temperature, const float* top_p, const uint32_t* top_k, const float* min_p,
+                                              const uint32_t* seed, uint32_t step, uint32_t* out_tokens) {
+    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, top_k || min_p, top_k, min_p, seed, step, out_tokens,
+                         "wrk_sample_logits_filtered");
 }

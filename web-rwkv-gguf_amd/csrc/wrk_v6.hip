@@ -16,7 +16,7 @@ struct V6Scratch : wrk::FrameIo {
     float* ks_part; uint32_t* ks_cnt; size_t ks_part_cap; uint32_t ks_cnt_cap;     // K-sliced GEMM scratch (2 .. 32 sequences), see MatJob
 };
 
-struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64 | stop 128 | queue 256)
+struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64 | stop 128 | queue 256 | filtered 512)
     wrk_v6_model_desc d{};
     std::vector<wrk_v6_layer_desc> layers;
     V6Scratch s{};
@@ -639,7 +639,7 @@ static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, cons
     }
     if (steps == 0) return WRK_OK;
     rc = m->ensure_scratch(B, B);
-    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, V, first_tokens, 0, B, steps, pp.par, pp.pen);
+    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, V, first_tokens, 0, B, steps, pp.par, pp.pen, pp.filt);
     if (rc == WRK_OK && stop_opt) rc = wrk_stop_prepare(*m, st, V, B, stop_rows.data());
     if (rc != WRK_OK) return rc;
     const wrk_stop_step ss{st, 0};
@@ -651,11 +651,12 @@ static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, cons
         if (mode == 1) r = m->enqueue_fused_decode(st, B, B, true, 0);
         if (r == WRK_E_UNSUPPORTED) r = m->enqueue_ops(st, B, B, true);
         if (r != WRK_OK) return r;
-        return wrk_enqueue_pick(*m, m->s, V, B, pp.par != nullptr, pp.pen != nullptr, stop_opt ? &ss : nullptr);
+        return wrk_enqueue_pick(*m, m->s, V, B, pp.par != nullptr, pp.pen != nullptr, stop_opt ? &ss : nullptr, pp.filt != nullptr);
     };
     std::vector<wrk_lane> lane{{&m->s, m->history, 0, B, nullptr, m}};
     if (!eager) {
-        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pp.par ? 32u : 0u) | (pp.pen ? 64u : 0u) | (stop_opt ? 128u : 0u)}, enqueue_step,
+        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pp.par ? 32u : 0u) | (pp.pen ? 64u : 0u) | (stop_opt ? 128u : 0u) | (pp.filt ? 512u : 0u)},
+                                enqueue_step,
                                 &lane[0].prog);
         if (rc != WRK_OK) return rc;
     }
@@ -715,7 +716,7 @@ int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, u
     rc = m->ensure_scratch(B, B);
     if (rc == WRK_OK)
         rc = wrk_decode_prepare(*m, m->s, V, pk.first_tokens.data(), 0, B, pk.max_steps, pk.sampled ? pk.par.data() : nullptr,
-                                pk.penalized ? pk.pen.data() : nullptr);
+                                pk.penalized ? pk.pen.data() : nullptr, pk.filtered ? pk.filt.data() : nullptr);
     if (rc == WRK_OK) rc = wrk_queue_prepare(*m, st, V, B, pk);
     if (rc != WRK_OK) return rc;
     const wrk_stop_step ss{st, 0, true};
@@ -727,11 +728,12 @@ int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, u
         if (mode == 1) r = m->enqueue_fused_decode(st, B, B, true, 0);
         if (r == WRK_E_UNSUPPORTED) r = m->enqueue_ops(st, B, B, true);
         if (r != WRK_OK) return r;
-        return wrk_enqueue_pick(*m, m->s, V, B, pk.sampled, pk.penalized, &ss);
+        return wrk_enqueue_pick(*m, m->s, V, B, pk.sampled, pk.penalized, &ss, pk.filtered);
     };
     std::vector<wrk_lane> lane{{&m->s, m->history, 0, B, nullptr, m}};
     if (!eager) {
-        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pk.sampled ? 32u : 0u) | (pk.penalized ? 64u : 0u) | 256u}, enqueue_step,
+        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pk.sampled ? 32u : 0u) | (pk.penalized ? 64u : 0u) | 256u | (pk.filtered ? 512u : 0u)},
+                                enqueue_step,
                                 &lane[0].prog);
         if (rc != WRK_OK) return rc;
     }

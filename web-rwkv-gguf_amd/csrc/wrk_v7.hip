@@ -619,8 +619,9 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
 // tokens / history / counter (wrk_enqueue_pick; the fused greedy path does both inside its head launch)
 // stop: a stop program's step (wrk_stop.hip) -- the fused greedy head keeps its arg-max and leaves the advance to the stop tail;
 // queue (with stop): a queue program's step (wrk_queue.hip), the queue tail in the stop tail's place
+// filtered (with sampled): the pick is the filtered sampler's (top-k / min-p rows of the frame)
 static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled,
-                                   bool penalized, bool stop = false, bool queue = false) {
+                                   bool penalized, bool stop = false, bool queue = false, bool filtered = false) {
     int32_t rc;
     const wrk_stop_step ss{st, b0, queue};
     if (mode == 1 && m->act_dtype == WRK_F16) {
@@ -633,7 +634,7 @@ static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* 
         rc = m->enqueue_ops(st, B, B, true);
     }
     if (rc != WRK_OK) return rc;
-    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, sampled, penalized, stop ? &ss : nullptr);
+    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, sampled, penalized, stop ? &ss : nullptr, filtered);
 }
 
 // generate_greedy / generate_sample / generate_penalized, part 1: frame, token / cursor / sampler-parameter upload and the (cached)
@@ -641,23 +642,25 @@ static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* 
 // pen: their occurrence rows and penalties (with par), or nullptr
 static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t b0, uint32_t B,
                               uint32_t steps, uint32_t mode, bool eager, const wrk::SampleParam* par, const wrk::PenaltyParam* pen,
-                              const wrk::StopParam* stop, wrk_program** prog_out, const wrk_queue_pack* queue = nullptr) {
+                              const wrk::StopParam* stop, wrk_program** prog_out, const wrk_queue_pack* queue = nullptr,
+                              const wrk::SampleFilter* filt = nullptr) {
     int32_t rc = m->ensure_scratch(B, B);
     if (rc == WRK_OK && B == 1 && mode == 1) rc = m->ensure_engine();
-    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, m->d.num_vocab, first_tokens, b0, B, steps, par, pen);
+    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, m->d.num_vocab, first_tokens, b0, B, steps, par, pen, filt);
     if (rc == WRK_OK && stop) rc = wrk_stop_prepare(*m, st, m->d.num_vocab, B, stop);
     if (rc == WRK_OK && queue) rc = wrk_queue_prepare(*m, st, m->d.num_vocab, B, *queue);
     *prog_out = nullptr;
     if (rc != WRK_OK || eager) return rc;
     // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo; sampled
     // steps have their own key bit, so greedy and sampled programs never alias, and so do penalised ones (bit 24, above every infer flag)
-    // and stop programs (bit 25) and queue programs (bit 26)
+    // and stop programs (bit 25), queue programs (bit 26) and programs whose pick is the filtered sampler (bit 27)
     const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
                                                              (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u) | (pen ? 1u << 24 : 0u) |
-                                                             (stop ? 1u << 25 : 0u) | (queue ? 1u << 26 : 0u)};
+                                                             (stop ? 1u << 25 : 0u) | (queue ? 1u << 26 : 0u) | (filt ? 1u << 27 : 0u)};
     return wrk_cached_program(ctx, m->graphs, key,
                               [&] {
-                                  return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr, stop || queue, queue != nullptr);
+                                  return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr, stop || queue, queue != nullptr,
+                                                             filt != nullptr);
                               },
                               prog_out);
 }
@@ -677,6 +680,7 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
     if (rc != WRK_OK) return rc;
     const wrk::SampleParam* par = pp.par;
     const wrk::PenaltyParam* pen = pp.pen;
+    const wrk::SampleFilter* filt = pp.filt;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     if (stop_opt) {
         *steps_run = 0;
@@ -720,7 +724,8 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
         L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
         // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
         rc = decode_prepare(ctx, mdl, st, first_tokens + L[g].b0, L[g].b0, L[g].nb, steps, mode, eager, par ? par + L[g].b0 : nullptr,
-                            pen ? pen + L[g].b0 : nullptr, stop_opt ? stop_rows.data() + L[g].b0 : nullptr, &L[g].prog);
+                            pen ? pen + L[g].b0 : nullptr, stop_opt ? stop_rows.data() + L[g].b0 : nullptr, &L[g].prog, nullptr,
+                            filt ? filt + L[g].b0 : nullptr);
         if (rc != WRK_OK) return rc;
         L[g].io = &mdl->s;
         L[g].history = mdl->history;
@@ -728,7 +733,8 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
     }
     const wrk_stop_run stop_run{st, stop_opt ? stop_opt->poll_steps : 0u, out_lengths, steps_run};
     rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, steps,
-                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr, pen != nullptr, stop_opt != nullptr); }, out_tokens,
+                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr, pen != nullptr, stop_opt != nullptr, false, filt != nullptr); },
+                       out_tokens,
                        last_logits, elapsed_ms, stop_opt ? &stop_run : nullptr);
     if (rc != WRK_OK) return rc;
     wrk::timing_report(ctx);
@@ -795,13 +801,13 @@ int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, u
     m->engine_blocked = false;
     std::vector<wrk_lane> L(1);
     rc = decode_prepare(ctx, m, st, pk.first_tokens.data(), 0, B, pk.max_steps, mode, eager, pk.sampled ? pk.par.data() : nullptr,
-                        pk.penalized ? pk.pen.data() : nullptr, nullptr, &L[0].prog, &pk);
+                        pk.penalized ? pk.pen.data() : nullptr, nullptr, &L[0].prog, &pk, pk.filtered ? pk.filt.data() : nullptr);
     if (rc != WRK_OK) return rc;
     L[0].io = &m->s; L[0].history = m->history; L[0].b0 = 0; L[0].nb = B; L[0].frame = m;
     uint32_t steps_run = 0;
     const wrk_stop_run run{st, pk.poll_steps, nullptr, &steps_run, true};
     rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, pk.max_steps,
-                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, pk.sampled, pk.penalized, true, true); }, nullptr, nullptr, elapsed_ms,
+                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, pk.sampled, pk.penalized, true, true, pk.filtered); }, nullptr, nullptr, elapsed_ms,
                        &run);
     if (rc != WRK_OK) return rc;
     rc = wrk_v7_engine_check(m->engine);

@@ -75,7 +75,8 @@ class GenerateOptions(C.Structure):
     """wrk_generate_options: the pick (sampler arrays all NULL: arg-max; occ NULL: no penalties) and the stop sets (CSR) of
     wrk_v*_generate_stop."""
     _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
-                ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32)]
+                ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
+                ("top_k", _u32p), ("min_p", _f32p)]
 
 
 class QueueOptions(C.Structure):
@@ -84,7 +85,7 @@ class QueueOptions(C.Structure):
     _fields_ = [("num_requests", C.c_uint32), ("prompt_tokens", _u32p), ("prompt_offsets", _u32p), ("max_new", _u32p),
                 ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p),
                 ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("init_state", _P),
-                ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32)]
+                ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32), ("top_k", _u32p), ("min_p", _f32p)]
 
 
 class QueueResult(C.Structure):
@@ -163,6 +164,8 @@ HIP_SYMBOLS = {
     "wrk_v6_infer": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _f32p, _u32p, C.c_uint32]),
     "wrk_v6_generate_greedy": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p, _f32p, C.c_uint32]),
     "wrk_sample_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, C.c_uint32, _u32p]),
+    "wrk_sample_logits_filtered": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _f32p, _u32p, C.c_uint32,
+                                               _u32p]),
     "wrk_v7_generate_sample": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _f32p, _f32p,
                                            C.c_uint32]),
     "wrk_v6_generate_sample": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _f32p, _f32p,
@@ -248,6 +251,19 @@ def _per_row(v, n: int, dtype) -> np.ndarray:
     return a
 
 
+def _filters(top_k, min_p, n: int, keep: list):
+    """(top_k pointer, min_p pointer) of the filtered sampler's per-row arrays, None for a filter that is off; the arrays go into
+    `keep`, which must outlive the call."""
+    tk = mp = None
+    if top_k is not None:
+        keep.append(_per_row(top_k, n, np.uint32))
+        tk = _ptr(keep[-1], _u32p)
+    if min_p is not None:
+        keep.append(_per_row(min_p, n, np.float32))
+        mp = _ptr(keep[-1], _f32p)
+    return tk, mp
+
+
 # ----------------------------------------------------------------------------- backend objects
 class Context:
     """`Context` (src/context.rs:51-64): one HIP device + submission stream."""
@@ -304,10 +320,12 @@ class Context:
         a = np.ascontiguousarray(array)
         return Buffer(self, a.nbytes, a)
 
-    def sample_logits(self, logits, temperature=1.0, top_p=0.5, seed=0, step: int = 0, num_vocab: Optional[int] = None) -> np.ndarray:
+    def sample_logits(self, logits, temperature=1.0, top_p=0.5, seed=0, step: int = 0, num_vocab: Optional[int] = None,
+                      top_k=None, min_p=None) -> np.ndarray:
         """`Sampler::sample` (examples/chat.rs:150-190; defaults are its `--temp 1.0 --top-p 0.5`) on the device, one token per row.
         `logits`: an [n, V] f32 array, or a `Buffer` of n rows of `num_vocab` f32; temperature / top_p / seed: scalars or per-row arrays.
-        Returns uint32 [n]."""
+        top_k (0: off) / min_p (0: off): scalars or per-row arrays; with either the candidates are also cut to the top_k highest logits
+        and to the tokens whose probability is at least min_p times the largest.  Returns uint32 [n]."""
         if isinstance(logits, Buffer):
             assert num_vocab, "a Buffer needs num_vocab"
             buf, V = logits, int(num_vocab)
@@ -319,7 +337,13 @@ class Context:
             buf = self.buffer(a)
         t, p, sd = _per_row(temperature, n, np.float32), _per_row(top_p, n, np.float32), _per_row(seed, n, np.uint32)
         out = np.zeros(n, np.uint32)
-        self.check(hip.wrk_sample_logits(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p), step, _ptr(out, _u32p)))
+        if top_k is None and min_p is None:
+            self.check(hip.wrk_sample_logits(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p), step, _ptr(out, _u32p)))
+            return out
+        keep = []
+        tk, mp = _filters(top_k, min_p, n, keep)
+        self.check(hip.wrk_sample_logits_filtered(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), tk, mp, _ptr(sd, _u32p), step,
+                                                  _ptr(out, _u32p)))
         return out
 
     def score_logits(self, logits, targets, num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
@@ -959,10 +983,28 @@ class Runtime:
                           _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
 
+    def _generate_options(self, first_tokens, steps, opt, keep, mode, want_logits):
+        """wrk_v*_generate_stop on prepared options: (tokens [steps, B], lengths [B], steps_run, elapsed ms, last logits or None)."""
+        ft = _u32(first_tokens)
+        B = ft.size
+        out = np.zeros((steps, B), np.uint32)
+        lengths = np.zeros(B, np.uint32)
+        run, ms = C.c_uint32(), C.c_float()
+        logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
+        fn, mdl = (hip.wrk_v6_generate_stop, self.model6) if self.model6 else (hip.wrk_v7_generate_stop, self.model)
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, C.byref(opt), _ptr(out, _u32p), _ptr(lengths, _u32p),
+                          _ptr(logits, _f32p) if want_logits else None, C.byref(run), C.byref(ms), mode))
+        return out, lengths, run.value, ms.value, logits
+
     def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
-                        groups: int = 1):
+                        groups: int = 1, top_k=None, min_p=None):
         """As `generate_greedy`, each sequence's next token drawn by `Sampler::sample` (examples/chat.rs:150-190) on the device with its
-        own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b."""
+        own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b.
+        top_k / min_p (a scalar or one value per sequence; None: off): the draw is `sample_logits(..., top_k, min_p)`'s; such a call goes
+        through the options entry point (wrk_v*_generate_stop without stop sets) and replays step programs of its own."""
+        if top_k is not None or min_p is not None:
+            return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
+                                           want_logits, groups)
         mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
         ft = _u32(first_tokens)
         B = ft.size
@@ -976,12 +1018,37 @@ class Runtime:
                           _ptr(out, _u32p), _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
 
+    def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
+                           want_logits, groups):
+        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
+        B = _u32(first_tokens).size
+        opt, keep = GenerateOptions(), []
+        t, p = _per_row(temperature, B, np.float32), _per_row(top_p, B, np.float32)
+        sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
+        keep += [t, p, sd]
+        opt.temperature, opt.top_p, opt.seed = _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p)
+        if occurrence is not None:
+            ap, af, g = _per_row(presence, B, np.float32), _per_row(frequency, B, np.float32), _per_row(decay, B, np.float32)
+            keep += [ap, af, g]
+            opt.presence, opt.frequency, opt.decay, opt.occ = _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h
+        tk, mp = _filters(top_k, min_p, B, keep)
+        if tk is not None:
+            opt.top_k = tk
+        if mp is not None:
+            opt.min_p = mp
+        out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, mode, want_logits)
+        return (out, ms, logits) if want_logits else (out, ms)
+
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
-                           frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1):
+                           frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1, top_k=None, min_p=None):
         """As `generate_sample`, each draw made on the logits penalised with the sequence's slot of `occurrence` (ChatRWKV's
         alpha_presence / alpha_frequency / token_ban), and the slot updated after every draw (count *= decay, then the drawn token's
         weight added).  The first token of a call is not counted; the last drawn one is.  The table carries over between calls.
-        Scalars broadcast; seed=None: seed[b] = b.  last logits: the head output before penalties."""
+        Scalars broadcast; seed=None: seed[b] = b.  last logits: the head output before penalties.  top_k / min_p: as `generate_sample`,
+        the cuts made on the penalised logits."""
+        if top_k is not None or min_p is not None:
+            return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
+                                           min_p, mode, want_logits, groups)
         mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
         ft = _u32(first_tokens)
         B = ft.size
@@ -999,13 +1066,13 @@ class Runtime:
 
     def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
-                      poll_steps: int = 0):
+                      poll_steps: int = 0, top_k=None, min_p=None):
         """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
         at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
         MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
         are what the call without stops draws, the stop token last; later rows repeat it.  The state slot, the occurrence slot and the
         logits row of a finished sequence are those of a `lengths[b]`-step call.  steps_run < steps once every sequence has ended (the host
-        looks every `poll_steps` steps; 0: the default)."""
+        looks every `poll_steps` steps; 0: the default).  top_k / min_p: as `generate_sample` (they make the pick a sampled one)."""
         mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
         ft = _u32(first_tokens)
         B = ft.size
@@ -1021,7 +1088,8 @@ class Runtime:
             ids = np.zeros(1, np.uint32)
         opt = GenerateOptions()
         keep = []
-        sampled = temperature is not None or top_p is not None or seed is not None or occurrence is not None
+        sampled = (temperature is not None or top_p is not None or seed is not None or occurrence is not None or top_k is not None
+                   or min_p is not None)
         if sampled:
             t = _per_row(1.0 if temperature is None else temperature, B, np.float32)
             p = _per_row(0.5 if top_p is None else top_p, B, np.float32)
@@ -1033,20 +1101,18 @@ class Runtime:
             keep += [ap, af, g]
             opt.presence, opt.frequency, opt.decay, opt.occ = _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h
         opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
-        out = np.zeros((steps, B), np.uint32)
-        lengths = np.zeros(B, np.uint32)
-        run, ms = C.c_uint32(), C.c_float()
-        logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
-        fn, mdl = (hip.wrk_v6_generate_stop, self.model6) if self.model6 else (hip.wrk_v7_generate_stop, self.model)
-        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, C.byref(opt), _ptr(out, _u32p), _ptr(lengths, _u32p),
-                          _ptr(logits, _f32p) if want_logits else None, C.byref(run), C.byref(ms), mode))
-        self.last_stop_ms = ms.value
-        out = out[:run.value]
+        tk, mp = _filters(top_k, min_p, B, keep)
+        if tk is not None:
+            opt.top_k = tk
+        if mp is not None:
+            opt.min_p = mp
+        out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, mode, want_logits)
+        out = out[:run]
         return (out, lengths, logits) if want_logits else (out, lengths)
 
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
-                       mode: int = 1):
+                       mode: int = 1, top_k=None, min_p=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1054,7 +1120,8 @@ class Runtime:
         parameters broadcast from scalars; seed=None: seed[r] = r.  The sampler step of a reply token is its index in the reply, so a
         reply does not depend on when its request was scheduled.  Returns ([(tokens, reason, slot, start_step)] per request, steps_run):
         reason 1 stop token (part of the reply), 2 max_new, 3 cut by max_steps, 0 never dispatched.  max_steps defaults to the sum of
-        prompt and max_new lengths, enough even for one slot.  The state and the occurrence rows are unspecified afterwards."""
+        prompt and max_new lengths, enough even for one slot.  The state and the occurrence rows are unspecified afterwards.
+        top_k / min_p: per request (scalars broadcast), as `generate_sample`."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1079,7 +1146,8 @@ class Runtime:
         opt.prompt_tokens, opt.prompt_offsets, opt.max_new = _ptr(ptok, _u32p), _ptr(poff, _u32p), _ptr(mn, _u32p)
         opt.stop_tokens, opt.stop_offsets = _ptr(ids, _u32p), _ptr(soff, _u32p)
         keep = []
-        if temperature is not None or top_p is not None or seed is not None or occurrence is not None:
+        if (temperature is not None or top_p is not None or seed is not None or occurrence is not None or top_k is not None
+                or min_p is not None):
             t = _per_row(1.0 if temperature is None else temperature, R, np.float32)
             p = _per_row(0.5 if top_p is None else top_p, R, np.float32)
             sd = np.arange(R, dtype=np.uint32) if seed is None else _per_row(seed, R, np.uint32)
@@ -1089,6 +1157,11 @@ class Runtime:
             ap, af, g = _per_row(presence, R, np.float32), _per_row(frequency, R, np.float32), _per_row(decay, R, np.float32)
             keep += [ap, af, g]
             opt.presence, opt.frequency, opt.decay, opt.occ = _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h
+        tk, mp = _filters(top_k, min_p, R, keep)
+        if tk is not None:
+            opt.top_k = tk
+        if mp is not None:
+            opt.min_p = mp
         if init_state is not None:
             opt.init_state = init_state.h
         opt.poll_steps = poll_steps
