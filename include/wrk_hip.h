@@ -471,6 +471,30 @@ typedef struct wrk_queue_result {
 int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
                               const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode);
 
+/* A state pool under the queue: sessions across calls, and several requests from one prefix.  `states` holds num_entries states, entry k at
+ * float offset k * L * (S+2) * D in wrk_v7_state_read's layout (what init_state holds), so wrk_buf_copy / wrk_buf_read / wrk_buf_write
+ * with that offset move entries to and from snapshots and the host.  start / save: host u32 [num_requests], WRK_QUEUE_NO_ENTRY for none;
+ * either array may be NULL (all none).  Request r with start[r] = k begins from a copy of entry k (at step 0 or at a refill), one with
+ * none as wrk_v7_generate_queue's: from zeros or init_state.  When request r ends with reason 1 or 2 and save[r] = k, entry k receives
+ * the slot's state in the step that ends it, on the device: the state has consumed the prompt and y_0 .. y_{j-1}, the last reply token
+ * y_j is not fed -- what wrk_v7_generate_stop freezes for a sequence that ends there.  Reasons 3 and 0 write nothing: the entry keeps its
+ * bits.  saved (host u32 [num_requests], may be NULL): 1 iff the entry was written.  start[r] == save[r] (a session in place) and any
+ * number of requests reading an entry that nobody saves are allowed.  WRK_E_ARG before any launch, besides wrk_v7_generate_queue's: a NULL
+ * pool or `states`, an index >= num_entries, a buffer whose size is not num_entries states or of another context, `states` the same
+ * buffer as init_state, two requests saving to one entry, a request reading an entry that another request of the call saves to.
+ * WRK_E_UNSUPPORTED: (S+2) * D not a multiple of 4.  The pool's address and entry count are data of the step program: one cached
+ * program serves any pool, and pool programs never share a program with wrk_v7_generate_queue's.  Occurrence rows are reset at every
+ * request start, as without a pool. */
+#define WRK_QUEUE_NO_ENTRY 0xFFFFFFFFu
+typedef struct wrk_queue_pool {
+    wrk_buf *states;
+    uint32_t num_entries;
+    const uint32_t *start, *save;
+    uint32_t *saved;
+} wrk_queue_pool;
+int32_t wrk_v7_generate_queue_pool(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
+                                   const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_pool* pool);
+
 /* ---------------------------------------------------------------- RWKV-6 (v6::Model, src/runtime/v6.rs)
  * Same chunk semantics, state layout ([D, S+2, B] per layer: v6.rs:150-214 == v7) and entry points as the V7
  * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph. */
@@ -536,6 +560,9 @@ int32_t wrk_v6_generate_stop(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* st
 /* as wrk_v7_generate_queue */
 int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
                               const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode);
+/* as wrk_v7_generate_queue_pool */
+int32_t wrk_v6_generate_queue_pool(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
+                                   const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_pool* pool);
 
 #ifdef __cplusplus
 }

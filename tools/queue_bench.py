@@ -15,6 +15,18 @@ The legs alternate; medians of the wall time of whole calls (a, b) and of the HI
 
     python tools/queue_bench.py [--batches 16,32] [--reps 5] [--steps 64]
 
+--pool measures the state pool under the queue instead:
+
+  (a) the per-step cost of a pool program whose requests never end (one request per slot, each in place on its own entry) next to the
+      plain queue program's, same B, alternating.  The plain program's launch list is what it was before the pool existed; the figure
+      of the commit before it comes from running this tool without --pool there ("queue_never_ending_ms_per_step").
+  (b) `--turns` turns of R = 8 * B conversations.  Pool side: one generate_queue call per turn, every conversation in place on its own
+      entry (turn 0 starts cold).  The host way: per wave of B conversations state_write x B, the prompt intake (both intakes timed, the
+      faster one is the baseline), generate_stop for the wave's longest reply, state_read x B -- entry points this feature does not touch.
+      As in the waves above, a wave stops nothing early, so the states it reads back are not the ones a caller wants: it is timed only.
+
+    python tools/queue_bench.py --pool [--batches 1,16,32] [--turn-batches 16,32] [--turns 4] [--reps 3] [--steps 64]
+
 Prints one JSON object.
 """
 import argparse
@@ -32,6 +44,94 @@ sys.path.insert(0, os.path.join(ROOT, "web-rwkv-gguf_amd"))
 import bench  # noqa: E402  (the bench's model writer; bench.py itself is not changed)
 
 
+def pool_bench(args, wrk, ctx, data, skw):
+    out = {"model": f"RWKV-7 {args.model} Q4_K_M (synthetic)", "prompt_tokens": args.prompt, "turns": args.turns,
+           "reply_lengths": "uniform [32, 256], seed 7 + turn", "reps": args.reps, **skw,
+           "host_way_note": "state_write x B, prompt intake, generate_stop for the wave's longest reply, state_read x B per wave; timed only",
+           "per_step": [], "sessions": []}
+    med = lambda runs: float(np.median(runs))                       # noqa: E731
+    for B in [int(b) for b in args.batches.split(",") if b]:       # (a)
+        rt = wrk.Runtime(ctx, wrk.GgufReader(data), num_batch=B)
+        V = rt.info.num_vocab
+        pool = wrk.StatePool(ctx, rt, B)
+        own = list(range(B))
+        reqs = [[(17 + 101 * b) % (V - 1)] for b in range(B)]
+        kw = dict(max_new=args.steps, max_steps=args.steps, poll_steps=0xffffffff, **skw)
+
+        def step_ms(**pk):
+            res, run = rt.generate_queue(reqs, **kw, **pk)
+            assert run == args.steps and [len(t) for t, *_ in res] == [args.steps] * B
+            return rt.last_queue_ms / args.steps
+        step_ms(), step_ms(pool=pool, start_state=own, save_state=own)          # capture and warm up
+        plain, pooled = [], []
+        for _ in range(args.reps):
+            plain.append(step_ms())
+            pooled.append(step_ms(pool=pool, start_state=own, save_state=own))
+        out["per_step"].append({"batch": B, "steps": args.steps, "queue_ms_per_step": round(med(plain), 5),
+                                "pool_queue_ms_per_step": round(med(pooled), 5),
+                                "pool_minus_queue_us": round((med(pooled) - med(plain)) * 1e3, 2),
+                                "queue_ms_per_step_all": [round(x, 5) for x in plain], "pool_queue_ms_per_step_all": [round(x, 5) for x in pooled]})
+        pool.close()
+        rt.close()
+    for B in [int(b) for b in args.turn_batches.split(",") if b]:   # (b)
+        rt = wrk.Runtime(ctx, wrk.GgufReader(data), num_batch=B)
+        V = rt.info.num_vocab
+        R, T = args.requests_per_slot * B, args.turns
+        lens = [np.random.default_rng(7 + t).integers(32, 257, R).tolist() for t in range(T)]
+        prompts = [[[(17 + 101 * r + 7 * i + 31 * t) % (V - 1) for i in range(args.prompt)] for r in range(R)] for t in range(T)]
+        useful = int(sum(sum(x) for x in lens))
+        pool = wrk.StatePool(ctx, rt, R)
+        own = list(range(R))
+        snaps = [pool.get(r) for r in range(R)]                     # the host way's sessions: one zero snapshot per conversation
+
+        def pool_turns():
+            t0 = time.perf_counter()
+            for t in range(T):
+                res, _ = rt.generate_queue(prompts[t], max_new=lens[t], pool=pool, start_state=own if t else None, save_state=own, **skw)
+                assert [len(x) for x, *_ in res] == lens[t] and all(rt.last_queue_saved)
+            return (time.perf_counter() - t0) * 1e3
+
+        def host_turns(intake):
+            t0 = time.perf_counter()
+            for t in range(T):
+                for w in range(0, R, B):
+                    wave = prompts[t][w:w + B]
+                    for b in range(B):
+                        rt.state_write(snaps[w + b], b)
+                    if intake == "infer" and args.prompt > 1:
+                        inp = wrk.RnnInput([p[:-1] for p in wave], 256)
+                        while sum(inp.remaining(b) for b in range(B)) > 0:
+                            rt.infer(inp)
+                    else:
+                        for i in range(args.prompt - 1):
+                            rt.generate_sample([p[i] for p in wave], 1, **skw)
+                    n = max(lens[t][w:w + B])
+                    tok, _ = rt.generate_stop([p[-1] for p in wave], n, [], **skw)
+                    assert tok.shape == (n, B)
+                    for b in range(B):                              # into the conversation's own snapshot: no allocation in the loop
+                        ctx.check(wrk.hip.wrk_v7_state_read(ctx.h, rt.state, b, snaps[w + b].h))
+            return (time.perf_counter() - t0) * 1e3
+        rt.generate_queue(prompts[0][:B], max_new=4, pool=pool, save_state=own[:B], **skw)     # capture and warm up
+        rt.generate_sample([p[0] for p in prompts[0][:B]], 1, **skw)
+        rt.generate_stop([p[0] for p in prompts[0][:B]], 4, [], **skw)
+        rt.infer(wrk.RnnInput([p[:-1] for p in prompts[0][:B]], 256))
+        pa, hs, hi = [], [], []
+        for _ in range(args.reps):
+            pa.append(pool_turns())
+            hs.append(host_turns("steps"))
+            hi.append(host_turns("infer"))
+        pm, hsm, him = med(pa), med(hs), med(hi)
+        hm, intake = (hsm, "one-step generate_sample calls") if hsm <= him else (him, "Runtime.infer of the first n - 1 prompt tokens")
+        out["sessions"].append({"batch": B, "conversations": R, "turns": T, "reply_tokens": useful,
+                                "pool_ms": round(pm, 2), "pool_reply_tokens_per_s": round(useful / pm * 1e3, 1),
+                                "host_ms": round(hm, 2), "host_reply_tokens_per_s": round(useful / hm * 1e3, 1), "host_prompt_intake": intake,
+                                "pool_ms_all": [round(x, 2) for x in pa], "host_steps_ms_all": [round(x, 2) for x in hs],
+                                "host_infer_ms_all": [round(x, 2) for x in hi]})
+        pool.close()
+        rt.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -40,13 +140,20 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--prompt", type=int, default=8)
     ap.add_argument("--requests-per-slot", type=int, default=8)
+    ap.add_argument("--pool", action="store_true", help="the state-pool legs (DESIGN.md §7g) in the place of the queue's")
+    ap.add_argument("--turns", type=int, default=4)
+    ap.add_argument("--turn-batches", default="16,32")
     args = ap.parse_args()
     import wrk
 
-    batches = [int(b) for b in args.batches.split(",")]
+    batches = [int(b) for b in args.batches.split(",") if b]
     ctx = wrk.Context(0)
     data = bench.make_model_gguf(args.model, seed=42)
     skw = dict(temperature=1.0, top_p=0.9)
+    if args.pool:
+        print(json.dumps(pool_bench(args, wrk, ctx, data, skw)))
+        ctx.close()
+        return
     out = {"model": f"RWKV-7 {args.model} Q4_K_M (synthetic)", "prompt_tokens": args.prompt, "reply_lengths": "uniform [32, 256], seed 7",
            "reps": args.reps, **skw,
            "waves_note": "a wave resets no state and gives no per-request max_new: it runs the longest reply of the wave, the host cuts the rest",

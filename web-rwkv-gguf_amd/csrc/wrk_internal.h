@@ -255,6 +255,26 @@ void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint3
 // occurrence rows: count = 0, present bit cleared, banned bit kept (v: vocabulary).  Workgroups of the other slots return at once
 struct QueueGeom { float* state; uint32_t layers, num_batch, b0, v; size_t slot; };
 void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t b, int num_cu);
+// A state pool under the queue: P states in wrk_v7_state_read's layout in one device buffer; request r may start from a
+// copy of entry start[r] and has its end state written to entry save[r] in the step that ends it.  QUEUE_NO_ENTRY: none.
+// QueueStateCtl: the pool's pointer and entry count are data (one captured program serves any pool), next to the length of the step's
+// turnover list.  QueueTurn: one slot that ended in the step -- `save` the entry its state goes to, `started` / `start` as started[slot]
+// and the entry the slot's next request begins from
+static constexpr uint32_t QUEUE_NO_ENTRY = 0xFFFFFFFFu;
+struct QueueStateCtl { float* states; uint32_t num_entries, turn_count; };
+struct QueueTurn { uint32_t slot, save, started, start; };
+struct QueueStateBufs {
+    const uint32_t *start, *save;   // [R] next to the request table (QueueReq's layout does not move)
+    QueueStateCtl* sctl;
+    QueueTurn* turn;                // [B]: written by advance_queue_pool at position (ended slots before this one), no atomics
+};
+// advance_queue for pool programs: the same body, and the step's turnover list
+void advance_queue_pool(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q,
+                        const QueueStateBufs& p, uint32_t b);
+// queue_reset for pool programs: a (layers x slices) grid that does not grow with b loops over the turnover list -- per 16-byte element
+// load the slot, store it to the save entry, then store the start entry / init_state / zero to the slot, in one thread -- and the
+// occurrence rows as queue_reset.  g.slot % 4 == 0 and 16-byte aligned bases only (the callers check)
+void queue_turnover(hipStream_t s, const QueueGeom& g, const QueueBufs& q, const QueueStateBufs& p, uint32_t b, int num_cu);
 // as occurrence_update with ntok == 1, for the rows whose draw of this step is a reply token (slots[r].phase == QUEUE_REPLY)
 void occurrence_update_queue(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const QueueSlot* slots);
 

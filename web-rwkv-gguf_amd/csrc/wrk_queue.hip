@@ -8,6 +8,9 @@
 //                   index from one next_request word), copies their parameters into the slot's rows, and moves the step counter last
 //   queue_reset     grid (layer x slice, slot): every workgroup reads started[b] and leaves when it is 0; else zero fill / init_state
 //                   copy of the slot, and a second small grid for the slot's occurrence row when the program is penalised
+//   advance_queue_pool, queue_turnover   their places in the programs of a call with a state pool: the same advance body
+//                   also lists the slots that ended; one (layer x slice) grid, whatever B, saves each listed slot's state to its
+//                   request's pool entry and then fills the slot from the next request's entry, init_state or zeros
 //
 // started[b] is written by EVERY advance_queue launch for every slot, so the flag a reset launch reads was written by the launch in front
 // of it in the same stream; nothing has to clear it.  Plain vector stores only; no atomics; no kernel waits on another.
@@ -20,10 +23,12 @@ static constexpr uint32_t QUEUE_THREADS = 256;
 static constexpr uint32_t QUEUE_CHUNK = QUEUE_THREADS * 4;     // floats a workgroup moves per pass (16 bytes per thread)
 static constexpr uint32_t QUEUE_WAVES = QUEUE_THREADS / 64;
 
-// slots are owned by the threads of ONE workgroup (B <= 256, as advance_stop)
-__global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
-                                                                      uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
-                                                                      const QueueBufs Q, uint32_t b) {
+// slots are owned by the threads of ONE workgroup (B <= 256, as advance_stop).  POOL (advance_queue_pool_kernel): the slots that ended
+// also go into the step's turnover list, at the position the scan below gives them
+template <bool POOL>
+__device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                   uint32_t* __restrict__ history, uint32_t* __restrict__ counter, const QueueBufs& Q,
+                                                   const QueueStateBufs& P, uint32_t b) {
     __shared__ uint32_t wave_ended[QUEUE_WAVES];
     const uint32_t step = *counter;
     const uint32_t next = Q.ctl->next_request, live = Q.ctl->live, num_requests = Q.ctl->num_requests;
@@ -64,8 +69,10 @@ __global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_kernel(const uint
     }
     if (i < b) {
         uint32_t started = 0;
+        QueueTurn turn{i, QUEUE_NO_ENTRY, 0u, QUEUE_NO_ENTRY};
         if (ended) {
             const uint32_t r = next + before + rank;
+            if (POOL) turn.save = P.save[s.req];
             if (r < num_requests) {
                 const QueueReq* q = Q.reqs + r;
                 s = QueueSlot{r, 0u, 0u, q->prompt_len == 1 ? QUEUE_REPLY : QUEUE_PROMPT};
@@ -76,17 +83,32 @@ __global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_kernel(const uint
                 if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
                 Q.log[r] = QueueLog{0u, 3u, i, step + 1};
                 started = 1;
+                if (POOL) { turn.started = 1; turn.start = P.start[r]; }
             } else {
                 s.phase = QUEUE_IDLE;
             }
+            if (POOL) P.turn[before + rank] = turn;
         }
         Q.slots[i] = s;
         Q.started[i] = started;
     }
     if (i == 0) {
         if (total) { Q.ctl->next_request = next + total; Q.ctl->live = live - total; }
+        if (POOL) P.sctl->turn_count = total;
         *counter = step + 1;
     }
+}
+
+__global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                                      uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
+                                                                      const QueueBufs Q, uint32_t b) {
+    advance_queue_body<false>(drawn, tokens, history, counter, Q, QueueStateBufs{}, b);
+}
+
+__global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_pool_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                                           uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
+                                                                           const QueueBufs Q, const QueueStateBufs P, uint32_t b) {
+    advance_queue_body<true>(drawn, tokens, history, counter, Q, P, b);
 }
 
 struct QueueResetArgs {
@@ -110,6 +132,39 @@ __global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_state_kernel(const 
             *(f32x4*)(dst + i) = src ? *(const f32x4*)(src + i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     } else {
         for (size_t i = (size_t)part * QUEUE_THREADS + threadIdx.x; i < n; i += (size_t)A.slices * QUEUE_THREADS) dst[i] = src ? src[i] : 0.0f;
+    }
+}
+
+// Pool programs: queue_reset_state_kernel's place.  Workgroup (layer, slice) walks the step's turnover list; a thread moves the same
+// 16-byte elements of every listed slot, and for one element loads the slot, stores it to the save entry and only then stores the slot's
+// new value, so a slot that ends and restarts in one step is saved before it is overwritten with no ordering between workgroups.  The
+// entries read and the entries written in one step are disjoint (host validation), and a slot is listed once
+struct QueueTurnArgs {
+    float* state;               // [L][num_batch][slot] f32
+    const QueueStateCtl* sctl;
+    const QueueTurn* turn;
+    const QueueCtl* ctl;
+    uint32_t layers, slices, num_batch, b0;
+    size_t slot;                // (S + 2) * D, a multiple of 4
+};
+
+__global__ void __launch_bounds__(QUEUE_THREADS) queue_turnover_kernel(const QueueTurnArgs A) {
+    const QueueStateCtl sc = *A.sctl;
+    if (sc.turn_count == 0) return;
+    const uint32_t l = blockIdx.x / A.slices, part = blockIdx.x - l * A.slices;
+    const float* init = A.ctl->init_state;
+    const size_t n = A.slot, entry = (size_t)A.layers * A.slot;
+    for (uint32_t t = 0; t < sc.turn_count; ++t) {
+        const QueueTurn e = A.turn[t];
+        float* cur = A.state + ((size_t)l * A.num_batch + A.b0 + e.slot) * A.slot;
+        float* save = e.save != QUEUE_NO_ENTRY ? sc.states + (size_t)e.save * entry + (size_t)l * A.slot : nullptr;
+        const float* src = e.start != QUEUE_NO_ENTRY ? sc.states + (size_t)e.start * entry + (size_t)l * A.slot
+                                                     : (init ? init + (size_t)l * A.slot : nullptr);
+        if (!save && !e.started) continue;
+        for (size_t i = (size_t)part * QUEUE_CHUNK + threadIdx.x * 4; i < n; i += (size_t)A.slices * QUEUE_CHUNK) {
+            if (save) *(f32x4*)(save + i) = *(const f32x4*)(cur + i);
+            if (e.started) *(f32x4*)(cur + i) = src ? *(const f32x4*)(src + i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
     }
 }
 
@@ -141,23 +196,45 @@ void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint3
     advance_queue_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, b);
 }
 
+// slices of a layer's slot: layers * slices workgroups come to about two per CU, so that one starting request's fill (13 MB at the
+// 1.5B shape) runs on the whole chip, and no slice is smaller than one pass
+static uint32_t queue_slices(const QueueGeom& g, uint32_t per_pass, int num_cu) {
+    const uint32_t max_slices = (uint32_t)((g.slot + per_pass - 1) / per_pass);
+    const uint32_t want = (2u * (uint32_t)num_cu + g.layers - 1) / g.layers;
+    return want < 1 ? 1 : (want > max_slices ? max_slices : want);
+}
+
+static void queue_reset_occurrence(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t b) {
+    if (!q.pen_par || g.v == 0) return;
+    const dim3 grid((g.v + QUEUE_CHUNK - 1) / QUEUE_CHUNK, b);
+    if (g.v % 4 == 0) queue_reset_occurrence_kernel<true><<<grid, QUEUE_THREADS, 0, s>>>(g.v, q.pen_par, q.started);
+    else queue_reset_occurrence_kernel<false><<<grid, QUEUE_THREADS, 0, s>>>(g.v, q.pen_par, q.started);
+}
+
 void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t b, int num_cu) {
     if (b == 0) return;
     QueueResetArgs A{};
     A.state = g.state; A.started = q.started; A.ctl = q.ctl;
     A.layers = g.layers; A.num_batch = g.num_batch; A.b0 = g.b0; A.slot = g.slot;
     A.vec = g.slot % 4 == 0;
-    // slices of a layer's slot: layers * slices workgroups come to about two per CU, so that one starting request's fill (13 MB at the
-    // 1.5B shape) runs on the whole chip, and no slice is smaller than one pass
-    const uint32_t per_pass = A.vec ? QUEUE_CHUNK : QUEUE_THREADS;
-    const uint32_t max_slices = (uint32_t)((g.slot + per_pass - 1) / per_pass);
-    const uint32_t want = (2u * (uint32_t)num_cu + g.layers - 1) / g.layers;
-    A.slices = want < 1 ? 1 : (want > max_slices ? max_slices : want);
+    A.slices = queue_slices(g, A.vec ? QUEUE_CHUNK : QUEUE_THREADS, num_cu);
     queue_reset_state_kernel<<<dim3(A.layers * A.slices, b), QUEUE_THREADS, 0, s>>>(A);
-    if (!q.pen_par || g.v == 0) return;
-    const dim3 grid((g.v + QUEUE_CHUNK - 1) / QUEUE_CHUNK, b);
-    if (g.v % 4 == 0) queue_reset_occurrence_kernel<true><<<grid, QUEUE_THREADS, 0, s>>>(g.v, q.pen_par, q.started);
-    else queue_reset_occurrence_kernel<false><<<grid, QUEUE_THREADS, 0, s>>>(g.v, q.pen_par, q.started);
+    queue_reset_occurrence(s, g, q, b);
+}
+
+void advance_queue_pool(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q,
+                        const QueueStateBufs& p, uint32_t b) {
+    advance_queue_pool_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, p, b);
+}
+
+void queue_turnover(hipStream_t s, const QueueGeom& g, const QueueBufs& q, const QueueStateBufs& p, uint32_t b, int num_cu) {
+    if (b == 0) return;
+    QueueTurnArgs A{};
+    A.state = g.state; A.sctl = p.sctl; A.turn = p.turn; A.ctl = q.ctl;
+    A.layers = g.layers; A.num_batch = g.num_batch; A.b0 = g.b0; A.slot = g.slot;
+    A.slices = queue_slices(g, QUEUE_CHUNK, num_cu);
+    queue_turnover_kernel<<<A.layers * A.slices, QUEUE_THREADS, 0, s>>>(A);
+    queue_reset_occurrence(s, g, q, b);
 }
 
 }  // namespace wrk

@@ -117,6 +117,12 @@ struct wrk_frame_common {
     uint32_t queue_slot_cap = 0, queue_req_cap = 0;
     size_t queue_pool_cap = 0;
     uint32_t* queue_live() const { return &queue_ctl->live; }
+    // a queue call with a state pool, allocated by the first such call only and written before every call: the pool's
+    // control words, the turnover list [turn cap], the start and save entries of the requests [2][index cap]
+    wrk::QueueStateCtl* queue_state_ctl = nullptr;
+    wrk::QueueTurn* queue_turn = nullptr;
+    uint32_t* queue_entries = nullptr;
+    uint32_t queue_turn_cap = 0, queue_entry_cap = 0;
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
     uint32_t live_host_cap = 0;
     std::vector<hipEvent_t> poll_events;        // [2 blocks][lanes]
@@ -138,6 +144,7 @@ struct wrk_frame_common {
     int32_t ensure_penalty(uint32_t n, uint32_t num_vocab);
     int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
     int32_t ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens);
+    int32_t ensure_queue_states(uint32_t slots, uint32_t requests);
     int32_t ensure_poll(uint32_t lanes);        // lane 0's frame: pinned live counts and events of the polled loop
     void release_common();          // destroy paths: programs, scratch and every buffer above
 };
@@ -175,7 +182,8 @@ int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, co
 // pen_par, which then count the drawn tokens (wrk_penalty.hip) -- and advance tokens / history / counter
 // stop: the step belongs to a stop program (wrk_enqueue_stop_tail instead of advance_tokens), or with `queue` to a queue program
 // (wrk_enqueue_queue_tail).  filtered (with `sampled`): the filtered sampler on the frame's filter_par rows
-struct wrk_stop_step { const wrk_v7_state* st; uint32_t b0; bool queue = false; };
+// pool (with queue): a queue program of a call with a state pool (wrk_enqueue_queue_pool_tail)
+struct wrk_stop_step { const wrk_v7_state* st; uint32_t b0; bool queue = false; bool pool = false; };
 int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
                          const wrk_stop_step* stop = nullptr, bool filtered = false);
 // tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
@@ -187,6 +195,10 @@ int32_t wrk_enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V,
 int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop,
                                bool filtered = false);
 
+// tail of a pool program's step: as wrk_enqueue_queue_tail with advance_queue_pool and queue_turnover, launch for launch
+int32_t wrk_enqueue_queue_pool_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
+                                    const wrk_stop_step& stop, bool filtered = false);
+
 // generate_queue: the options validated (WRK_E_ARG before any launch) into the request table, the prompt pool and the pick rows the slots
 // start with.  first_tokens [B]: p_0 of the requests dispatched at step 0, a valid id for the slots that start idle
 struct wrk_queue_pack {
@@ -195,11 +207,20 @@ struct wrk_queue_pack {
     std::vector<wrk::QueueReq> reqs; std::vector<uint32_t> pool, first_tokens;
     std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
     const float* init_state = nullptr;
+    // wrk_queue_pool_check: the call has a state pool; start / save: [R] entries, QUEUE_NO_ENTRY for none
+    bool has_pool = false;
+    float* pool_states = nullptr;
+    uint32_t pool_entries = 0;
+    std::vector<uint32_t> start, save;
+    uint32_t* saved_out = nullptr;
 };
 int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
                         wrk_queue_result* out, wrk_queue_pack& pk);
+// after wrk_queue_check: the pool of wrk_v*_generate_queue_pool validated into pk (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch)
+int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, const wrk_queue_options* opt, const wrk_v7_state* st, wrk_queue_pack& pk);
 // after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): queue buffers of the
-// frame, the tables, the slots that start at step 0, live = R; then queue_reset of those slots on the submission stream
+// frame, the tables, the slots that start at step 0, live = R; then queue_reset of those slots on the submission stream (with a pool:
+// the pool's buffers and queue_turnover on the list of those slots)
 int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk_queue_pack& pk);
 // after the loop: the log and the history rows come back and the replies are cut out of them
 int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,

@@ -150,6 +150,13 @@ static void free_queue(wrk_frame_common& f) {
     f.queue_slot_cap = 0; f.queue_req_cap = 0; f.queue_pool_cap = 0;
 }
 
+static void free_queue_states(wrk_frame_common& f) {
+    void* bufs[] = {f.queue_state_ctl, f.queue_turn, f.queue_entries};
+    for (void* p : bufs) if (p) hipFree(p);
+    f.queue_state_ctl = nullptr; f.queue_turn = nullptr; f.queue_entries = nullptr;
+    f.queue_turn_cap = 0; f.queue_entry_cap = 0;
+}
+
 int32_t wrk_frame_common::ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens) {
     if (queue_ctl && slots <= queue_slot_cap && requests <= queue_req_cap && pool_tokens <= queue_pool_cap) return WRK_OK;
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -166,6 +173,20 @@ int32_t wrk_frame_common::ensure_queue(uint32_t slots, uint32_t requests, size_t
     WRK_HIP(ctx, hipMalloc((void**)&queue_log, (size_t)requests * sizeof(wrk::QueueLog)));
     WRK_HIP(ctx, hipMalloc((void**)&queue_pool, pool_tokens * 4));
     queue_slot_cap = slots; queue_req_cap = requests; queue_pool_cap = pool_tokens;
+    return WRK_OK;
+}
+
+int32_t wrk_frame_common::ensure_queue_states(uint32_t slots, uint32_t requests) {
+    if (queue_state_ctl && slots <= queue_turn_cap && requests <= queue_entry_cap) return WRK_OK;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (queue_state_ctl) drop_graphs();              // pool programs hold the old pointers; before the first allocation none exists
+    if (slots < queue_turn_cap) slots = queue_turn_cap;
+    if (requests < queue_entry_cap) requests = queue_entry_cap;
+    free_queue_states(*this);
+    WRK_HIP(ctx, hipMalloc((void**)&queue_state_ctl, sizeof(wrk::QueueStateCtl)));
+    WRK_HIP(ctx, hipMalloc((void**)&queue_turn, (size_t)slots * sizeof(wrk::QueueTurn)));
+    WRK_HIP(ctx, hipMalloc((void**)&queue_entries, (size_t)2 * requests * 4));
+    queue_turn_cap = slots; queue_entry_cap = requests;
     return WRK_OK;
 }
 
@@ -193,6 +214,7 @@ void wrk_frame_common::release_common() {
     score.release();
     free_stop(*this);
     free_queue(*this);
+    free_queue_states(*this);
     if (live_host) hipHostFree(live_host);
     live_host = nullptr; live_host_cap = 0;
     for (hipEvent_t e : poll_events) hipEventDestroy(e);
@@ -453,9 +475,53 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
     return WRK_OK;
 }
 
+int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, const wrk_queue_options* opt, const wrk_v7_state* st, wrk_queue_pack& pk) {
+    WRK_ARG(ctx, pool, "pool required");
+    WRK_ARG(ctx, pool->states, "%s", pool->start || pool->save ? "start / save entries without a pool buffer" : "the pool has no buffer");
+    const uint32_t R = pk.R, P = pool->num_entries;
+    const size_t slot = (size_t)(st->head_size + 2) * st->num_emb, one = (size_t)st->num_layer * slot * 4;
+    WRK_ARG(ctx, pool->states->ctx == ctx, "the pool belongs to another context");
+    WRK_ARG(ctx, P >= 1 && pool->states->bytes / one == P && pool->states->bytes % one == 0,
+            "the pool holds %zu bytes: not %u entries of %zu", pool->states->bytes, P, one);
+    WRK_ARG(ctx, !opt->init_state || (opt->init_state != pool->states && opt->init_state->ptr != pool->states->ptr),
+            "the pool and init_state are one buffer");
+    pk.start.assign(R, wrk::QUEUE_NO_ENTRY);
+    pk.save.assign(R, wrk::QUEUE_NO_ENTRY);
+    std::vector<uint32_t> saver(P, wrk::QUEUE_NO_ENTRY);       // the request that saves to the entry
+    for (uint32_t r = 0; r < R; ++r) {
+        if (pool->start) pk.start[r] = pool->start[r];
+        if (pool->save) pk.save[r] = pool->save[r];
+        WRK_ARG(ctx, pk.start[r] == wrk::QUEUE_NO_ENTRY || pk.start[r] < P, "request %u: start entry %u of %u", r, pk.start[r], P);
+        const uint32_t k = pk.save[r];
+        if (k == wrk::QUEUE_NO_ENTRY) continue;
+        WRK_ARG(ctx, k < P, "request %u: save entry %u of %u", r, k, P);
+        WRK_ARG(ctx, saver[k] == wrk::QUEUE_NO_ENTRY, "requests %u and %u both save to entry %u", saver[k], r, k);
+        saver[k] = r;
+    }
+    // a request may read the entry it saves to itself (the read at its start precedes the write at its end); another request's
+    // target would make the result depend on the schedule
+    for (uint32_t r = 0; r < R; ++r) {
+        const uint32_t k = pk.start[r];
+        WRK_ARG(ctx, k == wrk::QUEUE_NO_ENTRY || saver[k] == wrk::QUEUE_NO_ENTRY || saver[k] == r,
+                "request %u starts from entry %u, which request %u saves to", r, k, k == wrk::QUEUE_NO_ENTRY ? 0u : saver[k]);
+    }
+    if (slot % 4 != 0) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "a state pool needs (S + 2) * D = %zu to be a multiple of 4", slot);
+    if ((((uintptr_t)pool->states->ptr) | ((uintptr_t)st->data) | ((uintptr_t)pk.init_state)) & 15u)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "a state pool needs 16-byte aligned state, pool and init_state buffers");
+    pk.has_pool = true;
+    pk.pool_states = (float*)pool->states->ptr;
+    pk.pool_entries = P;
+    pk.saved_out = pool->saved;
+    return WRK_OK;
+}
+
 static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, bool sampled, bool penalized, bool filtered) {
     return wrk::QueueBufs{f.queue_slots, f.queue_reqs, f.queue_pool, f.queue_log, f.queue_ctl, f.queue_started,
                           sampled ? f.sample_par : nullptr, penalized ? f.pen_par : nullptr, filtered ? f.filter_par : nullptr};
+}
+
+static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f) {
+    return wrk::QueueStateBufs{f.queue_entries, f.queue_entries + f.queue_entry_cap, f.queue_state_ctl, f.queue_turn};
 }
 
 static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V) {
@@ -465,6 +531,7 @@ static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V
 int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk_queue_pack& pk) {
     wrk_ctx* ctx = f.ctx;
     int32_t rc = f.ensure_queue(B, pk.R, pk.pool.size());
+    if (rc == WRK_OK && pk.has_pool) rc = f.ensure_queue_states(B, pk.R);
     if (rc != WRK_OK) return rc;
     const uint32_t nstart = B < pk.R ? B : pk.R;
     std::vector<wrk::QueueSlot> slots(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
@@ -482,9 +549,22 @@ int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t 
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_reqs, pk.reqs.data(), (size_t)pk.R * sizeof(wrk::QueueReq));
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_pool, pk.pool.data(), pk.pool.size() * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_ctl, &ctl, sizeof ctl);
+    if (rc == WRK_OK && pk.has_pool) {
+        // the turnover list of "step -1": the slots that start at step 0, nothing to save
+        std::vector<wrk::QueueTurn> turn(nstart);
+        for (uint32_t b = 0; b < nstart; ++b) turn[b] = wrk::QueueTurn{b, wrk::QUEUE_NO_ENTRY, 1u, pk.start[b]};
+        const wrk::QueueStateCtl sctl{pk.pool_states, pk.pool_entries, nstart};
+        rc = wrk_buf_write_raw(ctx, f.queue_entries, pk.start.data(), (size_t)pk.R * 4);
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_entries + f.queue_entry_cap, pk.save.data(), (size_t)pk.R * 4);
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_turn, turn.data(), (size_t)nstart * sizeof(wrk::QueueTurn));
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_state_ctl, &sctl, sizeof sctl);
+    }
     if (rc != WRK_OK) return rc;
     // the slots that start a request at step 0 are reset as the step that ends a request resets its slot
-    wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.sampled, pk.penalized, pk.filtered), B, ctx->num_cu);
+    if (pk.has_pool)
+        wrk::queue_turnover(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.sampled, pk.penalized, pk.filtered), queue_state_bufs(f), B, ctx->num_cu);
+    else
+        wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.sampled, pk.penalized, pk.filtered), B, ctx->num_cu);
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
@@ -498,6 +578,20 @@ int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V
     const wrk::QueueBufs bufs = queue_bufs(f, sampled, penalized, filtered);
     wrk::advance_queue(q, io.argmax, io.tokens, f.history, io.counter, bufs, B);
     wrk::queue_reset(q, queue_geom(stop.st, stop.b0, V), bufs, B, f.ctx->num_cu);
+    return WRK_OK;
+}
+
+int32_t wrk_enqueue_queue_pool_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
+                                    const wrk_stop_step& stop, bool filtered) {
+    hipStream_t q = f.ctx->op_stream();
+    if (!f.queue_ctl || B > f.queue_slot_cap || stop.b0 != 0 || B > stop.st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+    if (!f.queue_state_ctl || B > f.queue_turn_cap || ((size_t)(stop.st->head_size + 2) * stop.st->num_emb) % 4 != 0)
+        return wrk_fail(f.ctx, WRK_E_ARG, "state pool buffers are not prepared");
+    if (penalized) wrk::occurrence_update_queue(q, V, B, f.pen_par, io.argmax, f.queue_slots);
+    const wrk::QueueBufs bufs = queue_bufs(f, sampled, penalized, filtered);
+    const wrk::QueueStateBufs sb = queue_state_bufs(f);
+    wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history, io.counter, bufs, sb, B);
+    wrk::queue_turnover(q, queue_geom(stop.st, stop.b0, V), bufs, sb, B, f.ctx->num_cu);
     return WRK_OK;
 }
 
@@ -519,6 +613,8 @@ int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, co
         if (g.length > q.max_new || g.slot >= B || (g.length && (size_t)g.start_step + q.prompt_len - 1 + g.length > steps_run))
             return wrk_fail(ctx, WRK_E_HIP, "request %u: inconsistent queue log (length %u slot %u start %u)", r, g.length, g.slot, g.start_step);
         out->lengths[r] = g.length; out->reasons[r] = g.reason; out->slots[r] = g.slot; out->start_steps[r] = g.start_step;
+        // the step that gave the request reason 1 or 2 also wrote its state to its entry (queue_turnover)
+        if (pk.saved_out) pk.saved_out[r] = pk.save[r] != wrk::QUEUE_NO_ENTRY && (g.reason == 1 || g.reason == 2);
         for (uint32_t j = 0; j < g.length; ++j) out->out_tokens[o + j] = hist[((size_t)g.start_step + q.prompt_len - 1 + j) * B + g.slot];
         o += opt->max_new[r];
     }
@@ -558,6 +654,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint
     else if ((filtered ? wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax)
                        : wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax)) != 0)
         return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    if (stop && stop->queue && stop->pool) return wrk_enqueue_queue_pool_tail(f, io, V, B, sampled, penalized, *stop, filtered);
     if (stop && stop->queue) return wrk_enqueue_queue_tail(f, io, V, B, sampled, penalized, *stop, filtered);
     if (stop) return wrk_enqueue_stop_tail(f, io, V, B, penalized, *stop);
     if (penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);

@@ -16,7 +16,7 @@ struct V6Scratch : wrk::FrameIo {
     float* ks_part; uint32_t* ks_cnt; size_t ks_part_cap; uint32_t ks_cnt_cap;     // K-sliced GEMM scratch (2 .. 32 sequences), see MatJob
 };
 
-struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64 | stop 128 | queue 256 | filtered 512)
+struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, keyed (state, sequences, mode | sampled 32 | penalised 64 | stop 128 | queue 256 | filtered 512 | state pool 1024)
     wrk_v6_model_desc d{};
     std::vector<wrk_v6_layer_desc> layers;
     V6Scratch s{};
@@ -700,15 +700,16 @@ int32_t wrk_v6_generate_stop(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, co
                        steps_run);
 }
 
-// generate_queue: as v6_generate's stop call, the queue tail in the stop tail's place
-int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
-                              const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+// generate_queue: as v6_generate's stop call, the queue tail in the stop tail's place (with a state pool: the pool tail)
+static int32_t v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                                 const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, bool has_pool, const wrk_queue_pool* pool) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     const uint32_t V = m->d.num_vocab;
     wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
     wrk_queue_pack pk;
     int32_t rc = wrk_queue_check(ctx, opt, st, B, V, mode_arg, out_arg ? &out : nullptr, pk);
+    if (rc == WRK_OK && has_pool) rc = wrk_queue_pool_check(ctx, pool, opt, st, pk);
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->d.emb_f16 != nullptr, m->d.num_emb, m->d.num_layer, V, pk.first_tokens.data(), B);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
@@ -719,7 +720,7 @@ int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, u
                                 pk.penalized ? pk.pen.data() : nullptr, pk.filtered ? pk.filt.data() : nullptr);
     if (rc == WRK_OK) rc = wrk_queue_prepare(*m, st, V, B, pk);
     if (rc != WRK_OK) return rc;
-    const wrk_stop_step ss{st, 0, true};
+    const wrk_stop_step ss{st, 0, true, pk.has_pool};
     const char* ng = getenv("WRK_NO_GRAPH");
     const bool eager = ng && ng[0] == '1';
     auto enqueue_step = [&]() -> int32_t {
@@ -732,7 +733,7 @@ int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, u
     };
     std::vector<wrk_lane> lane{{&m->s, m->history, 0, B, nullptr, m}};
     if (!eager) {
-        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pk.sampled ? 32u : 0u) | (pk.penalized ? 64u : 0u) | 256u | (pk.filtered ? 512u : 0u)},
+        rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | (pk.sampled ? 32u : 0u) | (pk.penalized ? 64u : 0u) | 256u | (pk.filtered ? 512u : 0u) | (pk.has_pool ? 1024u : 0u)},
                                 enqueue_step,
                                 &lane[0].prog);
         if (rc != WRK_OK) return rc;
@@ -742,6 +743,16 @@ int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, u
     rc = wrk_run_lanes(ctx, lane, {}, {}, B, V, pk.max_steps, enqueue_step, nullptr, nullptr, elapsed_ms, &run);
     if (rc != WRK_OK) return rc;
     return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
+}
+
+int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                              const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+    return v6_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, false, nullptr);
+}
+
+int32_t wrk_v6_generate_queue_pool(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                                   const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_pool* pool) {
+    return v6_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, true, pool);
 }
 
 }  // extern "C"

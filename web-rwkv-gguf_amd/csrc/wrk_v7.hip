@@ -620,13 +620,15 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
 // stop: a stop program's step (wrk_stop.hip) -- the fused greedy head keeps its arg-max and leaves the advance to the stop tail;
 // queue (with stop): a queue program's step (wrk_queue.hip), the queue tail in the stop tail's place
 // filtered (with sampled): the pick is the filtered sampler's (top-k / min-p rows of the frame)
+// pool (with queue): a pool program's step, the pool tail in the queue tail's place
 static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled,
-                                   bool penalized, bool stop = false, bool queue = false, bool filtered = false) {
+                                   bool penalized, bool stop = false, bool queue = false, bool filtered = false, bool pool = false) {
     int32_t rc;
-    const wrk_stop_step ss{st, b0, queue};
+    const wrk_stop_step ss{st, b0, queue, pool};
     if (mode == 1 && m->act_dtype == WRK_F16) {
         rc = m->enqueue_fused_decode(st, B, B, true, true, !sampled, !sampled && !stop, b0, true);
         if (!sampled && (!stop || rc != WRK_OK)) return rc;
+        if (!sampled && queue && pool) return wrk_enqueue_queue_pool_tail(*m, m->s, m->d.num_vocab, B, false, false, ss);
         if (!sampled && queue) return wrk_enqueue_queue_tail(*m, m->s, m->d.num_vocab, B, false, false, ss);
         if (!sampled) return wrk_enqueue_stop_tail(*m, m->s, m->d.num_vocab, B, false, ss);
     } else {
@@ -653,14 +655,16 @@ static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, c
     if (rc != WRK_OK || eager) return rc;
     // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo; sampled
     // steps have their own key bit, so greedy and sampled programs never alias, and so do penalised ones (bit 24, above every infer flag)
-    // and stop programs (bit 25), queue programs (bit 26) and programs whose pick is the filtered sampler (bit 27)
+    // and stop programs (bit 25), queue programs (bit 26), programs whose pick is the filtered sampler (bit 27) and the queue programs
+    // of calls with a state pool (bit 28)
+    const bool pool = queue && queue->has_pool;
     const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
                                                              (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u) | (pen ? 1u << 24 : 0u) |
-                                                             (stop ? 1u << 25 : 0u) | (queue ? 1u << 26 : 0u) | (filt ? 1u << 27 : 0u)};
+                                                             (stop ? 1u << 25 : 0u) | (queue ? 1u << 26 : 0u) | (filt ? 1u << 27 : 0u) | (pool ? 1u << 28 : 0u)};
     return wrk_cached_program(ctx, m->graphs, key,
                               [&] {
                                   return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr, stop || queue, queue != nullptr,
-                                                             filt != nullptr);
+                                                             filt != nullptr, pool);
                               },
                               prog_out);
 }
@@ -783,14 +787,16 @@ int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, co
 }
 
 // generate_queue: one lane, the frame's own; the loop is generate_stop's polled one with the queue's live count
-int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
-                              const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+// pool: the state pool of wrk_v7_generate_queue_pool (required when has_pool)
+static int32_t v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                                 const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, bool has_pool, const wrk_queue_pool* pool) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     const uint32_t V = m->d.num_vocab;
     wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
     wrk_queue_pack pk;
     int32_t rc = wrk_queue_check(ctx, opt, st, B, V, mode_arg, out_arg ? &out : nullptr, pk);
+    if (rc == WRK_OK && has_pool) rc = wrk_queue_pool_check(ctx, pool, opt, st, pk);
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->emb != nullptr, m->d.num_emb, m->d.num_layer, V, pk.first_tokens.data(), B);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
@@ -807,12 +813,22 @@ int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, u
     uint32_t steps_run = 0;
     const wrk_stop_run run{st, pk.poll_steps, nullptr, &steps_run, true};
     rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, pk.max_steps,
-                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, pk.sampled, pk.penalized, true, true, pk.filtered); }, nullptr, nullptr, elapsed_ms,
+                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, pk.sampled, pk.penalized, true, true, pk.filtered, pk.has_pool); }, nullptr, nullptr, elapsed_ms,
                        &run);
     if (rc != WRK_OK) return rc;
     rc = wrk_v7_engine_check(m->engine);
     if (rc != WRK_OK) return rc;
     return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
+}
+
+int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                              const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+    return v7_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, false, nullptr);
+}
+
+int32_t wrk_v7_generate_queue_pool(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                                   const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_pool* pool) {
+    return v7_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, true, pool);
 }
 
 }  // extern "C"

@@ -94,7 +94,13 @@ class QueueResult(C.Structure):
                 ("steps_run", _u32p)]
 
 
+class QueuePool(C.Structure):
+    """wrk_queue_pool: the state pool of wrk_v*_generate_queue_pool and the start / save entries [R] of the requests."""
+    _fields_ = [("states", _P), ("num_entries", C.c_uint32), ("start", _u32p), ("save", _u32p), ("saved", _u32p)]
+
+
 MAX_STOP_TOKENS = 16        # WRK_MAX_STOP_TOKENS
+QUEUE_NO_ENTRY = 0xFFFFFFFF     # WRK_QUEUE_NO_ENTRY
 _TP = C.POINTER(TensorDesc)
 
 # name -> (restype, argtypes); every symbol declared in include/*.h
@@ -193,6 +199,10 @@ HIP_SYMBOLS = {
                                          _f32p, C.c_uint32]),
     "wrk_v7_generate_queue": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32]),
     "wrk_v6_generate_queue": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32]),
+    "wrk_v7_generate_queue_pool": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
+                                               C.POINTER(QueuePool)]),
+    "wrk_v6_generate_queue_pool": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
+                                               C.POINTER(QueuePool)]),
 }
 RT_SYMBOLS = {
     "wrk_host_last_error": (C.c_char_p, []),
@@ -1112,7 +1122,7 @@ class Runtime:
 
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
-                       mode: int = 1, top_k=None, min_p=None):
+                       mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1121,7 +1131,12 @@ class Runtime:
         reply does not depend on when its request was scheduled.  Returns ([(tokens, reason, slot, start_step)] per request, steps_run):
         reason 1 stop token (part of the reply), 2 max_new, 3 cut by max_steps, 0 never dispatched.  max_steps defaults to the sum of
         prompt and max_new lengths, enough even for one slot.  The state and the occurrence rows are unspecified afterwards.
-        top_k / min_p: per request (scalars broadcast), as `generate_sample`."""
+        top_k / min_p: per request (scalars broadcast), as `generate_sample`.
+        pool, start_state, save_state: request r begins from a copy of entry start_state[r] of the `StatePool` (None: zeros / init_state)
+        and, ending with reason 1 or 2, leaves its final state -- the prompt and the reply but its last token consumed, what
+        `generate_stop` freezes -- in entry save_state[r] (None: nowhere).  Each is one value for all requests or a list; the same entry
+        for start and save continues a session in place.  `last_queue_saved[r]` tells whether request r's entry was written.  Two
+        requests may not save to one entry, nor one read an entry another saves to."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1171,8 +1186,24 @@ class Runtime:
         run, ms = C.c_uint32(), C.c_float()
         res = QueueResult(_ptr(lengths, _u32p), _ptr(reasons, _u32p), _ptr(slots, _u32p), _ptr(starts, _u32p), _ptr(out, _u32p),
                           C.pointer(run))
-        fn, mdl = (hip.wrk_v6_generate_queue, self.model6) if self.model6 else (hip.wrk_v7_generate_queue, self.model)
-        self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode))
+        if pool is None:
+            if start_state is not None or save_state is not None:
+                raise ValueError("start_state / save_state need a pool")
+            fn, mdl = (hip.wrk_v6_generate_queue, self.model6) if self.model6 else (hip.wrk_v7_generate_queue, self.model)
+            self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode))
+            self.last_queue_saved = None
+        else:
+            def entries(v):
+                if v is None or np.isscalar(v):
+                    v = [v] * R
+                if len(v) != R:
+                    raise ValueError(f"{len(v)} pool entries for {R} requests")
+                return _u32([QUEUE_NO_ENTRY if k is None else int(k) for k in v]) if R else np.zeros(1, np.uint32)
+            st, sv, saved = entries(start_state), entries(save_state), np.zeros(max(R, 1), np.uint32)
+            qp = QueuePool(pool.buf.h, pool.entries, _ptr(st, _u32p), _ptr(sv, _u32p), _ptr(saved, _u32p))
+            fn, mdl = (hip.wrk_v6_generate_queue_pool, self.model6) if self.model6 else (hip.wrk_v7_generate_queue_pool, self.model)
+            self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qp)))
+            self.last_queue_saved = [bool(x) for x in saved[:R]]
         self.last_queue_ms = ms.value
         off = np.concatenate([[0], np.cumsum(mn)]).astype(np.int64)
         return [(out[off[r]:off[r] + lengths[r]].copy(), int(reasons[r]), int(slots[r]), int(starts[r])) for r in range(R)], run.value
@@ -1205,3 +1236,39 @@ class Runtime:
         if self.h:
             rt.wrk_runtime_destroy(self.h)
             self.h = None
+
+
+class StatePool:
+    """The state pool of `Runtime.generate_queue(pool=...)`: `entries` states of `runtime`'s model in one device buffer, entry k in
+    `state_read`'s layout [L, S+2, D] f32 (multi-session serving keeps its snapshots in HBM, v7.rs:229-262).  Entries start as zeros."""
+
+    def __init__(self, ctx: Context, runtime: Runtime, entries: int):
+        L, D, S = runtime.info.num_layer, runtime.info.num_emb, runtime.info.num_emb // runtime.info.num_head
+        self.ctx, self.entries, self.shape, self.entry_bytes = ctx, entries, (L, S + 2, D), L * (S + 2) * D * 4
+        self.buf = Buffer(ctx, entries * self.entry_bytes, np.zeros(entries * L * (S + 2) * D, np.float32))
+
+    def _at(self, k: int) -> int:
+        if not 0 <= k < self.entries:
+            raise IndexError(f"entry {k} of {self.entries}")
+        return k * self.entry_bytes
+
+    def put(self, k: int, snapshot: Buffer):
+        """entry k <- a `state_read` snapshot (device to device)"""
+        self.ctx.check(hip.wrk_buf_copy(self.ctx.h, snapshot.h, 0, self.buf.h, self._at(k), self.entry_bytes))
+
+    def get(self, k: int) -> Buffer:
+        """a snapshot of entry k for `state_write` / `init_state` (device to device)"""
+        out = Buffer(self.ctx, self.entry_bytes)
+        self.ctx.check(hip.wrk_buf_copy(self.ctx.h, self.buf.h, self._at(k), out.h, 0, self.entry_bytes))
+        return out
+
+    def load(self, k: int, tensor: np.ndarray):
+        a = np.ascontiguousarray(tensor, dtype=np.float32)
+        assert a.shape == self.shape
+        self.buf.write(a, self._at(k))
+
+    def back(self, k: int) -> np.ndarray:
+        return self.buf.read(np.float32, self.entry_bytes // 4, self._at(k)).reshape(self.shape)
+
+    def close(self):
+        self.buf = None
