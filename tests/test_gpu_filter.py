@@ -419,3 +419,93 @@ def test_argument_errors_leave_the_model_usable(ctx):
     t, _ = rt.generate_sample([1, 2], 4, temperature=1.0, top_p=0.9, top_k=4, min_p=0.05)
     assert t.shape == (4, 2) and (t < V).all()
     rt.close()
+
+
+# ----------------------------------------------------------------------------- 7. every step kind has a program of its own
+KIND_PICKS = ("greedy", "sample", "sample+filter", "pen", "pen+filter")
+KIND_TAILS = ("plain", "stop", "queue", "pool")
+
+
+@pytest.mark.parametrize("v6", [False, True])
+def test_every_step_kind_replays_its_own_program(ctx, v6):
+    """The key bits of a step program come from one function of its kind (wrk_step_kind::key, DESIGN.md §1): one runtime walks all
+    {greedy, sampled, sampled + filtered, penalised, penalised + filtered} x {plain, stop, queue, queue + pool} in modes 0 and 1, every
+    call from zero state slots and empty occurrence rows, once in order and once in reverse.  A kind that replayed another kind's
+    program would draw by another pick or advance by another tail: the second result of every kind must equal its first bit for bit
+    (tokens, last logits, lengths, the queue's log).  Across tails: a stop set that never fires draws what the plain call draws, and
+    B one-token requests with max_new = steps draw what sequence b of the plain call draws from the same first token -- the identity
+    test_gpu_queue.py's replays rest on (slot b, sampler step j for reply token j, state and occurrence row reset at the start).
+    Programs stay cached between the passes, so two picks that shared a key would agree with themselves; the parameters separate them.
+    The filtered picks run top_k = 1 at temperature 50: their draw is the arg-max whatever the seed (test_top_k_one_is_the_argmax), the
+    plain sampler's at that temperature is not.  The penalised picks ban the first token that their unpenalised counterpart draws
+    (bans survive the queue's row reset), so a program without the penalise launch draws a banned token.  Hence: sampled + filtered
+    equals greedy, which sampled does not; penalised differs from sampled in the first draw; penalised + filtered differs from greedy
+    in the first draw and does not change with the seeds."""
+    B, steps = 2, 4
+    data, V = model("tiny", v6), vocab("tiny", v6)
+    rt = fresh(ctx, data, B)
+    occ = wrk.Occurrence(ctx, B, V)
+    pool = wrk.StatePool(ctx, rt, B)
+    first = [7, 100]
+    skw = dict(temperature=[0.9, 1.1], top_p=[0.95, 0.9], seed=[21, 22])
+    fkw = dict(skw, temperature=50.0, top_p=1.0, top_k=1)
+    pkw = dict(presence=0.4, frequency=0.3, decay=0.99)
+    picks = {"greedy": {}, "sample": skw, "sample+filter": fkw, "pen": dict(skw, **pkw), "pen+filter": dict(fkw, **pkw)}
+    banned_from = {"pen": "sample", "pen+filter": "greedy"}
+    unused = {}     # per (mode, pick): an id the plain call does not draw -- a stop set that never fires
+    drawn = {}      # per (mode, pick): the first token of every sequence in the plain call
+
+    def run(mode, pick_, tail, seed=None):
+        zero_states(rt, B)
+        for b in range(B):
+            occ.load(b)
+            if pick_ in banned_from:
+                occ.ban(b, [drawn[mode, banned_from[pick_]][b]])
+        kw = dict(picks[pick_], mode=mode)
+        if seed is not None:
+            kw["seed"] = seed
+        if pick_.startswith("pen"):
+            kw["occurrence"] = occ
+        if tail == "plain":
+            fn = rt.generate_greedy if pick_ == "greedy" else rt.generate_penalized if pick_.startswith("pen") else rt.generate_sample
+            pen = (kw.pop("occurrence"),) if pick_.startswith("pen") else ()
+            tok, _, logits = fn(first, steps, *pen, want_logits=True, **kw)
+            unused[mode, pick_] = next(i for i in range(V) if i not in set(tok.reshape(-1).tolist()))
+            drawn.setdefault((mode, pick_), tok[0].tolist())
+            return tok, logits.view(np.uint32)
+        if tail == "stop":
+            tok, lens, logits = rt.generate_stop(first, steps, [unused[mode, pick_]], want_logits=True, **kw)
+            return tok, lens, logits.view(np.uint32)
+        pk = dict(pool=pool, save_state=list(range(B))) if tail == "pool" else {}
+        res, ran = rt.generate_queue([[t] for t in first], max_new=steps, **kw, **pk)
+        saved = rt.last_queue_saved if tail == "pool" else []
+        return np.stack([t for t, *_ in res], axis=1), np.array([r[1:] for r in res]), np.array(saved), ran
+
+    kinds = [(p, t) for p in KIND_PICKS for t in KIND_TAILS]
+    try:
+        for mode in (0, 1):
+            once = {k: run(mode, *k) for k in kinds}
+            again = {k: run(mode, *k) for k in reversed(kinds)}
+            for k in kinds:
+                assert len(once[k]) == len(again[k])
+                for x, y in zip(once[k], again[k]):
+                    assert np.array_equal(x, y), (mode, k)
+            for p in KIND_PICKS:
+                plain = once[p, "plain"][0]
+                assert plain.shape == (steps, B)
+                tok, lens, _ = once[p, "stop"]
+                assert np.array_equal(tok, plain) and lens.tolist() == [steps] * B, (mode, p)
+                for t in ("queue", "pool"):
+                    tok, log, saved, _ = once[p, t]
+                    assert np.array_equal(tok, plain), (mode, p, t)
+                    assert log.tolist() == [[2, b, 0] for b in range(B)], (mode, p, t)       # ended by max_new, slot b, fed at step 0
+                    assert saved.tolist() == [True] * B * (t == "pool"), (mode, p)
+            tok = {p: once[p, "plain"][0] for p in KIND_PICKS}
+            assert np.array_equal(tok["sample+filter"], tok["greedy"]) and not np.array_equal(tok["sample"], tok["greedy"]), mode
+            assert all(tok["pen"][0, b] != tok["sample"][0, b] for b in range(B)), mode
+            assert all(tok["pen+filter"][0, b] != tok["greedy"][0, b] for b in range(B)), mode
+            assert np.array_equal(run(mode, "pen+filter", "plain", seed=[121, 122])[0], tok["pen+filter"]), mode
+    finally:
+        pool.close()
+        occ.close()
+        rt.close()

@@ -5,6 +5,7 @@
 #pragma once
 #include <atomic>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <tuple>
 #include <vector>
@@ -128,7 +129,8 @@ struct wrk_frame_common {
     std::vector<hipEvent_t> poll_events;        // [2 blocks][lanes]
     uint32_t wkv_nseq = 0;          // sequences of the job being enqueued (0: unknown): picks the WKV chunk kernel (wrk::time_mix_v7 / _v6)
 
-    // b: tokens (generate: sequences | first sequence << 16); mode: the runner's mode and flag bits; nh: header rows
+    // b: tokens (generate: sequences | first sequence << 16); mode: the runner's mode and flag bits, in a decode step's key ORed
+    // with wrk_step_kind::key(); nh: header rows
     // (the analogue of the reference's cached RnnJob per RnnInfo, runtime/mod.rs:110-209)
     struct GraphKey {
         const void* state; uint32_t b, mode, nh = 0;
@@ -138,6 +140,12 @@ struct wrk_frame_common {
 
     // the ensure_* reallocate after a stream sync and drop the captured programs, which hold the old pointers; never inside a capture
     void drop_graphs();
+    // the buffers an ensure_* reallocates together; bufs(g): their pointers, the one list regrow and release_common go through
+    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, NUM_GROUPS };
+    std::vector<void**> bufs(Group g);
+    // sync, drop the programs (`drop`), free the buffers and allocate them again; after a failure all of them are freed
+    // bytes: one size per buffer of bufs(g), in its order.  The caller sets its caps after WRK_OK: an error leaves them as they were
+    int32_t regrow(Group g, std::initializer_list<size_t> bytes, bool drop);
     int32_t ensure_history(size_t n);
     int32_t ensure_sample_params(uint32_t n);
     int32_t ensure_filter_params(uint32_t n);
@@ -159,56 +167,68 @@ int32_t wrk_cached_program(wrk_ctx* ctx, std::map<wrk_frame_common::GraphKey, wr
 int32_t wrk_job_upload(wrk_frame_common& f, wrk::FrameIo& io, void* input, const wrk_buf* emb, uint32_t D, const wrk_job_args& a, bool gather);
 int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t V, const wrk_job_args& a);
 
-// ------------------------------------------------------------------ generate_greedy / generate_sample / generate_penalized
-struct wrk_pick_args {      // the ABI's sampler (and with `penalized` penalty) arrays; generate_greedy passes none
-    const float *temperature, *top_p; const uint32_t* seed;
-    bool penalized = false;
+// ------------------------------------------------------------------ the decode loops (generate_greedy ... generate_queue)
+// What a step program of the decode loops is: how each sequence's next token is picked from head_o, and what follows the pick.
+// A filtered pick is a sampled one and a pool tail is a queue tail by construction; wrk_pick_pack sets `penalized` only with a sampled pick
+struct wrk_step_kind {
+    enum Pick : uint32_t { GREEDY, SAMPLED, FILTERED };         // arg-max / the sampler (wrk_sample.hip) on sample_par / the filtered sampler, also on filter_par
+    enum Tail : uint32_t { PLAIN, STOP, QUEUE, QUEUE_POOL };    // advance_tokens / wrk_stop.hip / wrk_queue.hip / the same with a state pool
+    Pick pick = GREEDY;
+    bool penalized = false;     // the pick is made on pen_o = head_o penalised with the occurrence rows of pen_par, which then count the draw (wrk_penalty.hip)
+    Tail tail = PLAIN;
+    bool sampled() const { return pick != GREEDY; }
+    bool filtered() const { return pick == FILTERED; }
+    bool queue() const { return tail == QUEUE || tail == QUEUE_POOL; }
+    bool pool() const { return tail == QUEUE_POOL; }
+    // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25, penalised 26, tail 27-28 -- above every flag of an
+    // infer job and of a runner's own (a runner ORs its mode and flags, all below bit 24, into the same word)
+    uint32_t key() const { return (uint32_t)pick << 24 | (uint32_t)penalized << 26 | (uint32_t)tail << 27; }
+};
+
+// the ABI's pick arrays, of wrk_generate_options / wrk_queue_options (wrk_pick_of) or of an entry point's own arguments.  need: what
+// the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
+struct wrk_pick_args {
+    const float *temperature = nullptr, *top_p = nullptr; const uint32_t* seed = nullptr;
     const float *presence = nullptr, *frequency = nullptr, *decay = nullptr; wrk_occurrence* occ = nullptr;
     const uint32_t* top_k = nullptr; const float* min_p = nullptr;      // either set: a filtered pick
+    enum Need { ANY, SAMPLER, TABLE } need = ANY;
 };
-struct wrk_pick_params {    // validated per-sequence rows; par / pen / filt: nullptr for the arg-max / without penalties / without filters
-    std::vector<wrk::SampleParam> par_rows; std::vector<wrk::PenaltyParam> pen_rows; std::vector<wrk::SampleFilter> filt_rows;
-    const wrk::SampleParam* par = nullptr; const wrk::PenaltyParam* pen = nullptr; const wrk::SampleFilter* filt = nullptr;
+template <class Options> wrk_pick_args wrk_pick_of(const Options& o) {
+    return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p};
+}
+struct wrk_pick_params {    // validated rows; empty: the arg-max / without penalties / without filters
+    std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
 };
-int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args* pick, uint32_t B, uint32_t V, wrk_pick_params& out);
+// The one validation of the pick arrays (WRK_E_ARG): all three sampler arrays or none (the arg-max); penalty arrays only with a table;
+// a table or a filter only with the sampler arrays.  Sets kind.pick / kind.penalized and packs `n` rows; penalty row r names slot r of
+// the table for r < slots (the table must have `slots`), slot 0 beyond: the queue keeps only the values of its request rows
+int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, uint32_t slots, uint32_t V, wrk_pick_params& out, wrk_step_kind& kind);
+// a stop-set CSR over n owners ("sequence", "request") validated into rows [n] (ids, count); both arrays NULL: all empty
+int32_t wrk_stop_sets(wrk_ctx* ctx, const uint32_t* tokens, const uint32_t* offsets, uint32_t n, uint32_t V, const char* owner,
+                      std::vector<wrk::StopParam>& rows);
 int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, uint32_t num_emb, uint32_t num_layer, uint32_t V,
                            const uint32_t* first_tokens, uint32_t B);
-// after the model's ensure_scratch: history / parameter buffers, then cursors, header rows, first tokens and parameters of sequences
-// [b0, b0 + B) and a zero step counter
+bool wrk_no_graph();        // WRK_NO_GRAPH=1: the decode loops enqueue every step instead of replaying a program
+// after the model's ensure_scratch: history / parameter buffers, then cursors, header rows, first_tokens [b0, b0 + B) and rows
+// [b0, b0 + B) of `rows` for sequences [b0, b0 + B), and a zero step counter
 int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps,
-                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen, const wrk::SampleFilter* filt = nullptr);
-// after the layers and the head: pick each sequence's next token from head_o -- the arg-max, or with `sampled` the sampler (wrk_sample.hip)
-// on the frame's parameters at step *counter; `penalized` (implies `sampled`): from pen_o = head_o penalised with the occurrence rows of
-// pen_par, which then count the drawn tokens (wrk_penalty.hip) -- and advance tokens / history / counter
-// stop: the step belongs to a stop program (wrk_enqueue_stop_tail instead of advance_tokens), or with `queue` to a queue program
-// (wrk_enqueue_queue_tail).  filtered (with `sampled`): the filtered sampler on the frame's filter_par rows
-// pool (with queue): a queue program of a call with a state pool (wrk_enqueue_queue_pool_tail)
-struct wrk_stop_step { const wrk_v7_state* st; uint32_t b0; bool queue = false; bool pool = false; };
-int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
-                         const wrk_stop_step* stop = nullptr, bool filtered = false);
-// tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
-// (`penalized`), advance_stop, stop_snapshot of sequences [b0, b0 + B) of `st`
-int32_t wrk_enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool penalized, const wrk_stop_step& stop);
-
-// tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
-// token (`penalized`), advance_queue, queue_reset of slots [b0, b0 + B) of `st`
-int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop,
-                               bool filtered = false);
-
-// tail of a pool program's step: as wrk_enqueue_queue_tail with advance_queue_pool and queue_turnover, launch for launch
-int32_t wrk_enqueue_queue_pool_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
-                                    const wrk_stop_step& stop, bool filtered = false);
+                           const wrk_pick_params& rows);
+// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the penalise launch (penalised), the arg-max
+// or sampler launch on the frame's parameters at step *counter -- neither with `argmax_done`: the head launch has left the arg-max in
+// io.argmax (RWKV-7's fused greedy head) -- then the tail: the occurrence update that belongs to it (penalised), its advance of tokens /
+// history / counter, and stop_snapshot / queue_reset / queue_turnover
+int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0,
+                         bool argmax_done);
 
 // generate_queue: the options validated (WRK_E_ARG before any launch) into the request table, the prompt pool and the pick rows the slots
 // start with.  first_tokens [B]: p_0 of the requests dispatched at step 0, a valid id for the slots that start idle
 struct wrk_queue_pack {
     uint32_t R = 0, max_steps = 0, poll_steps = 0;
-    bool sampled = false, penalized = false, filtered = false;
+    wrk_step_kind kind{wrk_step_kind::GREEDY, false, wrk_step_kind::QUEUE};       // wrk_queue_pool_check: QUEUE_POOL
     std::vector<wrk::QueueReq> reqs; std::vector<uint32_t> pool, first_tokens;
-    std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
+    wrk_pick_params rows;       // [B]
     const float* init_state = nullptr;
-    // wrk_queue_pool_check: the call has a state pool; start / save: [R] entries, QUEUE_NO_ENTRY for none
-    bool has_pool = false;
+    // with a state pool; start / save: [R] entries, QUEUE_NO_ENTRY for none
     float* pool_states = nullptr;
     uint32_t pool_entries = 0;
     std::vector<uint32_t> start, save;
@@ -226,10 +246,6 @@ int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t 
 int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,
                          wrk_queue_result* out);
 
-// generate_stop: the options' stop sets validated into per-sequence rows (rows.size() == B; all counts 0 without stop arrays)
-int32_t wrk_stop_pack(wrk_ctx* ctx, const wrk_generate_options* opt, uint32_t B, uint32_t V, std::vector<wrk::StopParam>& rows);
-// the pick arrays of the options as generate_greedy / generate_sample / generate_penalized take them; *has_pick false: the arg-max
-int32_t wrk_stop_pick_args(wrk_ctx* ctx, const wrk_generate_options* opt, wrk_pick_args* pick, bool* has_pick);
 // after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): stop buffers of
 // the frame, the B rows, zero just_ended, live = B
 int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk::StopParam* rows);

@@ -72,122 +72,93 @@ void wrk_frame_common::drop_graphs() {
     graphs.clear();
 }
 
+std::vector<void**> wrk_frame_common::bufs(Group g) {
+    switch (g) {
+        case HISTORY: return {(void**)&history};
+        case SAMPLE: return {(void**)&sample_par};
+        case FILTER: return {(void**)&filter_par};
+        case PENALTY: return {(void**)&pen_par, (void**)&pen_o};
+        case STOP: return {(void**)&stop_par, (void**)&stop_flags, (void**)&stop_snap_state, (void**)&stop_snap_logits};
+        case QUEUE: return {(void**)&queue_slots, (void**)&queue_started, (void**)&queue_ctl, (void**)&queue_reqs, (void**)&queue_log, (void**)&queue_pool};
+        case QUEUE_STATES: return {(void**)&queue_state_ctl, (void**)&queue_turn, (void**)&queue_entries};
+        default: return {};
+    }
+}
+
+int32_t wrk_frame_common::regrow(Group g, std::initializer_list<size_t> bytes, bool drop) {
+    const std::vector<void**> list = bufs(g);
+    if (list.size() != bytes.size()) return wrk_fail(ctx, WRK_E_ARG, "buffer group %d: %zu sizes for %zu buffers", (int)g, bytes.size(), list.size());
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (drop) drop_graphs();
+    hipError_t e = hipSuccess;
+    size_t failed = 0, i = 0;
+    for (void** p : list) { if (*p) hipFree(*p); *p = nullptr; }
+    for (size_t n : bytes) {
+        if (e == hipSuccess && (e = hipMalloc(list[i], n)) != hipSuccess) failed = n;
+        ++i;
+    }
+    if (e == hipSuccess) return WRK_OK;
+    for (void** p : list) { if (*p) hipFree(*p); *p = nullptr; }       // the ensure_* look at their first pointer: the next call allocates again
+    return wrk_fail(ctx, e == hipErrorOutOfMemory ? WRK_E_OOM : WRK_E_HIP, "hipMalloc of %zu bytes: %s", failed, hipGetErrorString(e));
+}
+
 int32_t wrk_frame_common::ensure_history(size_t n) {
     if (n <= history_cap && history) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();
-    if (history) hipFree(history);
-    history = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&history, n * 4 + 256));
-    history_cap = n;
-    return WRK_OK;
+    const int32_t rc = regrow(HISTORY, {n * 4 + 256}, true);
+    if (rc == WRK_OK) history_cap = n;
+    return rc;
 }
 
 int32_t wrk_frame_common::ensure_sample_params(uint32_t n) {
     if (n <= sample_par_cap && sample_par) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();
-    if (sample_par) hipFree(sample_par);
-    sample_par = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&sample_par, (size_t)n * sizeof(wrk::SampleParam)));
-    sample_par_cap = n;
-    return WRK_OK;
+    const int32_t rc = regrow(SAMPLE, {(size_t)n * sizeof(wrk::SampleParam)}, true);
+    if (rc == WRK_OK) sample_par_cap = n;
+    return rc;
 }
 
 int32_t wrk_frame_common::ensure_filter_params(uint32_t n) {
     if (n <= filter_par_cap && filter_par) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();
-    if (filter_par) hipFree(filter_par);
-    filter_par = nullptr;
-    filter_par_cap = 0;
-    WRK_HIP(ctx, hipMalloc((void**)&filter_par, (size_t)n * sizeof(wrk::SampleFilter)));
-    filter_par_cap = n;
-    return WRK_OK;
+    const int32_t rc = regrow(FILTER, {(size_t)n * sizeof(wrk::SampleFilter)}, true);
+    if (rc == WRK_OK) filter_par_cap = n;
+    return rc;
 }
 
 int32_t wrk_frame_common::ensure_penalty(uint32_t n, uint32_t num_vocab) {
     if (n <= pen_cap && pen_par && pen_o) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();
-    if (pen_par) hipFree(pen_par);
-    if (pen_o) hipFree(pen_o);
-    pen_par = nullptr;
-    pen_o = nullptr;
-    pen_cap = 0;
-    WRK_HIP(ctx, hipMalloc((void**)&pen_par, (size_t)n * sizeof(wrk::PenaltyParam)));
-    WRK_HIP(ctx, hipMalloc((void**)&pen_o, (size_t)n * num_vocab * 4));
-    pen_cap = n;
-    return WRK_OK;
-}
-
-static void free_stop(wrk_frame_common& f) {
-    void* bufs[] = {f.stop_par, f.stop_flags, f.stop_snap_state, f.stop_snap_logits};
-    for (void* p : bufs) if (p) hipFree(p);
-    f.stop_par = nullptr; f.stop_flags = nullptr; f.stop_snap_state = nullptr; f.stop_snap_logits = nullptr;
-    f.stop_cap = 0; f.stop_slot_cap = 0; f.stop_vocab_cap = 0;
+    const int32_t rc = regrow(PENALTY, {(size_t)n * sizeof(wrk::PenaltyParam), (size_t)n * num_vocab * 4}, true);
+    if (rc == WRK_OK) pen_cap = n;
+    return rc;
 }
 
 int32_t wrk_frame_common::ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V) {
     const size_t slot = (size_t)L * (S + 2) * D;
     if (stop_par && n <= stop_cap && slot == stop_slot_cap && V == stop_vocab_cap) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs();
-    free_stop(*this);
-    WRK_HIP(ctx, hipMalloc((void**)&stop_par, (size_t)n * sizeof(wrk::StopParam)));
-    WRK_HIP(ctx, hipMalloc((void**)&stop_flags, ((size_t)2 * n + 1) * 4));
-    WRK_HIP(ctx, hipMalloc((void**)&stop_snap_state, (size_t)n * slot * 4));
-    WRK_HIP(ctx, hipMalloc((void**)&stop_snap_logits, (size_t)n * V * 4));
-    stop_cap = n; stop_slot_cap = slot; stop_vocab_cap = V;
-    return WRK_OK;
-}
-
-static void free_queue(wrk_frame_common& f) {
-    void* bufs[] = {f.queue_slots, f.queue_started, f.queue_ctl, f.queue_reqs, f.queue_log, f.queue_pool};
-    for (void* p : bufs) if (p) hipFree(p);
-    f.queue_slots = nullptr; f.queue_started = nullptr; f.queue_ctl = nullptr; f.queue_reqs = nullptr; f.queue_log = nullptr;
-    f.queue_pool = nullptr;
-    f.queue_slot_cap = 0; f.queue_req_cap = 0; f.queue_pool_cap = 0;
-}
-
-static void free_queue_states(wrk_frame_common& f) {
-    void* bufs[] = {f.queue_state_ctl, f.queue_turn, f.queue_entries};
-    for (void* p : bufs) if (p) hipFree(p);
-    f.queue_state_ctl = nullptr; f.queue_turn = nullptr; f.queue_entries = nullptr;
-    f.queue_turn_cap = 0; f.queue_entry_cap = 0;
+    const int32_t rc = regrow(STOP, {(size_t)n * sizeof(wrk::StopParam), ((size_t)2 * n + 1) * 4, (size_t)n * slot * 4, (size_t)n * V * 4}, true);
+    if (rc == WRK_OK) { stop_cap = n; stop_slot_cap = slot; stop_vocab_cap = V; }
+    return rc;
 }
 
 int32_t wrk_frame_common::ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens) {
     if (queue_ctl && slots <= queue_slot_cap && requests <= queue_req_cap && pool_tokens <= queue_pool_cap) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (queue_ctl) drop_graphs();                    // queue programs hold the old pointers; before the first allocation none exists
     // never smaller than before: a later, smaller queue reuses the buffers and the program
     if (slots < queue_slot_cap) slots = queue_slot_cap;
     if (requests < queue_req_cap) requests = queue_req_cap;
     if (pool_tokens < queue_pool_cap) pool_tokens = queue_pool_cap;
-    free_queue(*this);
-    WRK_HIP(ctx, hipMalloc((void**)&queue_slots, (size_t)slots * sizeof(wrk::QueueSlot)));
-    WRK_HIP(ctx, hipMalloc((void**)&queue_started, (size_t)slots * 4));
-    WRK_HIP(ctx, hipMalloc((void**)&queue_ctl, sizeof(wrk::QueueCtl)));
-    WRK_HIP(ctx, hipMalloc((void**)&queue_reqs, (size_t)requests * sizeof(wrk::QueueReq)));
-    WRK_HIP(ctx, hipMalloc((void**)&queue_log, (size_t)requests * sizeof(wrk::QueueLog)));
-    WRK_HIP(ctx, hipMalloc((void**)&queue_pool, pool_tokens * 4));
-    queue_slot_cap = slots; queue_req_cap = requests; queue_pool_cap = pool_tokens;
-    return WRK_OK;
+    // queue programs hold the old pointers; before the first allocation none exists
+    const int32_t rc = regrow(QUEUE, {(size_t)slots * sizeof(wrk::QueueSlot), (size_t)slots * 4, sizeof(wrk::QueueCtl), (size_t)requests * sizeof(wrk::QueueReq),
+                                      (size_t)requests * sizeof(wrk::QueueLog), pool_tokens * 4}, queue_ctl != nullptr);
+    if (rc == WRK_OK) { queue_slot_cap = slots; queue_req_cap = requests; queue_pool_cap = pool_tokens; }
+    return rc;
 }
 
 int32_t wrk_frame_common::ensure_queue_states(uint32_t slots, uint32_t requests) {
     if (queue_state_ctl && slots <= queue_turn_cap && requests <= queue_entry_cap) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (queue_state_ctl) drop_graphs();              // pool programs hold the old pointers; before the first allocation none exists
     if (slots < queue_turn_cap) slots = queue_turn_cap;
     if (requests < queue_entry_cap) requests = queue_entry_cap;
-    free_queue_states(*this);
-    WRK_HIP(ctx, hipMalloc((void**)&queue_state_ctl, sizeof(wrk::QueueStateCtl)));
-    WRK_HIP(ctx, hipMalloc((void**)&queue_turn, (size_t)slots * sizeof(wrk::QueueTurn)));
-    WRK_HIP(ctx, hipMalloc((void**)&queue_entries, (size_t)2 * requests * 4));
-    queue_turn_cap = slots; queue_entry_cap = requests;
-    return WRK_OK;
+    // pool programs hold the old pointers; before the first allocation none exists
+    const int32_t rc = regrow(QUEUE_STATES, {sizeof(wrk::QueueStateCtl), (size_t)slots * sizeof(wrk::QueueTurn), (size_t)2 * requests * 4}, queue_state_ctl != nullptr);
+    if (rc == WRK_OK) { queue_turn_cap = slots; queue_entry_cap = requests; }
+    return rc;
 }
 
 int32_t wrk_frame_common::ensure_poll(uint32_t lanes) {
@@ -207,14 +178,13 @@ int32_t wrk_frame_common::ensure_poll(uint32_t lanes) {
 
 void wrk_frame_common::release_common() {
     drop_graphs();
-    void* bufs[] = {scratch, history, sample_par, filter_par, pen_par, pen_o};
-    for (void* p : bufs) if (p) hipFree(p);
-    scratch = nullptr; history = nullptr; sample_par = nullptr; filter_par = nullptr; pen_par = nullptr; pen_o = nullptr;
-    filter_par_cap = 0;
+    if (scratch) hipFree(scratch);
+    scratch = nullptr;
+    for (int g = 0; g < NUM_GROUPS; ++g)
+        for (void** p : bufs((Group)g)) { if (*p) hipFree(*p); *p = nullptr; }
+    history_cap = 0; stop_slot_cap = 0; queue_pool_cap = 0;
+    sample_par_cap = filter_par_cap = pen_cap = stop_cap = stop_vocab_cap = queue_slot_cap = queue_req_cap = queue_turn_cap = queue_entry_cap = 0;
     score.release();
-    free_stop(*this);
-    free_queue(*this);
-    free_queue_states(*this);
     if (live_host) hipHostFree(live_host);
     live_host = nullptr; live_host_cap = 0;
     for (hipEvent_t e : poll_events) hipEventDestroy(e);
@@ -272,22 +242,58 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
 }
 
 // ------------------------------------------------------------------ decode loop
-int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args* pick, uint32_t B, uint32_t V, wrk_pick_params& out) {
-    if (!pick) return WRK_OK;
-    int32_t rc = wrk_sample_pack(ctx, pick->temperature, pick->top_p, pick->seed, B, out.par_rows);
-    if (rc != WRK_OK) return rc;
-    WRK_ARG(ctx, B >= 1, "num_batch 0");
-    out.par = out.par_rows.data();
-    if (pick->top_k || pick->min_p) {
-        rc = wrk_filter_pack(ctx, pick->top_k, pick->min_p, B, out.filt_rows);
-        if (rc != WRK_OK) return rc;
-        out.filt = out.filt_rows.data();
+int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, uint32_t slots, uint32_t V, wrk_pick_params& out, wrk_step_kind& kind) {
+    const int given = (a.temperature != nullptr) + (a.top_p != nullptr) + (a.seed != nullptr);
+    WRK_ARG(ctx, given == 3 || (given == 0 && a.need == wrk_pick_args::ANY), "temperature, top_p and seed: all three arrays%s",
+            a.need == wrk_pick_args::ANY ? ", or none for the arg-max" : "");
+    WRK_ARG(ctx, a.occ || a.need != wrk_pick_args::TABLE, "occurrence table required");
+    WRK_ARG(ctx, a.occ || (!a.presence && !a.frequency && !a.decay), "penalty arrays without an occurrence table");
+    WRK_ARG(ctx, !a.occ || given == 3, "penalties need the sampler arrays");
+    WRK_ARG(ctx, (!a.top_k && !a.min_p) || given == 3, "top_k / min_p need the sampler arrays");
+    kind.pick = given == 0 ? wrk_step_kind::GREEDY : (a.top_k || a.min_p) ? wrk_step_kind::FILTERED : wrk_step_kind::SAMPLED;
+    kind.penalized = a.occ != nullptr;
+    if (!kind.sampled()) return WRK_OK;
+    WRK_ARG(ctx, n >= 1, "a sampled pick of no rows");
+    int32_t rc = wrk_sample_pack(ctx, a.temperature, a.top_p, a.seed, n, out.par);
+    if (rc == WRK_OK && kind.filtered()) rc = wrk_filter_pack(ctx, a.top_k, a.min_p, n, out.filt);
+    if (rc != WRK_OK || !kind.penalized) return rc;
+    WRK_ARG(ctx, a.decay, "decay array required");
+    WRK_ARG(ctx, a.occ->num_batch >= slots, "occurrence table of %u slots, %u state slots", a.occ->num_batch, slots);
+    // the rows that name a slot of their own in one call, so that a bad value is reported with its row; request rows beyond the slots
+    // (a queue of more requests than slots) one at a time on slot 0
+    const uint32_t own = n < slots ? n : slots;
+    rc = wrk_penalty_pack(ctx, a.occ, 0, own, V, a.presence, a.frequency, a.decay, out.pen);
+    std::vector<wrk::PenaltyParam> one;
+    for (uint32_t r = own; r < n && rc == WRK_OK; ++r) {
+        rc = wrk_penalty_pack(ctx, a.occ, 0, 1, V, a.presence ? a.presence + r : nullptr, a.frequency ? a.frequency + r : nullptr, a.decay + r, one);
+        if (rc == WRK_OK) out.pen.push_back(one[0]);
     }
-    if (!pick->penalized) return WRK_OK;
-    WRK_ARG(ctx, pick->decay, "decay array required");
-    rc = wrk_penalty_pack(ctx, pick->occ, 0, B, V, pick->presence, pick->frequency, pick->decay, out.pen_rows);
-    out.pen = out.pen_rows.data();
     return rc;
+}
+
+int32_t wrk_stop_sets(wrk_ctx* ctx, const uint32_t* tokens, const uint32_t* off, uint32_t n, uint32_t V, const char* owner,
+                      std::vector<wrk::StopParam>& rows) {
+    WRK_ARG(ctx, !tokens || off, "stop_tokens without stop_offsets");
+    rows.assign(n, wrk::StopParam{});
+    if (!off) return WRK_OK;
+    WRK_ARG(ctx, off[0] == 0, "stop_offsets[0] = %u: must be 0", off[0]);
+    for (uint32_t i = 0; i < n; ++i) {
+        WRK_ARG(ctx, off[i + 1] >= off[i], "stop_offsets[%u] = %u decreases", i + 1, off[i + 1]);
+        const uint32_t cnt = off[i + 1] - off[i];
+        WRK_ARG(ctx, cnt <= WRK_MAX_STOP_TOKENS, "%s %u: %u stop tokens, at most %u", owner, i, cnt, (uint32_t)WRK_MAX_STOP_TOKENS);
+        WRK_ARG(ctx, cnt == 0 || tokens, "stop_offsets name %u stop tokens, stop_tokens is NULL", cnt);
+        for (uint32_t k = 0; k < cnt; ++k) {
+            rows[i].ids[k] = tokens[off[i] + k];
+            WRK_ARG(ctx, rows[i].ids[k] < V, "%s %u: stop token %u >= vocab %u", owner, i, rows[i].ids[k], V);
+        }
+        rows[i].count = cnt;
+    }
+    return WRK_OK;
+}
+
+bool wrk_no_graph() {
+    const char* e = getenv("WRK_NO_GRAPH");
+    return e && e[0] == '1';
 }
 
 int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, uint32_t num_emb, uint32_t num_layer, uint32_t V,
@@ -301,8 +307,11 @@ int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, u
 }
 
 int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps,
-                           const wrk::SampleParam* par, const wrk::PenaltyParam* pen, const wrk::SampleFilter* filt) {
+                           const wrk_pick_params& rows) {
     wrk_ctx* ctx = f.ctx;
+    const wrk::SampleParam* par = rows.par.empty() ? nullptr : rows.par.data() + b0;
+    const wrk::PenaltyParam* pen = rows.pen.empty() ? nullptr : rows.pen.data() + b0;
+    const wrk::SampleFilter* filt = rows.filt.empty() ? nullptr : rows.filt.data() + b0;
     int32_t rc = f.ensure_history((size_t)steps * B);
     if (rc == WRK_OK && par) rc = f.ensure_sample_params(B);
     if (rc == WRK_OK && filt) rc = f.ensure_filter_params(B);
@@ -312,7 +321,7 @@ int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, co
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
     rc = wrk_buf_write_raw(ctx, io.cursors, cur.data(), (size_t)B * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.headers, hdr.data(), (size_t)B * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.tokens, first_tokens, (size_t)B * 4);
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.tokens, first_tokens + b0, (size_t)B * 4);
     if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, f.sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
     if (rc == WRK_OK && filt) rc = wrk_buf_write_raw(ctx, f.filter_par, filt, (size_t)B * sizeof(wrk::SampleFilter));
     if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, f.pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
@@ -323,41 +332,6 @@ int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, co
 }
 
 // ------------------------------------------------------------------ stop tokens (wrk_stop.hip)
-int32_t wrk_stop_pack(wrk_ctx* ctx, const wrk_generate_options* opt, uint32_t B, uint32_t V, std::vector<wrk::StopParam>& rows) {
-    WRK_ARG(ctx, opt, "options required");
-    WRK_ARG(ctx, !opt->stop_tokens || opt->stop_offsets, "stop_tokens without stop_offsets");
-    rows.assign(B, wrk::StopParam{});
-    if (!opt->stop_offsets) return WRK_OK;
-    const uint32_t* off = opt->stop_offsets;
-    WRK_ARG(ctx, off[0] == 0, "stop_offsets[0] = %u: must be 0", off[0]);
-    for (uint32_t b = 0; b < B; ++b) {
-        WRK_ARG(ctx, off[b + 1] >= off[b], "stop_offsets[%u] = %u decreases", b + 1, off[b + 1]);
-        const uint32_t n = off[b + 1] - off[b];
-        WRK_ARG(ctx, n <= WRK_MAX_STOP_TOKENS, "sequence %u: %u stop tokens, at most %u", b, n, (uint32_t)WRK_MAX_STOP_TOKENS);
-        WRK_ARG(ctx, n == 0 || opt->stop_tokens, "stop_offsets name %u stop tokens, stop_tokens is NULL", n);
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t id = opt->stop_tokens[off[b] + k];
-            WRK_ARG(ctx, id < V, "sequence %u: stop token %u >= vocab %u", b, id, V);
-            rows[b].ids[k] = id;
-        }
-        rows[b].count = n;
-    }
-    return WRK_OK;
-}
-
-int32_t wrk_stop_pick_args(wrk_ctx* ctx, const wrk_generate_options* opt, wrk_pick_args* pick, bool* has_pick) {
-    WRK_ARG(ctx, opt, "options required");
-    const int given = (opt->temperature != nullptr) + (opt->top_p != nullptr) + (opt->seed != nullptr);
-    WRK_ARG(ctx, given == 0 || given == 3, "temperature, top_p and seed: all three arrays, or none for the arg-max");
-    WRK_ARG(ctx, opt->occ || (!opt->presence && !opt->frequency && !opt->decay), "penalty arrays without an occurrence table");
-    WRK_ARG(ctx, !opt->occ || given == 3, "penalties need the sampler arrays");
-    WRK_ARG(ctx, (!opt->top_k && !opt->min_p) || given == 3, "top_k / min_p need the sampler arrays");
-    *has_pick = given == 3;
-    *pick = wrk_pick_args{opt->temperature, opt->top_p, opt->seed, opt->occ != nullptr, opt->presence, opt->frequency, opt->decay, opt->occ,
-                          opt->top_k, opt->min_p};
-    return WRK_OK;
-}
-
 int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk::StopParam* rows) {
     wrk_ctx* ctx = f.ctx;
     int32_t rc = f.ensure_stop(B, st->num_layer, st->head_size, st->num_emb, V);
@@ -391,46 +365,18 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
     if (((mode_arg >> 8) & 0xffu) > 1)
         return wrk_fail(ctx, WRK_E_UNSUPPORTED, "generate_queue on several lanes: one queue shared by several streams would need cross-stream atomics");
     int32_t rc = queue_csr_check(ctx, opt->prompt_offsets, R, "prompt_offsets");
+    // the stop sets and the pick parameters go through the validation of the other loops, R rows at a time; of the penalty rows only
+    // (presence, frequency, decay) are kept, a slot's row pointers are its own
+    std::vector<wrk::StopParam> stops;
+    wrk_pick_params req;
+    if (rc == WRK_OK) rc = wrk_stop_sets(ctx, opt->stop_tokens, opt->stop_offsets, R, V, "request", stops);
+    if (rc == WRK_OK) rc = wrk_pick_pack(ctx, wrk_pick_of(*opt), R, B, V, req, pk.kind);
     if (rc != WRK_OK) return rc;
-    WRK_ARG(ctx, !opt->stop_tokens || opt->stop_offsets, "stop_tokens without stop_offsets");
-    if (opt->stop_offsets) {
-        rc = queue_csr_check(ctx, opt->stop_offsets, R, "stop_offsets");
-        if (rc != WRK_OK) return rc;
-    }
-    const int given = (opt->temperature != nullptr) + (opt->top_p != nullptr) + (opt->seed != nullptr);
-    WRK_ARG(ctx, given == 0 || given == 3, "temperature, top_p and seed: all three arrays, or none for the arg-max");
-    WRK_ARG(ctx, opt->occ || (!opt->presence && !opt->frequency && !opt->decay), "penalty arrays without an occurrence table");
-    WRK_ARG(ctx, !opt->occ || given == 3, "penalties need the sampler arrays");
-    WRK_ARG(ctx, (!opt->top_k && !opt->min_p) || given == 3, "top_k / min_p need the sampler arrays");
+    const wrk_step_kind kind = pk.kind;
     pk.R = R; pk.max_steps = opt->max_steps; pk.poll_steps = opt->poll_steps;
-    pk.sampled = given == 3; pk.penalized = opt->occ != nullptr; pk.filtered = opt->top_k || opt->min_p;
     pk.reqs.assign(R, wrk::QueueReq{});
     pk.pool.assign(opt->prompt_tokens, opt->prompt_tokens + opt->prompt_offsets[R]);
     for (size_t i = 0; i < pk.pool.size(); ++i) WRK_ARG(ctx, pk.pool[i] < V, "prompt token %zu: id %u >= vocab %u", i, pk.pool[i], V);
-    // the pick parameters go through the validation of the other loops, R rows at a time; the penalty rows of the R requests all
-    // name slot 0 here -- only their (presence, frequency, decay) are kept, a slot's row pointers are its own
-    std::vector<wrk::SampleParam> par;
-    std::vector<wrk::PenaltyParam> pen;
-    std::vector<wrk::SampleFilter> filt;
-    if (pk.sampled) {
-        rc = wrk_sample_pack(ctx, opt->temperature, opt->top_p, opt->seed, R, par);
-        if (rc != WRK_OK) return rc;
-    }
-    if (pk.filtered) {
-        rc = wrk_filter_pack(ctx, opt->top_k, opt->min_p, R, filt);
-        if (rc != WRK_OK) return rc;
-    }
-    if (pk.penalized) {
-        WRK_ARG(ctx, opt->decay, "decay array required");
-        WRK_ARG(ctx, opt->occ->num_batch >= B, "occurrence table of %u slots, %u state slots", opt->occ->num_batch, B);
-        std::vector<wrk::PenaltyParam> one;
-        for (uint32_t r = 0; r < R; ++r) {
-            rc = wrk_penalty_pack(ctx, opt->occ, 0, 1, V, opt->presence ? opt->presence + r : nullptr, opt->frequency ? opt->frequency + r : nullptr,
-                                  opt->decay + r, one);
-            if (rc != WRK_OK) return rc;
-            pen.push_back(one[0]);
-        }
-    }
     for (uint32_t r = 0; r < R; ++r) {
         wrk::QueueReq& q = pk.reqs[r];
         q.prompt_off = opt->prompt_offsets[r];
@@ -438,20 +384,12 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
         WRK_ARG(ctx, q.prompt_len >= 1, "request %u: empty prompt", r);
         q.max_new = opt->max_new[r];
         WRK_ARG(ctx, q.max_new >= 1, "request %u: max_new 0", r);
-        if (pk.sampled) { q.temperature = par[r].temperature; q.top_p = par[r].top_p; q.seed = par[r].seed; }
+        if (kind.sampled()) { q.temperature = req.par[r].temperature; q.top_p = req.par[r].top_p; q.seed = req.par[r].seed; }
         q.ln_min_p = -INFINITY;
-        if (pk.filtered) { q.top_k = filt[r].top_k; q.ln_min_p = filt[r].ln_min_p; }
-        if (pk.penalized) { q.presence = pen[r].presence; q.frequency = pen[r].frequency; q.decay = pen[r].decay; }
-        if (!opt->stop_offsets) continue;
-        const uint32_t n = opt->stop_offsets[r + 1] - opt->stop_offsets[r];
-        WRK_ARG(ctx, n <= WRK_MAX_STOP_TOKENS, "request %u: %u stop tokens, at most %u", r, n, (uint32_t)WRK_MAX_STOP_TOKENS);
-        WRK_ARG(ctx, n == 0 || opt->stop_tokens, "stop_offsets name %u stop tokens, stop_tokens is NULL", n);
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t id = opt->stop_tokens[opt->stop_offsets[r] + k];
-            WRK_ARG(ctx, id < V, "request %u: stop token %u >= vocab %u", r, id, V);
-            q.stop_ids[k] = id;
-        }
-        q.stop_count = n;
+        if (kind.filtered()) { q.top_k = req.filt[r].top_k; q.ln_min_p = req.filt[r].ln_min_p; }
+        if (kind.penalized) { q.presence = req.pen[r].presence; q.frequency = req.pen[r].frequency; q.decay = req.pen[r].decay; }
+        q.stop_count = stops[r].count;
+        memcpy(q.stop_ids, stops[r].ids, sizeof q.stop_ids);
     }
     if (opt->init_state) {
         const size_t need = (size_t)st->num_layer * (st->head_size + 2) * st->num_emb * 4;
@@ -461,16 +399,16 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
     }
     // what the slots start with: request b in slot b; a slot without a request idles on a valid id
     pk.first_tokens.assign(B, pk.pool[0]);
-    if (pk.sampled) pk.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
-    if (pk.penalized) pk.pen.resize(B);
-    if (pk.filtered) pk.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
+    if (kind.sampled()) pk.rows.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
+    if (kind.penalized) pk.rows.pen.resize(B);
+    if (kind.filtered()) pk.rows.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
     for (uint32_t b = 0; b < B; ++b) {
         const uint32_t r = b < R ? b : 0;       // idle slots: any valid row
         const wrk::QueueReq& q = pk.reqs[r];
         if (b < R) pk.first_tokens[b] = pk.pool[q.prompt_off];
-        if (pk.sampled && b < R) pk.par[b] = wrk::SampleParam{q.temperature, q.top_p, q.seed, q.prompt_len - 1};
-        if (pk.filtered && b < R) pk.filt[b] = wrk::SampleFilter{q.top_k, q.ln_min_p};
-        if (pk.penalized) pk.pen[b] = opt->occ->row(b, q.presence, q.frequency, q.decay);
+        if (kind.sampled() && b < R) pk.rows.par[b] = wrk::SampleParam{q.temperature, q.top_p, q.seed, q.prompt_len - 1};
+        if (kind.filtered() && b < R) pk.rows.filt[b] = wrk::SampleFilter{q.top_k, q.ln_min_p};
+        if (kind.penalized) pk.rows.pen[b] = opt->occ->row(b, q.presence, q.frequency, q.decay);
     }
     return WRK_OK;
 }
@@ -508,16 +446,16 @@ int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, const wrk
     if (slot % 4 != 0) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "a state pool needs (S + 2) * D = %zu to be a multiple of 4", slot);
     if ((((uintptr_t)pool->states->ptr) | ((uintptr_t)st->data) | ((uintptr_t)pk.init_state)) & 15u)
         return wrk_fail(ctx, WRK_E_UNSUPPORTED, "a state pool needs 16-byte aligned state, pool and init_state buffers");
-    pk.has_pool = true;
+    pk.kind.tail = wrk_step_kind::QUEUE_POOL;
     pk.pool_states = (float*)pool->states->ptr;
     pk.pool_entries = P;
     pk.saved_out = pool->saved;
     return WRK_OK;
 }
 
-static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, bool sampled, bool penalized, bool filtered) {
+static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
     return wrk::QueueBufs{f.queue_slots, f.queue_reqs, f.queue_pool, f.queue_log, f.queue_ctl, f.queue_started,
-                          sampled ? f.sample_par : nullptr, penalized ? f.pen_par : nullptr, filtered ? f.filter_par : nullptr};
+                          kind.sampled() ? f.sample_par : nullptr, kind.penalized ? f.pen_par : nullptr, kind.filtered() ? f.filter_par : nullptr};
 }
 
 static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f) {
@@ -531,7 +469,7 @@ static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V
 int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk_queue_pack& pk) {
     wrk_ctx* ctx = f.ctx;
     int32_t rc = f.ensure_queue(B, pk.R, pk.pool.size());
-    if (rc == WRK_OK && pk.has_pool) rc = f.ensure_queue_states(B, pk.R);
+    if (rc == WRK_OK && pk.kind.pool()) rc = f.ensure_queue_states(B, pk.R);
     if (rc != WRK_OK) return rc;
     const uint32_t nstart = B < pk.R ? B : pk.R;
     std::vector<wrk::QueueSlot> slots(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
@@ -549,7 +487,7 @@ int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t 
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_reqs, pk.reqs.data(), (size_t)pk.R * sizeof(wrk::QueueReq));
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_pool, pk.pool.data(), pk.pool.size() * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_ctl, &ctl, sizeof ctl);
-    if (rc == WRK_OK && pk.has_pool) {
+    if (rc == WRK_OK && pk.kind.pool()) {
         // the turnover list of "step -1": the slots that start at step 0, nothing to save
         std::vector<wrk::QueueTurn> turn(nstart);
         for (uint32_t b = 0; b < nstart; ++b) turn[b] = wrk::QueueTurn{b, wrk::QUEUE_NO_ENTRY, 1u, pk.start[b]};
@@ -561,37 +499,30 @@ int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t 
     }
     if (rc != WRK_OK) return rc;
     // the slots that start a request at step 0 are reset as the step that ends a request resets its slot
-    if (pk.has_pool)
-        wrk::queue_turnover(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.sampled, pk.penalized, pk.filtered), queue_state_bufs(f), B, ctx->num_cu);
-    else
-        wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.sampled, pk.penalized, pk.filtered), B, ctx->num_cu);
+    if (pk.kind.pool()) wrk::queue_turnover(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), queue_state_bufs(f), B, ctx->num_cu);
+    else wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), B, ctx->num_cu);
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
 }
 
-int32_t wrk_enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized, const wrk_stop_step& stop,
-                               bool filtered) {
+// tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
+// token (penalised), advance_queue, queue_reset of slots [b0, b0 + B) of `st`; with a pool advance_queue_pool and queue_turnover,
+// launch for launch
+static int32_t enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
     hipStream_t q = f.ctx->op_stream();
-    if (!f.queue_ctl || B > f.queue_slot_cap || stop.b0 != 0 || B > stop.st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
-    if (penalized) wrk::occurrence_update_queue(q, V, B, f.pen_par, io.argmax, f.queue_slots);
-    const wrk::QueueBufs bufs = queue_bufs(f, sampled, penalized, filtered);
-    wrk::advance_queue(q, io.argmax, io.tokens, f.history, io.counter, bufs, B);
-    wrk::queue_reset(q, queue_geom(stop.st, stop.b0, V), bufs, B, f.ctx->num_cu);
-    return WRK_OK;
-}
-
-int32_t wrk_enqueue_queue_pool_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
-                                    const wrk_stop_step& stop, bool filtered) {
-    hipStream_t q = f.ctx->op_stream();
-    if (!f.queue_ctl || B > f.queue_slot_cap || stop.b0 != 0 || B > stop.st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
-    if (!f.queue_state_ctl || B > f.queue_turn_cap || ((size_t)(stop.st->head_size + 2) * stop.st->num_emb) % 4 != 0)
+    if (!f.queue_ctl || B > f.queue_slot_cap || b0 != 0 || B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+    if (kind.pool() && (!f.queue_state_ctl || B > f.queue_turn_cap || ((size_t)(st->head_size + 2) * st->num_emb) % 4 != 0))
         return wrk_fail(f.ctx, WRK_E_ARG, "state pool buffers are not prepared");
-    if (penalized) wrk::occurrence_update_queue(q, V, B, f.pen_par, io.argmax, f.queue_slots);
-    const wrk::QueueBufs bufs = queue_bufs(f, sampled, penalized, filtered);
-    const wrk::QueueStateBufs sb = queue_state_bufs(f);
-    wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history, io.counter, bufs, sb, B);
-    wrk::queue_turnover(q, queue_geom(stop.st, stop.b0, V), bufs, sb, B, f.ctx->num_cu);
+    if (kind.penalized) wrk::occurrence_update_queue(q, V, B, f.pen_par, io.argmax, f.queue_slots);
+    const wrk::QueueBufs bufs = queue_bufs(f, kind);
+    if (kind.pool()) {
+        wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history, io.counter, bufs, queue_state_bufs(f), B);
+        wrk::queue_turnover(q, queue_geom(st, b0, V), bufs, queue_state_bufs(f), B, f.ctx->num_cu);
+    } else {
+        wrk::advance_queue(q, io.argmax, io.tokens, f.history, io.counter, bufs, B);
+        wrk::queue_reset(q, queue_geom(st, b0, V), bufs, B, f.ctx->num_cu);
+    }
     return WRK_OK;
 }
 
@@ -631,33 +562,35 @@ static wrk::StopGeom stop_geom(const wrk_frame_common& f, const wrk::FrameIo& io
     return g;
 }
 
-int32_t wrk_enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool penalized, const wrk_stop_step& stop) {
+// tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
+// (penalised), advance_stop, stop_snapshot of sequences [b0, b0 + B) of `st`
+static int32_t enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
     hipStream_t q = f.ctx->op_stream();
-    if (!f.stop_par || B > f.stop_cap || stop.b0 + B > stop.st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
-    if (penalized) wrk::occurrence_update_live(q, V, B, f.pen_par, io.argmax, f.stop_par);
+    if (!f.stop_par || B > f.stop_cap || b0 + B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
+    if (kind.penalized) wrk::occurrence_update_live(q, V, B, f.pen_par, io.argmax, f.stop_par);
     wrk::advance_stop(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(), B);
-    wrk::stop_snapshot(q, stop_geom(f, io, stop.st, stop.b0, V), B, f.ctx->num_cu);
+    wrk::stop_snapshot(q, stop_geom(f, io, st, b0, V), B, f.ctx->num_cu);
     return WRK_OK;
 }
 
-int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, bool sampled, bool penalized,
-                         const wrk_stop_step* stop, bool filtered) {
+int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0,
+                         bool argmax_done) {
     hipStream_t q = f.ctx->op_stream();
     const float* logits = io.head_o;
-    if (penalized) {
+    if (kind.penalized) {
         wrk::penalize_rows(q, io.head_o, V, V, B, f.pen_par, f.pen_o, V);
         logits = f.pen_o;
     }
-    // the sampler only reads the counter: rows run in different workgroups, so advance_tokens moves it after all of them
-    if (!sampled) wrk::argmax_rows(q, io.head_o, V, V, B, io.argmax);
-    else if (filtered && (!f.filter_par || B > f.filter_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
-    else if ((filtered ? wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax)
-                       : wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax)) != 0)
+    // the sampler only reads the counter: rows run in different workgroups, so the tail's advance moves it after all of them
+    if (!kind.sampled()) {
+        if (!argmax_done) wrk::argmax_rows(q, io.head_o, V, V, B, io.argmax);
+    } else if (kind.filtered() && (!f.filter_par || B > f.filter_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
+    else if ((kind.filtered() ? wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax)
+                              : wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax)) != 0)
         return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
-    if (stop && stop->queue && stop->pool) return wrk_enqueue_queue_pool_tail(f, io, V, B, sampled, penalized, *stop, filtered);
-    if (stop && stop->queue) return wrk_enqueue_queue_tail(f, io, V, B, sampled, penalized, *stop, filtered);
-    if (stop) return wrk_enqueue_stop_tail(f, io, V, B, penalized, *stop);
-    if (penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
+    if (kind.queue()) return enqueue_queue_tail(f, io, V, B, kind, st, b0);
+    if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, io, V, B, kind, st, b0);
+    if (kind.penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
     wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);
     return WRK_OK;
 }

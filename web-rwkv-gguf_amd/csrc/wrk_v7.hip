@@ -480,7 +480,7 @@ static int32_t v7_job(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const wrk
             r = wrk_fail(ctx, WRK_E_UNSUPPORTED, "score: vocabulary of %u tokens", V);
         return r;
     };
-    static const bool no_graph = [] { const char* e = getenv("WRK_NO_GRAPH"); return e && e[0] == '1'; }();
+    static const bool no_graph = wrk_no_graph();
     if (no_graph || ctx->capturing_here()) rc = enqueue_job();
     else {
         // bit 5: a non-fused job enqueues the merged launch list in mode 1 and the reference op list in mode 0 -- two graphs
@@ -615,76 +615,55 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
     return wrk_fail(ctx, WRK_E_ARG, "no frame buffer named %s", name);
 }
 
-// one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers, pick each sequence's next token and advance
-// tokens / history / counter (wrk_enqueue_pick; the fused greedy path does both inside its head launch)
-// stop: a stop program's step (wrk_stop.hip) -- the fused greedy head keeps its arg-max and leaves the advance to the stop tail;
-// queue (with stop): a queue program's step (wrk_queue.hip), the queue tail in the stop tail's place
-// filtered (with sampled): the pick is the filtered sampler's (top-k / min-p rows of the frame)
-// pool (with queue): a pool program's step, the pool tail in the queue tail's place
-static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, bool sampled,
-                                   bool penalized, bool stop = false, bool queue = false, bool filtered = false, bool pool = false) {
+// one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers and the head, then wrk_enqueue_pick.  The fused
+// greedy head leaves the arg-max in s.argmax, and in a plain step advances tokens / history / counter itself: nothing follows it
+static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) {
     int32_t rc;
-    const wrk_stop_step ss{st, b0, queue, pool};
-    if (mode == 1 && m->act_dtype == WRK_F16) {
-        rc = m->enqueue_fused_decode(st, B, B, true, true, !sampled, !sampled && !stop, b0, true);
-        if (!sampled && (!stop || rc != WRK_OK)) return rc;
-        if (!sampled && queue && pool) return wrk_enqueue_queue_pool_tail(*m, m->s, m->d.num_vocab, B, false, false, ss);
-        if (!sampled && queue) return wrk_enqueue_queue_tail(*m, m->s, m->d.num_vocab, B, false, false, ss);
-        if (!sampled) return wrk_enqueue_stop_tail(*m, m->s, m->d.num_vocab, B, false, ss);
-    } else {
+    const bool fused = mode == 1 && m->act_dtype == WRK_F16, head_picks = fused && !kind.sampled(),
+               head_advances = head_picks && kind.tail == wrk_step_kind::PLAIN;
+    if (fused) rc = m->enqueue_fused_decode(st, B, B, true, true, head_picks, head_advances, b0, true);
+    else {
         wrk::gather_rows_f16(ctx->op_stream(), m->emb->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
         rc = m->enqueue_ops(st, B, B, true);
     }
-    if (rc != WRK_OK) return rc;
-    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, sampled, penalized, stop ? &ss : nullptr, filtered);
+    if (rc != WRK_OK || head_advances) return rc;
+    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, kind, st, b0, head_picks);
 }
 
-// generate_greedy / generate_sample / generate_penalized, part 1: frame, token / cursor / sampler-parameter upload and the (cached)
-// decode-step program of sequences [b0, b0 + B) on model frame `m`; par: the B sequences' sampler parameters, or nullptr for the arg-max;
-// pen: their occurrence rows and penalties (with par), or nullptr
+// part 1 of a decode loop on model frame `m`: the frame, the upload of tokens / cursors / pick rows of sequences [b0, b0 + B) of the call,
+// the buffers of the tail (stop: the call's stop rows, queue: its tables -- whichever kind.tail names) and, unless `eager`, the cached
+// step program.  One program per (state, first sequence, B, mode, frame type, engine, split head, step kind): the analogue of the
+// reference's cached RnnJob for a repeated RnnInfo
 static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t b0, uint32_t B,
-                              uint32_t steps, uint32_t mode, bool eager, const wrk::SampleParam* par, const wrk::PenaltyParam* pen,
-                              const wrk::StopParam* stop, wrk_program** prog_out, const wrk_queue_pack* queue = nullptr,
-                              const wrk::SampleFilter* filt = nullptr) {
+                              uint32_t steps, uint32_t mode, bool eager, wrk_step_kind kind, const wrk_pick_params& rows,
+                              const wrk::StopParam* stop, const wrk_queue_pack* queue, wrk_program** prog_out) {
     int32_t rc = m->ensure_scratch(B, B);
     if (rc == WRK_OK && B == 1 && mode == 1) rc = m->ensure_engine();
-    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, m->d.num_vocab, first_tokens, b0, B, steps, par, pen, filt);
-    if (rc == WRK_OK && stop) rc = wrk_stop_prepare(*m, st, m->d.num_vocab, B, stop);
-    if (rc == WRK_OK && queue) rc = wrk_queue_prepare(*m, st, m->d.num_vocab, B, *queue);
+    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, m->d.num_vocab, first_tokens, b0, B, steps, rows);
+    if (rc == WRK_OK && kind.tail == wrk_step_kind::STOP) rc = wrk_stop_prepare(*m, st, m->d.num_vocab, B, stop + b0);
+    if (rc == WRK_OK && kind.queue()) rc = wrk_queue_prepare(*m, st, m->d.num_vocab, B, *queue);
     *prog_out = nullptr;
     if (rc != WRK_OK || eager) return rc;
-    // one graph per (state, first sequence, B, mode): the analogue of the reference's cached RnnJob for a repeated RnnInfo; sampled
-    // steps have their own key bit, so greedy and sampled programs never alias, and so do penalised ones (bit 24, above every infer flag)
-    // and stop programs (bit 25), queue programs (bit 26), programs whose pick is the filtered sampler (bit 27) and the queue programs
-    // of calls with a state pool (bit 28)
-    const bool pool = queue && queue->has_pool;
     const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
-                                                             (split_head_env_on() ? 0u : 16u) | (par ? 32u : 0u) | (pen ? 1u << 24 : 0u) |
-                                                             (stop ? 1u << 25 : 0u) | (queue ? 1u << 26 : 0u) | (filt ? 1u << 27 : 0u) | (pool ? 1u << 28 : 0u)};
-    return wrk_cached_program(ctx, m->graphs, key,
-                              [&] {
-                                  return enqueue_decode_step(ctx, m, st, b0, B, mode, par != nullptr, pen != nullptr, stop || queue, queue != nullptr,
-                                                             filt != nullptr, pool);
-                              },
-                              prog_out);
+                                                             (split_head_env_on() ? 0u : 16u) | kind.key()};
+    return wrk_cached_program(ctx, m->graphs, key, [&] { return enqueue_decode_step(ctx, m, st, b0, B, mode, kind); }, prog_out);
 }
 
-// pick: the sampler / penalty arrays of generate_sample / generate_penalized, or nullptr (generate_greedy)
+// pick: the ABI's pick arrays (none: generate_greedy); stop_opt: generate_stop's options, with out_lengths and steps_run
 static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
-                           const wrk_pick_args* pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,
+                           const wrk_pick_args& pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,
                            const wrk_generate_options* stop_opt = nullptr, uint32_t* out_lengths = nullptr, uint32_t* steps_run = nullptr) {
-    if (!ctx || !m || !st || !first_tokens || (pick && pick->penalized && !pick->occ)) return WRK_E_ARG;
+    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
     LOCK(ctx);
     const uint32_t V = m->d.num_vocab;
-    wrk_pick_params pp;
+    wrk_step_kind kind;
+    kind.tail = stop_opt ? wrk_step_kind::STOP : wrk_step_kind::PLAIN;
+    wrk_pick_params rows;
     std::vector<wrk::StopParam> stop_rows;      // generate_stop: one row per sequence
-    int32_t rc = wrk_pick_pack(ctx, pick, B, V, pp);
-    if (rc == WRK_OK && stop_opt) rc = wrk_stop_pack(ctx, stop_opt, B, V, stop_rows);
+    int32_t rc = wrk_pick_pack(ctx, pick, B, B, V, rows, kind);
+    if (rc == WRK_OK && stop_opt) rc = wrk_stop_sets(ctx, stop_opt->stop_tokens, stop_opt->stop_offsets, B, V, "sequence", stop_rows);
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->emb != nullptr, m->d.num_emb, m->d.num_layer, V, first_tokens, B);
     if (rc != WRK_OK) return rc;
-    const wrk::SampleParam* par = pp.par;
-    const wrk::PenaltyParam* pen = pp.pen;
-    const wrk::SampleFilter* filt = pp.filt;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     if (stop_opt) {
         *steps_run = 0;
@@ -696,8 +675,7 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
     uint32_t groups = (mode_arg >> 8) & 0xffu;
     if (groups < 1) groups = 1;
     if (groups > B) groups = B;
-    const char* ng = getenv("WRK_NO_GRAPH");
-    const bool eager = ng && ng[0] == '1';
+    const bool eager = wrk_no_graph();
     WRK_ARG(ctx, groups == 1 || !eager, "concurrent pipelines replay captured programs: not with WRK_NO_GRAPH=1");
     wrk::timing_slot(ctx, nullptr);     // WRK_TIMING=1: allocate the stamp buffer outside the capture
 
@@ -727,18 +705,14 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
         L[g].b0 = (uint32_t)((uint64_t)B * g / groups);
         L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
         // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
-        rc = decode_prepare(ctx, mdl, st, first_tokens + L[g].b0, L[g].b0, L[g].nb, steps, mode, eager, par ? par + L[g].b0 : nullptr,
-                            pen ? pen + L[g].b0 : nullptr, stop_opt ? stop_rows.data() + L[g].b0 : nullptr, &L[g].prog, nullptr,
-                            filt ? filt + L[g].b0 : nullptr);
+        rc = decode_prepare(ctx, mdl, st, first_tokens, L[g].b0, L[g].nb, steps, mode, eager, kind, rows, stop_rows.data(), nullptr, &L[g].prog);
         if (rc != WRK_OK) return rc;
         L[g].io = &mdl->s;
         L[g].history = mdl->history;
         L[g].frame = mdl;
     }
     const wrk_stop_run stop_run{st, stop_opt ? stop_opt->poll_steps : 0u, out_lengths, steps_run};
-    rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, steps,
-                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, par != nullptr, pen != nullptr, stop_opt != nullptr, false, filt != nullptr); },
-                       out_tokens,
+    rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, steps, [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, kind); }, out_tokens,
                        last_logits, elapsed_ms, stop_opt ? &stop_run : nullptr);
     if (rc != WRK_OK) return rc;
     wrk::timing_report(ctx);
@@ -752,69 +726,63 @@ static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, cons
 
 int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
                                uint32_t steps, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg) {
-    return v7_generate(ctx, m, st, first_tokens, B, steps, nullptr, out_tokens, last_logits, elapsed_ms, mode_arg);
+    return v7_generate(ctx, m, st, first_tokens, B, steps, wrk_pick_args{}, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                const float* temperature, const float* top_p, const uint32_t* seed, uint32_t* out_tokens, float* last_logits,
                                float* elapsed_ms, uint32_t mode_arg) {
-    const wrk_pick_args pick{temperature, top_p, seed};
-    return v7_generate(ctx, m, st, first_tokens, B, steps, &pick, out_tokens, last_logits, elapsed_ms, mode_arg);
+    wrk_pick_args pick{temperature, top_p, seed};
+    pick.need = wrk_pick_args::SAMPLER;
+    return v7_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                   const float* temperature, const float* top_p, const uint32_t* seed, const float* presence,
                                   const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens, float* last_logits,
                                   float* elapsed_ms, uint32_t mode_arg) {
-    const wrk_pick_args pick{temperature, top_p, seed, true, presence, frequency, decay, occ};
-    return v7_generate(ctx, m, st, first_tokens, B, steps, &pick, out_tokens, last_logits, elapsed_ms, mode_arg);
+    wrk_pick_args pick{temperature, top_p, seed, presence, frequency, decay, occ};
+    pick.need = wrk_pick_args::TABLE;
+    return v7_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                              const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths, float* last_logits,
                              uint32_t* steps_run, float* elapsed_ms, uint32_t mode_arg) {
     if (!ctx) return WRK_E_ARG;
-    wrk_pick_args pick{};
-    bool has_pick = false;
     {
         LOCK(ctx);
+        WRK_ARG(ctx, opt, "options required");
         WRK_ARG(ctx, out_lengths && steps_run, "out_lengths and steps_run are required");
-        const int32_t rc = wrk_stop_pick_args(ctx, opt, &pick, &has_pick);
-        if (rc != WRK_OK) return rc;
     }
-    return v7_generate(ctx, m, st, first_tokens, B, steps, has_pick ? &pick : nullptr, out_tokens, last_logits, elapsed_ms, mode_arg, opt,
-                       out_lengths, steps_run);
+    return v7_generate(ctx, m, st, first_tokens, B, steps, wrk_pick_of(*opt), out_tokens, last_logits, elapsed_ms, mode_arg, opt, out_lengths, steps_run);
 }
 
 // generate_queue: one lane, the frame's own; the loop is generate_stop's polled one with the queue's live count
-// pool: the state pool of wrk_v7_generate_queue_pool (required when has_pool)
+// tail: QUEUE, or QUEUE_POOL with the state pool of wrk_v7_generate_queue_pool
 static int32_t v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
-                                 const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, bool has_pool, const wrk_queue_pool* pool) {
+                                 const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail, const wrk_queue_pool* pool) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     const uint32_t V = m->d.num_vocab;
     wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
     wrk_queue_pack pk;
     int32_t rc = wrk_queue_check(ctx, opt, st, B, V, mode_arg, out_arg ? &out : nullptr, pk);
-    if (rc == WRK_OK && has_pool) rc = wrk_queue_pool_check(ctx, pool, opt, st, pk);
+    if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, pk);
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->emb != nullptr, m->d.num_emb, m->d.num_layer, V, pk.first_tokens.data(), B);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     const uint32_t mode = mode_arg & 0xffu;
-    const char* ng = getenv("WRK_NO_GRAPH");
-    const bool eager = ng && ng[0] == '1';
     wrk::timing_slot(ctx, nullptr);
     m->engine_blocked = false;
     std::vector<wrk_lane> L(1);
-    rc = decode_prepare(ctx, m, st, pk.first_tokens.data(), 0, B, pk.max_steps, mode, eager, pk.sampled ? pk.par.data() : nullptr,
-                        pk.penalized ? pk.pen.data() : nullptr, nullptr, &L[0].prog, &pk, pk.filtered ? pk.filt.data() : nullptr);
+    rc = decode_prepare(ctx, m, st, pk.first_tokens.data(), 0, B, pk.max_steps, mode, wrk_no_graph(), pk.kind, pk.rows, nullptr, &pk, &L[0].prog);
     if (rc != WRK_OK) return rc;
     L[0].io = &m->s; L[0].history = m->history; L[0].b0 = 0; L[0].nb = B; L[0].frame = m;
     uint32_t steps_run = 0;
     const wrk_stop_run run{st, pk.poll_steps, nullptr, &steps_run, true};
-    rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, pk.max_steps,
-                       [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, pk.sampled, pk.penalized, true, true, pk.filtered, pk.has_pool); }, nullptr, nullptr, elapsed_ms,
-                       &run);
+    rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, pk.max_steps, [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, pk.kind); },
+                       nullptr, nullptr, elapsed_ms, &run);
     if (rc != WRK_OK) return rc;
     rc = wrk_v7_engine_check(m->engine);
     if (rc != WRK_OK) return rc;
@@ -823,12 +791,12 @@ static int32_t v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st
 
 int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                               const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
-    return v7_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, false, nullptr);
+    return v7_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE, nullptr);
 }
 
 int32_t wrk_v7_generate_queue_pool(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                                    const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_pool* pool) {
-    return v7_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, true, pool);
+    return v7_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE_POOL, pool);
 }
 
 }  // extern "C"

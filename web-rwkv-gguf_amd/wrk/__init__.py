@@ -274,6 +274,41 @@ def _filters(top_k, min_p, n: int, keep: list):
     return tk, mp
 
 
+def _fill_pick(opt, n: int, keep: list, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p):
+    """The sampler / penalty / filter fields of a GenerateOptions or QueueOptions for n rows (scalars broadcast; seed None: seed[i] = i).
+    All of temperature, top_p, seed, occurrence, top_k, min_p None: nothing is set, the arg-max.  The arrays go into `keep`, which must
+    outlive the call."""
+    def put(v, dtype, ty):
+        keep.append(_per_row(v, n, dtype))
+        return _ptr(keep[-1], ty)
+    if all(v is None for v in (temperature, top_p, seed, occurrence, top_k, min_p)):
+        return
+    opt.temperature = put(1.0 if temperature is None else temperature, np.float32, _f32p)
+    opt.top_p = put(0.5 if top_p is None else top_p, np.float32, _f32p)
+    opt.seed = put(np.arange(n, dtype=np.uint32) if seed is None else seed, np.uint32, _u32p)
+    if occurrence is not None:
+        opt.presence, opt.frequency, opt.decay = (put(v, np.float32, _f32p) for v in (presence, frequency, decay))
+        opt.occ = occurrence.h
+    tk, mp = _filters(top_k, min_p, n, keep)
+    if tk is not None:
+        opt.top_k = tk
+    if mp is not None:
+        opt.min_p = mp
+
+
+def _stop_csr(stop, n: int, owners: str):
+    """Stop sets as (ids, offsets [n + 1]): one list of ids for all n owners, or one list per owner."""
+    sets = [] if stop is None else list(stop)
+    if not (sets and all(isinstance(x, (list, tuple, np.ndarray)) for x in sets)):
+        sets = [sets] * n
+    if len(sets) != n:
+        raise ValueError(f"{len(sets)} stop sets for {n} {owners}")
+    off = np.zeros(n + 1, np.uint32)
+    off[1:] = np.cumsum([len(x) for x in sets])
+    ids = _u32(np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in sets]) if n else [])
+    return (ids if ids.size else np.zeros(1, np.uint32)), off
+
+
 # ----------------------------------------------------------------------------- backend objects
 class Context:
     """`Context` (src/context.rs:51-64): one HIP device + submission stream."""
@@ -978,20 +1013,32 @@ class Runtime:
         self.ctx.check(hip.wrk_v7_frame_read(self.ctx.h, self.model, name.encode(), num_token, out.ctypes.data_as(_P), out.nbytes, C.byref(n)))
         return out.reshape(num_token, -1)
 
-    def generate_greedy(self, first_tokens, steps: int, mode: int = 1, want_logits: bool = False, groups: int = 1):
-        """Device-resident greedy loop; returns (tokens [steps, B], elapsed_ms[, last logits [B, V]]).
-        groups > 1 (RWKV-7): the B independent sequences are dealt over that many concurrent pipelines (each a contiguous block of
-        sequences with its own frame, decode program and HIP stream) instead of one batched step."""
-        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
+    def _entry(self, name: str):
+        """(wrk_v6_<name>, the RWKV-6 model) or (wrk_v7_<name>, the RWKV-7 model)."""
+        return (getattr(hip, "wrk_v6_" + name), self.model6) if self.model6 else (getattr(hip, "wrk_v7_" + name), self.model)
+
+    def _mode(self, mode: int, groups: int) -> int:
+        """The ABI's mode word: mode | concurrent pipelines << 8 (RWKV-7 only)."""
+        return (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
+
+    def _generate(self, name: str, first_tokens, steps, rows, mode, groups, want_logits):
+        """wrk_v*_generate_<name> with `rows` (per-sequence arrays and handles) between steps and the outputs: (tokens [steps, B],
+        elapsed ms[, last logits [B, V]])."""
         ft = _u32(first_tokens)
         B = ft.size
         out = np.zeros((steps, B), np.uint32)
         ms = C.c_float()
         logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
-        fn, mdl = (hip.wrk_v6_generate_greedy, self.model6) if self.model6 else (hip.wrk_v7_generate_greedy, self.model)
-        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, _ptr(out, _u32p),
-                          _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
+        fn, mdl = self._entry("generate_" + name)
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, *rows, _ptr(out, _u32p),
+                          _ptr(logits, _f32p) if want_logits else None, C.byref(ms), self._mode(mode, groups)))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
+
+    def generate_greedy(self, first_tokens, steps: int, mode: int = 1, want_logits: bool = False, groups: int = 1):
+        """Device-resident greedy loop; returns (tokens [steps, B], elapsed_ms[, last logits [B, V]]).
+        groups > 1 (RWKV-7): the B independent sequences are dealt over that many concurrent pipelines (each a contiguous block of
+        sequences with its own frame, decode program and HIP stream) instead of one batched step."""
+        return self._generate("greedy", first_tokens, steps, (), mode, groups, want_logits)
 
     def _generate_options(self, first_tokens, steps, opt, keep, mode, want_logits):
         """wrk_v*_generate_stop on prepared options: (tokens [steps, B], lengths [B], steps_run, elapsed ms, last logits or None)."""
@@ -1001,10 +1048,17 @@ class Runtime:
         lengths = np.zeros(B, np.uint32)
         run, ms = C.c_uint32(), C.c_float()
         logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
-        fn, mdl = (hip.wrk_v6_generate_stop, self.model6) if self.model6 else (hip.wrk_v7_generate_stop, self.model)
+        fn, mdl = self._entry("generate_stop")
         self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, C.byref(opt), _ptr(out, _u32p), _ptr(lengths, _u32p),
                           _ptr(logits, _f32p) if want_logits else None, C.byref(run), C.byref(ms), mode))
         return out, lengths, run.value, ms.value, logits
+
+    @staticmethod
+    def _sampler_rows(B: int, temperature, top_p, seed):
+        """(temperature, top_p, seed) [B] and their pointers, as wrk_v*_generate_sample takes them."""
+        t, p = _per_row(temperature, B, np.float32), _per_row(top_p, B, np.float32)
+        sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
+        return (t, p, sd), (_ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p))
 
     def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
                         groups: int = 1, top_k=None, min_p=None):
@@ -1015,38 +1069,14 @@ class Runtime:
         if top_k is not None or min_p is not None:
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
                                            want_logits, groups)
-        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
-        ft = _u32(first_tokens)
-        B = ft.size
-        t, p = _per_row(temperature, B, np.float32), _per_row(top_p, B, np.float32)
-        sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
-        out = np.zeros((steps, B), np.uint32)
-        ms = C.c_float()
-        logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
-        fn, mdl = (hip.wrk_v6_generate_sample, self.model6) if self.model6 else (hip.wrk_v7_generate_sample, self.model)
-        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p),
-                          _ptr(out, _u32p), _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
-        return (out, ms.value, logits) if want_logits else (out, ms.value)
+        keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
+        return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
 
     def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
                            want_logits, groups):
-        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
-        B = _u32(first_tokens).size
         opt, keep = GenerateOptions(), []
-        t, p = _per_row(temperature, B, np.float32), _per_row(top_p, B, np.float32)
-        sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
-        keep += [t, p, sd]
-        opt.temperature, opt.top_p, opt.seed = _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p)
-        if occurrence is not None:
-            ap, af, g = _per_row(presence, B, np.float32), _per_row(frequency, B, np.float32), _per_row(decay, B, np.float32)
-            keep += [ap, af, g]
-            opt.presence, opt.frequency, opt.decay, opt.occ = _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h
-        tk, mp = _filters(top_k, min_p, B, keep)
-        if tk is not None:
-            opt.top_k = tk
-        if mp is not None:
-            opt.min_p = mp
-        out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, mode, want_logits)
+        _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p)
+        out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits)
         return (out, ms, logits) if want_logits else (out, ms)
 
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
@@ -1059,20 +1089,11 @@ class Runtime:
         if top_k is not None or min_p is not None:
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
                                            min_p, mode, want_logits, groups)
-        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
-        ft = _u32(first_tokens)
-        B = ft.size
-        t, p = _per_row(temperature, B, np.float32), _per_row(top_p, B, np.float32)
-        sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
-        ap, af, g = _per_row(presence, B, np.float32), _per_row(frequency, B, np.float32), _per_row(decay, B, np.float32)
-        out = np.zeros((steps, B), np.uint32)
-        ms = C.c_float()
-        logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
-        fn, mdl = (hip.wrk_v6_generate_penalized, self.model6) if self.model6 else (hip.wrk_v7_generate_penalized, self.model)
-        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p),
-                          _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h, _ptr(out, _u32p),
-                          _ptr(logits, _f32p) if want_logits else None, C.byref(ms), mode))
-        return (out, ms.value, logits) if want_logits else (out, ms.value)
+        B = _u32(first_tokens).size
+        keep, rows = self._sampler_rows(B, temperature, top_p, seed)
+        pen = [_per_row(v, B, np.float32) for v in (presence, frequency, decay)]
+        rows += tuple(_ptr(a, _f32p) for a in pen) + (occurrence.h,)
+        return self._generate("penalized", first_tokens, steps, rows, mode, groups, want_logits)
 
     def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
@@ -1083,40 +1104,12 @@ class Runtime:
         are what the call without stops draws, the stop token last; later rows repeat it.  The state slot, the occurrence slot and the
         logits row of a finished sequence are those of a `lengths[b]`-step call.  steps_run < steps once every sequence has ended (the host
         looks every `poll_steps` steps; 0: the default).  top_k / min_p: as `generate_sample` (they make the pick a sampled one)."""
-        mode = (mode & 0xff) | ((groups & 0xff) << 8 if groups > 1 and not self.model6 else 0)
         ft = _u32(first_tokens)
-        B = ft.size
-        sets = list(stop)
-        if not (sets and all(isinstance(x, (list, tuple, np.ndarray)) for x in sets)):
-            sets = [sets] * B
-        if len(sets) != B:
-            raise ValueError(f"{len(sets)} stop sets for {B} sequences")
-        off = np.zeros(B + 1, np.uint32)
-        off[1:] = np.cumsum([len(x) for x in sets])
-        ids = _u32(np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in sets]) if B else [])
-        if ids.size == 0:
-            ids = np.zeros(1, np.uint32)
-        opt = GenerateOptions()
-        keep = []
-        sampled = (temperature is not None or top_p is not None or seed is not None or occurrence is not None or top_k is not None
-                   or min_p is not None)
-        if sampled:
-            t = _per_row(1.0 if temperature is None else temperature, B, np.float32)
-            p = _per_row(0.5 if top_p is None else top_p, B, np.float32)
-            sd = np.arange(B, dtype=np.uint32) if seed is None else _per_row(seed, B, np.uint32)
-            keep += [t, p, sd]
-            opt.temperature, opt.top_p, opt.seed = _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p)
-        if occurrence is not None:
-            ap, af, g = _per_row(presence, B, np.float32), _per_row(frequency, B, np.float32), _per_row(decay, B, np.float32)
-            keep += [ap, af, g]
-            opt.presence, opt.frequency, opt.decay, opt.occ = _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h
+        ids, off = _stop_csr(stop, ft.size, "sequences")
+        opt, keep = GenerateOptions(), []
+        _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p)
         opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
-        tk, mp = _filters(top_k, min_p, B, keep)
-        if tk is not None:
-            opt.top_k = tk
-        if mp is not None:
-            opt.min_p = mp
-        out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, mode, want_logits)
+        out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, self._mode(mode, groups), want_logits)
         out = out[:run]
         return (out, lengths, logits) if want_logits else (out, lengths)
 
@@ -1140,19 +1133,10 @@ class Runtime:
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
-        sets = [] if stop is None else list(stop)
-        if not (sets and all(isinstance(x, (list, tuple, np.ndarray)) for x in sets)):
-            sets = [sets] * R
-        if len(sets) != R:
-            raise ValueError(f"{len(sets)} stop sets for {R} requests")
         poff = np.zeros(R + 1, np.uint32)
         poff[1:] = np.cumsum([x.size for x in prompts])
         ptok = _u32(np.concatenate(prompts) if R else [])
-        soff = np.zeros(R + 1, np.uint32)
-        soff[1:] = np.cumsum([len(x) for x in sets])
-        ids = _u32(np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in sets]) if R else [])
-        if ids.size == 0:
-            ids = np.zeros(1, np.uint32)
+        ids, soff = _stop_csr(stop, R, "requests")
         if ptok.size == 0:
             ptok = np.zeros(1, np.uint32)
         mn = _per_row(max_new, R, np.uint32)
@@ -1161,22 +1145,7 @@ class Runtime:
         opt.prompt_tokens, opt.prompt_offsets, opt.max_new = _ptr(ptok, _u32p), _ptr(poff, _u32p), _ptr(mn, _u32p)
         opt.stop_tokens, opt.stop_offsets = _ptr(ids, _u32p), _ptr(soff, _u32p)
         keep = []
-        if (temperature is not None or top_p is not None or seed is not None or occurrence is not None or top_k is not None
-                or min_p is not None):
-            t = _per_row(1.0 if temperature is None else temperature, R, np.float32)
-            p = _per_row(0.5 if top_p is None else top_p, R, np.float32)
-            sd = np.arange(R, dtype=np.uint32) if seed is None else _per_row(seed, R, np.uint32)
-            keep += [t, p, sd]
-            opt.temperature, opt.top_p, opt.seed = _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p)
-        if occurrence is not None:
-            ap, af, g = _per_row(presence, R, np.float32), _per_row(frequency, R, np.float32), _per_row(decay, R, np.float32)
-            keep += [ap, af, g]
-            opt.presence, opt.frequency, opt.decay, opt.occ = _ptr(ap, _f32p), _ptr(af, _f32p), _ptr(g, _f32p), occurrence.h
-        tk, mp = _filters(top_k, min_p, R, keep)
-        if tk is not None:
-            opt.top_k = tk
-        if mp is not None:
-            opt.min_p = mp
+        _fill_pick(opt, R, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p)
         if init_state is not None:
             opt.init_state = init_state.h
         opt.poll_steps = poll_steps
@@ -1189,7 +1158,7 @@ class Runtime:
         if pool is None:
             if start_state is not None or save_state is not None:
                 raise ValueError("start_state / save_state need a pool")
-            fn, mdl = (hip.wrk_v6_generate_queue, self.model6) if self.model6 else (hip.wrk_v7_generate_queue, self.model)
+            fn, mdl = self._entry("generate_queue")
             self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode))
             self.last_queue_saved = None
         else:
@@ -1201,7 +1170,7 @@ class Runtime:
                 return _u32([QUEUE_NO_ENTRY if k is None else int(k) for k in v]) if R else np.zeros(1, np.uint32)
             st, sv, saved = entries(start_state), entries(save_state), np.zeros(max(R, 1), np.uint32)
             qp = QueuePool(pool.buf.h, pool.entries, _ptr(st, _u32p), _ptr(sv, _u32p), _ptr(saved, _u32p))
-            fn, mdl = (hip.wrk_v6_generate_queue_pool, self.model6) if self.model6 else (hip.wrk_v7_generate_queue_pool, self.model)
+            fn, mdl = self._entry("generate_queue_pool")
             self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qp)))
             self.last_queue_saved = [bool(x) for x in saved[:R]]
         self.last_queue_ms = ms.value
