@@ -497,7 +497,10 @@ int32_t wrk_v7_generate_queue_pool(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_sta
 
 /* ---------------------------------------------------------------- RWKV-6 (v6::Model, src/runtime/v6.rs)
  * Same chunk semantics, state layout ([D, S+2, B] per layer: v6.rs:150-214 == v7) and entry points as the V7
- * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph. */
+ * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph.
+ * Every decode loop (generate_greedy ... generate_queue_pool) reads bits 0-7 of `mode` and runs on one lane: bits 8-15,
+ * RWKV-7's number of concurrent pipelines, are ignored, except that a queue call refuses more than one lane
+ * (WRK_E_UNSUPPORTED) as RWKV-7's does. */
 typedef struct wrk_v6_model wrk_v6_model;
 
 typedef struct wrk_v6_layer_desc {

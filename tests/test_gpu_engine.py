@@ -107,6 +107,28 @@ def test_engine_greedy_loop_and_layer_entry(ctx, monkeypatch):
         rt.close()
 
 
+def test_engine_returns_after_concurrent_pipelines(ctx, monkeypatch):
+    """Concurrent pipelines block the engine on every lane they use (two persistent engines side by side would wait for each other's
+    CUs); the next call on one lane takes it back.  After generate_greedy(B = 2, groups = 2) a one-sequence call on the same runtime
+    equals, bit for bit, the call on a fresh runtime, and engine_status() reports what it reported before."""
+    monkeypatch.setenv("WRK_ENGINE", "1")
+    data = synth.make_v7_gguf(synth.CONFIGS["small"], 42)
+    rt = wrk.Runtime(ctx, wrk.GgufReader(data), num_batch=2, weights=wrk.WEIGHTS_INLINE)
+    other = wrk.Runtime(ctx, wrk.GgufReader(data), num_batch=1, weights=wrk.WEIGHTS_INLINE)
+    try:
+        before = rt.engine_status()
+        assert before[0], before[1]
+        rt.generate_greedy([3, 9], 6, mode=1, groups=2)
+        rt.state_load(np.zeros_like(rt.state_back(0)), 0)
+        tok, _, logits = rt.generate_greedy([3], 8, mode=1, want_logits=True)
+        want_tok, _, want_logits = other.generate_greedy([3], 8, mode=1, want_logits=True)
+        assert np.array_equal(tok, want_tok)
+        assert np.array_equal(logits.view(np.uint32), want_logits.view(np.uint32))
+        assert rt.engine_status() == before
+    finally:
+        rt.close(); other.close()
+
+
 def test_engine_equals_launches_headline_model(ctx, monkeypatch):
     """bench.py's 1.5B Q4_K_M model (the configuration the metric is quoted on): 12 teacher-forced tokens + a 24-token greedy run."""
     gg = bench.make_model_gguf("1.5B", seed=7)

@@ -181,6 +181,44 @@ def test_v6_generate_rejects_a_state_of_another_model(ctx):
     tiny.close(); small.close()
 
 
+def test_v6_decode_loops_ignore_the_lane_bits(ctx):
+    """RWKV-6 runs one lane: bits 8-15 of the mode word (RWKV-7's number of concurrent pipelines) change nothing in generate_greedy and
+    generate_stop -- same fused step, same tokens, last logits and state slots, bit for bit, as mode 1 from the same zeroed state.  The
+    Python wrapper masks the bits for RWKV-6 (Runtime._mode), so the calls go to the C entry points."""
+    import ctypes as C
+    B, steps = 2, 4
+    rt = wrk.Runtime(ctx, wrk.GgufReader(synth.make_v6_gguf(synth.V6_CONFIGS["tiny"], 42)), num_batch=B, weights=wrk.WEIGHTS_INLINE)
+    V = rt.info.num_vocab
+    first = np.array([7, 100], np.uint32)
+    zero = np.zeros_like(rt.state_back(0))
+
+    def run(entry, mode):
+        for b in range(B):
+            rt.state_load(zero, b)
+        tok, logits = np.zeros((steps, B), np.uint32), np.zeros((B, V), np.float32)
+        head = (ctx.h, rt.model6, rt.state, wrk._ptr(first, wrk._u32p), B, steps)
+        if entry == "greedy":
+            rc = wrk.hip.wrk_v6_generate_greedy(*head, wrk._ptr(tok, wrk._u32p), wrk._ptr(logits, wrk._f32p), None, mode)
+        else:
+            opt, lens, ran = wrk.GenerateOptions(), np.zeros(B, np.uint32), C.c_uint32()
+            rc = wrk.hip.wrk_v6_generate_stop(*head, C.byref(opt), wrk._ptr(tok, wrk._u32p), wrk._ptr(lens, wrk._u32p),
+                                              wrk._ptr(logits, wrk._f32p), C.byref(ran), None, mode)
+            assert lens.tolist() == [steps] * B and ran.value == steps
+        ctx.check(rc)
+        return tok, logits.view(np.uint32), [rt.state_back(b).view(np.uint32) for b in range(B)]
+
+    try:
+        for entry in ("greedy", "stop"):
+            want, got = run(entry, 1), run(entry, 1 | 2 << 8)
+            assert np.abs(want[2][0]).max() > 0
+            assert np.array_equal(got[0], want[0]), entry
+            assert np.array_equal(got[1], want[1]), entry
+            for b in range(B):
+                assert np.array_equal(got[2][b], want[2][b]), (entry, b)
+    finally:
+        rt.close()
+
+
 @pytest.mark.parametrize("B", [1, 3, 5])
 @pytest.mark.parametrize("mat", ["Q5_K", "Q8_0"])
 def test_v6_fused_decode_matches_op_by_op_and_oracle(ctx, B, mat):

@@ -1,7 +1,7 @@
 // Host-side driver shared by the RWKV-7 and RWKV-6 runners (wrk_v7.hip, wrk_v6.hip): matmul launches, job validation, the
-// frame state both models carry, cached step programs, job upload / read-back and the timed decode loop.  A runner keeps what is
-// its own -- the scratch layout, enqueue_ops / enqueue_fused_decode, its graph-key bits -- and hands these functions a callback
-// that enqueues its launches.
+// frame state both models carry, cached step programs, job upload / read-back and the decode loops (wrk_generate,
+// wrk_generate_queue).  A runner keeps what is its own -- the scratch layout, enqueue_ops / enqueue_fused_decode, its graph-key
+// bits, its lanes -- behind the few virtual methods of wrk_frame_common.
 #pragma once
 #include <atomic>
 #include <functional>
@@ -80,8 +80,46 @@ int32_t wrk_job_check(wrk_ctx* ctx, const wrk_v7_state* st, const uint32_t* curs
                       const uint32_t* headers, uint32_t NH, wrk_job_shape* shape);
 int32_t wrk_score_check(wrk_ctx* ctx, const wrk_job_args& a, uint32_t V, const char* who);
 
+// What a step program of the decode loops is: how each sequence's next token is picked from head_o, and what follows the pick.
+// A filtered pick is a sampled one and a pool tail is a queue tail by construction; wrk_pick_pack sets `penalized` only with a sampled pick
+struct wrk_step_kind {
+    enum Pick : uint32_t { GREEDY, SAMPLED, FILTERED };         // arg-max / the sampler (wrk_sample.hip) on sample_par / the filtered sampler, also on filter_par
+    enum Tail : uint32_t { PLAIN, STOP, QUEUE, QUEUE_POOL };    // advance_tokens / wrk_stop.hip / wrk_queue.hip / the same with a state pool
+    Pick pick = GREEDY;
+    bool penalized = false;     // the pick is made on pen_o = head_o penalised with the occurrence rows of pen_par, which then count the draw (wrk_penalty.hip)
+    Tail tail = PLAIN;
+    bool sampled() const { return pick != GREEDY; }
+    bool filtered() const { return pick == FILTERED; }
+    bool queue() const { return tail == QUEUE || tail == QUEUE_POOL; }
+    bool pool() const { return tail == QUEUE_POOL; }
+    // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25, penalised 26, tail 27-28 -- above every flag of an
+    // infer job and of a runner's own (wrk_frame_common::key_bits, all below bit 24, ORed into the same word)
+    uint32_t key() const { return (uint32_t)pick << 24 | (uint32_t)penalized << 26 | (uint32_t)tail << 27; }
+};
+
 // ------------------------------------------------------------------ frame state of a model (base of wrk_v7_model / wrk_v6_model)
 struct wrk_frame_common {
+    // ---- what the decode loops ask of a runner (host only: never passed to a kernel)
+    virtual ~wrk_frame_common() = default;
+    struct Facts { uint32_t num_vocab, num_emb, num_layer; bool has_emb; };    // has_emb: a device embedding table exists
+    virtual Facts facts() const = 0;
+    virtual wrk::FrameIo& io() = 0;
+    // the frame of B sequences and their header rows (RWKV-7, one sequence in mode 1: also the engine); drops the programs when it grows
+    virtual int32_t ensure_frame(uint32_t B, uint32_t mode) = 0;
+    // one decode step of sequences [b0, b0 + B) of `st`: embed io().tokens, run the layers and the head, then wrk_enqueue_pick
+    virtual int32_t enqueue_step(wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) = 0;
+    // the runner's bits of a step program's GraphKey::mode, all below bit 24
+    virtual uint32_t key_bits(uint32_t B, uint32_t mode) const { return mode; }
+    // concurrent pipelines: how many the runner can run, and the frame of lane g of `groups` (lane 0 is the runner itself); the loop
+    // replays lane g on lane_streams[g] and joins it through lane_events[g], which a runner of several lanes creates with the lane
+    virtual uint32_t max_lanes() const { return 1; }
+    virtual int32_t lane(uint32_t g, uint32_t groups, wrk_frame_common** out) { *out = this; return WRK_OK; }
+    std::vector<hipStream_t> lane_streams;
+    std::vector<hipEvent_t> lane_events;
+    // around the timed loop of lanes [0, groups), on lane 0
+    virtual void before_loop() {}
+    virtual int32_t after_loop(uint32_t groups) { return WRK_OK; }
+
     wrk_ctx* ctx = nullptr;
     void* scratch = nullptr;
     uint32_t scratch_tokens = 0, scratch_headers = 0;
@@ -168,25 +206,9 @@ int32_t wrk_job_upload(wrk_frame_common& f, wrk::FrameIo& io, void* input, const
 int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t V, const wrk_job_args& a);
 
 // ------------------------------------------------------------------ the decode loops (generate_greedy ... generate_queue)
-// What a step program of the decode loops is: how each sequence's next token is picked from head_o, and what follows the pick.
-// A filtered pick is a sampled one and a pool tail is a queue tail by construction; wrk_pick_pack sets `penalized` only with a sampled pick
-struct wrk_step_kind {
-    enum Pick : uint32_t { GREEDY, SAMPLED, FILTERED };         // arg-max / the sampler (wrk_sample.hip) on sample_par / the filtered sampler, also on filter_par
-    enum Tail : uint32_t { PLAIN, STOP, QUEUE, QUEUE_POOL };    // advance_tokens / wrk_stop.hip / wrk_queue.hip / the same with a state pool
-    Pick pick = GREEDY;
-    bool penalized = false;     // the pick is made on pen_o = head_o penalised with the occurrence rows of pen_par, which then count the draw (wrk_penalty.hip)
-    Tail tail = PLAIN;
-    bool sampled() const { return pick != GREEDY; }
-    bool filtered() const { return pick == FILTERED; }
-    bool queue() const { return tail == QUEUE || tail == QUEUE_POOL; }
-    bool pool() const { return tail == QUEUE_POOL; }
-    // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25, penalised 26, tail 27-28 -- above every flag of an
-    // infer job and of a runner's own (a runner ORs its mode and flags, all below bit 24, into the same word)
-    uint32_t key() const { return (uint32_t)pick << 24 | (uint32_t)penalized << 26 | (uint32_t)tail << 27; }
-};
-
-// the ABI's pick arrays, of wrk_generate_options / wrk_queue_options (wrk_pick_of) or of an entry point's own arguments.  need: what
-// the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
+// the ABI's pick arrays, of wrk_generate_options / wrk_queue_options (wrk_pick_of) or of an entry point's own arguments, validated in
+// one place (WRK_E_ARG): all three sampler arrays or none (the arg-max); penalty arrays only with a table; a table or a filter only
+// with the sampler arrays.  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
 struct wrk_pick_args {
     const float *temperature = nullptr, *top_p = nullptr; const uint32_t* seed = nullptr;
     const float *presence = nullptr, *frequency = nullptr, *decay = nullptr; wrk_occurrence* occ = nullptr;
@@ -196,70 +218,27 @@ struct wrk_pick_args {
 template <class Options> wrk_pick_args wrk_pick_of(const Options& o) {
     return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p};
 }
-struct wrk_pick_params {    // validated rows; empty: the arg-max / without penalties / without filters
-    std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
-};
-// The one validation of the pick arrays (WRK_E_ARG): all three sampler arrays or none (the arg-max); penalty arrays only with a table;
-// a table or a filter only with the sampler arrays.  Sets kind.pick / kind.penalized and packs `n` rows; penalty row r names slot r of
-// the table for r < slots (the table must have `slots`), slot 0 beyond: the queue keeps only the values of its request rows
-int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, uint32_t slots, uint32_t V, wrk_pick_params& out, wrk_step_kind& kind);
-// a stop-set CSR over n owners ("sequence", "request") validated into rows [n] (ids, count); both arrays NULL: all empty
-int32_t wrk_stop_sets(wrk_ctx* ctx, const uint32_t* tokens, const uint32_t* offsets, uint32_t n, uint32_t V, const char* owner,
-                      std::vector<wrk::StopParam>& rows);
-int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, uint32_t num_emb, uint32_t num_layer, uint32_t V,
-                           const uint32_t* first_tokens, uint32_t B);
 bool wrk_no_graph();        // WRK_NO_GRAPH=1: the decode loops enqueue every step instead of replaying a program
-// after the model's ensure_scratch: history / parameter buffers, then cursors, header rows, first_tokens [b0, b0 + B) and rows
-// [b0, b0 + B) of `rows` for sequences [b0, b0 + B), and a zero step counter
-int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps,
-                           const wrk_pick_params& rows);
 // Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the penalise launch (penalised), the arg-max
 // or sampler launch on the frame's parameters at step *counter -- neither with `argmax_done`: the head launch has left the arg-max in
-// io.argmax (RWKV-7's fused greedy head) -- then the tail: the occurrence update that belongs to it (penalised), its advance of tokens /
-// history / counter, and stop_snapshot / queue_reset / queue_turnover
-int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0,
-                         bool argmax_done);
+// io().argmax (RWKV-7's fused greedy head) -- then the tail: the occurrence update that belongs to it (penalised), its advance of
+// tokens / history / counter, and stop_snapshot / queue_reset / queue_turnover
+int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, bool argmax_done);
 
-// generate_queue: the options validated (WRK_E_ARG before any launch) into the request table, the prompt pool and the pick rows the slots
-// start with.  first_tokens [B]: p_0 of the requests dispatched at step 0, a valid id for the slots that start idle
-struct wrk_queue_pack {
-    uint32_t R = 0, max_steps = 0, poll_steps = 0;
-    wrk_step_kind kind{wrk_step_kind::GREEDY, false, wrk_step_kind::QUEUE};       // wrk_queue_pool_check: QUEUE_POOL
-    std::vector<wrk::QueueReq> reqs; std::vector<uint32_t> pool, first_tokens;
-    wrk_pick_params rows;       // [B]
-    const float* init_state = nullptr;
-    // with a state pool; start / save: [R] entries, QUEUE_NO_ENTRY for none
-    float* pool_states = nullptr;
-    uint32_t pool_entries = 0;
-    std::vector<uint32_t> start, save;
-    uint32_t* saved_out = nullptr;
-};
-int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
-                        wrk_queue_result* out, wrk_queue_pack& pk);
-// after wrk_queue_check: the pool of wrk_v*_generate_queue_pool validated into pk (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch)
-int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, const wrk_queue_options* opt, const wrk_v7_state* st, wrk_queue_pack& pk);
-// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): queue buffers of the
-// frame, the tables, the slots that start at step 0, live = R; then queue_reset of those slots on the submission stream (with a pool:
-// the pool's buffers and queue_turnover on the list of those slots)
-int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk_queue_pack& pk);
-// after the loop: the log and the history rows come back and the replies are cut out of them
-int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,
-                         wrk_queue_result* out);
-
-// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): stop buffers of
-// the frame, the B rows, zero just_ended, live = B
-int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk::StopParam* rows);
-
-// a pipeline of the timed replay: sequences [b0, b0 + nb) on their own frame; prog: its step program, or nullptr to enqueue eagerly
-struct wrk_lane { wrk::FrameIo* io; uint32_t* history; uint32_t b0, nb; wrk_program* prog; wrk_frame_common* frame = nullptr; };
-// generate_stop's loop: steps go out in blocks of poll_steps (0: WRK_STOP_POLL_DEFAULT), each followed by a copy of every lane's live
-// count to pinned memory and an event; before block k + 2 the host waits for block k's event and stops submitting once every count
-// is 0.  Then stop_restore, and lengths [B] / *steps_run come back.  Every lane carries its frame
-// queue: generate_queue's loop -- the live count is the queue's (requests not yet ended), nothing is restored and no lengths come back
-struct wrk_stop_run { wrk_v7_state* st; uint32_t poll_steps; uint32_t* out_lengths; uint32_t* steps_run; bool queue = false; };
-static constexpr uint32_t WRK_STOP_POLL_DEFAULT = 16;
-// `steps` steps of every lane between two events: one lane on the submission stream (eagerly through `eager_step` without a program),
-// several on streams[g], joined through events[g].  Then tokens [steps][B] and last logits [B][V] come back
-int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const std::vector<hipStream_t>& streams, const std::vector<hipEvent_t>& events,
-                      uint32_t B, uint32_t V, uint32_t steps, const std::function<int32_t()>& eager_step, uint32_t* out_tokens, float* last_logits,
-                      float* elapsed_ms, const wrk_stop_run* stop = nullptr);
+// wrk_v*_generate_greedy / _sample / _penalized, and with `stop` _stop: `steps` timed steps of sequences [0, B) of `st` on runner `m`,
+// dealt over the lanes that bits 8-15 of mode_arg ask for (clamped to [1, min(B, m->max_lanes())]; lane g owns sequences
+// [B g / groups, B (g + 1) / groups)).  Per lane, in this order -- growing a buffer drops the cached programs: ensure_frame, the
+// upload of tokens / cursors / pick rows, the stop buffers, the step program {state, B | b0 << 16, key_bits | kind.key()} (none with
+// WRK_NO_GRAPH=1: lane 0 enqueues every step).  Then tokens [steps][B] and last logits [B][V] come back.
+// stop: steps go out in blocks of poll_steps (0: 16), each followed by a copy of every lane's live count to pinned memory and an
+// event; before block k + 2 the host waits for block k's event and stops submitting once every count is 0.  Then stop_restore, and
+// lengths [B] / *steps_run come back
+struct wrk_stop_call { const wrk_generate_options* opt; uint32_t* out_lengths; uint32_t* steps_run; };
+int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                     const wrk_pick_args& pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,
+                     const wrk_stop_call* stop = nullptr);
+// wrk_v*_generate_queue (tail QUEUE) / _queue_pool (QUEUE_POOL): the stop call on one lane with the queue's tail and live count
+// (requests not yet ended); after the loop the log and the history rows come back and the replies are cut out of them
+int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                           const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail,
+                           const wrk_queue_pool* pool);

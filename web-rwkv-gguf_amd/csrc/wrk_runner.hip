@@ -1,6 +1,8 @@
 // Host-side driver shared by the RWKV-7 and RWKV-6 runners (wrk_runner.h).  No kernels here.
 #include "wrk_runner.h"
 
+#define LOCK(ctx) std::lock_guard<std::recursive_mutex> _lk((ctx)->mu)
+
 // ------------------------------------------------------------------ matmul launches
 wrk::MatJob wrk::mat_job(const wrk_matrix* m, DTensor in, DTensor out, uint32_t act) {
     wrk::MatJob j{m->data, m->aux, m->kind, m->flags, m->k, m->m, (uint32_t)m->row_bytes, in, out, act, 0};
@@ -241,8 +243,14 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
     return WRK_OK;
 }
 
-// ------------------------------------------------------------------ decode loop
-int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, uint32_t slots, uint32_t V, wrk_pick_params& out, wrk_step_kind& kind) {
+// ------------------------------------------------------------------ decode loops: validation and upload
+struct wrk_pick_params {    // validated rows; empty: the arg-max / without penalties / without filters
+    std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
+};
+
+// The one validation of the pick arrays (wrk_pick_args).  Sets kind.pick / kind.penalized and packs `n` rows; penalty row r names slot r
+// of the table for r < slots (the table must have `slots`), slot 0 beyond: the queue keeps only the values of its request rows
+static int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, uint32_t slots, uint32_t V, wrk_pick_params& out, wrk_step_kind& kind) {
     const int given = (a.temperature != nullptr) + (a.top_p != nullptr) + (a.seed != nullptr);
     WRK_ARG(ctx, given == 3 || (given == 0 && a.need == wrk_pick_args::ANY), "temperature, top_p and seed: all three arrays%s",
             a.need == wrk_pick_args::ANY ? ", or none for the arg-max" : "");
@@ -271,8 +279,9 @@ int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, uint32_t
     return rc;
 }
 
-int32_t wrk_stop_sets(wrk_ctx* ctx, const uint32_t* tokens, const uint32_t* off, uint32_t n, uint32_t V, const char* owner,
-                      std::vector<wrk::StopParam>& rows) {
+// a stop-set CSR over n owners ("sequence", "request") validated into rows [n] (ids, count); both arrays NULL: all empty
+static int32_t wrk_stop_sets(wrk_ctx* ctx, const uint32_t* tokens, const uint32_t* off, uint32_t n, uint32_t V, const char* owner,
+                               std::vector<wrk::StopParam>& rows) {
     WRK_ARG(ctx, !tokens || off, "stop_tokens without stop_offsets");
     rows.assign(n, wrk::StopParam{});
     if (!off) return WRK_OK;
@@ -296,26 +305,27 @@ bool wrk_no_graph() {
     return e && e[0] == '1';
 }
 
-int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, bool has_emb, uint32_t num_emb, uint32_t num_layer, uint32_t V,
-                           const uint32_t* first_tokens, uint32_t B) {
+static int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, const wrk_frame_common::Facts& m, const uint32_t* first_tokens, uint32_t B) {
     WRK_HIP(ctx, hipSetDevice(ctx->device));
-    WRK_ARG(ctx, has_emb, "generate_greedy needs the device embedding table");
+    WRK_ARG(ctx, m.has_emb, "generate_greedy needs the device embedding table");
     WRK_ARG(ctx, B >= 1 && B <= st->num_batch, "num_batch %u exceeds the state's %u", B, st->num_batch);
-    WRK_ARG(ctx, st->num_emb == num_emb && st->num_layer == num_layer, "state does not belong to this model");
-    for (uint32_t b = 0; b < B; ++b) WRK_ARG(ctx, first_tokens[b] < V, "first token %u out of vocab", first_tokens[b]);
+    WRK_ARG(ctx, st->num_emb == m.num_emb && st->num_layer == m.num_layer, "state does not belong to this model");
+    for (uint32_t b = 0; b < B; ++b) WRK_ARG(ctx, first_tokens[b] < m.num_vocab, "first token %u out of vocab", first_tokens[b]);
     return WRK_OK;
 }
 
-int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps,
-                           const wrk_pick_params& rows) {
+// after the runner's ensure_frame: history / parameter buffers, then cursors, header rows, first_tokens [b0, b0 + B) and rows
+// [b0, b0 + B) of `rows` for sequences [b0, b0 + B), and a zero step counter
+static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps, const wrk_pick_params& rows) {
     wrk_ctx* ctx = f.ctx;
+    wrk::FrameIo& io = f.io();
     const wrk::SampleParam* par = rows.par.empty() ? nullptr : rows.par.data() + b0;
     const wrk::PenaltyParam* pen = rows.pen.empty() ? nullptr : rows.pen.data() + b0;
     const wrk::SampleFilter* filt = rows.filt.empty() ? nullptr : rows.filt.data() + b0;
     int32_t rc = f.ensure_history((size_t)steps * B);
     if (rc == WRK_OK && par) rc = f.ensure_sample_params(B);
     if (rc == WRK_OK && filt) rc = f.ensure_filter_params(B);
-    if (rc == WRK_OK && pen) rc = f.ensure_penalty(B, V);
+    if (rc == WRK_OK && pen) rc = f.ensure_penalty(B, f.facts().num_vocab);
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
@@ -332,9 +342,11 @@ int32_t wrk_decode_prepare(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, co
 }
 
 // ------------------------------------------------------------------ stop tokens (wrk_stop.hip)
-int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk::StopParam* rows) {
+// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): stop buffers of
+// the frame, the B rows, zero just_ended, live = B
+static int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t B, const wrk::StopParam* rows) {
     wrk_ctx* ctx = f.ctx;
-    int32_t rc = f.ensure_stop(B, st->num_layer, st->head_size, st->num_emb, V);
+    int32_t rc = f.ensure_stop(B, st->num_layer, st->head_size, st->num_emb, f.facts().num_vocab);
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> flags(f.stop_cap + 1, 0u);      // just_ended = 0, then the live count
     flags[f.stop_cap] = B;
@@ -352,8 +364,23 @@ static int32_t queue_csr_check(wrk_ctx* ctx, const uint32_t* off, uint32_t R, co
     return WRK_OK;
 }
 
-int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
-                        wrk_queue_result* out, wrk_queue_pack& pk) {
+// generate_queue: the options validated (WRK_E_ARG before any launch) into the request table, the prompt pool and the pick rows the slots
+// start with.  first_tokens [B]: p_0 of the requests dispatched at step 0, a valid id for the slots that start idle
+struct wrk_queue_pack {
+    uint32_t R = 0, max_steps = 0, poll_steps = 0;
+    wrk_step_kind kind{wrk_step_kind::GREEDY, false, wrk_step_kind::QUEUE};       // wrk_queue_pool_check: QUEUE_POOL
+    std::vector<wrk::QueueReq> reqs; std::vector<uint32_t> pool, first_tokens;
+    wrk_pick_params rows;       // [B]
+    const float* init_state = nullptr;
+    // with a state pool; start / save: [R] entries, QUEUE_NO_ENTRY for none
+    float* pool_states = nullptr;
+    uint32_t pool_entries = 0;
+    std::vector<uint32_t> start, save;
+    uint32_t* saved_out = nullptr;
+};
+
+static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
+                               wrk_queue_result* out, wrk_queue_pack& pk) {
     WRK_ARG(ctx, opt, "options required");
     WRK_ARG(ctx, out && out->lengths && out->reasons && out->slots && out->start_steps && out->out_tokens && out->steps_run,
             "every result array is required");
@@ -413,7 +440,8 @@ int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7
     return WRK_OK;
 }
 
-int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, const wrk_queue_options* opt, const wrk_v7_state* st, wrk_queue_pack& pk) {
+// after wrk_queue_check: the pool of wrk_v*_generate_queue_pool validated into pk (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch)
+static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, const wrk_queue_options* opt, const wrk_v7_state* st, wrk_queue_pack& pk) {
     WRK_ARG(ctx, pool, "pool required");
     WRK_ARG(ctx, pool->states, "%s", pool->start || pool->save ? "start / save entries without a pool buffer" : "the pool has no buffer");
     const uint32_t R = pk.R, P = pool->num_entries;
@@ -466,8 +494,12 @@ static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V
     return wrk::QueueGeom{st->data, st->num_layer, st->num_batch, b0, V, (size_t)(st->head_size + 2) * st->num_emb};
 }
 
-int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t V, uint32_t B, const wrk_queue_pack& pk) {
+// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): queue buffers of the
+// frame, the tables, the slots that start at step 0, live = R; then queue_reset of those slots on the submission stream (with a pool:
+// the pool's buffers and queue_turnover on the list of those slots)
+static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t B, const wrk_queue_pack& pk) {
     wrk_ctx* ctx = f.ctx;
+    const uint32_t V = f.facts().num_vocab;
     int32_t rc = f.ensure_queue(B, pk.R, pk.pool.size());
     if (rc == WRK_OK && pk.kind.pool()) rc = f.ensure_queue_states(B, pk.R);
     if (rc != WRK_OK) return rc;
@@ -509,8 +541,10 @@ int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t 
 // tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
 // token (penalised), advance_queue, queue_reset of slots [b0, b0 + B) of `st`; with a pool advance_queue_pool and queue_turnover,
 // launch for launch
-static int32_t enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
+static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
     hipStream_t q = f.ctx->op_stream();
+    const wrk::FrameIo& io = f.io();
+    const uint32_t V = f.facts().num_vocab;
     if (!f.queue_ctl || B > f.queue_slot_cap || b0 != 0 || B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
     if (kind.pool() && (!f.queue_state_ctl || B > f.queue_turn_cap || ((size_t)(st->head_size + 2) * st->num_emb) % 4 != 0))
         return wrk_fail(f.ctx, WRK_E_ARG, "state pool buffers are not prepared");
@@ -526,8 +560,9 @@ static int32_t enqueue_queue_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_
     return WRK_OK;
 }
 
-int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,
-                         wrk_queue_result* out) {
+// after the loop: the log and the history rows come back and the replies are cut out of them
+static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,
+                                wrk_queue_result* out) {
     wrk_ctx* ctx = f.ctx;
     std::vector<wrk::QueueLog> log(pk.R);
     std::vector<uint32_t> hist((size_t)steps_run * B);
@@ -553,29 +588,32 @@ int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, co
     return WRK_OK;
 }
 
-static wrk::StopGeom stop_geom(const wrk_frame_common& f, const wrk::FrameIo& io, const wrk_v7_state* st, uint32_t b0, uint32_t V) {
+static wrk::StopGeom stop_geom(wrk_frame_common& f, const wrk_v7_state* st, uint32_t b0) {
+    const wrk::FrameIo& io = f.io();
     wrk::StopGeom g{};
     g.state = st->data; g.head_o = io.head_o; g.snap_state = f.stop_snap_state; g.snap_logits = f.stop_snap_logits;
     g.just_ended = f.stop_just_ended(); g.par = f.stop_par; g.counter = io.counter; g.lengths = f.stop_lengths();
-    g.layers = st->num_layer; g.num_batch = st->num_batch; g.b0 = b0; g.v = V;
+    g.layers = st->num_layer; g.num_batch = st->num_batch; g.b0 = b0; g.v = f.facts().num_vocab;
     g.slot = (size_t)(st->head_size + 2) * st->num_emb;
     return g;
 }
 
 // tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
 // (penalised), advance_stop, stop_snapshot of sequences [b0, b0 + B) of `st`
-static int32_t enqueue_stop_tail(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
+static int32_t enqueue_stop_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
     hipStream_t q = f.ctx->op_stream();
+    const wrk::FrameIo& io = f.io();
     if (!f.stop_par || B > f.stop_cap || b0 + B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
-    if (kind.penalized) wrk::occurrence_update_live(q, V, B, f.pen_par, io.argmax, f.stop_par);
+    if (kind.penalized) wrk::occurrence_update_live(q, f.facts().num_vocab, B, f.pen_par, io.argmax, f.stop_par);
     wrk::advance_stop(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(), B);
-    wrk::stop_snapshot(q, stop_geom(f, io, st, b0, V), B, f.ctx->num_cu);
+    wrk::stop_snapshot(q, stop_geom(f, st, b0), B, f.ctx->num_cu);
     return WRK_OK;
 }
 
-int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0,
-                         bool argmax_done) {
+int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, bool argmax_done) {
     hipStream_t q = f.ctx->op_stream();
+    const wrk::FrameIo& io = f.io();
+    const uint32_t V = f.facts().num_vocab;
     const float* logits = io.head_o;
     if (kind.penalized) {
         wrk::penalize_rows(q, io.head_o, V, V, B, f.pen_par, f.pen_o, V);
@@ -588,17 +626,48 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, wrk::FrameIo& io, uint32_t V, uint
     else if ((kind.filtered() ? wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax)
                               : wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax)) != 0)
         return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
-    if (kind.queue()) return enqueue_queue_tail(f, io, V, B, kind, st, b0);
-    if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, io, V, B, kind, st, b0);
+    if (kind.queue()) return enqueue_queue_tail(f, B, kind, st, b0);
+    if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, B, kind, st, b0);
     if (kind.penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
     wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);
     return WRK_OK;
 }
 
-int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const std::vector<hipStream_t>& streams, const std::vector<hipEvent_t>& events,
-                      uint32_t B, uint32_t V, uint32_t steps, const std::function<int32_t()>& eager_step, uint32_t* out_tokens, float* last_logits,
-                      float* elapsed_ms, const wrk_stop_run* stop) {
+// ------------------------------------------------------------------ decode loops: lanes and the timed replay
+// a pipeline of the timed replay: sequences [b0, b0 + nb) on their own frame; prog: its step program, or nullptr to enqueue eagerly
+struct wrk_lane { wrk_frame_common* frame; uint32_t b0, nb; wrk_program* prog; };
+// of a stop or queue call (kind.tail != PLAIN): what the polled loop cannot derive from the lanes and the kind
+struct wrk_stop_run { uint32_t poll_steps; uint32_t* out_lengths; uint32_t* steps_run; };
+static constexpr uint32_t WRK_STOP_POLL_DEFAULT = 16;
+
+// Part 1 of a decode loop on lane `ln`: the frame, the upload of tokens / cursors / pick rows of its sequences, the buffers of the tail
+// (stop: the call's stop rows, queue: its tables -- whichever kind.tail names) and, unless WRK_NO_GRAPH=1, the cached step program.
+// Every ensure_* comes before the look-up: growing a buffer drops the programs.  One program per (state, first sequence, B, the runner's
+// key bits, step kind): the analogue of the reference's cached RnnJob for a repeated RnnInfo
+static int32_t lane_prepare(wrk_lane& ln, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t steps, uint32_t mode, wrk_step_kind kind,
+                            const wrk_pick_params& rows, const wrk::StopParam* stop, const wrk_queue_pack* queue) {
+    wrk_frame_common& f = *ln.frame;
+    const uint32_t b0 = ln.b0, B = ln.nb;
+    int32_t rc = f.ensure_frame(B, mode);
+    if (rc == WRK_OK) rc = wrk_decode_prepare(f, first_tokens, b0, B, steps, rows);
+    if (rc == WRK_OK && kind.tail == wrk_step_kind::STOP) rc = wrk_stop_prepare(f, st, B, stop + b0);
+    if (rc == WRK_OK && kind.queue()) rc = wrk_queue_prepare(f, st, B, *queue);
+    ln.prog = nullptr;
+    if (rc != WRK_OK || wrk_no_graph()) return rc;
+    const wrk_frame_common::GraphKey key{st->uid, B | (b0 << 16), f.key_bits(B, mode) | kind.key()};
+    return wrk_cached_program(f.ctx, f.graphs, key, [&] { return f.enqueue_step(st, b0, B, mode, kind); }, &ln.prog);
+}
+
+// `steps` steps of every lane between two events: one lane on the submission stream (enqueued step by step without a program), several
+// on lane 0's lane_streams[g], joined through lane_events[g].  A stop or queue tail: the polled loop of wrk_generate's comment on the
+// tail's live count, then stop_restore and the lengths (stop).  Then tokens [steps][B] and last logits [B][V] come back
+static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, wrk_v7_state* st, uint32_t B, uint32_t steps, uint32_t mode,
+                             wrk_step_kind kind, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, const wrk_stop_run& stop) {
     const size_t groups = lanes.size();
+    const bool polled = kind.tail != wrk_step_kind::PLAIN;
+    const std::vector<hipStream_t>& streams = lanes[0].frame->lane_streams;
+    const std::vector<hipEvent_t>& events = lanes[0].frame->lane_events;
+    const uint32_t V = lanes[0].frame->facts().num_vocab;
     // every early return below leaves through this guard: the timing events are destroyed and, after an error, the lane streams are
     // drained (a lane's queued step programs must not outlive a frame that the next call may reallocate)
     struct Guard {
@@ -612,11 +681,16 @@ int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const st
     WRK_HIP(ctx, hipEventCreate(&guard.e0));
     WRK_HIP(ctx, hipEventCreate(&guard.e1));
     hipEvent_t e0 = guard.e0, e1 = guard.e1;
+    auto step = [&]() -> int32_t {      // one step of every lane
+        if (groups == 1 && !lanes[0].prog) return lanes[0].frame->enqueue_step(st, 0, B, mode, kind);
+        for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipGraphLaunch(lanes[g].prog->exec, groups == 1 ? ctx->stream : streams[g]));
+        return WRK_OK;
+    };
     uint32_t* live_host = nullptr;
     hipEvent_t* poll_events = nullptr;
-    if (stop) {
+    if (polled) {
         for (const wrk_lane& ln : lanes)
-            if (!ln.frame || !(stop->queue ? (void*)ln.frame->queue_ctl : (void*)ln.frame->stop_par))
+            if (!(kind.queue() ? (void*)ln.frame->queue_ctl : (void*)ln.frame->stop_par))
                 return wrk_fail(ctx, WRK_E_ARG, "stop run on a lane without stop buffers");
         const int32_t rc = lanes[0].frame->ensure_poll((uint32_t)groups);
         if (rc != WRK_OK) return rc;
@@ -624,10 +698,12 @@ int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const st
         poll_events = lanes[0].frame->poll_events.data();
     }
     WRK_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    if (stop) {
-        const uint32_t poll = stop->poll_steps ? stop->poll_steps : WRK_STOP_POLL_DEFAULT;
-        if (groups > 1)
-            for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipStreamWaitEvent(streams[g], e0, 0));
+    // several lanes: every lane replays its own step program on its own stream; the lanes start together behind e0 and the submission
+    // stream joins them all before e1
+    if (groups > 1)
+        for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipStreamWaitEvent(streams[g], e0, 0));
+    if (polled) {
+        const uint32_t poll = stop.poll_steps ? stop.poll_steps : WRK_STOP_POLL_DEFAULT;
         uint32_t run = 0;
         for (uint32_t k = 0; run < steps; ++k) {
             if (k >= 2) {       // block k - 2 has been followed by a whole block of queued work: the wait is an event wait, short or none
@@ -640,70 +716,127 @@ int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, const st
             }
             const uint32_t n = steps - run < poll ? steps - run : poll;
             for (uint32_t i = 0; i < n; ++i) {
-                if (groups == 1 && !lanes[0].prog) {
-                    const int32_t rc = eager_step();
-                    if (rc != WRK_OK) return rc;
-                    continue;
-                }
-                for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipGraphLaunch(lanes[g].prog->exec, groups == 1 ? ctx->stream : streams[g]));
+                const int32_t rc = step();
+                if (rc != WRK_OK) return rc;
             }
             run += n;
             for (size_t g = 0; g < groups; ++g) {
                 hipStream_t ls = groups == 1 ? ctx->stream : streams[g];
-                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, stop->queue ? lanes[g].frame->queue_live() : lanes[g].frame->stop_live(), 4,
+                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, kind.queue() ? lanes[g].frame->queue_live() : lanes[g].frame->stop_live(), 4,
                                             hipMemcpyDeviceToHost, ls));
                 WRK_HIP(ctx, hipEventRecord(poll_events[(k & 1) * groups + g], ls));
             }
         }
         steps = run;
-        if (groups > 1)
-            for (size_t g = 0; g < groups; ++g) {
-                WRK_HIP(ctx, hipEventRecord(events[g], streams[g]));
-                WRK_HIP(ctx, hipStreamWaitEvent(ctx->stream, events[g], 0));
-            }
-    } else if (groups == 1) {
-        for (uint32_t i = 0; i < steps; ++i) {
-            if (lanes[0].prog) WRK_HIP(ctx, hipGraphLaunch(lanes[0].prog->exec, ctx->stream));
-            else {
-                const int32_t rc = eager_step();
-                if (rc != WRK_OK) return rc;
-            }
-        }
     } else {
-        // every lane replays its own step program on its own stream; the lanes start together behind e0 and the submission
-        // stream joins them all before e1
-        for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipStreamWaitEvent(streams[g], e0, 0));
-        for (uint32_t i = 0; i < steps; ++i)
-            for (size_t g = 0; g < groups; ++g) WRK_HIP(ctx, hipGraphLaunch(lanes[g].prog->exec, streams[g]));
+        for (uint32_t i = 0; i < steps; ++i) {
+            const int32_t rc = step();
+            if (rc != WRK_OK) return rc;
+        }
+    }
+    if (groups > 1)
         for (size_t g = 0; g < groups; ++g) {
             WRK_HIP(ctx, hipEventRecord(events[g], streams[g]));
             WRK_HIP(ctx, hipStreamWaitEvent(ctx->stream, events[g], 0));
         }
-    }
     WRK_HIP(ctx, hipEventRecord(e1, ctx->stream));
     WRK_HIP(ctx, hipEventSynchronize(e1));
     float ms = 0.0f;
     WRK_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
     if (elapsed_ms) *elapsed_ms = ms;
-    if (stop && stop->queue) *stop->steps_run = steps;
-    else if (stop) {
+    if (kind.tail == wrk_step_kind::STOP) {
         // the frozen slots and logits rows go back (head_o is what the read-back below takes), the lengths come out
         for (const wrk_lane& ln : lanes) {
-            wrk::stop_restore(ctx->stream, stop_geom(*ln.frame, *ln.io, stop->st, ln.b0, V), ln.nb, ctx->num_cu);
-            WRK_HIP(ctx, hipMemcpyAsync(stop->out_lengths + ln.b0, ln.frame->stop_lengths(), (size_t)ln.nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+            wrk::stop_restore(ctx->stream, stop_geom(*ln.frame, st, ln.b0), ln.nb, ctx->num_cu);
+            WRK_HIP(ctx, hipMemcpyAsync(stop.out_lengths + ln.b0, ln.frame->stop_lengths(), (size_t)ln.nb * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
         WRK_LAUNCH_CHECK(ctx);
-        *stop->steps_run = steps;
     }
+    if (polled) *stop.steps_run = steps;
     for (const wrk_lane& ln : lanes) {
         if (out_tokens) {
-            if (groups == 1) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.history, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
-            else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)B * 4, ln.history, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
+            if (groups == 1) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.frame->history, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
+            else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)B * 4, ln.frame->history, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
                                                hipMemcpyDeviceToHost, ctx->stream));
         }
-        if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits + (size_t)ln.b0 * V, ln.io->head_o, (size_t)ln.nb * V * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits + (size_t)ln.b0 * V, ln.frame->io().head_o, (size_t)ln.nb * V * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     guard.ok = true;
     return WRK_OK;
+}
+
+// ------------------------------------------------------------------ decode loops: the two calls
+int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
+                     const wrk_pick_args& pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,
+                     const wrk_stop_call* stop) {
+    if (!ctx) return WRK_E_ARG;
+    LOCK(ctx);
+    if (stop) {
+        WRK_ARG(ctx, stop->opt, "options required");
+        WRK_ARG(ctx, stop->out_lengths && stop->steps_run, "out_lengths and steps_run are required");
+    }
+    if (!m || !st || !first_tokens) return WRK_E_ARG;
+    const uint32_t V = m->facts().num_vocab;
+    wrk_step_kind kind;
+    kind.tail = stop ? wrk_step_kind::STOP : wrk_step_kind::PLAIN;
+    wrk_pick_params rows;
+    std::vector<wrk::StopParam> stop_rows;      // generate_stop: one row per sequence
+    int32_t rc = wrk_pick_pack(ctx, pick, B, B, V, rows, kind);
+    if (rc == WRK_OK && stop) rc = wrk_stop_sets(ctx, stop->opt->stop_tokens, stop->opt->stop_offsets, B, V, "sequence", stop_rows);
+    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), first_tokens, B);
+    if (rc != WRK_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0f;
+    if (stop) {
+        *stop->steps_run = 0;
+        for (uint32_t b = 0; b < B; ++b) stop->out_lengths[b] = 0;
+    }
+    if (steps == 0) return WRK_OK;
+    // mode: bits 0-7 = 0 op-by-op / 1 fused; bits 8-15 = number of concurrent pipelines the sequences are dealt over (0, 1: one)
+    const uint32_t mode = mode_arg & 0xffu;
+    uint32_t groups = (mode_arg >> 8) & 0xffu;
+    if (groups > m->max_lanes()) groups = m->max_lanes();
+    if (groups < 1) groups = 1;
+    if (groups > B) groups = B;
+    WRK_ARG(ctx, groups == 1 || !wrk_no_graph(), "concurrent pipelines replay captured programs: not with WRK_NO_GRAPH=1");
+    m->before_loop();
+    std::vector<wrk_lane> L(groups);
+    for (uint32_t g = 0; g < groups; ++g) {
+        rc = m->lane(g, groups, &L[g].frame);
+        if (rc != WRK_OK) return rc;
+        L[g].b0 = (uint32_t)((uint64_t)B * g / groups);
+        L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
+        // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
+        rc = lane_prepare(L[g], st, first_tokens, steps, mode, kind, rows, stop_rows.data(), nullptr);
+        if (rc != WRK_OK) return rc;
+    }
+    const wrk_stop_run run{stop ? stop->opt->poll_steps : 0u, stop ? stop->out_lengths : nullptr, stop ? stop->steps_run : nullptr};
+    rc = wrk_run_lanes(ctx, L, st, B, steps, mode, kind, out_tokens, last_logits, elapsed_ms, run);
+    if (rc != WRK_OK) return rc;
+    return m->after_loop(groups);
+}
+
+int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                           const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail,
+                           const wrk_queue_pool* pool) {
+    if (!ctx || !m || !st) return WRK_E_ARG;
+    LOCK(ctx);
+    wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
+    wrk_queue_pack pk;
+    int32_t rc = wrk_queue_check(ctx, opt, st, B, m->facts().num_vocab, mode_arg, out_arg ? &out : nullptr, pk);
+    if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, pk);
+    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), pk.first_tokens.data(), B);
+    if (rc != WRK_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0f;
+    const uint32_t mode = mode_arg & 0xffu;
+    m->before_loop();
+    std::vector<wrk_lane> L{{nullptr, 0, B, nullptr}};      // one lane: a queue shared by several streams would need cross-stream atomics
+    rc = m->lane(0, 1, &L[0].frame);
+    if (rc == WRK_OK) rc = lane_prepare(L[0], st, pk.first_tokens.data(), pk.max_steps, mode, pk.kind, pk.rows, nullptr, &pk);
+    if (rc != WRK_OK) return rc;
+    uint32_t steps_run = 0;
+    rc = wrk_run_lanes(ctx, L, st, B, pk.max_steps, mode, pk.kind, nullptr, nullptr, elapsed_ms, wrk_stop_run{pk.poll_steps, nullptr, &steps_run});
+    if (rc == WRK_OK) rc = m->after_loop(1);
+    if (rc != WRK_OK) return rc;
+    return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
 }

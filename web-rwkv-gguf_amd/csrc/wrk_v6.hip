@@ -21,6 +21,12 @@ struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, key
     std::vector<wrk_v6_layer_desc> layers;
     V6Scratch s{};
 
+    // the runner interface of the decode loops (wrk_runner.h): one lane, no key bits but the mode, nothing around the loop
+    Facts facts() const override { return {d.num_vocab, d.num_emb, d.num_layer, d.emb_f16 != nullptr}; }
+    wrk::FrameIo& io() override { return s; }
+    int32_t ensure_frame(uint32_t B, uint32_t) override { return ensure_scratch(B, B); }
+    int32_t enqueue_step(wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) override;
+
     int32_t ensure_scratch(uint32_t T, uint32_t NH);
     int32_t enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity, bool merged = false);
     int32_t enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity, uint32_t batch0);
@@ -619,60 +625,23 @@ int32_t wrk_v6_score(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint
     return v6_job(ctx, m, st, {tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank}, mode);
 }
 
-// one decode step of sequences [0, B): embed s.tokens, run the layers and the head, then wrk_enqueue_pick
-static int32_t v6_enqueue_step(wrk_v6_model* m, wrk_v7_state* st, uint32_t B, uint32_t mode, wrk_step_kind kind) {
-    wrk::gather_rows_f16(m->ctx->op_stream(), m->d.emb_f16->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
+}  // extern "C"
+
+// one decode step of sequences [0, B) (one lane: b0 is 0): embed s.tokens, run the layers and the head, then wrk_enqueue_pick
+int32_t wrk_v6_model::enqueue_step(wrk_v7_state* st, uint32_t, uint32_t B, uint32_t mode, wrk_step_kind kind) {
+    wrk::gather_rows_f16(ctx->op_stream(), d.emb_f16->ptr, s.tokens, s.input, d.num_emb, B);
     int32_t r = WRK_E_UNSUPPORTED;
-    if (mode == 1) r = m->enqueue_fused_decode(st, B, B, true, 0);
-    if (r == WRK_E_UNSUPPORTED) r = m->enqueue_ops(st, B, B, true);
+    if (mode == 1) r = enqueue_fused_decode(st, B, B, true, 0);
+    if (r == WRK_E_UNSUPPORTED) r = enqueue_ops(st, B, B, true);
     if (r != WRK_OK) return r;
-    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, kind, st, 0, false);
+    return wrk_enqueue_pick(*this, B, kind, st, 0, false);
 }
 
-// the loop of a prepared frame: the cached step program of `kind` (WRK_NO_GRAPH=1: every step enqueued), then wrk_run_lanes
-static int32_t v6_run(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, uint32_t steps, uint32_t mode, wrk_step_kind kind,
-                      uint32_t* out_tokens, float* last_logits, float* elapsed_ms, const wrk_stop_run* stop) {
-    auto enqueue_step = [&] { return v6_enqueue_step(m, st, B, mode, kind); };
-    std::vector<wrk_lane> lane{{&m->s, m->history, 0, B, nullptr, m}};
-    if (!wrk_no_graph()) {
-        const int32_t rc = wrk_cached_program(ctx, m->graphs, {st->uid, B, mode | kind.key()}, enqueue_step, &lane[0].prog);
-        if (rc != WRK_OK) return rc;
-    }
-    return wrk_run_lanes(ctx, lane, {}, {}, B, m->d.num_vocab, steps, enqueue_step, out_tokens, last_logits, elapsed_ms, stop);
-}
-
-// pick: the ABI's pick arrays (none: generate_greedy); stop_opt: generate_stop's options, with out_lengths and steps_run; mode is used as given
-static int32_t v6_generate(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
-                           const wrk_pick_args& pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode,
-                           const wrk_generate_options* stop_opt = nullptr, uint32_t* out_lengths = nullptr, uint32_t* steps_run = nullptr) {
-    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
-    LOCK(ctx);
-    const uint32_t V = m->d.num_vocab;
-    wrk_step_kind kind;
-    kind.tail = stop_opt ? wrk_step_kind::STOP : wrk_step_kind::PLAIN;
-    wrk_pick_params rows;
-    std::vector<wrk::StopParam> stop_rows;      // generate_stop: one row per sequence
-    int32_t rc = wrk_pick_pack(ctx, pick, B, B, V, rows, kind);
-    if (rc == WRK_OK && stop_opt) rc = wrk_stop_sets(ctx, stop_opt->stop_tokens, stop_opt->stop_offsets, B, V, "sequence", stop_rows);
-    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->d.emb_f16 != nullptr, m->d.num_emb, m->d.num_layer, V, first_tokens, B);
-    if (rc != WRK_OK) return rc;
-    if (elapsed_ms) *elapsed_ms = 0.0f;
-    if (stop_opt) {
-        *steps_run = 0;
-        for (uint32_t b = 0; b < B; ++b) out_lengths[b] = 0;
-    }
-    if (steps == 0) return WRK_OK;
-    rc = m->ensure_scratch(B, B);
-    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, V, first_tokens, 0, B, steps, rows);
-    if (rc == WRK_OK && stop_opt) rc = wrk_stop_prepare(*m, st, V, B, stop_rows.data());
-    if (rc != WRK_OK) return rc;
-    const wrk_stop_run stop_run{st, stop_opt ? stop_opt->poll_steps : 0u, out_lengths, steps_run};
-    return v6_run(ctx, m, st, B, steps, mode, kind, out_tokens, last_logits, elapsed_ms, stop_opt ? &stop_run : nullptr);
-}
+extern "C" {
 
 int32_t wrk_v6_generate_greedy(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                                uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode) {
-    return v6_generate(ctx, m, st, first_tokens, B, steps, wrk_pick_args{}, out_tokens, last_logits, elapsed_ms, mode);
+    return wrk_generate(ctx, m, st, first_tokens, B, steps, wrk_pick_args{}, out_tokens, last_logits, elapsed_ms, mode);
 }
 
 int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
@@ -680,7 +649,7 @@ int32_t wrk_v6_generate_sample(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, 
                                float* elapsed_ms, uint32_t mode) {
     wrk_pick_args pick{temperature, top_p, seed};
     pick.need = wrk_pick_args::SAMPLER;
-    return v6_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode);
+    return wrk_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode);
 }
 
 int32_t wrk_v6_generate_penalized(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
@@ -689,53 +658,24 @@ int32_t wrk_v6_generate_penalized(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* s
                                   float* elapsed_ms, uint32_t mode) {
     wrk_pick_args pick{temperature, top_p, seed, presence, frequency, decay, occ};
     pick.need = wrk_pick_args::TABLE;
-    return v6_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode);
+    return wrk_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode);
 }
 
 int32_t wrk_v6_generate_stop(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                              const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths, float* last_logits,
                              uint32_t* steps_run, float* elapsed_ms, uint32_t mode) {
-    if (!ctx) return WRK_E_ARG;
-    {
-        LOCK(ctx);
-        WRK_ARG(ctx, opt, "options required");
-        WRK_ARG(ctx, out_lengths && steps_run, "out_lengths and steps_run are required");
-    }
-    return v6_generate(ctx, m, st, first_tokens, B, steps, wrk_pick_of(*opt), out_tokens, last_logits, elapsed_ms, mode, opt, out_lengths, steps_run);
-}
-
-// generate_queue: as v6_generate's stop call, the queue tail in the stop tail's place (with a state pool: the pool tail)
-static int32_t v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
-                                 const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail, const wrk_queue_pool* pool) {
-    if (!ctx || !m || !st) return WRK_E_ARG;
-    LOCK(ctx);
-    const uint32_t V = m->d.num_vocab;
-    wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
-    wrk_queue_pack pk;
-    int32_t rc = wrk_queue_check(ctx, opt, st, B, V, mode_arg, out_arg ? &out : nullptr, pk);
-    if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, pk);
-    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->d.emb_f16 != nullptr, m->d.num_emb, m->d.num_layer, V, pk.first_tokens.data(), B);
-    if (rc != WRK_OK) return rc;
-    if (elapsed_ms) *elapsed_ms = 0.0f;
-    rc = m->ensure_scratch(B, B);
-    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, V, pk.first_tokens.data(), 0, B, pk.max_steps, pk.rows);
-    if (rc == WRK_OK) rc = wrk_queue_prepare(*m, st, V, B, pk);
-    if (rc != WRK_OK) return rc;
-    uint32_t steps_run = 0;
-    const wrk_stop_run run{st, pk.poll_steps, nullptr, &steps_run, true};
-    rc = v6_run(ctx, m, st, B, pk.max_steps, mode_arg & 0xffu, pk.kind, nullptr, nullptr, elapsed_ms, &run);
-    if (rc != WRK_OK) return rc;
-    return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
+    const wrk_stop_call stop{opt, out_lengths, steps_run};
+    return wrk_generate(ctx, m, st, first_tokens, B, steps, opt ? wrk_pick_of(*opt) : wrk_pick_args{}, out_tokens, last_logits, elapsed_ms, mode, &stop);
 }
 
 int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                               const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
-    return v6_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE, nullptr);
+    return wrk_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE, nullptr);
 }
 
 int32_t wrk_v6_generate_queue_pool(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                                    const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_pool* pool) {
-    return v6_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE_POOL, pool);
+    return wrk_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE_POOL, pool);
 }
 
 }  // extern "C"

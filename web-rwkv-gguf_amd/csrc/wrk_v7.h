@@ -37,17 +37,25 @@ struct wrk_v7_model : wrk_frame_common {
     // history and cached programs -- whose decode graphs are replayed on a stream of its own, so that several latency-bound
     // pipelines overlap on the GPU (independent sequences: separate state slices, no synchronisation between lanes)
     std::vector<wrk_v7_model*> lanes;
-    std::vector<hipStream_t> lane_streams;
-    std::vector<hipEvent_t> lane_events;
 
     // persistent batch-1 decode engine (wrk_v7_engine.hip): built on first use, nullptr when the model / device does not fit it
     struct wrk_v7_engine* engine = nullptr;
     bool engine_tried = false;
     bool engine_skip_once = false;      // wrk_v7_infer_layer: the frame buffers must be materialised -> launches (unless WRK_ENGINE_INSPECT=1)
-    bool engine_blocked = false;        // set while several pipelines share the GPU (generate_greedy with groups > 1)
+    bool engine_blocked = false;        // set by lane() while several pipelines share the GPU (groups > 1), cleared by the next call on one
     std::string engine_why;             // why the engine is not available (diagnostics)
     int32_t ensure_engine();            // outside captures; WRK_OK also when the engine is unavailable
     bool engine_on() const;             // WRK_ENGINE != 0 and the engine exists
+    // the runner interface of the decode loops (wrk_runner.h)
+    Facts facts() const override { return {d.num_vocab, d.num_emb, d.num_layer, emb != nullptr}; }
+    wrk::FrameIo& io() override { return s; }
+    int32_t ensure_frame(uint32_t B, uint32_t mode) override;
+    int32_t enqueue_step(wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) override;
+    uint32_t key_bits(uint32_t B, uint32_t mode) const override;
+    uint32_t max_lanes() const override { return 255; }
+    int32_t lane(uint32_t g, uint32_t groups, wrk_frame_common** out) override;
+    void before_loop() override;
+    int32_t after_loop(uint32_t groups) override;
     int32_t ensure_scratch(uint32_t T, uint32_t NH);
     int32_t enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity_headers, bool merged = false);
     // from_tokens: gather embedding rows of s.tokens on the device; want_argmax: greedy token per header row into

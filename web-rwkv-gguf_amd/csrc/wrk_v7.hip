@@ -615,118 +615,76 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
     return wrk_fail(ctx, WRK_E_ARG, "no frame buffer named %s", name);
 }
 
-// one decode step of sequences [b0, b0 + B) on frame `m`: embed s.tokens, run the layers and the head, then wrk_enqueue_pick.  The fused
+}  // extern "C"
+
+// one decode step of sequences [b0, b0 + B) on this frame: embed s.tokens, run the layers and the head, then wrk_enqueue_pick.  The fused
 // greedy head leaves the arg-max in s.argmax, and in a plain step advances tokens / history / counter itself: nothing follows it
-static int32_t enqueue_decode_step(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) {
+int32_t wrk_v7_model::enqueue_step(wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) {
     int32_t rc;
-    const bool fused = mode == 1 && m->act_dtype == WRK_F16, head_picks = fused && !kind.sampled(),
+    const bool fused = mode == 1 && act_dtype == WRK_F16, head_picks = fused && !kind.sampled(),
                head_advances = head_picks && kind.tail == wrk_step_kind::PLAIN;
-    if (fused) rc = m->enqueue_fused_decode(st, B, B, true, true, head_picks, head_advances, b0, true);
+    if (fused) rc = enqueue_fused_decode(st, B, B, true, true, head_picks, head_advances, b0, true);
     else {
-        wrk::gather_rows_f16(ctx->op_stream(), m->emb->ptr, m->s.tokens, m->s.input, m->d.num_emb, B);
-        rc = m->enqueue_ops(st, B, B, true);
+        wrk::gather_rows_f16(ctx->op_stream(), emb->ptr, s.tokens, s.input, d.num_emb, B);
+        rc = enqueue_ops(st, B, B, true);
     }
     if (rc != WRK_OK || head_advances) return rc;
-    return wrk_enqueue_pick(*m, m->s, m->d.num_vocab, B, kind, st, b0, head_picks);
+    return wrk_enqueue_pick(*this, B, kind, st, b0, head_picks);
 }
 
-// part 1 of a decode loop on model frame `m`: the frame, the upload of tokens / cursors / pick rows of sequences [b0, b0 + B) of the call,
-// the buffers of the tail (stop: the call's stop rows, queue: its tables -- whichever kind.tail names) and, unless `eager`, the cached
-// step program.  One program per (state, first sequence, B, mode, frame type, engine, split head, step kind): the analogue of the
-// reference's cached RnnJob for a repeated RnnInfo
-static int32_t decode_prepare(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t b0, uint32_t B,
-                              uint32_t steps, uint32_t mode, bool eager, wrk_step_kind kind, const wrk_pick_params& rows,
-                              const wrk::StopParam* stop, const wrk_queue_pack* queue, wrk_program** prog_out) {
-    int32_t rc = m->ensure_scratch(B, B);
-    if (rc == WRK_OK && B == 1 && mode == 1) rc = m->ensure_engine();
-    if (rc == WRK_OK) rc = wrk_decode_prepare(*m, m->s, m->d.num_vocab, first_tokens, b0, B, steps, rows);
-    if (rc == WRK_OK && kind.tail == wrk_step_kind::STOP) rc = wrk_stop_prepare(*m, st, m->d.num_vocab, B, stop + b0);
-    if (rc == WRK_OK && kind.queue()) rc = wrk_queue_prepare(*m, st, m->d.num_vocab, B, *queue);
-    *prog_out = nullptr;
-    if (rc != WRK_OK || eager) return rc;
-    const wrk_v7_model::GraphKey key{st->uid, B | (b0 << 16), mode | (m->act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && m->engine_on()) ? 8u : 0u) |
-                                                             (split_head_env_on() ? 0u : 16u) | kind.key()};
-    return wrk_cached_program(ctx, m->graphs, key, [&] { return enqueue_decode_step(ctx, m, st, b0, B, mode, kind); }, prog_out);
+int32_t wrk_v7_model::ensure_frame(uint32_t B, uint32_t mode) {
+    const int32_t rc = ensure_scratch(B, B);
+    return rc == WRK_OK && B == 1 && mode == 1 ? ensure_engine() : rc;
 }
 
-// pick: the ABI's pick arrays (none: generate_greedy); stop_opt: generate_stop's options, with out_lengths and steps_run
-static int32_t v7_generate(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
-                           const wrk_pick_args& pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,
-                           const wrk_generate_options* stop_opt = nullptr, uint32_t* out_lengths = nullptr, uint32_t* steps_run = nullptr) {
-    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
-    LOCK(ctx);
-    const uint32_t V = m->d.num_vocab;
-    wrk_step_kind kind;
-    kind.tail = stop_opt ? wrk_step_kind::STOP : wrk_step_kind::PLAIN;
-    wrk_pick_params rows;
-    std::vector<wrk::StopParam> stop_rows;      // generate_stop: one row per sequence
-    int32_t rc = wrk_pick_pack(ctx, pick, B, B, V, rows, kind);
-    if (rc == WRK_OK && stop_opt) rc = wrk_stop_sets(ctx, stop_opt->stop_tokens, stop_opt->stop_offsets, B, V, "sequence", stop_rows);
-    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->emb != nullptr, m->d.num_emb, m->d.num_layer, V, first_tokens, B);
-    if (rc != WRK_OK) return rc;
-    if (elapsed_ms) *elapsed_ms = 0.0f;
-    if (stop_opt) {
-        *steps_run = 0;
-        for (uint32_t b = 0; b < B; ++b) out_lengths[b] = 0;
-    }
-    if (steps == 0) return WRK_OK;
-    // mode: bits 0-7 = 0 op-by-op / 1 fused; bits 8-15 = number of concurrent pipelines the sequences are dealt over (0, 1: one)
-    const uint32_t mode = mode_arg & 0xffu;
-    uint32_t groups = (mode_arg >> 8) & 0xffu;
-    if (groups < 1) groups = 1;
-    if (groups > B) groups = B;
-    const bool eager = wrk_no_graph();
-    WRK_ARG(ctx, groups == 1 || !eager, "concurrent pipelines replay captured programs: not with WRK_NO_GRAPH=1");
-    wrk::timing_slot(ctx, nullptr);     // WRK_TIMING=1: allocate the stamp buffer outside the capture
+// mode, f32 frames (4), the engine (8), the unsplit head (16)
+uint32_t wrk_v7_model::key_bits(uint32_t B, uint32_t mode) const {
+    return mode | (act_dtype == WRK_F32 ? 4u : 0u) | ((B == 1 && mode == 1 && engine_on()) ? 8u : 0u) | (split_head_env_on() ? 0u : 16u);
+}
 
-    // lanes: lane 0 is this model's own frame; lanes 1.. are clones sharing the weight handles
-    while (m->lanes.size() + 1 < groups) {
-        wrk_v7_model* lane = nullptr;
-        rc = wrk_v7_model_create(ctx, &m->d, &lane);
+// lane 0 is this model's own frame; lanes 1.. are clones sharing the weight handles, created with their streams and events on demand
+int32_t wrk_v7_model::lane(uint32_t g, uint32_t groups, wrk_frame_common** out) {
+    while (lanes.size() + 1 < groups) {
+        wrk_v7_model* clone = nullptr;
+        const int32_t rc = wrk_v7_model_create(ctx, &d, &clone);
         if (rc != WRK_OK) return rc;
-        lane->act_dtype = m->act_dtype;
-        m->lanes.push_back(lane);
+        clone->act_dtype = act_dtype;
+        lanes.push_back(clone);
     }
-    while (m->lane_streams.size() < groups) {
-        hipStream_t s = nullptr;
+    while (lane_streams.size() < groups) {
+        hipStream_t ls = nullptr;
         hipEvent_t e = nullptr;
-        WRK_HIP(ctx, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        WRK_HIP(ctx, hipStreamCreateWithFlags(&ls, hipStreamNonBlocking));
         WRK_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        m->lane_streams.push_back(s);
-        m->lane_events.push_back(e);
+        lane_streams.push_back(ls);
+        lane_events.push_back(e);
     }
-    std::vector<wrk_lane> L(groups);
-    auto frame = [&](uint32_t g) { return g == 0 ? m : m->lanes[g - 1]; };
-    for (uint32_t g = 0; g < groups; ++g) {
-        wrk_v7_model* mdl = frame(g);
-        // the persistent engine needs every CU for itself: two of them side by side (one per lane) would each hold part of the chip
-        // and wait for the rest forever (until their bounded spins give up) -- concurrent pipelines keep the five-launch layer
-        mdl->engine_blocked = groups > 1;
-        L[g].b0 = (uint32_t)((uint64_t)B * g / groups);
-        L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
-        // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
-        rc = decode_prepare(ctx, mdl, st, first_tokens, L[g].b0, L[g].nb, steps, mode, eager, kind, rows, stop_rows.data(), nullptr, &L[g].prog);
-        if (rc != WRK_OK) return rc;
-        L[g].io = &mdl->s;
-        L[g].history = mdl->history;
-        L[g].frame = mdl;
-    }
-    const wrk_stop_run stop_run{st, stop_opt ? stop_opt->poll_steps : 0u, out_lengths, steps_run};
-    rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, steps, [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, kind); }, out_tokens,
-                       last_logits, elapsed_ms, stop_opt ? &stop_run : nullptr);
-    if (rc != WRK_OK) return rc;
+    wrk_v7_model* mdl = g == 0 ? this : lanes[g - 1];
+    // the persistent engine needs every CU for itself: two of them side by side (one per lane) would each hold part of the chip
+    // and wait for the rest forever (until their bounded spins give up) -- concurrent pipelines keep the five-launch layer
+    mdl->engine_blocked = groups > 1;
+    *out = mdl;
+    return WRK_OK;
+}
+
+void wrk_v7_model::before_loop() { wrk::timing_slot(ctx, nullptr); }     // WRK_TIMING=1: allocate the stamp buffer outside the capture
+
+int32_t wrk_v7_model::after_loop(uint32_t groups) {
     wrk::timing_report(ctx);
     for (uint32_t g = 0; g < groups; ++g) {
-        wrk_v7_engine_report(frame(g)->engine);
-        rc = wrk_v7_engine_check(frame(g)->engine);
+        wrk_v7_engine* e = (g == 0 ? this : lanes[g - 1])->engine;
+        wrk_v7_engine_report(e);
+        const int32_t rc = wrk_v7_engine_check(e);
         if (rc != WRK_OK) return rc;
     }
     return WRK_OK;
 }
 
+extern "C" {
+
 int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B,
                                uint32_t steps, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg) {
-    return v7_generate(ctx, m, st, first_tokens, B, steps, wrk_pick_args{}, out_tokens, last_logits, elapsed_ms, mode_arg);
+    return wrk_generate(ctx, m, st, first_tokens, B, steps, wrk_pick_args{}, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
@@ -734,7 +692,7 @@ int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, 
                                float* elapsed_ms, uint32_t mode_arg) {
     wrk_pick_args pick{temperature, top_p, seed};
     pick.need = wrk_pick_args::SAMPLER;
-    return v7_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode_arg);
+    return wrk_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
@@ -743,60 +701,24 @@ int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* s
                                   float* elapsed_ms, uint32_t mode_arg) {
     wrk_pick_args pick{temperature, top_p, seed, presence, frequency, decay, occ};
     pick.need = wrk_pick_args::TABLE;
-    return v7_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode_arg);
+    return wrk_generate(ctx, m, st, first_tokens, B, steps, pick, out_tokens, last_logits, elapsed_ms, mode_arg);
 }
 
 int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                              const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths, float* last_logits,
                              uint32_t* steps_run, float* elapsed_ms, uint32_t mode_arg) {
-    if (!ctx) return WRK_E_ARG;
-    {
-        LOCK(ctx);
-        WRK_ARG(ctx, opt, "options required");
-        WRK_ARG(ctx, out_lengths && steps_run, "out_lengths and steps_run are required");
-    }
-    return v7_generate(ctx, m, st, first_tokens, B, steps, wrk_pick_of(*opt), out_tokens, last_logits, elapsed_ms, mode_arg, opt, out_lengths, steps_run);
-}
-
-// generate_queue: one lane, the frame's own; the loop is generate_stop's polled one with the queue's live count
-// tail: QUEUE, or QUEUE_POOL with the state pool of wrk_v7_generate_queue_pool
-static int32_t v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
-                                 const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail, const wrk_queue_pool* pool) {
-    if (!ctx || !m || !st) return WRK_E_ARG;
-    LOCK(ctx);
-    const uint32_t V = m->d.num_vocab;
-    wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
-    wrk_queue_pack pk;
-    int32_t rc = wrk_queue_check(ctx, opt, st, B, V, mode_arg, out_arg ? &out : nullptr, pk);
-    if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, pk);
-    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->emb != nullptr, m->d.num_emb, m->d.num_layer, V, pk.first_tokens.data(), B);
-    if (rc != WRK_OK) return rc;
-    if (elapsed_ms) *elapsed_ms = 0.0f;
-    const uint32_t mode = mode_arg & 0xffu;
-    wrk::timing_slot(ctx, nullptr);
-    m->engine_blocked = false;
-    std::vector<wrk_lane> L(1);
-    rc = decode_prepare(ctx, m, st, pk.first_tokens.data(), 0, B, pk.max_steps, mode, wrk_no_graph(), pk.kind, pk.rows, nullptr, &pk, &L[0].prog);
-    if (rc != WRK_OK) return rc;
-    L[0].io = &m->s; L[0].history = m->history; L[0].b0 = 0; L[0].nb = B; L[0].frame = m;
-    uint32_t steps_run = 0;
-    const wrk_stop_run run{st, pk.poll_steps, nullptr, &steps_run, true};
-    rc = wrk_run_lanes(ctx, L, m->lane_streams, m->lane_events, B, V, pk.max_steps, [&] { return enqueue_decode_step(ctx, m, st, 0, B, mode, pk.kind); },
-                       nullptr, nullptr, elapsed_ms, &run);
-    if (rc != WRK_OK) return rc;
-    rc = wrk_v7_engine_check(m->engine);
-    if (rc != WRK_OK) return rc;
-    return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
+    const wrk_stop_call stop{opt, out_lengths, steps_run};
+    return wrk_generate(ctx, m, st, first_tokens, B, steps, opt ? wrk_pick_of(*opt) : wrk_pick_args{}, out_tokens, last_logits, elapsed_ms, mode_arg, &stop);
 }
 
 int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                               const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
-    return v7_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE, nullptr);
+    return wrk_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE, nullptr);
 }
 
 int32_t wrk_v7_generate_queue_pool(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                                    const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_pool* pool) {
-    return v7_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE_POOL, pool);
+    return wrk_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE_POOL, pool);
 }
 
 }  // extern "C"
