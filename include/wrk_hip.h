@@ -345,6 +345,24 @@ int32_t wrk_sample_logits_filtered(wrk_ctx* ctx, const wrk_buf* logits, uint32_t
  * Blocking; logprob: host f32 [num_rows], rank: host u32 [num_rows].  Same bits for the same (num_rows, num_vocab, row_stride). */
 int32_t wrk_score_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
                          const uint32_t* targets, float* logprob, uint32_t* rank);
+/* Log-probs of chosen tokens and their most likely alternatives, per row x of f32 logits [num_rows][row_stride] (first num_vocab used)
+ * and its chosen token y = tokens[row] (OpenAI's logprobs / top_logprobs, vLLM's logprobs=N):
+ *   logprob         = (x_y - m) - log sum_i exp(x_i - m), m = the row max: wrk_score_logits' expression
+ *   top_ids[j]      = the j-th token in wrk_sample_logits' order: logit descending, ties by index ascending (j < num_top)
+ *   top_logprobs[j] = the same expression at top_ids[j]
+ * The row is the raw head output at temperature 1, before penalties, bans and filters -- what last_logits returns and wrk_score_logits
+ * scores: a banned or filtered-out token may appear among the alternatives, and the chosen token of a sampled or penalised pick gets
+ * its probability under the model, not under the sampler.  A logit of -inf has log-prob -inf and sorts after every finite logit, by
+ * index.  With num_top > num_vocab the entries j >= num_vocab are id 0xFFFFFFFF and log-prob -inf.  A NaN anywhere in the row gives NaN
+ * in logprob and in every top_logprobs entry; the ids of such a row are unspecified.  When y is the first index of the maximum (a greedy
+ * pick) top_ids[0] == y and top_logprobs[0] has the bits of logprob.  Same bits for the same (num_rows, num_vocab, row_stride, num_top).
+ * 0 <= num_top <= WRK_MAX_TOP_LOGPROBS; with 0 only logprob is produced and the top arrays may be NULL.  tokens: host u32 [num_rows].
+ * Blocking; logprob: host f32 [num_rows], top_ids: host u32 [num_rows][num_top], top_logprobs: host f32 [num_rows][num_top].
+ * WRK_E_ARG before any launch: a token >= num_vocab, num_top > WRK_MAX_TOP_LOGPROBS, a NULL required array.  num_vocab > 2^20:
+ * WRK_E_UNSUPPORTED (the sampler's limit). */
+#define WRK_MAX_TOP_LOGPROBS 20
+int32_t wrk_top_logprobs(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                         const uint32_t* tokens, uint32_t num_top, float* logprob, uint32_t* top_ids, float* top_logprobs);
 /* as wrk_v7_infer, with the header rows scored instead of read back: header row h gets wrk_score_logits' (logprob[h], rank[h]) of
  * target targets[h] (host u32 [num_header], each < num_vocab, required when num_header > 0).  The state advances exactly as
  * wrk_v7_infer's on the same job; only num_header floats and u32 come back.  Targets are device data: one cached program per job shape
@@ -406,7 +424,16 @@ int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_stat
  * top_k / min_p (host arrays [num_batch], either may be NULL: off) make the pick wrk_sample_logits_filtered's; they need the sampler
  * arrays (else WRK_E_ARG), and min_p outside [0, 1] is WRK_E_ARG.  With both stop arrays NULL this is the options form of
  * wrk_v7_generate_sample / wrk_v7_generate_penalized.  Filtered calls replay step programs of their own (any filter values: the rows
- * are device data); a call with both NULL runs exactly the programs it ran before. */
+ * are device data); a call with both NULL runs exactly the programs it ran before.
+ * Log-probs (wrk_top_logprobs on every step's head output, inside the step program): on iff out_logprob is non-NULL, host f32
+ * [steps][num_batch]; with num_top > 0 (<= WRK_MAX_TOP_LOGPROBS, else WRK_E_ARG) out_top_ids (host u32) and out_top_logprobs (host f32)
+ * [steps][num_batch][num_top] are required (else WRK_E_ARG).  Row j of sequence b belongs to y_j, scored on the raw head output it was
+ * picked from.  Rows j < out_lengths[b] are what the same call without stop sets produces, the row of the stop token's own step
+ * included; rows at or after out_lengths[b] are unspecified; rows at or after *steps_run are not written.  Tokens, lengths and states are
+ * those of the call without log-probs.  num_top is data of the step program: one cached program serves any num_top; log-prob calls
+ * replay step programs of their own, a call without them exactly the programs it ran before.  A sequence's log-probs do not depend on
+ * the number of lanes.  The log-prob fields sit between poll_steps and the filter fields, which stay the last two: callers that name
+ * their fields or start from a zeroed struct keep working after a recompile. */
 #define WRK_MAX_STOP_TOKENS 16
 typedef struct wrk_generate_options {
     const float *temperature, *top_p;
@@ -415,6 +442,10 @@ typedef struct wrk_generate_options {
     wrk_occurrence *occ;
     const uint32_t *stop_tokens, *stop_offsets;
     uint32_t poll_steps;
+    uint32_t num_top;
+    float *out_logprob;
+    uint32_t *out_top_ids;
+    float *out_top_logprobs;
     const uint32_t *top_k;
     const float *min_p;
 } wrk_generate_options;
@@ -451,7 +482,14 @@ int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* st
  * only partly given, penalty arrays without a table, a table with fewer slots than num_batch or of another vocabulary or context,
  * init_state of another size, max_steps == 0, and whatever wrk_v7_generate_stop rejects for the same pick.  mode bits 8-15 > 1 (lanes):
  * WRK_E_UNSUPPORTED -- a queue shared by several streams would need cross-stream atomics.
- * top_k / min_p [num_requests] (either may be NULL: off): request r's draws are wrk_sample_logits_filtered's, as in wrk_generate_options. */
+ * top_k / min_p [num_requests] (either may be NULL: off): request r's draws are wrk_sample_logits_filtered's, as in wrk_generate_options.
+ * Log-probs, as in wrk_generate_options: on iff out_logprob is non-NULL (then, with num_top > 0, out_top_ids and out_top_logprobs are
+ * required; all three NULL: off; anything else, or num_top > WRK_MAX_TOP_LOGPROBS: WRK_E_ARG).  The rows of a request's reply are cut
+ * out of the step rows exactly as its tokens are: reply token j of request r has out_logprob[o_r + j] and out_top_ids /
+ * out_top_logprobs[(o_r + j) * num_top ..], as wrk_top_logprobs gives them on the head output y_j was drawn from.  The rows of steps that
+ * feed prompt tokens are discarded (prompt log-probs: wrk_v7_score).  out_logprob: host f32 [sum of max_new]; out_top_ids /
+ * out_top_logprobs: host [sum of max_new][num_top].  They sit with the options, before the filter fields, as in wrk_generate_options:
+ * wrk_queue_result keeps its six arrays. */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
     const uint32_t *prompt_tokens, *prompt_offsets, *max_new;
@@ -462,6 +500,10 @@ typedef struct wrk_queue_options {
     wrk_occurrence *occ;
     const wrk_buf *init_state;
     uint32_t poll_steps, max_steps;
+    uint32_t num_top;
+    float *out_logprob;
+    uint32_t *out_top_ids;
+    float *out_top_logprobs;
     const uint32_t *top_k;
     const float *min_p;
 } wrk_queue_options;

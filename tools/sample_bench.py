@@ -12,8 +12,13 @@ A fifth pair of legs (--top-k K and / or --min-p M), alternating with the others
 the same top_p (the filtered kernel's fused boundary descent), and with --top-k also top_k alone at top_p = 1 (its count-only descent),
 each against the plain sampled leg, with the run-to-run spread of both.
 
+A sixth leg (--logprobs N[,N...]): the decode loop with log-probs and N alternatives per token against the same loop
+without them -- both through the options entry point without stop sets, so the step programs differ by the log-prob launches alone --
+for the greedy and the sampled pick, alternating, with the run-to-run spread of both; and, as context, the host route: leaving the
+loop after every step to read back last_logits (wall time per step of one-step calls).
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
-                                 [--top-k 40] [--min-p 0.05]
+                                 [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20]
 
 Prints one JSON object.
 """
@@ -106,6 +111,50 @@ def stop_leg(rt, first, B, V, args):
     return res
 
 
+def logprob_leg(rt, first, args):
+    """Per pick (greedy, sampled) and per N: medians of the per-step time of generate_stop without stop sets, with logprobs=N against
+    without, alternating in one process; every call starts from the same state, so both draw the same tokens."""
+    B = len(first)
+    ns = [int(x) for x in args.logprobs.split(",")]
+    start = [rt.state_read(b) for b in range(B)]
+
+    def run(pick, **kw):
+        for b in range(B):
+            rt.state_write(start[b], b)
+        tok, _ = rt.generate_stop(first, args.steps, [], poll_steps=POLL_OFF, **pick, **kw)
+        return tok, rt.last_stop_ms / args.steps
+    res = {}
+    for name, pick in (("greedy", {}), ("sample", dict(temperature=args.temperature, top_p=args.top_p))):
+        want, _ = run(pick)
+        for n in ns:                                                       # capture and warm up
+            run(pick, logprobs=n)
+        base, per, same = [], {n: [] for n in ns}, True
+        for _ in range(args.reps):
+            base.append(run(pick)[1])
+            for n in ns:
+                tok, ms = run(pick, logprobs=n)
+                same &= bool(np.array_equal(tok, want))
+                per[n].append(ms)
+        bm = float(np.median(base))
+        # the host route: one-step calls, the logits read back after each
+        for b in range(B):
+            rt.state_write(start[b], b)
+        cur, t0 = list(first), time.perf_counter()
+        for _ in range(args.steps):
+            tok, _, _ = rt.generate_stop(cur, 1, [], want_logits=True, **pick)
+            cur = tok[0].tolist()
+        host = (time.perf_counter() - t0) * 1e3 / args.steps
+        res[name] = {"same_tokens": same, "without_ms_per_step": round(bm, 5), "without_ms_all": [round(x, 5) for x in base],
+                     "without_spread_us": round((max(base) - min(base)) * 1e3, 2), "host_route_wall_ms_per_step": round(host, 4), "num_top": []}
+        for n in ns:
+            m = float(np.median(per[n]))
+            res[name]["num_top"].append({"n": n, "with_ms_per_step": round(m, 5), "with_minus_without_us": round((m - bm) * 1e3, 2),
+                                         "with_spread_us": round((max(per[n]) - min(per[n])) * 1e3, 2), "with_ms_all": [round(x, 5) for x in per[n]]})
+    for b in range(B):
+        rt.state_write(start[b], b)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -120,6 +169,7 @@ def main():
     ap.add_argument("--stop-steps", type=int, default=1024)
     ap.add_argument("--top-k", type=int, default=None)
     ap.add_argument("--min-p", type=float, default=None)
+    ap.add_argument("--logprobs", default=None, help="comma-separated numbers of alternatives, e.g. 0,5,20")
     args = ap.parse_args()
     import wrk
 
@@ -197,6 +247,8 @@ def main():
                                        "top_k_only_spread_us": round((max(k) - min(k)) * 1e3, 2), "top_k_only_ms_all": [round(x, 5) for x in k]})
         if args.stop:
             out["batches"][-1]["stop"] = stop_leg(rt, first, B, V, args)
+        if args.logprobs:
+            out["batches"][-1]["logprobs"] = logprob_leg(rt, first, args)
     if occ is not None:
         occ.close()
     rt.close()

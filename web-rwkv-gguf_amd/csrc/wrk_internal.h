@@ -193,6 +193,19 @@ uint32_t score_slices(uint32_t n, uint32_t v, int num_cu);
 int score_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const uint32_t* targets, ScorePart* part,
                float* logprob, uint32_t* rank, int num_cu);
 
+// wrk_logprob.hip: per row, the log-prob of the chosen token tokens[row] (< v, else NaN) and the num_top first tokens of the sampler's
+// order with their log-probs, on the raw logits.  LogprobParam is device data, in a decode loop a per-frame block written
+// before every call: the output buffers and num_top (<= LOGPROB_MAX_TOP), so one captured program serves any num_top.  Row r goes to row
+// (step ? *step : 0) * n + r of logprob [cap_rows], top_ids / top_logprobs [cap_rows][num_top]; a row at or past cap_rows is not written.
+// part / keys: scratch of logprob_part_bytes(n) / logprob_key_bytes(n).  -1: v == 0, v > SAMPLE_MAX_VOCAB or stride < v
+static constexpr uint32_t LOGPROB_MAX_TOP = WRK_MAX_TOP_LOGPROBS;
+struct LogprobParam { float* logprob; uint32_t* top_ids; float* top_logprobs; uint32_t num_top, cap_rows; };
+struct LogprobPart { float m, s; };
+inline size_t logprob_part_bytes(uint32_t n) { return (size_t)n * SCORE_MAX_SLICES * sizeof(LogprobPart); }
+inline size_t logprob_key_bytes(uint32_t n) { return (size_t)n * SCORE_MAX_SLICES * 4 * LOGPROB_MAX_TOP * 8; }
+int logprob_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const uint32_t* tokens, const uint32_t* step,
+                 const LogprobParam* par, LogprobPart* part, unsigned long long* keys, int num_cu);
+
 // wrk_penalty.hip: repetition penalties.  One PenaltyParam per row: the row's slot of an occurrence table (count f32 [v],
 // flags u8 [v]: bit 0 present, bit 1 banned), the table's weights f32 [v] and the sequence's (presence, frequency, decay).  Decode loops
 // keep these in a per-frame device buffer written before every call, so a captured step never holds a table pointer of its own.

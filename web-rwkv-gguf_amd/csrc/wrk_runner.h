@@ -88,13 +88,14 @@ struct wrk_step_kind {
     Pick pick = GREEDY;
     bool penalized = false;     // the pick is made on pen_o = head_o penalised with the occurrence rows of pen_par, which then count the draw (wrk_penalty.hip)
     Tail tail = PLAIN;
+    bool logprobs = false;      // between the pick and the tail, the log-prob launches (wrk_logprob.hip) on head_o and the picked tokens, on lp_par
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
     bool queue() const { return tail == QUEUE || tail == QUEUE_POOL; }
     bool pool() const { return tail == QUEUE_POOL; }
-    // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25, penalised 26, tail 27-28 -- above every flag of an
+    // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25, penalised 26, tail 27-28, log-probs 29 -- above every flag of an
     // infer job and of a runner's own (wrk_frame_common::key_bits, all below bit 24, ORed into the same word)
-    uint32_t key() const { return (uint32_t)pick << 24 | (uint32_t)penalized << 26 | (uint32_t)tail << 27; }
+    uint32_t key() const { return (uint32_t)pick << 24 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29; }
 };
 
 // ------------------------------------------------------------------ frame state of a model (base of wrk_v7_model / wrk_v6_model)
@@ -162,6 +163,18 @@ struct wrk_frame_common {
     wrk::QueueTurn* queue_turn = nullptr;
     uint32_t* queue_entries = nullptr;
     uint32_t queue_turn_cap = 0, queue_entry_cap = 0;
+    // log-probs in the decode loops (wrk_logprob.hip), allocated by the first such call only.  lp_par: the parameter block,
+    // written before every call (the output buffers and num_top: one program serves any num_top); the per-step rows lp_logprob
+    // [lp_rows_cap], lp_top_ids / lp_top_logprobs [lp_rows_cap][WRK_MAX_TOP_LOGPROBS], indexed [steps][B](, [num_top]) by a call; the
+    // slice partials and candidate keys of lp_batch_cap rows
+    wrk::LogprobParam* lp_par = nullptr;
+    float* lp_logprob = nullptr;
+    uint32_t* lp_top_ids = nullptr;
+    float* lp_top_logprobs = nullptr;
+    wrk::LogprobPart* lp_part = nullptr;
+    unsigned long long* lp_keys = nullptr;
+    size_t lp_rows_cap = 0;
+    uint32_t lp_batch_cap = 0;
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
     uint32_t live_host_cap = 0;
     std::vector<hipEvent_t> poll_events;        // [2 blocks][lanes]
@@ -179,7 +192,7 @@ struct wrk_frame_common {
     // the ensure_* reallocate after a stream sync and drop the captured programs, which hold the old pointers; never inside a capture
     void drop_graphs();
     // the buffers an ensure_* reallocates together; bufs(g): their pointers, the one list regrow and release_common go through
-    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, NUM_GROUPS };
+    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, LOGPROB, NUM_GROUPS };
     std::vector<void**> bufs(Group g);
     // sync, drop the programs (`drop`), free the buffers and allocate them again; after a failure all of them are freed
     // bytes: one size per buffer of bufs(g), in its order.  The caller sets its caps after WRK_OK: an error leaves them as they were
@@ -191,6 +204,7 @@ struct wrk_frame_common {
     int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
     int32_t ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens);
     int32_t ensure_queue_states(uint32_t slots, uint32_t requests);
+    int32_t ensure_logprobs(size_t rows, uint32_t B);
     int32_t ensure_poll(uint32_t lanes);        // lane 0's frame: pinned live counts and events of the polled loop
     void release_common();          // destroy paths: programs, scratch and every buffer above
 };
@@ -218,10 +232,16 @@ struct wrk_pick_args {
 template <class Options> wrk_pick_args wrk_pick_of(const Options& o) {
     return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p};
 }
+// the log-prob outputs of a call (wrk_generate_options / wrk_queue_options); logprob NULL: off
+struct wrk_logprob_call {
+    uint32_t num_top = 0; float* logprob = nullptr; uint32_t* top_ids = nullptr; float* top_logprobs = nullptr;
+    bool on() const { return logprob != nullptr; }
+};
 bool wrk_no_graph();        // WRK_NO_GRAPH=1: the decode loops enqueue every step instead of replaying a program
 // Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the penalise launch (penalised), the arg-max
 // or sampler launch on the frame's parameters at step *counter -- neither with `argmax_done`: the head launch has left the arg-max in
-// io().argmax (RWKV-7's fused greedy head) -- then the tail: the occurrence update that belongs to it (penalised), its advance of
+// io().argmax (RWKV-7's fused greedy head) -- with kind.logprobs the log-prob launches on head_o (never pen_o) and io().argmax into row
+// *counter of the frame's log-prob buffers, then the tail: the occurrence update that belongs to it (penalised), its advance of
 // tokens / history / counter, and stop_snapshot / queue_reset / queue_turnover
 int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, bool argmax_done);
 
@@ -229,7 +249,8 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
 // dealt over the lanes that bits 8-15 of mode_arg ask for (clamped to [1, min(B, m->max_lanes())]; lane g owns sequences
 // [B g / groups, B (g + 1) / groups)).  Per lane, in this order -- growing a buffer drops the cached programs: ensure_frame, the
 // upload of tokens / cursors / pick rows, the stop buffers, the step program {state, B | b0 << 16, key_bits | kind.key()} (none with
-// WRK_NO_GRAPH=1: lane 0 enqueues every step).  Then tokens [steps][B] and last logits [B][V] come back.
+// WRK_NO_GRAPH=1: lane 0 enqueues every step).  Then tokens [steps][B] and last logits [B][V] come back, and with stop->opt->out_logprob
+// (kind.logprobs) the log-prob rows of the steps that ran, lane by lane with the pitch copies of the tokens.
 // stop: steps go out in blocks of poll_steps (0: 16), each followed by a copy of every lane's live count to pinned memory and an
 // event; before block k + 2 the host waits for block k's event and stops submitting once every count is 0.  Then stop_restore, and
 // lengths [B] / *steps_run come back

@@ -83,6 +83,7 @@ std::vector<void**> wrk_frame_common::bufs(Group g) {
         case STOP: return {(void**)&stop_par, (void**)&stop_flags, (void**)&stop_snap_state, (void**)&stop_snap_logits};
         case QUEUE: return {(void**)&queue_slots, (void**)&queue_started, (void**)&queue_ctl, (void**)&queue_reqs, (void**)&queue_log, (void**)&queue_pool};
         case QUEUE_STATES: return {(void**)&queue_state_ctl, (void**)&queue_turn, (void**)&queue_entries};
+        case LOGPROB: return {(void**)&lp_par, (void**)&lp_logprob, (void**)&lp_top_ids, (void**)&lp_top_logprobs, (void**)&lp_part, (void**)&lp_keys};
         default: return {};
     }
 }
@@ -163,6 +164,18 @@ int32_t wrk_frame_common::ensure_queue_states(uint32_t slots, uint32_t requests)
     return rc;
 }
 
+int32_t wrk_frame_common::ensure_logprobs(size_t rows, uint32_t B) {
+    if (lp_par && rows <= lp_rows_cap && B <= lp_batch_cap) return WRK_OK;
+    if (rows < lp_rows_cap) rows = lp_rows_cap;
+    if (B < lp_batch_cap) B = lp_batch_cap;
+    // log-prob programs hold the old pointers; before the first allocation none exists
+    const size_t top = rows * WRK_MAX_TOP_LOGPROBS * 4;
+    const int32_t rc = regrow(LOGPROB, {sizeof(wrk::LogprobParam), rows * 4, top, top, wrk::logprob_part_bytes(B), wrk::logprob_key_bytes(B)}, lp_par != nullptr);
+    lp_rows_cap = rc == WRK_OK ? rows : 0;
+    lp_batch_cap = rc == WRK_OK ? B : 0;
+    return rc;
+}
+
 int32_t wrk_frame_common::ensure_poll(uint32_t lanes) {
     if (live_host_cap < 2 * lanes) {
         if (live_host) hipHostFree(live_host);
@@ -184,7 +197,7 @@ void wrk_frame_common::release_common() {
     scratch = nullptr;
     for (int g = 0; g < NUM_GROUPS; ++g)
         for (void** p : bufs((Group)g)) { if (*p) hipFree(*p); *p = nullptr; }
-    history_cap = 0; stop_slot_cap = 0; queue_pool_cap = 0;
+    history_cap = 0; stop_slot_cap = 0; queue_pool_cap = 0; lp_rows_cap = 0; lp_batch_cap = 0;
     sample_par_cap = filter_par_cap = pen_cap = stop_cap = stop_vocab_cap = queue_slot_cap = queue_req_cap = queue_turn_cap = queue_entry_cap = 0;
     score.release();
     if (live_host) hipHostFree(live_host);
@@ -300,6 +313,31 @@ static int32_t wrk_stop_sets(wrk_ctx* ctx, const uint32_t* tokens, const uint32_
     return WRK_OK;
 }
 
+// the log-prob fields of an options struct validated (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch); sets kind.logprobs
+static int32_t wrk_logprob_check(wrk_ctx* ctx, const wrk_logprob_call& lp, uint32_t V, wrk_step_kind& kind) {
+    kind.logprobs = lp.on();
+    WRK_ARG(ctx, lp.num_top <= WRK_MAX_TOP_LOGPROBS, "num_top %u: at most %u", lp.num_top, (uint32_t)WRK_MAX_TOP_LOGPROBS);
+    if (!lp.on()) {
+        WRK_ARG(ctx, !lp.top_ids && !lp.top_logprobs, "top_ids / top_logprobs without logprob");
+        return WRK_OK;
+    }
+    WRK_ARG(ctx, lp.num_top == 0 || (lp.top_ids && lp.top_logprobs), "top_ids and top_logprobs are required with num_top > 0");
+    if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "log-probs: vocabulary of %u tokens", V);
+    return WRK_OK;
+}
+
+// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): the frame's log-prob
+// buffers for `steps` steps of B sequences and the parameter block of this call
+static int32_t wrk_logprob_prepare(wrk_frame_common& f, uint32_t B, uint32_t steps, uint32_t num_top) {
+    const int32_t rc = f.ensure_logprobs((size_t)steps * B, B);
+    if (rc != WRK_OK) return rc;
+    const wrk::LogprobParam par{f.lp_logprob, f.lp_top_ids, f.lp_top_logprobs, num_top, (uint32_t)((size_t)steps * B)};
+    const int32_t rc2 = wrk_buf_write_raw(f.ctx, f.lp_par, &par, sizeof par);
+    if (rc2 != WRK_OK) return rc2;
+    WRK_HIP(f.ctx, hipStreamSynchronize(f.ctx->stream));
+    return WRK_OK;
+}
+
 bool wrk_no_graph() {
     const char* e = getenv("WRK_NO_GRAPH");
     return e && e[0] == '1';
@@ -377,6 +415,7 @@ struct wrk_queue_pack {
     uint32_t pool_entries = 0;
     std::vector<uint32_t> start, save;
     uint32_t* saved_out = nullptr;
+    wrk_logprob_call lp;        // the options' log-prob arrays and num_top
 };
 
 static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
@@ -388,6 +427,7 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     WRK_ARG(ctx, R >= 1, "num_requests 0");
     WRK_ARG(ctx, opt->prompt_tokens && opt->prompt_offsets && opt->max_new, "prompt_tokens, prompt_offsets and max_new are required");
     WRK_ARG(ctx, opt->max_steps >= 1, "max_steps 0");
+    pk.lp = wrk_logprob_call{opt->num_top, opt->out_logprob, opt->out_top_ids, opt->out_top_logprobs};
     WRK_ARG(ctx, B >= 1 && B <= st->num_batch && B <= 256, "num_batch %u: must be in [1, min(%u, 256)]", B, st->num_batch);
     if (((mode_arg >> 8) & 0xffu) > 1)
         return wrk_fail(ctx, WRK_E_UNSUPPORTED, "generate_queue on several lanes: one queue shared by several streams would need cross-stream atomics");
@@ -398,6 +438,7 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     wrk_pick_params req;
     if (rc == WRK_OK) rc = wrk_stop_sets(ctx, opt->stop_tokens, opt->stop_offsets, R, V, "request", stops);
     if (rc == WRK_OK) rc = wrk_pick_pack(ctx, wrk_pick_of(*opt), R, B, V, req, pk.kind);
+    if (rc == WRK_OK) rc = wrk_logprob_check(ctx, pk.lp, V, pk.kind);
     if (rc != WRK_OK) return rc;
     const wrk_step_kind kind = pk.kind;
     pk.R = R; pk.max_steps = opt->max_steps; pk.poll_steps = opt->poll_steps;
@@ -560,7 +601,7 @@ static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind
     return WRK_OK;
 }
 
-// after the loop: the log and the history rows come back and the replies are cut out of them
+// after the loop: the log and the history rows (with log-probs: their rows too) come back and the replies are cut out of them
 static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,
                                 wrk_queue_result* out) {
     wrk_ctx* ctx = f.ctx;
@@ -568,6 +609,14 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
     std::vector<uint32_t> hist((size_t)steps_run * B);
     WRK_HIP(ctx, hipMemcpyAsync(log.data(), f.queue_log, (size_t)pk.R * sizeof(wrk::QueueLog), hipMemcpyDeviceToHost, ctx->stream));
     if (!hist.empty()) WRK_HIP(ctx, hipMemcpyAsync(hist.data(), f.history, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t nt = pk.lp.num_top;
+    std::vector<float> lp_rows(pk.lp.on() ? hist.size() : 0), top_lp(lp_rows.size() * nt);
+    std::vector<uint32_t> top_id(top_lp.size());
+    if (!lp_rows.empty()) WRK_HIP(ctx, hipMemcpyAsync(lp_rows.data(), f.lp_logprob, lp_rows.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (!top_lp.empty()) {
+        WRK_HIP(ctx, hipMemcpyAsync(top_id.data(), f.lp_top_ids, top_id.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(top_lp.data(), f.lp_top_logprobs, top_lp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     size_t o = 0;
     for (uint32_t r = 0; r < pk.R; ++r) {
@@ -581,7 +630,13 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         out->lengths[r] = g.length; out->reasons[r] = g.reason; out->slots[r] = g.slot; out->start_steps[r] = g.start_step;
         // the step that gave the request reason 1 or 2 also wrote its state to its entry (queue_turnover)
         if (pk.saved_out) pk.saved_out[r] = pk.save[r] != wrk::QUEUE_NO_ENTRY && (g.reason == 1 || g.reason == 2);
-        for (uint32_t j = 0; j < g.length; ++j) out->out_tokens[o + j] = hist[((size_t)g.start_step + q.prompt_len - 1 + j) * B + g.slot];
+        for (uint32_t j = 0; j < g.length; ++j) {
+            const size_t row = ((size_t)g.start_step + q.prompt_len - 1 + j) * B + g.slot;
+            out->out_tokens[o + j] = hist[row];
+            if (!pk.lp.on()) continue;
+            pk.lp.logprob[o + j] = lp_rows[row];
+            for (size_t t = 0; t < nt; ++t) { pk.lp.top_ids[(o + j) * nt + t] = top_id[row * nt + t]; pk.lp.top_logprobs[(o + j) * nt + t] = top_lp[row * nt + t]; }
+        }
         o += opt->max_new[r];
     }
     *out->steps_run = steps_run;
@@ -626,6 +681,12 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     else if ((kind.filtered() ? wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax)
                               : wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax)) != 0)
         return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    // the picked tokens are in io.argmax and the tail has not moved the counter: row *counter of the frame's buffers, on the raw head output
+    if (kind.logprobs) {
+        if (!f.lp_par || B > f.lp_batch_cap) return wrk_fail(f.ctx, WRK_E_ARG, "log-prob buffers are not prepared");
+        if (wrk::logprob_rows(q, io.head_o, V, V, B, io.argmax, io.counter, f.lp_par, f.lp_part, f.lp_keys, f.ctx->num_cu) != 0)
+            return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "log-probs: vocabulary of %u tokens", V);
+    }
     if (kind.queue()) return enqueue_queue_tail(f, B, kind, st, b0);
     if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, B, kind, st, b0);
     if (kind.penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
@@ -645,13 +706,14 @@ static constexpr uint32_t WRK_STOP_POLL_DEFAULT = 16;
 // Every ensure_* comes before the look-up: growing a buffer drops the programs.  One program per (state, first sequence, B, the runner's
 // key bits, step kind): the analogue of the reference's cached RnnJob for a repeated RnnInfo
 static int32_t lane_prepare(wrk_lane& ln, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t steps, uint32_t mode, wrk_step_kind kind,
-                            const wrk_pick_params& rows, const wrk::StopParam* stop, const wrk_queue_pack* queue) {
+                            const wrk_pick_params& rows, const wrk::StopParam* stop, const wrk_queue_pack* queue, uint32_t num_top) {
     wrk_frame_common& f = *ln.frame;
     const uint32_t b0 = ln.b0, B = ln.nb;
     int32_t rc = f.ensure_frame(B, mode);
     if (rc == WRK_OK) rc = wrk_decode_prepare(f, first_tokens, b0, B, steps, rows);
     if (rc == WRK_OK && kind.tail == wrk_step_kind::STOP) rc = wrk_stop_prepare(f, st, B, stop + b0);
     if (rc == WRK_OK && kind.queue()) rc = wrk_queue_prepare(f, st, B, *queue);
+    if (rc == WRK_OK && kind.logprobs) rc = wrk_logprob_prepare(f, B, steps, num_top);
     ln.prog = nullptr;
     if (rc != WRK_OK || wrk_no_graph()) return rc;
     const wrk_frame_common::GraphKey key{st->uid, B | (b0 << 16), f.key_bits(B, mode) | kind.key()};
@@ -660,9 +722,11 @@ static int32_t lane_prepare(wrk_lane& ln, wrk_v7_state* st, const uint32_t* firs
 
 // `steps` steps of every lane between two events: one lane on the submission stream (enqueued step by step without a program), several
 // on lane 0's lane_streams[g], joined through lane_events[g].  A stop or queue tail: the polled loop of wrk_generate's comment on the
-// tail's live count, then stop_restore and the lengths (stop).  Then tokens [steps][B] and last logits [B][V] come back
+// tail's live count, then stop_restore and the lengths (stop).  Then tokens [steps][B] and last logits [B][V] come back, and into `lp`
+// (when on) the log-prob rows of the steps that ran
 static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, wrk_v7_state* st, uint32_t B, uint32_t steps, uint32_t mode,
-                             wrk_step_kind kind, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, const wrk_stop_run& stop) {
+                             wrk_step_kind kind, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, const wrk_stop_run& stop,
+                             const wrk_logprob_call& lp) {
     const size_t groups = lanes.size();
     const bool polled = kind.tail != wrk_step_kind::PLAIN;
     const std::vector<hipStream_t>& streams = lanes[0].frame->lane_streams;
@@ -759,6 +823,18 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
             else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)B * 4, ln.frame->history, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
                                                hipMemcpyDeviceToHost, ctx->stream));
         }
+        if (lp.on() && steps) {
+            // rows [steps][nb] of the lane into [steps][B] at its first sequence; the top arrays the same with num_top entries per sequence
+            const size_t n = lp.num_top;
+            WRK_HIP(ctx, hipMemcpy2DAsync(lp.logprob + ln.b0, (size_t)B * 4, ln.frame->lp_logprob, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
+                                          hipMemcpyDeviceToHost, ctx->stream));
+            if (n) {
+                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_ids + ln.b0 * n, B * n * 4, ln.frame->lp_top_ids, ln.nb * n * 4, ln.nb * n * 4, steps,
+                                              hipMemcpyDeviceToHost, ctx->stream));
+                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_logprobs + ln.b0 * n, B * n * 4, ln.frame->lp_top_logprobs, ln.nb * n * 4, ln.nb * n * 4, steps,
+                                              hipMemcpyDeviceToHost, ctx->stream));
+            }
+        }
         if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits + (size_t)ln.b0 * V, ln.frame->io().head_o, (size_t)ln.nb * V * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -782,7 +858,10 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
     kind.tail = stop ? wrk_step_kind::STOP : wrk_step_kind::PLAIN;
     wrk_pick_params rows;
     std::vector<wrk::StopParam> stop_rows;      // generate_stop: one row per sequence
+    wrk_logprob_call lp;
+    if (stop) lp = wrk_logprob_call{stop->opt->num_top, stop->opt->out_logprob, stop->opt->out_top_ids, stop->opt->out_top_logprobs};
     int32_t rc = wrk_pick_pack(ctx, pick, B, B, V, rows, kind);
+    if (rc == WRK_OK) rc = wrk_logprob_check(ctx, lp, V, kind);
     if (rc == WRK_OK && stop) rc = wrk_stop_sets(ctx, stop->opt->stop_tokens, stop->opt->stop_offsets, B, V, "sequence", stop_rows);
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), first_tokens, B);
     if (rc != WRK_OK) return rc;
@@ -807,11 +886,11 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
         L[g].b0 = (uint32_t)((uint64_t)B * g / groups);
         L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
         // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
-        rc = lane_prepare(L[g], st, first_tokens, steps, mode, kind, rows, stop_rows.data(), nullptr);
+        rc = lane_prepare(L[g], st, first_tokens, steps, mode, kind, rows, stop_rows.data(), nullptr, lp.num_top);
         if (rc != WRK_OK) return rc;
     }
     const wrk_stop_run run{stop ? stop->opt->poll_steps : 0u, stop ? stop->out_lengths : nullptr, stop ? stop->steps_run : nullptr};
-    rc = wrk_run_lanes(ctx, L, st, B, steps, mode, kind, out_tokens, last_logits, elapsed_ms, run);
+    rc = wrk_run_lanes(ctx, L, st, B, steps, mode, kind, out_tokens, last_logits, elapsed_ms, run, lp);
     if (rc != WRK_OK) return rc;
     return m->after_loop(groups);
 }
@@ -832,10 +911,10 @@ int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, 
     m->before_loop();
     std::vector<wrk_lane> L{{nullptr, 0, B, nullptr}};      // one lane: a queue shared by several streams would need cross-stream atomics
     rc = m->lane(0, 1, &L[0].frame);
-    if (rc == WRK_OK) rc = lane_prepare(L[0], st, pk.first_tokens.data(), pk.max_steps, mode, pk.kind, pk.rows, nullptr, &pk);
+    if (rc == WRK_OK) rc = lane_prepare(L[0], st, pk.first_tokens.data(), pk.max_steps, mode, pk.kind, pk.rows, nullptr, &pk, pk.lp.num_top);
     if (rc != WRK_OK) return rc;
     uint32_t steps_run = 0;
-    rc = wrk_run_lanes(ctx, L, st, B, pk.max_steps, mode, pk.kind, nullptr, nullptr, elapsed_ms, wrk_stop_run{pk.poll_steps, nullptr, &steps_run});
+    rc = wrk_run_lanes(ctx, L, st, B, pk.max_steps, mode, pk.kind, nullptr, nullptr, elapsed_ms, wrk_stop_run{pk.poll_steps, nullptr, &steps_run}, wrk_logprob_call{});
     if (rc == WRK_OK) rc = m->after_loop(1);
     if (rc != WRK_OK) return rc;
     return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);

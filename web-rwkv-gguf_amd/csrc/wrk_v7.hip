@@ -622,7 +622,7 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
 int32_t wrk_v7_model::enqueue_step(wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) {
     int32_t rc;
     const bool fused = mode == 1 && act_dtype == WRK_F16, head_picks = fused && !kind.sampled(),
-               head_advances = head_picks && kind.tail == wrk_step_kind::PLAIN;
+               head_advances = head_picks && kind.tail == wrk_step_kind::PLAIN && !kind.logprobs;     // log-probs go between the pick and the advance
     if (fused) rc = enqueue_fused_decode(st, B, B, true, true, head_picks, head_advances, b0, true);
     else {
         wrk::gather_rows_f16(ctx->op_stream(), emb->ptr, s.tokens, s.input, d.num_emb, B);

@@ -72,20 +72,23 @@ _f32p = C.POINTER(C.c_float)
 
 
 class GenerateOptions(C.Structure):
-    """wrk_generate_options: the pick (sampler arrays all NULL: arg-max; occ NULL: no penalties) and the stop sets (CSR) of
-    wrk_v*_generate_stop."""
+    """wrk_generate_options: the pick (sampler arrays all NULL: arg-max; occ NULL: no penalties), the stop sets (CSR) and the log-prob
+    outputs (out_logprob NULL: off) of wrk_v*_generate_stop."""
     _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
                 ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
+                ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
                 ("top_k", _u32p), ("min_p", _f32p)]
 
 
 class QueueOptions(C.Structure):
     """wrk_queue_options: the requests (CSR prompts, max_new, CSR stop sets), the pick arrays [R] as in GenerateOptions, the shared
-    prefix state and the polled loop's block size and step cap of wrk_v*_generate_queue."""
+    prefix state, the polled loop's block size and step cap and the log-prob outputs (out_logprob NULL: off) of wrk_v*_generate_queue."""
     _fields_ = [("num_requests", C.c_uint32), ("prompt_tokens", _u32p), ("prompt_offsets", _u32p), ("max_new", _u32p),
                 ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p),
                 ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("init_state", _P),
-                ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32), ("top_k", _u32p), ("min_p", _f32p)]
+                ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32),
+                ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
+                ("top_k", _u32p), ("min_p", _f32p)]
 
 
 class QueueResult(C.Structure):
@@ -100,6 +103,7 @@ class QueuePool(C.Structure):
 
 
 MAX_STOP_TOKENS = 16        # WRK_MAX_STOP_TOKENS
+MAX_TOP_LOGPROBS = 20       # WRK_MAX_TOP_LOGPROBS
 QUEUE_NO_ENTRY = 0xFFFFFFFF     # WRK_QUEUE_NO_ENTRY
 _TP = C.POINTER(TensorDesc)
 
@@ -177,6 +181,7 @@ HIP_SYMBOLS = {
     "wrk_v6_generate_sample": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _f32p, _f32p,
                                            C.c_uint32]),
     "wrk_score_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p, _u32p]),
+    "wrk_top_logprobs": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _f32p, _u32p, _f32p]),
     "wrk_v7_score": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _u32p, _f32p, _u32p,
                                  C.c_uint32]),
     "wrk_v6_score": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _u32p, _f32p, _u32p,
@@ -296,6 +301,15 @@ def _fill_pick(opt, n: int, keep: list, temperature, top_p, seed, occurrence, pr
         opt.min_p = mp
 
 
+def _logprob_arrays(logprobs, rows: int):
+    """(logprob [rows], top_ids [rows, n], top_logprobs [rows, n]) host arrays for `logprobs` = n alternatives per row; the top arrays
+    keep one element when empty so that their pointers are valid."""
+    n = int(logprobs)
+    if not 0 <= n <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs = {logprobs}: None, or 0..{MAX_TOP_LOGPROBS}")
+    return np.zeros(max(rows, 1), np.float32), np.zeros(max(rows * n, 1), np.uint32), np.zeros(max(rows * n, 1), np.float32)
+
+
 def _stop_csr(stop, n: int, owners: str):
     """Stop sets as (ids, offsets [n + 1]): one list of ids for all n owners, or one list per owner."""
     sets = [] if stop is None else list(stop)
@@ -411,6 +425,31 @@ class Context:
         rk = np.zeros(n, np.uint32)
         self.check(hip.wrk_score_logits(self.h, buf.h, V, stride, n, _ptr(tg, _u32p), _ptr(lp, _f32p), _ptr(rk, _u32p)))
         return lp, rk
+
+    def top_logprobs(self, logits, tokens, num_top: int, num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
+        """Per row of f32 logits and its chosen token y: (logprob = x_y - logsumexp(x), the ids of the `num_top` most likely tokens --
+        logit descending, ties by index ascending, the sampler's order -- and their log-probs), computed on the device on the raw row
+        (DESIGN.md §7h).  `logits`: an [n, V] f32 array, or a `Buffer` of n rows of `row_stride` f32 (first `num_vocab` used).  Returns
+        (float32 [n], uint32 [n, num_top], float32 [n, num_top]); entries past the vocabulary are id 0xFFFFFFFF and -inf."""
+        tk = _u32(tokens).reshape(-1)
+        n = tk.size
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            stride = int(row_stride or V)
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            assert a.shape[0] == n, "one token per row"
+            V = stride = a.shape[1]
+            buf = self.buffer(a)
+        num_top = int(num_top)
+        lp = np.zeros(max(n, 1), np.float32)
+        ids = np.zeros(max(n * num_top, 1), np.uint32)
+        tlp = np.zeros(max(n * num_top, 1), np.float32)
+        self.check(hip.wrk_top_logprobs(self.h, buf.h, V, stride, n, _ptr(tk, _u32p), num_top, _ptr(lp, _f32p), _ptr(ids, _u32p),
+                                        _ptr(tlp, _f32p)))
+        return lp[:n], ids[:n * num_top].reshape(n, num_top), tlp[:n * num_top].reshape(n, num_top)
 
     def penalize_logits(self, logits, occ: "Occurrence", presence, frequency, first_batch: int = 0, num_vocab: Optional[int] = None,
                         row_stride: Optional[int] = None):
@@ -913,6 +952,9 @@ class Runtime:
         self.model = rt.wrk_runtime_model(h)
         self.model6 = rt.wrk_runtime_model_v6(h)
         self.state = rt.wrk_runtime_state(h)
+        # the log-probs of the last generate_* call with `logprobs`: (logprob [steps_run, B], top_ids [steps_run, B, n], top_logprobs
+        # [steps_run, B, n]); after generate_queue one such triple per request ([len], [len, n], [len, n]); None after a call without
+        self.last_logprobs = None
 
     def token_bytes(self, num_batch: int = 1) -> int:
         if self.model6:
@@ -1030,27 +1072,44 @@ class Runtime:
         ms = C.c_float()
         logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
         fn, mdl = self._entry("generate_" + name)
+        self.last_logprobs = None
         self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, *rows, _ptr(out, _u32p),
                           _ptr(logits, _f32p) if want_logits else None, C.byref(ms), self._mode(mode, groups)))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
 
-    def generate_greedy(self, first_tokens, steps: int, mode: int = 1, want_logits: bool = False, groups: int = 1):
+    def generate_greedy(self, first_tokens, steps: int, mode: int = 1, want_logits: bool = False, groups: int = 1, logprobs=None):
         """Device-resident greedy loop; returns (tokens [steps, B], elapsed_ms[, last logits [B, V]]).
         groups > 1 (RWKV-7): the B independent sequences are dealt over that many concurrent pipelines (each a contiguous block of
-        sequences with its own frame, decode program and HIP stream) instead of one batched step."""
+        sequences with its own frame, decode program and HIP stream) instead of one batched step.
+        logprobs (None: off; 0..MAX_TOP_LOGPROBS): every step also leaves the log-prob of each picked token and the `logprobs` most
+        likely alternatives at its position, computed on the device on the raw head output (`Context.top_logprobs`), in
+        `last_logprobs`; such a call goes through the options entry point (wrk_v*_generate_stop without stop sets).  The return
+        shapes do not change."""
+        if logprobs is not None:
+            return self._generate_filtered(first_tokens, steps, None, None, None, None, 0.0, 0.0, 1.0, None, None, mode, want_logits, groups,
+                                           logprobs)
         return self._generate("greedy", first_tokens, steps, (), mode, groups, want_logits)
 
-    def _generate_options(self, first_tokens, steps, opt, keep, mode, want_logits):
-        """wrk_v*_generate_stop on prepared options: (tokens [steps, B], lengths [B], steps_run, elapsed ms, last logits or None)."""
+    def _generate_options(self, first_tokens, steps, opt, keep, mode, want_logits, logprobs=None):
+        """wrk_v*_generate_stop on prepared options: (tokens [steps, B], lengths [B], steps_run, elapsed ms, last logits or None).
+        logprobs: the alternatives per row, None for a call without log-probs; sets `last_logprobs`."""
         ft = _u32(first_tokens)
         B = ft.size
         out = np.zeros((steps, B), np.uint32)
         lengths = np.zeros(B, np.uint32)
         run, ms = C.c_uint32(), C.c_float()
         logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
+        self.last_logprobs = None
+        if logprobs is not None:
+            lp, ids, tlp = _logprob_arrays(logprobs, steps * B)
+            opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(ids, _u32p), _ptr(tlp, _f32p)
         fn, mdl = self._entry("generate_stop")
         self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, C.byref(opt), _ptr(out, _u32p), _ptr(lengths, _u32p),
                           _ptr(logits, _f32p) if want_logits else None, C.byref(run), C.byref(ms), mode))
+        if logprobs is not None:
+            n, rows = int(logprobs), run.value * B
+            self.last_logprobs = (lp[:rows].reshape(run.value, B), ids[:rows * n].reshape(run.value, B, n),
+                                  tlp[:rows * n].reshape(run.value, B, n))
         return out, lengths, run.value, ms.value, logits
 
     @staticmethod
@@ -1061,34 +1120,37 @@ class Runtime:
         return (t, p, sd), (_ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p))
 
     def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
-                        groups: int = 1, top_k=None, min_p=None):
+                        groups: int = 1, top_k=None, min_p=None, logprobs=None):
         """As `generate_greedy`, each sequence's next token drawn by `Sampler::sample` (examples/chat.rs:150-190) on the device with its
         own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b.
         top_k / min_p (a scalar or one value per sequence; None: off): the draw is `sample_logits(..., top_k, min_p)`'s; such a call goes
-        through the options entry point (wrk_v*_generate_stop without stop sets) and replays step programs of its own."""
-        if top_k is not None or min_p is not None:
+        through the options entry point (wrk_v*_generate_stop without stop sets) and replays step programs of its own.
+        logprobs: as `generate_greedy`; the log-prob of a drawn token is its probability under the model, not under the sampler."""
+        if top_k is not None or min_p is not None or logprobs is not None:
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
-                                           want_logits, groups)
+                                           want_logits, groups, logprobs)
         keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
         return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
 
     def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
-                           want_logits, groups):
+                           want_logits, groups, logprobs=None):
         opt, keep = GenerateOptions(), []
         _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p)
-        out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits)
+        out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits, logprobs)
         return (out, ms, logits) if want_logits else (out, ms)
 
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
-                           frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1, top_k=None, min_p=None):
+                           frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1, top_k=None, min_p=None,
+                           logprobs=None):
         """As `generate_sample`, each draw made on the logits penalised with the sequence's slot of `occurrence` (ChatRWKV's
         alpha_presence / alpha_frequency / token_ban), and the slot updated after every draw (count *= decay, then the drawn token's
         weight added).  The first token of a call is not counted; the last drawn one is.  The table carries over between calls.
         Scalars broadcast; seed=None: seed[b] = b.  last logits: the head output before penalties.  top_k / min_p: as `generate_sample`,
-        the cuts made on the penalised logits."""
-        if top_k is not None or min_p is not None:
+        the cuts made on the penalised logits.  logprobs: as `generate_greedy`, on the head output before penalties and bans (a banned
+        token may appear among the alternatives)."""
+        if top_k is not None or min_p is not None or logprobs is not None:
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
-                                           min_p, mode, want_logits, groups)
+                                           min_p, mode, want_logits, groups, logprobs)
         B = _u32(first_tokens).size
         keep, rows = self._sampler_rows(B, temperature, top_p, seed)
         pen = [_per_row(v, B, np.float32) for v in (presence, frequency, decay)]
@@ -1097,25 +1159,28 @@ class Runtime:
 
     def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
-                      poll_steps: int = 0, top_k=None, min_p=None):
+                      poll_steps: int = 0, top_k=None, min_p=None, logprobs=None):
         """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
         at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
         MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
         are what the call without stops draws, the stop token last; later rows repeat it.  The state slot, the occurrence slot and the
         logits row of a finished sequence are those of a `lengths[b]`-step call.  steps_run < steps once every sequence has ended (the host
-        looks every `poll_steps` steps; 0: the default).  top_k / min_p: as `generate_sample` (they make the pick a sampled one)."""
+        looks every `poll_steps` steps; 0: the default).  top_k / min_p: as `generate_sample` (they make the pick a sampled one).
+        logprobs: as `generate_greedy`; rows [:lengths[b], b] of `last_logprobs` are those of the call without stops, the stop token's
+        own row included; later rows of a finished sequence are unspecified."""
         ft = _u32(first_tokens)
         ids, off = _stop_csr(stop, ft.size, "sequences")
         opt, keep = GenerateOptions(), []
         _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p)
         opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
-        out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, self._mode(mode, groups), want_logits)
+        out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, self._mode(mode, groups), want_logits,
+                                                                              logprobs)
         out = out[:run]
         return (out, lengths, logits) if want_logits else (out, lengths)
 
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
-                       mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None):
+                       mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1129,7 +1194,9 @@ class Runtime:
         and, ending with reason 1 or 2, leaves its final state -- the prompt and the reply but its last token consumed, what
         `generate_stop` freezes -- in entry save_state[r] (None: nowhere).  Each is one value for all requests or a list; the same entry
         for start and save continues a session in place.  `last_queue_saved[r]` tells whether request r's entry was written.  Two
-        requests may not save to one entry, nor one read an entry another saves to."""
+        requests may not save to one entry, nor one read an entry another saves to.
+        logprobs (None: off; 0..MAX_TOP_LOGPROBS): `last_logprobs[r]` = (logprob [len], top_ids [len, n], top_logprobs [len, n]) of
+        request r's reply tokens, as `generate_greedy`'s; the rows of the steps that feed prompt tokens are discarded."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1155,6 +1222,10 @@ class Runtime:
         run, ms = C.c_uint32(), C.c_float()
         res = QueueResult(_ptr(lengths, _u32p), _ptr(reasons, _u32p), _ptr(slots, _u32p), _ptr(starts, _u32p), _ptr(out, _u32p),
                           C.pointer(run))
+        self.last_logprobs = None
+        if logprobs is not None:
+            lp, ids, tlp = _logprob_arrays(logprobs, int(mn.sum()))
+            opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(ids, _u32p), _ptr(tlp, _f32p)
         if pool is None:
             if start_state is not None or save_state is not None:
                 raise ValueError("start_state / save_state need a pool")
@@ -1175,6 +1246,10 @@ class Runtime:
             self.last_queue_saved = [bool(x) for x in saved[:R]]
         self.last_queue_ms = ms.value
         off = np.concatenate([[0], np.cumsum(mn)]).astype(np.int64)
+        if logprobs is not None:
+            n = int(logprobs)
+            self.last_logprobs = [(lp[off[r]:off[r] + lengths[r]].copy(), ids[off[r] * n:(off[r] + lengths[r]) * n].reshape(-1, n).copy(),
+                                   tlp[off[r] * n:(off[r] + lengths[r]) * n].reshape(-1, n).copy()) for r in range(R)]
         return [(out[off[r]:off[r] + lengths[r]].copy(), int(reasons[r]), int(slots[r]), int(starts[r])) for r in range(R)], run.value
 
     def state_back(self, batch: int) -> np.ndarray:
