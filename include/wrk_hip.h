@@ -337,6 +337,29 @@ int32_t wrk_v7_generate_sample(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* 
 int32_t wrk_sample_logits_filtered(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
                                    const float* temperature, const float* top_p, const uint32_t* top_k, const float* min_p,
                                    const uint32_t* seed, uint32_t step, uint32_t* out_tokens);
+/* Mirostat v2 (Basu et al. 2021, Alg. 2; llama.cpp mirostat_v2) per row, on wrk_sample_logits' row l (NaN as -inf, -0 as +0), its maximum
+ * mx, its order and its u.  Row parameters: tau > 0 (target surprise, bits), eta >= 0 (learning rate) and the state mu (f32).  With
+ *   w_i = exp((l_i - mx) / T), W = sum_i w_i, s_i = log2 W - (l_i - mx) / T * log2 e
+ * the candidates are rank 0 and every token with s_i <= mu (a prefix of the order); the drawn token y is the first rank whose cumulative
+ * weight reaches u * W_c, W_c = the candidates' weight; its observed surprise s = log2 W_c - (l_y - mx) / T * log2 e is renormalised over
+ * the candidates (one candidate: s == 0 exactly); then mu <- mu - eta * (s - tau).  top_p is not read by such a row.  tau[r] == 0 turns
+ * Mirostat off for the row: wrk_sample_logits' token, top_p included, bit for bit, and mu untouched.  temperature == 0 and an all -inf
+ * row are the greedy branch, which leaves mu untouched as well.  tau / eta: host f32 [num_rows] (eta NULL: 0); mu_inout: host f32
+ * [num_rows], the mu each row starts from and, on return, the mu after its draw; NULL: every row starts at 2 tau, a fresh sequence, and
+ * nothing is returned.  WRK_E_ARG before any launch: NaN, negative or non-finite tau / eta, a non-finite mu, a NULL tau.  Blocking. */
+int32_t wrk_sample_logits_mirostat(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                                   const float* temperature, const float* top_p, const float* tau, const float* eta, float* mu_inout,
+                                   const uint32_t* seed, uint32_t step, uint32_t* out_tokens);
+/* Locally typical sampling (Meister et al. 2022; HF TypicalLogitsWarper, llama.cpp typical_p) per row, on the same row, order and u.
+ * With p = softmax(l) at temperature 1, g_i = mx - l_i and gbar = sum_i p_i g_i, a token's distance to the entropy is
+ * d_i = |-ln p_i - H| = |g_i - gbar| (a -inf logit adds 0 to gbar and has d = +inf).  In the typical order -- d ascending, ties by index
+ * ascending -- the token at rank r is a candidate iff the mass sum p before it is <= typical_p: the token that crosses is in, rank 0
+ * always.  The draw is among the candidates in wrk_sample_logits' order with weights p^(1/T).  top_p is not read by such a row.
+ * typical_p[r] >= 1 turns the cut off for the row: wrk_sample_logits' token, top_p included, bit for bit.  temperature == 0 and an
+ * all -inf row are the greedy branch.  typical_p: host f32 [num_rows] in [0, 1] (NaN or outside, or NULL: WRK_E_ARG).  Blocking. */
+int32_t wrk_sample_logits_typical(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                                  const float* temperature, const float* top_p, const float* typical_p, const uint32_t* seed,
+                                  uint32_t step, uint32_t* out_tokens);
 
 /* Sequence scoring on the device, per row of f32 logits [num_rows][row_stride] (first num_vocab used) and its target token t:
  *   logprob = x_t - (m + log sum_i exp(x_i - m)), m = the row max;   rank = #{i : x_i > x_t} + #{i < t : x_i == x_t}
@@ -433,7 +456,19 @@ int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_stat
  * those of the call without log-probs.  num_top is data of the step program: one cached program serves any num_top; log-prob calls
  * replay step programs of their own, a call without them exactly the programs it ran before.  A sequence's log-probs do not depend on
  * the number of lanes.  The log-prob fields sit between poll_steps and the filter fields, which stay the last two: callers that name
- * their fields or start from a zeroed struct keep working after a recompile. */
+ * their fields or start from a zeroed struct keep working after a recompile.
+ * Mirostat v2 and locally typical sampling.  mirostat_tau (host f32 [num_batch]) makes the pick wrk_sample_logits_mirostat's with
+ * (mirostat_tau[b], mirostat_eta[b]; eta NULL: 0) and a mu per sequence that lives in the step program from one draw to the next;
+ * typical_p (host f32 [num_batch]) makes it wrk_sample_logits_typical's.  One call uses one family -- plain, filtered (top_k / min_p),
+ * Mirostat or typical: arrays of two of them, mirostat_eta or mirostat_mu without mirostat_tau, or either new family without the sampler
+ * arrays are WRK_E_ARG, as are the values the two row functions reject.  Both combine with penalties (the pick is made on the
+ * penalised row), with stop sets and with log-probs (which stay on the raw head output).  mirostat_mu (host f32 [num_batch], in/out, may
+ * be NULL): on entry the mu sequence b starts from (NULL: 2 tau, a fresh sequence), on return the mu after the draws of this call that
+ * count -- the draws an occurrence row counts: every step up to and including the one that draws b's stop token, none after it, so
+ * after the call mu[b] has seen exactly out_lengths[b] draws; a session carries mu from call to call through this array.  Tokens and
+ * mu do not depend on the number of lanes.  The parameters are device data: one cached step program per family serves any values;
+ * the two families replay step programs of their own, and a call with all four fields NULL runs exactly the programs it ran before.
+ * The four fields sit between the log-prob fields and the filter fields, which stay the last two. */
 #define WRK_MAX_STOP_TOKENS 16
 typedef struct wrk_generate_options {
     const float *temperature, *top_p;
@@ -446,6 +481,9 @@ typedef struct wrk_generate_options {
     float *out_logprob;
     uint32_t *out_top_ids;
     float *out_top_logprobs;
+    const float *mirostat_tau, *mirostat_eta;
+    float *mirostat_mu;
+    const float *typical_p;
     const uint32_t *top_k;
     const float *min_p;
 } wrk_generate_options;
@@ -489,7 +527,14 @@ int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* st
  * out_top_logprobs[(o_r + j) * num_top ..], as wrk_top_logprobs gives them on the head output y_j was drawn from.  The rows of steps that
  * feed prompt tokens are discarded (prompt log-probs: wrk_v7_score).  out_logprob: host f32 [sum of max_new]; out_top_ids /
  * out_top_logprobs: host [sum of max_new][num_top].  They sit with the options, before the filter fields, as in wrk_generate_options:
- * wrk_queue_result keeps its six arrays. */
+ * wrk_queue_result keeps its six arrays.
+ * mirostat_tau / mirostat_eta / typical_p [num_requests], as in wrk_generate_options: request r's draws are wrk_sample_logits_mirostat's
+ * or wrk_sample_logits_typical's with its own parameters.  mirostat_mu (host f32 [num_requests], in/out, may be NULL): request r starts
+ * from mirostat_mu[r] (NULL: 2 tau[r]) when it is dispatched, at step 0 or at a refill on the device -- never from what its slot's
+ * previous request left -- and only its reply draws move it: the draws of the steps that feed prompt tokens are discarded for mu as
+ * they are for the occurrence row.  On return entry r holds the mu after the request's reply draws for reasons 1, 2 and 3, and is
+ * untouched for reason 0.  A reply and its final mu do not depend on the slot or the step the request was scheduled at.  mu is not part
+ * of a state-pool entry: a session carries it through this array. */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
     const uint32_t *prompt_tokens, *prompt_offsets, *max_new;
@@ -504,6 +549,9 @@ typedef struct wrk_queue_options {
     float *out_logprob;
     uint32_t *out_top_ids;
     float *out_top_logprobs;
+    const float *mirostat_tau, *mirostat_eta;
+    float *mirostat_mu;
+    const float *typical_p;
     const uint32_t *top_k;
     const float *min_p;
 } wrk_queue_options;

@@ -17,8 +17,12 @@ without them -- both through the options entry point without stop sets, so the s
 for the greedy and the sampled pick, alternating, with the run-to-run spread of both; and, as context, the host route: leaving the
 loop after every step to read back last_logits (wall time per step of one-step calls).
 
+A seventh pair of legs (--mirostat TAU,ETA and / or --typical P): the decode loop with the Mirostat v2 / the locally typical pick
+ against the plain sampler loop of the same run -- all through the options entry point without stop sets, so the step
+programs differ by the sampler launch alone -- alternating, with the run-to-run spread of each.  Every call starts from the same state.
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
-                                 [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20]
+                                 [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9]
 
 Prints one JSON object.
 """
@@ -155,6 +159,42 @@ def logprob_leg(rt, first, args):
     return res
 
 
+def alt_leg(rt, first, args):
+    """Medians of the per-step time of generate_stop without stop sets with the plain sampler, and with mirostat= / typical_p=,
+    alternating in one process; every call starts from the same state."""
+    B = len(first)
+    start = [rt.state_read(b) for b in range(B)]
+    skw = dict(temperature=args.temperature, top_p=args.top_p)
+    legs = {"sample": {}}
+    if args.mirostat:
+        tau, eta = (float(x) for x in args.mirostat.split(","))
+        legs["mirostat"] = dict(mirostat=(tau, eta))
+    if args.typical is not None:
+        legs["typical"] = dict(typical_p=args.typical)
+
+    def run(kw):
+        for b in range(B):
+            rt.state_write(start[b], b)
+        tok, _ = rt.generate_stop(first, args.steps, [], poll_steps=POLL_OFF, **skw, **kw)
+        return tok, rt.last_stop_ms / args.steps
+    per = {name: [] for name in legs}
+    distinct = {name: len(np.unique(run(kw)[0])) for name, kw in legs.items()}       # capture and warm up
+    for _ in range(args.reps):
+        for name, kw in legs.items():
+            per[name].append(run(kw)[1])
+    for b in range(B):
+        rt.state_write(start[b], b)
+    bm = float(np.median(per["sample"]))
+    res = {}
+    for name in legs:
+        m = float(np.median(per[name]))
+        res[name] = {"ms_per_step": round(m, 5), "spread_us": round((max(per[name]) - min(per[name])) * 1e3, 2),
+                     "ms_all": [round(x, 5) for x in per[name]], "distinct_tokens": distinct[name]}
+        if name != "sample":
+            res[name]["minus_sample_us"] = round((m - bm) * 1e3, 2)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -170,6 +210,8 @@ def main():
     ap.add_argument("--top-k", type=int, default=None)
     ap.add_argument("--min-p", type=float, default=None)
     ap.add_argument("--logprobs", default=None, help="comma-separated numbers of alternatives, e.g. 0,5,20")
+    ap.add_argument("--mirostat", default=None, help="TAU,ETA, e.g. 5,0.1")
+    ap.add_argument("--typical", type=float, default=None, help="typical_p, e.g. 0.9")
     args = ap.parse_args()
     import wrk
 
@@ -191,6 +233,8 @@ def main():
     kkw = dict(temperature=args.temperature, top_p=1.0, top_k=args.top_k)
     if filt:
         out["filters"] = {"top_k": args.top_k, "min_p": args.min_p}
+    if args.mirostat or args.typical is not None:
+        out["mirostat"], out["typical_p"] = args.mirostat, args.typical
     for B in batches:
         first = [(17 + 101 * b) % (V - 1) for b in range(B)]
         engine = rt.engine_status()[0] if B == 1 else False
@@ -249,6 +293,8 @@ def main():
             out["batches"][-1]["stop"] = stop_leg(rt, first, B, V, args)
         if args.logprobs:
             out["batches"][-1]["logprobs"] = logprob_leg(rt, first, args)
+        if args.mirostat or args.typical is not None:
+            out["batches"][-1]["mirostat_typical"] = alt_leg(rt, first, args)
     if occ is not None:
         occ.close()
     rt.close()

@@ -183,6 +183,18 @@ int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride,
 struct SampleFilter { uint32_t top_k; float ln_min_p; };
 int sample_rows_filtered(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
                          const SampleFilter* filt, const uint32_t* step, uint32_t* out);
+// The two samplers whose candidates are not one of sample_rows' cuts, one SampleAlt per row next to SampleParam.
+// sample_rows_mirostat: Mirostat v2 -- candidates = rank 0 and every token whose surprise log2 W - (l - max) / T * log2 e is <= mu (top_p
+// is not read), then mu <- mu - eta * (s - tau) with s the drawn token's surprise among the candidates; tau == 0: sample_rows' token, bit
+// for bit, mu untouched, and the greedy branch leaves mu alone too.  The update is made iff the row's draw counts: gate == nullptr, or
+// gate[row * gate_stride] == gate_eq (a stop program: StopParam::done == 0; a queue program: QueueSlot::phase == QUEUE_REPLY).
+// sample_rows_typical: locally typical sampling -- candidates = the tokens, by |(max - l) - gbar| ascending (ties by index), whose
+// preceding softmax mass is <= typical_p (top_p is not read); typical_p >= 1: sample_rows' token, bit for bit
+struct SampleAlt { float tau, eta, mu, typical_p; };
+int sample_rows_mirostat(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, SampleAlt* alt,
+                         const uint32_t* gate, uint32_t gate_stride, uint32_t gate_eq, const uint32_t* step, uint32_t* out);
+int sample_rows_typical(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
+                        const SampleAlt* alt, const uint32_t* step, uint32_t* out);
 
 // wrk_score.hip: per row, logprob = x_t - logsumexp(x) and rank = #{x_i > x_t} + #{i < t : x_i == x_t} of the target t = targets[row]
 // (targets < v: the caller validates them).  Each row is split over score_slices(n, v, num_cu) workgroups; part holds n * that many
@@ -249,6 +261,7 @@ struct QueueReq {
     float temperature, top_p, presence, frequency, decay;
     uint32_t stop_count, stop_ids[WRK_MAX_STOP_TOKENS];
     uint32_t top_k; float ln_min_p;     // the request's SampleFilter row (filtered queues)
+    float tau, eta, typical_p;          // the request's SampleAlt row (Mirostat / typical queues); its mu: QueueBufs::alt_mu
 };
 struct QueueSlot { uint32_t req, pos, reply, phase; };
 struct QueueLog { uint32_t length, reason, slot, start_step; };
@@ -259,6 +272,10 @@ struct QueueBufs {
     SampleParam* sample_par;        // the frame's rows, or nullptr (arg-max)
     PenaltyParam* pen_par;          // the frame's rows, or nullptr (no penalties)
     SampleFilter* filter_par;       // the frame's rows, or nullptr (no top-k / min-p)
+    // the frame's rows, or nullptr (neither Mirostat nor typical).  alt_mu [R]: request r's mu -- its start value until it is dispatched,
+    // its final value once it has ended (advance_queue copies it into and out of the slot's row); nullptr unless Mirostat
+    SampleAlt* alt_par = nullptr;
+    float* alt_mu = nullptr;
 };
 // takes advance_tokens' place in a queue program: history <- drawn; per slot the next prompt token or the draw, stop / max_new check,
 // next requests to the slots that ended (ascending slot order), their parameters into the slot's rows, started[b], the log,
@@ -362,6 +379,10 @@ int32_t wrk_sample_pack(wrk_ctx* ctx, const float* temperature, const float* top
                         std::vector<wrk::SampleParam>& out);
 // validated per-sequence filter rows; either array may be NULL (off).  WRK_E_ARG on a min_p that is NaN or outside [0, 1]
 int32_t wrk_filter_pack(wrk_ctx* ctx, const uint32_t* top_k, const float* min_p, uint32_t n, std::vector<wrk::SampleFilter>& out);
+// validated per-sequence SampleAlt rows of a Mirostat call (tau required; eta NULL: 0; mu NULL: 2 tau) or of a typical call (typical_p).
+// WRK_E_ARG on NaN, negative or non-finite tau / eta, a non-finite mu, a typical_p that is NaN or outside [0, 1]
+int32_t wrk_mirostat_pack(wrk_ctx* ctx, const float* tau, const float* eta, const float* mu, uint32_t n, std::vector<wrk::SampleAlt>& out);
+int32_t wrk_typical_pack(wrk_ctx* ctx, const float* typical_p, uint32_t n, std::vector<wrk::SampleAlt>& out);
 
 // device slots of a scoring job (wrk_score.hip): targets u32, logprob f32, rank u32 [cap] and the slice partials [cap][SCORE_MAX_SLICES];
 // ensure() reallocates (after a stream sync) when n > cap and then sets *grown: programs captured with the old pointers must go

@@ -53,7 +53,10 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
             s.reply += 1;
             Q.log[s.req].length = s.reply;
             const uint32_t reason = hit ? 1u : (s.reply == r->max_new ? 2u : 0u);
-            if (reason) { Q.log[s.req].reason = reason; ended = 1; }
+            if (reason) {
+                Q.log[s.req].reason = reason; ended = 1;
+                if (Q.alt_mu) Q.alt_mu[s.req] = Q.alt_par[i].mu;     // the sampler of this step has counted the last draw
+            }
         }                                       // idle: tokens[i] stays, a valid id keeps flowing through the embedding gather
     }
     // exclusive scan of `ended` over the slot index: in-wave by ballot, across the four waves through LDS
@@ -80,6 +83,9 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
                 // reply token j is drawn at step (step + 1) + prompt_len - 1 + j: its sampler step is j whenever it is scheduled
                 if (Q.sample_par) Q.sample_par[i] = SampleParam{q->temperature, q->top_p, q->seed, step + q->prompt_len};
                 if (Q.filter_par) Q.filter_par[i] = SampleFilter{q->top_k, q->ln_min_p};
+                // a refilled slot starts from its own request's mu, not from its predecessor's (a request is dispatched once: its entry
+                // still holds its start value)
+                if (Q.alt_par) Q.alt_par[i] = SampleAlt{q->tau, q->eta, Q.alt_mu ? Q.alt_mu[r] : 0.0f, q->typical_p};
                 if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
                 Q.log[r] = QueueLog{0u, 3u, i, step + 1};
                 started = 1;

@@ -83,7 +83,9 @@ int32_t wrk_score_check(wrk_ctx* ctx, const wrk_job_args& a, uint32_t V, const c
 // What a step program of the decode loops is: how each sequence's next token is picked from head_o, and what follows the pick.
 // A filtered pick is a sampled one and a pool tail is a queue tail by construction; wrk_pick_pack sets `penalized` only with a sampled pick
 struct wrk_step_kind {
-    enum Pick : uint32_t { GREEDY, SAMPLED, FILTERED };         // arg-max / the sampler (wrk_sample.hip) on sample_par / the filtered sampler, also on filter_par
+    // arg-max / the sampler (wrk_sample.hip) on sample_par / the filtered sampler, also on filter_par / the Mirostat v2 sampler, also on
+    // alt_par, whose mu it carries from draw to draw / the typical sampler, also on alt_par
+    enum Pick : uint32_t { GREEDY, SAMPLED, FILTERED, MIROSTAT, TYPICAL };
     enum Tail : uint32_t { PLAIN, STOP, QUEUE, QUEUE_POOL };    // advance_tokens / wrk_stop.hip / wrk_queue.hip / the same with a state pool
     Pick pick = GREEDY;
     bool penalized = false;     // the pick is made on pen_o = head_o penalised with the occurrence rows of pen_par, which then count the draw (wrk_penalty.hip)
@@ -91,11 +93,16 @@ struct wrk_step_kind {
     bool logprobs = false;      // between the pick and the tail, the log-prob launches (wrk_logprob.hip) on head_o and the picked tokens, on lp_par
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
+    bool mirostat() const { return pick == MIROSTAT; }
+    bool alt() const { return pick == MIROSTAT || pick == TYPICAL; }
     bool queue() const { return tail == QUEUE || tail == QUEUE_POOL; }
     bool pool() const { return tail == QUEUE_POOL; }
-    // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25, penalised 26, tail 27-28, log-probs 29 -- above every flag of an
-    // infer job and of a runner's own (wrk_frame_common::key_bits, all below bit 24, ORed into the same word)
-    uint32_t key() const { return (uint32_t)pick << 24 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29; }
+    // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25 and, its third bit, 30 (the first three picks keep the
+    // keys they had with two bits), penalised 26, tail 27-28, log-probs 29 -- above every flag of an infer job and of a runner's own
+    // (wrk_frame_common::key_bits, all below bit 24, ORed into the same word)
+    uint32_t key() const {
+        return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29;
+    }
 };
 
 // ------------------------------------------------------------------ frame state of a model (base of wrk_v7_model / wrk_v6_model)
@@ -130,6 +137,12 @@ struct wrk_frame_common {
     uint32_t sample_par_cap = 0;                // into the step programs, which read them through this pointer)
     wrk::SampleFilter* filter_par = nullptr;   // filtered picks: per-sequence top-k / min-p rows next to sample_par, written before every call
     uint32_t filter_par_cap = 0;
+    // Mirostat / typical picks: per-sequence (tau, eta, mu, typical_p) rows next to sample_par, written before every call; the
+    // Mirostat sampler rewrites a row's mu at every draw that counts, and the call reads the rows back.  alt_mu [alt_mu_cap]: a queue's
+    // per-request mu (wrk::QueueBufs::alt_mu)
+    wrk::SampleAlt* alt_par = nullptr;
+    float* alt_mu = nullptr;
+    uint32_t alt_par_cap = 0, alt_mu_cap = 0;
     wrk::PenaltyParam* pen_par = nullptr;      // generate_penalized: per-sequence occurrence rows and penalties, written before every call
     float* pen_o = nullptr;                     // (the step programs read the table's pointers from here); pen_o: penalised logits [B][V]
     uint32_t pen_cap = 0;
@@ -192,7 +205,7 @@ struct wrk_frame_common {
     // the ensure_* reallocate after a stream sync and drop the captured programs, which hold the old pointers; never inside a capture
     void drop_graphs();
     // the buffers an ensure_* reallocates together; bufs(g): their pointers, the one list regrow and release_common go through
-    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, LOGPROB, NUM_GROUPS };
+    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, LOGPROB, ALT, NUM_GROUPS };
     std::vector<void**> bufs(Group g);
     // sync, drop the programs (`drop`), free the buffers and allocate them again; after a failure all of them are freed
     // bytes: one size per buffer of bufs(g), in its order.  The caller sets its caps after WRK_OK: an error leaves them as they were
@@ -200,6 +213,7 @@ struct wrk_frame_common {
     int32_t ensure_history(size_t n);
     int32_t ensure_sample_params(uint32_t n);
     int32_t ensure_filter_params(uint32_t n);
+    int32_t ensure_alt_params(uint32_t n, uint32_t requests);
     int32_t ensure_penalty(uint32_t n, uint32_t num_vocab);
     int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
     int32_t ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens);
@@ -221,16 +235,19 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
 
 // ------------------------------------------------------------------ the decode loops (generate_greedy ... generate_queue)
 // the ABI's pick arrays, of wrk_generate_options / wrk_queue_options (wrk_pick_of) or of an entry point's own arguments, validated in
-// one place (WRK_E_ARG): all three sampler arrays or none (the arg-max); penalty arrays only with a table; a table or a filter only
-// with the sampler arrays.  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
+// one place (WRK_E_ARG): all three sampler arrays or none (the arg-max); penalty arrays only with a table; a table, a filter, Mirostat
+// or typical only with the sampler arrays; one family of filter / Mirostat / typical per call.  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
 struct wrk_pick_args {
     const float *temperature = nullptr, *top_p = nullptr; const uint32_t* seed = nullptr;
     const float *presence = nullptr, *frequency = nullptr, *decay = nullptr; wrk_occurrence* occ = nullptr;
     const uint32_t* top_k = nullptr; const float* min_p = nullptr;      // either set: a filtered pick
+    const float *mirostat_tau = nullptr, *mirostat_eta = nullptr; float* mirostat_mu = nullptr;     // tau set: a Mirostat pick; mu: in / out
+    const float* typical_p = nullptr;                                   // set: a typical pick
     enum Need { ANY, SAMPLER, TABLE } need = ANY;
 };
 template <class Options> wrk_pick_args wrk_pick_of(const Options& o) {
-    return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p};
+    return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p,
+            o.mirostat_tau, o.mirostat_eta, o.mirostat_mu, o.typical_p};
 }
 // the log-prob outputs of a call (wrk_generate_options / wrk_queue_options); logprob NULL: off
 struct wrk_logprob_call {

@@ -79,6 +79,7 @@ std::vector<void**> wrk_frame_common::bufs(Group g) {
         case HISTORY: return {(void**)&history};
         case SAMPLE: return {(void**)&sample_par};
         case FILTER: return {(void**)&filter_par};
+        case ALT: return {(void**)&alt_par, (void**)&alt_mu};
         case PENALTY: return {(void**)&pen_par, (void**)&pen_o};
         case STOP: return {(void**)&stop_par, (void**)&stop_flags, (void**)&stop_snap_state, (void**)&stop_snap_logits};
         case QUEUE: return {(void**)&queue_slots, (void**)&queue_started, (void**)&queue_ctl, (void**)&queue_reqs, (void**)&queue_log, (void**)&queue_pool};
@@ -123,6 +124,18 @@ int32_t wrk_frame_common::ensure_filter_params(uint32_t n) {
     if (n <= filter_par_cap && filter_par) return WRK_OK;
     const int32_t rc = regrow(FILTER, {(size_t)n * sizeof(wrk::SampleFilter)}, true);
     if (rc == WRK_OK) filter_par_cap = n;
+    return rc;
+}
+
+int32_t wrk_frame_common::ensure_alt_params(uint32_t n, uint32_t requests) {
+    if (requests < 1) requests = 1;
+    if (alt_par && n <= alt_par_cap && requests <= alt_mu_cap) return WRK_OK;
+    if (n < alt_par_cap) n = alt_par_cap;
+    if (requests < alt_mu_cap) requests = alt_mu_cap;
+    // Mirostat / typical programs hold the old pointers; before the first allocation none exists
+    const int32_t rc = regrow(ALT, {(size_t)n * sizeof(wrk::SampleAlt), (size_t)requests * 4}, alt_par != nullptr);
+    alt_par_cap = rc == WRK_OK ? n : 0;
+    alt_mu_cap = rc == WRK_OK ? requests : 0;
     return rc;
 }
 
@@ -198,6 +211,7 @@ void wrk_frame_common::release_common() {
     for (int g = 0; g < NUM_GROUPS; ++g)
         for (void** p : bufs((Group)g)) { if (*p) hipFree(*p); *p = nullptr; }
     history_cap = 0; stop_slot_cap = 0; queue_pool_cap = 0; lp_rows_cap = 0; lp_batch_cap = 0;
+    alt_par_cap = alt_mu_cap = 0;
     sample_par_cap = filter_par_cap = pen_cap = stop_cap = stop_vocab_cap = queue_slot_cap = queue_req_cap = queue_turn_cap = queue_entry_cap = 0;
     score.release();
     if (live_host) hipHostFree(live_host);
@@ -259,6 +273,8 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
 // ------------------------------------------------------------------ decode loops: validation and upload
 struct wrk_pick_params {    // validated rows; empty: the arg-max / without penalties / without filters
     std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
+    std::vector<wrk::SampleAlt> alt;        // Mirostat / typical rows
+    uint32_t alt_requests = 0;              // a queue: its requests (the size of the frame's per-request mu array)
 };
 
 // The one validation of the pick arrays (wrk_pick_args).  Sets kind.pick / kind.penalized and packs `n` rows; penalty row r names slot r
@@ -271,12 +287,20 @@ static int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, u
     WRK_ARG(ctx, a.occ || (!a.presence && !a.frequency && !a.decay), "penalty arrays without an occurrence table");
     WRK_ARG(ctx, !a.occ || given == 3, "penalties need the sampler arrays");
     WRK_ARG(ctx, (!a.top_k && !a.min_p) || given == 3, "top_k / min_p need the sampler arrays");
-    kind.pick = given == 0 ? wrk_step_kind::GREEDY : (a.top_k || a.min_p) ? wrk_step_kind::FILTERED : wrk_step_kind::SAMPLED;
+    const bool filt = a.top_k || a.min_p, miro = a.mirostat_tau || a.mirostat_eta || a.mirostat_mu, typ = a.typical_p != nullptr;
+    WRK_ARG(ctx, !miro || a.mirostat_tau, "mirostat_eta / mirostat_mu without mirostat_tau");
+    WRK_ARG(ctx, (int)filt + (int)miro + (int)typ <= 1, "one family per call: top_k / min_p, mirostat_* or typical_p");
+    WRK_ARG(ctx, (!miro && !typ) || given == 3, "mirostat_* / typical_p need the sampler arrays");
+    kind.pick = given == 0 ? wrk_step_kind::GREEDY : filt ? wrk_step_kind::FILTERED : miro ? wrk_step_kind::MIROSTAT
+                           : typ ? wrk_step_kind::TYPICAL : wrk_step_kind::SAMPLED;
     kind.penalized = a.occ != nullptr;
     if (!kind.sampled()) return WRK_OK;
     WRK_ARG(ctx, n >= 1, "a sampled pick of no rows");
     int32_t rc = wrk_sample_pack(ctx, a.temperature, a.top_p, a.seed, n, out.par);
     if (rc == WRK_OK && kind.filtered()) rc = wrk_filter_pack(ctx, a.top_k, a.min_p, n, out.filt);
+    if (rc == WRK_OK && miro) rc = wrk_mirostat_pack(ctx, a.mirostat_tau, a.mirostat_eta, a.mirostat_mu, n, out.alt);
+    if (rc == WRK_OK && typ) rc = wrk_typical_pack(ctx, a.typical_p, n, out.alt);
+    if (rc == WRK_OK && kind.alt() && V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
     if (rc != WRK_OK || !kind.penalized) return rc;
     WRK_ARG(ctx, a.decay, "decay array required");
     WRK_ARG(ctx, a.occ->num_batch >= slots, "occurrence table of %u slots, %u state slots", a.occ->num_batch, slots);
@@ -360,9 +384,11 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     const wrk::SampleParam* par = rows.par.empty() ? nullptr : rows.par.data() + b0;
     const wrk::PenaltyParam* pen = rows.pen.empty() ? nullptr : rows.pen.data() + b0;
     const wrk::SampleFilter* filt = rows.filt.empty() ? nullptr : rows.filt.data() + b0;
+    const wrk::SampleAlt* alt = rows.alt.empty() ? nullptr : rows.alt.data() + b0;
     int32_t rc = f.ensure_history((size_t)steps * B);
     if (rc == WRK_OK && par) rc = f.ensure_sample_params(B);
     if (rc == WRK_OK && filt) rc = f.ensure_filter_params(B);
+    if (rc == WRK_OK && alt) rc = f.ensure_alt_params(B, rows.alt_requests);
     if (rc == WRK_OK && pen) rc = f.ensure_penalty(B, f.facts().num_vocab);
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
@@ -372,6 +398,7 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.tokens, first_tokens + b0, (size_t)B * 4);
     if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, f.sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
     if (rc == WRK_OK && filt) rc = wrk_buf_write_raw(ctx, f.filter_par, filt, (size_t)B * sizeof(wrk::SampleFilter));
+    if (rc == WRK_OK && alt) rc = wrk_buf_write_raw(ctx, f.alt_par, alt, (size_t)B * sizeof(wrk::SampleAlt));
     if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, f.pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
     if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipMemsetAsync(io.counter, 0, 4, ctx->stream));
@@ -416,6 +443,8 @@ struct wrk_queue_pack {
     std::vector<uint32_t> start, save;
     uint32_t* saved_out = nullptr;
     wrk_logprob_call lp;        // the options' log-prob arrays and num_top
+    std::vector<float> mu;      // Mirostat / typical: [R] the mu every request starts from
+    float* mu_out = nullptr;    // Mirostat: the options' mirostat_mu, or nullptr
 };
 
 static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
@@ -455,6 +484,8 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
         if (kind.sampled()) { q.temperature = req.par[r].temperature; q.top_p = req.par[r].top_p; q.seed = req.par[r].seed; }
         q.ln_min_p = -INFINITY;
         if (kind.filtered()) { q.top_k = req.filt[r].top_k; q.ln_min_p = req.filt[r].ln_min_p; }
+        q.typical_p = 1.0f;
+        if (kind.alt()) { q.tau = req.alt[r].tau; q.eta = req.alt[r].eta; q.typical_p = req.alt[r].typical_p; }
         if (kind.penalized) { q.presence = req.pen[r].presence; q.frequency = req.pen[r].frequency; q.decay = req.pen[r].decay; }
         q.stop_count = stops[r].count;
         memcpy(q.stop_ids, stops[r].ids, sizeof q.stop_ids);
@@ -470,12 +501,20 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     if (kind.sampled()) pk.rows.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
     if (kind.penalized) pk.rows.pen.resize(B);
     if (kind.filtered()) pk.rows.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
+    if (kind.alt()) {
+        pk.rows.alt.assign(B, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
+        pk.rows.alt_requests = R;
+        pk.mu.resize(R);
+        for (uint32_t r = 0; r < R; ++r) pk.mu[r] = req.alt[r].mu;
+        pk.mu_out = kind.mirostat() ? opt->mirostat_mu : nullptr;
+    }
     for (uint32_t b = 0; b < B; ++b) {
         const uint32_t r = b < R ? b : 0;       // idle slots: any valid row
         const wrk::QueueReq& q = pk.reqs[r];
         if (b < R) pk.first_tokens[b] = pk.pool[q.prompt_off];
         if (kind.sampled() && b < R) pk.rows.par[b] = wrk::SampleParam{q.temperature, q.top_p, q.seed, q.prompt_len - 1};
         if (kind.filtered() && b < R) pk.rows.filt[b] = wrk::SampleFilter{q.top_k, q.ln_min_p};
+        if (kind.alt() && b < R) pk.rows.alt[b] = req.alt[b];
         if (kind.penalized) pk.rows.pen[b] = opt->occ->row(b, q.presence, q.frequency, q.decay);
     }
     return WRK_OK;
@@ -524,7 +563,8 @@ static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, co
 
 static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
     return wrk::QueueBufs{f.queue_slots, f.queue_reqs, f.queue_pool, f.queue_log, f.queue_ctl, f.queue_started,
-                          kind.sampled() ? f.sample_par : nullptr, kind.penalized ? f.pen_par : nullptr, kind.filtered() ? f.filter_par : nullptr};
+                          kind.sampled() ? f.sample_par : nullptr, kind.penalized ? f.pen_par : nullptr, kind.filtered() ? f.filter_par : nullptr,
+                          kind.alt() ? f.alt_par : nullptr, kind.mirostat() ? f.alt_mu : nullptr};
 }
 
 static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f) {
@@ -560,6 +600,10 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_reqs, pk.reqs.data(), (size_t)pk.R * sizeof(wrk::QueueReq));
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_pool, pk.pool.data(), pk.pool.size() * 4);
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_ctl, &ctl, sizeof ctl);
+    if (rc == WRK_OK && pk.kind.mirostat()) {
+        if (!f.alt_mu || pk.R > f.alt_mu_cap) return wrk_fail(ctx, WRK_E_ARG, "Mirostat rows are not prepared");
+        rc = wrk_buf_write_raw(ctx, f.alt_mu, pk.mu.data(), (size_t)pk.R * 4);
+    }
     if (rc == WRK_OK && pk.kind.pool()) {
         // the turnover list of "step -1": the slots that start at step 0, nothing to save
         std::vector<wrk::QueueTurn> turn(nstart);
@@ -617,6 +661,13 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         WRK_HIP(ctx, hipMemcpyAsync(top_id.data(), f.lp_top_ids, top_id.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         WRK_HIP(ctx, hipMemcpyAsync(top_lp.data(), f.lp_top_logprobs, top_lp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
+    // Mirostat: a request that ended left its mu in alt_mu[r]; one still running has it in its slot's row
+    std::vector<float> mu_req(pk.mu_out ? pk.R : 0);
+    std::vector<wrk::SampleAlt> mu_slot(pk.mu_out ? B : 0);
+    if (pk.mu_out) {
+        WRK_HIP(ctx, hipMemcpyAsync(mu_req.data(), f.alt_mu, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(mu_slot.data(), f.alt_par, (size_t)B * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost, ctx->stream));
+    }
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     size_t o = 0;
     for (uint32_t r = 0; r < pk.R; ++r) {
@@ -628,6 +679,7 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         if (g.length > q.max_new || g.slot >= B || (g.length && (size_t)g.start_step + q.prompt_len - 1 + g.length > steps_run))
             return wrk_fail(ctx, WRK_E_HIP, "request %u: inconsistent queue log (length %u slot %u start %u)", r, g.length, g.slot, g.start_step);
         out->lengths[r] = g.length; out->reasons[r] = g.reason; out->slots[r] = g.slot; out->start_steps[r] = g.start_step;
+        if (pk.mu_out && g.reason != 0) pk.mu_out[r] = g.reason == 3 ? mu_slot[g.slot].mu : mu_req[r];
         // the step that gave the request reason 1 or 2 also wrote its state to its entry (queue_turnover)
         if (pk.saved_out) pk.saved_out[r] = pk.save[r] != wrk::QUEUE_NO_ENTRY && (g.reason == 1 || g.reason == 2);
         for (uint32_t j = 0; j < g.length; ++j) {
@@ -678,9 +730,27 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     if (!kind.sampled()) {
         if (!argmax_done) wrk::argmax_rows(q, io.head_o, V, V, B, io.argmax);
     } else if (kind.filtered() && (!f.filter_par || B > f.filter_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
-    else if ((kind.filtered() ? wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax)
-                              : wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax)) != 0)
-        return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    else if (kind.alt() && (!f.alt_par || B > f.alt_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "Mirostat / typical rows are not prepared");
+    else {
+        int rc = 0;
+        if (kind.mirostat()) {
+            // mu moves exactly where an occurrence row counts a draw: the sampler reads the flag the tail's occurrence update reads --
+            // written by the previous step's advance -- so a finished sequence, a prompt-phase or an idle slot leaves mu alone
+            const uint32_t* gate = nullptr;
+            uint32_t stride = 0, eq = 0;
+            if (kind.tail == wrk_step_kind::STOP) {
+                if (!f.stop_par || B > f.stop_cap) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
+                gate = &f.stop_par->done; stride = sizeof(wrk::StopParam) / 4; eq = 0;
+            } else if (kind.queue()) {
+                if (!f.queue_slots || B > f.queue_slot_cap) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+                gate = &f.queue_slots->phase; stride = sizeof(wrk::QueueSlot) / 4; eq = wrk::QUEUE_REPLY;
+            }
+            rc = wrk::sample_rows_mirostat(q, logits, V, V, B, f.sample_par, f.alt_par, gate, stride, eq, io.counter, io.argmax);
+        } else if (kind.pick == wrk_step_kind::TYPICAL) rc = wrk::sample_rows_typical(q, logits, V, V, B, f.sample_par, f.alt_par, io.counter, io.argmax);
+        else if (kind.filtered()) rc = wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax);
+        else rc = wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax);
+        if (rc != 0) return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
+    }
     // the picked tokens are in io.argmax and the tail has not moved the counter: row *counter of the frame's buffers, on the raw head output
     if (kind.logprobs) {
         if (!f.lp_par || B > f.lp_batch_cap) return wrk_fail(f.ctx, WRK_E_ARG, "log-prob buffers are not prepared");
@@ -892,6 +962,12 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
     const wrk_stop_run run{stop ? stop->opt->poll_steps : 0u, stop ? stop->out_lengths : nullptr, stop ? stop->steps_run : nullptr};
     rc = wrk_run_lanes(ctx, L, st, B, steps, mode, kind, out_tokens, last_logits, elapsed_ms, run, lp);
     if (rc != WRK_OK) return rc;
+    if (kind.mirostat() && pick.mirostat_mu) {      // every lane's rows hold the mu after the draws that counted
+        for (const wrk_lane& ln : L) {
+            WRK_HIP(ctx, hipMemcpy(rows.alt.data() + ln.b0, ln.frame->alt_par, (size_t)ln.nb * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost));
+            for (uint32_t b = ln.b0; b < ln.b0 + ln.nb; ++b) pick.mirostat_mu[b] = rows.alt[b].mu;
+        }
+    }
     return m->after_loop(groups);
 }
 

@@ -15,7 +15,15 @@
 // nucleus's descent: each pass finds the bin the mass target chooses and the bin the count target chooses; the higher bin (the earlier
 // rank) wins and the other target is dropped, equal bins descend with both.  The min-p cut, fl32(l - mx) >= ln(min_p), is part of the
 // draw's candidate predicate.
+//
+// sample_rows_mirostat_kernel and sample_rows_typical_kernel (DESIGN.md "Mirostat v2 and locally typical sampling") share the body too.
+// Mirostat: one full-row mass pass gives W; "rank 0, or surprise <= mu" is a term of the draw's candidate predicate; no boundary descent;
+// the draw's pass-0 total is W_c, from which one lane takes the drawn token's surprise and writes the next mu.  Typical: one moments
+// pass (sum e and sum e g in fixed point, g = max - l) gives gbar; the boundary is the nucleus's mass select over the key
+// monotone(-d) << 20 | (2^20 - 1 - index), d = |g - gbar|, with the pass-0 digit taken from the range of d; the draw's candidates are
+// the tokens whose d-key is >= the boundary's.  The descent is one lambda, generic in which key it walks.
 #include <cmath>
+#include <type_traits>
 
 #include "wrk_device.h"
 
@@ -24,6 +32,9 @@ namespace wrk {
 static constexpr uint32_t SAMPLE_BINS = 2048;
 static constexpr uint32_t SAMPLE_THREADS = 1024;
 static constexpr float SAMPLE_ONE = 1099511627776.0f;      // 2^40: mass of the row's top token
+// the largest register copy (tokens per thread) of the Mirostat / typical kernels that does not spill; longer rows are
+// re-read from L2
+static constexpr int MIRO_NPT_MAX = 8, TYP_NPT_MAX = 8;
 
 __host__ __device__ inline uint64_t sample_splitmix(uint32_t seed, uint32_t step) {
     uint64_t z = (((uint64_t)seed << 32) | step) + 0x9E3779B97F4A7C15ull;
@@ -43,6 +54,17 @@ __device__ __forceinline__ uint32_t coarse_digit(float l, float mx, float scale)
     const float d = l == mx ? 0.0f : (mx - l) * scale;
     return (SAMPLE_BINS - 1) - (uint32_t)fminf(d, (float)(SAMPLE_BINS - 1));
 }
+
+// typical order: d = |(mx - l) - gbar| ascending, ties by index ascending; d >= 0 or +inf (a -inf logit), never NaN
+__device__ __forceinline__ float typical_dist(float l, float mx, float gbar) { return fabsf((l == mx ? 0.0f : mx - l) - gbar); }
+__device__ __forceinline__ uint64_t typical_key(float d, uint32_t i) {
+    return ((uint64_t)(0x7FFFFFFFu - __float_as_uint(d)) << 20) | (0xFFFFFu - i);     // monotone(-d) of a d >= 0
+}
+__device__ __forceinline__ uint32_t typical_digit(float d, float scale) {
+    return (SAMPLE_BINS - 1) - (uint32_t)fminf(d * scale, (float)(SAMPLE_BINS - 1));
+}
+
+static constexpr float SAMPLE_LOG2E = 1.44269504088896340736f;
 
 struct SampleSmem {
     unsigned long long mass[SAMPLE_BINS];
@@ -105,15 +127,34 @@ __device__ __forceinline__ unsigned long long block_excl_scan2(unsigned long lon
     return before + x - v;
 }
 
+// sum of v over the workgroup (same value in every thread); an integer sum: independent of the order
+__device__ __forceinline__ unsigned long long block_sum(unsigned long long v, SampleSmem& sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+    __syncthreads();            // the readers of an earlier wsum are done
+    if ((threadIdx.x & 63) == 0) sm.wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < SAMPLE_THREADS / WAVE; ++w) all += sm.wsum[w];
+    return all;
+}
+
 static constexpr uint32_t SAMPLE_NO_COUNT = 0xffffffffu;
+enum : int { SAMPLE_PLAIN = 0, SAMPLE_FILT = 1, SAMPLE_MIRO = 2, SAMPLE_TYP = 3 };
+// of a Mirostat row: whether its draw counts (moves mu); gate == nullptr: always
+struct SampleGate { const uint32_t* gate; uint32_t stride, eq; };
 
 // One row per workgroup.  NPT > 0: the row (V <= 1024 * NPT) stays in registers; NPT == 0: every pass re-reads it from L2 (V <= 2^20;
 // a 64-per-thread register copy of a 65536-token row spills, the passes' own state needs ~95 VGPRs)
-// FILT: the filtered kernel's body (filt: one SampleFilter per row); every addition sits under `if constexpr (FILT)`
-template <int NPT, bool FILT>
+// MODE SAMPLE_FILT: the filtered kernel's body (filt: one SampleFilter per row); every addition sits under `if constexpr (FILT)`.
+// SAMPLE_MIRO / SAMPLE_TYP: the Mirostat / typical kernel's (alt: one SampleAlt per row); additions under `if constexpr (MIRO)` / `(TYP)`
+template <int NPT, int MODE>
 __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __restrict__ logits, uint32_t V, uint32_t stride,
                                                  const SampleParam* __restrict__ par, const SampleFilter* __restrict__ filt,
+                                                 SampleAlt* alt, const SampleGate gate,
                                                  const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
+    constexpr bool FILT = MODE == SAMPLE_FILT, MIRO = MODE == SAMPLE_MIRO, TYP = MODE == SAMPLE_TYP;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* row = logits + (size_t)blockIdx.x * stride;
     const int nj = NPT > 0 ? NPT : (int)((V + SAMPLE_THREADS - 1) / SAMPLE_THREADS);
@@ -129,7 +170,7 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
     }
     // f(j, logit) over this thread's elements; from memory, 16 loads are issued ahead of their use (one at a time, every pass would pay the
     // L2 latency 64 times over)
-    auto for_each = [&](auto&& f) {
+    auto for_each = [&](auto&& f) __attribute__((always_inline)) {
         if constexpr (NPT > 0) {
 #pragma unroll
             for (int j = 0; j < NPT; ++j) f(j, lv[j]);
@@ -174,7 +215,17 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
     if (!(scale > 0.0f) || !(scale < INFINITY)) scale = 64.0f;
 
     const SampleParam pr = par[blockIdx.x];
-    const float temp = pr.temperature, top_p = pr.top_p;
+    const float temp = pr.temperature;
+    float top_p = pr.top_p;
+    bool miro = false, typ = false;     // the row's own sampler is on (off: a plain sampler row)
+    float tau = 0.0f, eta = 0.0f, mu = 0.0f, typical_p = 1.0f;
+    if constexpr (MIRO || TYP) {
+        const SampleAlt a = alt[blockIdx.x];
+        tau = a.tau; eta = a.eta; mu = a.mu; typical_p = a.typical_p;
+        miro = MIRO && tau > 0.0f;
+        typ = TYP && !(typical_p >= 1.0f);
+        if (miro || typ) top_p = 1.0f;      // not read by such a row: neither its greedy test nor a nucleus cut
+    }
     uint32_t top_k = 0;             // 0: no top-k cut (top_k >= V cuts nothing either)
     float ln_min_p = -INFINITY;
     if constexpr (FILT) {
@@ -188,13 +239,51 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
     }
     const float inv_t = 1.0f / temp;
 
+    // Mirostat: W in fixed point over the whole row -> log2 W; a token is a candidate iff it is rank 0 or its surprise is <= mu
+    float log2_w = 0.0f;
+    if constexpr (MIRO) {
+        if (miro) {
+            unsigned long long acc = 0;
+            for_each([&](int j, float l) {
+                if (tid + SAMPLE_THREADS * (uint32_t)j < V) acc += (unsigned long long)((l == mx ? 1.0f : expf((l - mx) * inv_t)) * SAMPLE_ONE);
+            });
+            log2_w = log2f((float)block_sum(acc, sm)) - 40.0f;
+        }
+    }
+    // typical: gbar = sum e g / sum e with e = exp(l - mx), g = mx - l, both sums in fixed point (e g <= 1 / e: no overflow below 2^20 tokens);
+    // a -inf logit adds nothing to either.  The pass-0 digit of the d-key spreads [0, max d] over the bins
+    float gbar = 0.0f, dscale = 64.0f;
+    if constexpr (TYP) {
+        if (typ) {
+            unsigned long long se = 0, seg = 0;
+            for_each([&](int j, float l) {      // branch-free: two accumulators updated under different branches end up in scratch
+                const bool in = tid + SAMPLE_THREADS * (uint32_t)j < V && l > -INFINITY;
+                const float g = l == mx ? 0.0f : mx - l, e = l == mx ? 1.0f : expf(l - mx);
+                const float eg = in && e > 0.0f ? e * g : 0.0f;     // mx = +inf: g = inf next to e = 0
+                se += in ? (unsigned long long)(e * SAMPLE_ONE) : 0ull;
+                seg += (unsigned long long)(eg * SAMPLE_ONE);
+            });
+            se = block_sum(se, sm);
+            seg = block_sum(seg, sm);
+            gbar = (float)((double)seg / (double)se);
+            const float dmax = fmaxf(gbar, (mx - low) - gbar);      // low: the smallest finite logit (mx = +inf: inf, the scale falls back)
+            dscale = (float)(SAMPLE_BINS - 1) / dmax;
+            if (!(dscale > 0.0f) || !(dscale < INFINITY)) dscale = 64.0f;
+        }
+    }
+    unsigned long long draw_total = 0;      // Mirostat: W_c, the draw's pass-0 total
+
     // Weighted select over K among the tokens with K >= kmin.  use_w = false: masses e = exp(l - mx); the LAST rank whose mass before
     // it is <= P * sum (the nucleus boundary).  use_w = true: masses w = exp((l - mx) / T); the FIRST rank whose mass up to and
     // including it is >= u * sum (the draw).  Returns the token index.
     // FILT, boundary only: by_mass = false drops the mass target (no mass atomics, no expf); ktarget != SAMPLE_NO_COUNT adds the count
     // target, the LAST rank with at most ktarget tokens before it.  The earlier of the two ranks is returned.  FILT, draw: the candidates
     // also pass the min-p test
-    auto select = [&](bool use_w, uint64_t kmin, bool by_mass, uint32_t ktarget) -> uint32_t {
+    // DK (TYP only): std::true_type walks the typical order -- key typical_key, digit typical_digit -- for the boundary; the draw walks
+    // the sampler's order with "typical_key >= kmin" as its candidate predicate
+    // (always inlined: the typical kernel has three call sites, and a call would put the captured row state into scratch)
+    auto select = [&](auto DK, bool use_w, uint64_t kmin, bool by_mass, uint32_t ktarget) __attribute__((always_inline)) -> uint32_t {
+        constexpr bool dkey = decltype(DK)::value;
         bool live_p = FILT ? by_mass : true;                        // the target is still inside the chosen bins
         bool live_k = FILT ? ktarget != SAMPLE_NO_COUNT : false;
         uint32_t cbase = 0;             // number of the candidates' predecessors
@@ -218,11 +307,27 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
             __syncthreads();
             for_each([&](int j, float l) {
                 const uint32_t i = tid + SAMPLE_THREADS * (uint32_t)j;
-                const uint64_t k = rank_key(l, i);
-                const uint32_t c = coarse_digit(l, mx, scale);
-                bool cand = i < V && k >= kmin;
+                uint64_t k;
+                uint32_t c;
+                bool cand;
+                if constexpr (dkey) {
+                    const float d = typical_dist(l, mx, gbar);
+                    k = typical_key(d, i);
+                    c = typical_digit(d, dscale);
+                    cand = i < V;
+                } else {
+                    k = rank_key(l, i);
+                    c = coarse_digit(l, mx, scale);
+                    cand = i < V && k >= kmin;
+                    if constexpr (TYP) {
+                        if (typ) cand = i < V && typical_key(typical_dist(l, mx, gbar), i) >= kmin;
+                    }
+                }
                 if constexpr (FILT) {
                     if (use_w) cand = cand && (l == mx || l - mx >= ln_min_p);      // rank 0 always passes (mx = +inf: inf - inf is NaN)
+                }
+                if constexpr (MIRO) {
+                    if (miro) cand = cand && (i == top || log2_w - (l - mx) * inv_t * SAMPLE_LOG2E <= mu);      // rank 0 always passes
                 }
                 if (p >= 1) cand = cand && c == sel0;
                 if (p >= 2) cand = cand && (k >> lo) == prefix;
@@ -248,12 +353,13 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
             const unsigned long long above_l = above_h + mh;
             if (p == 0) {
                 if (!use_w) {
-                    if (live_p) target = (unsigned long long)floor((double)top_p * (double)total);
+                    if (live_p) target = (unsigned long long)floor((double)(dkey ? typical_p : top_p) * (double)total);
                 } else {          // ceil(u * W), u = U / 2^24, in 128-bit integer arithmetic
                     const unsigned long long U = sample_splitmix(pr.seed, *step_word - pr.step_base) >> 40;
                     const unsigned long long plo = U * total, phi = __umul64hi(U, total);
                     target = (phi << 40) | (plo >> 24);
                     if (plo & 0xFFFFFFull) ++target;
+                    if constexpr (MIRO) draw_total = total;
                 }
             }
             if (!use_w) {
@@ -310,12 +416,31 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
     uint64_t kmin = 0;              // P >= 1: every token is in the nucleus
     const bool cut_p = !(top_p >= 1.0f), cut_k = FILT && top_k != 0;
     if (cut_p || cut_k) {           // kmin = max(kmin_P, kmin_K) in one descent; with cut_k alone it is count-only
-        const uint32_t r = select(false, 0, cut_p, cut_k ? top_k - 1u : SAMPLE_NO_COUNT);
+        const uint32_t r = select(std::false_type{}, false, 0, cut_p, cut_k ? top_k - 1u : SAMPLE_NO_COUNT);
         const float lr = row[r];       // r < V: a token index
         kmin = rank_key(lr != lr ? -INFINITY : lr + 0.0f, r);
     }
-    const uint32_t tok = select(true, kmin, true, SAMPLE_NO_COUNT);
-    if (tid == 0) out[blockIdx.x] = tok;
+    if constexpr (TYP) {
+        if (typ) {                  // the boundary of the typical order; the draw's kmin is a d-key
+            const uint32_t r = select(std::true_type{}, false, 0, true, SAMPLE_NO_COUNT);
+            const float lr = row[r];
+            kmin = typical_key(typical_dist(lr != lr ? -INFINITY : lr + 0.0f, mx, gbar), r);
+        }
+    }
+    const uint32_t tok = select(std::false_type{}, true, kmin, true, SAMPLE_NO_COUNT);
+    if (tid == 0) {
+        out[blockIdx.x] = tok;
+        if constexpr (MIRO) {
+            // the drawn token's surprise among the candidates, its own term from its logit (a weight of 2^-30 keeps ten bits in fixed point)
+            if (miro && (!gate.gate || gate.gate[(size_t)blockIdx.x * gate.stride] == gate.eq)) {
+                float ly = row[tok];
+                ly = ly != ly ? -INFINITY : ly + 0.0f;
+                const float x = ly == mx ? 0.0f : (ly - mx) * inv_t;
+                const float s = (log2f((float)draw_total) - 40.0f) - x * SAMPLE_LOG2E;
+                alt[blockIdx.x].mu = mu - eta * (s - tau);
+            }
+        }
+    }
 }
 
 template <int NPT>
@@ -323,7 +448,7 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float
                                                                      const SampleParam* __restrict__ par, const uint32_t* __restrict__ step_word,
                                                                      uint32_t* __restrict__ out) {
     __shared__ SampleSmem sm;
-    sample_rows_body<NPT, false>(sm, logits, V, stride, par, nullptr, step_word, out);
+    sample_rows_body<NPT, SAMPLE_PLAIN>(sm, logits, V, stride, par, nullptr, nullptr, SampleGate{}, step_word, out);
 }
 
 // sample_rows_kernel with a top-k and a min-p cut per row (filt[row]); both off: sample_rows_kernel's token, bit for bit
@@ -333,7 +458,27 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_filtered_kernel(co
                                                                               const SampleFilter* __restrict__ filt,
                                                                               const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
     __shared__ SampleSmem sm;
-    sample_rows_body<NPT, true>(sm, logits, V, stride, par, filt, step_word, out);
+    sample_rows_body<NPT, SAMPLE_FILT>(sm, logits, V, stride, par, filt, nullptr, SampleGate{}, step_word, out);
+}
+
+// sample_rows_kernel with Mirostat v2 per row (alt[row]: tau, eta and the running mu, rewritten when the draw counts); tau == 0:
+// sample_rows_kernel's token, bit for bit
+template <int NPT>
+__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_mirostat_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
+                                                                              const SampleParam* __restrict__ par, SampleAlt* alt,
+                                                                              const SampleGate gate, const uint32_t* __restrict__ step_word,
+                                                                              uint32_t* __restrict__ out) {
+    __shared__ SampleSmem sm;
+    sample_rows_body<NPT, SAMPLE_MIRO>(sm, logits, V, stride, par, nullptr, alt, gate, step_word, out);
+}
+
+// sample_rows_kernel with the locally typical cut per row (alt[row].typical_p); >= 1: sample_rows_kernel's token, bit for bit
+template <int NPT>
+__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_typical_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
+                                                                             const SampleParam* __restrict__ par, SampleAlt* alt,
+                                                                             const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
+    __shared__ SampleSmem sm;
+    sample_rows_body<NPT, SAMPLE_TYP>(sm, logits, V, stride, par, nullptr, alt, SampleGate{}, step_word, out);
 }
 
 int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
@@ -357,6 +502,30 @@ int sample_rows_filtered(hipStream_t s, const float* logits, uint32_t v, uint32_
     // thread, and rows of 8193..16384 tokens are re-read from L2
     else if (v <= 8192) sample_rows_filtered_kernel<8><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
     else sample_rows_filtered_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
+    return 0;
+}
+
+int sample_rows_mirostat(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, SampleAlt* alt,
+                         const uint32_t* gate, uint32_t gate_stride, uint32_t gate_eq, const uint32_t* step, uint32_t* out) {
+    if (n == 0) return 0;
+    if (v == 0 || v > SAMPLE_MAX_VOCAB || stride < v) return -1;
+    const SampleGate g{gate, gate_stride, gate_eq};
+    if (v <= 1024) sample_rows_mirostat_kernel<1><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, alt, g, step, out);
+    else if (v <= 4096) sample_rows_mirostat_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, alt, g, step, out);
+    else if (v <= MIRO_NPT_MAX * 1024) sample_rows_mirostat_kernel<MIRO_NPT_MAX><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, alt, g, step, out);
+    else sample_rows_mirostat_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, alt, g, step, out);
+    return 0;
+}
+
+int sample_rows_typical(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
+                        const SampleAlt* alt, const uint32_t* step, uint32_t* out) {
+    if (n == 0) return 0;
+    if (v == 0 || v > SAMPLE_MAX_VOCAB || stride < v) return -1;
+    SampleAlt* a = const_cast<SampleAlt*>(alt);     // the shared body writes mu in the Mirostat kernel only
+    if (v <= 1024) sample_rows_typical_kernel<1><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, a, step, out);
+    else if (v <= 4096) sample_rows_typical_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, a, step, out);
+    else if (v <= TYP_NPT_MAX * 1024) sample_rows_typical_kernel<TYP_NPT_MAX><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, a, step, out);
+    else sample_rows_typical_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, a, step, out);
     return 0;
 }
 
@@ -387,16 +556,60 @@ int32_t wrk_filter_pack(wrk_ctx* ctx, const uint32_t* top_k, const float* min_p,
     return WRK_OK;
 }
 
-// filtered: the filtered kernel on (top_k, min_p), either of which may be NULL
+static bool finite_f32(float x) { return x - x == 0.0f; }
+
+int32_t wrk_mirostat_pack(wrk_ctx* ctx, const float* tau, const float* eta, const float* mu, uint32_t n, std::vector<wrk::SampleAlt>& out) {
+    WRK_ARG(ctx, tau, "mirostat_eta / mirostat_mu without mirostat_tau");
+    out.assign(n, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
+    for (uint32_t b = 0; b < n; ++b) {
+        const float t = tau[b], e = eta ? eta[b] : 0.0f;
+        WRK_ARG(ctx, finite_f32(t) && t >= 0.0f, "mirostat_tau[%u] = %g: must be finite and >= 0", b, (double)t);
+        WRK_ARG(ctx, finite_f32(e) && e >= 0.0f, "mirostat_eta[%u] = %g: must be finite and >= 0", b, (double)e);
+        const float m = mu ? mu[b] : 2.0f * t;       // a fresh sequence
+        WRK_ARG(ctx, finite_f32(m), "mirostat_mu[%u] = %g: must be finite", b, (double)m);
+        out[b] = wrk::SampleAlt{t, e, m, 1.0f};
+    }
+    return WRK_OK;
+}
+
+int32_t wrk_typical_pack(wrk_ctx* ctx, const float* typical_p, uint32_t n, std::vector<wrk::SampleAlt>& out) {
+    out.assign(n, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
+    for (uint32_t b = 0; b < n; ++b) {
+        const float p = typical_p[b];
+        WRK_ARG(ctx, !(p != p) && p >= 0.0f && p <= 1.0f, "typical_p[%u] = %g: must be in [0, 1]", b, (double)p);
+        out[b].typical_p = p;
+    }
+    return WRK_OK;
+}
+
+// the row functions' sampler: the filtered kernel on (top_k, min_p), either of which may be NULL; the Mirostat kernel on (tau, eta,
+// mu_inout); the typical kernel on typical_p
+struct sample_logits_kind {
+    enum { PLAIN, FILTERED, MIROSTAT, TYPICAL } k = PLAIN;
+    const uint32_t* top_k = nullptr; const float* min_p = nullptr;
+    const float *tau = nullptr, *eta = nullptr; float* mu_inout = nullptr;
+    const float* typical_p = nullptr;
+};
+
 static int32_t sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const float* temperature,
-                             const float* top_p, bool filtered, const uint32_t* top_k, const float* min_p, const uint32_t* seed, uint32_t step,
+                             const float* top_p, const sample_logits_kind& kind, const uint32_t* seed, uint32_t step,
                              uint32_t* out_tokens, const char* who) {
     if (!ctx || !logits || !out_tokens) return WRK_E_ARG;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const bool filtered = kind.k == sample_logits_kind::FILTERED, miro = kind.k == sample_logits_kind::MIROSTAT,
+               typical = kind.k == sample_logits_kind::TYPICAL;
+    const uint32_t* top_k = kind.top_k;
+    const float* min_p = kind.min_p;
     std::vector<wrk::SampleParam> par;
     std::vector<wrk::SampleFilter> filt;
+    std::vector<wrk::SampleAlt> alt;
     int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, n, par);
     if (rc == WRK_OK && filtered) rc = wrk_filter_pack(ctx, top_k, min_p, n, filt);
+    if (rc == WRK_OK && miro) rc = wrk_mirostat_pack(ctx, kind.tau, kind.eta, kind.mu_inout, n, alt);
+    if (rc == WRK_OK && typical) {
+        WRK_ARG(ctx, kind.typical_p, "typical_p array required");
+        rc = wrk_typical_pack(ctx, kind.typical_p, n, alt);
+    }
     if (rc != WRK_OK) return rc;
     if (n == 0) return WRK_OK;
     WRK_ARG(ctx, !ctx->capturing_here(), "%s is blocking: not inside a capture", who);
@@ -406,8 +619,9 @@ static int32_t sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, ui
             logits->bytes);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t o_step = (size_t)n * sizeof(wrk::SampleParam), o_out = o_step + 256, o_filt = (o_out + (size_t)n * 4 + 255) / 256 * 256;
+    static_assert(sizeof(wrk::SampleAlt) >= sizeof(wrk::SampleFilter), "the rows after o_filt are sized for the larger struct");
     char* dev = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&dev, o_filt + (size_t)n * sizeof(wrk::SampleFilter)));
+    WRK_HIP(ctx, hipMalloc((void**)&dev, o_filt + (size_t)n * sizeof(wrk::SampleAlt)));
     struct Free { char* p; ~Free() { hipFree(p); } } guard{dev};
     WRK_HIP(ctx, hipMemcpyAsync(dev, par.data(), o_step, hipMemcpyHostToDevice, ctx->stream));
     WRK_HIP(ctx, hipMemcpyAsync(dev + o_step, &step, 4, hipMemcpyHostToDevice, ctx->stream));
@@ -415,25 +629,55 @@ static int32_t sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, ui
         WRK_HIP(ctx, hipMemcpyAsync(dev + o_filt, filt.data(), (size_t)n * sizeof(wrk::SampleFilter), hipMemcpyHostToDevice, ctx->stream));
         wrk::sample_rows_filtered(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev,
                                   (const wrk::SampleFilter*)(dev + o_filt), (const uint32_t*)(dev + o_step), (uint32_t*)(dev + o_out));
+    } else if (miro || typical) {
+        wrk::SampleAlt* rows = (wrk::SampleAlt*)(dev + o_filt);
+        WRK_HIP(ctx, hipMemcpyAsync(rows, alt.data(), (size_t)n * sizeof(wrk::SampleAlt), hipMemcpyHostToDevice, ctx->stream));
+        if (miro) wrk::sample_rows_mirostat(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, rows, nullptr, 0, 0,
+                                            (const uint32_t*)(dev + o_step), (uint32_t*)(dev + o_out));
+        else wrk::sample_rows_typical(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, rows,
+                                      (const uint32_t*)(dev + o_step), (uint32_t*)(dev + o_out));
     } else {
         wrk::sample_rows(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, (const uint32_t*)(dev + o_step),
                          (uint32_t*)(dev + o_out));
     }
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipMemcpyAsync(out_tokens, dev + o_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (miro && kind.mu_inout) WRK_HIP(ctx, hipMemcpyAsync(alt.data(), dev + o_filt, (size_t)n * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (miro && kind.mu_inout)
+        for (uint32_t b = 0; b < n; ++b) kind.mu_inout[b] = alt[b].mu;
     return WRK_OK;
 }
 
 extern "C" int32_t wrk_sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const float* temperature,
                                      const float* top_p, const uint32_t* seed, uint32_t step, uint32_t* out_tokens) {
-    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, false, nullptr, nullptr, seed, step, out_tokens, "wrk_sample_logits");
+    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, sample_logits_kind{}, seed, step, out_tokens, "wrk_sample_logits");
 }
 
 // both filter arrays NULL: wrk_sample_logits' kernel
 extern "C" int32_t wrk_sample_logits_filtered(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n,
                                               const float* temperature, const float* top_p, const uint32_t* top_k, const float* min_p,
                                               const uint32_t* seed, uint32_t step, uint32_t* out_tokens) {
-    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, top_k || min_p, top_k, min_p, seed, step, out_tokens,
-                         "wrk_sample_logits_filtered");
+    sample_logits_kind kind;
+    if (top_k || min_p) kind.k = sample_logits_kind::FILTERED;
+    kind.top_k = top_k; kind.min_p = min_p;
+    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, kind, seed, step, out_tokens, "wrk_sample_logits_filtered");
+}
+
+extern "C" int32_t wrk_sample_logits_mirostat(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n,
+                                              const float* temperature, const float* top_p, const float* tau, const float* eta,
+                                              float* mu_inout, const uint32_t* seed, uint32_t step, uint32_t* out_tokens) {
+    sample_logits_kind kind;
+    kind.k = sample_logits_kind::MIROSTAT;
+    kind.tau = tau; kind.eta = eta; kind.mu_inout = mu_inout;
+    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, kind, seed, step, out_tokens, "wrk_sample_logits_mirostat");
+}
+
+extern "C" int32_t wrk_sample_logits_typical(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n,
+                                             const float* temperature, const float* top_p, const float* typical_p, const uint32_t* seed,
+                                             uint32_t step, uint32_t* out_tokens) {
+    sample_logits_kind kind;
+    kind.k = sample_logits_kind::TYPICAL;
+    kind.typical_p = typical_p;
+    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, kind, seed, step, out_tokens, "wrk_sample_logits_typical");
 }

@@ -77,6 +77,7 @@ class GenerateOptions(C.Structure):
     _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
                 ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
+                ("mirostat_tau", _f32p), ("mirostat_eta", _f32p), ("mirostat_mu", _f32p), ("typical_p", _f32p),
                 ("top_k", _u32p), ("min_p", _f32p)]
 
 
@@ -88,6 +89,7 @@ class QueueOptions(C.Structure):
                 ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("init_state", _P),
                 ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
+                ("mirostat_tau", _f32p), ("mirostat_eta", _f32p), ("mirostat_mu", _f32p), ("typical_p", _f32p),
                 ("top_k", _u32p), ("min_p", _f32p)]
 
 
@@ -176,6 +178,9 @@ HIP_SYMBOLS = {
     "wrk_sample_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, C.c_uint32, _u32p]),
     "wrk_sample_logits_filtered": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _f32p, _u32p, C.c_uint32,
                                                _u32p]),
+    "wrk_sample_logits_mirostat": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _u32p, C.c_uint32,
+                                               _u32p]),
+    "wrk_sample_logits_typical": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, _u32p, C.c_uint32, _u32p]),
     "wrk_v7_generate_sample": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _f32p, _f32p,
                                            C.c_uint32]),
     "wrk_v6_generate_sample": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _f32p, _f32p,
@@ -279,15 +284,27 @@ def _filters(top_k, min_p, n: int, keep: list):
     return tk, mp
 
 
-def _fill_pick(opt, n: int, keep: list, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p):
+def _mirostat_rows(mirostat, mirostat_mu, n: int):
+    """(tau [n], eta [n], mu [n]) f32 of `mirostat` = (tau, eta), scalars or one value per row; mu: `mirostat_mu`, or 2 tau (a fresh
+    sequence).  mu is a writable copy: the call returns the new values in it."""
+    tau, eta = mirostat
+    tau, eta = _per_row(tau, n, np.float32), _per_row(eta, n, np.float32)
+    mu = (2.0 * tau).astype(np.float32) if mirostat_mu is None else np.array(_per_row(mirostat_mu, n, np.float32), np.float32)
+    return tau, eta, mu
+
+
+def _fill_pick(opt, n: int, keep: list, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
+               mirostat=None, mirostat_mu=None, typical_p=None):
     """The sampler / penalty / filter fields of a GenerateOptions or QueueOptions for n rows (scalars broadcast; seed None: seed[i] = i).
-    All of temperature, top_p, seed, occurrence, top_k, min_p None: nothing is set, the arg-max.  The arrays go into `keep`, which must
-    outlive the call."""
+    All of temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p None: nothing is set, the arg-max.  The arrays go into
+    `keep`, which must outlive the call.  mirostat = (tau, eta): returns the in/out mu array [n] (mirostat_mu, or 2 tau), else None."""
     def put(v, dtype, ty):
         keep.append(_per_row(v, n, dtype))
         return _ptr(keep[-1], ty)
-    if all(v is None for v in (temperature, top_p, seed, occurrence, top_k, min_p)):
-        return
+    if mirostat is None and mirostat_mu is not None:
+        raise ValueError("mirostat_mu without mirostat")
+    if all(v is None for v in (temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p)):
+        return None
     opt.temperature = put(1.0 if temperature is None else temperature, np.float32, _f32p)
     opt.top_p = put(0.5 if top_p is None else top_p, np.float32, _f32p)
     opt.seed = put(np.arange(n, dtype=np.uint32) if seed is None else seed, np.uint32, _u32p)
@@ -299,6 +316,14 @@ def _fill_pick(opt, n: int, keep: list, temperature, top_p, seed, occurrence, pr
         opt.top_k = tk
     if mp is not None:
         opt.min_p = mp
+    if typical_p is not None:
+        opt.typical_p = put(typical_p, np.float32, _f32p)
+    if mirostat is None:
+        return None
+    tau, eta, mu = _mirostat_rows(mirostat, mirostat_mu, n)
+    keep.extend([tau, eta, mu])
+    opt.mirostat_tau, opt.mirostat_eta, opt.mirostat_mu = _ptr(tau, _f32p), _ptr(eta, _f32p), _ptr(mu, _f32p)
+    return mu
 
 
 def _logprob_arrays(logprobs, rows: int):
@@ -380,11 +405,15 @@ class Context:
         return Buffer(self, a.nbytes, a)
 
     def sample_logits(self, logits, temperature=1.0, top_p=0.5, seed=0, step: int = 0, num_vocab: Optional[int] = None,
-                      top_k=None, min_p=None) -> np.ndarray:
+                      top_k=None, min_p=None, mirostat=None, typical_p=None):
         """`Sampler::sample` (examples/chat.rs:150-190; defaults are its `--temp 1.0 --top-p 0.5`) on the device, one token per row.
         `logits`: an [n, V] f32 array, or a `Buffer` of n rows of `num_vocab` f32; temperature / top_p / seed: scalars or per-row arrays.
         top_k (0: off) / min_p (0: off): scalars or per-row arrays; with either the candidates are also cut to the top_k highest logits
-        and to the tokens whose probability is at least min_p times the largest.  Returns uint32 [n]."""
+        and to the tokens whose probability is at least min_p times the largest.  Returns uint32 [n].
+        mirostat=(tau, eta, mu): Mirostat v2 with the target surprise tau (bits; 0: a plain row), the learning rate eta
+        and the running mu (None: 2 tau, a fresh sequence), scalars or per-row arrays; returns (tokens uint32 [n], mu float32 [n]), mu
+        after the draw.  typical_p (>= 1: a plain row): locally typical sampling.  One family per call; top_p is not read by a Mirostat
+        or typical row."""
         if isinstance(logits, Buffer):
             assert num_vocab, "a Buffer needs num_vocab"
             buf, V = logits, int(num_vocab)
@@ -396,6 +425,18 @@ class Context:
             buf = self.buffer(a)
         t, p, sd = _per_row(temperature, n, np.float32), _per_row(top_p, n, np.float32), _per_row(seed, n, np.uint32)
         out = np.zeros(n, np.uint32)
+        if sum(x is not None for x in (mirostat, typical_p)) + (top_k is not None or min_p is not None) > 1:
+            raise ValueError("one family per call: top_k / min_p, mirostat or typical_p")
+        if mirostat is not None:
+            tau, eta, mu = _mirostat_rows(mirostat[:2], mirostat[2], n)
+            self.check(hip.wrk_sample_logits_mirostat(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(tau, _f32p), _ptr(eta, _f32p),
+                                                      _ptr(mu, _f32p), _ptr(sd, _u32p), step, _ptr(out, _u32p)))
+            return out, mu
+        if typical_p is not None:
+            ty = _per_row(typical_p, n, np.float32)
+            self.check(hip.wrk_sample_logits_typical(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(ty, _f32p), _ptr(sd, _u32p),
+                                                     step, _ptr(out, _u32p)))
+            return out
         if top_k is None and min_p is None:
             self.check(hip.wrk_sample_logits(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p), step, _ptr(out, _u32p)))
             return out
@@ -955,6 +996,8 @@ class Runtime:
         # the log-probs of the last generate_* call with `logprobs`: (logprob [steps_run, B], top_ids [steps_run, B, n], top_logprobs
         # [steps_run, B, n]); after generate_queue one such triple per request ([len], [len, n], [len, n]); None after a call without
         self.last_logprobs = None
+        # the mu of the last generate_* call with `mirostat`, per sequence (generate_queue: per request); None after a call without
+        self.last_mirostat_mu = None
 
     def token_bytes(self, num_batch: int = 1) -> int:
         if self.model6:
@@ -1120,37 +1163,45 @@ class Runtime:
         return (t, p, sd), (_ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p))
 
     def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
-                        groups: int = 1, top_k=None, min_p=None, logprobs=None):
+                        groups: int = 1, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None):
         """As `generate_greedy`, each sequence's next token drawn by `Sampler::sample` (examples/chat.rs:150-190) on the device with its
         own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b.
         top_k / min_p (a scalar or one value per sequence; None: off): the draw is `sample_logits(..., top_k, min_p)`'s; such a call goes
         through the options entry point (wrk_v*_generate_stop without stop sets) and replays step programs of its own.
-        logprobs: as `generate_greedy`; the log-prob of a drawn token is its probability under the model, not under the sampler."""
-        if top_k is not None or min_p is not None or logprobs is not None:
+        logprobs: as `generate_greedy`; the log-prob of a drawn token is its probability under the model, not under the sampler.
+        mirostat=(tau, eta) (scalars or one pair of values per sequence): the draw is Mirostat v2's (`sample_logits(..., mirostat=)`,
+        DESIGN.md §7i), mu carried on the device from step to step; mirostat_mu: the mu each sequence starts from (None: 2 tau);
+        afterwards `last_mirostat_mu` [B] holds the values to pass to the next call of a session.  typical_p (a scalar or one value per
+        sequence): locally typical sampling.  One family per call (top_k / min_p, mirostat, typical_p); such a call goes through the
+        options entry point and replays step programs of its own."""
+        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
-                                           want_logits, groups, logprobs)
+                                           want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p)
         keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
         return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
 
     def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
-                           want_logits, groups, logprobs=None):
+                           want_logits, groups, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None):
         opt, keep = GenerateOptions(), []
-        _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p)
+        mu = _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
+                        mirostat, mirostat_mu, typical_p)
         out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits, logprobs)
+        self.last_mirostat_mu = mu
         return (out, ms, logits) if want_logits else (out, ms)
 
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
                            frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1, top_k=None, min_p=None,
-                           logprobs=None):
+                           logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None):
         """As `generate_sample`, each draw made on the logits penalised with the sequence's slot of `occurrence` (ChatRWKV's
         alpha_presence / alpha_frequency / token_ban), and the slot updated after every draw (count *= decay, then the drawn token's
         weight added).  The first token of a call is not counted; the last drawn one is.  The table carries over between calls.
         Scalars broadcast; seed=None: seed[b] = b.  last logits: the head output before penalties.  top_k / min_p: as `generate_sample`,
         the cuts made on the penalised logits.  logprobs: as `generate_greedy`, on the head output before penalties and bans (a banned
-        token may appear among the alternatives)."""
-        if top_k is not None or min_p is not None or logprobs is not None:
+        token may appear among the alternatives).  mirostat / mirostat_mu / typical_p: as `generate_sample`, the pick made on the
+        penalised logits."""
+        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
-                                           min_p, mode, want_logits, groups, logprobs)
+                                           min_p, mode, want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p)
         B = _u32(first_tokens).size
         keep, rows = self._sampler_rows(B, temperature, top_p, seed)
         pen = [_per_row(v, B, np.float32) for v in (presence, frequency, decay)]
@@ -1159,7 +1210,7 @@ class Runtime:
 
     def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
-                      poll_steps: int = 0, top_k=None, min_p=None, logprobs=None):
+                      poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None):
         """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
         at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
         MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
@@ -1167,11 +1218,14 @@ class Runtime:
         logits row of a finished sequence are those of a `lengths[b]`-step call.  steps_run < steps once every sequence has ended (the host
         looks every `poll_steps` steps; 0: the default).  top_k / min_p: as `generate_sample` (they make the pick a sampled one).
         logprobs: as `generate_greedy`; rows [:lengths[b], b] of `last_logprobs` are those of the call without stops, the stop token's
-        own row included; later rows of a finished sequence are unspecified."""
+        own row included; later rows of a finished sequence are unspecified.
+        mirostat / mirostat_mu / typical_p: as `generate_sample`; `last_mirostat_mu[b]` has seen exactly lengths[b] draws, the stop
+        token's included."""
         ft = _u32(first_tokens)
         ids, off = _stop_csr(stop, ft.size, "sequences")
         opt, keep = GenerateOptions(), []
-        _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p)
+        self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
+                                           mirostat, mirostat_mu, typical_p)
         opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
         out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, self._mode(mode, groups), want_logits,
                                                                               logprobs)
@@ -1180,7 +1234,8 @@ class Runtime:
 
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
-                       mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None):
+                       mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None,
+                       mirostat=None, mirostat_mu=None, typical_p=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1196,7 +1251,10 @@ class Runtime:
         for start and save continues a session in place.  `last_queue_saved[r]` tells whether request r's entry was written.  Two
         requests may not save to one entry, nor one read an entry another saves to.
         logprobs (None: off; 0..MAX_TOP_LOGPROBS): `last_logprobs[r]` = (logprob [len], top_ids [len, n], top_logprobs [len, n]) of
-        request r's reply tokens, as `generate_greedy`'s; the rows of the steps that feed prompt tokens are discarded."""
+        request r's reply tokens, as `generate_greedy`'s; the rows of the steps that feed prompt tokens are discarded.
+        mirostat=(tau, eta) / typical_p: per request (scalars broadcast), as `generate_sample`.  mirostat_mu[r] (None: 2 tau[r]) is what
+        request r starts from when it is dispatched, whatever its slot held; `last_mirostat_mu[r]` is its mu after its reply draws
+        (untouched for reason 0).  mu is not part of a pool entry: a session carries it through these arrays."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1212,7 +1270,8 @@ class Runtime:
         opt.prompt_tokens, opt.prompt_offsets, opt.max_new = _ptr(ptok, _u32p), _ptr(poff, _u32p), _ptr(mn, _u32p)
         opt.stop_tokens, opt.stop_offsets = _ptr(ids, _u32p), _ptr(soff, _u32p)
         keep = []
-        _fill_pick(opt, R, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p)
+        self.last_mirostat_mu = _fill_pick(opt, R, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
+                                           mirostat, mirostat_mu, typical_p)
         if init_state is not None:
             opt.init_state = init_state.h
         opt.poll_steps = poll_steps
