@@ -1,4 +1,4 @@
-"""Top-k and min-p on the device sampler (web-rwkv-gguf_amd/csrc/wrk_sample.hip `sample_rows_filtered_kernel`) against
+"""Top-k and min-p on the device sampler (web-rwkv-gguf_amd/csrc/wrk_sample.hip `sample_rows_kernel<NPT, SAMPLE_FILT>`) against
 the restatement in tests/filter_ref.py: through `Context.sample_logits(top_k=, min_p=)`, the decode loops (`generate_sample`,
 `generate_penalized`, `generate_stop`) and `generate_queue`.
 

@@ -104,6 +104,36 @@ def test_kernel_orders_more_than_twenty_equal_maxima_by_index(ctx):
     assert np.array_equal(bits(tlp), np.broadcast_to(bits(lp)[:, None], tlp.shape))
 
 
+@pytest.mark.parametrize("pad", [0, 3])
+@pytest.mark.parametrize("V", [5, 1025, 4097])
+def test_arg_max_first_alternative_and_rank_zero_are_one_token(ctx, V, pad):
+    """The sampler at temperature 0, the first alternative and the scorer's rank 0 name one token, and its log-prob has one bit
+    pattern, on rows where a second order or a second expression would show: the maximum 0 held as -0.0 and as +0.0 (in either
+    order), next to a NaN and a -inf; stride V + 3 takes the scalar loads."""
+    stride, lo, hi = V + pad, V // 2, V - 1
+    x = (-np.abs(np.random.default_rng(V).normal(0.0, 2.0, (2, V))) - 0.5).astype(np.float32)
+    x[:, 0], x[:, 1] = np.nan, -np.inf
+    x[0, lo], x[0, hi] = -0.0, 0.0
+    x[1, lo], x[1, hi] = 0.0, -0.0
+    for r in x:         # the restatement's order has one answer for these rows
+        k = L.keys(r)
+        assert np.unique(k).size == V and int(k.argmax()) == lo
+        assert np.nonzero(np.nan_to_num(r, nan=-np.inf) == r[lo])[0].tolist() == [lo, hi]
+    rows = np.full((2, stride), 7.0e3, np.float32)          # padding would win every row if it were read
+    rows[:, :V] = x
+    buf = ctx.buffer(rows)
+    f32p, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    t, p, seed, tok = np.zeros(2, np.float32), np.full(2, 0.9, np.float32), np.arange(2, dtype=np.uint32), np.full(2, V, np.uint32)
+    assert wrk.hip.wrk_sample_logits(ctx.h, buf.h, V, stride, 2, t.ctypes.data_as(f32p), p.ctypes.data_as(f32p), seed.ctypes.data_as(u32p), 0,
+                                     tok.ctypes.data_as(u32p)) == 0
+    lp, ids, tlp = ctx.top_logprobs(buf, tok, 3, num_vocab=V, row_stride=stride)
+    assert tok.tolist() == ids[:, 0].tolist() == [lo] * 2
+    score_lp, rank = ctx.score_logits(buf, tok, num_vocab=V, row_stride=stride)
+    assert rank.tolist() == [0] * 2
+    assert np.array_equal(bits(score_lp), bits(tlp[:, 0])) and np.array_equal(bits(lp), bits(tlp[:, 0]))
+    assert np.isnan(score_lp).all()
+
+
 def test_kernel_rejects_bad_arguments(ctx):
     x = np.zeros((2, 10), np.float32)
     for call in (lambda: ctx.top_logprobs(x, [1, 10], 3), lambda: ctx.top_logprobs(x, [1, 2], wrk.MAX_TOP_LOGPROBS + 1)):
@@ -341,6 +371,25 @@ def test_queue_rows_equal_each_request_alone(ctx, kind, B):
 
 def test_queue_rows_equal_each_request_alone_v6(ctx):
     queue_rows_equal_replays(ctx, "sample", 2, v6=True)
+
+
+def test_queue_stop_ids_outlive_the_log_prob_arrays(ctx):
+    """`generate_queue` with stop ids and log-probs together: the stop ids the options point to stay alive next to the log-prob
+    arrays, so every request ends where it ends without log-probs (request 0 at its stop token)."""
+    rt = make_runtime(ctx, 7, "tiny", 2)
+    reqs = [[5, 9], [17], [40, 3, 8], [11]]
+    kw = dict(max_new=6, temperature=1.0, top_p=0.9, seed=[1, 2, 3, 4])
+    reset(rt)
+    free, _ = rt.generate_queue(reqs, **kw)
+    stop = int(free[0][0][1])           # the second reply token of request 0
+    runs = []
+    for lp in (None, 1, wrk.MAX_TOP_LOGPROBS):
+        reset(rt)
+        res, ran = rt.generate_queue(reqs, stop=[stop], logprobs=lp, **kw)
+        runs.append(([t.tolist() for t, *_ in res], [r[1:] for r in res], ran))
+    assert runs[0][0][0][-1] == stop and runs[0][1][0][0] == 1 and len(runs[0][0][0]) <= 2
+    assert runs[1] == runs[0] and runs[2] == runs[0]
+    rt.close()
 
 
 def test_pool_call_in_place_is_unchanged_and_has_the_rows_of_replays(ctx):

@@ -1,4 +1,4 @@
-"""Mirostat v2 on the device sampler (web-rwkv-gguf_amd/csrc/wrk_sample.hip `sample_rows_mirostat_kernel`) against the
+"""Mirostat v2 on the device sampler (web-rwkv-gguf_amd/csrc/wrk_sample.hip `sample_rows_kernel<NPT, SAMPLE_MIRO>`) against the
 restatement in tests/mirostat_ref.py: through `Context.sample_logits(mirostat=)`, the decode loops (`generate_sample`,
 `generate_penalized`, `generate_stop`, RWKV-6) and `generate_queue` with and without a state pool.
 

@@ -1,4 +1,4 @@
-"""Locally typical sampling on the device sampler (web-rwkv-gguf_amd/csrc/wrk_sample.hip `sample_rows_typical_kernel`)
+"""Locally typical sampling on the device sampler (web-rwkv-gguf_amd/csrc/wrk_sample.hip `sample_rows_kernel<NPT, SAMPLE_TYP>`)
 against the restatement in tests/typical_ref.py: through `Context.sample_logits(typical_p=)`, the decode loops and `generate_queue`.
 
 The kernel test runs the grid of tests/alt_cases.py on four row kinds per vocabulary size (the register variants of one, four and eight

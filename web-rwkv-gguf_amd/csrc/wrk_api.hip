@@ -84,7 +84,7 @@ int32_t wrk_buf_create(wrk_ctx* ctx, size_t bytes, const void* init, wrk_buf** o
     *out = nullptr;
     WRK_HIP(ctx, hipSetDevice(ctx->device));
     void* p = nullptr;
-    const size_t alloc = bytes ? ((bytes + 255) & ~(size_t)255) : 256;
+    const size_t alloc = bytes ? wrk_up256(bytes) : 256;
     WRK_HIP(ctx, hipMalloc(&p, alloc));
     if (init) {
         hipError_t e = hipMemcpyAsync(p, init, bytes, hipMemcpyHostToDevice, ctx->stream);
@@ -98,6 +98,20 @@ int32_t wrk_buf_create(wrk_ctx* ctx, size_t bytes, const void* init, wrk_buf** o
     *out = b;
     return WRK_OK;
 }
+
+}  // extern "C"
+
+int32_t wrk_rows_check(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const char* who, uint32_t max_vocab) {
+    WRK_ARG(ctx, !ctx->capturing_here(), "%s is blocking: not inside a capture", who);
+    if (n == 0) return WRK_OK;
+    WRK_ARG(ctx, V >= 1 && stride >= V, "num_vocab %u / row_stride %u", V, stride);
+    if (max_vocab && V > max_vocab) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "num_vocab %u > %u", V, max_vocab);
+    WRK_ARG(ctx, ((size_t)(n - 1) * stride + V) * 4 <= logits->bytes, "%u rows of stride %u exceed the buffer of %zu bytes", n, stride,
+            logits->bytes);
+    return WRK_OK;
+}
+
+extern "C" {
 
 int32_t wrk_buf_retain(wrk_buf* buf) {
     if (!buf) return WRK_E_ARG;

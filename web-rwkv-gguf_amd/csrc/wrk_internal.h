@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -93,6 +94,29 @@ inline int32_t wrk_fail(wrk_ctx* ctx, int32_t code, const char* fmt, ...) {
 
 #define WRK_LAUNCH_CHECK(ctx) WRK_HIP(ctx, hipGetLastError())
 
+// ------------------------------------------------------------------ what the blocking row functions share (wrk_api.hip)
+inline size_t wrk_up256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline bool finite_f32(float x) { return std::isfinite(x); }
+// The argument checks of a blocking call `who` on n rows of V logits, `stride` floats apart, in `logits`; the caller holds ctx->mu.
+// WRK_E_ARG inside a capture of this thread and, with n > 0, unless V >= 1 && stride >= V or when the rows exceed the buffer;
+// WRK_E_UNSUPPORTED when max_vocab != 0 and V > max_vocab
+int32_t wrk_rows_check(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const char* who, uint32_t max_vocab);
+// Pieces of one device allocation at 256-byte offsets: add() every piece first, then alloc() once, then at<T>(offset).  wrk_dev_layout
+// is the offsets alone, for an owner that keeps the memory itself; wrk_dev_arena frees it when it goes out of scope
+struct wrk_dev_layout {
+    size_t total = 0;
+    size_t add(size_t bytes) { const size_t o = total; total += wrk_up256(bytes); return o; }
+};
+struct wrk_dev_arena : wrk_dev_layout {
+    char* base = nullptr;
+    wrk_dev_arena() = default;
+    wrk_dev_arena(const wrk_dev_arena&) = delete;
+    wrk_dev_arena& operator=(const wrk_dev_arena&) = delete;
+    ~wrk_dev_arena() { if (base) hipFree(base); }
+    hipError_t alloc() { return hipMalloc((void**)&base, total ? total : 256); }
+    template <class T> T* at(size_t o) const { return (T*)(base + o); }
+};
+
 // ------------------------------------------------------------------ device-side tensor descriptor
 // Mirrors `View` addressing (see wrk_hip.h).  Passed by value to kernels.
 struct DTensor {
@@ -176,25 +200,26 @@ void argmax_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t v_stri
 // stride < v.  step_base is 0 everywhere but in queue programs (wrk_queue.hip), where a request's draws are numbered from its own reply
 struct SampleParam { float temperature, top_p; uint32_t seed, step_base; };
 static constexpr uint32_t SAMPLE_MAX_VOCAB = 1u << 20;
-int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
-                uint32_t* out);
-// sample_rows with two more cuts of the candidates per row: the first min(n_P, n_K, n_M) ranks stay, n_K = top_k (0 or
-// >= v: v; 1: the arg-max, as temperature 0) and n_M = #{fl32(l - max) >= ln_min_p} (-inf: v).  Both off: sample_rows' token, bit for bit
+// One RowGate says whether a row's draw counts: flag == nullptr always, else iff flag[row * stride] == eq (a stop program:
+// StopParam::done == 0; a queue program: QueueSlot::phase == QUEUE_REPLY).  The Mirostat sampler moves mu and occurrence_update counts
+// the draw under the same gate
+struct RowGate { const uint32_t* flag; uint32_t stride, eq; };
+// SAMPLE_FILT: two more cuts of the candidates per row, one SampleFilter per row: the first min(n_P, n_K, n_M) ranks
+// stay, n_K = top_k (0 or >= v: v; 1: the arg-max, as temperature 0) and n_M = #{fl32(l - max) >= ln_min_p} (-inf: v).  Both off:
+// SAMPLE_PLAIN's token, bit for bit
 struct SampleFilter { uint32_t top_k; float ln_min_p; };
-int sample_rows_filtered(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
-                         const SampleFilter* filt, const uint32_t* step, uint32_t* out);
-// The two samplers whose candidates are not one of sample_rows' cuts, one SampleAlt per row next to SampleParam.
-// sample_rows_mirostat: Mirostat v2 -- candidates = rank 0 and every token whose surprise log2 W - (l - max) / T * log2 e is <= mu (top_p
-// is not read), then mu <- mu - eta * (s - tau) with s the drawn token's surprise among the candidates; tau == 0: sample_rows' token, bit
-// for bit, mu untouched, and the greedy branch leaves mu alone too.  The update is made iff the row's draw counts: gate == nullptr, or
-// gate[row * gate_stride] == gate_eq (a stop program: StopParam::done == 0; a queue program: QueueSlot::phase == QUEUE_REPLY).
-// sample_rows_typical: locally typical sampling -- candidates = the tokens, by |(max - l) - gbar| ascending (ties by index), whose
-// preceding softmax mass is <= typical_p (top_p is not read); typical_p >= 1: sample_rows' token, bit for bit
+// The two samplers whose candidates are not one of the plain sampler's cuts, one SampleAlt per row next to SampleParam.
+// SAMPLE_MIRO: Mirostat v2 -- candidates = rank 0 and every token whose surprise log2 W - (l - max) / T * log2 e is <= mu (top_p is not
+// read), then mu <- mu - eta * (s - tau) with s the drawn token's surprise among the candidates; tau == 0: SAMPLE_PLAIN's token, bit for
+// bit, mu untouched, and the greedy branch leaves mu alone too.  The update is made iff the row's draw counts (gate).
+// SAMPLE_TYP: locally typical sampling -- candidates = the tokens, by |(max - l) - gbar| ascending (ties by index), whose preceding
+// softmax mass is <= typical_p (top_p is not read); typical_p >= 1: SAMPLE_PLAIN's token, bit for bit.  alt is only read
 struct SampleAlt { float tau, eta, mu, typical_p; };
-int sample_rows_mirostat(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, SampleAlt* alt,
-                         const uint32_t* gate, uint32_t gate_stride, uint32_t gate_eq, const uint32_t* step, uint32_t* out);
-int sample_rows_typical(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
-                        const SampleAlt* alt, const uint32_t* step, uint32_t* out);
+enum : int { SAMPLE_PLAIN = 0, SAMPLE_FILT = 1, SAMPLE_MIRO = 2, SAMPLE_TYP = 3 };
+// which sampler, and its rows: par always, filt with SAMPLE_FILT, alt with SAMPLE_MIRO / SAMPLE_TYP, gate with SAMPLE_MIRO
+struct SamplePick { int mode; const SampleParam* par; const SampleFilter* filt; SampleAlt* alt; RowGate gate; };
+int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SamplePick& pick, const uint32_t* step,
+                uint32_t* out);
 
 // wrk_score.hip: per row, logprob = x_t - logsumexp(x) and rank = #{x_i > x_t} + #{i < t : x_i == x_t} of the target t = targets[row]
 // (targets < v: the caller validates them).  Each row is split over score_slices(n, v, num_cu) workgroups; part holds n * that many
@@ -222,18 +247,17 @@ int logprob_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride
 // flags u8 [v]: bit 0 present, bit 1 banned), the table's weights f32 [v] and the sequence's (presence, frequency, decay).  Decode loops
 // keep these in a per-frame device buffer written before every call, so a captured step never holds a table pointer of its own.
 // penalize_rows: dst row r = the penalised src row r (src == dst allowed).  occurrence_update: row r applies tokens[r * ntok ..] in
-// order (count *= decay, then count[y] += weight[y], present[y] = 1); tokens < v (the caller validates them)
+// order (count *= decay, then count[y] += weight[y], present[y] = 1); tokens < v (the caller validates them).  A row whose draw does not
+// count (gate: a finished sequence of a stop program, a prompt-phase or idle slot of a queue program) is left alone
 struct PenaltyParam { float* count; uint8_t* flags; const float* weight; float presence, frequency, decay; uint32_t pad; };
 void penalize_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_stride, uint32_t n, const PenaltyParam* par, float* dst,
                    uint32_t dst_stride);
-void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, uint32_t ntok);
+void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, uint32_t ntok, const RowGate& gate);
 
 // wrk_stop.hip: stop tokens in the decode loops.  One StopParam per sequence in a per-frame device buffer written
 // before every call: the stop ids are data, one captured program serves any stop sets.  done / length / end_token are the device's:
 // the step that draws a stop id sets them (length = step + 1: the stop token is part of the output)
 struct StopParam { uint32_t ids[WRK_MAX_STOP_TOKENS]; uint32_t count, done, length, end_token; };
-// as occurrence_update with ntok == 1, rows whose StopParam is done left alone (a finished sequence's slot is frozen)
-void occurrence_update_live(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const StopParam* stop);
 // a frame's stop buffers and the state they snapshot: sequences [b0, b0 + B) of a state [L][num_batch][slot] f32
 struct StopGeom {
     float *state, *head_o, *snap_state, *snap_logits;
@@ -305,8 +329,6 @@ void advance_queue_pool(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, 
 // load the slot, store it to the save entry, then store the start entry / init_state / zero to the slot, in one thread -- and the
 // occurrence rows as queue_reset.  g.slot % 4 == 0 and 16-byte aligned bases only (the callers check)
 void queue_turnover(hipStream_t s, const QueueGeom& g, const QueueBufs& q, const QueueStateBufs& p, uint32_t b, int num_cu);
-// as occurrence_update with ntok == 1, for the rows whose draw of this step is a reply token (slots[r].phase == QUEUE_REPLY)
-void occurrence_update_queue(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const QueueSlot* slots);
 
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled

@@ -9,7 +9,7 @@
 // Both kernels cover a row with ceil(V / 1024) workgroups of 256 threads (grid (slices, rows)), 4 elements per thread, so that one
 // 65 536-token row spreads over 64 workgroups instead of one CU.  The update has no atomics: the thread that owns element y also does
 // its decay, so the result is the same on every replay.  Rows with g == 1 touch only element y.
-#include "wrk_device.h"
+#include "wrk_rows_dev.h"
 #include "wrk_runner.h" // wrk_buf_write_raw
 
 #include <cmath>
@@ -115,28 +115,12 @@ __device__ __forceinline__ void occurrence_update_row(uint32_t v, const PenaltyP
         if (hit & (1u << j)) p.flags[idx[j]] |= 1u;
 }
 
+// a row whose draw does not count returns before it reads anything else of its row
 template <bool VEC>
 __global__ void __launch_bounds__(PEN_THREADS) occurrence_update_kernel(uint32_t v, const PenaltyParam* __restrict__ par,
-                                                                        const uint32_t* __restrict__ tokens, uint32_t ntok) {
+                                                                        const uint32_t* __restrict__ tokens, uint32_t ntok, const RowGate gate) {
+    if (!row_counts(gate, blockIdx.y)) return;
     occurrence_update_row<VEC>(v, par, tokens, ntok);
-}
-
-// stop programs (wrk_stop.hip): one drawn token per row; the slot of a sequence that has ended stays as the stop token left it
-template <bool VEC>
-__global__ void __launch_bounds__(PEN_THREADS) occurrence_update_live_kernel(uint32_t v, const PenaltyParam* __restrict__ par,
-                                                                             const uint32_t* __restrict__ tokens,
-                                                                             const StopParam* __restrict__ stop) {
-    if (stop[blockIdx.y].done) return;
-    occurrence_update_row<VEC>(v, par, tokens, 1);
-}
-
-// queue programs (wrk_queue.hip): only a draw that is a reply token counts -- not a prompt-phase draw, not an idle slot's
-template <bool VEC>
-__global__ void __launch_bounds__(PEN_THREADS) occurrence_update_queue_kernel(uint32_t v, const PenaltyParam* __restrict__ par,
-                                                                              const uint32_t* __restrict__ tokens,
-                                                                              const QueueSlot* __restrict__ slots) {
-    if (slots[blockIdx.y].phase != QUEUE_REPLY) return;
-    occurrence_update_row<VEC>(v, par, tokens, 1);
 }
 
 // rows of an occurrence table start at slot * v: 16-byte aligned counts (and 4-byte aligned flags) exactly when v % 4 == 0
@@ -151,25 +135,11 @@ void penalize_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_str
     else penalize_rows_kernel<false><<<grid, PEN_THREADS, 0, s>>>(src, v, src_stride, par, dst, dst_stride);
 }
 
-void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, uint32_t ntok) {
+void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, uint32_t ntok, const RowGate& gate) {
     if (n == 0 || v == 0 || ntok == 0) return;
     const dim3 grid((v + PEN_TILE - 1) / PEN_TILE, n);
-    if (pen_vec(v)) occurrence_update_kernel<true><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, ntok);
-    else occurrence_update_kernel<false><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, ntok);
-}
-
-void occurrence_update_live(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const StopParam* stop) {
-    if (n == 0 || v == 0) return;
-    const dim3 grid((v + PEN_TILE - 1) / PEN_TILE, n);
-    if (pen_vec(v)) occurrence_update_live_kernel<true><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, stop);
-    else occurrence_update_live_kernel<false><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, stop);
-}
-
-void occurrence_update_queue(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, const QueueSlot* slots) {
-    if (n == 0 || v == 0) return;
-    const dim3 grid((v + PEN_TILE - 1) / PEN_TILE, n);
-    if (pen_vec(v)) occurrence_update_queue_kernel<true><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, slots);
-    else occurrence_update_queue_kernel<false><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, slots);
+    if (pen_vec(v)) occurrence_update_kernel<true><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, ntok, gate);
+    else occurrence_update_kernel<false><<<grid, PEN_THREADS, 0, s>>>(v, par, tokens, ntok, gate);
 }
 
 }  // namespace wrk
@@ -177,8 +147,6 @@ void occurrence_update_queue(hipStream_t s, uint32_t v, uint32_t n, const Penalt
 wrk::PenaltyParam wrk_occurrence::row(uint32_t slot, float presence, float frequency, float decay) const {
     return wrk::PenaltyParam{counts + (size_t)slot * num_vocab, flags + (size_t)slot * num_vocab, weights, presence, frequency, decay, 0u};
 }
-
-static bool finite_f32(float x) { return std::isfinite(x); }
 
 int32_t wrk_penalty_pack(wrk_ctx* ctx, const wrk_occurrence* occ, uint32_t first, uint32_t n, uint32_t V, const float* presence,
                          const float* frequency, const float* decay, std::vector<wrk::PenaltyParam>& out) {
@@ -209,15 +177,16 @@ int32_t wrk_occurrence_create(wrk_ctx* ctx, uint32_t B, uint32_t V, wrk_occurren
     if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "num_vocab %u > %u", V, wrk::SAMPLE_MAX_VOCAB);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)B * V;
-    const size_t o_w = (n * 4 + 255) & ~(size_t)255, o_f = o_w + (((size_t)V * 4 + 255) & ~(size_t)255);
+    wrk_dev_layout lay;
+    const size_t o_c = lay.add(n * 4), o_w = lay.add((size_t)V * 4), o_f = lay.add(n);
     void* mem = nullptr;
-    WRK_HIP(ctx, hipMalloc(&mem, o_f + n));
+    WRK_HIP(ctx, hipMalloc(&mem, lay.total));
     wrk_occurrence* occ = new wrk_occurrence;
     occ->ctx = ctx;
     occ->num_batch = B;
     occ->num_vocab = V;
     occ->mem = mem;
-    occ->counts = (float*)mem;
+    occ->counts = (float*)((char*)mem + o_c);
     occ->weights = (float*)((char*)mem + o_w);
     occ->flags = (uint8_t*)((char*)mem + o_f);
     hipError_t e = hipMemsetAsync(occ->counts, 0, n * 4, ctx->stream);
@@ -291,13 +260,12 @@ int32_t wrk_occurrence_add(wrk_ctx* ctx, wrk_occurrence* occ, uint32_t b, const 
     const int32_t rc = wrk_penalty_pack(ctx, occ, b, 1, V, &zero, &zero, &decay, par);
     if (rc != WRK_OK || n == 0) return rc;
     WRK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_tok = (sizeof(wrk::PenaltyParam) + 255) & ~(size_t)255;
-    char* dev = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&dev, o_tok + (size_t)n * 4));
-    struct Free { char* p; ~Free() { hipFree(p); } } guard{dev};
-    WRK_HIP(ctx, hipMemcpyAsync(dev, par.data(), sizeof(wrk::PenaltyParam), hipMemcpyHostToDevice, ctx->stream));
-    WRK_HIP(ctx, hipMemcpyAsync(dev + o_tok, tokens, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    wrk::occurrence_update(ctx->stream, V, 1, (const wrk::PenaltyParam*)dev, (const uint32_t*)(dev + o_tok), n);
+    wrk_dev_arena dev;
+    const size_t o_par = dev.add(sizeof(wrk::PenaltyParam)), o_tok = dev.add((size_t)n * 4);
+    WRK_HIP(ctx, dev.alloc());
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_par), par.data(), sizeof(wrk::PenaltyParam), hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_tok), tokens, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    wrk::occurrence_update(ctx->stream, V, 1, dev.at<wrk::PenaltyParam>(o_par), dev.at<uint32_t>(o_tok), n, wrk::RowGate{});
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
@@ -349,19 +317,16 @@ int32_t wrk_penalize_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t V, uint32_t 
                             uint32_t first, const float* presence, const float* frequency) {
     if (!ctx || !logits || !occ) return WRK_E_ARG;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    WRK_ARG(ctx, !ctx->capturing_here(), "wrk_penalize_logits is blocking: not inside a capture");
+    int32_t rc = wrk_rows_check(ctx, logits, V, stride, n, "wrk_penalize_logits", 0);
     std::vector<wrk::PenaltyParam> par;
-    int32_t rc = wrk_penalty_pack(ctx, occ, first, n, V, presence, frequency, nullptr, par);
+    if (rc == WRK_OK) rc = wrk_penalty_pack(ctx, occ, first, n, V, presence, frequency, nullptr, par);
     if (rc != WRK_OK || n == 0) return rc;
-    WRK_ARG(ctx, V >= 1 && stride >= V, "num_vocab %u / row_stride %u", V, stride);
-    WRK_ARG(ctx, ((size_t)(n - 1) * stride + V) * 4 <= logits->bytes, "%u rows of stride %u exceed the buffer of %zu bytes", n, stride,
-            logits->bytes);
     WRK_HIP(ctx, hipSetDevice(ctx->device));
-    char* dev = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&dev, (size_t)n * sizeof(wrk::PenaltyParam)));
-    struct Free { char* p; ~Free() { hipFree(p); } } guard{dev};
-    WRK_HIP(ctx, hipMemcpyAsync(dev, par.data(), (size_t)n * sizeof(wrk::PenaltyParam), hipMemcpyHostToDevice, ctx->stream));
-    wrk::penalize_rows(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::PenaltyParam*)dev, (float*)logits->ptr, stride);
+    wrk_dev_arena dev;
+    dev.add((size_t)n * sizeof(wrk::PenaltyParam));
+    WRK_HIP(ctx, dev.alloc());
+    WRK_HIP(ctx, hipMemcpyAsync(dev.base, par.data(), (size_t)n * sizeof(wrk::PenaltyParam), hipMemcpyHostToDevice, ctx->stream));
+    wrk::penalize_rows(ctx->stream, (const float*)logits->ptr, V, stride, n, dev.at<wrk::PenaltyParam>(0), (float*)logits->ptr, stride);
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;

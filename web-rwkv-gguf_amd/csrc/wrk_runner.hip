@@ -623,6 +623,30 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     return WRK_OK;
 }
 
+// Whether a row's draw of this step counts -- moves its Mirostat mu, enters its occurrence row -- as one RowGate for both: the flag the
+// previous step's advance wrote.  A finished sequence of a stop program, a prompt-phase or an idle slot of a queue program does not count
+static int32_t draw_gate(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, wrk::RowGate& g) {
+    g = wrk::RowGate{nullptr, 0u, 0u};
+    if (kind.tail == wrk_step_kind::STOP) {
+        if (!f.stop_par || B > f.stop_cap) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
+        g = wrk::RowGate{&f.stop_par->done, sizeof(wrk::StopParam) / 4, 0u};
+    } else if (kind.queue()) {
+        if (!f.queue_slots || B > f.queue_slot_cap) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+        g = wrk::RowGate{&f.queue_slots->phase, sizeof(wrk::QueueSlot) / 4, wrk::QUEUE_REPLY};
+    }
+    return WRK_OK;
+}
+
+// the occurrence rows count the drawn tokens in io.argmax (penalised kinds), under the step's gate
+static int32_t enqueue_occurrence_update(wrk_frame_common& f, uint32_t B, wrk_step_kind kind) {
+    if (!kind.penalized) return WRK_OK;
+    wrk::RowGate gate;
+    const int32_t rc = draw_gate(f, B, kind, gate);
+    if (rc != WRK_OK) return rc;
+    wrk::occurrence_update(f.ctx->op_stream(), f.facts().num_vocab, B, f.pen_par, f.io().argmax, 1, gate);
+    return WRK_OK;
+}
+
 // tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
 // token (penalised), advance_queue, queue_reset of slots [b0, b0 + B) of `st`; with a pool advance_queue_pool and queue_turnover,
 // launch for launch
@@ -633,7 +657,8 @@ static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind
     if (!f.queue_ctl || B > f.queue_slot_cap || b0 != 0 || B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
     if (kind.pool() && (!f.queue_state_ctl || B > f.queue_turn_cap || ((size_t)(st->head_size + 2) * st->num_emb) % 4 != 0))
         return wrk_fail(f.ctx, WRK_E_ARG, "state pool buffers are not prepared");
-    if (kind.penalized) wrk::occurrence_update_queue(q, V, B, f.pen_par, io.argmax, f.queue_slots);
+    const int32_t rc = enqueue_occurrence_update(f, B, kind);
+    if (rc != WRK_OK) return rc;
     const wrk::QueueBufs bufs = queue_bufs(f, kind);
     if (kind.pool()) {
         wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history, io.counter, bufs, queue_state_bufs(f), B);
@@ -711,7 +736,8 @@ static int32_t enqueue_stop_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind 
     hipStream_t q = f.ctx->op_stream();
     const wrk::FrameIo& io = f.io();
     if (!f.stop_par || B > f.stop_cap || b0 + B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
-    if (kind.penalized) wrk::occurrence_update_live(q, f.facts().num_vocab, B, f.pen_par, io.argmax, f.stop_par);
+    const int32_t rc = enqueue_occurrence_update(f, B, kind);
+    if (rc != WRK_OK) return rc;
     wrk::advance_stop(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(), B);
     wrk::stop_snapshot(q, stop_geom(f, st, b0), B, f.ctx->num_cu);
     return WRK_OK;
@@ -732,23 +758,15 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     } else if (kind.filtered() && (!f.filter_par || B > f.filter_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
     else if (kind.alt() && (!f.alt_par || B > f.alt_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "Mirostat / typical rows are not prepared");
     else {
-        int rc = 0;
+        // mu moves exactly where an occurrence row counts a draw: both read the step's one gate
+        wrk::SamplePick pick{wrk::SAMPLE_PLAIN, f.sample_par, nullptr, nullptr, wrk::RowGate{nullptr, 0u, 0u}};
+        if (kind.filtered()) { pick.mode = wrk::SAMPLE_FILT; pick.filt = f.filter_par; }
+        if (kind.alt()) { pick.mode = kind.mirostat() ? wrk::SAMPLE_MIRO : wrk::SAMPLE_TYP; pick.alt = f.alt_par; }
         if (kind.mirostat()) {
-            // mu moves exactly where an occurrence row counts a draw: the sampler reads the flag the tail's occurrence update reads --
-            // written by the previous step's advance -- so a finished sequence, a prompt-phase or an idle slot leaves mu alone
-            const uint32_t* gate = nullptr;
-            uint32_t stride = 0, eq = 0;
-            if (kind.tail == wrk_step_kind::STOP) {
-                if (!f.stop_par || B > f.stop_cap) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
-                gate = &f.stop_par->done; stride = sizeof(wrk::StopParam) / 4; eq = 0;
-            } else if (kind.queue()) {
-                if (!f.queue_slots || B > f.queue_slot_cap) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
-                gate = &f.queue_slots->phase; stride = sizeof(wrk::QueueSlot) / 4; eq = wrk::QUEUE_REPLY;
-            }
-            rc = wrk::sample_rows_mirostat(q, logits, V, V, B, f.sample_par, f.alt_par, gate, stride, eq, io.counter, io.argmax);
-        } else if (kind.pick == wrk_step_kind::TYPICAL) rc = wrk::sample_rows_typical(q, logits, V, V, B, f.sample_par, f.alt_par, io.counter, io.argmax);
-        else if (kind.filtered()) rc = wrk::sample_rows_filtered(q, logits, V, V, B, f.sample_par, f.filter_par, io.counter, io.argmax);
-        else rc = wrk::sample_rows(q, logits, V, V, B, f.sample_par, io.counter, io.argmax);
+            const int32_t grc = draw_gate(f, B, kind, pick.gate);
+            if (grc != WRK_OK) return grc;
+        }
+        const int rc = wrk::sample_rows(q, logits, V, V, B, pick, io.counter, io.argmax);
         if (rc != 0) return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
     }
     // the picked tokens are in io.argmax and the tail has not moved the counter: row *counter of the frame's buffers, on the raw head output
@@ -759,7 +777,8 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     }
     if (kind.queue()) return enqueue_queue_tail(f, B, kind, st, b0);
     if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, B, kind, st, b0);
-    if (kind.penalized) wrk::occurrence_update(q, V, B, f.pen_par, io.argmax, 1);
+    const int32_t urc = enqueue_occurrence_update(f, B, kind);
+    if (urc != WRK_OK) return urc;
     wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);
     return WRK_OK;
 }

@@ -10,13 +10,13 @@
 // each pass stops the descent as soon as the chosen bin holds one token.  Masses are fixed point (e * 2^40 in u64): every sum that
 // feeds a decision is an integer sum, so the result does not depend on the order the atomics land in.
 //
-// sample_rows_filtered_kernel (DESIGN.md "Top-k and min-p") shares the body.  A top-k cut is one more prefix of the same order: its
+// MODE SAMPLE_FILT (DESIGN.md "Top-k and min-p") shares the body.  A top-k cut is one more prefix of the same order: its
 // boundary, the token at rank top_k - 1, is a COUNT select over K, and the pass histograms already hold cnt next to mass, so it rides the
 // nucleus's descent: each pass finds the bin the mass target chooses and the bin the count target chooses; the higher bin (the earlier
 // rank) wins and the other target is dropped, equal bins descend with both.  The min-p cut, fl32(l - mx) >= ln(min_p), is part of the
 // draw's candidate predicate.
 //
-// sample_rows_mirostat_kernel and sample_rows_typical_kernel (DESIGN.md "Mirostat v2 and locally typical sampling") share the body too.
+// MODE SAMPLE_MIRO and SAMPLE_TYP (DESIGN.md "Mirostat v2 and locally typical sampling") share the body too.
 // Mirostat: one full-row mass pass gives W; "rank 0, or surprise <= mu" is a term of the draw's candidate predicate; no boundary descent;
 // the draw's pass-0 total is W_c, from which one lane takes the drawn token's surprise and writes the next mu.  Typical: one moments
 // pass (sum e and sum e g in fixed point, g = max - l) gives gbar; the boundary is the nucleus's mass select over the key
@@ -25,28 +25,19 @@
 #include <cmath>
 #include <type_traits>
 
-#include "wrk_device.h"
+#include "wrk_rows_dev.h"
 
 namespace wrk {
 
 static constexpr uint32_t SAMPLE_BINS = 2048;
 static constexpr uint32_t SAMPLE_THREADS = 1024;
 static constexpr float SAMPLE_ONE = 1099511627776.0f;      // 2^40: mass of the row's top token
-// the largest register copy (tokens per thread) of the Mirostat / typical kernels that does not spill; longer rows are
-// re-read from L2
-static constexpr int MIRO_NPT_MAX = 8, TYP_NPT_MAX = 8;
 
 __host__ __device__ inline uint64_t sample_splitmix(uint32_t seed, uint32_t step) {
     uint64_t z = (((uint64_t)seed << 32) | step) + 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint64_t rank_key(float l, uint32_t i) {
-    uint32_t b = __float_as_uint(l);
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((uint64_t)b << 20) | (0xFFFFFu - i);
 }
 
 // pass-0 digit, higher = earlier rank: (mx - l) * scale, monotone in l; l == mx also covers mx = +inf
@@ -141,9 +132,6 @@ __device__ __forceinline__ unsigned long long block_sum(unsigned long long v, Sa
 }
 
 static constexpr uint32_t SAMPLE_NO_COUNT = 0xffffffffu;
-enum : int { SAMPLE_PLAIN = 0, SAMPLE_FILT = 1, SAMPLE_MIRO = 2, SAMPLE_TYP = 3 };
-// of a Mirostat row: whether its draw counts (moves mu); gate == nullptr: always
-struct SampleGate { const uint32_t* gate; uint32_t stride, eq; };
 
 // One row per workgroup.  NPT > 0: the row (V <= 1024 * NPT) stays in registers; NPT == 0: every pass re-reads it from L2 (V <= 2^20;
 // a 64-per-thread register copy of a 65536-token row spills, the passes' own state needs ~95 VGPRs)
@@ -152,7 +140,7 @@ struct SampleGate { const uint32_t* gate; uint32_t stride, eq; };
 template <int NPT, int MODE>
 __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __restrict__ logits, uint32_t V, uint32_t stride,
                                                  const SampleParam* __restrict__ par, const SampleFilter* __restrict__ filt,
-                                                 SampleAlt* alt, const SampleGate gate,
+                                                 SampleAlt* alt, const RowGate gate,
                                                  const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
     constexpr bool FILT = MODE == SAMPLE_FILT, MIRO = MODE == SAMPLE_MIRO, TYP = MODE == SAMPLE_TYP;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -161,7 +149,7 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
     auto load = [&](int j) -> float {
         const uint32_t i = tid + SAMPLE_THREADS * (uint32_t)j;
         const float x = i < V ? row[i] : -INFINITY;
-        return x != x ? -INFINITY : x + 0.0f;       // NaN counts as -inf (p = 0); -0 becomes +0 (ties by index, not by sign bit)
+        return row_norm(x);
     };
     float lv[NPT > 0 ? NPT : 1];
     if constexpr (NPT > 0) {
@@ -418,13 +406,13 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
     if (cut_p || cut_k) {           // kmin = max(kmin_P, kmin_K) in one descent; with cut_k alone it is count-only
         const uint32_t r = select(std::false_type{}, false, 0, cut_p, cut_k ? top_k - 1u : SAMPLE_NO_COUNT);
         const float lr = row[r];       // r < V: a token index
-        kmin = rank_key(lr != lr ? -INFINITY : lr + 0.0f, r);
+        kmin = rank_key(row_norm(lr), r);
     }
     if constexpr (TYP) {
         if (typ) {                  // the boundary of the typical order; the draw's kmin is a d-key
             const uint32_t r = select(std::true_type{}, false, 0, true, SAMPLE_NO_COUNT);
             const float lr = row[r];
-            kmin = typical_key(typical_dist(lr != lr ? -INFINITY : lr + 0.0f, mx, gbar), r);
+            kmin = typical_key(typical_dist(row_norm(lr), mx, gbar), r);
         }
     }
     const uint32_t tok = select(std::false_type{}, true, kmin, true, SAMPLE_NO_COUNT);
@@ -432,9 +420,8 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
         out[blockIdx.x] = tok;
         if constexpr (MIRO) {
             // the drawn token's surprise among the candidates, its own term from its logit (a weight of 2^-30 keeps ten bits in fixed point)
-            if (miro && (!gate.gate || gate.gate[(size_t)blockIdx.x * gate.stride] == gate.eq)) {
-                float ly = row[tok];
-                ly = ly != ly ? -INFINITY : ly + 0.0f;
+            if (miro && row_counts(gate, blockIdx.x)) {
+                const float ly = row_norm(row[tok]);
                 const float x = ly == mx ? 0.0f : (ly - mx) * inv_t;
                 const float s = (log2f((float)draw_total) - 40.0f) - x * SAMPLE_LOG2E;
                 alt[blockIdx.x].mu = mu - eta * (s - tau);
@@ -443,89 +430,43 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
     }
 }
 
-template <int NPT>
+// MODE SAMPLE_FILT: a top-k and a min-p cut per row (filt[row]).  SAMPLE_MIRO: Mirostat v2 per row (alt[row]: tau, eta and the running
+// mu, rewritten when the draw counts).  SAMPLE_TYP: the locally typical cut per row (alt[row].typical_p).  A row whose own cut is off
+// draws SAMPLE_PLAIN's token, bit for bit.  The arguments every mode reads come first: they are the preloaded kernarg words
+template <int NPT, int MODE>
 __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
                                                                      const SampleParam* __restrict__ par, const uint32_t* __restrict__ step_word,
-                                                                     uint32_t* __restrict__ out) {
+                                                                     uint32_t* __restrict__ out, const SampleFilter* __restrict__ filt,
+                                                                     SampleAlt* alt, const RowGate gate) {
     __shared__ SampleSmem sm;
-    sample_rows_body<NPT, SAMPLE_PLAIN>(sm, logits, V, stride, par, nullptr, nullptr, SampleGate{}, step_word, out);
+    sample_rows_body<NPT, MODE>(sm, logits, V, stride, par, filt, alt, gate, step_word, out);
 }
 
-// sample_rows_kernel with a top-k and a min-p cut per row (filt[row]); both off: sample_rows_kernel's token, bit for bit
-template <int NPT>
-__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_filtered_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
-                                                                              const SampleParam* __restrict__ par,
-                                                                              const SampleFilter* __restrict__ filt,
-                                                                              const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
-    __shared__ SampleSmem sm;
-    sample_rows_body<NPT, SAMPLE_FILT>(sm, logits, V, stride, par, filt, nullptr, SampleGate{}, step_word, out);
+// The largest register copy (tokens per thread) of a mode; longer rows are re-read from L2.  Next to the count select's state of
+// SAMPLE_FILT a 16-per-thread copy spills (88 bytes of scratch per lane), and so it does next to the Mirostat / typical state (DESIGN.md
+// §7i): those keep 8 per thread, and their rows of 8193..16384 tokens are re-read
+constexpr int sample_npt_max(int mode) { return mode == SAMPLE_PLAIN ? 16 : 8; }
+
+template <int MODE>
+static void sample_rows_mode(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SamplePick& p, const uint32_t* step,
+                             uint32_t* out) {
+    constexpr int TOP = sample_npt_max(MODE);
+    if (v <= 1024) sample_rows_kernel<1, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate);
+    else if (v <= 4096) sample_rows_kernel<4, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate);
+    else if (v <= TOP * 1024) sample_rows_kernel<TOP, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate);
+    else sample_rows_kernel<0, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate);
 }
 
-// sample_rows_kernel with Mirostat v2 per row (alt[row]: tau, eta and the running mu, rewritten when the draw counts); tau == 0:
-// sample_rows_kernel's token, bit for bit
-template <int NPT>
-__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_mirostat_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
-                                                                              const SampleParam* __restrict__ par, SampleAlt* alt,
-                                                                              const SampleGate gate, const uint32_t* __restrict__ step_word,
-                                                                              uint32_t* __restrict__ out) {
-    __shared__ SampleSmem sm;
-    sample_rows_body<NPT, SAMPLE_MIRO>(sm, logits, V, stride, par, nullptr, alt, gate, step_word, out);
-}
-
-// sample_rows_kernel with the locally typical cut per row (alt[row].typical_p); >= 1: sample_rows_kernel's token, bit for bit
-template <int NPT>
-__global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_typical_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
-                                                                             const SampleParam* __restrict__ par, SampleAlt* alt,
-                                                                             const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
-    __shared__ SampleSmem sm;
-    sample_rows_body<NPT, SAMPLE_TYP>(sm, logits, V, stride, par, nullptr, alt, SampleGate{}, step_word, out);
-}
-
-int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, const uint32_t* step,
+int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SamplePick& pick, const uint32_t* step,
                 uint32_t* out) {
     if (n == 0) return 0;
     if (v == 0 || v > SAMPLE_MAX_VOCAB || stride < v) return -1;
-    if (v <= 1024) sample_rows_kernel<1><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
-    else if (v <= 4096) sample_rows_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
-    else if (v <= 16384) sample_rows_kernel<16><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
-    else sample_rows_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, step, out);
-    return 0;
-}
-
-int sample_rows_filtered(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
-                         const SampleFilter* filt, const uint32_t* step, uint32_t* out) {
-    if (n == 0) return 0;
-    if (v == 0 || v > SAMPLE_MAX_VOCAB || stride < v) return -1;
-    if (v <= 1024) sample_rows_filtered_kernel<1><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
-    else if (v <= 4096) sample_rows_filtered_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
-    // a 16-per-thread register copy spills next to the count select's state (88 bytes of scratch per lane): this variant keeps 8 per
-    // thread, and rows of 8193..16384 tokens are re-read from L2
-    else if (v <= 8192) sample_rows_filtered_kernel<8><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
-    else sample_rows_filtered_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, filt, step, out);
-    return 0;
-}
-
-int sample_rows_mirostat(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par, SampleAlt* alt,
-                         const uint32_t* gate, uint32_t gate_stride, uint32_t gate_eq, const uint32_t* step, uint32_t* out) {
-    if (n == 0) return 0;
-    if (v == 0 || v > SAMPLE_MAX_VOCAB || stride < v) return -1;
-    const SampleGate g{gate, gate_stride, gate_eq};
-    if (v <= 1024) sample_rows_mirostat_kernel<1><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, alt, g, step, out);
-    else if (v <= 4096) sample_rows_mirostat_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, alt, g, step, out);
-    else if (v <= MIRO_NPT_MAX * 1024) sample_rows_mirostat_kernel<MIRO_NPT_MAX><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, alt, g, step, out);
-    else sample_rows_mirostat_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, alt, g, step, out);
-    return 0;
-}
-
-int sample_rows_typical(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SampleParam* par,
-                        const SampleAlt* alt, const uint32_t* step, uint32_t* out) {
-    if (n == 0) return 0;
-    if (v == 0 || v > SAMPLE_MAX_VOCAB || stride < v) return -1;
-    SampleAlt* a = const_cast<SampleAlt*>(alt);     // the shared body writes mu in the Mirostat kernel only
-    if (v <= 1024) sample_rows_typical_kernel<1><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, a, step, out);
-    else if (v <= 4096) sample_rows_typical_kernel<4><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, a, step, out);
-    else if (v <= TYP_NPT_MAX * 1024) sample_rows_typical_kernel<TYP_NPT_MAX><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, a, step, out);
-    else sample_rows_typical_kernel<0><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, par, a, step, out);
+    switch (pick.mode) {
+        case SAMPLE_FILT: sample_rows_mode<SAMPLE_FILT>(s, logits, v, stride, n, pick, step, out); break;
+        case SAMPLE_MIRO: sample_rows_mode<SAMPLE_MIRO>(s, logits, v, stride, n, pick, step, out); break;
+        case SAMPLE_TYP: sample_rows_mode<SAMPLE_TYP>(s, logits, v, stride, n, pick, step, out); break;
+        default: sample_rows_mode<SAMPLE_PLAIN>(s, logits, v, stride, n, pick, step, out); break;
+    }
     return 0;
 }
 
@@ -555,8 +496,6 @@ int32_t wrk_filter_pack(wrk_ctx* ctx, const uint32_t* top_k, const float* min_p,
     }
     return WRK_OK;
 }
-
-static bool finite_f32(float x) { return x - x == 0.0f; }
 
 int32_t wrk_mirostat_pack(wrk_ctx* ctx, const float* tau, const float* eta, const float* mu, uint32_t n, std::vector<wrk::SampleAlt>& out) {
     WRK_ARG(ctx, tau, "mirostat_eta / mirostat_mu without mirostat_tau");
@@ -612,37 +551,30 @@ static int32_t sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, ui
     }
     if (rc != WRK_OK) return rc;
     if (n == 0) return WRK_OK;
-    WRK_ARG(ctx, !ctx->capturing_here(), "%s is blocking: not inside a capture", who);
-    WRK_ARG(ctx, V >= 1 && stride >= V, "num_vocab %u / row_stride %u", V, stride);
-    if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "num_vocab %u > %u", V, wrk::SAMPLE_MAX_VOCAB);
-    WRK_ARG(ctx, ((size_t)(n - 1) * stride + V) * 4 <= logits->bytes, "%u rows of stride %u exceed the buffer of %zu bytes", n, stride,
-            logits->bytes);
+    rc = wrk_rows_check(ctx, logits, V, stride, n, who, wrk::SAMPLE_MAX_VOCAB);
+    if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_step = (size_t)n * sizeof(wrk::SampleParam), o_out = o_step + 256, o_filt = (o_out + (size_t)n * 4 + 255) / 256 * 256;
-    static_assert(sizeof(wrk::SampleAlt) >= sizeof(wrk::SampleFilter), "the rows after o_filt are sized for the larger struct");
-    char* dev = nullptr;
-    WRK_HIP(ctx, hipMalloc((void**)&dev, o_filt + (size_t)n * sizeof(wrk::SampleAlt)));
-    struct Free { char* p; ~Free() { hipFree(p); } } guard{dev};
-    WRK_HIP(ctx, hipMemcpyAsync(dev, par.data(), o_step, hipMemcpyHostToDevice, ctx->stream));
-    WRK_HIP(ctx, hipMemcpyAsync(dev + o_step, &step, 4, hipMemcpyHostToDevice, ctx->stream));
+    static_assert(sizeof(wrk::SampleAlt) >= sizeof(wrk::SampleFilter), "the rows at o_rows are sized for the larger struct");
+    wrk_dev_arena dev;
+    const size_t o_par = dev.add((size_t)n * sizeof(wrk::SampleParam)), o_step = dev.add(4), o_out = dev.add((size_t)n * 4);
+    const size_t o_rows = dev.add((size_t)n * sizeof(wrk::SampleAlt));
+    WRK_HIP(ctx, dev.alloc());
+    wrk::SamplePick pick{wrk::SAMPLE_PLAIN, dev.at<wrk::SampleParam>(o_par), nullptr, nullptr, wrk::RowGate{}};
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_par), par.data(), (size_t)n * sizeof(wrk::SampleParam), hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_step), &step, 4, hipMemcpyHostToDevice, ctx->stream));
     if (filtered) {
-        WRK_HIP(ctx, hipMemcpyAsync(dev + o_filt, filt.data(), (size_t)n * sizeof(wrk::SampleFilter), hipMemcpyHostToDevice, ctx->stream));
-        wrk::sample_rows_filtered(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev,
-                                  (const wrk::SampleFilter*)(dev + o_filt), (const uint32_t*)(dev + o_step), (uint32_t*)(dev + o_out));
+        pick.mode = wrk::SAMPLE_FILT;
+        pick.filt = dev.at<wrk::SampleFilter>(o_rows);
+        WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_rows), filt.data(), (size_t)n * sizeof(wrk::SampleFilter), hipMemcpyHostToDevice, ctx->stream));
     } else if (miro || typical) {
-        wrk::SampleAlt* rows = (wrk::SampleAlt*)(dev + o_filt);
-        WRK_HIP(ctx, hipMemcpyAsync(rows, alt.data(), (size_t)n * sizeof(wrk::SampleAlt), hipMemcpyHostToDevice, ctx->stream));
-        if (miro) wrk::sample_rows_mirostat(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, rows, nullptr, 0, 0,
-                                            (const uint32_t*)(dev + o_step), (uint32_t*)(dev + o_out));
-        else wrk::sample_rows_typical(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, rows,
-                                      (const uint32_t*)(dev + o_step), (uint32_t*)(dev + o_out));
-    } else {
-        wrk::sample_rows(ctx->stream, (const float*)logits->ptr, V, stride, n, (const wrk::SampleParam*)dev, (const uint32_t*)(dev + o_step),
-                         (uint32_t*)(dev + o_out));
+        pick.mode = miro ? wrk::SAMPLE_MIRO : wrk::SAMPLE_TYP;
+        pick.alt = dev.at<wrk::SampleAlt>(o_rows);
+        WRK_HIP(ctx, hipMemcpyAsync(pick.alt, alt.data(), (size_t)n * sizeof(wrk::SampleAlt), hipMemcpyHostToDevice, ctx->stream));
     }
+    wrk::sample_rows(ctx->stream, (const float*)logits->ptr, V, stride, n, pick, dev.at<uint32_t>(o_step), dev.at<uint32_t>(o_out));
     WRK_LAUNCH_CHECK(ctx);
-    WRK_HIP(ctx, hipMemcpyAsync(out_tokens, dev + o_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (miro && kind.mu_inout) WRK_HIP(ctx, hipMemcpyAsync(alt.data(), dev + o_filt, (size_t)n * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(out_tokens, dev.at<char>(o_out), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (miro && kind.mu_inout) WRK_HIP(ctx, hipMemcpyAsync(alt.data(), pick.alt, (size_t)n * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (miro && kind.mu_inout)
         for (uint32_t b = 0; b < n; ++b) kind.mu_inout[b] = alt[b].mu;

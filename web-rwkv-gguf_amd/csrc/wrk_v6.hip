@@ -32,8 +32,6 @@ struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, key
     int32_t enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_t NH, bool identity, uint32_t batch0);
 };
 
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int32_t wrk_v6_model::ensure_scratch(uint32_t T, uint32_t NH) {
     if (T <= scratch_tokens && NH <= scratch_headers && scratch) return WRK_OK;
     if (ctx->capturing_here()) return wrk_fail(ctx, WRK_E_ARG, "scratch must be sized before capture");
@@ -44,7 +42,7 @@ int32_t wrk_v6_model::ensure_scratch(uint32_t T, uint32_t NH) {
     scratch = nullptr;
     const size_t D = d.num_emb, F = d.num_hidden, V = d.num_vocab, R = d.time_mix, W = d.time_decay;
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += up256(bytes); return o; };
+    auto take = [&](size_t bytes) { size_t o = off; off += wrk_up256(bytes); return o; };
     const size_t v16 = D * nt * 2, v32 = D * nt * 4;
     const size_t o_input = take(v16), o_x = take(v16), o_aux = take(v16), o_attx = take(v16), o_attxx = take(v16), o_sx = take(v16 * 5);
     const size_t o_w = take(W * nt * 2), o_g = take(v16), o_o = take(v16), o_tmx = take(R * 5 * nt * 2), o_tmt = take(R * 5 * nt * 2), o_tm = take(v16 * 5);

@@ -15,7 +15,6 @@ static constexpr float LN_EPS = 1.0e-5f;    // v7.rs:47
 static constexpr float GN_EPS = 64.0e-5f;   // v7.rs:48
 static constexpr float L2_EPS = 1.0e-12f;   // v7.rs:46
 
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 using wrk::mat_job;
 
 // ------------------------------------------------------------------ scratch ("Runtime<f16>" + "Header<f16>")
@@ -30,7 +29,7 @@ int32_t wrk_v7_model::ensure_scratch(uint32_t T, uint32_t NH) {
     scratch = nullptr;
     const size_t D = d.num_emb, F = d.num_hidden, V = d.num_vocab;
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += up256(bytes); return o; };
+    auto take = [&](size_t bytes) { size_t o = off; off += wrk_up256(bytes); return o; };
     const size_t esz = act_dtype == WRK_F32 ? 4 : 2;        // Runtime<F>: every buffer but `input` holds F
     const size_t vecT = D * nt * esz;
     size_t o_named[32];

@@ -1283,8 +1283,8 @@ class Runtime:
                           C.pointer(run))
         self.last_logprobs = None
         if logprobs is not None:
-            lp, ids, tlp = _logprob_arrays(logprobs, int(mn.sum()))
-            opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(ids, _u32p), _ptr(tlp, _f32p)
+            lp, top_ids, tlp = _logprob_arrays(logprobs, int(mn.sum()))     # `ids` stays alive: opt.stop_tokens points into it
+            opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(top_ids, _u32p), _ptr(tlp, _f32p)
         if pool is None:
             if start_state is not None or save_state is not None:
                 raise ValueError("start_state / save_state need a pool")
@@ -1307,7 +1307,7 @@ class Runtime:
         off = np.concatenate([[0], np.cumsum(mn)]).astype(np.int64)
         if logprobs is not None:
             n = int(logprobs)
-            self.last_logprobs = [(lp[off[r]:off[r] + lengths[r]].copy(), ids[off[r] * n:(off[r] + lengths[r]) * n].reshape(-1, n).copy(),
+            self.last_logprobs = [(lp[off[r]:off[r] + lengths[r]].copy(), top_ids[off[r] * n:(off[r] + lengths[r]) * n].reshape(-1, n).copy(),
                                    tlp[off[r] * n:(off[r] + lengths[r]) * n].reshape(-1, n).copy()) for r in range(R)]
         return [(out[off[r]:off[r] + lengths[r]].copy(), int(reasons[r]), int(slots[r]), int(starts[r])) for r in range(R)], run.value
 
