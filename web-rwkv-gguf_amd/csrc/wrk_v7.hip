@@ -543,7 +543,9 @@ int32_t wrk_v7_model_engine_status(wrk_ctx* ctx, wrk_v7_model* m, char* why, siz
     const int32_t rc = m->ensure_engine();
     if (rc != WRK_OK) return rc;
     if (why && capacity) {
-        const std::string& w = m->engine ? std::string() : (m->engine_tried ? m->engine_why : std::string("disabled (WRK_ENGINE=0 or f32 frames)"));
+        // with an engine: how it was built ("8 compute waves"), so that a caller can tell which kernel its tokens run on
+        const std::string w = m->engine ? std::to_string(wrk_v7_engine_waves(m->engine)) + " compute waves"
+                                        : (m->engine_tried ? m->engine_why : std::string("disabled (WRK_ENGINE=0 or f32 frames)"));
         snprintf(why, capacity, "%s", w.c_str());
     }
     return m->engine ? 1 : 0;

@@ -67,6 +67,56 @@ struct EngArgs {
 };
 constexpr int ENG_STAMPS = 32;
 
+// ---- rows of a compute wave in the one-wave-per-row stages (K1, K3, K5)
+// The `nrows` rows of a workgroup go out in PAIRS (a granule carries two f16 outputs), every wave takes a contiguous range, in wave
+// order, and the pair counts differ by at most one.  Which waves take the `pairs % ncw` extra pairs is chosen by SIMD: a workgroup's
+// waves go to the four SIMDs round-robin (wave % 4), the gather wave (wave ncw) and the loader (ncw + 1) share two of them with the
+// compute waves, so extra pair k goes to the k-th SIMD counted from the one behind the loader's -- the two SIMDs without a service wave
+// first -- and to that SIMD's (k / 4)-th compute wave.  The extra pairs of any two SIMDs differ by at most one.
+// 1.5B on 256 CUs: K1's 36 rows of r / k / v = 18 pairs on 8 waves -> 4 4 6 6 4 4 4 4 rows (SIMDs 2 and 3 carry 10, SIMDs 0 and 1
+// carry 8 and a service wave); the 10 rows of a LoRA workgroup -> one pair on waves 2 3 0 1 6.
+constexpr __host__ __device__ uint32_t eng_wave_pairs(uint32_t pairs, uint32_t ncw, uint32_t wave) {
+    const uint32_t simd_rank = (wave + 4u - (ncw + 2u) % 4u) % 4u;      // 0, 1: SIMDs that hold compute waves only
+    return pairs / ncw + ((wave / 4u) * 4u + simd_rank < pairs % ncw ? 1u : 0u);
+}
+// pairs of the waves in front of `wave`: whole groups of four waves take their extra pairs in full, the wave's own group one by one
+constexpr __host__ __device__ uint32_t eng_wave_first_pair(uint32_t pairs, uint32_t ncw, uint32_t wave) {
+    const uint32_t extra = pairs % ncw, g4 = (wave / 4u) * 4u;
+    uint32_t first = wave * (pairs / ncw) + (extra < g4 ? extra : g4);
+    for (uint32_t w = g4; w < wave; ++w) first += eng_wave_pairs(pairs, ncw, w) - pairs / ncw;
+    return first;
+}
+constexpr __host__ __device__ void eng_wave_rows(uint32_t nrows, uint32_t ncw, uint32_t wave, uint32_t& begin, uint32_t& end) {
+    const uint32_t pairs = (nrows + 1u) / 2u;
+    const uint32_t first = eng_wave_first_pair(pairs, ncw, wave), last = first + eng_wave_pairs(pairs, ncw, wave);
+    begin = 2u * first < nrows ? 2u * first : nrows;
+    end = 2u * last < nrows ? 2u * last : nrows;
+}
+// A pair that no wave owns is a granule that is never published: its consumers spin to their bound.  So the mapping is proved at
+// compile time, for both wave counts and every even row count a workgroup can get: ranges in wave order, contiguous and pair-aligned,
+// every pair owned exactly once, no wave above ceil(pairs / ncw), extra pairs spread evenly over the SIMDs, service-free SIMDs first.
+constexpr bool eng_wave_rows_ok(uint32_t ncw) {
+    for (uint32_t nrows = 0; nrows <= 128; nrows += 2) {
+        const uint32_t pairs = nrows / 2, most = (pairs + ncw - 1) / ncw;
+        uint32_t next = 0, simd[4] = {0, 0, 0, 0};
+        for (uint32_t w = 0; w < ncw; ++w) {
+            uint32_t b = 0, e = 0;
+            eng_wave_rows(nrows, ncw, w, b, e);
+            if (b != next || e < b || (b & 1u) || (e & 1u) || (e - b) / 2 > most || (e - b) / 2 < pairs / ncw) return false;
+            simd[w % 4] += (e - b) / 2 - pairs / ncw;
+            next = e;
+        }
+        if (next != nrows) return false;
+        const uint32_t s0 = (ncw + 2) % 4;                  // first SIMD without a service wave
+        for (uint32_t i = 0; i + 1 < 4; ++i) {              // extras fall in SIMD order s0, s0 + 1, ...: never rising, spread <= 1
+            const uint32_t a = simd[(s0 + i) % 4], c = simd[(s0 + i + 1) % 4];
+            if (c > a || simd[s0] - simd[(s0 + 3) % 4] > 1) return false;
+        }
+    }
+    return true;
+}
+static_assert(eng_wave_rows_ok(8) && eng_wave_rows_ok(14), "a row pair without exactly one owner wave, or an uneven schedule");
+
 }  // namespace wrk
 
 // host side (wrk_v7_engine.hip)
@@ -81,5 +131,6 @@ void wrk_v7_engine_destroy(wrk_v7_engine* e);
 int32_t wrk_v7_engine_enqueue(wrk_v7_engine* e, hipStream_t q, wrk_v7_state* st, uint32_t batch, uint32_t l0, uint32_t l1, const void* x_in,
                               void* x_out, void* v_first, const uint32_t* token = nullptr);
 bool wrk_v7_engine_has_table(const wrk_v7_engine* e);
+int wrk_v7_engine_waves(const wrk_v7_engine* e);     // compute waves per workgroup (8, or 14 with WRK_ENGINE_WAVES=14)
 int32_t wrk_v7_engine_check(wrk_v7_engine* e);       // after a synchronisation: WRK_E_HIP if a launch gave up
 void wrk_v7_engine_report(wrk_v7_engine* e);         // WRK_TIMING=1: print the in-kernel timeline of the stamped layer

@@ -218,8 +218,11 @@ __device__ __forceinline__ float eng_finish(const EngFin& f, uint32_t row, float
 }
 
 // Rows [r_begin, r_end) of the slot (relative to the workgroup's first row `row0`), one wave per row, lane L owns chunks L, L + 64, ...
-// of every row (KS == 1) -- dmv_body's arithmetic with LDS-resident weights.  Rows are taken four at a time; lane 0 publishes rows
-// (0, 1) of a batch as one granule, lane 1 rows (2, 3).  `gidx(row)` = granule index of the pair that starts at `row`.
+// of every row (KS == 1) -- dmv_body's arithmetic with LDS-resident weights.  The range is a whole number of row pairs (eng_wave_rows;
+// the host keeps a workgroup's row count even).  Rows are taken RB at a time; with RB == 4 and one chunk per lane a last pair is a
+// batch of TWO rows: the same loop body, whose dot products, reductions and finish of the missing pair are skipped by a wave-uniform
+// branch (a row's dot product does not depend on the batch it sits in).  Lane 0 publishes rows (0, 1) of a batch as one granule,
+// lane 1 rows (2, 3) of a batch of four.  `gidx(row)` = granule index of the pair that starts at `row`.
 template <int KIND, bool R16, int XI, int RB, class GIDX>
 __device__ __forceinline__ void eng_rows(const lds_u8* slot, uint32_t row_bytes, uint32_t K, const ENG_LDS f16* xs, uint32_t row0, uint32_t r_begin,
                                          uint32_t r_end, const EngFin& fin, ENG_LDS uint32_t* pub, unsigned long long* gran, uint32_t tag, GIDX gidx,
@@ -239,7 +242,13 @@ __device__ __forceinline__ void eng_rows(const lds_u8* slot, uint32_t row_bytes,
         x_sums<KIND>(x[0][ci]);
     }
     static_assert(RB == 2 || RB == 4, "rows per batch");
+    // The form of this loop is pinned by the register budget (profiles/engine_sched_resource_usage.txt: every instantiation at the
+    // parent's figures).  The LDS reads of a batch stay unconditional and clamped to the last row; only the arithmetic is switched.
+    // With more than one chunk per lane (D > 2048, and the F16 rows) the switch itself costs 5 - 12 spilled registers, so those
+    // instantiations keep the padded last batch: the pair is computed with its second row repeated, and only the pair is published.
+    constexpr bool PAD = XI > 1;
     for (uint32_t ri = r_begin; ri < r_end; ri += RB) {
+        const bool whole = PAD || RB == 2 || ri + RB <= r_end;      // wave-uniform: the batch computes all its RB rows
         Raw raw[RB][XI];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -249,15 +258,16 @@ __device__ __forceinline__ void eng_rows(const lds_u8* slot, uint32_t row_bytes,
         }
         float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            float acc[1] = {0.0f};
+        for (int rb = 0; rb < RB; ++rb)
+            if (rb < 2 || whole) {
+                float acc[1] = {0.0f};
 #pragma unroll
-            for (int ci = 0; ci < XI; ++ci) dot_raw_tokens<KIND, R16, 1, XI>(raw[rb][ci], min(lane + 64u * ci, nch - 1), x, ci, acc);
-            v[rb] = wave_sum(acc[0]);
-        }
+                for (int ci = 0; ci < XI; ++ci) dot_raw_tokens<KIND, R16, 1, XI>(raw[rb][ci], min(lane + 64u * ci, nch - 1), x, ci, acc);
+                v[rb] = wave_sum(acc[0]);
+            }
         if (lane < RB / 2) {
-            const uint32_t ra = ri + 2 * lane;              // first row of this lane's pair (rows come in pairs: host-checked)
-            if (ra < r_end) {
+            const uint32_t ra = ri + 2 * lane;              // first row of this lane's pair
+            if (ra < r_end) {                               // (a batch of two of RB == 4: lane 0 only)
                 const float o0 = eng_finish(fin, row0 + ra, lane ? v[2] : v[0]) * fin.post;
                 const float o1 = eng_finish(fin, row0 + ra + 1, lane ? v[3] : v[1]) * fin.post;
                 if (pub) pub[ra >> 1] = pack_h2(o0, o1);    // published by ONE wave, coalesced (eng_publish)
@@ -329,7 +339,25 @@ __device__ __forceinline__ void eng_ln_mix(bool active, const ENG_LDS f16* xraw,
 // NCW: compute waves (8 or 14).  Wave NCW gathers, wave NCW + 1 loads.  A lone wave on a SIMD issues one vector instruction per ~4
 // cycles, and the stages are instruction-issue bound (~125 instructions per row): the first build (4 compute waves, one per SIMD) spent
 // 1.9 us on the 8 rows per wave of K1 -- hence as many compute waves as the register file allows.
-constexpr int ENG_K2_BARRIERS = 6;      // barriers of stage K2, the first one included
+// Barriers of a stage, the first one included.  EVERY role executes exactly these on every path: the compute waves in their stage
+// bodies (each barrier there carries its number), the loader and the gather wave by replaying the counts (eng_replay).  The first
+// ENG_K2_CHECKED barriers of K2, and the first barrier of every other stage, are the ones a give-up can be raised in front of: all
+// three roles test the give-up flag behind each of them and leave the layer loop at the same barrier.  The flag is two words: between
+// K2's (1) and (2) the gather wave is already sweeping again while a slow compute wave may not yet have read the flag behind (1), so a
+// give-up of that second sweep is latched into abort_flag[1], which is read behind (2) only; abort_flag[0] is never written between a
+// barrier and the reads behind it.
+constexpr int ENG_LN_BARRIERS = 2;                          // eng_ln_mix: LN statistics | LN + shift written
+constexpr int ENG_K1_BARRIERS = 2 + ENG_LN_BARRIERS;        // input in LDS | LN | K1 done
+constexpr int ENG_K2_BARRIERS = 6;                          // (1) intermediates in | (2) r, k, v in + LoRA dots written | (3) | (4) | (5) | (6) K2 done
+constexpr int ENG_K2_CHECKED = 2;                           // (1) and (2)
+constexpr int ENG_K3_BARRIERS = 2;                          // input in LDS | K3 done
+constexpr int ENG_K5_BARRIERS = 3 + ENG_LN_BARRIERS;        // input in LDS | LN | row pairs in `pub` | K5 done
+constexpr int ENG_K6_BARRIERS = 3;                          // every wave has its inputs | partial sums written | K6 done
+template <int N>
+__device__ __forceinline__ void eng_replay() {
+#pragma unroll
+    for (int i = 0; i < N; ++i) ENG_BAR();
+}
 template <int XD, bool R16, int QK, int NCW>
 __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs A, const uint32_t* __restrict__ wg_head) {
     extern __shared__ __attribute__((aligned(16))) unsigned char eng_smem_generic[];
@@ -341,7 +369,7 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
     const uint32_t D = S.D, F = S.F;
     const uint32_t head = wg_head[2 * wg], k1r = wg_head[2 * wg + 1];       // head of this workgroup (or none); its rank among the K1 workgroups
     const bool is_head = head != ENG_NO_HEAD;
-    ENG_LDS uint32_t* abort_flag = (ENG_LDS uint32_t*)(smem + S.lds_misc + 1008);
+    ENG_LDS uint32_t* abort_flag = (ENG_LDS uint32_t*)(smem + S.lds_misc + 1008);       // [0]: every checked barrier but K2's (2); [1]: K2's (2)
     ENG_LDS float* red = (ENG_LDS float*)(smem + S.lds_misc);                // 8 floats
     ENG_LDS float* part = (ENG_LDS float*)(smem + S.lds_misc + 64);          // 32 rows x 4 K quarters
     ENG_LDS uint32_t* pub = (ENG_LDS uint32_t*)(smem + S.lds_misc + 64);     // K1 / K3 / K5: the payload of every row pair of the workgroup (<= 128)
@@ -387,7 +415,7 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
     } while (0)
 
     if (A.stamps && tid_all < (NCW + 2) * 24) lds_stamps[tid_all] = 0;
-    if (tid_all == 0) *abort_flag = 0;
+    if (tid_all == 0) { abort_flag[0] = 0; abort_flag[1] = 0; }
     ENG_BAR();
 
     // ================================================================== loader wave
@@ -416,33 +444,34 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             ENG_BAR();
             if (*abort_flag) break;
             if (p6) { fill6(l); p6 = false; }
-            ENG_BAR(); ENG_BAR(); ENG_BAR();
+            eng_replay<ENG_K1_BARRIERS - 1>();
             ENG_STAMP(l, 0);
             if (more) fill1(l + 1);                         // K1's own slot at once: until K3's gather this workgroup polls nothing (a head workgroup has no K1 rows)
             // K2
             if (is_head) {
-                ENG_BAR();
+                ENG_BAR();                                  // (1)
                 if (*abort_flag) break;
-#pragma unroll
-                for (int i = 1; i < ENG_K2_BARRIERS; ++i) ENG_BAR();
+                ENG_BAR();                                  // (2)
+                if (abort_flag[1]) break;
+                eng_replay<ENG_K2_BARRIERS - ENG_K2_CHECKED>();
             }
             // K3
             eng_wait_vm(issued - m3);
             ENG_BAR();
             if (*abort_flag) break;
-            ENG_BAR();
+            eng_replay<ENG_K3_BARRIERS - 1>();
             // K5
             eng_wait_vm(issued - m5);
             ENG_BAR();
             if (*abort_flag) break;
             if (more) fill3(l + 1);
-            ENG_BAR(); ENG_BAR(); ENG_BAR(); ENG_BAR();
+            eng_replay<ENG_K5_BARRIERS - 1>();
             // K6
             eng_wait_vm(issued - m6);
             ENG_BAR();
             if (*abort_flag) break;
             if (more) fill5(l + 1);
-            ENG_BAR(); ENG_BAR();
+            eng_replay<ENG_K6_BARRIERS - 1>();
             p6 = more;
             ENG_FLUSH(l);
         }
@@ -462,18 +491,21 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             ENG_STAMP(l, 0);
             ENG_BAR();
             if (*abort_flag) break;
-            ENG_BAR(); ENG_BAR(); ENG_BAR();
-            // K2: LoRA intermediates + this head's r, k, v
+            eng_replay<ENG_K1_BARRIERS - 1>();
+            // K2: the LoRA intermediates, which the up-projections start on at once, then this head's r, k, v behind them in auxbuf
             if (is_head) {
                 // (layer 0 has no value-residual LoRA: its granules are never written there)
                 ok = eng_gather(A.gran + S.g_k1, (l == 0 ? naux - S.rv : naux) >> 2, eng_tag(l, 0), (ENG_LDS uint32_t*)auxbuf, lane);
-                if (ok) ok = eng_gather(A.gran + S.g_k1 + S.g_aux + head * 96u, 48u, eng_tag(l, 0), (ENG_LDS uint32_t*)(auxbuf + naux), lane);
                 if (!ok && lane == 0) { *abort_flag = 1; atomicOr(A.fail, 2u); }
-                ENG_STAMP(l, 1);
-                ENG_BAR();
+                ENG_STAMP(l, 4);
+                ENG_BAR();                                  // (1)
                 if (*abort_flag) break;
-#pragma unroll
-                for (int i = 1; i < ENG_K2_BARRIERS; ++i) ENG_BAR();
+                ok = eng_gather(A.gran + S.g_k1 + S.g_aux + head * 96u, 48u, eng_tag(l, 0), (ENG_LDS uint32_t*)(auxbuf + naux), lane);
+                if (!ok && lane == 0) { abort_flag[1] = 1; atomicOr(A.fail, 2u); }
+                ENG_STAMP(l, 1);
+                ENG_BAR();                                  // (2)
+                if (abort_flag[1]) break;
+                eng_replay<ENG_K2_BARRIERS - ENG_K2_CHECKED>();
             }
             // K3: the gated head outputs
             ok = eng_gather(A.gran + S.g_o, D >> 2, eng_tag(l, 1), (ENG_LDS uint32_t*)xs, lane);
@@ -481,18 +513,18 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             ENG_STAMP(l, 2);
             ENG_BAR();
             if (*abort_flag) break;
-            ENG_BAR();
+            eng_replay<ENG_K3_BARRIERS - 1>();
             // K5: x after the time mix
             ok = eng_gather(A.gran + S.g_x1, D >> 2, eng_tag(l, 2), (ENG_LDS uint32_t*)xraw1, lane);
             if (!ok && lane == 0) { *abort_flag = 1; atomicOr(A.fail, 8u); }
             ENG_STAMP(l, 3);
             ENG_BAR();
             if (*abort_flag) break;
-            ENG_BAR(); ENG_BAR(); ENG_BAR(); ENG_BAR();
+            eng_replay<ENG_K5_BARRIERS - 1>();
             // K6: the compute waves poll their own quarters of the ffn vector
             ENG_BAR();
             if (*abort_flag) break;
-            ENG_BAR(); ENG_BAR();
+            eng_replay<ENG_K6_BARRIERS - 1>();
             ENG_FLUSH(l);
         }
         return;
@@ -505,12 +537,6 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
     const uint32_t nvec = D >> 3;
     const float eps = S.ln_eps;
     const bool ln_wave = wave < 4;                          // the 256 threads of the launches' mapping
-    // rows of a wave in the KS == 1 stages: a contiguous block of row pairs
-    auto wave_rows = [&](uint32_t nrows, uint32_t& b, uint32_t& e) {
-        const uint32_t q = 2u * (((nrows + 1u) / 2u + NCW - 1u) / NCW);
-        b = min(wave * q, nrows);
-        e = min(b + q, nrows);
-    };
     const uint32_t c0 = is_head ? head * S64 : 0u;
     float vfirst_keep = 0.0f;                               // wave 0, lane = channel of the head
     if (is_head && S.layer_begin > 0 && wave == 0) vfirst_keep = (float)((const f16*)A.v_first)[c0 + (tid_all & 63u)];
@@ -574,7 +600,7 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             if (k1_active(l)) {
                 const EngJob& J = S.k1[j1];
                 uint32_t rb, re;
-                wave_rows(k1_rows, rb, re);
+                eng_wave_rows(k1_rows, NCW, wave, rb, re);
                 const EngFin fin{J.act, sc_k1, nullptr, 1.0f};
                 const lds_u8* slot = smem + S.lds_slot1;
                 ENG_LDS uint32_t* nopub = nullptr;
@@ -592,7 +618,9 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             ENG_BAR();                                      // K1 done: slot, xs free
         } else {
             // ================================================ K1 on a head workgroup: no rows; the LoRA up-projection rows, per-channel
-            // vectors and the state of K2 are requested NOW, a whole stage before they are needed (80 KB through one CU take 2 - 3 us)
+            // vectors and the state of K2 are requested NOW, a whole stage before they are needed (80 KB through one CU take 2 - 3 us).
+            // The compute waves stall ISSUING them: this workgroup passes the barrier below at ~2.9 us.  Requested behind that barrier,
+            // or with LN moved behind K2's barrier (1), the step was 3 % / 1 % slower (profiles/engine_sched_ab.txt).
             const EngLayer& Lp = A.layers[l];
             const uint8_t* p_m[4] = {Lp.w2, Lp.a2, Lp.g2, layer0 ? Lp.w2 : Lp.v2};
             const uint32_t rbm[4] = {S.rb_w2, S.rb_a2, S.rb_g2, layer0 ? S.rb_w2 : S.rb_v2};
@@ -631,7 +659,7 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             ENG_LDS float* sh_red = k2f + 512;              // [4][64]: sa partials
             ENG_LDS float* sh_red2 = k2f + 768;             // [4][64]: y partials
             ENG_LDS float* sh_d = k2f + 1024;               // [4][64]: LoRA dots (w, a, g, v) per channel
-            ENG_BAR();                                      // (1) LoRA intermediates and r, k, v of this head in auxbuf
+            ENG_BAR();                                      // (1) LoRA intermediates in auxbuf[0, naux); r, k, v still on their way
             if (*abort_flag) break;
             ENG_STAMP0(l, 4);
             {
@@ -647,7 +675,8 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
                 }
             }
             ENG_STAMP0(l, 16);
-            ENG_BAR();                                      // (2)
+            ENG_BAR();                                      // (2) r, k, v of this head behind them (the dots read below naux only); dots in sh_d
+            if (abort_flag[1]) break;
             const ENG_LDS f16* hr = auxbuf + naux, *hk = hr + 64, *hv = hr + 128;
             if (wave == 0) {                                // per-channel stage: lane = channel of the head
                 const float w0 = (float)h_w0, a0 = (float)h_a0, kkw = (float)h_kk, kaw = (float)h_ka;
@@ -732,7 +761,7 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
         ENG_STAMP0(l, 6);
         {
             uint32_t rb, re;
-            wave_rows(k3_rows, rb, re);
+            eng_wave_rows(k3_rows, NCW, wave, rb, re);
             const EngFin fin{WRK_ACT_NONE, sc_o, xraw0, 1.0f};
             const uint32_t gb = S.g_x1;
             ENG_LDS uint32_t* nopub = nullptr;
@@ -750,7 +779,7 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
         ENG_STAMP0(l, 14);
         {
             uint32_t rb, re;
-            wave_rows(k5_rows, rb, re);
+            eng_wave_rows(k5_rows, NCW, wave, rb, re);
             const EngFin fin{WRK_ACT_SQUARED_RELU, sc_fk, nullptr, 1.0f};
             const uint32_t gb = S.g_k;
             eng_rows<QK, R16, XD, 4>(smem + S.lds_slot5, S.rb_d, D, xs, k5_row0, rb, re, fin, pub, A.gran, eng_tag(l, 3), [&](uint32_t r) { return gb + (r >> 1); }, lane);
@@ -1084,6 +1113,7 @@ int32_t wrk_v7_engine_create(wrk_v7_model* m, wrk_v7_engine** out) {
 }
 
 bool wrk_v7_engine_has_table(const wrk_v7_engine* e) { return e && e->emb_ln; }
+int wrk_v7_engine_waves(const wrk_v7_engine* e) { return e ? e->ncw : 0; }
 
 void wrk_v7_engine_destroy(wrk_v7_engine* e) {
     if (!e) return;
@@ -1136,10 +1166,14 @@ void wrk_v7_engine_report(wrk_v7_engine* e) {
     if (hipMemcpy(h.data(), e->stamps, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
     unsigned long long t0 = ~0ull;
     for (auto v : h) if (v && v < t0) t0 = v;
-    // wave: which wave's stamp; -1 = the LAST compute wave of each workgroup to pass the point
-    auto col = [&](int wave, uint32_t k, const char* label) {
+    std::vector<char> is_head(NWG, 0);                      // the placement of wrk_v7_engine_create
+    for (uint32_t hd = 0; hd < e->S.H; ++hd) is_head[(size_t)hd * NWG / e->S.H] = 1;
+    // wave: which wave's stamp; -1 = the LAST compute wave of each workgroup to pass the point.  cls: 0 = workgroups without a head,
+    // 1 = head workgroups, -1 = all
+    auto col = [&](int wave, uint32_t k, const char* label, int cls = -1) {
         std::vector<double> v;
         for (uint32_t w = 0; w < NWG; ++w) {
+            if (cls >= 0 && is_head[w] != cls) continue;
             unsigned long long x = 0;
             if (wave >= 0) x = h[((size_t)w * NW + wave) * 24 + k];
             else for (int cw = 0; cw < e->ncw; ++cw) x = std::max(x, h[((size_t)w * NW + cw) * 24 + k]);
@@ -1157,11 +1191,15 @@ void wrk_v7_engine_report(wrk_v7_engine* e) {
     }
     const int G = e->ncw, Ld = e->ncw + 1;
     fprintf(stderr, "[WRK_TIMING] decode engine (%d compute waves), one layer of the last token; us since the layer's first stamp\n", e->ncw);
-    col(G, 0, "gather: layer input complete");
-    col(0, 1, "K1 start (input + weights in LDS), wave 0");
+    col(G, 0, "gather: layer input complete, workgroups without a head", 0);
+    col(G, 0, "gather: layer input complete, head workgroups", 1);
+    col(0, 1, "K1 start (input + weights in LDS), wave 0, no head", 0);
+    col(0, 1, "K1 start (input in LDS), wave 0, head workgroups", 1);
     col(0, 2, "K1 LN + shift done, wave 0");
-    col(0, 3, "K1 rows published, wave 0");
-    col(-1, 3, "K1 rows published, slowest wave");
+    col(0, 3, "K1 rows published, wave 0, no head", 0);
+    col(-1, 3, "K1 rows published, slowest wave, no head", 0);
+    col(-1, 3, "K1 LN + shift done, slowest wave, head workgroups", 1);
+    col(G, 4, "gather (heads): LoRA intermediates complete");
     col(G, 1, "gather (heads): K1 outputs complete");
     col(0, 4, "K2 start");
     col(-1, 16, "K2 LoRA dots done, slowest wave");

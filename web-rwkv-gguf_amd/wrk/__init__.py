@@ -1073,7 +1073,7 @@ class Runtime:
         self.frame_dtype = dtype
 
     def engine_status(self):
-        """(exists, reason) of the persistent batch-1 decode engine of this model (RWKV-7)."""
+        """(exists, note) of the persistent batch-1 decode engine of this model (RWKV-7): why there is none, or "<N> compute waves"."""
         buf = C.create_string_buffer(512)
         rc = hip.wrk_v7_model_engine_status(self.ctx.h, self.model, buf, 512)
         if rc < 0:
