@@ -429,6 +429,31 @@ int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_stat
                                   const float* frequency, const float* decay, wrk_occurrence* occ, uint32_t* out_tokens,
                                   float* last_logits_or_null, float* elapsed_ms_or_null, uint32_t mode);
 
+/* Constrained decoding ("structured output": ai00's BNF sampler, vLLM's guided_choice / guided_regex, llama.cpp's grammars, below their
+ * compilers): a deterministic automaton over token ids, supplied by the caller, says which tokens a row may draw as a function of what
+ * it drew before.  Alphabet compression: token_class[num_vocab] (u16) maps every token to one of num_classes classes, and
+ * transitions[num_states][num_classes] (u16) holds the next state, or WRK_GRAMMAR_REJECT when the class is not allowed in that state;
+ * with num_classes == num_vocab and the identity map this is the dense table.  1 <= num_states <= 65535, 1 <= num_classes <=
+ * WRK_MAX_TOKEN_CLASSES (one state's row is at most 16 KB: it is staged in LDS), num_vocab <= 2^20 (the sampler's limit, beyond it
+ * WRK_E_UNSUPPORTED).  WRK_E_ARG before anything is uploaded: NULL arrays, a class >= num_classes, a next state that is neither
+ * < num_states nor WRK_GRAMMAR_REJECT, and a state in which no token is allowed (no class that at least one token maps to has a next
+ * state) -- so a row masked by a grammar alone is never empty.  A grammar that is "finished" says so itself: its final state allows
+ * only the caller's end token and loops on it.  Both arrays are copied: the caller's may go after the call. */
+#define WRK_GRAMMAR_REJECT 0xFFFFu
+#define WRK_MAX_TOKEN_CLASSES 8192
+typedef struct wrk_grammar wrk_grammar;
+int32_t wrk_grammar_create(wrk_ctx* ctx, uint32_t num_vocab, uint32_t num_states, uint32_t num_classes, const uint16_t* token_class,
+                           const uint16_t* transitions, wrk_grammar** out);
+int32_t wrk_grammar_destroy(wrk_grammar* grammar);
+/* masks f32 logits [num_rows][row_stride] (first num_vocab used) in place: row r keeps logits[r][v], bits unchanged (NaN payloads
+ * included), if token v is allowed in states[r], and gets -inf otherwise.  states: host u32 [num_rows], each < num_states (else
+ * WRK_E_ARG).  Blocking.  In a host-side loop it goes between wrk_penalize_logits and wrk_sample_logits. */
+int32_t wrk_constrain_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                             const wrk_grammar* grammar, const uint32_t* states);
+/* states[r] <- transitions[states[r]][token_class[tokens[r]]] on the device; a rejected token leaves states[r] as it was.  states: host
+ * u32 [num_rows], in/out; tokens: host u32 [num_rows], each < num_vocab.  Blocking. */
+int32_t wrk_grammar_advance(wrk_ctx* ctx, const wrk_grammar* grammar, uint32_t* states, const uint32_t* tokens, uint32_t num_rows);
+
 /* Stop tokens in the decode loops.  Sequence b has the stop set stop_tokens[stop_offsets[b] .. stop_offsets[b + 1]) (CSR, num_batch + 1
  * offsets, at most WRK_MAX_STOP_TOKENS ids each, every id < num_vocab).  Step i feeds x_i (x_0 = first_tokens[b]) and draws y_i; a
  * sequence that has not ended and whose y_i is in its stop set ends at step i: out_lengths[b] = i + 1 (the stop token is part of the
@@ -468,7 +493,22 @@ int32_t wrk_v7_generate_penalized(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_stat
  * after the call mu[b] has seen exactly out_lengths[b] draws; a session carries mu from call to call through this array.  Tokens and
  * mu do not depend on the number of lanes.  The parameters are device data: one cached step program per family serves any values;
  * the two families replay step programs of their own, and a call with all four fields NULL runs exactly the programs it ran before.
- * The four fields sit between the log-prob fields and the filter fields, which stay the last two. */
+ * The four fields sit between the log-prob fields and the filter fields, which stay the last two.
+ * Constrained decoding.  `grammar` (NULL: off) masks the row every pick is made on as wrk_constrain_logits does with the sequence's
+ * automaton state, and every draw that counts moves that state as wrk_grammar_advance does -- inside the step program.  Order within a
+ * step: penalties, then the mask (in place on the penalised row, else into a copy of the head output), then the call's pick -- bit for
+ * bit the pick of the same call on the masked row -- then log-probs, which stay on the raw head output (a disallowed token may appear
+ * among the alternatives), then the tail.  With no sampler arrays the pick is the arg-max of the masked row: this entry point, with or
+ * without stop sets, is constrained greedy.  The automaton sees exactly the draws an occurrence row counts and a Mirostat mu sees: every
+ * step up to and including the one that draws b's stop token, none after it.  grammar_state (host u32 [num_batch], in/out, may be NULL):
+ * on entry the state sequence b starts in (NULL: 0), on return the state after the draws that counted, out_lengths[b] of them; a session
+ * carries it from call to call through this array.  WRK_E_ARG before any launch: grammar_state without grammar, a grammar of another
+ * context or another num_vocab, a start state >= num_states.  The tables and the states are device data: one cached step program serves
+ * any grammar and any start states; constrained calls replay step programs of their own, a call without a grammar exactly the programs
+ * it ran before.  Tokens and final states do not depend on the number of lanes.  If the bans of `occ` and the automaton together leave
+ * a row with no finite logit, the picked id is unspecified but < num_vocab (as for a NaN row); the automaton then sees a rejected token
+ * and keeps its state, and nothing faults: to combine bans with a grammar, put them in the grammar.  The two fields sit between
+ * the log-prob fields and the Mirostat fields: the six fields behind them, the filter fields last, stay where they were. */
 #define WRK_MAX_STOP_TOKENS 16
 typedef struct wrk_generate_options {
     const float *temperature, *top_p;
@@ -481,6 +521,8 @@ typedef struct wrk_generate_options {
     float *out_logprob;
     uint32_t *out_top_ids;
     float *out_top_logprobs;
+    const wrk_grammar *grammar;
+    uint32_t *grammar_state;
     const float *mirostat_tau, *mirostat_eta;
     float *mirostat_mu;
     const float *typical_p;
@@ -534,7 +576,13 @@ int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* st
  * previous request left -- and only its reply draws move it: the draws of the steps that feed prompt tokens are discarded for mu as
  * they are for the occurrence row.  On return entry r holds the mu after the request's reply draws for reasons 1, 2 and 3, and is
  * untouched for reason 0.  A reply and its final mu do not depend on the slot or the step the request was scheduled at.  mu is not part
- * of a state-pool entry: a session carries it through this array. */
+ * of a state-pool entry: a session carries it through this array.
+ * grammar / grammar_state (host u32 [num_requests], in/out, may be NULL), as in wrk_generate_options: one automaton for the call;
+ * request r starts in grammar_state[r] (NULL: 0) when it is dispatched, at step 0 or at a refill on the device -- never in what its
+ * slot's previous request left -- and only its reply draws move the state: the steps that feed prompt tokens do not.  On return entry
+ * r holds the state after the request's reply draws for reasons 1, 2 and 3 (3: the state reached so far) and is untouched for reason
+ * 0.  Requests that need different grammars use disjoint state sets of one automaton.  The state is not part of a state-pool entry: a
+ * session carries it through this array. */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
     const uint32_t *prompt_tokens, *prompt_offsets, *max_new;
@@ -549,6 +597,8 @@ typedef struct wrk_queue_options {
     float *out_logprob;
     uint32_t *out_top_ids;
     float *out_top_logprobs;
+    const wrk_grammar *grammar;
+    uint32_t *grammar_state;
     const float *mirostat_tau, *mirostat_eta;
     float *mirostat_mu;
     const float *typical_p;

@@ -21,8 +21,14 @@ A seventh pair of legs (--mirostat TAU,ETA and / or --typical P): the decode loo
  against the plain sampler loop of the same run -- all through the options entry point without stop sets, so the step
 programs differ by the sampler launch alone -- alternating, with the run-to-run spread of each.  Every call starts from the same state.
 
+An eighth leg (--grammar): the decode loop constrained by a two-state automaton that allows about half of the vocabulary in either state
+ against the same loop without a grammar -- both through the options entry point without stop sets, so the step programs
+differ by the mask launch and the advance launch alone -- for the greedy and the plain-sampler pick, alternating, with the run-to-run
+spread of each.  Every call starts from the same state; the unconstrained tokens are recorded (as a hash) so that the same leg on another
+build can be compared with them.
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
-                                 [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9]
+                                 [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9] [--grammar]
 
 Prints one JSON object.
 """
@@ -195,6 +201,57 @@ def alt_leg(rt, first, args):
     return res
 
 
+def half_vocabulary_automaton(V):
+    """Two states over four token classes (id mod 4): state 0 allows classes 0 and 1, state 1 classes 1 and 2; class 1 changes the state."""
+    token_class = np.arange(V, dtype=np.uint16) % 4
+    rej = 0xFFFF
+    return token_class, np.array([[0, 1, rej, rej], [rej, 0, 1, rej]], np.uint16)
+
+
+def grammar_leg(rt, ctx, first, V, args):
+    """Per pick (greedy, sampled): medians of the per-step time of generate_stop without stop sets, with the automaton against without,
+    alternating in one process; every call starts from the same state."""
+    import hashlib
+    import wrk
+    B = len(first)
+    cls, trans = half_vocabulary_automaton(V)
+    g = wrk.Grammar(ctx, V, cls, trans)
+    start = [rt.state_read(b) for b in range(B)]
+
+    def run(pick, **kw):
+        for b in range(B):
+            rt.state_write(start[b], b)
+        tok, _ = rt.generate_stop(first, args.steps, [], poll_steps=POLL_OFF, **pick, **kw)
+        return tok, rt.last_stop_ms / args.steps
+    res = {}
+    for name, pick in (("greedy", {}), ("sample", dict(temperature=args.temperature, top_p=args.top_p))):
+        want, _ = run(pick)
+        con, _ = run(pick, grammar=g, grammar_state=0)                     # capture and warm up
+        for b in range(B):
+            g.walk(0, con[:, b])                                           # raises at a disallowed token
+        accepted = True
+        base, with_, same = [], [], True
+        for _ in range(args.reps):
+            tok, ms = run(pick)
+            same &= bool(np.array_equal(tok, want))
+            base.append(ms)
+            tok, ms = run(pick, grammar=g, grammar_state=0)
+            same &= bool(np.array_equal(tok, con))
+            with_.append(ms)
+        bm, wm = float(np.median(base)), float(np.median(with_))
+        res[name] = {"same_tokens_every_rep": same, "constrained_tokens_accepted": accepted,
+                     "constrained_differs_from_plain": bool(not np.array_equal(want, con)),
+                     "without_tokens_sha1": hashlib.sha1(np.ascontiguousarray(want).tobytes()).hexdigest(),
+                     "without_ms_per_step": round(bm, 5), "without_spread_us": round((max(base) - min(base)) * 1e3, 2),
+                     "without_ms_all": [round(x, 5) for x in base],
+                     "with_ms_per_step": round(wm, 5), "with_spread_us": round((max(with_) - min(with_)) * 1e3, 2),
+                     "with_ms_all": [round(x, 5) for x in with_], "with_minus_without_us": round((wm - bm) * 1e3, 2)}
+    for b in range(B):
+        rt.state_write(start[b], b)
+    g.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -212,6 +269,7 @@ def main():
     ap.add_argument("--logprobs", default=None, help="comma-separated numbers of alternatives, e.g. 0,5,20")
     ap.add_argument("--mirostat", default=None, help="TAU,ETA, e.g. 5,0.1")
     ap.add_argument("--typical", type=float, default=None, help="typical_p, e.g. 0.9")
+    ap.add_argument("--grammar", action="store_true", help="the constrained loop against the same loop without a grammar")
     args = ap.parse_args()
     import wrk
 
@@ -295,6 +353,10 @@ def main():
             out["batches"][-1]["logprobs"] = logprob_leg(rt, first, args)
         if args.mirostat or args.typical is not None:
             out["batches"][-1]["mirostat_typical"] = alt_leg(rt, first, args)
+        if args.grammar:
+            out["grammar_note"] = ("two states, four token classes (id mod 4), two classes allowed per state; a constrained step adds two "
+                                   "launches to the step program: constrain_rows before the pick and grammar_advance in the tail")
+            out["batches"][-1]["grammar"] = grammar_leg(rt, ctx, first, V, args)
     if occ is not None:
         occ.close()
     rt.close()

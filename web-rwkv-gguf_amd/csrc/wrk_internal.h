@@ -254,6 +254,17 @@ void penalize_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_str
                    uint32_t dst_stride);
 void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, uint32_t ntok, const RowGate& gate);
 
+// wrk_grammar.hip: constrained decoding.  A grammar is a DFA over token ids with alphabet compression: token_class u16 [v]
+// and transitions u16 [states][num_classes], WRK_GRAMMAR_REJECT for a class that is not allowed.  GrammarParam is device data, in a
+// decode loop a per-frame block written before every call: the two tables, num_classes and the per-row state words, so a captured step
+// never holds a table pointer of its own.  constrain_rows: dst row r = src row r with the bits of -inf wherever the token is not allowed
+// in states[r], the source bits elsewhere (src == dst allowed).  grammar_advance: states[r] <- the next state on tokens[r]; a rejected
+// token, and a row whose draw does not count (gate), leave it alone
+struct GrammarParam { const uint16_t* token_class; const uint16_t* transitions; uint32_t num_classes, pad; uint32_t* states; };
+void constrain_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_stride, uint32_t n, const GrammarParam* par, float* dst,
+                    uint32_t dst_stride);
+void grammar_advance(hipStream_t s, uint32_t v, uint32_t n, const GrammarParam* par, const uint32_t* tokens, const RowGate& gate);
+
 // wrk_stop.hip: stop tokens in the decode loops.  One StopParam per sequence in a per-frame device buffer written
 // before every call: the stop ids are data, one captured program serves any stop sets.  done / length / end_token are the device's:
 // the step that draws a stop id sets them (length = step + 1: the stop token is part of the output)
@@ -300,6 +311,10 @@ struct QueueBufs {
     // its final value once it has ended (advance_queue copies it into and out of the slot's row); nullptr unless Mirostat
     SampleAlt* alt_par = nullptr;
     float* alt_mu = nullptr;
+    // constrained queues: the frame's automaton state words [B], and gram_req [R]: request r's state -- its start value until it is
+    // dispatched, its final value once it has ended, exactly as alt_mu; both nullptr without a grammar
+    uint32_t* gram_state = nullptr;
+    uint32_t* gram_req = nullptr;
 };
 // takes advance_tokens' place in a queue program: history <- drawn; per slot the next prompt token or the draw, stop / max_new check,
 // next requests to the slots that ended (ascending slot order), their parameters into the slot's rows, started[b], the log,
@@ -436,3 +451,16 @@ struct wrk_occurrence {
 // vocabulary, slots out of range, a non-finite presence / frequency, a decay outside [0, 1]); decay NULL: 1
 int32_t wrk_penalty_pack(wrk_ctx* ctx, const wrk_occurrence* occ, uint32_t first, uint32_t n, uint32_t V, const float* presence,
                          const float* frequency, const float* decay, std::vector<wrk::PenaltyParam>& out);
+
+// include/wrk_hip.h wrk_grammar: one allocation holding token_class u16 [num_vocab] and transitions u16 [num_states][num_classes]
+struct wrk_grammar {
+    wrk_ctx* ctx = nullptr;
+    uint32_t num_vocab = 0, num_states = 0, num_classes = 0;
+    void* mem = nullptr;
+    uint16_t* token_class = nullptr;
+    uint16_t* transitions = nullptr;
+    wrk::GrammarParam param(uint32_t* states) const;
+};
+// validated start states of n rows (WRK_E_ARG on a NULL grammar, a grammar of another context or another vocabulary, a state >=
+// num_states); state NULL: all 0
+int32_t wrk_grammar_pack(wrk_ctx* ctx, const wrk_grammar* g, const uint32_t* state, uint32_t n, uint32_t V, std::vector<uint32_t>& out);

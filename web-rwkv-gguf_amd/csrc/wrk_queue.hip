@@ -56,6 +56,7 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
             if (reason) {
                 Q.log[s.req].reason = reason; ended = 1;
                 if (Q.alt_mu) Q.alt_mu[s.req] = Q.alt_par[i].mu;     // the sampler of this step has counted the last draw
+                if (Q.gram_req) Q.gram_req[s.req] = Q.gram_state[i];    // and grammar_advance, in front of this launch, has moved on it
             }
         }                                       // idle: tokens[i] stays, a valid id keeps flowing through the embedding gather
     }
@@ -86,6 +87,7 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
                 // a refilled slot starts from its own request's mu, not from its predecessor's (a request is dispatched once: its entry
                 // still holds its start value)
                 if (Q.alt_par) Q.alt_par[i] = SampleAlt{q->tau, q->eta, Q.alt_mu ? Q.alt_mu[r] : 0.0f, q->typical_p};
+                if (Q.gram_req) Q.gram_state[i] = Q.gram_req[r];        // the same for its automaton state
                 if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
                 Q.log[r] = QueueLog{0u, 3u, i, step + 1};
                 started = 1;

@@ -91,6 +91,9 @@ struct wrk_step_kind {
     bool penalized = false;     // the pick is made on pen_o = head_o penalised with the occurrence rows of pen_par, which then count the draw (wrk_penalty.hip)
     Tail tail = PLAIN;
     bool logprobs = false;      // between the pick and the tail, the log-prob launches (wrk_logprob.hip) on head_o and the picked tokens, on lp_par
+    // the pick is made on the row masked by the automaton of gram_par (wrk_grammar.hip): pen_o masked in place when penalised, else con_o =
+    // the masked head_o; the tail then advances the automaton states where it updates the occurrence rows, under the same gate
+    bool constrained = false;
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
     bool mirostat() const { return pick == MIROSTAT; }
@@ -98,10 +101,11 @@ struct wrk_step_kind {
     bool queue() const { return tail == QUEUE || tail == QUEUE_POOL; }
     bool pool() const { return tail == QUEUE_POOL; }
     // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25 and, its third bit, 30 (the first three picks keep the
-    // keys they had with two bits), penalised 26, tail 27-28, log-probs 29 -- above every flag of an infer job and of a runner's own
-    // (wrk_frame_common::key_bits, all below bit 24, ORed into the same word)
+    // keys they had with two bits), penalised 26, tail 27-28, log-probs 29, constrained 31 (the word is full) -- above every flag of an
+    // infer job and of a runner's own (wrk_frame_common::key_bits, all below bit 24, ORed into the same word)
     uint32_t key() const {
-        return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29;
+        return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29 |
+               (uint32_t)constrained << 31;
     }
 };
 
@@ -146,6 +150,15 @@ struct wrk_frame_common {
     wrk::PenaltyParam* pen_par = nullptr;      // generate_penalized: per-sequence occurrence rows and penalties, written before every call
     float* pen_o = nullptr;                     // (the step programs read the table's pointers from here); pen_o: penalised logits [B][V]
     uint32_t pen_cap = 0;
+    // constrained decoding (wrk_grammar.hip), allocated by the first call with a grammar only and written before every call.
+    // gram_par: the parameter block (the grammar's tables and gram_state: one program serves any grammar and any start states);
+    // gram_state [gram_cap]: the sequences' automaton states, read back after the call; con_o [gram_cap][V]: the masked head output of a
+    // pick without penalties; gram_req [gram_req_cap]: a queue's per-request states (wrk::QueueBufs::gram_req)
+    wrk::GrammarParam* gram_par = nullptr;
+    uint32_t* gram_state = nullptr;
+    float* con_o = nullptr;
+    uint32_t* gram_req = nullptr;
+    uint32_t gram_cap = 0, gram_req_cap = 0, gram_vocab_cap = 0;
     wrk_score_scratch score;                    // wrk_v*_score: targets / logprob / rank / slice partials of the header rows
     // generate_stop (wrk_stop.hip), allocated by the first stop call only.  stop_par: per-sequence stop sets and end marks,
     // written before every call; stop_flags: just_ended [cap], then the frame's live count, then lengths [cap]; stop_snap_state
@@ -205,7 +218,7 @@ struct wrk_frame_common {
     // the ensure_* reallocate after a stream sync and drop the captured programs, which hold the old pointers; never inside a capture
     void drop_graphs();
     // the buffers an ensure_* reallocates together; bufs(g): their pointers, the one list regrow and release_common go through
-    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, LOGPROB, ALT, NUM_GROUPS };
+    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, LOGPROB, ALT, GRAMMAR, NUM_GROUPS };
     std::vector<void**> bufs(Group g);
     // sync, drop the programs (`drop`), free the buffers and allocate them again; after a failure all of them are freed
     // bytes: one size per buffer of bufs(g), in its order.  The caller sets its caps after WRK_OK: an error leaves them as they were
@@ -215,6 +228,7 @@ struct wrk_frame_common {
     int32_t ensure_filter_params(uint32_t n);
     int32_t ensure_alt_params(uint32_t n, uint32_t requests);
     int32_t ensure_penalty(uint32_t n, uint32_t num_vocab);
+    int32_t ensure_grammar(uint32_t n, uint32_t num_vocab, uint32_t requests = 0);      // requests: a queue's (0: none)
     int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
     int32_t ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens);
     int32_t ensure_queue_states(uint32_t slots, uint32_t requests);
@@ -236,18 +250,19 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
 // ------------------------------------------------------------------ the decode loops (generate_greedy ... generate_queue)
 // the ABI's pick arrays, of wrk_generate_options / wrk_queue_options (wrk_pick_of) or of an entry point's own arguments, validated in
 // one place (WRK_E_ARG): all three sampler arrays or none (the arg-max); penalty arrays only with a table; a table, a filter, Mirostat
-// or typical only with the sampler arrays; one family of filter / Mirostat / typical per call.  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
+// or typical only with the sampler arrays; one family of filter / Mirostat / typical per call; grammar_state only with a grammar (which any pick may have).  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
 struct wrk_pick_args {
     const float *temperature = nullptr, *top_p = nullptr; const uint32_t* seed = nullptr;
     const float *presence = nullptr, *frequency = nullptr, *decay = nullptr; wrk_occurrence* occ = nullptr;
     const uint32_t* top_k = nullptr; const float* min_p = nullptr;      // either set: a filtered pick
     const float *mirostat_tau = nullptr, *mirostat_eta = nullptr; float* mirostat_mu = nullptr;     // tau set: a Mirostat pick; mu: in / out
     const float* typical_p = nullptr;                                   // set: a typical pick
+    const wrk_grammar* grammar = nullptr; uint32_t* grammar_state = nullptr;    // grammar set: a constrained pick; grammar_state: in / out
     enum Need { ANY, SAMPLER, TABLE } need = ANY;
 };
 template <class Options> wrk_pick_args wrk_pick_of(const Options& o) {
     return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p,
-            o.mirostat_tau, o.mirostat_eta, o.mirostat_mu, o.typical_p};
+            o.mirostat_tau, o.mirostat_eta, o.mirostat_mu, o.typical_p, o.grammar, o.grammar_state};
 }
 // the log-prob outputs of a call (wrk_generate_options / wrk_queue_options); logprob NULL: off
 struct wrk_logprob_call {
@@ -255,10 +270,11 @@ struct wrk_logprob_call {
     bool on() const { return logprob != nullptr; }
 };
 bool wrk_no_graph();        // WRK_NO_GRAPH=1: the decode loops enqueue every step instead of replaying a program
-// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the penalise launch (penalised), the arg-max
-// or sampler launch on the frame's parameters at step *counter -- neither with `argmax_done`: the head launch has left the arg-max in
-// io().argmax (RWKV-7's fused greedy head) -- with kind.logprobs the log-prob launches on head_o (never pen_o) and io().argmax into row
-// *counter of the frame's log-prob buffers, then the tail: the occurrence update that belongs to it (penalised), its advance of
+// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the penalise launch (penalised), the mask
+// launch (constrained), the arg-max or sampler launch on the resulting row and the frame's parameters at step *counter -- neither with
+// `argmax_done`: the head launch has left the arg-max in io().argmax (RWKV-7's fused greedy head, never in a constrained step) -- with
+// kind.logprobs the log-prob launches on head_o (never pen_o) and io().argmax into row
+// *counter of the frame's log-prob buffers, then the tail: the occurrence update (penalised) and the automaton advance (constrained) that belong to it, its advance of
 // tokens / history / counter, and stop_snapshot / queue_reset / queue_turnover
 int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, bool argmax_done);
 

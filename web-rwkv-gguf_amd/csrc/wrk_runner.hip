@@ -81,6 +81,7 @@ std::vector<void**> wrk_frame_common::bufs(Group g) {
         case FILTER: return {(void**)&filter_par};
         case ALT: return {(void**)&alt_par, (void**)&alt_mu};
         case PENALTY: return {(void**)&pen_par, (void**)&pen_o};
+        case GRAMMAR: return {(void**)&gram_par, (void**)&gram_state, (void**)&con_o, (void**)&gram_req};
         case STOP: return {(void**)&stop_par, (void**)&stop_flags, (void**)&stop_snap_state, (void**)&stop_snap_logits};
         case QUEUE: return {(void**)&queue_slots, (void**)&queue_started, (void**)&queue_ctl, (void**)&queue_reqs, (void**)&queue_log, (void**)&queue_pool};
         case QUEUE_STATES: return {(void**)&queue_state_ctl, (void**)&queue_turn, (void**)&queue_entries};
@@ -143,6 +144,19 @@ int32_t wrk_frame_common::ensure_penalty(uint32_t n, uint32_t num_vocab) {
     if (n <= pen_cap && pen_par && pen_o) return WRK_OK;
     const int32_t rc = regrow(PENALTY, {(size_t)n * sizeof(wrk::PenaltyParam), (size_t)n * num_vocab * 4}, true);
     if (rc == WRK_OK) pen_cap = n;
+    return rc;
+}
+
+int32_t wrk_frame_common::ensure_grammar(uint32_t n, uint32_t num_vocab, uint32_t requests) {
+    if (requests < 1) requests = 1;
+    if (gram_par && n <= gram_cap && requests <= gram_req_cap && num_vocab == gram_vocab_cap) return WRK_OK;
+    if (n < gram_cap) n = gram_cap;
+    if (requests < gram_req_cap) requests = gram_req_cap;
+    // constrained programs hold the old pointers; before the first allocation none exists
+    const int32_t rc = regrow(GRAMMAR, {sizeof(wrk::GrammarParam), (size_t)n * 4, (size_t)n * num_vocab * 4, (size_t)requests * 4}, gram_par != nullptr);
+    gram_cap = rc == WRK_OK ? n : 0;
+    gram_req_cap = rc == WRK_OK ? requests : 0;
+    gram_vocab_cap = rc == WRK_OK ? num_vocab : 0;
     return rc;
 }
 
@@ -212,6 +226,7 @@ void wrk_frame_common::release_common() {
         for (void** p : bufs((Group)g)) { if (*p) hipFree(*p); *p = nullptr; }
     history_cap = 0; stop_slot_cap = 0; queue_pool_cap = 0; lp_rows_cap = 0; lp_batch_cap = 0;
     alt_par_cap = alt_mu_cap = 0;
+    gram_cap = gram_req_cap = gram_vocab_cap = 0;
     sample_par_cap = filter_par_cap = pen_cap = stop_cap = stop_vocab_cap = queue_slot_cap = queue_req_cap = queue_turn_cap = queue_entry_cap = 0;
     score.release();
     if (live_host) hipHostFree(live_host);
@@ -275,6 +290,9 @@ struct wrk_pick_params {    // validated rows; empty: the arg-max / without pena
     std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
     std::vector<wrk::SampleAlt> alt;        // Mirostat / typical rows
     uint32_t alt_requests = 0;              // a queue: its requests (the size of the frame's per-request mu array)
+    const wrk_grammar* grammar = nullptr;   // a constrained pick: the automaton and the state every row starts in
+    std::vector<uint32_t> gram_state;
+    uint32_t gram_requests = 0;             // a queue: its requests (the size of the frame's per-request state array)
 };
 
 // The one validation of the pick arrays (wrk_pick_args).  Sets kind.pick / kind.penalized and packs `n` rows; penalty row r names slot r
@@ -294,6 +312,13 @@ static int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, u
     kind.pick = given == 0 ? wrk_step_kind::GREEDY : filt ? wrk_step_kind::FILTERED : miro ? wrk_step_kind::MIROSTAT
                            : typ ? wrk_step_kind::TYPICAL : wrk_step_kind::SAMPLED;
     kind.penalized = a.occ != nullptr;
+    WRK_ARG(ctx, a.grammar || !a.grammar_state, "grammar_state without grammar");
+    kind.constrained = a.grammar != nullptr;
+    if (kind.constrained) {
+        const int32_t grc = wrk_grammar_pack(ctx, a.grammar, a.grammar_state, n, V, out.gram_state);
+        if (grc != WRK_OK) return grc;
+        out.grammar = a.grammar;
+    }
     if (!kind.sampled()) return WRK_OK;
     WRK_ARG(ctx, n >= 1, "a sampled pick of no rows");
     int32_t rc = wrk_sample_pack(ctx, a.temperature, a.top_p, a.seed, n, out.par);
@@ -390,6 +415,7 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     if (rc == WRK_OK && filt) rc = f.ensure_filter_params(B);
     if (rc == WRK_OK && alt) rc = f.ensure_alt_params(B, rows.alt_requests);
     if (rc == WRK_OK && pen) rc = f.ensure_penalty(B, f.facts().num_vocab);
+    if (rc == WRK_OK && rows.grammar) rc = f.ensure_grammar(B, f.facts().num_vocab, rows.gram_requests);
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
@@ -400,6 +426,11 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     if (rc == WRK_OK && filt) rc = wrk_buf_write_raw(ctx, f.filter_par, filt, (size_t)B * sizeof(wrk::SampleFilter));
     if (rc == WRK_OK && alt) rc = wrk_buf_write_raw(ctx, f.alt_par, alt, (size_t)B * sizeof(wrk::SampleAlt));
     if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, f.pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
+    if (rc == WRK_OK && rows.grammar) {
+        const wrk::GrammarParam gp = rows.grammar->param(f.gram_state);
+        rc = wrk_buf_write_raw(ctx, f.gram_par, &gp, sizeof gp);
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.gram_state, rows.gram_state.data() + b0, (size_t)B * 4);
+    }
     if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipMemsetAsync(io.counter, 0, 4, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -445,6 +476,8 @@ struct wrk_queue_pack {
     wrk_logprob_call lp;        // the options' log-prob arrays and num_top
     std::vector<float> mu;      // Mirostat / typical: [R] the mu every request starts from
     float* mu_out = nullptr;    // Mirostat: the options' mirostat_mu, or nullptr
+    std::vector<uint32_t> gram; // constrained: [R] the automaton state every request starts in
+    uint32_t* gram_out = nullptr;   // the options' grammar_state, or nullptr
 };
 
 static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
@@ -508,6 +541,14 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
         for (uint32_t r = 0; r < R; ++r) pk.mu[r] = req.alt[r].mu;
         pk.mu_out = kind.mirostat() ? opt->mirostat_mu : nullptr;
     }
+    if (kind.constrained) {        // the slots start in their requests' states; an idle slot in state 0, which every grammar has
+        pk.gram = req.gram_state;
+        pk.gram_out = opt->grammar_state;
+        pk.rows.grammar = req.grammar;
+        pk.rows.gram_requests = R;
+        pk.rows.gram_state.assign(B, 0u);
+        for (uint32_t b = 0; b < B && b < R; ++b) pk.rows.gram_state[b] = pk.gram[b];
+    }
     for (uint32_t b = 0; b < B; ++b) {
         const uint32_t r = b < R ? b : 0;       // idle slots: any valid row
         const wrk::QueueReq& q = pk.reqs[r];
@@ -564,7 +605,8 @@ static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, co
 static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
     return wrk::QueueBufs{f.queue_slots, f.queue_reqs, f.queue_pool, f.queue_log, f.queue_ctl, f.queue_started,
                           kind.sampled() ? f.sample_par : nullptr, kind.penalized ? f.pen_par : nullptr, kind.filtered() ? f.filter_par : nullptr,
-                          kind.alt() ? f.alt_par : nullptr, kind.mirostat() ? f.alt_mu : nullptr};
+                          kind.alt() ? f.alt_par : nullptr, kind.mirostat() ? f.alt_mu : nullptr,
+                          kind.constrained ? f.gram_state : nullptr, kind.constrained ? f.gram_req : nullptr};
 }
 
 static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f) {
@@ -603,6 +645,10 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     if (rc == WRK_OK && pk.kind.mirostat()) {
         if (!f.alt_mu || pk.R > f.alt_mu_cap) return wrk_fail(ctx, WRK_E_ARG, "Mirostat rows are not prepared");
         rc = wrk_buf_write_raw(ctx, f.alt_mu, pk.mu.data(), (size_t)pk.R * 4);
+    }
+    if (rc == WRK_OK && pk.kind.constrained) {
+        if (!f.gram_req || pk.R > f.gram_req_cap) return wrk_fail(ctx, WRK_E_ARG, "grammar states are not prepared");
+        rc = wrk_buf_write_raw(ctx, f.gram_req, pk.gram.data(), (size_t)pk.R * 4);
     }
     if (rc == WRK_OK && pk.kind.pool()) {
         // the turnover list of "step -1": the slots that start at step 0, nothing to save
@@ -647,6 +693,23 @@ static int32_t enqueue_occurrence_update(wrk_frame_common& f, uint32_t B, wrk_st
     return WRK_OK;
 }
 
+// the automaton states move on the drawn tokens in io.argmax (constrained kinds), under the step's gate
+static int32_t enqueue_grammar_advance(wrk_frame_common& f, uint32_t B, wrk_step_kind kind) {
+    if (!kind.constrained) return WRK_OK;
+    if (!f.gram_par || B > f.gram_cap) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
+    wrk::RowGate gate;
+    const int32_t rc = draw_gate(f, B, kind, gate);
+    if (rc != WRK_OK) return rc;
+    wrk::grammar_advance(f.ctx->op_stream(), f.facts().num_vocab, B, f.gram_par, f.io().argmax, gate);
+    return WRK_OK;
+}
+
+// what a tail does with the drawn tokens before it advances: the occurrence update, then the automaton advance
+static int32_t enqueue_draw_updates(wrk_frame_common& f, uint32_t B, wrk_step_kind kind) {
+    const int32_t rc = enqueue_occurrence_update(f, B, kind);
+    return rc == WRK_OK ? enqueue_grammar_advance(f, B, kind) : rc;
+}
+
 // tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
 // token (penalised), advance_queue, queue_reset of slots [b0, b0 + B) of `st`; with a pool advance_queue_pool and queue_turnover,
 // launch for launch
@@ -657,7 +720,7 @@ static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind
     if (!f.queue_ctl || B > f.queue_slot_cap || b0 != 0 || B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
     if (kind.pool() && (!f.queue_state_ctl || B > f.queue_turn_cap || ((size_t)(st->head_size + 2) * st->num_emb) % 4 != 0))
         return wrk_fail(f.ctx, WRK_E_ARG, "state pool buffers are not prepared");
-    const int32_t rc = enqueue_occurrence_update(f, B, kind);
+    const int32_t rc = enqueue_draw_updates(f, B, kind);
     if (rc != WRK_OK) return rc;
     const wrk::QueueBufs bufs = queue_bufs(f, kind);
     if (kind.pool()) {
@@ -693,6 +756,12 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         WRK_HIP(ctx, hipMemcpyAsync(mu_req.data(), f.alt_mu, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
         WRK_HIP(ctx, hipMemcpyAsync(mu_slot.data(), f.alt_par, (size_t)B * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost, ctx->stream));
     }
+    // constrained: the same two places hold a request's automaton state
+    std::vector<uint32_t> gram_req(pk.gram_out ? pk.R : 0), gram_slot(pk.gram_out ? B : 0);
+    if (pk.gram_out) {
+        WRK_HIP(ctx, hipMemcpyAsync(gram_req.data(), f.gram_req, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(gram_slot.data(), f.gram_state, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     size_t o = 0;
     for (uint32_t r = 0; r < pk.R; ++r) {
@@ -705,6 +774,7 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
             return wrk_fail(ctx, WRK_E_HIP, "request %u: inconsistent queue log (length %u slot %u start %u)", r, g.length, g.slot, g.start_step);
         out->lengths[r] = g.length; out->reasons[r] = g.reason; out->slots[r] = g.slot; out->start_steps[r] = g.start_step;
         if (pk.mu_out && g.reason != 0) pk.mu_out[r] = g.reason == 3 ? mu_slot[g.slot].mu : mu_req[r];
+        if (pk.gram_out && g.reason != 0) pk.gram_out[r] = g.reason == 3 ? gram_slot[g.slot] : gram_req[r];
         // the step that gave the request reason 1 or 2 also wrote its state to its entry (queue_turnover)
         if (pk.saved_out) pk.saved_out[r] = pk.save[r] != wrk::QUEUE_NO_ENTRY && (g.reason == 1 || g.reason == 2);
         for (uint32_t j = 0; j < g.length; ++j) {
@@ -736,7 +806,7 @@ static int32_t enqueue_stop_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind 
     hipStream_t q = f.ctx->op_stream();
     const wrk::FrameIo& io = f.io();
     if (!f.stop_par || B > f.stop_cap || b0 + B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
-    const int32_t rc = enqueue_occurrence_update(f, B, kind);
+    const int32_t rc = enqueue_draw_updates(f, B, kind);
     if (rc != WRK_OK) return rc;
     wrk::advance_stop(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(), B);
     wrk::stop_snapshot(q, stop_geom(f, st, b0), B, f.ctx->num_cu);
@@ -752,9 +822,16 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
         wrk::penalize_rows(q, io.head_o, V, V, B, f.pen_par, f.pen_o, V);
         logits = f.pen_o;
     }
+    // the mask: in place on the penalised row, else from head_o (which log-probs, last_logits and the stop snapshot keep raw) into con_o
+    if (kind.constrained) {
+        if (!f.gram_par || B > f.gram_cap || V != f.gram_vocab_cap || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
+        float* masked = kind.penalized ? f.pen_o : f.con_o;
+        wrk::constrain_rows(q, logits, V, V, B, f.gram_par, masked, V);
+        logits = masked;
+    }
     // the sampler only reads the counter: rows run in different workgroups, so the tail's advance moves it after all of them
     if (!kind.sampled()) {
-        if (!argmax_done) wrk::argmax_rows(q, io.head_o, V, V, B, io.argmax);
+        if (!argmax_done) wrk::argmax_rows(q, logits, V, V, B, io.argmax);
     } else if (kind.filtered() && (!f.filter_par || B > f.filter_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
     else if (kind.alt() && (!f.alt_par || B > f.alt_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "Mirostat / typical rows are not prepared");
     else {
@@ -777,7 +854,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     }
     if (kind.queue()) return enqueue_queue_tail(f, B, kind, st, b0);
     if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, B, kind, st, b0);
-    const int32_t urc = enqueue_occurrence_update(f, B, kind);
+    const int32_t urc = enqueue_draw_updates(f, B, kind);
     if (urc != WRK_OK) return urc;
     wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);
     return WRK_OK;
@@ -987,6 +1064,9 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
             for (uint32_t b = ln.b0; b < ln.b0 + ln.nb; ++b) pick.mirostat_mu[b] = rows.alt[b].mu;
         }
     }
+    if (kind.constrained && pick.grammar_state)     // every lane's words hold the states after the draws that counted
+        for (const wrk_lane& ln : L)
+            WRK_HIP(ctx, hipMemcpy(pick.grammar_state + ln.b0, ln.frame->gram_state, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
     return m->after_loop(groups);
 }
 

@@ -77,6 +77,7 @@ class GenerateOptions(C.Structure):
     _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
                 ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
+                ("grammar", _P), ("grammar_state", _u32p),
                 ("mirostat_tau", _f32p), ("mirostat_eta", _f32p), ("mirostat_mu", _f32p), ("typical_p", _f32p),
                 ("top_k", _u32p), ("min_p", _f32p)]
 
@@ -89,6 +90,7 @@ class QueueOptions(C.Structure):
                 ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("init_state", _P),
                 ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
+                ("grammar", _P), ("grammar_state", _u32p),
                 ("mirostat_tau", _f32p), ("mirostat_eta", _f32p), ("mirostat_mu", _f32p), ("typical_p", _f32p),
                 ("top_k", _u32p), ("min_p", _f32p)]
 
@@ -107,6 +109,9 @@ class QueuePool(C.Structure):
 MAX_STOP_TOKENS = 16        # WRK_MAX_STOP_TOKENS
 MAX_TOP_LOGPROBS = 20       # WRK_MAX_TOP_LOGPROBS
 QUEUE_NO_ENTRY = 0xFFFFFFFF     # WRK_QUEUE_NO_ENTRY
+GRAMMAR_REJECT = 0xFFFF         # WRK_GRAMMAR_REJECT
+MAX_TOKEN_CLASSES = 8192        # WRK_MAX_TOKEN_CLASSES
+_u16p = C.POINTER(C.c_uint16)
 _TP = C.POINTER(TensorDesc)
 
 # name -> (restype, argtypes); every symbol declared in include/*.h
@@ -203,6 +208,10 @@ HIP_SYMBOLS = {
                                               _u32p, _f32p, _f32p, C.c_uint32]),
     "wrk_v6_generate_penalized": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _f32p, _f32p, _f32p, _P,
                                               _u32p, _f32p, _f32p, C.c_uint32]),
+    "wrk_grammar_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _u16p, _u16p, C.POINTER(_P)]),
+    "wrk_grammar_destroy": (C.c_int32, [_P]),
+    "wrk_constrain_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _u32p]),
+    "wrk_grammar_advance": (C.c_int32, [_P, _P, _u32p, _u32p, C.c_uint32]),
     "wrk_v7_generate_stop": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(GenerateOptions), _u32p, _u32p, _f32p, _u32p,
                                          _f32p, C.c_uint32]),
     "wrk_v6_generate_stop": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(GenerateOptions), _u32p, _u32p, _f32p, _u32p,
@@ -346,6 +355,103 @@ def _stop_csr(stop, n: int, owners: str):
     off[1:] = np.cumsum([len(x) for x in sets])
     ids = _u32(np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in sets]) if n else [])
     return (ids if ids.size else np.zeros(1, np.uint32)), off
+
+
+def _fill_grammar(opt, n: int, keep: list, grammar, grammar_state):
+    """The grammar fields of a GenerateOptions or QueueOptions for n rows; returns the in/out state array [n] (grammar_state, a scalar
+    or one value per row; None: every row starts in state 0), or None without a grammar.  The array goes into `keep`."""
+    if grammar is None:
+        if grammar_state is not None:
+            raise ValueError("grammar_state without grammar")
+        return None
+    st = np.array(_per_row(0 if grammar_state is None else grammar_state, n, np.uint32), np.uint32)
+    keep.append(st)
+    opt.grammar, opt.grammar_state = grammar.h, _ptr(st, _u32p)
+    return st
+
+
+def _grammar_tables(num_vocab: int, token_class, transitions):
+    """(token_class u16 [V], transitions u16 [S, C]) checked for range and shape (ValueError); what `Grammar` uploads."""
+    tc = np.asarray(token_class, np.int64).reshape(-1)
+    tr = np.asarray(transitions, np.int64)
+    if tc.size != num_vocab:
+        raise ValueError(f"token_class has {tc.size} entries for {num_vocab} tokens")
+    if tr.ndim != 2 or tr.size == 0:
+        raise ValueError("transitions: a non-empty [num_states, num_classes] table")
+    if tc.min(initial=0) < 0 or tc.max(initial=0) > 0xFFFF or tr.min() < 0 or tr.max() > 0xFFFF:
+        raise ValueError("token_class / transitions entries must fit 16 bits")
+    return np.ascontiguousarray(tc.astype(np.uint16)), np.ascontiguousarray(tr.astype(np.uint16))
+
+
+def grammar_walk(token_class, transitions, state: int, tokens) -> int:
+    """The state after `tokens` from `state` on the host; ValueError at the first rejected token."""
+    s = int(state)
+    for i, t in enumerate(np.asarray(tokens, np.int64).reshape(-1)):
+        nx = int(transitions[s][int(token_class[int(t)])])
+        if nx == GRAMMAR_REJECT:
+            raise ValueError(f"token {i} (id {int(t)}) is not allowed in state {s}")
+        s = nx
+    return s
+
+
+def grammar_from_dense(table):
+    """table [S][V] of next states (-1: the token is not allowed in the state) -> (token_class u16 [V], transitions u16 [S][C]):
+    identical columns are merged into one class, classes numbered by first occurrence.  Bookkeeping only: no device is touched."""
+    t = np.asarray(table, np.int64)
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("table: [num_states >= 1][num_vocab >= 1]")
+    S, V = t.shape
+    if S > 0xFFFF or t.min() < -1 or t.max() >= S:
+        raise ValueError(f"table: at most 65535 states, entries -1 or < {S}")
+    _, first, inv = np.unique(t, axis=1, return_index=True, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    order = np.argsort(first, kind="stable")            # unique column k -> its rank by first occurrence
+    rank = np.empty_like(order)
+    rank[order] = np.arange(order.size)
+    if order.size > MAX_TOKEN_CLASSES:
+        raise ValueError(f"{order.size} distinct columns, at most {MAX_TOKEN_CLASSES} classes")
+    cols = t[:, first[order]]
+    return rank[inv].astype(np.uint16), np.where(cols < 0, GRAMMAR_REJECT, cols).astype(np.uint16)
+
+
+def grammar_from_choices(num_vocab: int, choices, end_token: int):
+    """The trie automaton that accepts exactly one of the token sequences `choices` and then `end_token` forever (vLLM's
+    guided_choice) -> (token_class, transitions, start_state).  A state per trie node, the root first, and one final state that
+    allows only end_token and loops on it; a choice may be a prefix of another (its node then allows end_token beside its children)
+    but may not contain end_token.  Bookkeeping only: no device is touched."""
+    seqs = [[int(t) for t in c] for c in choices]
+    end_token = int(end_token)
+    if not seqs:
+        raise ValueError("no choices")
+    if not 0 <= end_token < num_vocab or any(not 0 <= t < num_vocab for c in seqs for t in c):
+        raise ValueError(f"token ids must be < {num_vocab}")
+    if any(end_token in c for c in seqs):
+        raise ValueError("a choice contains end_token")
+    used = {end_token: 0}                               # token -> column of the reduced table; the last column: every other token
+    nodes, terminal = [{}], [False]                     # per trie node: column -> child, and whether a choice ends there
+    for c in seqs:
+        s = 0
+        for t in c:
+            k = used.setdefault(t, len(used))
+            if k not in nodes[s]:
+                nodes[s][k] = len(nodes)
+                nodes.append({})
+                terminal.append(False)
+            s = nodes[s][k]
+        terminal[s] = True
+    final = len(nodes)
+    small = np.full((final + 1, len(used) + 1), -1, np.int64)
+    for s, kids in enumerate(nodes):
+        for k, child in kids.items():
+            small[s, k] = child
+        if terminal[s]:
+            small[s, 0] = final
+    small[final, 0] = final
+    cls, trans = grammar_from_dense(small)
+    token_class = np.full(num_vocab, cls[-1], np.uint16)
+    for t, k in used.items():
+        token_class[t] = cls[k]
+    return token_class, trans, 0
 
 
 # ----------------------------------------------------------------------------- backend objects
@@ -513,6 +619,68 @@ class Context:
         ap, af = _per_row(presence, n, np.float32), _per_row(frequency, n, np.float32)
         self.check(hip.wrk_penalize_logits(self.h, buf.h, V, stride, n, occ.h, first_batch, _ptr(ap, _f32p), _ptr(af, _f32p)))
         return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
+
+    def constrain_logits(self, logits, grammar: "Grammar", states, num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
+        """Masks rows of logits with an automaton on the device: row r keeps the bits of every token that `grammar`
+        allows in states[r] and gets -inf elsewhere.  `logits`: an [n, V] f32 array (returns the masked copy), or a `Buffer` of n rows
+        of `row_stride` f32 (first `num_vocab` used), masked in place (returns None).  states: a scalar or one state per row."""
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            stride = int(row_stride or V)
+            n = (buf.nbytes // 4 - V) // stride + 1 if buf.nbytes >= 4 * V else 0
+            a = None
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            n, V = a.shape
+            stride = V
+            buf = self.buffer(a)
+        st = _per_row(states, n, np.uint32)
+        self.check(hip.wrk_constrain_logits(self.h, buf.h, V, stride, n, grammar.h, _ptr(st, _u32p)))
+        return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
+
+
+class Grammar:
+    """A deterministic automaton over token ids for constrained decoding, on the device: token_class [num_vocab] maps
+    every token to a class and transitions [num_states, num_classes] holds the next state, or GRAMMAR_REJECT where the class is not
+    allowed.  `grammar_from_dense` / `grammar_from_choices` build the two tables; regex, BNF or JSON-schema compilers sit above them.
+    Every state must allow at least one token.  Pass it to the decode loops as `grammar=`, with `grammar_state=` the state each
+    sequence starts in."""
+
+    REJECT = GRAMMAR_REJECT
+
+    def __init__(self, ctx: Context, num_vocab: int, token_class, transitions):
+        self.token_class, self.transitions = _grammar_tables(num_vocab, token_class, transitions)
+        self.num_vocab = int(num_vocab)
+        self.num_states, self.num_classes = self.transitions.shape
+        h = _P()
+        ctx.check(hip.wrk_grammar_create(ctx.h, self.num_vocab, self.num_states, self.num_classes, _ptr(self.token_class, _u16p),
+                                         _ptr(self.transitions, _u16p), C.byref(h)))
+        self.ctx, self.h = ctx, h
+
+    def walk(self, state: int, tokens) -> int:
+        """The state after `tokens` from `state`, walked on the host; ValueError at the first rejected token."""
+        return grammar_walk(self.token_class, self.transitions, state, tokens)
+
+    def advance(self, states, tokens) -> np.ndarray:
+        """One step per row on the device: the next state of states[r] on tokens[r]; a rejected token leaves the state as it was.
+        Returns uint32 [n]."""
+        tk = _u32(tokens).reshape(-1)
+        st = np.array(_per_row(states, tk.size, np.uint32), np.uint32)
+        self.ctx.check(hip.wrk_grammar_advance(self.ctx.h, self.h, _ptr(st, _u32p), _ptr(tk, _u32p), tk.size))
+        return st
+
+    def close(self):
+        if self.h and self.ctx.h:
+            hip.wrk_grammar_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Occurrence:
@@ -998,6 +1166,9 @@ class Runtime:
         self.last_logprobs = None
         # the mu of the last generate_* call with `mirostat`, per sequence (generate_queue: per request); None after a call without
         self.last_mirostat_mu = None
+        # the automaton states after the last generate_* call with `grammar`, per sequence (generate_queue: per request); None after
+        # a call without
+        self.last_grammar_state = None
 
     def token_bytes(self, num_batch: int = 1) -> int:
         if self.model6:
@@ -1116,21 +1287,27 @@ class Runtime:
         logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
         fn, mdl = self._entry("generate_" + name)
         self.last_logprobs = None
+        self.last_grammar_state = None
         self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, *rows, _ptr(out, _u32p),
                           _ptr(logits, _f32p) if want_logits else None, C.byref(ms), self._mode(mode, groups)))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
 
-    def generate_greedy(self, first_tokens, steps: int, mode: int = 1, want_logits: bool = False, groups: int = 1, logprobs=None):
+    def generate_greedy(self, first_tokens, steps: int, mode: int = 1, want_logits: bool = False, groups: int = 1, logprobs=None,
+                        grammar: "Grammar" = None, grammar_state=None):
         """Device-resident greedy loop; returns (tokens [steps, B], elapsed_ms[, last logits [B, V]]).
         groups > 1 (RWKV-7): the B independent sequences are dealt over that many concurrent pipelines (each a contiguous block of
         sequences with its own frame, decode program and HIP stream) instead of one batched step.
         logprobs (None: off; 0..MAX_TOP_LOGPROBS): every step also leaves the log-prob of each picked token and the `logprobs` most
         likely alternatives at its position, computed on the device on the raw head output (`Context.top_logprobs`), in
         `last_logprobs`; such a call goes through the options entry point (wrk_v*_generate_stop without stop sets).  The return
-        shapes do not change."""
-        if logprobs is not None:
+        shapes do not change.
+        grammar / grammar_state (a scalar or one state per sequence; None: 0): constrained decoding: every pick is made
+        on the row masked by the `Grammar` in the sequence's automaton state, and every draw moves that state, on the device;
+        afterwards `last_grammar_state` [B] holds the states to pass to the next call of a session.  Such a call goes through the
+        options entry point and replays step programs of its own."""
+        if logprobs is not None or grammar is not None or grammar_state is not None:
             return self._generate_filtered(first_tokens, steps, None, None, None, None, 0.0, 0.0, 1.0, None, None, mode, want_logits, groups,
-                                           logprobs)
+                                           logprobs, grammar=grammar, grammar_state=grammar_state)
         return self._generate("greedy", first_tokens, steps, (), mode, groups, want_logits)
 
     def _generate_options(self, first_tokens, steps, opt, keep, mode, want_logits, logprobs=None):
@@ -1163,7 +1340,8 @@ class Runtime:
         return (t, p, sd), (_ptr(t, _f32p), _ptr(p, _f32p), _ptr(sd, _u32p))
 
     def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
-                        groups: int = 1, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None):
+                        groups: int = 1, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
+                        grammar: "Grammar" = None, grammar_state=None):
         """As `generate_greedy`, each sequence's next token drawn by `Sampler::sample` (examples/chat.rs:150-190) on the device with its
         own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b.
         top_k / min_p (a scalar or one value per sequence; None: off): the draw is `sample_logits(..., top_k, min_p)`'s; such a call goes
@@ -1173,35 +1351,40 @@ class Runtime:
         DESIGN.md §7i), mu carried on the device from step to step; mirostat_mu: the mu each sequence starts from (None: 2 tau);
         afterwards `last_mirostat_mu` [B] holds the values to pass to the next call of a session.  typical_p (a scalar or one value per
         sequence): locally typical sampling.  One family per call (top_k / min_p, mirostat, typical_p); such a call goes through the
-        options entry point and replays step programs of its own."""
-        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p)):
+        options entry point and replays step programs of its own.
+        grammar / grammar_state: as `generate_greedy`; the draw is the same sampler's on the masked row."""
+        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
-                                           want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p)
+                                           want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state)
         keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
         return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
 
     def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
-                           want_logits, groups, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None):
+                           want_logits, groups, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar=None,
+                           grammar_state=None):
         opt, keep = GenerateOptions(), []
         mu = _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                         mirostat, mirostat_mu, typical_p)
+        gs = _fill_grammar(opt, _u32(first_tokens).size, keep, grammar, grammar_state)
         out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits, logprobs)
         self.last_mirostat_mu = mu
+        self.last_grammar_state = gs
         return (out, ms, logits) if want_logits else (out, ms)
 
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
                            frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1, top_k=None, min_p=None,
-                           logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None):
+                           logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None):
         """As `generate_sample`, each draw made on the logits penalised with the sequence's slot of `occurrence` (ChatRWKV's
         alpha_presence / alpha_frequency / token_ban), and the slot updated after every draw (count *= decay, then the drawn token's
         weight added).  The first token of a call is not counted; the last drawn one is.  The table carries over between calls.
         Scalars broadcast; seed=None: seed[b] = b.  last logits: the head output before penalties.  top_k / min_p: as `generate_sample`,
         the cuts made on the penalised logits.  logprobs: as `generate_greedy`, on the head output before penalties and bans (a banned
         token may appear among the alternatives).  mirostat / mirostat_mu / typical_p: as `generate_sample`, the pick made on the
-        penalised logits."""
-        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p)):
+        penalised logits.  grammar / grammar_state: as `generate_greedy`, the mask applied to the penalised logits; bans belong in the
+        grammar (a row that bans and automaton together leave empty draws an unspecified token, which the automaton rejects)."""
+        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
-                                           min_p, mode, want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p)
+                                           min_p, mode, want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state)
         B = _u32(first_tokens).size
         keep, rows = self._sampler_rows(B, temperature, top_p, seed)
         pen = [_per_row(v, B, np.float32) for v in (presence, frequency, decay)]
@@ -1210,7 +1393,8 @@ class Runtime:
 
     def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
-                      poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None):
+                      poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
+                      grammar: "Grammar" = None, grammar_state=None):
         """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
         at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
         MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
@@ -1220,12 +1404,15 @@ class Runtime:
         logprobs: as `generate_greedy`; rows [:lengths[b], b] of `last_logprobs` are those of the call without stops, the stop token's
         own row included; later rows of a finished sequence are unspecified.
         mirostat / mirostat_mu / typical_p: as `generate_sample`; `last_mirostat_mu[b]` has seen exactly lengths[b] draws, the stop
-        token's included."""
+        token's included.
+        grammar / grammar_state: as `generate_greedy`; `last_grammar_state[b]` has seen exactly lengths[b] draws, the stop token's
+        included: the state freezes with the sequence."""
         ft = _u32(first_tokens)
         ids, off = _stop_csr(stop, ft.size, "sequences")
         opt, keep = GenerateOptions(), []
         self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                                            mirostat, mirostat_mu, typical_p)
+        self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
         opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
         out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, self._mode(mode, groups), want_logits,
                                                                               logprobs)
@@ -1235,7 +1422,7 @@ class Runtime:
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
                        mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None,
-                       mirostat=None, mirostat_mu=None, typical_p=None):
+                       mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1254,7 +1441,11 @@ class Runtime:
         request r's reply tokens, as `generate_greedy`'s; the rows of the steps that feed prompt tokens are discarded.
         mirostat=(tau, eta) / typical_p: per request (scalars broadcast), as `generate_sample`.  mirostat_mu[r] (None: 2 tau[r]) is what
         request r starts from when it is dispatched, whatever its slot held; `last_mirostat_mu[r]` is its mu after its reply draws
-        (untouched for reason 0).  mu is not part of a pool entry: a session carries it through these arrays."""
+        (untouched for reason 0).  mu is not part of a pool entry: a session carries it through these arrays.
+        grammar / grammar_state (a scalar or one state per request; None: 0): one `Grammar` for the call; request r starts in
+        grammar_state[r] when it is dispatched, whatever its slot held, and only its reply draws move the state (the steps that feed
+        prompt tokens do not); `last_grammar_state[r]` is its state after its reply draws (the start state for reason 0).  Requests
+        that need different grammars use disjoint state sets of one automaton; the state is not part of a pool entry."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1272,6 +1463,7 @@ class Runtime:
         keep = []
         self.last_mirostat_mu = _fill_pick(opt, R, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                                            mirostat, mirostat_mu, typical_p)
+        self.last_grammar_state = _fill_grammar(opt, R, keep, grammar, grammar_state)
         if init_state is not None:
             opt.init_state = init_state.h
         opt.poll_steps = poll_steps
