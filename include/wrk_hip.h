@@ -508,8 +508,35 @@ int32_t wrk_grammar_advance(wrk_ctx* ctx, const wrk_grammar* grammar, uint32_t* 
  * it ran before.  Tokens and final states do not depend on the number of lanes.  If the bans of `occ` and the automaton together leave
  * a row with no finite logit, the picked id is unspecified but < num_vocab (as for a NaN row); the automaton then sees a rejected token
  * and keeps its state, and nothing faults: to combine bans with a grammar, put them in the grammar.  The two fields sit between
- * the log-prob fields and the Mirostat fields: the six fields behind them, the filter fields last, stay where they were. */
+ * the log-prob fields and the Mirostat fields: the six fields behind them, the filter fields last, stay where they were.
+ * Stop sequences (multi-token stops: a stop string, tokenized by the caller, one sequence per way it tokenizes).  Next to its stop set,
+ * sequence b has 0 .. WRK_MAX_STOP_SEQUENCES stop sequences of 1 .. WRK_MAX_STOP_SEQUENCE_LEN ids as a CSR of a CSR: stop sequence s is
+ * stop_seq_tokens[stop_seq_offsets[s] .. stop_seq_offsets[s + 1]) and sequence b owns stop sequences [stop_seq_owners[b] ..
+ * stop_seq_owners[b + 1]) (num_batch + 1 owners entries).  All three arrays or none; non-NULL arrays select the stop-sequence step
+ * programs even when nobody owns a sequence, NULL arrays exactly the programs that ran before.  Every sequence has a tail: its last
+ * WRK_STOP_TAIL_LEN draws that counted (the draws an occurrence row counts: every step up to and including the one that ends the
+ * sequence, none after it; x_0 is not a draw), oldest first, right aligned, WRK_STOP_TAIL_EMPTY for a missing entry.  At a counted
+ * draw y stop sequence k of length l matches when the last l entries of (tail ++ [y]) equal it; EMPTY equals no id, so nothing matches
+ * across the start of the tail.  The sequence ends at that step if a stop sequence matches or y is in its stop set, exactly as a stop
+ * token ends it: out_lengths, the frozen state slot, occurrence row, last_logits row, mu, grammar state and log-prob rows are those of
+ * the call without stops run for out_lengths[b] steps.  out_stop_match (host u32 [num_batch], may be NULL): WRK_STOP_MATCH_NONE (not
+ * ended by a stop), WRK_STOP_MATCH_TOKEN (an id of the stop set), else the index k of the matching stop sequence within b's list.  Of
+ * several matches in one step the longest wins, at equal length the stop-set id beats a sequence and the lower index the higher.  The
+ * host trims len(sequence k) tokens, or 1; the device trims nothing.  stop_tail (host u32 [num_batch][WRK_STOP_TAIL_LEN], in/out, may be
+ * NULL: every tail starts empty and nothing is returned): a session carries its tail from call to call through this array, as it
+ * carries mirostat_mu and grammar_state, so that a stop sequence that straddles two calls still ends the reply; the tail of a finished
+ * sequence is frozen with it.  WRK_E_ARG before any launch: only some of the three arrays, offsets or owners that do not start at 0 or
+ * decrease, more than WRK_MAX_STOP_SEQUENCES for one owner, a stop sequence of length 0 or above WRK_MAX_STOP_SEQUENCE_LEN, an id >=
+ * num_vocab, out_stop_match or stop_tail without the three arrays, a stop_tail entry that is neither EMPTY nor < num_vocab, an EMPTY
+ * entry after a non-EMPTY one.  The stop sequences are device data: one cached step program serves any of them.  Tokens, lengths,
+ * matches and tails do not depend on the number of lanes.  The five fields sit between grammar_state and mirostat_tau. */
 #define WRK_MAX_STOP_TOKENS 16
+#define WRK_MAX_STOP_SEQUENCES 8
+#define WRK_MAX_STOP_SEQUENCE_LEN 8
+#define WRK_STOP_TAIL_LEN 7
+#define WRK_STOP_TAIL_EMPTY 0xFFFFFFFFu
+#define WRK_STOP_MATCH_NONE 0xFFFFFFFFu
+#define WRK_STOP_MATCH_TOKEN 0xFFFFFFFEu
 typedef struct wrk_generate_options {
     const float *temperature, *top_p;
     const uint32_t *seed;
@@ -523,6 +550,9 @@ typedef struct wrk_generate_options {
     float *out_top_logprobs;
     const wrk_grammar *grammar;
     uint32_t *grammar_state;
+    const uint32_t *stop_seq_tokens, *stop_seq_offsets, *stop_seq_owners;
+    uint32_t *out_stop_match;
+    uint32_t *stop_tail;
     const float *mirostat_tau, *mirostat_eta;
     float *mirostat_mu;
     const float *typical_p;
@@ -532,6 +562,16 @@ typedef struct wrk_generate_options {
 int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_batch,
                              uint32_t steps, const wrk_generate_options* opt, uint32_t* out_tokens, uint32_t* out_lengths,
                              float* last_logits_or_null, uint32_t* steps_run, float* elapsed_ms_or_null, uint32_t mode);
+/* One counted draw of the stop-sequence matcher on the device, for num_rows owners: what a stop-sequence step program does with a drawn
+ * token, and what a host-driven loop calls after each of its own draws.  Row r has the stop sequences of wrk_generate_options' three
+ * arrays (num_rows + 1 owners entries; all three required), optionally the stop set stop_tokens[stop_offsets[r] .. stop_offsets[r + 1])
+ * (both NULL: none), the tail tails[r][WRK_STOP_TAIL_LEN] (host u32, in/out) and the drawn token tokens[r].  out_match[r] (host u32
+ * [num_rows]) receives WRK_STOP_MATCH_NONE, WRK_STOP_MATCH_TOKEN or the index of the matching stop sequence, resolved as in
+ * wrk_generate_options; the tail then takes the token in, match or not.  Every id, token and non-EMPTY tail entry must be < num_vocab
+ * (else WRK_E_ARG, as for the other errors listed there).  Blocking. */
+int32_t wrk_stop_sequences_advance(wrk_ctx* ctx, uint32_t num_vocab, uint32_t num_rows, const uint32_t* stop_seq_tokens,
+                                   const uint32_t* stop_seq_offsets, const uint32_t* stop_seq_owners, const uint32_t* stop_tokens,
+                                   const uint32_t* stop_offsets, uint32_t* tails, const uint32_t* tokens, uint32_t* out_match);
 
 /* A request queue in the decode loops: num_requests requests of different prompt and reply lengths are served on the num_batch slots of
  * `state` in one call, with the slot bookkeeping on the device (the reference's examples/batch.rs: "multiple inferences of different
@@ -582,7 +622,15 @@ int32_t wrk_v7_generate_stop(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* st
  * slot's previous request left -- and only its reply draws move the state: the steps that feed prompt tokens do not.  On return entry
  * r holds the state after the request's reply draws for reasons 1, 2 and 3 (3: the state reached so far) and is untouched for reason
  * 0.  Requests that need different grammars use disjoint state sets of one automaton.  The state is not part of a state-pool entry: a
- * session carries it through this array. */
+ * session carries it through this array.
+ * Stop sequences, as in wrk_generate_options: stop_seq_owners has num_requests + 1 entries and request r owns stop sequences
+ * [stop_seq_owners[r] .. stop_seq_owners[r + 1]).  Only reply draws enter a request's tail: prompt tokens and the discarded draws of
+ * the steps that feed them never do, so a prompt that is (or ends in the beginning of) a stop sequence does not end its reply.  The
+ * tail starts empty when the request is dispatched, at step 0 or at a refill on the device -- never with what its slot's previous
+ * request left -- and is not returned.  A match ends the request with reason 1 exactly as a stop token does: the slot resets and
+ * refills in the same step and a pool entry is saved as for a stop token.  out_stop_match (host u32 [num_requests], may be NULL):
+ * WRK_STOP_MATCH_NONE for reasons 0, 2 and 3, else as in wrk_generate_options.  The tail is not part of a state-pool entry.  The four
+ * fields sit between grammar_state and mirostat_tau. */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
     const uint32_t *prompt_tokens, *prompt_offsets, *max_new;
@@ -599,6 +647,8 @@ typedef struct wrk_queue_options {
     float *out_top_logprobs;
     const wrk_grammar *grammar;
     uint32_t *grammar_state;
+    const uint32_t *stop_seq_tokens, *stop_seq_offsets, *stop_seq_owners;
+    uint32_t *out_stop_match;
     const float *mirostat_tau, *mirostat_eta;
     float *mirostat_mu;
     const float *typical_p;

@@ -27,8 +27,12 @@ differ by the mask launch and the advance launch alone -- for the greedy and the
 spread of each.  Every call starts from the same state; the unconstrained tokens are recorded (as a hash) so that the same leg on another
 build can be compared with them.
 
+A ninth leg (--stop-seq): the stop-sequence step program with 8 sequences of 8 ids per sequence that never match against
+the stop program with 16 ids that never match and against the plain sampled step, alternating, with the run-to-run spread of each; at the
+runtime's full batch the same for a queue whose requests never end.  The stop-sequence program has the launch count of the stop program.
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
-                                 [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9] [--grammar]
+                                 [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9] [--grammar] [--stop-seq]
 
 Prints one JSON object.
 """
@@ -117,6 +121,53 @@ def stop_leg(rt, first, B, V, args):
         runs.append(int(tok.shape[0]))
     res["early_exit"] = {"steps": args.stop_steps, "lengths_max": int(lens.max()), "steps_run": runs, "poll_steps": "default",
                          "plain_wall_ms": [round(x, 3) for x in long_plain], "stop_wall_ms": [round(x, 3) for x in long_stop]}
+    reset()
+    return res
+
+
+def stopseq_leg(rt, first, B, V, args):
+    """Medians of the per-step time, alternating in one process and every call from the same state: the plain sampled step, the stop
+    program with 16 stop ids per sequence that are never drawn (the --stop leg at polling off), and the stop-sequence program with 8
+    stop sequences of 8 ids per sequence that never match.  At the runtime's full batch also the queue: one request per slot that never
+    ends, with the 16 ids against with the 8 x 8 sequences."""
+    skw = dict(temperature=args.temperature, top_p=args.top_p)
+    start = [rt.state_read(b) for b in range(B)]
+
+    def reset():
+        for b in range(B):
+            rt.state_write(start[b], b)
+    reset()
+    drawn, _ = rt.generate_sample(first, args.steps, **skw)
+    used = set(drawn.reshape(-1).tolist())
+    never = [i for i in range(V - 1, -1, -1) if i not in used][:16]
+    seqs = [[never[(k + j) % 16] for j in range(8)] for k in range(8)]      # 8 x 8 of ids that are never drawn: one compare per sequence
+    legs = {"sample": lambda: rt.generate_sample(first, args.steps, **skw)[1],
+            "stop": lambda: (rt.generate_stop(first, args.steps, never, poll_steps=POLL_OFF, **skw), rt.last_stop_ms)[1],
+            "stop_seq": lambda: (rt.generate_stop(first, args.steps, [], poll_steps=POLL_OFF, stop_sequences=seqs, **skw), rt.last_stop_ms)[1]}
+    queue = B == rt.num_batch
+    if queue:
+        qkw = dict(max_new=args.steps, max_steps=args.steps, poll_steps=POLL_OFF, **skw)
+        legs["queue_stop"] = lambda: (rt.generate_queue([[t] for t in first], stop=never, **qkw), rt.last_queue_ms)[1]
+        legs["queue_stop_seq"] = lambda: (rt.generate_queue([[t] for t in first], stop_sequences=seqs, **qkw), rt.last_queue_ms)[1]
+    reset()
+    tok, lens = rt.generate_stop(first, args.steps, [], poll_steps=POLL_OFF, stop_sequences=seqs, **skw)
+    never_stopped = bool((lens == args.steps).all()) and np.array_equal(tok, drawn) and bool((rt.last_stop_match == 0xFFFFFFFF).all())
+    per = {k: [] for k in legs}
+    for k, fn in legs.items():                                          # capture and warm up
+        reset()
+        fn()
+    for _ in range(args.reps):
+        for k, fn in legs.items():
+            reset()
+            per[k].append(fn() / args.steps)
+    med = {k: float(np.median(v)) for k, v in per.items()}
+    res = {"never_stops": never_stopped, "sequences": "8 x 8 ids, never drawn", "stop_ids": 16, "poll_steps": "off", "queue_slots": rt.num_batch if queue else None}
+    for k, v in per.items():
+        res[k] = {"ms_per_step": round(med[k], 5), "spread_us": round((max(v) - min(v)) * 1e3, 2), "ms_all": [round(x, 5) for x in v]}
+    res["stop_seq_minus_stop_us"] = round((med["stop_seq"] - med["stop"]) * 1e3, 2)
+    res["stop_seq_minus_sample_us"] = round((med["stop_seq"] - med["sample"]) * 1e3, 2)
+    if queue:
+        res["queue_stop_seq_minus_queue_stop_us"] = round((med["queue_stop_seq"] - med["queue_stop"]) * 1e3, 2)
     reset()
     return res
 
@@ -270,6 +321,7 @@ def main():
     ap.add_argument("--mirostat", default=None, help="TAU,ETA, e.g. 5,0.1")
     ap.add_argument("--typical", type=float, default=None, help="typical_p, e.g. 0.9")
     ap.add_argument("--grammar", action="store_true", help="the constrained loop against the same loop without a grammar")
+    ap.add_argument("--stop-seq", action="store_true", help="the stop-sequence programs against the stop programs and the sampled step")
     args = ap.parse_args()
     import wrk
 
@@ -349,6 +401,8 @@ def main():
                                        "top_k_only_spread_us": round((max(k) - min(k)) * 1e3, 2), "top_k_only_ms_all": [round(x, 5) for x in k]})
         if args.stop:
             out["batches"][-1]["stop"] = stop_leg(rt, first, B, V, args)
+        if args.stop_seq:
+            out["batches"][-1]["stop_seq"] = stopseq_leg(rt, first, B, V, args)
         if args.logprobs:
             out["batches"][-1]["logprobs"] = logprob_leg(rt, first, args)
         if args.mirostat or args.typical is not None:

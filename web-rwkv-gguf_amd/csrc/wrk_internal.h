@@ -285,6 +285,20 @@ void stop_snapshot(hipStream_t s, const StopGeom& g, uint32_t b, int num_cu);
 // snapshot -> state slot and head_o row of every sequence that is done; lengths[b] = its length, or *counter if it never ended
 void stop_restore(hipStream_t s, const StopGeom& g, uint32_t b, int num_cu);
 
+// Stop sequences (the matcher itself: wrk_stopseq_dev.h).  StopSeqRow: one owner's stop sequences as device data, each
+// stored REVERSED (tok[k][0] is sequence k's last id), so that the usual step rejects a sequence after one compare with the drawn token.
+// An owner's tail is WRK_STOP_TAIL_LEN words, oldest first, right aligned, WRK_STOP_TAIL_EMPTY for a missing entry -- the ABI's layout
+struct StopSeqRow { uint32_t count, pad[3]; uint32_t len[WRK_MAX_STOP_SEQUENCES]; uint32_t tok[WRK_MAX_STOP_SEQUENCES][WRK_MAX_STOP_SEQUENCE_LEN]; };
+// the stop-sequence buffers of a stop program: rows [B], tails [B][WRK_STOP_TAIL_LEN], match words [B] (NONE until the sequence ends)
+struct StopSeqBufs { const StopSeqRow* rows; uint32_t* tail; uint32_t* match; };
+// advance_stop for stop programs with sequences: the same ownership and ordering; a sequence ends on its stop set or on a stop
+// sequence, and the step also writes its tail and, where it ends, its match word
+void advance_stop_seq(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, StopParam* par,
+                      uint32_t* just_ended, uint32_t* live, const StopSeqBufs& q, uint32_t b);
+// one counted draw of n owners (wrk_stop_sequences_advance): row r's stop sequences rows[r], its stop set ids[r] (nullptr: none; only
+// ids / count of a StopParam are read), tail[r] in / out, tokens[r], match[r] out
+void stop_seq_rows(hipStream_t s, uint32_t n, const StopSeqRow* rows, const StopParam* ids, uint32_t* tail, const uint32_t* tokens, uint32_t* match);
+
 // wrk_queue.hip: a request queue in the decode loops.  R requests are served on the B slots of a state; the slot
 // bookkeeping is device data in per-frame buffers written before every call, so one captured program serves any queue.
 // QueueReq: one request (prompt = pool[prompt_off .. + prompt_len), its pick parameters and stop set).  QueueSlot: what slot b is doing --
@@ -315,6 +329,12 @@ struct QueueBufs {
     // dispatched, its final value once it has ended, exactly as alt_mu; both nullptr without a grammar
     uint32_t* gram_state = nullptr;
     uint32_t* gram_req = nullptr;
+    // queues with stop sequences: seq_rows [R]: request r's stop sequences; seq_tail [B][WRK_STOP_TAIL_LEN]: the slot's
+    // tail, set empty where the slot takes a request; seq_match [R]: request r's match word (NONE until a stop ends it); all nullptr
+    // without stop sequences
+    const StopSeqRow* seq_rows = nullptr;
+    uint32_t* seq_tail = nullptr;
+    uint32_t* seq_match = nullptr;
 };
 // takes advance_tokens' place in a queue program: history <- drawn; per slot the next prompt token or the draw, stop / max_new check,
 // next requests to the slots that ended (ascending slot order), their parameters into the slot's rows, started[b], the log,

@@ -16,6 +16,7 @@
 // of it in the same stream; nothing has to clear it.  Plain vector stores only; no atomics; no kernel waits on another.
 #include "wrk_device.h"
 #include "wrk_runner.h"
+#include "wrk_stopseq_dev.h"
 
 namespace wrk {
 
@@ -24,8 +25,10 @@ static constexpr uint32_t QUEUE_CHUNK = QUEUE_THREADS * 4;     // floats a workg
 static constexpr uint32_t QUEUE_WAVES = QUEUE_THREADS / 64;
 
 // slots are owned by the threads of ONE workgroup (B <= 256, as advance_stop).  POOL (advance_queue_pool_kernel): the slots that ended
-// also go into the step's turnover list, at the position the scan below gives them
-template <bool POOL>
+// also go into the step's turnover list, at the position the scan below gives them.  SEQ (the _seq kernels): a reply draw
+// goes through stop_seq_step (wrk_stopseq_dev.h) with the request's stop set and its StopSeqRow and enters the slot's tail; a match ends
+// the request as a stop token does and leaves its match word; a slot that takes a request starts with an empty tail
+template <bool POOL, bool SEQ>
 __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
                                                    uint32_t* __restrict__ history, uint32_t* __restrict__ counter, const QueueBufs& Q,
                                                    const QueueStateBufs& P, uint32_t b) {
@@ -49,7 +52,16 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
             tokens[i] = y;
             const uint32_t n = r->stop_count < WRK_MAX_STOP_TOKENS ? r->stop_count : WRK_MAX_STOP_TOKENS;
             int hit = 0;
-            for (uint32_t k = 0; k < n; ++k) hit |= (r->stop_ids[k] == y);
+            if (SEQ) {
+                uint32_t* tp = Q.seq_tail + (size_t)i * STOP_TAIL;
+                StopTail tail = stop_tail_load(tp);
+                const uint32_t match = stop_seq_step(tail, y, Q.seq_rows + s.req, r->stop_ids, n);
+                stop_tail_store(tp, tail);
+                hit = match != WRK_STOP_MATCH_NONE;
+                if (hit) Q.seq_match[s.req] = match;
+            } else {
+                for (uint32_t k = 0; k < n; ++k) hit |= (r->stop_ids[k] == y);
+            }
             s.reply += 1;
             Q.log[s.req].length = s.reply;
             const uint32_t reason = hit ? 1u : (s.reply == r->max_new ? 2u : 0u);
@@ -88,6 +100,7 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
                 // still holds its start value)
                 if (Q.alt_par) Q.alt_par[i] = SampleAlt{q->tau, q->eta, Q.alt_mu ? Q.alt_mu[r] : 0.0f, q->typical_p};
                 if (Q.gram_req) Q.gram_state[i] = Q.gram_req[r];        // the same for its automaton state
+                if (SEQ) stop_tail_clear(Q.seq_tail + (size_t)i * STOP_TAIL);      // and its tail starts empty
                 if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
                 Q.log[r] = QueueLog{0u, 3u, i, step + 1};
                 started = 1;
@@ -110,13 +123,25 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
 __global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
                                                                       uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
                                                                       const QueueBufs Q, uint32_t b) {
-    advance_queue_body<false>(drawn, tokens, history, counter, Q, QueueStateBufs{}, b);
+    advance_queue_body<false, false>(drawn, tokens, history, counter, Q, QueueStateBufs{}, b);
+}
+
+__global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_seq_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                                          uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
+                                                                          const QueueBufs Q, uint32_t b) {
+    advance_queue_body<false, true>(drawn, tokens, history, counter, Q, QueueStateBufs{}, b);
 }
 
 __global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_pool_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
                                                                            uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
                                                                            const QueueBufs Q, const QueueStateBufs P, uint32_t b) {
-    advance_queue_body<true>(drawn, tokens, history, counter, Q, P, b);
+    advance_queue_body<true, false>(drawn, tokens, history, counter, Q, P, b);
+}
+
+__global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_pool_seq_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                                               uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
+                                                                               const QueueBufs Q, const QueueStateBufs P, uint32_t b) {
+    advance_queue_body<true, true>(drawn, tokens, history, counter, Q, P, b);
 }
 
 struct QueueResetArgs {
@@ -201,7 +226,9 @@ __global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_occurrence_kernel(u
 }
 
 void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q, uint32_t b) {
-    advance_queue_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, b);
+    // a queue with stop sequences has all three of their buffers (queue_bufs)
+    if (q.seq_rows) advance_queue_seq_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, b);
+    else advance_queue_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, b);
 }
 
 // slices of a layer's slot: layers * slices workgroups come to about two per CU, so that one starting request's fill (13 MB at the
@@ -232,7 +259,8 @@ void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t
 
 void advance_queue_pool(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q,
                         const QueueStateBufs& p, uint32_t b) {
-    advance_queue_pool_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, p, b);
+    if (q.seq_rows) advance_queue_pool_seq_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, p, b);
+    else advance_queue_pool_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, p, b);
 }
 
 void queue_turnover(hipStream_t s, const QueueGeom& g, const QueueBufs& q, const QueueStateBufs& p, uint32_t b, int num_cu) {

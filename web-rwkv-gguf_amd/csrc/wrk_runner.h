@@ -94,6 +94,9 @@ struct wrk_step_kind {
     // the pick is made on the row masked by the automaton of gram_par (wrk_grammar.hip): pen_o masked in place when penalised, else con_o =
     // the masked head_o; the tail then advances the automaton states where it updates the occurrence rows, under the same gate
     bool constrained = false;
+    // a STOP or queue tail that also matches stop sequences (wrk_stopseq_dev.h): advance_stop_seq / the queue's _seq kernels
+    // on the frame's stop-sequence buffers, in the place and with the launch count of the tail without them
+    bool stop_seqs = false;
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
     bool mirostat() const { return pick == MIROSTAT; }
@@ -107,6 +110,9 @@ struct wrk_step_kind {
         return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29 |
                (uint32_t)constrained << 31;
     }
+    // The kind's bits of GraphKey::mode2, the word that takes what key() has no room for: stop sequences 0.  0 for every kind that existed
+    // before the word did, so their keys compare as they always have
+    uint32_t key2() const { return (uint32_t)stop_seqs; }
 };
 
 // ------------------------------------------------------------------ frame state of a model (base of wrk_v7_model / wrk_v6_model)
@@ -183,6 +189,15 @@ struct wrk_frame_common {
     uint32_t queue_slot_cap = 0, queue_req_cap = 0;
     size_t queue_pool_cap = 0;
     uint32_t* queue_live() const { return &queue_ctl->live; }
+    // stop sequences (wrk_stopseq_dev.h), allocated by the first call that passes them only and written before every call.
+    // generate_stop: stopseq_rows / stopseq_tail [cap][WRK_STOP_TAIL_LEN] / stopseq_match [stopseq_cap], per sequence; generate_queue:
+    // queue_seq_rows / queue_seq_match [queue_seq_req_cap], per request, and queue_seq_tail [queue_seq_slot_cap][WRK_STOP_TAIL_LEN], per slot
+    wrk::StopSeqRow* stopseq_rows = nullptr;
+    uint32_t *stopseq_tail = nullptr, *stopseq_match = nullptr;
+    uint32_t stopseq_cap = 0;
+    wrk::StopSeqRow* queue_seq_rows = nullptr;
+    uint32_t *queue_seq_tail = nullptr, *queue_seq_match = nullptr;
+    uint32_t queue_seq_slot_cap = 0, queue_seq_req_cap = 0;
     // a queue call with a state pool, allocated by the first such call only and written before every call: the pool's
     // control words, the turnover list [turn cap], the start and save entries of the requests [2][index cap]
     wrk::QueueStateCtl* queue_state_ctl = nullptr;
@@ -209,16 +224,18 @@ struct wrk_frame_common {
     // b: tokens (generate: sequences | first sequence << 16); mode: the runner's mode and flag bits, in a decode step's key ORed
     // with wrk_step_kind::key(); nh: header rows
     // (the analogue of the reference's cached RnnJob per RnnInfo, runtime/mod.rs:110-209)
+    // mode2: wrk_step_kind::key2() in a decode step's key, 0 everywhere else -- the last word compared, so keys that leave it 0 order as
+    // they did without it
     struct GraphKey {
-        const void* state; uint32_t b, mode, nh = 0;
-        bool operator<(const GraphKey& o) const { return std::tie(state, b, mode, nh) < std::tie(o.state, o.b, o.mode, o.nh); }
+        const void* state; uint32_t b, mode, nh = 0, mode2 = 0;
+        bool operator<(const GraphKey& o) const { return std::tie(state, b, mode, nh, mode2) < std::tie(o.state, o.b, o.mode, o.nh, o.mode2); }
     };
     std::map<GraphKey, wrk_program*> graphs;
 
     // the ensure_* reallocate after a stream sync and drop the captured programs, which hold the old pointers; never inside a capture
     void drop_graphs();
     // the buffers an ensure_* reallocates together; bufs(g): their pointers, the one list regrow and release_common go through
-    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, LOGPROB, ALT, GRAMMAR, NUM_GROUPS };
+    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, LOGPROB, ALT, GRAMMAR, STOP_SEQ, QUEUE_SEQ, NUM_GROUPS };
     std::vector<void**> bufs(Group g);
     // sync, drop the programs (`drop`), free the buffers and allocate them again; after a failure all of them are freed
     // bytes: one size per buffer of bufs(g), in its order.  The caller sets its caps after WRK_OK: an error leaves them as they were
@@ -232,6 +249,8 @@ struct wrk_frame_common {
     int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
     int32_t ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens);
     int32_t ensure_queue_states(uint32_t slots, uint32_t requests);
+    int32_t ensure_stop_seqs(uint32_t n);
+    int32_t ensure_queue_seqs(uint32_t slots, uint32_t requests);
     int32_t ensure_logprobs(size_t rows, uint32_t B);
     int32_t ensure_poll(uint32_t lanes);        // lane 0's frame: pinned live counts and events of the polled loop
     void release_common();          // destroy paths: programs, scratch and every buffer above
@@ -286,7 +305,8 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
 // (kind.logprobs) the log-prob rows of the steps that ran, lane by lane with the pitch copies of the tokens.
 // stop: steps go out in blocks of poll_steps (0: 16), each followed by a copy of every lane's live count to pinned memory and an
 // event; before block k + 2 the host waits for block k's event and stops submitting once every count is 0.  Then stop_restore, and
-// lengths [B] / *steps_run come back
+// lengths [B] / *steps_run come back.  With the stop-sequence arrays of stop->opt (kind.stop_seqs) every lane also gets the
+// stop-sequence buffers with its sequences' rows and tails, and out_stop_match / stop_tail come back lane by lane
 struct wrk_stop_call { const wrk_generate_options* opt; uint32_t* out_lengths; uint32_t* steps_run; };
 int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                      const wrk_pick_args& pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,

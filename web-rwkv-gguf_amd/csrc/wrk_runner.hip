@@ -85,6 +85,8 @@ std::vector<void**> wrk_frame_common::bufs(Group g) {
         case STOP: return {(void**)&stop_par, (void**)&stop_flags, (void**)&stop_snap_state, (void**)&stop_snap_logits};
         case QUEUE: return {(void**)&queue_slots, (void**)&queue_started, (void**)&queue_ctl, (void**)&queue_reqs, (void**)&queue_log, (void**)&queue_pool};
         case QUEUE_STATES: return {(void**)&queue_state_ctl, (void**)&queue_turn, (void**)&queue_entries};
+        case STOP_SEQ: return {(void**)&stopseq_rows, (void**)&stopseq_tail, (void**)&stopseq_match};
+        case QUEUE_SEQ: return {(void**)&queue_seq_rows, (void**)&queue_seq_tail, (void**)&queue_seq_match};
         case LOGPROB: return {(void**)&lp_par, (void**)&lp_logprob, (void**)&lp_top_ids, (void**)&lp_top_logprobs, (void**)&lp_part, (void**)&lp_keys};
         default: return {};
     }
@@ -191,6 +193,25 @@ int32_t wrk_frame_common::ensure_queue_states(uint32_t slots, uint32_t requests)
     return rc;
 }
 
+int32_t wrk_frame_common::ensure_stop_seqs(uint32_t n) {
+    if (stopseq_rows && n <= stopseq_cap) return WRK_OK;
+    // stop-sequence programs hold the old pointers; before the first allocation none exists
+    const int32_t rc = regrow(STOP_SEQ, {(size_t)n * sizeof(wrk::StopSeqRow), (size_t)n * WRK_STOP_TAIL_LEN * 4, (size_t)n * 4}, stopseq_rows != nullptr);
+    stopseq_cap = rc == WRK_OK ? n : 0;
+    return rc;
+}
+
+int32_t wrk_frame_common::ensure_queue_seqs(uint32_t slots, uint32_t requests) {
+    if (queue_seq_rows && slots <= queue_seq_slot_cap && requests <= queue_seq_req_cap) return WRK_OK;
+    if (slots < queue_seq_slot_cap) slots = queue_seq_slot_cap;
+    if (requests < queue_seq_req_cap) requests = queue_seq_req_cap;
+    const int32_t rc = regrow(QUEUE_SEQ, {(size_t)requests * sizeof(wrk::StopSeqRow), (size_t)slots * WRK_STOP_TAIL_LEN * 4, (size_t)requests * 4},
+                              queue_seq_rows != nullptr);
+    queue_seq_slot_cap = rc == WRK_OK ? slots : 0;
+    queue_seq_req_cap = rc == WRK_OK ? requests : 0;
+    return rc;
+}
+
 int32_t wrk_frame_common::ensure_logprobs(size_t rows, uint32_t B) {
     if (lp_par && rows <= lp_rows_cap && B <= lp_batch_cap) return WRK_OK;
     if (rows < lp_rows_cap) rows = lp_rows_cap;
@@ -227,6 +248,7 @@ void wrk_frame_common::release_common() {
     history_cap = 0; stop_slot_cap = 0; queue_pool_cap = 0; lp_rows_cap = 0; lp_batch_cap = 0;
     alt_par_cap = alt_mu_cap = 0;
     gram_cap = gram_req_cap = gram_vocab_cap = 0;
+    stopseq_cap = queue_seq_slot_cap = queue_seq_req_cap = 0;
     sample_par_cap = filter_par_cap = pen_cap = stop_cap = stop_vocab_cap = queue_slot_cap = queue_req_cap = queue_turn_cap = queue_entry_cap = 0;
     score.release();
     if (live_host) hipHostFree(live_host);
@@ -362,6 +384,88 @@ static int32_t wrk_stop_sets(wrk_ctx* ctx, const uint32_t* tokens, const uint32_
     return WRK_OK;
 }
 
+// The stop-sequence arrays of a call over n owners ("sequence", "request", "row"), validated (WRK_E_ARG before any launch)
+// into device rows [n], every sequence reversed as wrk::StopSeqRow says, and tails [n][WRK_STOP_TAIL_LEN] (tail_in NULL: empty).  on:
+// the three arrays are given -- the call runs stop-sequence programs, whatever they hold.  has_out: the call passed out_stop_match or
+// stop_tail, which need the arrays
+struct wrk_stopseq_pack {
+    bool on = false;
+    std::vector<wrk::StopSeqRow> rows;
+    std::vector<uint32_t> tails;
+};
+static int32_t wrk_stop_seqs(wrk_ctx* ctx, const uint32_t* tokens, const uint32_t* off, const uint32_t* owners, bool has_out, const uint32_t* tail_in,
+                             uint32_t n, uint32_t V, const char* owner, wrk_stopseq_pack& pk) {
+    const int given = (tokens != nullptr) + (off != nullptr) + (owners != nullptr);
+    WRK_ARG(ctx, given == 0 || given == 3, "stop_seq_tokens, stop_seq_offsets and stop_seq_owners: all three arrays, or none");
+    pk.on = given == 3;
+    WRK_ARG(ctx, pk.on || !has_out, "out_stop_match / stop_tail without the stop-sequence arrays");
+    if (!pk.on) return WRK_OK;
+    pk.rows.assign(n, wrk::StopSeqRow{});
+    pk.tails.assign((size_t)n * WRK_STOP_TAIL_LEN, WRK_STOP_TAIL_EMPTY);
+    WRK_ARG(ctx, owners[0] == 0, "stop_seq_owners[0] = %u: must be 0", owners[0]);
+    WRK_ARG(ctx, off[0] == 0, "stop_seq_offsets[0] = %u: must be 0", off[0]);
+    for (uint32_t i = 0; i < n; ++i) {
+        WRK_ARG(ctx, owners[i + 1] >= owners[i], "stop_seq_owners[%u] = %u decreases", i + 1, owners[i + 1]);
+        const uint32_t cnt = owners[i + 1] - owners[i];
+        WRK_ARG(ctx, cnt <= WRK_MAX_STOP_SEQUENCES, "%s %u: %u stop sequences, at most %u", owner, i, cnt, (uint32_t)WRK_MAX_STOP_SEQUENCES);
+        wrk::StopSeqRow& row = pk.rows[i];
+        row.count = cnt;
+        for (uint32_t k = 0; k < cnt; ++k) {
+            const uint32_t s = owners[i] + k;
+            WRK_ARG(ctx, off[s + 1] >= off[s], "stop_seq_offsets[%u] = %u decreases", s + 1, off[s + 1]);
+            const uint32_t l = off[s + 1] - off[s];
+            WRK_ARG(ctx, l >= 1 && l <= WRK_MAX_STOP_SEQUENCE_LEN, "%s %u: stop sequence %u has %u ids, 1 to %u", owner, i, k, l,
+                    (uint32_t)WRK_MAX_STOP_SEQUENCE_LEN);
+            row.len[k] = l;
+            for (uint32_t j = 0; j < l; ++j) {
+                const uint32_t id = tokens[off[s] + j];
+                WRK_ARG(ctx, id < V, "%s %u: stop sequence %u holds id %u >= vocab %u", owner, i, k, id, V);
+                row.tok[k][l - 1 - j] = id;
+            }
+        }
+    }
+    for (size_t i = 0; tail_in && i < pk.tails.size(); ++i) {
+        const uint32_t t = tail_in[i];
+        WRK_ARG(ctx, t == WRK_STOP_TAIL_EMPTY || t < V, "stop_tail[%zu] = %u: neither EMPTY nor < vocab %u", i, t, V);
+        WRK_ARG(ctx, t != WRK_STOP_TAIL_EMPTY || i % WRK_STOP_TAIL_LEN == 0 || tail_in[i - 1] == WRK_STOP_TAIL_EMPTY,
+                "stop_tail[%zu]: EMPTY after an id (a tail is right aligned)", i);
+        pk.tails[i] = t;
+    }
+    return WRK_OK;
+}
+
+extern "C" int32_t wrk_stop_sequences_advance(wrk_ctx* ctx, uint32_t V, uint32_t n, const uint32_t* seq_tokens, const uint32_t* seq_offsets,
+                                              const uint32_t* seq_owners, const uint32_t* stop_tokens, const uint32_t* stop_offsets, uint32_t* tails,
+                                              const uint32_t* tokens, uint32_t* out_match) {
+    if (!ctx) return WRK_E_ARG;
+    LOCK(ctx);
+    WRK_ARG(ctx, !ctx->capturing_here(), "wrk_stop_sequences_advance is blocking: not inside a capture");
+    WRK_ARG(ctx, seq_tokens && seq_offsets && seq_owners, "stop_seq_tokens, stop_seq_offsets and stop_seq_owners are required");
+    WRK_ARG(ctx, n == 0 || (tails && tokens && out_match), "tails, tokens and out_match are required");
+    wrk_stopseq_pack pk;
+    std::vector<wrk::StopParam> ids;
+    int32_t rc = wrk_stop_seqs(ctx, seq_tokens, seq_offsets, seq_owners, true, tails, n, V, "row", pk);
+    if (rc == WRK_OK) rc = wrk_stop_sets(ctx, stop_tokens, stop_offsets, n, V, "row", ids);
+    if (rc != WRK_OK || n == 0) return rc;
+    for (uint32_t r = 0; r < n; ++r) WRK_ARG(ctx, tokens[r] < V, "token %u: id %u >= vocab %u", r, tokens[r], V);
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    wrk_dev_arena dev;
+    const size_t o_rows = dev.add((size_t)n * sizeof(wrk::StopSeqRow)), o_ids = dev.add((size_t)n * sizeof(wrk::StopParam)),
+                 o_tail = dev.add((size_t)n * WRK_STOP_TAIL_LEN * 4), o_tok = dev.add((size_t)n * 4), o_match = dev.add((size_t)n * 4);
+    WRK_HIP(ctx, dev.alloc());
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_rows), pk.rows.data(), (size_t)n * sizeof(wrk::StopSeqRow), hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_ids), ids.data(), (size_t)n * sizeof(wrk::StopParam), hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_tail), pk.tails.data(), pk.tails.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_tok), tokens, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    wrk::stop_seq_rows(ctx->stream, n, dev.at<wrk::StopSeqRow>(o_rows), dev.at<wrk::StopParam>(o_ids), dev.at<uint32_t>(o_tail), dev.at<uint32_t>(o_tok),
+                       dev.at<uint32_t>(o_match));
+    WRK_LAUNCH_CHECK(ctx);
+    WRK_HIP(ctx, hipMemcpyAsync(tails, dev.at<char>(o_tail), pk.tails.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(out_match, dev.at<char>(o_match), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
 // the log-prob fields of an options struct validated (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch); sets kind.logprobs
 static int32_t wrk_logprob_check(wrk_ctx* ctx, const wrk_logprob_call& lp, uint32_t V, wrk_step_kind& kind) {
     kind.logprobs = lp.on();
@@ -440,14 +544,23 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
 // ------------------------------------------------------------------ stop tokens (wrk_stop.hip)
 // after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): stop buffers of
 // the frame, the B rows, zero just_ended, live = B
-static int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t B, const wrk::StopParam* rows) {
+// seq (a call with stop sequences, else nullptr): also their buffers, rows and tails [b0, b0 + B) of the pack, match words NONE
+static int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t b0, uint32_t B, const wrk::StopParam* rows,
+                                const wrk_stopseq_pack* seq) {
     wrk_ctx* ctx = f.ctx;
     int32_t rc = f.ensure_stop(B, st->num_layer, st->head_size, st->num_emb, f.facts().num_vocab);
+    if (rc == WRK_OK && seq) rc = f.ensure_stop_seqs(B);
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> flags(f.stop_cap + 1, 0u);      // just_ended = 0, then the live count
     flags[f.stop_cap] = B;
     rc = wrk_buf_write_raw(ctx, f.stop_par, rows, (size_t)B * sizeof(wrk::StopParam));
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.stop_flags, flags.data(), flags.size() * 4);
+    if (rc == WRK_OK && seq) {
+        const std::vector<uint32_t> none(B, WRK_STOP_MATCH_NONE);
+        rc = wrk_buf_write_raw(ctx, f.stopseq_rows, seq->rows.data() + b0, (size_t)B * sizeof(wrk::StopSeqRow));
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.stopseq_tail, seq->tails.data() + (size_t)b0 * WRK_STOP_TAIL_LEN, (size_t)B * WRK_STOP_TAIL_LEN * 4);
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.stopseq_match, none.data(), (size_t)B * 4);
+    }
     if (rc != WRK_OK) return rc;
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
@@ -478,6 +591,8 @@ struct wrk_queue_pack {
     float* mu_out = nullptr;    // Mirostat: the options' mirostat_mu, or nullptr
     std::vector<uint32_t> gram; // constrained: [R] the automaton state every request starts in
     uint32_t* gram_out = nullptr;   // the options' grammar_state, or nullptr
+    wrk_stopseq_pack seq;       // stop sequences: [R] the requests' rows (the tails: every slot starts empty)
+    uint32_t* match_out = nullptr;  // the options' out_stop_match, or nullptr
 };
 
 static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
@@ -499,9 +614,13 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     std::vector<wrk::StopParam> stops;
     wrk_pick_params req;
     if (rc == WRK_OK) rc = wrk_stop_sets(ctx, opt->stop_tokens, opt->stop_offsets, R, V, "request", stops);
+    if (rc == WRK_OK)
+        rc = wrk_stop_seqs(ctx, opt->stop_seq_tokens, opt->stop_seq_offsets, opt->stop_seq_owners, opt->out_stop_match != nullptr, nullptr, R, V, "request", pk.seq);
     if (rc == WRK_OK) rc = wrk_pick_pack(ctx, wrk_pick_of(*opt), R, B, V, req, pk.kind);
     if (rc == WRK_OK) rc = wrk_logprob_check(ctx, pk.lp, V, pk.kind);
     if (rc != WRK_OK) return rc;
+    pk.kind.stop_seqs = pk.seq.on;
+    pk.match_out = opt->out_stop_match;
     const wrk_step_kind kind = pk.kind;
     pk.R = R; pk.max_steps = opt->max_steps; pk.poll_steps = opt->poll_steps;
     pk.reqs.assign(R, wrk::QueueReq{});
@@ -606,7 +725,9 @@ static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) 
     return wrk::QueueBufs{f.queue_slots, f.queue_reqs, f.queue_pool, f.queue_log, f.queue_ctl, f.queue_started,
                           kind.sampled() ? f.sample_par : nullptr, kind.penalized ? f.pen_par : nullptr, kind.filtered() ? f.filter_par : nullptr,
                           kind.alt() ? f.alt_par : nullptr, kind.mirostat() ? f.alt_mu : nullptr,
-                          kind.constrained ? f.gram_state : nullptr, kind.constrained ? f.gram_req : nullptr};
+                          kind.constrained ? f.gram_state : nullptr, kind.constrained ? f.gram_req : nullptr,
+                          kind.stop_seqs ? f.queue_seq_rows : nullptr, kind.stop_seqs ? f.queue_seq_tail : nullptr,
+                          kind.stop_seqs ? f.queue_seq_match : nullptr};
 }
 
 static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f) {
@@ -625,6 +746,7 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     const uint32_t V = f.facts().num_vocab;
     int32_t rc = f.ensure_queue(B, pk.R, pk.pool.size());
     if (rc == WRK_OK && pk.kind.pool()) rc = f.ensure_queue_states(B, pk.R);
+    if (rc == WRK_OK && pk.kind.stop_seqs) rc = f.ensure_queue_seqs(B, pk.R);
     if (rc != WRK_OK) return rc;
     const uint32_t nstart = B < pk.R ? B : pk.R;
     std::vector<wrk::QueueSlot> slots(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
@@ -649,6 +771,12 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     if (rc == WRK_OK && pk.kind.constrained) {
         if (!f.gram_req || pk.R > f.gram_req_cap) return wrk_fail(ctx, WRK_E_ARG, "grammar states are not prepared");
         rc = wrk_buf_write_raw(ctx, f.gram_req, pk.gram.data(), (size_t)pk.R * 4);
+    }
+    if (rc == WRK_OK && pk.kind.stop_seqs) {     // every slot's tail starts empty, no request has a match yet
+        const std::vector<uint32_t> tails((size_t)B * WRK_STOP_TAIL_LEN, WRK_STOP_TAIL_EMPTY), none(pk.R, WRK_STOP_MATCH_NONE);
+        rc = wrk_buf_write_raw(ctx, f.queue_seq_rows, pk.seq.rows.data(), (size_t)pk.R * sizeof(wrk::StopSeqRow));
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_seq_tail, tails.data(), tails.size() * 4);
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_seq_match, none.data(), (size_t)pk.R * 4);
     }
     if (rc == WRK_OK && pk.kind.pool()) {
         // the turnover list of "step -1": the slots that start at step 0, nothing to save
@@ -718,6 +846,7 @@ static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind
     const wrk::FrameIo& io = f.io();
     const uint32_t V = f.facts().num_vocab;
     if (!f.queue_ctl || B > f.queue_slot_cap || b0 != 0 || B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+    if (kind.stop_seqs && (!f.queue_seq_rows || B > f.queue_seq_slot_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "stop-sequence buffers are not prepared");
     if (kind.pool() && (!f.queue_state_ctl || B > f.queue_turn_cap || ((size_t)(st->head_size + 2) * st->num_emb) % 4 != 0))
         return wrk_fail(f.ctx, WRK_E_ARG, "state pool buffers are not prepared");
     const int32_t rc = enqueue_draw_updates(f, B, kind);
@@ -762,6 +891,9 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         WRK_HIP(ctx, hipMemcpyAsync(gram_req.data(), f.gram_req, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
         WRK_HIP(ctx, hipMemcpyAsync(gram_slot.data(), f.gram_state, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
+    // stop sequences: a request's match word is written by the step that ends it with reason 1, and by nothing else
+    std::vector<uint32_t> match(pk.match_out ? pk.R : 0);
+    if (pk.match_out) WRK_HIP(ctx, hipMemcpyAsync(match.data(), f.queue_seq_match, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     size_t o = 0;
     for (uint32_t r = 0; r < pk.R; ++r) {
@@ -775,6 +907,7 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         out->lengths[r] = g.length; out->reasons[r] = g.reason; out->slots[r] = g.slot; out->start_steps[r] = g.start_step;
         if (pk.mu_out && g.reason != 0) pk.mu_out[r] = g.reason == 3 ? mu_slot[g.slot].mu : mu_req[r];
         if (pk.gram_out && g.reason != 0) pk.gram_out[r] = g.reason == 3 ? gram_slot[g.slot] : gram_req[r];
+        if (pk.match_out) pk.match_out[r] = g.reason == 1 ? match[r] : WRK_STOP_MATCH_NONE;
         // the step that gave the request reason 1 or 2 also wrote its state to its entry (queue_turnover)
         if (pk.saved_out) pk.saved_out[r] = pk.save[r] != wrk::QUEUE_NO_ENTRY && (g.reason == 1 || g.reason == 2);
         for (uint32_t j = 0; j < g.length; ++j) {
@@ -808,7 +941,13 @@ static int32_t enqueue_stop_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind 
     if (!f.stop_par || B > f.stop_cap || b0 + B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
     const int32_t rc = enqueue_draw_updates(f, B, kind);
     if (rc != WRK_OK) return rc;
-    wrk::advance_stop(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(), B);
+    if (kind.stop_seqs) {
+        if (!f.stopseq_rows || B > f.stopseq_cap) return wrk_fail(f.ctx, WRK_E_ARG, "stop-sequence buffers are not prepared");
+        wrk::advance_stop_seq(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(),
+                              wrk::StopSeqBufs{f.stopseq_rows, f.stopseq_tail, f.stopseq_match}, B);
+    } else {
+        wrk::advance_stop(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(), B);
+    }
     wrk::stop_snapshot(q, stop_geom(f, st, b0), B, f.ctx->num_cu);
     return WRK_OK;
 }
@@ -870,19 +1009,20 @@ static constexpr uint32_t WRK_STOP_POLL_DEFAULT = 16;
 // Part 1 of a decode loop on lane `ln`: the frame, the upload of tokens / cursors / pick rows of its sequences, the buffers of the tail
 // (stop: the call's stop rows, queue: its tables -- whichever kind.tail names) and, unless WRK_NO_GRAPH=1, the cached step program.
 // Every ensure_* comes before the look-up: growing a buffer drops the programs.  One program per (state, first sequence, B, the runner's
-// key bits, step kind): the analogue of the reference's cached RnnJob for a repeated RnnInfo
+// key bits, step kind -- key() in the mode word, key2() in the second): the analogue of the reference's cached RnnJob for a repeated RnnInfo
 static int32_t lane_prepare(wrk_lane& ln, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t steps, uint32_t mode, wrk_step_kind kind,
-                            const wrk_pick_params& rows, const wrk::StopParam* stop, const wrk_queue_pack* queue, uint32_t num_top) {
+                            const wrk_pick_params& rows, const wrk::StopParam* stop, const wrk_stopseq_pack* seq, const wrk_queue_pack* queue,
+                            uint32_t num_top) {
     wrk_frame_common& f = *ln.frame;
     const uint32_t b0 = ln.b0, B = ln.nb;
     int32_t rc = f.ensure_frame(B, mode);
     if (rc == WRK_OK) rc = wrk_decode_prepare(f, first_tokens, b0, B, steps, rows);
-    if (rc == WRK_OK && kind.tail == wrk_step_kind::STOP) rc = wrk_stop_prepare(f, st, B, stop + b0);
+    if (rc == WRK_OK && kind.tail == wrk_step_kind::STOP) rc = wrk_stop_prepare(f, st, b0, B, stop + b0, seq);
     if (rc == WRK_OK && kind.queue()) rc = wrk_queue_prepare(f, st, B, *queue);
     if (rc == WRK_OK && kind.logprobs) rc = wrk_logprob_prepare(f, B, steps, num_top);
     ln.prog = nullptr;
     if (rc != WRK_OK || wrk_no_graph()) return rc;
-    const wrk_frame_common::GraphKey key{st->uid, B | (b0 << 16), f.key_bits(B, mode) | kind.key()};
+    const wrk_frame_common::GraphKey key{st->uid, B | (b0 << 16), f.key_bits(B, mode) | kind.key(), 0u, kind.key2()};
     return wrk_cached_program(f.ctx, f.graphs, key, [&] { return f.enqueue_step(st, b0, B, mode, kind); }, &ln.prog);
 }
 
@@ -1029,12 +1169,19 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
     int32_t rc = wrk_pick_pack(ctx, pick, B, B, V, rows, kind);
     if (rc == WRK_OK) rc = wrk_logprob_check(ctx, lp, V, kind);
     if (rc == WRK_OK && stop) rc = wrk_stop_sets(ctx, stop->opt->stop_tokens, stop->opt->stop_offsets, B, V, "sequence", stop_rows);
+    wrk_stopseq_pack seq;                       // generate_stop with stop sequences: their rows and the tails the sequences start with
+    if (rc == WRK_OK && stop) {
+        const wrk_generate_options& o = *stop->opt;
+        rc = wrk_stop_seqs(ctx, o.stop_seq_tokens, o.stop_seq_offsets, o.stop_seq_owners, o.out_stop_match || o.stop_tail, o.stop_tail, B, V, "sequence", seq);
+        kind.stop_seqs = seq.on;
+    }
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), first_tokens, B);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     if (stop) {
         *stop->steps_run = 0;
         for (uint32_t b = 0; b < B; ++b) stop->out_lengths[b] = 0;
+        for (uint32_t b = 0; b < B && stop->opt->out_stop_match; ++b) stop->opt->out_stop_match[b] = WRK_STOP_MATCH_NONE;
     }
     if (steps == 0) return WRK_OK;
     // mode: bits 0-7 = 0 op-by-op / 1 fused; bits 8-15 = number of concurrent pipelines the sequences are dealt over (0, 1: one)
@@ -1052,7 +1199,7 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
         L[g].b0 = (uint32_t)((uint64_t)B * g / groups);
         L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
         // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
-        rc = lane_prepare(L[g], st, first_tokens, steps, mode, kind, rows, stop_rows.data(), nullptr, lp.num_top);
+        rc = lane_prepare(L[g], st, first_tokens, steps, mode, kind, rows, stop_rows.data(), seq.on ? &seq : nullptr, nullptr, lp.num_top);
         if (rc != WRK_OK) return rc;
     }
     const wrk_stop_run run{stop ? stop->opt->poll_steps : 0u, stop ? stop->out_lengths : nullptr, stop ? stop->steps_run : nullptr};
@@ -1067,6 +1214,14 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
     if (kind.constrained && pick.grammar_state)     // every lane's words hold the states after the draws that counted
         for (const wrk_lane& ln : L)
             WRK_HIP(ctx, hipMemcpy(pick.grammar_state + ln.b0, ln.frame->gram_state, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
+    if (kind.stop_seqs)                             // and the match words and the tails, frozen with the sequences that ended
+        for (const wrk_lane& ln : L) {
+            if (stop->opt->out_stop_match)
+                WRK_HIP(ctx, hipMemcpy(stop->opt->out_stop_match + ln.b0, ln.frame->stopseq_match, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
+            if (stop->opt->stop_tail)
+                WRK_HIP(ctx, hipMemcpy(stop->opt->stop_tail + (size_t)ln.b0 * WRK_STOP_TAIL_LEN, ln.frame->stopseq_tail,
+                                       (size_t)ln.nb * WRK_STOP_TAIL_LEN * 4, hipMemcpyDeviceToHost));
+        }
     return m->after_loop(groups);
 }
 
@@ -1086,7 +1241,7 @@ int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, 
     m->before_loop();
     std::vector<wrk_lane> L{{nullptr, 0, B, nullptr}};      // one lane: a queue shared by several streams would need cross-stream atomics
     rc = m->lane(0, 1, &L[0].frame);
-    if (rc == WRK_OK) rc = lane_prepare(L[0], st, pk.first_tokens.data(), pk.max_steps, mode, pk.kind, pk.rows, nullptr, &pk, pk.lp.num_top);
+    if (rc == WRK_OK) rc = lane_prepare(L[0], st, pk.first_tokens.data(), pk.max_steps, mode, pk.kind, pk.rows, nullptr, nullptr, &pk, pk.lp.num_top);
     if (rc != WRK_OK) return rc;
     uint32_t steps_run = 0;
     rc = wrk_run_lanes(ctx, L, st, B, pk.max_steps, mode, pk.kind, nullptr, nullptr, elapsed_ms, wrk_stop_run{pk.poll_steps, nullptr, &steps_run}, wrk_logprob_call{});

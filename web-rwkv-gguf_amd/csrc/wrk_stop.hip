@@ -6,12 +6,16 @@
 //                   history / tokens, marks a sequence that has just drawn a stop id, and moves the step counter last
 //   stop_snapshot   grid (layer x slice + logits slices, sequence): every workgroup reads just_ended[b] and leaves when it is 0
 //   stop_restore    once after the loop, outside the captured program: snapshot -> state and logits of the sequences that are done
+//   advance_stop_seq   advance_stop's place in a stop program with stop sequences: the same, and the sequence's draw also
+//                   goes through the matcher of wrk_stopseq_dev.h, which moves its tail and, where it ends, leaves its match word
+//   stop_seq_rows   the matcher alone on n rows, behind wrk_stop_sequences_advance
 //
 // just_ended[b] is written by EVERY advance_stop launch for every sequence (1 when the sequence ended in this step, else 0), so the flag
 // a snapshot launch reads was written by the advance_stop launch in front of it in the same stream; nothing has to clear it.
 // Plain vector stores only; no atomics; no kernel waits on another.
 #include "wrk_device.h"
 #include "wrk_runner.h"
+#include "wrk_stopseq_dev.h"
 
 namespace wrk {
 
@@ -45,6 +49,52 @@ __global__ void __launch_bounds__(STOP_THREADS) advance_stop_kernel(const uint32
         if (n_ended) *live = *live - (uint32_t)n_ended;
         *counter = step + 1;
     }
+}
+
+// advance_stop_kernel for stop programs with stop sequences: the same workgroup, ownership and ordering.  The draw of a
+// sequence that is still running goes through stop_seq_step (wrk_stopseq_dev.h) with its stop set and its StopSeqRow; the tail takes it
+// in, and the step that ends the sequence also writes its match word.  A finished sequence's tail and match word are never touched again
+__global__ void __launch_bounds__(STOP_THREADS) advance_stop_seq_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                                        uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
+                                                                        StopParam* __restrict__ par, uint32_t* __restrict__ just_ended,
+                                                                        uint32_t* __restrict__ live, const StopSeqBufs Q, uint32_t b) {
+    const uint32_t step = *counter;
+    const uint32_t i = threadIdx.x;
+    int ended = 0;
+    if (i < b) {
+        StopParam* p = par + i;
+        if (p->done) {
+            history[(size_t)step * b + i] = p->end_token;
+        } else {
+            const uint32_t y = drawn[i];
+            tokens[i] = y;
+            history[(size_t)step * b + i] = y;
+            uint32_t* tp = Q.tail + (size_t)i * STOP_TAIL;
+            StopTail tail = stop_tail_load(tp);
+            const uint32_t match = stop_seq_step(tail, y, Q.rows + i, p->ids, p->count);
+            stop_tail_store(tp, tail);
+            ended = match != WRK_STOP_MATCH_NONE;
+            if (ended) { p->done = 1; p->length = step + 1; p->end_token = y; Q.match[i] = match; }
+        }
+        just_ended[i] = (uint32_t)ended;
+    }
+    const int n_ended = __syncthreads_count(ended);     // also orders every read of *counter before its update
+    if (i == 0) {
+        if (n_ended) *live = *live - (uint32_t)n_ended;
+        *counter = step + 1;
+    }
+}
+
+// wrk_stop_sequences_advance: one owner per thread, any number of rows
+__global__ void __launch_bounds__(STOP_THREADS) stop_seq_rows_kernel(uint32_t n, const StopSeqRow* __restrict__ rows, const StopParam* __restrict__ ids,
+                                                                     uint32_t* __restrict__ tail, const uint32_t* __restrict__ tokens,
+                                                                     uint32_t* __restrict__ match) {
+    const uint32_t r = blockIdx.x * STOP_THREADS + threadIdx.x;
+    if (r >= n) return;
+    uint32_t* tp = tail + (size_t)r * STOP_TAIL;
+    StopTail t = stop_tail_load(tp);
+    match[r] = stop_seq_step(t, tokens[r], rows + r, ids ? ids[r].ids : nullptr, ids ? ids[r].count : 0u);
+    stop_tail_store(tp, t);
 }
 
 // 16-byte copies of n floats (n % 4 == 0, both 16-byte aligned), or scalar ones; workgroup `part` of `parts`
@@ -98,6 +148,16 @@ __global__ void __launch_bounds__(STOP_THREADS) stop_copy_kernel(const StopCopyA
 void advance_stop(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, StopParam* par,
                   uint32_t* just_ended, uint32_t* live, uint32_t b) {
     advance_stop_kernel<<<1, STOP_THREADS, 0, s>>>(drawn, tokens, history, counter, par, just_ended, live, b);
+}
+
+void advance_stop_seq(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, StopParam* par,
+                      uint32_t* just_ended, uint32_t* live, const StopSeqBufs& q, uint32_t b) {
+    advance_stop_seq_kernel<<<1, STOP_THREADS, 0, s>>>(drawn, tokens, history, counter, par, just_ended, live, q, b);
+}
+
+void stop_seq_rows(hipStream_t s, uint32_t n, const StopSeqRow* rows, const StopParam* ids, uint32_t* tail, const uint32_t* tokens, uint32_t* match) {
+    if (n == 0) return;
+    stop_seq_rows_kernel<<<(n + STOP_THREADS - 1) / STOP_THREADS, STOP_THREADS, 0, s>>>(n, rows, ids, tail, tokens, match);
 }
 
 // slices of a layer's slot: layers * slices workgroups come to about two per CU, so that one ending sequence's copy (13 MB at the

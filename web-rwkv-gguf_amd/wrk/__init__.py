@@ -78,6 +78,8 @@ class GenerateOptions(C.Structure):
                 ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
                 ("grammar", _P), ("grammar_state", _u32p),
+                ("stop_seq_tokens", _u32p), ("stop_seq_offsets", _u32p), ("stop_seq_owners", _u32p), ("out_stop_match", _u32p),
+                ("stop_tail", _u32p),
                 ("mirostat_tau", _f32p), ("mirostat_eta", _f32p), ("mirostat_mu", _f32p), ("typical_p", _f32p),
                 ("top_k", _u32p), ("min_p", _f32p)]
 
@@ -91,6 +93,7 @@ class QueueOptions(C.Structure):
                 ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
                 ("grammar", _P), ("grammar_state", _u32p),
+                ("stop_seq_tokens", _u32p), ("stop_seq_offsets", _u32p), ("stop_seq_owners", _u32p), ("out_stop_match", _u32p),
                 ("mirostat_tau", _f32p), ("mirostat_eta", _f32p), ("mirostat_mu", _f32p), ("typical_p", _f32p),
                 ("top_k", _u32p), ("min_p", _f32p)]
 
@@ -108,6 +111,12 @@ class QueuePool(C.Structure):
 
 MAX_STOP_TOKENS = 16        # WRK_MAX_STOP_TOKENS
 MAX_TOP_LOGPROBS = 20       # WRK_MAX_TOP_LOGPROBS
+MAX_STOP_SEQUENCES = 8      # WRK_MAX_STOP_SEQUENCES
+MAX_STOP_SEQUENCE_LEN = 8   # WRK_MAX_STOP_SEQUENCE_LEN
+STOP_TAIL_LEN = 7           # WRK_STOP_TAIL_LEN
+STOP_TAIL_EMPTY = 0xFFFFFFFF    # WRK_STOP_TAIL_EMPTY
+STOP_MATCH_NONE = 0xFFFFFFFF    # WRK_STOP_MATCH_NONE
+STOP_MATCH_TOKEN = 0xFFFFFFFE   # WRK_STOP_MATCH_TOKEN
 QUEUE_NO_ENTRY = 0xFFFFFFFF     # WRK_QUEUE_NO_ENTRY
 GRAMMAR_REJECT = 0xFFFF         # WRK_GRAMMAR_REJECT
 MAX_TOKEN_CLASSES = 8192        # WRK_MAX_TOKEN_CLASSES
@@ -212,6 +221,7 @@ HIP_SYMBOLS = {
     "wrk_grammar_destroy": (C.c_int32, [_P]),
     "wrk_constrain_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _u32p]),
     "wrk_grammar_advance": (C.c_int32, [_P, _P, _u32p, _u32p, C.c_uint32]),
+    "wrk_stop_sequences_advance": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, _u32p, _u32p, _u32p]),
     "wrk_v7_generate_stop": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(GenerateOptions), _u32p, _u32p, _f32p, _u32p,
                                          _f32p, C.c_uint32]),
     "wrk_v6_generate_stop": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(GenerateOptions), _u32p, _u32p, _f32p, _u32p,
@@ -355,6 +365,68 @@ def _stop_csr(stop, n: int, owners: str):
     off[1:] = np.cumsum([len(x) for x in sets])
     ids = _u32(np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in sets]) if n else [])
     return (ids if ids.size else np.zeros(1, np.uint32)), off
+
+
+def _stop_seq_csr(stop_sequences, n: int, owners: str):
+    """Stop sequences as the ABI's CSR of a CSR, (ids, offsets [S + 1], owners [n + 1]): one list of id lists for all n owners, or one
+    such list per owner.  Told apart by depth: a list whose entries hold ids is one owner's list.  ValueError on a wrong owner count, an
+    empty sequence, one longer than MAX_STOP_SEQUENCE_LEN, or more than MAX_STOP_SEQUENCES for an owner; the ids are checked against
+    the vocabulary by the call."""
+    def is_seq(x):
+        return isinstance(x, (list, tuple, np.ndarray))
+    top = list(stop_sequences)
+    if any(not is_seq(x) for x in top):
+        raise ValueError("stop_sequences: a list of id lists, or one such list per " + owners[:-1])
+    per_owner = any(is_seq(y) for x in top for y in x) or (len(top) == n and all(len(x) == 0 for x in top) and n > 0)
+    lists = [list(x) for x in top] if per_owner else [top] * n
+    if len(lists) != n:
+        raise ValueError(f"{len(lists)} lists of stop sequences for {n} {owners}")
+    seqs, own = [], np.zeros(n + 1, np.uint32)
+    for b, lst in enumerate(lists):
+        if len(lst) > MAX_STOP_SEQUENCES:
+            raise ValueError(f"{len(lst)} stop sequences, at most {MAX_STOP_SEQUENCES}")
+        for q in lst:
+            q = np.asarray(q, np.int64).reshape(-1)
+            if not 1 <= q.size <= MAX_STOP_SEQUENCE_LEN:
+                raise ValueError(f"a stop sequence of {q.size} ids: 1 to {MAX_STOP_SEQUENCE_LEN}")
+            if q.min() < 0 or q.max() > 0xFFFFFFFF:
+                raise ValueError("stop sequence ids must fit 32 bits")
+            seqs.append(q)
+        own[b + 1] = len(seqs)
+    off = np.zeros(len(seqs) + 1, np.uint32)
+    off[1:] = np.cumsum([q.size for q in seqs])
+    ids = _u32(np.concatenate(seqs)) if seqs else np.zeros(1, np.uint32)
+    return ids, off, own
+
+
+def _stop_tails(stop_tail, n: int) -> np.ndarray:
+    """A writable [n, STOP_TAIL_LEN] u32 copy of `stop_tail` (None: all EMPTY); a shorter row is right aligned."""
+    out = np.full((n, STOP_TAIL_LEN), STOP_TAIL_EMPTY, np.uint32)
+    if stop_tail is None:
+        return out
+    rows = list(stop_tail)
+    if len(rows) != n:
+        raise ValueError(f"{len(rows)} tails for {n} sequences")
+    for b, row in enumerate(rows):
+        row = np.asarray(row, np.int64).reshape(-1)
+        if row.size > STOP_TAIL_LEN:
+            raise ValueError(f"a tail of {row.size} entries, at most {STOP_TAIL_LEN}")
+        if row.size:
+            out[b, STOP_TAIL_LEN - row.size:] = row.astype(np.uint32)
+    return out
+
+
+def _fill_stop_sequences(opt, n: int, keep: list, stop_sequences, owners: str):
+    """The stop-sequence fields of a GenerateOptions or QueueOptions for n owners; returns the out_stop_match array [n], or None
+    without stop sequences.  The arrays go into `keep`."""
+    if stop_sequences is None:
+        return None
+    ids, off, own = _stop_seq_csr(stop_sequences, n, owners)
+    match = np.full(max(n, 1), STOP_MATCH_NONE, np.uint32)
+    keep.extend([ids, off, own, match])
+    opt.stop_seq_tokens, opt.stop_seq_offsets, opt.stop_seq_owners = _ptr(ids, _u32p), _ptr(off, _u32p), _ptr(own, _u32p)
+    opt.out_stop_match = _ptr(match, _u32p)
+    return match
 
 
 def _fill_grammar(opt, n: int, keep: list, grammar, grammar_state):
@@ -639,6 +711,24 @@ class Context:
         st = _per_row(states, n, np.uint32)
         self.check(hip.wrk_constrain_logits(self.h, buf.h, V, stride, n, grammar.h, _ptr(st, _u32p)))
         return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
+
+    def stop_sequences_advance(self, tails, tokens, stop_sequences, stop=None, num_vocab: Optional[int] = None):
+        """One counted draw of the stop-sequence matcher on the device (wrk_stop_sequences_advance) for n rows: row r has the
+        tail tails[r] (STOP_TAIL_LEN entries, oldest first, STOP_TAIL_EMPTY where there is none), the drawn token tokens[r], the stop
+        sequences `stop_sequences` (one list of id lists for all rows, or one per row) and optionally the stop ids `stop` (as
+        `generate_stop`).  Returns (match [n], tails [n, STOP_TAIL_LEN]): STOP_MATCH_NONE, STOP_MATCH_TOKEN or the index of the matching
+        sequence (the longest wins, then a stop id, then the lower index), and the tails with the token taken in.  num_vocab: the bound the
+        ids are checked against (None: any id below STOP_TAIL_EMPTY)."""
+        tk = _u32(tokens).reshape(-1)
+        n = tk.size
+        tl = _stop_tails(tails, n)
+        ids, off, own = _stop_seq_csr(stop_sequences, n, "rows")
+        sid, soff = (None, None) if stop is None else _stop_csr(stop, n, "rows")
+        match = np.zeros(max(n, 1), np.uint32)
+        self.check(hip.wrk_stop_sequences_advance(self.h, 0xFFFFFFFF if num_vocab is None else int(num_vocab), n, _ptr(ids, _u32p), _ptr(off, _u32p),
+                                                  _ptr(own, _u32p), None if sid is None else _ptr(sid, _u32p),
+                                                  None if soff is None else _ptr(soff, _u32p), _ptr(tl, _u32p), _ptr(tk, _u32p), _ptr(match, _u32p)))
+        return match[:n], tl
 
 
 class Grammar:
@@ -1169,6 +1259,10 @@ class Runtime:
         # the automaton states after the last generate_* call with `grammar`, per sequence (generate_queue: per request); None after
         # a call without
         self.last_grammar_state = None
+        # what ended each sequence (generate_queue: each request) of the last call with `stop_sequences`, and after generate_stop the
+        # tails [B, STOP_TAIL_LEN] to pass to the next call of a session; None after a call without
+        self.last_stop_match = None
+        self.last_stop_tail = None
 
     def token_bytes(self, num_batch: int = 1) -> int:
         if self.model6:
@@ -1288,6 +1382,7 @@ class Runtime:
         fn, mdl = self._entry("generate_" + name)
         self.last_logprobs = None
         self.last_grammar_state = None
+        self.last_stop_match = self.last_stop_tail = None
         self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), B, steps, *rows, _ptr(out, _u32p),
                           _ptr(logits, _f32p) if want_logits else None, C.byref(ms), self._mode(mode, groups)))
         return (out, ms.value, logits) if want_logits else (out, ms.value)
@@ -1369,6 +1464,7 @@ class Runtime:
         out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits, logprobs)
         self.last_mirostat_mu = mu
         self.last_grammar_state = gs
+        self.last_stop_match = self.last_stop_tail = None
         return (out, ms, logits) if want_logits else (out, ms)
 
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
@@ -1394,7 +1490,7 @@ class Runtime:
     def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
                       poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
-                      grammar: "Grammar" = None, grammar_state=None):
+                      grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, stop_tail=None):
         """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
         at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
         MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
@@ -1406,10 +1502,24 @@ class Runtime:
         mirostat / mirostat_mu / typical_p: as `generate_sample`; `last_mirostat_mu[b]` has seen exactly lengths[b] draws, the stop
         token's included.
         grammar / grammar_state: as `generate_greedy`; `last_grammar_state[b]` has seen exactly lengths[b] draws, the stop token's
-        included: the state freezes with the sequence."""
+        included: the state freezes with the sequence.
+        stop_sequences (None: off): multi-token stops -- one list of id lists for all sequences, or one such list per
+        sequence, at most MAX_STOP_SEQUENCES of 1 .. MAX_STOP_SEQUENCE_LEN ids each (a stop string: one entry per way it tokenizes).  A
+        sequence also ends at the draw that completes one of them, with everything frozen as for a stop id; `last_stop_match[b]` is
+        STOP_MATCH_NONE, STOP_MATCH_TOKEN or the index of the sequence that matched (the caller trims its length, or 1: the device trims
+        nothing).  stop_tail ([B, STOP_TAIL_LEN] from an earlier call's `last_stop_tail`; None: empty): the last draws of the session so
+        far, so that a stop sequence that straddles two calls still ends the reply; `last_stop_tail` holds the tails after this call.
+        Both are None after a call without stop_sequences, which runs exactly the step programs it ran before."""
         ft = _u32(first_tokens)
         ids, off = _stop_csr(stop, ft.size, "sequences")
         opt, keep = GenerateOptions(), []
+        if stop_sequences is None and stop_tail is not None:
+            raise ValueError("stop_tail without stop_sequences")
+        self.last_stop_match = _fill_stop_sequences(opt, ft.size, keep, stop_sequences, "sequences")
+        self.last_stop_tail = None
+        if stop_sequences is not None:
+            self.last_stop_tail = _stop_tails(stop_tail, ft.size)
+            opt.stop_tail = _ptr(self.last_stop_tail, _u32p)
         self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                                            mirostat, mirostat_mu, typical_p)
         self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
@@ -1422,7 +1532,7 @@ class Runtime:
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
                        mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None,
-                       mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None):
+                       mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1445,7 +1555,11 @@ class Runtime:
         grammar / grammar_state (a scalar or one state per request; None: 0): one `Grammar` for the call; request r starts in
         grammar_state[r] when it is dispatched, whatever its slot held, and only its reply draws move the state (the steps that feed
         prompt tokens do not); `last_grammar_state[r]` is its state after its reply draws (the start state for reason 0).  Requests
-        that need different grammars use disjoint state sets of one automaton; the state is not part of a pool entry."""
+        that need different grammars use disjoint state sets of one automaton; the state is not part of a pool entry.
+        stop_sequences (None: off): as `generate_stop`, one list of id lists for all requests or one such list per request.  Only reply
+        draws are matched: a prompt that is, or ends in the beginning of, a stop sequence does not end its reply, and a refilled slot
+        starts with an empty tail.  A match ends the request with reason 1; `last_stop_match[r]` says what ended request r
+        (STOP_MATCH_NONE for reasons 0, 2 and 3).  None after a call without stop_sequences."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1464,6 +1578,8 @@ class Runtime:
         self.last_mirostat_mu = _fill_pick(opt, R, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                                            mirostat, mirostat_mu, typical_p)
         self.last_grammar_state = _fill_grammar(opt, R, keep, grammar, grammar_state)
+        match = _fill_stop_sequences(opt, R, keep, stop_sequences, "requests")
+        self.last_stop_match = self.last_stop_tail = None
         if init_state is not None:
             opt.init_state = init_state.h
         opt.poll_steps = poll_steps
@@ -1496,6 +1612,8 @@ class Runtime:
             self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qp)))
             self.last_queue_saved = [bool(x) for x in saved[:R]]
         self.last_queue_ms = ms.value
+        if match is not None:
+            self.last_stop_match = match[:R]
         off = np.concatenate([[0], np.cumsum(mn)]).astype(np.int64)
         if logprobs is not None:
             n = int(logprobs)
