@@ -318,7 +318,9 @@ int32_t wrk_v7_generate_greedy(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* 
 /* examples/chat.rs:150-190 Sampler::sample on the device, one token per row of f32 logits [num_rows][row_stride] (first num_vocab used):
  * softmax, nucleus = the tokens (by probability descending, ties by index ascending) whose preceding mass is <= top_p, weights p^(1/T)
  * inside it, then the first token whose cumulative weight reaches u * total, u = SplitMix64((seed << 32) | step) >> 40, times 2^-24.
- * temperature or top_p == 0: the first index of the maximum (greedy); NaN or negative: WRK_E_ARG; num_vocab > 2^20: WRK_E_UNSUPPORTED.
+ * temperature or top_p == 0: the first index of the maximum (greedy); NaN or negative, or a temperature of +inf: WRK_E_ARG (every
+ * entry point that takes a temperature, the decode loops included; top_p may be +inf: no cut); num_vocab > 2^20: WRK_E_UNSUPPORTED.
+ * A logit of NaN counts as -inf, -0 as +0; with a +inf in the row the draw is among the +inf tokens alone, each with weight 1.
  * temperature / top_p / seed: host arrays of num_rows.  Blocking; out_tokens: host u32 [num_rows]. */
 int32_t wrk_sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
                           const float* temperature, const float* top_p, const uint32_t* seed, uint32_t step, uint32_t* out_tokens);

@@ -315,7 +315,8 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
                     if (use_w) cand = cand && (l == mx || l - mx >= ln_min_p);      // rank 0 always passes (mx = +inf: inf - inf is NaN)
                 }
                 if constexpr (MIRO) {
-                    if (miro) cand = cand && (i == top || log2_w - (l - mx) * inv_t * SAMPLE_LOG2E <= mu);      // rank 0 always passes
+                    // rank 0 always passes; l == mx: surprise log2 W, as the mass pass weighs it (mx = +inf: inf - inf, 1 / T = inf: 0 * inf)
+                    if (miro) cand = cand && (i == top || log2_w - (l == mx ? 0.0f : (l - mx) * inv_t) * SAMPLE_LOG2E <= mu);
                 }
                 if (p >= 1) cand = cand && c == sel0;
                 if (p >= 2) cand = cand && (k >> lo) == prefix;
@@ -478,7 +479,8 @@ int32_t wrk_sample_pack(wrk_ctx* ctx, const float* temperature, const float* top
     out.resize(n);
     for (uint32_t b = 0; b < n; ++b) {
         const float t = temperature[b], p = top_p[b];
-        WRK_ARG(ctx, !(t != t) && t >= 0.0f, "temperature[%u] = %g: must be >= 0", b, (double)t);
+        // +inf: 1 / T = 0 would weigh a -inf logit inside the nucleus with exp(-inf * 0) = exp(NaN)
+        WRK_ARG(ctx, finite_f32(t) && t >= 0.0f, "temperature[%u] = %g: must be finite and >= 0", b, (double)t);
         WRK_ARG(ctx, !(p != p) && p >= 0.0f, "top_p[%u] = %g: must be >= 0", b, (double)p);
         out[b] = wrk::SampleParam{t, p, seed[b], 0u};
     }

@@ -586,6 +586,8 @@ class Context:
                       top_k=None, min_p=None, mirostat=None, typical_p=None):
         """`Sampler::sample` (examples/chat.rs:150-190; defaults are its `--temp 1.0 --top-p 0.5`) on the device, one token per row.
         `logits`: an [n, V] f32 array, or a `Buffer` of n rows of `num_vocab` f32; temperature / top_p / seed: scalars or per-row arrays.
+        A temperature must be finite and >= 0 (+inf or NaN: WrkError E_ARG, here and in every decode loop); a NaN logit counts as -inf,
+        and a row with +inf logits draws among those alone.
         top_k (0: off) / min_p (0: off): scalars or per-row arrays; with either the candidates are also cut to the top_k highest logits
         and to the tokens whose probability is at least min_p times the largest.  Returns uint32 [n].
         mirostat=(tau, eta, mu): Mirostat v2 with the target surprise tau (bits; 0: a plain row), the learning rate eta
