@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "wrk_hip.h"
+#include "wrk_dev_group.h"
 
 struct wrk_ctx {
     int device = 0;
@@ -95,18 +96,13 @@ inline int32_t wrk_fail(wrk_ctx* ctx, int32_t code, const char* fmt, ...) {
 #define WRK_LAUNCH_CHECK(ctx) WRK_HIP(ctx, hipGetLastError())
 
 // ------------------------------------------------------------------ what the blocking row functions share (wrk_api.hip)
-inline size_t wrk_up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool finite_f32(float x) { return std::isfinite(x); }
 // The argument checks of a blocking call `who` on n rows of V logits, `stride` floats apart, in `logits`; the caller holds ctx->mu.
 // WRK_E_ARG inside a capture of this thread and, with n > 0, unless V >= 1 && stride >= V or when the rows exceed the buffer;
 // WRK_E_UNSUPPORTED when max_vocab != 0 and V > max_vocab
 int32_t wrk_rows_check(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const char* who, uint32_t max_vocab);
-// Pieces of one device allocation at 256-byte offsets: add() every piece first, then alloc() once, then at<T>(offset).  wrk_dev_layout
-// is the offsets alone, for an owner that keeps the memory itself; wrk_dev_arena frees it when it goes out of scope
-struct wrk_dev_layout {
-    size_t total = 0;
-    size_t add(size_t bytes) { const size_t o = total; total += wrk_up256(bytes); return o; }
-};
+// Temporary device memory of a blocking call, laid out as wrk_dev_layout (wrk_dev_group.h) says: add() every piece first, then alloc()
+// once, then at<T>(offset); freed when it goes out of scope
 struct wrk_dev_arena : wrk_dev_layout {
     char* base = nullptr;
     wrk_dev_arena() = default;
@@ -441,18 +437,6 @@ int32_t wrk_filter_pack(wrk_ctx* ctx, const uint32_t* top_k, const float* min_p,
 int32_t wrk_mirostat_pack(wrk_ctx* ctx, const float* tau, const float* eta, const float* mu, uint32_t n, std::vector<wrk::SampleAlt>& out);
 int32_t wrk_typical_pack(wrk_ctx* ctx, const float* typical_p, uint32_t n, std::vector<wrk::SampleAlt>& out);
 
-// device slots of a scoring job (wrk_score.hip): targets u32, logprob f32, rank u32 [cap] and the slice partials [cap][SCORE_MAX_SLICES];
-// ensure() reallocates (after a stream sync) when n > cap and then sets *grown: programs captured with the old pointers must go
-struct wrk_score_scratch {
-    void* buf = nullptr;
-    uint32_t cap = 0;
-    uint32_t* targets = nullptr;
-    float* logprob = nullptr;
-    uint32_t* rank = nullptr;
-    wrk::ScorePart* part = nullptr;
-    int32_t ensure(wrk_ctx* ctx, uint32_t n, bool* grown);
-    void release();
-};
 // WRK_E_ARG unless every target < V (targets may be NULL only when n == 0)
 int32_t wrk_score_check_targets(wrk_ctx* ctx, const uint32_t* targets, uint32_t n, uint32_t V);
 

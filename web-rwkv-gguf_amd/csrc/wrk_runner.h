@@ -115,6 +115,155 @@ struct wrk_step_kind {
     uint32_t key2() const { return (uint32_t)stop_seqs; }
 };
 
+// ------------------------------------------------------------------ the buffer groups of a frame (Pieces of wrk_dev_group)
+// Each struct is the device pointers of one feature and its layout(): the only place the sizes of its buffers are written
+struct wrk_history_bufs {       // generated tokens [steps][B]
+    static constexpr int DIMS = 1;              // entries
+    static constexpr unsigned EXACT = 0;
+    uint32_t* tokens = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(tokens, d[0] * 4 + 256); }
+};
+// per-sequence parameter rows the step programs read through the pointer, never baked in: generate_sample's sampler rows
+// (wrk::SampleParam) and, next to them, the top-k / min-p rows of a filtered pick (wrk::SampleFilter)
+template <class Row> struct wrk_rows_bufs {
+    static constexpr int DIMS = 1;              // sequences
+    static constexpr unsigned EXACT = 0;
+    Row* par = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, d[0] * sizeof(Row)); }
+};
+// Mirostat / typical picks: per-sequence (tau, eta, mu, typical_p) rows next to the sampler's; the Mirostat sampler rewrites
+// a row's mu at every draw that counts, and the call reads the rows back.  mu: a queue's per-request mu (wrk::QueueBufs::alt_mu)
+struct wrk_alt_bufs {
+    static constexpr int DIMS = 2;              // sequences, requests (>= 1)
+    static constexpr unsigned EXACT = 0;
+    wrk::SampleAlt* par = nullptr;
+    float* mu = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, d[0] * sizeof(wrk::SampleAlt)); c.take(mu, d[1] * 4); }
+};
+// generate_penalized: per-sequence occurrence rows and penalties (the step programs read the table's pointers from here); out: the
+// penalised logits [B][V]
+struct wrk_penalty_bufs {
+    static constexpr int DIMS = 2;              // sequences, vocabulary
+    static constexpr unsigned EXACT = 0;
+    wrk::PenaltyParam* par = nullptr;
+    float* out = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, d[0] * sizeof(wrk::PenaltyParam)); c.take(out, d[0] * d[1] * 4); }
+};
+// constrained decoding (wrk_grammar.hip).  par: the parameter block (the grammar's tables and `state`: one program serves
+// any grammar and any start states); state: the sequences' automaton states, read back after the call; out [B][V]: the masked head
+// output of a pick without penalties; req: a queue's per-request states (wrk::QueueBufs::gram_req)
+struct wrk_grammar_bufs {
+    static constexpr int DIMS = 3;              // sequences, requests (>= 1), vocabulary
+    static constexpr unsigned EXACT = 4;
+    wrk::GrammarParam* par = nullptr;
+    uint32_t* state = nullptr;
+    float* out = nullptr;
+    uint32_t* req = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(par, sizeof(wrk::GrammarParam)); c.take(state, d[0] * 4); c.take(out, d[0] * d[2] * 4); c.take(req, d[1] * 4);
+    }
+};
+// wrk_v*_score (wrk_score.hip): targets / logprob / rank of the header rows and their slice partials [rows][SCORE_MAX_SLICES]
+struct wrk_score_bufs {
+    static constexpr int DIMS = 1;              // header rows
+    static constexpr unsigned EXACT = 0;
+    uint32_t* targets = nullptr;
+    float* logprob = nullptr;
+    uint32_t* rank = nullptr;
+    wrk::ScorePart* part = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(targets, d[0] * 4); c.take(logprob, d[0] * 4); c.take(rank, d[0] * 4);
+        c.take(part, d[0] * wrk::SCORE_MAX_SLICES * sizeof(wrk::ScorePart));
+    }
+};
+// generate_stop (wrk_stop.hip).  par: per-sequence stop sets and end marks; flags: just_ended [cap], then the frame's live
+// count, then lengths [cap]; snap_state [cap][slot floats] and snap_logits [cap][V]: slot and logits row of a sequence at the step that
+// ended it
+struct wrk_stop_bufs {
+    static constexpr int DIMS = 3;              // sequences, floats of one sequence's state (L * (S+2) * D), vocabulary
+    static constexpr unsigned EXACT = 6;
+    wrk::StopParam* par = nullptr;
+    uint32_t* flags = nullptr;
+    float *snap_state = nullptr, *snap_logits = nullptr;
+    size_t cap = 0;                             // sequences the flags are laid out for
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        cap = d[0];
+        c.take(par, d[0] * sizeof(wrk::StopParam)); c.take(flags, (2 * d[0] + 1) * 4);
+        c.take(snap_state, d[0] * d[1] * 4); c.take(snap_logits, d[0] * d[2] * 4);
+    }
+    uint32_t* just_ended() const { return flags; }
+    uint32_t* live() const { return flags + cap; }
+    uint32_t* lengths() const { return flags + cap + 1; }
+};
+// stop sequences of generate_stop (wrk_stopseq_dev.h), per sequence: rows, tails [n][WRK_STOP_TAIL_LEN], match words
+struct wrk_seq_bufs {
+    static constexpr int DIMS = 1;              // sequences
+    static constexpr unsigned EXACT = 0;
+    wrk::StopSeqRow* rows = nullptr;
+    uint32_t *tail = nullptr, *match = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(rows, d[0] * sizeof(wrk::StopSeqRow)); c.take(tail, d[0] * WRK_STOP_TAIL_LEN * 4); c.take(match, d[0] * 4);
+    }
+};
+// generate_queue (wrk_queue.hip): slot rows and started flags [slots], the control words, the request table and log
+// [requests], the prompt token pool [pool tokens]
+struct wrk_queue_bufs {
+    static constexpr int DIMS = 3;              // slots, requests, pool tokens
+    static constexpr unsigned EXACT = 0;
+    wrk::QueueSlot* slots = nullptr;
+    uint32_t* started = nullptr;
+    wrk::QueueCtl* ctl = nullptr;
+    wrk::QueueReq* reqs = nullptr;
+    wrk::QueueLog* log = nullptr;
+    uint32_t* pool = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(slots, d[0] * sizeof(wrk::QueueSlot)); c.take(started, d[0] * 4); c.take(ctl, sizeof(wrk::QueueCtl));
+        c.take(reqs, d[1] * sizeof(wrk::QueueReq)); c.take(log, d[1] * sizeof(wrk::QueueLog)); c.take(pool, d[2] * 4);
+    }
+    uint32_t* live() const { return &ctl->live; }
+};
+// stop sequences of generate_queue: rows and match words per request, tails [slots][WRK_STOP_TAIL_LEN] per slot
+struct wrk_queue_seq_bufs {
+    static constexpr int DIMS = 2;              // slots, requests
+    static constexpr unsigned EXACT = 0;
+    wrk::StopSeqRow* rows = nullptr;
+    uint32_t *tail = nullptr, *match = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(rows, d[1] * sizeof(wrk::StopSeqRow)); c.take(tail, d[0] * WRK_STOP_TAIL_LEN * 4); c.take(match, d[1] * 4);
+    }
+};
+// a queue call with a state pool: the pool's control words, the turnover list [slots], the start and save entries of the
+// requests [2][entry cap]
+struct wrk_queue_state_bufs {
+    static constexpr int DIMS = 2;              // slots, requests
+    static constexpr unsigned EXACT = 0;
+    wrk::QueueStateCtl* ctl = nullptr;
+    wrk::QueueTurn* turn = nullptr;
+    uint32_t *start = nullptr, *save = nullptr; // one piece: save == start + entry cap
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(ctl, sizeof(wrk::QueueStateCtl)); c.take(turn, d[0] * sizeof(wrk::QueueTurn)); c.take(start, 2 * d[1] * 4);
+        save = start ? start + d[1] : nullptr;
+    }
+};
+// log-probs in the decode loops (wrk_logprob.hip).  par: the parameter block (the output buffers and num_top: one program
+// serves any num_top); the per-step rows logprob [rows], top_ids / top_logprobs [rows][WRK_MAX_TOP_LOGPROBS], indexed
+// [steps][B](, [num_top]) by a call; the slice partials and candidate keys of `batch` rows
+struct wrk_logprob_bufs {
+    static constexpr int DIMS = 2;              // rows, batch
+    static constexpr unsigned EXACT = 0;
+    wrk::LogprobParam* par = nullptr;
+    float* logprob = nullptr;
+    uint32_t* top_ids = nullptr;
+    float* top_logprobs = nullptr;
+    wrk::LogprobPart* part = nullptr;
+    unsigned long long* keys = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(par, sizeof(wrk::LogprobParam)); c.take(logprob, d[0] * 4);
+        c.take(top_ids, d[0] * WRK_MAX_TOP_LOGPROBS * 4); c.take(top_logprobs, d[0] * WRK_MAX_TOP_LOGPROBS * 4);
+        c.take(part, wrk::logprob_part_bytes((uint32_t)d[1])); c.take(keys, wrk::logprob_key_bytes((uint32_t)d[1]));
+    }
+};
+
 // ------------------------------------------------------------------ frame state of a model (base of wrk_v7_model / wrk_v6_model)
 struct wrk_frame_common {
     // ---- what the decode loops ask of a runner (host only: never passed to a kernel)
@@ -141,81 +290,25 @@ struct wrk_frame_common {
     wrk_ctx* ctx = nullptr;
     void* scratch = nullptr;
     uint32_t scratch_tokens = 0, scratch_headers = 0;
-    uint32_t* history = nullptr;    // generated tokens [steps][B] (device)
-    size_t history_cap = 0;
-    wrk::SampleParam* sample_par = nullptr;    // generate_sample: per-sequence sampler parameters, written before every call (not baked
-    uint32_t sample_par_cap = 0;                // into the step programs, which read them through this pointer)
-    wrk::SampleFilter* filter_par = nullptr;   // filtered picks: per-sequence top-k / min-p rows next to sample_par, written before every call
-    uint32_t filter_par_cap = 0;
-    // Mirostat / typical picks: per-sequence (tau, eta, mu, typical_p) rows next to sample_par, written before every call; the
-    // Mirostat sampler rewrites a row's mu at every draw that counts, and the call reads the rows back.  alt_mu [alt_mu_cap]: a queue's
-    // per-request mu (wrk::QueueBufs::alt_mu)
-    wrk::SampleAlt* alt_par = nullptr;
-    float* alt_mu = nullptr;
-    uint32_t alt_par_cap = 0, alt_mu_cap = 0;
-    wrk::PenaltyParam* pen_par = nullptr;      // generate_penalized: per-sequence occurrence rows and penalties, written before every call
-    float* pen_o = nullptr;                     // (the step programs read the table's pointers from here); pen_o: penalised logits [B][V]
-    uint32_t pen_cap = 0;
-    // constrained decoding (wrk_grammar.hip), allocated by the first call with a grammar only and written before every call.
-    // gram_par: the parameter block (the grammar's tables and gram_state: one program serves any grammar and any start states);
-    // gram_state [gram_cap]: the sequences' automaton states, read back after the call; con_o [gram_cap][V]: the masked head output of a
-    // pick without penalties; gram_req [gram_req_cap]: a queue's per-request states (wrk::QueueBufs::gram_req)
-    wrk::GrammarParam* gram_par = nullptr;
-    uint32_t* gram_state = nullptr;
-    float* con_o = nullptr;
-    uint32_t* gram_req = nullptr;
-    uint32_t gram_cap = 0, gram_req_cap = 0, gram_vocab_cap = 0;
-    wrk_score_scratch score;                    // wrk_v*_score: targets / logprob / rank / slice partials of the header rows
-    // generate_stop (wrk_stop.hip), allocated by the first stop call only.  stop_par: per-sequence stop sets and end marks,
-    // written before every call; stop_flags: just_ended [cap], then the frame's live count, then lengths [cap]; stop_snap_state
-    // [cap][L][(S+2) D] and stop_snap_logits [cap][V]: slot and logits row of a sequence at the step that ended it
-    wrk::StopParam* stop_par = nullptr;
-    uint32_t* stop_flags = nullptr;
-    float *stop_snap_state = nullptr, *stop_snap_logits = nullptr;
-    uint32_t stop_cap = 0;
-    size_t stop_slot_cap = 0;                   // floats of one sequence's state snapshot (L * (S+2) * D)
-    uint32_t stop_vocab_cap = 0;
-    uint32_t* stop_just_ended() const { return stop_flags; }
-    uint32_t* stop_live() const { return stop_flags + stop_cap; }
-    uint32_t* stop_lengths() const { return stop_flags + stop_cap + 1; }
-    // generate_queue (wrk_queue.hip), allocated by the first queue call only and written before every call: slot rows and
-    // started flags [slot cap], the control words, the request table and log [request cap], the prompt token pool [pool cap]
-    wrk::QueueSlot* queue_slots = nullptr;
-    uint32_t* queue_started = nullptr;
-    wrk::QueueCtl* queue_ctl = nullptr;
-    wrk::QueueReq* queue_reqs = nullptr;
-    wrk::QueueLog* queue_log = nullptr;
-    uint32_t* queue_pool = nullptr;
-    uint32_t queue_slot_cap = 0, queue_req_cap = 0;
-    size_t queue_pool_cap = 0;
-    uint32_t* queue_live() const { return &queue_ctl->live; }
-    // stop sequences (wrk_stopseq_dev.h), allocated by the first call that passes them only and written before every call.
-    // generate_stop: stopseq_rows / stopseq_tail [cap][WRK_STOP_TAIL_LEN] / stopseq_match [stopseq_cap], per sequence; generate_queue:
-    // queue_seq_rows / queue_seq_match [queue_seq_req_cap], per request, and queue_seq_tail [queue_seq_slot_cap][WRK_STOP_TAIL_LEN], per slot
-    wrk::StopSeqRow* stopseq_rows = nullptr;
-    uint32_t *stopseq_tail = nullptr, *stopseq_match = nullptr;
-    uint32_t stopseq_cap = 0;
-    wrk::StopSeqRow* queue_seq_rows = nullptr;
-    uint32_t *queue_seq_tail = nullptr, *queue_seq_match = nullptr;
-    uint32_t queue_seq_slot_cap = 0, queue_seq_req_cap = 0;
-    // a queue call with a state pool, allocated by the first such call only and written before every call: the pool's
-    // control words, the turnover list [turn cap], the start and save entries of the requests [2][index cap]
-    wrk::QueueStateCtl* queue_state_ctl = nullptr;
-    wrk::QueueTurn* queue_turn = nullptr;
-    uint32_t* queue_entries = nullptr;
-    uint32_t queue_turn_cap = 0, queue_entry_cap = 0;
-    // log-probs in the decode loops (wrk_logprob.hip), allocated by the first such call only.  lp_par: the parameter block,
-    // written before every call (the output buffers and num_top: one program serves any num_top); the per-step rows lp_logprob
-    // [lp_rows_cap], lp_top_ids / lp_top_logprobs [lp_rows_cap][WRK_MAX_TOP_LOGPROBS], indexed [steps][B](, [num_top]) by a call; the
-    // slice partials and candidate keys of lp_batch_cap rows
-    wrk::LogprobParam* lp_par = nullptr;
-    float* lp_logprob = nullptr;
-    uint32_t* lp_top_ids = nullptr;
-    float* lp_top_logprobs = nullptr;
-    wrk::LogprobPart* lp_part = nullptr;
-    unsigned long long* lp_keys = nullptr;
-    size_t lp_rows_cap = 0;
-    uint32_t lp_batch_cap = 0;
+    // The side buffers of the decode-loop features and of scoring, one group each (wrk_dev_group.h): allocated by the first
+    // call that needs the group, regrown by grow() before the step program is looked up, written before every call
+    wrk_dev_group<wrk_history_bufs> history;
+    wrk_dev_group<wrk_rows_bufs<wrk::SampleParam>> sample;
+    wrk_dev_group<wrk_rows_bufs<wrk::SampleFilter>> filter;
+    wrk_dev_group<wrk_alt_bufs> alt;
+    wrk_dev_group<wrk_penalty_bufs> penalty;
+    wrk_dev_group<wrk_grammar_bufs> grammar;
+    wrk_dev_group<wrk_score_bufs> score;
+    wrk_dev_group<wrk_stop_bufs> stop;
+    wrk_dev_group<wrk_seq_bufs> stop_seq;           // generate_stop: rows, tails and match words per sequence
+    wrk_dev_group<wrk_queue_bufs> queue;
+    wrk_dev_group<wrk_queue_seq_bufs> queue_seq;
+    wrk_dev_group<wrk_queue_state_bufs> queue_states;
+    wrk_dev_group<wrk_logprob_bufs> logprob;
+    template <class F> void each_group(F&& f) {     // the one list of the groups
+        f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
+        f(queue_states); f(logprob);
+    }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
     uint32_t live_host_cap = 0;
     std::vector<hipEvent_t> poll_events;        // [2 blocks][lanes]
@@ -232,26 +325,17 @@ struct wrk_frame_common {
     };
     std::map<GraphKey, wrk_program*> graphs;
 
-    // the ensure_* reallocate after a stream sync and drop the captured programs, which hold the old pointers; never inside a capture
+    // the captured programs hold the groups' addresses: they go whenever a held group is reallocated; never inside a capture
     void drop_graphs();
-    // the buffers an ensure_* reallocates together; bufs(g): their pointers, the one list regrow and release_common go through
-    enum Group { HISTORY, SAMPLE, FILTER, PENALTY, STOP, QUEUE, QUEUE_STATES, LOGPROB, ALT, GRAMMAR, STOP_SEQ, QUEUE_SEQ, NUM_GROUPS };
-    std::vector<void**> bufs(Group g);
-    // sync, drop the programs (`drop`), free the buffers and allocate them again; after a failure all of them are freed
-    // bytes: one size per buffer of bufs(g), in its order.  The caller sets its caps after WRK_OK: an error leaves them as they were
-    int32_t regrow(Group g, std::initializer_list<size_t> bytes, bool drop);
-    int32_t ensure_history(size_t n);
-    int32_t ensure_sample_params(uint32_t n);
-    int32_t ensure_filter_params(uint32_t n);
-    int32_t ensure_alt_params(uint32_t n, uint32_t requests);
-    int32_t ensure_penalty(uint32_t n, uint32_t num_vocab);
-    int32_t ensure_grammar(uint32_t n, uint32_t num_vocab, uint32_t requests = 0);      // requests: a queue's (0: none)
-    int32_t ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V);
-    int32_t ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens);
-    int32_t ensure_queue_states(uint32_t slots, uint32_t requests);
-    int32_t ensure_stop_seqs(uint32_t n);
-    int32_t ensure_queue_seqs(uint32_t slots, uint32_t requests);
-    int32_t ensure_logprobs(size_t rows, uint32_t B);
+    // g.ensure(want) under the one policy of wrk_dev_group, the programs dropped when a held group moves.  WRK_E_OOM / WRK_E_HIP with the
+    // byte count when the allocation fails: the group is then not held, and the next call allocates again
+    template <class G> int32_t grow(G& g, std::initializer_list<size_t> want) {
+        const hipError_t e = g.ensure(ctx->stream, want, [this] { drop_graphs(); });
+        if (e == hipSuccess) return WRK_OK;
+        const int32_t code = e == hipErrorOutOfMemory ? WRK_E_OOM : WRK_E_HIP;
+        if (!g.asked) return wrk_fail(ctx, code, "hipStreamSynchronize: %s", hipGetErrorString(e));
+        return wrk_fail(ctx, code, "hipMalloc of %zu bytes: %s", g.asked, hipGetErrorString(e));
+    }
     int32_t ensure_poll(uint32_t lanes);        // lane 0's frame: pinned live counts and events of the polled loop
     void release_common();          // destroy paths: programs, scratch and every buffer above
 };

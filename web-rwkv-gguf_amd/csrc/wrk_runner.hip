@@ -34,6 +34,16 @@ int32_t wrk_buf_write_raw(wrk_ctx* ctx, void* dst, const void* src, size_t bytes
     return wrk_buf_write(ctx, &tmp, 0, src, bytes);
 }
 
+// the uploads of a prepare function: up(dst, src, n) writes n elements of T from the host to the device, nothing after the first error
+struct wrk_upload {
+    wrk_ctx* ctx;
+    int32_t rc = WRK_OK;
+    template <class T> wrk_upload& operator()(T* dst, const T* src, size_t n) {
+        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, dst, src, n * sizeof(T));
+        return *this;
+    }
+};
+
 // ------------------------------------------------------------------ job validation
 int32_t wrk_job_check(wrk_ctx* ctx, const wrk_v7_state* st, const uint32_t* cursors, uint32_t T, const uint32_t* tokens, uint32_t V,
                       const uint32_t* headers, uint32_t NH, wrk_job_shape* shape) {
@@ -74,156 +84,6 @@ void wrk_frame_common::drop_graphs() {
     graphs.clear();
 }
 
-std::vector<void**> wrk_frame_common::bufs(Group g) {
-    switch (g) {
-        case HISTORY: return {(void**)&history};
-        case SAMPLE: return {(void**)&sample_par};
-        case FILTER: return {(void**)&filter_par};
-        case ALT: return {(void**)&alt_par, (void**)&alt_mu};
-        case PENALTY: return {(void**)&pen_par, (void**)&pen_o};
-        case GRAMMAR: return {(void**)&gram_par, (void**)&gram_state, (void**)&con_o, (void**)&gram_req};
-        case STOP: return {(void**)&stop_par, (void**)&stop_flags, (void**)&stop_snap_state, (void**)&stop_snap_logits};
-        case QUEUE: return {(void**)&queue_slots, (void**)&queue_started, (void**)&queue_ctl, (void**)&queue_reqs, (void**)&queue_log, (void**)&queue_pool};
-        case QUEUE_STATES: return {(void**)&queue_state_ctl, (void**)&queue_turn, (void**)&queue_entries};
-        case STOP_SEQ: return {(void**)&stopseq_rows, (void**)&stopseq_tail, (void**)&stopseq_match};
-        case QUEUE_SEQ: return {(void**)&queue_seq_rows, (void**)&queue_seq_tail, (void**)&queue_seq_match};
-        case LOGPROB: return {(void**)&lp_par, (void**)&lp_logprob, (void**)&lp_top_ids, (void**)&lp_top_logprobs, (void**)&lp_part, (void**)&lp_keys};
-        default: return {};
-    }
-}
-
-int32_t wrk_frame_common::regrow(Group g, std::initializer_list<size_t> bytes, bool drop) {
-    const std::vector<void**> list = bufs(g);
-    if (list.size() != bytes.size()) return wrk_fail(ctx, WRK_E_ARG, "buffer group %d: %zu sizes for %zu buffers", (int)g, bytes.size(), list.size());
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (drop) drop_graphs();
-    hipError_t e = hipSuccess;
-    size_t failed = 0, i = 0;
-    for (void** p : list) { if (*p) hipFree(*p); *p = nullptr; }
-    for (size_t n : bytes) {
-        if (e == hipSuccess && (e = hipMalloc(list[i], n)) != hipSuccess) failed = n;
-        ++i;
-    }
-    if (e == hipSuccess) return WRK_OK;
-    for (void** p : list) { if (*p) hipFree(*p); *p = nullptr; }       // the ensure_* look at their first pointer: the next call allocates again
-    return wrk_fail(ctx, e == hipErrorOutOfMemory ? WRK_E_OOM : WRK_E_HIP, "hipMalloc of %zu bytes: %s", failed, hipGetErrorString(e));
-}
-
-int32_t wrk_frame_common::ensure_history(size_t n) {
-    if (n <= history_cap && history) return WRK_OK;
-    const int32_t rc = regrow(HISTORY, {n * 4 + 256}, true);
-    if (rc == WRK_OK) history_cap = n;
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_sample_params(uint32_t n) {
-    if (n <= sample_par_cap && sample_par) return WRK_OK;
-    const int32_t rc = regrow(SAMPLE, {(size_t)n * sizeof(wrk::SampleParam)}, true);
-    if (rc == WRK_OK) sample_par_cap = n;
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_filter_params(uint32_t n) {
-    if (n <= filter_par_cap && filter_par) return WRK_OK;
-    const int32_t rc = regrow(FILTER, {(size_t)n * sizeof(wrk::SampleFilter)}, true);
-    if (rc == WRK_OK) filter_par_cap = n;
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_alt_params(uint32_t n, uint32_t requests) {
-    if (requests < 1) requests = 1;
-    if (alt_par && n <= alt_par_cap && requests <= alt_mu_cap) return WRK_OK;
-    if (n < alt_par_cap) n = alt_par_cap;
-    if (requests < alt_mu_cap) requests = alt_mu_cap;
-    // Mirostat / typical programs hold the old pointers; before the first allocation none exists
-    const int32_t rc = regrow(ALT, {(size_t)n * sizeof(wrk::SampleAlt), (size_t)requests * 4}, alt_par != nullptr);
-    alt_par_cap = rc == WRK_OK ? n : 0;
-    alt_mu_cap = rc == WRK_OK ? requests : 0;
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_penalty(uint32_t n, uint32_t num_vocab) {
-    if (n <= pen_cap && pen_par && pen_o) return WRK_OK;
-    const int32_t rc = regrow(PENALTY, {(size_t)n * sizeof(wrk::PenaltyParam), (size_t)n * num_vocab * 4}, true);
-    if (rc == WRK_OK) pen_cap = n;
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_grammar(uint32_t n, uint32_t num_vocab, uint32_t requests) {
-    if (requests < 1) requests = 1;
-    if (gram_par && n <= gram_cap && requests <= gram_req_cap && num_vocab == gram_vocab_cap) return WRK_OK;
-    if (n < gram_cap) n = gram_cap;
-    if (requests < gram_req_cap) requests = gram_req_cap;
-    // constrained programs hold the old pointers; before the first allocation none exists
-    const int32_t rc = regrow(GRAMMAR, {sizeof(wrk::GrammarParam), (size_t)n * 4, (size_t)n * num_vocab * 4, (size_t)requests * 4}, gram_par != nullptr);
-    gram_cap = rc == WRK_OK ? n : 0;
-    gram_req_cap = rc == WRK_OK ? requests : 0;
-    gram_vocab_cap = rc == WRK_OK ? num_vocab : 0;
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_stop(uint32_t n, uint32_t L, uint32_t S, uint32_t D, uint32_t V) {
-    const size_t slot = (size_t)L * (S + 2) * D;
-    if (stop_par && n <= stop_cap && slot == stop_slot_cap && V == stop_vocab_cap) return WRK_OK;
-    const int32_t rc = regrow(STOP, {(size_t)n * sizeof(wrk::StopParam), ((size_t)2 * n + 1) * 4, (size_t)n * slot * 4, (size_t)n * V * 4}, true);
-    if (rc == WRK_OK) { stop_cap = n; stop_slot_cap = slot; stop_vocab_cap = V; }
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_queue(uint32_t slots, uint32_t requests, size_t pool_tokens) {
-    if (queue_ctl && slots <= queue_slot_cap && requests <= queue_req_cap && pool_tokens <= queue_pool_cap) return WRK_OK;
-    // never smaller than before: a later, smaller queue reuses the buffers and the program
-    if (slots < queue_slot_cap) slots = queue_slot_cap;
-    if (requests < queue_req_cap) requests = queue_req_cap;
-    if (pool_tokens < queue_pool_cap) pool_tokens = queue_pool_cap;
-    // queue programs hold the old pointers; before the first allocation none exists
-    const int32_t rc = regrow(QUEUE, {(size_t)slots * sizeof(wrk::QueueSlot), (size_t)slots * 4, sizeof(wrk::QueueCtl), (size_t)requests * sizeof(wrk::QueueReq),
-                                      (size_t)requests * sizeof(wrk::QueueLog), pool_tokens * 4}, queue_ctl != nullptr);
-    if (rc == WRK_OK) { queue_slot_cap = slots; queue_req_cap = requests; queue_pool_cap = pool_tokens; }
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_queue_states(uint32_t slots, uint32_t requests) {
-    if (queue_state_ctl && slots <= queue_turn_cap && requests <= queue_entry_cap) return WRK_OK;
-    if (slots < queue_turn_cap) slots = queue_turn_cap;
-    if (requests < queue_entry_cap) requests = queue_entry_cap;
-    // pool programs hold the old pointers; before the first allocation none exists
-    const int32_t rc = regrow(QUEUE_STATES, {sizeof(wrk::QueueStateCtl), (size_t)slots * sizeof(wrk::QueueTurn), (size_t)2 * requests * 4}, queue_state_ctl != nullptr);
-    if (rc == WRK_OK) { queue_turn_cap = slots; queue_entry_cap = requests; }
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_stop_seqs(uint32_t n) {
-    if (stopseq_rows && n <= stopseq_cap) return WRK_OK;
-    // stop-sequence programs hold the old pointers; before the first allocation none exists
-    const int32_t rc = regrow(STOP_SEQ, {(size_t)n * sizeof(wrk::StopSeqRow), (size_t)n * WRK_STOP_TAIL_LEN * 4, (size_t)n * 4}, stopseq_rows != nullptr);
-    stopseq_cap = rc == WRK_OK ? n : 0;
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_queue_seqs(uint32_t slots, uint32_t requests) {
-    if (queue_seq_rows && slots <= queue_seq_slot_cap && requests <= queue_seq_req_cap) return WRK_OK;
-    if (slots < queue_seq_slot_cap) slots = queue_seq_slot_cap;
-    if (requests < queue_seq_req_cap) requests = queue_seq_req_cap;
-    const int32_t rc = regrow(QUEUE_SEQ, {(size_t)requests * sizeof(wrk::StopSeqRow), (size_t)slots * WRK_STOP_TAIL_LEN * 4, (size_t)requests * 4},
-                              queue_seq_rows != nullptr);
-    queue_seq_slot_cap = rc == WRK_OK ? slots : 0;
-    queue_seq_req_cap = rc == WRK_OK ? requests : 0;
-    return rc;
-}
-
-int32_t wrk_frame_common::ensure_logprobs(size_t rows, uint32_t B) {
-    if (lp_par && rows <= lp_rows_cap && B <= lp_batch_cap) return WRK_OK;
-    if (rows < lp_rows_cap) rows = lp_rows_cap;
-    if (B < lp_batch_cap) B = lp_batch_cap;
-    // log-prob programs hold the old pointers; before the first allocation none exists
-    const size_t top = rows * WRK_MAX_TOP_LOGPROBS * 4;
-    const int32_t rc = regrow(LOGPROB, {sizeof(wrk::LogprobParam), rows * 4, top, top, wrk::logprob_part_bytes(B), wrk::logprob_key_bytes(B)}, lp_par != nullptr);
-    lp_rows_cap = rc == WRK_OK ? rows : 0;
-    lp_batch_cap = rc == WRK_OK ? B : 0;
-    return rc;
-}
-
 int32_t wrk_frame_common::ensure_poll(uint32_t lanes) {
     if (live_host_cap < 2 * lanes) {
         if (live_host) hipHostFree(live_host);
@@ -243,14 +103,7 @@ void wrk_frame_common::release_common() {
     drop_graphs();
     if (scratch) hipFree(scratch);
     scratch = nullptr;
-    for (int g = 0; g < NUM_GROUPS; ++g)
-        for (void** p : bufs((Group)g)) { if (*p) hipFree(*p); *p = nullptr; }
-    history_cap = 0; stop_slot_cap = 0; queue_pool_cap = 0; lp_rows_cap = 0; lp_batch_cap = 0;
-    alt_par_cap = alt_mu_cap = 0;
-    gram_cap = gram_req_cap = gram_vocab_cap = 0;
-    stopseq_cap = queue_seq_slot_cap = queue_seq_req_cap = 0;
-    sample_par_cap = filter_par_cap = pen_cap = stop_cap = stop_vocab_cap = queue_slot_cap = queue_req_cap = queue_turn_cap = queue_entry_cap = 0;
-    score.release();
+    each_group([](auto& g) { g.release(); });
     if (live_host) hipHostFree(live_host);
     live_host = nullptr; live_host_cap = 0;
     for (hipEvent_t e : poll_events) hipEventDestroy(e);
@@ -278,10 +131,8 @@ int32_t wrk_job_upload(wrk_frame_common& f, wrk::FrameIo& io, void* input, const
     wrk_ctx* ctx = f.ctx;
     int32_t rc = WRK_OK;
     if (a.score && a.NH) {
-        bool grown = false;
-        rc = f.score.ensure(ctx, a.NH, &grown);
+        rc = f.grow(f.score, {a.NH});          // captured score jobs hold the old slots: they go when the slots move
         if (rc != WRK_OK) return rc;
-        if (grown) f.drop_graphs();            // captured score jobs hold the old slots
         rc = wrk_buf_write_raw(ctx, f.score.targets, a.targets, (size_t)a.NH * 4);
     }
     if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.cursors, a.cursors, (size_t)a.T * 4);
@@ -482,11 +333,11 @@ static int32_t wrk_logprob_check(wrk_ctx* ctx, const wrk_logprob_call& lp, uint3
 // after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): the frame's log-prob
 // buffers for `steps` steps of B sequences and the parameter block of this call
 static int32_t wrk_logprob_prepare(wrk_frame_common& f, uint32_t B, uint32_t steps, uint32_t num_top) {
-    const int32_t rc = f.ensure_logprobs((size_t)steps * B, B);
+    const int32_t rc = f.grow(f.logprob, {(size_t)steps * B, B});
     if (rc != WRK_OK) return rc;
-    const wrk::LogprobParam par{f.lp_logprob, f.lp_top_ids, f.lp_top_logprobs, num_top, (uint32_t)((size_t)steps * B)};
-    const int32_t rc2 = wrk_buf_write_raw(f.ctx, f.lp_par, &par, sizeof par);
-    if (rc2 != WRK_OK) return rc2;
+    const wrk::LogprobParam par{f.logprob.logprob, f.logprob.top_ids, f.logprob.top_logprobs, num_top, (uint32_t)((size_t)steps * B)};
+    wrk_upload up{f.ctx};
+    if (up(f.logprob.par, &par, 1).rc != WRK_OK) return up.rc;
     WRK_HIP(f.ctx, hipStreamSynchronize(f.ctx->stream));
     return WRK_OK;
 }
@@ -514,28 +365,28 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     const wrk::PenaltyParam* pen = rows.pen.empty() ? nullptr : rows.pen.data() + b0;
     const wrk::SampleFilter* filt = rows.filt.empty() ? nullptr : rows.filt.data() + b0;
     const wrk::SampleAlt* alt = rows.alt.empty() ? nullptr : rows.alt.data() + b0;
-    int32_t rc = f.ensure_history((size_t)steps * B);
-    if (rc == WRK_OK && par) rc = f.ensure_sample_params(B);
-    if (rc == WRK_OK && filt) rc = f.ensure_filter_params(B);
-    if (rc == WRK_OK && alt) rc = f.ensure_alt_params(B, rows.alt_requests);
-    if (rc == WRK_OK && pen) rc = f.ensure_penalty(B, f.facts().num_vocab);
-    if (rc == WRK_OK && rows.grammar) rc = f.ensure_grammar(B, f.facts().num_vocab, rows.gram_requests);
+    // a per-request array of a queue (none: 0) has at least one entry
+    const size_t V = f.facts().num_vocab, alt_req = rows.alt_requests ? rows.alt_requests : 1, gram_req = rows.gram_requests ? rows.gram_requests : 1;
+    int32_t rc = f.grow(f.history, {(size_t)steps * B});
+    if (rc == WRK_OK && par) rc = f.grow(f.sample, {B});
+    if (rc == WRK_OK && filt) rc = f.grow(f.filter, {B});
+    if (rc == WRK_OK && alt) rc = f.grow(f.alt, {B, alt_req});
+    if (rc == WRK_OK && pen) rc = f.grow(f.penalty, {B, V});
+    if (rc == WRK_OK && rows.grammar) rc = f.grow(f.grammar, {B, gram_req, V});
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
-    rc = wrk_buf_write_raw(ctx, io.cursors, cur.data(), (size_t)B * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.headers, hdr.data(), (size_t)B * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, io.tokens, first_tokens + b0, (size_t)B * 4);
-    if (rc == WRK_OK && par) rc = wrk_buf_write_raw(ctx, f.sample_par, par, (size_t)B * sizeof(wrk::SampleParam));
-    if (rc == WRK_OK && filt) rc = wrk_buf_write_raw(ctx, f.filter_par, filt, (size_t)B * sizeof(wrk::SampleFilter));
-    if (rc == WRK_OK && alt) rc = wrk_buf_write_raw(ctx, f.alt_par, alt, (size_t)B * sizeof(wrk::SampleAlt));
-    if (rc == WRK_OK && pen) rc = wrk_buf_write_raw(ctx, f.pen_par, pen, (size_t)B * sizeof(wrk::PenaltyParam));
-    if (rc == WRK_OK && rows.grammar) {
-        const wrk::GrammarParam gp = rows.grammar->param(f.gram_state);
-        rc = wrk_buf_write_raw(ctx, f.gram_par, &gp, sizeof gp);
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.gram_state, rows.gram_state.data() + b0, (size_t)B * 4);
+    wrk_upload up{ctx};
+    up(io.cursors, cur.data(), B)(io.headers, hdr.data(), B)(io.tokens, first_tokens + b0, B);
+    if (par) up(f.sample.par, par, B);
+    if (filt) up(f.filter.par, filt, B);
+    if (alt) up(f.alt.par, alt, B);
+    if (pen) up(f.penalty.par, pen, B);
+    if (rows.grammar) {
+        const wrk::GrammarParam gp = rows.grammar->param(f.grammar.state);
+        up(f.grammar.par, &gp, 1)(f.grammar.state, rows.gram_state.data() + b0, B);
     }
-    if (rc != WRK_OK) return rc;
+    if (up.rc != WRK_OK) return up.rc;
     WRK_HIP(ctx, hipMemsetAsync(io.counter, 0, 4, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
@@ -548,20 +399,19 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
 static int32_t wrk_stop_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t b0, uint32_t B, const wrk::StopParam* rows,
                                 const wrk_stopseq_pack* seq) {
     wrk_ctx* ctx = f.ctx;
-    int32_t rc = f.ensure_stop(B, st->num_layer, st->head_size, st->num_emb, f.facts().num_vocab);
-    if (rc == WRK_OK && seq) rc = f.ensure_stop_seqs(B);
+    int32_t rc = f.grow(f.stop, {B, (size_t)st->num_layer * (st->head_size + 2) * st->num_emb, f.facts().num_vocab});
+    if (rc == WRK_OK && seq) rc = f.grow(f.stop_seq, {B});
     if (rc != WRK_OK) return rc;
-    std::vector<uint32_t> flags(f.stop_cap + 1, 0u);      // just_ended = 0, then the live count
-    flags[f.stop_cap] = B;
-    rc = wrk_buf_write_raw(ctx, f.stop_par, rows, (size_t)B * sizeof(wrk::StopParam));
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.stop_flags, flags.data(), flags.size() * 4);
-    if (rc == WRK_OK && seq) {
+    std::vector<uint32_t> flags(f.stop.cap + 1, 0u);      // just_ended = 0, then the live count
+    flags[f.stop.cap] = B;
+    wrk_upload up{ctx};
+    up(f.stop.par, rows, B)(f.stop.flags, flags.data(), flags.size());
+    if (seq) {
         const std::vector<uint32_t> none(B, WRK_STOP_MATCH_NONE);
-        rc = wrk_buf_write_raw(ctx, f.stopseq_rows, seq->rows.data() + b0, (size_t)B * sizeof(wrk::StopSeqRow));
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.stopseq_tail, seq->tails.data() + (size_t)b0 * WRK_STOP_TAIL_LEN, (size_t)B * WRK_STOP_TAIL_LEN * 4);
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.stopseq_match, none.data(), (size_t)B * 4);
+        up(f.stop_seq.rows, seq->rows.data() + b0, B)(f.stop_seq.tail, seq->tails.data() + (size_t)b0 * WRK_STOP_TAIL_LEN, (size_t)B * WRK_STOP_TAIL_LEN);
+        up(f.stop_seq.match, none.data(), B);
     }
-    if (rc != WRK_OK) return rc;
+    if (up.rc != WRK_OK) return up.rc;
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
 }
@@ -722,16 +572,16 @@ static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, co
 }
 
 static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
-    return wrk::QueueBufs{f.queue_slots, f.queue_reqs, f.queue_pool, f.queue_log, f.queue_ctl, f.queue_started,
-                          kind.sampled() ? f.sample_par : nullptr, kind.penalized ? f.pen_par : nullptr, kind.filtered() ? f.filter_par : nullptr,
-                          kind.alt() ? f.alt_par : nullptr, kind.mirostat() ? f.alt_mu : nullptr,
-                          kind.constrained ? f.gram_state : nullptr, kind.constrained ? f.gram_req : nullptr,
-                          kind.stop_seqs ? f.queue_seq_rows : nullptr, kind.stop_seqs ? f.queue_seq_tail : nullptr,
-                          kind.stop_seqs ? f.queue_seq_match : nullptr};
+    return wrk::QueueBufs{f.queue.slots, f.queue.reqs, f.queue.pool, f.queue.log, f.queue.ctl, f.queue.started,
+                          kind.sampled() ? f.sample.par : nullptr, kind.penalized ? f.penalty.par : nullptr, kind.filtered() ? f.filter.par : nullptr,
+                          kind.alt() ? f.alt.par : nullptr, kind.mirostat() ? f.alt.mu : nullptr,
+                          kind.constrained ? f.grammar.state : nullptr, kind.constrained ? f.grammar.req : nullptr,
+                          kind.stop_seqs ? f.queue_seq.rows : nullptr, kind.stop_seqs ? f.queue_seq.tail : nullptr,
+                          kind.stop_seqs ? f.queue_seq.match : nullptr};
 }
 
 static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f) {
-    return wrk::QueueStateBufs{f.queue_entries, f.queue_entries + f.queue_entry_cap, f.queue_state_ctl, f.queue_turn};
+    return wrk::QueueStateBufs{f.queue_states.start, f.queue_states.save, f.queue_states.ctl, f.queue_states.turn};
 }
 
 static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V) {
@@ -744,9 +594,10 @@ static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V
 static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t B, const wrk_queue_pack& pk) {
     wrk_ctx* ctx = f.ctx;
     const uint32_t V = f.facts().num_vocab;
-    int32_t rc = f.ensure_queue(B, pk.R, pk.pool.size());
-    if (rc == WRK_OK && pk.kind.pool()) rc = f.ensure_queue_states(B, pk.R);
-    if (rc == WRK_OK && pk.kind.stop_seqs) rc = f.ensure_queue_seqs(B, pk.R);
+    // never smaller than before: a later, smaller queue reuses the buffers and the program
+    int32_t rc = f.grow(f.queue, {B, pk.R, pk.pool.size()});
+    if (rc == WRK_OK && pk.kind.pool()) rc = f.grow(f.queue_states, {B, pk.R});
+    if (rc == WRK_OK && pk.kind.stop_seqs) rc = f.grow(f.queue_seq, {B, pk.R});
     if (rc != WRK_OK) return rc;
     const uint32_t nstart = B < pk.R ? B : pk.R;
     std::vector<wrk::QueueSlot> slots(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
@@ -758,37 +609,27 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
         log[b] = wrk::QueueLog{0u, 3u, b, 0u};
     }
     const wrk::QueueCtl ctl{nstart, pk.R, pk.R, 0u, pk.init_state};
-    rc = wrk_buf_write_raw(ctx, f.queue_slots, slots.data(), (size_t)B * sizeof(wrk::QueueSlot));
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_started, started.data(), (size_t)B * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_log, log.data(), (size_t)pk.R * sizeof(wrk::QueueLog));
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_reqs, pk.reqs.data(), (size_t)pk.R * sizeof(wrk::QueueReq));
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_pool, pk.pool.data(), pk.pool.size() * 4);
-    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_ctl, &ctl, sizeof ctl);
-    if (rc == WRK_OK && pk.kind.mirostat()) {
-        if (!f.alt_mu || pk.R > f.alt_mu_cap) return wrk_fail(ctx, WRK_E_ARG, "Mirostat rows are not prepared");
-        rc = wrk_buf_write_raw(ctx, f.alt_mu, pk.mu.data(), (size_t)pk.R * 4);
-    }
-    if (rc == WRK_OK && pk.kind.constrained) {
-        if (!f.gram_req || pk.R > f.gram_req_cap) return wrk_fail(ctx, WRK_E_ARG, "grammar states are not prepared");
-        rc = wrk_buf_write_raw(ctx, f.gram_req, pk.gram.data(), (size_t)pk.R * 4);
-    }
-    if (rc == WRK_OK && pk.kind.stop_seqs) {     // every slot's tail starts empty, no request has a match yet
+    // the per-request mu and automaton states live in groups that wrk_decode_prepare sized with the request count
+    if (pk.kind.mirostat() && !f.alt.holds({0, pk.R})) return wrk_fail(ctx, WRK_E_ARG, "Mirostat rows are not prepared");
+    if (pk.kind.constrained && !f.grammar.holds({0, pk.R})) return wrk_fail(ctx, WRK_E_ARG, "grammar states are not prepared");
+    wrk_upload up{ctx};
+    up(f.queue.slots, slots.data(), B)(f.queue.started, started.data(), B)(f.queue.log, log.data(), pk.R)(f.queue.reqs, pk.reqs.data(), pk.R);
+    up(f.queue.pool, pk.pool.data(), pk.pool.size())(f.queue.ctl, &ctl, 1);
+    if (pk.kind.mirostat()) up(f.alt.mu, pk.mu.data(), pk.R);
+    if (pk.kind.constrained) up(f.grammar.req, pk.gram.data(), pk.R);
+    if (pk.kind.stop_seqs) {     // every slot's tail starts empty, no request has a match yet
         const std::vector<uint32_t> tails((size_t)B * WRK_STOP_TAIL_LEN, WRK_STOP_TAIL_EMPTY), none(pk.R, WRK_STOP_MATCH_NONE);
-        rc = wrk_buf_write_raw(ctx, f.queue_seq_rows, pk.seq.rows.data(), (size_t)pk.R * sizeof(wrk::StopSeqRow));
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_seq_tail, tails.data(), tails.size() * 4);
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_seq_match, none.data(), (size_t)pk.R * 4);
+        up(f.queue_seq.rows, pk.seq.rows.data(), pk.R)(f.queue_seq.tail, tails.data(), tails.size())(f.queue_seq.match, none.data(), pk.R);
     }
-    if (rc == WRK_OK && pk.kind.pool()) {
+    if (pk.kind.pool()) {
         // the turnover list of "step -1": the slots that start at step 0, nothing to save
         std::vector<wrk::QueueTurn> turn(nstart);
         for (uint32_t b = 0; b < nstart; ++b) turn[b] = wrk::QueueTurn{b, wrk::QUEUE_NO_ENTRY, 1u, pk.start[b]};
         const wrk::QueueStateCtl sctl{pk.pool_states, pk.pool_entries, nstart};
-        rc = wrk_buf_write_raw(ctx, f.queue_entries, pk.start.data(), (size_t)pk.R * 4);
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_entries + f.queue_entry_cap, pk.save.data(), (size_t)pk.R * 4);
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_turn, turn.data(), (size_t)nstart * sizeof(wrk::QueueTurn));
-        if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, f.queue_state_ctl, &sctl, sizeof sctl);
+        up(f.queue_states.start, pk.start.data(), pk.R)(f.queue_states.save, pk.save.data(), pk.R);
+        up(f.queue_states.turn, turn.data(), nstart)(f.queue_states.ctl, &sctl, 1);
     }
-    if (rc != WRK_OK) return rc;
+    if (up.rc != WRK_OK) return up.rc;
     // the slots that start a request at step 0 are reset as the step that ends a request resets its slot
     if (pk.kind.pool()) wrk::queue_turnover(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), queue_state_bufs(f), B, ctx->num_cu);
     else wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), B, ctx->num_cu);
@@ -802,11 +643,11 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
 static int32_t draw_gate(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, wrk::RowGate& g) {
     g = wrk::RowGate{nullptr, 0u, 0u};
     if (kind.tail == wrk_step_kind::STOP) {
-        if (!f.stop_par || B > f.stop_cap) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
-        g = wrk::RowGate{&f.stop_par->done, sizeof(wrk::StopParam) / 4, 0u};
+        if (!f.stop.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
+        g = wrk::RowGate{&f.stop.par->done, sizeof(wrk::StopParam) / 4, 0u};
     } else if (kind.queue()) {
-        if (!f.queue_slots || B > f.queue_slot_cap) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
-        g = wrk::RowGate{&f.queue_slots->phase, sizeof(wrk::QueueSlot) / 4, wrk::QUEUE_REPLY};
+        if (!f.queue.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+        g = wrk::RowGate{&f.queue.slots->phase, sizeof(wrk::QueueSlot) / 4, wrk::QUEUE_REPLY};
     }
     return WRK_OK;
 }
@@ -817,18 +658,18 @@ static int32_t enqueue_occurrence_update(wrk_frame_common& f, uint32_t B, wrk_st
     wrk::RowGate gate;
     const int32_t rc = draw_gate(f, B, kind, gate);
     if (rc != WRK_OK) return rc;
-    wrk::occurrence_update(f.ctx->op_stream(), f.facts().num_vocab, B, f.pen_par, f.io().argmax, 1, gate);
+    wrk::occurrence_update(f.ctx->op_stream(), f.facts().num_vocab, B, f.penalty.par, f.io().argmax, 1, gate);
     return WRK_OK;
 }
 
 // the automaton states move on the drawn tokens in io.argmax (constrained kinds), under the step's gate
 static int32_t enqueue_grammar_advance(wrk_frame_common& f, uint32_t B, wrk_step_kind kind) {
     if (!kind.constrained) return WRK_OK;
-    if (!f.gram_par || B > f.gram_cap) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
+    if (!f.grammar.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
     wrk::RowGate gate;
     const int32_t rc = draw_gate(f, B, kind, gate);
     if (rc != WRK_OK) return rc;
-    wrk::grammar_advance(f.ctx->op_stream(), f.facts().num_vocab, B, f.gram_par, f.io().argmax, gate);
+    wrk::grammar_advance(f.ctx->op_stream(), f.facts().num_vocab, B, f.grammar.par, f.io().argmax, gate);
     return WRK_OK;
 }
 
@@ -845,18 +686,18 @@ static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind
     hipStream_t q = f.ctx->op_stream();
     const wrk::FrameIo& io = f.io();
     const uint32_t V = f.facts().num_vocab;
-    if (!f.queue_ctl || B > f.queue_slot_cap || b0 != 0 || B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
-    if (kind.stop_seqs && (!f.queue_seq_rows || B > f.queue_seq_slot_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "stop-sequence buffers are not prepared");
-    if (kind.pool() && (!f.queue_state_ctl || B > f.queue_turn_cap || ((size_t)(st->head_size + 2) * st->num_emb) % 4 != 0))
+    if (!f.queue.holds({B}) || b0 != 0 || B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+    if (kind.stop_seqs && !f.queue_seq.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "stop-sequence buffers are not prepared");
+    if (kind.pool() && (!f.queue_states.holds({B}) || ((size_t)(st->head_size + 2) * st->num_emb) % 4 != 0))
         return wrk_fail(f.ctx, WRK_E_ARG, "state pool buffers are not prepared");
     const int32_t rc = enqueue_draw_updates(f, B, kind);
     if (rc != WRK_OK) return rc;
     const wrk::QueueBufs bufs = queue_bufs(f, kind);
     if (kind.pool()) {
-        wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history, io.counter, bufs, queue_state_bufs(f), B);
+        wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history.tokens, io.counter, bufs, queue_state_bufs(f), B);
         wrk::queue_turnover(q, queue_geom(st, b0, V), bufs, queue_state_bufs(f), B, f.ctx->num_cu);
     } else {
-        wrk::advance_queue(q, io.argmax, io.tokens, f.history, io.counter, bufs, B);
+        wrk::advance_queue(q, io.argmax, io.tokens, f.history.tokens, io.counter, bufs, B);
         wrk::queue_reset(q, queue_geom(st, b0, V), bufs, B, f.ctx->num_cu);
     }
     return WRK_OK;
@@ -868,32 +709,32 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
     wrk_ctx* ctx = f.ctx;
     std::vector<wrk::QueueLog> log(pk.R);
     std::vector<uint32_t> hist((size_t)steps_run * B);
-    WRK_HIP(ctx, hipMemcpyAsync(log.data(), f.queue_log, (size_t)pk.R * sizeof(wrk::QueueLog), hipMemcpyDeviceToHost, ctx->stream));
-    if (!hist.empty()) WRK_HIP(ctx, hipMemcpyAsync(hist.data(), f.history, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(log.data(), f.queue.log, (size_t)pk.R * sizeof(wrk::QueueLog), hipMemcpyDeviceToHost, ctx->stream));
+    if (!hist.empty()) WRK_HIP(ctx, hipMemcpyAsync(hist.data(), f.history.tokens, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     const size_t nt = pk.lp.num_top;
     std::vector<float> lp_rows(pk.lp.on() ? hist.size() : 0), top_lp(lp_rows.size() * nt);
     std::vector<uint32_t> top_id(top_lp.size());
-    if (!lp_rows.empty()) WRK_HIP(ctx, hipMemcpyAsync(lp_rows.data(), f.lp_logprob, lp_rows.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (!lp_rows.empty()) WRK_HIP(ctx, hipMemcpyAsync(lp_rows.data(), f.logprob.logprob, lp_rows.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (!top_lp.empty()) {
-        WRK_HIP(ctx, hipMemcpyAsync(top_id.data(), f.lp_top_ids, top_id.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-        WRK_HIP(ctx, hipMemcpyAsync(top_lp.data(), f.lp_top_logprobs, top_lp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(top_id.data(), f.logprob.top_ids, top_id.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(top_lp.data(), f.logprob.top_logprobs, top_lp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     // Mirostat: a request that ended left its mu in alt_mu[r]; one still running has it in its slot's row
     std::vector<float> mu_req(pk.mu_out ? pk.R : 0);
     std::vector<wrk::SampleAlt> mu_slot(pk.mu_out ? B : 0);
     if (pk.mu_out) {
-        WRK_HIP(ctx, hipMemcpyAsync(mu_req.data(), f.alt_mu, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
-        WRK_HIP(ctx, hipMemcpyAsync(mu_slot.data(), f.alt_par, (size_t)B * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(mu_req.data(), f.alt.mu, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(mu_slot.data(), f.alt.par, (size_t)B * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost, ctx->stream));
     }
     // constrained: the same two places hold a request's automaton state
     std::vector<uint32_t> gram_req(pk.gram_out ? pk.R : 0), gram_slot(pk.gram_out ? B : 0);
     if (pk.gram_out) {
-        WRK_HIP(ctx, hipMemcpyAsync(gram_req.data(), f.gram_req, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
-        WRK_HIP(ctx, hipMemcpyAsync(gram_slot.data(), f.gram_state, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(gram_req.data(), f.grammar.req, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(gram_slot.data(), f.grammar.state, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     // stop sequences: a request's match word is written by the step that ends it with reason 1, and by nothing else
     std::vector<uint32_t> match(pk.match_out ? pk.R : 0);
-    if (pk.match_out) WRK_HIP(ctx, hipMemcpyAsync(match.data(), f.queue_seq_match, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (pk.match_out) WRK_HIP(ctx, hipMemcpyAsync(match.data(), f.queue_seq.match, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     size_t o = 0;
     for (uint32_t r = 0; r < pk.R; ++r) {
@@ -926,8 +767,8 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
 static wrk::StopGeom stop_geom(wrk_frame_common& f, const wrk_v7_state* st, uint32_t b0) {
     const wrk::FrameIo& io = f.io();
     wrk::StopGeom g{};
-    g.state = st->data; g.head_o = io.head_o; g.snap_state = f.stop_snap_state; g.snap_logits = f.stop_snap_logits;
-    g.just_ended = f.stop_just_ended(); g.par = f.stop_par; g.counter = io.counter; g.lengths = f.stop_lengths();
+    g.state = st->data; g.head_o = io.head_o; g.snap_state = f.stop.snap_state; g.snap_logits = f.stop.snap_logits;
+    g.just_ended = f.stop.just_ended(); g.par = f.stop.par; g.counter = io.counter; g.lengths = f.stop.lengths();
     g.layers = st->num_layer; g.num_batch = st->num_batch; g.b0 = b0; g.v = f.facts().num_vocab;
     g.slot = (size_t)(st->head_size + 2) * st->num_emb;
     return g;
@@ -938,15 +779,15 @@ static wrk::StopGeom stop_geom(wrk_frame_common& f, const wrk_v7_state* st, uint
 static int32_t enqueue_stop_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
     hipStream_t q = f.ctx->op_stream();
     const wrk::FrameIo& io = f.io();
-    if (!f.stop_par || B > f.stop_cap || b0 + B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
+    if (!f.stop.holds({B}) || b0 + B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
     const int32_t rc = enqueue_draw_updates(f, B, kind);
     if (rc != WRK_OK) return rc;
     if (kind.stop_seqs) {
-        if (!f.stopseq_rows || B > f.stopseq_cap) return wrk_fail(f.ctx, WRK_E_ARG, "stop-sequence buffers are not prepared");
-        wrk::advance_stop_seq(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(),
-                              wrk::StopSeqBufs{f.stopseq_rows, f.stopseq_tail, f.stopseq_match}, B);
+        if (!f.stop_seq.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "stop-sequence buffers are not prepared");
+        wrk::advance_stop_seq(q, io.argmax, io.tokens, f.history.tokens, io.counter, f.stop.par, f.stop.just_ended(), f.stop.live(),
+                              wrk::StopSeqBufs{f.stop_seq.rows, f.stop_seq.tail, f.stop_seq.match}, B);
     } else {
-        wrk::advance_stop(q, io.argmax, io.tokens, f.history, io.counter, f.stop_par, f.stop_just_ended(), f.stop_live(), B);
+        wrk::advance_stop(q, io.argmax, io.tokens, f.history.tokens, io.counter, f.stop.par, f.stop.just_ended(), f.stop.live(), B);
     }
     wrk::stop_snapshot(q, stop_geom(f, st, b0), B, f.ctx->num_cu);
     return WRK_OK;
@@ -958,26 +799,26 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     const uint32_t V = f.facts().num_vocab;
     const float* logits = io.head_o;
     if (kind.penalized) {
-        wrk::penalize_rows(q, io.head_o, V, V, B, f.pen_par, f.pen_o, V);
-        logits = f.pen_o;
+        wrk::penalize_rows(q, io.head_o, V, V, B, f.penalty.par, f.penalty.out, V);
+        logits = f.penalty.out;
     }
     // the mask: in place on the penalised row, else from head_o (which log-probs, last_logits and the stop snapshot keep raw) into con_o
     if (kind.constrained) {
-        if (!f.gram_par || B > f.gram_cap || V != f.gram_vocab_cap || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
-        float* masked = kind.penalized ? f.pen_o : f.con_o;
-        wrk::constrain_rows(q, logits, V, V, B, f.gram_par, masked, V);
+        if (!f.grammar.holds({B, 0, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
+        float* masked = kind.penalized ? f.penalty.out : f.grammar.out;
+        wrk::constrain_rows(q, logits, V, V, B, f.grammar.par, masked, V);
         logits = masked;
     }
     // the sampler only reads the counter: rows run in different workgroups, so the tail's advance moves it after all of them
     if (!kind.sampled()) {
         if (!argmax_done) wrk::argmax_rows(q, logits, V, V, B, io.argmax);
-    } else if (kind.filtered() && (!f.filter_par || B > f.filter_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
-    else if (kind.alt() && (!f.alt_par || B > f.alt_par_cap)) return wrk_fail(f.ctx, WRK_E_ARG, "Mirostat / typical rows are not prepared");
+    } else if (kind.filtered() && !f.filter.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
+    else if (kind.alt() && !f.alt.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "Mirostat / typical rows are not prepared");
     else {
         // mu moves exactly where an occurrence row counts a draw: both read the step's one gate
-        wrk::SamplePick pick{wrk::SAMPLE_PLAIN, f.sample_par, nullptr, nullptr, wrk::RowGate{nullptr, 0u, 0u}};
-        if (kind.filtered()) { pick.mode = wrk::SAMPLE_FILT; pick.filt = f.filter_par; }
-        if (kind.alt()) { pick.mode = kind.mirostat() ? wrk::SAMPLE_MIRO : wrk::SAMPLE_TYP; pick.alt = f.alt_par; }
+        wrk::SamplePick pick{wrk::SAMPLE_PLAIN, f.sample.par, nullptr, nullptr, wrk::RowGate{nullptr, 0u, 0u}};
+        if (kind.filtered()) { pick.mode = wrk::SAMPLE_FILT; pick.filt = f.filter.par; }
+        if (kind.alt()) { pick.mode = kind.mirostat() ? wrk::SAMPLE_MIRO : wrk::SAMPLE_TYP; pick.alt = f.alt.par; }
         if (kind.mirostat()) {
             const int32_t grc = draw_gate(f, B, kind, pick.gate);
             if (grc != WRK_OK) return grc;
@@ -987,15 +828,15 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     }
     // the picked tokens are in io.argmax and the tail has not moved the counter: row *counter of the frame's buffers, on the raw head output
     if (kind.logprobs) {
-        if (!f.lp_par || B > f.lp_batch_cap) return wrk_fail(f.ctx, WRK_E_ARG, "log-prob buffers are not prepared");
-        if (wrk::logprob_rows(q, io.head_o, V, V, B, io.argmax, io.counter, f.lp_par, f.lp_part, f.lp_keys, f.ctx->num_cu) != 0)
+        if (!f.logprob.holds({0, B})) return wrk_fail(f.ctx, WRK_E_ARG, "log-prob buffers are not prepared");
+        if (wrk::logprob_rows(q, io.head_o, V, V, B, io.argmax, io.counter, f.logprob.par, f.logprob.part, f.logprob.keys, f.ctx->num_cu) != 0)
             return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "log-probs: vocabulary of %u tokens", V);
     }
     if (kind.queue()) return enqueue_queue_tail(f, B, kind, st, b0);
     if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, B, kind, st, b0);
     const int32_t urc = enqueue_draw_updates(f, B, kind);
     if (urc != WRK_OK) return urc;
-    wrk::advance_tokens(q, io.argmax, io.tokens, f.history, io.counter, B);
+    wrk::advance_tokens(q, io.argmax, io.tokens, f.history.tokens, io.counter, B);
     return WRK_OK;
 }
 
@@ -1008,7 +849,7 @@ static constexpr uint32_t WRK_STOP_POLL_DEFAULT = 16;
 
 // Part 1 of a decode loop on lane `ln`: the frame, the upload of tokens / cursors / pick rows of its sequences, the buffers of the tail
 // (stop: the call's stop rows, queue: its tables -- whichever kind.tail names) and, unless WRK_NO_GRAPH=1, the cached step program.
-// Every ensure_* comes before the look-up: growing a buffer drops the programs.  One program per (state, first sequence, B, the runner's
+// Every group is grown before the look-up: growing a held group drops the programs.  One program per (state, first sequence, B, the runner's
 // key bits, step kind -- key() in the mode word, key2() in the second): the analogue of the reference's cached RnnJob for a repeated RnnInfo
 static int32_t lane_prepare(wrk_lane& ln, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t steps, uint32_t mode, wrk_step_kind kind,
                             const wrk_pick_params& rows, const wrk::StopParam* stop, const wrk_stopseq_pack* seq, const wrk_queue_pack* queue,
@@ -1060,7 +901,7 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
     hipEvent_t* poll_events = nullptr;
     if (polled) {
         for (const wrk_lane& ln : lanes)
-            if (!(kind.queue() ? (void*)ln.frame->queue_ctl : (void*)ln.frame->stop_par))
+            if (!(kind.queue() ? ln.frame->queue.held() : ln.frame->stop.held()))
                 return wrk_fail(ctx, WRK_E_ARG, "stop run on a lane without stop buffers");
         const int32_t rc = lanes[0].frame->ensure_poll((uint32_t)groups);
         if (rc != WRK_OK) return rc;
@@ -1092,7 +933,7 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
             run += n;
             for (size_t g = 0; g < groups; ++g) {
                 hipStream_t ls = groups == 1 ? ctx->stream : streams[g];
-                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, kind.queue() ? lanes[g].frame->queue_live() : lanes[g].frame->stop_live(), 4,
+                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, kind.queue() ? lanes[g].frame->queue.live() : lanes[g].frame->stop.live(), 4,
                                             hipMemcpyDeviceToHost, ls));
                 WRK_HIP(ctx, hipEventRecord(poll_events[(k & 1) * groups + g], ls));
             }
@@ -1118,26 +959,26 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
         // the frozen slots and logits rows go back (head_o is what the read-back below takes), the lengths come out
         for (const wrk_lane& ln : lanes) {
             wrk::stop_restore(ctx->stream, stop_geom(*ln.frame, st, ln.b0), ln.nb, ctx->num_cu);
-            WRK_HIP(ctx, hipMemcpyAsync(stop.out_lengths + ln.b0, ln.frame->stop_lengths(), (size_t)ln.nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+            WRK_HIP(ctx, hipMemcpyAsync(stop.out_lengths + ln.b0, ln.frame->stop.lengths(), (size_t)ln.nb * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
         WRK_LAUNCH_CHECK(ctx);
     }
     if (polled) *stop.steps_run = steps;
     for (const wrk_lane& ln : lanes) {
         if (out_tokens) {
-            if (groups == 1) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.frame->history, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
-            else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)B * 4, ln.frame->history, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
+            if (groups == 1) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.frame->history.tokens, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
+            else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)B * 4, ln.frame->history.tokens, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
                                                hipMemcpyDeviceToHost, ctx->stream));
         }
         if (lp.on() && steps) {
             // rows [steps][nb] of the lane into [steps][B] at its first sequence; the top arrays the same with num_top entries per sequence
             const size_t n = lp.num_top;
-            WRK_HIP(ctx, hipMemcpy2DAsync(lp.logprob + ln.b0, (size_t)B * 4, ln.frame->lp_logprob, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
+            WRK_HIP(ctx, hipMemcpy2DAsync(lp.logprob + ln.b0, (size_t)B * 4, ln.frame->logprob.logprob, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
                                           hipMemcpyDeviceToHost, ctx->stream));
             if (n) {
-                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_ids + ln.b0 * n, B * n * 4, ln.frame->lp_top_ids, ln.nb * n * 4, ln.nb * n * 4, steps,
+                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_ids + ln.b0 * n, B * n * 4, ln.frame->logprob.top_ids, ln.nb * n * 4, ln.nb * n * 4, steps,
                                               hipMemcpyDeviceToHost, ctx->stream));
-                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_logprobs + ln.b0 * n, B * n * 4, ln.frame->lp_top_logprobs, ln.nb * n * 4, ln.nb * n * 4, steps,
+                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_logprobs + ln.b0 * n, B * n * 4, ln.frame->logprob.top_logprobs, ln.nb * n * 4, ln.nb * n * 4, steps,
                                               hipMemcpyDeviceToHost, ctx->stream));
             }
         }
@@ -1207,19 +1048,19 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
     if (rc != WRK_OK) return rc;
     if (kind.mirostat() && pick.mirostat_mu) {      // every lane's rows hold the mu after the draws that counted
         for (const wrk_lane& ln : L) {
-            WRK_HIP(ctx, hipMemcpy(rows.alt.data() + ln.b0, ln.frame->alt_par, (size_t)ln.nb * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost));
+            WRK_HIP(ctx, hipMemcpy(rows.alt.data() + ln.b0, ln.frame->alt.par, (size_t)ln.nb * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost));
             for (uint32_t b = ln.b0; b < ln.b0 + ln.nb; ++b) pick.mirostat_mu[b] = rows.alt[b].mu;
         }
     }
     if (kind.constrained && pick.grammar_state)     // every lane's words hold the states after the draws that counted
         for (const wrk_lane& ln : L)
-            WRK_HIP(ctx, hipMemcpy(pick.grammar_state + ln.b0, ln.frame->gram_state, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
+            WRK_HIP(ctx, hipMemcpy(pick.grammar_state + ln.b0, ln.frame->grammar.state, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
     if (kind.stop_seqs)                             // and the match words and the tails, frozen with the sequences that ended
         for (const wrk_lane& ln : L) {
             if (stop->opt->out_stop_match)
-                WRK_HIP(ctx, hipMemcpy(stop->opt->out_stop_match + ln.b0, ln.frame->stopseq_match, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
+                WRK_HIP(ctx, hipMemcpy(stop->opt->out_stop_match + ln.b0, ln.frame->stop_seq.match, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
             if (stop->opt->stop_tail)
-                WRK_HIP(ctx, hipMemcpy(stop->opt->stop_tail + (size_t)ln.b0 * WRK_STOP_TAIL_LEN, ln.frame->stopseq_tail,
+                WRK_HIP(ctx, hipMemcpy(stop->opt->stop_tail + (size_t)ln.b0 * WRK_STOP_TAIL_LEN, ln.frame->stop_seq.tail,
                                        (size_t)ln.nb * WRK_STOP_TAIL_LEN * 4, hipMemcpyDeviceToHost));
         }
     return m->after_loop(groups);

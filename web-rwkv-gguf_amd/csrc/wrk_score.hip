@@ -113,30 +113,6 @@ int score_rows(hipStream_t st, const float* logits, uint32_t v, uint32_t stride,
 
 }  // namespace wrk
 
-int32_t wrk_score_scratch::ensure(wrk_ctx* ctx, uint32_t n, bool* grown) {
-    *grown = false;
-    if (n <= cap && buf) return WRK_OK;
-    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (buf) hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    *grown = true;
-    wrk_dev_layout lay;
-    const size_t o_tg = lay.add((size_t)n * 4), o_lp = lay.add((size_t)n * 4), o_rk = lay.add((size_t)n * 4);
-    const size_t o_part = lay.add((size_t)n * wrk::SCORE_MAX_SLICES * sizeof(wrk::ScorePart));
-    WRK_HIP(ctx, hipMalloc(&buf, lay.total));
-    char* b = (char*)buf;
-    targets = (uint32_t*)(b + o_tg); logprob = (float*)(b + o_lp); rank = (uint32_t*)(b + o_rk); part = (wrk::ScorePart*)(b + o_part);
-    cap = n;
-    return WRK_OK;
-}
-
-void wrk_score_scratch::release() {
-    if (buf) hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-}
-
 int32_t wrk_score_check_targets(wrk_ctx* ctx, const uint32_t* targets, uint32_t n, uint32_t V) {
     WRK_ARG(ctx, n == 0 || targets, "targets required");
     for (uint32_t h = 0; h < n; ++h) WRK_ARG(ctx, targets[h] < V, "target %u: id %u >= vocab %u", h, targets[h], V);

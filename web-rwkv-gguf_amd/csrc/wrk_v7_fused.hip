@@ -519,7 +519,7 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         if (rc != WRK_OK) return rc;
         if (want_argmax && NH) {
             argmax_rows(q, s.head_o, V, V, NH, s.argmax);
-            if (advance) advance_tokens(q, s.argmax, s.tokens, history, s.counter, NH);
+            if (advance) advance_tokens(q, s.argmax, s.tokens, history.tokens, s.counter, NH);
         }
         return WRK_OK;
     }
@@ -724,7 +724,7 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         if (!head_mv && matmul_mfma(q, j, ctx->num_cu) == 0) {
             if (want_argmax) {
                 wrk::argmax_rows(q, (const float*)s.head_o, V, V, NH, s.argmax);
-                if (advance) wrk::advance_tokens(q, s.argmax, s.tokens, history, s.counter, NH);
+                if (advance) wrk::advance_tokens(q, s.argmax, s.tokens, history.tokens, s.counter, NH);
             }
         } else {
             if (want_argmax) {
@@ -734,7 +734,7 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
             }
             if (matvec(q, &j, 1, ctx->num_cu) != 0) return wrk_fail(ctx, WRK_E_ARG, "fused head rejected");
             if (want_argmax)
-                argmax_finish(q, amax_val, amax_idx, nwg, NH, s.argmax, advance ? s.tokens : nullptr, history, advance ? s.counter : nullptr);
+                argmax_finish(q, amax_val, amax_idx, nwg, NH, s.argmax, advance ? s.tokens : nullptr, history.tokens, advance ? s.counter : nullptr);
         }
     }
 #undef LN
