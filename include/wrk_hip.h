@@ -456,6 +456,43 @@ int32_t wrk_constrain_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, 
  * u32 [num_rows], in/out; tokens: host u32 [num_rows], each < num_vocab.  Blocking. */
 int32_t wrk_grammar_advance(wrk_ctx* ctx, const wrk_grammar* grammar, uint32_t* states, const uint32_t* tokens, uint32_t num_rows);
 
+/* DRY ("don't repeat yourself": text-generation-webui, koboldcpp, llama.cpp's dry_multiplier / dry_base / dry_allowed_length /
+ * dry_sequence_breakers) and the hard ban of the same match (Hugging Face's no_repeat_ngram_size), on the device.  Both look at the ORDER
+ * of what a sequence generated, which the occurrence table cannot: a token window has num_batch slots (slot b belongs to state slot b),
+ * each the last `capacity` tokens that counted, oldest first, kept as a ring on the device; a push into a full slot drops the oldest.
+ * 1 <= capacity <= WRK_MAX_TOKEN_WINDOW, every stored id < num_vocab, num_vocab <= 2^20 (beyond it WRK_E_UNSUPPORTED).
+ * Match length.  A row has the window w[0..n), last = w[n-1], and the call-wide breaker set Bk (at most WRK_MAX_DRY_BREAKERS ids).
+ * If n < 2 or last is in Bk nothing matches.  Else for every i in [0, n-2] with w[i] == last and t = w[i+1] not in Bk: m = 1; while
+ * m < WRK_DRY_MAX_MATCH and i - m >= 0 and w[i-m] == w[n-1-m] and w[n-1-m] is not in Bk, m += 1; M[t] = max(M[t], m).  Tokens never
+ * reached have M = 0.  (text-generation-webui's loop with llama.cpp's cap.)
+ * Row parameters: multiplier finite >= 0, base finite >= 1, allowed_length in [1, WRK_DRY_MAX_MATCH], no_repeat_ngram 0 or in
+ * [2, WRK_DRY_MAX_MATCH + 1]; anything else is WRK_E_ARG.  The host computes pen[m] = 0 for m < allowed_length, else p_0 = (double)
+ * multiplier, p_{k+1} = p_k * (double)base (one f64 rounding per product), pen[m] = min(FLT_MAX, (float)p_{m - allowed_length}): the
+ * same table on every IEEE host, and a finite penalty never meets a +inf logit as inf - inf.
+ * Row result for token t with M = M[t]: -inf if no_repeat_ngram != 0 and M >= no_repeat_ngram - 1; else x[t] - pen[M] (one f32
+ * subtraction) if multiplier != 0 and M >= allowed_length; else the input bits unchanged (NaN payloads and -0 included).  With no
+ * breakers the ban is exactly no_repeat_ngram_size over the window; a row with multiplier == 0 and no_repeat_ngram == 0 is its input
+ * bit for bit. */
+#define WRK_MAX_TOKEN_WINDOW 4096
+#define WRK_MAX_DRY_BREAKERS 16
+#define WRK_DRY_MAX_MATCH 50
+typedef struct wrk_token_window wrk_token_window;
+int32_t wrk_token_window_create(wrk_ctx* ctx, uint32_t num_batch, uint32_t num_vocab, uint32_t capacity, wrk_token_window** out);  /* empty slots */
+int32_t wrk_token_window_destroy(wrk_token_window* window);
+/* pushes tokens[0], tokens[1], ... into slot `batch` in order (e.g. a prompt); every id < num_vocab */
+int32_t wrk_token_window_add(wrk_ctx* ctx, wrk_token_window* window, uint32_t batch, const uint32_t* tokens, uint32_t n);
+/* tokens_out: host u32 [capacity], receives the slot's tokens oldest first; *len: how many */
+int32_t wrk_token_window_back(wrk_ctx* ctx, const wrk_token_window* window, uint32_t batch, uint32_t* tokens_out, uint32_t* len);
+/* the slot becomes tokens[0..n) (n <= capacity, oldest first); tokens NULL: the slot becomes empty */
+int32_t wrk_token_window_load(wrk_ctx* ctx, wrk_token_window* window, uint32_t batch, const uint32_t* tokens_or_null, uint32_t n);
+/* applies the row result above to f32 logits [num_rows][row_stride] (first num_vocab used) in place; row r uses slot first_batch + r
+ * and multiplier[r], base[r], allowed_length[r], no_repeat_ngram[r] (host arrays [num_rows]; any may be NULL: 0 (off) / 1.75 / 2 / 0
+ * (off)); breakers: host u32 [num_breakers], each < num_vocab, may be NULL with num_breakers 0.  The window is only read.  Blocking.
+ * In a host-side loop it goes between wrk_penalize_logits and wrk_constrain_logits. */
+int32_t wrk_dry_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                       const wrk_token_window* window, uint32_t first_batch, const float* multiplier, const float* base,
+                       const uint32_t* allowed_length, const uint32_t* no_repeat_ngram, const uint32_t* breakers, uint32_t num_breakers);
+
 /* Stop tokens in the decode loops.  Sequence b has the stop set stop_tokens[stop_offsets[b] .. stop_offsets[b + 1]) (CSR, num_batch + 1
  * offsets, at most WRK_MAX_STOP_TOKENS ids each, every id < num_vocab).  Step i feeds x_i (x_0 = first_tokens[b]) and draws y_i; a
  * sequence that has not ended and whose y_i is in its stop set ends at step i: out_lengths[b] = i + 1 (the stop token is part of the
@@ -531,7 +568,22 @@ int32_t wrk_grammar_advance(wrk_ctx* ctx, const wrk_grammar* grammar, uint32_t* 
  * decrease, more than WRK_MAX_STOP_SEQUENCES for one owner, a stop sequence of length 0 or above WRK_MAX_STOP_SEQUENCE_LEN, an id >=
  * num_vocab, out_stop_match or stop_tail without the three arrays, a stop_tail entry that is neither EMPTY nor < num_vocab, an EMPTY
  * entry after a non-EMPTY one.  The stop sequences are device data: one cached step program serves any of them.  Tokens, lengths,
- * matches and tails do not depend on the number of lanes.  The five fields sit between grammar_state and mirostat_tau. */
+ * matches and tails do not depend on the number of lanes.  The five fields sit between grammar_state and mirostat_tau.
+ * DRY and the n-gram ban.  `window` (NULL: off) makes every pick see its row as wrk_dry_logits leaves it with slot b of the window and
+ * (dry_multiplier[b], dry_base[b], dry_allowed_length[b], no_repeat_ngram[b]) (host arrays [num_batch], any may be NULL as there) and
+ * the call-wide dry_breakers [num_dry_breakers], and every draw that counts is pushed into slot b -- inside the step program.  Order
+ * within a step: penalties, then DRY (in place on the penalised row, else on a copy of the head output), then the grammar mask (in
+ * place on that row), then the call's pick -- bit for bit the pick of the same call on that row; with no sampler arrays the arg-max,
+ * the deterministic "no loops" mode -- then log-probs, which stay on the raw head output, then the tail.  The window takes a draw
+ * exactly where an occurrence row counts it and a Mirostat mu moves: every step up to and including the one that ends the sequence,
+ * none after it; x_0 is not pushed.  After the call slot b has taken exactly out_lengths[b] pushes; a session carries the window from
+ * call to call in the handle.  A window with all four parameter arrays NULL still runs the DRY step programs and records the draws;
+ * window NULL runs exactly the programs that ran before.  WRK_E_ARG before any launch: a parameter or breaker array without a
+ * window, a window of another context or another num_vocab or with fewer slots than num_batch, more than WRK_MAX_DRY_BREAKERS
+ * breakers, a breaker >= num_vocab, num_dry_breakers > 0 with dry_breakers NULL, the value ranges of wrk_dry_logits.  The window, the
+ * tables and the breakers are device data: one cached step program serves any of them.  Tokens and final windows do not depend on the
+ * number of lanes.  If bans, a grammar and the n-gram ban together leave a row with no finite logit, the picked id is unspecified but
+ * < num_vocab and nothing faults.  The seven fields sit between out_top_logprobs and grammar. */
 #define WRK_MAX_STOP_TOKENS 16
 #define WRK_MAX_STOP_SEQUENCES 8
 #define WRK_MAX_STOP_SEQUENCE_LEN 8
@@ -550,6 +602,10 @@ typedef struct wrk_generate_options {
     float *out_logprob;
     uint32_t *out_top_ids;
     float *out_top_logprobs;
+    wrk_token_window *window;
+    const float *dry_multiplier, *dry_base;
+    const uint32_t *dry_allowed_length, *no_repeat_ngram, *dry_breakers;
+    uint32_t num_dry_breakers;
     const wrk_grammar *grammar;
     uint32_t *grammar_state;
     const uint32_t *stop_seq_tokens, *stop_seq_offsets, *stop_seq_owners;
@@ -632,7 +688,13 @@ int32_t wrk_stop_sequences_advance(wrk_ctx* ctx, uint32_t num_vocab, uint32_t nu
  * request left -- and is not returned.  A match ends the request with reason 1 exactly as a stop token does: the slot resets and
  * refills in the same step and a pool entry is saved as for a stop token.  out_stop_match (host u32 [num_requests], may be NULL):
  * WRK_STOP_MATCH_NONE for reasons 0, 2 and 3, else as in wrk_generate_options.  The tail is not part of a state-pool entry.  The four
- * fields sit between grammar_state and mirostat_tau. */
+ * fields sit between grammar_state and mirostat_tau.
+ * DRY and the n-gram ban, as in wrk_generate_options: `window` has at least num_batch slots and slot b serves whatever request runs
+ * on state slot b; dry_multiplier / dry_base / dry_allowed_length / no_repeat_ngram are per request [num_requests], the breakers are
+ * call-wide.  A slot's window is set to length 0 when a request is dispatched to it, at step 0 or at a refill on the device, and
+ * takes only that request's reply draws: prompt tokens and the discarded draws of the steps that feed them never enter it.  After
+ * the call rows [0, num_batch) of the window are unspecified.  The window is not part of a state-pool entry.  The seven fields sit
+ * between out_top_logprobs and grammar. */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
     const uint32_t *prompt_tokens, *prompt_offsets, *max_new;
@@ -647,6 +709,10 @@ typedef struct wrk_queue_options {
     float *out_logprob;
     uint32_t *out_top_ids;
     float *out_top_logprobs;
+    wrk_token_window *window;
+    const float *dry_multiplier, *dry_base;
+    const uint32_t *dry_allowed_length, *no_repeat_ngram, *dry_breakers;
+    uint32_t num_dry_breakers;
     const wrk_grammar *grammar;
     uint32_t *grammar_state;
     const uint32_t *stop_seq_tokens, *stop_seq_offsets, *stop_seq_owners;

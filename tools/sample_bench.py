@@ -31,8 +31,15 @@ A ninth leg (--stop-seq): the stop-sequence step program with 8
 the stop program with 16 ids that never match and against the plain sampled step, alternating, with the run-to-run spread of each; at the
 runtime's full batch the same for a queue whose requests never end.  The stop-sequence program has the launch count of the stop program.
 
+A tenth leg (--dry): the decode loop with a token window and DRY at text-generation-webui's defaults (multiplier 0.8, base 1.75,
+allowed_length 2) against the same loop without a window -- both through the options entry point without stop sets, so
+the step programs differ by the row copy, dry_rows and window_push alone -- for the greedy and the plain-sampler pick, alternating, with
+the run-to-run spread of each; and the kernel's worst case: one-step calls whose windows hold 4096 equal tokens (4095 candidates that
+all reach the cap and meet at one token) against one-step calls whose windows hold one token.
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
                                  [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9] [--grammar] [--stop-seq]
+                                 [--dry]
 
 Prints one JSON object.
 """
@@ -303,6 +310,66 @@ def grammar_leg(rt, ctx, first, V, args):
     return res
 
 
+def dry_leg(rt, ctx, first, V, args):
+    """Per pick (greedy, sampled): medians of the per-step time of generate_stop without stop sets, with a token window and DRY against
+    without, alternating in one process; every call starts from the same state and from empty windows.  Then the worst case."""
+    import hashlib
+    import wrk
+    B = len(first)
+    win = wrk.TokenWindow(ctx, B, V, 1024)
+    big = wrk.TokenWindow(ctx, B, V, wrk.MAX_TOKEN_WINDOW)
+    start = [rt.state_read(b) for b in range(B)]
+    dkw = dict(dry=(0.8, 1.75, 2))
+
+    def run(pick, steps=args.steps, **kw):
+        for b in range(B):
+            rt.state_write(start[b], b)
+        tok, _ = rt.generate_stop(first, steps, [], poll_steps=POLL_OFF, **pick, **kw)
+        return tok, rt.last_stop_ms / steps
+
+    def with_dry(pick):
+        for b in range(B):
+            win.load(b)
+        return run(pick, window=win, **dkw)
+    res = {}
+    for name, pick in (("greedy", {}), ("sample", dict(temperature=args.temperature, top_p=args.top_p))):
+        want, _ = run(pick)
+        con, _ = with_dry(pick)                                            # capture and warm up
+        base, with_, same = [], [], True
+        for _ in range(args.reps):
+            tok, ms = run(pick)
+            same &= bool(np.array_equal(tok, want))
+            base.append(ms)
+            tok, ms = with_dry(pick)
+            same &= bool(np.array_equal(tok, con))
+            with_.append(ms)
+        bm, wm = float(np.median(base)), float(np.median(with_))
+        res[name] = {"same_tokens_every_rep": same, "dry_differs_from_plain": bool(not np.array_equal(want, con)),
+                     "without_tokens_sha1": hashlib.sha1(np.ascontiguousarray(want).tobytes()).hexdigest(),
+                     "without_ms_per_step": round(bm, 5), "without_spread_us": round((max(base) - min(base)) * 1e3, 2),
+                     "without_ms_all": [round(x, 5) for x in base],
+                     "with_ms_per_step": round(wm, 5), "with_spread_us": round((max(with_) - min(with_)) * 1e3, 2),
+                     "with_ms_all": [round(x, 5) for x in with_], "with_minus_without_us": round((wm - bm) * 1e3, 2)}
+    # the worst case: every window holds 4096 times one token, so 4095 candidates walk to the cap and meet at that token's scratch word
+    full, one = [], []
+    for _ in range(args.reps + 1):
+        for b in range(B):
+            big.load(b, [7] * wrk.MAX_TOKEN_WINDOW)
+        full.append(run({}, steps=1, window=big, **dkw)[1])
+        for b in range(B):
+            big.load(b, [7])
+        one.append(run({}, steps=1, window=big, **dkw)[1])
+    full, one = full[1:], one[1:]                                          # the first pair captures the one-step program
+    res["worst_case_one_step"] = {"window": "4096 equal tokens", "full_ms": round(float(np.median(full)), 5), "one_token_ms": round(float(np.median(one)), 5),
+                                  "full_minus_one_token_us": round((float(np.median(full)) - float(np.median(one))) * 1e3, 2),
+                                  "full_ms_all": [round(x, 5) for x in full], "one_token_ms_all": [round(x, 5) for x in one]}
+    for b in range(B):
+        rt.state_write(start[b], b)
+    win.close()
+    big.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -322,6 +389,7 @@ def main():
     ap.add_argument("--typical", type=float, default=None, help="typical_p, e.g. 0.9")
     ap.add_argument("--grammar", action="store_true", help="the constrained loop against the same loop without a grammar")
     ap.add_argument("--stop-seq", action="store_true", help="the stop-sequence programs against the stop programs and the sampled step")
+    ap.add_argument("--dry", action="store_true", help="the loop with a token window and DRY against the same loop without")
     args = ap.parse_args()
     import wrk
 
@@ -411,6 +479,10 @@ def main():
             out["grammar_note"] = ("two states, four token classes (id mod 4), two classes allowed per state; a constrained step adds two "
                                    "launches to the step program: constrain_rows before the pick and grammar_advance in the tail")
             out["batches"][-1]["grammar"] = grammar_leg(rt, ctx, first, V, args)
+        if args.dry:
+            out["dry_note"] = ("multiplier 0.8, base 1.75, allowed_length 2, no breakers, windows of 1024 tokens that start empty; a DRY step "
+                               "adds three launches to the step program: copy_rows and dry_rows before the pick, window_push in the tail")
+            out["batches"][-1]["dry"] = dry_leg(rt, ctx, first, V, args)
     if occ is not None:
         occ.close()
     rt.close()

@@ -261,6 +261,24 @@ void constrain_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_st
                     uint32_t dst_stride);
 void grammar_advance(hipStream_t s, uint32_t v, uint32_t n, const GrammarParam* par, const uint32_t* tokens, const RowGate& gate);
 
+// wrk_dry.hip: DRY and the no-repeat-n-gram ban.  One DryParam per row: the row's slot of a token window -- ring [cap] of
+// ids, meta = (length, next write position) -- and the row's values, pen[m] the host-computed penalty of a match of m tokens (0 below
+// allowed_length).  DryBreakers: the call's breaker ids.  Both are device data, in a decode loop per-frame buffers written before
+// every call, so a captured step never holds a window pointer of its own.  dry_rows: row r of x [n][stride] in place -- per token the
+// longest match M that the token would extend (text-generation-webui's loop, capped at WRK_DRY_MAX_MATCH), then -inf for
+// no_repeat != 0 && M >= no_repeat - 1, else x - pen[M] for multiplier != 0 && M >= allowed; every other element keeps its bits.
+// scratch: u32 [n][v], all zero before and after every launch.  copy_rows: dst row r = src row r, bit for bit (the head output into the
+// rows dry_rows then works on).  window_push: slot r takes tokens[r]; a row whose draw does not count (gate) is left alone
+struct DryParam {
+    uint32_t* ring; uint32_t* meta; uint32_t cap;
+    uint32_t allowed, no_repeat; float multiplier;
+    float pen[WRK_DRY_MAX_MATCH + 2];       // [0, WRK_DRY_MAX_MATCH]; one entry of padding keeps the row a multiple of 8 bytes
+};
+struct DryBreakers { uint32_t count; uint32_t ids[WRK_MAX_DRY_BREAKERS]; };
+void dry_rows(hipStream_t s, float* x, uint32_t v, uint32_t stride, uint32_t n, const DryParam* par, const DryBreakers* brk, uint32_t* scratch);
+void copy_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_stride, uint32_t n, float* dst, uint32_t dst_stride);
+void window_push(hipStream_t s, uint32_t v, uint32_t n, const DryParam* par, const uint32_t* tokens, const RowGate& gate);
+
 // wrk_stop.hip: stop tokens in the decode loops.  One StopParam per sequence in a per-frame device buffer written
 // before every call: the stop ids are data, one captured program serves any stop sets.  done / length / end_token are the device's:
 // the step that draws a stop id sets them (length = step + 1: the stop token is part of the output)
@@ -325,6 +343,10 @@ struct QueueBufs {
     // dispatched, its final value once it has ended, exactly as alt_mu; both nullptr without a grammar
     uint32_t* gram_state = nullptr;
     uint32_t* gram_req = nullptr;
+    // queues with a token window: the frame's DryParam rows [B] and dry_req [R]: request r's values (its ring / meta are
+    // not read).  A slot that takes a request gets the request's values and a window of length 0; both nullptr without a window
+    DryParam* dry_par = nullptr;
+    const DryParam* dry_req = nullptr;
     // queues with stop sequences: seq_rows [R]: request r's stop sequences; seq_tail [B][WRK_STOP_TAIL_LEN]: the slot's
     // tail, set empty where the slot takes a request; seq_match [R]: request r's match word (NONE until a stop ends it); all nullptr
     // without stop sequences
@@ -468,3 +490,26 @@ struct wrk_grammar {
 // validated start states of n rows (WRK_E_ARG on a NULL grammar, a grammar of another context or another vocabulary, a state >=
 // num_states); state NULL: all 0
 int32_t wrk_grammar_pack(wrk_ctx* ctx, const wrk_grammar* g, const uint32_t* state, uint32_t n, uint32_t V, std::vector<uint32_t>& out);
+
+// include/wrk_hip.h wrk_token_window: one allocation holding the rings u32 [num_batch][capacity] and meta u32 [num_batch][2]
+// (length, next write position)
+struct wrk_token_window {
+    wrk_ctx* ctx = nullptr;
+    uint32_t num_batch = 0, num_vocab = 0, capacity = 0;
+    void* mem = nullptr;
+    uint32_t* ring = nullptr;
+    uint32_t* meta = nullptr;
+};
+// the DRY fields of a call (wrk_generate_options / wrk_queue_options / wrk_dry_logits); the four parameter arrays may be NULL
+struct wrk_dry_args {
+    wrk_token_window* window = nullptr;
+    const float *multiplier = nullptr, *base = nullptr;
+    const uint32_t *allowed_length = nullptr, *no_repeat_ngram = nullptr, *breakers = nullptr;
+    uint32_t num_breakers = 0;
+    bool any_array() const { return multiplier || base || allowed_length || no_repeat_ngram || breakers || num_breakers; }
+};
+// validated DryParam rows of n owners and the breaker block (WRK_E_ARG on a NULL window, a window of another context or another
+// vocabulary, slots out of range, a value outside its range, too many breakers or one >= V; WRK_E_UNSUPPORTED on V > 2^20).  Row r
+// names slot first + r for r < slots, slot `first` beyond (a queue keeps only the values of its request rows)
+int32_t wrk_dry_pack(wrk_ctx* ctx, const wrk_dry_args& a, uint32_t first, uint32_t n, uint32_t slots, uint32_t V, std::vector<wrk::DryParam>& rows,
+                     wrk::DryBreakers& brk);

@@ -100,6 +100,15 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
                 // still holds its start value)
                 if (Q.alt_par) Q.alt_par[i] = SampleAlt{q->tau, q->eta, Q.alt_mu ? Q.alt_mu[r] : 0.0f, q->typical_p};
                 if (Q.gram_req) Q.gram_state[i] = Q.gram_req[r];        // the same for its automaton state
+                // its DRY values and table, and an empty window: window_push, in front of this launch, has pushed the last draw of the
+                // request that ended, and the next launch that reads the slot's window is the next step's dry_rows
+                if (Q.dry_par) {
+                    DryParam* dp = Q.dry_par + i;
+                    const DryParam* dq = Q.dry_req + r;
+                    dp->allowed = dq->allowed; dp->no_repeat = dq->no_repeat; dp->multiplier = dq->multiplier;
+                    for (uint32_t m = 0; m <= WRK_DRY_MAX_MATCH; ++m) dp->pen[m] = dq->pen[m];
+                    dp->meta[0] = 0u; dp->meta[1] = 0u;
+                }
                 if (SEQ) stop_tail_clear(Q.seq_tail + (size_t)i * STOP_TAIL);      // and its tail starts empty
                 if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
                 Q.log[r] = QueueLog{0u, 3u, i, step + 1};

@@ -97,6 +97,10 @@ struct wrk_step_kind {
     // a STOP or queue tail that also matches stop sequences (wrk_stopseq_dev.h): advance_stop_seq / the queue's _seq kernels
     // on the frame's stop-sequence buffers, in the place and with the launch count of the tail without them
     bool stop_seqs = false;
+    // DRY / the n-gram ban (wrk_dry.hip): between the penalise and the mask, dry_rows on dry_par -- in place on pen_o when
+    // penalised, else on dry.out = a copy of head_o -- and the tail pushes the draw into the token window where it updates the occurrence
+    // rows, under the same gate
+    bool dry = false;
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
     bool mirostat() const { return pick == MIROSTAT; }
@@ -110,9 +114,9 @@ struct wrk_step_kind {
         return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29 |
                (uint32_t)constrained << 31;
     }
-    // The kind's bits of GraphKey::mode2, the word that takes what key() has no room for: stop sequences 0.  0 for every kind that existed
-    // before the word did, so their keys compare as they always have
-    uint32_t key2() const { return (uint32_t)stop_seqs; }
+    // The kind's bits of GraphKey::mode2, the word that takes what key() has no room for: stop sequences 0, DRY 1.  0 for every kind that
+    // existed before the word did, and bit 0 alone for every stop-sequence kind, so their keys compare as they always have
+    uint32_t key2() const { return (uint32_t)stop_seqs | (uint32_t)dry << 1; }
 };
 
 // ------------------------------------------------------------------ the buffer groups of a frame (Pieces of wrk_dev_group)
@@ -161,6 +165,23 @@ struct wrk_grammar_bufs {
     uint32_t* req = nullptr;
     void layout(wrk_dev_cut& c, const size_t* d) {
         c.take(par, sizeof(wrk::GrammarParam)); c.take(state, d[0] * 4); c.take(out, d[0] * d[2] * 4); c.take(req, d[1] * 4);
+    }
+};
+// DRY / the n-gram ban (wrk_dry.hip).  par: the sequences' DryParam rows (window slot, values, penalty table: one program
+// serves any window and any parameters); brk: the call's breaker ids; out [B][V]: the copy of the head output that a pick without
+// penalties is made on; scratch u32 [B][V]: dry_rows' per-token maxima, zero between launches; req: a queue's per-request rows
+// (wrk::QueueBufs::dry_req)
+struct wrk_dry_bufs {
+    static constexpr int DIMS = 3;              // sequences, requests (>= 1), vocabulary
+    static constexpr unsigned EXACT = 4;
+    wrk::DryParam* par = nullptr;
+    wrk::DryBreakers* brk = nullptr;
+    float* out = nullptr;
+    uint32_t* scratch = nullptr;
+    wrk::DryParam* req = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(par, d[0] * sizeof(wrk::DryParam)); c.take(brk, sizeof(wrk::DryBreakers)); c.take(out, d[0] * d[2] * 4);
+        c.take(scratch, d[0] * d[2] * 4); c.take(req, d[1] * sizeof(wrk::DryParam));
     }
 };
 // wrk_v*_score (wrk_score.hip): targets / logprob / rank of the header rows and their slice partials [rows][SCORE_MAX_SLICES]
@@ -298,6 +319,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_alt_bufs> alt;
     wrk_dev_group<wrk_penalty_bufs> penalty;
     wrk_dev_group<wrk_grammar_bufs> grammar;
+    wrk_dev_group<wrk_dry_bufs> dry;
     wrk_dev_group<wrk_score_bufs> score;
     wrk_dev_group<wrk_stop_bufs> stop;
     wrk_dev_group<wrk_seq_bufs> stop_seq;           // generate_stop: rows, tails and match words per sequence
@@ -306,7 +328,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_queue_state_bufs> queue_states;
     wrk_dev_group<wrk_logprob_bufs> logprob;
     template <class F> void each_group(F&& f) {     // the one list of the groups
-        f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
+        f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
         f(queue_states); f(logprob);
     }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
@@ -353,7 +375,8 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
 // ------------------------------------------------------------------ the decode loops (generate_greedy ... generate_queue)
 // the ABI's pick arrays, of wrk_generate_options / wrk_queue_options (wrk_pick_of) or of an entry point's own arguments, validated in
 // one place (WRK_E_ARG): all three sampler arrays or none (the arg-max); penalty arrays only with a table; a table, a filter, Mirostat
-// or typical only with the sampler arrays; one family of filter / Mirostat / typical per call; grammar_state only with a grammar (which any pick may have).  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
+// or typical only with the sampler arrays; one family of filter / Mirostat / typical per call; grammar_state only with a grammar (which
+// any pick may have); the DRY arrays only with a token window (which any pick may have), its values in their ranges.  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
 struct wrk_pick_args {
     const float *temperature = nullptr, *top_p = nullptr; const uint32_t* seed = nullptr;
     const float *presence = nullptr, *frequency = nullptr, *decay = nullptr; wrk_occurrence* occ = nullptr;
@@ -361,11 +384,13 @@ struct wrk_pick_args {
     const float *mirostat_tau = nullptr, *mirostat_eta = nullptr; float* mirostat_mu = nullptr;     // tau set: a Mirostat pick; mu: in / out
     const float* typical_p = nullptr;                                   // set: a typical pick
     const wrk_grammar* grammar = nullptr; uint32_t* grammar_state = nullptr;    // grammar set: a constrained pick; grammar_state: in / out
+    wrk_dry_args dry;                                                   // window set: a DRY pick
     enum Need { ANY, SAMPLER, TABLE } need = ANY;
 };
 template <class Options> wrk_pick_args wrk_pick_of(const Options& o) {
     return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p,
-            o.mirostat_tau, o.mirostat_eta, o.mirostat_mu, o.typical_p, o.grammar, o.grammar_state};
+            o.mirostat_tau, o.mirostat_eta, o.mirostat_mu, o.typical_p, o.grammar, o.grammar_state,
+            wrk_dry_args{o.window, o.dry_multiplier, o.dry_base, o.dry_allowed_length, o.no_repeat_ngram, o.dry_breakers, o.num_dry_breakers}};
 }
 // the log-prob outputs of a call (wrk_generate_options / wrk_queue_options); logprob NULL: off
 struct wrk_logprob_call {
@@ -373,11 +398,11 @@ struct wrk_logprob_call {
     bool on() const { return logprob != nullptr; }
 };
 bool wrk_no_graph();        // WRK_NO_GRAPH=1: the decode loops enqueue every step instead of replaying a program
-// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the penalise launch (penalised), the mask
-// launch (constrained), the arg-max or sampler launch on the resulting row and the frame's parameters at step *counter -- neither with
-// `argmax_done`: the head launch has left the arg-max in io().argmax (RWKV-7's fused greedy head, never in a constrained step) -- with
+// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the penalise launch (penalised), the DRY
+// launches (dry: the row copy unless penalised, then dry_rows), the mask launch (constrained), the arg-max or sampler launch on the resulting row and the frame's parameters at step *counter -- neither with
+// `argmax_done`: the head launch has left the arg-max in io().argmax (RWKV-7's fused greedy head, never in a constrained or a DRY step) -- with
 // kind.logprobs the log-prob launches on head_o (never pen_o) and io().argmax into row
-// *counter of the frame's log-prob buffers, then the tail: the occurrence update (penalised) and the automaton advance (constrained) that belong to it, its advance of
+// *counter of the frame's log-prob buffers, then the tail: the occurrence update (penalised), the automaton advance (constrained) and the window push (dry) that belong to it, its advance of
 // tokens / history / counter, and stop_snapshot / queue_reset / queue_turnover
 int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, bool argmax_done);
 

@@ -166,6 +166,10 @@ struct wrk_pick_params {    // validated rows; empty: the arg-max / without pena
     const wrk_grammar* grammar = nullptr;   // a constrained pick: the automaton and the state every row starts in
     std::vector<uint32_t> gram_state;
     uint32_t gram_requests = 0;             // a queue: its requests (the size of the frame's per-request state array)
+    bool has_dry = false;                   // a DRY pick: the rows' window slots, values and tables, and the call's breakers
+    std::vector<wrk::DryParam> dry;
+    wrk::DryBreakers brk{};
+    uint32_t dry_requests = 0;              // a queue: its requests (the size of the frame's per-request row array)
 };
 
 // The one validation of the pick arrays (wrk_pick_args).  Sets kind.pick / kind.penalized and packs `n` rows; penalty row r names slot r
@@ -191,6 +195,14 @@ static int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, u
         const int32_t grc = wrk_grammar_pack(ctx, a.grammar, a.grammar_state, n, V, out.gram_state);
         if (grc != WRK_OK) return grc;
         out.grammar = a.grammar;
+    }
+    WRK_ARG(ctx, a.dry.window || !a.dry.any_array(), "dry_* / no_repeat_ngram arrays without a token window");
+    kind.dry = a.dry.window != nullptr;
+    if (kind.dry) {
+        const int32_t drc = wrk_dry_pack(ctx, a.dry, 0, n, slots, V, out.dry, out.brk);
+        if (drc != WRK_OK) return drc;
+        WRK_ARG(ctx, a.dry.window->num_batch >= slots, "token window of %u slots, %u state slots", a.dry.window->num_batch, slots);
+        out.has_dry = true;
     }
     if (!kind.sampled()) return WRK_OK;
     WRK_ARG(ctx, n >= 1, "a sampled pick of no rows");
@@ -366,13 +378,15 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     const wrk::SampleFilter* filt = rows.filt.empty() ? nullptr : rows.filt.data() + b0;
     const wrk::SampleAlt* alt = rows.alt.empty() ? nullptr : rows.alt.data() + b0;
     // a per-request array of a queue (none: 0) has at least one entry
-    const size_t V = f.facts().num_vocab, alt_req = rows.alt_requests ? rows.alt_requests : 1, gram_req = rows.gram_requests ? rows.gram_requests : 1;
+    const size_t V = f.facts().num_vocab, alt_req = rows.alt_requests ? rows.alt_requests : 1, gram_req = rows.gram_requests ? rows.gram_requests : 1,
+                 dry_req = rows.dry_requests ? rows.dry_requests : 1;
     int32_t rc = f.grow(f.history, {(size_t)steps * B});
     if (rc == WRK_OK && par) rc = f.grow(f.sample, {B});
     if (rc == WRK_OK && filt) rc = f.grow(f.filter, {B});
     if (rc == WRK_OK && alt) rc = f.grow(f.alt, {B, alt_req});
     if (rc == WRK_OK && pen) rc = f.grow(f.penalty, {B, V});
     if (rc == WRK_OK && rows.grammar) rc = f.grow(f.grammar, {B, gram_req, V});
+    if (rc == WRK_OK && rows.has_dry) rc = f.grow(f.dry, {B, dry_req, V});
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
@@ -385,6 +399,11 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     if (rows.grammar) {
         const wrk::GrammarParam gp = rows.grammar->param(f.grammar.state);
         up(f.grammar.par, &gp, 1)(f.grammar.state, rows.gram_state.data() + b0, B);
+    }
+    if (rows.has_dry) {
+        up(f.dry.par, rows.dry.data() + b0, B)(f.dry.brk, &rows.brk, 1);
+        // dry_rows leaves its scratch zero; a freshly allocated group, or one a failed call left behind, does not hold zeros yet
+        WRK_HIP(ctx, hipMemsetAsync(f.dry.scratch, 0, (size_t)B * V * 4, ctx->stream));
     }
     if (up.rc != WRK_OK) return up.rc;
     WRK_HIP(ctx, hipMemsetAsync(io.counter, 0, 4, ctx->stream));
@@ -441,7 +460,9 @@ struct wrk_queue_pack {
     float* mu_out = nullptr;    // Mirostat: the options' mirostat_mu, or nullptr
     std::vector<uint32_t> gram; // constrained: [R] the automaton state every request starts in
     uint32_t* gram_out = nullptr;   // the options' grammar_state, or nullptr
-    wrk_stopseq_pack seq;       // stop sequences: [R] the requests' rows (the tails: every slot starts empty)
+    std::vector<wrk::DryParam> dry; // DRY: [R] the requests' rows (values and tables; a slot's row keeps its own window pointers)
+    wrk_token_window* window = nullptr;
+    wrk_stopseq_pack seq;      // stop sequences: [R] the requests' rows (the tails: every slot starts empty)
     uint32_t* match_out = nullptr;  // the options' out_stop_match, or nullptr
 };
 
@@ -518,6 +539,19 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
         pk.rows.gram_state.assign(B, 0u);
         for (uint32_t b = 0; b < B && b < R; ++b) pk.rows.gram_state[b] = pk.gram[b];
     }
+    if (kind.dry) {                // slot b's row names slot b of the window, whatever request it serves; an idle slot: any valid values
+        pk.dry = req.dry;
+        pk.window = opt->window;
+        pk.rows.has_dry = true;
+        pk.rows.brk = req.brk;
+        pk.rows.dry_requests = R;
+        pk.rows.dry.resize(B);
+        for (uint32_t b = 0; b < B; ++b) {
+            pk.rows.dry[b] = pk.dry[b < R ? b : 0];
+            pk.rows.dry[b].ring = opt->window->ring + (size_t)b * opt->window->capacity;
+            pk.rows.dry[b].meta = opt->window->meta + (size_t)b * 2;
+        }
+    }
     for (uint32_t b = 0; b < B; ++b) {
         const uint32_t r = b < R ? b : 0;       // idle slots: any valid row
         const wrk::QueueReq& q = pk.reqs[r];
@@ -576,6 +610,7 @@ static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) 
                           kind.sampled() ? f.sample.par : nullptr, kind.penalized ? f.penalty.par : nullptr, kind.filtered() ? f.filter.par : nullptr,
                           kind.alt() ? f.alt.par : nullptr, kind.mirostat() ? f.alt.mu : nullptr,
                           kind.constrained ? f.grammar.state : nullptr, kind.constrained ? f.grammar.req : nullptr,
+                          kind.dry ? f.dry.par : nullptr, kind.dry ? f.dry.req : nullptr,
                           kind.stop_seqs ? f.queue_seq.rows : nullptr, kind.stop_seqs ? f.queue_seq.tail : nullptr,
                           kind.stop_seqs ? f.queue_seq.match : nullptr};
 }
@@ -612,11 +647,16 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     // the per-request mu and automaton states live in groups that wrk_decode_prepare sized with the request count
     if (pk.kind.mirostat() && !f.alt.holds({0, pk.R})) return wrk_fail(ctx, WRK_E_ARG, "Mirostat rows are not prepared");
     if (pk.kind.constrained && !f.grammar.holds({0, pk.R})) return wrk_fail(ctx, WRK_E_ARG, "grammar states are not prepared");
+    if (pk.kind.dry && !f.dry.holds({0, pk.R})) return wrk_fail(ctx, WRK_E_ARG, "DRY rows are not prepared");
     wrk_upload up{ctx};
     up(f.queue.slots, slots.data(), B)(f.queue.started, started.data(), B)(f.queue.log, log.data(), pk.R)(f.queue.reqs, pk.reqs.data(), pk.R);
     up(f.queue.pool, pk.pool.data(), pk.pool.size())(f.queue.ctl, &ctl, 1);
     if (pk.kind.mirostat()) up(f.alt.mu, pk.mu.data(), pk.R);
     if (pk.kind.constrained) up(f.grammar.req, pk.gram.data(), pk.R);
+    if (pk.kind.dry) {          // the slots that start a request at step 0 begin with an empty window, as a refilled slot does
+        const std::vector<uint32_t> empty((size_t)nstart * 2, 0u);
+        up(f.dry.req, pk.dry.data(), pk.R)(pk.window->meta, empty.data(), empty.size());
+    }
     if (pk.kind.stop_seqs) {     // every slot's tail starts empty, no request has a match yet
         const std::vector<uint32_t> tails((size_t)B * WRK_STOP_TAIL_LEN, WRK_STOP_TAIL_EMPTY), none(pk.R, WRK_STOP_MATCH_NONE);
         up(f.queue_seq.rows, pk.seq.rows.data(), pk.R)(f.queue_seq.tail, tails.data(), tails.size())(f.queue_seq.match, none.data(), pk.R);
@@ -673,10 +713,22 @@ static int32_t enqueue_grammar_advance(wrk_frame_common& f, uint32_t B, wrk_step
     return WRK_OK;
 }
 
-// what a tail does with the drawn tokens before it advances: the occurrence update, then the automaton advance
+// the token windows take the drawn tokens in io.argmax (DRY kinds), under the step's gate
+static int32_t enqueue_window_push(wrk_frame_common& f, uint32_t B, wrk_step_kind kind) {
+    if (!kind.dry) return WRK_OK;
+    if (!f.dry.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "DRY rows are not prepared");
+    wrk::RowGate gate;
+    const int32_t rc = draw_gate(f, B, kind, gate);
+    if (rc != WRK_OK) return rc;
+    wrk::window_push(f.ctx->op_stream(), f.facts().num_vocab, B, f.dry.par, f.io().argmax, gate);
+    return WRK_OK;
+}
+
+// what a tail does with the drawn tokens before it advances: the occurrence update, then the automaton advance, then the window push
 static int32_t enqueue_draw_updates(wrk_frame_common& f, uint32_t B, wrk_step_kind kind) {
-    const int32_t rc = enqueue_occurrence_update(f, B, kind);
-    return rc == WRK_OK ? enqueue_grammar_advance(f, B, kind) : rc;
+    int32_t rc = enqueue_occurrence_update(f, B, kind);
+    if (rc == WRK_OK) rc = enqueue_grammar_advance(f, B, kind);
+    return rc == WRK_OK ? enqueue_window_push(f, B, kind) : rc;
 }
 
 // tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
@@ -798,14 +850,22 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     const wrk::FrameIo& io = f.io();
     const uint32_t V = f.facts().num_vocab;
     const float* logits = io.head_o;
+    if (kind.dry && (!f.dry.holds({B, 0, V}) || argmax_done)) return wrk_fail(f.ctx, WRK_E_ARG, "DRY rows are not prepared");
     if (kind.penalized) {
         wrk::penalize_rows(q, io.head_o, V, V, B, f.penalty.par, f.penalty.out, V);
         logits = f.penalty.out;
     }
-    // the mask: in place on the penalised row, else from head_o (which log-probs, last_logits and the stop snapshot keep raw) into con_o
+    // DRY: in place on the penalised row, else on a copy of head_o (which log-probs, last_logits and the stop snapshot keep raw)
+    if (kind.dry) {
+        float* rows = kind.penalized ? f.penalty.out : f.dry.out;
+        if (!kind.penalized) wrk::copy_rows(q, io.head_o, V, V, B, rows, V);
+        wrk::dry_rows(q, rows, V, V, B, f.dry.par, f.dry.brk, f.dry.scratch);
+        logits = rows;
+    }
+    // the mask: in place on the penalised or the DRY row, else from head_o into con_o
     if (kind.constrained) {
         if (!f.grammar.holds({B, 0, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
-        float* masked = kind.penalized ? f.penalty.out : f.grammar.out;
+        float* masked = kind.penalized ? f.penalty.out : kind.dry ? f.dry.out : f.grammar.out;
         wrk::constrain_rows(q, logits, V, V, B, f.grammar.par, masked, V);
         logits = masked;
     }

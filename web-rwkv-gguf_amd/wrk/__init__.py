@@ -77,6 +77,8 @@ class GenerateOptions(C.Structure):
     _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
                 ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
+                ("window", _P), ("dry_multiplier", _f32p), ("dry_base", _f32p), ("dry_allowed_length", _u32p), ("no_repeat_ngram", _u32p),
+                ("dry_breakers", _u32p), ("num_dry_breakers", C.c_uint32),
                 ("grammar", _P), ("grammar_state", _u32p),
                 ("stop_seq_tokens", _u32p), ("stop_seq_offsets", _u32p), ("stop_seq_owners", _u32p), ("out_stop_match", _u32p),
                 ("stop_tail", _u32p),
@@ -92,6 +94,8 @@ class QueueOptions(C.Structure):
                 ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("init_state", _P),
                 ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
+                ("window", _P), ("dry_multiplier", _f32p), ("dry_base", _f32p), ("dry_allowed_length", _u32p), ("no_repeat_ngram", _u32p),
+                ("dry_breakers", _u32p), ("num_dry_breakers", C.c_uint32),
                 ("grammar", _P), ("grammar_state", _u32p),
                 ("stop_seq_tokens", _u32p), ("stop_seq_offsets", _u32p), ("stop_seq_owners", _u32p), ("out_stop_match", _u32p),
                 ("mirostat_tau", _f32p), ("mirostat_eta", _f32p), ("mirostat_mu", _f32p), ("typical_p", _f32p),
@@ -120,6 +124,9 @@ STOP_MATCH_TOKEN = 0xFFFFFFFE   # WRK_STOP_MATCH_TOKEN
 QUEUE_NO_ENTRY = 0xFFFFFFFF     # WRK_QUEUE_NO_ENTRY
 GRAMMAR_REJECT = 0xFFFF         # WRK_GRAMMAR_REJECT
 MAX_TOKEN_CLASSES = 8192        # WRK_MAX_TOKEN_CLASSES
+MAX_TOKEN_WINDOW = 4096         # WRK_MAX_TOKEN_WINDOW
+MAX_DRY_BREAKERS = 16           # WRK_MAX_DRY_BREAKERS
+DRY_MAX_MATCH = 50              # WRK_DRY_MAX_MATCH
 _u16p = C.POINTER(C.c_uint16)
 _TP = C.POINTER(TensorDesc)
 
@@ -221,6 +228,12 @@ HIP_SYMBOLS = {
     "wrk_grammar_destroy": (C.c_int32, [_P]),
     "wrk_constrain_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _u32p]),
     "wrk_grammar_advance": (C.c_int32, [_P, _P, _u32p, _u32p, C.c_uint32]),
+    "wrk_token_window_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "wrk_token_window_destroy": (C.c_int32, [_P]),
+    "wrk_token_window_add": (C.c_int32, [_P, _P, C.c_uint32, _u32p, C.c_uint32]),
+    "wrk_token_window_back": (C.c_int32, [_P, _P, C.c_uint32, _u32p, _u32p]),
+    "wrk_token_window_load": (C.c_int32, [_P, _P, C.c_uint32, _u32p, C.c_uint32]),
+    "wrk_dry_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, _f32p, _f32p, _u32p, _u32p, _u32p, C.c_uint32]),
     "wrk_stop_sequences_advance": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, _u32p, _u32p, _u32p]),
     "wrk_v7_generate_stop": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(GenerateOptions), _u32p, _u32p, _f32p, _u32p,
                                          _f32p, C.c_uint32]),
@@ -427,6 +440,36 @@ def _fill_stop_sequences(opt, n: int, keep: list, stop_sequences, owners: str):
     opt.stop_seq_tokens, opt.stop_seq_offsets, opt.stop_seq_owners = _ptr(ids, _u32p), _ptr(off, _u32p), _ptr(own, _u32p)
     opt.out_stop_match = _ptr(match, _u32p)
     return match
+
+
+def _dry_rows(n: int, keep: list, dry, no_repeat_ngram, dry_breakers):
+    """(multiplier, base, allowed_length, no_repeat_ngram, breakers) pointers and the breaker count for n rows: dry = (multiplier, base,
+    allowed_length), scalars or one value per row (None: off); no_repeat_ngram a scalar or one value per row (None: off); dry_breakers a
+    list of ids (None: none).  A part that is None stays a NULL pointer.  The arrays go into `keep`."""
+    mult = base = allowed = nr = brk = None
+    nb = 0
+    if dry is not None:
+        m, b, a = dry
+        keep.extend((_per_row(m, n, np.float32), _per_row(b, n, np.float32), _per_row(a, n, np.uint32)))
+        mult, base, allowed = _ptr(keep[-3], _f32p), _ptr(keep[-2], _f32p), _ptr(keep[-1], _u32p)
+    if no_repeat_ngram is not None:
+        keep.append(_per_row(no_repeat_ngram, n, np.uint32))
+        nr = _ptr(keep[-1], _u32p)
+    if dry_breakers is not None and len(dry_breakers):
+        keep.append(_u32(dry_breakers).reshape(-1))
+        brk, nb = _ptr(keep[-1], _u32p), int(keep[-1].size)
+    return mult, base, allowed, nr, brk, nb
+
+
+def _fill_dry(opt, n: int, keep: list, window, dry, no_repeat_ngram, dry_breakers):
+    """The DRY fields of a GenerateOptions or QueueOptions for n rows; nothing is set without a window."""
+    if window is None:
+        if dry is not None or no_repeat_ngram is not None or dry_breakers is not None:
+            raise ValueError("dry / no_repeat_ngram / dry_breakers without window")
+        return
+    opt.window = window.h
+    (opt.dry_multiplier, opt.dry_base, opt.dry_allowed_length, opt.no_repeat_ngram, opt.dry_breakers,
+     opt.num_dry_breakers) = _dry_rows(n, keep, dry, no_repeat_ngram, dry_breakers)
 
 
 def _fill_grammar(opt, n: int, keep: list, grammar, grammar_state):
@@ -731,6 +774,75 @@ class Context:
                                                   _ptr(own, _u32p), None if sid is None else _ptr(sid, _u32p),
                                                   None if soff is None else _ptr(soff, _u32p), _ptr(tl, _u32p), _ptr(tk, _u32p), _ptr(match, _u32p)))
         return match[:n], tl
+
+    def dry_logits(self, logits, window: "TokenWindow", dry=None, no_repeat_ngram=None, dry_breakers=None, first_batch: int = 0,
+                   num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
+        """DRY and the no-repeat-n-gram ban on rows of logits, on the device: row r is changed with slot first_batch + r
+        of `window` -- the token that would extend a repeat of M tokens loses multiplier * base ** (M - allowed_length) once M >=
+        allowed_length, and gets -inf once M >= no_repeat_ngram - 1; every other token keeps its bits.  dry = (multiplier, base,
+        allowed_length), scalars or one value per row (None: off); no_repeat_ngram: a scalar or one value per row (None: off);
+        dry_breakers: ids a match never crosses.  `logits`: an [n, V] f32 array (returns the changed copy), or a `Buffer` of n rows of
+        `row_stride` f32 (first `num_vocab` used), changed in place (returns None).  In a host loop it goes between `penalize_logits`
+        and `constrain_logits`.  The window is only read."""
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            stride = int(row_stride or V)
+            n = (buf.nbytes // 4 - V) // stride + 1 if buf.nbytes >= 4 * V else 0
+            a = None
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            n, V = a.shape
+            stride = V
+            buf = self.buffer(a)
+        keep = []
+        self.check(hip.wrk_dry_logits(self.h, buf.h, V, stride, n, window.h, first_batch, *_dry_rows(n, keep, dry, no_repeat_ngram, dry_breakers)))
+        return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
+
+
+class TokenWindow:
+    """The per-sequence window of recent tokens that DRY and the no-repeat-n-gram ban match on, on the device:
+    `num_batch` slots (slot b belongs to state slot b) of the last `capacity` tokens that counted, oldest first.  The decode loops push
+    every draw that counts when it is passed as `window=`; a prompt is pushed with `add`."""
+
+    def __init__(self, ctx: "Context", num_batch: int, num_vocab: int, capacity: int):
+        h = _P()
+        ctx.check(hip.wrk_token_window_create(ctx.h, num_batch, num_vocab, capacity, C.byref(h)))
+        self.ctx, self.h = ctx, h
+        self.num_batch, self.num_vocab, self.capacity = int(num_batch), int(num_vocab), int(capacity)
+
+    def add(self, batch: int, tokens):
+        """Pushes `tokens` into slot `batch` in order."""
+        t = _u32(tokens).reshape(-1)
+        self.ctx.check(hip.wrk_token_window_add(self.ctx.h, self.h, batch, _ptr(t, _u32p) if t.size else None, t.size))
+
+    def back(self, batch: int) -> np.ndarray:
+        """The tokens of slot `batch`, oldest first (uint32 [length])."""
+        out, n = np.zeros(self.capacity, np.uint32), C.c_uint32()
+        self.ctx.check(hip.wrk_token_window_back(self.ctx.h, self.h, batch, _ptr(out, _u32p), C.byref(n)))
+        return out[:n.value].copy()
+
+    def load(self, batch: int, tokens=None):
+        """Slot `batch` becomes `tokens` (at most `capacity`, oldest first); None: empty."""
+        if tokens is None:
+            self.ctx.check(hip.wrk_token_window_load(self.ctx.h, self.h, batch, None, 0))
+            return
+        t = _u32(tokens).reshape(-1)
+        if t.size == 0:
+            return self.load(batch, None)
+        self.ctx.check(hip.wrk_token_window_load(self.ctx.h, self.h, batch, _ptr(t, _u32p), t.size))
+
+    def close(self):
+        if self.h and self.ctx.h:
+            hip.wrk_token_window_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Grammar:
@@ -1390,7 +1502,7 @@ class Runtime:
         return (out, ms.value, logits) if want_logits else (out, ms.value)
 
     def generate_greedy(self, first_tokens, steps: int, mode: int = 1, want_logits: bool = False, groups: int = 1, logprobs=None,
-                        grammar: "Grammar" = None, grammar_state=None):
+                        grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
         """Device-resident greedy loop; returns (tokens [steps, B], elapsed_ms[, last logits [B, V]]).
         groups > 1 (RWKV-7): the B independent sequences are dealt over that many concurrent pipelines (each a contiguous block of
         sequences with its own frame, decode program and HIP stream) instead of one batched step.
@@ -1401,10 +1513,16 @@ class Runtime:
         grammar / grammar_state (a scalar or one state per sequence; None: 0): constrained decoding: every pick is made
         on the row masked by the `Grammar` in the sequence's automaton state, and every draw moves that state, on the device;
         afterwards `last_grammar_state` [B] holds the states to pass to the next call of a session.  Such a call goes through the
-        options entry point and replays step programs of its own."""
-        if logprobs is not None or grammar is not None or grammar_state is not None:
+        options entry point and replays step programs of its own.
+        window / dry=(multiplier, base, allowed_length) / no_repeat_ngram / dry_breakers: every pick sees its row as
+        `Context.dry_logits` leaves it with the sequence's slot of the `TokenWindow` -- the token that would extend a verbatim repeat
+        is penalised, or with no_repeat_ngram banned -- and every draw is pushed into that slot, on the device.  Scalars or one value
+        per sequence; a window alone only records the draws.  Greedy with DRY is the deterministic "no loops" mode.  Such a call goes
+        through the options entry point and replays step programs of its own."""
+        if any(v is not None for v in (logprobs, grammar, grammar_state, window, dry, no_repeat_ngram, dry_breakers)):
             return self._generate_filtered(first_tokens, steps, None, None, None, None, 0.0, 0.0, 1.0, None, None, mode, want_logits, groups,
-                                           logprobs, grammar=grammar, grammar_state=grammar_state)
+                                           logprobs, grammar=grammar, grammar_state=grammar_state,
+                                           dry_args=(window, dry, no_repeat_ngram, dry_breakers))
         return self._generate("greedy", first_tokens, steps, (), mode, groups, want_logits)
 
     def _generate_options(self, first_tokens, steps, opt, keep, mode, want_logits, logprobs=None):
@@ -1438,7 +1556,7 @@ class Runtime:
 
     def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
                         groups: int = 1, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
-                        grammar: "Grammar" = None, grammar_state=None):
+                        grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
         """As `generate_greedy`, each sequence's next token drawn by `Sampler::sample` (examples/chat.rs:150-190) on the device with its
         own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b.
         top_k / min_p (a scalar or one value per sequence; None: off): the draw is `sample_logits(..., top_k, min_p)`'s; such a call goes
@@ -1449,20 +1567,24 @@ class Runtime:
         afterwards `last_mirostat_mu` [B] holds the values to pass to the next call of a session.  typical_p (a scalar or one value per
         sequence): locally typical sampling.  One family per call (top_k / min_p, mirostat, typical_p); such a call goes through the
         options entry point and replays step programs of its own.
-        grammar / grammar_state: as `generate_greedy`; the draw is the same sampler's on the masked row."""
-        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state)):
+        grammar / grammar_state: as `generate_greedy`; the draw is the same sampler's on the masked row.
+        window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`; the draw is the same sampler's on the changed row."""
+        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state, window, dry,
+                                       no_repeat_ngram, dry_breakers)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
-                                           want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state)
+                                           want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
+                                           (window, dry, no_repeat_ngram, dry_breakers))
         keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
         return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
 
     def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
                            want_logits, groups, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar=None,
-                           grammar_state=None):
+                           grammar_state=None, dry_args=(None, None, None, None)):
         opt, keep = GenerateOptions(), []
         mu = _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                         mirostat, mirostat_mu, typical_p)
         gs = _fill_grammar(opt, _u32(first_tokens).size, keep, grammar, grammar_state)
+        _fill_dry(opt, _u32(first_tokens).size, keep, *dry_args)
         out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits, logprobs)
         self.last_mirostat_mu = mu
         self.last_grammar_state = gs
@@ -1471,7 +1593,7 @@ class Runtime:
 
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
                            frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1, top_k=None, min_p=None,
-                           logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None):
+                           logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
         """As `generate_sample`, each draw made on the logits penalised with the sequence's slot of `occurrence` (ChatRWKV's
         alpha_presence / alpha_frequency / token_ban), and the slot updated after every draw (count *= decay, then the drawn token's
         weight added).  The first token of a call is not counted; the last drawn one is.  The table carries over between calls.
@@ -1479,10 +1601,13 @@ class Runtime:
         the cuts made on the penalised logits.  logprobs: as `generate_greedy`, on the head output before penalties and bans (a banned
         token may appear among the alternatives).  mirostat / mirostat_mu / typical_p: as `generate_sample`, the pick made on the
         penalised logits.  grammar / grammar_state: as `generate_greedy`, the mask applied to the penalised logits; bans belong in the
-        grammar (a row that bans and automaton together leave empty draws an unspecified token, which the automaton rejects)."""
-        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state)):
+        grammar (a row that bans and automaton together leave empty draws an unspecified token, which the automaton rejects).
+        window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`, applied to the penalised logits, before the grammar."""
+        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state, window, dry,
+                                       no_repeat_ngram, dry_breakers)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
-                                           min_p, mode, want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state)
+                                           min_p, mode, want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
+                                           (window, dry, no_repeat_ngram, dry_breakers))
         B = _u32(first_tokens).size
         keep, rows = self._sampler_rows(B, temperature, top_p, seed)
         pen = [_per_row(v, B, np.float32) for v in (presence, frequency, decay)]
@@ -1492,7 +1617,7 @@ class Runtime:
     def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
                       poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
-                      grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, stop_tail=None):
+                      grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, stop_tail=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
         """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
         at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
         MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
@@ -1511,7 +1636,9 @@ class Runtime:
         STOP_MATCH_NONE, STOP_MATCH_TOKEN or the index of the sequence that matched (the caller trims its length, or 1: the device trims
         nothing).  stop_tail ([B, STOP_TAIL_LEN] from an earlier call's `last_stop_tail`; None: empty): the last draws of the session so
         far, so that a stop sequence that straddles two calls still ends the reply; `last_stop_tail` holds the tails after this call.
-        Both are None after a call without stop_sequences, which runs exactly the step programs it ran before."""
+        Both are None after a call without stop_sequences, which runs exactly the step programs it ran before.
+        window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`; slot b of the window has taken exactly lengths[b] pushes,
+        the stop token's included: the window freezes with the sequence."""
         ft = _u32(first_tokens)
         ids, off = _stop_csr(stop, ft.size, "sequences")
         opt, keep = GenerateOptions(), []
@@ -1525,6 +1652,7 @@ class Runtime:
         self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                                            mirostat, mirostat_mu, typical_p)
         self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
+        _fill_dry(opt, ft.size, keep, window, dry, no_repeat_ngram, dry_breakers)
         opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
         out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, self._mode(mode, groups), want_logits,
                                                                               logprobs)
@@ -1534,7 +1662,7 @@ class Runtime:
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
                        mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None,
-                       mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None):
+                       mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1561,7 +1689,11 @@ class Runtime:
         stop_sequences (None: off): as `generate_stop`, one list of id lists for all requests or one such list per request.  Only reply
         draws are matched: a prompt that is, or ends in the beginning of, a stop sequence does not end its reply, and a refilled slot
         starts with an empty tail.  A match ends the request with reason 1; `last_stop_match[r]` says what ended request r
-        (STOP_MATCH_NONE for reasons 0, 2 and 3).  None after a call without stop_sequences."""
+        (STOP_MATCH_NONE for reasons 0, 2 and 3).  None after a call without stop_sequences.
+        window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`, dry and no_repeat_ngram per request (scalars broadcast), the
+        breakers for the call.  Slot b of the window serves whatever request runs on state slot b: it is emptied when a request is
+        dispatched to it and takes only that request's reply draws, never prompt tokens.  The window's rows are unspecified afterwards
+        and are not part of a pool entry."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1580,6 +1712,7 @@ class Runtime:
         self.last_mirostat_mu = _fill_pick(opt, R, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                                            mirostat, mirostat_mu, typical_p)
         self.last_grammar_state = _fill_grammar(opt, R, keep, grammar, grammar_state)
+        _fill_dry(opt, R, keep, window, dry, no_repeat_ngram, dry_breakers)
         match = _fill_stop_sequences(opt, R, keep, stop_sequences, "requests")
         self.last_stop_match = self.last_stop_tail = None
         if init_state is not None:
