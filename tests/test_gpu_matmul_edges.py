@@ -13,15 +13,17 @@ accumulation in 16-wide partial sums stays below C / 2 on every input profile at
 (all expected values here are far inside the f32 range); an all-zero token gives exactly 0.0; the value-preserving sign flips of Q6_K and
 Q8_0 (blocks_ref.flip) give the same f32 bits wherever the kernel is sign-symmetric (see BIT_IDENTICAL) and stay inside the bound elsewhere.
 
-Which kernel a case runs on follows from its shape and from the switches that are read per call.  The rules, in
-web-rwkv-gguf_amd/csrc (wrk_api.hip:434-442 wrk_op_matmul: turbo and >= 2 tokens -> matmul_mfma, else / on -2 -> matvec;
-wrk_gemm.hip:1610-1628 gemm_ok; wrk_gemm.hip:1725-1829 matmul_mfma_multi; wrk_dmv.hip:44-160 launch_dmv):
+Which kernel a case runs on follows from its shape and from the switches that are read per call.  wrk_op_matmul (wrk_api.hip) sends
+turbo calls of >= 2 tokens to matmul_mfma, whose routing is one pure function, gemm_plan (web-rwkv-gguf_amd/csrc/wrk_gemm_route.h); every
+other call, and a launch gemm_plan declines, goes to matvec (wrk_matvec.hip, wrk_dmv.hip launch_dmv).  tests/matmul_paths.py holds the shapes
+and names each turbo path's route; tests/test_gemm_route_host.py asserts on the CPU that gemm_plan gives every row that route, so the
+table below cannot drift from the dispatch:
 
 | path        | kernel                                   | rule the shape relies on                                                                  |
 |-------------|------------------------------------------|-------------------------------------------------------------------------------------------|
 | vec1        | dmv_kernel (NF4, long ROUND_F16 rows: matvec_kernel family) | T = 1, turbo off; K = 256 / 512 (one chunk) and K = 8192 (4096 F16): K over the waves, two iterations; MATRIX_EXACT and MATRIX_ROUND_F16 |
-| vecT        | dmv token kernels, matvec kernels (Q8_0, INT8, NF4) | T = 2, 3, 4, turbo off (wrk_dmv.hip:57-72: <= 4 tokens; Q8_0 / Int8 / NF4 fall back)        |
-| ks14        | gemm_kernel<1,4>                         | turbo, T = 5 <= 16, wg < 256 but K = 512 < 4096: not deep (wrk_gemm.hip:1797-1826)        |
+| vecT        | dmv token kernels, matvec kernels (Q8_0, INT8, NF4) | T = 2, 3, 4, turbo off (launch_dmv: <= 4 tokens; Q8_0 / Int8 / NF4 fall back)              |
+| ks14        | gemm_kernel<1,4>                         | turbo, T = 5 <= 16, wg < 256 but K = 512 < 4096: not deep                              |
 | ks18        | gemm_kernel<1,8>                         | turbo, T = 16, 4 row tiles, K = 4096: deep                                                |
 | ks24        | gemm_kernel<2,4>                         | turbo, T = 17 (16 < n <= 64), K = 512                                                     |
 | ks28        | gemm_kernel<2,8>                         | turbo, T = 40 < 48 (no tile), K = 4096: deep                                              |
@@ -31,7 +33,7 @@ wrk_gemm.hip:1610-1628 gemm_ok; wrk_gemm.hip:1725-1829 matmul_mfma_multi; wrk_dm
 | tile2       | gemm_tile2_kernel                        | T = 520 >= 512, 9 x 9 tiles, K % 128 == 0: Q8_0, F16; Q4_K / Q5_K with WRK_GEMM_TILE3=0   |
 | tile2_q8_48 | gemm_tile2_kernel                        | Q8_0 from 48 tokens: T = 48, 65 tiles at K = 256                                          |
 | tile3       | xsum_kernel + gemm_tile3_kernel          | T = 515 >= 512, Q4_K / Q5_K, m = 132 >= 128; K = 2048 (sum pre-pass: a wave per token), 2560 (last group of two blocks), 8192 |
-| tile3_split | xsum + gemm_tile3 (grid.z) + t3_reduce_kernel | T = 140 (128 < n <= 256) K = 8192, and T = 128 with K = 4096 (wrk_gemm3.hip gemm_tile3_launch) |
+| tile3_split | xsum + gemm_tile3 (grid.z) + t3_reduce_kernel | T = 140 (128 < n <= 256) K = 8192, and T = 128 with K = 4096 (gemm_plan_tile3)              |
 | plane_vec / plane_mfma | matvec kernels / gemm_kernel<2,4> | INT8, NF4: T = 1, 3 turbo off; T = 33 turbo (as test_gpu_wrkquant.py)                     |
 
 profiles/matmul_edges_kernel_stats.csv is a rocprofv3 --kernel-trace --stats run of this file and lists every kernel of the table.
@@ -50,34 +52,12 @@ import pytest
 import blocks_ref as br
 import wrk
 from oracle import dequant as dq
+from matmul_paths import PATHS
 from oracle import wrkquant as wq
 
 pytestmark = pytest.mark.gpu
 
 C = 4e-6
-K4 = ("Q4_K", "Q5_K")
-GG = ("Q4_K", "Q5_K", "Q6_K", "Q8_0", "F16")
-PLANES = ("INT8", "NF4")
-
-# path -> (kinds, [(k, m, T)], turbo, env)
-PATHS = {
-    "vec1": (GG, [(512, 12, 1), (8192, 8, 1)], False, {}),
-    "vecT": (GG, [(512, 20, 2), (512, 20, 3), (1024, 20, 4)], False, {}),
-    "ks14": (GG, [(512, 64, 5)], True, {}),
-    "ks18": (GG, [(4096, 64, 16)], True, {}),
-    "ks24": (GG, [(512, 32, 17)], True, {}),
-    "ks28": (GG, [(4096, 32, 40)], True, {}),
-    "ks44": (GG, [(512, 32, 100)], True, {}),
-    "pair": (("Q4_K", "Q5_K", "F16"), [(512, 6416, 5), (512, 6416, 16)], True, {"WRK_GEMM_PAIR": "1"}),
-    "tile1": (("Q4_K", "Q5_K", "Q6_K", "F16"), [(512, 2052, 100)], True, {}),
-    "tile2": (("Q8_0", "F16"), [(512, 516, 520)], True, {}),
-    "tile2_k4": (K4, [(512, 516, 520)], True, {"WRK_GEMM_TILE3": "0"}),
-    "tile2_q8_48": (("Q8_0",), [(256, 4100, 48)], True, {}),
-    "tile3": (K4, [(2048, 132, 515), (2560, 132, 515), (8192, 132, 515)], True, {}),
-    "tile3_split": (K4, [(8192, 132, 140), (4096, 132, 128)], True, {}),
-    "plane_vec": (PLANES, [(512, 12, 1), (2048, 8, 3)], False, {}),
-    "plane_mfma": (PLANES, [(512, 32, 33)], True, {}),
-}
 F16_LONG = {8192: 4096}                     # F16 rows: the two-iteration walk starts at 4096
 
 
@@ -147,7 +127,7 @@ def check(got, w, terms, x, what):
 @pytest.mark.parametrize("enc", br.ENCODINGS)
 @pytest.mark.parametrize("path,kind", PATH_KIND)
 def test_encoding_x_input(ctx, monkeypatch, path, kind, enc, profile):
-    _, _, turbo, env = PATHS[path]
+    _, _, turbo, env, _ = PATHS[path]
     for key, val in env.items():
         monkeypatch.setenv(key, val)
     for k, m, T in shapes_of(path, kind):
@@ -168,7 +148,7 @@ def test_encoding_x_input(ctx, monkeypatch, path, kind, enc, profile):
 def test_f16_output_activation_epilogue(ctx, monkeypatch, path, kind, enc):
     """f16 store behind tanh (bounded, so no encoding overflows the store), `normal` inputs: one f16 ulp of the exact value plus the
     f32 bound carried through tanh (slope <= 1) plus the 2e-5 the other matmul tests grant the device tanh."""
-    _, _, turbo, env = PATHS[path]
+    _, _, turbo, env, _ = PATHS[path]
     for key, val in env.items():
         monkeypatch.setenv(key, val)
     for k, m, T in shapes_of(path, kind):
@@ -201,7 +181,7 @@ def test_sign_flipped_encoding(ctx, monkeypatch, path, kind, profile):
     """Q6_K with d and every scale negated, Q8_0 with d and every code negated: the same weights, (-d) * (-sc) is the same f32 product.
     Bit-identical outputs where the kernel is sign-symmetric (BIT_IDENTICAL; an output that is zero may be either zero), within the bound
     for both encodings everywhere."""
-    _, _, turbo, env = PATHS[path]
+    _, _, turbo, env, _ = PATHS[path]
     for key, val in env.items():
         monkeypatch.setenv(key, val)
     for k, m, T in shapes_of(path, kind):

@@ -1154,127 +1154,6 @@ __global__ void __launch_bounds__(256) gemm_tile_kernel(const GemmBatch B) {
     else gemm_tile_body_f16(P, (f16*)tile_smem);
 }
 
-// ------------------------------------------------------------------ decode-batch tile kernel (Q4_K / Q5_K, <= 16 tokens)
-// Same idea as the prefill tile for the few-token regime of batched decode: 64 rows x 16 tokens per workgroup, every
-// wave walks the whole K for its 16 rows, the 16 x 256 activation block is shared through LDS (8 KB per block, double
-// buffered).  Against the K-split kernel this (a) reads the activations once per 64 rows instead of once per 16 (at
-// D = 4096 the K-split kernel moves 128 KB of activations per 45 KB of weights), and (b) takes the B fragments off the
-// vector-memory queue (LDS has its own counter), so the weight rows can be prefetched FOUR blocks ahead without the
-// in-order return of loads stalling the multiply.
-template <int KIND>
-__device__ __forceinline__ void gemm_dec_body(const GemmParams& P, f16* __restrict__ lds) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t r = lane & 15, g = lane >> 4;
-    const uint32_t m0 = (blockIdx.x - P.wg_begin) * TILE_ROWS + wave * 16;
-    const uint32_t K = P.k, nb = K >> 8;
-    const uint32_t row = min(m0 + r, P.m - 1);
-    const uint8_t* wrow = P.w + (size_t)row * P.row_bytes;
-    const uint32_t hoff = KIND == WRK_MAT_Q4_K ? nb * 128 : nb * 160, soff = hoff + nb * 4;
-    const uint8_t* crow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) crow[i] = P.w + (size_t)min(m0 + 4 * g + i, P.m - 1) * P.row_bytes + hoff;
-    // staging: 16 tokens x 32 chunks of 8 f16 per block, 2 per thread: chunk q -> token (tid >> 5) + 8 q
-    const size_t xs0 = P.in.stride[0];
-    const f16* xbase = (const f16*)P.in.p + dt_index(P.in, 0, 0, 0) + (size_t)(tid >> 5) * xs0 + (tid & 31u) * 8;
-    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-    f16x8 stage[2];
-    auto fetch_x = [&](uint32_t b) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) stage[q] = ((tid >> 5) + 8 * q < P.n) ? *(const f16x8*)(xbase + (size_t)8 * q * xs0 + (size_t)b * 256) : zero8;
-    };
-    auto store_x = [&](uint32_t buf) {
-        f16* base = lds + (size_t)buf * 16 * TILE_LDS_ROW;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) *(f16x8*)(base + ((tid >> 5) + 8 * q) * TILE_LDS_ROW + (tid & 31u) * 8) = stage[q];
-    };
-    struct WBlk { u32x2 q[4]; u32x2 qh; u32x4 sm; uint32_t dd[4]; };
-    auto load_w = [&](WBlk& R, uint32_t b) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) R.q[j] = *(const u32x2*)(wrow + (size_t)b * 128 + j * 32 + 8 * g);
-        if (KIND == WRK_MAT_Q5_K) R.qh = *(const u32x2*)(wrow + (size_t)nb * 128 + (size_t)b * 32 + 8 * g);
-        R.sm = *(const u32x4*)(wrow + soff + (size_t)b * 16);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) R.dd[i] = *(const uint32_t*)(crow[i] + (size_t)b * 4);
-    };
-    f32x4v total = {0.f, 0.f, 0.f, 0.f};
-    auto mul_blk = [&](const WBlk& R, uint32_t buf) {
-        const f16* xt = lds + (size_t)buf * 16 * TILE_LDS_ROW + r * TILE_LDS_ROW + 8 * g;
-        f32x4v acc = {0.f, 0.f, 0.f, 0.f}, amin = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const u32x2 q = R.q[j];
-            const uint32_t v = R.sm[j];
-            const float sc0 = (float)(v & 0xffu), sc1 = (float)((v >> 8) & 0xffu);
-            f16x8 alo, ahi;
-            if (KIND == WRK_MAT_Q4_K) {
-                alo = mul8(codes8(q.x & 0x0f0f0f0fu, q.y & 0x0f0f0f0fu), sc0 * 1024.0f);
-                ahi = mul8(codes8(q.x & 0xf0f0f0f0u, q.y & 0xf0f0f0f0u), sc1 * 64.0f);
-            } else {
-                const uint32_t s0 = 2 * j, s1 = 2 * j + 1;
-                alo = mul8(codes8((q.x & 0x0f0f0f0fu) | (((R.qh.x >> s0) & 0x01010101u) << 4), (q.y & 0x0f0f0f0fu) | (((R.qh.y >> s0) & 0x01010101u) << 4)), sc0 * 1024.0f);
-                ahi = mul8(codes8(((q.x >> 4) & 0x0f0f0f0fu) | (((R.qh.x >> s1) & 0x01010101u) << 4), ((q.y >> 4) & 0x0f0f0f0fu) | (((R.qh.y >> s1) & 0x01010101u) << 4)), sc1 * 1024.0f);
-            }
-            const f16 m0h = (f16)(float)((v >> 16) & 0xffu), m1h = (f16)(float)(v >> 24);
-            const f16x8 mlo = {m0h, m0h, m0h, m0h, m0h, m0h, m0h, m0h}, mhi = {m1h, m1h, m1h, m1h, m1h, m1h, m1h, m1h};
-            const f16x8 b0 = *(const f16x8*)(xt + j * 64), b1 = *(const f16x8*)(xt + j * 64 + 32);
-            acc = mfma16(alo, b0, acc);
-            acc = mfma16(ahi, b1, acc);
-            amin = mfma16(mlo, b0, amin);
-            amin = mfma16(mhi, b1, amin);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float d = (float)__builtin_bit_cast(f16, (uint16_t)(R.dd[i] & 0xffffu)) * 16384.0f;
-            const float dmin = (float)__builtin_bit_cast(f16, (uint16_t)(R.dd[i] >> 16));
-            total[i] += d * acc[i] - dmin * amin[i];
-        }
-    };
-    WBlk W[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-        if ((uint32_t)u < nb) load_w(W[u], u);
-    fetch_x(0);
-    store_x(0);
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < nb; b0 += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {           // unrolled by the ring depth: every buffer index is a compile-time constant
-            const uint32_t b = b0 + u;
-            if (b >= nb) break;
-            const bool more = b + 1 < nb;
-            if (more) fetch_x(b + 1);           // L2-resident, issued BEFORE the far weight prefetch below (loads return in order)
-            mul_blk(W[u], u & 1);
-            if (b + 4 < nb) load_w(W[u], b + 4);
-            if (more) store_x((u & 1) ^ 1);
-            __syncthreads();
-        }
-    }
-    const uint32_t tok = r;
-    if (tok < P.n) {
-        uint32_t tt, bb;
-        tok_tb(P.out, tok, tt, bb);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t mr = m0 + 4 * g + i;
-            if (mr >= P.m) continue;
-            float o = act_apply(P.act, total[i] * P.scale);
-            if (P.has_res) { uint32_t rt, rb; tok_tb(P.res, tok, rt, rb); o = dt_round(P.out, o) + dt_load(P.res, dt_index(P.res, mr, rt, rb)); }
-            dt_store(P.out, dt_index(P.out, mr, tt, bb), o);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) gemm_dec_kernel(const GemmBatch B) {
-    __shared__ __attribute__((aligned(16))) f16 dec_smem[2 * 16 * TILE_LDS_ROW];
-    int ji = 0;
-#pragma unroll
-    for (int q = 1; q < GEMM_MAX_JOBS; ++q)
-        if (q < B.njobs && blockIdx.x >= B.jobs[q].wg_begin) ji = q;
-    const GemmParams& P = B.jobs[ji];
-    if (P.kind == WRK_MAT_Q4_K) gemm_dec_body<WRK_MAT_Q4_K>(P, dec_smem);
-    else gemm_dec_body<WRK_MAT_Q5_K>(P, dec_smem);
-}
-
 // ------------------------------------------------------------------ K-sliced GEMM for decode batches (5 .. 32 stacked tokens; round 2)
 // What the in-kernel timelines of batched decode showed: a CU ingests only ~30 GB/s when its loads are one
 // dependent burst (outstanding misses x latency), and the kernels above make every workgroup pull the WHOLE activation stack -- 64 KB at
@@ -1597,38 +1476,41 @@ __global__ void __launch_bounds__(256) gemm_ks_kernel(const KsBatch B) {
     }
 }
 
-// fewest stacked tokens sent to the matrix cores (tiles are padded to 16 tokens; below this the matvec kernels run)
-uint32_t gemm_min_tokens() {
-    static const uint32_t v = [] { const char* e = getenv("WRK_GEMM_MIN"); const int x = e ? atoi(e) : 2; return (uint32_t)(x < 2 ? 2 : x); }();     // measured (1.5B decode): 2 sequences break even, 3: 1.33 vs 1.79 ms, 8: 2x in favour of MFMA
+// ------------------------------------------------------------------ host: switches -> plan (wrk_gemm_route.h) -> launches
+static_assert(TILE_ROWS == (int)ROUTE_TILE_ROWS && TILE_TOK == (int)ROUTE_TILE_TOK, "gemm_plan counts the tile kernels' workgroups");
+
+// the switches that are read once per process: WRK_GEMM_MIN, WRK_KS_BPS, WRK_GEMM_TILE, WRK_GEMM_TILE2, WRK_GEMM_TILE2_F16
+static const GemmSwitches& switches_once() {
+    static const GemmSwitches v = [] {
+        auto on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
+        GemmSwitches sw;
+        const char* e = getenv("WRK_GEMM_MIN");
+        const int x = e ? atoi(e) : 2;
+        sw.min_tokens = (uint32_t)(x < 2 ? 2 : x);
+        e = getenv("WRK_KS_BPS");
+        sw.ks_bps = e ? atoi(e) : 0;
+        sw.tile = on("WRK_GEMM_TILE"); sw.tile2 = on("WRK_GEMM_TILE2"); sw.tile2_f16 = on("WRK_GEMM_TILE2_F16");
+        return sw;
+    }();
     return v;
 }
+uint32_t gemm_min_tokens() { return switches_once().min_tokens; }
 
-// token tok = t + b * shape[1] of a [C, T, B] view sits at base + tok * stride[0] when the view covers the whole T extent of
-// its parent (or has a single batch)
-static bool dense_stack(const DTensor& d) { return d.shape[2] == 1 || (d.shape[1] == d.stride[1] && d.offset[1] == 0); }
-static size_t stack_base(const DTensor& d) { return ((size_t)d.offset[2] * d.stride[1] + d.offset[1]) * d.stride[0] + d.offset[0]; }
-
-static bool gemm_ok(const MatJob& j, uint32_t n) {
-    if (j.in.shape[1] * j.in.shape[2] != n || n < gemm_min_tokens()) return false;
-    if (!dense_stack(j.in) || !dense_stack(j.out) || (j.has_res && !dense_stack(j.res))) return false;
-    if (j.m < 4 || (j.m & 3u) || (j.out.dtype != WRK_F16 && j.out.dtype != WRK_F32) || (j.has_res && j.res.dtype != WRK_F16 && j.res.dtype != WRK_F32)) return false;
-    // four consecutive output rows are stored (and residual rows loaded) as one vector
-    if (((stack_base(j.out) | j.out.stride[0]) & 3u) || (j.has_res && ((stack_base(j.res) | j.res.stride[0]) & 3u))) return false;
-    if (j.k < 32) return false;
-    if (j.flags & WRK_MATRIX_ROUND_F16) return false;       // parity mode: per-element f16 rounding lives in the matvec kernels
-    if (j.in.dtype != WRK_F16 || (j.k & 31u)) return false;
-    // rows of the input views must be 16-byte aligned for the B-fragment loads
-    if ((j.in.stride[0] & 7u) || (j.in.offset[0] & 7u)) return false;
-    switch (j.kind) {
-        case WRK_MAT_F16: case WRK_MAT_Q8_0: case WRK_MAT_Q6_K: case WRK_MAT_Q4_K: case WRK_MAT_Q5_K: return true;
-        case WRK_MAT_INT8: return (j.k & 127u) == 0;      // rows aligned to the 128-element blocks
-        case WRK_MAT_NF4: return (j.k & 63u) == 0 && j.aux != nullptr;
-        default: return false;
+// Every switch of the planner.  WRK_GEMM_KS, WRK_GEMM_TILE3, WRK_T3_SPLIT and WRK_GEMM_PAIR are read per call, not once per process: the
+// tests switch them; launches are captured into graphs, so this is off the replay path.  An eager launch reads only those that its token
+// count and scratch let matter, at most two.
+static GemmSwitches gemm_switches(uint32_t n, bool ks_scratch, bool t3_scratch) {
+    GemmSwitches sw = switches_once();
+    const char* e;
+    if (ks_scratch && n <= 32 && (e = getenv("WRK_GEMM_KS"))) sw.ks_mode = atoi(e);
+    if (n <= 16 && (e = getenv("WRK_GEMM_PAIR"))) sw.pair = e[0] == '1';
+    if (t3_scratch && n >= 128) {
+        if ((e = getenv("WRK_GEMM_TILE3"))) sw.tile3 = e[0] != '0';
+        if (n <= 2 * ROUTE_T3_TOK && (e = getenv("WRK_T3_SPLIT"))) sw.t3_split = e[0] != '0';
     }
+    return sw;
 }
 
-// All jobs multiply the same number of tokens; they run in ONE launch.  Returns -2 when any job is not for the MFMA
-// path (n < 16, ROUND_F16, non-f16 / unaligned input, K % 32, Int8 / NF4): the caller falls back to the matvec kernels.
 static void fill_job(GemmParams& P, const MatJob& j, uint32_t n, uint32_t wg_begin) {
     P.w = j.w; P.kind = j.kind; P.k = j.k; P.m = j.m; P.row_bytes = j.row_bytes; P.act = j.act; P.n = n;
     P.has_res = j.has_res; P.in = j.in; P.out = j.out; P.res = j.res; P.wg_begin = wg_begin; P.scale = j.scale; P.dbg = j.dbg;
@@ -1640,190 +1522,86 @@ static void fill_job(GemmParams& P, const MatJob& j, uint32_t n, uint32_t wg_beg
     P.levels = (const float*)j.aux;
 }
 
-// the K-sliced kernel: 0 = launched, -1 = not applicable (the caller continues with the other kernels)
-static int launch_ks(hipStream_t s, const MatJob* jobs, int njobs, uint32_t n) {
-    // Measured (1.5B Q4_K_M decode, ms per step: K-split kernels | this kernel for ffn.value only | for every launch; profiles/r02_ks_modes.txt):
-    //   5 seq 1.265 | 1.222 | 1.382    8: 1.319 | 1.251 | 1.391    16: 1.498 | 1.390 | 1.468    24: 1.962 | 1.899 | 1.877
-    //   32: 2.158 | 2.044 | 1.967      48: 3.150 | 3.981 | 3.803   64: 3.474 | 4.295 | 4.011
-    // -> up to 16 tokens only the launch with few row tiles and long rows (ffn.value: 2048 rows x K = 8192, 13.8 -> 8.7 us at 16 tokens),
-    // 17 .. 32 tokens every eligible launch, beyond that none (a 64-token slice is 32 KB per 256-block: the ingest problem again).
-    // Each phase of the kernel is one memory round trip of ~2 us under load (stage | weights | tile out + count | tiles in), which is why it
-    // only wins where the K-split kernel needs four dependent block iterations.  WRK_GEMM_KS: 0 off | 1 as above | 2 every eligible launch.
-    // (read per call, not once per process: the tests switch it; launches are captured into graphs, so this is off the replay path)
-    const char* mode_env = getenv("WRK_GEMM_KS");
-    const int mode = mode_env ? atoi(mode_env) : 1;
-    if (mode <= 0 || !jobs[0].ks_part || !jobs[0].ks_cnt || n > 32) return -1;
-    const int nt = n <= 16 ? 1 : 2;
-    bool all_q8 = false, any_other = false;
-    for (int q = 0; q < njobs; ++q) {
-        if (jobs[q].kind == WRK_MAT_Q8_0) all_q8 = true;
-        else if (jobs[q].kind != WRK_MAT_F16) any_other = true;
-    }
-    all_q8 = all_q8 && !any_other;
-    if (mode == 1 && n <= 16) {
-        uint32_t tiles16 = 0, kmax = 0;
-        for (int q = 0; q < njobs; ++q) { tiles16 += (jobs[q].m + 15) / 16; kmax = jobs[q].k > kmax ? jobs[q].k : kmax; }
-        // round 3 (tools/ks_v6_sweep.sh, three RWKV-6 layers with D = 4096, ms per step, K-split kernels | this kernel with 2 | 4 blocks per slice):
-        //   Q5_K x 16 streams 0.508 | 0.515 | 0.570, x 8 0.429 | - | 0.538        -> the K4 kinds keep the rule above
-        //   Q8_0 x 16 streams 0.808 | 0.542 | 0.631, x 8 0.725 | - | 0.605        -> Q8_0 launches always come here (the K-split kernel's Q8_0
-        //   body loads four row scales per 32-block and lane; here a slice's scales are one 16-byte load per row), two blocks per slice
-        if (!(all_q8 || (tiles16 < 256 && kmax >= 4096))) return -1;
-    }
-    for (int q = 0; q < njobs; ++q) {
-        const MatJob& j = jobs[q];
-        if (j.kind != WRK_MAT_Q4_K && j.kind != WRK_MAT_Q5_K && j.kind != WRK_MAT_Q6_K && j.kind != WRK_MAT_Q8_0 && j.kind != WRK_MAT_F16) return -1;
-        if (j.kind == WRK_MAT_Q8_0 && (j.row_bytes & 15u)) return -1;       // the block scales of a slice are loaded as 16-byte vectors
-        if ((j.k & 255u) || j.k < 256) return -1;
-    }
-    // blocks per slice: as many as still give every CU a workgroup (fewer slices = fewer partial tiles to add); the staged activation
-    // slice (16 nt tokens x bps x 256) has to fit the default 64 KB of dynamic LDS
-    static const int force_bps = [] { const char* e = getenv("WRK_KS_BPS"); return e ? atoi(e) : 0; }();
-    int bps = 0;
-    for (int cand = (all_q8 && !force_bps) ? 2 : 4; cand >= 1 && !bps; cand >>= 1) {
-        if (nt * cand > 4) continue;
-        if (force_bps && cand != force_bps) continue;
-        bool div = true;
-        uint32_t wgs = 0;
-        for (int q = 0; q < njobs; ++q) { const uint32_t nb = jobs[q].k >> 8; div = div && nb % cand == 0; wgs += ((jobs[q].m + 63) / 64) * (nb / cand); }
-        if (div && (wgs >= 256 || cand == 1 || force_bps)) bps = cand;
-    }
-    if (!bps) return -1;
+// the K-sliced kernel takes a whole group; its scratch comes from the group's first job
+static int launch_ks(hipStream_t s, const MatJob* jobs, int njobs, const GemmPlan& P) {
     KsBatch B;
     B.g.njobs = njobs;
-    B.part = jobs[0].ks_part; B.counters = jobs[0].ks_cnt; B.ntp = 16u * nt;
-    uint32_t wg = 0, rg0 = 0;
-    size_t floats = 0;
+    B.part = jobs[0].ks_part; B.counters = jobs[0].ks_cnt; B.ntp = 16u * P.ks.nt;
     for (int q = 0; q < njobs; ++q) {
-        const uint32_t nsl = (jobs[q].k >> 8) / bps, nrg = (jobs[q].m + 63) / 64;
-        if (nsl > 64) return -1;
-        fill_job(B.g.jobs[q], jobs[q], n, wg);
-        B.ks[q].nslices = nsl; B.ks[q].rg_begin = rg0;
-        wg += nrg * nsl; rg0 += nrg;
-        floats += (size_t)nrg * nsl * 64 * 16 * nt;
+        fill_job(B.g.jobs[q], jobs[q], P.n, P.wg_begin[q]);
+        B.ks[q].nslices = P.ks.nslices[q]; B.ks[q].rg_begin = P.ks.rg_begin[q];
     }
-    // (row groups of one job are contiguous in the partial space: rg_begin counts row groups, the slices of a group sit side by side,
-    // so the partial offset of job q is rg_begin x nslices_q tiles only when all jobs share nslices -- they do: one bps, and K differs
-    // only between launches; checked here)
-    for (int q = 1; q < njobs; ++q)
-        if (B.ks[q].nslices != B.ks[0].nslices) return -1;
-    if (floats > jobs[0].ks_part_cap || rg0 > jobs[0].ks_cnt_cap) return -1;
-    const size_t smem = (size_t)16 * nt * (bps * 256 + 8) * sizeof(f16);
+    const size_t smem = P.ks.lds_bytes;
 #define KS_LAUNCH(NT_, BPS_)                                                                                                              \
     do {                                                                                                                                  \
         if (smem > 64 * 1024) {                                                                                                           \
             if (!lds_attr_once((const void*)gemm_ks_kernel<NT_, BPS_>, smem)) return -1;                                                  \
         }                                                                                                                                 \
-        gemm_ks_kernel<NT_, BPS_><<<dim3(wg), 256, smem, s>>>(B);                                                                         \
+        gemm_ks_kernel<NT_, BPS_><<<dim3(P.wgs[GEMM_KSLICED]), 256, smem, s>>>(B);                                                        \
     } while (0)
-    if (nt == 1) { if (bps == 4) KS_LAUNCH(1, 4); else if (bps == 2) KS_LAUNCH(1, 2); else KS_LAUNCH(1, 1); }
-    else { if (bps == 2) KS_LAUNCH(2, 2); else KS_LAUNCH(2, 1); }
+    if (P.ks.nt == 1) { if (P.ks.bps == 4) KS_LAUNCH(1, 4); else if (P.ks.bps == 2) KS_LAUNCH(1, 2); else KS_LAUNCH(1, 1); }
+    else { if (P.ks.bps == 2) KS_LAUNCH(2, 2); else KS_LAUNCH(2, 1); }
 #undef KS_LAUNCH
     return 0;
 }
 
+// All jobs multiply the same number of tokens; the jobs of a route run in ONE launch.  Returns -2 when any job is not for the MFMA
+// path: the caller falls back to the matvec kernels.
 int matmul_mfma_multi(hipStream_t s, const MatJob* jobs, int njobs, int) {
     if (njobs <= 0 || njobs > GEMM_MAX_JOBS) return -2;
     const uint32_t n = jobs[0].in.shape[1] * jobs[0].in.shape[2];
-    for (int j = 0; j < njobs; ++j)
-        if (!gemm_ok(jobs[j], n)) return -2;
-    if (launch_ks(s, jobs, njobs, n) == 0) return 0;
-    // prefill regime: Q4_K / Q5_K / Q6_K / F16 matrices with >= 64 rows go to the LDS-tiled kernel, the rest (Q8_0, Int8, short)
-    // to the K-split kernel, each group in one launch
-    static const bool use_tile = [] { const char* e = getenv("WRK_GEMM_TILE"); return !(e && e[0] == '0'); }();
-    // measured (round 1): SLOWER than the K-split kernel -- 12.2 vs 8.9 us for 8192 x 2048 x 16 tokens, batch-16 decode 2.35 vs
-    // 1.76 ms -- 128 workgroups leave half the CUs idle and every 256-block costs a workgroup barrier.  Off unless WRK_GEMM_DEC=1.
-    static const bool use_dec = [] { const char* e = getenv("WRK_GEMM_DEC"); return e && e[0] == '1'; }();
-    GemmBatch T, B, Dq, T2, T3;
-    T.njobs = B.njobs = Dq.njobs = T2.njobs = T3.njobs = 0;
-    uint32_t twg = 0, wg = 0, kmax = 0, dwg = 0, t2wg = 0, t3wg = 0;
-    // third-generation prefill tile (wrk_gemm3.hip): Q4_K, >= 128 stacked tokens, the launch's sum scratch at hand.  WRK_GEMM_TILE3=0: off
-    // (read per call: the tests compare the kernels)
-    const char* t3e = getenv("WRK_GEMM_TILE3");
-    const bool use_tile3 = !(t3e && t3e[0] == '0') && jobs[0].xsum != nullptr && n >= 128;        // (round 3: from 128 tokens on, K split over workgroups for one or two token tiles)
-    static const bool use_tile2 = [] { const char* e = getenv("WRK_GEMM_TILE2"); return !(e && e[0] == '0'); }();
+    GemmPlan P;
+    if (!gemm_plan(jobs, njobs, gemm_switches(n, jobs[0].ks_part && jobs[0].ks_cnt, jobs[0].xsum != nullptr), P)) return -2;
+    if (P.route[0] == GEMM_KSLICED) return launch_ks(s, jobs, njobs, P);
+    GemmBatch B[GEMM_ROUTES];
+    for (GemmBatch& b : B) b.njobs = 0;
     for (int q = 0; q < njobs; ++q) {
-        const MatJob& j = jobs[q];
-        // below 512 tokens the tile runs K-split (wrk_gemm3.hip) and pays a sum pre-pass and a reduce launch: measured (1.5B, tokens/s, this tile |
-        // the kernels below): 128 tokens 21.5 k | 21.6 k with every matrix on it -- only the long rows gain (ffn value, K = 8192: 49.5 us -> 16 + 6.5 + 5);
-        // 256 tokens 38.9 k | 35.8 k; 384 tokens (three token tiles, no split) 37.8 k | 46.6 k
-        const bool t3_n = n >= 512 || (n > 128 && n <= 256) || (n == 128 && j.k >= 4096);
-        if (use_tile3 && t3_n && (j.kind == WRK_MAT_Q4_K || j.kind == WRK_MAT_Q5_K) && j.m >= 128 && j.in.shape[2] == 1 && (j.k & 255u) == 0 && T3.njobs < GEMM_MAX_JOBS) {
-            fill_job(T3.jobs[T3.njobs++], j, n, t3wg);
-            t3wg += (j.m + 127) / 128;
-            continue;
-        }
-        // decode batches (<= 16 tokens): rows up to 24 blocks long go to the 64-row LDS tile; longer rows keep the K split
-        if (use_dec && n <= 16 && (j.kind == WRK_MAT_Q4_K || j.kind == WRK_MAT_Q5_K) && j.m >= 64 && j.in.shape[2] == 1 && (j.k >> 8) <= 24) {
-            fill_job(Dq.jobs[Dq.njobs++], j, n, dwg);
-            dwg += (j.m + TILE_ROWS - 1) / TILE_ROWS;
-            continue;
-        }
-        // the tile kernel walks the whole K in every wave: it needs enough workgroups to fill the chip (a 2048 x 8192
-        // matrix x 128 tokens has only 64 tiles and is faster on the K-split kernel: 44 vs 74 us)
-        const uint32_t tiles = ((j.m + TILE_ROWS - 1) / TILE_ROWS) * ((n + TILE_TOK - 1) / TILE_TOK);
-        // (Q8_0 has a body in the second-generation tile kernel only: >= 512 tokens, K % 128 == 0, rows in fours)
-        // (round 3: from 48 tokens on -- the first-generation tile has no Q8_0 body, and the K-split kernel re-reads the activations per 16 rows)
-        const bool q8_tile2 = j.kind == WRK_MAT_Q8_0 && use_tile2 && n >= 48 && (j.k & 127u) == 0 && (j.m & 3u) == 0;
-        const bool tile = use_tile && n >= 48 && (j.kind == WRK_MAT_Q4_K || j.kind == WRK_MAT_Q5_K || j.kind == WRK_MAT_Q6_K || j.kind == WRK_MAT_F16 || q8_tile2) && j.m >= 64 &&
-                          j.in.shape[2] == 1 && (tiles >= 96 || (j.k <= 2560 && tiles >= 64) ||    // enough workgroups, or a short serial walk,
-                                                 (j.kind == WRK_MAT_F16 && j.k <= 2560));          // or a LoRA down-projection (64..320 rows): a handful of
-        // tiles that ride along with the big matrices of their stage; on the K-split kernel they were a 32-us launch of 64 workgroups per layer
-        // K4 kinds whose output rows come in fours (one vector store per lane) take the second-generation tile kernel
-        // (with few workgroups -- a single 128-token chunk -- the first-generation kernel's longer stages are 4 % faster)
-        static const bool f16_tile2_on = [] { const char* e = getenv("WRK_GEMM_TILE2_F16"); return !(e && e[0] == '0'); }();
-        const bool f16_tile2 = f16_tile2_on && j.kind == WRK_MAT_F16 && (j.k & 127u) == 0 && (j.row_bytes & 15u) == 0;
-        if (tile && use_tile2 && (n >= 512 || q8_tile2) && (j.kind == WRK_MAT_Q4_K || j.kind == WRK_MAT_Q5_K || q8_tile2 || f16_tile2) && (j.m & 3u) == 0) { fill_job(T2.jobs[T2.njobs++], j, n, t2wg); t2wg += (j.m + TILE_ROWS - 1) / TILE_ROWS; }
-        else if (tile) { fill_job(T.jobs[T.njobs++], j, n, twg); twg += (j.m + TILE_ROWS - 1) / TILE_ROWS; }
-        else { fill_job(B.jobs[B.njobs++], j, n, wg); wg += (j.m + 15) / 16; kmax = j.k > kmax ? j.k : kmax; }
+        GemmBatch& b = B[P.route[q]];
+        fill_job(b.jobs[b.njobs++], jobs[q], n, P.wg_begin[q]);
     }
-    if (T3.njobs && gemm_tile3_launch(s, T3, t3wg, n, jobs[0].xsum, jobs[0].xsum_cap) != 0) {
-        // (scratch too small for this launch: the second-generation tile takes the jobs)
-        for (int q = 0; q < T3.njobs; ++q) { T2.jobs[T2.njobs] = T3.jobs[q]; T2.jobs[T2.njobs].wg_begin = t2wg; t2wg += (T3.jobs[q].m + TILE_ROWS - 1) / TILE_ROWS; ++T2.njobs; }
-    }
-    if (T2.njobs) {
+    if (B[GEMM_TILE3].njobs && gemm_tile3_launch(s, B[GEMM_TILE3], P, jobs[0].xsum) != 0) return -1;
+    if (B[GEMM_TILE2].njobs) {
         // 64-token tiles (TT = 4).  Measured on MI355X (round 2, 32 x 128-token prefill, tokens/s, 1.5B | 2.9B): first-generation tile
         // 86.8 k | 44.1 k; this kernel TT = 4 96.2 k | 49.0 k, TT = 6 96.8 k | 48.6 k, TT = 8 83.3 k | 42.1 k (308 registers: one
         // workgroup per CU, or spills at 256) -- more MFMAs per dequantised fragment buy nothing, the LDS fragment reads (1 KB per two
         // MFMAs) are the co-limiter; the gain is the unconditional loads and the shorter stages.
         const size_t smem2 = (size_t)2 * 64 * T2_ROW * sizeof(f16);       // 34 816 B
-        gemm_tile2_kernel<4><<<dim3(t2wg, (n + 63) / 64), 256, smem2, s>>>(T2);
+        gemm_tile2_kernel<4><<<dim3(P.wgs[GEMM_TILE2], (n + 63) / 64), 256, smem2, s>>>(B[GEMM_TILE2]);
     }
-    if (T.njobs) {
+    if (B[GEMM_TILE1].njobs) {
         const size_t smem = (size_t)2 * TILE_TOK * TILE_LDS_ROW * sizeof(f16);       // 67 584 B
         if (!lds_attr_once((const void*)gemm_tile_kernel, smem)) return -1;
-        gemm_tile_kernel<<<dim3(twg, (n + TILE_TOK - 1) / TILE_TOK), 256, smem, s>>>(T);
+        gemm_tile_kernel<<<dim3(P.wgs[GEMM_TILE1], (n + TILE_TOK - 1) / TILE_TOK), 256, smem, s>>>(B[GEMM_TILE1]);
     }
-    if (Dq.njobs) gemm_dec_kernel<<<dim3(dwg), 256, 0, s>>>(Dq);
-    if (B.njobs) {
-        // tokens per wave: enough tiles to amortise the decode, few enough to keep >= ~2 waves per SIMD;
-        // few row tiles x long rows (decode batches through ffn.value): 8 waves split K so a wave's serial chain is short
-        const bool deep = wg < 256 && kmax >= 4096;
-        // (measured, round 1: 16 waves x 2 blocks for K = 8192 is SLOWER, 23 vs 12 us at 2..16 tokens: 128 VGPRs per lane at 1024
-        // threads spill the all-kinds kernel to scratch)
-        if (n > 64) gemm_kernel<4, 4><<<dim3(wg, (n + 63) / 64), 256, 0, s>>>(B);
-        else if (n > 16) { if (deep) gemm_kernel<2, 8><<<dim3(wg, (n + 31) / 32), 512, 0, s>>>(B); else gemm_kernel<2, 4><<<dim3(wg, (n + 31) / 32), 256, 0, s>>>(B); }
-        else {
-            // two row tiles per workgroup where that still leaves >= ~200 workgroups (r, k, v + LoRA, ffn key at 16 tokens).  MEASURED SLOWER
-            // (round 3, 1.5B decode, ms per step, pairs | single tiles: 8 sequences 1.339 | 1.244, 16 sequences 1.456 | 1.377): halving the
-            // activation re-reads does not pay for twice the serial blocks per wave -- these launches are bound by the dependent chain of a
-            // workgroup, not by the L2 bandwidth of the shared stack.  Off unless WRK_GEMM_PAIR=1 (kept for the A/B and its test).
-            const char* n8 = getenv("WRK_GEMM_NW8");           // A/B: eight waves split K for every launch of <= 16 tokens
-            const bool nw8 = n8 && n8[0] == '1';
-            const char* pe = getenv("WRK_GEMM_PAIR");
-            bool pair = pe && pe[0] == '1' && !deep && wg >= 400;
-            for (int q = 0; q < B.njobs; ++q) pair = pair && (B.jobs[q].kind == WRK_MAT_Q4_K || B.jobs[q].kind == WRK_MAT_Q5_K || B.jobs[q].kind == WRK_MAT_F16);
-            if (pair) {
-                uint32_t wg2 = 0;
-                for (int q = 0; q < B.njobs; ++q) { B.jobs[q].wg_begin = wg2; wg2 += (B.jobs[q].m + 31) / 32; }
-                gemm_pair_kernel<4><<<dim3(wg2, (n + 15) / 16), 256, 0, s>>>(B);
-            }
-            else if (deep || nw8) gemm_kernel<1, 8><<<dim3(wg, (n + 15) / 16), 512, 0, s>>>(B);
-            else gemm_kernel<1, 4><<<dim3(wg, (n + 15) / 16), 256, 0, s>>>(B);
-        }
+    if (B[GEMM_KSPLIT].njobs) {
+        const GemmBatch& K = B[GEMM_KSPLIT];
+        const uint32_t wg = P.wgs[GEMM_KSPLIT], nt = P.split.nt, ty = (n + 16 * nt - 1) / (16 * nt);
+        if (P.split.pair) gemm_pair_kernel<4><<<dim3(wg, ty), 256, 0, s>>>(K);
+        else if (nt == 4) gemm_kernel<4, 4><<<dim3(wg, ty), 256, 0, s>>>(K);
+        else if (nt == 2) { if (P.split.nw == 8) gemm_kernel<2, 8><<<dim3(wg, ty), 512, 0, s>>>(K); else gemm_kernel<2, 4><<<dim3(wg, ty), 256, 0, s>>>(K); }
+        else { if (P.split.nw == 8) gemm_kernel<1, 8><<<dim3(wg, ty), 512, 0, s>>>(K); else gemm_kernel<1, 4><<<dim3(wg, ty), 256, 0, s>>>(K); }
     }
     return 0;
 }
 
 int matmul_mfma(hipStream_t s, const MatJob& j, int num_cu) { return matmul_mfma_multi(s, &j, 1, num_cu); }
+
+// The one chain every matmul call site runs: all jobs in one MFMA group, else per matrix on the MFMA path, else per matrix on the matvec
+// kernels; with fewer than gemm_min_tokens() `tokens` the matvec kernels at once.  ks / t3: scratch for the group, set on job 0 (a launch reads it
+// from its first job), nullptr = none.  On failure *bad (if given) is the job that was rejected.
+int matmul_jobs(hipStream_t s, MatJob* jobs, int n, uint32_t tokens, int num_cu, const KsScratch* ks, const T3Scratch* t3, FewTokens few, int* bad) {
+    const bool gemm = tokens >= gemm_min_tokens();
+    if (gemm) {
+        if (ks) { jobs[0].ks_part = ks->part; jobs[0].ks_cnt = ks->cnt; jobs[0].ks_part_cap = ks->part_cap; jobs[0].ks_cnt_cap = ks->cnt_cap; }
+        if (t3) { jobs[0].xsum = t3->p; jobs[0].xsum_cap = t3->cap; }
+        if (matmul_mfma_multi(s, jobs, n, num_cu) == 0) return 0;
+    } else if (few == FewTokens::matvec_grouped) return matvec_grouped(s, jobs, n, num_cu);
+    for (int i = 0; i < n; ++i) {
+        int rc = gemm ? matmul_mfma(s, jobs[i], num_cu) : -2;
+        if (rc == -2) rc = matvec(s, &jobs[i], 1, num_cu);
+        if (rc != 0) { if (bad) *bad = i; return rc; }
+    }
+    return 0;
+}
 
 }  // namespace wrk

@@ -450,54 +450,28 @@ __global__ void __launch_bounds__(256) t3_reduce_kernel(const T3Batch B, uint32_
     else { typedef _Float16 f16x4 __attribute__((ext_vector_type(4))); *(f16x4*)((f16*)P.out_p + oo) = (f16x4){(f16)o[0], (f16)o[1], (f16)o[2], (f16)o[3]}; }
 }
 
-int gemm_tile3_launch(hipStream_t s, const GemmBatch& T3, uint32_t row_tiles, uint32_t n, void* xsum, size_t xsum_cap) {
-    if (T3.njobs <= 0 || !xsum) return -1;
+static_assert(T3_ROWS == (int)ROUTE_T3_ROWS && T3_TOK == (int)ROUTE_T3_TOK, "gemm_plan counts this kernel's tiles");
+
+int gemm_tile3_launch(hipStream_t s, const GemmBatch& T3, const GemmPlan& plan, void* xsum) {
+    const GemmPlan::Tile3& t3 = plan.t3;
+    const uint32_t n = plan.n;
     T3Batch B;
     B.g = T3;
-    // one pair of sum arrays per DISTINCT input (r, k, v of a layer read three different shifted inputs; a repeated one is summed once)
-    size_t used = 0;
-    const f16* seen_x[GEMM_MAX_JOBS];
-    int nseen = 0;
+    B.bps = t3.bps; B.kslices = t3.kslices; B.part = t3.kslices > 1 ? (float*)xsum : nullptr;
     for (int q = 0; q < T3.njobs; ++q) {
         const GemmParams& P = T3.jobs[q];
-        int hit = -1;
-        for (int u = 0; u < q; ++u)
-            if (T3.jobs[u].x == P.x && T3.jobs[u].xs == P.xs && T3.jobs[u].k == P.k) { hit = u; break; }
-        if (hit >= 0) { B.sh[q] = B.sh[hit]; B.sl[q] = B.sl[hit]; B.ts[q] = B.ts[hit]; continue; }
-        const size_t cnt = (size_t)n * (P.k >> 5), bytes = (cnt * 2 + 255) & ~(size_t)255, tbytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-        if (used + 2 * bytes + tbytes > xsum_cap) return -1;
-        f16* sh = (f16*)((char*)xsum + used);
-        f16* sl = (f16*)((char*)xsum + used + bytes);
-        float* ts = (float*)((char*)xsum + used + 2 * bytes);
-        used += 2 * bytes + tbytes;
+        f16* sh = (f16*)((char*)xsum + t3.sh_off[q]);
+        f16* sl = (f16*)((char*)xsum + t3.sl_off[q]);
+        float* ts = (float*)((char*)xsum + t3.ts_off[q]);
         B.sh[q] = sh; B.sl[q] = sl; B.ts[q] = ts;
-        seen_x[nseen++] = P.x;
+        B.poff[q] = t3.part_off[q] / sizeof(float);
+        if (t3.sums_of[q] != q) continue;       // an earlier job's input: summed once
         if ((P.k >> 5) > 64) xsum_kernel<4><<<dim3(n), 256, 0, s>>>(P.x, P.xs, n, P.k >> 5, sh, sl, ts);
         else xsum_kernel<1><<<dim3((n + 3) / 4), 256, 0, s>>>(P.x, P.xs, n, P.k >> 5, sh, sl, ts);
     }
-    (void)seen_x;
-    // K split: one or two token tiles and fewer than ~160 workgroups -> slices of 4, 2 or 1 blocks (the first that fills the chip), all jobs of the
-    // launch the same K.  Partial tiles behind the sum arrays in the launch's scratch.
-    const uint32_t ttiles = (n + T3_TOK - 1) / T3_TOK;
-    B.bps = 0; B.kslices = 1; B.part = nullptr;
-    {
-        bool same_k = true;
-        for (int q = 1; q < T3.njobs; ++q) same_k = same_k && T3.jobs[q].k == T3.jobs[0].k;
-        const uint32_t nb = T3.jobs[0].k >> 8;
-        const char* se = getenv("WRK_T3_SPLIT");        // 0: off (A/B)
-        if (same_k && ttiles <= 2 && row_tiles * ttiles < 160 && nb >= 2 && !(se && se[0] == '0')) {
-            uint32_t bps = 1;
-            for (uint32_t cand = 4; cand >= 1; cand >>= 1)
-                if (nb % cand == 0 && nb / cand >= 2 && row_tiles * ttiles * (nb / cand) >= 160) { bps = cand; break; }
-            const uint32_t ks = (nb + bps - 1) / bps;
-            size_t floats = 0, at = (used + 255) & ~(size_t)255;
-            for (int q = 0; q < T3.njobs; ++q) { B.poff[q] = floats; floats += (size_t)ks * n * T3.jobs[q].m; }
-            if (ks >= 2 && at + floats * 4 <= xsum_cap) { B.bps = bps; B.kslices = ks; B.part = (float*)((char*)xsum + at); }
-        }
-    }
     const char* de = getenv("WRK_T3_DIAG");
     const int diag = de ? atoi(de) : 0;
-    const dim3 grid(row_tiles, ttiles, B.kslices);
+    const dim3 grid(plan.wgs[GEMM_TILE3], t3.ttiles, B.kslices);
 #define T3_GO(D) do { if (!lds_attr_once((const void*)gemm_tile3_kernel<D>, T3_LDS)) return -1; gemm_tile3_kernel<D><<<grid, 512, T3_LDS, s>>>(B); } while (0)
     if (diag == 1) T3_GO(1); else if (diag == 2) T3_GO(2); else if (diag == 3) T3_GO(3); else if (diag == 4) T3_GO(4); else T3_GO(0);
 #undef T3_GO

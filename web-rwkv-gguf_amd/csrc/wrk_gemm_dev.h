@@ -6,6 +6,7 @@
 #include <utility>
 
 #include "wrk_device.h"
+#include "wrk_gemm_route.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel: set it once per (device, kernel), under a lock (contexts
 // on several GPUs, encoders on several threads) -- ADVICE r02: a process-wide `static bool done` left the second GPU's launch rejected.
@@ -66,8 +67,7 @@ struct GemmParams {
     const float* levels;        // NF4 / SF4: the 16 f32 levels (device)
 };
 
-constexpr int GEMM_MAX_JOBS = 8;
-struct GemmBatch {
+struct GemmBatch {        // the jobs of one launch (at most GEMM_MAX_JOBS: wrk_gemm_route.h)
     GemmParams jobs[GEMM_MAX_JOBS];
     int njobs;
 };
@@ -76,8 +76,8 @@ struct GemmBatch {
 __device__ __forceinline__ void tok_tb(const DTensor& d, uint32_t tok, uint32_t& t, uint32_t& b) { t = tok % d.shape[1]; b = tok / d.shape[1]; }
 
 
-// wrk_gemm3.hip: third-generation prefill tile (Q4_K, >= 512 stacked tokens).  `xsum`: scratch of xsum_cap bytes for the per-sub-block
-// input sums.  0 = launched, -1 = not applicable (scratch too small, ...)
-int gemm_tile3_launch(hipStream_t s, const GemmBatch& T3, uint32_t row_tiles, uint32_t n, void* xsum, size_t xsum_cap);
+// wrk_gemm3.hip: third-generation prefill tile (Q4_K / Q5_K, >= 128 stacked tokens).  T3: the jobs gemm_plan() routed to it, plan.t3 their
+// scratch layout and K split, `xsum` the scratch the layout was planned for.  0 = launched, -1 = a HIP call failed
+int gemm_tile3_launch(hipStream_t s, const GemmBatch& T3, const GemmPlan& plan, void* xsum);
 
 }  // namespace wrk

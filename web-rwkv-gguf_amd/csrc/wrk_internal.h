@@ -15,6 +15,7 @@
 
 #include "wrk_hip.h"
 #include "wrk_dev_group.h"
+#include "wrk_matjob.h"
 
 struct wrk_ctx {
     int device = 0;
@@ -113,16 +114,7 @@ struct wrk_dev_arena : wrk_dev_layout {
     template <class T> T* at(size_t o) const { return (T*)(base + o); }
 };
 
-// ------------------------------------------------------------------ device-side tensor descriptor
-// Mirrors `View` addressing (see wrk_hip.h).  Passed by value to kernels.
-struct DTensor {
-    void* p;
-    uint32_t dtype;     // WRK_F16 / WRK_F32
-    uint32_t shape[4];
-    uint32_t stride[4];
-    uint32_t offset[4];
-};
-
+// ------------------------------------------------------------------ device-side tensor descriptor (DTensor: wrk_matjob.h)
 inline DTensor make_dtensor(const wrk_tensor* t) {
     DTensor d;
     d.p = t->buf ? t->buf->ptr : nullptr;
@@ -387,47 +379,7 @@ void queue_turnover(hipStream_t s, const QueueGeom& g, const QueueBufs& q, const
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled
 void timing_report(wrk_ctx* ctx);
 
-// wrk_matvec.hip
-struct MatJob {
-    const uint8_t* w;       // matrix data (device layout)
-    const uint8_t* aux;
-    uint32_t kind, flags;
-    uint32_t k, m;
-    uint32_t row_bytes;
-    DTensor in;             // [K, T, B]
-    DTensor out;            // [M, T, B]
-    uint32_t act;
-    uint32_t sparse;
-    uint32_t has_res = 0;   // fused `add`: out = round_to_out_dtype(act(W.x)) + res
-    DTensor res{};
-    float* amax_val = nullptr;      // optional fused arg-max partials [num_wg][ntok]
-    uint32_t* amax_idx = nullptr;
-    // fused decode prologue / epilogue (single input vector only; matvec() returns -3 if it cannot honour them)
-    uint32_t pro = 0;               // 1: input = mix(LN(in; ln_w, ln_b, pro_eps), prev, mixw)
-                                    // 2: input = mixw * r16(r16(GN64(in; ln_w, ln_b, pro_eps)) + prev): the post-WKV stage of a split head
-                                    //    (in = WKV output, prev = f32 time_first term, mixw = gate), dmv kernels only
-    float pro_eps = 0.0f;
-    const void *ln_w = nullptr, *ln_b = nullptr, *mixw = nullptr;
-    const float* prev = nullptr;    // f32 shift-state row of this sequence
-    void* ln_out = nullptr;         // f16 [K]: LN(in), published by the first workgroup of the job
-    const void* carry_src = nullptr;    // epilogue: carry_dst[row] = carry_src[row]
-    float* carry_dst = nullptr;
-    float scale = 1.0f;                 // wrk_matrix::out_scale
-    const void* gate = nullptr;         // f16 [M]: out = round(sigmoid(gate[row]) * round(act(W.x)))  (channel_mix.wgsl:104-106, RWKV-6), before the residual
-    unsigned long long* dbg = nullptr;  // WRK_TIMING=1: 16 device timestamps of this launch (first and last workgroup)
-    // several input vectors (2 .. 4 sequences decoding together, dmv kernels): element strides from one token's operand to the next
-    uint32_t tok_prev_stride = 0, tok_mix_stride = 0, tok_carry_src_stride = 0, tok_carry_dst_stride = 0, tok_gate_stride = 0;
-    // decode batches on the matrix cores: scratch of the K-sliced GEMM (f32 partial tiles, per-row-group arrival counters that are
-    // zero between launches); taken from the first job of a launch, nullptr = the kernel is not used
-    float* ks_part = nullptr;
-    uint32_t* ks_cnt = nullptr;
-    size_t ks_part_cap = 0;         // floats
-    uint32_t ks_cnt_cap = 0;
-    // third-generation prefill tile (>= 512 stacked tokens, Q4_K): scratch for the sub-block input sums, taken from the first job of a
-    // launch (wrk_ctx::gemm_scratch); nullptr = the kernel is not used
-    void* xsum = nullptr;
-    size_t xsum_cap = 0;            // bytes
-};
+// wrk_matvec.hip (MatJob: wrk_matjob.h)
 uint32_t matvec_num_wg(const MatJob* jobs, int njobs, int num_cu, uint32_t* rows_per_wg);
 // dry_run: classify only (0 = a launch would honour every job's prologue / carry request, -3 = it cannot)
 // dmv_only: with 2 .. 4 input vectors, -5 unless the multi-token dmv kernels take the launch (the caller then prefers the matrix cores)
@@ -438,6 +390,15 @@ int matvec_grouped(hipStream_t s, const MatJob* jobs, int njobs, int num_cu, boo
 int matmul_mfma(hipStream_t s, const MatJob& job, int num_cu);
 // several matrices x the same tokens in ONE launch (-2 if any job is not for the MFMA path)
 int matmul_mfma_multi(hipStream_t s, const MatJob* jobs, int njobs, int num_cu);
+// The chain every matmul call site runs: the jobs as one MFMA group, else per matrix on the MFMA path, else per matrix on the matvec
+// kernels.  With `tokens` (the caller's step; a head launch may have fewer rows of its own) below gemm_min_tokens() the matvec kernels at
+// once, per matrix or as one matvec_grouped call (few).  ks: scratch of the K-sliced GEMM, t3: of the third-generation prefill tile; both
+// go to job 0 only (a launch reads them from its first job), nullptr = none: that kernel is not used.  Returns 0 or the failing launch's
+// code, with *bad (if given) the job it was for
+struct KsScratch { float* part; uint32_t* cnt; size_t part_cap; uint32_t cnt_cap; };
+struct T3Scratch { void* p; size_t cap; };
+enum class FewTokens { matvec_each, matvec_grouped };
+int matmul_jobs(hipStream_t s, MatJob* jobs, int n, uint32_t tokens, int num_cu, const KsScratch* ks, const T3Scratch* t3, FewTokens few, int* bad = nullptr);
 uint32_t gemm_min_tokens();
 // wrk_quant.hip
 void quantize_int8(hipStream_t s, const void* src_f16, uint8_t* dst, uint32_t k, uint32_t m, uint32_t row_bytes);

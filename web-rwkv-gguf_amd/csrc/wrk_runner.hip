@@ -16,16 +16,13 @@ int32_t wrk_mm(wrk_ctx* ctx, const wrk_matrix* m, DTensor in, DTensor out, uint3
 }
 
 int32_t wrk_mm_group(wrk_ctx* ctx, wrk::MatJob* jobs, int n) {
-    hipStream_t q = ctx->op_stream();
-    const bool gemm = jobs[0].in.shape[1] * jobs[0].in.shape[2] >= wrk::gemm_min_tokens();
-    // scratch of the third-generation prefill tile: a launch reads it from its first job, and every job may lead a launch of its own below
-    for (int i = 0; i < n; ++i) { jobs[i].xsum = ctx->gemm_scratch; jobs[i].xsum_cap = ctx->gemm_scratch_cap; }
-    if (gemm && wrk::matmul_mfma_multi(q, jobs, n, ctx->num_cu) == 0) return WRK_OK;
-    for (int i = 0; i < n; ++i) {
-        int rc = gemm ? wrk::matmul_mfma(q, jobs[i], ctx->num_cu) : -2;
-        if (rc == -2) rc = wrk::matvec(q, &jobs[i], 1, ctx->num_cu);
-        if (rc != 0) return wrk_fail(ctx, WRK_E_ARG, "matmul launch rejected (K=%u M=%u rc=%d)", jobs[i].k, jobs[i].m, rc);
-    }
+    // scratch of the third-generation prefill tile: a launch reads it from its first job, and every job may lead a launch of its own in the
+    // per-matrix leg
+    const wrk::T3Scratch t3{ctx->gemm_scratch, ctx->gemm_scratch_cap};
+    for (int i = 1; i < n; ++i) { jobs[i].xsum = t3.p; jobs[i].xsum_cap = t3.cap; }
+    int bad = 0;
+    const int rc = wrk::matmul_jobs(ctx->op_stream(), jobs, n, jobs[0].in.shape[1] * jobs[0].in.shape[2], ctx->num_cu, nullptr, &t3, wrk::FewTokens::matvec_each, &bad);
+    if (rc != 0) return wrk_fail(ctx, WRK_E_ARG, "matmul launch rejected (K=%u M=%u rc=%d)", jobs[bad].k, jobs[bad].m, rc);
     return WRK_OK;
 }
 

@@ -362,18 +362,9 @@ int32_t wrk_v6_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
         if (L.time_mix_w2[1]->row_bytes != L.time_mix_w2[0]->row_bytes) return WRK_E_UNSUPPORTED;
     }
     auto vec = [&](void* p, uint32_t c = 0, uint32_t dt = WRK_F16) { return make_dense(p, dt, c ? c : D, T); };
+    const wrk::KsScratch ks{s.ks_part, s.ks_cnt, s.ks_part_cap, s.ks_cnt_cap};
     auto run_jobs = [&](wrk::MatJob* jobs, int n) -> int {
-        if (T >= wrk::gemm_min_tokens()) {
-            jobs[0].ks_part = s.ks_part; jobs[0].ks_cnt = s.ks_cnt; jobs[0].ks_part_cap = s.ks_part_cap; jobs[0].ks_cnt_cap = s.ks_cnt_cap;
-            if (wrk::matmul_mfma_multi(q, jobs, n, ctx->num_cu) == 0) return 0;
-            for (int i = 0; i < n; ++i) {
-                int rc = wrk::matmul_mfma(q, jobs[i], ctx->num_cu);
-                if (rc == -2) rc = wrk::matvec(q, &jobs[i], 1, ctx->num_cu);
-                if (rc != 0) return rc;
-            }
-            return 0;
-        }
-        return wrk::matvec_grouped(q, jobs, n, ctx->num_cu);
+        return wrk::matmul_jobs(q, jobs, n, T, ctx->num_cu, &ks, nullptr, wrk::FewTokens::matvec_grouped);
     };
 #define LNMIX(P, n) do { if (wrk::ln_mix(q, P, n) != 0) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "ln_mix shape"); } while (0)
     // arrival counters of the K-sliced GEMM: zero at the head of every step (a launch that aborted must not poison the next replay)

@@ -526,19 +526,11 @@ int32_t wrk_v7_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
     auto vec = [&](void* p, uint32_t c = 0) { return make_dense(p, WRK_F16, c ? c : D, T); };
     // batched decode (many sequences): each matrix goes to the MFMA GEMM; few sequences: one multi-matrix matvec launch
     bool single = false;        // this layer runs the 5-launch structure (prologue-fused dmv kernels)
+    const KsScratch ks{s.ks_part, s.ks_cnt, s.ks_part_cap, s.ks_cnt_cap};
+    const T3Scratch t3{ctx->gemm_scratch, ctx->gemm_scratch_cap};
     auto run_jobs = [&](MatJob* jobs, int n) -> int {
-        if (!single && T >= gemm_min_tokens()) {
-            jobs[0].ks_part = s.ks_part; jobs[0].ks_cnt = s.ks_cnt; jobs[0].ks_part_cap = s.ks_part_cap; jobs[0].ks_cnt_cap = s.ks_cnt_cap;
-            jobs[0].xsum = ctx->gemm_scratch; jobs[0].xsum_cap = ctx->gemm_scratch_cap;
-            if (matmul_mfma_multi(q, jobs, n, ctx->num_cu) == 0) return 0;      // all matrices of the stage in one launch
-            for (int i = 0; i < n; ++i) {
-                int rc = matmul_mfma(q, jobs[i], ctx->num_cu);
-                if (rc == -2) rc = matvec(q, &jobs[i], 1, ctx->num_cu);
-                if (rc != 0) return rc;
-            }
-            return 0;
-        }
-        return matvec_grouped(q, jobs, n, ctx->num_cu);
+        if (single) return matvec_grouped(q, jobs, n, ctx->num_cu);
+        return matmul_jobs(q, jobs, n, T, ctx->num_cu, &ks, &t3, FewTokens::matvec_grouped);     // all matrices of the stage in one launch
     };
 #define LN(P, n)                                                                             \
     do {                                                                                     \
