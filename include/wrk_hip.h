@@ -694,7 +694,21 @@ int32_t wrk_stop_sequences_advance(wrk_ctx* ctx, uint32_t num_vocab, uint32_t nu
  * call-wide.  A slot's window is set to length 0 when a request is dispatched to it, at step 0 or at a refill on the device, and
  * takes only that request's reply draws: prompt tokens and the discarded draws of the steps that feed them never enter it.  After
  * the call rows [0, num_batch) of the window are unspecified.  The window is not part of a state-pool entry.  The seven fields sit
- * between out_top_logprobs and grammar. */
+ * between out_top_logprobs and grammar.
+ * Prompt intake.  prompt_context_from (host u32 [num_requests], NULL: off -- everything above) lets a request's prompt enter its slot's
+ * context, the slot's occurrence row and its window: with f = prompt_context_from[r] the tokens p_f .. p_{n-1} enter in order, on the
+ * device, after the reset (or the restore from a history pool) that the dispatch makes and before the row y_0 is picked from is
+ * penalised; f >= n: none.  A token enters the occurrence row as wrk_occurrence_add does with decay[r] (every count *= decay[r], then
+ * count[p] += w[p], present[p] = 1) and the window as wrk_token_window_add does (a full ring drops its oldest token).  The draws of the
+ * steps that feed prompt tokens stay discarded, and mu, the automaton state, the stop tail and the log-probs see what they saw: a reply
+ * still does not depend on when or where its request was scheduled.  An offset, not a flag: a state-pool entry has consumed its
+ * conversation but the last reply token, which therefore opens the next turn's prompt and which the entry's history has already
+ * counted as a draw -- such a turn passes 1.  WRK_E_ARG before any launch: prompt_context_from with neither `occ` (and its penalty
+ * arrays) nor `window`.  The offsets are device data: one cached step program serves any of them; intake calls replay step programs of
+ * their own, a call with NULL exactly the programs it ran before.  `history` (NULL: off) is the history pool of a call with a state
+ * pool, described with wrk_queue_pool below; without a pool (wrk_v7_generate_queue) it is WRK_E_ARG.  The two fields sit between
+ * max_steps and num_top: every field behind them keeps its order, the filter fields last. */
+typedef struct wrk_history_pool wrk_history_pool;   /* a history pool beside a state pool: wrk_queue_pool, below */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
     const uint32_t *prompt_tokens, *prompt_offsets, *max_new;
@@ -705,6 +719,8 @@ typedef struct wrk_queue_options {
     wrk_occurrence *occ;
     const wrk_buf *init_state;
     uint32_t poll_steps, max_steps;
+    const uint32_t *prompt_context_from;
+    wrk_history_pool *history;
     uint32_t num_top;
     float *out_logprob;
     uint32_t *out_top_ids;
@@ -742,8 +758,40 @@ int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* s
  * buffer as init_state, two requests saving to one entry, a request reading an entry that another request of the call saves to.
  * WRK_E_UNSUPPORTED: (S+2) * D not a multiple of 4.  The pool's address and entry count are data of the step program: one cached
  * program serves any pool, and pool programs never share a program with wrk_v7_generate_queue's.  Occurrence rows are reset at every
- * request start, as without a pool. */
+ * request start, as without a pool -- unless the call has a `history` (below).
+ * A history pool beside the state pool: what a conversation's penalties have seen, kept on the device next to its state.  Entry k of a
+ * wrk_history_pool holds an occurrence row -- count f32 [num_vocab] and the present bit per token -- and, with window_capacity > 0, a
+ * token window (the ring, its length and its write position): what slot b of a wrk_occurrence and of a wrk_token_window hold.  Banned
+ * bits are not part of an entry: they stay the slot's, as at a reset.  create: empty entries (zero counts, no bits, empty windows).
+ * load: entry <- counts / present (host f32 / u32 [num_vocab], both or neither: an empty row; counts finite, present 0 or 1) and
+ * tokens[0..n) (n <= window_capacity, ids < num_vocab, oldest first; NULL: an empty window).  back: the reverse; tokens_out host u32
+ * [window_capacity] (may be NULL without windows), *len the window's length.  put: entry <- slot `batch` of `occ` (the present bit
+ * only) and of `window`; get: slot <- entry, the slot keeping its banned bits; both on the device, with the copy kernel of the queue's
+ * turnover.  occ or window may be NULL (one is required); a pool with windows needs `window`, of the pool's capacity, and a pool
+ * without them takes none; context and num_vocab must be the pool's (else WRK_E_ARG).  All six are blocking.
+ * wrk_queue_options.history (NULL: off; wrk_queue_pool keeps its five fields, so the pointer travels with the options of the call):
+ * entry k of it belongs to entry k of `states`, and start / save index both.  Request r with
+ * start[r] = k begins, at step 0 or at a refill, with slot.count = entry.count, slot.flags = (slot.flags & banned) | entry.present and
+ * the entry's window, order and length kept; a request with no start entry begins as without a history -- row reset, bans kept,
+ * window empty.  When r ends with reason 1 or 2 and save[r] = k, entry k receives the slot's row (the present bit only) and window in
+ * the step that ends r, on the device, after that step's counted draw: the entry has counted the last reply token y_j that the saved
+ * state has not consumed -- what wrk_v7_generate_stop leaves in the handles of a sequence that ends there.  Reasons 3 and 0 write
+ * nothing; saved[r] speaks for both pools.  prompt_context_from enters its tokens after the restore.  WRK_E_ARG before any launch,
+ * nothing on the device changed: a history in a call without a pool; a history with neither `occ` nor `window` in the options; a history of another context, num_vocab or
+ * num_entries; a history with windows of another capacity than `window`'s; `window` with a history created without windows; a history
+ * with windows and no `window`.  The pool's addresses are device data: one cached step program serves any history pool; history calls
+ * replay step programs of their own, a call with NULL exactly the programs it ran before. */
 #define WRK_QUEUE_NO_ENTRY 0xFFFFFFFFu
+int32_t wrk_history_pool_create(wrk_ctx* ctx, uint32_t num_entries, uint32_t num_vocab, uint32_t window_capacity, wrk_history_pool** out);
+int32_t wrk_history_pool_destroy(wrk_history_pool* history);
+int32_t wrk_history_pool_load(wrk_ctx* ctx, wrk_history_pool* history, uint32_t entry, const float* counts_or_null,
+                              const uint32_t* present_or_null, const uint32_t* tokens_or_null, uint32_t n);
+int32_t wrk_history_pool_back(wrk_ctx* ctx, const wrk_history_pool* history, uint32_t entry, float* counts, uint32_t* present,
+                              uint32_t* tokens_out, uint32_t* len);
+int32_t wrk_history_pool_put(wrk_ctx* ctx, wrk_history_pool* history, uint32_t entry, wrk_occurrence* occ_or_null, uint32_t batch,
+                             wrk_token_window* window_or_null);
+int32_t wrk_history_pool_get(wrk_ctx* ctx, wrk_history_pool* history, uint32_t entry, wrk_occurrence* occ_or_null, uint32_t batch,
+                             wrk_token_window* window_or_null);
 typedef struct wrk_queue_pool {
     wrk_buf *states;
     uint32_t num_entries;

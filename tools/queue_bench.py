@@ -27,6 +27,18 @@ The legs alternate; medians of the wall time of whole calls (a, b) and of the HI
 
     python tools/queue_bench.py --pool [--batches 1,16,32] [--turn-batches 16,32] [--turns 4] [--reps 3] [--steps 64]
 
+--history measures prompt intake and the history pool: one runtime of --history-batch slots, a penalised + DRY sampled
+queue with a state pool, R = --requests-per-slot * B requests with prompts of --history-prompt tokens -- several times their replies,
+uniform in [8, 16] -- every request in place on its own entry.
+
+  (a) the call without the new arguments: the whole workload (wall time) and the per-step time of a program whose requests never end
+  (c) the same two with `history` and `count_prompt`, alternating with (a)
+
+--baseline runs (a) alone and names nothing this feature added, so the same file also runs on the commit before it: that run is leg
+(b), taken in the same job, the two commits alternating.
+
+    python tools/queue_bench.py --history [--baseline] [--history-batch 16] [--history-prompt 48] [--reps 5] [--steps 64]
+
 Prints one JSON object.
 """
 import argparse
@@ -132,6 +144,60 @@ def pool_bench(args, wrk, ctx, data, skw):
     return out
 
 
+def history_bench(args, wrk, ctx, data, skw):
+    B, W = args.history_batch, args.history_window
+    rt = wrk.Runtime(ctx, wrk.GgufReader(data), num_batch=B)
+    V = rt.info.num_vocab
+    R = args.requests_per_slot * B
+    lens = np.random.default_rng(7).integers(8, 17, R).tolist()
+    prompts = [[(17 + 101 * r + 7 * i) % (V - 1) for i in range(args.history_prompt)] for r in range(R)]
+    occ, win, pool = wrk.Occurrence(ctx, B, V), wrk.TokenWindow(ctx, B, V, W), wrk.StatePool(ctx, rt, R)
+    pick = dict(occurrence=occ, presence=0.3, frequency=0.2, decay=0.996, window=win, dry=(0.8, 1.75, 2), **skw)
+    own = list(range(R))
+    new = {} if args.baseline else dict(history=wrk.HistoryPool(ctx, R, V, W), count_prompt=True)
+
+    def workload(**extra):
+        t0 = time.perf_counter()
+        res, run = rt.generate_queue(prompts, max_new=lens, pool=pool, start_state=own, save_state=own, **pick, **extra)
+        ms = (time.perf_counter() - t0) * 1e3
+        assert [len(t) for t, *_ in res] == lens and all(rt.last_queue_saved)
+        return ms, run
+
+    def step_ms(**extra):
+        res, run = rt.generate_queue([[(17 + 101 * b) % (V - 1)] for b in range(B)], max_new=args.steps, max_steps=args.steps, poll_steps=0xffffffff,
+                                     pool=pool, start_state=own[:B], save_state=own[:B], **pick, **extra)
+        assert run == args.steps and [len(t) for t, *_ in res] == [args.steps] * B
+        return rt.last_queue_ms / args.steps
+    legs = [("plain", {})] + ([] if args.baseline else [("history", new)])
+    for _, extra in legs:                           # capture and warm up
+        workload(**extra), step_ms(**extra)
+    wall, steps, per_step = {k: [] for k, _ in legs}, {}, {k: [] for k, _ in legs}
+    for _ in range(args.reps):
+        for k, extra in legs:
+            ms, steps[k] = workload(**extra)
+            wall[k].append(ms)
+            per_step[k].append(step_ms(**extra))
+    med = lambda runs: float(np.median(runs))       # noqa: E731
+    out = {"model": f"RWKV-7 {args.model} Q4_K_M (synthetic)", "batch": B, "requests": R, "prompt_tokens": args.history_prompt,
+           "reply_lengths": "uniform [8, 16], seed 7", "reply_tokens": int(sum(lens)), "window_capacity": W, "reps": args.reps,
+           "pick": "sampled, presence 0.3 frequency 0.2 decay 0.996, DRY 0.8 / 1.75 / 2", "baseline_only": bool(args.baseline), **skw}
+    for k, _ in legs:
+        out[k] = {"workload_ms": round(med(wall[k]), 2), "workload_steps": steps[k], "never_ending_ms_per_step": round(med(per_step[k]), 5),
+                  "workload_ms_all": [round(x, 2) for x in wall[k]], "never_ending_ms_per_step_all": [round(x, 5) for x in per_step[k]]}
+    if not args.baseline:
+        d_step = (med(per_step["history"]) - med(per_step["plain"])) * 1e3
+        d_wall = (med(wall["history"]) - med(wall["plain"])) * 1e3
+        out["history_minus_plain_us_per_step"] = round(d_step, 2)
+        out["history_minus_plain_workload_us"] = round(d_wall, 1)
+        # what of the workload's difference the per-step difference does not explain, over its R turnovers: a residual, which also
+        # holds whatever the sampler and DRY spend on rows and windows that now have a context
+        out["per_turnover_us"] = round((d_wall - d_step * steps["history"]) / R, 2)
+        new["history"].close()
+    for h in (occ, win, pool, rt):
+        h.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -143,6 +209,11 @@ def main():
     ap.add_argument("--pool", action="store_true", help="the state-pool legs (DESIGN.md §7g) in the place of the queue's")
     ap.add_argument("--turns", type=int, default=4)
     ap.add_argument("--turn-batches", default="16,32")
+    ap.add_argument("--history", action="store_true", help="prompt intake and the history pool (DESIGN.md §7o) in the place of the queue's legs")
+    ap.add_argument("--baseline", action="store_true", help="with --history: leg (a) alone, with no argument this feature added")
+    ap.add_argument("--history-batch", type=int, default=16)
+    ap.add_argument("--history-prompt", type=int, default=48)
+    ap.add_argument("--history-window", type=int, default=256)
     args = ap.parse_args()
     import wrk
 
@@ -150,6 +221,10 @@ def main():
     ctx = wrk.Context(0)
     data = bench.make_model_gguf(args.model, seed=42)
     skw = dict(temperature=1.0, top_p=0.9)
+    if args.history:
+        print(json.dumps(history_bench(args, wrk, ctx, data, skw)))
+        ctx.close()
+        return
     if args.pool:
         print(json.dumps(pool_bench(args, wrk, ctx, data, skw)))
         ctx.close()

@@ -345,6 +345,11 @@ struct QueueBufs {
     const StopSeqRow* seq_rows = nullptr;
     uint32_t* seq_tail = nullptr;
     uint32_t* seq_match = nullptr;
+    // prompt intake: ctx_from [R]: the index of request r's first prompt token that enters the slot's context; intake [B]:
+    // 1 when the token this launch wrote into tokens[b] is such a prompt token (written for every slot by every launch, as started);
+    // both nullptr without intake
+    const uint32_t* ctx_from = nullptr;
+    uint32_t* intake = nullptr;
 };
 // takes advance_tokens' place in a queue program: history <- drawn; per slot the next prompt token or the draw, stop / max_new check,
 // next requests to the slots that ended (ascending slot order), their parameters into the slot's rows, started[b], the log,
@@ -360,12 +365,19 @@ void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t
 // turnover list.  QueueTurn: one slot that ended in the step -- `save` the entry its state goes to, `started` / `start` as started[slot]
 // and the entry the slot's next request begins from
 static constexpr uint32_t QUEUE_NO_ENTRY = 0xFFFFFFFFu;
-struct QueueStateCtl { float* states; uint32_t num_entries, turn_count; };
+// QueueHistory: a history pool beside the state pool, entry k of it belonging to entry k of the states: count f32
+// [entries][v] and flags u8 [entries][v] (the present bit only), and with cap > 0 ring u32 [entries][cap] and meta u32 [entries][2]
+// (length, next write position) -- what an occurrence slot and a token-window slot hold.  All nullptr / 0: none.  Device data as the
+// states' pointer is: one captured program serves any history pool
+struct QueueHistory { float* count; uint8_t* flags; uint32_t* ring; uint32_t* meta; uint32_t cap, pad; };
+struct QueueStateCtl { float* states; uint32_t num_entries, turn_count; QueueHistory hist; };
 struct QueueTurn { uint32_t slot, save, started, start; };
 struct QueueStateBufs {
     const uint32_t *start, *save;   // [R] next to the request table (QueueReq's layout does not move)
     QueueStateCtl* sctl;
     QueueTurn* turn;                // [B]: written by advance_queue_pool at position (ended slots before this one), no atomics
+    // a call with a history pool: queue_history_turnover takes the place of the occurrence reset and of advance_queue's window reset
+    bool history = false;
 };
 // advance_queue for pool programs: the same body, and the step's turnover list
 void advance_queue_pool(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q,
@@ -374,6 +386,13 @@ void advance_queue_pool(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, 
 // load the slot, store it to the save entry, then store the start entry / init_state / zero to the slot, in one thread -- and the
 // occurrence rows as queue_reset.  g.slot % 4 == 0 and 16-byte aligned bases only (the callers check)
 void queue_turnover(hipStream_t s, const QueueGeom& g, const QueueBufs& q, const QueueStateBufs& p, uint32_t b, int num_cu);
+// The turnover of the slots' contexts in a call with a history pool, and the copy kernel of wrk_history_pool_put / _get: one grid of
+// ceil(v / 1024) + ceil(WRK_MAX_TOKEN_WINDOW / 1024) workgroups, whatever b and whatever the windows' capacity, walks the turnover list.  Per element of a listed slot, in one thread: load
+// the slot (pen[slot]'s count / flags, dry[slot]'s ring / meta), store it to the save entry (the present bit only), then store the
+// slot's new value -- the start entry's, or count 0 / no present bit / an empty window -- keeping the slot's banned bits.  pen or dry
+// may be nullptr (no occurrence rows / no windows in the call); 16-byte elements when v % 4 == 0, scalar otherwise
+void queue_history_turnover(hipStream_t s, uint32_t v, const QueueStateCtl* sctl, const QueueTurn* turn, const PenaltyParam* pen,
+                            const DryParam* dry);
 
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled
@@ -460,6 +479,18 @@ struct wrk_token_window {
     void* mem = nullptr;
     uint32_t* ring = nullptr;
     uint32_t* meta = nullptr;
+};
+// include/wrk_hip.h wrk_history_pool: one allocation holding counts f32 [num_entries][num_vocab], flags u8 [num_entries][num_vocab]
+// (bit 0 present; bit 1 is never set) and, with capacity > 0, rings u32 [num_entries][capacity] and meta u32 [num_entries][2]
+struct wrk_history_pool {
+    wrk_ctx* ctx = nullptr;
+    uint32_t num_entries = 0, num_vocab = 0, capacity = 0;
+    void* mem = nullptr;
+    float* counts = nullptr;
+    uint8_t* flags = nullptr;
+    uint32_t* ring = nullptr;
+    uint32_t* meta = nullptr;
+    wrk::QueueHistory dev() const { return wrk::QueueHistory{counts, flags, ring, meta, capacity, 0u}; }
 };
 // the DRY fields of a call (wrk_generate_options / wrk_queue_options / wrk_dry_logits); the four parameter arrays may be NULL
 struct wrk_dry_args {

@@ -11,6 +11,10 @@
 //   advance_queue_pool, queue_turnover   their places in the programs of a call with a state pool: the same advance body
 //                   also lists the slots that ended; one (layer x slice) grid, whatever B, saves each listed slot's state to its
 //                   request's pool entry and then fills the slot from the next request's entry, init_state or zeros
+//   queue_history_turnover   in the programs of a pool call with a history pool, and behind wrk_history_pool_put / _get:
+//                   the occurrence reset's place; one grid over the vocabulary and the largest ring walks the same turnover list, saves
+//                   each listed slot's occurrence row and token window to its request's history entry and then sets them from the
+//                   next request's entry, or to the reset
 //
 // started[b] is written by EVERY advance_queue launch for every slot, so the flag a reset launch reads was written by the launch in front
 // of it in the same stream; nothing has to clear it.  Plain vector stores only; no atomics; no kernel waits on another.
@@ -23,6 +27,7 @@ namespace wrk {
 static constexpr uint32_t QUEUE_THREADS = 256;
 static constexpr uint32_t QUEUE_CHUNK = QUEUE_THREADS * 4;     // floats a workgroup moves per pass (16 bytes per thread)
 static constexpr uint32_t QUEUE_WAVES = QUEUE_THREADS / 64;
+static constexpr uint32_t QUEUE_WINDOW_TILES = (WRK_MAX_TOKEN_WINDOW + QUEUE_CHUNK - 1) / QUEUE_CHUNK;
 
 // slots are owned by the threads of ONE workgroup (B <= 256, as advance_stop).  POOL (advance_queue_pool_kernel): the slots that ended
 // also go into the step's turnover list, at the position the scan below gives them.  SEQ (the _seq kernels): a reply draw
@@ -37,6 +42,7 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
     const uint32_t next = Q.ctl->next_request, live = Q.ctl->live, num_requests = Q.ctl->num_requests;
     const uint32_t i = threadIdx.x, lane = i & 63u, wave = i >> 6;
     int ended = 0;
+    uint32_t take = 0;                          // the token this launch writes into tokens[i] is a prompt token that enters the context
     QueueSlot s{0u, 0u, 0u, QUEUE_IDLE};
     if (i < b) {
         s = Q.slots[i];
@@ -46,6 +52,7 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
             const QueueReq* r = Q.reqs + s.req;
             s.pos += 1;
             tokens[i] = Q.pool[r->prompt_off + s.pos];
+            if (Q.ctx_from) take = s.pos >= Q.ctx_from[s.req];
             if (s.pos + 1 == r->prompt_len) s.phase = QUEUE_REPLY;
         } else if (s.phase == QUEUE_REPLY) {
             const QueueReq* r = Q.reqs + s.req;
@@ -93,6 +100,7 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
                 const QueueReq* q = Q.reqs + r;
                 s = QueueSlot{r, 0u, 0u, q->prompt_len == 1 ? QUEUE_REPLY : QUEUE_PROMPT};
                 tokens[i] = Q.pool[q->prompt_off];
+                if (Q.ctx_from) take = Q.ctx_from[r] == 0u;
                 // reply token j is drawn at step (step + 1) + prompt_len - 1 + j: its sampler step is j whenever it is scheduled
                 if (Q.sample_par) Q.sample_par[i] = SampleParam{q->temperature, q->top_p, q->seed, step + q->prompt_len};
                 if (Q.filter_par) Q.filter_par[i] = SampleFilter{q->top_k, q->ln_min_p};
@@ -107,7 +115,8 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
                     const DryParam* dq = Q.dry_req + r;
                     dp->allowed = dq->allowed; dp->no_repeat = dq->no_repeat; dp->multiplier = dq->multiplier;
                     for (uint32_t m = 0; m <= WRK_DRY_MAX_MATCH; ++m) dp->pen[m] = dq->pen[m];
-                    dp->meta[0] = 0u; dp->meta[1] = 0u;
+                    // with a history pool queue_history_turnover, behind this launch, saves the window first and then sets it
+                    if (!(POOL && P.history)) { dp->meta[0] = 0u; dp->meta[1] = 0u; }
                 }
                 if (SEQ) stop_tail_clear(Q.seq_tail + (size_t)i * STOP_TAIL);      // and its tail starts empty
                 if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
@@ -121,6 +130,7 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
         }
         Q.slots[i] = s;
         Q.started[i] = started;
+        if (Q.intake) Q.intake[i] = take;
     }
     if (i == 0) {
         if (total) { Q.ctl->next_request = next + total; Q.ctl->live = live - total; }
@@ -234,6 +244,108 @@ __global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_occurrence_kernel(u
     }
 }
 
+// Call with a history pool: queue_reset_occurrence_kernel's place, and the window reset's.  Workgroups [0, row_tiles) own 1024 elements
+// of the occurrence rows each (thread tid the 4 at 4 * tid when VEC, else tid + 256 * j); the QUEUE_WINDOW_TILES workgroups behind them
+// 1024 ring elements each -- the largest ring, whatever the window's capacity, which is data -- and the first of them, in thread 0, the
+// window's (length, position) words.  Every thread walks the turnover list and, per element of
+// a listed slot, loads the slot, stores it to the save entry and only then stores the slot's new value: a slot that ends and restarts
+// in one step is saved before it is overwritten with no ordering between workgroups.  The entries read and written in one step are
+// disjoint (host validation), a slot is listed once, and a ring is copied whole, so no element depends on the meta words
+struct QueueHistArgs {
+    const QueueStateCtl* sctl;
+    const QueueTurn* turn;
+    const PenaltyParam* pen;    // the slots' occurrence rows, or nullptr
+    const DryParam* dry;        // the slots' windows, or nullptr
+    uint32_t v, row_tiles;
+};
+
+template <bool VEC>
+__global__ void __launch_bounds__(QUEUE_THREADS) queue_history_turnover_kernel(const QueueHistArgs A) {
+    const QueueStateCtl sc = *A.sctl;
+    if (sc.turn_count == 0) return;
+    const QueueHistory H = sc.hist;
+    const uint32_t tid = threadIdx.x;
+    if (blockIdx.x < A.row_tiles) {
+        if (!A.pen || !H.count) return;
+        const uint32_t a = blockIdx.x * QUEUE_CHUNK, v = A.v;
+        for (uint32_t t = 0; t < sc.turn_count; ++t) {
+            const QueueTurn e = A.turn[t];
+            const bool save = e.save != QUEUE_NO_ENTRY, load = e.started && e.start != QUEUE_NO_ENTRY;
+            if (!save && !e.started) continue;
+            const PenaltyParam p = A.pen[e.slot];
+            float* sc_c = save ? H.count + (size_t)e.save * v : nullptr;
+            uint8_t* sc_f = save ? H.flags + (size_t)e.save * v : nullptr;
+            const float* ld_c = load ? H.count + (size_t)e.start * v : nullptr;
+            const uint8_t* ld_f = load ? H.flags + (size_t)e.start * v : nullptr;
+            if (VEC) {
+                const uint32_t i = a + tid * 4;
+                if (i >= v) continue;
+                const f32x4 c = *(const f32x4*)(p.count + i);
+                const uint32_t f = *(const uint32_t*)(p.flags + i);
+                if (save) { *(f32x4*)(sc_c + i) = c; *(uint32_t*)(sc_f + i) = f & 0x01010101u; }
+                if (e.started) {
+                    *(f32x4*)(p.count + i) = load ? *(const f32x4*)(ld_c + i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                    *(uint32_t*)(p.flags + i) = (f & 0x02020202u) | (load ? *(const uint32_t*)(ld_f + i) & 0x01010101u : 0u);
+                }
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint32_t i = a + j * QUEUE_THREADS + tid;
+                    if (i >= v) continue;
+                    const float c = p.count[i];
+                    const uint8_t f = p.flags[i];
+                    if (save) { sc_c[i] = c; sc_f[i] = f & 1u; }
+                    if (e.started) {
+                        p.count[i] = load ? ld_c[i] : 0.0f;
+                        p.flags[i] = (uint8_t)((f & 2u) | (load ? ld_f[i] & 1u : 0u));
+                    }
+                }
+            }
+        }
+        return;
+    }
+    if (!A.dry || !H.ring) return;
+    const uint32_t w = blockIdx.x - A.row_tiles;
+    for (uint32_t t = 0; t < sc.turn_count; ++t) {
+        const QueueTurn e = A.turn[t];
+        const bool save = e.save != QUEUE_NO_ENTRY, load = e.started && e.start != QUEUE_NO_ENTRY;
+        if (!save && !e.started) continue;
+        const DryParam* p = A.dry + e.slot;
+        uint32_t* ring = p->ring;
+        const uint32_t cap = p->cap < H.cap ? p->cap : H.cap;      // equal (host validation); the window's capacity is data
+        uint32_t* sv = save ? H.ring + (size_t)e.save * cap : nullptr;
+        const uint32_t* ld = load ? H.ring + (size_t)e.start * cap : nullptr;
+        if (save || load) {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t i = w * QUEUE_CHUNK + j * QUEUE_THREADS + tid;
+                if (i >= cap) continue;
+                const uint32_t x = ring[i];
+                if (save) sv[i] = x;
+                if (load) ring[i] = ld[i];
+            }
+        }
+        if (w == 0 && tid == 0) {
+            uint32_t* m = p->meta;
+            const uint32_t len = m[0], pos = m[1];
+            if (save) { H.meta[(size_t)e.save * 2] = len; H.meta[(size_t)e.save * 2 + 1] = pos; }
+            if (e.started) {
+                m[0] = load ? H.meta[(size_t)e.start * 2] : 0u;
+                m[1] = load ? H.meta[(size_t)e.start * 2 + 1] : 0u;
+            }
+        }
+    }
+}
+
+void queue_history_turnover(hipStream_t s, uint32_t v, const QueueStateCtl* sctl, const QueueTurn* turn, const PenaltyParam* pen,
+                            const DryParam* dry) {
+    QueueHistArgs A{sctl, turn, pen, dry, v, pen ? (v + QUEUE_CHUNK - 1) / QUEUE_CHUNK : 0u};
+    const uint32_t grid = A.row_tiles + (dry ? QUEUE_WINDOW_TILES : 0u);
+    if (grid == 0) return;
+    if (v % 4 == 0) queue_history_turnover_kernel<true><<<grid, QUEUE_THREADS, 0, s>>>(A);
+    else queue_history_turnover_kernel<false><<<grid, QUEUE_THREADS, 0, s>>>(A);
+}
+
 void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q, uint32_t b) {
     // a queue with stop sequences has all three of their buffers (queue_bufs)
     if (q.seq_rows) advance_queue_seq_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, b);
@@ -279,7 +391,175 @@ void queue_turnover(hipStream_t s, const QueueGeom& g, const QueueBufs& q, const
     A.layers = g.layers; A.num_batch = g.num_batch; A.b0 = g.b0; A.slot = g.slot;
     A.slices = queue_slices(g, QUEUE_CHUNK, num_cu);
     queue_turnover_kernel<<<A.layers * A.slices, QUEUE_THREADS, 0, s>>>(A);
-    queue_reset_occurrence(s, g, q, b);
+    if (p.history) queue_history_turnover(s, g.v, p.sctl, p.turn, q.pen_par, q.dry_par);
+    else queue_reset_occurrence(s, g, q, b);
 }
 
 }  // namespace wrk
+
+// ------------------------------------------------------------------ include/wrk_hip.h wrk_history_pool
+static int32_t history_entry_check(wrk_ctx* ctx, const wrk_history_pool* hp, uint32_t k, const char* who) {
+    WRK_ARG(ctx, !ctx->capturing_here(), "%s is blocking: not inside a capture", who);
+    WRK_ARG(ctx, hp->ctx == ctx, "the history pool belongs to another context");
+    WRK_ARG(ctx, k < hp->num_entries, "entry %u >= %u", k, hp->num_entries);
+    return WRK_OK;
+}
+
+// wrk_history_pool_put / _get: slot `b` of `occ` and of `win` against entry k through queue_history_turnover on a list of one turn,
+// the kernel of the queue's turnover.  The rules for the handles are those of a queue call with the pool
+static int32_t history_move(wrk_ctx* ctx, wrk_history_pool* hp, uint32_t k, wrk_occurrence* occ, uint32_t b, wrk_token_window* win, bool put,
+                            const char* who) {
+    const int32_t rc = history_entry_check(ctx, hp, k, who);
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, occ || win, "an occurrence table or a token window is required");
+    if (occ) {
+        WRK_ARG(ctx, occ->ctx == ctx, "the occurrence table belongs to another context");
+        WRK_ARG(ctx, occ->num_vocab == hp->num_vocab, "occurrence table of %u tokens, history pool of %u", occ->num_vocab, hp->num_vocab);
+        WRK_ARG(ctx, b < occ->num_batch, "slot %u >= %u", b, occ->num_batch);
+    }
+    WRK_ARG(ctx, win || hp->capacity == 0, "the history pool has windows: a token window is required");
+    if (win) {
+        WRK_ARG(ctx, win->ctx == ctx, "the token window belongs to another context");
+        WRK_ARG(ctx, hp->capacity != 0, "the history pool was created without windows");
+        WRK_ARG(ctx, win->capacity == hp->capacity, "token window of capacity %u, history pool of %u", win->capacity, hp->capacity);
+        WRK_ARG(ctx, win->num_vocab == hp->num_vocab, "token window of %u tokens, history pool of %u", win->num_vocab, hp->num_vocab);
+        WRK_ARG(ctx, b < win->num_batch, "slot %u >= %u", b, win->num_batch);
+    }
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    const wrk::QueueStateCtl sctl{nullptr, hp->num_entries, 1u, hp->dev()};
+    const wrk::QueueTurn turn = put ? wrk::QueueTurn{0u, k, 0u, wrk::QUEUE_NO_ENTRY} : wrk::QueueTurn{0u, wrk::QUEUE_NO_ENTRY, 1u, k};
+    wrk::PenaltyParam pen{};
+    if (occ) pen = occ->row(b, 0.0f, 0.0f, 1.0f);
+    wrk::DryParam dry{};
+    if (win) { dry.ring = win->ring + (size_t)b * win->capacity; dry.meta = win->meta + (size_t)b * 2; dry.cap = win->capacity; }
+    wrk_dev_arena dev;
+    const size_t o_ctl = dev.add(sizeof sctl), o_turn = dev.add(sizeof turn), o_pen = dev.add(sizeof pen), o_dry = dev.add(sizeof dry);
+    WRK_HIP(ctx, dev.alloc());
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_ctl), &sctl, sizeof sctl, hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_turn), &turn, sizeof turn, hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_pen), &pen, sizeof pen, hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_dry), &dry, sizeof dry, hipMemcpyHostToDevice, ctx->stream));
+    wrk::queue_history_turnover(ctx->stream, hp->num_vocab, dev.at<wrk::QueueStateCtl>(o_ctl), dev.at<wrk::QueueTurn>(o_turn),
+                                occ ? dev.at<wrk::PenaltyParam>(o_pen) : nullptr, win ? dev.at<wrk::DryParam>(o_dry) : nullptr);
+    WRK_LAUNCH_CHECK(ctx);
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+extern "C" {
+
+int32_t wrk_history_pool_create(wrk_ctx* ctx, uint32_t P, uint32_t V, uint32_t capacity, wrk_history_pool** out) {
+    if (!ctx || !out) return WRK_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    *out = nullptr;
+    WRK_ARG(ctx, P >= 1, "num_entries 0");
+    WRK_ARG(ctx, V >= 1, "num_vocab 0");
+    if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "num_vocab %u > %u", V, wrk::SAMPLE_MAX_VOCAB);
+    WRK_ARG(ctx, capacity <= WRK_MAX_TOKEN_WINDOW, "window_capacity %u: at most %u (0: no windows)", capacity, (uint32_t)WRK_MAX_TOKEN_WINDOW);
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)P * V;
+    wrk_dev_layout lay;
+    const size_t o_c = lay.add(n * 4), o_f = lay.add(n), o_r = lay.add((size_t)P * capacity * 4), o_m = lay.add(capacity ? (size_t)P * 8 : 0);
+    void* mem = nullptr;
+    WRK_HIP(ctx, hipMalloc(&mem, lay.total));
+    wrk_history_pool* hp = new wrk_history_pool;
+    hp->ctx = ctx;
+    hp->num_entries = P; hp->num_vocab = V; hp->capacity = capacity;
+    hp->mem = mem;
+    hp->counts = (float*)((char*)mem + o_c);
+    hp->flags = (uint8_t*)((char*)mem + o_f);
+    if (capacity) { hp->ring = (uint32_t*)((char*)mem + o_r); hp->meta = (uint32_t*)((char*)mem + o_m); }
+    hipError_t e = hipMemsetAsync(mem, 0, lay.total, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        wrk_history_pool_destroy(hp);
+        return wrk_fail(ctx, WRK_E_HIP, "history pool: %s", hipGetErrorString(e));
+    }
+    *out = hp;
+    return WRK_OK;
+}
+
+int32_t wrk_history_pool_destroy(wrk_history_pool* hp) {
+    if (!hp) return WRK_E_ARG;
+    {
+        std::lock_guard<std::recursive_mutex> lk(hp->ctx->mu);
+        hipSetDevice(hp->ctx->device);
+        hipStreamSynchronize(hp->ctx->stream);      // no step in flight still reads the pool
+        hipFree(hp->mem);
+    }
+    delete hp;
+    return WRK_OK;
+}
+
+int32_t wrk_history_pool_load(wrk_ctx* ctx, wrk_history_pool* hp, uint32_t k, const float* counts, const uint32_t* present,
+                              const uint32_t* tokens, uint32_t n) {
+    if (!ctx || !hp) return WRK_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    int32_t rc = history_entry_check(ctx, hp, k, "wrk_history_pool_load");
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, (counts == nullptr) == (present == nullptr), "counts and present: both, or neither (an empty row)");
+    const uint32_t V = hp->num_vocab, cap = hp->capacity;
+    std::vector<float> c(V, 0.0f);
+    std::vector<uint8_t> f(V, 0);
+    for (uint32_t i = 0; counts && i < V; ++i) {
+        WRK_ARG(ctx, finite_f32(counts[i]), "counts[%u] = %g: must be finite", i, (double)counts[i]);
+        WRK_ARG(ctx, present[i] <= 1u, "present[%u] = %u: 0 or 1 (banned bits are not part of an entry)", i, present[i]);
+        c[i] = counts[i];
+        f[i] = (uint8_t)present[i];
+    }
+    if (!tokens) n = 0;
+    WRK_ARG(ctx, n <= cap, "%u tokens, an entry's window holds %u", n, cap);
+    for (uint32_t i = 0; i < n; ++i) WRK_ARG(ctx, tokens[i] < V, "token %u: id %u >= vocab %u", i, tokens[i], V);
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    rc = wrk_buf_write_raw(ctx, hp->counts + (size_t)k * V, c.data(), (size_t)V * 4);
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, hp->flags + (size_t)k * V, f.data(), V);
+    if (rc == WRK_OK && n) rc = wrk_buf_write_raw(ctx, hp->ring + (size_t)k * cap, tokens, (size_t)n * 4);
+    const uint32_t meta[2] = {n, cap ? n % cap : 0u};
+    if (rc == WRK_OK && cap) rc = wrk_buf_write_raw(ctx, hp->meta + (size_t)k * 2, meta, 8);
+    if (rc != WRK_OK) return rc;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+int32_t wrk_history_pool_back(wrk_ctx* ctx, const wrk_history_pool* hp, uint32_t k, float* counts, uint32_t* present, uint32_t* tokens_out,
+                              uint32_t* len) {
+    if (!ctx || !hp) return WRK_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const int32_t rc = history_entry_check(ctx, hp, k, "wrk_history_pool_back");
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, counts && present && len, "counts, present and len are required");
+    const uint32_t V = hp->num_vocab, cap = hp->capacity;
+    WRK_ARG(ctx, tokens_out || cap == 0, "tokens_out is required: the pool has windows");
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint8_t> f(V);
+    std::vector<uint32_t> ring(cap);
+    uint32_t meta[2] = {0u, 0u};
+    WRK_HIP(ctx, hipMemcpyAsync(counts, hp->counts + (size_t)k * V, (size_t)V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(f.data(), hp->flags + (size_t)k * V, V, hipMemcpyDeviceToHost, ctx->stream));
+    if (cap) {
+        WRK_HIP(ctx, hipMemcpyAsync(ring.data(), hp->ring + (size_t)k * cap, (size_t)cap * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(meta, hp->meta + (size_t)k * 2, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < V; ++i) present[i] = f[i];
+    if (cap && (meta[0] > cap || meta[1] >= cap))
+        return wrk_fail(ctx, WRK_E_HIP, "entry %u: inconsistent window (length %u position %u capacity %u)", k, meta[0], meta[1], cap);
+    const uint32_t start = cap ? (meta[1] + cap - meta[0]) % cap : 0u;
+    for (uint32_t j = 0; j < meta[0]; ++j) tokens_out[j] = ring[(start + j) % cap];
+    *len = meta[0];
+    return WRK_OK;
+}
+
+int32_t wrk_history_pool_put(wrk_ctx* ctx, wrk_history_pool* hp, uint32_t k, wrk_occurrence* occ, uint32_t b, wrk_token_window* win) {
+    if (!ctx || !hp) return WRK_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    return history_move(ctx, hp, k, occ, b, win, true, "wrk_history_pool_put");
+}
+
+int32_t wrk_history_pool_get(wrk_ctx* ctx, wrk_history_pool* hp, uint32_t k, wrk_occurrence* occ, uint32_t b, wrk_token_window* win) {
+    if (!ctx || !hp) return WRK_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    return history_move(ctx, hp, k, occ, b, win, false, "wrk_history_pool_get");
+}
+
+}  // extern "C"

@@ -101,6 +101,11 @@ struct wrk_step_kind {
     // penalised, else on dry.out = a copy of head_o -- and the tail pushes the draw into the token window where it updates the occurrence
     // rows, under the same gate
     bool dry = false;
+    // a queue tail whose prompt tokens enter the slots' contexts: behind the reset / turnover, occurrence_update (penalised)
+    // and window_push (dry) once more, on io.tokens under the gate of the intake flags advance_queue wrote
+    bool intake = false;
+    // a QUEUE_POOL tail with a history pool: queue_history_turnover in the place of the occurrence reset
+    bool history = false;
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
     bool mirostat() const { return pick == MIROSTAT; }
@@ -114,9 +119,10 @@ struct wrk_step_kind {
         return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29 |
                (uint32_t)constrained << 31;
     }
-    // The kind's bits of GraphKey::mode2, the word that takes what key() has no room for: stop sequences 0, DRY 1.  0 for every kind that
-    // existed before the word did, and bit 0 alone for every stop-sequence kind, so their keys compare as they always have
-    uint32_t key2() const { return (uint32_t)stop_seqs | (uint32_t)dry << 1; }
+    // The kind's bits of GraphKey::mode2, the word that takes what key() has no room for: stop sequences 0, DRY 1, prompt intake 2,
+    // history 3.  0 for every kind that existed before the word did, and bit 0 alone for every stop-sequence kind, so their keys compare
+    // as they always have
+    uint32_t key2() const { return (uint32_t)stop_seqs | (uint32_t)dry << 1 | (uint32_t)intake << 2 | (uint32_t)history << 3; }
 };
 
 // ------------------------------------------------------------------ the buffer groups of a frame (Pieces of wrk_dev_group)
@@ -266,6 +272,13 @@ struct wrk_queue_state_bufs {
         save = start ? start + d[1] : nullptr;
     }
 };
+// prompt intake of a queue call: the intake flags [slots] and the requests' context offsets [requests]
+struct wrk_queue_intake_bufs {
+    static constexpr int DIMS = 2;              // slots, requests
+    static constexpr unsigned EXACT = 0;
+    uint32_t *flags = nullptr, *from = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(flags, d[0] * 4); c.take(from, d[1] * 4); }
+};
 // log-probs in the decode loops (wrk_logprob.hip).  par: the parameter block (the output buffers and num_top: one program
 // serves any num_top); the per-step rows logprob [rows], top_ids / top_logprobs [rows][WRK_MAX_TOP_LOGPROBS], indexed
 // [steps][B](, [num_top]) by a call; the slice partials and candidate keys of `batch` rows
@@ -326,10 +339,11 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_queue_bufs> queue;
     wrk_dev_group<wrk_queue_seq_bufs> queue_seq;
     wrk_dev_group<wrk_queue_state_bufs> queue_states;
+    wrk_dev_group<wrk_queue_intake_bufs> queue_intake;
     wrk_dev_group<wrk_logprob_bufs> logprob;
     template <class F> void each_group(F&& f) {     // the one list of the groups
         f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
-        f(queue_states); f(logprob);
+        f(queue_states); f(queue_intake); f(logprob);
     }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
     uint32_t live_host_cap = 0;

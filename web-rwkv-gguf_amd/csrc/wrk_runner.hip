@@ -461,6 +461,8 @@ struct wrk_queue_pack {
     wrk_token_window* window = nullptr;
     wrk_stopseq_pack seq;      // stop sequences: [R] the requests' rows (the tails: every slot starts empty)
     uint32_t* match_out = nullptr;  // the options' out_stop_match, or nullptr
+    std::vector<uint32_t> from;     // prompt intake: [R] the options' prompt_context_from
+    const wrk_history_pool* history = nullptr;  // with a state pool: its history pool, or nullptr
 };
 
 static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
@@ -489,6 +491,9 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     if (rc != WRK_OK) return rc;
     pk.kind.stop_seqs = pk.seq.on;
     pk.match_out = opt->out_stop_match;
+    WRK_ARG(ctx, !opt->prompt_context_from || pk.kind.penalized || pk.kind.dry, "prompt_context_from needs an occurrence table or a token window");
+    pk.kind.intake = opt->prompt_context_from != nullptr;
+    if (pk.kind.intake) pk.from.assign(opt->prompt_context_from, opt->prompt_context_from + R);
     const wrk_step_kind kind = pk.kind;
     pk.R = R; pk.max_steps = opt->max_steps; pk.poll_steps = opt->poll_steps;
     pk.reqs.assign(R, wrk::QueueReq{});
@@ -562,7 +567,8 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
 }
 
 // after wrk_queue_check: the pool of wrk_v*_generate_queue_pool validated into pk (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch)
-static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, const wrk_queue_options* opt, const wrk_v7_state* st, wrk_queue_pack& pk) {
+static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t V,
+                                    wrk_queue_pack& pk) {
     WRK_ARG(ctx, pool, "pool required");
     WRK_ARG(ctx, pool->states, "%s", pool->start || pool->save ? "start / save entries without a pool buffer" : "the pool has no buffer");
     const uint32_t R = pk.R, P = pool->num_entries;
@@ -592,6 +598,18 @@ static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, co
         WRK_ARG(ctx, k == wrk::QUEUE_NO_ENTRY || saver[k] == wrk::QUEUE_NO_ENTRY || saver[k] == r,
                 "request %u starts from entry %u, which request %u saves to", r, k, k == wrk::QUEUE_NO_ENTRY ? 0u : saver[k]);
     }
+    if (const wrk_history_pool* hp = opt->history) {
+        WRK_ARG(ctx, pk.kind.penalized || pk.kind.dry, "a history pool needs an occurrence table or a token window");
+        WRK_ARG(ctx, hp->ctx == ctx, "the history pool belongs to another context");
+        WRK_ARG(ctx, hp->num_vocab == V, "history pool of %u tokens, logits of %u", hp->num_vocab, V);
+        WRK_ARG(ctx, hp->num_entries == P, "history pool of %u entries, state pool of %u", hp->num_entries, P);
+        WRK_ARG(ctx, !pk.kind.dry || hp->capacity != 0, "a token window with a history pool created without windows");
+        WRK_ARG(ctx, pk.kind.dry || hp->capacity == 0, "a history pool with windows and no token window");
+        WRK_ARG(ctx, !pk.kind.dry || hp->capacity == opt->window->capacity, "history pool windows of capacity %u, token window of %u",
+                hp->capacity, opt->window->capacity);
+        pk.history = hp;
+        pk.kind.history = true;
+    }
     if (slot % 4 != 0) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "a state pool needs (S + 2) * D = %zu to be a multiple of 4", slot);
     if ((((uintptr_t)pool->states->ptr) | ((uintptr_t)st->data) | ((uintptr_t)pk.init_state)) & 15u)
         return wrk_fail(ctx, WRK_E_UNSUPPORTED, "a state pool needs 16-byte aligned state, pool and init_state buffers");
@@ -609,15 +627,29 @@ static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) 
                           kind.constrained ? f.grammar.state : nullptr, kind.constrained ? f.grammar.req : nullptr,
                           kind.dry ? f.dry.par : nullptr, kind.dry ? f.dry.req : nullptr,
                           kind.stop_seqs ? f.queue_seq.rows : nullptr, kind.stop_seqs ? f.queue_seq.tail : nullptr,
-                          kind.stop_seqs ? f.queue_seq.match : nullptr};
+                          kind.stop_seqs ? f.queue_seq.match : nullptr,
+                          kind.intake ? f.queue_intake.from : nullptr, kind.intake ? f.queue_intake.flags : nullptr};
 }
 
-static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f) {
-    return wrk::QueueStateBufs{f.queue_states.start, f.queue_states.save, f.queue_states.ctl, f.queue_states.turn};
+static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
+    return wrk::QueueStateBufs{f.queue_states.start, f.queue_states.save, f.queue_states.ctl, f.queue_states.turn, kind.history};
 }
 
 static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V) {
     return wrk::QueueGeom{st->data, st->num_layer, st->num_batch, b0, V, (size_t)(st->head_size + 2) * st->num_emb};
+}
+
+// prompt intake (intake kinds): the prompt tokens that advance_queue -- or, for step 0, the host -- marked in the intake flags enter
+// the slots' occurrence rows (penalised) and windows (dry) from io.tokens, with the launches that take a counted draw in
+static int32_t enqueue_prompt_intake(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, hipStream_t q) {
+    if (!kind.intake) return WRK_OK;
+    if (!f.queue_intake.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "intake buffers are not prepared");
+    if (kind.dry && !f.dry.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "DRY rows are not prepared");
+    const wrk::RowGate gate{f.queue_intake.flags, 1u, 1u};
+    const uint32_t V = f.facts().num_vocab;
+    if (kind.penalized) wrk::occurrence_update(q, V, B, f.penalty.par, f.io().tokens, 1, gate);
+    if (kind.dry) wrk::window_push(q, V, B, f.dry.par, f.io().tokens, gate);
+    return WRK_OK;
 }
 
 // after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): queue buffers of the
@@ -630,7 +662,9 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     int32_t rc = f.grow(f.queue, {B, pk.R, pk.pool.size()});
     if (rc == WRK_OK && pk.kind.pool()) rc = f.grow(f.queue_states, {B, pk.R});
     if (rc == WRK_OK && pk.kind.stop_seqs) rc = f.grow(f.queue_seq, {B, pk.R});
+    if (rc == WRK_OK && pk.kind.intake) rc = f.grow(f.queue_intake, {B, pk.R});
     if (rc != WRK_OK) return rc;
+    const wrk_step_kind kind = pk.kind;
     const uint32_t nstart = B < pk.R ? B : pk.R;
     std::vector<wrk::QueueSlot> slots(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
     std::vector<uint32_t> started(B, 0u);
@@ -662,14 +696,22 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
         // the turnover list of "step -1": the slots that start at step 0, nothing to save
         std::vector<wrk::QueueTurn> turn(nstart);
         for (uint32_t b = 0; b < nstart; ++b) turn[b] = wrk::QueueTurn{b, wrk::QUEUE_NO_ENTRY, 1u, pk.start[b]};
-        const wrk::QueueStateCtl sctl{pk.pool_states, pk.pool_entries, nstart};
+        const wrk::QueueStateCtl sctl{pk.pool_states, pk.pool_entries, nstart, pk.history ? pk.history->dev() : wrk::QueueHistory{}};
         up(f.queue_states.start, pk.start.data(), pk.R)(f.queue_states.save, pk.save.data(), pk.R);
         up(f.queue_states.turn, turn.data(), nstart)(f.queue_states.ctl, &sctl, 1);
     }
+    if (pk.kind.intake) {       // p_0 of the slots that start at step 0 enters where the request's offset is 0
+        std::vector<uint32_t> take(B, 0u);
+        for (uint32_t b = 0; b < nstart; ++b) take[b] = pk.from[b] == 0u;
+        up(f.queue_intake.flags, take.data(), B)(f.queue_intake.from, pk.from.data(), pk.R);
+    }
     if (up.rc != WRK_OK) return up.rc;
     // the slots that start a request at step 0 are reset as the step that ends a request resets its slot
-    if (pk.kind.pool()) wrk::queue_turnover(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), queue_state_bufs(f), B, ctx->num_cu);
+    if (pk.kind.pool()) wrk::queue_turnover(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), queue_state_bufs(f, kind), B, ctx->num_cu);
     else wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), B, ctx->num_cu);
+    // and takes its intake as a step's tail does: the first tokens are in io.tokens (wrk_decode_prepare)
+    const int32_t irc = enqueue_prompt_intake(f, B, pk.kind, ctx->stream);
+    if (irc != WRK_OK) return irc;
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;
@@ -743,13 +785,13 @@ static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind
     if (rc != WRK_OK) return rc;
     const wrk::QueueBufs bufs = queue_bufs(f, kind);
     if (kind.pool()) {
-        wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history.tokens, io.counter, bufs, queue_state_bufs(f), B);
-        wrk::queue_turnover(q, queue_geom(st, b0, V), bufs, queue_state_bufs(f), B, f.ctx->num_cu);
+        wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history.tokens, io.counter, bufs, queue_state_bufs(f, kind), B);
+        wrk::queue_turnover(q, queue_geom(st, b0, V), bufs, queue_state_bufs(f, kind), B, f.ctx->num_cu);
     } else {
         wrk::advance_queue(q, io.argmax, io.tokens, f.history.tokens, io.counter, bufs, B);
         wrk::queue_reset(q, queue_geom(st, b0, V), bufs, B, f.ctx->num_cu);
     }
-    return WRK_OK;
+    return enqueue_prompt_intake(f, B, kind, q);
 }
 
 // after the loop: the log and the history rows (with log-probs: their rows too) come back and the replies are cut out of them
@@ -1131,7 +1173,8 @@ int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, 
     wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
     wrk_queue_pack pk;
     int32_t rc = wrk_queue_check(ctx, opt, st, B, m->facts().num_vocab, mode_arg, out_arg ? &out : nullptr, pk);
-    if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, pk);
+    if (rc == WRK_OK && tail != wrk_step_kind::QUEUE_POOL && opt->history) rc = wrk_fail(ctx, WRK_E_ARG, "a history pool without a state pool");
+    if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, m->facts().num_vocab, pk);
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), pk.first_tokens.data(), B);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;

@@ -92,7 +92,8 @@ class QueueOptions(C.Structure):
     _fields_ = [("num_requests", C.c_uint32), ("prompt_tokens", _u32p), ("prompt_offsets", _u32p), ("max_new", _u32p),
                 ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p),
                 ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("init_state", _P),
-                ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32),
+                ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32), ("prompt_context_from", _u32p),
+                ("history", _P),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
                 ("window", _P), ("dry_multiplier", _f32p), ("dry_base", _f32p), ("dry_allowed_length", _u32p), ("no_repeat_ngram", _u32p),
                 ("dry_breakers", _u32p), ("num_dry_breakers", C.c_uint32),
@@ -241,6 +242,12 @@ HIP_SYMBOLS = {
                                          _f32p, C.c_uint32]),
     "wrk_v7_generate_queue": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32]),
     "wrk_v6_generate_queue": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32]),
+    "wrk_history_pool_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "wrk_history_pool_destroy": (C.c_int32, [_P]),
+    "wrk_history_pool_load": (C.c_int32, [_P, _P, C.c_uint32, _f32p, _u32p, _u32p, C.c_uint32]),
+    "wrk_history_pool_back": (C.c_int32, [_P, _P, C.c_uint32, _f32p, _u32p, _u32p, _u32p]),
+    "wrk_history_pool_put": (C.c_int32, [_P, _P, C.c_uint32, _P, C.c_uint32, _P]),
+    "wrk_history_pool_get": (C.c_int32, [_P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     "wrk_v7_generate_queue_pool": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
                                                C.POINTER(QueuePool)]),
     "wrk_v6_generate_queue_pool": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
@@ -1662,7 +1669,8 @@ class Runtime:
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
                        mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None,
-                       mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
+                       mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
+                       count_prompt=None, history: "HistoryPool" = None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1693,7 +1701,14 @@ class Runtime:
         window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`, dry and no_repeat_ngram per request (scalars broadcast), the
         breakers for the call.  Slot b of the window serves whatever request runs on state slot b: it is emptied when a request is
         dispatched to it and takes only that request's reply draws, never prompt tokens.  The window's rows are unspecified afterwards
-        and are not part of a pool entry."""
+        and are not part of a pool entry.
+        count_prompt (None: off; True: 0 for every request; or one offset f per request): the prompt tokens p_f .. p_{n-1} of request r
+        enter its slot's occurrence row (as `Occurrence.add` with decay[r]) and window (as `TokenWindow.add`), on the device, after
+        the reset or restore its dispatch makes and before y_0 is picked.  f >= n: none.  A turn that continues a pool entry passes 1:
+        its prompt opens with the last reply token, which the entry's history has already counted.  Needs `occurrence` or `window`.
+        history: a `HistoryPool` beside `pool`, entry k of it belonging to entry k of the states: a request that starts from entry k
+        begins with the entry's occurrence row (the slot's bans kept) and window instead of empty ones, and one that saves to entry k
+        (reasons 1 and 2) leaves its slot's row and window there in the step that ends it, its last reply token counted."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1717,6 +1732,12 @@ class Runtime:
         self.last_stop_match = self.last_stop_tail = None
         if init_state is not None:
             opt.init_state = init_state.h
+        if count_prompt is not None:
+            frm = _per_row(0 if count_prompt is True else count_prompt, R, np.uint32)
+            keep.append(frm)
+            opt.prompt_context_from = _ptr(frm, _u32p)
+        if history is not None:
+            opt.history = history.h
         opt.poll_steps = poll_steps
         opt.max_steps = int(poff[-1]) + int(mn.sum()) if max_steps is None else max_steps
         lengths, reasons, slots, starts = (np.zeros(max(R, 1), np.uint32) for _ in range(4))
@@ -1820,3 +1841,54 @@ class StatePool:
 
     def close(self):
         self.buf = None
+
+
+class HistoryPool:
+    """The history pool of `Runtime.generate_queue(pool=..., history=...)`: `entries` entries on the device, entry k beside entry k of
+    the `StatePool`.  An entry holds what a slot of an `Occurrence` and of a `TokenWindow` hold -- counts, the present bit per token
+    and, with window_capacity > 0, the last window_capacity tokens that counted -- but no banned bits: those stay the slot's.
+    Entries start empty."""
+
+    def __init__(self, ctx: Context, entries: int, num_vocab: int, window_capacity: int = 0):
+        self.ctx, self.entries, self.num_vocab, self.capacity = ctx, entries, num_vocab, window_capacity
+        h = _P()
+        ctx.check(hip.wrk_history_pool_create(ctx.h, entries, num_vocab, window_capacity, C.byref(h)))
+        self.h = h
+
+    def load(self, k: int, counts=None, present=None, tokens=None):
+        """entry k <- counts / present (both or neither: an empty row) and tokens, oldest first (None: an empty window)"""
+        c = None if counts is None else np.ascontiguousarray(counts, np.float32)
+        f = None if present is None else _u32(present)
+        if (c is not None and c.size != self.num_vocab) or (f is not None and f.size != self.num_vocab):
+            raise ValueError(f"counts / present of an entry hold {self.num_vocab} values")
+        t = None if tokens is None else _u32(tokens).reshape(-1)
+        self.ctx.check(hip.wrk_history_pool_load(self.ctx.h, self.h, k, None if c is None else _ptr(c, _f32p), None if f is None else _ptr(f, _u32p),
+                                                 None if t is None or t.size == 0 else _ptr(t, _u32p), 0 if t is None else t.size))
+
+    def back(self, k: int):
+        """(counts f32 [V], present u32 [V], the window's tokens oldest first) of entry k"""
+        c, f = np.empty(self.num_vocab, np.float32), np.empty(self.num_vocab, np.uint32)
+        t, n = np.zeros(max(self.capacity, 1), np.uint32), C.c_uint32()
+        self.ctx.check(hip.wrk_history_pool_back(self.ctx.h, self.h, k, _ptr(c, _f32p), _ptr(f, _u32p), _ptr(t, _u32p), C.byref(n)))
+        return c, f, t[:n.value].copy()
+
+    def put(self, k: int, occurrence: "Occurrence" = None, batch: int = 0, window: "TokenWindow" = None):
+        """entry k <- slot `batch` of the occurrence table (the present bit only) and of the window, device to device"""
+        self.ctx.check(hip.wrk_history_pool_put(self.ctx.h, self.h, k, occurrence.h if occurrence is not None else None, batch,
+                                                window.h if window is not None else None))
+
+    def get(self, k: int, occurrence: "Occurrence" = None, batch: int = 0, window: "TokenWindow" = None):
+        """slot `batch` of the occurrence table and of the window <- entry k, device to device; the slot keeps its banned bits"""
+        self.ctx.check(hip.wrk_history_pool_get(self.ctx.h, self.h, k, occurrence.h if occurrence is not None else None, batch,
+                                                window.h if window is not None else None))
+
+    def close(self):
+        if self.h and self.ctx.h:
+            hip.wrk_history_pool_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
