@@ -359,7 +359,65 @@ def test_existing_loops_are_unchanged_by_a_queue_call(ctx, v6):
         assert np.array_equal(a, b)
 
 
-# ----------------------------------------------------------------------------------------------------------------- 7. validation
+# ----------------------------------------------------------------------------------------------------------------- 7. one dispatch rule
+@pytest.mark.parametrize("v6", [False, True])
+@pytest.mark.parametrize("family", ["mirostat", "filtered"])
+def test_host_and_device_dispatch_agree(ctx, v6, family):
+    """The same five requests in order and in reversed order on two slots: the requests that the host dispatched at step 0 of one call
+    are dispatched by a refill on the device in the other, and the other way round.  With every feature on that a dispatch writes --
+    penalties, a token window with DRY, a grammar whose state a reply moves, stop ids and stop sequences, prompt intake -- a request's
+    reply, reason, final mu, final automaton state and match word are equal bit for bit: "a reply does not depend on the slot or the
+    step".  Whether each reply is the right one is the business of the replays in the dry / grammar / mirostat / stopseq / history files."""
+    V, B, n = vocab("small", v6), 2, 5
+    lens, max_new = [3, 1, 2, 1, 3], [6, 4, 5, 6, 3]
+    P = prompts(V, lens)
+    per = pick("pen", n) | dict(grammar_state=[r % 2 for r in range(n)], no_repeat_ngram=[0, 3, 0, 4, 0], count_prompt=[0, 1, 0, 0, 2])
+    if family == "mirostat":
+        tau = [3.0, 2.5, 4.0, 3.5, 2.0]
+        per |= dict(mirostat_mu=[2 * t + 0.25 * r for r, t in enumerate(tau)])
+        family_kw = lambda order: dict(mirostat=([tau[r] for r in order], [0.1 + 0.05 * r for r in order]))
+    else:
+        per |= dict(top_k=[40, 5, 200, 17, 3], min_p=[0.0, 0.02, 0.0, 0.01, 0.05])
+        family_kw = lambda order: {}
+    dry = ([3.0, 0.0, 25.0, 40.0, 3.0], [1.75, 1.75, 2.0, 1.75, 1e30], [1, 2, 1, 1, 2])
+    rt = wrk.Runtime(ctx, wrk.GgufReader(model("small", v6)), num_batch=B)
+    occ, win = wrk.Occurrence(ctx, B, V), wrk.TokenWindow(ctx, B, V, 8)
+    # two states, every token allowed: an odd token id toggles the state, so the final state depends on the whole reply
+    gram = wrk.Grammar(ctx, V, np.arange(V) % 2, [[0, 1], [1, 0]])
+
+    def call(order, stop, seqs):
+        for b in range(B):
+            occ.load(b)
+            win.load(b)
+        kw = {k: [v[r] for r in order] for k, v in per.items()} | family_kw(order)
+        res, _ = rt.generate_queue([P[r] for r in order], stop=[stop[r] for r in order], max_new=[max_new[r] for r in order], mode=1, poll_steps=POLL,
+                                   occurrence=occ, window=win, dry=tuple([x[r] for r in order] for x in dry), grammar=gram,
+                                   stop_sequences=None if seqs is None else [seqs[r] for r in order], **kw)
+        mu, gs, match = rt.last_mirostat_mu, rt.last_grammar_state, rt.last_stop_match
+        at = {r: i for i, r in enumerate(order)}
+        return [dict(tok=res[at[r]][0].tolist(), reason=res[at[r]][1], start=res[at[r]][3], mu=None if mu is None else int(bits(mu[at[r]])),
+                     gs=int(gs[at[r]]), match=None if match is None else int(match[at[r]])) for r in range(n)]
+    try:
+        plain = call(list(range(n)), [[]] * n, None)
+        assert all(len(p["tok"]) == m for p, m in zip(plain, max_new))
+        # request 0 ends on the id of its third draw, request 4 on the stop sequence of its first two draws
+        stop, seqs = [[] for _ in range(n)], [[] for _ in range(n)]
+        stop[0], seqs[4] = [plain[0]["tok"][2]], [plain[4]["tok"][:2]]
+        fwd, rev = call(list(range(n)), stop, seqs), call(list(range(n))[::-1], stop, seqs)
+    finally:
+        gram.close()
+        win.close()
+        occ.close()
+        rt.close()
+    assert fwd[0]["reason"] == Q.STOP and fwd[4]["reason"] == Q.STOP and fwd[4]["match"] == 0 and len(fwd[4]["tok"]) == 2
+    assert len({tuple(p["tok"]) for p in fwd}) > 1                      # the requests do not all draw the same reply
+    for r in range(n):
+        host_first = r < B              # dispatched by the host at step 0 in order, by the device in reversed order -- or the reverse
+        assert (fwd[r]["start"] == 0) == host_first and (rev[r]["start"] == 0) == (n - 1 - r < B), (r, fwd[r], rev[r])
+        assert {k: v for k, v in fwd[r].items() if k != "start"} == {k: v for k, v in rev[r].items() if k != "start"}, (r, fwd[r], rev[r])
+
+
+# ----------------------------------------------------------------------------------------------------------------- 8. validation
 @pytest.mark.parametrize("v6", [False, True])
 def test_bad_arguments_are_rejected_before_any_launch(ctx, v6):
     data, V, B = model("tiny", v6), vocab("tiny", v6), 2

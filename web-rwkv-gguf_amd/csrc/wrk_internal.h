@@ -16,6 +16,7 @@
 #include "wrk_hip.h"
 #include "wrk_dev_group.h"
 #include "wrk_matjob.h"
+#include "wrk_queue_dispatch.h"
 
 struct wrk_ctx {
     int device = 0;
@@ -185,8 +186,8 @@ void argmax_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t v_stri
 
 // wrk_sample.hip: examples/chat.rs:150-190 Sampler::sample per row (nucleus cut at top_p, temperature inside it, inverse-CDF draw with
 // the SplitMix64 uniform of (seed, *step - step_base)); temperature or top_p == 0 is argmax_rows.  -1: v == 0, v > SAMPLE_MAX_VOCAB or
-// stride < v.  step_base is 0 everywhere but in queue programs (wrk_queue.hip), where a request's draws are numbered from its own reply
-struct SampleParam { float temperature, top_p; uint32_t seed, step_base; };
+// stride < v.  step_base is 0 everywhere but in queue programs (wrk_queue.hip), where a request's draws are numbered from its own reply.
+// SampleParam and the other rows that a queue dispatch writes (SampleFilter, SampleAlt, PenaltyParam, DryParam): wrk_queue_dispatch.h
 static constexpr uint32_t SAMPLE_MAX_VOCAB = 1u << 20;
 // One RowGate says whether a row's draw counts: flag == nullptr always, else iff flag[row * stride] == eq (a stop program:
 // StopParam::done == 0; a queue program: QueueSlot::phase == QUEUE_REPLY).  The Mirostat sampler moves mu and occurrence_update counts
@@ -195,14 +196,12 @@ struct RowGate { const uint32_t* flag; uint32_t stride, eq; };
 // SAMPLE_FILT: two more cuts of the candidates per row, one SampleFilter per row: the first min(n_P, n_K, n_M) ranks
 // stay, n_K = top_k (0 or >= v: v; 1: the arg-max, as temperature 0) and n_M = #{fl32(l - max) >= ln_min_p} (-inf: v).  Both off:
 // SAMPLE_PLAIN's token, bit for bit
-struct SampleFilter { uint32_t top_k; float ln_min_p; };
 // The two samplers whose candidates are not one of the plain sampler's cuts, one SampleAlt per row next to SampleParam.
 // SAMPLE_MIRO: Mirostat v2 -- candidates = rank 0 and every token whose surprise log2 W - (l - max) / T * log2 e is <= mu (top_p is not
 // read), then mu <- mu - eta * (s - tau) with s the drawn token's surprise among the candidates; tau == 0: SAMPLE_PLAIN's token, bit for
 // bit, mu untouched, and the greedy branch leaves mu alone too.  The update is made iff the row's draw counts (gate).
 // SAMPLE_TYP: locally typical sampling -- candidates = the tokens, by |(max - l) - gbar| ascending (ties by index), whose preceding
 // softmax mass is <= typical_p (top_p is not read); typical_p >= 1: SAMPLE_PLAIN's token, bit for bit.  alt is only read
-struct SampleAlt { float tau, eta, mu, typical_p; };
 enum : int { SAMPLE_PLAIN = 0, SAMPLE_FILT = 1, SAMPLE_MIRO = 2, SAMPLE_TYP = 3 };
 // which sampler, and its rows: par always, filt with SAMPLE_FILT, alt with SAMPLE_MIRO / SAMPLE_TYP, gate with SAMPLE_MIRO
 struct SamplePick { int mode; const SampleParam* par; const SampleFilter* filt; SampleAlt* alt; RowGate gate; };
@@ -237,7 +236,6 @@ int logprob_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride
 // penalize_rows: dst row r = the penalised src row r (src == dst allowed).  occurrence_update: row r applies tokens[r * ntok ..] in
 // order (count *= decay, then count[y] += weight[y], present[y] = 1); tokens < v (the caller validates them).  A row whose draw does not
 // count (gate: a finished sequence of a stop program, a prompt-phase or idle slot of a queue program) is left alone
-struct PenaltyParam { float* count; uint8_t* flags; const float* weight; float presence, frequency, decay; uint32_t pad; };
 void penalize_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_stride, uint32_t n, const PenaltyParam* par, float* dst,
                    uint32_t dst_stride);
 void occurrence_update(hipStream_t s, uint32_t v, uint32_t n, const PenaltyParam* par, const uint32_t* tokens, uint32_t ntok, const RowGate& gate);
@@ -261,11 +259,6 @@ void grammar_advance(hipStream_t s, uint32_t v, uint32_t n, const GrammarParam* 
 // no_repeat != 0 && M >= no_repeat - 1, else x - pen[M] for multiplier != 0 && M >= allowed; every other element keeps its bits.
 // scratch: u32 [n][v], all zero before and after every launch.  copy_rows: dst row r = src row r, bit for bit (the head output into the
 // rows dry_rows then works on).  window_push: slot r takes tokens[r]; a row whose draw does not count (gate) is left alone
-struct DryParam {
-    uint32_t* ring; uint32_t* meta; uint32_t cap;
-    uint32_t allowed, no_repeat; float multiplier;
-    float pen[WRK_DRY_MAX_MATCH + 2];       // [0, WRK_DRY_MAX_MATCH]; one entry of padding keeps the row a multiple of 8 bytes
-};
 struct DryBreakers { uint32_t count; uint32_t ids[WRK_MAX_DRY_BREAKERS]; };
 void dry_rows(hipStream_t s, float* x, uint32_t v, uint32_t stride, uint32_t n, const DryParam* par, const DryBreakers* brk, uint32_t* scratch);
 void copy_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_stride, uint32_t n, float* dst, uint32_t dst_stride);
@@ -305,53 +298,9 @@ void advance_stop_seq(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, ui
 // ids / count of a StopParam are read), tail[r] in / out, tokens[r], match[r] out
 void stop_seq_rows(hipStream_t s, uint32_t n, const StopSeqRow* rows, const StopParam* ids, uint32_t* tail, const uint32_t* tokens, uint32_t* match);
 
-// wrk_queue.hip: a request queue in the decode loops.  R requests are served on the B slots of a state; the slot
-// bookkeeping is device data in per-frame buffers written before every call, so one captured program serves any queue.
-// QueueReq: one request (prompt = pool[prompt_off .. + prompt_len), its pick parameters and stop set).  QueueSlot: what slot b is doing --
-// phase says what the draw of the NEXT step is: QUEUE_PROMPT a draw to discard (the step feeds a prompt token that is not the last),
-// QUEUE_REPLY reply token number `reply`, QUEUE_IDLE nothing.  QueueLog: per request, written as it runs (reason 3 while running)
-enum : uint32_t { QUEUE_IDLE = 0, QUEUE_PROMPT = 1, QUEUE_REPLY = 2 };
-struct QueueReq {
-    uint32_t prompt_off, prompt_len, max_new, seed;
-    float temperature, top_p, presence, frequency, decay;
-    uint32_t stop_count, stop_ids[WRK_MAX_STOP_TOKENS];
-    uint32_t top_k; float ln_min_p;     // the request's SampleFilter row (filtered queues)
-    float tau, eta, typical_p;          // the request's SampleAlt row (Mirostat / typical queues); its mu: QueueBufs::alt_mu
-};
-struct QueueSlot { uint32_t req, pos, reply, phase; };
-struct QueueLog { uint32_t length, reason, slot, start_step; };
-struct QueueCtl { uint32_t next_request, num_requests, live, pad; const float* init_state; };     // init_state: [L][slot] f32 or nullptr
-struct QueueBufs {
-    QueueSlot* slots; const QueueReq* reqs; const uint32_t* pool; QueueLog* log; QueueCtl* ctl;
-    uint32_t* started;              // [B]: 1 when the slot took a new request in this step (written for every slot by every launch)
-    SampleParam* sample_par;        // the frame's rows, or nullptr (arg-max)
-    PenaltyParam* pen_par;          // the frame's rows, or nullptr (no penalties)
-    SampleFilter* filter_par;       // the frame's rows, or nullptr (no top-k / min-p)
-    // the frame's rows, or nullptr (neither Mirostat nor typical).  alt_mu [R]: request r's mu -- its start value until it is dispatched,
-    // its final value once it has ended (advance_queue copies it into and out of the slot's row); nullptr unless Mirostat
-    SampleAlt* alt_par = nullptr;
-    float* alt_mu = nullptr;
-    // constrained queues: the frame's automaton state words [B], and gram_req [R]: request r's state -- its start value until it is
-    // dispatched, its final value once it has ended, exactly as alt_mu; both nullptr without a grammar
-    uint32_t* gram_state = nullptr;
-    uint32_t* gram_req = nullptr;
-    // queues with a token window: the frame's DryParam rows [B] and dry_req [R]: request r's values (its ring / meta are
-    // not read).  A slot that takes a request gets the request's values and a window of length 0; both nullptr without a window
-    DryParam* dry_par = nullptr;
-    const DryParam* dry_req = nullptr;
-    // queues with stop sequences: seq_rows [R]: request r's stop sequences; seq_tail [B][WRK_STOP_TAIL_LEN]: the slot's
-    // tail, set empty where the slot takes a request; seq_match [R]: request r's match word (NONE until a stop ends it); all nullptr
-    // without stop sequences
-    const StopSeqRow* seq_rows = nullptr;
-    uint32_t* seq_tail = nullptr;
-    uint32_t* seq_match = nullptr;
-    // prompt intake: ctx_from [R]: the index of request r's first prompt token that enters the slot's context; intake [B]:
-    // 1 when the token this launch wrote into tokens[b] is such a prompt token (written for every slot by every launch, as started);
-    // both nullptr without intake
-    const uint32_t* ctx_from = nullptr;
-    uint32_t* intake = nullptr;
-};
-// takes advance_tokens' place in a queue program: history <- drawn; per slot the next prompt token or the draw, stop / max_new check,
+// wrk_queue.hip: a request queue in the decode loops.  Its structures (QueueReq ... QueueBufs, QueueStateBufs) and its
+// dispatch rule: wrk_queue_dispatch.h.
+// advance_queue takes advance_tokens' place in a queue program: history <- drawn; per slot the next prompt token or the draw, stop / max_new check,
 // next requests to the slots that ended (ascending slot order), their parameters into the slot's rows, started[b], the log,
 // ctl->live -= ended, counter += 1 last (the sampler reads it)
 void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q, uint32_t b);
@@ -360,25 +309,14 @@ void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint3
 struct QueueGeom { float* state; uint32_t layers, num_batch, b0, v; size_t slot; };
 void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t b, int num_cu);
 // A state pool under the queue: P states in wrk_v7_state_read's layout in one device buffer; request r may start from a
-// copy of entry start[r] and has its end state written to entry save[r] in the step that ends it.  QUEUE_NO_ENTRY: none.
-// QueueStateCtl: the pool's pointer and entry count are data (one captured program serves any pool), next to the length of the step's
-// turnover list.  QueueTurn: one slot that ended in the step -- `save` the entry its state goes to, `started` / `start` as started[slot]
-// and the entry the slot's next request begins from
-static constexpr uint32_t QUEUE_NO_ENTRY = 0xFFFFFFFFu;
+// copy of entry start[r] and has its end state written to entry save[r] in the step that ends it.  QueueStateCtl: the pool's pointer and
+// entry count are data (one captured program serves any pool), next to the length of the step's turnover list (QueueTurn).
 // QueueHistory: a history pool beside the state pool, entry k of it belonging to entry k of the states: count f32
 // [entries][v] and flags u8 [entries][v] (the present bit only), and with cap > 0 ring u32 [entries][cap] and meta u32 [entries][2]
 // (length, next write position) -- what an occurrence slot and a token-window slot hold.  All nullptr / 0: none.  Device data as the
 // states' pointer is: one captured program serves any history pool
 struct QueueHistory { float* count; uint8_t* flags; uint32_t* ring; uint32_t* meta; uint32_t cap, pad; };
 struct QueueStateCtl { float* states; uint32_t num_entries, turn_count; QueueHistory hist; };
-struct QueueTurn { uint32_t slot, save, started, start; };
-struct QueueStateBufs {
-    const uint32_t *start, *save;   // [R] next to the request table (QueueReq's layout does not move)
-    QueueStateCtl* sctl;
-    QueueTurn* turn;                // [B]: written by advance_queue_pool at position (ended slots before this one), no atomics
-    // a call with a history pool: queue_history_turnover takes the place of the occurrence reset and of advance_queue's window reset
-    bool history = false;
-};
 // advance_queue for pool programs: the same body, and the step's turnover list
 void advance_queue_pool(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q,
                         const QueueStateBufs& p, uint32_t b);

@@ -5,7 +5,8 @@
 //
 //   advance_queue   takes advance_tokens' place in a queue program: one thread owns a slot, pops the next prompt token or takes the
 //                   draw, checks the stop set and max_new, deals the next requests to the slots that ended (exclusive scan over the slot
-//                   index from one next_request word), copies their parameters into the slot's rows, and moves the step counter last
+//                   index from one next_request word) by queue_dispatch (wrk_queue_dispatch.h) -- the one rule for "request r goes to
+//                   slot b, p_0 fed at step f", which the host runs for step 0 too -- and moves the step counter last
 //   queue_reset     grid (layer x slice, slot): every workgroup reads started[b] and leaves when it is 0; else zero fill / init_state
 //                   copy of the slot, and a second small grid for the slot's occurrence row when the program is penalised
 //   advance_queue_pool, queue_turnover   their places in the programs of a call with a state pool: the same advance body
@@ -32,7 +33,7 @@ static constexpr uint32_t QUEUE_WINDOW_TILES = (WRK_MAX_TOKEN_WINDOW + QUEUE_CHU
 // slots are owned by the threads of ONE workgroup (B <= 256, as advance_stop).  POOL (advance_queue_pool_kernel): the slots that ended
 // also go into the step's turnover list, at the position the scan below gives them.  SEQ (the _seq kernels): a reply draw
 // goes through stop_seq_step (wrk_stopseq_dev.h) with the request's stop set and its StopSeqRow and enters the slot's tail; a match ends
-// the request as a stop token does and leaves its match word; a slot that takes a request starts with an empty tail
+// the request as a stop token does and leaves its match word.  What a slot that takes a request starts with is queue_dispatch's
 template <bool POOL, bool SEQ>
 __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
                                                    uint32_t* __restrict__ history, uint32_t* __restrict__ counter, const QueueBufs& Q,
@@ -91,46 +92,26 @@ __device__ __forceinline__ void advance_queue_body(const uint32_t* __restrict__ 
         total += wave_ended[w];
     }
     if (i < b) {
-        uint32_t started = 0;
-        QueueTurn turn{i, QUEUE_NO_ENTRY, 0u, QUEUE_NO_ENTRY};
+        uint32_t started = 0, save = QUEUE_NO_ENTRY;
         if (ended) {
-            const uint32_t r = next + before + rank;
-            if (POOL) turn.save = P.save[s.req];
-            if (r < num_requests) {
-                const QueueReq* q = Q.reqs + r;
-                s = QueueSlot{r, 0u, 0u, q->prompt_len == 1 ? QUEUE_REPLY : QUEUE_PROMPT};
-                tokens[i] = Q.pool[q->prompt_off];
-                if (Q.ctx_from) take = Q.ctx_from[r] == 0u;
-                // reply token j is drawn at step (step + 1) + prompt_len - 1 + j: its sampler step is j whenever it is scheduled
-                if (Q.sample_par) Q.sample_par[i] = SampleParam{q->temperature, q->top_p, q->seed, step + q->prompt_len};
-                if (Q.filter_par) Q.filter_par[i] = SampleFilter{q->top_k, q->ln_min_p};
-                // a refilled slot starts from its own request's mu, not from its predecessor's (a request is dispatched once: its entry
-                // still holds its start value)
-                if (Q.alt_par) Q.alt_par[i] = SampleAlt{q->tau, q->eta, Q.alt_mu ? Q.alt_mu[r] : 0.0f, q->typical_p};
-                if (Q.gram_req) Q.gram_state[i] = Q.gram_req[r];        // the same for its automaton state
-                // its DRY values and table, and an empty window: window_push, in front of this launch, has pushed the last draw of the
-                // request that ended, and the next launch that reads the slot's window is the next step's dry_rows
-                if (Q.dry_par) {
-                    DryParam* dp = Q.dry_par + i;
-                    const DryParam* dq = Q.dry_req + r;
-                    dp->allowed = dq->allowed; dp->no_repeat = dq->no_repeat; dp->multiplier = dq->multiplier;
-                    for (uint32_t m = 0; m <= WRK_DRY_MAX_MATCH; ++m) dp->pen[m] = dq->pen[m];
-                    // with a history pool queue_history_turnover, behind this launch, saves the window first and then sets it
-                    if (!(POOL && P.history)) { dp->meta[0] = 0u; dp->meta[1] = 0u; }
-                }
-                if (SEQ) stop_tail_clear(Q.seq_tail + (size_t)i * STOP_TAIL);      // and its tail starts empty
-                if (Q.pen_par) { Q.pen_par[i].presence = q->presence; Q.pen_par[i].frequency = q->frequency; Q.pen_par[i].decay = q->decay; }
-                Q.log[r] = QueueLog{0u, 3u, i, step + 1};
-                started = 1;
-                if (POOL) { turn.started = 1; turn.start = P.start[r]; }
-            } else {
-                s.phase = QUEUE_IDLE;
-            }
-            if (POOL) P.turn[before + rank] = turn;
+            if (POOL) save = P.save[s.req];
+            s.phase = QUEUE_IDLE;
+            started = next + before + rank < num_requests;
         }
-        Q.slots[i] = s;
+        if (started) {
+            // the next step feeds p_0 (a request is dispatched once: its own mu and automaton state still hold their start values).  An
+            // empty window: window_push, in front of this launch, has pushed the last draw of the request that ended, and dry_rows of the
+            // next step reads it next; with a history pool queue_history_turnover, behind this launch, saves the window, then sets it
+            if (queue_dispatch(Q, tokens, next + before + rank, i, step + 1, POOL ? &P : nullptr, before + rank, save)) {
+                uint32_t* meta = Q.dry_par[i].meta;
+                meta[0] = meta[1] = 0u;
+            }
+        } else {
+            if (POOL && ended) P.turn[before + rank] = QueueTurn{i, save, 0u, QUEUE_NO_ENTRY};
+            Q.slots[i] = s;
+            if (Q.intake) Q.intake[i] = take;
+        }
         Q.started[i] = started;
-        if (Q.intake) Q.intake[i] = take;
     }
     if (i == 0) {
         if (total) { Q.ctl->next_request = next + total; Q.ctl->live = live - total; }

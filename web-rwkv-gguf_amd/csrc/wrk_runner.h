@@ -134,21 +134,14 @@ struct wrk_history_bufs {       // generated tokens [steps][B]
     void layout(wrk_dev_cut& c, const size_t* d) { c.take(tokens, d[0] * 4 + 256); }
 };
 // per-sequence parameter rows the step programs read through the pointer, never baked in: generate_sample's sampler rows
-// (wrk::SampleParam) and, next to them, the top-k / min-p rows of a filtered pick (wrk::SampleFilter)
+// (wrk::SampleParam), next to them the top-k / min-p rows of a filtered pick (wrk::SampleFilter) or the (tau, eta, mu, typical_p) rows
+// of a Mirostat / typical pick (wrk::SampleAlt): the Mirostat sampler rewrites a row's mu at every draw that counts, and the
+// call reads the rows back
 template <class Row> struct wrk_rows_bufs {
     static constexpr int DIMS = 1;              // sequences
     static constexpr unsigned EXACT = 0;
     Row* par = nullptr;
     void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, d[0] * sizeof(Row)); }
-};
-// Mirostat / typical picks: per-sequence (tau, eta, mu, typical_p) rows next to the sampler's; the Mirostat sampler rewrites
-// a row's mu at every draw that counts, and the call reads the rows back.  mu: a queue's per-request mu (wrk::QueueBufs::alt_mu)
-struct wrk_alt_bufs {
-    static constexpr int DIMS = 2;              // sequences, requests (>= 1)
-    static constexpr unsigned EXACT = 0;
-    wrk::SampleAlt* par = nullptr;
-    float* mu = nullptr;
-    void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, d[0] * sizeof(wrk::SampleAlt)); c.take(mu, d[1] * 4); }
 };
 // generate_penalized: per-sequence occurrence rows and penalties (the step programs read the table's pointers from here); out: the
 // penalised logits [B][V]
@@ -161,33 +154,28 @@ struct wrk_penalty_bufs {
 };
 // constrained decoding (wrk_grammar.hip).  par: the parameter block (the grammar's tables and `state`: one program serves
 // any grammar and any start states); state: the sequences' automaton states, read back after the call; out [B][V]: the masked head
-// output of a pick without penalties; req: a queue's per-request states (wrk::QueueBufs::gram_req)
+// output of a pick without penalties
 struct wrk_grammar_bufs {
-    static constexpr int DIMS = 3;              // sequences, requests (>= 1), vocabulary
-    static constexpr unsigned EXACT = 4;
+    static constexpr int DIMS = 2;              // sequences, vocabulary
+    static constexpr unsigned EXACT = 2;
     wrk::GrammarParam* par = nullptr;
     uint32_t* state = nullptr;
     float* out = nullptr;
-    uint32_t* req = nullptr;
-    void layout(wrk_dev_cut& c, const size_t* d) {
-        c.take(par, sizeof(wrk::GrammarParam)); c.take(state, d[0] * 4); c.take(out, d[0] * d[2] * 4); c.take(req, d[1] * 4);
-    }
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, sizeof(wrk::GrammarParam)); c.take(state, d[0] * 4); c.take(out, d[0] * d[1] * 4); }
 };
 // DRY / the n-gram ban (wrk_dry.hip).  par: the sequences' DryParam rows (window slot, values, penalty table: one program
 // serves any window and any parameters); brk: the call's breaker ids; out [B][V]: the copy of the head output that a pick without
-// penalties is made on; scratch u32 [B][V]: dry_rows' per-token maxima, zero between launches; req: a queue's per-request rows
-// (wrk::QueueBufs::dry_req)
+// penalties is made on; scratch u32 [B][V]: dry_rows' per-token maxima, zero between launches
 struct wrk_dry_bufs {
-    static constexpr int DIMS = 3;              // sequences, requests (>= 1), vocabulary
-    static constexpr unsigned EXACT = 4;
+    static constexpr int DIMS = 2;              // sequences, vocabulary
+    static constexpr unsigned EXACT = 2;
     wrk::DryParam* par = nullptr;
     wrk::DryBreakers* brk = nullptr;
     float* out = nullptr;
     uint32_t* scratch = nullptr;
-    wrk::DryParam* req = nullptr;
     void layout(wrk_dev_cut& c, const size_t* d) {
-        c.take(par, d[0] * sizeof(wrk::DryParam)); c.take(brk, sizeof(wrk::DryBreakers)); c.take(out, d[0] * d[2] * 4);
-        c.take(scratch, d[0] * d[2] * 4); c.take(req, d[1] * sizeof(wrk::DryParam));
+        c.take(par, d[0] * sizeof(wrk::DryParam)); c.take(brk, sizeof(wrk::DryBreakers)); c.take(out, d[0] * d[1] * 4);
+        c.take(scratch, d[0] * d[1] * 4);
     }
 };
 // wrk_v*_score (wrk_score.hip): targets / logprob / rank of the header rows and their slice partials [rows][SCORE_MAX_SLICES]
@@ -232,8 +220,9 @@ struct wrk_seq_bufs {
         c.take(rows, d[0] * sizeof(wrk::StopSeqRow)); c.take(tail, d[0] * WRK_STOP_TAIL_LEN * 4); c.take(match, d[0] * 4);
     }
 };
-// generate_queue (wrk_queue.hip): slot rows and started flags [slots], the control words, the request table and log
-// [requests], the prompt token pool [pool tokens]
+// generate_queue (wrk_queue.hip): slot records and started flags [slots], the control words, the prompt token pool [pool
+// tokens] and everything of a request [requests], the only group with that dimension: the table and the log, and what a request carries
+// for the call's features, used or not -- its mu, automaton state, DRY values, stop sequences and match word, intake offset, pool entries
 struct wrk_queue_bufs {
     static constexpr int DIMS = 3;              // slots, requests, pool tokens
     static constexpr unsigned EXACT = 0;
@@ -243,41 +232,41 @@ struct wrk_queue_bufs {
     wrk::QueueReq* reqs = nullptr;
     wrk::QueueLog* log = nullptr;
     uint32_t* pool = nullptr;
+    float* mu = nullptr;
+    wrk::DryParam* dry = nullptr;
+    wrk::StopSeqRow* seq_rows = nullptr;
+    uint32_t *gram = nullptr, *seq_match = nullptr, *from = nullptr;
+    uint32_t *start = nullptr, *save = nullptr; // one piece: save == start + request cap
     void layout(wrk_dev_cut& c, const size_t* d) {
         c.take(slots, d[0] * sizeof(wrk::QueueSlot)); c.take(started, d[0] * 4); c.take(ctl, sizeof(wrk::QueueCtl));
         c.take(reqs, d[1] * sizeof(wrk::QueueReq)); c.take(log, d[1] * sizeof(wrk::QueueLog)); c.take(pool, d[2] * 4);
+        c.take(mu, d[1] * 4); c.take(gram, d[1] * 4); c.take(dry, d[1] * sizeof(wrk::DryParam));
+        c.take(seq_rows, d[1] * sizeof(wrk::StopSeqRow)); c.take(seq_match, d[1] * 4); c.take(from, d[1] * 4); c.take(start, 2 * d[1] * 4);
+        save = start ? start + d[1] : nullptr;
     }
     uint32_t* live() const { return &ctl->live; }
 };
-// stop sequences of generate_queue: rows and match words per request, tails [slots][WRK_STOP_TAIL_LEN] per slot
+// what the queue's features keep per slot: the stop-sequence tails [slots][WRK_STOP_TAIL_LEN] ...
 struct wrk_queue_seq_bufs {
-    static constexpr int DIMS = 2;              // slots, requests
+    static constexpr int DIMS = 1;              // slots
     static constexpr unsigned EXACT = 0;
-    wrk::StopSeqRow* rows = nullptr;
-    uint32_t *tail = nullptr, *match = nullptr;
-    void layout(wrk_dev_cut& c, const size_t* d) {
-        c.take(rows, d[1] * sizeof(wrk::StopSeqRow)); c.take(tail, d[0] * WRK_STOP_TAIL_LEN * 4); c.take(match, d[1] * 4);
-    }
+    uint32_t* tail = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(tail, d[0] * WRK_STOP_TAIL_LEN * 4); }
 };
-// a queue call with a state pool: the pool's control words, the turnover list [slots], the start and save entries of the
-// requests [2][entry cap]
+// ... and the prompt-intake flags
+struct wrk_queue_intake_bufs {
+    static constexpr int DIMS = 1;              // slots
+    static constexpr unsigned EXACT = 0;
+    uint32_t* flags = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(flags, d[0] * 4); }
+};
+// a queue call with a state pool: the pool's control words and the turnover list [slots]
 struct wrk_queue_state_bufs {
-    static constexpr int DIMS = 2;              // slots, requests
+    static constexpr int DIMS = 1;              // slots
     static constexpr unsigned EXACT = 0;
     wrk::QueueStateCtl* ctl = nullptr;
     wrk::QueueTurn* turn = nullptr;
-    uint32_t *start = nullptr, *save = nullptr; // one piece: save == start + entry cap
-    void layout(wrk_dev_cut& c, const size_t* d) {
-        c.take(ctl, sizeof(wrk::QueueStateCtl)); c.take(turn, d[0] * sizeof(wrk::QueueTurn)); c.take(start, 2 * d[1] * 4);
-        save = start ? start + d[1] : nullptr;
-    }
-};
-// prompt intake of a queue call: the intake flags [slots] and the requests' context offsets [requests]
-struct wrk_queue_intake_bufs {
-    static constexpr int DIMS = 2;              // slots, requests
-    static constexpr unsigned EXACT = 0;
-    uint32_t *flags = nullptr, *from = nullptr;
-    void layout(wrk_dev_cut& c, const size_t* d) { c.take(flags, d[0] * 4); c.take(from, d[1] * 4); }
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(ctl, sizeof(wrk::QueueStateCtl)); c.take(turn, d[0] * sizeof(wrk::QueueTurn)); }
 };
 // log-probs in the decode loops (wrk_logprob.hip).  par: the parameter block (the output buffers and num_top: one program
 // serves any num_top); the per-step rows logprob [rows], top_ids / top_logprobs [rows][WRK_MAX_TOP_LOGPROBS], indexed
@@ -329,7 +318,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_history_bufs> history;
     wrk_dev_group<wrk_rows_bufs<wrk::SampleParam>> sample;
     wrk_dev_group<wrk_rows_bufs<wrk::SampleFilter>> filter;
-    wrk_dev_group<wrk_alt_bufs> alt;
+    wrk_dev_group<wrk_rows_bufs<wrk::SampleAlt>> alt;
     wrk_dev_group<wrk_penalty_bufs> penalty;
     wrk_dev_group<wrk_grammar_bufs> grammar;
     wrk_dev_group<wrk_dry_bufs> dry;

@@ -159,14 +159,11 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
 struct wrk_pick_params {    // validated rows; empty: the arg-max / without penalties / without filters
     std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
     std::vector<wrk::SampleAlt> alt;        // Mirostat / typical rows
-    uint32_t alt_requests = 0;              // a queue: its requests (the size of the frame's per-request mu array)
     const wrk_grammar* grammar = nullptr;   // a constrained pick: the automaton and the state every row starts in
     std::vector<uint32_t> gram_state;
-    uint32_t gram_requests = 0;             // a queue: its requests (the size of the frame's per-request state array)
     bool has_dry = false;                   // a DRY pick: the rows' window slots, values and tables, and the call's breakers
     std::vector<wrk::DryParam> dry;
     wrk::DryBreakers brk{};
-    uint32_t dry_requests = 0;              // a queue: its requests (the size of the frame's per-request row array)
 };
 
 // The one validation of the pick arrays (wrk_pick_args).  Sets kind.pick / kind.penalized and packs `n` rows; penalty row r names slot r
@@ -374,16 +371,14 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     const wrk::PenaltyParam* pen = rows.pen.empty() ? nullptr : rows.pen.data() + b0;
     const wrk::SampleFilter* filt = rows.filt.empty() ? nullptr : rows.filt.data() + b0;
     const wrk::SampleAlt* alt = rows.alt.empty() ? nullptr : rows.alt.data() + b0;
-    // a per-request array of a queue (none: 0) has at least one entry
-    const size_t V = f.facts().num_vocab, alt_req = rows.alt_requests ? rows.alt_requests : 1, gram_req = rows.gram_requests ? rows.gram_requests : 1,
-                 dry_req = rows.dry_requests ? rows.dry_requests : 1;
+    const size_t V = f.facts().num_vocab;
     int32_t rc = f.grow(f.history, {(size_t)steps * B});
     if (rc == WRK_OK && par) rc = f.grow(f.sample, {B});
     if (rc == WRK_OK && filt) rc = f.grow(f.filter, {B});
-    if (rc == WRK_OK && alt) rc = f.grow(f.alt, {B, alt_req});
+    if (rc == WRK_OK && alt) rc = f.grow(f.alt, {B});
     if (rc == WRK_OK && pen) rc = f.grow(f.penalty, {B, V});
-    if (rc == WRK_OK && rows.grammar) rc = f.grow(f.grammar, {B, gram_req, V});
-    if (rc == WRK_OK && rows.has_dry) rc = f.grow(f.dry, {B, dry_req, V});
+    if (rc == WRK_OK && rows.grammar) rc = f.grow(f.grammar, {B, V});
+    if (rc == WRK_OK && rows.has_dry) rc = f.grow(f.dry, {B, V});
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
@@ -439,13 +434,18 @@ static int32_t queue_csr_check(wrk_ctx* ctx, const uint32_t* off, uint32_t R, co
     return WRK_OK;
 }
 
-// generate_queue: the options validated (WRK_E_ARG before any launch) into the request table, the prompt pool and the pick rows the slots
-// start with.  first_tokens [B]: p_0 of the requests dispatched at step 0, a valid id for the slots that start idle
+// generate_queue: the options validated (WRK_E_ARG before any launch) into the request table, the prompt pool and what a request
+// carries per feature [R] (wrk_queue_check, wrk_queue_pool_check), then what the B slots start with (wrk_queue_start)
 struct wrk_queue_pack {
     uint32_t R = 0, max_steps = 0, poll_steps = 0;
     wrk_step_kind kind{wrk_step_kind::GREEDY, false, wrk_step_kind::QUEUE};       // wrk_queue_pool_check: QUEUE_POOL
-    std::vector<wrk::QueueReq> reqs; std::vector<uint32_t> pool, first_tokens;
-    wrk_pick_params rows;       // [B]
+    std::vector<wrk::QueueReq> reqs; std::vector<uint32_t> pool;
+    // wrk_queue_start, all [B]: the tokens of step 0, the features' rows, the slot records, tails and intake flags; the log [R]; the
+    // turnover list of "step -1", the nstart slots that start a request and save nothing; wipe: the leading slots whose window to empty
+    std::vector<uint32_t> first_tokens, tails, take;
+    wrk_pick_params rows;
+    std::vector<wrk::QueueSlot> slots; std::vector<wrk::QueueLog> log; std::vector<wrk::QueueTurn> turn;
+    uint32_t nstart = 0, wipe = 0;
     const float* init_state = nullptr;
     // with a state pool; start / save: [R] entries, QUEUE_NO_ENTRY for none
     float* pool_states = nullptr;
@@ -521,48 +521,11 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
         WRK_ARG(ctx, opt->init_state->bytes == need, "init_state holds %zu bytes, a sequence's state is %zu", opt->init_state->bytes, need);
         pk.init_state = (const float*)opt->init_state->ptr;
     }
-    // what the slots start with: request b in slot b; a slot without a request idles on a valid id
-    pk.first_tokens.assign(B, pk.pool[0]);
-    if (kind.sampled()) pk.rows.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
-    if (kind.penalized) pk.rows.pen.resize(B);
-    if (kind.filtered()) pk.rows.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
-    if (kind.alt()) {
-        pk.rows.alt.assign(B, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
-        pk.rows.alt_requests = R;
-        pk.mu.resize(R);
-        for (uint32_t r = 0; r < R; ++r) pk.mu[r] = req.alt[r].mu;
-        pk.mu_out = kind.mirostat() ? opt->mirostat_mu : nullptr;
-    }
-    if (kind.constrained) {        // the slots start in their requests' states; an idle slot in state 0, which every grammar has
-        pk.gram = req.gram_state;
-        pk.gram_out = opt->grammar_state;
-        pk.rows.grammar = req.grammar;
-        pk.rows.gram_requests = R;
-        pk.rows.gram_state.assign(B, 0u);
-        for (uint32_t b = 0; b < B && b < R; ++b) pk.rows.gram_state[b] = pk.gram[b];
-    }
-    if (kind.dry) {                // slot b's row names slot b of the window, whatever request it serves; an idle slot: any valid values
-        pk.dry = req.dry;
-        pk.window = opt->window;
-        pk.rows.has_dry = true;
-        pk.rows.brk = req.brk;
-        pk.rows.dry_requests = R;
-        pk.rows.dry.resize(B);
-        for (uint32_t b = 0; b < B; ++b) {
-            pk.rows.dry[b] = pk.dry[b < R ? b : 0];
-            pk.rows.dry[b].ring = opt->window->ring + (size_t)b * opt->window->capacity;
-            pk.rows.dry[b].meta = opt->window->meta + (size_t)b * 2;
-        }
-    }
-    for (uint32_t b = 0; b < B; ++b) {
-        const uint32_t r = b < R ? b : 0;       // idle slots: any valid row
-        const wrk::QueueReq& q = pk.reqs[r];
-        if (b < R) pk.first_tokens[b] = pk.pool[q.prompt_off];
-        if (kind.sampled() && b < R) pk.rows.par[b] = wrk::SampleParam{q.temperature, q.top_p, q.seed, q.prompt_len - 1};
-        if (kind.filtered() && b < R) pk.rows.filt[b] = wrk::SampleFilter{q.top_k, q.ln_min_p};
-        if (kind.alt() && b < R) pk.rows.alt[b] = req.alt[b];
-        if (kind.penalized) pk.rows.pen[b] = opt->occ->row(b, q.presence, q.frequency, q.decay);
-    }
+    // what a request carries besides its QueueReq
+    for (uint32_t r = 0; r < R && kind.alt(); ++r) pk.mu.push_back(req.alt[r].mu);
+    pk.mu_out = kind.mirostat() ? opt->mirostat_mu : nullptr;
+    if (kind.constrained) { pk.gram = req.gram_state; pk.gram_out = opt->grammar_state; pk.rows.grammar = req.grammar; }
+    if (kind.dry) { pk.dry = req.dry; pk.window = opt->window; pk.rows.has_dry = true; pk.rows.brk = req.brk; }
     return WRK_OK;
 }
 
@@ -623,16 +586,49 @@ static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, co
 static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
     return wrk::QueueBufs{f.queue.slots, f.queue.reqs, f.queue.pool, f.queue.log, f.queue.ctl, f.queue.started,
                           kind.sampled() ? f.sample.par : nullptr, kind.penalized ? f.penalty.par : nullptr, kind.filtered() ? f.filter.par : nullptr,
-                          kind.alt() ? f.alt.par : nullptr, kind.mirostat() ? f.alt.mu : nullptr,
-                          kind.constrained ? f.grammar.state : nullptr, kind.constrained ? f.grammar.req : nullptr,
-                          kind.dry ? f.dry.par : nullptr, kind.dry ? f.dry.req : nullptr,
-                          kind.stop_seqs ? f.queue_seq.rows : nullptr, kind.stop_seqs ? f.queue_seq.tail : nullptr,
-                          kind.stop_seqs ? f.queue_seq.match : nullptr,
-                          kind.intake ? f.queue_intake.from : nullptr, kind.intake ? f.queue_intake.flags : nullptr};
+                          kind.alt() ? f.alt.par : nullptr, kind.mirostat() ? f.queue.mu : nullptr,
+                          kind.constrained ? f.grammar.state : nullptr, kind.constrained ? f.queue.gram : nullptr,
+                          kind.dry ? f.dry.par : nullptr, kind.dry ? f.queue.dry : nullptr,
+                          kind.stop_seqs ? f.queue.seq_rows : nullptr, kind.stop_seqs ? f.queue_seq.tail : nullptr,
+                          kind.stop_seqs ? f.queue.seq_match : nullptr,
+                          kind.intake ? f.queue.from : nullptr, kind.intake ? f.queue_intake.flags : nullptr};
 }
 
 static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
-    return wrk::QueueStateBufs{f.queue_states.start, f.queue_states.save, f.queue_states.ctl, f.queue_states.turn, kind.history};
+    return wrk::QueueStateBufs{f.queue.start, f.queue.save, f.queue_states.ctl, f.queue_states.turn, kind.history};
+}
+
+// The host's step 0, after the checks.  Every slot gets valid rows, which an idle slot (b >= R) keeps -- a valid token, state 0, which
+// every grammar has -- with the pointers that are the slot's whatever request it serves: row b of the occurrence table, slot b of the
+// window.  Then the dispatch rule deals request b to slot b < min(B, R) with first_step 0, over host mirrors of the device's arrays
+static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_pack& pk) {
+    const wrk_step_kind kind = pk.kind;
+    wrk_pick_params& rows = pk.rows;
+    pk.first_tokens.assign(B, pk.pool[0]);
+    if (kind.sampled()) rows.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
+    if (kind.filtered()) rows.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
+    if (kind.alt()) rows.alt.assign(B, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
+    if (kind.constrained) rows.gram_state.assign(B, 0u);
+    for (uint32_t b = 0; b < B && kind.penalized; ++b) rows.pen.push_back(opt->occ->row(b, 0.0f, 0.0f, 1.0f));
+    for (uint32_t b = 0; b < B && kind.dry; ++b) {
+        rows.dry.push_back(pk.dry[0]);
+        rows.dry[b].ring = pk.window->ring + (size_t)b * pk.window->capacity;
+        rows.dry[b].meta = pk.window->meta + (size_t)b * 2;
+    }
+    pk.slots.assign(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
+    pk.log.assign(pk.R, wrk::QueueLog{0u, 0u, 0u, 0u});
+    if (kind.stop_seqs) pk.tails.assign((size_t)B * WRK_STOP_TAIL_LEN, WRK_STOP_TAIL_EMPTY);
+    if (kind.intake) pk.take.assign(B, 0u);
+    pk.nstart = B < pk.R ? B : pk.R;
+    pk.turn.resize(pk.nstart);
+    // as queue_bufs: an array is nullptr exactly when the kind is without its feature (a vector of the pack is empty then)
+    auto at = [](auto& v) { return v.empty() ? nullptr : v.data(); };
+    const wrk::QueueBufs Q{pk.slots.data(), pk.reqs.data(), pk.pool.data(), pk.log.data(), nullptr, nullptr, at(rows.par), at(rows.pen), at(rows.filt),
+                           at(rows.alt), kind.mirostat() ? pk.mu.data() : nullptr, at(rows.gram_state), at(pk.gram), at(rows.dry), at(pk.dry),
+                           at(pk.seq.rows), at(pk.tails), nullptr, at(pk.from), at(pk.take)};
+    const wrk::QueueStateBufs P{pk.start.data(), pk.save.data(), nullptr, pk.turn.data(), kind.history};
+    for (uint32_t b = 0; b < pk.nstart; ++b)
+        if (wrk::queue_dispatch(Q, pk.first_tokens.data(), b, b, 0u, kind.pool() ? &P : nullptr, b)) pk.wipe = b + 1;
 }
 
 static wrk::QueueGeom queue_geom(const wrk_v7_state* st, uint32_t b0, uint32_t V) {
@@ -652,59 +648,41 @@ static int32_t enqueue_prompt_intake(wrk_frame_common& f, uint32_t B, wrk_step_k
     return WRK_OK;
 }
 
-// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): queue buffers of the
-// frame, the tables, the slots that start at step 0, live = R; then queue_reset of those slots on the submission stream (with a pool:
-// the pool's buffers and queue_turnover on the list of those slots)
+// after wrk_decode_prepare, which uploaded the slots' tokens and rows of step 0, and before the step program is looked up (growing the
+// buffers drops the programs): the queue's buffers grown, the tables and what wrk_queue_start left for the slots uploaded, live = R;
+// then queue_reset of the slots that start at step 0 on the submission stream (with a pool: queue_turnover on the list of those slots)
 static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t B, const wrk_queue_pack& pk) {
     wrk_ctx* ctx = f.ctx;
     const uint32_t V = f.facts().num_vocab;
     // never smaller than before: a later, smaller queue reuses the buffers and the program
     int32_t rc = f.grow(f.queue, {B, pk.R, pk.pool.size()});
-    if (rc == WRK_OK && pk.kind.pool()) rc = f.grow(f.queue_states, {B, pk.R});
-    if (rc == WRK_OK && pk.kind.stop_seqs) rc = f.grow(f.queue_seq, {B, pk.R});
-    if (rc == WRK_OK && pk.kind.intake) rc = f.grow(f.queue_intake, {B, pk.R});
+    if (rc == WRK_OK && pk.kind.pool()) rc = f.grow(f.queue_states, {B});
+    if (rc == WRK_OK && pk.kind.stop_seqs) rc = f.grow(f.queue_seq, {B});
+    if (rc == WRK_OK && pk.kind.intake) rc = f.grow(f.queue_intake, {B});
     if (rc != WRK_OK) return rc;
     const wrk_step_kind kind = pk.kind;
-    const uint32_t nstart = B < pk.R ? B : pk.R;
-    std::vector<wrk::QueueSlot> slots(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
     std::vector<uint32_t> started(B, 0u);
-    std::vector<wrk::QueueLog> log(pk.R, wrk::QueueLog{0u, 0u, 0u, 0u});
-    for (uint32_t b = 0; b < nstart; ++b) {
-        slots[b] = wrk::QueueSlot{b, 0u, 0u, pk.reqs[b].prompt_len == 1 ? wrk::QUEUE_REPLY : wrk::QUEUE_PROMPT};
-        started[b] = 1;
-        log[b] = wrk::QueueLog{0u, 3u, b, 0u};
-    }
-    const wrk::QueueCtl ctl{nstart, pk.R, pk.R, 0u, pk.init_state};
-    // the per-request mu and automaton states live in groups that wrk_decode_prepare sized with the request count
-    if (pk.kind.mirostat() && !f.alt.holds({0, pk.R})) return wrk_fail(ctx, WRK_E_ARG, "Mirostat rows are not prepared");
-    if (pk.kind.constrained && !f.grammar.holds({0, pk.R})) return wrk_fail(ctx, WRK_E_ARG, "grammar states are not prepared");
-    if (pk.kind.dry && !f.dry.holds({0, pk.R})) return wrk_fail(ctx, WRK_E_ARG, "DRY rows are not prepared");
+    for (uint32_t b = 0; b < pk.nstart; ++b) started[b] = 1u;
+    const wrk::QueueCtl ctl{pk.nstart, pk.R, pk.R, 0u, pk.init_state};
     wrk_upload up{ctx};
-    up(f.queue.slots, slots.data(), B)(f.queue.started, started.data(), B)(f.queue.log, log.data(), pk.R)(f.queue.reqs, pk.reqs.data(), pk.R);
+    up(f.queue.slots, pk.slots.data(), B)(f.queue.started, started.data(), B)(f.queue.log, pk.log.data(), pk.R)(f.queue.reqs, pk.reqs.data(), pk.R);
     up(f.queue.pool, pk.pool.data(), pk.pool.size())(f.queue.ctl, &ctl, 1);
-    if (pk.kind.mirostat()) up(f.alt.mu, pk.mu.data(), pk.R);
-    if (pk.kind.constrained) up(f.grammar.req, pk.gram.data(), pk.R);
-    if (pk.kind.dry) {          // the slots that start a request at step 0 begin with an empty window, as a refilled slot does
-        const std::vector<uint32_t> empty((size_t)nstart * 2, 0u);
-        up(f.dry.req, pk.dry.data(), pk.R)(pk.window->meta, empty.data(), empty.size());
+    if (kind.mirostat()) up(f.queue.mu, pk.mu.data(), pk.R);
+    if (kind.constrained) up(f.queue.gram, pk.gram.data(), pk.R);
+    if (kind.dry) up(f.queue.dry, pk.dry.data(), pk.R);
+    // a slot that starts a request at step 0 begins with an empty window, as a refilled slot does
+    const std::vector<uint32_t> empty((size_t)pk.wipe * 2, 0u);
+    if (pk.wipe) up(pk.window->meta, empty.data(), empty.size());
+    if (kind.stop_seqs) {       // no request has a match yet
+        const std::vector<uint32_t> none(pk.R, WRK_STOP_MATCH_NONE);
+        up(f.queue.seq_rows, pk.seq.rows.data(), pk.R)(f.queue_seq.tail, pk.tails.data(), pk.tails.size())(f.queue.seq_match, none.data(), pk.R);
     }
-    if (pk.kind.stop_seqs) {     // every slot's tail starts empty, no request has a match yet
-        const std::vector<uint32_t> tails((size_t)B * WRK_STOP_TAIL_LEN, WRK_STOP_TAIL_EMPTY), none(pk.R, WRK_STOP_MATCH_NONE);
-        up(f.queue_seq.rows, pk.seq.rows.data(), pk.R)(f.queue_seq.tail, tails.data(), tails.size())(f.queue_seq.match, none.data(), pk.R);
+    if (kind.pool()) {
+        const wrk::QueueStateCtl sctl{pk.pool_states, pk.pool_entries, pk.nstart, pk.history ? pk.history->dev() : wrk::QueueHistory{}};
+        up(f.queue.start, pk.start.data(), pk.R)(f.queue.save, pk.save.data(), pk.R);
+        up(f.queue_states.turn, pk.turn.data(), pk.nstart)(f.queue_states.ctl, &sctl, 1);
     }
-    if (pk.kind.pool()) {
-        // the turnover list of "step -1": the slots that start at step 0, nothing to save
-        std::vector<wrk::QueueTurn> turn(nstart);
-        for (uint32_t b = 0; b < nstart; ++b) turn[b] = wrk::QueueTurn{b, wrk::QUEUE_NO_ENTRY, 1u, pk.start[b]};
-        const wrk::QueueStateCtl sctl{pk.pool_states, pk.pool_entries, nstart, pk.history ? pk.history->dev() : wrk::QueueHistory{}};
-        up(f.queue_states.start, pk.start.data(), pk.R)(f.queue_states.save, pk.save.data(), pk.R);
-        up(f.queue_states.turn, turn.data(), nstart)(f.queue_states.ctl, &sctl, 1);
-    }
-    if (pk.kind.intake) {       // p_0 of the slots that start at step 0 enters where the request's offset is 0
-        std::vector<uint32_t> take(B, 0u);
-        for (uint32_t b = 0; b < nstart; ++b) take[b] = pk.from[b] == 0u;
-        up(f.queue_intake.flags, take.data(), B)(f.queue_intake.from, pk.from.data(), pk.R);
-    }
+    if (kind.intake) up(f.queue_intake.flags, pk.take.data(), B)(f.queue.from, pk.from.data(), pk.R);
     if (up.rc != WRK_OK) return up.rc;
     // the slots that start a request at step 0 are reset as the step that ends a request resets its slot
     if (pk.kind.pool()) wrk::queue_turnover(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), queue_state_bufs(f, kind), B, ctx->num_cu);
@@ -810,22 +788,23 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         WRK_HIP(ctx, hipMemcpyAsync(top_id.data(), f.logprob.top_ids, top_id.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         WRK_HIP(ctx, hipMemcpyAsync(top_lp.data(), f.logprob.top_logprobs, top_lp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
-    // Mirostat: a request that ended left its mu in alt_mu[r]; one still running has it in its slot's row
+    // Mirostat: a request that ended left its mu in its own entry; one still running (reason 3) has it in its slot's row
+    auto final_of = [](const wrk::QueueLog& g, auto in_slot, auto in_entry) { return g.reason == 3 ? in_slot : in_entry; };
     std::vector<float> mu_req(pk.mu_out ? pk.R : 0);
     std::vector<wrk::SampleAlt> mu_slot(pk.mu_out ? B : 0);
     if (pk.mu_out) {
-        WRK_HIP(ctx, hipMemcpyAsync(mu_req.data(), f.alt.mu, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(mu_req.data(), f.queue.mu, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
         WRK_HIP(ctx, hipMemcpyAsync(mu_slot.data(), f.alt.par, (size_t)B * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost, ctx->stream));
     }
     // constrained: the same two places hold a request's automaton state
     std::vector<uint32_t> gram_req(pk.gram_out ? pk.R : 0), gram_slot(pk.gram_out ? B : 0);
     if (pk.gram_out) {
-        WRK_HIP(ctx, hipMemcpyAsync(gram_req.data(), f.grammar.req, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(gram_req.data(), f.queue.gram, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
         WRK_HIP(ctx, hipMemcpyAsync(gram_slot.data(), f.grammar.state, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     // stop sequences: a request's match word is written by the step that ends it with reason 1, and by nothing else
     std::vector<uint32_t> match(pk.match_out ? pk.R : 0);
-    if (pk.match_out) WRK_HIP(ctx, hipMemcpyAsync(match.data(), f.queue_seq.match, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (pk.match_out) WRK_HIP(ctx, hipMemcpyAsync(match.data(), f.queue.seq_match, (size_t)pk.R * 4, hipMemcpyDeviceToHost, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     size_t o = 0;
     for (uint32_t r = 0; r < pk.R; ++r) {
@@ -837,8 +816,8 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         if (g.length > q.max_new || g.slot >= B || (g.length && (size_t)g.start_step + q.prompt_len - 1 + g.length > steps_run))
             return wrk_fail(ctx, WRK_E_HIP, "request %u: inconsistent queue log (length %u slot %u start %u)", r, g.length, g.slot, g.start_step);
         out->lengths[r] = g.length; out->reasons[r] = g.reason; out->slots[r] = g.slot; out->start_steps[r] = g.start_step;
-        if (pk.mu_out && g.reason != 0) pk.mu_out[r] = g.reason == 3 ? mu_slot[g.slot].mu : mu_req[r];
-        if (pk.gram_out && g.reason != 0) pk.gram_out[r] = g.reason == 3 ? gram_slot[g.slot] : gram_req[r];
+        if (pk.mu_out && g.reason != 0) pk.mu_out[r] = final_of(g, mu_slot[g.slot].mu, mu_req[r]);
+        if (pk.gram_out && g.reason != 0) pk.gram_out[r] = final_of(g, gram_slot[g.slot], gram_req[r]);
         if (pk.match_out) pk.match_out[r] = g.reason == 1 ? match[r] : WRK_STOP_MATCH_NONE;
         // the step that gave the request reason 1 or 2 also wrote its state to its entry (queue_turnover)
         if (pk.saved_out) pk.saved_out[r] = pk.save[r] != wrk::QUEUE_NO_ENTRY && (g.reason == 1 || g.reason == 2);
@@ -889,7 +868,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     const wrk::FrameIo& io = f.io();
     const uint32_t V = f.facts().num_vocab;
     const float* logits = io.head_o;
-    if (kind.dry && (!f.dry.holds({B, 0, V}) || argmax_done)) return wrk_fail(f.ctx, WRK_E_ARG, "DRY rows are not prepared");
+    if (kind.dry && (!f.dry.holds({B, V}) || argmax_done)) return wrk_fail(f.ctx, WRK_E_ARG, "DRY rows are not prepared");
     if (kind.penalized) {
         wrk::penalize_rows(q, io.head_o, V, V, B, f.penalty.par, f.penalty.out, V);
         logits = f.penalty.out;
@@ -903,7 +882,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     }
     // the mask: in place on the penalised or the DRY row, else from head_o into con_o
     if (kind.constrained) {
-        if (!f.grammar.holds({B, 0, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
+        if (!f.grammar.holds({B, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
         float* masked = kind.penalized ? f.penalty.out : kind.dry ? f.dry.out : f.grammar.out;
         wrk::constrain_rows(q, logits, V, V, B, f.grammar.par, masked, V);
         logits = masked;
@@ -1175,7 +1154,9 @@ int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, 
     int32_t rc = wrk_queue_check(ctx, opt, st, B, m->facts().num_vocab, mode_arg, out_arg ? &out : nullptr, pk);
     if (rc == WRK_OK && tail != wrk_step_kind::QUEUE_POOL && opt->history) rc = wrk_fail(ctx, WRK_E_ARG, "a history pool without a state pool");
     if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, m->facts().num_vocab, pk);
-    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), pk.first_tokens.data(), B);
+    if (rc != WRK_OK) return rc;
+    wrk_queue_start(opt, B, pk);
+    rc = wrk_generate_check(ctx, st, m->facts(), pk.first_tokens.data(), B);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     const uint32_t mode = mode_arg & 0xffu;

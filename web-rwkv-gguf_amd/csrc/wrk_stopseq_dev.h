@@ -33,11 +33,6 @@ __device__ __forceinline__ void stop_tail_store(uint32_t* __restrict__ p, const 
     for (uint32_t j = 0; j < STOP_TAIL; ++j) p[j] = a.t[j];
 }
 
-__device__ __forceinline__ void stop_tail_clear(uint32_t* __restrict__ p) {
-#pragma unroll
-    for (uint32_t j = 0; j < STOP_TAIL; ++j) p[j] = WRK_STOP_TAIL_EMPTY;
-}
-
 // The counted draw y of one owner: the match word -- WRK_STOP_MATCH_NONE, WRK_STOP_MATCH_TOKEN (y is one of ids[0 .. nids)) or the index
 // of the matching sequence of `row`; the longest match wins, at equal length the stop-set id beats a sequence and the lower index the
 // higher -- and the tail moved on by y, match or not (the draw that ends an owner counts).  row == nullptr: no sequences
