@@ -456,6 +456,29 @@ int32_t wrk_constrain_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, 
  * u32 [num_rows], in/out; tokens: host u32 [num_rows], each < num_vocab.  Blocking. */
 int32_t wrk_grammar_advance(wrk_ctx* ctx, const wrk_grammar* grammar, uint32_t* states, const uint32_t* tokens, uint32_t num_rows);
 
+/* Logit bias (ai00's `bias`, llama.cpp's --logit-bias, the first link of its sampler chain, vLLM's and the OpenAI interfaces'
+ * logit_bias, whose -100 is -inf here): a wrk_logit_bias is an immutable, device-resident collection of num_sets bias sets over one
+ * vocabulary.  Set s is the pairs (ids[e], values[e]) for e in [set_offsets[s], set_offsets[s + 1]) (num_sets + 1 offsets); the three
+ * arrays are copied, the caller's may go after the call.  1 <= num_sets <= WRK_MAX_BIAS_SETS, num_vocab <= 2^20 (the sampler's limit,
+ * beyond it WRK_E_UNSUPPORTED).  A set may be empty and may have up to num_vocab entries: there is no per-set cap.  WRK_E_ARG before
+ * anything is uploaded: NULL arrays, offsets that do not start at 0 or that decrease, an id >= num_vocab, the same id twice in one set,
+ * a value that is NaN or +inf, and a set that bans every token of the vocabulary -- so a row biased by a set alone is never empty, as
+ * for a grammar. */
+#define WRK_BIAS_NONE 0xFFFFFFFFu
+#define WRK_MAX_BIAS_SETS 65536
+typedef struct wrk_logit_bias wrk_logit_bias;
+int32_t wrk_logit_bias_create(wrk_ctx* ctx, uint32_t num_vocab, uint32_t num_sets, const uint32_t* set_offsets, const uint32_t* ids,
+                              const float* values, wrk_logit_bias** out);
+int32_t wrk_logit_bias_destroy(wrk_logit_bias* bias);
+/* biases f32 logits [num_rows][row_stride] (first num_vocab used) in place: row r with set s = sets[r] gets -inf at every token of s
+ * whose value is -inf, whatever the logit is (a ban is a ban, as the occurrence table's: not x + (-inf), which is NaN for x = +inf),
+ * and x + v, one IEEE f32 addition, at every token of s with a finite value v (NaN stays NaN, +-inf stay +-inf); every other token
+ * keeps its bits, NaN payloads and -0 included, and a row with sets[r] == WRK_BIAS_NONE is left as it is.  sets: host u32 [num_rows],
+ * each < num_sets or WRK_BIAS_NONE (else WRK_E_ARG, as for an object of another context or another num_vocab).  Blocking.  In a
+ * host-side loop it goes in front of wrk_penalize_logits. */
+int32_t wrk_bias_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                        const wrk_logit_bias* bias, const uint32_t* sets);
+
 /* DRY ("don't repeat yourself": text-generation-webui, koboldcpp, llama.cpp's dry_multiplier / dry_base / dry_allowed_length /
  * dry_sequence_breakers) and the hard ban of the same match (Hugging Face's no_repeat_ngram_size), on the device.  Both look at the ORDER
  * of what a sequence generated, which the occurrence table cannot: a token window has num_batch slots (slot b belongs to state slot b),
@@ -583,7 +606,19 @@ int32_t wrk_dry_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, uint32
  * breakers, a breaker >= num_vocab, num_dry_breakers > 0 with dry_breakers NULL, the value ranges of wrk_dry_logits.  The window, the
  * tables and the breakers are device data: one cached step program serves any of them.  Tokens and final windows do not depend on the
  * number of lanes.  If bans, a grammar and the n-gram ban together leave a row with no finite logit, the picked id is unspecified but
- * < num_vocab and nothing faults.  The seven fields sit between out_top_logprobs and grammar. */
+ * < num_vocab and nothing faults.  The seven fields sit between out_top_logprobs and grammar.
+ * Logit bias.  `bias` (NULL: off) makes every pick see its row as wrk_bias_logits leaves it with set bias_set[b] (host u32 [num_batch],
+ * each < num_sets or WRK_BIAS_NONE; NULL: set 0 for every sequence) -- inside the step program.  Order within a step: bias first.  The
+ * biased row is made from the raw head output in a buffer of its own, and everything that read the head output for the pick reads it
+ * instead: penalties, then DRY, then the grammar mask, then the call's pick -- bit for bit the pick of the same call on that row; with
+ * no sampler arrays the arg-max, so this entry point bans and prefers tokens in greedy decoding too.  A penalised, biased token is
+ * (x + v) - t, in that order of rounding.  Log-probs, last_logits and the stop snapshot stay on the raw head output: a banned token may
+ * appear among the alternatives.  The bias has no state: nothing moves from draw to draw and nothing is returned.  WRK_E_ARG before any
+ * launch: bias_set without bias, an object of another context or another num_vocab, a set word that is neither < num_sets nor
+ * WRK_BIAS_NONE.  The object and the set words are device data: one cached step program serves any object and any choice of sets;
+ * biased calls replay step programs of their own, a call with bias NULL exactly the programs it ran before.  Tokens do not depend on
+ * the number of lanes.  If a bias set, bans, a grammar and the n-gram ban together leave a row with no finite logit, the picked id is
+ * unspecified but < num_vocab and nothing faults.  The two fields sit directly behind `occ`: every field behind them keeps its order. */
 #define WRK_MAX_STOP_TOKENS 16
 #define WRK_MAX_STOP_SEQUENCES 8
 #define WRK_MAX_STOP_SEQUENCE_LEN 8
@@ -596,6 +631,8 @@ typedef struct wrk_generate_options {
     const uint32_t *seed;
     const float *presence, *frequency, *decay;
     wrk_occurrence *occ;
+    const wrk_logit_bias *bias;
+    const uint32_t *bias_set;
     const uint32_t *stop_tokens, *stop_offsets;
     uint32_t poll_steps;
     uint32_t num_top;
@@ -707,7 +744,12 @@ int32_t wrk_stop_sequences_advance(wrk_ctx* ctx, uint32_t num_vocab, uint32_t nu
  * arrays) nor `window`.  The offsets are device data: one cached step program serves any of them; intake calls replay step programs of
  * their own, a call with NULL exactly the programs it ran before.  `history` (NULL: off) is the history pool of a call with a state
  * pool, described with wrk_queue_pool below; without a pool (wrk_v7_generate_queue) it is WRK_E_ARG.  The two fields sit between
- * max_steps and num_top: every field behind them keeps its order, the filter fields last. */
+ * max_steps and num_top: every field behind them keeps its order, the filter fields last.
+ * Logit bias, as in wrk_generate_options: one object for the call, bias_set per request (host u32 [num_requests]; NULL: set 0 for
+ * every request).  Request r's rows are biased with set bias_set[r] from the step it is dispatched, at step 0 or at a refill on the
+ * device, and never with what its slot's previous request used; the rows of the steps that feed prompt tokens are biased too, their
+ * draws are discarded as before.  A reply does not depend on the slot or the step the request was scheduled at.  Nothing of the bias
+ * belongs to a state-pool or history-pool entry.  The two fields sit directly behind `occ`. */
 typedef struct wrk_history_pool wrk_history_pool;   /* a history pool beside a state pool: wrk_queue_pool, below */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
@@ -717,6 +759,8 @@ typedef struct wrk_queue_options {
     const uint32_t *seed;
     const float *presence, *frequency, *decay;
     wrk_occurrence *occ;
+    const wrk_logit_bias *bias;
+    const uint32_t *bias_set;
     const wrk_buf *init_state;
     uint32_t poll_steps, max_steps;
     const uint32_t *prompt_context_from;

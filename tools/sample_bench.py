@@ -37,9 +37,14 @@ the step programs differ by the row copy, dry_rows and window_push alone -- for 
 the run-to-run spread of each; and the kernel's worst case: one-step calls whose windows hold 4096 equal tokens (4095 candidates that
 all reach the cap and meet at one token) against one-step calls whose windows hold one token.
 
+An eleventh leg (--logit-bias N): the decode loop with a logit bias of N entries per sequence (every sequence its own set,
+a quarter of the entries bans, the rest uniform in [-4, 4]) against the same loop without a bias -- both through the options entry point
+without stop sets, so the step programs differ by the bias_rows launch alone -- for the greedy and the plain-sampler pick, alternating,
+with the run-to-run spread of each.  Every call starts from the same state.
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
                                  [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9] [--grammar] [--stop-seq]
-                                 [--dry]
+                                 [--dry] [--logit-bias 64]
 
 Prints one JSON object.
 """
@@ -370,6 +375,53 @@ def dry_leg(rt, ctx, first, V, args):
     return res
 
 
+def bias_leg(rt, ctx, first, V, args):
+    """Per pick (greedy, sampled): medians of the per-step time of generate_stop without stop sets, with a bias of args.logit_bias entries
+    per sequence against without, alternating in one process; every call starts from the same state."""
+    import hashlib
+    import wrk
+    B = len(first)
+    rng = np.random.default_rng(args.logit_bias)
+    sets = []
+    for _ in range(B):
+        vals = rng.uniform(-4, 4, args.logit_bias).astype(np.float32)
+        vals[rng.random(args.logit_bias) < 0.25] = -np.inf
+        sets.append((rng.choice(V, args.logit_bias, replace=False), vals))
+    lb = wrk.LogitBias(ctx, V, sets)
+    start = [rt.state_read(b) for b in range(B)]
+
+    def run(pick, **kw):
+        for b in range(B):
+            rt.state_write(start[b], b)
+        tok, _ = rt.generate_stop(first, args.steps, [], poll_steps=POLL_OFF, **pick, **kw)
+        return tok, rt.last_stop_ms / args.steps
+    bkw = dict(logit_bias=lb, bias_set=list(range(B)))
+    res = {}
+    for name, pick in (("greedy", {}), ("sample", dict(temperature=args.temperature, top_p=args.top_p))):
+        want, _ = run(pick)
+        con, _ = run(pick, **bkw)                                          # capture and warm up
+        banned = any(v == -np.inf and t in set(con[:, b].tolist()) for b in range(B) for t, v in zip(*sets[b]))
+        base, with_, same = [], [], True
+        for _ in range(args.reps):
+            tok, ms = run(pick)
+            same &= bool(np.array_equal(tok, want))
+            base.append(ms)
+            tok, ms = run(pick, **bkw)
+            same &= bool(np.array_equal(tok, con))
+            with_.append(ms)
+        bm, wm = float(np.median(base)), float(np.median(with_))
+        res[name] = {"same_tokens_every_rep": same, "banned_token_drawn": bool(banned), "biased_differs_from_plain": bool(not np.array_equal(want, con)),
+                     "without_tokens_sha1": hashlib.sha1(np.ascontiguousarray(want).tobytes()).hexdigest(),
+                     "without_ms_per_step": round(bm, 5), "without_spread_us": round((max(base) - min(base)) * 1e3, 2),
+                     "without_ms_all": [round(x, 5) for x in base],
+                     "with_ms_per_step": round(wm, 5), "with_spread_us": round((max(with_) - min(with_)) * 1e3, 2),
+                     "with_ms_all": [round(x, 5) for x in with_], "with_minus_without_us": round((wm - bm) * 1e3, 2)}
+    for b in range(B):
+        rt.state_write(start[b], b)
+    lb.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -390,6 +442,7 @@ def main():
     ap.add_argument("--grammar", action="store_true", help="the constrained loop against the same loop without a grammar")
     ap.add_argument("--stop-seq", action="store_true", help="the stop-sequence programs against the stop programs and the sampled step")
     ap.add_argument("--dry", action="store_true", help="the loop with a token window and DRY against the same loop without")
+    ap.add_argument("--logit-bias", type=int, default=None, help="entries per set: the loop with a logit bias against the same loop without")
     args = ap.parse_args()
     import wrk
 
@@ -483,6 +536,10 @@ def main():
             out["dry_note"] = ("multiplier 0.8, base 1.75, allowed_length 2, no breakers, windows of 1024 tokens that start empty; a DRY step "
                                "adds three launches to the step program: copy_rows and dry_rows before the pick, window_push in the tail")
             out["batches"][-1]["dry"] = dry_leg(rt, ctx, first, V, args)
+        if args.logit_bias:
+            out["logit_bias_note"] = (f"{args.logit_bias} entries per sequence, every sequence its own set, a quarter bans, the rest uniform in "
+                                      "[-4, 4]; a biased step adds one launch to the step program: bias_rows before everything else")
+            out["batches"][-1]["logit_bias"] = bias_leg(rt, ctx, first, V, args)
     if occ is not None:
         occ.close()
     rt.close()

@@ -251,6 +251,14 @@ void constrain_rows(hipStream_t s, const float* src, uint32_t v, uint32_t src_st
                     uint32_t dst_stride);
 void grammar_advance(hipStream_t s, uint32_t v, uint32_t n, const GrammarParam* par, const uint32_t* tokens, const RowGate& gate);
 
+// wrk_bias.hip: logit bias.  A wrk_logit_bias is one CSR of bias sets, every set sorted by id: set s is the pairs
+// (ids[e], values[e]), e in [offsets[s], offsets[s + 1]).  BiasParam is device data, in a decode loop a per-frame block written before
+// every call: the object's three arrays and the per-row set words (WRK_BIAS_NONE: the row is left alone), so a captured step never holds
+// a pointer of the object.  bias_rows: out row r = in row r with -inf (its bits) at every id of the row's set whose value is -inf,
+// in + value at every other id of the set, the source bits elsewhere; in == out (same stride): in place, only the entries are applied
+struct BiasParam { const uint32_t* offsets; const uint32_t* ids; const float* values; const uint32_t* sets; };
+void bias_rows(hipStream_t s, const float* in, uint32_t v, uint32_t in_stride, uint32_t n, const BiasParam* par, float* out, uint32_t out_stride);
+
 // wrk_dry.hip: DRY and the no-repeat-n-gram ban.  One DryParam per row: the row's slot of a token window -- ring [cap] of
 // ids, meta = (length, next write position) -- and the row's values, pen[m] the host-computed penalty of a match of m tokens (0 below
 // allowed_length).  DryBreakers: the call's breaker ids.  Both are device data, in a decode loop per-frame buffers written before
@@ -408,6 +416,21 @@ struct wrk_grammar {
 // validated start states of n rows (WRK_E_ARG on a NULL grammar, a grammar of another context or another vocabulary, a state >=
 // num_states); state NULL: all 0
 int32_t wrk_grammar_pack(wrk_ctx* ctx, const wrk_grammar* g, const uint32_t* state, uint32_t n, uint32_t V, std::vector<uint32_t>& out);
+
+// include/wrk_hip.h wrk_logit_bias: one allocation holding offsets u32 [num_sets + 1], ids u32 [num_entries] and values f32
+// [num_entries], every set sorted by id
+struct wrk_logit_bias {
+    wrk_ctx* ctx = nullptr;
+    uint32_t num_vocab = 0, num_sets = 0, num_entries = 0;
+    void* mem = nullptr;
+    uint32_t* offsets = nullptr;
+    uint32_t* ids = nullptr;
+    float* values = nullptr;
+    wrk::BiasParam param(const uint32_t* sets) const;
+};
+// validated set words of n rows (WRK_E_ARG on a NULL object, an object of another context or another vocabulary, a word that is neither
+// < num_sets nor WRK_BIAS_NONE); set NULL: all 0
+int32_t wrk_bias_pack(wrk_ctx* ctx, const wrk_logit_bias* lb, const uint32_t* set, uint32_t n, uint32_t V, std::vector<uint32_t>& out);
 
 // include/wrk_hip.h wrk_token_window: one allocation holding the rings u32 [num_batch][capacity] and meta u32 [num_batch][2]
 // (length, next write position)

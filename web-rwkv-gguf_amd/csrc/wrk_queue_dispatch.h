@@ -68,6 +68,8 @@ struct QueueBufs {
     // prompt intake: ctx_from: the index of request r's first prompt token that enters the slot's context; intake: 1 when
     // the token this launch wrote into tokens[b] is such a prompt token (written for every slot by every launch, as started)
     const uint32_t* ctx_from = nullptr; uint32_t* intake = nullptr;
+    // biased queues: the slots' bias set words and request r's (only read: a bias has no state)
+    uint32_t *bias_set = nullptr, *bias_req = nullptr;
 };
 // A state pool under the queue.  QueueTurn: one slot that ended in the step -- `save` the entry its state goes to,
 // `started` / `start` as started[slot] and the entry the slot's next request begins from; QUEUE_NO_ENTRY: none
@@ -84,7 +86,7 @@ struct QueueStateBufs {
 // on steps first_step .. first_step + n - 1 and the draw of the last of them is reply token 0, so the sampler's step base is
 // first_step + n - 1 and reply token j has sampler step j wherever and whenever the request runs.  Writes, through the arrays handed in
 // and nothing else: the slot record, p_0, the intake flag, the slot's sampler / filter / alt rows (mu from alt_mu[r]), its automaton
-// state, the values and table of its DRY row, an empty stop tail, the three values of its penalty row, the request's log entry and,
+// state, its bias set word, the values and table of its DRY row, an empty stop tail, the three values of its penalty row, the request's log entry and,
 // with a pool, turn[turn_at] = {b, save, 1, start[r]}.  The slot's own pointers -- occurrence row, window ring / meta / cap -- are never
 // written.  Returns whether the caller is to set the slot's window to length 0 (the two words behind DryParam::meta): with a window,
 // unless a history pool's turnover sets it
@@ -96,6 +98,7 @@ WRK_HD inline bool queue_dispatch(const QueueBufs& Q, uint32_t* tokens, uint32_t
     if (Q.filter_par) Q.filter_par[b] = SampleFilter{q->top_k, q->ln_min_p};
     if (Q.alt_par) Q.alt_par[b] = SampleAlt{q->tau, q->eta, Q.alt_mu ? Q.alt_mu[r] : 0.0f, q->typical_p};
     if (Q.gram_req) Q.gram_state[b] = Q.gram_req[r];
+    if (Q.bias_req) Q.bias_set[b] = Q.bias_req[r];
     if (Q.dry_par) {
         DryParam* dp = Q.dry_par + b;
         const DryParam* dq = Q.dry_req + r;

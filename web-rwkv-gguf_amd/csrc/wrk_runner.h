@@ -106,6 +106,9 @@ struct wrk_step_kind {
     bool intake = false;
     // a QUEUE_POOL tail with a history pool: queue_history_turnover in the place of the occurrence reset
     bool history = false;
+    // logit bias (wrk_bias.hip): in front of everything else, bias_rows makes bias.out = head_o biased with the rows' sets of
+    // bias.par, and the penalise, the DRY copy, the mask and the pick read it where they read head_o; log-probs keep head_o
+    bool biased = false;
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
     bool mirostat() const { return pick == MIROSTAT; }
@@ -120,9 +123,9 @@ struct wrk_step_kind {
                (uint32_t)constrained << 31;
     }
     // The kind's bits of GraphKey::mode2, the word that takes what key() has no room for: stop sequences 0, DRY 1, prompt intake 2,
-    // history 3.  0 for every kind that existed before the word did, and bit 0 alone for every stop-sequence kind, so their keys compare
+    // history 3, biased 4.  0 for every kind that existed before the word did, and bit 0 alone for every stop-sequence kind, so their keys compare
     // as they always have
-    uint32_t key2() const { return (uint32_t)stop_seqs | (uint32_t)dry << 1 | (uint32_t)intake << 2 | (uint32_t)history << 3; }
+    uint32_t key2() const { return (uint32_t)stop_seqs | (uint32_t)dry << 1 | (uint32_t)intake << 2 | (uint32_t)history << 3 | (uint32_t)biased << 4; }
 };
 
 // ------------------------------------------------------------------ the buffer groups of a frame (Pieces of wrk_dev_group)
@@ -162,6 +165,16 @@ struct wrk_grammar_bufs {
     uint32_t* state = nullptr;
     float* out = nullptr;
     void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, sizeof(wrk::GrammarParam)); c.take(state, d[0] * 4); c.take(out, d[0] * d[1] * 4); }
+};
+// logit bias (wrk_bias.hip).  par: the parameter block (the object's arrays and `set`: one program serves any object and any
+// choice of sets); set: the sequences' set words; out [B][V]: the biased head output
+struct wrk_bias_bufs {
+    static constexpr int DIMS = 2;              // sequences, vocabulary
+    static constexpr unsigned EXACT = 2;
+    wrk::BiasParam* par = nullptr;
+    uint32_t* set = nullptr;
+    float* out = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, sizeof(wrk::BiasParam)); c.take(set, d[0] * 4); c.take(out, d[0] * d[1] * 4); }
 };
 // DRY / the n-gram ban (wrk_dry.hip).  par: the sequences' DryParam rows (window slot, values, penalty table: one program
 // serves any window and any parameters); brk: the call's breaker ids; out [B][V]: the copy of the head output that a pick without
@@ -222,7 +235,7 @@ struct wrk_seq_bufs {
 };
 // generate_queue (wrk_queue.hip): slot records and started flags [slots], the control words, the prompt token pool [pool
 // tokens] and everything of a request [requests], the only group with that dimension: the table and the log, and what a request carries
-// for the call's features, used or not -- its mu, automaton state, DRY values, stop sequences and match word, intake offset, pool entries
+// for the call's features, used or not -- its mu, automaton state, bias set word, DRY values, stop sequences and match word, intake offset, pool entries
 struct wrk_queue_bufs {
     static constexpr int DIMS = 3;              // slots, requests, pool tokens
     static constexpr unsigned EXACT = 0;
@@ -235,13 +248,14 @@ struct wrk_queue_bufs {
     float* mu = nullptr;
     wrk::DryParam* dry = nullptr;
     wrk::StopSeqRow* seq_rows = nullptr;
-    uint32_t *gram = nullptr, *seq_match = nullptr, *from = nullptr;
+    uint32_t *gram = nullptr, *seq_match = nullptr, *from = nullptr, *bias = nullptr;
     uint32_t *start = nullptr, *save = nullptr; // one piece: save == start + request cap
     void layout(wrk_dev_cut& c, const size_t* d) {
         c.take(slots, d[0] * sizeof(wrk::QueueSlot)); c.take(started, d[0] * 4); c.take(ctl, sizeof(wrk::QueueCtl));
         c.take(reqs, d[1] * sizeof(wrk::QueueReq)); c.take(log, d[1] * sizeof(wrk::QueueLog)); c.take(pool, d[2] * 4);
         c.take(mu, d[1] * 4); c.take(gram, d[1] * 4); c.take(dry, d[1] * sizeof(wrk::DryParam));
         c.take(seq_rows, d[1] * sizeof(wrk::StopSeqRow)); c.take(seq_match, d[1] * 4); c.take(from, d[1] * 4); c.take(start, 2 * d[1] * 4);
+        c.take(bias, d[1] * 4);
         save = start ? start + d[1] : nullptr;
     }
     uint32_t* live() const { return &ctl->live; }
@@ -321,6 +335,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_rows_bufs<wrk::SampleAlt>> alt;
     wrk_dev_group<wrk_penalty_bufs> penalty;
     wrk_dev_group<wrk_grammar_bufs> grammar;
+    wrk_dev_group<wrk_bias_bufs> bias;
     wrk_dev_group<wrk_dry_bufs> dry;
     wrk_dev_group<wrk_score_bufs> score;
     wrk_dev_group<wrk_stop_bufs> stop;
@@ -331,7 +346,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_queue_intake_bufs> queue_intake;
     wrk_dev_group<wrk_logprob_bufs> logprob;
     template <class F> void each_group(F&& f) {     // the one list of the groups
-        f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
+        f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(bias); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
         f(queue_states); f(queue_intake); f(logprob);
     }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
@@ -379,7 +394,8 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
 // the ABI's pick arrays, of wrk_generate_options / wrk_queue_options (wrk_pick_of) or of an entry point's own arguments, validated in
 // one place (WRK_E_ARG): all three sampler arrays or none (the arg-max); penalty arrays only with a table; a table, a filter, Mirostat
 // or typical only with the sampler arrays; one family of filter / Mirostat / typical per call; grammar_state only with a grammar (which
-// any pick may have); the DRY arrays only with a token window (which any pick may have), its values in their ranges.  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
+// any pick may have); bias_set only with a logit bias (which any pick may have); the DRY arrays only with a token window (which any pick
+// may have), its values in their ranges.  need: what the entry point requires -- SAMPLER: the sampler arrays (generate_sample), TABLE: also the occurrence table (generate_penalized)
 struct wrk_pick_args {
     const float *temperature = nullptr, *top_p = nullptr; const uint32_t* seed = nullptr;
     const float *presence = nullptr, *frequency = nullptr, *decay = nullptr; wrk_occurrence* occ = nullptr;
@@ -388,12 +404,14 @@ struct wrk_pick_args {
     const float* typical_p = nullptr;                                   // set: a typical pick
     const wrk_grammar* grammar = nullptr; uint32_t* grammar_state = nullptr;    // grammar set: a constrained pick; grammar_state: in / out
     wrk_dry_args dry;                                                   // window set: a DRY pick
+    const wrk_logit_bias* bias = nullptr; const uint32_t* bias_set = nullptr;   // bias set: a biased pick; bias_set: only read
     enum Need { ANY, SAMPLER, TABLE } need = ANY;
 };
 template <class Options> wrk_pick_args wrk_pick_of(const Options& o) {
     return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p,
             o.mirostat_tau, o.mirostat_eta, o.mirostat_mu, o.typical_p, o.grammar, o.grammar_state,
-            wrk_dry_args{o.window, o.dry_multiplier, o.dry_base, o.dry_allowed_length, o.no_repeat_ngram, o.dry_breakers, o.num_dry_breakers}};
+            wrk_dry_args{o.window, o.dry_multiplier, o.dry_base, o.dry_allowed_length, o.no_repeat_ngram, o.dry_breakers, o.num_dry_breakers},
+            o.bias, o.bias_set};
 }
 // the log-prob outputs of a call (wrk_generate_options / wrk_queue_options); logprob NULL: off
 struct wrk_logprob_call {
@@ -401,9 +419,10 @@ struct wrk_logprob_call {
     bool on() const { return logprob != nullptr; }
 };
 bool wrk_no_graph();        // WRK_NO_GRAPH=1: the decode loops enqueue every step instead of replaying a program
-// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the penalise launch (penalised), the DRY
+// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the bias launch (biased: what follows reads
+// its output where it read head_o), the penalise launch (penalised), the DRY
 // launches (dry: the row copy unless penalised, then dry_rows), the mask launch (constrained), the arg-max or sampler launch on the resulting row and the frame's parameters at step *counter -- neither with
-// `argmax_done`: the head launch has left the arg-max in io().argmax (RWKV-7's fused greedy head, never in a constrained or a DRY step) -- with
+// `argmax_done`: the head launch has left the arg-max in io().argmax (RWKV-7's fused greedy head, never in a constrained, a DRY or a biased step) -- with
 // kind.logprobs the log-prob launches on head_o (never pen_o) and io().argmax into row
 // *counter of the frame's log-prob buffers, then the tail: the occurrence update (penalised), the automaton advance (constrained) and the window push (dry) that belong to it, its advance of
 // tokens / history / counter, and stop_snapshot / queue_reset / queue_turnover

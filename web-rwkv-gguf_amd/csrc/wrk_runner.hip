@@ -161,6 +161,8 @@ struct wrk_pick_params {    // validated rows; empty: the arg-max / without pena
     std::vector<wrk::SampleAlt> alt;        // Mirostat / typical rows
     const wrk_grammar* grammar = nullptr;   // a constrained pick: the automaton and the state every row starts in
     std::vector<uint32_t> gram_state;
+    const wrk_logit_bias* bias = nullptr;   // a biased pick: the object and every row's set word
+    std::vector<uint32_t> bias_set;
     bool has_dry = false;                   // a DRY pick: the rows' window slots, values and tables, and the call's breakers
     std::vector<wrk::DryParam> dry;
     wrk::DryBreakers brk{};
@@ -189,6 +191,13 @@ static int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, u
         const int32_t grc = wrk_grammar_pack(ctx, a.grammar, a.grammar_state, n, V, out.gram_state);
         if (grc != WRK_OK) return grc;
         out.grammar = a.grammar;
+    }
+    WRK_ARG(ctx, a.bias || !a.bias_set, "bias_set without bias");
+    kind.biased = a.bias != nullptr;
+    if (kind.biased) {
+        const int32_t brc = wrk_bias_pack(ctx, a.bias, a.bias_set, n, V, out.bias_set);
+        if (brc != WRK_OK) return brc;
+        out.bias = a.bias;
     }
     WRK_ARG(ctx, a.dry.window || !a.dry.any_array(), "dry_* / no_repeat_ngram arrays without a token window");
     kind.dry = a.dry.window != nullptr;
@@ -378,6 +387,7 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     if (rc == WRK_OK && alt) rc = f.grow(f.alt, {B});
     if (rc == WRK_OK && pen) rc = f.grow(f.penalty, {B, V});
     if (rc == WRK_OK && rows.grammar) rc = f.grow(f.grammar, {B, V});
+    if (rc == WRK_OK && rows.bias) rc = f.grow(f.bias, {B, V});
     if (rc == WRK_OK && rows.has_dry) rc = f.grow(f.dry, {B, V});
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
@@ -391,6 +401,10 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     if (rows.grammar) {
         const wrk::GrammarParam gp = rows.grammar->param(f.grammar.state);
         up(f.grammar.par, &gp, 1)(f.grammar.state, rows.gram_state.data() + b0, B);
+    }
+    if (rows.bias) {
+        const wrk::BiasParam bp = rows.bias->param(f.bias.set);
+        up(f.bias.par, &bp, 1)(f.bias.set, rows.bias_set.data() + b0, B);
     }
     if (rows.has_dry) {
         up(f.dry.par, rows.dry.data() + b0, B)(f.dry.brk, &rows.brk, 1);
@@ -457,6 +471,7 @@ struct wrk_queue_pack {
     float* mu_out = nullptr;    // Mirostat: the options' mirostat_mu, or nullptr
     std::vector<uint32_t> gram; // constrained: [R] the automaton state every request starts in
     uint32_t* gram_out = nullptr;   // the options' grammar_state, or nullptr
+    std::vector<uint32_t> bias; // biased: [R] the requests' set words
     std::vector<wrk::DryParam> dry; // DRY: [R] the requests' rows (values and tables; a slot's row keeps its own window pointers)
     wrk_token_window* window = nullptr;
     wrk_stopseq_pack seq;      // stop sequences: [R] the requests' rows (the tails: every slot starts empty)
@@ -525,6 +540,7 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     for (uint32_t r = 0; r < R && kind.alt(); ++r) pk.mu.push_back(req.alt[r].mu);
     pk.mu_out = kind.mirostat() ? opt->mirostat_mu : nullptr;
     if (kind.constrained) { pk.gram = req.gram_state; pk.gram_out = opt->grammar_state; pk.rows.grammar = req.grammar; }
+    if (kind.biased) { pk.bias = req.bias_set; pk.rows.bias = req.bias; }
     if (kind.dry) { pk.dry = req.dry; pk.window = opt->window; pk.rows.has_dry = true; pk.rows.brk = req.brk; }
     return WRK_OK;
 }
@@ -591,7 +607,8 @@ static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) 
                           kind.dry ? f.dry.par : nullptr, kind.dry ? f.queue.dry : nullptr,
                           kind.stop_seqs ? f.queue.seq_rows : nullptr, kind.stop_seqs ? f.queue_seq.tail : nullptr,
                           kind.stop_seqs ? f.queue.seq_match : nullptr,
-                          kind.intake ? f.queue.from : nullptr, kind.intake ? f.queue_intake.flags : nullptr};
+                          kind.intake ? f.queue.from : nullptr, kind.intake ? f.queue_intake.flags : nullptr,
+                          kind.biased ? f.bias.set : nullptr, kind.biased ? f.queue.bias : nullptr};
 }
 
 static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
@@ -599,7 +616,7 @@ static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f, wrk_step_
 }
 
 // The host's step 0, after the checks.  Every slot gets valid rows, which an idle slot (b >= R) keeps -- a valid token, state 0, which
-// every grammar has -- with the pointers that are the slot's whatever request it serves: row b of the occurrence table, slot b of the
+// every grammar has, no bias set -- with the pointers that are the slot's whatever request it serves: row b of the occurrence table, slot b of the
 // window.  Then the dispatch rule deals request b to slot b < min(B, R) with first_step 0, over host mirrors of the device's arrays
 static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_pack& pk) {
     const wrk_step_kind kind = pk.kind;
@@ -609,6 +626,7 @@ static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_
     if (kind.filtered()) rows.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
     if (kind.alt()) rows.alt.assign(B, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
     if (kind.constrained) rows.gram_state.assign(B, 0u);
+    if (kind.biased) rows.bias_set.assign(B, WRK_BIAS_NONE);
     for (uint32_t b = 0; b < B && kind.penalized; ++b) rows.pen.push_back(opt->occ->row(b, 0.0f, 0.0f, 1.0f));
     for (uint32_t b = 0; b < B && kind.dry; ++b) {
         rows.dry.push_back(pk.dry[0]);
@@ -625,7 +643,7 @@ static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_
     auto at = [](auto& v) { return v.empty() ? nullptr : v.data(); };
     const wrk::QueueBufs Q{pk.slots.data(), pk.reqs.data(), pk.pool.data(), pk.log.data(), nullptr, nullptr, at(rows.par), at(rows.pen), at(rows.filt),
                            at(rows.alt), kind.mirostat() ? pk.mu.data() : nullptr, at(rows.gram_state), at(pk.gram), at(rows.dry), at(pk.dry),
-                           at(pk.seq.rows), at(pk.tails), nullptr, at(pk.from), at(pk.take)};
+                           at(pk.seq.rows), at(pk.tails), nullptr, at(pk.from), at(pk.take), at(rows.bias_set), at(pk.bias)};
     const wrk::QueueStateBufs P{pk.start.data(), pk.save.data(), nullptr, pk.turn.data(), kind.history};
     for (uint32_t b = 0; b < pk.nstart; ++b)
         if (wrk::queue_dispatch(Q, pk.first_tokens.data(), b, b, 0u, kind.pool() ? &P : nullptr, b)) pk.wipe = b + 1;
@@ -669,6 +687,7 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     up(f.queue.pool, pk.pool.data(), pk.pool.size())(f.queue.ctl, &ctl, 1);
     if (kind.mirostat()) up(f.queue.mu, pk.mu.data(), pk.R);
     if (kind.constrained) up(f.queue.gram, pk.gram.data(), pk.R);
+    if (kind.biased) up(f.queue.bias, pk.bias.data(), pk.R);
     if (kind.dry) up(f.queue.dry, pk.dry.data(), pk.R);
     // a slot that starts a request at step 0 begins with an empty window, as a refilled slot does
     const std::vector<uint32_t> empty((size_t)pk.wipe * 2, 0u);
@@ -869,18 +888,24 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
     const uint32_t V = f.facts().num_vocab;
     const float* logits = io.head_o;
     if (kind.dry && (!f.dry.holds({B, V}) || argmax_done)) return wrk_fail(f.ctx, WRK_E_ARG, "DRY rows are not prepared");
+    // the bias first: the biased copy of head_o (which log-probs, last_logits and the stop snapshot keep raw) is what the rest reads
+    if (kind.biased) {
+        if (!f.bias.holds({B, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "bias rows are not prepared");
+        wrk::bias_rows(q, io.head_o, V, V, B, f.bias.par, f.bias.out, V);
+        logits = f.bias.out;
+    }
     if (kind.penalized) {
-        wrk::penalize_rows(q, io.head_o, V, V, B, f.penalty.par, f.penalty.out, V);
+        wrk::penalize_rows(q, logits, V, V, B, f.penalty.par, f.penalty.out, V);
         logits = f.penalty.out;
     }
-    // DRY: in place on the penalised row, else on a copy of head_o (which log-probs, last_logits and the stop snapshot keep raw)
+    // DRY: in place on the penalised row, else on a copy of the biased row or of head_o
     if (kind.dry) {
         float* rows = kind.penalized ? f.penalty.out : f.dry.out;
-        if (!kind.penalized) wrk::copy_rows(q, io.head_o, V, V, B, rows, V);
+        if (!kind.penalized) wrk::copy_rows(q, logits, V, V, B, rows, V);
         wrk::dry_rows(q, rows, V, V, B, f.dry.par, f.dry.brk, f.dry.scratch);
         logits = rows;
     }
-    // the mask: in place on the penalised or the DRY row, else from head_o into con_o
+    // the mask: in place on the penalised or the DRY row, else from the biased row or head_o into grammar.out
     if (kind.constrained) {
         if (!f.grammar.holds({B, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
         float* masked = kind.penalized ? f.penalty.out : kind.dry ? f.dry.out : f.grammar.out;

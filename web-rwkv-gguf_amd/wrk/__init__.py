@@ -75,7 +75,7 @@ class GenerateOptions(C.Structure):
     """wrk_generate_options: the pick (sampler arrays all NULL: arg-max; occ NULL: no penalties), the stop sets (CSR) and the log-prob
     outputs (out_logprob NULL: off) of wrk_v*_generate_stop."""
     _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
-                ("occ", _P), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
+                ("occ", _P), ("bias", _P), ("bias_set", _u32p), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
                 ("window", _P), ("dry_multiplier", _f32p), ("dry_base", _f32p), ("dry_allowed_length", _u32p), ("no_repeat_ngram", _u32p),
                 ("dry_breakers", _u32p), ("num_dry_breakers", C.c_uint32),
@@ -91,7 +91,7 @@ class QueueOptions(C.Structure):
     prefix state, the polled loop's block size and step cap and the log-prob outputs (out_logprob NULL: off) of wrk_v*_generate_queue."""
     _fields_ = [("num_requests", C.c_uint32), ("prompt_tokens", _u32p), ("prompt_offsets", _u32p), ("max_new", _u32p),
                 ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p),
-                ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("init_state", _P),
+                ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("bias", _P), ("bias_set", _u32p), ("init_state", _P),
                 ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32), ("prompt_context_from", _u32p),
                 ("history", _P),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
@@ -125,6 +125,8 @@ STOP_MATCH_TOKEN = 0xFFFFFFFE   # WRK_STOP_MATCH_TOKEN
 QUEUE_NO_ENTRY = 0xFFFFFFFF     # WRK_QUEUE_NO_ENTRY
 GRAMMAR_REJECT = 0xFFFF         # WRK_GRAMMAR_REJECT
 MAX_TOKEN_CLASSES = 8192        # WRK_MAX_TOKEN_CLASSES
+BIAS_NONE = 0xFFFFFFFF          # WRK_BIAS_NONE
+MAX_BIAS_SETS = 65536           # WRK_MAX_BIAS_SETS
 MAX_TOKEN_WINDOW = 4096         # WRK_MAX_TOKEN_WINDOW
 MAX_DRY_BREAKERS = 16           # WRK_MAX_DRY_BREAKERS
 DRY_MAX_MATCH = 50              # WRK_DRY_MAX_MATCH
@@ -229,6 +231,9 @@ HIP_SYMBOLS = {
     "wrk_grammar_destroy": (C.c_int32, [_P]),
     "wrk_constrain_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _u32p]),
     "wrk_grammar_advance": (C.c_int32, [_P, _P, _u32p, _u32p, C.c_uint32]),
+    "wrk_logit_bias_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p, C.POINTER(_P)]),
+    "wrk_logit_bias_destroy": (C.c_int32, [_P]),
+    "wrk_bias_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _u32p]),
     "wrk_token_window_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "wrk_token_window_destroy": (C.c_int32, [_P]),
     "wrk_token_window_add": (C.c_int32, [_P, _P, C.c_uint32, _u32p, C.c_uint32]),
@@ -490,6 +495,37 @@ def _fill_grammar(opt, n: int, keep: list, grammar, grammar_state):
     keep.append(st)
     opt.grammar, opt.grammar_state = grammar.h, _ptr(st, _u32p)
     return st
+
+
+def _fill_bias(opt, n: int, keep: list, logit_bias, bias_set):
+    """The bias fields of a GenerateOptions or QueueOptions for n rows: bias_set a scalar or one set index per row (BIAS_NONE: the row
+    is left alone); None: set 0 for every row.  The array goes into `keep`."""
+    if logit_bias is None:
+        if bias_set is not None:
+            raise ValueError("bias_set without logit_bias")
+        return
+    opt.bias = logit_bias.h
+    if bias_set is not None:
+        keep.append(_per_row(bias_set, n, np.uint32))
+        opt.bias_set = _ptr(keep[-1], _u32p)
+
+
+def _bias_csr(sets):
+    """(offsets u32 [S + 1], ids u32 [E], values f32 [E]) of a list of bias sets, each a {token: value} dict or an (ids, values) pair;
+    what `LogitBias` hands to the library, which validates it."""
+    off, ids, vals = [0], [], []
+    for st in sets:
+        i, v = (list(st.keys()), list(st.values())) if isinstance(st, dict) else st
+        i, v = np.asarray(i, np.int64).reshape(-1), np.asarray(v, np.float32).reshape(-1)
+        if i.size != v.size:
+            raise ValueError(f"a bias set of {i.size} ids and {v.size} values")
+        if i.size and (i.min() < 0 or i.max() > 0xFFFFFFFF):
+            raise ValueError("a bias id outside [0, 2^32)")
+        ids.append(i.astype(np.uint32))
+        vals.append(v)
+        off.append(off[-1] + i.size)
+    cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else [], dt)
+    return np.asarray(off, np.uint32), cat(ids, np.uint32), cat(vals, np.float32)
 
 
 def _grammar_tables(num_vocab: int, token_class, transitions):
@@ -764,6 +800,27 @@ class Context:
         self.check(hip.wrk_constrain_logits(self.h, buf.h, V, stride, n, grammar.h, _ptr(st, _u32p)))
         return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
 
+    def bias_logits(self, logits, lb: "LogitBias", sets, num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
+        """Biases rows of logits on the device: row r gets -inf at every token its set bans (value -inf), x + v at every
+        other token of the set and keeps the bits of the rest; a row with BIAS_NONE is left alone.  `logits`: an [n, V] f32 array
+        (returns the biased copy), or a `Buffer` of n rows of `row_stride` f32 (first `num_vocab` used), biased in place (returns
+        None).  sets: a scalar or one set index per row.  In a host loop it goes in front of `penalize_logits`."""
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            stride = int(row_stride or V)
+            n = (buf.nbytes // 4 - V) // stride + 1 if buf.nbytes >= 4 * V else 0
+            a = None
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            n, V = a.shape
+            stride = V
+            buf = self.buffer(a)
+        st = _per_row(sets, n, np.uint32)
+        self.check(hip.wrk_bias_logits(self.h, buf.h, V, stride, n, lb.h, _ptr(st, _u32p)))
+        return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
+
     def stop_sequences_advance(self, tails, tokens, stop_sequences, stop=None, num_vocab: Optional[int] = None):
         """One counted draw of the stop-sequence matcher on the device (wrk_stop_sequences_advance) for n rows: row r has the
         tail tails[r] (STOP_TAIL_LEN entries, oldest first, STOP_TAIL_EMPTY where there is none), the drawn token tokens[r], the stop
@@ -843,6 +900,36 @@ class TokenWindow:
     def close(self):
         if self.h and self.ctx.h:
             hip.wrk_token_window_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LogitBias:
+    """Bias sets for the decode loops, on the device and immutable: `sets` is a list of {token: value} dicts or of
+    (ids, values) pairs over one vocabulary; a value of -inf bans the token, a finite one is added to its logit, NaN and +inf are
+    refused, as is a set that bans the whole vocabulary.  Pass it to the decode loops as `logit_bias=`, with `bias_set=` the index of
+    the set each sequence or request uses (BIAS_NONE: none)."""
+
+    NONE = BIAS_NONE
+
+    def __init__(self, ctx: Context, num_vocab: int, sets):
+        off, ids, vals = _bias_csr(sets)
+        self.num_vocab, self.num_sets = int(num_vocab), int(off.size - 1)
+        h = _P()
+        if ids.size == 0:       # no entry at all: the arrays must still be there
+            ids, vals = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+        ctx.check(hip.wrk_logit_bias_create(ctx.h, self.num_vocab, self.num_sets, _ptr(off, _u32p), _ptr(ids, _u32p), _ptr(vals, _f32p),
+                                            C.byref(h)))
+        self.ctx, self.h = ctx, h
+
+    def close(self):
+        if self.h and self.ctx.h:
+            hip.wrk_logit_bias_destroy(self.h)
         self.h = None
 
     def __del__(self):
@@ -1509,7 +1596,8 @@ class Runtime:
         return (out, ms.value, logits) if want_logits else (out, ms.value)
 
     def generate_greedy(self, first_tokens, steps: int, mode: int = 1, want_logits: bool = False, groups: int = 1, logprobs=None,
-                        grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
+                        grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
+                        logit_bias: "LogitBias" = None, bias_set=None):
         """Device-resident greedy loop; returns (tokens [steps, B], elapsed_ms[, last logits [B, V]]).
         groups > 1 (RWKV-7): the B independent sequences are dealt over that many concurrent pipelines (each a contiguous block of
         sequences with its own frame, decode program and HIP stream) instead of one batched step.
@@ -1525,11 +1613,15 @@ class Runtime:
         `Context.dry_logits` leaves it with the sequence's slot of the `TokenWindow` -- the token that would extend a verbatim repeat
         is penalised, or with no_repeat_ngram banned -- and every draw is pushed into that slot, on the device.  Scalars or one value
         per sequence; a window alone only records the draws.  Greedy with DRY is the deterministic "no loops" mode.  Such a call goes
-        through the options entry point and replays step programs of its own."""
-        if any(v is not None for v in (logprobs, grammar, grammar_state, window, dry, no_repeat_ngram, dry_breakers)):
+        through the options entry point and replays step programs of its own.
+        logit_bias / bias_set (a scalar or one set index per sequence; None: set 0; BIAS_NONE: none): every pick sees
+        its row as `Context.bias_logits` leaves it with the sequence's set of the `LogitBias` -- banned tokens at -inf, the others of
+        the set shifted -- before penalties, DRY and the grammar; log-probs and last logits stay raw.  Greedy with a bias bans and
+        prefers tokens without a sampler.  Such a call goes through the options entry point and replays step programs of its own."""
+        if any(v is not None for v in (logprobs, grammar, grammar_state, window, dry, no_repeat_ngram, dry_breakers, logit_bias, bias_set)):
             return self._generate_filtered(first_tokens, steps, None, None, None, None, 0.0, 0.0, 1.0, None, None, mode, want_logits, groups,
                                            logprobs, grammar=grammar, grammar_state=grammar_state,
-                                           dry_args=(window, dry, no_repeat_ngram, dry_breakers))
+                                           dry_args=(window, dry, no_repeat_ngram, dry_breakers), bias_args=(logit_bias, bias_set))
         return self._generate("greedy", first_tokens, steps, (), mode, groups, want_logits)
 
     def _generate_options(self, first_tokens, steps, opt, keep, mode, want_logits, logprobs=None):
@@ -1563,7 +1655,8 @@ class Runtime:
 
     def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
                         groups: int = 1, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
-                        grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
+                        grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
+                        logit_bias: "LogitBias" = None, bias_set=None):
         """As `generate_greedy`, each sequence's next token drawn by `Sampler::sample` (examples/chat.rs:150-190) on the device with its
         own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b.
         top_k / min_p (a scalar or one value per sequence; None: off): the draw is `sample_logits(..., top_k, min_p)`'s; such a call goes
@@ -1575,23 +1668,25 @@ class Runtime:
         sequence): locally typical sampling.  One family per call (top_k / min_p, mirostat, typical_p); such a call goes through the
         options entry point and replays step programs of its own.
         grammar / grammar_state: as `generate_greedy`; the draw is the same sampler's on the masked row.
-        window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`; the draw is the same sampler's on the changed row."""
+        window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`; the draw is the same sampler's on the changed row.
+        logit_bias / bias_set: as `generate_greedy`; the draw is the same sampler's on the biased row."""
         if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state, window, dry,
-                                       no_repeat_ngram, dry_breakers)):
+                                       no_repeat_ngram, dry_breakers, logit_bias, bias_set)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
                                            want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
-                                           (window, dry, no_repeat_ngram, dry_breakers))
+                                           (window, dry, no_repeat_ngram, dry_breakers), (logit_bias, bias_set))
         keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
         return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
 
     def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
                            want_logits, groups, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar=None,
-                           grammar_state=None, dry_args=(None, None, None, None)):
+                           grammar_state=None, dry_args=(None, None, None, None), bias_args=(None, None)):
         opt, keep = GenerateOptions(), []
         mu = _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
                         mirostat, mirostat_mu, typical_p)
         gs = _fill_grammar(opt, _u32(first_tokens).size, keep, grammar, grammar_state)
         _fill_dry(opt, _u32(first_tokens).size, keep, *dry_args)
+        _fill_bias(opt, _u32(first_tokens).size, keep, *bias_args)
         out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits, logprobs)
         self.last_mirostat_mu = mu
         self.last_grammar_state = gs
@@ -1600,7 +1695,8 @@ class Runtime:
 
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
                            frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1, top_k=None, min_p=None,
-                           logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
+                           logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
+                           logit_bias: "LogitBias" = None, bias_set=None):
         """As `generate_sample`, each draw made on the logits penalised with the sequence's slot of `occurrence` (ChatRWKV's
         alpha_presence / alpha_frequency / token_ban), and the slot updated after every draw (count *= decay, then the drawn token's
         weight added).  The first token of a call is not counted; the last drawn one is.  The table carries over between calls.
@@ -1609,12 +1705,13 @@ class Runtime:
         token may appear among the alternatives).  mirostat / mirostat_mu / typical_p: as `generate_sample`, the pick made on the
         penalised logits.  grammar / grammar_state: as `generate_greedy`, the mask applied to the penalised logits; bans belong in the
         grammar (a row that bans and automaton together leave empty draws an unspecified token, which the automaton rejects).
-        window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`, applied to the penalised logits, before the grammar."""
+        window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`, applied to the penalised logits, before the grammar.
+        logit_bias / bias_set: as `generate_greedy`; the penalties are applied to the biased logits: a token is (x + v) - penalty."""
         if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state, window, dry,
-                                       no_repeat_ngram, dry_breakers)):
+                                       no_repeat_ngram, dry_breakers, logit_bias, bias_set)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
                                            min_p, mode, want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
-                                           (window, dry, no_repeat_ngram, dry_breakers))
+                                           (window, dry, no_repeat_ngram, dry_breakers), (logit_bias, bias_set))
         B = _u32(first_tokens).size
         keep, rows = self._sampler_rows(B, temperature, top_p, seed)
         pen = [_per_row(v, B, np.float32) for v in (presence, frequency, decay)]
@@ -1624,7 +1721,8 @@ class Runtime:
     def generate_stop(self, first_tokens, steps: int, stop, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
                       poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
-                      grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, stop_tail=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None):
+                      grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, stop_tail=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
+                      logit_bias: "LogitBias" = None, bias_set=None):
         """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
         at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
         MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
@@ -1645,7 +1743,8 @@ class Runtime:
         far, so that a stop sequence that straddles two calls still ends the reply; `last_stop_tail` holds the tails after this call.
         Both are None after a call without stop_sequences, which runs exactly the step programs it ran before.
         window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`; slot b of the window has taken exactly lengths[b] pushes,
-        the stop token's included: the window freezes with the sequence."""
+        the stop token's included: the window freezes with the sequence.
+        logit_bias / bias_set: as `generate_greedy`; the tokens are a prefix of those of the call without stops."""
         ft = _u32(first_tokens)
         ids, off = _stop_csr(stop, ft.size, "sequences")
         opt, keep = GenerateOptions(), []
@@ -1660,6 +1759,7 @@ class Runtime:
                                            mirostat, mirostat_mu, typical_p)
         self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
         _fill_dry(opt, ft.size, keep, window, dry, no_repeat_ngram, dry_breakers)
+        _fill_bias(opt, ft.size, keep, logit_bias, bias_set)
         opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
         out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, self._mode(mode, groups), want_logits,
                                                                               logprobs)
@@ -1670,7 +1770,7 @@ class Runtime:
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
                        mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None,
                        mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
-                       count_prompt=None, history: "HistoryPool" = None):
+                       count_prompt=None, history: "HistoryPool" = None, logit_bias: "LogitBias" = None, bias_set=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1708,7 +1808,10 @@ class Runtime:
         its prompt opens with the last reply token, which the entry's history has already counted.  Needs `occurrence` or `window`.
         history: a `HistoryPool` beside `pool`, entry k of it belonging to entry k of the states: a request that starts from entry k
         begins with the entry's occurrence row (the slot's bans kept) and window instead of empty ones, and one that saves to entry k
-        (reasons 1 and 2) leaves its slot's row and window there in the step that ends it, its last reply token counted."""
+        (reasons 1 and 2) leaves its slot's row and window there in the step that ends it, its last reply token counted.
+        logit_bias / bias_set (a scalar or one set index per request; None: set 0; BIAS_NONE: none): one `LogitBias` for the call;
+        request r's rows are biased with set bias_set[r] from the step it is dispatched, whatever its slot's previous request used, so
+        two requests of one call may ban different tokens.  The bias is not part of a pool entry."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1728,6 +1831,7 @@ class Runtime:
                                            mirostat, mirostat_mu, typical_p)
         self.last_grammar_state = _fill_grammar(opt, R, keep, grammar, grammar_state)
         _fill_dry(opt, R, keep, window, dry, no_repeat_ngram, dry_breakers)
+        _fill_bias(opt, R, keep, logit_bias, bias_set)
         match = _fill_stop_sequences(opt, R, keep, stop_sequences, "requests")
         self.last_stop_match = self.last_stop_tail = None
         if init_state is not None:
