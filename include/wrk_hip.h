@@ -845,6 +845,87 @@ typedef struct wrk_queue_pool {
 int32_t wrk_v7_generate_queue_pool(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
                                    const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_pool* pool);
 
+/* Beam search in the decode loops (Hugging Face's num_beams, vLLM's beam_search): the search over continuations that the other loops do
+ * not make.  A hypothesis of an RWKV model is one fixed-size state slot, so a beam step is the batched step, a selection over at most
+ * W * W + W candidates per group, and a device-to-device permutation of state slots -- all inside the captured step program.
+ * Slots.  G groups of W = num_beams beams run on B = G * W consecutive state slots, 1 <= W <= WRK_MAX_BEAMS and B <= the state's
+ * num_batch; group g owns slots gW .. gW + W - 1.  A slot carries score (f32 sum of log-probs), key (what it is ordered by), length
+ * (generated tokens) and a status WRK_BEAM_LIVE / WRK_BEAM_DONE / WRK_BEAM_DEAD.
+ * Start.  Slot gW is LIVE with score 0, length 0 and the caller's state (what wrk_v7_infer or a previous call left there); the group's
+ * other slots are DEAD and their contents are overwritten.  Every slot of the group feeds first_tokens[g].
+ * One step, after the layers and the head, on the row the pick of wrk_generate_options would see: the head output, or with a logit bias
+ * the biased row (set bias_set[g] for every slot of group g), so log-probs, ties and bans follow that row.
+ *   1. Every LIVE slot b gives W candidates: its W first tokens t_{b,j} in wrk_sample_logits' order with log-probs lp_{b,j}, bit for bit
+ *      what wrk_top_logprobs returns for the row with num_top = W (same rows, num_vocab and stride).  A token whose lp is -inf or NaN is
+ *      no candidate.  Candidate (b, j): raw = score_b + lp_{b,j} (one f32 addition), len = length_b + 1, key = raw * inv_norm[len] (one
+ *      f32 multiplication), inv_norm[l] = (float)(1.0 / pow((double)l, (double)length_penalty)) computed once per call on the host; with
+ *      length_penalty 0 key == raw bit for bit.  No transcendental runs on the device in the selection.
+ *   2. Every DONE slot gives one candidate, itself, with the key it got when it ended.
+ *   3. The group's candidates are ordered by key descending, ties by slot of origin ascending, then j ascending; the first W survive
+ *      (fewer if there are fewer).
+ *   4. A surviving DONE slot stays where it is (nothing is copied, its frozen snapshot stays valid); the group's other slots, ascending,
+ *      take the surviving live candidates in their order; slots left over become DEAD with score and key -inf and length 0.
+ *   5. A live candidate (p, j) placed in slot q: state_q <- the post-step state of slot p (no bytes move when p == q; a slot may be source
+ *      and destination in one step: swaps, chains and broadcasts are all correct), score_q = raw, key_q = key, length_q = len, and the
+ *      slot feeds t_{p,j} next.  It is DONE if t_{p,j} is in the group's stop set (stop_tokens / stop_offsets: a CSR per group of G + 1
+ *      offsets, at most WRK_MAX_BEAM_STOP_TOKENS ids: a group's set is kept sorted and searched, so it may be larger than a sequence's
+ *      WRK_MAX_STOP_TOKENS), else LIVE.  A slot that became DONE is snapshotted in that step, state only: its state
+ *      has consumed everything but its last token, as a sequence wrk_v7_generate_stop froze.
+ *   6. The step records step_tokens[s][q] and step_parents[s][q] (a slot index) and step_scores[s][q] (score_q after the step).  A slot
+ *      not filled in the step (a staying DONE slot, a DEAD one) records WRK_BEAM_NO_TOKEN and parent q.  DONE and DEAD slots go on
+ *      feeding a valid token; what the steps do to their live state does not matter.
+ * End.  A group is over when it has no LIVE slot.  The host submits steps in blocks of poll_steps (0: the default) and stops once every
+ * group is over, or after `steps` steps; DONE slots are then restored from their snapshots.  A group's hypotheses are its non-DEAD
+ * slots by key descending, ties by slot (a LIVE slot's key is score * inv_norm[length]).  wrk_beam_result, all host arrays: per group g
+ * and rank r at [g * W + r]: lengths, scores, finished (1: DONE) and slots, WRK_BEAM_NO_TOKEN in slots and 0 elsewhere for a rank
+ * the group does not have; tokens [G][W][steps]: the rank's tokens (the stop token included), backtracked through step_parents on the
+ * host; num_hyps [G]; *steps_run.  step_tokens / step_parents (u32) and step_scores (f32), [steps][B], may each be NULL; rows at or
+ * after *steps_run are not written.  After the call slot slots[g * W + r] holds that hypothesis's state, having consumed everything but
+ * its last token: the next turn's prompt begins with that token.  The contents of DEAD slots are unspecified.
+ * Composition.  `gen` (may be NULL) carries what the call shares with wrk_generate_options: stop_tokens / stop_offsets, bias / bias_set
+ * (one set word per group; NULL: set 0) and poll_steps.  Every other field of it must be NULL / 0: a call that passes a sampler,
+ * penalties, DRY, a grammar, stop sequences or log-probs is refused, as is one with lanes (bits 8-15 of mode above 1).  W = 1 is greedy
+ * decoding with a score.  WRK_E_ARG before any launch: a NULL opt / out or a NULL required array (every array of wrk_beam_result but
+ * the three step arrays), num_beams outside [1, WRK_MAX_BEAMS], G * W above the state's num_batch or above 256, a length_penalty that
+ * is negative, infinite or NaN or so large that inv_norm[steps] is not a normal number, a first token or stop id >= num_vocab, steps
+ * == 0, and the stop-set and bias errors of wrk_generate_options (a group's cap being WRK_MAX_BEAM_STOP_TOKENS).  num_vocab > 2^20: WRK_E_UNSUPPORTED.  The slot records, inv_norm,
+ * the stop sets and W are device data: one cached step program per (state, B) serves any of them; beam calls replay step programs
+ * of their own, every other call exactly the programs it ran before. */
+#define WRK_MAX_BEAMS 16
+#define WRK_MAX_BEAM_STOP_TOKENS 128
+#define WRK_BEAM_NO_TOKEN 0xFFFFFFFFu
+#define WRK_BEAM_NO_COPY 0xFFFFFFFFu
+enum { WRK_BEAM_DEAD = 0, WRK_BEAM_LIVE = 1, WRK_BEAM_DONE = 2 };
+typedef struct wrk_beam_options {
+    uint32_t num_beams;
+    float length_penalty;
+    const wrk_generate_options *gen;
+} wrk_beam_options;
+typedef struct wrk_beam_result {
+    uint32_t *tokens, *lengths;
+    float *scores;
+    uint32_t *finished, *slots, *num_hyps, *steps_run;
+    uint32_t *step_tokens, *step_parents;
+    float *step_scores;
+} wrk_beam_result;
+int32_t wrk_v7_generate_beam(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
+                             uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null, uint32_t mode);
+/* One beam step on rows of f32 logits, for a host-driven loop: steps 1 - 5 above on logits [num_groups * num_beams][row_stride] (first
+ * num_vocab used; a caller with a bias applies wrk_bias_logits first).  scores / keys (host f32) and lengths / status (host u32), all
+ * [B], in/out: the slot records; stop_tokens / stop_offsets: the groups' stop sets (both NULL: none).  Out, host u32 [B]: out_tokens
+ * (the token the slot feeds next, WRK_BEAM_NO_TOKEN for a slot not filled), out_parents (slot indices) and out_copy_src, the step's copy
+ * list: slot q takes the state of slot out_copy_src[q], WRK_BEAM_NO_COPY for a slot that moves no bytes -- wrk_v7_state_permute's
+ * argument once NO_COPY entries are replaced by q.  inv_norm is computed for the lengths the records reach.  WRK_E_ARG: NULL arrays, W
+ * out of range, B > 256, a status above WRK_BEAM_DONE, a bad length_penalty, a stop id >= num_vocab, and what wrk_top_logprobs
+ * rejects.  Blocking. */
+int32_t wrk_beam_step(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_groups, uint32_t num_beams,
+                      float length_penalty, const uint32_t* stop_tokens, const uint32_t* stop_offsets, float* scores, float* keys,
+                      uint32_t* lengths, uint32_t* status, uint32_t* out_tokens, uint32_t* out_parents, uint32_t* out_copy_src);
+/* state slot q <- state slot parents[q] for q in [0, n), all layers, on the device: every slot is read before any is written (a gather
+ * into a scratch of n slots, then a scatter), so any map is correct -- swaps, chains, many-to-one.  Slots with parents[q] == q move no
+ * bytes and slots >= n are untouched.  parents: host u32 [n], each < n; n <= the state's num_batch (else WRK_E_ARG).  Blocking. */
+int32_t wrk_v7_state_permute(wrk_ctx* ctx, wrk_v7_state* state, const uint32_t* parents, uint32_t n);
+
 /* ---------------------------------------------------------------- RWKV-6 (v6::Model, src/runtime/v6.rs)
  * Same chunk semantics, state layout ([D, S+2, B] per layer: v6.rs:150-214 == v7) and entry points as the V7
  * runner; one kernel per reference TensorOp (v6.rs:701-958), decode steps replayed from a hipGraph.
@@ -916,6 +997,9 @@ int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* s
 /* as wrk_v7_generate_queue_pool */
 int32_t wrk_v6_generate_queue_pool(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
                                    const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_pool* pool);
+/* as wrk_v7_generate_beam */
+int32_t wrk_v6_generate_beam(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
+                             uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null, uint32_t mode);
 
 #ifdef __cplusplus
 }

@@ -42,9 +42,13 @@ a quarter of the entries bans, the rest uniform in [-4, 4]) against the same loo
 without stop sets, so the step programs differ by the bias_rows launch alone -- for the greedy and the plain-sampler pick, alternating,
 with the run-to-run spread of each.  Every call starts from the same state.
 
+A twelfth leg (--beam W): generate_beam with W beams per group on the B slots (B / W groups, --beam-length-penalty, no stop set, so every
+step runs) against generate_greedy on the same B slots, alternating, with the run-to-run spread of each, and next to them
+the bytes the slot permutation may move per step and moved on average.  Every call starts from the same states.
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
                                  [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9] [--grammar] [--stop-seq]
-                                 [--dry] [--logit-bias 64]
+                                 [--dry] [--logit-bias 64] [--beam 4]
 
 Prints one JSON object.
 """
@@ -422,6 +426,49 @@ def bias_leg(rt, ctx, first, V, args):
     return res
 
 
+def beam_leg(rt, first, B, V, args):
+    """Medians of the per-step time of generate_beam with args.beam beams per group on B slots (B / beams groups, no stop set, so every
+    step runs) against generate_greedy on the same B slots, alternating in one process; every call starts from the same states.  Next to
+    them the bytes a step's permutation may move: a gather into the scratch and a scatter back, each at most B slots."""
+    W = args.beam
+    if B % W:
+        return {"skipped": f"{B} slots are not groups of {W} beams"}
+    G = B // W
+    start = [rt.state_read(b) for b in range(B)]
+    slot_bytes = rt.info.num_layer * (rt.info.num_emb // rt.info.num_head + 2) * rt.info.num_emb * 4
+
+    def reset():
+        for b in range(B):
+            rt.state_write(start[b], b)
+
+    def beam():
+        reset()
+        res, run = rt.generate_beam(first[:G], args.steps, W, length_penalty=args.beam_length_penalty)
+        return res, rt.last_beam_ms / max(run, 1)
+
+    def greedy():
+        reset()
+        return rt.generate_greedy(first, args.steps)[1] / args.steps
+    want, _ = beam()                                                       # capture and warm up
+    greedy()
+    moved = int((rt.last_beam_steps[1] != np.arange(B)[None, :]).sum())    # slots whose parent is another slot, over the call
+    bm, gm, same = [], [], True
+    for _ in range(args.reps):
+        gm.append(greedy())
+        res, ms = beam()
+        same &= all(a[0].tolist() == b[0].tolist() and a[1:] == b[1:] for x, y in zip(res, want) for a, b in zip(x, y))
+        bm.append(ms)
+    reset()
+    b_med, g_med = float(np.median(bm)), float(np.median(gm))
+    return {"num_beams": W, "groups": G, "length_penalty": args.beam_length_penalty, "same_hypotheses_every_rep": bool(same),
+            "beam_ms_per_step": round(b_med, 5), "beam_spread_us": round((max(bm) - min(bm)) * 1e3, 2), "beam_ms_all": [round(x, 5) for x in bm],
+            "greedy_ms_per_step": round(g_med, 5), "greedy_spread_us": round((max(gm) - min(gm)) * 1e3, 2),
+            "greedy_ms_all": [round(x, 5) for x in gm], "beam_over_greedy": round(b_med / g_med, 4),
+            "beam_minus_greedy_us": round((b_med - g_med) * 1e3, 2), "state_slot_bytes": slot_bytes,
+            "permute_bytes_read_and_written_per_step_max": 2 * 2 * B * slot_bytes, "slots_moved_per_step_mean": round(moved / args.steps, 3),
+            "permute_bytes_read_and_written_per_step_mean": round(2 * 2 * slot_bytes * moved / args.steps)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -443,6 +490,8 @@ def main():
     ap.add_argument("--stop-seq", action="store_true", help="the stop-sequence programs against the stop programs and the sampled step")
     ap.add_argument("--dry", action="store_true", help="the loop with a token window and DRY against the same loop without")
     ap.add_argument("--logit-bias", type=int, default=None, help="entries per set: the loop with a logit bias against the same loop without")
+    ap.add_argument("--beam", type=int, default=None, help="beams per group: generate_beam against generate_greedy on the same slots")
+    ap.add_argument("--beam-length-penalty", type=float, default=1.0)
     args = ap.parse_args()
     import wrk
 
@@ -540,6 +589,11 @@ def main():
             out["logit_bias_note"] = (f"{args.logit_bias} entries per sequence, every sequence its own set, a quarter bans, the rest uniform in "
                                       "[-4, 4]; a biased step adds one launch to the step program: bias_rows before everything else")
             out["batches"][-1]["logit_bias"] = bias_leg(rt, ctx, first, V, args)
+        if args.beam:
+            out["beam_note"] = ("no stop set: every step runs; a beam step replaces the pick and the advance of a greedy step with five "
+                                "launches: the two of the candidate front (wrk_top_logprobs' kernels), beam_select, and the gather and the "
+                                "scatter of the slot permutation; the snapshot launch returns at once when no slot ended")
+            out["batches"][-1]["beam"] = beam_leg(rt, first, B, V, args)
     if occ is not None:
         occ.close()
     rt.close()

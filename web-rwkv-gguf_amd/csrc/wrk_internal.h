@@ -17,6 +17,7 @@
 #include "wrk_dev_group.h"
 #include "wrk_matjob.h"
 #include "wrk_queue_dispatch.h"
+#include "wrk_beam_select.h"
 
 struct wrk_ctx {
     int device = 0;
@@ -340,6 +341,35 @@ void queue_turnover(hipStream_t s, const QueueGeom& g, const QueueBufs& q, const
 void queue_history_turnover(hipStream_t s, uint32_t v, const QueueStateCtl* sctl, const QueueTurn* turn, const PenaltyParam* pen,
                             const DryParam* dry);
 
+// wrk_beam.hip: beam search in the decode loops (the rule itself: wrk_beam_select.h).  BeamParam is device data, in a
+// decode loop a per-frame block written before every call: W, the number of groups and how many history rows and inv_norm entries
+// there are, so one captured program serves any W.  BeamBufs: the slot records [B], the groups' stop sets, the host's inv_norm table,
+// the candidate front's output (ids / lp [B][W]: wrk_top_logprobs' top arrays of the rows with num_top = W), the step history
+// [hist_rows][B] x 3, the step's copy list copy_src [B] (NO_COPY: the slot moves no bytes), snap_map [B] (q where slot q ended in this
+// step, else NO_COPY), done_map [B] (q where slot q is DONE, else NO_COPY) and the count of LIVE slots
+struct BeamParam { uint32_t w, groups, hist_rows, inv_len; };
+struct BeamBufs {
+    const BeamParam* par; BeamSlot* slots; const BeamStop* stops; const float* inv_norm;
+    const uint32_t* cand_ids; const float* cand_lp;
+    uint32_t *step_tokens, *step_parents; float* step_scores;
+    uint32_t *copy_src, *snap_map, *done_map, *live;
+};
+// the candidate front and the selection of one step over rows [b][stride] (v used): logprob_rows with `lp` (num_top = W, its top arrays
+// Q.cand_ids / Q.cand_lp) on the chosen tokens lp_tokens (any ids < v), then beam_select: one workgroup, a wave per group; writes the
+// records, tokens[q] of every slot filled, row *counter of the history, the three maps, *live, and moves the counter last.
+// -1: logprob_rows' refusals
+int beam_step_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t b, const uint32_t* lp_tokens, const LogprobParam* lp,
+                   LogprobPart* part, unsigned long long* keys, const BeamBufs& Q, uint32_t* tokens, uint32_t* counter, int num_cu);
+// Slot copies over all layers between two arrays of slots, layer l's slot i of an array at base + ((size_t)l * nb + b0 + i) * slot:
+// for every q < n with map[q] != WRK_BEAM_NO_COPY, dst slot q <- src slot (src_mapped ? map[q] : q).  16-byte copies cut over about two
+// workgroups per CU (scalar ones unless slot % 4 == 0 and both bases are 16-byte aligned); workgroups of the other slots return at
+// once.  src and dst do not overlap
+struct BeamSlots { float* base; uint32_t nb, b0; };
+void beam_copy(hipStream_t s, const BeamSlots& src, const BeamSlots& dst, uint32_t layers, size_t slot, const uint32_t* map, bool src_mapped,
+               uint32_t n, int num_cu);
+// state slot q <- state slot map[q] for the listed q, under any aliasing: a gather into `scratch` (n slots per layer), then the scatter
+void beam_permute(hipStream_t s, const BeamSlots& state, float* scratch, uint32_t layers, size_t slot, const uint32_t* map, uint32_t n, int num_cu);
+
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled
 void timing_report(wrk_ctx* ctx);
@@ -431,6 +461,13 @@ struct wrk_logit_bias {
 // validated set words of n rows (WRK_E_ARG on a NULL object, an object of another context or another vocabulary, a word that is neither
 // < num_sets nor WRK_BIAS_NONE); set NULL: all 0
 int32_t wrk_bias_pack(wrk_ctx* ctx, const wrk_logit_bias* lb, const uint32_t* set, uint32_t n, uint32_t V, std::vector<uint32_t>& out);
+
+// beam search (wrk_beam.hip): inv_norm[l] = (float)(1.0 / pow((double)l, (double)length_penalty)) for l in [1, max_len], entry 0 unused
+// (WRK_E_ARG on a penalty that is negative, infinite or NaN, or whose table leaves the normal numbers); the groups' stop sets from a CSR
+// of G + 1 offsets, every set sorted (both arrays NULL: all empty; WRK_E_ARG as wrk_generate_options' stop sets, the cap being
+// WRK_MAX_BEAM_STOP_TOKENS)
+int32_t wrk_beam_inv_norm(wrk_ctx* ctx, float length_penalty, uint32_t max_len, std::vector<float>& out);
+int32_t wrk_beam_stops(wrk_ctx* ctx, const uint32_t* tokens, const uint32_t* off, uint32_t G, uint32_t V, std::vector<wrk::BeamStop>& rows);
 
 // include/wrk_hip.h wrk_token_window: one allocation holding the rings u32 [num_batch][capacity] and meta u32 [num_batch][2]
 // (length, next write position)

@@ -86,7 +86,9 @@ struct wrk_step_kind {
     // arg-max / the sampler (wrk_sample.hip) on sample_par / the filtered sampler, also on filter_par / the Mirostat v2 sampler, also on
     // alt_par, whose mu it carries from draw to draw / the typical sampler, also on alt_par
     enum Pick : uint32_t { GREEDY, SAMPLED, FILTERED, MIROSTAT, TYPICAL };
-    enum Tail : uint32_t { PLAIN, STOP, QUEUE, QUEUE_POOL };    // advance_tokens / wrk_stop.hip / wrk_queue.hip / the same with a state pool
+    // advance_tokens / wrk_stop.hip / wrk_queue.hip / the same with a state pool / beam search (wrk_beam.hip): no pick at all --
+    // on head_o, or biased on bias.out, the candidate front and beam_select, then the slot permutation and the snapshot of the slots that ended
+    enum Tail : uint32_t { PLAIN, STOP, QUEUE, QUEUE_POOL, BEAM };
     Pick pick = GREEDY;
     bool penalized = false;     // the pick is made on pen_o = head_o penalised with the occurrence rows of pen_par, which then count the draw (wrk_penalty.hip)
     Tail tail = PLAIN;
@@ -116,16 +118,18 @@ struct wrk_step_kind {
     bool queue() const { return tail == QUEUE || tail == QUEUE_POOL; }
     bool pool() const { return tail == QUEUE_POOL; }
     // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25 and, its third bit, 30 (the first three picks keep the
-    // keys they had with two bits), penalised 26, tail 27-28, log-probs 29, constrained 31 (the word is full) -- above every flag of an
+    // keys they had with two bits), penalised 26, tail 27-28 (its third bit: key2()), log-probs 29, constrained 31 (the word is full) -- above every flag of an
     // infer job and of a runner's own (wrk_frame_common::key_bits, all below bit 24, ORed into the same word)
     uint32_t key() const {
-        return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | (uint32_t)tail << 27 | (uint32_t)logprobs << 29 |
+        return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | ((uint32_t)tail & 3u) << 27 | (uint32_t)logprobs << 29 |
                (uint32_t)constrained << 31;
     }
     // The kind's bits of GraphKey::mode2, the word that takes what key() has no room for: stop sequences 0, DRY 1, prompt intake 2,
-    // history 3, biased 4.  0 for every kind that existed before the word did, and bit 0 alone for every stop-sequence kind, so their keys compare
-    // as they always have
-    uint32_t key2() const { return (uint32_t)stop_seqs | (uint32_t)dry << 1 | (uint32_t)intake << 2 | (uint32_t)history << 3 | (uint32_t)biased << 4; }
+    // history 3, biased 4, the tail's third bit (the beam tail) 5.  0 for every kind that existed before the word did, and bit 0 alone for every
+    // stop-sequence kind, so their keys compare as they always have
+    uint32_t key2() const {
+        return (uint32_t)stop_seqs | (uint32_t)dry << 1 | (uint32_t)intake << 2 | (uint32_t)history << 3 | (uint32_t)biased << 4 | ((uint32_t)tail >> 2) << 5;
+    }
 };
 
 // ------------------------------------------------------------------ the buffer groups of a frame (Pieces of wrk_dev_group)
@@ -300,6 +304,35 @@ struct wrk_logprob_bufs {
         c.take(part, wrk::logprob_part_bytes((uint32_t)d[1])); c.take(keys, wrk::logprob_key_bytes((uint32_t)d[1]));
     }
 };
+// beam search (wrk_beam.hip).  par / lp_par: the parameter blocks (W and the sizes; the candidate front's outputs and num_top = W);
+// the slot records, the groups' stop sets, the maps and cand_ids / cand_lp [slots][WRK_MAX_BEAMS]; the front's chosen-token log-probs, slice
+// partials and candidate keys; the step history [rows] x 3; inv_norm [entries]; scratch [slots][state floats]: what the permutation
+// gathers into; snap [slots][state floats]: a slot's state at the step that ended it.  Both as layers of [slots of the call][slot floats]
+struct wrk_beam_bufs {
+    static constexpr int DIMS = 4;              // slots, history rows, inv_norm entries, floats of one sequence's state (L * (S+2) * D)
+    static constexpr unsigned EXACT = 8;
+    wrk::BeamParam* par = nullptr;
+    wrk::LogprobParam* lp_par = nullptr;
+    wrk::BeamSlot* slots = nullptr;
+    wrk::BeamStop* stops = nullptr;
+    uint32_t *cand_ids = nullptr, *copy_src = nullptr, *snap_map = nullptr, *done_map = nullptr, *live = nullptr;
+    float *cand_lp = nullptr, *chosen_lp = nullptr;
+    wrk::LogprobPart* part = nullptr;
+    unsigned long long* keys = nullptr;
+    uint32_t *step_tokens = nullptr, *step_parents = nullptr;
+    float *step_scores = nullptr, *inv_norm = nullptr, *scratch = nullptr, *snap = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(par, sizeof(wrk::BeamParam)); c.take(lp_par, sizeof(wrk::LogprobParam)); c.take(slots, d[0] * sizeof(wrk::BeamSlot));
+        c.take(stops, d[0] * sizeof(wrk::BeamStop)); c.take(cand_ids, d[0] * WRK_MAX_BEAMS * 4); c.take(cand_lp, d[0] * WRK_MAX_BEAMS * 4);
+        c.take(copy_src, d[0] * 4); c.take(snap_map, d[0] * 4); c.take(done_map, d[0] * 4); c.take(live, 4); c.take(chosen_lp, d[0] * 4);
+        c.take(part, wrk::logprob_part_bytes((uint32_t)d[0])); c.take(keys, wrk::logprob_key_bytes((uint32_t)d[0]));
+        c.take(step_tokens, d[1] * 4); c.take(step_parents, d[1] * 4); c.take(step_scores, d[1] * 4); c.take(inv_norm, d[2] * 4);
+        c.take(scratch, d[0] * d[3] * 4); c.take(snap, d[0] * d[3] * 4);
+    }
+    wrk::BeamBufs dev() const {
+        return wrk::BeamBufs{par, slots, stops, inv_norm, cand_ids, cand_lp, step_tokens, step_parents, step_scores, copy_src, snap_map, done_map, live};
+    }
+};
 
 // ------------------------------------------------------------------ frame state of a model (base of wrk_v7_model / wrk_v6_model)
 struct wrk_frame_common {
@@ -345,9 +378,10 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_queue_state_bufs> queue_states;
     wrk_dev_group<wrk_queue_intake_bufs> queue_intake;
     wrk_dev_group<wrk_logprob_bufs> logprob;
+    wrk_dev_group<wrk_beam_bufs> beam;
     template <class F> void each_group(F&& f) {     // the one list of the groups
         f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(bias); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
-        f(queue_states); f(queue_intake); f(logprob);
+        f(queue_states); f(queue_intake); f(logprob); f(beam);
     }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
     uint32_t live_host_cap = 0;
@@ -447,3 +481,8 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
 int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                            const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail,
                            const wrk_queue_pool* pool);
+// wrk_v*_generate_beam (tail BEAM): the stop call's polled loop on one lane over B = G * num_beams slots with the beam tail and the count of
+// LIVE slots; after the loop the DONE slots are restored from their snapshots, the records and the history rows come back and the
+// hypotheses are backtracked through the parents on the host
+int32_t wrk_generate_beam(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t G, uint32_t steps,
+                          const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg);

@@ -1,6 +1,8 @@
 // Host-side driver shared by the RWKV-7 and RWKV-6 runners (wrk_runner.h).  No kernels here.
 #include "wrk_runner.h"
 
+#include <algorithm>
+
 #define LOCK(ctx) std::lock_guard<std::recursive_mutex> _lk((ctx)->mu)
 
 // ------------------------------------------------------------------ matmul launches
@@ -882,6 +884,59 @@ static int32_t enqueue_stop_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind 
     return WRK_OK;
 }
 
+// ------------------------------------------------------------------ beam search (wrk_beam.hip)
+// generate_beam: the options validated (WRK_E_ARG before any launch) into what the B = G * W slots start with
+struct wrk_beam_pack {
+    uint32_t G = 0, W = 0, steps = 0, poll_steps = 0;
+    std::vector<uint32_t> first_tokens;         // [B]: every slot of group g feeds first_tokens[g]
+    std::vector<wrk::BeamSlot> slots;           // [B]: slot gW LIVE with score 0 and length 0, the others DEAD
+    std::vector<wrk::BeamStop> stops;           // [G]
+    std::vector<float> inv_norm;                // [steps + 1]
+    wrk_pick_params rows;                       // biased: the object and the slots' set words [B]
+};
+
+static size_t state_slot_floats(const wrk_v7_state* st) { return (size_t)(st->head_size + 2) * st->num_emb; }
+
+// after wrk_decode_prepare and before the step program is looked up (growing the buffers drops the programs): the beam buffers of the
+// frame, the parameter blocks, the records, the stop sets and inv_norm of this call, empty maps, live = G
+static int32_t wrk_beam_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t B, const wrk_beam_pack& pk) {
+    wrk_ctx* ctx = f.ctx;
+    const int32_t rc = f.grow(f.beam, {B, (size_t)pk.steps * B, pk.inv_norm.size(), (size_t)st->num_layer * state_slot_floats(st)});
+    if (rc != WRK_OK) return rc;
+    const wrk::BeamParam par{pk.W, pk.G, pk.steps, (uint32_t)pk.inv_norm.size()};
+    const wrk::LogprobParam lp{f.beam.chosen_lp, f.beam.cand_ids, f.beam.cand_lp, pk.W, B};
+    const std::vector<uint32_t> none(B, WRK_BEAM_NO_COPY);
+    wrk_upload up{ctx};
+    up(f.beam.par, &par, 1)(f.beam.lp_par, &lp, 1)(f.beam.slots, pk.slots.data(), B)(f.beam.stops, pk.stops.data(), pk.G);
+    up(f.beam.inv_norm, pk.inv_norm.data(), pk.inv_norm.size())(f.beam.copy_src, none.data(), B)(f.beam.snap_map, none.data(), B);
+    up(f.beam.done_map, none.data(), B)(f.beam.live, &pk.G, 1);
+    if (up.rc != WRK_OK) return up.rc;
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+// the slots [b0, b0 + B) of `st`, as beam_copy addresses them
+static wrk::BeamSlots beam_state(const wrk_v7_state* st, uint32_t b0) { return wrk::BeamSlots{st->data, st->num_batch, b0}; }
+
+// tail of a beam program's step, on the row the pick would be made on: the candidate front and beam_select, the permutation of the
+// slots by the step's copy list, then the snapshot of the slots that ended in the step (their state after the permutation)
+static int32_t enqueue_beam_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, const float* logits,
+                                 bool argmax_done) {
+    hipStream_t q = f.ctx->op_stream();
+    const wrk::FrameIo& io = f.io();
+    const uint32_t V = f.facts().num_vocab;
+    const size_t slot = state_slot_floats(st);
+    if (!f.beam.holds({B}) || f.beam.dim[3] != (size_t)st->num_layer * slot || b0 + B > st->num_batch || argmax_done)
+        return wrk_fail(f.ctx, WRK_E_ARG, "beam buffers are not prepared");
+    if (kind.sampled() || kind.penalized || kind.constrained || kind.dry || kind.logprobs || kind.stop_seqs)
+        return wrk_fail(f.ctx, WRK_E_ARG, "a beam step composes with a logit bias only");
+    if (wrk::beam_step_rows(q, logits, V, V, B, io.tokens, f.beam.lp_par, f.beam.part, f.beam.keys, f.beam.dev(), io.tokens, io.counter, f.ctx->num_cu) != 0)
+        return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "beam search: vocabulary of %u tokens", V);
+    wrk::beam_permute(q, beam_state(st, b0), f.beam.scratch, st->num_layer, slot, f.beam.copy_src, B, f.ctx->num_cu);
+    wrk::beam_copy(q, beam_state(st, b0), wrk::BeamSlots{f.beam.snap, B, 0u}, st->num_layer, slot, f.beam.snap_map, false, B, f.ctx->num_cu);
+    return WRK_OK;
+}
+
 int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, bool argmax_done) {
     hipStream_t q = f.ctx->op_stream();
     const wrk::FrameIo& io = f.io();
@@ -894,6 +949,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
         wrk::bias_rows(q, io.head_o, V, V, B, f.bias.par, f.bias.out, V);
         logits = f.bias.out;
     }
+    if (kind.tail == wrk_step_kind::BEAM) return enqueue_beam_tail(f, B, kind, st, b0, logits, argmax_done);
     if (kind.penalized) {
         wrk::penalize_rows(q, logits, V, V, B, f.penalty.par, f.penalty.out, V);
         logits = f.penalty.out;
@@ -956,13 +1012,14 @@ static constexpr uint32_t WRK_STOP_POLL_DEFAULT = 16;
 // key bits, step kind -- key() in the mode word, key2() in the second): the analogue of the reference's cached RnnJob for a repeated RnnInfo
 static int32_t lane_prepare(wrk_lane& ln, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t steps, uint32_t mode, wrk_step_kind kind,
                             const wrk_pick_params& rows, const wrk::StopParam* stop, const wrk_stopseq_pack* seq, const wrk_queue_pack* queue,
-                            uint32_t num_top) {
+                            uint32_t num_top, const wrk_beam_pack* beam = nullptr) {
     wrk_frame_common& f = *ln.frame;
     const uint32_t b0 = ln.b0, B = ln.nb;
     int32_t rc = f.ensure_frame(B, mode);
     if (rc == WRK_OK) rc = wrk_decode_prepare(f, first_tokens, b0, B, steps, rows);
     if (rc == WRK_OK && kind.tail == wrk_step_kind::STOP) rc = wrk_stop_prepare(f, st, b0, B, stop + b0, seq);
     if (rc == WRK_OK && kind.queue()) rc = wrk_queue_prepare(f, st, B, *queue);
+    if (rc == WRK_OK && kind.tail == wrk_step_kind::BEAM) rc = wrk_beam_prepare(f, st, B, *beam);
     if (rc == WRK_OK && kind.logprobs) rc = wrk_logprob_prepare(f, B, steps, num_top);
     ln.prog = nullptr;
     if (rc != WRK_OK || wrk_no_graph()) return rc;
@@ -1002,9 +1059,12 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
     };
     uint32_t* live_host = nullptr;
     hipEvent_t* poll_events = nullptr;
+    const bool beam = kind.tail == wrk_step_kind::BEAM;
+    // the tail's live count: requests not yet ended / LIVE slots / sequences still running
+    auto live_of = [&](const wrk_lane& ln) { return kind.queue() ? ln.frame->queue.live() : beam ? ln.frame->beam.live : ln.frame->stop.live(); };
     if (polled) {
         for (const wrk_lane& ln : lanes)
-            if (!(kind.queue() ? ln.frame->queue.held() : ln.frame->stop.held()))
+            if (!(kind.queue() ? ln.frame->queue.held() : beam ? ln.frame->beam.held() : ln.frame->stop.held()))
                 return wrk_fail(ctx, WRK_E_ARG, "stop run on a lane without stop buffers");
         const int32_t rc = lanes[0].frame->ensure_poll((uint32_t)groups);
         if (rc != WRK_OK) return rc;
@@ -1036,8 +1096,7 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
             run += n;
             for (size_t g = 0; g < groups; ++g) {
                 hipStream_t ls = groups == 1 ? ctx->stream : streams[g];
-                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, kind.queue() ? lanes[g].frame->queue.live() : lanes[g].frame->stop.live(), 4,
-                                            hipMemcpyDeviceToHost, ls));
+                WRK_HIP(ctx, hipMemcpyAsync(live_host + (k & 1) * groups + g, live_of(lanes[g]), 4, hipMemcpyDeviceToHost, ls));
                 WRK_HIP(ctx, hipEventRecord(poll_events[(k & 1) * groups + g], ls));
             }
         }
@@ -1064,6 +1123,13 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
             wrk::stop_restore(ctx->stream, stop_geom(*ln.frame, st, ln.b0), ln.nb, ctx->num_cu);
             WRK_HIP(ctx, hipMemcpyAsync(stop.out_lengths + ln.b0, ln.frame->stop.lengths(), (size_t)ln.nb * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
+        WRK_LAUNCH_CHECK(ctx);
+    }
+    if (beam) {
+        // the frozen slots go back: every DONE slot's snapshot, taken by the step that ended it
+        for (const wrk_lane& ln : lanes)
+            wrk::beam_copy(ctx->stream, wrk::BeamSlots{ln.frame->beam.snap, ln.nb, 0u}, beam_state(st, ln.b0), st->num_layer, state_slot_floats(st),
+                           ln.frame->beam.done_map, false, ln.nb, ctx->num_cu);
         WRK_LAUNCH_CHECK(ctx);
     }
     if (polled) *stop.steps_run = steps;
@@ -1195,4 +1261,121 @@ int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, 
     if (rc == WRK_OK) rc = m->after_loop(1);
     if (rc != WRK_OK) return rc;
     return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
+}
+
+// generate_beam: opt validated into pk (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch); sets kind
+static int32_t wrk_beam_check(wrk_ctx* ctx, const wrk_beam_options* opt, const wrk_beam_result* out, const wrk_v7_state* st, const uint32_t* first_tokens,
+                              uint32_t G, uint32_t steps, uint32_t V, uint32_t mode_arg, wrk_beam_pack& pk, wrk_step_kind& kind) {
+    WRK_ARG(ctx, opt, "options required");
+    WRK_ARG(ctx, out && out->tokens && out->lengths && out->scores && out->finished && out->slots && out->num_hyps && out->steps_run,
+            "every result array but the step arrays is required");
+    const uint32_t W = opt->num_beams;
+    WRK_ARG(ctx, W >= 1 && W <= WRK_MAX_BEAMS, "num_beams %u: must be in [1, %u]", W, (uint32_t)WRK_MAX_BEAMS);
+    WRK_ARG(ctx, G >= 1 && (uint64_t)G * W <= st->num_batch && (uint64_t)G * W <= 256, "%u groups of %u beams: at most min(%u, 256) slots", G, W,
+            st->num_batch);
+    WRK_ARG(ctx, steps >= 1, "steps 0");
+    WRK_ARG(ctx, ((mode_arg >> 8) & 0xffu) <= 1, "generate_beam runs on one lane");
+    static const wrk_generate_options none{};
+    const wrk_generate_options& g = opt->gen ? *opt->gen : none;
+    WRK_ARG(ctx, !g.temperature && !g.top_p && !g.seed && !g.top_k && !g.min_p && !g.mirostat_tau && !g.mirostat_eta && !g.mirostat_mu && !g.typical_p,
+            "beam search takes no sampler");
+    WRK_ARG(ctx, !g.presence && !g.frequency && !g.decay && !g.occ, "beam search takes no penalties");
+    WRK_ARG(ctx, !g.window && !g.dry_multiplier && !g.dry_base && !g.dry_allowed_length && !g.no_repeat_ngram && !g.dry_breakers && !g.num_dry_breakers,
+            "beam search takes no DRY / n-gram ban");
+    WRK_ARG(ctx, !g.grammar && !g.grammar_state, "beam search takes no grammar");
+    WRK_ARG(ctx, !g.num_top && !g.out_logprob && !g.out_top_ids && !g.out_top_logprobs, "beam search returns no log-prob rows");
+    WRK_ARG(ctx, !g.stop_seq_tokens && !g.stop_seq_offsets && !g.stop_seq_owners && !g.out_stop_match && !g.stop_tail, "beam search takes no stop sequences");
+    if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "beam search: vocabulary of %u tokens", V);
+    const uint32_t B = G * W;
+    pk.G = G; pk.W = W; pk.steps = steps; pk.poll_steps = g.poll_steps;
+    int32_t rc = wrk_beam_inv_norm(ctx, opt->length_penalty, steps, pk.inv_norm);
+    if (rc == WRK_OK) rc = wrk_beam_stops(ctx, g.stop_tokens, g.stop_offsets, G, V, pk.stops);
+    wrk_pick_params per_group;
+    wrk_pick_args pick;
+    pick.bias = g.bias; pick.bias_set = g.bias_set;
+    kind = wrk_step_kind{};
+    if (rc == WRK_OK) rc = wrk_pick_pack(ctx, pick, G, G, V, per_group, kind);
+    if (rc != WRK_OK) return rc;
+    kind.tail = wrk_step_kind::BEAM;
+    pk.rows.bias = per_group.bias;
+    pk.first_tokens.resize(B);
+    pk.slots.assign(B, wrk::BeamSlot{-INFINITY, -INFINITY, 0u, (uint32_t)WRK_BEAM_DEAD});
+    for (uint32_t q = 0; q < B; ++q) {
+        pk.first_tokens[q] = first_tokens[q / W];
+        if (kind.biased) pk.rows.bias_set.push_back(per_group.bias_set[q / W]);
+        if (q % W == 0) pk.slots[q] = wrk::BeamSlot{0.0f, 0.0f, 0u, (uint32_t)WRK_BEAM_LIVE};
+    }
+    return WRK_OK;
+}
+
+// after the loop and the restore: the records and the history rows come back; per group the non-DEAD slots by key descending, ties by
+// slot, each backtracked through the parents
+static int32_t wrk_beam_finish(wrk_frame_common& f, const wrk_beam_pack& pk, uint32_t steps_run, const wrk_beam_result& out) {
+    wrk_ctx* ctx = f.ctx;
+    const uint32_t G = pk.G, W = pk.W, B = G * W;
+    const size_t rows = (size_t)steps_run * B;
+    std::vector<wrk::BeamSlot> slots(B);
+    std::vector<uint32_t> tok(rows), par(rows);
+    WRK_HIP(ctx, hipMemcpyAsync(slots.data(), f.beam.slots, (size_t)B * sizeof(wrk::BeamSlot), hipMemcpyDeviceToHost, ctx->stream));
+    if (rows) {
+        WRK_HIP(ctx, hipMemcpyAsync(tok.data(), f.beam.step_tokens, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+        WRK_HIP(ctx, hipMemcpyAsync(par.data(), f.beam.step_parents, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (out.step_scores) WRK_HIP(ctx, hipMemcpyAsync(out.step_scores, f.beam.step_scores, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (out.step_tokens && rows) memcpy(out.step_tokens, tok.data(), rows * 4);
+    if (out.step_parents && rows) memcpy(out.step_parents, par.data(), rows * 4);
+    for (uint32_t g = 0; g < G; ++g) {
+        std::vector<uint32_t> order;
+        for (uint32_t q = g * W; q < (g + 1) * W; ++q)
+            if (slots[q].status != WRK_BEAM_DEAD) order.push_back(q);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return slots[a].key > slots[b].key; });
+        out.num_hyps[g] = (uint32_t)order.size();
+        for (uint32_t r = 0; r < W; ++r) {
+            const size_t at = (size_t)g * W + r;
+            uint32_t* dst = out.tokens + at * pk.steps;
+            for (uint32_t j = 0; j < pk.steps; ++j) dst[j] = 0u;
+            out.lengths[at] = 0u; out.scores[at] = 0.0f; out.finished[at] = 0u; out.slots[at] = WRK_BEAM_NO_TOKEN;
+            if (r >= order.size()) continue;
+            const uint32_t q = order[r];
+            const wrk::BeamSlot& s = slots[q];
+            uint32_t cur = q, left = s.length;
+            // nothing below can leave the rows that ran or the group unless the device history is wrong
+            for (uint32_t t = steps_run; t-- > 0 && left > 0;) {
+                const uint32_t y = tok[(size_t)t * B + cur], p = par[(size_t)t * B + cur];
+                if (p / W != g) return wrk_fail(ctx, WRK_E_HIP, "slot %u: inconsistent beam history at step %u (parent %u)", q, t, p);
+                if (y != WRK_BEAM_NO_TOKEN) dst[--left] = y;
+                cur = p;
+            }
+            if (left != 0 || s.length > pk.steps) return wrk_fail(ctx, WRK_E_HIP, "slot %u: inconsistent beam history (length %u)", q, s.length);
+            out.lengths[at] = s.length; out.scores[at] = s.score; out.finished[at] = s.status == WRK_BEAM_DONE; out.slots[at] = q;
+        }
+    }
+    *out.steps_run = steps_run;
+    return WRK_OK;
+}
+
+int32_t wrk_generate_beam(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t G, uint32_t steps,
+                          const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+    if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
+    LOCK(ctx);
+    const uint32_t V = m->facts().num_vocab;
+    wrk_beam_pack pk;
+    wrk_step_kind kind;
+    int32_t rc = wrk_beam_check(ctx, opt, out_arg, st, first_tokens, G, steps, V, mode_arg, pk, kind);
+    const uint32_t B = pk.G * pk.W;
+    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), pk.first_tokens.data(), B);
+    if (rc != WRK_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0f;
+    const uint32_t mode = mode_arg & 0xffu;
+    m->before_loop();
+    std::vector<wrk_lane> L{{nullptr, 0, B, nullptr}};
+    rc = m->lane(0, 1, &L[0].frame);
+    if (rc == WRK_OK) rc = lane_prepare(L[0], st, pk.first_tokens.data(), steps, mode, kind, pk.rows, nullptr, nullptr, nullptr, 0u, &pk);
+    if (rc != WRK_OK) return rc;
+    uint32_t steps_run = 0;
+    rc = wrk_run_lanes(ctx, L, st, B, steps, mode, kind, nullptr, nullptr, elapsed_ms, wrk_stop_run{pk.poll_steps, nullptr, &steps_run}, wrk_logprob_call{});
+    if (rc == WRK_OK) rc = m->after_loop(1);
+    if (rc != WRK_OK) return rc;
+    return wrk_beam_finish(*L[0].frame, pk, steps_run, *out_arg);
 }

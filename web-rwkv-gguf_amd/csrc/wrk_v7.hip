@@ -620,10 +620,10 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
 
 // one decode step of sequences [b0, b0 + B) on this frame: embed s.tokens, run the layers and the head, then wrk_enqueue_pick.  The fused
 // greedy head leaves the arg-max in s.argmax, and in a plain step advances tokens / history / counter itself: nothing follows it.  A
-// constrained, a DRY or a biased step picks on the modified row: its head only writes head_o, as a sampled step's does
+// constrained, a DRY or a biased step picks on the modified row, and a beam step makes no pick: its head only writes head_o, as a sampled step's does
 int32_t wrk_v7_model::enqueue_step(wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) {
     int32_t rc;
-    const bool fused = mode == 1 && act_dtype == WRK_F16, head_picks = fused && !kind.sampled() && !kind.constrained && !kind.dry && !kind.biased,
+    const bool fused = mode == 1 && act_dtype == WRK_F16, head_picks = fused && !kind.sampled() && !kind.constrained && !kind.dry && !kind.biased && kind.tail != wrk_step_kind::BEAM,
                head_advances = head_picks && kind.tail == wrk_step_kind::PLAIN && !kind.logprobs;     // log-probs go between the pick and the advance
     if (fused) rc = enqueue_fused_decode(st, B, B, true, true, head_picks, head_advances, b0, true);
     else {
@@ -721,6 +721,11 @@ int32_t wrk_v7_generate_queue(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, u
 int32_t wrk_v7_generate_queue_pool(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                                    const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_pool* pool) {
     return wrk_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE_POOL, pool);
+}
+
+int32_t wrk_v7_generate_beam(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t G, uint32_t steps,
+                             const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+    return wrk_generate_beam(ctx, m, st, first_tokens, G, steps, opt, out_arg, elapsed_ms, mode_arg);
 }
 
 }  // extern "C"

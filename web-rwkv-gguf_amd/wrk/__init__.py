@@ -114,6 +114,23 @@ class QueuePool(C.Structure):
     _fields_ = [("states", _P), ("num_entries", C.c_uint32), ("start", _u32p), ("save", _u32p), ("saved", _u32p)]
 
 
+class BeamOptions(C.Structure):
+    """wrk_beam_options: num_beams, length_penalty and the GenerateOptions a beam call shares (stop sets, bias, poll_steps)."""
+    _fields_ = [("num_beams", C.c_uint32), ("length_penalty", C.c_float), ("gen", C.POINTER(GenerateOptions))]
+
+
+class BeamResult(C.Structure):
+    """wrk_beam_result: host arrays per group and rank [G * W] (tokens: [G][W][steps]), num_hyps [G], the steps the call ran and the
+    optional per-step arrays [steps][B]."""
+    _fields_ = [("tokens", _u32p), ("lengths", _u32p), ("scores", _f32p), ("finished", _u32p), ("slots", _u32p), ("num_hyps", _u32p),
+                ("steps_run", _u32p), ("step_tokens", _u32p), ("step_parents", _u32p), ("step_scores", _f32p)]
+
+
+MAX_BEAMS = 16              # WRK_MAX_BEAMS
+MAX_BEAM_STOP_TOKENS = 128  # WRK_MAX_BEAM_STOP_TOKENS
+BEAM_NO_TOKEN = 0xFFFFFFFF  # WRK_BEAM_NO_TOKEN
+BEAM_NO_COPY = 0xFFFFFFFF   # WRK_BEAM_NO_COPY
+BEAM_DEAD, BEAM_LIVE, BEAM_DONE = 0, 1, 2   # WRK_BEAM_DEAD / _LIVE / _DONE
 MAX_STOP_TOKENS = 16        # WRK_MAX_STOP_TOKENS
 MAX_TOP_LOGPROBS = 20       # WRK_MAX_TOP_LOGPROBS
 MAX_STOP_SEQUENCES = 8      # WRK_MAX_STOP_SEQUENCES
@@ -257,6 +274,13 @@ HIP_SYMBOLS = {
                                                C.POINTER(QueuePool)]),
     "wrk_v6_generate_queue_pool": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
                                                C.POINTER(QueuePool)]),
+    "wrk_v7_generate_beam": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(BeamOptions), C.POINTER(BeamResult), _f32p,
+                                         C.c_uint32]),
+    "wrk_v6_generate_beam": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(BeamOptions), C.POINTER(BeamResult), _f32p,
+                                         C.c_uint32]),
+    "wrk_beam_step": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u32p, _u32p, _f32p, _f32p, _u32p, _u32p,
+                                  _u32p, _u32p, _u32p]),
+    "wrk_v7_state_permute": (C.c_int32, [_P, _P, _u32p, C.c_uint32]),
 }
 RT_SYMBOLS = {
     "wrk_host_last_error": (C.c_char_p, []),
@@ -820,6 +844,38 @@ class Context:
         st = _per_row(sets, n, np.uint32)
         self.check(hip.wrk_bias_logits(self.h, buf.h, V, stride, n, lb.h, _ptr(st, _u32p)))
         return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
+
+    def beam_step(self, logits, num_beams: int, scores, keys, lengths, status, stop=None, length_penalty: float = 0.0,
+                  num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
+        """One beam-search step on the device (wrk_beam_step) for a host-driven loop: rows [G * num_beams, V] of logits --
+        an f32 array, or a `Buffer` of rows of `row_stride` f32 (first `num_vocab` used) -- and the slot records scores / keys (f32) and
+        lengths / status (BEAM_LIVE / BEAM_DONE / BEAM_DEAD), all [B].  stop: one list of ids for all groups, or one list per group.
+        Returns (tokens [B], parents [B], copy_src [B], scores, keys, lengths, status): the token every slot feeds next (BEAM_NO_TOKEN:
+        not filled in this step), the slot it descends from, the step's copy list (BEAM_NO_COPY: the slot moves no bytes) and the
+        records after the step."""
+        sc, ky = np.array(scores, np.float32).reshape(-1), np.array(keys, np.float32).reshape(-1)
+        ln, stt = np.array(lengths, np.uint32).reshape(-1), np.array(status, np.uint32).reshape(-1)
+        B, W = sc.size, int(num_beams)
+        assert ky.size == B and ln.size == B and stt.size == B, "one record per slot"
+        if W < 1 or B % W:
+            raise ValueError(f"{B} slots are not groups of {W} beams")
+        G = B // W
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            stride = int(row_stride or V)
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            assert a.shape[0] == B, "one row per slot"
+            V = stride = a.shape[1]
+            buf = self.buffer(a)
+        ids, off = _stop_csr(stop, G, "groups")
+        tok, par, cp = np.zeros(B, np.uint32), np.zeros(B, np.uint32), np.zeros(B, np.uint32)
+        self.check(hip.wrk_beam_step(self.h, buf.h, V, stride, G, W, float(length_penalty), _ptr(ids, _u32p), _ptr(off, _u32p),
+                                     _ptr(sc, _f32p), _ptr(ky, _f32p), _ptr(ln, _u32p), _ptr(stt, _u32p), _ptr(tok, _u32p), _ptr(par, _u32p),
+                                     _ptr(cp, _u32p)))
+        return tok, par, cp, sc, ky, ln, stt
 
     def stop_sequences_advance(self, tails, tokens, stop_sequences, stop=None, num_vocab: Optional[int] = None):
         """One counted draw of the stop-sequence matcher on the device (wrk_stop_sequences_advance) for n rows: row r has the
@@ -1471,6 +1527,8 @@ class Runtime:
         # tails [B, STOP_TAIL_LEN] to pass to the next call of a session; None after a call without
         self.last_stop_match = None
         self.last_stop_tail = None
+        # what every step of the last generate_beam call put in every slot: (tokens, parents, scores), each [steps_run, B]
+        self.last_beam_steps = None
 
     def token_bytes(self, num_batch: int = 1) -> int:
         if self.model6:
@@ -1880,6 +1938,51 @@ class Runtime:
             self.last_logprobs = [(lp[off[r]:off[r] + lengths[r]].copy(), top_ids[off[r] * n:(off[r] + lengths[r]) * n].reshape(-1, n).copy(),
                                    tlp[off[r] * n:(off[r] + lengths[r]) * n].reshape(-1, n).copy()) for r in range(R)]
         return [(out[off[r]:off[r] + lengths[r]].copy(), int(reasons[r]), int(slots[r]), int(starts[r])) for r in range(R)], run.value
+
+    def generate_beam(self, first_tokens, steps: int, num_beams: int, stop=None, length_penalty: float = 0.0, logit_bias: "LogitBias" = None,
+                      bias_set=None, mode: int = 1, poll_steps: int = 0):
+        """Beam search kept on the device (wrk_v*_generate_beam): G = len(first_tokens) groups of `num_beams` beams on
+        state slots [0, G * num_beams); group g starts from the state in slot g * num_beams and feeds first_tokens[g].  Every step
+        keeps, per group, the num_beams best of the live beams' continuations and the finished hypotheses, ordered by
+        score / length ** length_penalty (score: the f32 sum of the tokens' log-probs), and moves the state slots accordingly, all
+        inside the step program.  stop: one list of ids for all groups, or one list per group; a hypothesis that draws one is finished,
+        the stop token its last.  logit_bias / bias_set (one set index per group; None: set 0): the beams see the biased row, so a
+        banned token is in no hypothesis.  Returns (per group: [(tokens, score, finished, slot)] by rank, steps_run); afterwards state
+        slot `slot` holds that hypothesis's state, having consumed everything but its last token.  `last_beam_steps` = (tokens,
+        parents, scores), each [steps_run, B]: what every step put in every slot (BEAM_NO_TOKEN: not filled)."""
+        ft = _u32(first_tokens).reshape(-1)
+        G, W, steps = ft.size, int(num_beams), int(steps)
+        B = G * max(W, 0)
+        ids, off = _stop_csr(stop, G, "groups")
+        gen, keep = GenerateOptions(), []
+        _fill_bias(gen, G, keep, logit_bias, bias_set)
+        gen.stop_tokens, gen.stop_offsets, gen.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
+        opt = BeamOptions(max(W, 0), float(length_penalty), C.pointer(gen))
+        n = max(B, 1)
+        tokens, lengths = np.zeros((n, max(steps, 1)), np.uint32), np.zeros(n, np.uint32)
+        scores, finished, slots, hyps = np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(max(G, 1), np.uint32)
+        st, sp, ss = (np.zeros((max(steps, 1), n), np.uint32), np.zeros((max(steps, 1), n), np.uint32), np.zeros((max(steps, 1), n), np.float32))
+        run, ms = C.c_uint32(), C.c_float()
+        res = BeamResult(_ptr(tokens, _u32p), _ptr(lengths, _u32p), _ptr(scores, _f32p), _ptr(finished, _u32p), _ptr(slots, _u32p),
+                         _ptr(hyps, _u32p), C.pointer(run), _ptr(st, _u32p), _ptr(sp, _u32p), _ptr(ss, _f32p))
+        fn, mdl = self._entry("generate_beam")
+        self.last_beam_steps = None
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), G, steps, C.byref(opt), C.byref(res), C.byref(ms), mode & 0xff))
+        self.last_beam_ms = ms.value
+        r = run.value
+        self.last_beam_steps = (st.reshape(-1)[:r * B].reshape(r, B).copy(), sp.reshape(-1)[:r * B].reshape(r, B).copy(),
+                                ss.reshape(-1)[:r * B].reshape(r, B).copy())
+        out = []
+        for g in range(G):
+            out.append([(tokens[g * W + k, :lengths[g * W + k]].copy(), float(scores[g * W + k]), bool(finished[g * W + k]), int(slots[g * W + k]))
+                        for k in range(int(hyps[g]))])
+        return out, r
+
+    def state_permute(self, parents):
+        """State slot q <- state slot parents[q] for q < len(parents), on the device and correct under any aliasing (swaps, chains,
+        many-to-one); slots with parents[q] == q move no bytes and slots >= len(parents) are untouched (wrk_v7_state_permute)."""
+        p = _u32(parents).reshape(-1)
+        self.ctx.check(hip.wrk_v7_state_permute(self.ctx.h, self.state, _ptr(p, _u32p), p.size))
 
     def state_back(self, batch: int) -> np.ndarray:
         """`State::back(batch)` -> [L, S+2, D] f32."""
