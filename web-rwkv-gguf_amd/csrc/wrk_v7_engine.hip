@@ -94,32 +94,33 @@ __device__ __forceinline__ void eng_copy_in(const void* src, uint32_t n16, ENG_L
     for (uint32_t q = lane; q < n16; q += 64) dst[q] = ((const u32x4*)src)[q];
 }
 
-// The ffn vector of K6 straight into a wave's register-resident inputs: lane L of wave w multiplies chunk c of every row, i.e. elements
-// [lo, lo + 16) and [hi, hi + 16) of the vector = 2 x 4 pieces of granules.  Each compute wave polls exactly the quarter of the vector
-// it multiplies (K is split over the four waves): no LDS round trip, no wave waits for another wave's quarter.
+// The ffn vector of K6.  Lane L of K-quarter wave kq multiplies chunk c of every row, i.e. elements [lo, lo + 16) and [hi, hi + 16) of
+// the vector = 2 x 4 pieces of granules.  A quarter has one wave per row group, and they multiply the same chunks: the wave of row
+// group 0 polls the `lo` pieces (half 0), the wave of row group 1 the `hi` pieces (half 1), so a CU fetches every granule once per
+// pass.  The 16 payload elements go to `xe` (LDS, the vector's own element order); every K6 wave reads its chunks back from there
+// behind the stage's first barrier (lds_x).  false: gave up.
 template <int KIND>
-__device__ __forceinline__ bool eng_sweep_x(const unsigned long long* g, uint32_t c, uint32_t tag, XRegs& x) {
+__device__ __forceinline__ bool eng_sweep_half(const unsigned long long* g, uint32_t c, uint32_t half, uint32_t tag, ENG_LDS f16* xe) {
     uint32_t lo, hi;
     chunk_xoff<KIND>(c, lo, hi);
-    const u32x4* pl = (const u32x4*)g + (lo >> 2);
-    const u32x4* ph = (const u32x4*)g + (hi >> 2);
-    u32x4 v[8];
+    const uint32_t off = half ? hi : lo;
+    const u32x4* p = (const u32x4*)g + (off >> 2);
+    u32x4 v[4];
     for (uint32_t spins = 0; spins < ENG_SPIN_MAX; ++spins) {
         asm volatile(
-            "global_load_dwordx4 %0, %8, off sc1\n\tglobal_load_dwordx4 %1, %8, off offset:16 sc1\n\tglobal_load_dwordx4 %2, %8, off offset:32 sc1\n\t"
-            "global_load_dwordx4 %3, %8, off offset:48 sc1\n\tglobal_load_dwordx4 %4, %9, off sc1\n\tglobal_load_dwordx4 %5, %9, off offset:16 sc1\n\t"
-            "global_load_dwordx4 %6, %9, off offset:32 sc1\n\tglobal_load_dwordx4 %7, %9, off offset:48 sc1\n\ts_waitcnt vmcnt(0)"
-            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-            : "v"(pl), "v"(ph)
+            "global_load_dwordx4 %0, %4, off sc1\n\tglobal_load_dwordx4 %1, %4, off offset:16 sc1\n\tglobal_load_dwordx4 %2, %4, off offset:32 sc1\n\t"
+            "global_load_dwordx4 %3, %4, off offset:48 sc1\n\ts_waitcnt vmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
+            : "v"(p)
             : "memory");
         bool ok = true;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) ok &= (v[i].y == tag) & (v[i].w == tag);
+        for (int i = 0; i < 4; ++i) ok &= (v[i].y == tag) & (v[i].w == tag);
         if (__all(ok)) {
 #pragma unroll
-            for (int h = 0; h < 4; ++h) {
+            for (int h = 0; h < 2; ++h) {
                 const u32x4 q = {v[2 * h].x, v[2 * h].z, v[2 * h + 1].x, v[2 * h + 1].z};
-                x.v[h] = __builtin_bit_cast(f16x8, q);
+                *(ENG_LDS u32x4*)(xe + off + 8 * h) = q;
             }
             return true;
         }
@@ -791,7 +792,10 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
 
         // ================================================ K6: x = x1 + ffn_value . k   (K over four waves, rows over NCW / 4 groups)
         {
-            // every compute wave polls its own K quarter of the ffn vector straight into registers (eng_sweep_x)
+            // The two waves (kq, 0) and (kq, 1) of a K quarter poll one half each of the quarter's granules into the exchange area `xe`
+            // (eng_sweep_half): a CU fetches the vector once per pass.  They poll whenever the workgroup has rows at all -- their own
+            // row group may be empty, their partner's is not.  `xe` lies over xs and K2's scratch, which nothing reads between K5's
+            // rows and the next layer's LN; the host has checked that it fits (wrk_v7_engine_create).
             constexpr uint32_t NG = NCW / 4;                // row groups
             const uint32_t kq = wave & 3u, grp = wave >> 2;
             const bool k6_wave = grp < NG;
@@ -800,23 +804,32 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             const uint32_t kpad = (F + 15u) & ~15u;
             const uint32_t nch = num_chunks<QK>(F, kpad);
             const uint32_t cbase = lane + 64u * kq;
-            XRegs x[1][XD];
+            ENG_LDS f16* xe = xs;
             bool swept = true;
+            if (grp < 2 && k6_rows > 0) {
 #pragma unroll
-            for (int ci = 0; ci < XD; ++ci) {
-                const uint32_t c = cbase + 256u * ci;
-                x[0][ci].s[0] = x[0][ci].s[1] = 0.0f;
-                const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-                x[0][ci].v[0] = x[0][ci].v[1] = x[0][ci].v[2] = x[0][ci].v[3] = z;
-                if (k6_wave && g_b < g_e && swept) swept = eng_sweep_x<QK>(A.gran + S.g_k, min(c, nch - 1), eng_tag(l, 3), x[0][ci]);
-                if (c >= nch) x[0][ci].v[0] = x[0][ci].v[1] = x[0][ci].v[2] = x[0][ci].v[3] = z;
-                x_sums<QK>(x[0][ci]);
+                for (int ci = 0; ci < XD; ++ci)
+                    if (swept) swept = eng_sweep_half<QK>(A.gran + S.g_k, min(cbase + 256u * ci, nch - 1), grp, eng_tag(l, 3), xe);
             }
             if (!swept && lane == 0) { *abort_flag = 1; atomicOr(A.fail, 16u); }
             ENG_STAMP0(l, 10);
-            ENG_BAR();                                      // ffn value rows in their slot (loader), every wave has its inputs
-            if (*abort_flag) break;
+            ENG_BAR();                                      // ffn value rows in their slot (loader), the whole ffn vector in xe
+            if (*abort_flag) break;                         // (xe is read behind this test only: a give-up feeds no row)
             ENG_STAMP0(l, 11);
+            // The read-back is unconditional (a wave without rows reads and drops it): behind the branch "this wave has rows" it cost
+            // 30 - 80 spilled registers in every instantiation (profiles/ffn_sweep_resource_usage.txt).
+            XRegs x[1][XD];
+#pragma unroll
+            for (int ci = 0; ci < XD; ++ci) {
+                const uint32_t c = cbase + 256u * ci;
+                x[0][ci] = lds_x<QK>(xe, min(c, nch - 1));
+                if (c >= nch) {
+                    const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+                    x[0][ci].v[0] = x[0][ci].v[1] = x[0][ci].v[2] = x[0][ci].v[3] = z;
+                }
+                x_sums<QK>(x[0][ci]);
+            }
+            ENG_STAMP0(l, 15);
             const lds_u8* slot = smem + S.lds_slot6;
             if (k6_wave)
                 for (uint32_t ri = g_b; ri < g_e; ri += 4) {
@@ -998,14 +1011,17 @@ int32_t wrk_v7_engine_create(wrk_v7_model* m, wrk_v7_engine** out) {
     S.lds_xraw0 = take(D * 2);
     S.lds_xraw1 = take(D * 2);
     const uint32_t naux = S.rw + S.ra + S.rg + S.rv;
-    S.lds_xs = take(D * 2 + up((naux + 192) * 2, 16) + 1280 * 4);      // a stage's input vector (D elements); K2's scratch lives behind it
     S.lds_ln = take(D * 2);
     S.lds_misc = take(4096);
-    S.lds_total = off;
+    S.lds_xs = take(D * 2 + up((naux + 192) * 2, 16) + 1280 * 4);      // a stage's input vector (D elements); K2's scratch lives behind it
     int lds_max = 0;
     hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device);
     if (lds_max < 160 * 1024) lds_max = 160 * 1024;      // gfx950: 160 KiB per workgroup (the attribute reports the 64 KiB default limit on some stacks)
-    if (S.lds_total > (uint32_t)lds_max) { delete e; return no("weights of a layer do not fit the LDS"); }
+    if (off > (uint32_t)lds_max) { delete e; return no("weights of a layer do not fit the LDS"); }
+    // K6's exchange area (the ffn vector, F elements) lies over the xs block, which is dead from K5's rows to the next layer's LN, and
+    // over the unused tail behind it: the xs block comes last for that (1.5B: 142 KB in front of it, 11 KB of its own, 16 KB needed)
+    S.lds_total = std::max(off, S.lds_xs + F * 2);
+    if (S.lds_total > (uint32_t)lds_max) { delete e; return no("the ffn vector's exchange area does not fit the LDS behind a layer's weights"); }
     // ---- granules
     S.g_aux = naux / 2;
     uint32_t g = 0;
@@ -1217,6 +1233,7 @@ void wrk_v7_engine_report(wrk_v7_engine* e) {
     col(0, 10, "K6 own quarter of the ffn vector swept, wave 0");
     col(-1, 10, "K6 swept, slowest wave");
     col(0, 11, "K6 start");
+    col(-1, 15, "K6 inputs read back from LDS, slowest wave");
     col(-1, 12, "K6 partial sums done, slowest wave");
     col(0, 13, "K6 published");
     col(Ld, 0, "loader: K1 slot free, next layer's fill issued");
