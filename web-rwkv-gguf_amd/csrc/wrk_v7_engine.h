@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "wrk_internal.h"
+#include "wrk_lora2_pack.h"
 
 namespace wrk {
 
@@ -22,7 +23,6 @@ struct EngShape {
     uint32_t D, F, H, nwg;
     uint32_t rw, ra, rg, rv;                        // LoRA ranks
     uint32_t rb_d, rb_f;                            // device row bytes of the D-wide / F-wide quantised matrices
-    uint32_t rb_w2, rb_a2, rb_g2, rb_v2;            // row bytes of the F16 up-projections
     EngJob k1[ENG_K1_JOBS];
     uint32_t k3_rpw, k5_rpw, k6_rpw;                // rows per workgroup of W_o, ffn key, ffn value
     // LDS layout, byte offsets
@@ -38,7 +38,6 @@ struct EngShape {
 // matrix pointers of a layer (read by the loader wave a layer ahead, and by the head workgroups once per layer)
 struct EngLayer {
     const uint8_t *w_r, *w_k, *w_v, *w1, *a1, *g1, *v1;      // K1 (v1 unused on layer 0)
-    const uint8_t *w2, *a2, *g2, *v2;                        // K2, F16 rows
     const uint8_t *w_o, *ffn_k, *ffn_v;
 };
 // The f16 vectors of every layer are PACKED into one buffer [L][ENG_NV][D] when the engine is built, so that a stage computes their
@@ -53,6 +52,7 @@ struct EngArgs {
     EngShape S;
     const EngLayer* layers;         // [num_layer]
     const void* vecs;               // f16 [num_layer][ENG_NV][D]
+    const uint8_t* l2;              // K2's LoRA up-projections w2, a2, g2, v2 of every layer, packed per head (wrk_lora2_pack.h): [num_layer][H] runs of pieces
     const float* scal;              // [num_layer][ENG_NS]
     unsigned long long* gran;       // granule buffer, zeroed before every launch
     const void* x_in;               // f16 [D]: input of layer_begin (embedding LN output); with x_row: base of a table of such rows

@@ -205,6 +205,17 @@ __device__ __forceinline__ float eng_lora_dot(const f16x8 (&w)[MAXCH], const ENG
     return acc;
 }
 
+// NP pieces of a LoRA-2 unit from the packed image (wrk_lora2_pack.h), lane's 16 bytes of piece n into w[n]; the registers without a piece
+// are zeroed (eng_lora_dot never multiplies them)
+template <int NP>
+__device__ __forceinline__ void eng_l2_load(f16x8 (&w)[8], const uint8_t* up) {
+#pragma unroll
+    for (int n = 0; n < NP; ++n) w[n] = *(const f16x8*)(up + n * ENG_L2_PIECE_BYTES);
+    const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int n = NP; n < 8; ++n) w[n] = z;
+}
+
 // what the epilogue of a row does with its dot product
 struct EngFin {
     uint32_t act;           // activation
@@ -287,16 +298,14 @@ __device__ __forceinline__ void eng_publish(const ENG_LDS uint32_t* pub, uint32_
     for (uint32_t i = lane; 2 * i < nrows; i += 64) eng_store_granule(gran + gidx(row0 + 2 * i), tag, pub[i]);
 }
 
-// LN + token shift of the layer input (dmv_body PRO 1, one input vector): x (LDS, f16) -> xs = mix(LN(x), prev, mixw), ln_out = LN(x).
-// Two barriers inside.  The first four waves do the work (the 256-thread mapping of the launches: same partial sums); `active` = this
-// wave is one of them.  VPT vectors of 8 channels per thread.
+// The statistics of an LN over x (LDS, f16 [K]), in the 256-thread mapping of the launches (same partial sums): the first four waves
+// (`active`) keep their VPT vectors of 8 channels in xv, sum them shifted by c0 = x[0], and leave one partial sum per wave in red[0, 8).
+// A barrier later eng_ln_stats gives every thread that asks the same mean and 1 / deviation.
 template <int VPT>
-__device__ __forceinline__ void eng_ln_mix(bool active, const ENG_LDS f16* xraw, ENG_LDS f16* xs, ENG_LDS f16* ln_out, ENG_LDS float* red, uint32_t K, float eps,
-                                           const f16x8 (&wv)[VPT], const f16x8 (&bv)[VPT], const f16x8 (&mv)[VPT], const f32x4 (&pv)[VPT][2],
-                                           uint32_t tid, uint32_t lane, uint32_t wave) {
+__device__ __forceinline__ void eng_ln_partial(bool active, const ENG_LDS f16* xraw, ENG_LDS float* red, uint32_t K, f16x8 (&xv)[VPT], float& c0, uint32_t tid,
+                                               uint32_t lane, uint32_t wave) {
     const uint32_t nvec = K >> 3;
-    f16x8 xv[VPT];
-    float c0 = 0.0f;
+    c0 = 0.0f;
     if (active) {
 #pragma unroll
         for (int v = 0; v < VPT; ++v) xv[v] = *(const ENG_LDS f16x8*)(xraw + min(tid + 256u * v, nvec - 1) * 8);
@@ -311,13 +320,29 @@ __device__ __forceinline__ void eng_ln_mix(bool active, const ENG_LDS f16* xraw,
         s2 = wave_sum(s2);
         if (lane == 0) { red[wave] = s1; red[4 + wave] = s2; }
     }
+}
+__device__ __forceinline__ void eng_ln_stats(const ENG_LDS float* red, float c0, uint32_t K, float eps, float& mean, float& dev) {
+    const float a1 = (red[0] + red[1]) + (red[2] + red[3]);
+    const float a2 = (red[4] + red[5]) + (red[6] + red[7]);
+    const float md = a1 / (float)K;
+    mean = c0 + md;
+    dev = 1.0f / sqrtf(fmaxf(a2 / (float)K - md * md, 0.0f) + eps);
+}
+
+// LN + token shift of the layer input (dmv_body PRO 1, one input vector): x (LDS, f16) -> xs = mix(LN(x), prev, mixw), ln_out = LN(x).
+// Two barriers inside.  The first four waves do the work; `active` = this wave is one of them.
+template <int VPT>
+__device__ __forceinline__ void eng_ln_mix(bool active, const ENG_LDS f16* xraw, ENG_LDS f16* xs, ENG_LDS f16* ln_out, ENG_LDS float* red, uint32_t K, float eps,
+                                           const f16x8 (&wv)[VPT], const f16x8 (&bv)[VPT], const f16x8 (&mv)[VPT], const f32x4 (&pv)[VPT][2],
+                                           uint32_t tid, uint32_t lane, uint32_t wave) {
+    const uint32_t nvec = K >> 3;
+    f16x8 xv[VPT];
+    float c0;
+    eng_ln_partial<VPT>(active, xraw, red, K, xv, c0, tid, lane, wave);
     ENG_BAR();
     if (active) {
-        const float a1 = (red[0] + red[1]) + (red[2] + red[3]);
-        const float a2 = (red[4] + red[5]) + (red[6] + red[7]);
-        const float md = a1 / (float)K;
-        const float mean = c0 + md;
-        const float dev = 1.0f / sqrtf(fmaxf(a2 / (float)K - md * md, 0.0f) + eps);
+        float mean, dev;
+        eng_ln_stats(red, c0, K, eps, mean, dev);
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {
             const uint32_t i = tid + 256u * v;
@@ -559,10 +584,11 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
         const float* scl = A.scal + (size_t)l * ENG_NS;
         const float sc_k1 = scl[j1 < ENG_K1_JOBS ? j1 : 0u], sc_o = scl[ENG_S_O], sc_fk = scl[ENG_S_FK], sc_fv = scl[ENG_S_FV];
 
-        // ---- requests that depend on nothing: LN1 operands (the four LN waves)
+        // ---- requests that depend on nothing: LN1 operands (the four LN waves).  A head workgroup has no K1 rows: it asks for the 64
+        // channels of the LN it keeps instead (below)
         f16x8 wv[VPT], bv[VPT], mv[VPT];
         f32x4 pv[VPT][2];
-        if (ln_wave) {
+        if (ln_wave && !is_head) {
             const f16* mixp = lvec(ENG_V_MIX0 + (j1 < ENG_K1_JOBS ? S.k1[j1].mix : 0u));
 #pragma unroll
             for (int v = 0; v < VPT; ++v) {
@@ -620,19 +646,39 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
         } else {
             // ================================================ K1 on a head workgroup: no rows; the LoRA up-projection rows, per-channel
             // vectors and the state of K2 are requested NOW, a whole stage before they are needed (80 KB through one CU take 2 - 3 us).
-            // The compute waves stall ISSUING them: this workgroup passes the barrier below at ~2.9 us.  Requested behind that barrier,
+            // Its LN1 is 64 channels wide, so it asks for no shift state, no mix vector and 64 elements of the LN weight and bias.
+            // The compute waves stall ISSUING them: this workgroup passes the barrier below at ~2.6 us, with 64 coalesced loads as with the
+            // 128 gathers before them (profiles/lora2_pack_ab.txt: one CU takes in 80 KB at ~32 GB/s).  Requested behind that barrier,
             // or with LN moved behind K2's barrier (1), the step was 3 % / 1 % slower (profiles/engine_sched_ab.txt).
-            const EngLayer& Lp = A.layers[l];
-            const uint8_t* p_m[4] = {Lp.w2, Lp.a2, Lp.g2, layer0 ? Lp.w2 : Lp.v2};
-            const uint32_t rbm[4] = {S.rb_w2, S.rb_a2, S.rb_g2, layer0 ? S.rb_w2 : S.rb_v2};
-            const uint32_t rkm[4] = {S.rw, S.ra, S.rg, layer0 ? S.rw : S.rv};
+            f16 h_lnw = 0, h_lnb = 0;                          // first in wave 1's queue: its LN waits for these two only
+            if (wave == 1) { h_lnw = lvec(ENG_V_LN1W)[c0 + lane]; h_lnb = lvec(ENG_V_LN1B)[c0 + lane]; }
+            // The LoRA rows come from the layer's packed image (wrk_lora2_pack.h): a unit is a run of 1 KB pieces in load order, and a
+            // wave loads the pieces that exist (32 n < rank) -- 64 loads of consecutive bytes per workgroup at 1.5B, where the matrices
+            // themselves took 128 loads of 64-byte pieces out of 16 rows each, half of them clamped re-reads that no dot used.  The same
+            // 16 bytes reach the same lu[i][n] of the same lane.  A register without a piece is zero and never multiplied (eng_lora_dot);
+            // layer 0's image has zeros for the value LoRA it does not have, and its dots are dropped below.  The image's address is
+            // computed from a kernel argument, as the vectors' is: behind a pointer of EngLayer the loads were flat loads (they count
+            // against lgkmcnt, so every ENG_BAR waited for them) behind a dependent fetch of the pointer.  One jump on the piece count
+            // to a straight run of NP loads (profiles/lora2_pack_resource_usage.txt).
+            const EngLora2Ranks R2{S.rw, S.ra, S.rg, S.rv};
+            const uint8_t* l2_head = A.l2 + (l * eng_l2_layer_bytes(R2, S.H) + eng_l2_piece(R2, head, 0, 0) * ENG_L2_PIECE_BYTES);
             f16x8 lu[MAXU][8];
 #pragma unroll
             for (int i = 0; i < MAXU; ++i) {
-                const uint32_t u = min(wave + (uint32_t)i * NCW, 15u), mi = u >> 2, bi = u & 3u;     // a wave without a second unit re-reads unit 15
-                const f16* rowp = (const f16*)(p_m[mi] + (size_t)(c0 + 16u * bi + (lane >> 2)) * rbm[mi]);
-#pragma unroll
-                for (int n = 0; n < 8; ++n) lu[i][n] = *(const f16x8*)(rowp + min((lane & 3u) * 8 + 32 * n, rkm[mi] - 8));
+                const uint32_t u = wave + (uint32_t)i * NCW;                                          // a wave without a second unit loads nothing
+                const uint32_t np = u < ENG_L2_UNITS ? eng_l2_pieces(eng_l2_rank(R2, u >> 2)) : 0u;
+                const uint8_t* up = l2_head + (eng_l2_unit_piece(R2, u) * ENG_L2_PIECE_BYTES + lane * 16u);
+                switch (np) {
+                    case 1: eng_l2_load<1>(lu[i], up); break;
+                    case 2: eng_l2_load<2>(lu[i], up); break;
+                    case 3: eng_l2_load<3>(lu[i], up); break;
+                    case 4: eng_l2_load<4>(lu[i], up); break;
+                    case 5: eng_l2_load<5>(lu[i], up); break;
+                    case 6: eng_l2_load<6>(lu[i], up); break;
+                    case 7: eng_l2_load<7>(lu[i], up); break;
+                    case 8: eng_l2_load<8>(lu[i], up); break;
+                    default: eng_l2_load<0>(lu[i], up); break;
+                }
             }
             float Sreg[16];
             const uint32_t ci64 = tid & 63u, g4 = tid >> 6;
@@ -647,10 +693,31 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
                 h_w0 = lvec(ENG_V_W0)[cc]; h_a0 = lvec(ENG_V_A0)[cc]; h_kk = lvec(ENG_V_KK)[cc]; h_ka = lvec(ENG_V_KA)[cc]; h_v0 = lvec(ENG_V_V0)[cc];
                 h_gnw = lvec(ENG_V_GNW)[cc]; h_gnb = lvec(ENG_V_GNB)[cc]; h_rk = lvec(ENG_V_RK)[cc];
             }
+            ENG_STAMP0(l, 19);
             ENG_BAR();                                      // x in xraw0
             if (*abort_flag) break;
             ENG_STAMP0(l, 1);
-            eng_ln_mix<VPT>(ln_wave, xraw0, xs, lnbuf, red, D, eps, wv, bv, mv, pv, tid, lane, wave);
+            // LN1 of a head workgroup: all that reads it is the att shift state of the head's own 64 channels (wave 1, behind barrier
+            // (2)); nothing reads xs before K3's gather overwrites it.  So: eng_ln_mix's statistics, bit for bit (the same four waves,
+            // elements and sums), then ONE wave normalises its 64 channels with eng_ln_mix's expression; no shift, no mix, and the same
+            // ENG_LN_BARRIERS barriers, which the loader and the gather wave replay.
+            {
+                f16x8 xv[VPT];
+                float x0;
+                eng_ln_partial<VPT>(ln_wave, xraw0, red, D, xv, x0, tid, lane, wave);
+                ENG_BAR();
+                if (wave == 1) {
+                    float mean, dev;
+                    eng_ln_stats(red, x0, D, eps, mean, dev);
+                    // The f32 result is made opaque before it is rounded to f16: for a lone `(f16)fmaf(..)` the compiler emits
+                    // v_fma_mixlo_f16, which rounds the exact sum ONCE, where eng_ln_mix's eight-wide form is v_fma_f32 + v_cvt_f16_f32
+                    // (rounded to f32, then to f16) -- one channel in a few thousand differed by an f16 ulp.
+                    float y = __builtin_fmaf(((float)xraw0[c0 + lane] - mean) * dev, (float)h_lnw, (float)h_lnb);
+                    asm volatile("" : "+v"(y));
+                    lnbuf[c0 + lane] = (f16)y;
+                }
+                ENG_BAR();
+            }
             ENG_STAMP0(l, 3);
             ENG_BAR();                                      // K1 done
 
@@ -670,7 +737,7 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
                     const uint32_t u = wave + (uint32_t)i * NCW;
                     if (u < 16u) {
                         const uint32_t mi = u >> 2, bi = u & 3u;
-                        const float dd = eng_lora_dot<8>(lu[i], auxm[mi], rkm[mi], lane & 3u);
+                        const float dd = eng_lora_dot<8>(lu[i], auxm[mi], eng_l2_rank(R2, mi), lane & 3u);
                         if ((lane & 3u) == 0) sh_d[mi * 64 + 16 * bi + (lane >> 2)] = dd;
                     }
                 }
@@ -896,6 +963,7 @@ struct wrk_v7_engine {
     unsigned long long* gran = nullptr;     // device
     uint32_t* fail = nullptr;               // device (pinned readable through memcpy)
     unsigned long long* stamps = nullptr;   // device, WRK_TIMING=1
+    uint8_t* l2pack = nullptr;              // device: the packed LoRA up-projections of every layer (wrk_lora2_pack.h)
     void* emb_ln = nullptr;                 // device f16 [V][D]: LN(ln0) of every embedding row (the same kernel as the step's embedding launch)
     bool r16 = false;
     int xd = 1, ncw = 8;
@@ -940,7 +1008,8 @@ int32_t wrk_v7_engine_create(wrk_v7_model* m, wrk_v7_engine** out) {
         for (const wrk_matrix* q : lo)
             if (!q || q->kind != WRK_MAT_F16) return no("LoRA matrices must be F16");
         if (L.w_r->k != D || L.w_r->m != D || L.ffn_w_k->m != F || L.ffn_w_v->k != F || L.w1->m != d.lora_w || L.a1->m != d.lora_a ||
-            L.g1->m != d.lora_g || (li && L.v1->m != d.lora_v))
+            L.g1->m != d.lora_g || (li && L.v1->m != d.lora_v) || L.w2->k != d.lora_w || L.a2->k != d.lora_a || L.g2->k != d.lora_g ||
+            (li && L.v2->k != d.lora_v) || L.w2->m != D || L.a2->m != D || L.g2->m != D || (li && L.v2->m != D))
             return no("matrix shapes");
     }
     if (quant != WRK_MAT_Q4_K) return no("only Q4_K matrices so far");
@@ -955,14 +1024,10 @@ int32_t wrk_v7_engine_create(wrk_v7_model* m, wrk_v7_engine** out) {
     S.D = D; S.F = F; S.H = H; S.nwg = NWG;
     S.rw = d.lora_w; S.ra = d.lora_a; S.rg = d.lora_g; S.rv = d.lora_v;
     const auto& L0 = m->layers[0];
-    const auto& L1 = m->layers[m->layers.size() > 1 ? 1 : 0];
     S.rb_d = (uint32_t)L0.w_r->row_bytes; S.rb_f = (uint32_t)L0.ffn_w_v->row_bytes;
-    S.rb_w2 = (uint32_t)L0.w2->row_bytes; S.rb_a2 = (uint32_t)L0.a2->row_bytes; S.rb_g2 = (uint32_t)L0.g2->row_bytes;
-    S.rb_v2 = (uint32_t)(m->layers.size() > 1 ? L1.v2->row_bytes : L0.a2->row_bytes);
     for (const auto& L : m->layers) {
         if (L.w_r->row_bytes != S.rb_d || L.w_k->row_bytes != S.rb_d || L.w_v->row_bytes != S.rb_d || L.w_o->row_bytes != S.rb_d ||
-            L.ffn_w_k->row_bytes != S.rb_d || L.ffn_w_v->row_bytes != S.rb_f || L.w2->row_bytes != S.rb_w2 || L.a2->row_bytes != S.rb_a2 ||
-            L.g2->row_bytes != S.rb_g2) { delete e; return no("row strides differ between layers"); }
+            L.ffn_w_k->row_bytes != S.rb_d || L.ffn_w_v->row_bytes != S.rb_f) { delete e; return no("row strides differ between layers"); }
     }
     // ---- K1: workgroups to matrices in proportion to bytes; rows per workgroup a multiple of 8 (4 waves x row pairs)
     const uint32_t rb_l = (uint32_t)L0.w1->row_bytes;
@@ -1045,7 +1110,6 @@ int32_t wrk_v7_engine_create(wrk_v7_model* m, wrk_v7_engine** out) {
         EngLayer& o = hl[li];
         o.w_r = L.w_r->data; o.w_k = L.w_k->data; o.w_v = L.w_v->data; o.w1 = L.w1->data; o.a1 = L.a1->data; o.g1 = L.g1->data;
         o.v1 = li ? L.v1->data : L.a1->data;
-        o.w2 = L.w2->data; o.a2 = L.a2->data; o.g2 = L.g2->data; o.v2 = li ? L.v2->data : L.a2->data;
         o.w_o = L.w_o->data; o.ffn_k = L.ffn_w_k->data; o.ffn_v = L.ffn_w_v->data;
         const wrk_matrix* k1m[ENG_K1_JOBS] = {L.w_r, L.w_k, L.w_v, L.w1, L.a1, L.g1, li ? L.v1 : L.a1};
         float* sc = hs.data() + li * ENG_NS;
@@ -1061,6 +1125,34 @@ int32_t wrk_v7_engine_create(wrk_v7_model* m, wrk_v7_engine** out) {
         for (int i = 0; i < ENG_NV; ++i) {
             if (!src[i] || src[i]->bytes < (size_t)D * 2) { wrk_v7_engine_destroy(e); return no("a layer vector is missing"); }
             if ((er = hipMemcpy((char*)e->vecs + (li * ENG_NV + i) * (size_t)D * 2, src[i]->ptr, (size_t)D * 2, hipMemcpyDeviceToDevice)) != hipSuccess) return fail_alloc(er);
+        }
+    }
+    // The LoRA up-projections of every layer, packed per head in the order a head workgroup loads them (wrk_lora2_pack.h), once: the rows
+    // never change after load.  H x 64 KB per layer at 1.5B (48 MB) beside the matrices themselves, which the launches and prefill keep.
+    {
+        const EngLora2Ranks R2{S.rw, S.ra, S.rg, S.rv};
+        const size_t lb = eng_l2_layer_bytes(R2, H), total_l2 = lb * m->layers.size();
+        if ((er = hipMalloc((void**)&e->l2pack, total_l2)) != hipSuccess) {
+            (void)hipGetLastError();
+            wrk_v7_engine_destroy(e);
+            return wrk_fail(ctx, WRK_E_UNSUPPORTED, "decode engine: %zu bytes for the packed LoRA up-projections refused (%s)", total_l2, hipGetErrorString(er));
+        }
+        std::vector<uint8_t> img(lb), rows[4];
+        for (size_t li = 0; li < m->layers.size(); ++li) {
+            const auto& L = m->layers[li];
+            const wrk_matrix* mats[4] = {L.w2, L.a2, L.g2, li ? L.v2 : nullptr};
+            const uint8_t* src[4] = {nullptr, nullptr, nullptr, nullptr};
+            size_t rbs[4] = {0, 0, 0, 0};
+            for (int i = 0; i < 4; ++i) {
+                if (!mats[i]) continue;
+                rbs[i] = mats[i]->row_bytes;
+                if (rbs[i] < (size_t)eng_l2_rank(R2, i) * 2) { wrk_v7_engine_destroy(e); return no("a LoRA up-projection's rows are shorter than its rank"); }
+                rows[i].resize((size_t)D * rbs[i]);
+                if ((er = hipMemcpy(rows[i].data(), mats[i]->data, rows[i].size(), hipMemcpyDeviceToHost)) != hipSuccess) return fail_alloc(er);
+                src[i] = rows[i].data();
+            }
+            eng_l2_pack_layer(R2, H, src, rbs, img.data());
+            if ((er = hipMemcpy(e->l2pack + li * lb, img.data(), lb, hipMemcpyHostToDevice)) != hipSuccess) return fail_alloc(er);
         }
     }
     if ((er = hipMalloc((void**)&e->scal, hs.size() * 4)) != hipSuccess) return fail_alloc(er);
@@ -1134,6 +1226,7 @@ int wrk_v7_engine_waves(const wrk_v7_engine* e) { return e ? e->ncw : 0; }
 void wrk_v7_engine_destroy(wrk_v7_engine* e) {
     if (!e) return;
     if (e->emb_ln) hipFree(e->emb_ln);
+    if (e->l2pack) hipFree(e->l2pack);
     if (e->layers) hipFree(e->layers);
     if (e->vecs) hipFree(e->vecs);
     if (e->scal) hipFree(e->scal);
@@ -1151,7 +1244,7 @@ int32_t wrk_v7_engine_enqueue(wrk_v7_engine* e, hipStream_t q, wrk_v7_state* st,
     EngArgs A{};
     A.S = e->S;
     A.S.layer_begin = l0; A.S.layer_end = l1; A.S.batch = batch;
-    A.layers = e->layers; A.vecs = e->vecs; A.scal = e->scal; A.gran = e->gran; A.x_in = x_in; A.x_out = x_out; A.v_first = v_first;
+    A.layers = e->layers; A.vecs = e->vecs; A.l2 = e->l2pack; A.scal = e->scal; A.gran = e->gran; A.x_in = x_in; A.x_out = x_out; A.v_first = v_first;
     if (token && e->emb_ln && l0 == 0) { A.x_in = e->emb_ln; A.x_row = token; }
     A.state = st->data; A.num_batch = st->num_batch; A.fail = e->fail; A.stamps = e->stamps; A.stamp_layer = std::min(5u, l1 - 1);
     // every polled word zeroed before every launch (a memset node, replayed first): tags are > 0 and unique within a launch
@@ -1209,6 +1302,7 @@ void wrk_v7_engine_report(wrk_v7_engine* e) {
     fprintf(stderr, "[WRK_TIMING] decode engine (%d compute waves), one layer of the last token; us since the layer's first stamp\n", e->ncw);
     col(G, 0, "gather: layer input complete, workgroups without a head", 0);
     col(G, 0, "gather: layer input complete, head workgroups", 1);
+    col(-1, 19, "operand requests issued, slowest wave, head workgroups", 1);
     col(0, 1, "K1 start (input + weights in LDS), wave 0, no head", 0);
     col(0, 1, "K1 start (input in LDS), wave 0, head workgroups", 1);
     col(0, 2, "K1 LN + shift done, wave 0");
