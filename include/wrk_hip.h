@@ -1001,6 +1001,18 @@ int32_t wrk_v6_generate_queue_pool(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_sta
 int32_t wrk_v6_generate_beam(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
                              uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null, uint32_t mode);
 
+/* Parity instrumentation, as wrk_v7_infer_layer / wrk_v7_frame_read (RWKV-6 has no layer-0 value to carry):
+ *   wrk_v6_infer_layer: run ONLY `layer` of a job on a caller-supplied layer input x (f16 [D, num_token]) and the state as it stands;
+ *                       the launches are the ones wrk_v6_infer picks for these cursors and this mode (mode 1, one token per sequence:
+ *                       the fused 7-launch layer, or the op list where it declines; mode 1 otherwise: the merged op list).  The halving
+ *                       after every `rescale`-th layer is part of that layer.  Blocking; not inside a capture.
+ *   wrk_v6_frame_read : TensorGpu::back of one frame buffer by name, in its own dtype.  f16: x, att_x, att_xx, aux_x, att_sx (5 planes
+ *                       [5][num_token][D]), att_w, att_g, att_o, tmx, tmt, tm (5 planes), ffn_x, ffn_kx, ffn_rx, ffn_k, ffn_v, ffn_r;
+ *                       f32: att_k, att_v, att_r, time_decay.  dst NULL: only *bytes is set. */
+int32_t wrk_v6_infer_layer(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t layer, const void* x, const uint32_t* cursors,
+                           uint32_t num_token, uint32_t mode);
+int32_t wrk_v6_frame_read(wrk_ctx* ctx, wrk_v6_model* model, const char* name, uint32_t num_token, void* dst, size_t capacity, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,23 +98,56 @@ class V6Runtime:
         info = model.info
         self.state = np.zeros((info.num_layer, num_batch, info.head_size + 2, info.num_emb), np.float32)
         self.rnd = r16 if act_f16 else _id
+        self.trace: Optional[Dict[str, np.ndarray]] = None     # when a dict: every stored stage of every layer, see _layer
 
     def _mm(self, w, x, act="none", f32_out=False):
         y = ACT[act](np.matmul(x.astype(np.float32), w.T.astype(np.float32)).astype(np.float32))
         return y if f32_out else self.rnd(y)
 
+    def _rec(self, layer, name, val):
+        if self.trace is not None:
+            self.trace[f"{layer}_{name}"] = np.array(val, copy=True)
+
+    @staticmethod
+    def _chunks(lens):
+        """Per stacked token: batch, first token of its chunk, chunk length, is-first, is-last (from the packed cursors)."""
+        cur = stack_cursors(lens)
+        batches = np.array([c & 0xFF for c in cur]); starts = np.array([(c >> 8) & 0xFFFF for c in cur]); clens = np.array([c >> 24 for c in cur])
+        idx = np.arange(len(cur))
+        return batches, starts, clens, idx == starts, (idx - starts + 1) == clens
+
     def infer_chunk(self, chunk_tokens: List[List[int]], headers: List[int]) -> np.ndarray:
         m, info, rnd = self.model, self.model.info, self.rnd
-        D, S, H, R = info.num_emb, info.head_size, info.num_head, info.custom["time_mix"]
         lens = [len(c) for c in chunk_tokens]
         T = sum(lens)
         if T == 0:
             return np.zeros((0, info.num_vocab), np.float32)
-        cur = stack_cursors(lens)
-        batches = np.array([c & 0xFF for c in cur]); starts = np.array([(c >> 8) & 0xFFFF for c in cur]); clens = np.array([c >> 24 for c in cur])
-        idx = np.arange(T)
-        firsts, lasts = idx == starts, (idx - starts + 1) == clens
+        where = self._chunks(lens)
         tokens = np.concatenate([np.asarray(c, dtype=np.int64) for c in chunk_tokens if len(c)])
+        x = rnd(layer_norm(m.emb[tokens], m.ln0[0], m.ln0[1], LN_EPS))
+        if self.trace is not None:
+            self.trace["emb_x"] = np.array(x, copy=True)
+        for li in range(len(m.layers)):
+            x = self._layer(li, x, where)
+        if not headers:
+            return np.zeros((0, info.num_vocab), np.float32)
+        hx = rnd(layer_norm(x[np.asarray(headers)], m.ln_out[0], m.ln_out[1], LN_EPS))
+        return np.matmul(hx, m.head.T.astype(np.float32)).astype(np.float32)
+
+    def infer_layer(self, li: int, x: np.ndarray, chunk_lens: List[int]) -> np.ndarray:
+        """Layer `li` alone on the layer input x [T, D] and the state as it stands (teacher-forced runs): the layer's output, after the
+        halving where the layer has one.  Records into `trace` like infer_chunk."""
+        assert sum(chunk_lens) == len(x) > 0
+        return self._layer(li, self.rnd(np.asarray(x, np.float32)), self._chunks(chunk_lens))
+
+    def _layer(self, li: int, x: np.ndarray, where) -> np.ndarray:
+        """dispatch_layer (v6.rs:701-958) on the stacked tokens x [T, D]; every stored stage goes to `trace` under f"{li}_{stage}"."""
+        m, info, rnd = self.model, self.model.info, self.rnd
+        D, S, H, R = info.num_emb, info.head_size, info.num_head, info.custom["time_mix"]
+        batches, starts, clens, firsts, lasts = where
+        T = len(x)
+        p, st = m.layers[li], self.state[li]
+        rec = lambda name, val: self._rec(li, name, val)
 
         def shift(xv, state_row, fac):                     # fac [D] or [T, D]
             prev = np.empty_like(xv)
@@ -123,54 +156,63 @@ class V6Runtime:
                 prev[t] = state_row[batches[t]]
             return rnd(mix(xv, prev, fac if fac.ndim == 2 else fac[None, :]))
 
-        x = rnd(layer_norm(m.emb[tokens], m.ln0[0], m.ln0[1], LN_EPS))
-        for li, p in enumerate(m.layers):
-            st = self.state[li]
-            att_x = rnd(layer_norm(x, p["ln1_w"], p["ln1_b"], LN_EPS))
-            row0 = st[:, 0, :]
-            att_xx = shift(att_x, row0, p["time_mix_x"])
-            tmx = self._mm(p["time_mix_w1"], att_xx, "tanh")                                   # [T, 5R] == [R, 5, T]
-            tmx = tmx.reshape(T, 5, R)
-            tm = np.stack([self._mm(p["time_mix_w2"][i], tmx[:, i, :]) for i in range(5)])     # [5, T, D]
-            tm = rnd(p["time_mix"][:, None, :] + tm)                                           # add(time_mix, buffer.time_mix)
-            sx = [shift(att_x, row0, tm[i]) for i in range(5)]                                 # w, k, v, r, g
-            k = self._mm(p["w_k"], sx[1], f32_out=True)
-            v = self._mm(p["w_v"], sx[2], f32_out=True)
-            r = self._mm(p["w_r"], sx[3], f32_out=True)
-            g = self._mm(p["w_g"], sx[4])
-            aw = self._mm(p["time_decay_w1"], sx[0], "tanh")
-            td = self._mm(p["time_decay_w2"], aw, f32_out=True)
-            td = (p["time_decay"][None, :] + td).astype(np.float32)
-            td = np.exp(-np.exp(td, dtype=np.float32), dtype=np.float32)                       # StableExp, f32 buffer
-            u = p["time_first"].reshape(H, S)
-            y = np.empty((T, D), np.float32)
-            for t in range(T):
-                b = batches[t]
-                if lasts[t]:
-                    st[b, 0, :] = att_x[starts[t] + clens[t] - 1]
-                Sm = st[b, 1:S + 1, :].reshape(S, H, S).transpose(1, 0, 2)                     # [H, j, i]
-                kt, vt, rt, wt = (z[t].reshape(H, S) for z in (k, v, r, td))
-                kv = kt[:, :, None] * vt[:, None, :]
-                y[t] = np.einsum("hj,hji->hi", rt, u[:, :, None] * kv + Sm).reshape(D)
-                st[b, 1:S + 1, :] = (wt[:, :, None] * Sm + kv).astype(np.float32).transpose(1, 0, 2).reshape(S, D)
-            aux = rnd(y)
-            aux = rnd(layer_norm(aux.reshape(T, H, S), p["gn_w"].reshape(H, S)[None], p["gn_b"].reshape(H, S)[None], GN_EPS).reshape(T, D))
-            att_x = rnd(silu(g) * aux)                                                         # mul_activate(att_g Silu, att_x)
-            o = self._mm(p["w_o"], att_x)
-            x = rnd(o + x)
-            ffn_x = rnd(layer_norm(x, p["ln2_w"], p["ln2_b"], LN_EPS))
-            rowf = st[:, S + 1, :]
-            kx, rx = shift(ffn_x, rowf, p["ffn_mix_k"]), shift(ffn_x, rowf, p["ffn_mix_r"])
-            fk = self._mm(p["ffn_w_k"], kx, "squared_relu")
-            fv = self._mm(p["ffn_w_v"], fk)
-            fr = self._mm(p["ffn_w_r"], rx)
-            for t in np.nonzero(lasts)[0]:
-                st[batches[t], S + 1, :] = ffn_x[t]
-            ffn_x = rnd(sigmoid(fr) * fv)                                                      # channel_mix
-            x = rnd(ffn_x + x)
-            if (li + 1) % m.rescale == 0:
-                x = rnd(np.float32(0.5) * x)
-        if not headers:
-            return np.zeros((0, info.num_vocab), np.float32)
-        hx = rnd(layer_norm(x[np.asarray(headers)], m.ln_out[0], m.ln_out[1], LN_EPS))
-        return np.matmul(hx, m.head.T.astype(np.float32)).astype(np.float32)
+        att_x = rnd(layer_norm(x, p["ln1_w"], p["ln1_b"], LN_EPS))
+        rec("att_x_ln", att_x)                                                             # LN1 output
+        row0 = st[:, 0, :]
+        att_xx = shift(att_x, row0, p["time_mix_x"])
+        rec("att_xx", att_xx)
+        tmx = self._mm(p["time_mix_w1"], att_xx, "tanh")                                   # [T, 5R] == [R, 5, T]
+        rec("tmx", tmx)
+        tmx = tmx.reshape(T, 5, R)
+        tm = np.stack([self._mm(p["time_mix_w2"][i], tmx[:, i, :]) for i in range(5)])     # [5, T, D]
+        tm = rnd(p["time_mix"][:, None, :] + tm)                                           # add(time_mix, buffer.time_mix)
+        rec("tm", tm)
+        sx = [shift(att_x, row0, tm[i]) for i in range(5)]                                 # w, k, v, r, g
+        rec("att_sx", np.stack(sx))
+        k = self._mm(p["w_k"], sx[1], f32_out=True)
+        v = self._mm(p["w_v"], sx[2], f32_out=True)
+        r = self._mm(p["w_r"], sx[3], f32_out=True)
+        g = self._mm(p["w_g"], sx[4])
+        aw = self._mm(p["time_decay_w1"], sx[0], "tanh")
+        td = self._mm(p["time_decay_w2"], aw, f32_out=True)
+        td = (p["time_decay"][None, :] + td).astype(np.float32)
+        td = np.exp(-np.exp(td, dtype=np.float32), dtype=np.float32)                       # StableExp, f32 buffer
+        rec("k", k); rec("v", v); rec("r", r); rec("g", g); rec("att_w", aw); rec("time_decay", td)
+        u = p["time_first"].reshape(H, S)
+        y = np.empty((T, D), np.float32)
+        for t in range(T):
+            b = batches[t]
+            if lasts[t]:
+                st[b, 0, :] = att_x[starts[t] + clens[t] - 1]
+            Sm = st[b, 1:S + 1, :].reshape(S, H, S).transpose(1, 0, 2)                     # [H, j, i]
+            kt, vt, rt, wt = (z[t].reshape(H, S) for z in (k, v, r, td))
+            kv = kt[:, :, None] * vt[:, None, :]
+            y[t] = np.einsum("hj,hji->hi", rt, u[:, :, None] * kv + Sm).reshape(D)
+            st[b, 1:S + 1, :] = (wt[:, :, None] * Sm + kv).astype(np.float32).transpose(1, 0, 2).reshape(S, D)
+        aux = rnd(y)
+        rec("wkv", aux)                                                                    # WKV output as stored
+        aux = rnd(layer_norm(aux.reshape(T, H, S), p["gn_w"].reshape(H, S)[None], p["gn_b"].reshape(H, S)[None], GN_EPS).reshape(T, D))
+        rec("gn", aux)
+        att_x = rnd(silu(g) * aux)                                                         # mul_activate(att_g Silu, att_x)
+        rec("att_x", att_x)                                                                # gated output
+        o = self._mm(p["w_o"], att_x)
+        rec("att_o", o)
+        x = rnd(o + x)
+        rec("x_att", x)                                                                    # x after attention
+        ffn_x = rnd(layer_norm(x, p["ln2_w"], p["ln2_b"], LN_EPS))
+        rec("ffn_x_ln", ffn_x)                                                             # LN2 output
+        rowf = st[:, S + 1, :]
+        kx, rx = shift(ffn_x, rowf, p["ffn_mix_k"]), shift(ffn_x, rowf, p["ffn_mix_r"])
+        fk = self._mm(p["ffn_w_k"], kx, "squared_relu")
+        fv = self._mm(p["ffn_w_v"], fk)
+        fr = self._mm(p["ffn_w_r"], rx)
+        rec("ffn_kx", kx); rec("ffn_rx", rx); rec("ffn_k", fk); rec("ffn_v", fv); rec("ffn_r", fr)
+        for t in np.nonzero(lasts)[0]:
+            st[batches[t], S + 1, :] = ffn_x[t]
+        ffn_x = rnd(sigmoid(fr) * fv)                                                      # channel_mix
+        rec("ffn_x", ffn_x)                                                                # gated ffn
+        x = rnd(ffn_x + x)
+        if (li + 1) % m.rescale == 0:
+            x = rnd(np.float32(0.5) * x)
+        rec("x", x)                                                                        # layer output, after the halving
+        return x

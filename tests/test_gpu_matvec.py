@@ -71,6 +71,27 @@ def test_matvec_stacked_tokens_activation_f16_out(ctx, kind, k, m, T, B):
         assert np.all(np.abs(got - want) <= tol), (act, np.abs(got - want).max())
 
 
+@pytest.mark.parametrize("T", [1, 2, 3, 4, 5])
+@pytest.mark.parametrize("k", [8, 40, 72, 104, 136])
+def test_f16_rows_of_k_8_mod_16_stop_at_k(ctx, k, T):
+    """F16 rows with K % 16 == 8 (a LoRA rank such as 40 or 72), 1 .. 5 tokens.  The register-input kernel (T = 1) and the 2- / 4-token dmv
+    kernels read their inputs straight from global memory and walk kpad / 8 = K / 8 + 1 chunks: the extra one multiplied the next row's
+    first weights with whatever follows the token's K elements -- here the next token, of order 8.  Such rows now go to the LDS-staged
+    kernel, which pads its copy of the input with zeros (found by tests/test_gpu_v6_layer_parity.py::test_lora_ranks; DESIGN.md section 2,
+    "RWKV-6, layer by layer")."""
+    m = 20
+    raw = make("F16", k, m, k)
+    mat = wrk.Matrix(ctx, "F16", k, m, raw)
+    w = dq.dequantize("F16", raw, k * m, round_f16=False).reshape(m, k).astype(np.float64)
+    x = (8 + np.random.default_rng(T).standard_normal((T + 1, k))).astype(np.float16)
+    out = ctx.zeros([m, T, 1], np.float32)
+    mat.matmul_op(ctx.tensor(x, [k, T + 1, 1]).view(None, (0, T)), out)
+    got = out.back().reshape(T, m)
+    want = x[:T].astype(np.float64) @ w.T
+    bound = 4e-6 * (np.abs(x[:T]).astype(np.float64) @ np.abs(w).T) + 1e-6
+    assert np.all(np.abs(got - want) <= bound), np.abs(got - want).max()
+
+
 def test_matvec_view_offsets(ctx):
     """Matrix::matmul_op on views: head rows of x into a slice of a wider output (v7.rs:1026-1031)."""
     k, m, T = 256, 24, 4

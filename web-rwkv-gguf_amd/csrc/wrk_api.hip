@@ -301,7 +301,9 @@ int32_t wrk_matrix_create(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m, c
     WRK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t rb = wrk::repack_row_bytes(dev_kind, k);
     const size_t total = rb * m;
-    std::vector<uint8_t> host(total, 0);
+    // + 256: the pad behind the matrix is read -- the LDS-staged matvec walks F16 rows in 16-element steps, so the last row of a matrix with
+    // K % 16 == 8 takes one 8-element chunk from there (times staged zeros: harmless only if those bytes are no NaN or inf)
+    std::vector<uint8_t> host(total + 256, 0);
     if (kind == WRK_MAT_F32) {
         std::vector<uint16_t> tmp((size_t)k * m);
         const float* f = (const float*)data;
@@ -313,7 +315,7 @@ int32_t wrk_matrix_create(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m, c
     }
     void* p = nullptr;
     WRK_HIP(ctx, hipMalloc(&p, total + 256));
-    hipError_t e = hipMemcpyAsync(p, host.data(), total, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(p, host.data(), total + 256, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { hipFree(p); return wrk_fail(ctx, WRK_E_HIP, "matrix upload: %s", hipGetErrorString(e)); }
     wrk_matrix* mt = new wrk_matrix{ctx, dev_kind, k, m, flags, (uint8_t*)p, rb, wrk::stored_bytes(kind, k, m), nullptr, 0, {1}};

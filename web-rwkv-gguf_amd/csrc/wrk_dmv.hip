@@ -65,6 +65,7 @@ int launch_dmv(hipStream_t s, const MatvecParams& P, uint32_t total_wg, int quan
     for (int j = 0; j < P.njobs; ++j) {
         const JobDev& J = P.jobs[j];
         if (J.in.dtype != WRK_F16 || (J.k & 7u) || J.in.shape[1] * J.in.shape[2] != ntok || J.kind == WRK_MAT_NF4) return -1;
+        if (J.kind == WRK_MAT_F16 && (J.k & 15u)) return -1;      // as pick_reg (wrk_matvec.hip): the input is read from global memory, kpad / 8 chunks
         if (nt > 1) {
             if (!dense_stack(J.in) || !dense_stack(J.out) || (J.has_res && !dense_stack(J.res)) || (J.in.stride[0] & 7u)) return -1;
             if (J.kind != WRK_MAT_F16 && J.kind != WRK_MAT_Q4_K && J.kind != WRK_MAT_Q5_K && J.kind != WRK_MAT_Q6_K) return -1;

@@ -664,6 +664,10 @@ static matvec_fn pick_reg(const MatvecParams& P, int quant, bool has_f16, bool r
     for (int j = 0; j < P.njobs; ++j) {
         const JobDev& J = P.jobs[j];
         if (J.in.dtype != WRK_F16 || (J.k & 7u) || J.in.shape[1] * J.in.shape[2] != 1) return nullptr;
+        // F16 rows are walked in kpad / 8 chunks and this kernel reads its input straight from global memory, where nothing pads it to 16: with
+        // K % 16 == 8 the chunk behind the row would multiply the next row's first weights with whatever follows the input vector.  Such rows
+        // (a LoRA rank of 40, 72, ...) go to the LDS-staged kernel, which pads its copy of the input with zeros
+        if (J.kind == WRK_MAT_F16 && (J.k & 15u)) return nullptr;
         if (J.pro && J.k > 4096) return nullptr;        // the staged input of the LN prologue is sized for K <= 4096
         if (J.pro == 2) return nullptr;                 // the split-head prologue exists in the dmv kernels only
         const size_t base = ((size_t)J.in.offset[2] * J.in.stride[1] + J.in.offset[1]) * J.in.stride[0] + J.in.offset[0];

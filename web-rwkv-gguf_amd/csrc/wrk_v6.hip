@@ -20,6 +20,10 @@ struct wrk_v6_model : wrk_frame_common {     // graphs: generate steps only, key
     wrk_v6_model_desc d{};
     std::vector<wrk_v6_layer_desc> layers;
     V6Scratch s{};
+    // teacher-forced single-layer runs (wrk_v6_infer_layer): the layer range both layer lists cover, and whether the LN0 prologue is
+    // skipped (the caller wrote the layer input into s.x)
+    uint32_t layer_begin = 0, layer_end = 0xffffffffu;
+    bool skip_embed = false;
 
     // the runner interface of the decode loops (wrk_runner.h): one lane, no key bits but the mode, nothing around the loop
     Facts facts() const override { return {d.num_vocab, d.num_emb, d.num_layer, d.emb_f16 != nullptr}; }
@@ -103,10 +107,12 @@ int32_t wrk_v6_model::enqueue_ops(wrk_v7_state* st, uint32_t T, uint32_t NH, boo
     DTensor sx5 = make_dense(s.att_sx, WRK_F16, D, T, 5), tm5 = make_dense(s.tm, WRK_F16, D, T, 5);
     auto slice = [&](DTensor t, uint32_t i) { t.shape[2] = 1; t.offset[2] = i; return t; };
 
-    DTensor input = vec(s.input);
-    wrk::layer_norm(q, d.ln0_w->ptr, d.ln0_b->ptr, input, LN_EPS);
-    wrk::blit(q, input, x);
-    for (uint32_t li = 0; li < d.num_layer; ++li) {
+    if (!skip_embed) {
+        DTensor input = vec(s.input);
+        wrk::layer_norm(q, d.ln0_w->ptr, d.ln0_b->ptr, input, LN_EPS);
+        wrk::blit(q, input, x);
+    }
+    for (uint32_t li = layer_begin; li < d.num_layer && li < layer_end; ++li) {
         const wrk_v6_layer_desc& L = layers[li];
         DTensor st_att = make_dense(st->layer_ptr(li), WRK_F32, D, S + 2, st->num_batch);
         st_att.shape[1] = S + 1;
@@ -369,14 +375,14 @@ int32_t wrk_v6_model::enqueue_fused_decode(wrk_v7_state* st, uint32_t T, uint32_
 #define LNMIX(P, n) do { if (wrk::ln_mix(q, P, n) != 0) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "ln_mix shape"); } while (0)
     // arrival counters of the K-sliced GEMM: zero at the head of every step (a launch that aborted must not poison the next replay)
     if (T >= 2 && s.ks_cnt && s.ks_cnt_cap) WRK_HIP(ctx, hipMemsetAsync(s.ks_cnt, 0, (size_t)s.ks_cnt_cap * 4, q));
-    {   // embedding rows (already gathered into s.input) -> LN0 -> x
+    if (!skip_embed) {   // embedding rows (already gathered into s.input) -> LN0 -> x
         wrk::LnMixParams P{};
         P.src = (const f16*)s.input; P.ln_w = (const f16*)d.ln0_w->ptr; P.ln_b = (const f16*)d.ln0_b->ptr; P.eps = LN_EPS;
         P.d = D; P.nmix = 0; P.ln_out = (f16*)s.x;
         LNMIX(P, T);
     }
     const size_t sxs = (size_t)T * D;                                   // elements between the five shifted inputs
-    for (uint32_t li = 0; li < d.num_layer; ++li) {
+    for (uint32_t li = layer_begin; li < d.num_layer && li < layer_end; ++li) {
         const wrk_v6_layer_desc& L = layers[li];
         float* lst = st->layer_ptr(li);
         float* row0 = lst + (size_t)batch0 * (S + 2) * D;               // att shift state (T == 1: of that sequence)
@@ -612,6 +618,65 @@ int32_t wrk_v6_infer(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint
 int32_t wrk_v6_score(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, const uint32_t* tokens, const uint16_t* emb_rows, const uint32_t* cursors,
                      uint32_t T, const uint32_t* headers, uint32_t NH, const uint32_t* targets, float* logprob, uint32_t* rank, uint32_t mode) {
     return v6_job(ctx, m, st, {tokens, emb_rows, cursors, T, headers, NH, nullptr, nullptr, true, targets, logprob, rank}, mode);
+}
+
+// Teacher-forced run of ONE layer (parity tests, as wrk_v7_infer_layer): the layer's op list (mode 0), or the launches wrk_v6_infer
+// would choose for these cursors in mode 1 (the fused 7-launch layer for one token per sequence, the op list where it declines, the
+// merged op list for chunks), on a caller-supplied layer input.  The halving after every `rescale`-th layer belongs to that layer's run.
+// Every buffer of the frame stays readable through wrk_v6_frame_read.
+int32_t wrk_v6_infer_layer(wrk_ctx* ctx, wrk_v6_model* m, wrk_v7_state* st, uint32_t layer, const void* x, const uint32_t* cursors, uint32_t T,
+                           uint32_t mode) {
+    if (!ctx || !m || !st || !x || !cursors) return WRK_E_ARG;
+    LOCK(ctx);
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    WRK_ARG(ctx, !ctx->capturing_here(), "wrk_v6_infer_layer cannot be captured");
+    WRK_ARG(ctx, layer < m->d.num_layer, "layer %u out of range", layer);
+    WRK_ARG(ctx, T >= 1, "no tokens");
+    WRK_ARG(ctx, st->num_emb == m->d.num_emb && st->num_layer == m->d.num_layer, "state does not belong to this model");
+    wrk_job_shape sh;
+    int32_t rc = wrk_job_check(ctx, st, cursors, T, nullptr, 0, nullptr, 0, &sh);
+    if (rc == WRK_OK) rc = m->ensure_scratch(T, 1);
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.cursors, cursors, (size_t)T * 4);
+    if (rc == WRK_OK) rc = wrk_buf_write_raw(ctx, m->s.x, x, (size_t)T * m->d.num_emb * 2);
+    if (rc != WRK_OK) return rc;
+    m->layer_begin = layer; m->layer_end = layer + 1; m->skip_embed = true;
+    m->wkv_nseq = sh.nseq;
+    rc = WRK_E_UNSUPPORTED;                     // path selection is v6_job's
+    if (mode == 1 && sh.one_token_each) rc = m->enqueue_fused_decode(st, T, 0, true, cursors[0] & 0xff);
+    if (rc == WRK_E_UNSUPPORTED) rc = m->enqueue_ops(st, T, 0, true, mode == 1 && !sh.one_token_each);
+    m->layer_begin = 0; m->layer_end = 0xffffffffu; m->skip_embed = false;
+    if (rc != WRK_OK) return rc;
+    WRK_LAUNCH_CHECK(ctx);
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+// TensorGpu::back on one buffer of the frame, in the buffer's own dtype (Runtime<f16>, v6.rs:265-300: att_k, att_v, att_r and time_decay
+// are f32, the rest f16); att_sx and tm hold five planes [5][T][D]
+int32_t wrk_v6_frame_read(wrk_ctx* ctx, wrk_v6_model* m, const char* name, uint32_t T, void* dst, size_t capacity, size_t* bytes) {
+    if (!ctx || !m || !name || !bytes) return WRK_E_ARG;
+    LOCK(ctx);
+    WRK_ARG(ctx, m->scratch && T >= 1 && T <= m->scratch_tokens, "no frame of %u tokens has been run", T);
+    const uint32_t D = m->d.num_emb, F = m->d.num_hidden, R = m->d.time_mix, W = m->d.time_decay;
+    const V6Scratch& s = m->s;
+    struct { const char* n; const void* p; uint32_t c, esz; } tab[] = {
+        {"x", s.x, D, 2}, {"att_x", s.att_x, D, 2}, {"att_xx", s.att_xx, D, 2}, {"aux_x", s.aux_x, D, 2}, {"att_sx", s.att_sx, 5 * D, 2},
+        {"att_w", s.att_w, W, 2}, {"att_g", s.att_g, D, 2}, {"att_o", s.att_o, D, 2}, {"tmx", s.tmx, 5 * R, 2}, {"tmt", s.tmt, 5 * R, 2},
+        {"tm", s.tm, 5 * D, 2}, {"ffn_x", s.ffn_x, D, 2}, {"ffn_kx", s.ffn_kx, D, 2}, {"ffn_rx", s.ffn_rx, D, 2}, {"ffn_k", s.ffn_k, F, 2},
+        {"ffn_v", s.ffn_v, D, 2}, {"ffn_r", s.ffn_r, D, 2},
+        {"att_k", s.att_k, D, 4}, {"att_v", s.att_v, D, 4}, {"att_r", s.att_r, D, 4}, {"time_decay", s.time_decay, D, 4}};
+    for (auto& e : tab)
+        if (strcmp(e.n, name) == 0) {
+            const size_t n = (size_t)e.c * T * e.esz;
+            *bytes = n;
+            if (!dst) return WRK_OK;
+            WRK_ARG(ctx, capacity >= n, "frame buffer %s needs %zu bytes, capacity %zu", name, n, capacity);
+            WRK_HIP(ctx, hipSetDevice(ctx->device));
+            WRK_HIP(ctx, hipMemcpyAsync(dst, e.p, n, hipMemcpyDeviceToHost, ctx->stream));
+            WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            return WRK_OK;
+        }
+    return wrk_fail(ctx, WRK_E_ARG, "no frame buffer named %s", name);
 }
 
 }  // extern "C"

@@ -214,6 +214,8 @@ HIP_SYMBOLS = {
     "wrk_v6_model_destroy": (C.c_int32, [_P]),
     "wrk_v6_model_token_bytes": (C.c_size_t, [_P, C.c_uint32]),
     "wrk_v6_state_create": (C.c_int32, [_P, _P, C.c_uint32, C.POINTER(_P)]),
+    "wrk_v6_infer_layer": (C.c_int32, [_P, _P, _P, C.c_uint32, _P, _u32p, C.c_uint32, C.c_uint32]),
+    "wrk_v6_frame_read": (C.c_int32, [_P, _P, C.c_char_p, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "wrk_v6_infer": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _f32p, _u32p, C.c_uint32]),
     "wrk_v6_generate_greedy": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p, _f32p, C.c_uint32]),
     "wrk_sample_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, C.c_uint32, _u32p]),
@@ -1612,7 +1614,11 @@ class Runtime:
         return rc == 1, buf.value.decode()
 
     def infer_layer(self, layer: int, x: np.ndarray, v_first: Optional[np.ndarray], cursors, mode: int = 0):
-        """Teacher-forced run of one layer on the layer input `x` [T, D] (and the layer-0 value `v_first`)."""
+        """Teacher-forced run of one layer on the layer input `x` [T, D] (and the layer-0 value `v_first`; RWKV-6 has none: pass None)."""
+        if self.model6:
+            xa, c = np.ascontiguousarray(x, dtype=np.float16), _u32(cursors)
+            self.ctx.check(hip.wrk_v6_infer_layer(self.ctx.h, self.model6, self.state, layer, xa.ctypes.data_as(_P), _ptr(c, _u32p), c.size, mode))
+            return
         dt = np.float32 if getattr(self, "frame_dtype", F16) == F32 else np.float16
         xa = np.ascontiguousarray(x, dtype=dt)
         va = np.ascontiguousarray(v_first, dtype=dt) if v_first is not None else None
@@ -1621,7 +1627,14 @@ class Runtime:
                                               va.ctypes.data_as(_P) if va is not None else None, _ptr(c, _u32p), c.size, mode))
 
     def frame(self, name: str, num_token: int) -> np.ndarray:
-        """One `Runtime<F>` buffer of the last job, [T, C] (names: examples/inspect.rs:208-248)."""
+        """One `Runtime<F>` buffer of the last job, [T, C] (names: examples/inspect.rs:208-248).  RWKV-6: in the buffer's own dtype
+        (att_k, att_v, att_r, time_decay are float32), the five-plane buffers att_sx and tm as [5, T, D]."""
+        if self.model6:
+            n = C.c_size_t()
+            self.ctx.check(hip.wrk_v6_frame_read(self.ctx.h, self.model6, name.encode(), num_token, None, 0, C.byref(n)))
+            out = np.empty(n.value // 4, np.float32) if name in ("att_k", "att_v", "att_r", "time_decay") else np.empty(n.value // 2, np.float16)
+            self.ctx.check(hip.wrk_v6_frame_read(self.ctx.h, self.model6, name.encode(), num_token, out.ctypes.data_as(_P), out.nbytes, C.byref(n)))
+            return out.reshape(5, num_token, -1) if name in ("att_sx", "tm") else out.reshape(num_token, -1)
         dt = np.float32 if getattr(self, "frame_dtype", F16) == F32 else np.float16
         n = C.c_size_t()
         self.ctx.check(hip.wrk_v7_frame_read(self.ctx.h, self.model, name.encode(), num_token, None, 0, C.byref(n)))
