@@ -479,6 +479,22 @@ int32_t wrk_logit_bias_destroy(wrk_logit_bias* bias);
 int32_t wrk_bias_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
                         const wrk_logit_bias* bias, const uint32_t* sets);
 
+/* Classifier-free guidance (Hugging Face's guidance_scale with negative_prompt_ids, llama.cpp's --cfg-scale with --cfg-negative-prompt,
+ * text-generation-webui's negative prompt): the row a pick is made on is mixed from the row of the sequence itself (conditional, xc) and
+ * the row of a partner sequence that was fed the negative prompt (unconditional, xu).  The rows are mixed raw, without a log-softmax:
+ * that differs from lu + s * (lc - lu) on log-softmaxed rows by one constant per row, which the arg-max, every sampler family, bias,
+ * penalties, DRY and the grammar mask do not see.  With c = xc and u = xu after NaN -> -inf and -0 -> +0, and the row's scale s, the
+ * first case that applies: s == 1: the bits of xc, unchanged (the row is off; NaN payloads and -0 included); c == -inf: -inf (impossible
+ * under the prompt stays impossible); c == +inf: +inf; u == -inf: c; s == 0: u; u == +inf: -inf if s > 1, else +inf; otherwise
+ * d = c - u, p = s * d, out = p + u, three separate IEEE f32 operations, never a fused multiply-add; when d or p overflows the result
+ * is that infinity.  Outside s == 1 rows the result is never NaN.
+ * wrk_guide_logits: logits holds 2 * num_rows f32 rows of row_stride (first num_vocab used), the num_rows conditional ones first, row
+ * num_rows + r the partner of row r; out receives num_rows rows of out_stride, another buffer; nothing between the rows of out is
+ * written.  scale: host f32 [num_rows], each finite and >= 0 (else WRK_E_ARG, from every call that takes one); num_vocab > 2^20:
+ * WRK_E_UNSUPPORTED.  Blocking.  In a host-side loop it goes in front of wrk_bias_logits. */
+int32_t wrk_guide_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                         const float* scale, wrk_buf* out, uint32_t out_stride);
+
 /* DRY ("don't repeat yourself": text-generation-webui, koboldcpp, llama.cpp's dry_multiplier / dry_base / dry_allowed_length /
  * dry_sequence_breakers) and the hard ban of the same match (Hugging Face's no_repeat_ngram_size), on the device.  Both look at the ORDER
  * of what a sequence generated, which the occurrence table cannot: a token window has num_batch slots (slot b belongs to state slot b),
@@ -618,7 +634,26 @@ int32_t wrk_dry_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, uint32
  * WRK_BIAS_NONE.  The object and the set words are device data: one cached step program serves any object and any choice of sets;
  * biased calls replay step programs of their own, a call with bias NULL exactly the programs it ran before.  Tokens do not depend on
  * the number of lanes.  If a bias set, bans, a grammar and the n-gram ban together leave a row with no finite logit, the picked id is
- * unspecified but < num_vocab and nothing faults.  The two fields sit directly behind `occ`: every field behind them keeps its order. */
+ * unspecified but < num_vocab and nothing faults.  The two fields sit directly behind `occ`: every field behind them keeps its order.
+ * Guidance.  guidance_scale (host f32 [num_batch]; NULL: off) makes sequence b a guided one: its partner is state slot num_batch + b,
+ * into which the caller has fed the negative prompt, so the state needs 2 * num_batch slots (else WRK_E_ARG).  Every step runs both
+ * slots, and the pick of b sees the row wrk_guide_logits makes of their two head rows with guidance_scale[b] -- inside the step program.
+ * Order within a step: guidance first, in front of the bias; everything that read the head output for the pick reads the guided row
+ * instead: bias, penalties, DRY, the grammar mask, then the call's pick -- bit for bit the pick of the same call on that row.  Log-probs,
+ * last_logits and the stop snapshot stay on the raw head output of the conditional sequence.  The partner is fed b's draws: at step 0 it
+ * feeds guidance_first_tokens[b] (host u32 [num_batch], each < num_vocab; NULL: first_tokens[b]), the last token of the negative prompt,
+ * then y_0, y_1, ... as b does; it has b's stop set, stop sequences and tail, ends in the same step and is frozen as b is.  After the
+ * call slot b is what the contract above says, and slot num_batch + b has consumed its own first token and the same draws: bit for bit
+ * what a guided call without stops and steps = out_lengths[b] leaves in both.  out_tokens, out_lengths, last_logits, the log-prob rows,
+ * mu, grammar states, matches and tails are num_batch wide, as without guidance; a call whose scales are all 1 returns, for sequences
+ * [0, num_batch), bit for bit what the call without guidance on the same frame returns -- 2 * num_batch sequences, the partners' first
+ * tokens behind the conditional ones; a call without guidance of num_batch sequences runs a smaller frame, whose matmul kernels round
+ * differently: its logits agree to rounding, not bit for bit, and a near-tie may then pick another token.  WRK_E_ARG before any launch: guidance_first_tokens without guidance_scale, a scale that is NaN, infinite
+ * or negative, a state of fewer than 2 * num_batch slots.  WRK_E_UNSUPPORTED before any launch: guidance on several lanes (mode bits
+ * 8-15 > 1), in wrk_v7_generate_queue (wrk_queue_options' guidance_scale) and in wrk_v7_generate_beam (either field in `gen`).  The
+ * scales are device data: one cached step program serves any of them; guided calls replay step programs of their own, a call with
+ * guidance_scale NULL exactly the programs it ran before.  The two fields sit directly behind `bias_set` (the bias fields stay directly
+ * behind `occ`, where callers and the binding checks know them): every field behind them keeps its order. */
 #define WRK_MAX_STOP_TOKENS 16
 #define WRK_MAX_STOP_SEQUENCES 8
 #define WRK_MAX_STOP_SEQUENCE_LEN 8
@@ -633,6 +668,8 @@ typedef struct wrk_generate_options {
     wrk_occurrence *occ;
     const wrk_logit_bias *bias;
     const uint32_t *bias_set;
+    const float *guidance_scale;
+    const uint32_t *guidance_first_tokens;
     const uint32_t *stop_tokens, *stop_offsets;
     uint32_t poll_steps;
     uint32_t num_top;
@@ -749,7 +786,9 @@ int32_t wrk_stop_sequences_advance(wrk_ctx* ctx, uint32_t num_vocab, uint32_t nu
  * every request).  Request r's rows are biased with set bias_set[r] from the step it is dispatched, at step 0 or at a refill on the
  * device, and never with what its slot's previous request used; the rows of the steps that feed prompt tokens are biased too, their
  * draws are discarded as before.  A reply does not depend on the slot or the step the request was scheduled at.  Nothing of the bias
- * belongs to a state-pool or history-pool entry.  The two fields sit directly behind `occ`. */
+ * belongs to a state-pool or history-pool entry.  The two fields sit directly behind `occ`.
+ * Guidance (wrk_generate_options) is not built for the queue: a refilled slot's partner would need the new request's negative prompt.
+ * guidance_scale non-NULL is WRK_E_UNSUPPORTED before any launch; the field sits directly behind `bias_set`. */
 typedef struct wrk_history_pool wrk_history_pool;   /* a history pool beside a state pool: wrk_queue_pool, below */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
@@ -761,6 +800,7 @@ typedef struct wrk_queue_options {
     wrk_occurrence *occ;
     const wrk_logit_bias *bias;
     const uint32_t *bias_set;
+    const float *guidance_scale;
     const wrk_buf *init_state;
     uint32_t poll_steps, max_steps;
     const uint32_t *prompt_context_from;

@@ -46,9 +46,16 @@ A twelfth leg (--beam W): generate_beam with W beams per group on the B slots (B
 step runs) against generate_greedy on the same B slots, alternating, with the run-to-run spread of each, and next to them
 the bytes the slot permutation may move per step and moved on average.  Every call starts from the same states.
 
+A thirteenth leg (--guidance S): generate_guided of B sequences with scale S and the plain-sampler pick (B conditional
+slots and B partner slots, so the runtime gets 2B slots) against the plain sampled loop of the options entry point on the same 2B slots,
+alternating, with the run-to-run spread of each: the step programs differ by guide_rows and guide_follow and by the pick, which runs on
+B rows instead of 2B.  Every call starts from the same states.  With --guidance the one runtime of the process has 2 * max(batches) slots,
+so the other legs of that invocation run on a larger state than in an invocation without the flag: compare those legs between
+invocations of the same kind only.
+
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
                                  [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9] [--grammar] [--stop-seq]
-                                 [--dry] [--logit-bias 64] [--beam 4]
+                                 [--dry] [--logit-bias 64] [--beam 4] [--guidance 1.5]
 
 Prints one JSON object.
 """
@@ -469,6 +476,47 @@ def beam_leg(rt, first, B, V, args):
             "permute_bytes_read_and_written_per_step_mean": round(2 * 2 * slot_bytes * moved / args.steps)}
 
 
+def guide_leg(rt, first, B, V, args):
+    """Medians of the per-step time of generate_guided with B guided sequences (scale args.guidance, sampled pick) against the plain sampled
+    loop of generate_stop on the same 2B slots, alternating in one process; every call starts from the same states and feeds the same
+    first tokens, the partners' being other tokens than the conditional ones'."""
+    start = [rt.state_read(b) for b in range(2 * B)]
+    neg = [(t + 7) % (V - 1) for t in first]
+    pick = dict(temperature=args.temperature, top_p=args.top_p)
+
+    def reset():
+        for b in range(2 * B):
+            rt.state_write(start[b], b)
+
+    def guided():
+        reset()
+        tok, _ = rt.generate_guided(first, args.steps, args.guidance, negative_first_tokens=neg, poll_steps=POLL_OFF, **pick)
+        return tok, rt.last_stop_ms / args.steps
+
+    def plain():
+        reset()
+        tok, _ = rt.generate_stop(first + neg, args.steps, [], poll_steps=POLL_OFF, **pick)
+        return tok, rt.last_stop_ms / args.steps
+    want, _ = guided()                                                     # capture and warm up
+    base, _ = plain()
+    gm, pm, same = [], [], True
+    for _ in range(args.reps):
+        tok, ms = plain()
+        same &= bool(np.array_equal(tok, base))
+        pm.append(ms)
+        tok, ms = guided()
+        same &= bool(np.array_equal(tok, want))
+        gm.append(ms)
+    reset()
+    g_med, p_med = float(np.median(gm)), float(np.median(pm))
+    return {"scale": args.guidance, "guided_sequences": B, "slots": 2 * B, "same_tokens_every_rep": bool(same),
+            "guided_differs_from_plain": bool(not np.array_equal(want, base[:, :B])),
+            "guided_ms_per_step": round(g_med, 5), "guided_spread_us": round((max(gm) - min(gm)) * 1e3, 2), "guided_ms_all": [round(x, 5) for x in gm],
+            "plain_2b_ms_per_step": round(p_med, 5), "plain_2b_spread_us": round((max(pm) - min(pm)) * 1e3, 2),
+            "plain_2b_ms_all": [round(x, 5) for x in pm], "guided_over_plain_2b": round(g_med / p_med, 4),
+            "guided_minus_plain_2b_us": round((g_med - p_med) * 1e3, 2), "guide_rows_bytes_per_step": 3 * B * V * 4}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -492,12 +540,14 @@ def main():
     ap.add_argument("--logit-bias", type=int, default=None, help="entries per set: the loop with a logit bias against the same loop without")
     ap.add_argument("--beam", type=int, default=None, help="beams per group: generate_beam against generate_greedy on the same slots")
     ap.add_argument("--beam-length-penalty", type=float, default=1.0)
+    ap.add_argument("--guidance", type=float, default=None,
+                    help="scale: generate_guided of B sequences against the plain sampled loop on the same 2B slots")
     args = ap.parse_args()
     import wrk
 
     batches = [int(b) for b in args.batches.split(",")]
     ctx = wrk.Context(0)
-    rt = wrk.Runtime(ctx, wrk.GgufReader(bench.make_model_gguf(args.model, seed=42)), num_batch=max(batches))
+    rt = wrk.Runtime(ctx, wrk.GgufReader(bench.make_model_gguf(args.model, seed=42)), num_batch=max(batches) * (2 if args.guidance is not None else 1))
     V = rt.info.num_vocab
     out = {"model": f"RWKV-7 {args.model} Q4_K_M (synthetic)", "temperature": args.temperature, "top_p": args.top_p, "steps": args.steps,
            "reps": args.reps, "batches": []}
@@ -594,6 +644,12 @@ def main():
                                 "launches: the two of the candidate front (wrk_top_logprobs' kernels), beam_select, and the gather and the "
                                 "scatter of the slot permutation; the snapshot launch returns at once when no slot ended")
             out["batches"][-1]["beam"] = beam_leg(rt, first, B, V, args)
+        if args.guidance is not None:
+            out["guidance_note"] = ("B guided sequences on 2B slots against the plain sampled loop of 2B sequences; a guided step adds two "
+                                    "launches to that step: guide_rows in front of the pick and guide_follow in front of the advance, and "
+                                    "its pick runs on B rows instead of 2B; the runtime of this whole invocation has 2 * max(batches) state slots, "
+                                    "also under the legs that are not guided")
+            out["batches"][-1]["guidance"] = guide_leg(rt, first, B, V, args)
     if occ is not None:
         occ.close()
     rt.close()

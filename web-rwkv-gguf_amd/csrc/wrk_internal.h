@@ -260,6 +260,12 @@ void grammar_advance(hipStream_t s, uint32_t v, uint32_t n, const GrammarParam* 
 struct BiasParam { const uint32_t* offsets; const uint32_t* ids; const float* values; const uint32_t* sets; };
 void bias_rows(hipStream_t s, const float* in, uint32_t v, uint32_t in_stride, uint32_t n, const BiasParam* par, float* out, uint32_t out_stride);
 
+// wrk_guide.hip: classifier-free guidance.  guide_rows: out row r = the guided row of in rows r (conditional) and n + r
+// (unconditional) with the scale par[r], device data, in a decode loop a per-frame buffer written before every call; a row with scale 1
+// is the conditional row bit for bit.  guide_follow: argmax[n + r] = argmax[r], the partner sequences take the conditional ones' draws
+void guide_rows(hipStream_t s, const float* in, uint32_t v, uint32_t in_stride, uint32_t n, const float* par, float* out, uint32_t out_stride);
+void guide_follow(hipStream_t s, uint32_t* argmax, uint32_t n);
+
 // wrk_dry.hip: DRY and the no-repeat-n-gram ban.  One DryParam per row: the row's slot of a token window -- ring [cap] of
 // ids, meta = (length, next write position) -- and the row's values, pen[m] the host-computed penalty of a match of m tokens (0 below
 // allowed_length).  DryBreakers: the call's breaker ids.  Both are device data, in a decode loop per-frame buffers written before
@@ -461,6 +467,10 @@ struct wrk_logit_bias {
 // validated set words of n rows (WRK_E_ARG on a NULL object, an object of another context or another vocabulary, a word that is neither
 // < num_sets nor WRK_BIAS_NONE); set NULL: all 0
 int32_t wrk_bias_pack(wrk_ctx* ctx, const wrk_logit_bias* lb, const uint32_t* set, uint32_t n, uint32_t V, std::vector<uint32_t>& out);
+
+// classifier-free guidance (wrk_guide.hip): validated scales of n rows (WRK_E_ARG on a NULL array with n > 0 and on a scale that is NaN,
+// infinite or negative; WRK_E_UNSUPPORTED on a vocabulary above the sampler's limit)
+int32_t wrk_guide_pack(wrk_ctx* ctx, const float* scale, uint32_t n, uint32_t V, std::vector<float>& out);
 
 // beam search (wrk_beam.hip): inv_norm[l] = (float)(1.0 / pow((double)l, (double)length_penalty)) for l in [1, max_len], entry 0 unused
 // (WRK_E_ARG on a penalty that is negative, infinite or NaN, or whose table leaves the normal numbers); the groups' stop sets from a CSR

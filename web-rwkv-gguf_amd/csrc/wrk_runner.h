@@ -111,6 +111,10 @@ struct wrk_step_kind {
     // logit bias (wrk_bias.hip): in front of everything else, bias_rows makes bias.out = head_o biased with the rows' sets of
     // bias.par, and the penalise, the DRY copy, the mask and the pick read it where they read head_o; log-probs keep head_o
     bool biased = false;
+    // classifier-free guidance (wrk_guide.hip): the step runs 2R sequences, the conditional ones [0, R) and their partners
+    // [R, 2R); in front of the bias guide_rows makes guide.out [R][V] from rows r and R + r of head_o and the scales of guide.par, and the
+    // whole chain and the pick run on R rows of it; log-probs keep rows [0, R) of head_o; then guide_follow, and the tail over 2R rows
+    bool guided = false;
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
     bool mirostat() const { return pick == MIROSTAT; }
@@ -125,10 +129,11 @@ struct wrk_step_kind {
                (uint32_t)constrained << 31;
     }
     // The kind's bits of GraphKey::mode2, the word that takes what key() has no room for: stop sequences 0, DRY 1, prompt intake 2,
-    // history 3, biased 4, the tail's third bit (the beam tail) 5.  0 for every kind that existed before the word did, and bit 0 alone for every
+    // history 3, biased 4, the tail's third bit (the beam tail) 5, guided 6.  0 for every kind that existed before the word did, and bit 0 alone for every
     // stop-sequence kind, so their keys compare as they always have
     uint32_t key2() const {
-        return (uint32_t)stop_seqs | (uint32_t)dry << 1 | (uint32_t)intake << 2 | (uint32_t)history << 3 | (uint32_t)biased << 4 | ((uint32_t)tail >> 2) << 5;
+        return (uint32_t)stop_seqs | (uint32_t)dry << 1 | (uint32_t)intake << 2 | (uint32_t)history << 3 | (uint32_t)biased << 4 | ((uint32_t)tail >> 2) << 5 |
+               (uint32_t)guided << 6;
     }
 };
 
@@ -179,6 +184,15 @@ struct wrk_bias_bufs {
     uint32_t* set = nullptr;
     float* out = nullptr;
     void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, sizeof(wrk::BiasParam)); c.take(set, d[0] * 4); c.take(out, d[0] * d[1] * 4); }
+};
+// classifier-free guidance (wrk_guide.hip).  par: the guided sequences' scales (one program serves any scales); out [R][V]:
+// the guided rows, which the chain reads where it read the head output
+struct wrk_guide_bufs {
+    static constexpr int DIMS = 2;              // guided sequences, vocabulary
+    static constexpr unsigned EXACT = 2;
+    float* par = nullptr;
+    float* out = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(par, d[0] * 4); c.take(out, d[0] * d[1] * 4); }
 };
 // DRY / the n-gram ban (wrk_dry.hip).  par: the sequences' DryParam rows (window slot, values, penalty table: one program
 // serves any window and any parameters); brk: the call's breaker ids; out [B][V]: the copy of the head output that a pick without
@@ -369,6 +383,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_penalty_bufs> penalty;
     wrk_dev_group<wrk_grammar_bufs> grammar;
     wrk_dev_group<wrk_bias_bufs> bias;
+    wrk_dev_group<wrk_guide_bufs> guide;
     wrk_dev_group<wrk_dry_bufs> dry;
     wrk_dev_group<wrk_score_bufs> score;
     wrk_dev_group<wrk_stop_bufs> stop;
@@ -380,7 +395,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_logprob_bufs> logprob;
     wrk_dev_group<wrk_beam_bufs> beam;
     template <class F> void each_group(F&& f) {     // the one list of the groups
-        f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(bias); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
+        f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(bias); f(guide); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
         f(queue_states); f(queue_intake); f(logprob); f(beam);
     }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
@@ -453,8 +468,10 @@ struct wrk_logprob_call {
     bool on() const { return logprob != nullptr; }
 };
 bool wrk_no_graph();        // WRK_NO_GRAPH=1: the decode loops enqueue every step instead of replaying a program
-// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: the bias launch (biased: what follows reads
-// its output where it read head_o), the penalise launch (penalised), the DRY
+// Everything of a step after the layers and the head, for sequences [b0, b0 + B) of `st`: in a guided step (B = 2R sequences)
+// guide_rows first, and the chain and the pick below on the R rows of guide.out, the log-probs on rows [0, R) of head_o, guide_follow
+// behind the draw updates and the tail over all B rows; the bias launch (biased: what follows reads
+// its output where it read head_o or guide.out), the penalise launch (penalised), the DRY
 // launches (dry: the row copy unless penalised, then dry_rows), the mask launch (constrained), the arg-max or sampler launch on the resulting row and the frame's parameters at step *counter -- neither with
 // `argmax_done`: the head launch has left the arg-max in io().argmax (RWKV-7's fused greedy head, never in a constrained, a DRY or a biased step) -- with
 // kind.logprobs the log-prob launches on head_o (never pen_o) and io().argmax into row
@@ -471,7 +488,9 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
 // stop: steps go out in blocks of poll_steps (0: 16), each followed by a copy of every lane's live count to pinned memory and an
 // event; before block k + 2 the host waits for block k's event and stops submitting once every count is 0.  Then stop_restore, and
 // lengths [B] / *steps_run come back.  With the stop-sequence arrays of stop->opt (kind.stop_seqs) every lane also gets the
-// stop-sequence buffers with its sequences' rows and tails, and out_stop_match / stop_tail come back lane by lane
+// stop-sequence buffers with its sequences' rows and tails, and out_stop_match / stop_tail come back lane by lane.
+// With stop->opt->guidance_scale (kind.guided) one lane runs 2B sequences -- first_tokens then guidance_first_tokens, the stop
+// rows, stop-sequence rows and tails of [0, B) repeated for the partners [B, 2B) -- with B pick rows, and columns [0, B) come back
 struct wrk_stop_call { const wrk_generate_options* opt; uint32_t* out_lengths; uint32_t* steps_run; };
 int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t B, uint32_t steps,
                      const wrk_pick_args& pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,

@@ -168,6 +168,7 @@ struct wrk_pick_params {    // validated rows; empty: the arg-max / without pena
     bool has_dry = false;                   // a DRY pick: the rows' window slots, values and tables, and the call's breakers
     std::vector<wrk::DryParam> dry;
     wrk::DryBreakers brk{};
+    std::vector<float> guide;               // a guided call: the scales of its R sequences (wrk_guide_pack); the frame then runs 2R
 };
 
 // The one validation of the pick arrays (wrk_pick_args).  Sets kind.pick / kind.penalized and packs `n` rows; penalty row r names slot r
@@ -374,7 +375,8 @@ static int32_t wrk_generate_check(wrk_ctx* ctx, const wrk_v7_state* st, const wr
 }
 
 // after the runner's ensure_frame: history / parameter buffers, then cursors, header rows, first_tokens [b0, b0 + B) and rows
-// [b0, b0 + B) of `rows` for sequences [b0, b0 + B), and a zero step counter
+// [b0, b0 + B) of `rows` for sequences [b0, b0 + B), and a zero step counter.  A guided call (rows.guide): B = 2R sequences of the
+// frame, the pick rows and the scales of the R conditional ones
 static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tokens, uint32_t b0, uint32_t B, uint32_t steps, const wrk_pick_params& rows) {
     wrk_ctx* ctx = f.ctx;
     wrk::FrameIo& io = f.io();
@@ -383,35 +385,39 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     const wrk::SampleFilter* filt = rows.filt.empty() ? nullptr : rows.filt.data() + b0;
     const wrk::SampleAlt* alt = rows.alt.empty() ? nullptr : rows.alt.data() + b0;
     const size_t V = f.facts().num_vocab;
+    const bool guided = !rows.guide.empty();
+    const uint32_t R = guided ? B / 2 : B;      // rows of the pick
     int32_t rc = f.grow(f.history, {(size_t)steps * B});
-    if (rc == WRK_OK && par) rc = f.grow(f.sample, {B});
-    if (rc == WRK_OK && filt) rc = f.grow(f.filter, {B});
-    if (rc == WRK_OK && alt) rc = f.grow(f.alt, {B});
-    if (rc == WRK_OK && pen) rc = f.grow(f.penalty, {B, V});
-    if (rc == WRK_OK && rows.grammar) rc = f.grow(f.grammar, {B, V});
-    if (rc == WRK_OK && rows.bias) rc = f.grow(f.bias, {B, V});
-    if (rc == WRK_OK && rows.has_dry) rc = f.grow(f.dry, {B, V});
+    if (rc == WRK_OK && par) rc = f.grow(f.sample, {R});
+    if (rc == WRK_OK && filt) rc = f.grow(f.filter, {R});
+    if (rc == WRK_OK && alt) rc = f.grow(f.alt, {R});
+    if (rc == WRK_OK && pen) rc = f.grow(f.penalty, {R, V});
+    if (rc == WRK_OK && rows.grammar) rc = f.grow(f.grammar, {R, V});
+    if (rc == WRK_OK && rows.bias) rc = f.grow(f.bias, {R, V});
+    if (rc == WRK_OK && guided) rc = f.grow(f.guide, {R, V});
+    if (rc == WRK_OK && rows.has_dry) rc = f.grow(f.dry, {R, V});
     if (rc != WRK_OK) return rc;
     std::vector<uint32_t> cur(B), hdr(B);
     for (uint32_t b = 0; b < B; ++b) { cur[b] = (b0 + b) | (b << 8) | (1u << 24); hdr[b] = b; }
     wrk_upload up{ctx};
     up(io.cursors, cur.data(), B)(io.headers, hdr.data(), B)(io.tokens, first_tokens + b0, B);
-    if (par) up(f.sample.par, par, B);
-    if (filt) up(f.filter.par, filt, B);
-    if (alt) up(f.alt.par, alt, B);
-    if (pen) up(f.penalty.par, pen, B);
+    if (par) up(f.sample.par, par, R);
+    if (filt) up(f.filter.par, filt, R);
+    if (alt) up(f.alt.par, alt, R);
+    if (pen) up(f.penalty.par, pen, R);
     if (rows.grammar) {
         const wrk::GrammarParam gp = rows.grammar->param(f.grammar.state);
-        up(f.grammar.par, &gp, 1)(f.grammar.state, rows.gram_state.data() + b0, B);
+        up(f.grammar.par, &gp, 1)(f.grammar.state, rows.gram_state.data() + b0, R);
     }
     if (rows.bias) {
         const wrk::BiasParam bp = rows.bias->param(f.bias.set);
-        up(f.bias.par, &bp, 1)(f.bias.set, rows.bias_set.data() + b0, B);
+        up(f.bias.par, &bp, 1)(f.bias.set, rows.bias_set.data() + b0, R);
     }
+    if (guided) up(f.guide.par, rows.guide.data() + b0, R);
     if (rows.has_dry) {
-        up(f.dry.par, rows.dry.data() + b0, B)(f.dry.brk, &rows.brk, 1);
+        up(f.dry.par, rows.dry.data() + b0, R)(f.dry.brk, &rows.brk, 1);
         // dry_rows leaves its scratch zero; a freshly allocated group, or one a failed call left behind, does not hold zeros yet
-        WRK_HIP(ctx, hipMemsetAsync(f.dry.scratch, 0, (size_t)B * V * 4, ctx->stream));
+        WRK_HIP(ctx, hipMemsetAsync(f.dry.scratch, 0, (size_t)R * V * 4, ctx->stream));
     }
     if (up.rc != WRK_OK) return up.rc;
     WRK_HIP(ctx, hipMemsetAsync(io.counter, 0, 4, ctx->stream));
@@ -495,6 +501,8 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     WRK_ARG(ctx, B >= 1 && B <= st->num_batch && B <= 256, "num_batch %u: must be in [1, min(%u, 256)]", B, st->num_batch);
     if (((mode_arg >> 8) & 0xffu) > 1)
         return wrk_fail(ctx, WRK_E_UNSUPPORTED, "generate_queue on several lanes: one queue shared by several streams would need cross-stream atomics");
+    if (opt->guidance_scale)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "generate_queue with guidance: a refilled slot's partner would need the new request's negative prompt");
     int32_t rc = queue_csr_check(ctx, opt->prompt_offsets, R, "prompt_offsets");
     // the stop sets and the pick parameters go through the validation of the other loops, R rows at a time; of the penalty rows only
     // (presence, frequency, decay) are kept, a slot's row pointers are its own
@@ -865,14 +873,21 @@ static wrk::StopGeom stop_geom(wrk_frame_common& f, const wrk_v7_state* st, uint
     return g;
 }
 
+// a guided step, behind the draw updates of its R conditional sequences and in front of the advance: the partners take the same tokens
+static void enqueue_guide_follow(wrk_frame_common& f, uint32_t R, wrk_step_kind kind) {
+    if (kind.guided) wrk::guide_follow(f.ctx->op_stream(), f.io().argmax, R);
+}
+
 // tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
-// (penalised), advance_stop, stop_snapshot of sequences [b0, b0 + B) of `st`
-static int32_t enqueue_stop_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
+// (penalised), advance_stop, stop_snapshot of sequences [b0, b0 + B) of `st`.  R: the rows of the pick (a guided step: B / 2, and
+// guide_follow between their draw updates and the advance)
+static int32_t enqueue_stop_tail(wrk_frame_common& f, uint32_t B, uint32_t R, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
     hipStream_t q = f.ctx->op_stream();
     const wrk::FrameIo& io = f.io();
     if (!f.stop.holds({B}) || b0 + B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "stop buffers are not prepared");
-    const int32_t rc = enqueue_draw_updates(f, B, kind);
+    const int32_t rc = enqueue_draw_updates(f, R, kind);
     if (rc != WRK_OK) return rc;
+    enqueue_guide_follow(f, R, kind);
     if (kind.stop_seqs) {
         if (!f.stop_seq.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "stop-sequence buffers are not prepared");
         wrk::advance_stop_seq(q, io.argmax, io.tokens, f.history.tokens, io.counter, f.stop.par, f.stop.just_ended(), f.stop.live(),
@@ -937,16 +952,26 @@ static int32_t enqueue_beam_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind 
     return WRK_OK;
 }
 
-int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, bool argmax_done) {
+int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t frame_b, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, bool argmax_done) {
+    // the rows of the pick: a guided step ran 2B sequences, B conditional ones and their partners
+    const uint32_t B = kind.guided ? frame_b / 2 : frame_b;
     hipStream_t q = f.ctx->op_stream();
     const wrk::FrameIo& io = f.io();
     const uint32_t V = f.facts().num_vocab;
     const float* logits = io.head_o;
     if (kind.dry && (!f.dry.holds({B, V}) || argmax_done)) return wrk_fail(f.ctx, WRK_E_ARG, "DRY rows are not prepared");
+    // guidance in front of the bias: the guided rows of head_o's pairs (r, B + r) are what the rest reads; log-probs, last_logits and the
+    // stop snapshot keep head_o
+    if (kind.guided) {
+        if (!f.guide.holds({B, V}) || argmax_done || frame_b != 2 * B || b0 != 0 || kind.queue() || kind.tail == wrk_step_kind::BEAM)
+            return wrk_fail(f.ctx, WRK_E_ARG, "guidance rows are not prepared");
+        wrk::guide_rows(q, io.head_o, V, V, B, f.guide.par, f.guide.out, V);
+        logits = f.guide.out;
+    }
     // the bias first: the biased copy of head_o (which log-probs, last_logits and the stop snapshot keep raw) is what the rest reads
     if (kind.biased) {
         if (!f.bias.holds({B, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "bias rows are not prepared");
-        wrk::bias_rows(q, io.head_o, V, V, B, f.bias.par, f.bias.out, V);
+        wrk::bias_rows(q, logits, V, V, B, f.bias.par, f.bias.out, V);
         logits = f.bias.out;
     }
     if (kind.tail == wrk_step_kind::BEAM) return enqueue_beam_tail(f, B, kind, st, b0, logits, argmax_done);
@@ -992,10 +1017,11 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, co
             return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "log-probs: vocabulary of %u tokens", V);
     }
     if (kind.queue()) return enqueue_queue_tail(f, B, kind, st, b0);
-    if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, B, kind, st, b0);
+    if (kind.tail == wrk_step_kind::STOP) return enqueue_stop_tail(f, frame_b, B, kind, st, b0);
     const int32_t urc = enqueue_draw_updates(f, B, kind);
     if (urc != WRK_OK) return urc;
-    wrk::advance_tokens(q, io.argmax, io.tokens, f.history.tokens, io.counter, B);
+    enqueue_guide_follow(f, B, kind);
+    wrk::advance_tokens(q, io.argmax, io.tokens, f.history.tokens, io.counter, frame_b);
     return WRK_OK;
 }
 
@@ -1020,7 +1046,7 @@ static int32_t lane_prepare(wrk_lane& ln, wrk_v7_state* st, const uint32_t* firs
     if (rc == WRK_OK && kind.tail == wrk_step_kind::STOP) rc = wrk_stop_prepare(f, st, b0, B, stop + b0, seq);
     if (rc == WRK_OK && kind.queue()) rc = wrk_queue_prepare(f, st, B, *queue);
     if (rc == WRK_OK && kind.tail == wrk_step_kind::BEAM) rc = wrk_beam_prepare(f, st, B, *beam);
-    if (rc == WRK_OK && kind.logprobs) rc = wrk_logprob_prepare(f, B, steps, num_top);
+    if (rc == WRK_OK && kind.logprobs) rc = wrk_logprob_prepare(f, kind.guided ? B / 2 : B, steps, num_top);     // the rows of the pick
     ln.prog = nullptr;
     if (rc != WRK_OK || wrk_no_graph()) return rc;
     const wrk_frame_common::GraphKey key{st->uid, B | (b0 << 16), f.key_bits(B, mode) | kind.key(), 0u, kind.key2()};
@@ -1039,6 +1065,9 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
     const std::vector<hipStream_t>& streams = lanes[0].frame->lane_streams;
     const std::vector<hipEvent_t>& events = lanes[0].frame->lane_events;
     const uint32_t V = lanes[0].frame->facts().num_vocab;
+    // what comes back: the sequences of the call, in a guided one (one lane of 2R sequences) the R conditional ones, columns [0, R)
+    const uint32_t OB = kind.guided ? B / 2 : B;
+    auto out_rows = [&](const wrk_lane& ln) { return kind.guided ? ln.nb / 2 : ln.nb; };
     // every early return below leaves through this guard: the timing events are destroyed and, after an error, the lane streams are
     // drained (a lane's queued step programs must not outlive a frame that the next call may reallocate)
     struct Guard {
@@ -1121,7 +1150,7 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
         // the frozen slots and logits rows go back (head_o is what the read-back below takes), the lengths come out
         for (const wrk_lane& ln : lanes) {
             wrk::stop_restore(ctx->stream, stop_geom(*ln.frame, st, ln.b0), ln.nb, ctx->num_cu);
-            WRK_HIP(ctx, hipMemcpyAsync(stop.out_lengths + ln.b0, ln.frame->stop.lengths(), (size_t)ln.nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+            WRK_HIP(ctx, hipMemcpyAsync(stop.out_lengths + ln.b0, ln.frame->stop.lengths(), (size_t)out_rows(ln) * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
         WRK_LAUNCH_CHECK(ctx);
     }
@@ -1134,24 +1163,25 @@ static int32_t wrk_run_lanes(wrk_ctx* ctx, const std::vector<wrk_lane>& lanes, w
     }
     if (polled) *stop.steps_run = steps;
     for (const wrk_lane& ln : lanes) {
+        const size_t onb = out_rows(ln);
         if (out_tokens) {
-            if (groups == 1) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.frame->history.tokens, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
-            else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)B * 4, ln.frame->history.tokens, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
+            if (groups == 1 && !kind.guided) WRK_HIP(ctx, hipMemcpyAsync(out_tokens, ln.frame->history.tokens, (size_t)steps * B * 4, hipMemcpyDeviceToHost, ctx->stream));
+            else WRK_HIP(ctx, hipMemcpy2DAsync(out_tokens + ln.b0, (size_t)OB * 4, ln.frame->history.tokens, (size_t)ln.nb * 4, onb * 4, steps,
                                                hipMemcpyDeviceToHost, ctx->stream));
         }
         if (lp.on() && steps) {
             // rows [steps][nb] of the lane into [steps][B] at its first sequence; the top arrays the same with num_top entries per sequence
             const size_t n = lp.num_top;
-            WRK_HIP(ctx, hipMemcpy2DAsync(lp.logprob + ln.b0, (size_t)B * 4, ln.frame->logprob.logprob, (size_t)ln.nb * 4, (size_t)ln.nb * 4, steps,
+            WRK_HIP(ctx, hipMemcpy2DAsync(lp.logprob + ln.b0, (size_t)OB * 4, ln.frame->logprob.logprob, onb * 4, onb * 4, steps,
                                           hipMemcpyDeviceToHost, ctx->stream));
             if (n) {
-                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_ids + ln.b0 * n, B * n * 4, ln.frame->logprob.top_ids, ln.nb * n * 4, ln.nb * n * 4, steps,
+                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_ids + ln.b0 * n, OB * n * 4, ln.frame->logprob.top_ids, onb * n * 4, onb * n * 4, steps,
                                               hipMemcpyDeviceToHost, ctx->stream));
-                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_logprobs + ln.b0 * n, B * n * 4, ln.frame->logprob.top_logprobs, ln.nb * n * 4, ln.nb * n * 4, steps,
+                WRK_HIP(ctx, hipMemcpy2DAsync(lp.top_logprobs + ln.b0 * n, OB * n * 4, ln.frame->logprob.top_logprobs, onb * n * 4, onb * n * 4, steps,
                                               hipMemcpyDeviceToHost, ctx->stream));
             }
         }
-        if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits + (size_t)ln.b0 * V, ln.frame->io().head_o, (size_t)ln.nb * V * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (last_logits) WRK_HIP(ctx, hipMemcpyAsync(last_logits + (size_t)ln.b0 * V, ln.frame->io().head_o, onb * V * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     guard.ok = true;
@@ -1185,7 +1215,31 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
         rc = wrk_stop_seqs(ctx, o.stop_seq_tokens, o.stop_seq_offsets, o.stop_seq_owners, o.out_stop_match || o.stop_tail, o.stop_tail, B, V, "sequence", seq);
         kind.stop_seqs = seq.on;
     }
-    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), first_tokens, B);
+    // Guidance: the frame runs FB = 2B sequences, the conditional ones on slots [0, B) and their partners, which the caller
+    // fed the negative prompt, on slots [B, 2B).  Partner B + b gets the first token, the stop set, the stop-sequence row and the tail of
+    // b, sees the same draws and so ends in the same step; the pick rows stay B
+    const float* gscale = stop ? stop->opt->guidance_scale : nullptr;
+    const uint32_t* gfirst = stop ? stop->opt->guidance_first_tokens : nullptr;
+    std::vector<uint32_t> guided_first;
+    uint32_t FB = B;
+    if (rc == WRK_OK) WRK_ARG(ctx, gscale || !gfirst, "guidance_first_tokens without guidance_scale");
+    if (rc == WRK_OK && gscale) {
+        rc = wrk_guide_pack(ctx, gscale, B, V, rows.guide);
+        if (rc != WRK_OK) return rc;
+        WRK_ARG(ctx, B >= 1, "a guided call of no sequences");
+        if (((mode_arg >> 8) & 0xffu) > 1) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "guidance on several lanes: a sequence and its partner share one frame");
+        WRK_ARG(ctx, (uint64_t)2 * B <= st->num_batch, "guidance of %u sequences needs %u state slots, the state has %u", B, 2 * B, st->num_batch);
+        kind.guided = true;
+        FB = 2 * B;
+        guided_first.assign(first_tokens, first_tokens + B);
+        guided_first.insert(guided_first.end(), gfirst ? gfirst : first_tokens, (gfirst ? gfirst : first_tokens) + B);
+        first_tokens = guided_first.data();
+        // the partners' rows: rows [0, B) once more, through a copy (a range insert may not read from the vector it grows)
+        auto twice = [](auto& v) { const auto head = v; v.insert(v.end(), head.begin(), head.end()); };
+        twice(stop_rows);
+        if (seq.on) { twice(seq.rows); twice(seq.tails); }
+    }
+    if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), first_tokens, FB);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     if (stop) {
@@ -1200,37 +1254,40 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
     if (groups > m->max_lanes()) groups = m->max_lanes();
     if (groups < 1) groups = 1;
     if (groups > B) groups = B;
+    if (kind.guided) groups = 1;
     WRK_ARG(ctx, groups == 1 || !wrk_no_graph(), "concurrent pipelines replay captured programs: not with WRK_NO_GRAPH=1");
     m->before_loop();
     std::vector<wrk_lane> L(groups);
     for (uint32_t g = 0; g < groups; ++g) {
         rc = m->lane(g, groups, &L[g].frame);
         if (rc != WRK_OK) return rc;
-        L[g].b0 = (uint32_t)((uint64_t)B * g / groups);
-        L[g].nb = (uint32_t)((uint64_t)B * (g + 1) / groups) - L[g].b0;
+        L[g].b0 = (uint32_t)((uint64_t)FB * g / groups);
+        L[g].nb = (uint32_t)((uint64_t)FB * (g + 1) / groups) - L[g].b0;
         // lane g uploads the parameters of its own sequences: a sequence's tokens do not depend on the number of lanes
         rc = lane_prepare(L[g], st, first_tokens, steps, mode, kind, rows, stop_rows.data(), seq.on ? &seq : nullptr, nullptr, lp.num_top);
         if (rc != WRK_OK) return rc;
     }
     const wrk_stop_run run{stop ? stop->opt->poll_steps : 0u, stop ? stop->out_lengths : nullptr, stop ? stop->steps_run : nullptr};
-    rc = wrk_run_lanes(ctx, L, st, B, steps, mode, kind, out_tokens, last_logits, elapsed_ms, run, lp);
+    rc = wrk_run_lanes(ctx, L, st, FB, steps, mode, kind, out_tokens, last_logits, elapsed_ms, run, lp);
     if (rc != WRK_OK) return rc;
+    // rows of a lane that come back: its sequences, in a guided call (one lane of 2B) the B conditional ones, the lane's leading half
+    auto back_rows = [&](const wrk_lane& ln) { return kind.guided ? B : ln.nb; };
     if (kind.mirostat() && pick.mirostat_mu) {      // every lane's rows hold the mu after the draws that counted
         for (const wrk_lane& ln : L) {
-            WRK_HIP(ctx, hipMemcpy(rows.alt.data() + ln.b0, ln.frame->alt.par, (size_t)ln.nb * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost));
-            for (uint32_t b = ln.b0; b < ln.b0 + ln.nb; ++b) pick.mirostat_mu[b] = rows.alt[b].mu;
+            WRK_HIP(ctx, hipMemcpy(rows.alt.data() + ln.b0, ln.frame->alt.par, (size_t)back_rows(ln) * sizeof(wrk::SampleAlt), hipMemcpyDeviceToHost));
+            for (uint32_t b = ln.b0; b < ln.b0 + back_rows(ln); ++b) pick.mirostat_mu[b] = rows.alt[b].mu;
         }
     }
     if (kind.constrained && pick.grammar_state)     // every lane's words hold the states after the draws that counted
         for (const wrk_lane& ln : L)
-            WRK_HIP(ctx, hipMemcpy(pick.grammar_state + ln.b0, ln.frame->grammar.state, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
+            WRK_HIP(ctx, hipMemcpy(pick.grammar_state + ln.b0, ln.frame->grammar.state, (size_t)back_rows(ln) * 4, hipMemcpyDeviceToHost));
     if (kind.stop_seqs)                             // and the match words and the tails, frozen with the sequences that ended
         for (const wrk_lane& ln : L) {
             if (stop->opt->out_stop_match)
-                WRK_HIP(ctx, hipMemcpy(stop->opt->out_stop_match + ln.b0, ln.frame->stop_seq.match, (size_t)ln.nb * 4, hipMemcpyDeviceToHost));
+                WRK_HIP(ctx, hipMemcpy(stop->opt->out_stop_match + ln.b0, ln.frame->stop_seq.match, (size_t)back_rows(ln) * 4, hipMemcpyDeviceToHost));
             if (stop->opt->stop_tail)
                 WRK_HIP(ctx, hipMemcpy(stop->opt->stop_tail + (size_t)ln.b0 * WRK_STOP_TAIL_LEN, ln.frame->stop_seq.tail,
-                                       (size_t)ln.nb * WRK_STOP_TAIL_LEN * 4, hipMemcpyDeviceToHost));
+                                       (size_t)back_rows(ln) * WRK_STOP_TAIL_LEN * 4, hipMemcpyDeviceToHost));
         }
     return m->after_loop(groups);
 }
@@ -1286,6 +1343,8 @@ static int32_t wrk_beam_check(wrk_ctx* ctx, const wrk_beam_options* opt, const w
     WRK_ARG(ctx, !g.num_top && !g.out_logprob && !g.out_top_ids && !g.out_top_logprobs, "beam search returns no log-prob rows");
     WRK_ARG(ctx, !g.stop_seq_tokens && !g.stop_seq_offsets && !g.stop_seq_owners && !g.out_stop_match && !g.stop_tail, "beam search takes no stop sequences");
     if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "beam search: vocabulary of %u tokens", V);
+    if (g.guidance_scale || g.guidance_first_tokens)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "beam search with guidance: the permutation would have to move the partner slots too");
     const uint32_t B = G * W;
     pk.G = G; pk.W = W; pk.steps = steps; pk.poll_steps = g.poll_steps;
     int32_t rc = wrk_beam_inv_norm(ctx, opt->length_penalty, steps, pk.inv_norm);

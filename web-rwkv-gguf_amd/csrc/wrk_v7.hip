@@ -620,10 +620,10 @@ int32_t wrk_v7_frame_read(wrk_ctx* ctx, wrk_v7_model* m, const char* name, uint3
 
 // one decode step of sequences [b0, b0 + B) on this frame: embed s.tokens, run the layers and the head, then wrk_enqueue_pick.  The fused
 // greedy head leaves the arg-max in s.argmax, and in a plain step advances tokens / history / counter itself: nothing follows it.  A
-// constrained, a DRY or a biased step picks on the modified row, and a beam step makes no pick: its head only writes head_o, as a sampled step's does
+// constrained, a DRY, a biased or a guided step picks on the modified row, and a beam step makes no pick: its head only writes head_o, as a sampled step's does
 int32_t wrk_v7_model::enqueue_step(wrk_v7_state* st, uint32_t b0, uint32_t B, uint32_t mode, wrk_step_kind kind) {
     int32_t rc;
-    const bool fused = mode == 1 && act_dtype == WRK_F16, head_picks = fused && !kind.sampled() && !kind.constrained && !kind.dry && !kind.biased && kind.tail != wrk_step_kind::BEAM,
+    const bool fused = mode == 1 && act_dtype == WRK_F16, head_picks = fused && !kind.sampled() && !kind.constrained && !kind.dry && !kind.biased && !kind.guided && kind.tail != wrk_step_kind::BEAM,
                head_advances = head_picks && kind.tail == wrk_step_kind::PLAIN && !kind.logprobs;     // log-probs go between the pick and the advance
     if (fused) rc = enqueue_fused_decode(st, B, B, true, true, head_picks, head_advances, b0, true);
     else {

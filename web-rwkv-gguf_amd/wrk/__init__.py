@@ -75,7 +75,8 @@ class GenerateOptions(C.Structure):
     """wrk_generate_options: the pick (sampler arrays all NULL: arg-max; occ NULL: no penalties), the stop sets (CSR) and the log-prob
     outputs (out_logprob NULL: off) of wrk_v*_generate_stop."""
     _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
-                ("occ", _P), ("bias", _P), ("bias_set", _u32p), ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
+                ("occ", _P), ("bias", _P), ("bias_set", _u32p), ("guidance_scale", _f32p), ("guidance_first_tokens", _u32p),
+                ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
                 ("window", _P), ("dry_multiplier", _f32p), ("dry_base", _f32p), ("dry_allowed_length", _u32p), ("no_repeat_ngram", _u32p),
                 ("dry_breakers", _u32p), ("num_dry_breakers", C.c_uint32),
@@ -91,7 +92,8 @@ class QueueOptions(C.Structure):
     prefix state, the polled loop's block size and step cap and the log-prob outputs (out_logprob NULL: off) of wrk_v*_generate_queue."""
     _fields_ = [("num_requests", C.c_uint32), ("prompt_tokens", _u32p), ("prompt_offsets", _u32p), ("max_new", _u32p),
                 ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p),
-                ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("bias", _P), ("bias_set", _u32p), ("init_state", _P),
+                ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p), ("occ", _P), ("bias", _P), ("bias_set", _u32p), ("guidance_scale", _f32p),
+                ("init_state", _P),
                 ("poll_steps", C.c_uint32), ("max_steps", C.c_uint32), ("prompt_context_from", _u32p),
                 ("history", _P),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
@@ -253,6 +255,7 @@ HIP_SYMBOLS = {
     "wrk_logit_bias_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p, C.POINTER(_P)]),
     "wrk_logit_bias_destroy": (C.c_int32, [_P]),
     "wrk_bias_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _u32p]),
+    "wrk_guide_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _P, C.c_uint32]),
     "wrk_token_window_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "wrk_token_window_destroy": (C.c_int32, [_P]),
     "wrk_token_window_add": (C.c_int32, [_P, _P, C.c_uint32, _u32p, C.c_uint32]),
@@ -534,6 +537,19 @@ def _fill_bias(opt, n: int, keep: list, logit_bias, bias_set):
     if bias_set is not None:
         keep.append(_per_row(bias_set, n, np.uint32))
         opt.bias_set = _ptr(keep[-1], _u32p)
+
+
+def _fill_guidance(opt, n: int, keep: list, guidance_scale, negative_first_tokens=None):
+    """The guidance fields of a GenerateOptions or QueueOptions for n sequences: guidance_scale a scalar or one value per sequence."""
+    if guidance_scale is None:
+        if negative_first_tokens is not None:
+            raise ValueError("negative_first_tokens without guidance_scale")
+        return
+    keep.append(_per_row(guidance_scale, n, np.float32))
+    opt.guidance_scale = _ptr(keep[-1], _f32p)
+    if negative_first_tokens is not None:
+        keep.append(_per_row(negative_first_tokens, n, np.uint32))
+        opt.guidance_first_tokens = _ptr(keep[-1], _u32p)
 
 
 def _bias_csr(sets):
@@ -846,6 +862,31 @@ class Context:
         st = _per_row(sets, n, np.uint32)
         self.check(hip.wrk_bias_logits(self.h, buf.h, V, stride, n, lb.h, _ptr(st, _u32p)))
         return None if a is None else buf.read(np.float32, n * V).reshape(n, V)
+
+    def guide_logits(self, logits, scale, num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
+        """Classifier-free guidance on rows of logits on the device.  `logits` holds 2R rows, the R conditional ones
+        first and row R + r the unconditional partner of row r: an [2R, V] f32 array, or a `Buffer` of 2R rows of `row_stride` f32
+        (first `num_vocab` used).  scale: a scalar or one value per guided row, finite and >= 0; a row with scale 1 is its conditional
+        row bit for bit.  The rows are mixed raw (u + s (c - u), three f32 roundings), not log-softmaxed: no pick sees the
+        difference.  Returns the guided rows [R, V].  In a host loop it goes in front of `bias_logits`."""
+        if isinstance(logits, Buffer):
+            assert num_vocab, "a Buffer needs num_vocab"
+            buf, V = logits, int(num_vocab)
+            stride = int(row_stride or V)
+            n2 = (buf.nbytes // 4 - V) // stride + 1 if buf.nbytes >= 4 * V else 0
+        else:
+            a = np.ascontiguousarray(logits, dtype=np.float32)
+            a = a.reshape(2, -1) if a.ndim == 1 else a
+            n2, V = a.shape
+            stride = V
+            buf = self.buffer(a)
+        if n2 % 2:
+            raise ValueError(f"{n2} rows: guidance takes the conditional rows and as many unconditional ones")
+        n = n2 // 2
+        sc = _per_row(scale, n, np.float32)
+        out = self.buffer(np.zeros(max(n * V, 1), np.float32))
+        self.check(hip.wrk_guide_logits(self.h, buf.h, V, stride, n, _ptr(sc, _f32p), out.h, V))
+        return out.read(np.float32, n * V).reshape(n, V)
 
     def beam_step(self, logits, num_beams: int, scores, keys, lengths, status, stop=None, length_penalty: float = 0.0,
                   num_vocab: Optional[int] = None, row_stride: Optional[int] = None):
@@ -1837,11 +1878,49 @@ class Runtime:
         out = out[:run]
         return (out, lengths, logits) if want_logits else (out, lengths)
 
+    def generate_guided(self, first_tokens, steps: int, guidance_scale, negative_first_tokens=None, stop=None, temperature=None, top_p=None,
+                        seed=None, occurrence: "Occurrence" = None, presence=0.0, frequency=0.0, decay=1.0, mode: int = 1,
+                        want_logits: bool = False, poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None,
+                        mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, stop_tail=None,
+                        window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None, logit_bias: "LogitBias" = None,
+                        bias_set=None):
+        """`generate_stop` with classifier-free guidance (a negative prompt).  B = len(first_tokens) sequences run on state
+        slots [0, B), and sequence b has a partner on slot B + b, which the caller has fed the negative prompt (`infer` on slots
+        [B, 2B)): the state needs 2B slots.  Every step runs both, and the pick of b is made on `Context.guide_logits` of their two
+        head rows with guidance_scale[b] (a scalar or one value per sequence, finite and >= 0; 1: the conditional row bit for bit, which
+        makes the call the unguided `generate_stop` of the same 2B-sequence frame, columns [0, B) -- a `generate_stop` of B sequences runs
+        a smaller frame whose matmuls round differently, so it agrees to rounding, not bit for bit; > 1:
+        away from the negative prompt) -- in front of the bias, the penalties, DRY and the grammar, inside the step program.  The
+        partner feeds negative_first_tokens[b] at step 0 (None: first_tokens[b]) and then b's draws; it ends and is frozen with b.
+        stop (None: no stop ids) and every pick argument: as `generate_stop`, all B wide; log-probs and last logits stay on the raw
+        conditional rows.  Returns what `generate_stop` returns.  One lane only."""
+        ft = _u32(first_tokens)
+        ids, off = _stop_csr(stop, ft.size, "sequences")
+        opt, keep = GenerateOptions(), []
+        if stop_sequences is None and stop_tail is not None:
+            raise ValueError("stop_tail without stop_sequences")
+        self.last_stop_match = _fill_stop_sequences(opt, ft.size, keep, stop_sequences, "sequences")
+        self.last_stop_tail = None
+        if stop_sequences is not None:
+            self.last_stop_tail = _stop_tails(stop_tail, ft.size)
+            opt.stop_tail = _ptr(self.last_stop_tail, _u32p)
+        self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
+                                           mirostat, mirostat_mu, typical_p)
+        self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
+        _fill_dry(opt, ft.size, keep, window, dry, no_repeat_ngram, dry_breakers)
+        _fill_bias(opt, ft.size, keep, logit_bias, bias_set)
+        _fill_guidance(opt, ft.size, keep, guidance_scale, negative_first_tokens)
+        opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
+        out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, mode, want_logits, logprobs)
+        out = out[:run]
+        return (out, lengths, logits) if want_logits else (out, lengths)
+
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
                        mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None,
                        mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
-                       count_prompt=None, history: "HistoryPool" = None, logit_bias: "LogitBias" = None, bias_set=None):
+                       count_prompt=None, history: "HistoryPool" = None, logit_bias: "LogitBias" = None, bias_set=None,
+                       guidance_scale=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1882,7 +1961,9 @@ class Runtime:
         (reasons 1 and 2) leaves its slot's row and window there in the step that ends it, its last reply token counted.
         logit_bias / bias_set (a scalar or one set index per request; None: set 0; BIAS_NONE: none): one `LogitBias` for the call;
         request r's rows are biased with set bias_set[r] from the step it is dispatched, whatever its slot's previous request used, so
-        two requests of one call may ban different tokens.  The bias is not part of a pool entry."""
+        two requests of one call may ban different tokens.  The bias is not part of a pool entry.
+        guidance_scale: the queue's guidance_scale field; guidance is not built for the queue: anything but None is
+        refused with WRK_E_UNSUPPORTED.  Guided sequences go through `generate_guided`."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1903,6 +1984,7 @@ class Runtime:
         self.last_grammar_state = _fill_grammar(opt, R, keep, grammar, grammar_state)
         _fill_dry(opt, R, keep, window, dry, no_repeat_ngram, dry_breakers)
         _fill_bias(opt, R, keep, logit_bias, bias_set)
+        _fill_guidance(opt, R, keep, guidance_scale)
         match = _fill_stop_sequences(opt, R, keep, stop_sequences, "requests")
         self.last_stop_match = self.last_stop_tail = None
         if init_state is not None:
@@ -1953,7 +2035,7 @@ class Runtime:
         return [(out[off[r]:off[r] + lengths[r]].copy(), int(reasons[r]), int(slots[r]), int(starts[r])) for r in range(R)], run.value
 
     def generate_beam(self, first_tokens, steps: int, num_beams: int, stop=None, length_penalty: float = 0.0, logit_bias: "LogitBias" = None,
-                      bias_set=None, mode: int = 1, poll_steps: int = 0):
+                      bias_set=None, mode: int = 1, poll_steps: int = 0, guidance_scale=None):
         """Beam search kept on the device (wrk_v*_generate_beam): G = len(first_tokens) groups of `num_beams` beams on
         state slots [0, G * num_beams); group g starts from the state in slot g * num_beams and feeds first_tokens[g].  Every step
         keeps, per group, the num_beams best of the live beams' continuations and the finished hypotheses, ordered by
@@ -1962,13 +2044,16 @@ class Runtime:
         the stop token its last.  logit_bias / bias_set (one set index per group; None: set 0): the beams see the biased row, so a
         banned token is in no hypothesis.  Returns (per group: [(tokens, score, finished, slot)] by rank, steps_run); afterwards state
         slot `slot` holds that hypothesis's state, having consumed everything but its last token.  `last_beam_steps` = (tokens,
-        parents, scores), each [steps_run, B]: what every step put in every slot (BEAM_NO_TOKEN: not filled)."""
+        parents, scores), each [steps_run, B]: what every step put in every slot (BEAM_NO_TOKEN: not filled).
+        guidance_scale: the `gen` options' guidance_scale field; guidance is not built for beam search: anything but
+        None is refused with WRK_E_UNSUPPORTED."""
         ft = _u32(first_tokens).reshape(-1)
         G, W, steps = ft.size, int(num_beams), int(steps)
         B = G * max(W, 0)
         ids, off = _stop_csr(stop, G, "groups")
         gen, keep = GenerateOptions(), []
         _fill_bias(gen, G, keep, logit_bias, bias_set)
+        _fill_guidance(gen, G, keep, guidance_scale)
         gen.stop_tokens, gen.stop_offsets, gen.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
         opt = BeamOptions(max(W, 0), float(length_penalty), C.pointer(gen))
         n = max(B, 1)
