@@ -787,8 +787,9 @@ int32_t wrk_stop_sequences_advance(wrk_ctx* ctx, uint32_t num_vocab, uint32_t nu
  * device, and never with what its slot's previous request used; the rows of the steps that feed prompt tokens are biased too, their
  * draws are discarded as before.  A reply does not depend on the slot or the step the request was scheduled at.  Nothing of the bias
  * belongs to a state-pool or history-pool entry.  The two fields sit directly behind `occ`.
- * Guidance (wrk_generate_options) is not built for the queue: a refilled slot's partner would need the new request's negative prompt.
- * guidance_scale non-NULL is WRK_E_UNSUPPORTED before any launch; the field sits directly behind `bias_set`. */
+ * Guidance (wrk_generate_options) is not taken through these options: a refilled slot's partner needs the new request's negative prompt,
+ * which wrk_v7_generate_queue_guided (below) takes.  guidance_scale non-NULL is WRK_E_UNSUPPORTED before any launch in
+ * wrk_v7_generate_queue and wrk_v7_generate_queue_pool; the field sits directly behind `bias_set`. */
 typedef struct wrk_history_pool wrk_history_pool;   /* a history pool beside a state pool: wrk_queue_pool, below */
 typedef struct wrk_queue_options {
     uint32_t num_requests;
@@ -884,6 +885,55 @@ typedef struct wrk_queue_pool {
 } wrk_queue_pool;
 int32_t wrk_v7_generate_queue_pool(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
                                    const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_pool* pool);
+
+/* Guidance in the request queue: every request brings its own negative prompt and scale, and a refilled slot's partner takes the new
+ * request's negative prompt in at decode rate beside it.  wrk_v7_generate_queue with classifier-free guidance (wrk_guide_logits).
+ * Layout.  A guided queue of B = num_batch request slots runs on a state of at least 2 B slots; request slot b is the pair (state slot b,
+ * state slot B + b): the conditional half and its partner.  B <= 128: the 2 B slot records fit the one workgroup of the advance kernel.
+ * A request.  Request r has the prompt p_0 .. p_{n-1} of wrk_queue_options (n >= 1), the negative prompt q_0 .. q_{m-1} =
+ * negative_tokens[negative_offsets[r] .. negative_offsets[r + 1]) (CSR, m >= 0) and the scale s = scale[r], finite and >= 0.  m == 0 is
+ * allowed only with s == 1: an unguided request inside a guided queue, whose partner slot idles.  Let L = max(n, m).
+ * Dispatch.  The order is wrk_v7_generate_queue's: index order, ascending slot order among pairs that end in the same step.  A pair
+ * given request r at step f (f = 0, or the step after the one that ended the pair's previous request) feeds p_0 at step f + L - n and
+ * q_0 at step f + L - m, so both halves feed their last prompt token at step f + L - 1.  The draw of that step, made on the guided row,
+ * is reply token y_0; from then on both halves feed the same draws.  The sampler step of y_j is j (the step base is f + L - 1), and
+ * start_steps[r] stays "the step that fed p_0" = f + L - n: reply token j of request r was drawn by step start_steps[r] + n - 1 + j, as
+ * without guidance.  The schedule is a pure function of (n, m, reply lengths); with every m <= n it is wrk_v7_generate_queue's.
+ * The wait.  The half that starts late waits until its first token: it feeds a valid id, its draws are ignored, and nothing is
+ * counted, matched or pushed for it.  The state slot of a half is set to its start state by the step program directly in front of the
+ * step that feeds that half's first token -- for a half that starts at f this is wrk_v7_generate_queue's reset; an idle or waiting slot
+ * still runs the model on its state, so a half that starts late is reset when it starts, not when the pair is dispatched.  The start
+ * state is zeros, or init_state (wrk_queue_options) for the conditional half and negative_init_state for the partner, both one shared
+ * prefix state in wrk_v7_state_read's layout.  The pair's pick rows -- sampler, filter, Mirostat / typical, automaton state, bias set,
+ * DRY values, stop tail, penalty values, the occurrence reset, the window reset, the scale -- are the conditional request's and are
+ * written by the dispatch; no draw counts before y_0, so nothing observes when within [f, f + L - 1] they are written.  A partner
+ * with m == 0 is neither reset nor fed.
+ * End.  The conditional half decides the end -- stop id, stop sequence or max_new; reasons 1, 2, 3 and 0 as in wrk_v7_generate_queue.
+ * Both halves are released in that step and the pair takes the next request in the same step.  A request that was given to a pair but
+ * whose p_0 was not fed when max_steps ran out has reason 0.
+ * The guided row is wrk_guide_logits' row of the pair's two head rows with the pair's scale, bit for bit; the scale is data of the step
+ * program, written by the dispatch.  A pair with s == 1 passes its conditional row through as words and does not read the partner row.
+ * Log-probs stay on the raw conditional rows.  Order within a step: as wrk_generate_options' guidance.
+ * Composition: every sampler family, top_k / min_p, mirostat_mu per request, penalties with prompt_context_from (the conditional prompt
+ * only), DRY / the n-gram window, grammar, logit bias, stop ids and stop sequences, log-probs, max_steps and poll_steps -- `occ`, `window`
+ * and every per-slot row are num_batch wide.  Not built: a state pool or a history pool under a guided queue (no entry point takes
+ * both; opt->history is WRK_E_ARG), lanes (mode bits 8-15 > 1: WRK_E_UNSUPPORTED), scales that change along a reply, negative prompts
+ * through the prefill GEMMs.
+ * WRK_E_ARG before any launch, besides wrk_v7_generate_queue's cases: a NULL `guide`, `scale` or `negative_offsets`; offsets that do
+ * not start at 0 or decrease; negative_tokens NULL with a non-empty negative prompt; a scale that is NaN, infinite or negative; an empty
+ * negative prompt with a scale != 1; a negative token >= num_vocab; a state of fewer than 2 * num_batch slots; num_batch > 128;
+ * negative_init_state of another size or context, or the same buffer as init_state; opt->guidance_scale non-NULL (the scales come from
+ * `guide`).  The requests, negative prompts and scales are data of the step program: one cached program serves any guided queue;
+ * guided queue programs never share a program with the other loops, and a call without this entry point replays exactly the programs
+ * it replayed before. */
+typedef struct wrk_queue_guidance {
+    const float *scale;
+    const uint32_t *negative_tokens;
+    const uint32_t *negative_offsets;
+    const wrk_buf *negative_init_state;
+} wrk_queue_guidance;
+int32_t wrk_v7_generate_queue_guided(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
+                                     const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_guidance* guide);
 
 /* Beam search in the decode loops (Hugging Face's num_beams, vLLM's beam_search): the search over continuations that the other loops do
  * not make.  A hypothesis of an RWKV model is one fixed-size state slot, so a beam step is the batched step, a selection over at most
@@ -1037,6 +1087,9 @@ int32_t wrk_v6_generate_queue(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* s
 /* as wrk_v7_generate_queue_pool */
 int32_t wrk_v6_generate_queue_pool(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
                                    const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_pool* pool);
+/* as wrk_v7_generate_queue_guided */
+int32_t wrk_v6_generate_queue_guided(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
+                                     const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_guidance* guide);
 /* as wrk_v7_generate_beam */
 int32_t wrk_v6_generate_beam(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
                              uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null, uint32_t mode);

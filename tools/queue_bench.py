@@ -39,6 +39,17 @@ uniform in [8, 16] -- every request in place on its own entry.
 
     python tools/queue_bench.py --history [--baseline] [--history-batch 16] [--history-prompt 48] [--reps 5] [--steps 64]
 
+--guidance S measures the guided queue: per B of --batches a runtime of 2B state slots, R = 8 * B requests with prompts
+and negative prompts of --prompt tokens each, scale S, the same reply lengths.
+
+  (a) generate_queue_guided: one call, the pairs refilled on the device
+  (b) waves of B requests through generate_guided on the same 2B slots; a wave takes both prompts of its requests in by Runtime.infer and
+      runs for the longest reply of the wave
+  (c) the per-step time of a guided queue program whose requests never end, next to the guided stop program (generate_guided) of the
+      same B and the plain queue program on the same 2B slots, alternating
+
+    python tools/queue_bench.py --guidance 1.5 [--batches 8,16] [--reps 5] [--steps 64]
+
 Prints one JSON object.
 """
 import argparse
@@ -198,6 +209,83 @@ def history_bench(args, wrk, ctx, data, skw):
     return out
 
 
+def guided_bench(args, wrk, ctx, data, skw):
+    scale = args.guidance
+    out = {"model": f"RWKV-7 {args.model} Q4_K_M (synthetic)", "prompt_tokens": args.prompt, "negative_prompt_tokens": args.prompt,
+           "guidance_scale": scale, "reply_lengths": "uniform [32, 256], seed 7", "reps": args.reps, **skw,
+           "waves_note": "waves of B requests through generate_guided on the same 2B slots; both prompts of a wave go in by Runtime.infer; "
+                         "a wave runs the longest reply of the wave, the host cuts the rest", "batches": []}
+    med = lambda runs: float(np.median(runs))                       # noqa: E731
+    for B in [int(b) for b in args.batches.split(",") if b]:
+        rt = wrk.Runtime(ctx, wrk.GgufReader(data), num_batch=2 * B)        # B request slots on 2B state slots
+        V = rt.info.num_vocab
+        R = args.requests_per_slot * B
+        lens = np.random.default_rng(7).integers(32, 257, R).tolist()
+        prompts = [[(17 + 101 * r + 7 * i) % (V - 1) for i in range(args.prompt)] for r in range(R)]
+        negs = [[(23 + 89 * r + 11 * i) % (V - 1) for i in range(args.prompt)] for r in range(R)]
+        useful = int(sum(lens))
+
+        def queue():
+            t0 = time.perf_counter()
+            res, run = rt.generate_queue_guided(prompts, negs, scale, max_new=lens, **skw)
+            ms = (time.perf_counter() - t0) * 1e3
+            assert [len(t) for t, *_ in res] == lens
+            assert sorted({slot for _, _, slot, _ in res}) == list(range(B)), "the guided queue must serve on exactly B pairs"
+            return ms
+
+        def waves():
+            t0 = time.perf_counter()
+            for w in range(0, R, B):
+                wave, nwave = prompts[w:w + B], negs[w:w + B]
+                if args.prompt > 1:
+                    inp = wrk.RnnInput([p[:-1] for p in wave + nwave], 256)
+                    while sum(inp.remaining(b) for b in range(2 * B)) > 0:
+                        rt.infer(inp)
+                n = max(lens[w:w + B])
+                tok, _ = rt.generate_guided([p[-1] for p in wave], n, scale, negative_first_tokens=[q[-1] for q in nwave], **skw)
+                assert tok.shape == (n, B)
+            return (time.perf_counter() - t0) * 1e3
+
+        first, nfirst = [p[0] for p in prompts[:B]], [q[0] for q in negs[:B]]
+        never = dict(max_new=args.steps, max_steps=args.steps, poll_steps=0xffffffff, **skw)
+
+        def guided_queue_step():
+            res, run = rt.generate_queue_guided([[t] for t in first], [[t] for t in nfirst], scale, **never)
+            assert run == args.steps and [len(t) for t, *_ in res] == [args.steps] * B
+            return rt.last_queue_ms / args.steps
+
+        def guided_stop_step():
+            tok, _ = rt.generate_guided(first, args.steps, scale, negative_first_tokens=nfirst, poll_steps=0xffffffff, **skw)
+            assert tok.shape == (args.steps, B)
+            return rt.last_stop_ms / args.steps
+
+        def plain_queue_step():                 # the plain queue on the same 2B slots
+            res, run = rt.generate_queue([[t] for t in first + nfirst], **never)
+            assert run == args.steps and [len(t) for t, *_ in res] == [args.steps] * (2 * B)
+            return rt.last_queue_ms / args.steps
+        queue(), waves(), guided_queue_step(), guided_stop_step(), plain_queue_step()      # capture and warm up
+        qa, wa, gq, gs, pq = [], [], [], [], []
+        for _ in range(args.reps):
+            qa.append(queue())
+            wa.append(waves())
+            gq.append(guided_queue_step())
+            gs.append(guided_stop_step())
+            pq.append(plain_queue_step())
+        out["batches"].append({
+            "request_slots": B, "state_slots": 2 * B, "requests": R, "reply_tokens": useful,
+            "guided_queue_ms": round(med(qa), 2), "guided_queue_reply_tokens_per_s": round(useful / med(qa) * 1e3, 1),
+            "waves_ms": round(med(wa), 2), "waves_reply_tokens_per_s": round(useful / med(wa) * 1e3, 1),
+            "guided_queue_ms_all": [round(x, 2) for x in qa], "waves_ms_all": [round(x, 2) for x in wa],
+            "guided_queue_never_ending_ms_per_step": round(med(gq), 5), "guided_stop_ms_per_step": round(med(gs), 5),
+            "plain_queue_2b_never_ending_ms_per_step": round(med(pq), 5),
+            "guided_queue_minus_guided_stop_us": round((med(gq) - med(gs)) * 1e3, 2),
+            "guided_queue_minus_plain_queue_us": round((med(gq) - med(pq)) * 1e3, 2),
+            "guided_queue_ms_per_step_all": [round(x, 5) for x in gq], "guided_stop_ms_per_step_all": [round(x, 5) for x in gs],
+            "plain_queue_ms_per_step_all": [round(x, 5) for x in pq]})
+        rt.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="1.5B")
@@ -214,6 +302,7 @@ def main():
     ap.add_argument("--history-batch", type=int, default=16)
     ap.add_argument("--history-prompt", type=int, default=48)
     ap.add_argument("--history-window", type=int, default=256)
+    ap.add_argument("--guidance", type=float, default=None, help="the guided queue (DESIGN.md §7s) with this scale in the place of the queue's legs")
     args = ap.parse_args()
     import wrk
 
@@ -221,6 +310,10 @@ def main():
     ctx = wrk.Context(0)
     data = bench.make_model_gguf(args.model, seed=42)
     skw = dict(temperature=1.0, top_p=0.9)
+    if args.guidance is not None:
+        print(json.dumps(guided_bench(args, wrk, ctx, data, skw)))
+        ctx.close()
+        return
     if args.history:
         print(json.dumps(history_bench(args, wrk, ctx, data, skw)))
         ctx.close()

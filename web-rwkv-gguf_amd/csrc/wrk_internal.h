@@ -323,6 +323,14 @@ void advance_queue(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint3
 // occurrence rows: count = 0, present bit cleared, banned bit kept (v: vocabulary).  Workgroups of the other slots return at once
 struct QueueGeom { float* state; uint32_t layers, num_batch, b0, v; size_t slot; };
 void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t b, int num_cu);
+// A guided queue (the rule: queue_dispatch_guided): `pairs` request slots, pair i = slots i and pairs + i of q.slots /
+// q.started / tokens / drawn (guide_follow has copied the draw of row i to row pairs + i) and of the state; pairs <= 128; q has the four
+// guided arrays and pair_started.  advance_queue_guided: advance_queue over the pairs, the history 2 * pairs wide.  queue_reset_guided:
+// queue_reset over the 2 * pairs state slots by q.started, a partner slot from ctl->negative_init_state, and the occurrence rows of the
+// pairs by q.pair_started
+void advance_queue_guided(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q,
+                          uint32_t pairs);
+void queue_reset_guided(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t pairs, int num_cu);
 // A state pool under the queue: P states in wrk_v7_state_read's layout in one device buffer; request r may start from a
 // copy of entry start[r] and has its end state written to entry save[r] in the step that ends it.  QueueStateCtl: the pool's pointer and
 // entry count are data (one captured program serves any pool), next to the length of the step's turnover list (QueueTurn).

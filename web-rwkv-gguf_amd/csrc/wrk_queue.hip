@@ -16,6 +16,10 @@
 //                   the occurrence reset's place; one grid over the vocabulary and the largest ring walks the same turnover list, saves
 //                   each listed slot's occurrence row and token window to its request's history entry and then sets them from the
 //                   next request's entry, or to the reset
+//   advance_queue_guided, queue_reset_guided   their places in the programs of a guided queue: a request slot is a pair of
+//                   state slots, the conditional half and its partner, which takes the request's negative prompt in beside it; the
+//                   advance schedules both halves so that they end their prompts in the same step, and the reset runs over 2B slots,
+//                   each half set to its own start state directly in front of the step that feeds its first token
 //
 // started[b] is written by EVERY advance_queue launch for every slot, so the flag a reset launch reads was written by the launch in front
 // of it in the same stream; nothing has to clear it.  Plain vector stores only; no atomics; no kernel waits on another.
@@ -144,6 +148,130 @@ __global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_pool_seq_kernel(c
     advance_queue_body<true, true>(drawn, tokens, history, counter, Q, P, b);
 }
 
+// A guided queue: B <= QUEUE_THREADS / 2 pairs, thread i < B owns pair i -- the slot records, tokens and start flags i
+// (the conditional half) and B + i (its partner).  Either half pops its prompt tokens or counts its wait down; the step that ends a wait
+// raises the half's start flag, so that the reset behind this launch sets its state slot directly in front of the step that feeds its
+// first token (which queue_dispatch_guided left in `tokens`).  The conditional half's reply draw -- made on the guided row, and copied to
+// row B + i by guide_follow in front of this launch -- is fed to both halves, checked and counted exactly as advance_queue_body does; the
+// end releases both halves and the pair takes the next request in the same step, by the same scan.  started [2B] and pair_started [B]
+// are written for every slot and pair by every launch
+template <bool SEQ>
+__device__ __forceinline__ void advance_queue_guided_body(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                          uint32_t* __restrict__ history, uint32_t* __restrict__ counter, const QueueBufs& Q,
+                                                          uint32_t b) {
+    __shared__ uint32_t wave_ended[QUEUE_WAVES];
+    const uint32_t step = *counter;
+    const uint32_t next = Q.ctl->next_request, live = Q.ctl->live, num_requests = Q.ctl->num_requests;
+    const uint32_t i = threadIdx.x, lane = i & 63u, wave = i >> 6;
+    int ended = 0;
+    uint32_t take = 0, start_c = 0, start_p = 0;
+    QueueSlot s{0u, 0u, 0u, QUEUE_IDLE}, p{0u, 0u, 0u, QUEUE_IDLE};
+    if (i < b) {
+        s = Q.slots[i];
+        p = Q.slots[b + i];
+        const uint32_t y = drawn[i];
+        history[(size_t)step * 2u * b + i] = y;         // 2B wide, as a guided stop program's: the host cuts the replies out of columns [0, B)
+        history[(size_t)step * 2u * b + b + i] = drawn[b + i];
+        // the partner first: its phases never decide anything
+        if (p.phase == QUEUE_WAIT) {
+            p.pos -= 1;
+            if (p.pos == 0) { start_p = 1; p.phase = Q.neg_len[p.req] == 1 ? QUEUE_REPLY : QUEUE_PROMPT; }
+        } else if (p.phase == QUEUE_PROMPT) {
+            p.pos += 1;
+            tokens[b + i] = Q.pool[Q.neg_off[p.req] + p.pos];
+            if (p.pos + 1 == Q.neg_len[p.req]) p.phase = QUEUE_REPLY;
+        } else if (p.phase == QUEUE_REPLY) {
+            tokens[b + i] = y;
+        }                                               // idle: tokens[b + i] stays
+        if (s.phase == QUEUE_WAIT) {
+            s.pos -= 1;
+            if (s.pos == 0) {
+                start_c = 1;
+                s.phase = Q.reqs[s.req].prompt_len == 1 ? QUEUE_REPLY : QUEUE_PROMPT;
+                if (Q.ctx_from) take = Q.ctx_from[s.req] == 0u;     // p_0, in tokens[i] since the dispatch, is fed by the next step
+            }
+        } else if (s.phase == QUEUE_PROMPT) {
+            const QueueReq* r = Q.reqs + s.req;
+            s.pos += 1;
+            tokens[i] = Q.pool[r->prompt_off + s.pos];
+            if (Q.ctx_from) take = s.pos >= Q.ctx_from[s.req];
+            if (s.pos + 1 == r->prompt_len) s.phase = QUEUE_REPLY;
+        } else if (s.phase == QUEUE_REPLY) {
+            const QueueReq* r = Q.reqs + s.req;
+            tokens[i] = y;
+            const uint32_t n = r->stop_count < WRK_MAX_STOP_TOKENS ? r->stop_count : WRK_MAX_STOP_TOKENS;
+            int hit = 0;
+            if (SEQ) {
+                uint32_t* tp = Q.seq_tail + (size_t)i * STOP_TAIL;
+                StopTail tail = stop_tail_load(tp);
+                const uint32_t match = stop_seq_step(tail, y, Q.seq_rows + s.req, r->stop_ids, n);
+                stop_tail_store(tp, tail);
+                hit = match != WRK_STOP_MATCH_NONE;
+                if (hit) Q.seq_match[s.req] = match;
+            } else {
+                for (uint32_t k = 0; k < n; ++k) hit |= (r->stop_ids[k] == y);
+            }
+            s.reply += 1;
+            Q.log[s.req].length = s.reply;
+            const uint32_t reason = hit ? 1u : (s.reply == r->max_new ? 2u : 0u);
+            if (reason) {
+                Q.log[s.req].reason = reason; ended = 1;
+                if (Q.alt_mu) Q.alt_mu[s.req] = Q.alt_par[i].mu;
+                if (Q.gram_req) Q.gram_req[s.req] = Q.gram_state[i];
+            }
+        }
+    }
+    const unsigned long long mask = __ballot(ended);
+    const uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_ended[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();                            // also orders every read of *counter and *ctl before their update
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < QUEUE_WAVES; ++w) {
+        if (w < wave) before += wave_ended[w];
+        total += wave_ended[w];
+    }
+    if (i < b) {
+        uint32_t dealt = 0;
+        if (ended) {
+            s.phase = QUEUE_IDLE;
+            p.phase = QUEUE_IDLE;
+            dealt = next + before + rank < num_requests;
+        }
+        if (dealt) {
+            const QueuePairStart ps = queue_dispatch_guided(Q, tokens, next + before + rank, i, b, step + 1);
+            if (ps.wipe) {
+                uint32_t* meta = Q.dry_par[i].meta;
+                meta[0] = meta[1] = 0u;
+            }
+            start_c = ps.start_cond; start_p = ps.start_part;
+        } else {
+            Q.slots[i] = s;
+            Q.slots[b + i] = p;
+            if (Q.intake) Q.intake[i] = take;
+        }
+        Q.started[i] = start_c;
+        Q.started[b + i] = start_p;
+        Q.pair_started[i] = dealt;
+    }
+    if (i == 0) {
+        if (total) { Q.ctl->next_request = next + total; Q.ctl->live = live - total; }
+        *counter = step + 1;
+    }
+}
+
+__global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_guided_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                                             uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
+                                                                             const QueueBufs Q, uint32_t b) {
+    advance_queue_guided_body<false>(drawn, tokens, history, counter, Q, b);
+}
+
+__global__ void __launch_bounds__(QUEUE_THREADS) advance_queue_guided_seq_kernel(const uint32_t* __restrict__ drawn, uint32_t* __restrict__ tokens,
+                                                                                 uint32_t* __restrict__ history, uint32_t* __restrict__ counter,
+                                                                                 const QueueBufs Q, uint32_t b) {
+    advance_queue_guided_body<true>(drawn, tokens, history, counter, Q, b);
+}
+
 struct QueueResetArgs {
     float* state;               // [L][num_batch][slot] f32
     const uint32_t* started;
@@ -152,12 +280,15 @@ struct QueueResetArgs {
     size_t slot;                // (S + 2) * D
 };
 
-__global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_state_kernel(const QueueResetArgs A) {
+// GUIDED (queue_reset_state_guided_kernel): the grid's y runs over the 2 * pairs state slots of a guided queue, and a partner slot
+// (y >= pairs) starts from negative_init_state
+template <bool GUIDED>
+__device__ __forceinline__ void queue_reset_state_body(const QueueResetArgs& A, uint32_t pairs) {
     const uint32_t b = blockIdx.y;
     if (A.started[b] == 0) return;
     const uint32_t l = blockIdx.x / A.slices, part = blockIdx.x - l * A.slices;
     float* dst = A.state + ((size_t)l * A.num_batch + A.b0 + b) * A.slot;
-    const float* init = A.ctl->init_state;
+    const float* init = GUIDED && b >= pairs ? A.ctl->negative_init_state : A.ctl->init_state;
     const float* src = init ? init + (size_t)l * A.slot : nullptr;
     const size_t n = A.slot;
     if (A.vec && (((uintptr_t)src) & 15u) == 0) {
@@ -166,6 +297,12 @@ __global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_state_kernel(const 
     } else {
         for (size_t i = (size_t)part * QUEUE_THREADS + threadIdx.x; i < n; i += (size_t)A.slices * QUEUE_THREADS) dst[i] = src ? src[i] : 0.0f;
     }
+}
+
+__global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_state_kernel(const QueueResetArgs A) { queue_reset_state_body<false>(A, 0u); }
+
+__global__ void __launch_bounds__(QUEUE_THREADS) queue_reset_state_guided_kernel(const QueueResetArgs A, uint32_t pairs) {
+    queue_reset_state_body<true>(A, pairs);
 }
 
 // Pool programs: queue_reset_state_kernel's place.  Workgroup (layer, slice) walks the step's turnover list; a thread moves the same
@@ -357,6 +494,26 @@ void queue_reset(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t
     A.slices = queue_slices(g, A.vec ? QUEUE_CHUNK : QUEUE_THREADS, num_cu);
     queue_reset_state_kernel<<<dim3(A.layers * A.slices, b), QUEUE_THREADS, 0, s>>>(A);
     queue_reset_occurrence(s, g, q, b);
+}
+
+void advance_queue_guided(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q,
+                          uint32_t pairs) {
+    if (q.seq_rows) advance_queue_guided_seq_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, pairs);
+    else advance_queue_guided_kernel<<<1, QUEUE_THREADS, 0, s>>>(drawn, tokens, history, counter, q, pairs);
+}
+
+void queue_reset_guided(hipStream_t s, const QueueGeom& g, const QueueBufs& q, uint32_t pairs, int num_cu) {
+    if (pairs == 0) return;
+    QueueResetArgs A{};
+    A.state = g.state; A.started = q.started; A.ctl = q.ctl;
+    A.layers = g.layers; A.num_batch = g.num_batch; A.b0 = g.b0; A.slot = g.slot;
+    A.vec = g.slot % 4 == 0;
+    A.slices = queue_slices(g, A.vec ? QUEUE_CHUNK : QUEUE_THREADS, num_cu);
+    queue_reset_state_guided_kernel<<<dim3(A.layers * A.slices, 2u * pairs), QUEUE_THREADS, 0, s>>>(A, pairs);
+    // the occurrence rows are the pairs': reset where a pair takes a request, whenever its halves start
+    QueueBufs rows = q;
+    rows.started = q.pair_started;
+    queue_reset_occurrence(s, g, rows, pairs);
 }
 
 void advance_queue_pool(hipStream_t s, const uint32_t* drawn, uint32_t* tokens, uint32_t* history, uint32_t* counter, const QueueBufs& q,

@@ -34,8 +34,10 @@ WRK_HD inline void stop_tail_clear(uint32_t* p) { for (uint32_t j = 0; j < WRK_S
 // R requests are served on the B slots of a state; the slot bookkeeping is device data in per-frame buffers written before every call, so
 // one captured program serves any queue.  QueueReq: one request (prompt = pool[prompt_off .. + prompt_len), its pick parameters and stop
 // set).  QueueSlot: what slot b is doing -- phase says what the draw of the NEXT step is: QUEUE_PROMPT a draw to discard (the step feeds a
-// prompt token that is not the last), QUEUE_REPLY reply token number `reply`, QUEUE_IDLE nothing.  QueueLog: per request, as it runs
-enum : uint32_t { QUEUE_IDLE = 0, QUEUE_PROMPT = 1, QUEUE_REPLY = 2 };
+// prompt token that is not the last), QUEUE_REPLY reply token number `reply`, QUEUE_IDLE nothing.  QueueLog: per request, as it runs.
+// QUEUE_WAIT (guided queues only): the half of a pair that starts late -- `pos` more steps feed a valid id whose draws are
+// ignored, then the step program resets the half's state slot and the half feeds its first token, which the dispatch left in `tokens`
+enum : uint32_t { QUEUE_IDLE = 0, QUEUE_PROMPT = 1, QUEUE_REPLY = 2, QUEUE_WAIT = 3 };
 static constexpr uint32_t QUEUE_NO_ENTRY = 0xFFFFFFFFu;
 struct QueueReq {
     uint32_t prompt_off, prompt_len, max_new, seed;
@@ -46,7 +48,8 @@ struct QueueReq {
 };
 struct QueueSlot { uint32_t req, pos, reply, phase; };
 struct QueueLog { uint32_t length, reason, slot, start_step; };
-struct QueueCtl { uint32_t next_request, num_requests, live, pad; const float* init_state; };     // init_state: [L][slot] f32 or nullptr
+// init_state: [L][slot] f32 or nullptr; negative_init_state: the same for the partner halves of a guided queue
+struct QueueCtl { uint32_t next_request, num_requests, live, pad; const float* init_state; const float* negative_init_state = nullptr; };
 // Per slot [B]: slots, started, the rows of the call's features in their groups (nullptr: the call is without the feature), seq_tail,
 // intake.  Per request [R], all the queue's own: reqs, log and what a request carries besides its QueueReq, nullptr as its rows are
 struct QueueBufs {
@@ -70,6 +73,12 @@ struct QueueBufs {
     const uint32_t* ctx_from = nullptr; uint32_t* intake = nullptr;
     // biased queues: the slots' bias set words and request r's (only read: a bias has no state)
     uint32_t *bias_set = nullptr, *bias_req = nullptr;
+    // guided queues, all four or none: request r's negative prompt pool[neg_off[r] .. + neg_len[r]) (length 0: none) and
+    // its scale; the pairs' scale row [B], the `guide` group's parameter row.  With them slots / started are [2B] -- pair b is the records
+    // b (conditional half) and B + b (partner) -- and pair_started [B] is 1 when the pair took a request in this step (written for every
+    // pair by every launch, as started): the flag of the occurrence reset, which stays B wide
+    const uint32_t *neg_off = nullptr, *neg_len = nullptr; const float* scale_req = nullptr; float* scale = nullptr;
+    uint32_t* pair_started = nullptr;
 };
 // A state pool under the queue.  QueueTurn: one slot that ended in the step -- `save` the entry its state goes to,
 // `started` / `start` as started[slot] and the entry the slot's next request begins from; QUEUE_NO_ENTRY: none
@@ -112,6 +121,34 @@ WRK_HD inline bool queue_dispatch(const QueueBufs& Q, uint32_t* tokens, uint32_t
     Q.slots[b] = QueueSlot{r, 0u, 0u, q->prompt_len == 1 ? QUEUE_REPLY : QUEUE_PROMPT};
     if (Q.intake) Q.intake[b] = Q.ctx_from[r] == 0u;
     return Q.dry_par && !(P && P->history);
+}
+
+// THE dispatch rule of a guided queue: request r goes to pair b of B -- slot records, tokens and state slots b and B + b --
+// and step f is the first the pair runs for it.  With n the prompt's and m the negative prompt's length and L = max(n, m), the
+// conditional half feeds p_0 at step f + L - n and the partner q_0 at step f + L - m, so both feed their last prompt token at step
+// f + L - 1, whose draw is reply token 0: the sampler's step base is f + L - 1, and start_step = f + L - n stays "the step that fed p_0".
+// Writes everything queue_dispatch writes for (r, b, first_step f + L - n) -- the pair's pick rows are the conditional request's -- and
+// then: a conditional half that starts late gets the record {r, L - n, 0, QUEUE_WAIT} and no intake flag (p_0 stays in tokens[b], a
+// valid id, until it is fed for good); the partner's record is QUEUE_IDLE when m == 0 (tokens[B + b] stays: neither reset nor fed), else
+// q_0 goes to tokens[B + b] and the record is {r, L - m, 0, QUEUE_WAIT} or, on time, {r, 0, 0, REPLY if m == 1 else PROMPT}; the pair's
+// scale.  start_cond / start_part: the half feeds its first token at step f itself -- its state slot is to be set to its start state
+// in front of step f; a half in QUEUE_WAIT is reset by the step that ends its wait.  wipe: queue_dispatch's answer
+struct QueuePairStart { bool wipe; uint32_t start_cond, start_part; };
+WRK_HD inline QueuePairStart queue_dispatch_guided(const QueueBufs& Q, uint32_t* tokens, uint32_t r, uint32_t b, uint32_t B, uint32_t f) {
+    const uint32_t n = Q.reqs[r].prompt_len, m = Q.neg_len[r], L = n > m ? n : m;
+    const bool wipe = queue_dispatch(Q, tokens, r, b, f + (L - n), nullptr);
+    if (L > n) {
+        Q.slots[b] = QueueSlot{r, L - n, 0u, QUEUE_WAIT};
+        if (Q.intake) Q.intake[b] = 0u;
+    }
+    if (m == 0) {
+        Q.slots[B + b] = QueueSlot{r, 0u, 0u, QUEUE_IDLE};
+    } else {
+        tokens[B + b] = Q.pool[Q.neg_off[r]];
+        Q.slots[B + b] = L > m ? QueueSlot{r, L - m, 0u, QUEUE_WAIT} : QueueSlot{r, 0u, 0u, m == 1 ? QUEUE_REPLY : QUEUE_PROMPT};
+    }
+    Q.scale[b] = Q.scale_req[r];
+    return QueuePairStart{wipe, L == n ? 1u : 0u, m != 0 && L == m ? 1u : 0u};
 }
 
 }  // namespace wrk

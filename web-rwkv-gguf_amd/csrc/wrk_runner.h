@@ -113,7 +113,8 @@ struct wrk_step_kind {
     bool biased = false;
     // classifier-free guidance (wrk_guide.hip): the step runs 2R sequences, the conditional ones [0, R) and their partners
     // [R, 2R); in front of the bias guide_rows makes guide.out [R][V] from rows r and R + r of head_o and the scales of guide.par, and the
-    // whole chain and the pick run on R rows of it; log-probs keep rows [0, R) of head_o; then guide_follow, and the tail over 2R rows
+    // whole chain and the pick run on R rows of it; log-probs keep rows [0, R) of head_o; then guide_follow, and the tail over 2R rows.
+    // With a QUEUE tail: R request slots, each a pair of state slots; advance_queue_guided / queue_reset_guided are the tail
     bool guided = false;
     bool sampled() const { return pick != GREEDY; }
     bool filtered() const { return pick == FILTERED; }
@@ -292,6 +293,15 @@ struct wrk_queue_intake_bufs {
     uint32_t* flags = nullptr;
     void layout(wrk_dev_cut& c, const size_t* d) { c.take(flags, d[0] * 4); }
 };
+// a guided queue: the pairs' dispatch flags [pairs] and the requests' negative prompts (offsets into the queue's token
+// pool, lengths) and scales [requests]; the pairs' scale row is the guide group's
+struct wrk_queue_guide_bufs {
+    static constexpr int DIMS = 2;              // pairs, requests
+    static constexpr unsigned EXACT = 0;
+    uint32_t *pair_started = nullptr, *neg_off = nullptr, *neg_len = nullptr;
+    float* scale = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) { c.take(pair_started, d[0] * 4); c.take(neg_off, d[1] * 4); c.take(neg_len, d[1] * 4); c.take(scale, d[1] * 4); }
+};
 // a queue call with a state pool: the pool's control words and the turnover list [slots]
 struct wrk_queue_state_bufs {
     static constexpr int DIMS = 1;              // slots
@@ -392,11 +402,12 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_queue_seq_bufs> queue_seq;
     wrk_dev_group<wrk_queue_state_bufs> queue_states;
     wrk_dev_group<wrk_queue_intake_bufs> queue_intake;
+    wrk_dev_group<wrk_queue_guide_bufs> queue_guide;
     wrk_dev_group<wrk_logprob_bufs> logprob;
     wrk_dev_group<wrk_beam_bufs> beam;
     template <class F> void each_group(F&& f) {     // the one list of the groups
         f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(bias); f(guide); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
-        f(queue_states); f(queue_intake); f(logprob); f(beam);
+        f(queue_states); f(queue_intake); f(queue_guide); f(logprob); f(beam);
     }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
     uint32_t live_host_cap = 0;
@@ -496,10 +507,12 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
                      const wrk_pick_args& pick, uint32_t* out_tokens, float* last_logits, float* elapsed_ms, uint32_t mode_arg,
                      const wrk_stop_call* stop = nullptr);
 // wrk_v*_generate_queue (tail QUEUE) / _queue_pool (QUEUE_POOL): the stop call on one lane with the queue's tail and live count
-// (requests not yet ended); after the loop the log and the history rows come back and the replies are cut out of them
+// (requests not yet ended); after the loop the log and the history rows come back and the replies are cut out of them.
+// wrk_v*_generate_queue_guided (tail QUEUE, `guide` set, `guided` true): B pairs on a frame of 2B sequences -- the pick rows, the
+// occurrence rows, the window, the tails and the intake flags stay B wide; the slot records, start flags, tokens and history are 2B wide
 int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                            const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail,
-                           const wrk_queue_pool* pool);
+                           const wrk_queue_pool* pool, const wrk_queue_guidance* guide = nullptr, bool guided = false);
 // wrk_v*_generate_beam (tail BEAM): the stop call's polled loop on one lane over B = G * num_beams slots with the beam tail and the count of
 // LIVE slots; after the loop the DONE slots are restored from their snapshots, the records and the history rows come back and the
 // hypotheses are backtracked through the parents on the host

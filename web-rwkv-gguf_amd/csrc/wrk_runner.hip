@@ -486,10 +486,17 @@ struct wrk_queue_pack {
     uint32_t* match_out = nullptr;  // the options' out_stop_match, or nullptr
     std::vector<uint32_t> from;     // prompt intake: [R] the options' prompt_context_from
     const wrk_history_pool* history = nullptr;  // with a state pool: its history pool, or nullptr
+    // a guided queue (kind.guided; wrk_queue_guide_check): [R] the negative prompts -- offsets into `pool`, where they follow
+    // the prompts, and lengths -- and the scales; the partner halves' start state.  wrk_queue_start: first_tokens, slots and `started`
+    // are [2B], pair b the entries b and B + b; pair_started [B]; rows.guide the pairs' scale row [B]
+    std::vector<uint32_t> neg_off, neg_len, started, pair_started;
+    std::vector<float> scale;
+    const float* negative_init_state = nullptr;
 };
 
+// guided: the call is wrk_v*_generate_queue_guided's -- B pairs of state slots; the guidance itself: wrk_queue_guide_check, behind this
 static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
-                               wrk_queue_result* out, wrk_queue_pack& pk) {
+                               wrk_queue_result* out, wrk_queue_pack& pk, bool guided) {
     WRK_ARG(ctx, opt, "options required");
     WRK_ARG(ctx, out && out->lengths && out->reasons && out->slots && out->start_steps && out->out_tokens && out->steps_run,
             "every result array is required");
@@ -498,11 +505,17 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     WRK_ARG(ctx, opt->prompt_tokens && opt->prompt_offsets && opt->max_new, "prompt_tokens, prompt_offsets and max_new are required");
     WRK_ARG(ctx, opt->max_steps >= 1, "max_steps 0");
     pk.lp = wrk_logprob_call{opt->num_top, opt->out_logprob, opt->out_top_ids, opt->out_top_logprobs};
-    WRK_ARG(ctx, B >= 1 && B <= st->num_batch && B <= 256, "num_batch %u: must be in [1, min(%u, 256)]", B, st->num_batch);
+    if (guided) {
+        WRK_ARG(ctx, B >= 1 && B <= 128, "num_batch %u: a guided queue has 1 to 128 request slots", B);
+        WRK_ARG(ctx, (uint64_t)2 * B <= st->num_batch, "a guided queue of %u request slots needs %u state slots, the state has %u", B, 2 * B, st->num_batch);
+    } else {
+        WRK_ARG(ctx, B >= 1 && B <= st->num_batch && B <= 256, "num_batch %u: must be in [1, min(%u, 256)]", B, st->num_batch);
+    }
     if (((mode_arg >> 8) & 0xffu) > 1)
         return wrk_fail(ctx, WRK_E_UNSUPPORTED, "generate_queue on several lanes: one queue shared by several streams would need cross-stream atomics");
+    WRK_ARG(ctx, !guided || !opt->guidance_scale, "guidance_scale in the options of a guided queue: the scales come from wrk_queue_guidance");
     if (opt->guidance_scale)
-        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "generate_queue with guidance: a refilled slot's partner would need the new request's negative prompt");
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "generate_queue with guidance_scale: the negative prompts go through wrk_v*_generate_queue_guided");
     int32_t rc = queue_csr_check(ctx, opt->prompt_offsets, R, "prompt_offsets");
     // the stop sets and the pick parameters go through the validation of the other loops, R rows at a time; of the penalty rows only
     // (presence, frequency, decay) are kept, a slot's row pointers are its own
@@ -609,7 +622,49 @@ static int32_t wrk_queue_pool_check(wrk_ctx* ctx, const wrk_queue_pool* pool, co
     return WRK_OK;
 }
 
+// after wrk_queue_check(guided): the guidance of wrk_v*_generate_queue_guided validated into pk (WRK_E_ARG / WRK_E_UNSUPPORTED before any
+// launch): the scales, the negative prompts appended to the token pool, the partners' start state; sets kind.guided
+static int32_t wrk_queue_guide_check(wrk_ctx* ctx, const wrk_queue_guidance* guide, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t V,
+                                     wrk_queue_pack& pk) {
+    WRK_ARG(ctx, guide, "guide required");
+    WRK_ARG(ctx, guide->scale && guide->negative_offsets, "scale and negative_offsets are required");
+    const uint32_t R = pk.R;
+    int32_t rc = wrk_guide_pack(ctx, guide->scale, R, V, pk.scale);
+    if (rc == WRK_OK) rc = queue_csr_check(ctx, guide->negative_offsets, R, "negative_offsets");
+    if (rc != WRK_OK) return rc;
+    WRK_ARG(ctx, guide->negative_tokens || guide->negative_offsets[R] == 0, "negative_offsets name %u tokens, negative_tokens is NULL",
+            guide->negative_offsets[R]);
+    const uint32_t base = (uint32_t)pk.pool.size();
+    for (uint32_t i = 0; i < guide->negative_offsets[R]; ++i) {
+        WRK_ARG(ctx, guide->negative_tokens[i] < V, "negative token %u: id %u >= vocab %u", i, guide->negative_tokens[i], V);
+        pk.pool.push_back(guide->negative_tokens[i]);
+    }
+    for (uint32_t r = 0; r < R; ++r) {
+        pk.neg_off.push_back(base + guide->negative_offsets[r]);
+        pk.neg_len.push_back(guide->negative_offsets[r + 1] - guide->negative_offsets[r]);
+        WRK_ARG(ctx, pk.neg_len[r] != 0 || pk.scale[r] == 1.0f, "request %u: an empty negative prompt with guidance scale %g (only 1 runs without a partner)",
+                r, (double)pk.scale[r]);
+    }
+    if (const wrk_buf* ns = guide->negative_init_state) {
+        const size_t need = (size_t)st->num_layer * (st->head_size + 2) * st->num_emb * 4;
+        WRK_ARG(ctx, ns->ctx == ctx, "negative_init_state belongs to another context");
+        WRK_ARG(ctx, ns->bytes == need, "negative_init_state holds %zu bytes, a sequence's state is %zu", ns->bytes, need);
+        WRK_ARG(ctx, !opt->init_state || (ns != opt->init_state && ns->ptr != opt->init_state->ptr), "init_state and negative_init_state are one buffer");
+        pk.negative_init_state = (const float*)ns->ptr;
+    }
+    pk.kind.guided = true;
+    return WRK_OK;
+}
+
 static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) {
+    if (kind.guided) {
+        wrk_step_kind plain = kind;
+        plain.guided = false;
+        wrk::QueueBufs q = queue_bufs(f, plain);
+        q.neg_off = f.queue_guide.neg_off; q.neg_len = f.queue_guide.neg_len; q.scale_req = f.queue_guide.scale; q.scale = f.guide.par;
+        q.pair_started = f.queue_guide.pair_started;
+        return q;
+    }
     return wrk::QueueBufs{f.queue.slots, f.queue.reqs, f.queue.pool, f.queue.log, f.queue.ctl, f.queue.started,
                           kind.sampled() ? f.sample.par : nullptr, kind.penalized ? f.penalty.par : nullptr, kind.filtered() ? f.filter.par : nullptr,
                           kind.alt() ? f.alt.par : nullptr, kind.mirostat() ? f.queue.mu : nullptr,
@@ -631,7 +686,9 @@ static wrk::QueueStateBufs queue_state_bufs(const wrk_frame_common& f, wrk_step_
 static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_pack& pk) {
     const wrk_step_kind kind = pk.kind;
     wrk_pick_params& rows = pk.rows;
-    pk.first_tokens.assign(B, pk.pool[0]);
+    const uint32_t FB = kind.guided ? 2 * B : B;        // a guided queue: B pairs, the rows below B wide, the records and tokens 2B
+    pk.first_tokens.assign(FB, pk.pool[0]);
+    if (kind.guided) rows.guide.assign(B, 1.0f);
     if (kind.sampled()) rows.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
     if (kind.filtered()) rows.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
     if (kind.alt()) rows.alt.assign(B, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
@@ -643,7 +700,7 @@ static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_
         rows.dry[b].ring = pk.window->ring + (size_t)b * pk.window->capacity;
         rows.dry[b].meta = pk.window->meta + (size_t)b * 2;
     }
-    pk.slots.assign(B, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
+    pk.slots.assign(FB, wrk::QueueSlot{0u, 0u, 0u, wrk::QUEUE_IDLE});
     pk.log.assign(pk.R, wrk::QueueLog{0u, 0u, 0u, 0u});
     if (kind.stop_seqs) pk.tails.assign((size_t)B * WRK_STOP_TAIL_LEN, WRK_STOP_TAIL_EMPTY);
     if (kind.intake) pk.take.assign(B, 0u);
@@ -655,6 +712,19 @@ static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_
                            at(rows.alt), kind.mirostat() ? pk.mu.data() : nullptr, at(rows.gram_state), at(pk.gram), at(rows.dry), at(pk.dry),
                            at(pk.seq.rows), at(pk.tails), nullptr, at(pk.from), at(pk.take), at(rows.bias_set), at(pk.bias)};
     const wrk::QueueStateBufs P{pk.start.data(), pk.save.data(), nullptr, pk.turn.data(), kind.history};
+    if (kind.guided) {
+        // the guided rule over the same mirrors: a half's start flag is raised when it feeds its first token at step 0, the others wait
+        wrk::QueueBufs G = Q;
+        G.neg_off = pk.neg_off.data(); G.neg_len = pk.neg_len.data(); G.scale_req = pk.scale.data(); G.scale = rows.guide.data();
+        pk.started.assign(FB, 0u);
+        pk.pair_started.assign(B, 0u);
+        for (uint32_t b = 0; b < pk.nstart; ++b) {
+            const wrk::QueuePairStart ps = wrk::queue_dispatch_guided(G, pk.first_tokens.data(), b, b, B, 0u);
+            if (ps.wipe) pk.wipe = b + 1;
+            pk.started[b] = ps.start_cond; pk.started[B + b] = ps.start_part; pk.pair_started[b] = 1u;
+        }
+        return;
+    }
     for (uint32_t b = 0; b < pk.nstart; ++b)
         if (wrk::queue_dispatch(Q, pk.first_tokens.data(), b, b, 0u, kind.pool() ? &P : nullptr, b)) pk.wipe = b + 1;
 }
@@ -679,22 +749,31 @@ static int32_t enqueue_prompt_intake(wrk_frame_common& f, uint32_t B, wrk_step_k
 // after wrk_decode_prepare, which uploaded the slots' tokens and rows of step 0, and before the step program is looked up (growing the
 // buffers drops the programs): the queue's buffers grown, the tables and what wrk_queue_start left for the slots uploaded, live = R;
 // then queue_reset of the slots that start at step 0 on the submission stream (with a pool: queue_turnover on the list of those slots)
-static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t B, const wrk_queue_pack& pk) {
+// A guided queue: FB = 2B sequences of the lane -- the slot records and start flags are FB wide, everything else B -- and
+// queue_reset_guided resets the halves that start at step 0
+static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t FB, const wrk_queue_pack& pk) {
     wrk_ctx* ctx = f.ctx;
     const uint32_t V = f.facts().num_vocab;
+    const wrk_step_kind kind = pk.kind;
+    const uint32_t B = kind.guided ? FB / 2 : FB;
     // never smaller than before: a later, smaller queue reuses the buffers and the program
-    int32_t rc = f.grow(f.queue, {B, pk.R, pk.pool.size()});
+    int32_t rc = f.grow(f.queue, {FB, pk.R, pk.pool.size()});
     if (rc == WRK_OK && pk.kind.pool()) rc = f.grow(f.queue_states, {B});
     if (rc == WRK_OK && pk.kind.stop_seqs) rc = f.grow(f.queue_seq, {B});
     if (rc == WRK_OK && pk.kind.intake) rc = f.grow(f.queue_intake, {B});
+    if (rc == WRK_OK && kind.guided) rc = f.grow(f.queue_guide, {B, pk.R});
     if (rc != WRK_OK) return rc;
-    const wrk_step_kind kind = pk.kind;
-    std::vector<uint32_t> started(B, 0u);
+    std::vector<uint32_t> started(FB, 0u);
     for (uint32_t b = 0; b < pk.nstart; ++b) started[b] = 1u;
-    const wrk::QueueCtl ctl{pk.nstart, pk.R, pk.R, 0u, pk.init_state};
+    if (kind.guided) started = pk.started;
+    const wrk::QueueCtl ctl{pk.nstart, pk.R, pk.R, 0u, pk.init_state, pk.negative_init_state};
     wrk_upload up{ctx};
-    up(f.queue.slots, pk.slots.data(), B)(f.queue.started, started.data(), B)(f.queue.log, pk.log.data(), pk.R)(f.queue.reqs, pk.reqs.data(), pk.R);
+    up(f.queue.slots, pk.slots.data(), FB)(f.queue.started, started.data(), FB)(f.queue.log, pk.log.data(), pk.R)(f.queue.reqs, pk.reqs.data(), pk.R);
     up(f.queue.pool, pk.pool.data(), pk.pool.size())(f.queue.ctl, &ctl, 1);
+    if (kind.guided) {
+        up(f.queue_guide.pair_started, pk.pair_started.data(), B)(f.queue_guide.neg_off, pk.neg_off.data(), pk.R);
+        up(f.queue_guide.neg_len, pk.neg_len.data(), pk.R)(f.queue_guide.scale, pk.scale.data(), pk.R);
+    }
     if (kind.mirostat()) up(f.queue.mu, pk.mu.data(), pk.R);
     if (kind.constrained) up(f.queue.gram, pk.gram.data(), pk.R);
     if (kind.biased) up(f.queue.bias, pk.bias.data(), pk.R);
@@ -715,6 +794,7 @@ static int32_t wrk_queue_prepare(wrk_frame_common& f, const wrk_v7_state* st, ui
     if (up.rc != WRK_OK) return up.rc;
     // the slots that start a request at step 0 are reset as the step that ends a request resets its slot
     if (pk.kind.pool()) wrk::queue_turnover(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), queue_state_bufs(f, kind), B, ctx->num_cu);
+    else if (kind.guided) wrk::queue_reset_guided(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), B, ctx->num_cu);
     else wrk::queue_reset(ctx->stream, queue_geom(st, 0, V), queue_bufs(f, pk.kind), B, ctx->num_cu);
     // and takes its intake as a step's tail does: the first tokens are in io.tokens (wrk_decode_prepare)
     const int32_t irc = enqueue_prompt_intake(f, B, pk.kind, ctx->stream);
@@ -777,21 +857,34 @@ static int32_t enqueue_draw_updates(wrk_frame_common& f, uint32_t B, wrk_step_ki
     return rc == WRK_OK ? enqueue_window_push(f, B, kind) : rc;
 }
 
+// a guided step, behind the draw updates of its R conditional sequences and in front of the advance: the partners take the same tokens
+static void enqueue_guide_follow(wrk_frame_common& f, uint32_t R, wrk_step_kind kind) {
+    if (kind.guided) wrk::guide_follow(f.ctx->op_stream(), f.io().argmax, R);
+}
+
 // tail of a queue program's step, after io.argmax holds the drawn tokens: the occurrence update of the slots whose draw is a reply
 // token (penalised), advance_queue, queue_reset of slots [b0, b0 + B) of `st`; with a pool advance_queue_pool and queue_turnover,
-// launch for launch
+// launch for launch; a guided queue (B pairs): guide_follow, advance_queue_guided, queue_reset_guided over 2B slots
 static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0) {
     hipStream_t q = f.ctx->op_stream();
     const wrk::FrameIo& io = f.io();
     const uint32_t V = f.facts().num_vocab;
-    if (!f.queue.holds({B}) || b0 != 0 || B > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+    const uint32_t FB = kind.guided ? 2 * B : B;        // a guided queue: B pairs of slots
+    if (!f.queue.holds({FB}) || b0 != 0 || FB > st->num_batch) return wrk_fail(f.ctx, WRK_E_ARG, "queue buffers are not prepared");
+    if (kind.guided && (kind.pool() || B > 128 || !f.queue_guide.holds({B}) || !f.guide.holds({B})))
+        return wrk_fail(f.ctx, WRK_E_ARG, "guided queue buffers are not prepared");
     if (kind.stop_seqs && !f.queue_seq.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "stop-sequence buffers are not prepared");
     if (kind.pool() && (!f.queue_states.holds({B}) || ((size_t)(st->head_size + 2) * st->num_emb) % 4 != 0))
         return wrk_fail(f.ctx, WRK_E_ARG, "state pool buffers are not prepared");
     const int32_t rc = enqueue_draw_updates(f, B, kind);
     if (rc != WRK_OK) return rc;
     const wrk::QueueBufs bufs = queue_bufs(f, kind);
-    if (kind.pool()) {
+    if (kind.guided) {
+        // the partners take the conditional halves' draws, then the pairs advance and the halves that start are reset
+        enqueue_guide_follow(f, B, kind);
+        wrk::advance_queue_guided(q, io.argmax, io.tokens, f.history.tokens, io.counter, bufs, B);
+        wrk::queue_reset_guided(q, queue_geom(st, b0, V), bufs, B, f.ctx->num_cu);
+    } else if (kind.pool()) {
         wrk::advance_queue_pool(q, io.argmax, io.tokens, f.history.tokens, io.counter, bufs, queue_state_bufs(f, kind), B);
         wrk::queue_turnover(q, queue_geom(st, b0, V), bufs, queue_state_bufs(f, kind), B, f.ctx->num_cu);
     } else {
@@ -802,15 +895,17 @@ static int32_t enqueue_queue_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind
 }
 
 // after the loop: the log and the history rows (with log-probs: their rows too) come back and the replies are cut out of them
+// A guided queue: the history rows are 2B wide and the replies are in columns [0, B); the log-prob rows are B wide
 static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_run, const wrk_queue_pack& pk, const wrk_queue_options* opt,
                                 wrk_queue_result* out) {
     wrk_ctx* ctx = f.ctx;
+    const size_t HB = pk.kind.guided ? (size_t)2 * B : B;
     std::vector<wrk::QueueLog> log(pk.R);
-    std::vector<uint32_t> hist((size_t)steps_run * B);
+    std::vector<uint32_t> hist((size_t)steps_run * HB);
     WRK_HIP(ctx, hipMemcpyAsync(log.data(), f.queue.log, (size_t)pk.R * sizeof(wrk::QueueLog), hipMemcpyDeviceToHost, ctx->stream));
     if (!hist.empty()) WRK_HIP(ctx, hipMemcpyAsync(hist.data(), f.history.tokens, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     const size_t nt = pk.lp.num_top;
-    std::vector<float> lp_rows(pk.lp.on() ? hist.size() : 0), top_lp(lp_rows.size() * nt);
+    std::vector<float> lp_rows(pk.lp.on() ? (size_t)steps_run * B : 0), top_lp(lp_rows.size() * nt);
     std::vector<uint32_t> top_id(top_lp.size());
     if (!lp_rows.empty()) WRK_HIP(ctx, hipMemcpyAsync(lp_rows.data(), f.logprob.logprob, lp_rows.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (!top_lp.empty()) {
@@ -851,8 +946,8 @@ static int32_t wrk_queue_finish(wrk_frame_common& f, uint32_t B, uint32_t steps_
         // the step that gave the request reason 1 or 2 also wrote its state to its entry (queue_turnover)
         if (pk.saved_out) pk.saved_out[r] = pk.save[r] != wrk::QUEUE_NO_ENTRY && (g.reason == 1 || g.reason == 2);
         for (uint32_t j = 0; j < g.length; ++j) {
-            const size_t row = ((size_t)g.start_step + q.prompt_len - 1 + j) * B + g.slot;
-            out->out_tokens[o + j] = hist[row];
+            const size_t at = (size_t)g.start_step + q.prompt_len - 1 + j, row = at * B + g.slot;
+            out->out_tokens[o + j] = hist[at * HB + g.slot];
             if (!pk.lp.on()) continue;
             pk.lp.logprob[o + j] = lp_rows[row];
             for (size_t t = 0; t < nt; ++t) { pk.lp.top_ids[(o + j) * nt + t] = top_id[row * nt + t]; pk.lp.top_logprobs[(o + j) * nt + t] = top_lp[row * nt + t]; }
@@ -871,11 +966,6 @@ static wrk::StopGeom stop_geom(wrk_frame_common& f, const wrk_v7_state* st, uint
     g.layers = st->num_layer; g.num_batch = st->num_batch; g.b0 = b0; g.v = f.facts().num_vocab;
     g.slot = (size_t)(st->head_size + 2) * st->num_emb;
     return g;
-}
-
-// a guided step, behind the draw updates of its R conditional sequences and in front of the advance: the partners take the same tokens
-static void enqueue_guide_follow(wrk_frame_common& f, uint32_t R, wrk_step_kind kind) {
-    if (kind.guided) wrk::guide_follow(f.ctx->op_stream(), f.io().argmax, R);
 }
 
 // tail of a stop program's step, after io.argmax holds the drawn tokens: the occurrence update of the sequences still running
@@ -963,7 +1053,7 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t frame_b, wrk_step_kind ki
     // guidance in front of the bias: the guided rows of head_o's pairs (r, B + r) are what the rest reads; log-probs, last_logits and the
     // stop snapshot keep head_o
     if (kind.guided) {
-        if (!f.guide.holds({B, V}) || argmax_done || frame_b != 2 * B || b0 != 0 || kind.queue() || kind.tail == wrk_step_kind::BEAM)
+        if (!f.guide.holds({B, V}) || argmax_done || frame_b != 2 * B || b0 != 0 || kind.pool() || kind.tail == wrk_step_kind::BEAM)
             return wrk_fail(f.ctx, WRK_E_ARG, "guidance rows are not prepared");
         wrk::guide_rows(q, io.head_o, V, V, B, f.guide.par, f.guide.out, V);
         logits = f.guide.out;
@@ -1294,27 +1384,29 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
 
 int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                            const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail,
-                           const wrk_queue_pool* pool) {
+                           const wrk_queue_pool* pool, const wrk_queue_guidance* guide, bool guided) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
     wrk_queue_pack pk;
-    int32_t rc = wrk_queue_check(ctx, opt, st, B, m->facts().num_vocab, mode_arg, out_arg ? &out : nullptr, pk);
+    int32_t rc = wrk_queue_check(ctx, opt, st, B, m->facts().num_vocab, mode_arg, out_arg ? &out : nullptr, pk, guided);
     if (rc == WRK_OK && tail != wrk_step_kind::QUEUE_POOL && opt->history) rc = wrk_fail(ctx, WRK_E_ARG, "a history pool without a state pool");
     if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, m->facts().num_vocab, pk);
+    if (rc == WRK_OK && guided) rc = wrk_queue_guide_check(ctx, guide, opt, st, m->facts().num_vocab, pk);
     if (rc != WRK_OK) return rc;
     wrk_queue_start(opt, B, pk);
-    rc = wrk_generate_check(ctx, st, m->facts(), pk.first_tokens.data(), B);
+    const uint32_t FB = pk.kind.guided ? 2 * B : B;         // the sequences of the frame: a guided queue runs B pairs
+    rc = wrk_generate_check(ctx, st, m->facts(), pk.first_tokens.data(), FB);
     if (rc != WRK_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     const uint32_t mode = mode_arg & 0xffu;
     m->before_loop();
-    std::vector<wrk_lane> L{{nullptr, 0, B, nullptr}};      // one lane: a queue shared by several streams would need cross-stream atomics
+    std::vector<wrk_lane> L{{nullptr, 0, FB, nullptr}};     // one lane: a queue shared by several streams would need cross-stream atomics
     rc = m->lane(0, 1, &L[0].frame);
     if (rc == WRK_OK) rc = lane_prepare(L[0], st, pk.first_tokens.data(), pk.max_steps, mode, pk.kind, pk.rows, nullptr, nullptr, &pk, pk.lp.num_top);
     if (rc != WRK_OK) return rc;
     uint32_t steps_run = 0;
-    rc = wrk_run_lanes(ctx, L, st, B, pk.max_steps, mode, pk.kind, nullptr, nullptr, elapsed_ms, wrk_stop_run{pk.poll_steps, nullptr, &steps_run}, wrk_logprob_call{});
+    rc = wrk_run_lanes(ctx, L, st, FB, pk.max_steps, mode, pk.kind, nullptr, nullptr, elapsed_ms, wrk_stop_run{pk.poll_steps, nullptr, &steps_run}, wrk_logprob_call{});
     if (rc == WRK_OK) rc = m->after_loop(1);
     if (rc != WRK_OK) return rc;
     return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);

@@ -116,6 +116,11 @@ class QueuePool(C.Structure):
     _fields_ = [("states", _P), ("num_entries", C.c_uint32), ("start", _u32p), ("save", _u32p), ("saved", _u32p)]
 
 
+class QueueGuidance(C.Structure):
+    """wrk_queue_guidance: the scales [R], the CSR negative prompts and the partners' shared prefix state of wrk_v*_generate_queue_guided."""
+    _fields_ = [("scale", _f32p), ("negative_tokens", _u32p), ("negative_offsets", _u32p), ("negative_init_state", _P)]
+
+
 class BeamOptions(C.Structure):
     """wrk_beam_options: num_beams, length_penalty and the GenerateOptions a beam call shares (stop sets, bias, poll_steps)."""
     _fields_ = [("num_beams", C.c_uint32), ("length_penalty", C.c_float), ("gen", C.POINTER(GenerateOptions))]
@@ -279,6 +284,10 @@ HIP_SYMBOLS = {
                                                C.POINTER(QueuePool)]),
     "wrk_v6_generate_queue_pool": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
                                                C.POINTER(QueuePool)]),
+    "wrk_v7_generate_queue_guided": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
+                                                 C.POINTER(QueueGuidance)]),
+    "wrk_v6_generate_queue_guided": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
+                                                 C.POINTER(QueueGuidance)]),
     "wrk_v7_generate_beam": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(BeamOptions), C.POINTER(BeamResult), _f32p,
                                          C.c_uint32]),
     "wrk_v6_generate_beam": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(BeamOptions), C.POINTER(BeamResult), _f32p,
@@ -1963,7 +1972,39 @@ class Runtime:
         request r's rows are biased with set bias_set[r] from the step it is dispatched, whatever its slot's previous request used, so
         two requests of one call may ban different tokens.  The bias is not part of a pool entry.
         guidance_scale: the queue's guidance_scale field; guidance is not built for the queue: anything but None is
-        refused with WRK_E_UNSUPPORTED.  Guided sequences go through `generate_guided`."""
+        refused with WRK_E_UNSUPPORTED.  Guided requests go through `generate_queue_guided`, guided sequences through `generate_guided`."""
+        args = dict(locals())
+        del args["self"]
+        return self._queue(None, **args)
+
+    def generate_queue_guided(self, requests, negative_prompts, guidance_scale, negative_init_state: "Buffer" = None, stop=None, max_new=16,
+                              temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None, presence=0.0, frequency=0.0,
+                              decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0, mode: int = 1, top_k=None,
+                              min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None,
+                              grammar_state=None, stop_sequences=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None,
+                              dry_breakers=None, count_prompt=None, logit_bias: "LogitBias" = None, bias_set=None, num_slots=None):
+        """`generate_queue` with classifier-free guidance per request: request r brings the negative prompt
+        negative_prompts[r] (None or []: none, an unguided request, only with scale 1) and guidance_scale[r] (a scalar or one value per
+        request, finite and >= 0).  The queue has B = num_slots request slots (None: half the state's slots), each a pair of state
+        slots: b runs the request and B + b its partner, which takes the negative prompt in at decode rate beside it, both prompts
+        ending in the same step; a half that starts late is reset on the device directly in front of its first token (to zeros, or to
+        `init_state` / `negative_init_state`, shared prefix states from `state_read`).  Every reply token is picked on
+        `Context.guide_logits` of the pair's two head rows with the request's scale, in front of the bias, the penalties, DRY and the
+        grammar; log-probs stay on the raw conditional rows.  A refilled pair takes the next request's negative prompt the same way.
+        Every other argument, the return value and the `last_*` attributes: as `generate_queue` without a pool; occurrence rows,
+        windows and count_prompt see the conditional prompt only.  max_steps defaults to the sum over the requests of the longer of the
+        two prompts plus max_new."""
+        args = dict(locals())
+        for name in ("self", "negative_prompts", "guidance_scale", "negative_init_state", "num_slots"):
+            del args[name]
+        return self._queue((negative_prompts, guidance_scale, negative_init_state, num_slots), pool=None, start_state=None, save_state=None,
+                           history=None, guidance_scale=None, **args)
+
+    def _queue(self, guide, requests, stop, max_new, temperature, top_p, seed, occurrence, presence, frequency, decay, init_state, max_steps,
+               poll_steps, mode, top_k, min_p, pool, start_state, save_state, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
+               stop_sequences, window, dry, no_repeat_ngram, dry_breakers, count_prompt, history, logit_bias, bias_set, guidance_scale):
+        """wrk_v*_generate_queue / _queue_pool / _queue_guided on the arguments of `generate_queue`; guide: None, or (negative_prompts,
+        guidance_scale, negative_init_state, num_slots) of `generate_queue_guided`."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -1997,6 +2038,19 @@ class Runtime:
             opt.history = history.h
         opt.poll_steps = poll_steps
         opt.max_steps = int(poff[-1]) + int(mn.sum()) if max_steps is None else max_steps
+        if guide is not None:
+            negs, scale, neg_init, num_slots = guide
+            if len(negs) != R:
+                raise ValueError(f"{len(negs)} negative prompts for {R} requests")
+            negs = [np.asarray([] if x is None else x, np.int64).reshape(-1) for x in negs]
+            noff = np.zeros(R + 1, np.uint32)
+            noff[1:] = np.cumsum([x.size for x in negs])
+            ntok = _u32(np.concatenate(negs) if noff[-1] else [0])
+            sc = _per_row(scale, R, np.float32) if R else np.ones(1, np.float32)
+            qg = QueueGuidance(_ptr(sc, _f32p), _ptr(ntok, _u32p), _ptr(noff, _u32p), neg_init.h if neg_init is not None else None)
+            B = self.num_batch // 2 if num_slots is None else int(num_slots)
+            if max_steps is None:       # a pair is busy for max(n, m) - 1 + reply steps
+                opt.max_steps = int(sum(max(p.size, q.size) for p, q in zip(prompts, negs))) + int(mn.sum())
         lengths, reasons, slots, starts = (np.zeros(max(R, 1), np.uint32) for _ in range(4))
         out = np.zeros(max(int(mn.sum()), 1), np.uint32)
         run, ms = C.c_uint32(), C.c_float()
@@ -2006,7 +2060,11 @@ class Runtime:
         if logprobs is not None:
             lp, top_ids, tlp = _logprob_arrays(logprobs, int(mn.sum()))     # `ids` stays alive: opt.stop_tokens points into it
             opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(top_ids, _u32p), _ptr(tlp, _f32p)
-        if pool is None:
+        if guide is not None:
+            fn, mdl = self._entry("generate_queue_guided")
+            self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qg)))
+            self.last_queue_saved = None
+        elif pool is None:
             if start_state is not None or save_state is not None:
                 raise ValueError("start_state / save_state need a pool")
             fn, mdl = self._entry("generate_queue")
