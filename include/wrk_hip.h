@@ -362,6 +362,28 @@ int32_t wrk_sample_logits_mirostat(wrk_ctx* ctx, const wrk_buf* logits, uint32_t
 int32_t wrk_sample_logits_typical(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
                                   const float* temperature, const float* top_p, const float* typical_p, const uint32_t* seed,
                                   uint32_t step, uint32_t* out_tokens);
+/* wrk_sample_logits_filtered with four more cuts per row: top-n-sigma (Tang et al. 2024; llama.cpp top_n_sigma), the epsilon and eta
+ * cut-offs (Hewitt et al. 2022; Hugging Face EpsilonLogitsWarper / EtaLogitsWarper) and XTC, "exclude top choices" (koboldcpp,
+ * text-generation-webui, llama.cpp).  p is the whole row's softmax at temperature 1, never renormalised after another cut (llama.cpp
+ * renormalises over the survivors before XTC).  In wrk_sample_logits' order the candidates are the ranks [m0, n).
+ *   n = min(n_P, n_K, n_M, n_S, n_E, n_H), each of the last three a prefix with rank 0 always in:
+ *     n_S = #{l >= max - top_n_sigma * sigma}, sigma the population standard deviation of the row's finite logits (fewer than two, or
+ *           a +inf in the row: 0 -- the ties of the maximum stay); top_n_sigma <= 0: off, +inf counts as the largest finite f32;
+ *     n_E = #{p >= epsilon_cutoff}; 0: off;
+ *     n_H = #{p >= min(eta_cutoff, sqrt(eta_cutoff) * exp(-H))}, H the row's entropy in nats (a -inf logit adds 0); 0: off.
+ *   XTC: m = #{p >= xtc_threshold}, m' = min(m, n); the row's coin c is the second output of the SplitMix64 stream whose first gives u,
+ *     c = (SplitMix64 state (seed << 32 | step) advanced twice) >> 40, times 2^-24.  m' >= 2 and c < xtc_probability: m0 = m' - 1 -- every
+ *     candidate at or above the threshold goes except the least likely of them; else m0 = 0.  xtc_probability == 0 or xtc_threshold >
+ *     0.5: off.  [m0, n) is never empty.
+ * Weights p^(1/T) inside the candidates, the draw as wrk_sample_logits'.  temperature == 0, top_p == 0, top_k == 1 and an all -inf row
+ * are the greedy branch: no cut applies, no coin is drawn.  The thresholds are compared as f32 bounds on l - max, their logarithms
+ * taken in f64 on the host and rounded once.  Every array is host f32 [num_rows] and may be NULL (off), xtc_probability and
+ * xtc_threshold both or neither; WRK_E_ARG before any launch: a NaN or negative value, an epsilon_cutoff, eta_cutoff, xtc_probability
+ * or xtc_threshold outside [0, 1].  With all five off every token equals wrk_sample_logits_filtered's, bit for bit.  Blocking. */
+int32_t wrk_sample_logits_cut(wrk_ctx* ctx, const wrk_buf* logits, uint32_t num_vocab, uint32_t row_stride, uint32_t num_rows,
+                              const float* temperature, const float* top_p, const uint32_t* top_k, const float* min_p,
+                              const float* top_n_sigma, const float* epsilon_cutoff, const float* eta_cutoff, const float* xtc_probability,
+                              const float* xtc_threshold, const uint32_t* seed, uint32_t step, uint32_t* out_tokens);
 
 /* Sequence scoring on the device, per row of f32 logits [num_rows][row_stride] (first num_vocab used) and its target token t:
  *   logprob = x_t - (m + log sum_i exp(x_i - m)), m = the row max;   rank = #{i : x_i > x_t} + #{i < t : x_i == x_t}
@@ -653,7 +675,16 @@ int32_t wrk_dry_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, uint32
  * 8-15 > 1), in wrk_v7_generate_queue (wrk_queue_options' guidance_scale) and in wrk_v7_generate_beam (either field in `gen`).  The
  * scales are device data: one cached step program serves any of them; guided calls replay step programs of their own, a call with
  * guidance_scale NULL exactly the programs it ran before.  The two fields sit directly behind `bias_set` (the bias fields stay directly
- * behind `occ`, where callers and the binding checks know them): every field behind them keeps its order. */
+ * behind `occ`, where callers and the binding checks know them): every field behind them keeps its order.
+ * XTC, top-n-sigma and the eta / epsilon cut-offs.  top_n_sigma / epsilon_cutoff / eta_cutoff / xtc_probability / xtc_threshold (host f32
+ * [num_batch], any may be NULL: off; the two XTC arrays both or neither) make the pick wrk_sample_logits_cut's with sequence b's values
+ * and its top_k / min_p; the row's coin is a pure function of (seed[b], step), so nothing moves from draw to draw and nothing is
+ * returned.  They need the sampler arrays and share the filtered family: together with mirostat_* or typical_p they are WRK_E_ARG, as
+ * are the values wrk_sample_logits_cut rejects; num_vocab > 2^20 is WRK_E_UNSUPPORTED.  The cuts act on the row after guidance, bias,
+ * penalties, DRY and the grammar mask; log-probs and last_logits stay on the raw head output.  The values are device data: one cached
+ * step program serves any of them; cut calls replay step programs of their own, a call with all five NULL exactly the programs it ran
+ * before.  Tokens do not depend on the number of lanes.  wrk_v7_generate_beam refuses them as it refuses every sampler.  The five
+ * fields sit between poll_steps and num_top: every field behind them keeps its order, the filter fields last. */
 #define WRK_MAX_STOP_TOKENS 16
 #define WRK_MAX_STOP_SEQUENCES 8
 #define WRK_MAX_STOP_SEQUENCE_LEN 8
@@ -672,6 +703,7 @@ typedef struct wrk_generate_options {
     const uint32_t *guidance_first_tokens;
     const uint32_t *stop_tokens, *stop_offsets;
     uint32_t poll_steps;
+    const float *top_n_sigma, *epsilon_cutoff, *eta_cutoff, *xtc_probability, *xtc_threshold;
     uint32_t num_top;
     float *out_logprob;
     uint32_t *out_top_ids;
@@ -935,6 +967,25 @@ typedef struct wrk_queue_guidance {
 int32_t wrk_v7_generate_queue_guided(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
                                      const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_guidance* guide);
 
+/* The cuts of wrk_sample_logits_cut in the request queue.  wrk_queue_options keeps its fields, so the five arrays travel beside it, as the
+ * guidance does: top_n_sigma / epsilon_cutoff / eta_cutoff / xtc_probability / xtc_threshold (host f32 [num_requests], any may be NULL:
+ * off; the two XTC arrays both or neither), validated as in wrk_generate_options.  Request r's reply draws are wrk_sample_logits_cut's
+ * with its own values and its top_k / min_p; the values are written into the slot's row by the dispatch, at step 0 on the host and at a
+ * refill on the device, and the coin of reply token j is a pure function of (seed[r], j): a reply does not depend on the slot or the
+ * step the request was scheduled at, and a slot in its prompt phase draws no coin that matters.  `pool` non-NULL: the call is
+ * wrk_v7_generate_queue_pool's with that pool; `guide` non-NULL: wrk_v7_generate_queue_guided's with that guidance; both NULL:
+ * wrk_v7_generate_queue's; both set: WRK_E_ARG (no entry point takes both).  Everything else -- arguments, results, errors -- is the
+ * selected call's.  WRK_E_ARG before any launch, besides that call's: a NULL `cuts`, the cuts without the sampler arrays or together
+ * with mirostat_* or typical_p, the values wrk_sample_logits_cut rejects.  With all five arrays NULL the call replays exactly the
+ * programs of the selected call. */
+typedef struct wrk_queue_cuts {
+    const float *top_n_sigma, *epsilon_cutoff, *eta_cutoff, *xtc_probability, *xtc_threshold;
+    const wrk_queue_pool *pool;
+    const wrk_queue_guidance *guide;
+} wrk_queue_cuts;
+int32_t wrk_v7_generate_queue_cut(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
+                                  const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_cuts* cuts);
+
 /* Beam search in the decode loops (Hugging Face's num_beams, vLLM's beam_search): the search over continuations that the other loops do
  * not make.  A hypothesis of an RWKV model is one fixed-size state slot, so a beam step is the batched step, a selection over at most
  * W * W + W candidates per group, and a device-to-device permutation of state slots -- all inside the captured step program.
@@ -1090,6 +1141,9 @@ int32_t wrk_v6_generate_queue_pool(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_sta
 /* as wrk_v7_generate_queue_guided */
 int32_t wrk_v6_generate_queue_guided(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
                                      const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_guidance* guide);
+/* as wrk_v7_generate_queue_cut */
+int32_t wrk_v6_generate_queue_cut(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, uint32_t num_batch, const wrk_queue_options* opt,
+                                  const wrk_queue_result* out, float* elapsed_ms_or_null, uint32_t mode, const wrk_queue_cuts* cuts);
 /* as wrk_v7_generate_beam */
 int32_t wrk_v6_generate_beam(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
                              uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null, uint32_t mode);

@@ -21,6 +21,10 @@ A seventh pair of legs (--mirostat TAU,ETA and / or --typical P): the decode loo
  against the plain sampler loop of the same run -- all through the options entry point without stop sets, so the step
 programs differ by the sampler launch alone -- alternating, with the run-to-run spread of each.  Every call starts from the same state.
 
+Cut legs (--xtc P,T, --top-n-sigma N, --eta E): generate_sample with each cut added to the filtered sampler's parameters
+(--top-k / --min-p, else top_k = 40 and min_p = 0.05, at the same top_p), and all given cuts together, alternating with that filtered
+step, medians and each leg's run-to-run spread: the step programs differ by the sampler kernel's instantiation alone.
+
 An eighth leg (--grammar): the decode loop constrained by a two-state automaton that allows about half of the vocabulary in either state
  against the same loop without a grammar -- both through the options entry point without stop sets, so the step programs
 differ by the mask launch and the advance launch alone -- for the greedy and the plain-sampler pick, alternating, with the run-to-run
@@ -272,6 +276,40 @@ def alt_leg(rt, first, args):
                      "ms_all": [round(x, 5) for x in per[name]], "distinct_tokens": distinct[name]}
         if name != "sample":
             res[name]["minus_sample_us"] = round((m - bm) * 1e3, 2)
+    return res
+
+
+def cut_leg(rt, first, args):
+    """Medians of the per-step time of generate_sample with the filtered sampler (--top-k / --min-p, else top_k = 40, min_p = 0.05) and
+    with each of --xtc P,T / --top-n-sigma N / --eta E added to it, and all of them together, alternating in one process."""
+    fkw = dict(temperature=args.temperature, top_p=args.top_p, top_k=40 if args.top_k is None else args.top_k,
+               min_p=0.05 if args.min_p is None else args.min_p)
+    legs = {"filtered": {}}
+    if args.xtc:
+        legs["xtc"] = dict(xtc=tuple(float(x) for x in args.xtc.split(",")))
+    if args.top_n_sigma is not None:
+        legs["top_n_sigma"] = dict(top_n_sigma=args.top_n_sigma)
+    if args.eta is not None:
+        legs["eta"] = dict(eta_cutoff=args.eta)
+    if len(legs) > 2:
+        legs["all"] = {k: v for name, kw in legs.items() for k, v in kw.items()}
+
+    def run(kw):
+        tok, ms = rt.generate_sample(first, args.steps, **fkw, **kw)
+        return tok, ms / args.steps
+    per = {name: [] for name in legs}
+    distinct = {name: len(np.unique(run(kw)[0])) for name, kw in legs.items()}       # capture and warm up
+    for _ in range(args.reps):
+        for name, kw in legs.items():
+            per[name].append(run(kw)[1])
+    bm = float(np.median(per["filtered"]))
+    res = {"filters": {k: fkw[k] for k in ("top_k", "min_p")}}
+    for name in legs:
+        m = float(np.median(per[name]))
+        res[name] = {"ms_per_step": round(m, 5), "spread_us": round((max(per[name]) - min(per[name])) * 1e3, 2),
+                     "ms_all": [round(x, 5) for x in per[name]], "distinct_tokens": distinct[name]}
+        if name != "filtered":
+            res[name]["minus_filtered_us"] = round((m - bm) * 1e3, 2)
     return res
 
 
@@ -534,6 +572,9 @@ def main():
     ap.add_argument("--logprobs", default=None, help="comma-separated numbers of alternatives, e.g. 0,5,20")
     ap.add_argument("--mirostat", default=None, help="TAU,ETA, e.g. 5,0.1")
     ap.add_argument("--typical", type=float, default=None, help="typical_p, e.g. 0.9")
+    ap.add_argument("--xtc", default=None, help="PROBABILITY,THRESHOLD, e.g. 0.5,0.1: the cut step against the filtered step")
+    ap.add_argument("--top-n-sigma", type=float, default=None, help="e.g. 1.0: the cut step against the filtered step")
+    ap.add_argument("--eta", type=float, default=None, help="eta_cutoff, e.g. 0.0003: the cut step against the filtered step")
     ap.add_argument("--grammar", action="store_true", help="the constrained loop against the same loop without a grammar")
     ap.add_argument("--stop-seq", action="store_true", help="the stop-sequence programs against the stop programs and the sampled step")
     ap.add_argument("--dry", action="store_true", help="the loop with a token window and DRY against the same loop without")
@@ -627,6 +668,10 @@ def main():
             out["batches"][-1]["logprobs"] = logprob_leg(rt, first, args)
         if args.mirostat or args.typical is not None:
             out["batches"][-1]["mirostat_typical"] = alt_leg(rt, first, args)
+        if args.xtc or args.top_n_sigma is not None or args.eta is not None:
+            out["cut_note"] = ("a cut step runs sample_rows_kernel<NPT, SAMPLE_CUT> in the place of the filtered kernel, the same launch count: "
+                               "XTC / eta add the moments pass, top-n-sigma the integer-moments pass, XTC (when its coin falls) the count / min-key pass")
+            out["batches"][-1]["cut"] = cut_leg(rt, first, args)
         if args.grammar:
             out["grammar_note"] = ("two states, four token classes (id mod 4), two classes allowed per state; a constrained step adds two "
                                    "launches to the step program: constrain_rows before the pick and grammar_advance in the tail")

@@ -203,9 +203,16 @@ struct RowGate { const uint32_t* flag; uint32_t stride, eq; };
 // bit, mu untouched, and the greedy branch leaves mu alone too.  The update is made iff the row's draw counts (gate).
 // SAMPLE_TYP: locally typical sampling -- candidates = the tokens, by |(max - l) - gbar| ascending (ties by index), whose preceding
 // softmax mass is <= typical_p (top_p is not read); typical_p >= 1: SAMPLE_PLAIN's token, bit for bit.  alt is only read
-enum : int { SAMPLE_PLAIN = 0, SAMPLE_FILT = 1, SAMPLE_MIRO = 2, SAMPLE_TYP = 3 };
-// which sampler, and its rows: par always, filt with SAMPLE_FILT, alt with SAMPLE_MIRO / SAMPLE_TYP, gate with SAMPLE_MIRO
-struct SamplePick { int mode; const SampleParam* par; const SampleFilter* filt; SampleAlt* alt; RowGate gate; };
+// SAMPLE_CUT: SAMPLE_FILT's candidates cut further, one SampleCut per row next to the SampleFilter.  The candidates are
+// ranks [m0, n): n = min(n_P, n_K, n_M, n_S, n_E, n_H), each new count a prefix with rank 0 always in -- n_S = #{max - l <= top_n_sigma *
+// sigma} (sigma: population deviation of the finite logits), n_E = #{p >= epsilon}, n_H = #{p >= min(eta, sqrt(eta) exp(-H))} -- and XTC:
+// with m' = min(#{p >= xtc_threshold}, n) >= 2 and the row's coin below xtc_probability, m0 = m' - 1, else 0.  p is the whole row's
+// softmax at temperature 1.  The coin is (SplitMix64's second output of the state that gives u) >> 40, times 2^-24:
+// sample_splitmix_next.  All five off: SAMPLE_FILT's token, bit for bit
+enum : int { SAMPLE_PLAIN = 0, SAMPLE_FILT = 1, SAMPLE_MIRO = 2, SAMPLE_TYP = 3, SAMPLE_CUT = 4 };
+// which sampler, and its rows: par always, filt with SAMPLE_FILT / SAMPLE_CUT, alt with SAMPLE_MIRO / SAMPLE_TYP, gate with SAMPLE_MIRO,
+// cut with SAMPLE_CUT
+struct SamplePick { int mode; const SampleParam* par; const SampleFilter* filt; SampleAlt* alt; RowGate gate; const SampleCut* cut = nullptr; };
 int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SamplePick& pick, const uint32_t* step,
                 uint32_t* out);
 
@@ -424,6 +431,13 @@ int32_t wrk_sample_pack(wrk_ctx* ctx, const float* temperature, const float* top
                         std::vector<wrk::SampleParam>& out);
 // validated per-sequence filter rows; either array may be NULL (off).  WRK_E_ARG on a min_p that is NaN or outside [0, 1]
 int32_t wrk_filter_pack(wrk_ctx* ctx, const uint32_t* top_k, const float* min_p, uint32_t n, std::vector<wrk::SampleFilter>& out);
+// the cut sampler's per-sequence arrays, any of which may be NULL (off), validated into rows.  WRK_E_ARG on a NaN or
+// negative value, on an epsilon_cutoff, eta_cutoff, xtc_probability or xtc_threshold outside [0, 1] and on one of the two XTC arrays alone
+struct wrk_cut_args {
+    const float *top_n_sigma = nullptr, *epsilon_cutoff = nullptr, *eta_cutoff = nullptr, *xtc_probability = nullptr, *xtc_threshold = nullptr;
+    bool any() const { return top_n_sigma || epsilon_cutoff || eta_cutoff || xtc_probability || xtc_threshold; }
+};
+int32_t wrk_cut_pack(wrk_ctx* ctx, const wrk_cut_args& a, uint32_t n, std::vector<wrk::SampleCut>& out);
 // validated per-sequence SampleAlt rows of a Mirostat call (tau required; eta NULL: 0; mu NULL: 2 tau) or of a typical call (typical_p).
 // WRK_E_ARG on NaN, negative or non-finite tau / eta, a non-finite mu, a typical_p that is NaN or outside [0, 1]
 int32_t wrk_mirostat_pack(wrk_ctx* ctx, const float* tau, const float* eta, const float* mu, uint32_t n, std::vector<wrk::SampleAlt>& out);

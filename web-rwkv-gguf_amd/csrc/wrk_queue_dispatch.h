@@ -19,6 +19,9 @@ namespace wrk {
 struct SampleParam { float temperature, top_p; uint32_t seed, step_base; };
 struct SampleFilter { uint32_t top_k; float ln_min_p; };
 struct SampleAlt { float tau, eta, mu, typical_p; };
+// the cut sampler's row next to SampleFilter, as wrk_cut_pack leaves it: logarithms taken once on the host in f64.
+// Off: top_n_sigma 0, ln_epsilon / ln_eta -inf, xtc_probability 0 (an xtc_threshold above 0.5 is stored as probability 0)
+struct SampleCut { float top_n_sigma, ln_epsilon, ln_eta, xtc_probability, ln_xtc_threshold; };
 struct PenaltyParam { float* count; uint8_t* flags; const float* weight; float presence, frequency, decay; uint32_t pad; };
 struct DryParam {
     uint32_t* ring; uint32_t* meta; uint32_t cap;
@@ -45,6 +48,7 @@ struct QueueReq {
     uint32_t stop_count, stop_ids[WRK_MAX_STOP_TOKENS];
     uint32_t top_k; float ln_min_p;     // the request's SampleFilter row (filtered queues)
     float tau, eta, typical_p;          // the request's SampleAlt row (Mirostat / typical queues); its mu: QueueBufs::alt_mu
+    float top_n_sigma, ln_epsilon, ln_eta, xtc_probability, ln_xtc_threshold;       // the request's SampleCut row (cut queues)
 };
 struct QueueSlot { uint32_t req, pos, reply, phase; };
 struct QueueLog { uint32_t length, reason, slot, start_step; };
@@ -79,6 +83,8 @@ struct QueueBufs {
     // pair by every launch, as started): the flag of the occurrence reset, which stays B wide
     const uint32_t *neg_off = nullptr, *neg_len = nullptr; const float* scale_req = nullptr; float* scale = nullptr;
     uint32_t* pair_started = nullptr;
+    // cut queues: the slots' SampleCut rows, next to filter_par
+    SampleCut* cut_par = nullptr;
 };
 // A state pool under the queue.  QueueTurn: one slot that ended in the step -- `save` the entry its state goes to,
 // `started` / `start` as started[slot] and the entry the slot's next request begins from; QUEUE_NO_ENTRY: none
@@ -94,7 +100,7 @@ struct QueueStateBufs {
 // THE dispatch rule: request r goes to slot b and its first prompt token p_0 is fed at step first_step.  The slot feeds p_0 .. p_{n-1}
 // on steps first_step .. first_step + n - 1 and the draw of the last of them is reply token 0, so the sampler's step base is
 // first_step + n - 1 and reply token j has sampler step j wherever and whenever the request runs.  Writes, through the arrays handed in
-// and nothing else: the slot record, p_0, the intake flag, the slot's sampler / filter / alt rows (mu from alt_mu[r]), its automaton
+// and nothing else: the slot record, p_0, the intake flag, the slot's sampler / filter / cut / alt rows (mu from alt_mu[r]), its automaton
 // state, its bias set word, the values and table of its DRY row, an empty stop tail, the three values of its penalty row, the request's log entry and,
 // with a pool, turn[turn_at] = {b, save, 1, start[r]}.  The slot's own pointers -- occurrence row, window ring / meta / cap -- are never
 // written.  Returns whether the caller is to set the slot's window to length 0 (the two words behind DryParam::meta): with a window,
@@ -105,6 +111,7 @@ WRK_HD inline bool queue_dispatch(const QueueBufs& Q, uint32_t* tokens, uint32_t
     tokens[b] = Q.pool[q->prompt_off];
     if (Q.sample_par) Q.sample_par[b] = SampleParam{q->temperature, q->top_p, q->seed, first_step + q->prompt_len - 1};
     if (Q.filter_par) Q.filter_par[b] = SampleFilter{q->top_k, q->ln_min_p};
+    if (Q.cut_par) Q.cut_par[b] = SampleCut{q->top_n_sigma, q->ln_epsilon, q->ln_eta, q->xtc_probability, q->ln_xtc_threshold};
     if (Q.alt_par) Q.alt_par[b] = SampleAlt{q->tau, q->eta, Q.alt_mu ? Q.alt_mu[r] : 0.0f, q->typical_p};
     if (Q.gram_req) Q.gram_state[b] = Q.gram_req[r];
     if (Q.bias_req) Q.bias_set[b] = Q.bias_req[r];

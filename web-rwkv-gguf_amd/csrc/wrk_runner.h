@@ -84,8 +84,9 @@ int32_t wrk_score_check(wrk_ctx* ctx, const wrk_job_args& a, uint32_t V, const c
 // A filtered pick is a sampled one and a pool tail is a queue tail by construction; wrk_pick_pack sets `penalized` only with a sampled pick
 struct wrk_step_kind {
     // arg-max / the sampler (wrk_sample.hip) on sample_par / the filtered sampler, also on filter_par / the Mirostat v2 sampler, also on
-    // alt_par, whose mu it carries from draw to draw / the typical sampler, also on alt_par
-    enum Pick : uint32_t { GREEDY, SAMPLED, FILTERED, MIROSTAT, TYPICAL };
+    // alt_par, whose mu it carries from draw to draw / the typical sampler, also on alt_par / the cut sampler, on filter_par
+    // and cut_par
+    enum Pick : uint32_t { GREEDY, SAMPLED, FILTERED, MIROSTAT, TYPICAL, CUT };
     // advance_tokens / wrk_stop.hip / wrk_queue.hip / the same with a state pool / beam search (wrk_beam.hip): no pick at all --
     // on head_o, or biased on bias.out, the candidate front and beam_select, then the slot permutation and the snapshot of the slots that ended
     enum Tail : uint32_t { PLAIN, STOP, QUEUE, QUEUE_POOL, BEAM };
@@ -117,13 +118,14 @@ struct wrk_step_kind {
     // With a QUEUE tail: R request slots, each a pair of state slots; advance_queue_guided / queue_reset_guided are the tail
     bool guided = false;
     bool sampled() const { return pick != GREEDY; }
-    bool filtered() const { return pick == FILTERED; }
+    bool filtered() const { return pick == FILTERED || pick == CUT; }     // the step has filter rows
+    bool cut() const { return pick == CUT; }
     bool mirostat() const { return pick == MIROSTAT; }
     bool alt() const { return pick == MIROSTAT || pick == TYPICAL; }
     bool queue() const { return tail == QUEUE || tail == QUEUE_POOL; }
     bool pool() const { return tail == QUEUE_POOL; }
     // The kind's bits of GraphKey::mode, the only place they are defined: pick 24-25 and, its third bit, 30 (the first three picks keep the
-    // keys they had with two bits), penalised 26, tail 27-28 (its third bit: key2()), log-probs 29, constrained 31 (the word is full) -- above every flag of an
+    // keys they had with two bits; CUT = 5 fits the three bits, so key() is as it was), penalised 26, tail 27-28 (its third bit: key2()), log-probs 29, constrained 31 (the word is full) -- above every flag of an
     // infer job and of a runner's own (wrk_frame_common::key_bits, all below bit 24, ORed into the same word)
     uint32_t key() const {
         return ((uint32_t)pick & 3u) << 24 | ((uint32_t)pick >> 2) << 30 | (uint32_t)penalized << 26 | ((uint32_t)tail & 3u) << 27 | (uint32_t)logprobs << 29 |
@@ -390,6 +392,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_rows_bufs<wrk::SampleParam>> sample;
     wrk_dev_group<wrk_rows_bufs<wrk::SampleFilter>> filter;
     wrk_dev_group<wrk_rows_bufs<wrk::SampleAlt>> alt;
+    wrk_dev_group<wrk_rows_bufs<wrk::SampleCut>> cut_par;      // the cut sampler's rows, next to `filter`
     wrk_dev_group<wrk_penalty_bufs> penalty;
     wrk_dev_group<wrk_grammar_bufs> grammar;
     wrk_dev_group<wrk_bias_bufs> bias;
@@ -406,7 +409,7 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_logprob_bufs> logprob;
     wrk_dev_group<wrk_beam_bufs> beam;
     template <class F> void each_group(F&& f) {     // the one list of the groups
-        f(history); f(sample); f(filter); f(alt); f(penalty); f(grammar); f(bias); f(guide); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
+        f(history); f(sample); f(filter); f(alt); f(cut_par); f(penalty); f(grammar); f(bias); f(guide); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
         f(queue_states); f(queue_intake); f(queue_guide); f(logprob); f(beam);
     }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
@@ -465,13 +468,22 @@ struct wrk_pick_args {
     const wrk_grammar* grammar = nullptr; uint32_t* grammar_state = nullptr;    // grammar set: a constrained pick; grammar_state: in / out
     wrk_dry_args dry;                                                   // window set: a DRY pick
     const wrk_logit_bias* bias = nullptr; const uint32_t* bias_set = nullptr;   // bias set: a biased pick; bias_set: only read
+    wrk_cut_args cut;                                                   // any set: a cut pick (with or without top_k / min_p)
     enum Need { ANY, SAMPLER, TABLE } need = ANY;
 };
+// the cut arrays travel in wrk_generate_options; a queue takes them beside its options (wrk_queue_cuts), whose field list is pinned
+inline wrk_cut_args wrk_cut_of(const wrk_generate_options& o) {
+    return {o.top_n_sigma, o.epsilon_cutoff, o.eta_cutoff, o.xtc_probability, o.xtc_threshold};
+}
+inline wrk_cut_args wrk_cut_of(const wrk_queue_options&) { return {}; }
+inline wrk_cut_args wrk_cut_of(const wrk_queue_cuts* c) {
+    return c ? wrk_cut_args{c->top_n_sigma, c->epsilon_cutoff, c->eta_cutoff, c->xtc_probability, c->xtc_threshold} : wrk_cut_args{};
+}
 template <class Options> wrk_pick_args wrk_pick_of(const Options& o) {
     return {o.temperature, o.top_p, o.seed, o.presence, o.frequency, o.decay, o.occ, o.top_k, o.min_p,
             o.mirostat_tau, o.mirostat_eta, o.mirostat_mu, o.typical_p, o.grammar, o.grammar_state,
             wrk_dry_args{o.window, o.dry_multiplier, o.dry_base, o.dry_allowed_length, o.no_repeat_ngram, o.dry_breakers, o.num_dry_breakers},
-            o.bias, o.bias_set};
+            o.bias, o.bias_set, wrk_cut_of(o)};
 }
 // the log-prob outputs of a call (wrk_generate_options / wrk_queue_options); logprob NULL: off
 struct wrk_logprob_call {
@@ -512,7 +524,11 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
 // occurrence rows, the window, the tails and the intake flags stay B wide; the slot records, start flags, tokens and history are 2B wide
 int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                            const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail,
-                           const wrk_queue_pool* pool, const wrk_queue_guidance* guide = nullptr, bool guided = false);
+                           const wrk_queue_pool* pool, const wrk_queue_guidance* guide = nullptr, bool guided = false,
+                           const wrk_queue_cuts* cuts = nullptr);
+// wrk_v*_generate_queue_cut: the queue call that cuts->pool / cuts->guide select (WRK_E_ARG: cuts NULL, or both) with cuts' arrays
+int32_t wrk_generate_queue_cut(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                               const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_cuts* cuts);
 // wrk_v*_generate_beam (tail BEAM): the stop call's polled loop on one lane over B = G * num_beams slots with the beam tail and the count of
 // LIVE slots; after the loop the DONE slots are restored from their snapshots, the records and the history rows come back and the
 // hypotheses are backtracked through the parents on the host

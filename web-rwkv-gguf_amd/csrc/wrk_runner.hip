@@ -161,6 +161,7 @@ int32_t wrk_job_read_back(wrk_frame_common& f, const wrk::FrameIo& io, uint32_t 
 struct wrk_pick_params {    // validated rows; empty: the arg-max / without penalties / without filters
     std::vector<wrk::SampleParam> par; std::vector<wrk::PenaltyParam> pen; std::vector<wrk::SampleFilter> filt;
     std::vector<wrk::SampleAlt> alt;        // Mirostat / typical rows
+    std::vector<wrk::SampleCut> cut;        // the cut sampler's rows, next to filt (which a cut pick always has)
     const wrk_grammar* grammar = nullptr;   // a constrained pick: the automaton and the state every row starts in
     std::vector<uint32_t> gram_state;
     const wrk_logit_bias* bias = nullptr;   // a biased pick: the object and every row's set word
@@ -181,11 +182,13 @@ static int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, u
     WRK_ARG(ctx, a.occ || (!a.presence && !a.frequency && !a.decay), "penalty arrays without an occurrence table");
     WRK_ARG(ctx, !a.occ || given == 3, "penalties need the sampler arrays");
     WRK_ARG(ctx, (!a.top_k && !a.min_p) || given == 3, "top_k / min_p need the sampler arrays");
-    const bool filt = a.top_k || a.min_p, miro = a.mirostat_tau || a.mirostat_eta || a.mirostat_mu, typ = a.typical_p != nullptr;
+    const bool cut = a.cut.any();
+    const bool filt = a.top_k || a.min_p || cut, miro = a.mirostat_tau || a.mirostat_eta || a.mirostat_mu, typ = a.typical_p != nullptr;
+    WRK_ARG(ctx, !cut || given == 3, "top_n_sigma / epsilon_cutoff / eta_cutoff / xtc_* need the sampler arrays");
     WRK_ARG(ctx, !miro || a.mirostat_tau, "mirostat_eta / mirostat_mu without mirostat_tau");
-    WRK_ARG(ctx, (int)filt + (int)miro + (int)typ <= 1, "one family per call: top_k / min_p, mirostat_* or typical_p");
+    WRK_ARG(ctx, (int)filt + (int)miro + (int)typ <= 1, "one family per call: top_k / min_p and the cuts, mirostat_* or typical_p");
     WRK_ARG(ctx, (!miro && !typ) || given == 3, "mirostat_* / typical_p need the sampler arrays");
-    kind.pick = given == 0 ? wrk_step_kind::GREEDY : filt ? wrk_step_kind::FILTERED : miro ? wrk_step_kind::MIROSTAT
+    kind.pick = given == 0 ? wrk_step_kind::GREEDY : cut ? wrk_step_kind::CUT : filt ? wrk_step_kind::FILTERED : miro ? wrk_step_kind::MIROSTAT
                            : typ ? wrk_step_kind::TYPICAL : wrk_step_kind::SAMPLED;
     kind.penalized = a.occ != nullptr;
     WRK_ARG(ctx, a.grammar || !a.grammar_state, "grammar_state without grammar");
@@ -214,6 +217,8 @@ static int32_t wrk_pick_pack(wrk_ctx* ctx, const wrk_pick_args& a, uint32_t n, u
     WRK_ARG(ctx, n >= 1, "a sampled pick of no rows");
     int32_t rc = wrk_sample_pack(ctx, a.temperature, a.top_p, a.seed, n, out.par);
     if (rc == WRK_OK && kind.filtered()) rc = wrk_filter_pack(ctx, a.top_k, a.min_p, n, out.filt);
+    if (rc == WRK_OK && kind.cut()) rc = wrk_cut_pack(ctx, a.cut, n, out.cut);
+    if (rc == WRK_OK && kind.cut() && V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
     if (rc == WRK_OK && miro) rc = wrk_mirostat_pack(ctx, a.mirostat_tau, a.mirostat_eta, a.mirostat_mu, n, out.alt);
     if (rc == WRK_OK && typ) rc = wrk_typical_pack(ctx, a.typical_p, n, out.alt);
     if (rc == WRK_OK && kind.alt() && V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "sampler: vocabulary of %u tokens", V);
@@ -384,6 +389,7 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     const wrk::PenaltyParam* pen = rows.pen.empty() ? nullptr : rows.pen.data() + b0;
     const wrk::SampleFilter* filt = rows.filt.empty() ? nullptr : rows.filt.data() + b0;
     const wrk::SampleAlt* alt = rows.alt.empty() ? nullptr : rows.alt.data() + b0;
+    const wrk::SampleCut* cut = rows.cut.empty() ? nullptr : rows.cut.data() + b0;
     const size_t V = f.facts().num_vocab;
     const bool guided = !rows.guide.empty();
     const uint32_t R = guided ? B / 2 : B;      // rows of the pick
@@ -391,6 +397,7 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     if (rc == WRK_OK && par) rc = f.grow(f.sample, {R});
     if (rc == WRK_OK && filt) rc = f.grow(f.filter, {R});
     if (rc == WRK_OK && alt) rc = f.grow(f.alt, {R});
+    if (rc == WRK_OK && cut) rc = f.grow(f.cut_par, {R});
     if (rc == WRK_OK && pen) rc = f.grow(f.penalty, {R, V});
     if (rc == WRK_OK && rows.grammar) rc = f.grow(f.grammar, {R, V});
     if (rc == WRK_OK && rows.bias) rc = f.grow(f.bias, {R, V});
@@ -404,6 +411,7 @@ static int32_t wrk_decode_prepare(wrk_frame_common& f, const uint32_t* first_tok
     if (par) up(f.sample.par, par, R);
     if (filt) up(f.filter.par, filt, R);
     if (alt) up(f.alt.par, alt, R);
+    if (cut) up(f.cut_par.par, cut, R);
     if (pen) up(f.penalty.par, pen, R);
     if (rows.grammar) {
         const wrk::GrammarParam gp = rows.grammar->param(f.grammar.state);
@@ -496,7 +504,7 @@ struct wrk_queue_pack {
 
 // guided: the call is wrk_v*_generate_queue_guided's -- B pairs of state slots; the guidance itself: wrk_queue_guide_check, behind this
 static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const wrk_v7_state* st, uint32_t B, uint32_t V, uint32_t mode_arg,
-                               wrk_queue_result* out, wrk_queue_pack& pk, bool guided) {
+                               wrk_queue_result* out, wrk_queue_pack& pk, bool guided, const wrk_queue_cuts* cuts) {
     WRK_ARG(ctx, opt, "options required");
     WRK_ARG(ctx, out && out->lengths && out->reasons && out->slots && out->start_steps && out->out_tokens && out->steps_run,
             "every result array is required");
@@ -524,7 +532,11 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
     if (rc == WRK_OK) rc = wrk_stop_sets(ctx, opt->stop_tokens, opt->stop_offsets, R, V, "request", stops);
     if (rc == WRK_OK)
         rc = wrk_stop_seqs(ctx, opt->stop_seq_tokens, opt->stop_seq_offsets, opt->stop_seq_owners, opt->out_stop_match != nullptr, nullptr, R, V, "request", pk.seq);
-    if (rc == WRK_OK) rc = wrk_pick_pack(ctx, wrk_pick_of(*opt), R, B, V, req, pk.kind);
+    if (rc == WRK_OK) {
+        wrk_pick_args pick = wrk_pick_of(*opt);
+        pick.cut = wrk_cut_of(cuts);
+        rc = wrk_pick_pack(ctx, pick, R, B, V, req, pk.kind);
+    }
     if (rc == WRK_OK) rc = wrk_logprob_check(ctx, pk.lp, V, pk.kind);
     if (rc != WRK_OK) return rc;
     pk.kind.stop_seqs = pk.seq.on;
@@ -547,6 +559,12 @@ static int32_t wrk_queue_check(wrk_ctx* ctx, const wrk_queue_options* opt, const
         if (kind.sampled()) { q.temperature = req.par[r].temperature; q.top_p = req.par[r].top_p; q.seed = req.par[r].seed; }
         q.ln_min_p = -INFINITY;
         if (kind.filtered()) { q.top_k = req.filt[r].top_k; q.ln_min_p = req.filt[r].ln_min_p; }
+        q.ln_epsilon = q.ln_eta = -INFINITY;
+        if (kind.cut()) {
+            const wrk::SampleCut& c = req.cut[r];
+            q.top_n_sigma = c.top_n_sigma; q.ln_epsilon = c.ln_epsilon; q.ln_eta = c.ln_eta;
+            q.xtc_probability = c.xtc_probability; q.ln_xtc_threshold = c.ln_xtc_threshold;
+        }
         q.typical_p = 1.0f;
         if (kind.alt()) { q.tau = req.alt[r].tau; q.eta = req.alt[r].eta; q.typical_p = req.alt[r].typical_p; }
         if (kind.penalized) { q.presence = req.pen[r].presence; q.frequency = req.pen[r].frequency; q.decay = req.pen[r].decay; }
@@ -665,6 +683,13 @@ static wrk::QueueBufs queue_bufs(const wrk_frame_common& f, wrk_step_kind kind) 
         q.pair_started = f.queue_guide.pair_started;
         return q;
     }
+    if (kind.cut()) {
+        wrk_step_kind filt = kind;
+        filt.pick = wrk_step_kind::FILTERED;
+        wrk::QueueBufs q = queue_bufs(f, filt);
+        q.cut_par = f.cut_par.par;
+        return q;
+    }
     return wrk::QueueBufs{f.queue.slots, f.queue.reqs, f.queue.pool, f.queue.log, f.queue.ctl, f.queue.started,
                           kind.sampled() ? f.sample.par : nullptr, kind.penalized ? f.penalty.par : nullptr, kind.filtered() ? f.filter.par : nullptr,
                           kind.alt() ? f.alt.par : nullptr, kind.mirostat() ? f.queue.mu : nullptr,
@@ -692,6 +717,7 @@ static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_
     if (kind.sampled()) rows.par.assign(B, wrk::SampleParam{1.0f, 0.0f, 0u, 0u});
     if (kind.filtered()) rows.filt.assign(B, wrk::SampleFilter{0u, -INFINITY});
     if (kind.alt()) rows.alt.assign(B, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
+    if (kind.cut()) rows.cut.assign(B, wrk::SampleCut{0.0f, -INFINITY, -INFINITY, 0.0f, 0.0f});
     if (kind.constrained) rows.gram_state.assign(B, 0u);
     if (kind.biased) rows.bias_set.assign(B, WRK_BIAS_NONE);
     for (uint32_t b = 0; b < B && kind.penalized; ++b) rows.pen.push_back(opt->occ->row(b, 0.0f, 0.0f, 1.0f));
@@ -708,9 +734,10 @@ static void wrk_queue_start(const wrk_queue_options* opt, uint32_t B, wrk_queue_
     pk.turn.resize(pk.nstart);
     // as queue_bufs: an array is nullptr exactly when the kind is without its feature (a vector of the pack is empty then)
     auto at = [](auto& v) { return v.empty() ? nullptr : v.data(); };
-    const wrk::QueueBufs Q{pk.slots.data(), pk.reqs.data(), pk.pool.data(), pk.log.data(), nullptr, nullptr, at(rows.par), at(rows.pen), at(rows.filt),
-                           at(rows.alt), kind.mirostat() ? pk.mu.data() : nullptr, at(rows.gram_state), at(pk.gram), at(rows.dry), at(pk.dry),
-                           at(pk.seq.rows), at(pk.tails), nullptr, at(pk.from), at(pk.take), at(rows.bias_set), at(pk.bias)};
+    wrk::QueueBufs Q{pk.slots.data(), pk.reqs.data(), pk.pool.data(), pk.log.data(), nullptr, nullptr, at(rows.par), at(rows.pen), at(rows.filt),
+                     at(rows.alt), kind.mirostat() ? pk.mu.data() : nullptr, at(rows.gram_state), at(pk.gram), at(rows.dry), at(pk.dry),
+                     at(pk.seq.rows), at(pk.tails), nullptr, at(pk.from), at(pk.take), at(rows.bias_set), at(pk.bias)};
+    Q.cut_par = at(rows.cut);
     const wrk::QueueStateBufs P{pk.start.data(), pk.save.data(), nullptr, pk.turn.data(), kind.history};
     if (kind.guided) {
         // the guided rule over the same mirrors: a half's start flag is raised when it feeds its first token at step 0, the others wait
@@ -1088,10 +1115,12 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t frame_b, wrk_step_kind ki
         if (!argmax_done) wrk::argmax_rows(q, logits, V, V, B, io.argmax);
     } else if (kind.filtered() && !f.filter.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "filter rows are not prepared");
     else if (kind.alt() && !f.alt.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "Mirostat / typical rows are not prepared");
+    else if (kind.cut() && !f.cut_par.holds({B})) return wrk_fail(f.ctx, WRK_E_ARG, "cut rows are not prepared");
     else {
         // mu moves exactly where an occurrence row counts a draw: both read the step's one gate
         wrk::SamplePick pick{wrk::SAMPLE_PLAIN, f.sample.par, nullptr, nullptr, wrk::RowGate{nullptr, 0u, 0u}};
         if (kind.filtered()) { pick.mode = wrk::SAMPLE_FILT; pick.filt = f.filter.par; }
+        if (kind.cut()) { pick.mode = wrk::SAMPLE_CUT; pick.cut = f.cut_par.par; }
         if (kind.alt()) { pick.mode = kind.mirostat() ? wrk::SAMPLE_MIRO : wrk::SAMPLE_TYP; pick.alt = f.alt.par; }
         if (kind.mirostat()) {
             const int32_t grc = draw_gate(f, B, kind, pick.gate);
@@ -1384,12 +1413,12 @@ int32_t wrk_generate(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const 
 
 int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
                            const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, wrk_step_kind::Tail tail,
-                           const wrk_queue_pool* pool, const wrk_queue_guidance* guide, bool guided) {
+                           const wrk_queue_pool* pool, const wrk_queue_guidance* guide, bool guided, const wrk_queue_cuts* cuts) {
     if (!ctx || !m || !st) return WRK_E_ARG;
     LOCK(ctx);
     wrk_queue_result out = out_arg ? *out_arg : wrk_queue_result{};
     wrk_queue_pack pk;
-    int32_t rc = wrk_queue_check(ctx, opt, st, B, m->facts().num_vocab, mode_arg, out_arg ? &out : nullptr, pk, guided);
+    int32_t rc = wrk_queue_check(ctx, opt, st, B, m->facts().num_vocab, mode_arg, out_arg ? &out : nullptr, pk, guided, cuts);
     if (rc == WRK_OK && tail != wrk_step_kind::QUEUE_POOL && opt->history) rc = wrk_fail(ctx, WRK_E_ARG, "a history pool without a state pool");
     if (rc == WRK_OK && tail == wrk_step_kind::QUEUE_POOL) rc = wrk_queue_pool_check(ctx, pool, opt, st, m->facts().num_vocab, pk);
     if (rc == WRK_OK && guided) rc = wrk_queue_guide_check(ctx, guide, opt, st, m->facts().num_vocab, pk);
@@ -1412,6 +1441,18 @@ int32_t wrk_generate_queue(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, 
     return wrk_queue_finish(*m, B, steps_run, pk, opt, &out);
 }
 
+int32_t wrk_generate_queue_cut(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                               const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_cuts* cuts) {
+    if (!ctx || !m || !st) return WRK_E_ARG;
+    {
+        LOCK(ctx);
+        WRK_ARG(ctx, cuts, "cuts required");
+        WRK_ARG(ctx, !cuts->pool || !cuts->guide, "a state pool under a guided queue: no entry point takes both");
+    }
+    const wrk_step_kind::Tail tail = cuts->pool ? wrk_step_kind::QUEUE_POOL : wrk_step_kind::QUEUE;
+    return wrk_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, tail, cuts->pool, cuts->guide, cuts->guide != nullptr, cuts);
+}
+
 // generate_beam: opt validated into pk (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch); sets kind
 static int32_t wrk_beam_check(wrk_ctx* ctx, const wrk_beam_options* opt, const wrk_beam_result* out, const wrk_v7_state* st, const uint32_t* first_tokens,
                               uint32_t G, uint32_t steps, uint32_t V, uint32_t mode_arg, wrk_beam_pack& pk, wrk_step_kind& kind) {
@@ -1426,7 +1467,8 @@ static int32_t wrk_beam_check(wrk_ctx* ctx, const wrk_beam_options* opt, const w
     WRK_ARG(ctx, ((mode_arg >> 8) & 0xffu) <= 1, "generate_beam runs on one lane");
     static const wrk_generate_options none{};
     const wrk_generate_options& g = opt->gen ? *opt->gen : none;
-    WRK_ARG(ctx, !g.temperature && !g.top_p && !g.seed && !g.top_k && !g.min_p && !g.mirostat_tau && !g.mirostat_eta && !g.mirostat_mu && !g.typical_p,
+    WRK_ARG(ctx, !g.temperature && !g.top_p && !g.seed && !g.top_k && !g.min_p && !g.mirostat_tau && !g.mirostat_eta && !g.mirostat_mu && !g.typical_p &&
+                     !wrk_cut_of(g).any(),
             "beam search takes no sampler");
     WRK_ARG(ctx, !g.presence && !g.frequency && !g.decay && !g.occ, "beam search takes no penalties");
     WRK_ARG(ctx, !g.window && !g.dry_multiplier && !g.dry_base && !g.dry_allowed_length && !g.no_repeat_ngram && !g.dry_breakers && !g.num_dry_breakers,

@@ -22,6 +22,18 @@
 // pass (sum e and sum e g in fixed point, g = max - l) gives gbar; the boundary is the nucleus's mass select over the key
 // monotone(-d) << 20 | (2^20 - 1 - index), d = |g - gbar|, with the pass-0 digit taken from the range of d; the draw's candidates are
 // the tokens whose d-key is >= the boundary's.  The descent is one lambda, generic in which key it walks.
+//
+// MODE SAMPLE_CUT (DESIGN.md "XTC, top-n-sigma and the eta / epsilon cut-offs") is SAMPLE_FILT's body with two additions.  Upper end: the
+// three new cuts are, like min-p, lower bounds on d = l - max, so the draw's predicate keeps its one compare, against
+//   thr = max(ln_min_p, -top_n_sigma * sigma, ln_epsilon + ln S, min(ln_eta, ln_eta / 2 - H) + ln S),
+// rank 0 always in.  S = sum e and H = ln S + gbar come from the typical kernel's moments pass (fixed point); sigma from one pass of
+// integer moments of q = trunc((max - l) * 2^21 / (max - low)) over the finite logits: sigma = sqrt(N sum q^2 - (sum q)^2) / N in units of
+// (max - low) / 2^21, the radicand an exact 128-bit integer.  Lower end (XTC): the row's coin c = (sample_splitmix_next >> 40) * 2^-24,
+// the second output of the SplitMix64 stream whose first gives u; with c < xtc_probability one count / min-key pass over the candidates
+// with d >= ln(xtc_threshold) + ln S gives m' and the key of rank m' - 1, and with m' >= 2 the draw runs on kmin <= K <= kmax, its
+// weights exp((l - l_m0) / T) relative to the logit of rank m0 = m' - 1, read back out of that key.  A pass a
+// row's parameters do not ask for is skipped; every sum is an integer sum and the minimum is a minimum of unique keys.
+#include <cfloat>
 #include <cmath>
 #include <type_traits>
 
@@ -35,6 +47,14 @@ static constexpr float SAMPLE_ONE = 1099511627776.0f;      // 2^40: mass of the 
 
 __host__ __device__ inline uint64_t sample_splitmix(uint32_t seed, uint32_t step) {
     uint64_t z = (((uint64_t)seed << 32) | step) + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// the second output of the SplitMix64 stream whose first output is sample_splitmix(seed, step): the state advanced once more
+__host__ __device__ inline uint64_t sample_splitmix_next(uint32_t seed, uint32_t step) {
+    uint64_t z = (((uint64_t)seed << 32) | step) + 2ull * 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
@@ -56,6 +76,8 @@ __device__ __forceinline__ uint32_t typical_digit(float d, float scale) {
 }
 
 static constexpr float SAMPLE_LOG2E = 1.44269504088896340736f;
+static constexpr float SAMPLE_LN_ONE = 27.725887222397812f;     // ln 2^40
+static constexpr float SAMPLE_SIGMA_ONE = 2097152.0f;            // 2^21: the fixed point of (max - l) / (max - low)
 
 struct SampleSmem {
     unsigned long long mass[SAMPLE_BINS];
@@ -131,18 +153,36 @@ __device__ __forceinline__ unsigned long long block_sum(unsigned long long v, Sa
     return all;
 }
 
+// minimum of v over the workgroup (same value in every thread)
+__device__ __forceinline__ unsigned long long block_min(unsigned long long v, SampleSmem& sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(v, o, WAVE);
+        v = t < v ? t : v;
+    }
+    __syncthreads();            // the readers of an earlier wsum are done
+    if ((threadIdx.x & 63) == 0) sm.wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long all = ~0ull;
+#pragma unroll
+    for (uint32_t w = 0; w < SAMPLE_THREADS / WAVE; ++w) all = sm.wsum[w] < all ? sm.wsum[w] : all;
+    return all;
+}
+
 static constexpr uint32_t SAMPLE_NO_COUNT = 0xffffffffu;
 
 // One row per workgroup.  NPT > 0: the row (V <= 1024 * NPT) stays in registers; NPT == 0: every pass re-reads it from L2 (V <= 2^20;
 // a 64-per-thread register copy of a 65536-token row spills, the passes' own state needs ~95 VGPRs)
 // MODE SAMPLE_FILT: the filtered kernel's body (filt: one SampleFilter per row); every addition sits under `if constexpr (FILT)`.
 // SAMPLE_MIRO / SAMPLE_TYP: the Mirostat / typical kernel's (alt: one SampleAlt per row); additions under `if constexpr (MIRO)` / `(TYP)`
+// SAMPLE_CUT: the filtered kernel's body (FILT holds) and the cuts of cut[row]; every addition sits under `if constexpr (CUT)`
 template <int NPT, int MODE>
 __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __restrict__ logits, uint32_t V, uint32_t stride,
                                                  const SampleParam* __restrict__ par, const SampleFilter* __restrict__ filt,
                                                  SampleAlt* alt, const RowGate gate,
-                                                 const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out) {
-    constexpr bool FILT = MODE == SAMPLE_FILT, MIRO = MODE == SAMPLE_MIRO, TYP = MODE == SAMPLE_TYP;
+                                                 const uint32_t* __restrict__ step_word, uint32_t* __restrict__ out,
+                                                 const SampleCut* __restrict__ cut) {
+    constexpr bool CUT = MODE == SAMPLE_CUT, FILT = MODE == SAMPLE_FILT || CUT, MIRO = MODE == SAMPLE_MIRO, TYP = MODE == SAMPLE_TYP;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* row = logits + (size_t)blockIdx.x * stride;
     const int nj = NPT > 0 ? NPT : (int)((V + SAMPLE_THREADS - 1) / SAMPLE_THREADS);
@@ -260,6 +300,58 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
         }
     }
     unsigned long long draw_total = 0;      // Mirostat: W_c, the draw's pass-0 total
+    // cut rows.  thr: the lowest d = l - max of a candidate below rank 0 (min-p, top-n-sigma, epsilon and eta in one bound; all four
+    // off: ln_min_p, SAMPLE_FILT's test).  xtc: the coin fell below xtc_probability; thr_x: the d of xtc_threshold
+    float thr = ln_min_p, thr_x = 0.0f;
+    bool xtc = false;
+    if constexpr (CUT) {
+        const SampleCut ct = cut[blockIdx.x];
+        const float coin = (float)(sample_splitmix_next(pr.seed, *step_word - pr.step_base) >> 40) * 5.9604644775390625e-8f;     // * 2^-24: exact
+        xtc = coin < ct.xtc_probability;
+        const bool use_h = ct.ln_eta > -INFINITY, use_e = ct.ln_epsilon > -INFINITY;
+        if (use_h || use_e || xtc) {        // the typical kernel's moments pass: S = sum e, and gbar = sum e g / sum e for H = ln S + gbar
+            unsigned long long se = 0, seg = 0;
+            for_each([&](int j, float l) {
+                const bool in = tid + SAMPLE_THREADS * (uint32_t)j < V && l > -INFINITY;
+                const float g = l == mx ? 0.0f : mx - l, e = l == mx ? 1.0f : expf(l - mx);
+                const float eg = in && e > 0.0f ? e * g : 0.0f;
+                se += in ? (unsigned long long)(e * SAMPLE_ONE) : 0ull;
+                seg += (unsigned long long)(eg * SAMPLE_ONE);
+            });
+            se = block_sum(se, sm);
+            seg = block_sum(seg, sm);
+            const float ln_s = logf((float)se) - SAMPLE_LN_ONE;
+            if (use_e) thr = fmaxf(thr, ct.ln_epsilon + ln_s);
+            if (use_h) {
+                const float h = ln_s + (float)((double)seg / (double)se);
+                thr = fmaxf(thr, fminf(ct.ln_eta, 0.5f * ct.ln_eta - h) + ln_s);
+            }
+            thr_x = ct.ln_xtc_threshold + ln_s;
+        }
+        // sigma of the finite logits; max - low == 0, or not finite (max = +inf): sigma = 0, the ties of the maximum stay (thr <= 0 already)
+        const float qs = SAMPLE_SIGMA_ONE / (mx - low);
+        if (ct.top_n_sigma > 0.0f && qs > 0.0f && qs < INFINITY) {
+            unsigned long long cn = 0, t1 = 0, t2 = 0;
+            for_each([&](int j, float l) {
+                const bool in = tid + SAMPLE_THREADS * (uint32_t)j < V && l > -INFINITY;
+                const unsigned long long q = in ? (unsigned long long)fminf((mx - l) * qs, SAMPLE_SIGMA_ONE) : 0ull;
+                cn += in ? 1ull : 0ull;
+                t1 += q;
+                t2 += q * q;            // q <= 2^21, at most 2^20 terms: below 2^62
+            });
+            cn = block_sum(cn, sm);
+            t1 = block_sum(t1, sm);
+            t2 = block_sum(t2, sm);
+            const unsigned __int128 rad = (unsigned __int128)cn * t2 - (unsigned __int128)t1 * t1;      // >= 0 (Cauchy-Schwarz), exact
+            const double radd = (double)(unsigned long long)(rad >> 64) * 18446744073709551616.0 + (double)(unsigned long long)rad;
+            const float sigma = (float)(sqrt(radd) / ((double)cn * (double)qs));
+            thr = fmaxf(thr, -(ct.top_n_sigma * sigma));
+        }
+    }
+    // cut rows: the key of rank m0 (XTC), the draw's upper bound, and its logit, which the draw's weights are taken relative to -- exp((l -
+    // mw) / T), 1 at rank m0 -- so that the fixed point keeps its 40 bits below the heaviest candidate, not below a token that is gone
+    uint64_t kmax = ~0ull;
+    float mw = mx;
 
     // Weighted select over K among the tokens with K >= kmin.  use_w = false: masses e = exp(l - mx); the LAST rank whose mass before
     // it is <= P * sum (the nucleus boundary).  use_w = true: masses w = exp((l - mx) / T); the FIRST rank whose mass up to and
@@ -311,7 +403,9 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
                         if (typ) cand = i < V && typical_key(typical_dist(l, mx, gbar), i) >= kmin;
                     }
                 }
-                if constexpr (FILT) {
+                if constexpr (CUT) {
+                    if (use_w) cand = cand && k <= kmax && (i == top || (l == mx ? 0.0f : l - mx) >= thr);   // thr > 0: p_max is below epsilon / eta, rank 0 alone
+                } else if constexpr (FILT) {
                     if (use_w) cand = cand && (l == mx || l - mx >= ln_min_p);      // rank 0 always passes (mx = +inf: inf - inf is NaN)
                 }
                 if constexpr (MIRO) {
@@ -323,7 +417,9 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
                 if (cand) {
                     const uint32_t d = p == 0 ? c : (uint32_t)(k >> shift) & ((1u << width) - 1u);
                     if (live_p) {
-                        const float e = l == mx ? 1.0f : expf(use_w ? (l - mx) * inv_t : l - mx);
+                        float e;
+                        if constexpr (CUT) e = use_w ? (l == mw ? 1.0f : expf((l - mw) * inv_t)) : (l == mx ? 1.0f : expf(l - mx));
+                        else e = l == mx ? 1.0f : expf(use_w ? (l - mx) * inv_t : l - mx);
                         atomicAdd(&sm.mass[d], (unsigned long long)(e * SAMPLE_ONE));
                     }
                     atomicAdd(&sm.cnt[d], 1u);
@@ -416,6 +512,26 @@ __device__ __forceinline__ void sample_rows_body(SampleSmem& sm, const float* __
             kmin = typical_key(typical_dist(row_norm(lr), mx, gbar), r);
         }
     }
+    if constexpr (CUT) {
+        if (xtc) {      // m' = #{candidates with p >= xtc_threshold} and the smallest of their keys, the key of rank m' - 1
+            unsigned long long cn = 0, kmn = ~0ull;
+            for_each([&](int j, float l) {
+                const uint32_t i = tid + SAMPLE_THREADS * (uint32_t)j;
+                const uint64_t k = rank_key(l, i);
+                const float d = l == mx ? 0.0f : l - mx;
+                const bool in = i < V && k >= kmin && (i == top || d >= thr) && d >= thr_x;
+                cn += in ? 1ull : 0ull;
+                kmn = in && k < kmn ? k : kmn;
+            });
+            cn = block_sum(cn, sm);
+            kmn = block_min(kmn, sm);
+            if (cn >= 2) {
+                kmax = kmn;
+                const uint32_t b = (uint32_t)(kmn >> 20);       // rank_key's monotone(logit), inverted
+                mw = __uint_as_float((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b);
+            }
+        }
+    }
     const uint32_t tok = select(std::false_type{}, true, kmin, true, SAMPLE_NO_COUNT);
     if (tid == 0) {
         out[blockIdx.x] = tok;
@@ -438,9 +554,9 @@ template <int NPT, int MODE>
 __global__ void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(const float* __restrict__ logits, uint32_t V, uint32_t stride,
                                                                      const SampleParam* __restrict__ par, const uint32_t* __restrict__ step_word,
                                                                      uint32_t* __restrict__ out, const SampleFilter* __restrict__ filt,
-                                                                     SampleAlt* alt, const RowGate gate) {
+                                                                     SampleAlt* alt, const RowGate gate, const SampleCut* __restrict__ cut) {
     __shared__ SampleSmem sm;
-    sample_rows_body<NPT, MODE>(sm, logits, V, stride, par, filt, alt, gate, step_word, out);
+    sample_rows_body<NPT, MODE>(sm, logits, V, stride, par, filt, alt, gate, step_word, out, cut);
 }
 
 // The largest register copy (tokens per thread) of a mode; longer rows are re-read from L2.  Next to the count select's state of
@@ -452,10 +568,10 @@ template <int MODE>
 static void sample_rows_mode(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SamplePick& p, const uint32_t* step,
                              uint32_t* out) {
     constexpr int TOP = sample_npt_max(MODE);
-    if (v <= 1024) sample_rows_kernel<1, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate);
-    else if (v <= 4096) sample_rows_kernel<4, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate);
-    else if (v <= TOP * 1024) sample_rows_kernel<TOP, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate);
-    else sample_rows_kernel<0, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate);
+    if (v <= 1024) sample_rows_kernel<1, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate, p.cut);
+    else if (v <= 4096) sample_rows_kernel<4, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate, p.cut);
+    else if (v <= TOP * 1024) sample_rows_kernel<TOP, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate, p.cut);
+    else sample_rows_kernel<0, MODE><<<n, SAMPLE_THREADS, 0, s>>>(logits, v, stride, p.par, step, out, p.filt, p.alt, p.gate, p.cut);
 }
 
 int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride, uint32_t n, const SamplePick& pick, const uint32_t* step,
@@ -466,6 +582,7 @@ int sample_rows(hipStream_t s, const float* logits, uint32_t v, uint32_t stride,
         case SAMPLE_FILT: sample_rows_mode<SAMPLE_FILT>(s, logits, v, stride, n, pick, step, out); break;
         case SAMPLE_MIRO: sample_rows_mode<SAMPLE_MIRO>(s, logits, v, stride, n, pick, step, out); break;
         case SAMPLE_TYP: sample_rows_mode<SAMPLE_TYP>(s, logits, v, stride, n, pick, step, out); break;
+        case SAMPLE_CUT: sample_rows_mode<SAMPLE_CUT>(s, logits, v, stride, n, pick, step, out); break;
         default: sample_rows_mode<SAMPLE_PLAIN>(s, logits, v, stride, n, pick, step, out); break;
     }
     return 0;
@@ -499,6 +616,37 @@ int32_t wrk_filter_pack(wrk_ctx* ctx, const uint32_t* top_k, const float* min_p,
     return WRK_OK;
 }
 
+int32_t wrk_cut_pack(wrk_ctx* ctx, const wrk_cut_args& a, uint32_t n, std::vector<wrk::SampleCut>& out) {
+    WRK_ARG(ctx, (a.xtc_probability != nullptr) == (a.xtc_threshold != nullptr), "xtc_probability and xtc_threshold: both arrays, or neither");
+    out.assign(n, wrk::SampleCut{0.0f, -INFINITY, -INFINITY, 0.0f, 0.0f});
+    auto unit = [](float x) { return !(x != x) && x >= 0.0f && x <= 1.0f; };
+    for (uint32_t b = 0; b < n; ++b) {
+        wrk::SampleCut& c = out[b];
+        if (a.top_n_sigma) {
+            const float s = a.top_n_sigma[b];
+            WRK_ARG(ctx, !(s != s) && s >= 0.0f, "top_n_sigma[%u] = %g: must be >= 0", b, (double)s);
+            c.top_n_sigma = s < FLT_MAX ? s : FLT_MAX;      // +inf: the largest finite value (inf * sigma with sigma = 0 would be NaN)
+        }
+        // the logarithms in f64, rounded once; 0: -inf, the cut is off
+        if (a.epsilon_cutoff) {
+            WRK_ARG(ctx, unit(a.epsilon_cutoff[b]), "epsilon_cutoff[%u] = %g: must be in [0, 1]", b, (double)a.epsilon_cutoff[b]);
+            c.ln_epsilon = (float)std::log((double)a.epsilon_cutoff[b]);
+        }
+        if (a.eta_cutoff) {
+            WRK_ARG(ctx, unit(a.eta_cutoff[b]), "eta_cutoff[%u] = %g: must be in [0, 1]", b, (double)a.eta_cutoff[b]);
+            c.ln_eta = (float)std::log((double)a.eta_cutoff[b]);
+        }
+        if (a.xtc_probability) {
+            const float p = a.xtc_probability[b], t = a.xtc_threshold[b];
+            WRK_ARG(ctx, unit(p), "xtc_probability[%u] = %g: must be in [0, 1]", b, (double)p);
+            WRK_ARG(ctx, unit(t), "xtc_threshold[%u] = %g: must be in [0, 1]", b, (double)t);
+            c.xtc_probability = t > 0.5f ? 0.0f : p;        // above one half at most one token qualifies: off
+            c.ln_xtc_threshold = (float)std::log((double)t);
+        }
+    }
+    return WRK_OK;
+}
+
 int32_t wrk_mirostat_pack(wrk_ctx* ctx, const float* tau, const float* eta, const float* mu, uint32_t n, std::vector<wrk::SampleAlt>& out) {
     WRK_ARG(ctx, tau, "mirostat_eta / mirostat_mu without mirostat_tau");
     out.assign(n, wrk::SampleAlt{0.0f, 0.0f, 0.0f, 1.0f});
@@ -526,7 +674,8 @@ int32_t wrk_typical_pack(wrk_ctx* ctx, const float* typical_p, uint32_t n, std::
 // the row functions' sampler: the filtered kernel on (top_k, min_p), either of which may be NULL; the Mirostat kernel on (tau, eta,
 // mu_inout); the typical kernel on typical_p
 struct sample_logits_kind {
-    enum { PLAIN, FILTERED, MIROSTAT, TYPICAL } k = PLAIN;
+    enum { PLAIN, FILTERED, MIROSTAT, TYPICAL, CUT } k = PLAIN;
+    wrk_cut_args cut;           // CUT: the filtered kernel's arrays and these
     const uint32_t* top_k = nullptr; const float* min_p = nullptr;
     const float *tau = nullptr, *eta = nullptr; float* mu_inout = nullptr;
     const float* typical_p = nullptr;
@@ -537,15 +686,18 @@ static int32_t sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, ui
                              uint32_t* out_tokens, const char* who) {
     if (!ctx || !logits || !out_tokens) return WRK_E_ARG;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    const bool filtered = kind.k == sample_logits_kind::FILTERED, miro = kind.k == sample_logits_kind::MIROSTAT,
+    const bool cutk = kind.k == sample_logits_kind::CUT;
+    const bool filtered = kind.k == sample_logits_kind::FILTERED || cutk, miro = kind.k == sample_logits_kind::MIROSTAT,
                typical = kind.k == sample_logits_kind::TYPICAL;
     const uint32_t* top_k = kind.top_k;
     const float* min_p = kind.min_p;
     std::vector<wrk::SampleParam> par;
     std::vector<wrk::SampleFilter> filt;
     std::vector<wrk::SampleAlt> alt;
+    std::vector<wrk::SampleCut> cut;
     int32_t rc = wrk_sample_pack(ctx, temperature, top_p, seed, n, par);
     if (rc == WRK_OK && filtered) rc = wrk_filter_pack(ctx, top_k, min_p, n, filt);
+    if (rc == WRK_OK && cutk) rc = wrk_cut_pack(ctx, kind.cut, n, cut);
     if (rc == WRK_OK && miro) rc = wrk_mirostat_pack(ctx, kind.tau, kind.eta, kind.mu_inout, n, alt);
     if (rc == WRK_OK && typical) {
         WRK_ARG(ctx, kind.typical_p, "typical_p array required");
@@ -560,6 +712,7 @@ static int32_t sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, ui
     wrk_dev_arena dev;
     const size_t o_par = dev.add((size_t)n * sizeof(wrk::SampleParam)), o_step = dev.add(4), o_out = dev.add((size_t)n * 4);
     const size_t o_rows = dev.add((size_t)n * sizeof(wrk::SampleAlt));
+    const size_t o_cut = dev.add(cutk ? (size_t)n * sizeof(wrk::SampleCut) : 0);
     WRK_HIP(ctx, dev.alloc());
     wrk::SamplePick pick{wrk::SAMPLE_PLAIN, dev.at<wrk::SampleParam>(o_par), nullptr, nullptr, wrk::RowGate{}};
     WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_par), par.data(), (size_t)n * sizeof(wrk::SampleParam), hipMemcpyHostToDevice, ctx->stream));
@@ -568,6 +721,11 @@ static int32_t sample_logits(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, ui
         pick.mode = wrk::SAMPLE_FILT;
         pick.filt = dev.at<wrk::SampleFilter>(o_rows);
         WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_rows), filt.data(), (size_t)n * sizeof(wrk::SampleFilter), hipMemcpyHostToDevice, ctx->stream));
+        if (cutk) {
+            pick.mode = wrk::SAMPLE_CUT;
+            pick.cut = dev.at<wrk::SampleCut>(o_cut);
+            WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_cut), cut.data(), (size_t)n * sizeof(wrk::SampleCut), hipMemcpyHostToDevice, ctx->stream));
+        }
     } else if (miro || typical) {
         pick.mode = miro ? wrk::SAMPLE_MIRO : wrk::SAMPLE_TYP;
         pick.alt = dev.at<wrk::SampleAlt>(o_rows);
@@ -596,6 +754,19 @@ extern "C" int32_t wrk_sample_logits_filtered(wrk_ctx* ctx, const wrk_buf* logit
     if (top_k || min_p) kind.k = sample_logits_kind::FILTERED;
     kind.top_k = top_k; kind.min_p = min_p;
     return sample_logits(ctx, logits, V, stride, n, temperature, top_p, kind, seed, step, out_tokens, "wrk_sample_logits_filtered");
+}
+
+// every cut array NULL: wrk_sample_logits_filtered's kernel
+extern "C" int32_t wrk_sample_logits_cut(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n, const float* temperature,
+                                         const float* top_p, const uint32_t* top_k, const float* min_p, const float* top_n_sigma,
+                                         const float* epsilon_cutoff, const float* eta_cutoff, const float* xtc_probability,
+                                         const float* xtc_threshold, const uint32_t* seed, uint32_t step, uint32_t* out_tokens) {
+    sample_logits_kind kind;
+    kind.cut = wrk_cut_args{top_n_sigma, epsilon_cutoff, eta_cutoff, xtc_probability, xtc_threshold};
+    if (kind.cut.any()) kind.k = sample_logits_kind::CUT;
+    else if (top_k || min_p) kind.k = sample_logits_kind::FILTERED;
+    kind.top_k = top_k; kind.min_p = min_p;
+    return sample_logits(ctx, logits, V, stride, n, temperature, top_p, kind, seed, step, out_tokens, "wrk_sample_logits_cut");
 }
 
 extern "C" int32_t wrk_sample_logits_mirostat(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V, uint32_t stride, uint32_t n,

@@ -728,6 +728,11 @@ int32_t wrk_v7_generate_queue_guided(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state
     return wrk_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, wrk_step_kind::QUEUE, nullptr, guide, true);
 }
 
+int32_t wrk_v7_generate_queue_cut(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, uint32_t B, const wrk_queue_options* opt,
+                                  const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_cuts* cuts) {
+    return wrk_generate_queue_cut(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, cuts);
+}
+
 int32_t wrk_v7_generate_beam(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t G, uint32_t steps,
                              const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
     return wrk_generate_beam(ctx, m, st, first_tokens, G, steps, opt, out_arg, elapsed_ms, mode_arg);

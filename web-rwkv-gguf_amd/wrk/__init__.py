@@ -77,6 +77,7 @@ class GenerateOptions(C.Structure):
     _fields_ = [("temperature", _f32p), ("top_p", _f32p), ("seed", _u32p), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
                 ("occ", _P), ("bias", _P), ("bias_set", _u32p), ("guidance_scale", _f32p), ("guidance_first_tokens", _u32p),
                 ("stop_tokens", _u32p), ("stop_offsets", _u32p), ("poll_steps", C.c_uint32),
+                ("top_n_sigma", _f32p), ("epsilon_cutoff", _f32p), ("eta_cutoff", _f32p), ("xtc_probability", _f32p), ("xtc_threshold", _f32p),
                 ("num_top", C.c_uint32), ("out_logprob", _f32p), ("out_top_ids", _u32p), ("out_top_logprobs", _f32p),
                 ("window", _P), ("dry_multiplier", _f32p), ("dry_base", _f32p), ("dry_allowed_length", _u32p), ("no_repeat_ngram", _u32p),
                 ("dry_breakers", _u32p), ("num_dry_breakers", C.c_uint32),
@@ -119,6 +120,13 @@ class QueuePool(C.Structure):
 class QueueGuidance(C.Structure):
     """wrk_queue_guidance: the scales [R], the CSR negative prompts and the partners' shared prefix state of wrk_v*_generate_queue_guided."""
     _fields_ = [("scale", _f32p), ("negative_tokens", _u32p), ("negative_offsets", _u32p), ("negative_init_state", _P)]
+
+
+class QueueCuts(C.Structure):
+    """wrk_queue_cuts: the cut sampler's arrays [R] of wrk_v*_generate_queue_cut and the pool or the guidance of the call (both NULL: the
+    plain queue)."""
+    _fields_ = [("top_n_sigma", _f32p), ("epsilon_cutoff", _f32p), ("eta_cutoff", _f32p), ("xtc_probability", _f32p), ("xtc_threshold", _f32p),
+                ("pool", C.POINTER(QueuePool)), ("guide", C.POINTER(QueueGuidance))]
 
 
 class BeamOptions(C.Structure):
@@ -226,6 +234,8 @@ HIP_SYMBOLS = {
     "wrk_v6_infer": (C.c_int32, [_P, _P, _P, _u32p, C.POINTER(C.c_uint16), _u32p, C.c_uint32, _u32p, C.c_uint32, _f32p, _u32p, C.c_uint32]),
     "wrk_v6_generate_greedy": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p, _f32p, C.c_uint32]),
     "wrk_sample_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, C.c_uint32, _u32p]),
+    "wrk_sample_logits_cut": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                          _u32p, C.c_uint32, _u32p]),
     "wrk_sample_logits_filtered": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _u32p, _f32p, _u32p, C.c_uint32,
                                                _u32p]),
     "wrk_sample_logits_mirostat": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _u32p, C.c_uint32,
@@ -288,6 +298,10 @@ HIP_SYMBOLS = {
                                                  C.POINTER(QueueGuidance)]),
     "wrk_v6_generate_queue_guided": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
                                                  C.POINTER(QueueGuidance)]),
+    "wrk_v7_generate_queue_cut": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
+                                              C.POINTER(QueueCuts)]),
+    "wrk_v6_generate_queue_cut": (C.c_int32, [_P, _P, _P, C.c_uint32, C.POINTER(QueueOptions), C.POINTER(QueueResult), _f32p, C.c_uint32,
+                                              C.POINTER(QueueCuts)]),
     "wrk_v7_generate_beam": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(BeamOptions), C.POINTER(BeamResult), _f32p,
                                          C.c_uint32]),
     "wrk_v6_generate_beam": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(BeamOptions), C.POINTER(BeamResult), _f32p,
@@ -366,6 +380,23 @@ def _filters(top_k, min_p, n: int, keep: list):
     return tk, mp
 
 
+def _cuts(cuts, n: int, keep: list):
+    """The cut sampler's five per-row pointers (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc_probability, xtc_threshold; None: off) of
+    `cuts` = (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc), each a scalar or one value per row, xtc = (probability, threshold); None when
+    all four are None.  The arrays go into `keep`, which must outlive the call."""
+    if cuts is None or all(v is None for v in cuts):
+        return None
+    ns, eps, eta, xtc = cuts
+    def put(v):
+        if v is None:
+            return None
+        keep.append(_per_row(v, n, np.float32))
+        return _ptr(keep[-1], _f32p)
+    if xtc is not None and len(xtc) != 2:
+        raise ValueError("xtc = (probability, threshold)")
+    return put(ns), put(eps), put(eta), put(None if xtc is None else xtc[0]), put(None if xtc is None else xtc[1])
+
+
 def _mirostat_rows(mirostat, mirostat_mu, n: int):
     """(tau [n], eta [n], mu [n]) f32 of `mirostat` = (tau, eta), scalars or one value per row; mu: `mirostat_mu`, or 2 tau (a fresh
     sequence).  mu is a writable copy: the call returns the new values in it."""
@@ -376,17 +407,22 @@ def _mirostat_rows(mirostat, mirostat_mu, n: int):
 
 
 def _fill_pick(opt, n: int, keep: list, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-               mirostat=None, mirostat_mu=None, typical_p=None):
+               mirostat=None, mirostat_mu=None, typical_p=None, cuts=None):
     """The sampler / penalty / filter fields of a GenerateOptions or QueueOptions for n rows (scalars broadcast; seed None: seed[i] = i).
-    All of temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p None: nothing is set, the arg-max.  The arrays go into
-    `keep`, which must outlive the call.  mirostat = (tau, eta): returns the in/out mu array [n] (mirostat_mu, or 2 tau), else None."""
+    All of temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p and cuts None: nothing is set, the arg-max.  The arrays
+    go into `keep`, which must outlive the call.  mirostat = (tau, eta): returns the in/out mu array [n] (mirostat_mu, or 2 tau), else
+    None.  cuts: `_cuts`' argument; a GenerateOptions takes the five arrays, a QueueOptions has no such fields (the queue passes them in
+    a QueueCuts) and only becomes a sampled pick."""
     def put(v, dtype, ty):
         keep.append(_per_row(v, n, dtype))
         return _ptr(keep[-1], ty)
     if mirostat is None and mirostat_mu is not None:
         raise ValueError("mirostat_mu without mirostat")
-    if all(v is None for v in (temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p)):
+    cut_ptrs = _cuts(cuts, n, keep)
+    if all(v is None for v in (temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p, cut_ptrs)):
         return None
+    if cut_ptrs is not None and isinstance(opt, GenerateOptions):
+        opt.top_n_sigma, opt.epsilon_cutoff, opt.eta_cutoff, opt.xtc_probability, opt.xtc_threshold = cut_ptrs
     opt.temperature = put(1.0 if temperature is None else temperature, np.float32, _f32p)
     opt.top_p = put(0.5 if top_p is None else top_p, np.float32, _f32p)
     opt.seed = put(np.arange(n, dtype=np.uint32) if seed is None else seed, np.uint32, _u32p)
@@ -720,7 +756,8 @@ class Context:
         return Buffer(self, a.nbytes, a)
 
     def sample_logits(self, logits, temperature=1.0, top_p=0.5, seed=0, step: int = 0, num_vocab: Optional[int] = None,
-                      top_k=None, min_p=None, mirostat=None, typical_p=None):
+                      top_k=None, min_p=None, mirostat=None, typical_p=None, top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None,
+                      row_stride: Optional[int] = None):
         """`Sampler::sample` (examples/chat.rs:150-190; defaults are its `--temp 1.0 --top-p 0.5`) on the device, one token per row.
         `logits`: an [n, V] f32 array, or a `Buffer` of n rows of `num_vocab` f32; temperature / top_p / seed: scalars or per-row arrays.
         A temperature must be finite and >= 0 (+inf or NaN: WrkError E_ARG, here and in every decode loop); a NaN logit counts as -inf,
@@ -730,11 +767,18 @@ class Context:
         mirostat=(tau, eta, mu): Mirostat v2 with the target surprise tau (bits; 0: a plain row), the learning rate eta
         and the running mu (None: 2 tau, a fresh sequence), scalars or per-row arrays; returns (tokens uint32 [n], mu float32 [n]), mu
         after the draw.  typical_p (>= 1: a plain row): locally typical sampling.  One family per call; top_p is not read by a Mirostat
-        or typical row."""
+        or typical row.
+        top_n_sigma (0: off) / epsilon_cutoff (0: off) / eta_cutoff (0: off) / xtc=(probability, threshold): scalars or per-row arrays,
+        the cuts of DESIGN.md §7t next to top_k / min_p -- the tokens within top_n_sigma standard deviations of the maximum logit, those
+        of probability at least epsilon_cutoff or min(eta, sqrt(eta) exp(-entropy)), and XTC, which with the given probability drops
+        every token at or above the threshold but the least likely of them.  They share the top_k / min_p family.
+        row_stride: the floats between the rows of a `Buffer` (None: num_vocab); only the cut sampler's path takes it."""
+        stride = None
         if isinstance(logits, Buffer):
             assert num_vocab, "a Buffer needs num_vocab"
             buf, V = logits, int(num_vocab)
-            n = buf.nbytes // (4 * V)
+            stride = V if row_stride is None else int(row_stride)
+            n = buf.nbytes // (4 * stride)
         else:
             a = np.ascontiguousarray(logits, dtype=np.float32)
             a = a.reshape(1, -1) if a.ndim == 1 else a
@@ -742,8 +786,17 @@ class Context:
             buf = self.buffer(a)
         t, p, sd = _per_row(temperature, n, np.float32), _per_row(top_p, n, np.float32), _per_row(seed, n, np.uint32)
         out = np.zeros(n, np.uint32)
-        if sum(x is not None for x in (mirostat, typical_p)) + (top_k is not None or min_p is not None) > 1:
-            raise ValueError("one family per call: top_k / min_p, mirostat or typical_p")
+        cut_keep = []
+        cut_ptrs = _cuts((top_n_sigma, epsilon_cutoff, eta_cutoff, xtc), n, cut_keep)
+        if sum(x is not None for x in (mirostat, typical_p)) + (top_k is not None or min_p is not None or cut_ptrs is not None) > 1:
+            raise ValueError("one family per call: top_k / min_p and the cuts, mirostat or typical_p")
+        if cut_ptrs is not None:
+            tk, mp = _filters(top_k, min_p, n, cut_keep)
+            self.check(hip.wrk_sample_logits_cut(self.h, buf.h, V, V if stride is None else stride, n, _ptr(t, _f32p), _ptr(p, _f32p), tk, mp,
+                                                 *cut_ptrs, _ptr(sd, _u32p), step, _ptr(out, _u32p)))
+            return out
+        if stride not in (None, V):
+            raise ValueError("row_stride: only with the cut sampler's parameters")
         if mirostat is not None:
             tau, eta, mu = _mirostat_rows(mirostat[:2], mirostat[2], n)
             self.check(hip.wrk_sample_logits_mirostat(self.h, buf.h, V, V, n, _ptr(t, _f32p), _ptr(p, _f32p), _ptr(tau, _f32p), _ptr(eta, _f32p),
@@ -1777,7 +1830,7 @@ class Runtime:
     def generate_sample(self, first_tokens, steps: int, temperature=1.0, top_p=0.5, seed=None, mode: int = 1, want_logits: bool = False,
                         groups: int = 1, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
                         grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
-                        logit_bias: "LogitBias" = None, bias_set=None):
+                        logit_bias: "LogitBias" = None, bias_set=None, top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None):
         """As `generate_greedy`, each sequence's next token drawn by `Sampler::sample` (examples/chat.rs:150-190) on the device with its
         own (temperature, top_p, seed) at step t = 0..steps-1 of this call.  Scalars broadcast; seed=None: seed[b] = b.
         top_k / min_p (a scalar or one value per sequence; None: off): the draw is `sample_logits(..., top_k, min_p)`'s; such a call goes
@@ -1790,21 +1843,24 @@ class Runtime:
         options entry point and replays step programs of its own.
         grammar / grammar_state: as `generate_greedy`; the draw is the same sampler's on the masked row.
         window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`; the draw is the same sampler's on the changed row.
-        logit_bias / bias_set: as `generate_greedy`; the draw is the same sampler's on the biased row."""
+        logit_bias / bias_set: as `generate_greedy`; the draw is the same sampler's on the biased row.
+        top_n_sigma / epsilon_cutoff / eta_cutoff / xtc=(probability, threshold) (a scalar or one value per sequence; None: off): the
+        cuts of `Context.sample_logits`, made next to top_k / min_p on the row the pick sees; they share that family
+        and make the pick a sampled one."""
         if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state, window, dry,
-                                       no_repeat_ngram, dry_breakers, logit_bias, bias_set)):
+                                       no_repeat_ngram, dry_breakers, logit_bias, bias_set, top_n_sigma, epsilon_cutoff, eta_cutoff, xtc)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
                                            want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
-                                           (window, dry, no_repeat_ngram, dry_breakers), (logit_bias, bias_set))
+                                           (window, dry, no_repeat_ngram, dry_breakers), (logit_bias, bias_set), (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
         keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
         return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
 
     def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
                            want_logits, groups, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar=None,
-                           grammar_state=None, dry_args=(None, None, None, None), bias_args=(None, None)):
+                           grammar_state=None, dry_args=(None, None, None, None), bias_args=(None, None), cuts=None):
         opt, keep = GenerateOptions(), []
         mu = _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-                        mirostat, mirostat_mu, typical_p)
+                        mirostat, mirostat_mu, typical_p, cuts)
         gs = _fill_grammar(opt, _u32(first_tokens).size, keep, grammar, grammar_state)
         _fill_dry(opt, _u32(first_tokens).size, keep, *dry_args)
         _fill_bias(opt, _u32(first_tokens).size, keep, *bias_args)
@@ -1817,7 +1873,7 @@ class Runtime:
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
                            frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1, top_k=None, min_p=None,
                            logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
-                           logit_bias: "LogitBias" = None, bias_set=None):
+                           logit_bias: "LogitBias" = None, bias_set=None, top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None):
         """As `generate_sample`, each draw made on the logits penalised with the sequence's slot of `occurrence` (ChatRWKV's
         alpha_presence / alpha_frequency / token_ban), and the slot updated after every draw (count *= decay, then the drawn token's
         weight added).  The first token of a call is not counted; the last drawn one is.  The table carries over between calls.
@@ -1827,12 +1883,13 @@ class Runtime:
         penalised logits.  grammar / grammar_state: as `generate_greedy`, the mask applied to the penalised logits; bans belong in the
         grammar (a row that bans and automaton together leave empty draws an unspecified token, which the automaton rejects).
         window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`, applied to the penalised logits, before the grammar.
-        logit_bias / bias_set: as `generate_greedy`; the penalties are applied to the biased logits: a token is (x + v) - penalty."""
+        logit_bias / bias_set: as `generate_greedy`; the penalties are applied to the biased logits: a token is (x + v) - penalty.
+        top_n_sigma / epsilon_cutoff / eta_cutoff / xtc: as `generate_sample`, the cuts made on the penalised logits."""
         if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state, window, dry,
-                                       no_repeat_ngram, dry_breakers, logit_bias, bias_set)):
+                                       no_repeat_ngram, dry_breakers, logit_bias, bias_set, top_n_sigma, epsilon_cutoff, eta_cutoff, xtc)):
             return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
                                            min_p, mode, want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
-                                           (window, dry, no_repeat_ngram, dry_breakers), (logit_bias, bias_set))
+                                           (window, dry, no_repeat_ngram, dry_breakers), (logit_bias, bias_set), (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
         B = _u32(first_tokens).size
         keep, rows = self._sampler_rows(B, temperature, top_p, seed)
         pen = [_per_row(v, B, np.float32) for v in (presence, frequency, decay)]
@@ -1843,7 +1900,7 @@ class Runtime:
                       presence=0.0, frequency=0.0, decay=1.0, mode: int = 1, want_logits: bool = False, groups: int = 1,
                       poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None,
                       grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, stop_tail=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
-                      logit_bias: "LogitBias" = None, bias_set=None):
+                      logit_bias: "LogitBias" = None, bias_set=None, top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None):
         """`generate_greedy` (no temperature / top_p), `generate_sample`, or with `occurrence` `generate_penalized`, each sequence ending
         at the step that draws one of its stop ids.  stop: one list of ids for all sequences, or one list per sequence (at most
         MAX_STOP_TOKENS each; empty: never ends).  Returns (tokens [steps_run, B], lengths [B][, last logits [B, V]]): tokens[:lengths[b], b]
@@ -1865,7 +1922,8 @@ class Runtime:
         Both are None after a call without stop_sequences, which runs exactly the step programs it ran before.
         window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`; slot b of the window has taken exactly lengths[b] pushes,
         the stop token's included: the window freezes with the sequence.
-        logit_bias / bias_set: as `generate_greedy`; the tokens are a prefix of those of the call without stops."""
+        logit_bias / bias_set: as `generate_greedy`; the tokens are a prefix of those of the call without stops.
+        top_n_sigma / epsilon_cutoff / eta_cutoff / xtc: as `generate_sample` (they make the pick a sampled one)."""
         ft = _u32(first_tokens)
         ids, off = _stop_csr(stop, ft.size, "sequences")
         opt, keep = GenerateOptions(), []
@@ -1877,7 +1935,7 @@ class Runtime:
             self.last_stop_tail = _stop_tails(stop_tail, ft.size)
             opt.stop_tail = _ptr(self.last_stop_tail, _u32p)
         self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-                                           mirostat, mirostat_mu, typical_p)
+                                           mirostat, mirostat_mu, typical_p, (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
         self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
         _fill_dry(opt, ft.size, keep, window, dry, no_repeat_ngram, dry_breakers)
         _fill_bias(opt, ft.size, keep, logit_bias, bias_set)
@@ -1892,7 +1950,7 @@ class Runtime:
                         want_logits: bool = False, poll_steps: int = 0, top_k=None, min_p=None, logprobs=None, mirostat=None,
                         mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, stop_tail=None,
                         window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None, logit_bias: "LogitBias" = None,
-                        bias_set=None):
+                        bias_set=None, top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None):
         """`generate_stop` with classifier-free guidance (a negative prompt).  B = len(first_tokens) sequences run on state
         slots [0, B), and sequence b has a partner on slot B + b, which the caller has fed the negative prompt (`infer` on slots
         [B, 2B)): the state needs 2B slots.  Every step runs both, and the pick of b is made on `Context.guide_logits` of their two
@@ -1914,7 +1972,7 @@ class Runtime:
             self.last_stop_tail = _stop_tails(stop_tail, ft.size)
             opt.stop_tail = _ptr(self.last_stop_tail, _u32p)
         self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-                                           mirostat, mirostat_mu, typical_p)
+                                           mirostat, mirostat_mu, typical_p, (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
         self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
         _fill_dry(opt, ft.size, keep, window, dry, no_repeat_ngram, dry_breakers)
         _fill_bias(opt, ft.size, keep, logit_bias, bias_set)
@@ -1929,7 +1987,7 @@ class Runtime:
                        mode: int = 1, top_k=None, min_p=None, pool: "StatePool" = None, start_state=None, save_state=None, logprobs=None,
                        mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None, grammar_state=None, stop_sequences=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
                        count_prompt=None, history: "HistoryPool" = None, logit_bias: "LogitBias" = None, bias_set=None,
-                       guidance_scale=None):
+                       guidance_scale=None, top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None):
         """Serves `requests` (one non-empty list of prompt tokens each) on the state's slots in one call: a slot whose request ends is
         reset on the device (to zeros, or to the shared prefix state `init_state` from `state_read`) and takes the next request in the
         same step.  Request r feeds its prompt at decode rate, then draws at most max_new[r] reply tokens, ending at the first one in
@@ -1972,7 +2030,11 @@ class Runtime:
         request r's rows are biased with set bias_set[r] from the step it is dispatched, whatever its slot's previous request used, so
         two requests of one call may ban different tokens.  The bias is not part of a pool entry.
         guidance_scale: the queue's guidance_scale field; guidance is not built for the queue: anything but None is
-        refused with WRK_E_UNSUPPORTED.  Guided requests go through `generate_queue_guided`, guided sequences through `generate_guided`."""
+        refused with WRK_E_UNSUPPORTED.  Guided requests go through `generate_queue_guided`, guided sequences through `generate_guided`.
+        top_n_sigma / epsilon_cutoff / eta_cutoff / xtc=(probability, threshold): per request (scalars broadcast), as `generate_sample`;
+        the dispatch writes request r's values into its slot's row, and XTC's coin for reply token j is a function of (seed[r], j) alone,
+        so a reply does not depend on when or where its request ran.  Such a call goes through wrk_v*_generate_queue_cut, which takes
+        the arrays beside the options, and replays step programs of its own."""
         args = dict(locals())
         del args["self"]
         return self._queue(None, **args)
@@ -1982,7 +2044,7 @@ class Runtime:
                               decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0, mode: int = 1, top_k=None,
                               min_p=None, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar: "Grammar" = None,
                               grammar_state=None, stop_sequences=None, window: "TokenWindow" = None, dry=None, no_repeat_ngram=None,
-                              dry_breakers=None, count_prompt=None, logit_bias: "LogitBias" = None, bias_set=None, num_slots=None):
+                              dry_breakers=None, count_prompt=None, logit_bias: "LogitBias" = None, bias_set=None, num_slots=None, top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None):
         """`generate_queue` with classifier-free guidance per request: request r brings the negative prompt
         negative_prompts[r] (None or []: none, an unguided request, only with scale 1) and guidance_scale[r] (a scalar or one value per
         request, finite and >= 0).  The queue has B = num_slots request slots (None: half the state's slots), each a pair of state
@@ -2002,9 +2064,11 @@ class Runtime:
 
     def _queue(self, guide, requests, stop, max_new, temperature, top_p, seed, occurrence, presence, frequency, decay, init_state, max_steps,
                poll_steps, mode, top_k, min_p, pool, start_state, save_state, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
-               stop_sequences, window, dry, no_repeat_ngram, dry_breakers, count_prompt, history, logit_bias, bias_set, guidance_scale):
+               stop_sequences, window, dry, no_repeat_ngram, dry_breakers, count_prompt, history, logit_bias, bias_set, guidance_scale,
+               top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None):
         """wrk_v*_generate_queue / _queue_pool / _queue_guided on the arguments of `generate_queue`; guide: None, or (negative_prompts,
-        guidance_scale, negative_init_state, num_slots) of `generate_queue_guided`."""
+        guidance_scale, negative_init_state, num_slots) of `generate_queue_guided`.  With any of the cut arguments the same call goes
+        through wrk_v*_generate_queue_cut with the pool or the guidance in its QueueCuts."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -2021,7 +2085,8 @@ class Runtime:
         opt.stop_tokens, opt.stop_offsets = _ptr(ids, _u32p), _ptr(soff, _u32p)
         keep = []
         self.last_mirostat_mu = _fill_pick(opt, R, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-                                           mirostat, mirostat_mu, typical_p)
+                                           mirostat, mirostat_mu, typical_p, (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
+        cut_ptrs = _cuts((top_n_sigma, epsilon_cutoff, eta_cutoff, xtc), R, keep)
         self.last_grammar_state = _fill_grammar(opt, R, keep, grammar, grammar_state)
         _fill_dry(opt, R, keep, window, dry, no_repeat_ngram, dry_breakers)
         _fill_bias(opt, R, keep, logit_bias, bias_set)
@@ -2060,9 +2125,22 @@ class Runtime:
         if logprobs is not None:
             lp, top_ids, tlp = _logprob_arrays(logprobs, int(mn.sum()))     # `ids` stays alive: opt.stop_tokens points into it
             opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(top_ids, _u32p), _ptr(tlp, _f32p)
+        cut_fn = None
+        if cut_ptrs is not None:
+            cut_fn, mdl = self._entry("generate_queue_cut")
         if guide is not None:
-            fn, mdl = self._entry("generate_queue_guided")
-            self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qg)))
+            if cut_fn:
+                qc = QueueCuts(*cut_ptrs, None, C.pointer(qg))
+                self.ctx.check(cut_fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qc)))
+            else:
+                fn, mdl = self._entry("generate_queue_guided")
+                self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qg)))
+            self.last_queue_saved = None
+        elif pool is None and cut_fn:
+            if start_state is not None or save_state is not None:
+                raise ValueError("start_state / save_state need a pool")
+            qc = QueueCuts(*cut_ptrs, None, None)
+            self.ctx.check(cut_fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qc)))
             self.last_queue_saved = None
         elif pool is None:
             if start_state is not None or save_state is not None:
@@ -2079,8 +2157,12 @@ class Runtime:
                 return _u32([QUEUE_NO_ENTRY if k is None else int(k) for k in v]) if R else np.zeros(1, np.uint32)
             st, sv, saved = entries(start_state), entries(save_state), np.zeros(max(R, 1), np.uint32)
             qp = QueuePool(pool.buf.h, pool.entries, _ptr(st, _u32p), _ptr(sv, _u32p), _ptr(saved, _u32p))
-            fn, mdl = self._entry("generate_queue_pool")
-            self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qp)))
+            if cut_fn:
+                qc = QueueCuts(*cut_ptrs, C.pointer(qp), None)
+                self.ctx.check(cut_fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qc)))
+            else:
+                fn, mdl = self._entry("generate_queue_pool")
+                self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qp)))
             self.last_queue_saved = [bool(x) for x in saved[:R]]
         self.last_queue_ms = ms.value
         if match is not None:
