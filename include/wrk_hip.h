@@ -1025,7 +1025,8 @@ int32_t wrk_v7_generate_queue_cut(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_stat
  * its last token: the next turn's prompt begins with that token.  The contents of DEAD slots are unspecified.
  * Composition.  `gen` (may be NULL) carries what the call shares with wrk_generate_options: stop_tokens / stop_offsets, bias / bias_set
  * (one set word per group; NULL: set 0) and poll_steps.  Every other field of it must be NULL / 0: a call that passes a sampler,
- * penalties, DRY, a grammar, stop sequences or log-probs is refused, as is one with lanes (bits 8-15 of mode above 1).  W = 1 is greedy
+ * penalties, DRY, a grammar, stop sequences or log-probs is refused, as is one with lanes (bits 8-15 of mode above 1); penalties, DRY
+ * and a grammar per hypothesis come through wrk_v7_generate_beam_context below.  W = 1 is greedy
  * decoding with a score.  WRK_E_ARG before any launch: a NULL opt / out or a NULL required array (every array of wrk_beam_result but
  * the three step arrays), num_beams outside [1, WRK_MAX_BEAMS], G * W above the state's num_batch or above 256, a length_penalty that
  * is negative, infinite or NaN or so large that inv_norm[steps] is not a normal number, a first token or stop id >= num_vocab, steps
@@ -1051,6 +1052,53 @@ typedef struct wrk_beam_result {
 } wrk_beam_result;
 int32_t wrk_v7_generate_beam(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
                              uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null, uint32_t mode);
+/* Beam search with a context per hypothesis (Hugging Face's no_repeat_ngram_size and repetition_penalty under num_beams, constrained beam
+ * search): wrk_v7_generate_beam with one more argument.  A wrk_beam_context holds any subset of: an occurrence table with presence /
+ * frequency / decay (decay NULL: 1), a token window with the dry_* / no_repeat_ngram arrays and the breakers, a grammar with start
+ * states.  Every array holds one value per group [G], as bias_set does; table and window have at least G * W slots, slot q of the call
+ * using slot q of each.
+ * Start.  Slot gW carries the caller's context -- what wrk_occurrence_add / _ban and wrk_token_window_add left in slot gW of the table
+ * and the window, and grammar_state[g] -- and the context rows of the group's other slots are overwritten, as their states are.
+ * One step, on the row the pick would see and in the order of the other loops' chain:
+ *   a. The row of slot b: head output -> bias -> penalties with slot b's occurrence row -> DRY / n-gram ban with slot b's window ->
+ *      grammar mask with slot b's automaton state: bit for bit what wrk_penalize_logits, wrk_dry_logits and wrk_constrain_logits give.
+ *   b. Steps 1 - 6 above run on that row, so scores are sums of log-probs under the modified row.  A LIVE slot whose row has no finite
+ *      log-prob gives no candidate and dies.
+ *   c. The context follows the hypothesis: for every slot q that step 5 gives the state of another slot p, slot q's occurrence row
+ *      (counts and both flag bits: bans follow the hypothesis), window (ring and the two meta words) and automaton state become slot
+ *      p's of before the step.  Every source is read before any destination is written (swaps, chains, broadcasts); other slots move no
+ *      bytes.
+ *   d. Every slot filled in the step (step_tokens is not WRK_BEAM_NO_TOKEN; LIVE or DONE) then counts the token it was given in its own
+ *      context: the occurrence update with the group's decay, the automaton advance, the window push.  Two children of one parent each
+ *      count only their own token.  Slots not filled (a staying DONE slot, a DEAD one) are not touched, so a DONE slot keeps the context
+ *      it ended with and needs no snapshot.
+ * End.  Slot slots[g * W + r] holds that hypothesis's context beside its state; the context has the last token counted, which the state
+ * has not consumed (as wrk_v7_generate_stop leaves a sequence).  out_grammar_state (may be NULL) [B]: the automaton state per slot.
+ * WRK_E_ARG before any launch, as wrk_generate_options: arrays without their table, window or grammar; a table, window or grammar of
+ * another context or vocabulary; fewer than G * W slots; values out of range; a start state >= num_states.  What `gen` refuses in
+ * wrk_v7_generate_beam it refuses here: samplers, stop sequences, log-prob rows, guidance, lanes -- and penalty, DRY or grammar fields
+ * in `gen` itself.  ctx NULL or all-empty: wrk_v7_generate_beam, the same programs and bits.  num_beams = 1: the greedy call with the
+ * same context.  Context calls replay step programs of their own (the kinds' key bits). */
+typedef struct wrk_beam_context {
+    wrk_occurrence* occ;
+    const float *presence, *frequency, *decay;
+    wrk_token_window* window;
+    const float *dry_multiplier, *dry_base;
+    const uint32_t *dry_allowed_length, *no_repeat_ngram, *dry_breakers;
+    uint32_t num_dry_breakers;
+    const wrk_grammar* grammar;
+    const uint32_t* grammar_state;
+    uint32_t* out_grammar_state;
+} wrk_beam_context;
+int32_t wrk_v7_generate_beam_context(wrk_ctx* ctx, wrk_v7_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
+                                     uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null,
+                                     uint32_t mode, const wrk_beam_context* context);
+/* The context's half of wrk_v7_state_permute, for a host-driven loop (wrk_beam_step + wrk_v7_state_permute + these): slot q of the table
+ * / the window <- slot parents[q] for q in [0, n) -- counts and flags / ring and meta -- every slot read before any is written.  Slots
+ * with parents[q] == q move no bytes and slots >= n are untouched.  parents: host u32 [n], each < n; n <= num_batch (else WRK_E_ARG).
+ * Blocking. */
+int32_t wrk_occurrence_permute(wrk_ctx* ctx, wrk_occurrence* occ, const uint32_t* parents, uint32_t n);
+int32_t wrk_token_window_permute(wrk_ctx* ctx, wrk_token_window* window, const uint32_t* parents, uint32_t n);
 /* One beam step on rows of f32 logits, for a host-driven loop: steps 1 - 5 above on logits [num_groups * num_beams][row_stride] (first
  * num_vocab used; a caller with a bias applies wrk_bias_logits first).  scores / keys (host f32) and lengths / status (host u32), all
  * [B], in/out: the slot records; stop_tokens / stop_offsets: the groups' stop sets (both NULL: none).  Out, host u32 [B]: out_tokens
@@ -1147,6 +1195,10 @@ int32_t wrk_v6_generate_queue_cut(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_stat
 /* as wrk_v7_generate_beam */
 int32_t wrk_v6_generate_beam(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
                              uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null, uint32_t mode);
+/* as wrk_v7_generate_beam_context */
+int32_t wrk_v6_generate_beam_context(wrk_ctx* ctx, wrk_v6_model* model, wrk_v7_state* state, const uint32_t* first_tokens, uint32_t num_groups,
+                                     uint32_t steps, const wrk_beam_options* opt, const wrk_beam_result* out, float* elapsed_ms_or_null,
+                                     uint32_t mode, const wrk_beam_context* context);
 
 /* Parity instrumentation, as wrk_v7_infer_layer / wrk_v7_frame_read (RWKV-6 has no layer-0 value to carry):
  *   wrk_v6_infer_layer: run ONLY `layer` of a job on a caller-supplied layer input x (f16 [D, num_token]) and the state as it stands;

@@ -48,7 +48,9 @@ with the run-to-run spread of each.  Every call starts from the same state.
 
 A twelfth leg (--beam W): generate_beam with W beams per group on the B slots (B / W groups, --beam-length-penalty, no stop set, so every
 step runs) against generate_greedy on the same B slots, alternating, with the run-to-run spread of each, and next to them
-the bytes the slot permutation may move per step and moved on average.  Every call starts from the same states.
+the bytes the slot permutation may move per step and moved on average.  Every call starts from the same states.  With --beam-ngram N,
+--beam-penalty P,F or --beam-grammar each of those contexts per hypothesis is timed too, the context loop against the
+same beam loop without a context, alternating, with the spread of each.
 
 A thirteenth leg (--guidance S): generate_guided of B sequences with scale S and the plain-sampler pick (B conditional
 slots and B partner slots, so the runtime gets 2B slots) against the plain sampled loop of the options entry point on the same 2B slots,
@@ -59,7 +61,8 @@ invocations of the same kind only.
 
     python tools/sample_bench.py [--batches 1,16,32] [--steps 64] [--reps 7] [--no-penalized] [--stop] [--poll 4,8,16,32,64]
                                  [--top-k 40] [--min-p 0.05] [--logprobs 0,5,20] [--mirostat 5,0.1] [--typical 0.9] [--grammar] [--stop-seq]
-                                 [--dry] [--logit-bias 64] [--beam 4] [--guidance 1.5]
+                                 [--dry] [--logit-bias 64] [--beam 4 [--beam-ngram 3] [--beam-penalty 0.5,0.5] [--beam-grammar]]
+                                 [--guidance 1.5]
 
 Prints one JSON object.
 """
@@ -514,6 +517,57 @@ def beam_leg(rt, first, B, V, args):
             "permute_bytes_read_and_written_per_step_mean": round(2 * 2 * slot_bytes * moved / args.steps)}
 
 
+def beam_context_legs(rt, ctx, first, B, V, args):
+    """Medians of the per-step time of generate_beam with a context per hypothesis -- --beam-ngram N: a token window and
+    no_repeat_ngram = N; --beam-penalty P,F: an occurrence table with presence P, frequency F, decay 0.99; --beam-grammar: the two-state
+    automaton of the grammar leg -- each against the same beam loop without a context, alternating in one process; every call starts
+    from the same states, empty windows and zero counts."""
+    import wrk
+    W = args.beam
+    if B % W:
+        return {"skipped": f"{B} slots are not groups of {W} beams"}
+    G = B // W
+    start = [rt.state_read(b) for b in range(B)]
+    legs = {}
+    if args.beam_ngram:
+        win = wrk.TokenWindow(ctx, B, V, 1024)
+        legs[f"ngram_{args.beam_ngram}"] = (dict(window=win, no_repeat_ngram=args.beam_ngram), win)
+    if args.beam_penalty:
+        p, f = (float(x) for x in args.beam_penalty.split(","))
+        occ = wrk.Occurrence(ctx, B, V)
+        legs[f"penalty_{p}_{f}"] = (dict(occurrence=occ, presence=p, frequency=f, decay=0.99), occ)
+    if args.beam_grammar:
+        trans = np.array([[0, 1, wrk.GRAMMAR_REJECT, wrk.GRAMMAR_REJECT], [wrk.GRAMMAR_REJECT, wrk.GRAMMAR_REJECT, 0, 1]], np.uint16)
+        g = wrk.Grammar(ctx, V, (np.arange(V) % 4).astype(np.uint16), trans)
+        legs["grammar"] = (dict(grammar=g, grammar_state=0), g)
+
+    def run(kw, table):
+        for b in range(B):
+            rt.state_write(start[b], b)
+            if isinstance(table, (wrk.TokenWindow, wrk.Occurrence)):
+                table.load(b)
+        res, steps = rt.generate_beam(first[:G], args.steps, W, length_penalty=args.beam_length_penalty, **kw)
+        return rt.last_beam_ms / max(steps, 1)
+    out = {}
+    for name, (kw, table) in legs.items():
+        run(kw, table)                                                      # capture and warm up
+        run({}, None)
+        cm, bm = [], []
+        for _ in range(args.reps):
+            bm.append(run({}, None))
+            cm.append(run(kw, table))
+        c_med, b_med = float(np.median(cm)), float(np.median(bm))
+        out[name] = {"context_ms_per_step": round(c_med, 5), "context_spread_us": round((max(cm) - min(cm)) * 1e3, 2),
+                     "context_ms_all": [round(x, 5) for x in cm], "beam_ms_per_step": round(b_med, 5),
+                     "beam_spread_us": round((max(bm) - min(bm)) * 1e3, 2), "beam_ms_all": [round(x, 5) for x in bm],
+                     "context_minus_beam_us": round((c_med - b_med) * 1e3, 2), "context_over_beam": round(c_med / b_med, 4)}
+        table.close()
+    for b in range(B):
+        rt.state_write(start[b], b)
+    out["context_bytes_per_slot"] = V * 5 + 1024 * 4 + 12
+    return out
+
+
 def guide_leg(rt, first, B, V, args):
     """Medians of the per-step time of generate_guided with B guided sequences (scale args.guidance, sampled pick) against the plain sampled
     loop of generate_stop on the same 2B slots, alternating in one process; every call starts from the same states and feeds the same
@@ -581,6 +635,9 @@ def main():
     ap.add_argument("--logit-bias", type=int, default=None, help="entries per set: the loop with a logit bias against the same loop without")
     ap.add_argument("--beam", type=int, default=None, help="beams per group: generate_beam against generate_greedy on the same slots")
     ap.add_argument("--beam-length-penalty", type=float, default=1.0)
+    ap.add_argument("--beam-ngram", type=int, default=None, help="with --beam: the beam loop with no_repeat_ngram = N against the loop without")
+    ap.add_argument("--beam-penalty", default=None, help="with --beam: P,F -- presence and frequency per hypothesis (decay 0.99)")
+    ap.add_argument("--beam-grammar", action="store_true", help="with --beam: a two-state automaton per hypothesis")
     ap.add_argument("--guidance", type=float, default=None,
                     help="scale: generate_guided of B sequences against the plain sampled loop on the same 2B slots")
     args = ap.parse_args()
@@ -689,6 +746,11 @@ def main():
                                 "launches: the two of the candidate front (wrk_top_logprobs' kernels), beam_select, and the gather and the "
                                 "scatter of the slot permutation; the snapshot launch returns at once when no slot ended")
             out["batches"][-1]["beam"] = beam_leg(rt, first, B, V, args)
+            if args.beam_ngram or args.beam_penalty or args.beam_grammar:
+                out["beam_context_note"] = ("a context step adds to the beam step the row launches of its stages in front of the candidate "
+                                            "front, the gather and the scatter of the context permutation, and one gated update launch "
+                                            "per stage")
+                out["batches"][-1]["beam_context"] = beam_context_legs(rt, ctx, first, B, V, args)
         if args.guidance is not None:
             out["guidance_note"] = ("B guided sequences on 2B slots against the plain sampled loop of 2B sequences; a guided step adds two "
                                     "launches to that step: guide_rows in front of the pick and guide_follow in front of the advance, and "

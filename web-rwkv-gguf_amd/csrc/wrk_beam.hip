@@ -13,6 +13,9 @@
 //   beam_permute     state slot q <- state slot map[q] under any aliasing: two beam_copy launches through a scratch.  The gather only
 //                    reads the state and only writes the scratch, the scatter only reads the scratch and only writes the state, and the
 //                    stream orders the two: no slot is written before every slot has been read
+//   beam_context     grid (slice, slot): the same gather and scatter for what a hypothesis carries beside its state -- its
+//                    occurrence row, token window and automaton state -- through a scratch of context rows.  Slice x moves elements
+//                    [1024 x, 1024 (x + 1)) of the counts, the flags and the ring; slice 0's first thread also the meta and state words
 // Plain vector stores only; no atomics; no kernel waits on another.
 #include "wrk_rows_dev.h"
 #include "wrk_runner.h"
@@ -89,6 +92,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) beam_select_kernel(const BeamBuf
             Q.copy_src[q] = (t != WRK_BEAM_NO_TOKEN && p != lane) ? g * w + p : WRK_BEAM_NO_COPY;
             Q.snap_map[q] = sm_end[wid][lane] ? q : WRK_BEAM_NO_COPY;
             Q.done_map[q] = o.status == WRK_BEAM_DONE ? q : WRK_BEAM_NO_COPY;
+            Q.filled[q] = t != WRK_BEAM_NO_TOKEN ? 1u : 0u;
             now_live = o.status == WRK_BEAM_LIVE;
         }
         live += (uint32_t)__popcll(__ballot(now_live));
@@ -125,6 +129,87 @@ __global__ void __launch_bounds__(BEAM_THREADS) beam_copy_kernel(const BeamCopyA
             *(f32x4*)(dst + i) = *(const f32x4*)(src + i);
     } else {
         for (size_t i = (size_t)part * BEAM_THREADS + threadIdx.x; i < A.slot; i += (size_t)A.slices * BEAM_THREADS) dst[i] = src[i];
+    }
+}
+
+// one direction of the context permutation: SCATTER false -- scratch row q <- slot map[q]; true -- slot q <- scratch row q
+struct BeamCtxArgs {
+    BeamCtxRows rows; BeamCtxScratch tmp;
+    const uint32_t* map;
+    uint32_t v;
+};
+
+template <bool VEC, bool SCATTER>
+__global__ void __launch_bounds__(BEAM_THREADS) beam_context_kernel(const BeamCtxArgs A) {
+    const uint32_t q = blockIdx.y;
+    const uint32_t m = A.map[q];
+    if (m == WRK_BEAM_NO_COPY) return;
+    const uint32_t tid = threadIdx.x, base = blockIdx.x * BEAM_CHUNK, v = A.v;
+    const uint32_t slot = SCATTER ? q : m;      // the table's side of the move; the scratch's side is row q
+    if (A.rows.pen && base < v) {
+        const PenaltyParam p = A.rows.pen[slot];
+        float* tc = A.tmp.count + (size_t)q * v;
+        uint8_t* tf = A.tmp.flags + (size_t)q * v;
+        if (VEC) {
+            const uint32_t i = base + tid * 4;
+            if (i < v) {
+                if (SCATTER) { *(f32x4*)(p.count + i) = *(const f32x4*)(tc + i); *(uint32_t*)(p.flags + i) = *(const uint32_t*)(tf + i); }
+                else { *(f32x4*)(tc + i) = *(const f32x4*)(p.count + i); *(uint32_t*)(tf + i) = *(const uint32_t*)(p.flags + i); }
+            }
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t i = base + j * BEAM_THREADS + tid;
+                if (i >= v) continue;
+                if (SCATTER) { p.count[i] = tc[i]; p.flags[i] = tf[i]; }
+                else { tc[i] = p.count[i]; tf[i] = p.flags[i]; }
+            }
+        }
+    }
+    if (A.rows.dry) {
+        const DryParam* p = A.rows.dry + slot;
+        const uint32_t cap = p->cap;            // every slot of a call has the one window's capacity; the scratch rows are that long
+        uint32_t* ring = p->ring;
+        uint32_t* tr = A.tmp.ring + (size_t)q * cap;
+        if (base < cap) {
+            if ((cap & 3u) == 0) {
+                const uint32_t i = base + tid * 4;
+                if (i < cap) {
+                    if (SCATTER) *(u32x4*)(ring + i) = *(const u32x4*)(tr + i);
+                    else *(u32x4*)(tr + i) = *(const u32x4*)(ring + i);
+                }
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint32_t i = base + j * BEAM_THREADS + tid;
+                    if (i >= cap) continue;
+                    if (SCATTER) ring[i] = tr[i]; else tr[i] = ring[i];
+                }
+            }
+        }
+        if (blockIdx.x == 0 && tid == 0) {
+            uint32_t* tm = A.tmp.meta + (size_t)q * 2;
+            if (SCATTER) { p->meta[0] = tm[0]; p->meta[1] = tm[1]; }
+            else { tm[0] = p->meta[0]; tm[1] = p->meta[1]; }
+        }
+    }
+    if (A.rows.gram && blockIdx.x == 0 && tid == 0) {
+        if (SCATTER) A.rows.gram[q] = A.tmp.gram[q];
+        else A.tmp.gram[q] = A.rows.gram[m];
+    }
+}
+
+void beam_context_permute(hipStream_t s, const BeamCtxRows& rows, const BeamCtxScratch& scratch, uint32_t v, const uint32_t* map, uint32_t n) {
+    if (n == 0 || (!rows.pen && !rows.dry && !rows.gram)) return;
+    const BeamCtxArgs A{rows, scratch, map, v};
+    const uint32_t longest = std::max(rows.pen ? v : 1u, rows.dry ? (uint32_t)WRK_MAX_TOKEN_WINDOW : 1u);
+    const dim3 grid((longest + BEAM_CHUNK - 1) / BEAM_CHUNK, n);
+    if (v % 4 == 0) {
+        beam_context_kernel<true, false><<<grid, BEAM_THREADS, 0, s>>>(A);
+        beam_context_kernel<true, true><<<grid, BEAM_THREADS, 0, s>>>(A);
+    } else {
+        beam_context_kernel<false, false><<<grid, BEAM_THREADS, 0, s>>>(A);
+        beam_context_kernel<false, true><<<grid, BEAM_THREADS, 0, s>>>(A);
     }
 }
 
@@ -218,7 +303,7 @@ extern "C" int32_t wrk_beam_step(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V
     const size_t o_par = dev.add(sizeof(wrk::BeamParam)), o_lpar = dev.add(sizeof(wrk::LogprobParam)), o_slots = dev.add((size_t)B * sizeof(wrk::BeamSlot));
     const size_t o_stops = dev.add((size_t)G * sizeof(wrk::BeamStop)), o_inv = dev.add(inv.size() * 4), o_ids = dev.add((size_t)B * W * 4);
     const size_t o_lp = dev.add((size_t)B * W * 4), o_chosen = dev.add((size_t)B * 4), o_part = dev.add(wrk::logprob_part_bytes(B));
-    const size_t o_keys = dev.add(wrk::logprob_key_bytes(B)), o_hist = dev.add((size_t)3 * B * 4), o_maps = dev.add((size_t)3 * B * 4);
+    const size_t o_keys = dev.add(wrk::logprob_key_bytes(B)), o_hist = dev.add((size_t)3 * B * 4), o_maps = dev.add((size_t)4 * B * 4);
     const size_t o_words = dev.add(8), o_tok = dev.add((size_t)2 * B * 4);
     WRK_HIP(ctx, dev.alloc());
     const wrk::BeamParam par{W, G, 1u, (uint32_t)inv.size()};
@@ -228,7 +313,7 @@ extern "C" int32_t wrk_beam_step(wrk_ctx* ctx, const wrk_buf* logits, uint32_t V
     uint32_t* words = dev.at<uint32_t>(o_words);        // the LIVE count, the step counter
     uint32_t* tok = dev.at<uint32_t>(o_tok);            // [B] zeros: the chosen tokens of the front; [B] the tokens the slots feed
     const wrk::BeamBufs Q{dev.at<wrk::BeamParam>(o_par), dev.at<wrk::BeamSlot>(o_slots), dev.at<wrk::BeamStop>(o_stops), dev.at<float>(o_inv),
-                          lpar.top_ids, lpar.top_logprobs, hist, hist + B, (float*)(hist + 2 * B), maps, maps + B, maps + 2 * B, words};
+                          lpar.top_ids, lpar.top_logprobs, hist, hist + B, (float*)(hist + 2 * B), maps, maps + B, maps + 2 * B, words, maps + 3 * B};
     WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_par), &par, sizeof par, hipMemcpyHostToDevice, ctx->stream));
     WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_lpar), &lpar, sizeof lpar, hipMemcpyHostToDevice, ctx->stream));
     WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_slots), slots.data(), (size_t)B * sizeof(wrk::BeamSlot), hipMemcpyHostToDevice, ctx->stream));
@@ -273,6 +358,78 @@ extern "C" int32_t wrk_v7_state_permute(wrk_ctx* ctx, wrk_v7_state* st, const ui
     WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_map), map.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     wrk::beam_permute(ctx->stream, wrk::BeamSlots{st->data, st->num_batch, 0u}, dev.at<float>(o_tmp), st->num_layer, slot, dev.at<uint32_t>(o_map), n,
                       ctx->num_cu);
+    WRK_LAUNCH_CHECK(ctx);
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+// parents of wrk_occurrence_permute / wrk_token_window_permute validated into a copy list (WRK_E_ARG as wrk_v7_state_permute); *any:
+// whether a slot moves at all
+static int32_t beam_parents_map(wrk_ctx* ctx, const uint32_t* parents, uint32_t n, uint32_t num_batch, const char* who, std::vector<uint32_t>& map, bool* any) {
+    WRK_ARG(ctx, !ctx->capturing_here(), "%s is blocking: not inside a capture", who);
+    WRK_ARG(ctx, n <= num_batch, "%u slots, %s has %u", n, who, num_batch);
+    *any = false;
+    if (n == 0) return WRK_OK;
+    WRK_ARG(ctx, parents, "parents is required");
+    map.resize(n);
+    for (uint32_t q = 0; q < n; ++q) {
+        WRK_ARG(ctx, parents[q] < n, "parents[%u] = %u: must be below %u", q, parents[q], n);
+        map[q] = parents[q] == q ? WRK_BEAM_NO_COPY : parents[q];
+        *any = *any || parents[q] != q;
+    }
+    return WRK_OK;
+}
+
+extern "C" int32_t wrk_occurrence_permute(wrk_ctx* ctx, wrk_occurrence* occ, const uint32_t* parents, uint32_t n) {
+    if (!ctx || !occ) return WRK_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    WRK_ARG(ctx, occ->ctx == ctx, "the occurrence table belongs to another context");
+    std::vector<uint32_t> map;
+    bool any = false;
+    const int32_t rc = beam_parents_map(ctx, parents, n, occ->num_batch, "the occurrence table", map, &any);
+    if (rc != WRK_OK || !any) return rc;
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t V = occ->num_vocab;
+    std::vector<wrk::PenaltyParam> rows(n);
+    for (uint32_t q = 0; q < n; ++q) rows[q] = occ->row(q, 0.0f, 0.0f, 1.0f);
+    wrk_dev_arena dev;
+    const size_t o_map = dev.add((size_t)n * 4), o_rows = dev.add((size_t)n * sizeof(wrk::PenaltyParam)), o_cnt = dev.add((size_t)n * V * 4),
+                 o_flg = dev.add((size_t)n * V);
+    WRK_HIP(ctx, dev.alloc());
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_map), map.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_rows), rows.data(), (size_t)n * sizeof(wrk::PenaltyParam), hipMemcpyHostToDevice, ctx->stream));
+    wrk::beam_context_permute(ctx->stream, wrk::BeamCtxRows{dev.at<wrk::PenaltyParam>(o_rows), nullptr, nullptr},
+                              wrk::BeamCtxScratch{dev.at<float>(o_cnt), dev.at<uint8_t>(o_flg), nullptr, nullptr, nullptr}, occ->num_vocab,
+                              dev.at<uint32_t>(o_map), n);
+    WRK_LAUNCH_CHECK(ctx);
+    WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return WRK_OK;
+}
+
+extern "C" int32_t wrk_token_window_permute(wrk_ctx* ctx, wrk_token_window* win, const uint32_t* parents, uint32_t n) {
+    if (!ctx || !win) return WRK_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    WRK_ARG(ctx, win->ctx == ctx, "the token window belongs to another context");
+    std::vector<uint32_t> map;
+    bool any = false;
+    const int32_t rc = beam_parents_map(ctx, parents, n, win->num_batch, "the token window", map, &any);
+    if (rc != WRK_OK || !any) return rc;
+    WRK_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<wrk::DryParam> rows(n);
+    for (uint32_t q = 0; q < n; ++q) {
+        rows[q].ring = win->ring + (size_t)q * win->capacity;
+        rows[q].meta = win->meta + (size_t)q * 2;
+        rows[q].cap = win->capacity;
+    }
+    wrk_dev_arena dev;
+    const size_t o_map = dev.add((size_t)n * 4), o_rows = dev.add((size_t)n * sizeof(wrk::DryParam)), o_ring = dev.add((size_t)n * win->capacity * 4),
+                 o_meta = dev.add((size_t)n * 8);
+    WRK_HIP(ctx, dev.alloc());
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_map), map.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    WRK_HIP(ctx, hipMemcpyAsync(dev.at<char>(o_rows), rows.data(), (size_t)n * sizeof(wrk::DryParam), hipMemcpyHostToDevice, ctx->stream));
+    wrk::beam_context_permute(ctx->stream, wrk::BeamCtxRows{nullptr, dev.at<wrk::DryParam>(o_rows), nullptr},
+                              wrk::BeamCtxScratch{nullptr, nullptr, dev.at<uint32_t>(o_ring), dev.at<uint32_t>(o_meta), nullptr}, win->num_vocab,
+                              dev.at<uint32_t>(o_map), n);
     WRK_LAUNCH_CHECK(ctx);
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WRK_OK;

@@ -367,13 +367,14 @@ void queue_history_turnover(hipStream_t s, uint32_t v, const QueueStateCtl* sctl
 // there are, so one captured program serves any W.  BeamBufs: the slot records [B], the groups' stop sets, the host's inv_norm table,
 // the candidate front's output (ids / lp [B][W]: wrk_top_logprobs' top arrays of the rows with num_top = W), the step history
 // [hist_rows][B] x 3, the step's copy list copy_src [B] (NO_COPY: the slot moves no bytes), snap_map [B] (q where slot q ended in this
-// step, else NO_COPY), done_map [B] (q where slot q is DONE, else NO_COPY) and the count of LIVE slots
+// step, else NO_COPY), done_map [B] (q where slot q is DONE, else NO_COPY), the count of LIVE slots and filled [B] (1 where the step
+// gave slot q a token, LIVE or DONE, else 0: the gate of a beam context's updates, written for every slot in every step)
 struct BeamParam { uint32_t w, groups, hist_rows, inv_len; };
 struct BeamBufs {
     const BeamParam* par; BeamSlot* slots; const BeamStop* stops; const float* inv_norm;
     const uint32_t* cand_ids; const float* cand_lp;
     uint32_t *step_tokens, *step_parents; float* step_scores;
-    uint32_t *copy_src, *snap_map, *done_map, *live;
+    uint32_t *copy_src, *snap_map, *done_map, *live, *filled;
 };
 // the candidate front and the selection of one step over rows [b][stride] (v used): logprob_rows with `lp` (num_top = W, its top arrays
 // Q.cand_ids / Q.cand_lp) on the chosen tokens lp_tokens (any ids < v), then beam_select: one workgroup, a wave per group; writes the
@@ -390,6 +391,17 @@ void beam_copy(hipStream_t s, const BeamSlots& src, const BeamSlots& dst, uint32
                uint32_t n, int num_cu);
 // state slot q <- state slot map[q] for the listed q, under any aliasing: a gather into `scratch` (n slots per layer), then the scatter
 void beam_permute(hipStream_t s, const BeamSlots& state, float* scratch, uint32_t layers, size_t slot, const uint32_t* map, uint32_t n, int num_cu);
+// A beam context: what a hypothesis carries beside its state -- its occurrence row (counts and both flag bits), its token
+// window (ring and the two meta words) and its automaton state -- found through the rows' own parameter blocks: pen[q] / dry[q] name slot
+// q's row and window (nullptr: the call has none), gram the state words [n] (nullptr: none).  BeamCtxScratch: n context rows, counts
+// [n][v], flags [n][v], rings [n][the window's capacity], meta [n][2], states [n].
+// beam_context_permute: slot q's context <- slot map[q]'s for every q < n with map[q] != WRK_BEAM_NO_COPY, under any aliasing: a gather
+// into the scratch, then the scatter, as beam_permute.  The grid is ceil(max(v, WRK_MAX_TOKEN_WINDOW) / 1024) x n whatever the map and
+// the capacity, which is data; workgroups of unlisted slots return at once.  16-byte moves of the counts (4-byte ones of the flags) when
+// v % 4 == 0 and of a ring when its capacity % 4 == 0, scalar moves otherwise
+struct BeamCtxRows { const PenaltyParam* pen; const DryParam* dry; uint32_t* gram; };
+struct BeamCtxScratch { float* count; uint8_t* flags; uint32_t* ring; uint32_t* meta; uint32_t* gram; };
+void beam_context_permute(hipStream_t s, const BeamCtxRows& rows, const BeamCtxScratch& scratch, uint32_t v, const uint32_t* map, uint32_t n);
 
 // WRK_TIMING=1 (debug): in-kernel wall-clock stamps of one decode layer, printed after wrk_v7_generate_greedy
 unsigned long long* timing_slot(wrk_ctx* ctx, const char* label);   // nullptr unless enabled

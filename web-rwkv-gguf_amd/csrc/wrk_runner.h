@@ -341,7 +341,7 @@ struct wrk_beam_bufs {
     wrk::LogprobParam* lp_par = nullptr;
     wrk::BeamSlot* slots = nullptr;
     wrk::BeamStop* stops = nullptr;
-    uint32_t *cand_ids = nullptr, *copy_src = nullptr, *snap_map = nullptr, *done_map = nullptr, *live = nullptr;
+    uint32_t *cand_ids = nullptr, *copy_src = nullptr, *snap_map = nullptr, *done_map = nullptr, *live = nullptr, *filled = nullptr;
     float *cand_lp = nullptr, *chosen_lp = nullptr;
     wrk::LogprobPart* part = nullptr;
     unsigned long long* keys = nullptr;
@@ -353,11 +353,25 @@ struct wrk_beam_bufs {
         c.take(copy_src, d[0] * 4); c.take(snap_map, d[0] * 4); c.take(done_map, d[0] * 4); c.take(live, 4); c.take(chosen_lp, d[0] * 4);
         c.take(part, wrk::logprob_part_bytes((uint32_t)d[0])); c.take(keys, wrk::logprob_key_bytes((uint32_t)d[0]));
         c.take(step_tokens, d[1] * 4); c.take(step_parents, d[1] * 4); c.take(step_scores, d[1] * 4); c.take(inv_norm, d[2] * 4);
-        c.take(scratch, d[0] * d[3] * 4); c.take(snap, d[0] * d[3] * 4);
+        c.take(scratch, d[0] * d[3] * 4); c.take(snap, d[0] * d[3] * 4); c.take(filled, d[0] * 4);
     }
     wrk::BeamBufs dev() const {
-        return wrk::BeamBufs{par, slots, stops, inv_norm, cand_ids, cand_lp, step_tokens, step_parents, step_scores, copy_src, snap_map, done_map, live};
+        return wrk::BeamBufs{par, slots, stops, inv_norm, cand_ids, cand_lp, step_tokens, step_parents, step_scores, copy_src, snap_map, done_map, live, filled};
     }
+};
+// a beam call with a context (wrk_beam.hip): the scratch of context rows that beam_context_permute gathers into -- counts
+// and flags [slots][vocabulary], rings [slots][capacity], meta [slots][2], automaton states [slots].  A call without an occurrence table
+// asks for vocabulary 0, one without a window for capacity 0
+struct wrk_beam_ctx_bufs {
+    static constexpr int DIMS = 3;              // slots, vocabulary, window capacity
+    static constexpr unsigned EXACT = 0;
+    float* count = nullptr;
+    uint8_t* flags = nullptr;
+    uint32_t *ring = nullptr, *meta = nullptr, *gram = nullptr;
+    void layout(wrk_dev_cut& c, const size_t* d) {
+        c.take(count, d[0] * d[1] * 4); c.take(flags, d[0] * d[1]); c.take(ring, d[0] * d[2] * 4); c.take(meta, d[0] * 2 * 4); c.take(gram, d[0] * 4);
+    }
+    wrk::BeamCtxScratch dev() const { return wrk::BeamCtxScratch{count, flags, ring, meta, gram}; }
 };
 
 // ------------------------------------------------------------------ frame state of a model (base of wrk_v7_model / wrk_v6_model)
@@ -408,9 +422,10 @@ struct wrk_frame_common {
     wrk_dev_group<wrk_queue_guide_bufs> queue_guide;
     wrk_dev_group<wrk_logprob_bufs> logprob;
     wrk_dev_group<wrk_beam_bufs> beam;
+    wrk_dev_group<wrk_beam_ctx_bufs> beam_ctx;
     template <class F> void each_group(F&& f) {     // the one list of the groups
         f(history); f(sample); f(filter); f(alt); f(cut_par); f(penalty); f(grammar); f(bias); f(guide); f(dry); f(score); f(stop); f(stop_seq); f(queue); f(queue_seq);
-        f(queue_states); f(queue_intake); f(queue_guide); f(logprob); f(beam);
+        f(queue_states); f(queue_intake); f(queue_guide); f(logprob); f(beam); f(beam_ctx);
     }
     uint32_t* live_host = nullptr;              // pinned: the live counts the polled loop reads, [2 blocks][lanes]
     uint32_t live_host_cap = 0;
@@ -531,6 +546,9 @@ int32_t wrk_generate_queue_cut(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* 
                                const wrk_queue_result* out_arg, float* elapsed_ms, uint32_t mode_arg, const wrk_queue_cuts* cuts);
 // wrk_v*_generate_beam (tail BEAM): the stop call's polled loop on one lane over B = G * num_beams slots with the beam tail and the count of
 // LIVE slots; after the loop the DONE slots are restored from their snapshots, the records and the history rows come back and the
-// hypotheses are backtracked through the parents on the host
+// hypotheses are backtracked through the parents on the host.  bc (wrk_v*_generate_beam_context; nullptr or empty: none): the
+// slots' contexts -- the step runs the penalise / DRY / mask launches in front of the candidate front, and behind the state permutation
+// the context permutation and the updates of the slots the step filled
 int32_t wrk_generate_beam(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t G, uint32_t steps,
-                          const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg);
+                          const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg,
+                          const wrk_beam_context* bc = nullptr);

@@ -1024,7 +1024,11 @@ struct wrk_beam_pack {
     std::vector<wrk::BeamSlot> slots;           // [B]: slot gW LIVE with score 0 and length 0, the others DEAD
     std::vector<wrk::BeamStop> stops;           // [G]
     std::vector<float> inv_norm;                // [steps + 1]
-    wrk_pick_params rows;                       // biased: the object and the slots' set words [B]
+    // biased: the object and the slots' set words [B]; with a context the slots' penalty rows, DRY rows and start states [B]
+    wrk_pick_params rows;
+    size_t ctx_vocab = 0, ctx_capacity = 0;     // what the context scratch is sized by: V with a table, the window's capacity
+    uint32_t* out_grammar_state = nullptr;      // [B], or nullptr
+    bool context() const { return !rows.pen.empty() || rows.has_dry || rows.grammar; }
 };
 
 static size_t state_slot_floats(const wrk_v7_state* st) { return (size_t)(st->head_size + 2) * st->num_emb; }
@@ -1033,7 +1037,8 @@ static size_t state_slot_floats(const wrk_v7_state* st) { return (size_t)(st->he
 // frame, the parameter blocks, the records, the stop sets and inv_norm of this call, empty maps, live = G
 static int32_t wrk_beam_prepare(wrk_frame_common& f, const wrk_v7_state* st, uint32_t B, const wrk_beam_pack& pk) {
     wrk_ctx* ctx = f.ctx;
-    const int32_t rc = f.grow(f.beam, {B, (size_t)pk.steps * B, pk.inv_norm.size(), (size_t)st->num_layer * state_slot_floats(st)});
+    int32_t rc = f.grow(f.beam, {B, (size_t)pk.steps * B, pk.inv_norm.size(), (size_t)st->num_layer * state_slot_floats(st)});
+    if (rc == WRK_OK && pk.context()) rc = f.grow(f.beam_ctx, {B, pk.ctx_vocab, pk.ctx_capacity});
     if (rc != WRK_OK) return rc;
     const wrk::BeamParam par{pk.W, pk.G, pk.steps, (uint32_t)pk.inv_norm.size()};
     const wrk::LogprobParam lp{f.beam.chosen_lp, f.beam.cand_ids, f.beam.cand_lp, pk.W, B};
@@ -1050,6 +1055,33 @@ static int32_t wrk_beam_prepare(wrk_frame_common& f, const wrk_v7_state* st, uin
 // the slots [b0, b0 + B) of `st`, as beam_copy addresses them
 static wrk::BeamSlots beam_state(const wrk_v7_state* st, uint32_t b0) { return wrk::BeamSlots{st->data, st->num_batch, b0}; }
 
+// The context stages of a pick's row chain, behind the bias and in front of the pick or the beam front: the penalise launch (penalised),
+// the DRY launches (dry: the row copy unless penalised, then dry_rows) and the mask launch (constrained).  `logits`: the row the chain
+// has reached, in and out
+static int32_t enqueue_context_rows(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const float*& logits, bool argmax_done) {
+    hipStream_t q = f.ctx->op_stream();
+    const uint32_t V = f.facts().num_vocab;
+    if (kind.penalized) {
+        wrk::penalize_rows(q, logits, V, V, B, f.penalty.par, f.penalty.out, V);
+        logits = f.penalty.out;
+    }
+    // DRY: in place on the penalised row, else on a copy of the biased row or of head_o
+    if (kind.dry) {
+        float* rows = kind.penalized ? f.penalty.out : f.dry.out;
+        if (!kind.penalized) wrk::copy_rows(q, logits, V, V, B, rows, V);
+        wrk::dry_rows(q, rows, V, V, B, f.dry.par, f.dry.brk, f.dry.scratch);
+        logits = rows;
+    }
+    // the mask: in place on the penalised or the DRY row, else from the biased row or head_o into grammar.out
+    if (kind.constrained) {
+        if (!f.grammar.holds({B, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
+        float* masked = kind.penalized ? f.penalty.out : kind.dry ? f.dry.out : f.grammar.out;
+        wrk::constrain_rows(q, logits, V, V, B, f.grammar.par, masked, V);
+        logits = masked;
+    }
+    return WRK_OK;
+}
+
 // tail of a beam program's step, on the row the pick would be made on: the candidate front and beam_select, the permutation of the
 // slots by the step's copy list, then the snapshot of the slots that ended in the step (their state after the permutation)
 static int32_t enqueue_beam_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind kind, const wrk_v7_state* st, uint32_t b0, const float* logits,
@@ -1060,11 +1092,28 @@ static int32_t enqueue_beam_tail(wrk_frame_common& f, uint32_t B, wrk_step_kind 
     const size_t slot = state_slot_floats(st);
     if (!f.beam.holds({B}) || f.beam.dim[3] != (size_t)st->num_layer * slot || b0 + B > st->num_batch || argmax_done)
         return wrk_fail(f.ctx, WRK_E_ARG, "beam buffers are not prepared");
-    if (kind.sampled() || kind.penalized || kind.constrained || kind.dry || kind.logprobs || kind.stop_seqs)
-        return wrk_fail(f.ctx, WRK_E_ARG, "a beam step composes with a logit bias only");
+    if (kind.sampled() || kind.logprobs || kind.stop_seqs || kind.guided)
+        return wrk_fail(f.ctx, WRK_E_ARG, "a beam step composes with a logit bias and a context only");
+    // a context: every slot's row goes through the stages of a pick's chain with the slot's own context
+    const bool context = kind.penalized || kind.dry || kind.constrained;
+    if (context && !f.beam_ctx.holds({B, kind.penalized ? (size_t)V : 0u}))
+        return wrk_fail(f.ctx, WRK_E_ARG, "beam context rows are not prepared");
+    if (kind.penalized && !f.penalty.holds({B, V})) return wrk_fail(f.ctx, WRK_E_ARG, "penalty rows are not prepared");
+    const int32_t src = enqueue_context_rows(f, B, kind, logits, argmax_done);
+    if (src != WRK_OK) return src;
     if (wrk::beam_step_rows(q, logits, V, V, B, io.tokens, f.beam.lp_par, f.beam.part, f.beam.keys, f.beam.dev(), io.tokens, io.counter, f.ctx->num_cu) != 0)
         return wrk_fail(f.ctx, WRK_E_UNSUPPORTED, "beam search: vocabulary of %u tokens", V);
     wrk::beam_permute(q, beam_state(st, b0), f.beam.scratch, st->num_layer, slot, f.beam.copy_src, B, f.ctx->num_cu);
+    if (context) {
+        // the contexts follow the hypotheses by the same copy list, and only then count the tokens the step gave out: io.tokens of the
+        // slots it filled
+        const wrk::BeamCtxRows rows{kind.penalized ? f.penalty.par : nullptr, kind.dry ? f.dry.par : nullptr, kind.constrained ? f.grammar.state : nullptr};
+        wrk::beam_context_permute(q, rows, f.beam_ctx.dev(), V, f.beam.copy_src, B);
+        const wrk::RowGate gate{f.beam.filled, 1u, 1u};
+        if (kind.penalized) wrk::occurrence_update(q, V, B, f.penalty.par, io.tokens, 1, gate);
+        if (kind.constrained) wrk::grammar_advance(q, V, B, f.grammar.par, io.tokens, gate);
+        if (kind.dry) wrk::window_push(q, V, B, f.dry.par, io.tokens, gate);
+    }
     wrk::beam_copy(q, beam_state(st, b0), wrk::BeamSlots{f.beam.snap, B, 0u}, st->num_layer, slot, f.beam.snap_map, false, B, f.ctx->num_cu);
     return WRK_OK;
 }
@@ -1092,24 +1141,8 @@ int32_t wrk_enqueue_pick(wrk_frame_common& f, uint32_t frame_b, wrk_step_kind ki
         logits = f.bias.out;
     }
     if (kind.tail == wrk_step_kind::BEAM) return enqueue_beam_tail(f, B, kind, st, b0, logits, argmax_done);
-    if (kind.penalized) {
-        wrk::penalize_rows(q, logits, V, V, B, f.penalty.par, f.penalty.out, V);
-        logits = f.penalty.out;
-    }
-    // DRY: in place on the penalised row, else on a copy of the biased row or of head_o
-    if (kind.dry) {
-        float* rows = kind.penalized ? f.penalty.out : f.dry.out;
-        if (!kind.penalized) wrk::copy_rows(q, logits, V, V, B, rows, V);
-        wrk::dry_rows(q, rows, V, V, B, f.dry.par, f.dry.brk, f.dry.scratch);
-        logits = rows;
-    }
-    // the mask: in place on the penalised or the DRY row, else from the biased row or head_o into grammar.out
-    if (kind.constrained) {
-        if (!f.grammar.holds({B, V}) || argmax_done) return wrk_fail(f.ctx, WRK_E_ARG, "grammar states are not prepared");
-        float* masked = kind.penalized ? f.penalty.out : kind.dry ? f.dry.out : f.grammar.out;
-        wrk::constrain_rows(q, logits, V, V, B, f.grammar.par, masked, V);
-        logits = masked;
-    }
+    const int32_t src = enqueue_context_rows(f, B, kind, logits, argmax_done);
+    if (src != WRK_OK) return src;
     // the sampler only reads the counter: rows run in different workgroups, so the tail's advance moves it after all of them
     if (!kind.sampled()) {
         if (!argmax_done) wrk::argmax_rows(q, logits, V, V, B, io.argmax);
@@ -1453,9 +1486,54 @@ int32_t wrk_generate_queue_cut(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* 
     return wrk_generate_queue(ctx, m, st, B, opt, out_arg, elapsed_ms, mode_arg, tail, cuts->pool, cuts->guide, cuts->guide != nullptr, cuts);
 }
 
+// the context of wrk_v*_generate_beam_context validated into pk.rows: one value per group becomes one row per slot, slot q
+// of the call naming slot q of the table and of the window.  Sets kind.penalized / dry / constrained; an empty context sets nothing
+static int32_t wrk_beam_context_check(wrk_ctx* ctx, const wrk_beam_context& c, uint32_t G, uint32_t W, uint32_t V, wrk_beam_pack& pk, wrk_step_kind& kind) {
+    const uint32_t B = G * W;
+    WRK_ARG(ctx, c.occ || (!c.presence && !c.frequency && !c.decay), "penalty arrays without an occurrence table");
+    WRK_ARG(ctx, c.grammar || (!c.grammar_state && !c.out_grammar_state), "grammar_state / out_grammar_state without grammar");
+    wrk_dry_args dry{c.window, c.dry_multiplier, c.dry_base, c.dry_allowed_length, c.no_repeat_ngram, c.dry_breakers, c.num_dry_breakers};
+    WRK_ARG(ctx, c.window || !dry.any_array(), "dry_* / no_repeat_ngram arrays without a token window");
+    // a group's value for each of its slots
+    auto per_slot = [&](auto* group, auto& slots) {
+        slots.clear();
+        for (uint32_t q = 0; group && q < B; ++q) slots.push_back(group[q / W]);
+        return group ? slots.data() : nullptr;
+    };
+    if (c.occ) {
+        std::vector<float> pres, freq, dec;
+        WRK_ARG(ctx, c.occ->num_batch >= B, "occurrence table of %u slots, %u beam slots", c.occ->num_batch, B);
+        const int32_t rc = wrk_penalty_pack(ctx, c.occ, 0, B, V, per_slot(c.presence, pres), per_slot(c.frequency, freq), per_slot(c.decay, dec), pk.rows.pen);
+        if (rc != WRK_OK) return rc;
+        kind.penalized = true;
+        pk.ctx_vocab = V;
+    }
+    if (c.window) {
+        std::vector<float> mult, base;
+        std::vector<uint32_t> allowed, nr;
+        WRK_ARG(ctx, c.window->num_batch >= B, "token window of %u slots, %u beam slots", c.window->num_batch, B);
+        dry.multiplier = per_slot(c.dry_multiplier, mult); dry.base = per_slot(c.dry_base, base);
+        dry.allowed_length = per_slot(c.dry_allowed_length, allowed); dry.no_repeat_ngram = per_slot(c.no_repeat_ngram, nr);
+        const int32_t rc = wrk_dry_pack(ctx, dry, 0, B, B, V, pk.rows.dry, pk.rows.brk);
+        if (rc != WRK_OK) return rc;
+        kind.dry = pk.rows.has_dry = true;
+        pk.ctx_capacity = c.window->capacity;
+    }
+    if (c.grammar) {
+        std::vector<uint32_t> start;
+        const int32_t rc = wrk_grammar_pack(ctx, c.grammar, per_slot(c.grammar_state, start), B, V, pk.rows.gram_state);
+        if (rc != WRK_OK) return rc;
+        kind.constrained = true;
+        pk.rows.grammar = c.grammar;
+        pk.out_grammar_state = c.out_grammar_state;
+    }
+    return WRK_OK;
+}
+
 // generate_beam: opt validated into pk (WRK_E_ARG / WRK_E_UNSUPPORTED before any launch); sets kind
 static int32_t wrk_beam_check(wrk_ctx* ctx, const wrk_beam_options* opt, const wrk_beam_result* out, const wrk_v7_state* st, const uint32_t* first_tokens,
-                              uint32_t G, uint32_t steps, uint32_t V, uint32_t mode_arg, wrk_beam_pack& pk, wrk_step_kind& kind) {
+                              uint32_t G, uint32_t steps, uint32_t V, uint32_t mode_arg, const wrk_beam_context* bc, wrk_beam_pack& pk,
+                              wrk_step_kind& kind) {
     WRK_ARG(ctx, opt, "options required");
     WRK_ARG(ctx, out && out->tokens && out->lengths && out->scores && out->finished && out->slots && out->num_hyps && out->steps_run,
             "every result array but the step arrays is required");
@@ -1470,10 +1548,10 @@ static int32_t wrk_beam_check(wrk_ctx* ctx, const wrk_beam_options* opt, const w
     WRK_ARG(ctx, !g.temperature && !g.top_p && !g.seed && !g.top_k && !g.min_p && !g.mirostat_tau && !g.mirostat_eta && !g.mirostat_mu && !g.typical_p &&
                      !wrk_cut_of(g).any(),
             "beam search takes no sampler");
-    WRK_ARG(ctx, !g.presence && !g.frequency && !g.decay && !g.occ, "beam search takes no penalties");
+    WRK_ARG(ctx, !g.presence && !g.frequency && !g.decay && !g.occ, "beam search takes penalties in a wrk_beam_context, not in gen");
     WRK_ARG(ctx, !g.window && !g.dry_multiplier && !g.dry_base && !g.dry_allowed_length && !g.no_repeat_ngram && !g.dry_breakers && !g.num_dry_breakers,
-            "beam search takes no DRY / n-gram ban");
-    WRK_ARG(ctx, !g.grammar && !g.grammar_state, "beam search takes no grammar");
+            "beam search takes DRY / the n-gram ban in a wrk_beam_context, not in gen");
+    WRK_ARG(ctx, !g.grammar && !g.grammar_state, "beam search takes a grammar in a wrk_beam_context, not in gen");
     WRK_ARG(ctx, !g.num_top && !g.out_logprob && !g.out_top_ids && !g.out_top_logprobs, "beam search returns no log-prob rows");
     WRK_ARG(ctx, !g.stop_seq_tokens && !g.stop_seq_offsets && !g.stop_seq_owners && !g.out_stop_match && !g.stop_tail, "beam search takes no stop sequences");
     if (V > wrk::SAMPLE_MAX_VOCAB) return wrk_fail(ctx, WRK_E_UNSUPPORTED, "beam search: vocabulary of %u tokens", V);
@@ -1498,7 +1576,7 @@ static int32_t wrk_beam_check(wrk_ctx* ctx, const wrk_beam_options* opt, const w
         if (kind.biased) pk.rows.bias_set.push_back(per_group.bias_set[q / W]);
         if (q % W == 0) pk.slots[q] = wrk::BeamSlot{0.0f, 0.0f, 0u, (uint32_t)WRK_BEAM_LIVE};
     }
-    return WRK_OK;
+    return bc ? wrk_beam_context_check(ctx, *bc, G, W, V, pk, kind) : WRK_OK;
 }
 
 // after the loop and the restore: the records and the history rows come back; per group the non-DEAD slots by key descending, ties by
@@ -1515,6 +1593,7 @@ static int32_t wrk_beam_finish(wrk_frame_common& f, const wrk_beam_pack& pk, uin
         WRK_HIP(ctx, hipMemcpyAsync(par.data(), f.beam.step_parents, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (out.step_scores) WRK_HIP(ctx, hipMemcpyAsync(out.step_scores, f.beam.step_scores, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
+    if (pk.out_grammar_state) WRK_HIP(ctx, hipMemcpyAsync(pk.out_grammar_state, f.grammar.state, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (out.step_tokens && rows) memcpy(out.step_tokens, tok.data(), rows * 4);
     if (out.step_parents && rows) memcpy(out.step_parents, par.data(), rows * 4);
@@ -1549,13 +1628,14 @@ static int32_t wrk_beam_finish(wrk_frame_common& f, const wrk_beam_pack& pk, uin
 }
 
 int32_t wrk_generate_beam(wrk_ctx* ctx, wrk_frame_common* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t G, uint32_t steps,
-                          const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg) {
+                          const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg,
+                          const wrk_beam_context* bc) {
     if (!ctx || !m || !st || !first_tokens) return WRK_E_ARG;
     LOCK(ctx);
     const uint32_t V = m->facts().num_vocab;
     wrk_beam_pack pk;
     wrk_step_kind kind;
-    int32_t rc = wrk_beam_check(ctx, opt, out_arg, st, first_tokens, G, steps, V, mode_arg, pk, kind);
+    int32_t rc = wrk_beam_check(ctx, opt, out_arg, st, first_tokens, G, steps, V, mode_arg, bc, pk, kind);
     const uint32_t B = pk.G * pk.W;
     if (rc == WRK_OK) rc = wrk_generate_check(ctx, st, m->facts(), pk.first_tokens.data(), B);
     if (rc != WRK_OK) return rc;

@@ -738,6 +738,12 @@ int32_t wrk_v7_generate_beam(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, co
     return wrk_generate_beam(ctx, m, st, first_tokens, G, steps, opt, out_arg, elapsed_ms, mode_arg);
 }
 
+int32_t wrk_v7_generate_beam_context(wrk_ctx* ctx, wrk_v7_model* m, wrk_v7_state* st, const uint32_t* first_tokens, uint32_t G, uint32_t steps,
+                                     const wrk_beam_options* opt, const wrk_beam_result* out_arg, float* elapsed_ms, uint32_t mode_arg,
+                                     const wrk_beam_context* bc) {
+    return wrk_generate_beam(ctx, m, st, first_tokens, G, steps, opt, out_arg, elapsed_ms, mode_arg, bc);
+}
+
 }  // extern "C"
 
 // Persistent decode engine: built once, outside captures.  WRK_ENGINE=0 keeps the five-launch layer (read per call, part of the

@@ -141,6 +141,15 @@ class BeamResult(C.Structure):
                 ("steps_run", _u32p), ("step_tokens", _u32p), ("step_parents", _u32p), ("step_scores", _f32p)]
 
 
+class BeamContext(C.Structure):
+    """wrk_beam_context: what every hypothesis of wrk_v*_generate_beam_context carries beside its state -- an occurrence table, a token
+    window and a grammar (each may be NULL) with one value per group in every array, and the per-slot automaton states that come back."""
+    _fields_ = [("occ", _P), ("presence", _f32p), ("frequency", _f32p), ("decay", _f32p),
+                ("window", _P), ("dry_multiplier", _f32p), ("dry_base", _f32p), ("dry_allowed_length", _u32p), ("no_repeat_ngram", _u32p),
+                ("dry_breakers", _u32p), ("num_dry_breakers", C.c_uint32),
+                ("grammar", _P), ("grammar_state", _u32p), ("out_grammar_state", _u32p)]
+
+
 MAX_BEAMS = 16              # WRK_MAX_BEAMS
 MAX_BEAM_STOP_TOKENS = 128  # WRK_MAX_BEAM_STOP_TOKENS
 BEAM_NO_TOKEN = 0xFFFFFFFF  # WRK_BEAM_NO_TOKEN
@@ -309,6 +318,12 @@ HIP_SYMBOLS = {
     "wrk_beam_step": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u32p, _u32p, _f32p, _f32p, _u32p, _u32p,
                                   _u32p, _u32p, _u32p]),
     "wrk_v7_state_permute": (C.c_int32, [_P, _P, _u32p, C.c_uint32]),
+    "wrk_v7_generate_beam_context": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(BeamOptions), C.POINTER(BeamResult), _f32p,
+                                                 C.c_uint32, C.POINTER(BeamContext)]),
+    "wrk_v6_generate_beam_context": (C.c_int32, [_P, _P, _P, _u32p, C.c_uint32, C.c_uint32, C.POINTER(BeamOptions), C.POINTER(BeamResult), _f32p,
+                                                 C.c_uint32, C.POINTER(BeamContext)]),
+    "wrk_occurrence_permute": (C.c_int32, [_P, _P, _u32p, C.c_uint32]),
+    "wrk_token_window_permute": (C.c_int32, [_P, _P, _u32p, C.c_uint32]),
 }
 RT_SYMBOLS = {
     "wrk_host_last_error": (C.c_char_p, []),
@@ -1048,6 +1063,13 @@ class TokenWindow:
         self.ctx.check(hip.wrk_token_window_back(self.ctx.h, self.h, batch, _ptr(out, _u32p), C.byref(n)))
         return out[:n.value].copy()
 
+    def permute(self, parents):
+        """Slot q <- slot parents[q] for q < len(parents), ring and meta, on the device and correct under any aliasing; slots with
+        parents[q] == q move no bytes and slots >= len(parents) are untouched (wrk_token_window_permute): `Runtime.state_permute`'s
+        companion in a host-driven beam loop."""
+        p = _u32(parents).reshape(-1)
+        self.ctx.check(hip.wrk_token_window_permute(self.ctx.h, self.h, _ptr(p, _u32p), p.size))
+
     def load(self, batch: int, tokens=None):
         """Slot `batch` becomes `tokens` (at most `capacity`, oldest first); None: empty."""
         if tokens is None:
@@ -1175,6 +1197,13 @@ class Occurrence:
         f = np.empty(self.num_vocab, np.uint32)
         self.ctx.check(hip.wrk_occurrence_back(self.ctx.h, self.h, b, _ptr(c, _f32p), _ptr(f, _u32p)))
         return c, f
+
+    def permute(self, parents):
+        """Slot q <- slot parents[q] for q < len(parents), counts and both flag bits, on the device and correct under any aliasing;
+        slots with parents[q] == q move no bytes and slots >= len(parents) are untouched (wrk_occurrence_permute): `Runtime.state_permute`'s
+        companion in a host-driven beam loop."""
+        p = _u32(parents).reshape(-1)
+        self.ctx.check(hip.wrk_occurrence_permute(self.ctx.h, self.h, _ptr(p, _u32p), p.size))
 
     def load(self, b: int, counts=None, flags=None):
         """Sets slot b; counts=None and flags=None reset it (zero counts, no flags)."""
@@ -2175,7 +2204,10 @@ class Runtime:
         return [(out[off[r]:off[r] + lengths[r]].copy(), int(reasons[r]), int(slots[r]), int(starts[r])) for r in range(R)], run.value
 
     def generate_beam(self, first_tokens, steps: int, num_beams: int, stop=None, length_penalty: float = 0.0, logit_bias: "LogitBias" = None,
-                      bias_set=None, mode: int = 1, poll_steps: int = 0, guidance_scale=None):
+                      bias_set=None, mode: int = 1, poll_steps: int = 0, guidance_scale=None,
+                      occurrence: "Occurrence" = None, presence=0.0, frequency=0.0, decay=1.0,
+                      window: "TokenWindow" = None, dry=None, no_repeat_ngram=None, dry_breakers=None,
+                      grammar: "Grammar" = None, grammar_state=None):
         """Beam search kept on the device (wrk_v*_generate_beam): G = len(first_tokens) groups of `num_beams` beams on
         state slots [0, G * num_beams); group g starts from the state in slot g * num_beams and feeds first_tokens[g].  Every step
         keeps, per group, the num_beams best of the live beams' continuations and the finished hypotheses, ordered by
@@ -2186,7 +2218,14 @@ class Runtime:
         slot `slot` holds that hypothesis's state, having consumed everything but its last token.  `last_beam_steps` = (tokens,
         parents, scores), each [steps_run, B]: what every step put in every slot (BEAM_NO_TOKEN: not filled).
         guidance_scale: the `gen` options' guidance_scale field; guidance is not built for beam search: anything but
-        None is refused with WRK_E_UNSUPPORTED."""
+        None is refused with WRK_E_UNSUPPORTED.
+        occurrence / presence / frequency / decay, window / dry / no_repeat_ngram / dry_breakers, grammar / grammar_state (DESIGN.md
+        §7u): a context per hypothesis, each value a scalar or one per group.  Slot g * num_beams of the table and the window carries
+        the group's context at the start (`occ.add` / `occ.ban` / `win.add`); every beam's row is penalised, DRY-penalised or n-gram
+        banned and masked with its own hypothesis's occurrence row, window and automaton state, which move with the hypothesis and
+        count the token it was given.  Afterwards slot `slot` of the table and the window holds that hypothesis's context, its last
+        token counted, and `last_grammar_state` [B] the automaton state per slot.  With none of them given the call is
+        wrk_v*_generate_beam, as before."""
         ft = _u32(first_tokens).reshape(-1)
         G, W, steps = ft.size, int(num_beams), int(steps)
         B = G * max(W, 0)
@@ -2203,9 +2242,30 @@ class Runtime:
         run, ms = C.c_uint32(), C.c_float()
         res = BeamResult(_ptr(tokens, _u32p), _ptr(lengths, _u32p), _ptr(scores, _f32p), _ptr(finished, _u32p), _ptr(slots, _u32p),
                          _ptr(hyps, _u32p), C.pointer(run), _ptr(st, _u32p), _ptr(sp, _u32p), _ptr(ss, _f32p))
-        fn, mdl = self._entry("generate_beam")
         self.last_beam_steps = None
-        self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), G, steps, C.byref(opt), C.byref(res), C.byref(ms), mode & 0xff))
+        self.last_grammar_state = None
+        if occurrence is None and window is None and grammar is None:
+            if dry is not None or no_repeat_ngram is not None or dry_breakers is not None:
+                raise ValueError("dry / no_repeat_ngram / dry_breakers without window")
+            if grammar_state is not None:
+                raise ValueError("grammar_state without grammar")
+            fn, mdl = self._entry("generate_beam")
+            self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), G, steps, C.byref(opt), C.byref(res), C.byref(ms), mode & 0xff))
+        else:
+            bc, gn = BeamContext(), max(G, 1)
+            if occurrence is not None:
+                keep.extend(_per_row(v, gn, np.float32) for v in (presence, frequency, decay))
+                bc.occ, bc.presence, bc.frequency, bc.decay = occurrence.h, *(_ptr(a, _f32p) for a in keep[-3:])
+            _fill_dry(bc, gn, keep, window, dry, no_repeat_ngram, dry_breakers)
+            _fill_grammar(bc, gn, keep, grammar, grammar_state)
+            gs = np.zeros(n, np.uint32)
+            if grammar is not None:
+                bc.out_grammar_state = _ptr(gs, _u32p)
+            fn, mdl = self._entry("generate_beam_context")
+            self.ctx.check(fn(self.ctx.h, mdl, self.state, _ptr(ft, _u32p), G, steps, C.byref(opt), C.byref(res), C.byref(ms), mode & 0xff,
+                              C.byref(bc)))
+            if grammar is not None:
+                self.last_grammar_state = gs[:B].copy()
         self.last_beam_ms = ms.value
         r = run.value
         self.last_beam_steps = (st.reshape(-1)[:r * B].reshape(r, B).copy(), sp.reshape(-1)[:r * B].reshape(r, B).copy(),
