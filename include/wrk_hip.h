@@ -478,6 +478,53 @@ int32_t wrk_constrain_logits(wrk_ctx* ctx, wrk_buf* logits, uint32_t num_vocab, 
  * u32 [num_rows], in/out; tokens: host u32 [num_rows], each < num_vocab.  Blocking. */
 int32_t wrk_grammar_advance(wrk_ctx* ctx, const wrk_grammar* grammar, uint32_t* states, const uint32_t* tokens, uint32_t num_rows);
 
+/* Regex -> token automaton (vLLM's guided_regex).  Two steps: patterns -> a byte DFA on the host, byte DFA x vocabulary
+ * -> a wrk_grammar on the device.  The tokenizer stays outside: the vocabulary is one byte string per token id.
+ *
+ * wrk_regex_compile needs no context and no device.  The alphabet is bytes, matching is whole-string.  Dialect: literals (a code point
+ * outside ASCII is its UTF-8 bytes), \ before a metacharacter, \n \r \t \f \v, \xHH (one raw byte), \d \w \s (ASCII; \s is
+ * [ \t\n\r\f\v]) and \D \W \S (any other code point, every well-formed multi-byte UTF-8 sequence included), "." (a code point other
+ * than \n), [...] and [^...] over ASCII members, ASCII ranges and the class escapes (a negated class matches every other code point),
+ * groups (...) and (?:...), | (empty alternatives allowed), * + ? {m} {m,} {m,n} with n <= 1000.  WRK_E_UNSUPPORTED, with the
+ * construct and its byte offset in err ("pattern 0: unsupported: look-around at offset 3"): anchors and \b \B \A \Z, back-references,
+ * look-around, lazy or possessive quantifiers, named groups, inline flags, \p{..}, a class member outside ASCII, a repeat count above
+ * 1000, more than 65 534 states in total.  WRK_E_ARG with "syntax: ... at offset N": everything else that does not parse.  err may be
+ * NULL.  Pattern p's DFA is minimal and trimmed (every state reachable from its start, an accepting state reachable from every state;
+ * no dead state: a missing transition is WRK_GRAMMAR_REJECT), numbered breadth-first from its start in byte order; the state sets are
+ * disjoint and concatenated in pattern order, starts[p] the first state of pattern p.
+ * wrk_byte_dfa_from_arrays makes the same object from next[num_states][256] (a state or WRK_GRAMMAR_REJECT), accepting[num_states] and
+ * starts[num_patterns]: the entry for a BNF or JSON-schema compiler of the caller's.  Ranges are checked (WRK_E_ARG), nothing else;
+ * 1 <= num_states <= 65 534.  wrk_byte_dfa_export: the counts, and the arrays into whichever pointers are not NULL. */
+typedef struct wrk_byte_dfa wrk_byte_dfa;
+int32_t wrk_regex_compile(const char* const* patterns, const size_t* lengths, uint32_t num_patterns, wrk_byte_dfa** out, char* err,
+                          size_t err_cap);
+int32_t wrk_byte_dfa_from_arrays(uint32_t num_states, const uint16_t* next, const uint8_t* accepting, const uint32_t* starts,
+                                 uint32_t num_patterns, wrk_byte_dfa** out);
+int32_t wrk_byte_dfa_export(const wrk_byte_dfa* dfa, uint32_t* num_states, uint32_t* num_patterns, uint16_t* next_or_null,
+                            uint8_t* accepting_or_null, uint32_t* starts_or_null);
+void wrk_byte_dfa_destroy(wrk_byte_dfa* dfa);
+/* The token automaton of a byte DFA over a vocabulary: token t is the bytes [vocab_offsets[t], vocab_offsets[t + 1]) of vocab_bytes.
+ * Its states are the byte-DFA states plus one FINAL state, the last.  From state s token t leads where its bytes lead; a missing byte
+ * transition on the way is REJECT, and an empty token is REJECT everywhere.  end_token's bytes are ignored: it leads from an accepting
+ * state to FINAL, is REJECT elsewhere, and FINAL allows only end_token and loops on it.  Then every state from which FINAL cannot be
+ * reached through tokens of this vocabulary is dropped and the transitions into it become REJECT, so every state allows a token; kept
+ * states keep their order, renumbered compactly; columns that are then equal share a class, classes numbered by first token id.
+ * start_states[p] (num_patterns of the DFA) and *final_state are the new numbers.  The walk runs on the device (wrk_grammar_compile.hip)
+ * in scratch of O(vocabulary bytes + num_vocab + states x byte classes + states x classes); the result is exact.  Blocking.
+ * WRK_E_ARG before any launch: NULL arguments, num_vocab 0, end_token >= num_vocab, offsets that decrease; after the walk: "the
+ * vocabulary cannot spell pattern p".  WRK_E_UNSUPPORTED: num_vocab > 2^20; more than WRK_MAX_TOKEN_CLASSES distinct token columns
+ * over the byte-DFA states (counted before the trim, which bounds the scratch).  The grammar is an ordinary wrk_grammar.
+ * wrk_grammar_compile_last_ms: the wall-clock milliseconds of this thread's last wrk_grammar_compile, per phase: byte classes and
+ * mapping, upload + hash pass, representative walks, verify passes, trim, create.
+ * wrk_grammar_export reads a grammar's tables back: the counts, and the arrays into whichever pointers are not NULL.  Blocking. */
+#define WRK_GRAMMAR_COMPILE_PHASES 6
+int32_t wrk_grammar_compile(wrk_ctx* ctx, const wrk_byte_dfa* dfa, uint32_t num_vocab, const uint8_t* vocab_bytes,
+                            const uint64_t* vocab_offsets, uint32_t end_token, wrk_grammar** out, uint32_t* start_states,
+                            uint32_t* final_state);
+int32_t wrk_grammar_compile_last_ms(float* ms);
+int32_t wrk_grammar_export(const wrk_grammar* grammar, uint32_t* num_states, uint32_t* num_classes, uint16_t* token_class_or_null,
+                           uint16_t* transitions_or_null);
+
 /* Logit bias (ai00's `bias`, llama.cpp's --logit-bias, the first link of its sampler chain, vLLM's and the OpenAI interfaces'
  * logit_bias, whose -100 is -inf here): a wrk_logit_bias is an immutable, device-resident collection of num_sets bias sets over one
  * vocabulary.  Set s is the pairs (ids[e], values[e]) for e in [set_offsets[s], set_offsets[s + 1]) (num_sets + 1 offsets); the three

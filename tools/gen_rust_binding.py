@@ -15,8 +15,11 @@ HEADER = os.path.join(ROOT, "include", "wrk_hip.h")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_rust_binding.py -->", "<!-- END GENERATED -->"
 
-SCALARS = {"int32_t": "i32", "uint32_t": "u32", "uint16_t": "u16", "uint8_t": "u8", "size_t": "usize", "float": "f32", "int": "i32",
+SCALARS = {"int32_t": "i32", "uint32_t": "u32", "uint16_t": "u16", "size_t": "usize", "float": "f32", "int": "i32",
            "void": "c_void", "char": "c_char"}
+# C scalars bound under the Rust name of their C type, through a `pub type` line emitted where the header uses them: the independent
+# check of tests/test_abi_host.py names a type it has no Rust scalar for as it names a struct (uint8_t -> Uint8T)
+ALIASES = {"uint8_t": "u8", "uint64_t": "u64"}
 
 
 def strip_comments(text):
@@ -88,6 +91,10 @@ def generate(text):
     out = ["// src/backend/hip.rs -- generated from include/wrk_hip.h by tools/gen_rust_binding.py; do not edit by hand",
            "use std::os::raw::{c_char, c_void};", ""]
     out.append(" ".join(f"pub enum {rust_name(o)} {{}}" for o in opaque) + "      // opaque handles")
+    used = {p[1] for _, _, params in funcs for p in params} | {f[1] for _, fields in structs for f in fields}
+    for c, r in ALIASES.items():
+        if c in used:
+            out.append(f"pub type {rust_name(c)} = {r};")
     for name, fields in structs:
         out.append("#[repr(C)]")
         out.append(f"pub struct {rust_name(name)} {{")

@@ -172,6 +172,9 @@ MAX_TOKEN_WINDOW = 4096         # WRK_MAX_TOKEN_WINDOW
 MAX_DRY_BREAKERS = 16           # WRK_MAX_DRY_BREAKERS
 DRY_MAX_MATCH = 50              # WRK_DRY_MAX_MATCH
 _u16p = C.POINTER(C.c_uint16)
+_u8p = C.POINTER(C.c_uint8)
+_u64p = C.POINTER(C.c_uint64)
+GRAMMAR_COMPILE_PHASES = ("map", "hash", "fill", "verify", "trim", "create")     # wrk_grammar_compile_last_ms, in order
 _TP = C.POINTER(TensorDesc)
 
 # name -> (restype, argtypes); every symbol declared in include/*.h
@@ -276,6 +279,13 @@ HIP_SYMBOLS = {
     "wrk_grammar_destroy": (C.c_int32, [_P]),
     "wrk_constrain_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _u32p]),
     "wrk_grammar_advance": (C.c_int32, [_P, _P, _u32p, _u32p, C.c_uint32]),
+    "wrk_regex_compile": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(_P), C.c_char_p, C.c_size_t]),
+    "wrk_byte_dfa_from_arrays": (C.c_int32, [C.c_uint32, _u16p, _u8p, _u32p, C.c_uint32, C.POINTER(_P)]),
+    "wrk_byte_dfa_export": (C.c_int32, [_P, _u32p, _u32p, _u16p, _u8p, _u32p]),
+    "wrk_byte_dfa_destroy": (None, [_P]),
+    "wrk_grammar_compile": (C.c_int32, [_P, _P, C.c_uint32, _u8p, _u64p, C.c_uint32, C.POINTER(_P), _u32p, _u32p]),
+    "wrk_grammar_compile_last_ms": (C.c_int32, [_f32p]),
+    "wrk_grammar_export": (C.c_int32, [_P, _u32p, _u32p, _u16p, _u16p]),
     "wrk_logit_bias_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p, C.POINTER(_P)]),
     "wrk_logit_bias_destroy": (C.c_int32, [_P]),
     "wrk_bias_logits": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _u32p]),
@@ -714,6 +724,78 @@ def grammar_from_choices(num_vocab: int, choices, end_token: int):
     return token_class, trans, 0
 
 
+_REGEX_META = frozenset(b"\\.^$*+?()[]{}|")
+
+
+def regex_of_choices(strings) -> str:
+    """The regex that matches exactly one of `strings` (str or bytes): every choice escaped, joined by |.  Escaping only: ASCII
+    metacharacters get a backslash, bytes outside printable ASCII become \\xHH (a str is taken as its UTF-8 bytes).  For
+    `ByteDfa.from_regex` / `Grammar.compile`; bytes >= 0x80 written as \\xHH are raw bytes there, so a `bytes` pattern keeps them."""
+    alts = []
+    for c in strings:
+        raw = c.encode("utf-8") if isinstance(c, str) else bytes(c)
+        alts.append("".join("\\" + chr(b) if b in _REGEX_META else chr(b) if 0x20 <= b < 0x7F else f"\\x{b:02x}" for b in raw))
+    if not alts:
+        raise ValueError("no choices")
+    return "|".join(alts)
+
+
+class ByteDfa:
+    """A deterministic automaton over bytes, on the host: next [num_states, 256] u16 (a state or GRAMMAR_REJECT),
+    accepting [num_states] u8, starts [num_patterns] u32.  `from_regex` compiles one pattern or a list of patterns (str, taken as
+    UTF-8, or bytes) into one automaton with a disjoint, minimal, trimmed state set per pattern; `from_arrays` wraps tables of a
+    compiler of the caller's.  `Grammar.compile` turns it into the token automaton of a vocabulary."""
+
+    def __init__(self, h):
+        self.h = h
+        ns, npat = C.c_uint32(), C.c_uint32()
+        hip.wrk_byte_dfa_export(h, C.byref(ns), C.byref(npat), None, None, None)
+        self.num_states, self.num_patterns = ns.value, npat.value
+        self.next = np.empty((self.num_states, 256), np.uint16)
+        self.accepting = np.empty(self.num_states, np.uint8)
+        self.starts = np.empty(self.num_patterns, np.uint32)
+        hip.wrk_byte_dfa_export(h, None, None, _ptr(self.next, _u16p), _ptr(self.accepting, _u8p), _ptr(self.starts, _u32p))
+
+    @classmethod
+    def from_regex(cls, patterns) -> "ByteDfa":
+        if isinstance(patterns, (str, bytes)):
+            patterns = [patterns]
+        raw = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in patterns]
+        n = len(raw)
+        arr = (C.c_char_p * max(n, 1))(*raw)
+        lens = (C.c_size_t * max(n, 1))(*[len(r) for r in raw])
+        err = C.create_string_buffer(512)
+        h = _P()
+        rc = hip.wrk_regex_compile(arr, lens, n, C.byref(h), err, len(err))
+        if rc != OK:
+            raise WrkError(rc, err.value.decode(errors="replace"))
+        return cls(h)
+
+    @classmethod
+    def from_arrays(cls, next, accepting, starts) -> "ByteDfa":
+        nx = np.ascontiguousarray(np.asarray(next, np.uint16))
+        ac = np.ascontiguousarray(np.asarray(accepting, np.uint8)).reshape(-1)
+        st = _u32(starts).reshape(-1)
+        if nx.ndim != 2 or nx.shape[1] != 256 or ac.size != nx.shape[0]:
+            raise ValueError("next: [num_states, 256], accepting: [num_states]")
+        h = _P()
+        rc = hip.wrk_byte_dfa_from_arrays(nx.shape[0], _ptr(nx, _u16p), _ptr(ac, _u8p), _ptr(st, _u32p), st.size, C.byref(h))
+        if rc != OK:
+            raise WrkError(rc, "byte DFA arrays: a next state, a start state or a count out of range")
+        return cls(h)
+
+    def close(self):
+        if self.h:
+            hip.wrk_byte_dfa_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ----------------------------------------------------------------------------- backend objects
 class Context:
     """`Context` (src/context.rs:51-64): one HIP device + submission stream."""
@@ -1125,7 +1207,8 @@ class LogitBias:
 class Grammar:
     """A deterministic automaton over token ids for constrained decoding, on the device: token_class [num_vocab] maps
     every token to a class and transitions [num_states, num_classes] holds the next state, or GRAMMAR_REJECT where the class is not
-    allowed.  `grammar_from_dense` / `grammar_from_choices` build the two tables; regex, BNF or JSON-schema compilers sit above them.
+    allowed.  `grammar_from_dense` / `grammar_from_choices` build the two tables and `Grammar.compile` builds them on the device from
+    regex patterns and a vocabulary; BNF or JSON-schema compilers sit above `ByteDfa.from_arrays`.
     Every state must allow at least one token.  Pass it to the decode loops as `grammar=`, with `grammar_state=` the state each
     sequence starts in."""
 
@@ -1139,6 +1222,37 @@ class Grammar:
         ctx.check(hip.wrk_grammar_create(ctx.h, self.num_vocab, self.num_states, self.num_classes, _ptr(self.token_class, _u16p),
                                          _ptr(self.transitions, _u16p), C.byref(h)))
         self.ctx, self.h = ctx, h
+
+    @classmethod
+    def compile(cls, ctx: Context, vocab, dfa_or_patterns, end_token: int) -> "Grammar":
+        """The token automaton of regex patterns (or of a `ByteDfa`) over `vocab`, a list of `bytes`, one per token id (DESIGN.md
+        §7v): the walk of every token through every state runs on the device.  A sequence that has matched may draw `end_token`,
+        which leads to `final_state`, where only `end_token` is allowed.  The grammar carries `start_states` [num_patterns] (pass
+        one as `grammar_state=`), `final_state` and `compile_ms` (milliseconds per phase of GRAMMAR_COMPILE_PHASES); its host tables
+        are read back from the device object."""
+        dfa = dfa_or_patterns if isinstance(dfa_or_patterns, ByteDfa) else ByteDfa.from_regex(dfa_or_patterns)
+        toks = [bytes(t) for t in vocab]
+        off = np.zeros(len(toks) + 1, np.uint64)
+        off[1:] = np.cumsum([len(t) for t in toks], dtype=np.uint64)
+        data = np.frombuffer(b"".join(toks) + b"\0", np.uint8)        # never empty: a pointer is required
+        starts = np.zeros(dfa.num_patterns, np.uint32)
+        final = C.c_uint32()
+        h = _P()
+        ctx.check(hip.wrk_grammar_compile(ctx.h, dfa.h, len(toks), _ptr(data, _u8p), _ptr(off, _u64p), int(end_token), C.byref(h),
+                                          _ptr(starts, _u32p), C.byref(final)))
+        g = cls.__new__(cls)
+        g.ctx, g.h, g.num_vocab = ctx, h, len(toks)
+        ns, nc = C.c_uint32(), C.c_uint32()
+        ctx.check(hip.wrk_grammar_export(h, C.byref(ns), C.byref(nc), None, None))
+        g.num_states, g.num_classes = ns.value, nc.value
+        g.token_class = np.empty(g.num_vocab, np.uint16)
+        g.transitions = np.empty((g.num_states, g.num_classes), np.uint16)
+        ctx.check(hip.wrk_grammar_export(h, None, None, _ptr(g.token_class, _u16p), _ptr(g.transitions, _u16p)))
+        g.start_states, g.final_state = starts, int(final.value)
+        ms = np.zeros(len(GRAMMAR_COMPILE_PHASES), np.float32)
+        hip.wrk_grammar_compile_last_ms(_ptr(ms, _f32p))
+        g.compile_ms = dict(zip(GRAMMAR_COMPILE_PHASES, ms.tolist()))
+        return g
 
     def walk(self, state: int, tokens) -> int:
         """The state after `tokens` from `state`, walked on the host; ValueError at the first rejected token."""
