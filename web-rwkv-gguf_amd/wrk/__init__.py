@@ -435,42 +435,65 @@ def _mirostat_rows(mirostat, mirostat_mu, n: int):
     return tau, eta, mu
 
 
-def _fill_pick(opt, n: int, keep: list, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-               mirostat=None, mirostat_mu=None, typical_p=None, cuts=None):
+_PICK_NAMES = ("temperature", "top_p", "seed", "occurrence", "presence", "frequency", "decay", "top_k", "min_p", "mirostat", "mirostat_mu",
+               "typical_p", "top_n_sigma", "epsilon_cutoff", "eta_cutoff", "xtc", "grammar", "grammar_state", "window", "dry",
+               "no_repeat_ngram", "dry_breakers", "logit_bias", "bias_set", "logprobs")
+"""The pick arguments every decode loop's public method takes, in the order `_fill_options` fills them (logprobs: by the launch)."""
+
+_PICK_DEFAULTS = {"presence": 0.0, "frequency": 0.0, "decay": 1.0}
+
+_PLAIN = {"greedy": ("presence", "frequency", "decay"),
+          "sample": ("presence", "frequency", "decay", "temperature", "top_p", "seed"),
+          "penalized": ("presence", "frequency", "decay", "temperature", "top_p", "seed", "occurrence")}
+
+
+def _pick(args) -> dict:
+    """The pick bundle of one call: `args` (a public method's locals) by `_PICK_NAMES`; a name the method does not take is off."""
+    return {k: args.get(k, _PICK_DEFAULTS.get(k)) for k in _PICK_NAMES}
+
+
+def _is_plain(pick: dict, plain) -> bool:
+    """Whether a legacy entry point (wrk_v*_generate_greedy / _sample / _penalized) can serve the call: no pick argument is given but
+    those in `plain`, that entry point's own (`_PLAIN`)."""
+    return all(pick[k] is None for k in _PICK_NAMES if k not in plain)
+
+
+def _fill_pick(opt, pick: dict, n: int, keep: list):
     """The sampler / penalty / filter fields of a GenerateOptions or QueueOptions for n rows (scalars broadcast; seed None: seed[i] = i).
-    All of temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p and cuts None: nothing is set, the arg-max.  The arrays
-    go into `keep`, which must outlive the call.  mirostat = (tau, eta): returns the in/out mu array [n] (mirostat_mu, or 2 tau), else
-    None.  cuts: `_cuts`' argument; a GenerateOptions takes the five arrays, a QueueOptions has no such fields (the queue passes them in
-    a QueueCuts) and only becomes a sampled pick."""
+    All of temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p and the cuts None: nothing is set, the arg-max.  The
+    arrays go into `keep`, which must outlive the call.  Returns (mu, cut pointers): mirostat = (tau, eta): the in/out mu array [n]
+    (mirostat_mu, or 2 tau), else None; `_cuts`' result: a GenerateOptions takes the five arrays, a QueueOptions has no such fields (the
+    queue passes them in a QueueCuts) and only becomes a sampled pick."""
     def put(v, dtype, ty):
         keep.append(_per_row(v, n, dtype))
         return _ptr(keep[-1], ty)
-    if mirostat is None and mirostat_mu is not None:
+    temperature, top_p, seed, occurrence, mirostat = (pick[k] for k in ("temperature", "top_p", "seed", "occurrence", "mirostat"))
+    if mirostat is None and pick["mirostat_mu"] is not None:
         raise ValueError("mirostat_mu without mirostat")
-    cut_ptrs = _cuts(cuts, n, keep)
-    if all(v is None for v in (temperature, top_p, seed, occurrence, top_k, min_p, mirostat, typical_p, cut_ptrs)):
-        return None
+    cut_ptrs = _cuts([pick[k] for k in ("top_n_sigma", "epsilon_cutoff", "eta_cutoff", "xtc")], n, keep)
+    if all(v is None for v in (temperature, top_p, seed, occurrence, pick["top_k"], pick["min_p"], mirostat, pick["typical_p"], cut_ptrs)):
+        return None, None
     if cut_ptrs is not None and isinstance(opt, GenerateOptions):
         opt.top_n_sigma, opt.epsilon_cutoff, opt.eta_cutoff, opt.xtc_probability, opt.xtc_threshold = cut_ptrs
     opt.temperature = put(1.0 if temperature is None else temperature, np.float32, _f32p)
     opt.top_p = put(0.5 if top_p is None else top_p, np.float32, _f32p)
     opt.seed = put(np.arange(n, dtype=np.uint32) if seed is None else seed, np.uint32, _u32p)
     if occurrence is not None:
-        opt.presence, opt.frequency, opt.decay = (put(v, np.float32, _f32p) for v in (presence, frequency, decay))
+        opt.presence, opt.frequency, opt.decay = (put(pick[k], np.float32, _f32p) for k in ("presence", "frequency", "decay"))
         opt.occ = occurrence.h
-    tk, mp = _filters(top_k, min_p, n, keep)
+    tk, mp = _filters(pick["top_k"], pick["min_p"], n, keep)
     if tk is not None:
         opt.top_k = tk
     if mp is not None:
         opt.min_p = mp
-    if typical_p is not None:
-        opt.typical_p = put(typical_p, np.float32, _f32p)
+    if pick["typical_p"] is not None:
+        opt.typical_p = put(pick["typical_p"], np.float32, _f32p)
     if mirostat is None:
-        return None
-    tau, eta, mu = _mirostat_rows(mirostat, mirostat_mu, n)
+        return None, cut_ptrs
+    tau, eta, mu = _mirostat_rows(mirostat, pick["mirostat_mu"], n)
     keep.extend([tau, eta, mu])
     opt.mirostat_tau, opt.mirostat_eta, opt.mirostat_mu = _ptr(tau, _f32p), _ptr(eta, _f32p), _ptr(mu, _f32p)
-    return mu
+    return mu, cut_ptrs
 
 
 def _logprob_arrays(logprobs, rows: int):
@@ -624,6 +647,18 @@ def _fill_guidance(opt, n: int, keep: list, guidance_scale, negative_first_token
     if negative_first_tokens is not None:
         keep.append(_per_row(negative_first_tokens, n, np.uint32))
         opt.guidance_first_tokens = _ptr(keep[-1], _u32p)
+
+
+def _fill_options(opt, pick: dict, n: int, keep: list, guidance_scale=None, negative_first_tokens=None):
+    """Every pick field of a GenerateOptions or QueueOptions for n rows from the bundle -- the pick, the grammar, DRY, the bias, then the
+    guidance of the call -- with the arrays in `keep`, which must outlive the call.  Returns (the in/out mirostat mu [n] or None, the
+    in/out grammar states [n] or None, `_cuts`' five pointers or None: a queue passes them in its QueueCuts)."""
+    mu, cut_ptrs = _fill_pick(opt, pick, n, keep)
+    states = _fill_grammar(opt, n, keep, pick["grammar"], pick["grammar_state"])
+    _fill_dry(opt, n, keep, pick["window"], pick["dry"], pick["no_repeat_ngram"], pick["dry_breakers"])
+    _fill_bias(opt, n, keep, pick["logit_bias"], pick["bias_set"])
+    _fill_guidance(opt, n, keep, guidance_scale, negative_first_tokens)
+    return mu, states, cut_ptrs
 
 
 def _bias_csr(sets):
@@ -1957,22 +1992,35 @@ class Runtime:
         its row as `Context.bias_logits` leaves it with the sequence's set of the `LogitBias` -- banned tokens at -inf, the others of
         the set shifted -- before penalties, DRY and the grammar; log-probs and last logits stay raw.  Greedy with a bias bans and
         prefers tokens without a sampler.  Such a call goes through the options entry point and replays step programs of its own."""
-        if any(v is not None for v in (logprobs, grammar, grammar_state, window, dry, no_repeat_ngram, dry_breakers, logit_bias, bias_set)):
-            return self._generate_filtered(first_tokens, steps, None, None, None, None, 0.0, 0.0, 1.0, None, None, mode, want_logits, groups,
-                                           logprobs, grammar=grammar, grammar_state=grammar_state,
-                                           dry_args=(window, dry, no_repeat_ngram, dry_breakers), bias_args=(logit_bias, bias_set))
-        return self._generate("greedy", first_tokens, steps, (), mode, groups, want_logits)
+        pick = _pick(locals())
+        if _is_plain(pick, _PLAIN["greedy"]):
+            return self._generate("greedy", first_tokens, steps, (), mode, groups, want_logits)
+        return self._generate_filtered(first_tokens, steps, pick, mode, groups, want_logits)
 
-    def _generate_options(self, first_tokens, steps, opt, keep, mode, want_logits, logprobs=None):
-        """wrk_v*_generate_stop on prepared options: (tokens [steps, B], lengths [B], steps_run, elapsed ms, last logits or None).
-        logprobs: the alternatives per row, None for a call without log-probs; sets `last_logprobs`."""
+    def _generate_options(self, first_tokens, steps, pick, mode, want_logits, stop=None, stop_sequences=None, stop_tail=None, poll_steps=0,
+                          guidance_scale=None, negative_first_tokens=None):
+        """wrk_v*_generate_stop on the pick bundle, the stop arguments of `generate_stop` and the guidance of `generate_guided`, with
+        the ABI's mode word: (tokens [steps, B], lengths [B], steps_run, elapsed ms, last logits or None).  Sets `last_logprobs`,
+        `last_mirostat_mu`, `last_grammar_state`, `last_stop_match` and `last_stop_tail`."""
         ft = _u32(first_tokens)
         B = ft.size
+        stop_ids, off = _stop_csr(stop, B, "sequences")
+        opt, keep = GenerateOptions(), []
+        if stop_sequences is None and stop_tail is not None:
+            raise ValueError("stop_tail without stop_sequences")
+        self.last_stop_match = _fill_stop_sequences(opt, B, keep, stop_sequences, "sequences")
+        self.last_stop_tail = None
+        if stop_sequences is not None:
+            self.last_stop_tail = _stop_tails(stop_tail, B)
+            opt.stop_tail = _ptr(self.last_stop_tail, _u32p)
+        self.last_mirostat_mu, self.last_grammar_state, _ = _fill_options(opt, pick, B, keep, guidance_scale, negative_first_tokens)
+        opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(stop_ids, _u32p), _ptr(off, _u32p), poll_steps
         out = np.zeros((steps, B), np.uint32)
         lengths = np.zeros(B, np.uint32)
         run, ms = C.c_uint32(), C.c_float()
         logits = np.empty((B, self.info.num_vocab), np.float32) if want_logits else None
         self.last_logprobs = None
+        logprobs = pick["logprobs"]
         if logprobs is not None:
             lp, ids, tlp = _logprob_arrays(logprobs, steps * B)
             opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(ids, _u32p), _ptr(tlp, _f32p)
@@ -2012,27 +2060,14 @@ class Runtime:
         top_n_sigma / epsilon_cutoff / eta_cutoff / xtc=(probability, threshold) (a scalar or one value per sequence; None: off): the
         cuts of `Context.sample_logits`, made next to top_k / min_p on the row the pick sees; they share that family
         and make the pick a sampled one."""
-        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state, window, dry,
-                                       no_repeat_ngram, dry_breakers, logit_bias, bias_set, top_n_sigma, epsilon_cutoff, eta_cutoff, xtc)):
-            return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, None, 0.0, 0.0, 1.0, top_k, min_p, mode,
-                                           want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
-                                           (window, dry, no_repeat_ngram, dry_breakers), (logit_bias, bias_set), (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
-        keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
-        return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
+        pick = _pick(locals())
+        if _is_plain(pick, _PLAIN["sample"]):
+            keep, rows = self._sampler_rows(_u32(first_tokens).size, temperature, top_p, seed)
+            return self._generate("sample", first_tokens, steps, rows, mode, groups, want_logits)
+        return self._generate_filtered(first_tokens, steps, pick, mode, groups, want_logits)
 
-    def _generate_filtered(self, first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p, mode,
-                           want_logits, groups, logprobs=None, mirostat=None, mirostat_mu=None, typical_p=None, grammar=None,
-                           grammar_state=None, dry_args=(None, None, None, None), bias_args=(None, None), cuts=None):
-        opt, keep = GenerateOptions(), []
-        mu = _fill_pick(opt, _u32(first_tokens).size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-                        mirostat, mirostat_mu, typical_p, cuts)
-        gs = _fill_grammar(opt, _u32(first_tokens).size, keep, grammar, grammar_state)
-        _fill_dry(opt, _u32(first_tokens).size, keep, *dry_args)
-        _fill_bias(opt, _u32(first_tokens).size, keep, *bias_args)
-        out, _, _, ms, logits = self._generate_options(first_tokens, steps, opt, keep, self._mode(mode, groups), want_logits, logprobs)
-        self.last_mirostat_mu = mu
-        self.last_grammar_state = gs
-        self.last_stop_match = self.last_stop_tail = None
+    def _generate_filtered(self, first_tokens, steps, pick, mode, groups, want_logits):
+        out, _, _, ms, logits = self._generate_options(first_tokens, steps, pick, self._mode(mode, groups), want_logits)
         return (out, ms, logits) if want_logits else (out, ms)
 
     def generate_penalized(self, first_tokens, steps: int, occurrence: "Occurrence", temperature=1.0, top_p=0.5, seed=None, presence=0.0,
@@ -2050,11 +2085,9 @@ class Runtime:
         window / dry / no_repeat_ngram / dry_breakers: as `generate_greedy`, applied to the penalised logits, before the grammar.
         logit_bias / bias_set: as `generate_greedy`; the penalties are applied to the biased logits: a token is (x + v) - penalty.
         top_n_sigma / epsilon_cutoff / eta_cutoff / xtc: as `generate_sample`, the cuts made on the penalised logits."""
-        if any(v is not None for v in (top_k, min_p, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state, window, dry,
-                                       no_repeat_ngram, dry_breakers, logit_bias, bias_set, top_n_sigma, epsilon_cutoff, eta_cutoff, xtc)):
-            return self._generate_filtered(first_tokens, steps, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k,
-                                           min_p, mode, want_logits, groups, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
-                                           (window, dry, no_repeat_ngram, dry_breakers), (logit_bias, bias_set), (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
+        pick = _pick(locals())
+        if not _is_plain(pick, _PLAIN["penalized"]):
+            return self._generate_filtered(first_tokens, steps, pick, mode, groups, want_logits)
         B = _u32(first_tokens).size
         keep, rows = self._sampler_rows(B, temperature, top_p, seed)
         pen = [_per_row(v, B, np.float32) for v in (presence, frequency, decay)]
@@ -2089,26 +2122,10 @@ class Runtime:
         the stop token's included: the window freezes with the sequence.
         logit_bias / bias_set: as `generate_greedy`; the tokens are a prefix of those of the call without stops.
         top_n_sigma / epsilon_cutoff / eta_cutoff / xtc: as `generate_sample` (they make the pick a sampled one)."""
-        ft = _u32(first_tokens)
-        ids, off = _stop_csr(stop, ft.size, "sequences")
-        opt, keep = GenerateOptions(), []
-        if stop_sequences is None and stop_tail is not None:
-            raise ValueError("stop_tail without stop_sequences")
-        self.last_stop_match = _fill_stop_sequences(opt, ft.size, keep, stop_sequences, "sequences")
-        self.last_stop_tail = None
-        if stop_sequences is not None:
-            self.last_stop_tail = _stop_tails(stop_tail, ft.size)
-            opt.stop_tail = _ptr(self.last_stop_tail, _u32p)
-        self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-                                           mirostat, mirostat_mu, typical_p, (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
-        self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
-        _fill_dry(opt, ft.size, keep, window, dry, no_repeat_ngram, dry_breakers)
-        _fill_bias(opt, ft.size, keep, logit_bias, bias_set)
-        opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
-        out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, self._mode(mode, groups), want_logits,
-                                                                              logprobs)
-        out = out[:run]
-        return (out, lengths, logits) if want_logits else (out, lengths)
+        pick = _pick(locals())
+        out, lengths, run, self.last_stop_ms, logits = self._generate_options(first_tokens, steps, pick, self._mode(mode, groups), want_logits,
+                                                                              stop, stop_sequences, stop_tail, poll_steps)
+        return (out[:run], lengths, logits) if want_logits else (out[:run], lengths)
 
     def generate_guided(self, first_tokens, steps: int, guidance_scale, negative_first_tokens=None, stop=None, temperature=None, top_p=None,
                         seed=None, occurrence: "Occurrence" = None, presence=0.0, frequency=0.0, decay=1.0, mode: int = 1,
@@ -2126,26 +2143,10 @@ class Runtime:
         partner feeds negative_first_tokens[b] at step 0 (None: first_tokens[b]) and then b's draws; it ends and is frozen with b.
         stop (None: no stop ids) and every pick argument: as `generate_stop`, all B wide; log-probs and last logits stay on the raw
         conditional rows.  Returns what `generate_stop` returns.  One lane only."""
-        ft = _u32(first_tokens)
-        ids, off = _stop_csr(stop, ft.size, "sequences")
-        opt, keep = GenerateOptions(), []
-        if stop_sequences is None and stop_tail is not None:
-            raise ValueError("stop_tail without stop_sequences")
-        self.last_stop_match = _fill_stop_sequences(opt, ft.size, keep, stop_sequences, "sequences")
-        self.last_stop_tail = None
-        if stop_sequences is not None:
-            self.last_stop_tail = _stop_tails(stop_tail, ft.size)
-            opt.stop_tail = _ptr(self.last_stop_tail, _u32p)
-        self.last_mirostat_mu = _fill_pick(opt, ft.size, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-                                           mirostat, mirostat_mu, typical_p, (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
-        self.last_grammar_state = _fill_grammar(opt, ft.size, keep, grammar, grammar_state)
-        _fill_dry(opt, ft.size, keep, window, dry, no_repeat_ngram, dry_breakers)
-        _fill_bias(opt, ft.size, keep, logit_bias, bias_set)
-        _fill_guidance(opt, ft.size, keep, guidance_scale, negative_first_tokens)
-        opt.stop_tokens, opt.stop_offsets, opt.poll_steps = _ptr(ids, _u32p), _ptr(off, _u32p), poll_steps
-        out, lengths, run, self.last_stop_ms, logits = self._generate_options(ft, steps, opt, keep, mode, want_logits, logprobs)
-        out = out[:run]
-        return (out, lengths, logits) if want_logits else (out, lengths)
+        pick = _pick(locals())
+        out, lengths, run, self.last_stop_ms, logits = self._generate_options(first_tokens, steps, pick, mode, want_logits, stop, stop_sequences,
+                                                                              stop_tail, poll_steps, guidance_scale, negative_first_tokens)
+        return (out[:run], lengths, logits) if want_logits else (out[:run], lengths)
 
     def generate_queue(self, requests, stop=None, max_new=16, temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None,
                        presence=0.0, frequency=0.0, decay=1.0, init_state: "Buffer" = None, max_steps=None, poll_steps: int = 0,
@@ -2200,9 +2201,10 @@ class Runtime:
         the dispatch writes request r's values into its slot's row, and XTC's coin for reply token j is a function of (seed[r], j) alone,
         so a reply does not depend on when or where its request ran.  Such a call goes through wrk_v*_generate_queue_cut, which takes
         the arrays beside the options, and replays step programs of its own."""
-        args = dict(locals())
-        del args["self"]
-        return self._queue(None, **args)
+        pick = _pick(locals())
+        return self._queue(pick, requests, stop=stop, max_new=max_new, init_state=init_state, max_steps=max_steps, poll_steps=poll_steps,
+                           mode=mode, stop_sequences=stop_sequences, count_prompt=count_prompt, pool=pool, start_state=start_state,
+                           save_state=save_state, history=history, guidance_scale=guidance_scale)
 
     def generate_queue_guided(self, requests, negative_prompts, guidance_scale, negative_init_state: "Buffer" = None, stop=None, max_new=16,
                               temperature=None, top_p=None, seed=None, occurrence: "Occurrence" = None, presence=0.0, frequency=0.0,
@@ -2221,19 +2223,16 @@ class Runtime:
         Every other argument, the return value and the `last_*` attributes: as `generate_queue` without a pool; occurrence rows,
         windows and count_prompt see the conditional prompt only.  max_steps defaults to the sum over the requests of the longer of the
         two prompts plus max_new."""
-        args = dict(locals())
-        for name in ("self", "negative_prompts", "guidance_scale", "negative_init_state", "num_slots"):
-            del args[name]
-        return self._queue((negative_prompts, guidance_scale, negative_init_state, num_slots), pool=None, start_state=None, save_state=None,
-                           history=None, guidance_scale=None, **args)
+        pick = _pick(locals())
+        return self._queue(pick, requests, stop=stop, max_new=max_new, init_state=init_state, max_steps=max_steps, poll_steps=poll_steps,
+                           mode=mode, stop_sequences=stop_sequences, count_prompt=count_prompt,
+                           guide=(negative_prompts, guidance_scale, negative_init_state, num_slots))
 
-    def _queue(self, guide, requests, stop, max_new, temperature, top_p, seed, occurrence, presence, frequency, decay, init_state, max_steps,
-               poll_steps, mode, top_k, min_p, pool, start_state, save_state, logprobs, mirostat, mirostat_mu, typical_p, grammar, grammar_state,
-               stop_sequences, window, dry, no_repeat_ngram, dry_breakers, count_prompt, history, logit_bias, bias_set, guidance_scale,
-               top_n_sigma=None, epsilon_cutoff=None, eta_cutoff=None, xtc=None):
-        """wrk_v*_generate_queue / _queue_pool / _queue_guided on the arguments of `generate_queue`; guide: None, or (negative_prompts,
-        guidance_scale, negative_init_state, num_slots) of `generate_queue_guided`.  With any of the cut arguments the same call goes
-        through wrk_v*_generate_queue_cut with the pool or the guidance in its QueueCuts."""
+    def _queue(self, pick, requests, *, stop, max_new, init_state, max_steps, poll_steps, mode, stop_sequences, count_prompt, pool=None,
+               start_state=None, save_state=None, history=None, guidance_scale=None, guide=None):
+        """wrk_v*_generate_queue / _queue_pool / _queue_guided on the pick bundle and the queue's own arguments of `generate_queue`;
+        guide: None, or (negative_prompts, guidance_scale, negative_init_state, num_slots) of `generate_queue_guided`.  With any of the
+        cut arguments the same call goes through wrk_v*_generate_queue_cut with the pool or the guidance in its QueueCuts."""
         prompts = [np.asarray(x, np.int64).reshape(-1) for x in requests]
         R = len(prompts)
         B = self.num_batch
@@ -2249,13 +2248,7 @@ class Runtime:
         opt.prompt_tokens, opt.prompt_offsets, opt.max_new = _ptr(ptok, _u32p), _ptr(poff, _u32p), _ptr(mn, _u32p)
         opt.stop_tokens, opt.stop_offsets = _ptr(ids, _u32p), _ptr(soff, _u32p)
         keep = []
-        self.last_mirostat_mu = _fill_pick(opt, R, keep, temperature, top_p, seed, occurrence, presence, frequency, decay, top_k, min_p,
-                                           mirostat, mirostat_mu, typical_p, (top_n_sigma, epsilon_cutoff, eta_cutoff, xtc))
-        cut_ptrs = _cuts((top_n_sigma, epsilon_cutoff, eta_cutoff, xtc), R, keep)
-        self.last_grammar_state = _fill_grammar(opt, R, keep, grammar, grammar_state)
-        _fill_dry(opt, R, keep, window, dry, no_repeat_ngram, dry_breakers)
-        _fill_bias(opt, R, keep, logit_bias, bias_set)
-        _fill_guidance(opt, R, keep, guidance_scale)
+        self.last_mirostat_mu, self.last_grammar_state, cut_ptrs = _fill_options(opt, pick, R, keep, guidance_scale)
         match = _fill_stop_sequences(opt, R, keep, stop_sequences, "requests")
         self.last_stop_match = self.last_stop_tail = None
         if init_state is not None:
@@ -2268,6 +2261,7 @@ class Runtime:
             opt.history = history.h
         opt.poll_steps = poll_steps
         opt.max_steps = int(poff[-1]) + int(mn.sum()) if max_steps is None else max_steps
+        name, extra, saved = "generate_queue", None, None
         if guide is not None:
             negs, scale, neg_init, num_slots = guide
             if len(negs) != R:
@@ -2277,43 +2271,12 @@ class Runtime:
             noff[1:] = np.cumsum([x.size for x in negs])
             ntok = _u32(np.concatenate(negs) if noff[-1] else [0])
             sc = _per_row(scale, R, np.float32) if R else np.ones(1, np.float32)
-            qg = QueueGuidance(_ptr(sc, _f32p), _ptr(ntok, _u32p), _ptr(noff, _u32p), neg_init.h if neg_init is not None else None)
+            name, extra = "generate_queue_guided", QueueGuidance(_ptr(sc, _f32p), _ptr(ntok, _u32p), _ptr(noff, _u32p),
+                                                                 neg_init.h if neg_init is not None else None)
             B = self.num_batch // 2 if num_slots is None else int(num_slots)
             if max_steps is None:       # a pair is busy for max(n, m) - 1 + reply steps
                 opt.max_steps = int(sum(max(p.size, q.size) for p, q in zip(prompts, negs))) + int(mn.sum())
-        lengths, reasons, slots, starts = (np.zeros(max(R, 1), np.uint32) for _ in range(4))
-        out = np.zeros(max(int(mn.sum()), 1), np.uint32)
-        run, ms = C.c_uint32(), C.c_float()
-        res = QueueResult(_ptr(lengths, _u32p), _ptr(reasons, _u32p), _ptr(slots, _u32p), _ptr(starts, _u32p), _ptr(out, _u32p),
-                          C.pointer(run))
-        self.last_logprobs = None
-        if logprobs is not None:
-            lp, top_ids, tlp = _logprob_arrays(logprobs, int(mn.sum()))     # `ids` stays alive: opt.stop_tokens points into it
-            opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(top_ids, _u32p), _ptr(tlp, _f32p)
-        cut_fn = None
-        if cut_ptrs is not None:
-            cut_fn, mdl = self._entry("generate_queue_cut")
-        if guide is not None:
-            if cut_fn:
-                qc = QueueCuts(*cut_ptrs, None, C.pointer(qg))
-                self.ctx.check(cut_fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qc)))
-            else:
-                fn, mdl = self._entry("generate_queue_guided")
-                self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qg)))
-            self.last_queue_saved = None
-        elif pool is None and cut_fn:
-            if start_state is not None or save_state is not None:
-                raise ValueError("start_state / save_state need a pool")
-            qc = QueueCuts(*cut_ptrs, None, None)
-            self.ctx.check(cut_fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qc)))
-            self.last_queue_saved = None
-        elif pool is None:
-            if start_state is not None or save_state is not None:
-                raise ValueError("start_state / save_state need a pool")
-            fn, mdl = self._entry("generate_queue")
-            self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode))
-            self.last_queue_saved = None
-        else:
+        elif pool is not None:
             def entries(v):
                 if v is None or np.isscalar(v):
                     v = [v] * R
@@ -2321,14 +2284,27 @@ class Runtime:
                     raise ValueError(f"{len(v)} pool entries for {R} requests")
                 return _u32([QUEUE_NO_ENTRY if k is None else int(k) for k in v]) if R else np.zeros(1, np.uint32)
             st, sv, saved = entries(start_state), entries(save_state), np.zeros(max(R, 1), np.uint32)
-            qp = QueuePool(pool.buf.h, pool.entries, _ptr(st, _u32p), _ptr(sv, _u32p), _ptr(saved, _u32p))
-            if cut_fn:
-                qc = QueueCuts(*cut_ptrs, C.pointer(qp), None)
-                self.ctx.check(cut_fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qc)))
-            else:
-                fn, mdl = self._entry("generate_queue_pool")
-                self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode, C.byref(qp)))
-            self.last_queue_saved = [bool(x) for x in saved[:R]]
+            name, extra = "generate_queue_pool", QueuePool(pool.buf.h, pool.entries, _ptr(st, _u32p), _ptr(sv, _u32p), _ptr(saved, _u32p))
+        elif start_state is not None or save_state is not None:
+            raise ValueError("start_state / save_state need a pool")
+        if cut_ptrs is not None:
+            inner = None if extra is None else C.pointer(extra)
+            name, extra = "generate_queue_cut", QueueCuts(*cut_ptrs, pool=None if guide is not None else inner,
+                                                          guide=None if guide is None else inner)
+        lengths, reasons, slots, starts = (np.zeros(max(R, 1), np.uint32) for _ in range(4))
+        out = np.zeros(max(int(mn.sum()), 1), np.uint32)
+        run, ms = C.c_uint32(), C.c_float()
+        res = QueueResult(_ptr(lengths, _u32p), _ptr(reasons, _u32p), _ptr(slots, _u32p), _ptr(starts, _u32p), _ptr(out, _u32p),
+                          C.pointer(run))
+        self.last_logprobs = None
+        logprobs = pick["logprobs"]
+        if logprobs is not None:
+            lp, top_ids, tlp = _logprob_arrays(logprobs, int(mn.sum()))     # `ids` stays alive: opt.stop_tokens points into it
+            opt.num_top, opt.out_logprob, opt.out_top_ids, opt.out_top_logprobs = int(logprobs), _ptr(lp, _f32p), _ptr(top_ids, _u32p), _ptr(tlp, _f32p)
+        fn, mdl = self._entry(name)
+        self.ctx.check(fn(self.ctx.h, mdl, self.state, B, C.byref(opt), C.byref(res), C.byref(ms), mode,
+                          *(() if extra is None else (C.byref(extra),))))
+        self.last_queue_saved = None if saved is None else [bool(x) for x in saved[:R]]
         self.last_queue_ms = ms.value
         if match is not None:
             self.last_stop_match = match[:R]
