@@ -4,6 +4,7 @@
 
 #include "wrk_internal.h"
 #include "wrk_lora2_pack.h"
+#include "wrk_ffn_granule.h"
 
 namespace wrk {
 

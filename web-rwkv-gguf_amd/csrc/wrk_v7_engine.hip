@@ -21,6 +21,7 @@
 //   K5  LN2 + token shift -> relu(ffn key)^2                                              all workgroups
 //   K6  x += ffn value . k ; ffn shift state ; (x *= 0.5 every `rescale` layers)           all workgroups, K over the 4 waves
 // Hand-offs: K1 -> K2 (LoRA intermediates to every head, r / k / v to their head), K2 -> K3, K3 -> K5, K5 -> K6, K6 -> next K1.
+// K5 -> K6, the widest, carries four f16 per granule with the tag in their sign bits (wrk_ffn_granule.h); the others {two f16, tag}.
 //
 // Safety: every spin is bounded; a give-up raises a device flag, the workgroup leaves at its next barrier, its consumers give up in
 // turn, and the host reports WRK_E_HIP at the next synchronisation.  The grid is one workgroup per CU and needs all of them resident
@@ -95,31 +96,31 @@ __device__ __forceinline__ void eng_copy_in(const void* src, uint32_t n16, ENG_L
 }
 
 // The ffn vector of K6.  Lane L of K-quarter wave kq multiplies chunk c of every row, i.e. elements [lo, lo + 16) and [hi, hi + 16) of
-// the vector = 2 x 4 pieces of granules.  A quarter has one wave per row group, and they multiply the same chunks: the wave of row
-// group 0 polls the `lo` pieces (half 0), the wave of row group 1 the `hi` pieces (half 1), so a CU fetches every granule once per
-// pass.  The 16 payload elements go to `xe` (LDS, the vector's own element order); every K6 wave reads its chunks back from there
-// behind the stage's first barrier (lds_x).  false: gave up.
+// the vector = 2 x 4 four-value granules (wrk_ffn_granule.h: the tag sits in the sign bits), two 16-byte pieces each.  A quarter has one
+// wave per row group, and they multiply the same chunks: the wave of row group 0 polls the `lo` pieces (half 0), the wave of row group
+// 1 the `hi` pieces (half 1), so a CU fetches every granule once per pass.  The 16 payload elements, signs cleared, go to `xe` (LDS, the
+// vector's own element order); every K6 wave reads its chunks back from there behind the stage's first barrier (lds_x).  false: gave up.
 template <int KIND>
-__device__ __forceinline__ bool eng_sweep_half(const unsigned long long* g, uint32_t c, uint32_t half, uint32_t tag, ENG_LDS f16* xe) {
+__device__ __forceinline__ bool eng_sweep_half(const unsigned long long* g, uint32_t c, uint32_t half, uint32_t nibble, ENG_LDS f16* xe) {
     uint32_t lo, hi;
     chunk_xoff<KIND>(c, lo, hi);
     const uint32_t off = half ? hi : lo;
-    const u32x4* p = (const u32x4*)g + (off >> 2);
-    u32x4 v[4];
+    const u32x4* p = (const u32x4*)g + (off >> 3);
+    constexpr uint32_t SG = (uint32_t)ENG_FFN_SIGNS;         // the two sign bits of a 32-bit half
+    const uint32_t t01 = eng_ffn_signs32(nibble & 3u), t23 = eng_ffn_signs32(nibble >> 2);
+    u32x4 v[2];
     for (uint32_t spins = 0; spins < ENG_SPIN_MAX; ++spins) {
-        asm volatile(
-            "global_load_dwordx4 %0, %4, off sc1\n\tglobal_load_dwordx4 %1, %4, off offset:16 sc1\n\tglobal_load_dwordx4 %2, %4, off offset:32 sc1\n\t"
-            "global_load_dwordx4 %3, %4, off offset:48 sc1\n\ts_waitcnt vmcnt(0)"
-            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
-            : "v"(p)
-            : "memory");
-        bool ok = true;
+        asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %2, off offset:16 sc1\n\ts_waitcnt vmcnt(0)"
+                     : "=&v"(v[0]), "=&v"(v[1])
+                     : "v"(p)
+                     : "memory");
+        uint32_t bad = 0;                                    // a sign bit that differs from the tag's, in any of the four granules
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ok &= (v[i].y == tag) & (v[i].w == tag);
-        if (__all(ok)) {
+        for (int i = 0; i < 2; ++i) bad |= (v[i].x ^ t01) | (v[i].y ^ t23) | (v[i].z ^ t01) | (v[i].w ^ t23);
+        if (__all((bad & SG) == 0)) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const u32x4 q = {v[2 * h].x, v[2 * h].z, v[2 * h + 1].x, v[2 * h + 1].z};
+                const u32x4 q = {v[h].x & ~SG, v[h].y & ~SG, v[h].z & ~SG, v[h].w & ~SG};
                 *(ENG_LDS u32x4*)(xe + off + 8 * h) = q;
             }
             return true;
@@ -282,20 +283,24 @@ __device__ __forceinline__ void eng_rows(const lds_u8* slot, uint32_t row_bytes,
             if (ra < r_end) {                               // (a batch of two of RB == 4: lane 0 only)
                 const float o0 = eng_finish(fin, row0 + ra, lane ? v[2] : v[0]) * fin.post;
                 const float o1 = eng_finish(fin, row0 + ra + 1, lane ? v[3] : v[1]) * fin.post;
-                if (pub) pub[ra >> 1] = pack_h2(o0, o1);    // published by ONE wave, coalesced (eng_publish)
+                if (pub) pub[ra >> 1] = pack_h2(o0, o1);    // published by ONE wave, coalesced (eng_publish_ffn)
                 else eng_store_granule(gran + gidx(row0 + ra), tag, pack_h2(o0, o1));
             }
         }
     }
 }
 
-// The row pairs of a workgroup leave as granules from ONE wave, consecutive lanes on consecutive pairs.  Measured per stage (it costs a
-// barrier): the ffn vector's hand-off (4 096 granules: 3.5 -> 2.6 us) gains from it; K1's and K3's do not (their 1.5 - 2.3 us turned out to
-// be the loader's DMA bursts in front of the polls, not the scattered 8-byte stores) and keep storing from every wave.
-template <class GIDX>
-__device__ __forceinline__ void eng_publish(const ENG_LDS uint32_t* pub, uint32_t nrows, uint32_t row0, unsigned long long* gran, uint32_t tag, GIDX gidx,
-                                            uint32_t lane) {
-    for (uint32_t i = lane; 2 * i < nrows; i += 64) eng_store_granule(gran + gidx(row0 + 2 * i), tag, pub[i]);
+// The rows of a workgroup's share of the ffn vector leave as granules from ONE wave, consecutive lanes on consecutive granules.  Measured
+// per stage (it costs a barrier): the ffn vector's hand-off (3.5 -> 2.6 us) gains from it; K1's and K3's do not (their 1.5 - 2.3 us
+// turned out to be the loader's DMA bursts in front of the polls, not the scattered 8-byte stores) and keep storing from every wave.
+// Two row pairs of `pub` make one four-value granule (wrk_ffn_granule.h); row0 and nrows are multiples of 4 (wrk_v7_engine_create).
+// `g_k`: the vector's first granule.
+__device__ __forceinline__ void eng_publish_ffn(const ENG_LDS uint32_t* pub, uint32_t nrows, uint32_t row0, unsigned long long* g_k, uint32_t nibble,
+                                                uint32_t lane) {
+    for (uint32_t j = lane; 4 * j < nrows; j += 64) {
+        const u32x2 p = *(const ENG_LDS u32x2*)(pub + 2 * j);
+        __hip_atomic_store(g_k + (row0 >> 2) + j, eng_ffn_pack(p.x, p.y, nibble), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // global_store_dwordx2 sc1
+    }
 }
 
 // The statistics of an LN over x (LDS, f16 [K]), in the 256-thread mapping of the launches (same partial sums): the first four waves
@@ -849,10 +854,9 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             uint32_t rb, re;
             eng_wave_rows(k5_rows, NCW, wave, rb, re);
             const EngFin fin{WRK_ACT_SQUARED_RELU, sc_fk, nullptr, 1.0f};
-            const uint32_t gb = S.g_k;
-            eng_rows<QK, R16, XD, 4>(smem + S.lds_slot5, S.rb_d, D, xs, k5_row0, rb, re, fin, pub, A.gran, eng_tag(l, 3), [&](uint32_t r) { return gb + (r >> 1); }, lane);
+            eng_rows<QK, R16, XD, 4>(smem + S.lds_slot5, S.rb_d, D, xs, k5_row0, rb, re, fin, pub, A.gran, 0u, [&](uint32_t) { return 0u; }, lane);     // pairs to `pub` only
             ENG_BAR();
-            if (wave == 0) eng_publish(pub, k5_rows, k5_row0, A.gran, eng_tag(l, 3), [&](uint32_t r) { return gb + (r >> 1); }, lane);
+            if (wave == 0) eng_publish_ffn(pub, k5_rows, k5_row0, A.gran + S.g_k, eng_ffn_nibble(l), lane);
         }
         ENG_STAMP0(l, 9);
         ENG_BAR();                                          // K5 done
@@ -876,7 +880,7 @@ __global__ void __launch_bounds__((NCW + 2) * 64) v7_engine_kernel(const EngArgs
             if (grp < 2 && k6_rows > 0) {
 #pragma unroll
                 for (int ci = 0; ci < XD; ++ci)
-                    if (swept) swept = eng_sweep_half<QK>(A.gran + S.g_k, min(cbase + 256u * ci, nch - 1), grp, eng_tag(l, 3), xe);
+                    if (swept) swept = eng_sweep_half<QK>(A.gran + S.g_k, min(cbase + 256u * ci, nch - 1), grp, eng_ffn_nibble(l), xe);
             }
             if (!swept && lane == 0) { *abort_flag = 1; atomicOr(A.fail, 16u); }
             ENG_STAMP0(l, 10);
@@ -1063,7 +1067,8 @@ int32_t wrk_v7_engine_create(wrk_v7_model* m, wrk_v7_engine** out) {
     }
     if (!placed) { delete e; return no("K1 partition"); }
     S.k3_rpw = std::max(8u, up((D + NWG - 1) / NWG, 8));
-    S.k5_rpw = std::max(8u, up((F + NWG - 1) / NWG, 8));
+    S.k5_rpw = std::max(8u, up((F + NWG - 1) / NWG, 8));                // a multiple of 8, as F is: every workgroup's first row and row count are
+                                                                        // multiples of 4, so the ffn vector always leaves as four-value granules
     S.k6_rpw = std::max(2u, up((D + NWG - 1) / NWG, 2));
     if (S.k6_rpw > 32) { delete e; return no("ffn value rows per workgroup"); }
     // ---- LDS
@@ -1095,7 +1100,7 @@ int32_t wrk_v7_engine_create(wrk_v7_model* m, wrk_v7_engine** out) {
     S.g_k1 = gtake(S.g_aux + H * 96);
     S.g_o = gtake(D / 2);
     S.g_x1 = gtake(D / 2);
-    S.g_k = gtake(F / 2);
+    S.g_k = gtake(F / 4);                                             // four-value granules (wrk_ffn_granule.h)
     S.g_total = g;
     S.ln_eps = 1.0e-5f; S.gn_eps = 64.0e-5f; S.l2_eps = 1.0e-12f;
     S.rescale = d.rescale ? d.rescale : 0xffffffffu;
