@@ -79,7 +79,8 @@ enum {
     WRK_MAT_Q4_K = 12,
     WRK_MAT_Q5_K = 13,
     WRK_MAT_Q6_K = 14,
-    WRK_MAT_INT8 = 100,     /* web-rwkv Int8: u8 + per-128 (min,max) f16                 */
+    WRK_MAT_MXFP4 = 39,     /* OCP microscaling FP4 (ggml block_mxfp4): 32 e2m1 codes + one E8M0 scale */
+    WRK_MAT_INT8 = 100,    /* web-rwkv Int8: u8 + per-128 (min,max) f16                 */
     WRK_MAT_NF4 = 101       /* web-rwkv NF4 : u4 + per-64 absmax f16 + 16-entry table    */
 };
 
@@ -150,13 +151,19 @@ int32_t wrk_matrix_create(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m,
  *   WRK_MAT_NF4 : data = nibbles [K*M/2] (element 2i in the low nibble) ++ absmax f16, one per 64 flattened
  *                 elements, optionally ++ the 16 f32 levels of `q` (default: the NF4 levels matrix.rs:50-67;
  *                 pass Float4Quant::new_student's for SF4); K % 64 == 0
+ * WRK_MAT_MXFP4 (no reference counterpart): data = rows of K / 32 blocks of 17 bytes { u8 e; u8 qs[16] }: element j < 16
+ * of a block is the low nibble of qs[j], element j + 16 its high nibble; code c is the e2m1 value T[c & 7] = {0, .5, 1, 1.5, 2, 3, 4, 6}
+ * with the sign in bit 3, and the weight is T[c] * 2^(e - 127) for every e in 0 .. 255.  K % 32 == 0; WRK_MATRIX_EXACT only
+ * (WRK_MATRIX_ROUND_F16: WRK_E_UNSUPPORTED).
  *
  * Matrix::quant_u8 / quant_nf4 / quant_sf4 (matrix.rs:211-271; quant_mat_int8.wgsl, quant_mat_nf4.wgsl):
  * on-device quantisation of an f16 [K, M] tensor (`f16_data`: M rows of K values).  `levels`: NULL for the
- * NF4 levels, else 16 f32 (SF4); ignored for WRK_MAT_INT8. */
+ * NF4 levels, else 16 f32 (SF4); ignored for WRK_MAT_INT8 and WRK_MAT_MXFP4.
+ * WRK_MAT_MXFP4 follows the OCP MX rule per block of 32 along K: amax == 0 gives e = 0 and codes 0; else e = clamp(floor(log2 amax) - 2
+ * + 127, 0, 254) and each code is the e2m1 value nearest to w / 2^(e - 127), ties to the even code, magnitudes above 6 to 6, sign kept. */
 int32_t wrk_matrix_quantize(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m,
                             const wrk_buf* f16_data, const float* levels, wrk_matrix** out);
-/* read the quantised planes back in wrk_matrix_create's layout (tests; Matrix serialisation): INT8 / NF4 only */
+/* read the quantised planes back in wrk_matrix_create's layout (tests; Matrix serialisation): INT8 / NF4 / MXFP4 only */
 int32_t wrk_matrix_export(wrk_matrix* mat, void* dst, size_t capacity, size_t* bytes);
 /* Loader::load_matrix_discount (loader.rs:923-951): the reference multiplies every weight by 2^-(layer / rescale) at load,
  * which forces the F16 path.  A power-of-two factor commutes with the contraction, so the blocks stay quantised and the

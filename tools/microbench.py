@@ -15,7 +15,7 @@ import ctypes as C  # noqa: E402
 
 import wrk  # noqa: E402
 
-BLOCK = {"Q4_K": (256, 144), "Q5_K": (256, 176), "Q6_K": (256, 210), "Q8_0": (32, 34), "F16": (1, 2), "INT8": (128, 132), "NF4": (64, 34)}
+BLOCK = {"Q4_K": (256, 144), "Q5_K": (256, 176), "Q6_K": (256, 210), "Q8_0": (32, 34), "F16": (1, 2), "INT8": (128, 132), "NF4": (64, 34), "MXFP4": (32, 17)}
 
 
 def run(ctx, kind, k, m, nin=1, reps=200, copies=4, turbo=False):
@@ -32,7 +32,9 @@ def run(ctx, kind, k, m, nin=1, reps=200, copies=4, turbo=False):
             mats.append(wrk.Matrix(ctx, kind, k, m, raw))
             continue
         raw = rng.integers(0, 256, k * m // be * bb, dtype=np.uint8)
-        if kind != "F16":
+        if kind == "MXFP4":     # u8 e; u8 qs[16]: scales around 2^-7
+            raw.reshape(-1, bb)[:, 0] = 120
+        elif kind != "F16":
             raw = raw.reshape(-1, bb)
             off = {"Q4_K": (0, 2), "Q5_K": (0, 2), "Q6_K": (208,), "Q8_0": (0,)}[kind]
             for o in off:
@@ -70,6 +72,15 @@ if __name__ == "__main__":
     shapes = [("Q4_K", 2048, 2048), ("Q4_K", 2048, 8192), ("Q4_K", 8192, 2048), ("Q6_K", 2048, 65536), ("F16", 2048, 65536),
               ("Q4_K", 2560, 2560), ("Q8_0", 4096, 4096), ("Q5_K", 4096, 4096), ("F16", 2048, 96), ("F16", 96, 2048),
               ("INT8", 4096, 4096), ("NF4", 4096, 4096), ("Q5_K", 14336, 4096), ("Q5_K", 4096, 14336)]
+    if sys.argv[1:] == ["mxfp4"]:       # MXFP4 against Q4_K at the 1.5B shapes: decode matvec, the head, a 32 x 128-token prefill GEMM
+        for k, m in ((2048, 2048), (2048, 8192), (8192, 2048), (2048, 65536)):
+            for kind in ("Q4_K", "MXFP4"):
+                run(ctx, kind, k, m)
+        for k, m in ((2048, 2048), (2048, 8192), (8192, 2048)):
+            for kind in ("Q4_K", "MXFP4"):
+                run(ctx, kind, k, m, nin=32 * 128, reps=20, turbo=True)
+        ctx.close()
+        sys.exit(0)
     if len(sys.argv) > 1:
         shapes = [s for s in shapes if s[0] in sys.argv[1:]]
     for kind, k, m in shapes:

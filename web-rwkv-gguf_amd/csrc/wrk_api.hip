@@ -3,6 +3,7 @@
 // constructors do (TensorError -> WRK_E_ARG) and enqueues the kernels of wrk_ops.hip /
 // wrk_matvec.hip on the context's stream.
 #include "wrk_internal.h"
+#include "wrk_mxfp4.h"
 
 #include <cmath>
 #include <memory>
@@ -295,6 +296,12 @@ int32_t wrk_matrix_create(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m, c
             expect = wrk::stored_bytes(kind, k, m);
             if (bytes == expect + 64) { levels = (const float*)((const uint8_t*)data + expect); bytes = expect; }
             break;
+        case WRK_MAT_MXFP4:
+            WRK_ARG(ctx, k % 32 == 0, "MXFP4 needs K %% 32 == 0 (one E8M0 scale per 32 elements)");
+            if (flags != WRK_MATRIX_EXACT)
+                return wrk_fail(ctx, WRK_E_UNSUPPORTED, "MXFP4 matrices are WRK_MATRIX_EXACT only (flags %u)", flags);
+            expect = (size_t)k / 32 * 17 * m;
+            break;
         default: return wrk_fail(ctx, WRK_E_UNSUPPORTED, "matrix kind %u not supported by wrk_matrix_create", kind);
     }
     WRK_ARG(ctx, bytes == expect, "matrix data is %zu bytes, expected %zu for kind %u [%u x %u]", bytes, expect, kind, k, m);
@@ -333,8 +340,9 @@ int32_t wrk_matrix_quantize(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m,
     LOCK(ctx);
     *out = nullptr;
     WRK_ARG(ctx, k > 0 && m > 0, "matrix dims must be positive");
-    if (kind != WRK_MAT_INT8 && kind != WRK_MAT_NF4)
-        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "wrk_matrix_quantize: kind %u is not Int8 / NF4", kind);
+    if (kind != WRK_MAT_INT8 && kind != WRK_MAT_NF4 && kind != WRK_MAT_MXFP4)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "wrk_matrix_quantize: kind %u is not Int8 / NF4 / MXFP4", kind);
+    WRK_ARG(ctx, kind != WRK_MAT_MXFP4 || k % 32 == 0, "MXFP4 matrices need K %% 32 == 0");
     WRK_ARG(ctx, kind != WRK_MAT_INT8 || (k >= 128 && k % 16 == 0 && ((size_t)k * m) % 128 == 0), "Int8 matrices need K %% 16 == 0 and K*M %% 128 == 0");
     WRK_ARG(ctx, kind != WRK_MAT_NF4 || k % 64 == 0, "NF4 matrices need K %% 64 == 0");
     WRK_ARG(ctx, f16_data->bytes >= (size_t)k * m * 2, "source holds %zu bytes, [%u x %u] f16 needs %zu", f16_data->bytes, k, m, (size_t)k * m * 2);
@@ -345,6 +353,7 @@ int32_t wrk_matrix_quantize(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m,
     wrk_matrix* mt = new wrk_matrix{ctx, kind, k, m, 0, (uint8_t*)p, rb, wrk::stored_bytes(kind, k, m), nullptr, 0, {1}};
     hipError_t e = hipMemsetAsync(p, 0, rb * m + 256, ctx->stream);
     if (e == hipSuccess && kind == WRK_MAT_INT8) wrk::quantize_int8(ctx->stream, f16_data->ptr, mt->data, k, m, (uint32_t)rb);
+    if (e == hipSuccess && kind == WRK_MAT_MXFP4) wrk::quantize_mxfp4(ctx->stream, f16_data->ptr, mt->data, k, m, (uint32_t)rb);
     if (e == hipSuccess && kind == WRK_MAT_NF4) {
         const int32_t rc = upload_levels(ctx, mt, levels);
         if (rc != WRK_OK) { hipFree(p); delete mt; return rc; }
@@ -360,10 +369,10 @@ int32_t wrk_matrix_export(wrk_matrix* mat, void* dst, size_t capacity, size_t* b
     if (!mat || !bytes) return WRK_E_ARG;
     wrk_ctx* ctx = mat->ctx;
     LOCK(ctx);
-    if (mat->kind != WRK_MAT_INT8 && mat->kind != WRK_MAT_NF4)
-        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "wrk_matrix_export: only Int8 / NF4 matrices keep their source layout");
+    if (mat->kind != WRK_MAT_INT8 && mat->kind != WRK_MAT_NF4 && mat->kind != WRK_MAT_MXFP4)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "wrk_matrix_export: only Int8 / NF4 / MXFP4 matrices keep their source layout");
     const uint32_t k = mat->k, m = mat->m;
-    const size_t total = wrk::stored_bytes(mat->kind, k, m) + (mat->kind == WRK_MAT_NF4 ? 64 : 0);
+    const size_t total = mat->kind == WRK_MAT_MXFP4 ? (size_t)k / 32 * 17 * m : wrk::stored_bytes(mat->kind, k, m) + (mat->kind == WRK_MAT_NF4 ? 64 : 0);
     *bytes = total;
     if (!dst) return WRK_OK;
     WRK_ARG(ctx, capacity >= total, "export needs %zu bytes, capacity %zu", total, capacity);
@@ -372,6 +381,10 @@ int32_t wrk_matrix_export(wrk_matrix* mat, void* dst, size_t capacity, size_t* b
     WRK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     WRK_HIP(ctx, hipMemcpy(host.data(), mat->data, host.size(), hipMemcpyDeviceToHost));
     uint8_t* o = (uint8_t*)dst;
+    if (mat->kind == WRK_MAT_MXFP4) {       // the stored planes back into ggml's 17-byte blocks
+        for (uint32_t r = 0; r < m; ++r) wrk::mxfp4_row_from_stored(k, host.data() + (size_t)r * mat->row_bytes, o + (size_t)r * (k / 32) * 17);
+        return WRK_OK;
+    }
     const size_t code_row = mat->kind == WRK_MAT_INT8 ? k : k / 2;
     for (uint32_t r = 0; r < m; ++r) memcpy(o + (size_t)r * code_row, host.data() + (size_t)r * mat->row_bytes, code_row);
     if (mat->kind == WRK_MAT_INT8) {       // block b lives (at least) in the row holding its first element

@@ -32,6 +32,7 @@
 #include "wrk_device.h"
 
 #include "wrk_gemm_dev.h"
+#include "wrk_mxfp4.h"
 
 namespace wrk {
 
@@ -1547,8 +1548,12 @@ static int launch_ks(hipStream_t s, const MatJob* jobs, int njobs, const GemmPla
 
 // All jobs multiply the same number of tokens; the jobs of a route run in ONE launch.  Returns -2 when any job is not for the MFMA
 // path: the caller falls back to the matvec kernels.
-int matmul_mfma_multi(hipStream_t s, const MatJob* jobs, int njobs, int) {
+int matmul_mfma_multi(hipStream_t s, const MatJob* jobs, int njobs, int num_cu) {
     if (njobs <= 0 || njobs > GEMM_MAX_JOBS) return -2;
+    // MXFP4 has a GEMM of its own (wrk_mxfp4.hip); a group that mixes it with other kinds goes matrix by matrix
+    int nmx = 0;
+    for (int q = 0; q < njobs; ++q) nmx += jobs[q].kind == WRK_MAT_MXFP4;
+    if (nmx) return nmx == njobs ? mxfp4_gemm(s, jobs, njobs, gemm_min_tokens(), num_cu) : -2;
     const uint32_t n = jobs[0].in.shape[1] * jobs[0].in.shape[2];
     GemmPlan P;
     if (!gemm_plan(jobs, njobs, gemm_switches(n, jobs[0].ks_part && jobs[0].ks_cnt, jobs[0].xsum != nullptr), P)) return -2;

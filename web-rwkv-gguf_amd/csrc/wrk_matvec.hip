@@ -28,6 +28,7 @@
 #include <cstdlib>
 
 #include "wrk_matvec_dev.h"
+#include "wrk_mxfp4.h"
 
 namespace wrk {
 
@@ -47,6 +48,7 @@ size_t repack_row_bytes(uint32_t kind, uint32_t k) {
         // block aligned, else up to k/128 + 2: the reference's own test multiplies a K = 320 Int8 matrix, ops.rs:3786)
         case WRK_MAT_INT8: return (k % 16) ? 0 : align16((size_t)k + (size_t)int8_row_blocks(k) * 4);
         case WRK_MAT_NF4: return (k % 64) ? 0 : align16((size_t)k / 2 + (size_t)(k / 64) * 2);   // nibbles | absmax f16 per 64
+        case WRK_MAT_MXFP4: return mxfp4_row_bytes(k);                                           // codes | E8M0 scale per 32 (wrk_mxfp4.h)
         default: return 0;
     }
 }
@@ -62,6 +64,7 @@ size_t stored_bytes(uint32_t kind, uint32_t k, uint32_t m) {
         case WRK_MAT_Q6_K: return n / 256 * 210;
         case WRK_MAT_INT8: return n + n / 128 * 4;
         case WRK_MAT_NF4: return n / 2 + n / 64 * 2;
+        case WRK_MAT_MXFP4: return mxfp4_row_bytes(k) * m;      // 17 bytes per block + the scale plane's padding to 16 bytes per row
         default: return 0;
     }
 }
@@ -140,6 +143,10 @@ int repack_rows(uint32_t kind, uint32_t k, uint32_t m, const uint8_t* src, uint8
             case WRK_MAT_NF4: {
                 memcpy(d, src + (size_t)r * (k / 2), k / 2);
                 memcpy(d + k / 2, src + (size_t)m * (k / 2) + (size_t)r * (k / 64) * 2, (size_t)(k / 64) * 2);
+                break;
+            }
+            case WRK_MAT_MXFP4: {
+                mxfp4_row_to_stored(k, src + (size_t)r * (k / 32) * 17, d);
                 break;
             }
             default: break;
@@ -785,6 +792,20 @@ uint32_t matvec_num_wg(const MatJob* jobs, int njobs, int num_cu, uint32_t* rows
 // All jobs of one call must have the same number of input vectors (T*B); they run in ONE launch.
 int matvec(hipStream_t s, const MatJob* jobs, int njobs, int num_cu, bool dry_run, bool no_catchall, bool dmv_only) {
     if (njobs <= 0 || njobs > MAX_JOBS) return -1;
+    // MXFP4 has kernels of its own (wrk_mxfp4.hip): a launch that mixes it with other kinds is split, the rest goes on as before
+    int nmx = 0;
+    for (int j = 0; j < njobs; ++j) nmx += jobs[j].kind == WRK_MAT_MXFP4;
+    if (nmx && nmx < njobs) {
+        MatJob g[2][MAX_JOBS];
+        int n[2] = {0, 0};
+        for (int j = 0; j < njobs; ++j) { const int q = jobs[j].kind == WRK_MAT_MXFP4; g[q][n[q]++] = jobs[j]; }
+        // nothing is launched unless both halves can be: a refusal after the first launch would have the caller launch it again
+        int rc = matvec(s, g[1], n[1], num_cu, true);
+        if (rc == 0) rc = matvec(s, g[0], n[0], num_cu, true, no_catchall, dmv_only);
+        if (rc != 0 || dry_run) return rc;
+        rc = matvec(s, g[1], n[1], num_cu);
+        return rc != 0 ? rc : matvec(s, g[0], n[0], num_cu, false, no_catchall, dmv_only);
+    }
     MatvecParams P;
     P.njobs = njobs;
     const uint32_t ntok = jobs[0].in.shape[1] * jobs[0].in.shape[2];
@@ -810,6 +831,7 @@ int matvec(hipStream_t s, const MatJob* jobs, int njobs, int num_cu, bool dry_ru
         d.tok_carry_dst_stride = jobs[j].tok_carry_dst_stride; d.tok_gate_stride = jobs[j].tok_gate_stride;
         wg += (jobs[j].m + d.rows_per_wg - 1) / d.rows_per_wg;
     }
+    if (nmx) return mxfp4_matvec(s, P, wg, ntok, dry_run);
     bool f32in = false;
     for (int j = 0; j < njobs; ++j) f32in = f32in || jobs[j].in.dtype == WRK_F32;
     if (f32in) {    // Bundle::<f32> frames: the f32-input kernel (no fused prologue / carry / arg-max there)

@@ -39,7 +39,7 @@ inline float bf2f(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(
 inline float ld_f16(const uint8_t* p) { uint16_t b; memcpy(&b, p, 2); return h2f(b); }
 
 // ------------------------------------------------------------------ GGML types (gguf.rs:888-1075)
-enum : uint32_t { T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q8_0 = 8, T_Q2K = 10, T_Q3K = 11, T_Q4K = 12, T_Q5K = 13, T_Q6K = 14, T_BF16 = 30 };
+enum : uint32_t { T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q8_0 = 8, T_Q2K = 10, T_Q3K = 11, T_Q4K = 12, T_Q5K = 13, T_Q6K = 14, T_BF16 = 30, T_MXFP4 = 39 };
 size_t type_size(uint32_t t) {
     switch (t) {
         case T_F32: return 4; case T_F16: return 2; case T_BF16: return 2;
@@ -47,12 +47,13 @@ size_t type_size(uint32_t t) {
         case T_Q8_0: return 34; case 9: return 36;
         case 10: return 84; case 11: return 110; case T_Q4K: return 144; case T_Q5K: return 176; case T_Q6K: return 210; case 15: return 292;
         case 24: return 1; case 25: return 2; case 26: return 4; case 27: return 8; case 28: return 8;
+        case T_MXFP4: return 17;
         default: return 0;
     }
 }
 size_t block_size(uint32_t t) {
     switch (t) {
-        case T_Q4_0: case 3: case 6: case 7: case T_Q8_0: case 9: return 32;
+        case T_Q4_0: case 3: case 6: case 7: case T_Q8_0: case 9: case T_MXFP4: return 32;
         case 10: case 11: case T_Q4K: case T_Q5K: case T_Q6K: case 15: return 256;
         default: return 1;
     }
@@ -73,6 +74,21 @@ void dequant_q8_0(const uint8_t* d, size_t n, uint16_t* out) {                  
         const uint8_t* blk = d + b * 34;
         const float scale = ld_f16(blk);
         for (int i = 0; i < 32; ++i) out[b * 32 + i] = f2h((float)(int8_t)blk[2 + i] * scale);
+    }
+}
+
+// ggml block_mxfp4 { u8 e; u8 qs[16] }: element j < 16 the low nibble of qs[j], element j + 16 the high one; w = e2m1(code) * 2^(e - 127)
+void dequant_mxfp4(const uint8_t* d, size_t n, uint16_t* out) {
+    static const double E2M1[8] = {0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0};
+    const long long nb = (long long)(n / 32);
+#pragma omp parallel for schedule(static)
+    for (long long b = 0; b < nb; ++b) {
+        const uint8_t* blk = d + b * 17;
+        for (int i = 0; i < 32; ++i) {
+            const uint32_t c = (blk[1 + (i & 15)] >> (i < 16 ? 0 : 4)) & 15u;
+            const double w = std::ldexp(E2M1[c & 7], (int)blk[0] - 127);      // exact: two significant bits; 2^128 overflows below
+            out[b * 32 + i] = f2h((float)((c & 8) ? -w : w));
+        }
     }
 }
 
@@ -579,6 +595,7 @@ struct wrk_gguf {
             case T_BF16: { const uint16_t* p = (const uint16_t*)d + skip; for (size_t i = 0; i < n; ++i) out[i] = f2h(bf2f(p[i])); break; }
             case T_Q8_0: dequant_q8_0(d, n, out.data()); break;
             case T_Q4_0: dequant_q4_0(d, n, out.data()); break;
+            case T_MXFP4: dequant_mxfp4(d, n, out.data()); break;
             case T_Q2K: dequant_q2_k(d, n, out.data()); break;
             case T_Q3K: dequant_q3_k(d, n, out.data()); break;
             case T_Q4K: dequant_q4_k(d, n, out.data()); break;
@@ -1039,10 +1056,12 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
         const TensorInfo* ti = g->info(name);
         wrk_matrix* mt = nullptr;
         int32_t r;
-        const uint32_t quant = big ? layer_quant : (uint32_t)WRK_QUANT_NONE;
+        // MXFP4 blocks in the file run as they are, whatever the quant map says (the blocks are exact in f16: no ROUND_F16 variant)
+        const bool mx_direct = big && weights != WRK_WEIGHTS_REFERENCE && ti->type == T_MXFP4 && k % 32 == 0;
+        const uint32_t quant = big && !mx_direct ? layer_quant : (uint32_t)WRK_QUANT_NONE;
         if (quant != WRK_QUANT_NONE) {
             const size_t n = (size_t)k * m;
-            const uint32_t kind = quant == WRK_QUANT_INT8 ? WRK_MAT_INT8 : WRK_MAT_NF4;
+            const uint32_t kind = quant == WRK_QUANT_INT8 ? WRK_MAT_INT8 : (quant == WRK_QUANT_NF4 ? WRK_MAT_NF4 : WRK_MAT_MXFP4);
             // try_load_matrix_direct's live arms (loader.rs:808-820, 901-918); load_matrix_discount never takes them
             if (discount == 1.0f && quant == WRK_QUANT_INT8 && ti->type == T_Q8_0 && k % 128 == 0) {
                 std::vector<uint8_t> blob;
@@ -1076,9 +1095,9 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
         const bool direct = big && weights != WRK_WEIGHTS_REFERENCE &&
                             (ti->type == T_Q4K || ti->type == T_Q5K || ti->type == T_Q6K || ti->type == T_Q8_0) &&
                             (ti->type == T_Q8_0 ? k % 32 == 0 : k % 256 == 0);
-        if (direct) {
+        if (direct || mx_direct) {
             r = wrk_matrix_create(ctx, ti->type, k, m, g->tensor_data(*ti), ti->data_size(),
-                                  weights == WRK_WEIGHTS_INLINE_F16 ? WRK_MATRIX_ROUND_F16 : WRK_MATRIX_EXACT, &mt);
+                                  weights == WRK_WEIGHTS_INLINE_F16 && !mx_direct ? WRK_MATRIX_ROUND_F16 : WRK_MATRIX_EXACT, &mt);
             if (r == WRK_OK && discount != 1.0f) r = wrk_matrix_set_scale(mt, discount);
         } else {
             std::vector<uint16_t> v;
@@ -1114,7 +1133,7 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
             wrk_v6_layer_desc& L = rt->layers6[l];
             const float discount = 1.0f / (float)(1u << std::min<uint32_t>(l / rescale6, 30));
             layer_quant = opt && opt->quant && l < opt->num_quant ? opt->quant[l] : (uint32_t)WRK_QUANT_NONE;
-            if (layer_quant > WRK_QUANT_NF4) return fail(WRK_E_ARG, "quant[%u] = %u is not a WRK_QUANT_* value", l, layer_quant);
+            if (layer_quant > WRK_QUANT_MXFP4) return fail(WRK_E_ARG, "quant[%u] = %u is not a WRK_QUANT_* value", l, layer_quant);
             const std::string blk = "blocks." + std::to_string(l), att = blk + ".att", ffn = blk + ".ffn";
             wrk_buf* vb;
             wrk_matrix* m;
@@ -1203,7 +1222,7 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
         wrk_v7_layer_desc& L = rt->layers[l];
         const float discount = 1.0f / (float)(1u << std::min<uint32_t>(l / rescale, 30));      // 2^-(layer / rescale), v7.rs:1090
         layer_quant = opt && opt->quant && l < opt->num_quant ? opt->quant[l] : (uint32_t)WRK_QUANT_NONE;   // v7.rs:1089
-        if (layer_quant > WRK_QUANT_NF4) return fail(WRK_E_ARG, "quant[%u] = %u is not a WRK_QUANT_* value", l, layer_quant);
+        if (layer_quant > WRK_QUANT_MXFP4) return fail(WRK_E_ARG, "quant[%u] = %u is not a WRK_QUANT_* value", l, layer_quant);
         const std::string blk = "blocks." + std::to_string(l), att = blk + ".att", ffn = blk + ".ffn";
         wrk_buf* b;
         wrk_matrix* m;

@@ -30,11 +30,12 @@ OK, E_ARG, E_OOM, E_HIP, E_UNSUPPORTED = 0, 1, 2, 3, 4
 STATUS = {0: "WRK_OK", 1: "WRK_E_ARG", 2: "WRK_E_OOM", 3: "WRK_E_HIP", 4: "WRK_E_UNSUPPORTED"}
 F16, F32, U8, U32 = 0, 1, 2, 3
 ACT = {"none": 0, "squared_relu": 1, "tanh": 2, "stable_exp": 3, "opposite_exp": 4, "softplus": 5, "sigmoid": 6, "silu": 7}
-MAT = {"F32": 0, "F16": 1, "Q8_0": 8, "Q4_K": 12, "Q5_K": 13, "Q6_K": 14, "INT8": 100, "NF4": 101}
+MAT = {"F32": 0, "F16": 1, "Q8_0": 8, "Q4_K": 12, "Q5_K": 13, "Q6_K": 14, "MXFP4": 39, "INT8": 100, "NF4": 101}
 MATRIX_EXACT, MATRIX_ROUND_F16 = 0, 1
 WEIGHTS_INLINE, WEIGHTS_INLINE_F16, WEIGHTS_REFERENCE = 0, 1, 2
 RNN_NONE, RNN_LAST, RNN_FULL = -1, 0, 1
-QUANT_NONE, QUANT_INT8, QUANT_NF4 = 0, 1, 2
+QUANT_NONE, QUANT_INT8, QUANT_NF4, QUANT_MXFP4 = 0, 1, 2, 3
+QUANT = {"none": QUANT_NONE, "int8": QUANT_INT8, "nf4": QUANT_NF4, "mxfp4": QUANT_MXFP4}     # the spellings a `quant=` map may use
 
 if not (os.path.exists(LIB_HIP) and os.path.exists(LIB_RT)):
     raise ImportError(
@@ -1505,8 +1506,13 @@ class Matrix:
         """`Matrix::quant_sf4` (matrix.rs:251-271) with the caller's 16 levels (`Float4Quant::new_student`)."""
         return cls._quant("NF4", matrix, k, m, levels)
 
+    @classmethod
+    def mxfp4(cls, matrix: "Buffer", k: int, m: int) -> "Matrix":
+        """f16 [K, M] buffer -> MXFP4 matrix (32 e2m1 codes under one E8M0 scale), quantised on the device by the OCP MX rule."""
+        return cls._quant("MXFP4", matrix, k, m)
+
     def export(self) -> np.ndarray:
-        """Int8 / NF4 planes in `wrk_matrix_create`'s layout (codes ++ side table [++ levels])."""
+        """Int8 / NF4 planes in `wrk_matrix_create`'s layout (codes ++ side table [++ levels]); MXFP4: the 17-byte block stream."""
         n = C.c_size_t()
         self.ctx.check(hip.wrk_matrix_export(self.h, None, 0, C.byref(n)))
         out = np.empty(n.value, np.uint8)
@@ -1805,12 +1811,12 @@ class Runtime:
 
     def __init__(self, ctx: Context, reader: GgufReader, num_batch: int = 1, weights: int = WEIGHTS_INLINE, rescale: int = 0,
                  quant: Optional[Dict[int, int]] = None):
-        """`quant`: `ModelBuilder::quant`'s layer -> QUANT_* map."""
+        """`quant`: `ModelBuilder::quant`'s layer -> QUANT_* map; a value may also be spelled "int8", "nf4" or "mxfp4"."""
         opt = BuildOptions(rescale, weights, None, 0)
         if quant:
             q = np.zeros(max(quant) + 1, np.uint8)
             for l, v in quant.items():
-                q[l] = v
+                q[l] = QUANT[v] if isinstance(v, str) else v
             opt.quant, opt.num_quant = q.ctypes.data_as(C.POINTER(C.c_uint8)), q.size
         h = _P()
         _host_check(rt.wrk_runtime_create(ctx.h, reader.h, C.byref(opt), num_batch, C.byref(h)))
