@@ -158,12 +158,21 @@ int32_t wrk_matrix_create(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m,
  *
  * Matrix::quant_u8 / quant_nf4 / quant_sf4 (matrix.rs:211-271; quant_mat_int8.wgsl, quant_mat_nf4.wgsl):
  * on-device quantisation of an f16 [K, M] tensor (`f16_data`: M rows of K values).  `levels`: NULL for the
- * NF4 levels, else 16 f32 (SF4); ignored for WRK_MAT_INT8 and WRK_MAT_MXFP4.
+ * NF4 levels, else 16 f32 (SF4); ignored for WRK_MAT_INT8 and WRK_MAT_MXFP4, WRK_E_ARG for WRK_MAT_Q4_K.
  * WRK_MAT_MXFP4 follows the OCP MX rule per block of 32 along K: amax == 0 gives e = 0 and codes 0; else e = clamp(floor(log2 amax) - 2
- * + 127, 0, 254) and each code is the e2m1 value nearest to w / 2^(e - 127), ties to the even code, magnitudes above 6 to 6, sign kept. */
+ * + 127, 0, 254) and each code is the e2m1 value nearest to w / 2^(e - 127), ties to the even code, magnitudes above 6 to 6, sign kept.
+ * WRK_MAT_Q4_K (no reference counterpart) follows ggml's quantize_row_q4_K_ref in f32; K % 256 == 0, `levels` must be NULL.
+ * Per sub-block of 32: weights w = sqrt(sum x^2 / 32) + |x|, min = min(x, 0), max; max == min gives (scale, offset) = (0, -min); else the
+ * grid iscale = 15 / (max - min), L = clamp(rint(iscale (x - min)), 0, 15), (scale, min) = (1 / iscale, min) is the start, and for is = 0
+ * .. 20 the grid iscale = (14 + 0.1 is) / (max - min) with the weighted least-squares (scale, min) of x on its L (min > 0: min = 0, scale
+ * = sum wLx / sum wL^2) replaces it when D = sum w sum wL^2 - (sum wL)^2 > 0 and its weighted squared error is strictly smaller.  Per
+ * super-block d = f16(max scale / 63), dmin = f16(max -min / 63), sc = min(63, rint(63 / max scale * scale)) (0 for a maximum of 0), m
+ * likewise, and every code is clamp(rint((x + f32(dmin) m) / (f32(d) sc)), 0, 15) from the header as stored, 0 where f32(d) sc == 0.  The
+ * result is an ordinary WRK_MATRIX_EXACT Q4_K matrix. */
 int32_t wrk_matrix_quantize(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m,
                             const wrk_buf* f16_data, const float* levels, wrk_matrix** out);
-/* read the quantised planes back in wrk_matrix_create's layout (tests; Matrix serialisation): INT8 / NF4 / MXFP4 only */
+/* read the quantised planes back in wrk_matrix_create's layout (tests; Matrix serialisation): INT8 / NF4 / MXFP4, and Q4_K as ggml's
+ * 144-byte blocks, whether the matrix came from wrk_matrix_quantize or wrk_matrix_create */
 int32_t wrk_matrix_export(wrk_matrix* mat, void* dst, size_t capacity, size_t* bytes);
 /* Loader::load_matrix_discount (loader.rs:923-951): the reference multiplies every weight by 2^-(layer / rescale) at load,
  * which forces the F16 path.  A power-of-two factor commutes with the contraction, so the blocks stay quantised and the

@@ -102,7 +102,8 @@ enum {
 
 enum { WRK_QUANT_NONE = 0, WRK_QUANT_INT8 = 1, WRK_QUANT_NF4 = 2,     /* Quant (runtime/model.rs); SF4 needs the caller's
                                                                           Student-t levels: wrk_matrix_quantize only */
-       WRK_QUANT_MXFP4 = 3 };                                          /* OCP MXFP4 (WRK_MAT_MXFP4), quantised on the device at load */
+       WRK_QUANT_MXFP4 = 3,                                            /* OCP MXFP4 (WRK_MAT_MXFP4), quantised on the device at load */
+       WRK_QUANT_Q4_K = 4 };                                           /* ggml Q4_K (WRK_MAT_Q4_K) by ggml's scale search, on the device at load */
 
 typedef struct wrk_build_options {
     uint32_t rescale;             /* ModelBuilder::rescale, 0 = default 1024 (v7.rs:50)  */
@@ -112,7 +113,8 @@ typedef struct wrk_build_options {
      * v6.rs:1110-1132) exactly as Loader::load_matrix / load_matrix_discount do (loader.rs:756-951):
      * Q8_0 + Int8 and Q4_0 + NF4 tensors loaded without discount are repacked on the host (gguf.rs:429-627),
      * everything else goes f16 -> (discount) -> on-device quantisation (MXFP4 always; a tensor of GGUF type 39 in the file is MXFP4
-     * as it is, whatever the map says). */
+     * as it is, whatever the map says).  Q4_K: Q4_K / Q5_K / Q6_K tensors of the file stay as they are and a matrix with K % 256 != 0 stays
+     * F16; every other one (F32 / F16 / BF16 / Q8_0 ...) goes f16 -> on-device quantisation and carries the discount as wrk_matrix_set_scale. */
     const uint8_t* quant;
     uint32_t num_quant;
 } wrk_build_options;

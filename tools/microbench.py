@@ -81,6 +81,22 @@ if __name__ == "__main__":
                 run(ctx, kind, k, m, nin=32 * 128, reps=20, turbo=True)
         ctx.close()
         sys.exit(0)
+    if sys.argv[1:] == ["quant"]:       # the load-time quantisers at the 1.5B shapes: one wrk_matrix_quantize call (allocation, clear, kernel) to its sync
+        for k, m in ((2048, 2048), (2048, 8192), (8192, 2048)):
+            w = (np.random.default_rng(0).standard_normal((m, k)) / np.sqrt(k)).astype(np.float16)
+            buf = wrk.Buffer(ctx, w.nbytes, w)
+            for name, make in (("Q4_K", wrk.Matrix.q4_k), ("MXFP4", wrk.Matrix.mxfp4)):
+                best = 1e9
+                for _ in range(10):
+                    ctx.sync()
+                    t0 = time.perf_counter()
+                    mt = make(buf, k, m)
+                    ctx.sync()
+                    best = min(best, time.perf_counter() - t0)
+                    del mt
+                print(f"quantise {name:5s} K={k:5d} M={m:6d}: {best * 1e6:9.1f} us  {k * m / best / 1e9:7.2f} G weights/s", flush=True)
+        ctx.close()
+        sys.exit(0)
     if len(sys.argv) > 1:
         shapes = [s for s in shapes if s[0] in sys.argv[1:]]
     for kind, k, m in shapes:

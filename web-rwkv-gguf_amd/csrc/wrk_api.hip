@@ -4,6 +4,7 @@
 // wrk_matvec.hip on the context's stream.
 #include "wrk_internal.h"
 #include "wrk_mxfp4.h"
+#include "wrk_q4k_quant.h"
 
 #include <cmath>
 #include <memory>
@@ -340,9 +341,11 @@ int32_t wrk_matrix_quantize(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m,
     LOCK(ctx);
     *out = nullptr;
     WRK_ARG(ctx, k > 0 && m > 0, "matrix dims must be positive");
-    if (kind != WRK_MAT_INT8 && kind != WRK_MAT_NF4 && kind != WRK_MAT_MXFP4)
-        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "wrk_matrix_quantize: kind %u is not Int8 / NF4 / MXFP4", kind);
+    if (kind != WRK_MAT_INT8 && kind != WRK_MAT_NF4 && kind != WRK_MAT_MXFP4 && kind != WRK_MAT_Q4_K)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "wrk_matrix_quantize: kind %u is not Int8 / NF4 / MXFP4 / Q4_K", kind);
     WRK_ARG(ctx, kind != WRK_MAT_MXFP4 || k % 32 == 0, "MXFP4 matrices need K %% 32 == 0");
+    WRK_ARG(ctx, kind != WRK_MAT_Q4_K || k % 256 == 0, "Q4_K matrices need K %% 256 == 0");
+    WRK_ARG(ctx, kind != WRK_MAT_Q4_K || !levels, "Q4_K has no level table");
     WRK_ARG(ctx, kind != WRK_MAT_INT8 || (k >= 128 && k % 16 == 0 && ((size_t)k * m) % 128 == 0), "Int8 matrices need K %% 16 == 0 and K*M %% 128 == 0");
     WRK_ARG(ctx, kind != WRK_MAT_NF4 || k % 64 == 0, "NF4 matrices need K %% 64 == 0");
     WRK_ARG(ctx, f16_data->bytes >= (size_t)k * m * 2, "source holds %zu bytes, [%u x %u] f16 needs %zu", f16_data->bytes, k, m, (size_t)k * m * 2);
@@ -354,6 +357,7 @@ int32_t wrk_matrix_quantize(wrk_ctx* ctx, uint32_t kind, uint32_t k, uint32_t m,
     hipError_t e = hipMemsetAsync(p, 0, rb * m + 256, ctx->stream);
     if (e == hipSuccess && kind == WRK_MAT_INT8) wrk::quantize_int8(ctx->stream, f16_data->ptr, mt->data, k, m, (uint32_t)rb);
     if (e == hipSuccess && kind == WRK_MAT_MXFP4) wrk::quantize_mxfp4(ctx->stream, f16_data->ptr, mt->data, k, m, (uint32_t)rb);
+    if (e == hipSuccess && kind == WRK_MAT_Q4_K) wrk::quantize_q4_k(ctx->stream, f16_data->ptr, mt->data, k, m, (uint32_t)rb);
     if (e == hipSuccess && kind == WRK_MAT_NF4) {
         const int32_t rc = upload_levels(ctx, mt, levels);
         if (rc != WRK_OK) { hipFree(p); delete mt; return rc; }
@@ -369,8 +373,8 @@ int32_t wrk_matrix_export(wrk_matrix* mat, void* dst, size_t capacity, size_t* b
     if (!mat || !bytes) return WRK_E_ARG;
     wrk_ctx* ctx = mat->ctx;
     LOCK(ctx);
-    if (mat->kind != WRK_MAT_INT8 && mat->kind != WRK_MAT_NF4 && mat->kind != WRK_MAT_MXFP4)
-        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "wrk_matrix_export: only Int8 / NF4 / MXFP4 matrices keep their source layout");
+    if (mat->kind != WRK_MAT_INT8 && mat->kind != WRK_MAT_NF4 && mat->kind != WRK_MAT_MXFP4 && mat->kind != WRK_MAT_Q4_K)
+        return wrk_fail(ctx, WRK_E_UNSUPPORTED, "wrk_matrix_export: only Int8 / NF4 / MXFP4 / Q4_K matrices go back to their source layout");
     const uint32_t k = mat->k, m = mat->m;
     const size_t total = mat->kind == WRK_MAT_MXFP4 ? (size_t)k / 32 * 17 * m : wrk::stored_bytes(mat->kind, k, m) + (mat->kind == WRK_MAT_NF4 ? 64 : 0);
     *bytes = total;
@@ -383,6 +387,10 @@ int32_t wrk_matrix_export(wrk_matrix* mat, void* dst, size_t capacity, size_t* b
     uint8_t* o = (uint8_t*)dst;
     if (mat->kind == WRK_MAT_MXFP4) {       // the stored planes back into ggml's 17-byte blocks
         for (uint32_t r = 0; r < m; ++r) wrk::mxfp4_row_from_stored(k, host.data() + (size_t)r * mat->row_bytes, o + (size_t)r * (k / 32) * 17);
+        return WRK_OK;
+    }
+    if (mat->kind == WRK_MAT_Q4_K) {        // the three planes back into ggml's 144-byte blocks, whoever made the matrix (quantiser or create)
+        for (uint32_t r = 0; r < m; ++r) wrk::q4k_row_from_stored(k, host.data() + (size_t)r * mat->row_bytes, o + (size_t)r * (k / 256) * 144);
         return WRK_OK;
     }
     const size_t code_row = mat->kind == WRK_MAT_INT8 ? k : k / 2;

@@ -1058,10 +1058,16 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
         int32_t r;
         // MXFP4 blocks in the file run as they are, whatever the quant map says (the blocks are exact in f16: no ROUND_F16 variant)
         const bool mx_direct = big && weights != WRK_WEIGHTS_REFERENCE && ti->type == T_MXFP4 && k % 32 == 0;
-        const uint32_t quant = big && !mx_direct ? layer_quant : (uint32_t)WRK_QUANT_NONE;
+        // a Q4_K layer: K-quant blocks in the file run as they are, and a matrix whose K is no multiple of 256 stays F16, as the file loader
+        // would leave it
+        const bool q4k_skip = layer_quant == WRK_QUANT_Q4_K && (ti->type == T_Q4K || ti->type == T_Q5K || ti->type == T_Q6K || k % 256 != 0);
+        const uint32_t quant = big && !mx_direct && !q4k_skip ? layer_quant : (uint32_t)WRK_QUANT_NONE;
         if (quant != WRK_QUANT_NONE) {
             const size_t n = (size_t)k * m;
-            const uint32_t kind = quant == WRK_QUANT_INT8 ? WRK_MAT_INT8 : (quant == WRK_QUANT_NF4 ? WRK_MAT_NF4 : WRK_MAT_MXFP4);
+            const uint32_t kind = quant == WRK_QUANT_INT8 ? WRK_MAT_INT8 : (quant == WRK_QUANT_NF4 ? WRK_MAT_NF4 :
+                                  (quant == WRK_QUANT_MXFP4 ? WRK_MAT_MXFP4 : WRK_MAT_Q4_K));
+            // Q4_K keeps the power-of-two layer discount out of the blocks, as the K-quants of a file do: it rides on the dot product
+            const bool scale_after = quant == WRK_QUANT_Q4_K && discount != 1.0f;
             // try_load_matrix_direct's live arms (loader.rs:808-820, 901-918); load_matrix_discount never takes them
             if (discount == 1.0f && quant == WRK_QUANT_INT8 && ti->type == T_Q8_0 && k % 128 == 0) {
                 std::vector<uint8_t> blob;
@@ -1076,7 +1082,7 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
                 std::vector<uint16_t> v;
                 r = g->tensor_f16(name, v);
                 if (r != WRK_OK) return r;
-                if (discount != 1.0f)
+                if (discount != 1.0f && !scale_after)
                     for (auto& h : v) h = f2h(discount * h2f(h));
                 wrk_buf* src = nullptr;
                 r = wrk_buf_create(ctx, v.size() * 2, v.data(), &src);
@@ -1084,6 +1090,7 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
                 r = wrk_matrix_quantize(ctx, kind, k, m, src, nullptr, &mt);
                 wrk_ctx_sync(ctx);
                 wrk_buf_release(src);
+                if (r == WRK_OK && scale_after) r = wrk_matrix_set_scale(mt, discount);
             }
             if (r != WRK_OK) return fail(r, "quantise %s: %s", name.c_str(), wrk_last_error(ctx));
             rt->mats.push_back(mt);
@@ -1133,7 +1140,7 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
             wrk_v6_layer_desc& L = rt->layers6[l];
             const float discount = 1.0f / (float)(1u << std::min<uint32_t>(l / rescale6, 30));
             layer_quant = opt && opt->quant && l < opt->num_quant ? opt->quant[l] : (uint32_t)WRK_QUANT_NONE;
-            if (layer_quant > WRK_QUANT_MXFP4) return fail(WRK_E_ARG, "quant[%u] = %u is not a WRK_QUANT_* value", l, layer_quant);
+            if (layer_quant > WRK_QUANT_Q4_K) return fail(WRK_E_ARG, "quant[%u] = %u is not a WRK_QUANT_* value", l, layer_quant);
             const std::string blk = "blocks." + std::to_string(l), att = blk + ".att", ffn = blk + ".ffn";
             wrk_buf* vb;
             wrk_matrix* m;
@@ -1222,7 +1229,7 @@ int32_t wrk_runtime_create(wrk_ctx* ctx, const wrk_gguf* g, const wrk_build_opti
         wrk_v7_layer_desc& L = rt->layers[l];
         const float discount = 1.0f / (float)(1u << std::min<uint32_t>(l / rescale, 30));      // 2^-(layer / rescale), v7.rs:1090
         layer_quant = opt && opt->quant && l < opt->num_quant ? opt->quant[l] : (uint32_t)WRK_QUANT_NONE;   // v7.rs:1089
-        if (layer_quant > WRK_QUANT_MXFP4) return fail(WRK_E_ARG, "quant[%u] = %u is not a WRK_QUANT_* value", l, layer_quant);
+        if (layer_quant > WRK_QUANT_Q4_K) return fail(WRK_E_ARG, "quant[%u] = %u is not a WRK_QUANT_* value", l, layer_quant);
         const std::string blk = "blocks." + std::to_string(l), att = blk + ".att", ffn = blk + ".ffn";
         wrk_buf* b;
         wrk_matrix* m;

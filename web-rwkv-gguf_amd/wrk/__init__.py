@@ -34,8 +34,8 @@ MAT = {"F32": 0, "F16": 1, "Q8_0": 8, "Q4_K": 12, "Q5_K": 13, "Q6_K": 14, "MXFP4
 MATRIX_EXACT, MATRIX_ROUND_F16 = 0, 1
 WEIGHTS_INLINE, WEIGHTS_INLINE_F16, WEIGHTS_REFERENCE = 0, 1, 2
 RNN_NONE, RNN_LAST, RNN_FULL = -1, 0, 1
-QUANT_NONE, QUANT_INT8, QUANT_NF4, QUANT_MXFP4 = 0, 1, 2, 3
-QUANT = {"none": QUANT_NONE, "int8": QUANT_INT8, "nf4": QUANT_NF4, "mxfp4": QUANT_MXFP4}     # the spellings a `quant=` map may use
+QUANT_NONE, QUANT_INT8, QUANT_NF4, QUANT_MXFP4, QUANT_Q4_K = 0, 1, 2, 3, 4
+QUANT = {"none": QUANT_NONE, "int8": QUANT_INT8, "nf4": QUANT_NF4, "mxfp4": QUANT_MXFP4, "q4_k": QUANT_Q4_K}     # the spellings a `quant=` map may use
 
 if not (os.path.exists(LIB_HIP) and os.path.exists(LIB_RT)):
     raise ImportError(
@@ -1511,8 +1511,14 @@ class Matrix:
         """f16 [K, M] buffer -> MXFP4 matrix (32 e2m1 codes under one E8M0 scale), quantised on the device by the OCP MX rule."""
         return cls._quant("MXFP4", matrix, k, m)
 
+    @classmethod
+    def q4_k(cls, matrix: "Buffer", k: int, m: int) -> "Matrix":
+        """f16 [K, M] buffer -> Q4_K matrix, quantised on the device by ggml's scale search (K % 256 == 0); an ordinary exact Q4_K matrix."""
+        return cls._quant("Q4_K", matrix, k, m)
+
     def export(self) -> np.ndarray:
-        """Int8 / NF4 planes in `wrk_matrix_create`'s layout (codes ++ side table [++ levels]); MXFP4: the 17-byte block stream."""
+        """Int8 / NF4 planes in `wrk_matrix_create`'s layout (codes ++ side table [++ levels]); MXFP4: the 17-byte block stream; Q4_K:
+        ggml's 144-byte block stream."""
         n = C.c_size_t()
         self.ctx.check(hip.wrk_matrix_export(self.h, None, 0, C.byref(n)))
         out = np.empty(n.value, np.uint8)
@@ -1811,7 +1817,7 @@ class Runtime:
 
     def __init__(self, ctx: Context, reader: GgufReader, num_batch: int = 1, weights: int = WEIGHTS_INLINE, rescale: int = 0,
                  quant: Optional[Dict[int, int]] = None):
-        """`quant`: `ModelBuilder::quant`'s layer -> QUANT_* map; a value may also be spelled "int8", "nf4" or "mxfp4"."""
+        """`quant`: `ModelBuilder::quant`'s layer -> QUANT_* map; a value may also be spelled "int8", "nf4", "mxfp4" or "q4_k"."""
         opt = BuildOptions(rescale, weights, None, 0)
         if quant:
             q = np.zeros(max(quant) + 1, np.uint8)
